@@ -8,10 +8,12 @@ A "step" (--steps K) is one full pass of the hot path over one batch: pd_ddim_sa
 input already resident in HBM (torch CUDA tensors handed over as device pointers).  Weights are
 random-initialised on the device (no checkpoint exists offline), inputs synthetic.
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
         python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 `python bench.py --gpus N` without a torchrun environment launches that second line itself, as a CHILD process and
 before anything touches the GPU, and relays the child's JSON line.  Prints ONE JSON line on rank 0.
+--dump-outputs DIR writes what the last timed step returned (the final latents of every image, float32) as DIR/latents.npy;
+the weights and inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -69,7 +71,7 @@ def cpu_baseline(ddim_steps: int):
 
 def parity_leg(E, W, precision, stream_f32, device):
     """The second half of BASELINE's metric: per-step latent error against the reference's own CPU trajectories
-    (tests/golden/, made by tests/golden/make_golden.py from /root/reference), computed in this run with the seeded
+    (tests/golden/, made by tests/golden/make_golden.py from the reference project), computed in this run with the seeded
     synthetic weights those fixtures were made with.  `per_step_relerr`: 50-step schedule (the metric's schedule) --
     the engine gets the reference's x_i and must reproduce x_{i+1}; max over the sampled steps of max|dx| / max|x_ref|."""
     import numpy as np
@@ -166,10 +168,36 @@ def sd3_leg(precision, device):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(d: str, **arrays) -> None:
+    """Write each array as d/<name>.npy in float32.  An array over its share of DUMP_MAX_BYTES is written as a fixed sample
+    instead: the elements at seeded random flat indices, in index order (d/<name>_index.npy holds the indices, float64).
+    A directory this creates gets a .gitignore of its own, so that a dump inside a checkout leaves `git status` clean."""
+    import numpy as np
+    cap = DUMP_MAX_BYTES // max(len(arrays), 1) // 12    # elements per array: float32 values + float64 indices
+    if not os.path.isdir(d):
+        os.makedirs(d)
+        with open(os.path.join(d, ".gitignore"), "w") as f:
+            f.write("*\n")
+    for name, a in arrays.items():
+        if hasattr(a, "detach"):
+            a = a.detach().float().cpu().numpy()
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))
+            np.save(os.path.join(d, name + "_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2, help="timed passes (each = one 50-step sampling of the batch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed passes, write the latents the last one returned to DIR/latents.npy (float32)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--batch", type=int, default=8, help="images per GPU")
     ap.add_argument("--size", type=int, default=512)
@@ -191,6 +219,8 @@ def main():
                     help="serialise ControlNet and UNet on one stream in every pass (used for the committed rocprof summary, so\n"
                          "that per-kernel durations are not stretched by the concurrent kernel of the other stream)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(spawn_ranks(args.gpus))
@@ -281,6 +311,8 @@ def main():
         rank_ms = [1e3 * float(t.item()) / args.steps for t in tall]
         dt = max(float(t.item()) for t in tall)
     assert torch.isfinite(out).all(), "non-finite latents"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, latents=out)
     images = world * B * args.steps
     value = images / dt
 

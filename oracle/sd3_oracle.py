@@ -1,5 +1,5 @@
 """CPU restatement (NumPy fp32) of the SD3 hot path of the reference: SD3PromptDiffusionModel.forward
-(/root/reference/promptdiffusioncontrolnet_sd3.py:362-483) + the MMDiT it steers + the flow-matching Euler loop of
+(the reference's promptdiffusioncontrolnet_sd3.py:362-483) + the MMDiT it steers + the flow-matching Euler loop of
 promptdiffusioncontrolnetpipeline_sd3.py:1192-1245.  TEST INFRASTRUCTURE ONLY.
 
 PARITY UNPINNED.  The block arithmetic (SD3Transformer2DModel, JointTransformerBlock, AdaLayerNormZero / Continuous,

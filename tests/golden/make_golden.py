@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generate the golden fixtures under tests/golden/ from the REFERENCE itself.
 
-Runs only in the build container (needs /root/reference).  It imports the reference's
+Runs only where a checkout of the reference project exists (--reference DIR).  It imports the reference's
 unmodified (L)-path modules -- cldm.cldm.{ControlNet, ControlledUnetModel},
 cldm.ddim_hacked.DDIMSampler, ControlLDM.apply_model (called unbound on a shim) --
 feeds them the seeded synthetic weights/inputs of prompt-diffusion_amd/weights.py and
@@ -13,7 +13,7 @@ absent in this image and only needed by training code at module import (SURVEY.m
 DDIMSampler.register_buffer is overridden because the stock one force-moves buffers to
 "cuda" (cldm/ddim_hacked.py:17-21) and there is no GPU here.
 
-Usage: python tests/golden/make_golden.py [--skip-sd15] [--only sd15_s50,sd15_512_s50]   (the 50-step cases take
+Usage: python tests/golden/make_golden.py --reference DIR [--skip-sd15] [--only sd15_s50,sd15_512_s50]   (the 50-step cases take
 ~3 and ~12 minutes on 8 cores and are generated only when named)
 """
 import argparse
@@ -27,7 +27,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = "/root/reference"
+REF = None   # the reference checkout, set from --reference
 sys.path.insert(0, ROOT)
 
 
@@ -519,7 +519,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--skip-sd15", action="store_true")
     ap.add_argument("--only", default="")
+    ap.add_argument("--reference", required=True, metavar="DIR", help="checkout of the reference project")
     args = ap.parse_args()
+    global REF
+    REF = os.path.abspath(args.reference)
     if not args.only or "clip" in args.only.split(","):
         from transformers import CLIPTextModel  # noqa: F401  (before the stub modules go in: it probes torchvision)
     install_stubs()
