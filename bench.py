@@ -8,10 +8,14 @@ A "step" (--steps K) is one full pass of the hot path over one batch: pd_ddim_sa
 input already resident in HBM (torch CUDA tensors handed over as device pointers).  Weights are
 random-initialised on the device (no checkpoint exists offline), inputs synthetic.
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
         python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 `python bench.py --gpus N` without a torchrun environment launches that second line itself, as a CHILD process and
 before anything touches the GPU, and relays the child's JSON line.  Prints ONE JSON line on rank 0.
+A plain run does only what the headline needs: set-up, W warm-up passes, the K timed passes, the dump, the JSON line.
+--full adds, after the timed passes, everything that takes runs of its own: the rate with option cfg_share off, the profiled
+pass behind `roofline`, the VAE decode, the `parity` leg against tests/golden/, the f16x2 mode, the SD3 leg and the CPU
+baseline (each of which a --no-* flag skips).
 --dump-outputs DIR writes what the last timed step returned (the final latents of every image, float32) as DIR/latents.npy;
 the weights and inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
@@ -205,6 +209,9 @@ def main():
     ap.add_argument("--precision", default="f16", choices=["f16", "bf16", "f16x2", "f32"],
                     help="engine mode; f16 (default) is the reference's own GPU dtype (README.md:44-45)")
     ap.add_argument("--stream-f32", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the legs that take runs of their own (cfg_share-off rate, profiled roofline pass, "
+                         "VAE decode, parity, f16x2 mode, SD3 leg, CPU baseline); the --no-* flags below skip single legs of --full")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--no-f32", "--no-extra-modes", dest="no_f32", action="store_true",
@@ -345,7 +352,7 @@ def main():
                     "every layer still runs in every step on every distinct input; option cfg_share / --no-cfg-share turns it off",
             "tflop_per_image_executed": tflop_image, "tflop_per_image_reference_count": tflop_image_ref,
             "path_tflops_per_gpu_at_reference_count": value / world * tflop_image_ref}
-        if shared and world == 1 and not args.no_f32:
+        if args.full and shared and world == 1 and not args.no_f32:
             # the same workload with the option off (1 warm-up + 1 timed pass, outside the metric's timed region)
             eng.set_option("cfg_share", 0)
             eng.ddim_sample(**kw)
@@ -357,7 +364,7 @@ def main():
             eng.set_option("cfg_share", 1)
             result["cfg_shared_front"]["value_with_option_off"] = B / dq
             result["cfg_shared_front"]["latents_shared_vs_doubled_max_rel"] = float((out[:B] - o_off).abs().max() / o_off.abs().max())
-        if not args.no_profile:
+        if args.full and not args.no_profile:
             # one more pass with HIP events around every contraction launch (not part of the timed region).  It runs
             # single-stream: with ControlNet overlapped on the second stream two kernels share the chip and each one's
             # wall duration no longer measures that kernel alone.
@@ -450,21 +457,22 @@ def main():
                                   "event_bracket_calibration": "back-to-back event pairs with nothing between them",
                                   "trace": trace,
                                   "flop_per_launch": 1e9 * fl_g / max(n_g, 1), "device_ms_per_pass": ms_g, "by_kernel": classes}
-        # first-stage decode of the 8 latents, outside the metric's timed region: reported for context
-        try:
-            eng.vae_decode(out[:B])
-            torch.cuda.synchronize()
-            tv = time.perf_counter()
-            img = eng.vae_decode(out[:B])
-            torch.cuda.synchronize()
-            result["vae_decode_ms"] = 1e3 * (time.perf_counter() - tv)
-            assert torch.isfinite(img).all()
-        except Exception as ex:   # noqa: BLE001 - context only
-            result["vae_decode_ms"] = f"failed: {ex}"
-        if not args.no_parity and world == 1:
+        if args.full:
+            # first-stage decode of the 8 latents, outside the metric's timed region: reported for context
+            try:
+                eng.vae_decode(out[:B])
+                torch.cuda.synchronize()
+                tv = time.perf_counter()
+                img = eng.vae_decode(out[:B])
+                torch.cuda.synchronize()
+                result["vae_decode_ms"] = 1e3 * (time.perf_counter() - tv)
+                assert torch.isfinite(img).all()
+            except Exception as ex:   # noqa: BLE001 - context only
+                result["vae_decode_ms"] = f"failed: {ex}"
+        if args.full and not args.no_parity and world == 1:
             eng.close()
             result["parity"] = parity_leg(E, W, args.precision, args.stream_f32, local)
-        if not args.no_f32 and world == 1 and args.precision in ("f16", "bf16"):
+        if args.full and not args.no_f32 and world == 1 and args.precision in ("f16", "bf16"):
             # the f16x2 mode (split fp16 operands over fp32 storage: fp32-class results, ~5e-6 per step against every
             # reference fixture) on the same workload: 1 warm-up + 1 timed pass.  The fp32-MFMA mode is `--precision f32`.
             eng.close()
@@ -480,9 +488,9 @@ def main():
             result["f16x2_mode"] = {"value": B / d2, "unit": "images/sec", "ms_per_step": 1e3 * d2, "dtype": "f16x2",
                                     "path_tflops": B / d2 * tflop_image}
             e2.close()
-        if not args.no_sd3 and world == 1 and args.precision in ("f16", "bf16"):
+        if args.full and not args.no_sd3 and world == 1 and args.precision in ("f16", "bf16"):
             result["sd3_leg"] = sd3_leg(args.precision, local)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             result["cpu_baseline"] = cpu_baseline(S)
         print(json.dumps(result))
     if world > 1:

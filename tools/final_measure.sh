@@ -6,7 +6,7 @@ set -e
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 R=${1:-r04}
 O=gpurun_out/final; rm -rf $O; mkdir -p $O
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --single-stream --steps 2 --warmup 1 --no-cpu-baseline --no-parity --no-sd3 --no-f32 > $O/bench_under_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --full --single-stream --steps 2 --warmup 1 --no-cpu-baseline --no-parity --no-sd3 --no-f32 > $O/bench_under_rocprof.log 2>&1
 cp $(find $O/stats -name "*kernel_stats.csv" | head -1) $O/${R}_bench_kernel_stats.csv
 grep -a '^{' $O/bench_under_rocprof.log | tail -1 > $O/${R}_bench_under_rocprof.json
 rm -rf $O/stats
@@ -33,6 +33,6 @@ echo "[final] --gpus 2 rehearsal done"
 python bench.py --batch 1 --steps 3 --no-cpu-baseline --no-profile --no-f32 --no-parity --no-sd3 > $O/bench_bs1.log 2>&1
 tail -1 $O/bench_bs1.log > $O/${R}_bench_bs1.json
 cp $O/${R}_pmc_traffic.json $O/${R}_pmc_mfma_util.json $O/${R}_roofline.json profiles/   # the default line below quotes the counters measured in THIS call
-python bench.py > $O/bench_default.log 2>&1
+python bench.py --full > $O/bench_default.log 2>&1
 tail -1 $O/bench_default.log > $O/${R}_bench_default.json
 head -c 700 $O/${R}_bench_default.json

@@ -14,7 +14,7 @@ fam = {
     "attention": (("attn2_kernel<", "attn_kernel<"), ("attn_kernel",)),
     "st_tail + st_front": (("st_tail_kernel<", "st_front_kernel<"), ("st_tail_kernel",)),
 }
-out = {"source": "rocprofv3 --kernel-trace --stats -- python bench.py --single-stream --steps 2 --warmup 1 (same run as the bench line in " + sys.argv[2] + ")",
+out = {"source": "rocprofv3 --kernel-trace --stats -- python bench.py --full --single-stream --steps 2 --warmup 1 (same run as the bench line in " + sys.argv[2] + ")",
        "definition": "avg_us = sum(TotalDurationNs) / sum(Calls) over the family's rows; tflops = bench.py's algorithmic FLOPs per launch / avg_us",
        "families": {}}
 for name, (pats, classes) in fam.items():
