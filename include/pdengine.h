@@ -175,6 +175,43 @@ int pd_sample_set_guidance(pd_engine* e, float scale);
 int pd_sample_eps_at(pd_engine* e, int64_t t, const float* scales13);
 int pd_sample_end(pd_engine* e);
 
+/* UniPC multistep solver inside the engine's loop (Zhao et al. 2023, "UniPC", data-prediction form: UniP-p predictor +
+ * UniC corrector; the same update as the host plug-in UniPCMultistepScheduler of the Python package).  Given the grid,
+ * every coefficient of every step is fixed, so one step is one elementwise kernel over the guided eps, the latents, the
+ * last corrected sample and up to three earlier x0 predictions; that state is kept in fp64 on the device, and only the
+ * sample each step returns is rounded to fp32 -- exactly where the host scheduler rounds.
+ * The grid is pd_sample_args.timesteps (required, HOST memory, strictly descending, sampling order) with `steps` entries;
+ * eta must be 0 and noise NULL (UniPC draws no noise). */
+typedef struct pd_unipc_args {
+    int32_t order;              /* solver_order, 1..3 */
+    int32_t bh2;                /* 1: B(h) = expm1(h) ("bh2"), 0: B(h) = h ("bh1") */
+    int32_t lower_order_final;  /* the last steps lower the order to the number of steps left */
+    int32_t n_disable_corrector;
+    const int32_t* disable_corrector; /* HOST, n_disable_corrector entries: no corrector at step i + 1 for every listed i
+                                         (UniPCMultistepScheduler.disable_corrector) */
+    int32_t reserved[4];
+} pd_unipc_args;
+/* One coefficient row per step i, fp64.  m_i = (x_i - sigma_i * eps_i) / alpha_i is the x0 prediction at step i.
+ *   [0] alpha_i   [1] sigma_i
+ *   [2] 1.0 when the corrector runs at step i, else 0.0
+ *   [3..7]  corrector: x_c = [3] last_sample + [4] m_i + [5] m_{i-1} + [6] m_{i-2} + [7] m_{i-3}   (x_c = x_i when off)
+ *   [8..11] predictor: x_{i+1} = [8] x_c + [9] m_i + [10] m_{i-1} + [11] m_{i-2}
+ *   [12] predictor order   [13] corrector order (0: off)   [14], [15] zero
+ * last_sample is the x_c of the previous step. */
+#define PD_UNIPC_NCOEF 16
+/* Host only (no engine, no GPU): rows [steps][PD_UNIPC_NCOEF] for the grid `timesteps` (sampling order, strictly
+ * descending, inside [0, cfg->timesteps)), alphas_cumprod derived from cfg in fp64 as pd_make_schedule derives it (before
+ * its float32 rounding). */
+int pd_unipc_coefficients(const pd_config* cfg, const pd_unipc_args* u, const int64_t* timesteps, int32_t steps,
+                          double* coef);
+/* The fused UniPC loop: begin + steps + read-back, blocking; latents_out / per_step_out as in pd_ddim_sample.  Option
+ * "graph" captures it like the DDIM loop. */
+int pd_unipc_sample(pd_engine* e, const pd_sample_args* args, const pd_unipc_args* u, int32_t mem_out, float* latents_out,
+                    float* per_step_out);
+/* Stepwise form: pd_sample_step / _get / _set_latents / _set_guidance / _end then work as for DDIM.  PD_GET_PRED_X0 is
+ * m_i of the last step, PD_GET_EPS its guided eps. */
+int pd_sample_begin_unipc(pd_engine* e, const pd_sample_args* args, const pd_unipc_args* u);
+
 /* schedule exactly as DDIMSampler.make_schedule derives it (cldm/ddim_hacked.py:23-52):
  * fills timesteps[S] (ascending), alphas[S], alphas_prev[S], sigmas[S], sqrt_one_minus_alphas[S] */
 int pd_make_schedule(pd_engine* e, int32_t steps, float eta, int64_t* timesteps, float* alphas,

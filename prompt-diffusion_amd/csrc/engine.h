@@ -12,6 +12,8 @@
 void pd_set_error(const char* fmt, ...);
 // timestep_embedding (util.py:154-174) of n timesteps on the host: [cos | sin] halves, fp32 like the reference
 void pd_host_timestep_embedding(const int64_t* t, int n, int dim, std::vector<float>& out);
+// coefficient rows [n][PD_UNIPC_NCOEF] of the fused UniPC loop (multistep.cpp; pd_unipc_coefficients)
+int pd_unipc_table(const pd_config& cfg, const pd_unipc_args& u, const int64_t* ts, int n, std::vector<double>& coef);
 
 #define HIP_OK(expr)                                                                            \
     do {                                                                                        \
@@ -249,7 +251,14 @@ struct Session {
     // the ControlNet's layers in front of the first cross-attention once for both halves
     bool hint_shared = false, share_u = false, share_c = false;
     bool cn_cond_only = false;   // guess mode under guidance: this evaluation runs the ControlNet on the conditional half only (run_controlnet)
+    // solver of step(): DDIM, or the fused UniPC loop (pd_sample_begin_unipc / pd_unipc_sample)
+    int solver = 0;                  // SOLVER_DDIM / SOLVER_UNIPC
+    std::vector<double> unipc_coef;  // [S][PD_UNIPC_NCOEF] (multistep.cpp)
+    int unipc_ring = 0;              // x0 predictions kept: the solver order
+    double* u_last = nullptr;        // [B, HW, C] fp64: corrected sample of the previous step
+    double* u_ring[3] = {nullptr, nullptr, nullptr};   // [B, HW, C] fp64 each: m_j in slot j % unipc_ring
 };
+enum { SOLVER_DDIM = 0, SOLVER_UNIPC = 1 };
 
 struct pd_engine {
     pd_config cfg{};
@@ -428,8 +437,9 @@ struct pd_engine {
     int ensure_arena(int Bf, int h, int w, int rows, bool per_step);
     int session_setup(const pd_sample_args& a, const int64_t* t_rows, int n_rows, bool per_sample_t, bool want_per_step);
     int compute_emb(NetW& net, std::vector<float*>& tabs, const int64_t* t, int n, int row0);
-    int begin(const pd_sample_args* a, bool want_per_step);
+    int begin(const pd_sample_args* a, bool want_per_step, const pd_unipc_args* u = nullptr);
     int step(int i);
+    int step_unipc(int i, const Act& eps);
     int make_schedule(int steps, float eta, std::vector<int64_t>& ts, std::vector<float>& a, std::vector<float>& ap,
                       std::vector<float>& sg, std::vector<float>& s1m, const int64_t* custom_desc = nullptr);
 };

@@ -293,6 +293,15 @@ struct DdimCoef { float sqrt_one_minus_at, sqrt_at, sqrt_a_prev, dir_coef, sigma
 int launch_cfg_ddim(const void* eps, int eps_dt, int eps_C, float* x_state, float* pred_x0, float* eps_guided,
                     void* x_in, const float* noise, int B, int HW, int C, int Cpad, int use_cfg, DdimCoef k,
                     float temperature, int do_update, hipStream_t s);
+// Fused UniPC step (include/pdengine.h, PD_UNIPC_NCOEF): one coefficient row, passed by value so a captured graph bakes it in.
+//   c_m[0..3]: corrector weights of m_i, m_{i-1}, m_{i-2}, m_{i-3}; p_m[0..2]: predictor weights of m_i, m_{i-1}, m_{i-2};
+//   n_hist: how many of the history slots m_{i-1}, m_{i-2}, m_{i-3} the step reads (the others may be null)
+struct UnipcCoef { double alpha, sigma, c_last, c_m[4], p_x, p_m[3]; int corr, n_hist; float cfg_scale; };
+// last [B, HW, C] fp64: corrected sample of the previous step (rewritten); m_out [B, HW, C] fp64: m_i (may alias hist[n_hist-1],
+// which is read first); x_state / pred_x0 / eps_guided / x_in as in launch_cfg_ddim
+int launch_cfg_unipc(const void* eps, int eps_dt, int eps_C, float* x_state, float* pred_x0, float* eps_guided, void* x_in,
+                     int B, int HW, int C, int Cpad, int use_cfg, const UnipcCoef& k, double* last, double* m_out,
+                     const double* const hist[3], hipStream_t s);
 int launch_fill_random(void* p, int dt, long long n, float scale, float shift, uint64_t seed, hipStream_t s);
 // sd3_kernels.hip: element-wise pieces of the MMDiT path
 // y_dt == DT_FP8: y holds e4m3 bytes and y_scale[row] the row's scale (max |value| / 448); add: x <- x + add first (written back)

@@ -1,4 +1,4 @@
-// pdengine: sampling sessions (DDIM loop state, hoisted loop invariants) and the C ABI.
+// pdengine: sampling sessions (DDIM / fused UniPC loop state, hoisted loop invariants) and the C ABI.
 // Follows DDIMSampler.{make_schedule, sample, ddim_sampling, p_sample_ddim}, cldm/ddim_hacked.py:23-234.
 #include <algorithm>
 #include <cmath>
@@ -138,6 +138,13 @@ int pd_engine::session_setup(const pd_sample_args& a, const int64_t* t_rows, int
     s.emb_c.assign(cnet.n_emb, nullptr);
     for (ResW* r : unet.res_list) s.emb_u[r->emb_slot] = reinterpret_cast<float*>(arena.alloc((size_t)s.emb_rows * r->cout * 4));
     for (ResW* r : cnet.res_list) s.emb_c[r->emb_slot] = reinterpret_cast<float*>(arena.alloc((size_t)s.emb_rows * r->cout * 4));
+    // UniPC solver state, after everything a DDIM session allocates (whose layout stays as it is)
+    s.u_last = nullptr;
+    for (double*& r : s.u_ring) r = nullptr;
+    if (s.solver == SOLVER_UNIPC) {
+        s.u_last = reinterpret_cast<double*>(arena.alloc((size_t)B * HW * C * 8));
+        for (int r = 0; r < s.unipc_ring; ++r) s.u_ring[r] = reinterpret_cast<double*>(arena.alloc((size_t)B * HW * C * 8));
+    }
     s.session_top = arena.top;
 
     // ---- inputs -> device, NHWC, compute type
@@ -318,11 +325,21 @@ static int check_args(pd_engine* e, const pd_sample_args* a) {
     return 0;
 }
 
-int pd_engine::begin(const pd_sample_args* a, bool want_per_step) {
+int pd_engine::begin(const pd_sample_args* a, bool want_per_step, const pd_unipc_args* u) {
     PD_TRY(check_args(this, a));
+    ses.active = false;
+    ses.solver = SOLVER_DDIM;
+    ses.unipc_coef.clear();
+    ses.unipc_ring = 0;
+    if (u) {
+        if (a->eta != 0.f || a->noise) { pd_set_error("unipc: eta must be 0 and noise NULL (UniPC draws no noise)"); return 1; }
+        if (!a->timesteps) { pd_set_error("unipc: the timestep grid (pd_sample_args.timesteps) is required"); return 1; }
+        PD_TRY(pd_unipc_table(cfg, *u, a->timesteps, a->steps, ses.unipc_coef));
+        ses.solver = SOLVER_UNIPC;
+        ses.unipc_ring = u->order;
+    }
     HIP_OK(hipSetDevice(device));
     PD_TRY(fold_layernorms());
-    ses.active = false;
     ses.a = *a;
     ses.Bf = a->use_cfg ? 2 * a->batch : a->batch;
     ses.custom_ts.clear();
@@ -357,6 +374,11 @@ int pd_engine::step(int i) {
     const size_t mk = arena.mark();
     Act eps;
     PD_TRY(forward_eps(i, 0, &s.scales_step[(size_t)i * PD_NUM_CONTROL], eps));
+    if (s.solver == SOLVER_UNIPC) {
+        PD_TRY(step_unipc(i, eps));
+        arena.release(mk);
+        return 0;
+    }
     // p_sample_ddim, ddim_hacked.py:206-233, scalars in float32 as torch.full materialises them
     DdimCoef k;
     const float a_t = s.alphas[index], a_prev = s.alphas_prev[index], sig = s.sigmas[index];
@@ -380,6 +402,42 @@ int pd_engine::step(int i) {
             return 1;
     }
     arena.release(mk);
+    return 0;
+}
+
+// One fused UniPC step on the eps of step i: the coefficient row of multistep.cpp by value, the x0 predictions in a ring of
+// `order` slots (m_j in slot j % order; the step reads m_{i-1}.. before it writes m_i over the oldest).
+int pd_engine::step_unipc(int i, const Act& eps) {
+    Session& s = ses;
+    const pd_sample_args& a = s.a;
+    const double* row = &s.unipc_coef[(size_t)i * PD_UNIPC_NCOEF];
+    UnipcCoef k{};
+    k.alpha = row[0];
+    k.sigma = row[1];
+    k.corr = row[2] != 0.0;
+    k.c_last = row[3];
+    for (int j = 0; j < 4; ++j) k.c_m[j] = row[4 + j];
+    k.p_x = row[8];
+    for (int j = 0; j < 3; ++j) k.p_m[j] = row[9 + j];
+    const int p_order = (int)row[12], c_order = (int)row[13];
+    k.n_hist = std::max(p_order - 1, k.corr ? c_order : 0);
+    k.cfg_scale = a.cfg_scale;
+    const int R = s.unipc_ring;
+    if (k.n_hist > R || k.n_hist > i) { pd_set_error("unipc: step %d needs %d earlier x0 predictions", i, k.n_hist); return 1; }
+    const double* hist[3] = {nullptr, nullptr, nullptr};
+    for (int j = 0; j < k.n_hist; ++j) hist[j] = s.u_ring[(i - 1 - j) % R];
+    const int C = cfg.in_channels, HW = a.h * a.w;
+    ++launches;
+    if (launch_cfg_unipc(eps.p, eps.dt, eps.C, s.x_state, s.pred_x0, s.eps_g, s.x_in, a.batch, HW, C, 8, a.use_cfg, k, s.u_last,
+                         s.u_ring[i % R], hist, stream)) {
+        pd_set_error("unipc update launch failed");
+        return 1;
+    }
+    if (s.per_step) {
+        ++launches;
+        if (launch_nhwc_to_nchw(s.x_state, DT_F32, s.per_step + (size_t)(i + 1) * a.batch * C * HW, a.batch, C, a.h, a.w, 8, 1.f, stream))
+            return 1;
+    }
     return 0;
 }
 
@@ -414,6 +472,9 @@ int pd_engine::run_steps_graph() {
     hash_mix(key, ptrs, sizeof(ptrs));
     hash_mix(key, ses.scales_step.data(), ses.scales_step.size() * sizeof(float));
     hash_mix(key, ses.timesteps.data(), ses.timesteps.size() * sizeof(int64_t));
+    // the solver: a DDIM and a UniPC loop over the same grid and buffers launch the same kernels up to the update
+    hash_mix(key, &ses.solver, sizeof(ses.solver));
+    hash_mix(key, ses.unipc_coef.data(), ses.unipc_coef.size() * sizeof(double));
     for (auto& g : graphs)
         if (g.key == key) {
             HIP_OK(hipGraphLaunch(g.exec, stream));
@@ -583,6 +644,7 @@ int pd_eps(pd_engine* e, const float* x, const int64_t* t, const float* ctx, con
     else memcpy(th.data(), t, (size_t)Bf * 8);
     Session& s = e->ses;
     s.active = false;
+    s.solver = SOLVER_DDIM;
     s.a = a;
     s.Bf = Bf;
     s.S = 1;
@@ -707,6 +769,28 @@ int pd_sample_end(pd_engine* e) {
 int pd_ddim_sample(pd_engine* e, const pd_sample_args* args, int32_t mem_out, float* latents_out, float* per_step_out) {
     if (!e || !latents_out) { pd_set_error("null argument"); return 1; }
     PD_TRY(e->begin(args, per_step_out != nullptr));
+    if (e->opt_graph && !e->profiling) {
+        PD_TRY(e->run_steps_graph());
+    } else {
+        for (int i = 0; i < e->ses.S; ++i) PD_TRY(e->step(i));
+    }
+    PD_TRY(pd_sample_get(e, PD_GET_LATENTS, mem_out, latents_out));
+    if (per_step_out) {
+        const size_t n = (size_t)(e->ses.S + 1) * args->batch * e->cfg.in_channels * args->h * args->w;
+        PD_TRY(copy_out(e, e->ses.per_step, per_step_out, n, mem_out));
+    }
+    return pd_sample_end(e);
+}
+
+int pd_sample_begin_unipc(pd_engine* e, const pd_sample_args* args, const pd_unipc_args* u) {
+    if (!e || !u) { pd_set_error("null argument"); return 1; }
+    return e->begin(args, false, u);
+}
+
+int pd_unipc_sample(pd_engine* e, const pd_sample_args* args, const pd_unipc_args* u, int32_t mem_out, float* latents_out,
+                    float* per_step_out) {
+    if (!e || !u || !latents_out) { pd_set_error("null argument"); return 1; }
+    PD_TRY(e->begin(args, per_step_out != nullptr, u));
     if (e->opt_graph && !e->profiling) {
         PD_TRY(e->run_steps_graph());
     } else {

@@ -61,6 +61,15 @@ class pd_sample_args(C.Structure):
     ]
 
 
+class pd_unipc_args(C.Structure):
+    _fields_ = [
+        ("order", C.c_int32), ("bh2", C.c_int32), ("lower_order_final", C.c_int32), ("n_disable_corrector", C.c_int32),
+        ("disable_corrector", C.c_void_p), ("reserved", C.c_int32 * 4),
+    ]
+
+
+PD_UNIPC_NCOEF = 16
+
 _lib = None
 
 
@@ -118,6 +127,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.pd_sample_set_guidance.argtypes = [C.c_void_p, C.c_float]
     lib.pd_sample_end.argtypes = [C.c_void_p]
     lib.pd_make_schedule.argtypes = [C.c_void_p, C.c_int32, C.c_float] + [C.c_void_p] * 5
+    lib.pd_unipc_coefficients.argtypes = [C.POINTER(pd_config), C.POINTER(pd_unipc_args), C.c_void_p, C.c_int32, C.c_void_p]
+    lib.pd_unipc_sample.argtypes = [C.c_void_p, C.POINTER(pd_sample_args), C.POINTER(pd_unipc_args), C.c_int32, C.c_void_p,
+                                    C.c_void_p]
+    lib.pd_sample_begin_unipc.argtypes = [C.c_void_p, C.POINTER(pd_sample_args), C.POINTER(pd_unipc_args)]
     lib.pd_synchronize.argtypes = [C.c_void_p]
     lib.pd_stream.argtypes = [C.c_void_p]
     lib.pd_stream.restype = C.c_void_p
@@ -153,6 +166,7 @@ EXPORTS = [
     "pd_last_error", "pd_abi_version", "pd_engine_create", "pd_engine_destroy", "pd_param_count", "pd_param_info",
     "pd_load_weights", "pd_init_random_weights", "pd_weights_missing", "pd_vae_weights_missing", "pd_vae_decode", "pd_eps", "pd_control_shape", "pd_ddim_sample",
     "pd_sample_begin", "pd_sample_step", "pd_sample_get", "pd_sample_set_latents", "pd_sample_set_guidance", "pd_sample_eps_at", "pd_sample_end",
+    "pd_unipc_coefficients", "pd_unipc_sample", "pd_sample_begin_unipc",
     "pd_make_schedule", "pd_synchronize", "pd_stream", "pd_wait_stream", "pd_set_option", "pd_get_stat", "pd_bench_conv3x3", "pd_bench_linear", "pd_text_encode", "pd_text_encode_ex", "pd_text_weights_missing",
     "pd_profile_read", "pd_profile_dump", "pd_comm_new_id", "pd_comm_init", "pd_comm_world", "pd_comm_all_gather", "pd_comm_destroy",
     "pd_sd3_configure", "pd_sd3_weights_missing", "pd_sd3_forward", "pd_sd3_control", "pd_sd3_sample", "pd_sd3_down_proj",
@@ -187,6 +201,43 @@ def make_config(cfg: ModelConfig, precision: int = PD_PREC_F16, stream_f32: bool
     c.vae_num_res_blocks, c.vae_out_ch, c.scale_factor = cfg.vae_num_res_blocks, cfg.vae_out_ch, cfg.scale_factor
     c.text_vocab, c.text_layers, c.text_heads, c.text_ff = cfg.text_vocab, cfg.text_layers, cfg.text_heads, cfg.text_ff
     return c
+
+
+def alphas_cumprod(cfg: ModelConfig) -> np.ndarray:
+    """The engine's noise schedule in fp64: make_beta_schedule('linear') (betas linear in sqrt space), cumulative product
+    of 1 - beta -- the values the fused UniPC coefficients are derived from (pd_unipc_coefficients)."""
+    T = cfg.timesteps
+    s0, s1 = np.sqrt(cfg.linear_start), np.sqrt(cfg.linear_end)
+    st = (s1 - s0) / (T - 1) if T > 1 else 0.0
+    b = s0 + st * np.arange(T, dtype=np.float64)
+    b[-1] = s1
+    return np.cumprod(1.0 - b * b)
+
+
+def _unipc_args(order: int, solver_type: str, lower_order_final: bool, disable_corrector) -> Tuple[pd_unipc_args, np.ndarray]:
+    if solver_type not in ("bh1", "bh2"):
+        raise ValueError("solver_type must be 'bh1' or 'bh2'")
+    dc = np.ascontiguousarray(np.asarray(list(disable_corrector), dtype=np.int64).astype(np.int32).reshape(-1))
+    u = pd_unipc_args()
+    u.order, u.bh2, u.lower_order_final = int(order), 1 if solver_type == "bh2" else 0, 1 if lower_order_final else 0
+    u.n_disable_corrector = len(dc)
+    u.disable_corrector = dc.ctypes.data if len(dc) else None
+    return u, dc
+
+
+def unipc_coefficients(cfg: ModelConfig, timesteps, order: int = 2, solver_type: str = "bh2", lower_order_final: bool = True,
+                       disable_corrector: Sequence[int] = ()) -> np.ndarray:
+    """Per-step coefficient rows [steps, PD_UNIPC_NCOEF] (fp64) of the fused UniPC loop for the grid `timesteps` (sampling
+    order); row layout in include/pdengine.h.  Host only: needs the library, not a GPU."""
+    lib = load_library()
+    ts = np.ascontiguousarray(_to_host(timesteps), dtype=np.int64).reshape(-1)
+    u, dc = _unipc_args(order, solver_type, lower_order_final, disable_corrector)
+    c = make_config(cfg)
+    out = np.zeros((max(len(ts), 1), PD_UNIPC_NCOEF), np.float64)
+    if lib.pd_unipc_coefficients(C.byref(c), C.byref(u), ts.ctypes.data if len(ts) else None, len(ts), out.ctypes.data) != 0:
+        raise PdError(lib.pd_last_error().decode(errors="replace"))
+    del dc
+    return out[:len(ts)]
 
 
 def _is_torch(x) -> bool:
@@ -453,6 +504,39 @@ class Engine:
         self._check(self.lib.pd_ddim_sample(self._h, C.byref(a), a.mem, op, ip))
         del keep
         return (out, inter) if return_intermediates else out
+
+    def unipc_sample(self, *, return_intermediates: bool = False, order: int = 2, solver_type: str = "bh2",
+                     lower_order_final: bool = True, disable_corrector: Sequence[int] = (), **kw):
+        """The fused UniPC loop (the update of schedulers.UniPCMultistepScheduler, run on the device): `timesteps` (the grid,
+        sampling order) is required; otherwise the arguments and returns of ddim_sample."""
+        a, keep, (B, h, w) = self._args(**kw)
+        u, dc = _unipc_args(order, solver_type, lower_order_final, disable_corrector)
+        S = a.steps
+        Cc = self.cfg.in_channels
+        if a.mem == PD_MEM_DEVICE:
+            import torch
+            dev = keep[0].owner.device
+            out = torch.empty((B, Cc, h, w), dtype=torch.float32, device=dev)
+            inter = torch.empty((S + 1, B, Cc, h, w), dtype=torch.float32, device=dev) if return_intermediates else None
+            op, ip = out.data_ptr(), (inter.data_ptr() if inter is not None else None)
+        else:
+            out = np.empty((B, Cc, h, w), np.float32)
+            inter = np.empty((S + 1, B, Cc, h, w), np.float32) if return_intermediates else None
+            op, ip = out.ctypes.data, (inter.ctypes.data if inter is not None else None)
+        self._check(self.lib.pd_unipc_sample(self._h, C.byref(a), C.byref(u), a.mem, op, ip))
+        del keep, dc
+        return (out, inter) if return_intermediates else out
+
+    def sample_begin_unipc(self, *, order: int = 2, solver_type: str = "bh2", lower_order_final: bool = True,
+                           disable_corrector: Sequence[int] = (), **kw) -> int:
+        """Stepwise form of unipc_sample: then sample_step / sample_get / sample_set_latents / sample_end."""
+        a, keep, shape = self._args(**kw)
+        u, dc = _unipc_args(order, solver_type, lower_order_final, disable_corrector)
+        self._check(self.lib.pd_sample_begin_unipc(self._h, C.byref(a), C.byref(u)))
+        del dc
+        self._keep = keep
+        self._ses = (shape, a.mem, keep[0].owner if a.mem == PD_MEM_DEVICE else None)
+        return a.steps
 
     def sample_begin(self, **kw) -> int:
         a, keep, shape = self._args(**kw)

@@ -49,7 +49,9 @@ class PromptDiffusionPipeline:
     vae_scaling_factor = 0.18215      # models/cldm_v15.yaml:17
 
     def __init__(self, engine: E.Engine, text_encoder: Optional[Callable] = None, vae_decode: Optional[Callable] = None,
-                 scheduler: Any = None, tokenizer: Any = None):
+                 scheduler: Any = None, tokenizer: Any = None, fuse_scheduler: bool = False):
+        """fuse_scheduler: run a UniPCMultistepScheduler's update inside the engine's loop (pd_unipc_sample) instead of on
+        the host between eps evaluations; same grid, same controlnet_keep scales, same callback semantics."""
         self.engine = engine
         self.tokenizer = tokenizer
         if text_encoder is None and tokenizer is not None:
@@ -59,7 +61,25 @@ class PromptDiffusionPipeline:
         self.text_encoder = text_encoder
         self.vae_decode = vae_decode
         self.scheduler = scheduler          # None = the engine's fused DDIM (DDIMScheduler semantics of SD1.5)
+        self.fuse_scheduler = bool(fuse_scheduler)
+        if self.fuse_scheduler:
+            self._check_fusable()
         self._guidance_scale = 7.5
+
+    def _check_fusable(self):
+        """The fused loop restates this package's UniPC on the engine's own noise schedule; anything else is refused."""
+        from .schedulers import UniPCMultistepScheduler
+        sched = self.scheduler
+        if type(sched) is not UniPCMultistepScheduler:
+            raise ValueError(f"fuse_scheduler=True needs prompt_diffusion_amd.schedulers.UniPCMultistepScheduler, got {type(sched)}")
+        cfg = self.engine.cfg
+        if sched.num_train_timesteps != cfg.timesteps:
+            raise ValueError(f"fuse_scheduler=True: scheduler num_train_timesteps {sched.num_train_timesteps} != the engine's "
+                             f"{cfg.timesteps}")
+        ac = E.alphas_cumprod(cfg)
+        if not np.allclose(sched.alphas_cumprod, ac, rtol=1e-12, atol=0):
+            raise ValueError("fuse_scheduler=True: the scheduler's alphas_cumprod differ from the engine's noise schedule "
+                             "(beta_start / beta_end / beta_schedule)")
 
     # ------------------------------------------------------------------ properties of the reference
     @property
@@ -328,7 +348,19 @@ class PromptDiffusionPipeline:
         if custom_ts is not None:
             kw["timesteps"] = custom_ts
         eng = self.engine
-        if self.scheduler is None and callback_on_step_end is None and callback is None:
+        if self.fuse_scheduler:
+            # the scheduler's update inside the engine's loop: its grid, the per-step controlnet_keep scales; UniPC draws no noise
+            self._check_fusable()
+            sched = self.scheduler
+            kw.update(timesteps=[int(t) for t in sched.timesteps], eta=0.0, noise=None)
+            unipc = dict(order=sched.solver_order, solver_type=sched.solver_type, lower_order_final=sched.lower_order_final,
+                         disable_corrector=list(sched.disable_corrector))
+            if callback_on_step_end is None and callback is None:
+                lat = eng.unipc_sample(**kw, **unipc)
+            else:
+                lat = self._stepwise(kw, scales_step, callback_on_step_end, callback_on_step_end_tensor_inputs, callback,
+                                     callback_steps, pe, ne, eta, generator, unipc=unipc)
+        elif self.scheduler is None and callback_on_step_end is None and callback is None:
             lat = eng.ddim_sample(**kw)                                  # 8. the fused loop
         else:
             lat = self._stepwise(kw, scales_step, callback_on_step_end, callback_on_step_end_tensor_inputs, callback,
@@ -355,13 +387,18 @@ class PromptDiffusionPipeline:
         return StableDiffusionPipelineOutput(images=images, nsfw_content_detected=None)
 
     # ------------------------------------------------------------------ per-step driver (callbacks / plug-in schedulers)
-    def _stepwise(self, kw, scales_step, cb_end, cb_inputs, cb_legacy, cb_steps, pe, ne, eta, generator):
+    def _stepwise(self, kw, scales_step, cb_end, cb_inputs, cb_legacy, cb_steps, pe, ne, eta, generator, unipc=None):
         eng = self.engine
         sched = self.scheduler
-        if sched is not None:       # the engine only evaluates eps at the scheduler's timesteps: no DDIM tables needed
+        if unipc is not None:       # fused UniPC: the engine steps on the scheduler's grid (kw["timesteps"])
+            sched = None
+            n = eng.sample_begin_unipc(**kw, **unipc)
+        elif sched is not None:     # the engine only evaluates eps at the scheduler's timesteps: no DDIM tables needed
             kw = {k: v for k, v in kw.items() if k not in ("control_scales_step", "noise")}
             kw["eta"] = 0.0
-        n = eng.sample_begin(**kw)
+            n = eng.sample_begin(**kw)
+        else:
+            n = eng.sample_begin(**kw)
         if sched is not None:
             ts = [int(t) for t in sched.timesteps]       # set_timesteps ran in __call__
             extra = {}
