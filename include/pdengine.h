@@ -82,7 +82,10 @@ typedef struct pd_config {
     int32_t text_layers;      /* 12 */
     int32_t text_heads;       /* 12 */
     int32_t text_ff;          /* 3072 */
-    int32_t reserved[2];
+    /* first-stage KL-VAE encoder (Encoder + quant_conv, ldm/models/autoencoder.py:31-33, 83-87; same vae_* hyper-parameters,
+     * double_z, no attention in the levels).  0: not built (the default); needs vae_ch > 0 */
+    int32_t vae_encoder;
+    int32_t reserved[1];
 } pd_config;
 
 /* Arguments of one sampling call (replaces DDIMSampler.sample's arguments,
@@ -142,6 +145,20 @@ int pd_vae_weights_missing(pd_engine* e);
  * latents [B, in_ch, h, w] -> images [B, vae_out_ch, 8h, 8w] in roughly [-1, 1] (fp32, NCHW).  Call after the sampling
  * session has ended; parameters are the checkpoint's first_stage_model.decoder.* / first_stage_model.post_quant_conv.* */
 int pd_vae_decode(pd_engine* e, const float* latents, int32_t B, int32_t h, int32_t w, int32_t mem, float* images_out);
+
+/* first-stage encode, LatentDiffusion.encode_first_stage + get_first_stage_encoding (ddpm.py:831-832, :655-662) ->
+ * AutoencoderKL.encode (autoencoder.py:83-87) -> Encoder.forward (model.py:508-544) -> DiagonalGaussianDistribution
+ * (ldm/modules/distributions/distributions.py:24-62; logvar clamped to [-30, 20], std = exp(0.5 logvar)).
+ * images [B, vae_out_ch, H, W] in [-1, 1], NCHW fp32; H and W multiples of 8 with (H/8)*(W/8) a multiple of 64.  `images`,
+ * `noise` and `out` live in `mem`.  Needs an engine created with vae_encoder = 1, its first_stage_model.encoder.* /
+ * first_stage_model.quant_conv.* weights, and no active sampling session.  Random draws come from the caller: */
+#define PD_VAE_MEAN    0  /* scale_factor * posterior.mode()                        -> [B, z, H/8, W/8]   */
+#define PD_VAE_SAMPLE  1  /* scale_factor * posterior.sample() with caller `noise`  -> [B, z, H/8, W/8]   */
+#define PD_VAE_MOMENTS 2  /* quant_conv output (mean ; logvar), unscaled            -> [B, 2z, H/8, W/8]  */
+int pd_vae_encode(pd_engine* e, const float* images, int32_t B, int32_t H, int32_t W, int32_t mem, int32_t what,
+                  const float* noise /* [B, z, H/8, W/8], SAMPLE only */, float* out);
+/* number of encoder tensors not loaded yet (0 when the encoder is not built) */
+int pd_vae_encoder_weights_missing(pd_engine* e);
 
 /* operator boundary: eps = apply_model(x, t, cond), cldm/cldm.py:369-382.
  *   x [Bf,in_ch,h,w], t [Bf] (int64), ctx [Bf,L,D], pair [Bf,hint_ch,8h,8w], query [Bf,q_ch,8h,8w],

@@ -10,6 +10,7 @@
  *   pd_op_attention  softmax(q k^T dh^-0.5) v, heads from the engine config        attention.py:171-193
  *   pd_op_spatial_transformer  one SpatialTransformer block of the loaded networks  attention.py:271-275,321-340
  *   pd_op_time_embed timestep_embedding + the time_embed MLP of a loaded network    util.py:154-174, openaimodel.py:526-531
+ *   pd_op_vae_downsample  the KL-VAE encoder's Downsample (asymmetric pad)          ldm/modules/diffusionmodules/model.py:68-88
  */
 #ifndef PDENGINE_OPS_H
 #define PDENGINE_OPS_H
@@ -36,6 +37,9 @@ int pd_op_spatial_transformer(pd_engine* e, const char* prefix, const float* x, 
  * and time_embed(temb) = Linear -> SiLU -> Linear of the loaded network (net 0: UNet, 1: ControlNet; openaimodel.py:526-531) -> emb
  * [n][4 * model_channels]; exactly what the sampler computes once per call for all its steps (pd_engine::compute_emb). */
 int pd_op_time_embed(pd_engine* e, int net, const int64_t* t, int n, float* temb, float* emb);
+/* Downsample.forward with_conv (model.py:80-88): F.pad(x, (0,1,0,1)) then Conv2d 3x3, stride 2, padding 0; x [B, C, H, W] ->
+ * y [B, C, H/2, W/2] (floor), w [C, C, 3, 3], bias [C] or NULL; the implicit-GEMM gather with GemmParams::pad_shift = 1 */
+int pd_op_vae_downsample(pd_engine* e, const float* x, const float* w, const float* bias, int B, int C, int H, int W, float* y);
 #ifdef __cplusplus
 }
 #endif

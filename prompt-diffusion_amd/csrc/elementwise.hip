@@ -1,6 +1,7 @@
 // Layout conversion, concat, CFG + DDIM / UniPC update and device-side weight initialisation (gfx950).
 // All of these are HBM-trivial next to the contractions; they exist to keep the whole denoising loop
 // on the device with no host round trip per step.
+#include "../../include/pdengine.h"
 #include "pd_common.h"
 
 namespace {
@@ -81,6 +82,36 @@ __global__ void nhwc_to_nchw_kernel(const void* __restrict__ in, int in_dt, floa
         const long long j = ((long long)b * HW + p) * Cpad + c;
         const float v = in_dt == DT_F32 ? reinterpret_cast<const float*>(in)[j] : cvt32_rt(reinterpret_cast<const uint16_t*>(in)[j], in_dt);
         out[i] = v * scale;
+    }
+}
+
+// One thread per output element, fp32 arithmetic throughout; reads of `mom` are strided by Cpad (8 floats = 32 bytes for the
+// SD VAE), the NCHW writes and noise reads are contiguous.  Tiny next to the encoder's convolutions.
+__global__ void vae_posterior_kernel(const void* __restrict__ mom, int mom_dt, int Cpad, const float* __restrict__ noise,
+                                     float* __restrict__ out, int B, int z, int HW, int what, float scale) {
+    const int Cout = what == PD_VAE_MOMENTS ? 2 * z : z;
+    const long long total = (long long)B * Cout * HW;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int p = (int)(i % HW);
+        const long long bc = i / HW;
+        const int c = (int)(bc % Cout);
+        const int b = (int)(bc / Cout);
+        const long long j = ((long long)b * HW + p) * Cpad + c;
+        auto ld = [&](long long k) {
+            return mom_dt == DT_F32 ? reinterpret_cast<const float*>(mom)[k] : cvt32_rt(reinterpret_cast<const uint16_t*>(mom)[k], mom_dt);
+        };
+        const float m = ld(j);
+        float v;
+        if (what == PD_VAE_MOMENTS) {
+            v = m;   // DiagonalGaussianDistribution.parameters: unscaled, logvar unclamped
+        } else if (what == PD_VAE_SAMPLE) {
+            const float lv = fminf(fmaxf(ld(j + z), -30.0f), 20.0f);
+            const float sd = expf(0.5f * lv);   // std = exp(0.5 * logvar) (distributions.py:28-29)
+            v = scale * (m + sd * noise[((long long)b * z + c) * HW + p]);
+        } else {
+            v = scale * m;
+        }
+        out[i] = v;
     }
 }
 
@@ -282,6 +313,13 @@ int launch_embed_tokens(const int* ids, const void* tok, int tok_ld, const void*
 int launch_nhwc_to_nchw(const void* in, int in_dt, float* out, int B, int C, int H, int W, int Cpad, float scale, hipStream_t s) {
     const long long n = (long long)B * C * H * W;
     hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(nblocks(n)), dim3(TPB), 0, s, in, in_dt, out, B, C, H * W, Cpad, scale);
+    CHECK_LAUNCH();
+}
+int launch_vae_posterior(const void* mom, int mom_dt, int Cpad, const float* noise, float* out, int B, int z, int HW, int what, float scale,
+                         hipStream_t s) {
+    if (Cpad < 2 * z || (what == PD_VAE_SAMPLE && !noise) || (what != PD_VAE_MEAN && what != PD_VAE_SAMPLE && what != PD_VAE_MOMENTS)) return 1;
+    const long long n = (long long)B * (what == PD_VAE_MOMENTS ? 2 * z : z) * HW;
+    hipLaunchKernelGGL(vae_posterior_kernel, dim3(nblocks(n)), dim3(TPB), 0, s, mom, mom_dt, Cpad, noise, out, B, z, HW, what, scale);
     CHECK_LAUNCH();
 }
 int launch_cast_rows(const float* in, void* out, int out_dt, long long rows, int C, int Cpad, hipStream_t s) {

@@ -304,6 +304,7 @@ int pd_engine::build() {
     }
     build_vae();
     build_text();
+    build_vae_encoder();   // after the text transformer: a default engine's registry is unchanged
     if ((int)cnet.enc.size() + 1 != PD_NUM_CONTROL && verbose)
         fprintf(stderr, "[pdengine] note: %zu control tensors (reference SD1.5 has 13)\n", cnet.enc.size() + 1);
     if ((int)cnet.enc.size() + 1 > PD_NUM_CONTROL) {
@@ -649,7 +650,13 @@ int pd_engine::gemm(const WMat& m, const Act& in, Act& out, int stride, int ups,
     p.c_sample_rows = gx.c_sample_rows; p.c_row_off = gx.c_row_off; p.vt_tok_off = gx.vt_tok_off;
     p.a_sample_rows = gx.a_sample_rows; p.a_row_off = gx.a_row_off;
     p.c_scale = gx.c_scale;
+    p.pad_shift = gx.pad_shift;
     if (out.dt == DT_FP8 && !gx.c_scale) { pd_set_error("internal: fp8 output without row scales"); return 1; }
+    // a shifted window exists in the implicit-GEMM gather only: never hand it to a kernel that would pad symmetrically
+    if (p.pad_shift && (m.taps != 9 || ups || gn_coef || in.dt == DT_FP8 || m.geglu || VT)) {
+        pd_set_error("gemm: asymmetric conv padding needs a plain conv3x3 (no upsample / fused GroupNorm / fp8 / GEGLU / V^T)");
+        return 1;
+    }
     const bool fp8 = in.dt == DT_FP8;
     if (fp8) {   // e4m3 operands with per-row scales: the layer's quantised copy
         if (!m.w8 || !gx.a_scale || m.taps != 1 || m.geglu) { pd_set_error("internal: fp8 GEMM without quantised weights / row scales"); return 1; }
@@ -689,7 +696,7 @@ int pd_engine::gemm(const WMat& m, const Act& in, Act& out, int stride, int ups,
         p.ln_eps = 1e-5f;
     }
     // conv3x3 with enough 16x16 patches to fill the chip: LDS-patch kernel (conv_patch.hip)
-    const int ptiles = opt_patch ? conv_patch_tiles(p, P) : 0;
+    const int ptiles = (opt_patch && !p.pad_shift) ? conv_patch_tiles(p, P) : 0;   // the patch kernels pad 1 on every side
     bool use_patch = ptiles >= ncu * 3 / 4;   // (192 of 256 CUs: a launch that fills three quarters of the chip takes the patch kernel unsplit)
     // 16x16-level convs: too few 16x16 patches for the chip, but the patch kernel still beats the generic gather when the
     // channel chunks are split across 2-4 slices (fp32 slabs + the same deterministic finalize pass as the GEMM's split-K)
@@ -860,6 +867,7 @@ int pd_engine::gemm(const WMat& m, const Act& in, Act& out, int stride, int ups,
 
 int pd_engine::conv(const ConvW& c, const Act& in, Act& out, int act, float scale, const Act* R, const float* rowvec,
                     int rowvec_stride, int ups) {
+    gx.pad_shift = c.pad_shift;
     return gemm(c.m, in, out, c.stride, ups, act, scale, R, rowvec, rowvec_stride, false, nullptr, 0, 0);
 }
 
@@ -921,7 +929,7 @@ int pd_engine::conv_gn(const ConvW& c, const Act& x, Act& out, const float* g, c
     GemmParams q{};
     q.M = (int)out.rows(); q.N = c.m.N; q.K = c.m.K; q.taps = c.m.taps; q.Cin = c.m.cin_pad; q.stride = c.stride;
     q.Hin = x.H; q.Win = x.W; q.Hout = out.H; q.Wout = out.W; q.a_dt = x.dt; q.vt_begin = INT_MAX; q.splitk = 1;
-    const bool fuse = opt_gn_fuse && opt_patch && x.C == c.m.cin_pad && conv_patch_tiles(q, P) >= ncu * 3 / 4;
+    const bool fuse = opt_gn_fuse && opt_patch && !c.pad_shift && x.C == c.m.cin_pad && conv_patch_tiles(q, P) >= ncu * 3 / 4;
     if (!fuse) {
         const size_t mk = arena.mark();
         Act a = new_act(x.B, x.H, x.W, x.C, T);

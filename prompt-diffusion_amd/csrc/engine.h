@@ -63,6 +63,7 @@ struct LnStats {
 struct ConvW {
     WMat m;
     int cin = 0, cout = 0, k = 1, stride = 1;
+    int pad_shift = 0;   // GemmParams::pad_shift: 1 = the encoder Downsample's F.pad(x, (0, 1, 0, 1)) + padding 0
 };
 
 struct ResW {
@@ -125,6 +126,13 @@ struct NetW {
     std::vector<STW*> st_list;    // in kv_slot order
 };
 
+// AttnBlock (model.py:144-202) of the first stage's mid level: norm, fused q|k|v rows, proj_out (decoder and encoder)
+struct VaeAttnW {
+    int C = 0;
+    float *g = nullptr, *b = nullptr;
+    WMat qkv;
+    ConvW proj_out;
+};
 // First-stage decoder: ldm/modules/diffusionmodules/model.py:546-653 + post_quant_conv (autoencoder.py:34)
 struct VaeLevel {
     std::vector<ResW> blocks;
@@ -134,11 +142,27 @@ struct VaeLevel {
 };
 struct VaeW {
     bool built = false;
-    ConvW post_quant, conv_in, conv_out, proj_out;
+    ConvW post_quant, conv_in, conv_out;
     ResW mid1, mid2;
-    float *attn_g = nullptr, *attn_b = nullptr, *out_g = nullptr, *out_b = nullptr;
-    WMat qkv;
+    VaeAttnW attn;
+    float *out_g = nullptr, *out_b = nullptr;
     std::vector<VaeLevel> levels;  // execution order (highest resolution level last)
+    int top = 0;
+};
+// First-stage encoder (option vae_encoder): Encoder (model.py:452-544, double_z, no attention in the levels) + quant_conv
+// (autoencoder.py:33); levels in module order = execution order, every level but the last ends in a Downsample
+struct VaeEncLevel {
+    std::vector<ResW> blocks;
+    bool down = false;
+    ConvW downconv;   // stride 2, pad_shift 1
+};
+struct VaeEncW {
+    bool built = false;
+    ConvW conv_in, conv_out, quant;
+    std::vector<VaeEncLevel> levels;
+    ResW mid1, mid2;
+    VaeAttnW attn;
+    float *out_g = nullptr, *out_b = nullptr;
     int top = 0;
 };
 
@@ -194,7 +218,7 @@ struct Param {
     bool conv = false;  // OIHW source
     char init = 'w';    // recipe class for pd_init_random_weights: w, b, g(amma), e(beta)
     bool loaded = false;
-    int group = 0;      // 0: UNet + ControlNet (needed to sample), 1: VAE decoder, 2: text transformer, 3: SD3 networks
+    int group = 0;      // 0: UNet + ControlNet (needed to sample), 1: VAE decoder, 2: text transformer, 3: SD3 networks, 4: VAE encoder
 };
 
 struct Act {
@@ -275,6 +299,7 @@ struct pd_engine {
     std::unordered_map<std::string, int> index;
     NetW unet, cnet;
     VaeW vae;
+    VaeEncW vae_enc;
     TextW text;
     // captured step loops (option "graph"): key = everything a step's kernel arguments depend on
     struct GraphEntry { uint64_t key; hipGraph_t graph; hipGraphExec_t exec; };
@@ -364,11 +389,17 @@ struct pd_engine {
     void build_encoder(const std::string& prefix, NetW& net);
     void build_middle(const std::string& prefix, NetW& net);
     void build_vres(const std::string& prefix, ResW& r, int cin, int cout);
+    void build_vattn(const std::string& prefix, VaeAttnW& a, int C);
     void build_vae();
+    void build_vae_encoder();
     void build_text();
     int text_forward(const int* ids_dev, int B, float* out_dev, int clip_skip);
     int vae_forward(const float* latents_dev, int B, int h, int w, float* out_dev);
-    int vae_attention(const Act& x, Act& out);
+    int vae_encoder_forward(const float* images_dev, int B, int H, int W, int what, const float* noise_dev, float* out_dev);
+    int vae_attention(const VaeAttnW& a, const Act& x, Act& out);
+    // pd_vae_decode / pd_vae_encode: `sizing` (a dry pass of the forward) measures the workspace, which is the ControlNet
+    // context's (arena2, idle outside a sampling step) grown to that plus io_bytes if needed; then `run` enqueues for real
+    int vae_in_workspace(size_t io_bytes, const std::function<int()>& sizing, const std::function<int()>& run);
 
     // SD3 / MMDiT path (sd3.cpp)
     pd_sd3_config sd3{};
@@ -392,7 +423,8 @@ struct pd_engine {
     struct SlabDefer { bool allow = false, active = false; const float* slabs = nullptr; int nslab = 0; const float* bias = nullptr; const float* rowvec = nullptr; int rowvec_stride = 0; };
     SlabDefer* gx_defer = nullptr;   // one-shot, like gx: consumed (and cleared) by the next gemm()
     int opt_slab_gn = 1;             // the fusion above (option "slab_gn")
-    struct GemmExtra { const float* a_scale = nullptr; const float* c_scale = nullptr; const float* gate = nullptr; int gate_stride = 0, c_sample_rows = 0, c_row_off = 0, vt_tok_off = 0, a_sample_rows = 0, a_row_off = 0; } gx;
+    struct GemmExtra { const float* a_scale = nullptr; const float* c_scale = nullptr; const float* gate = nullptr; int gate_stride = 0, c_sample_rows = 0, c_row_off = 0, vt_tok_off = 0, a_sample_rows = 0, a_row_off = 0;
+                       int pad_shift = 0; } gx;   // pad_shift: ConvW::pad_shift, set by conv()
     int opt_sd3_fp8 = 0;       // 0 off, 1: the AdaLN-fed projections, 2: also the feed-forward-out projections (e4m3 GELU output under a norm bound)  // SD3 path: QKV and feed-forward-in projections in PREC_FP8 (e4m3 operands, per-row scales)
     bool sd3_fp8_dirty = true;
     int sd3_quantize();        // (re)builds the e4m3 weights of those layers after a weight change

@@ -93,8 +93,8 @@ __global__ __launch_bounds__(WM * WN * 64, (BM == 128 && WM * WN == 8) ? 4 : 2) 
             const int rem = mm - b * p.rows_per_sample;
             const int oy = rem / p.Wout;
             a_pix[i] = b * p.Hin;
-            a_y[i] = oy * p.stride - 1;
-            a_x[i] = (rem - oy * p.Wout) * p.stride - 1;
+            a_y[i] = oy * p.stride - 1 + p.pad_shift;
+            a_x[i] = (rem - oy * p.Wout) * p.stride - 1 + p.pad_shift;
             a_base[i] = 0;
         } else {
             a_base[i] = (size_t)mm * p.lda;

@@ -72,6 +72,30 @@ int pd_op_conv2d(pd_engine* e, const float* x, const float* w, const float* bias
     return from_dev_nhwc(e, out.p, odt, y, B, Cout, Ho, Wo, copad);
 }
 
+// y = Downsample(x) of the KL-VAE encoder: zero row / column appended at the bottom / right, then conv3x3 stride 2 padding 0
+int pd_op_vae_downsample(pd_engine* e, const float* x, const float* w, const float* bias, int B, int C, int H, int W, float* y) {
+    if (!e || !x || !w || !y) { pd_set_error("null argument"); return 1; }
+    if (B < 1 || C < 1 || H < 2 || W < 2) { pd_set_error("pd_op_vae_downsample: need B, C >= 1 and H, W >= 2"); return 1; }
+    HIP_OK(hipSetDevice(e->device));
+    TempMat guard(e);
+    ConvW c;
+    c.cin = C; c.cout = C; c.k = 3; c.stride = 2; c.pad_shift = 1;
+    e->make_mat(c.m, C, C * 9, 9, C, true);
+    if (!c.m.w) { pd_set_error("allocation failed"); return 1; }
+    PD_TRY(e->upload_rows(c.m, 0, w, C, true));
+    if (bias) PD_TRY(e->upload_vec(c.m.bias, bias, C, false, 0));
+    const int Ho = H / 2, Wo = W / 2;   // (H + 1 - 3) / 2 + 1
+    const int cpad = c.m.cin_pad, copad = round_up(C, 4);
+    DevBuf in((size_t)B * H * W * cpad * dt_size(e->T)), out((size_t)B * Ho * Wo * copad * dt_size(e->T));
+    if (!in.p || !out.p) { pd_set_error("allocation failed"); return 1; }
+    PD_TRY(to_dev_nhwc(e, x, in.p, e->T, B, C, H, W, cpad));
+    Act a, o;
+    a.p = in.p; a.B = B; a.H = H; a.W = W; a.C = cpad; a.dt = e->T;
+    o.p = out.p; o.B = B; o.H = Ho; o.W = Wo; o.C = copad; o.dt = e->T;
+    PD_TRY(e->conv(c, a, o));
+    return from_dev_nhwc(e, out.p, e->T, y, B, C, Ho, Wo, copad);
+}
+
 // y[M,N] = act(x[M,K] @ w[N,K]^T + b) ; geglu: w [2*N, K] -> y[M,N] = (x w_a + b_a) * gelu(x w_g + b_g)
 int pd_op_linear(pd_engine* e, const float* x, const float* w, const float* bias, int M, int K, int N, int geglu, int a_silu,
                  float* y) {

@@ -202,6 +202,10 @@ struct GemmParams {
     // c_dt == DT_FP8 (MM instantiations): the output rows are written as e4m3 of value / c_scale[row]; the caller guarantees
     // |value| <= 448 c_scale[row] (sd3.cpp: a Cauchy-Schwarz bound from the input row's norm)
     const float* c_scale;
+    // conv3x3 in the implicit-GEMM gather only: shifts the window's top-left corner by this many pixels down / right.  0 is
+    // the symmetric pad 1 of every other conv; 1 gives F.pad(x, (0, 1, 0, 1)) + padding 0, the KL-VAE encoder's Downsample
+    // (model.py:80-88) -- the bounds check already reads row Hin / column Win as the bottom / right zero.
+    int pad_shift;
 };
 
 // element-wise / norm / attention launchers (definitions in the .hip files)
@@ -303,6 +307,11 @@ int launch_cfg_unipc(const void* eps, int eps_dt, int eps_C, float* x_state, flo
                      int B, int HW, int C, int Cpad, int use_cfg, const UnipcCoef& k, double* last, double* m_out,
                      const double* const hist[3], hipStream_t s);
 int launch_fill_random(void* p, int dt, long long n, float scale, float shift, uint64_t seed, hipStream_t s);
+// DiagonalGaussianDistribution of the first-stage encoder (distributions.py:24-62) from quant_conv's NHWC output `mom` (dtype mom_dt,
+// Cpad >= 2 z channels: mean 0..z-1, logvar z..2z-1) into caller-layout fp32 NCHW: what = PD_VAE_MEAN: scale * mean,
+// PD_VAE_SAMPLE: scale * (mean + exp(0.5 clamp(logvar, -30, 20)) * noise[B, z, HW]), PD_VAE_MOMENTS: the raw [B, 2z, HW] moments
+int launch_vae_posterior(const void* mom, int mom_dt, int Cpad, const float* noise, float* out, int B, int z, int HW, int what, float scale,
+                         hipStream_t s);
 // sd3_kernels.hip: element-wise pieces of the MMDiT path
 // y_dt == DT_FP8: y holds e4m3 bytes and y_scale[row] the row's scale (max |value| / 448); add: x <- x + add first (written back)
 int launch_adaln(const void* x, int x_dt, void* y, int y_dt, const float* mod, int mod_stride, int shift_off, int scale_off, int rows,

@@ -1,8 +1,11 @@
-// pdengine: first-stage KL-VAE decoder (SURVEY.md §8f "next" row N1), built from the same kernels as the loop.
+// pdengine: first-stage KL-VAE decoder (SURVEY.md §8f "next" row N1) and encoder, built from the same kernels as the loop.
 //   LatentDiffusion.decode_first_stage   ldm/models/diffusion/ddpm.py:820-828   (z / scale_factor)
 //   AutoencoderKL.decode                 ldm/models/autoencoder.py:89-92        (post_quant_conv, decoder)
 //   Decoder.forward                      ldm/modules/diffusionmodules/model.py:619-653
 //   ResnetBlock / AttnBlock / Upsample   model.py:82-141, 144-202, 45-65        (GroupNorm eps 1e-6, swish)
+//   AutoencoderKL.encode                 autoencoder.py:83-87                   (encoder, quant_conv, posterior)
+//   Encoder.forward / Downsample         model.py:508-544, 68-88                (pad (0,1,0,1) + stride-2 conv)
+//   DiagonalGaussianDistribution         ldm/modules/distributions/distributions.py:24-62
 #include <climits>
 #include <cmath>
 
@@ -24,6 +27,19 @@ void pd_engine::build_vres(const std::string& prefix, ResW& r, int cin, int cout
     if (r.has_skip) build_conv(prefix + "nin_shortcut.", r.skip, cin, cout, 1, 1);
 }
 
+void pd_engine::build_vattn(const std::string& prefix, VaeAttnW& a, int C) {
+    a.C = C;
+    reg_vec(prefix + "norm.weight", C, &a.g, 'g');
+    reg_vec(prefix + "norm.bias", C, &a.b, 'e');
+    make_mat(a.qkv, 3 * C, C, 1, C, true);
+    const char* nm[3] = {"q", "k", "v"};
+    for (int i = 0; i < 3; ++i) {
+        reg_mat(prefix + nm[i] + ".weight", {C, C, 1, 1}, &a.qkv, i * C, true);
+        reg_bias(prefix + nm[i] + ".bias", &a.qkv, i * C, C);
+    }
+    build_conv(prefix + "proj_out.", a.proj_out, C, C, 1, 1);
+}
+
 void pd_engine::build_vae() {
     if (cfg.vae_ch <= 0) return;
     reg_group = 1;
@@ -34,15 +50,7 @@ void pd_engine::build_vae() {
     v.top = top;
     build_conv(D + "conv_in.", v.conv_in, cfg.in_channels, top, 3, 1);
     build_vres(D + "mid.block_1.", v.mid1, top, top);
-    reg_vec(D + "mid.attn_1.norm.weight", top, &v.attn_g, 'g');
-    reg_vec(D + "mid.attn_1.norm.bias", top, &v.attn_b, 'e');
-    make_mat(v.qkv, 3 * top, top, 1, top, true);
-    const char* nm[3] = {"q", "k", "v"};
-    for (int i = 0; i < 3; ++i) {
-        reg_mat(D + "mid.attn_1." + nm[i] + ".weight", {top, top, 1, 1}, &v.qkv, i * top, true);
-        reg_bias(D + "mid.attn_1." + nm[i] + ".bias", &v.qkv, i * top, top);
-    }
-    build_conv(D + "mid.attn_1.proj_out.", v.proj_out, top, top, 1, 1);
+    build_vattn(D + "mid.attn_1.", v.attn, top);
     build_vres(D + "mid.block_2.", v.mid2, top, top);
     // parameters are registered in module order up.0 .. up.N-1; execution runs the highest level first
     std::vector<std::vector<std::pair<int, int>>> io(nl);
@@ -75,15 +83,52 @@ void pd_engine::build_vae() {
     reg_group = 0;
 }
 
+// Encoder.__init__ (model.py:452-506) with double_z and attn_resolutions = [] (models/cldm_v15.yaml:64-85), then quant_conv =
+// Conv2d(2 z, 2 embed_dim, 1) (autoencoder.py:33).  Registered in module order under the checkpoint's names.
+void pd_engine::build_vae_encoder() {
+    if (!cfg.vae_encoder || cfg.vae_ch <= 0) return;
+    reg_group = 4;
+    const std::string P = "first_stage_model.", E = P + "encoder.";
+    const int nl = cfg.vae_num_levels, z2 = 2 * cfg.in_channels;
+    VaeEncW& v = vae_enc;
+    build_conv(E + "conv_in.", v.conv_in, cfg.vae_out_ch, cfg.vae_ch, 3, 1);
+    v.levels.resize(nl);   // never resized again
+    int block_in = cfg.vae_ch;
+    for (int lvl = 0; lvl < nl; ++lvl) {
+        VaeEncLevel& L = v.levels[lvl];
+        const int block_out = cfg.vae_ch * cfg.vae_ch_mult[lvl];
+        L.blocks.resize(cfg.vae_num_res_blocks);
+        const std::string pl = E + "down." + std::to_string(lvl) + ".";
+        for (int j = 0; j < cfg.vae_num_res_blocks; ++j) {
+            build_vres(pl + "block." + std::to_string(j) + ".", L.blocks[j], block_in, block_out);
+            block_in = block_out;
+        }
+        L.down = lvl != nl - 1;
+        if (L.down) {
+            build_conv(pl + "downsample.conv.", L.downconv, block_in, block_in, 3, 2);
+            L.downconv.pad_shift = 1;   // F.pad(x, (0, 1, 0, 1)), padding 0 (model.py:80-85)
+        }
+    }
+    v.top = block_in;
+    build_vres(E + "mid.block_1.", v.mid1, block_in, block_in);
+    build_vattn(E + "mid.attn_1.", v.attn, block_in);
+    build_vres(E + "mid.block_2.", v.mid2, block_in, block_in);
+    reg_vec(E + "norm_out.weight", block_in, &v.out_g, 'g');
+    reg_vec(E + "norm_out.bias", block_in, &v.out_b, 'e');
+    build_conv(E + "conv_out.", v.conv_out, block_in, z2, 3, 1);
+    build_conv(P + "quant_conv.", v.quant, z2, z2, 1, 1);
+    v.built = true;
+    reg_group = 0;
+}
+
 // AttnBlock.forward: one head over all C channels, N = H*W tokens.  Scores are materialised per sample (fp32
 // [N,N]) exactly like the reference's bmm + softmax; at 512x512 that is 64 MiB per sample, once per image.
-int pd_engine::vae_attention(const Act& x, Act& out) {
-    VaeW& v = vae;
-    const int B = x.B, H = x.H, W = x.W, C = v.top, N = H * W;
+int pd_engine::vae_attention(const VaeAttnW& v, const Act& x, Act& out) {
+    const int B = x.B, H = x.H, W = x.W, C = v.C, N = H * W;
     out = new_act(B, H, W, C, S);
     const size_t mk = arena.mark();
     Act a = new_act(B, H, W, C, T);
-    PD_TRY(groupnorm(x, a, v.attn_g, v.attn_b, 1e-6f, false));
+    PD_TRY(groupnorm(x, a, v.g, v.b, 1e-6f, false));
     Act qk = new_act(B, H, W, 2 * C, T);
     const int npad = round_up(N, 8);
     Act vt = new_act(B, C, 1, npad, T);
@@ -140,7 +185,7 @@ int pd_engine::vae_forward(const float* latents_dev, int B, int h, int w, float*
     Act t;
     PD_TRY(resblock(v.mid1, hcur, t, nullptr, 0));
     hcur = t;
-    PD_TRY(vae_attention(hcur, t));
+    PD_TRY(vae_attention(v.attn, hcur, t));
     hcur = t;
     PD_TRY(resblock(v.mid2, hcur, t, nullptr, 0));
     hcur = t;
@@ -171,6 +216,34 @@ extern "C" int pd_vae_weights_missing(pd_engine* e) {
     return n;
 }
 
+int pd_engine::vae_in_workspace(size_t io_bytes, const std::function<int()>& sizing, const std::function<int()>& run) {
+    // the first stage runs in the ControlNet context's workspace (idle outside a sampling step) on the main stream
+    std::swap(arena, arena2);
+    Arena saved = arena;
+    arena.base = nullptr; arena.cap = 0; arena.top = 0; arena.peak = 0; arena.dry = true;
+    int r = sizing();
+    const size_t need = arena.peak + io_bytes + (64u << 20);
+    arena = saved;
+    arena.dry = false;
+    if (!r && need > arena.cap) {
+        hipStreamSynchronize(stream);
+        if (stream2) hipStreamSynchronize(stream2);
+        clear_graphs();   // captured step loops point into this workspace
+        if (arena.base) hipFree(arena.base);
+        arena.base = nullptr; arena.cap = 0;
+        void* p = nullptr;
+        if (hipMalloc(&p, need) != hipSuccess) { pd_set_error("VAE workspace allocation of %.2f GiB failed", (double)need / (1 << 30)); r = 1; }
+        else { arena.base = reinterpret_cast<char*>(p); arena.cap = need; }
+    }
+    if (!r) {
+        arena.top = 0; arena.peak = 0;
+        r = run();
+        arena.top = 0;
+    }
+    std::swap(arena, arena2);
+    return r;
+}
+
 extern "C" int pd_vae_decode(pd_engine* e, const float* latents, int32_t B, int32_t h, int32_t w, int32_t mem, float* images_out) {
     if (!e || !latents || !images_out || B < 1 || h < 1 || w < 1) { pd_set_error("bad argument"); return 1; }
     if (!e->vae.built) { pd_set_error("this engine was created without a VAE decoder (vae_ch = 0)"); return 1; }
@@ -181,26 +254,8 @@ extern "C" int pd_vae_decode(pd_engine* e, const float* latents, int32_t B, int3
     HIP_OK(hipSetDevice(e->device));
     const int H = 8 * h, W = 8 * w;
     const size_t n_in = (size_t)B * e->cfg.in_channels * h * w, n_out = (size_t)B * e->cfg.vae_out_ch * H * W;
-    // the decoder runs in the ControlNet context's workspace (idle outside a sampling step) on the main stream
-    std::swap(e->arena, e->arena2);
-    Arena saved = e->arena;
-    e->arena.base = nullptr; e->arena.cap = 0; e->arena.top = 0; e->arena.peak = 0; e->arena.dry = true;
-    int r = e->vae_forward(nullptr, B, h, w, nullptr);
-    const size_t need = e->arena.peak + (n_in + n_out) * sizeof(float) + (64u << 20);
-    e->arena = saved;
-    e->arena.dry = false;
-    if (!r && need > e->arena.cap) {
-        hipStreamSynchronize(e->stream);
-        if (e->stream2) hipStreamSynchronize(e->stream2);
-        e->clear_graphs();   // captured step loops point into this workspace
-        if (e->arena.base) hipFree(e->arena.base);
-        e->arena.base = nullptr; e->arena.cap = 0;
-        void* p = nullptr;
-        if (hipMalloc(&p, need) != hipSuccess) { pd_set_error("VAE workspace allocation of %.2f GiB failed", (double)need / (1 << 30)); r = 1; }
-        else { e->arena.base = reinterpret_cast<char*>(p); e->arena.cap = need; }
-    }
-    if (!r) {
-        e->arena.top = 0; e->arena.peak = 0;
+    return e->vae_in_workspace((n_in + n_out) * sizeof(float), [&] { return e->vae_forward(nullptr, B, h, w, nullptr); }, [&] {
+        int r = 0;
         float* din = reinterpret_cast<float*>(e->arena.alloc(n_in * sizeof(float)));
         float* dout = reinterpret_cast<float*>(e->arena.alloc(n_out * sizeof(float)));
         const float* src = latents;
@@ -215,8 +270,105 @@ extern "C" int pd_vae_decode(pd_engine* e, const float* latents, int32_t B, int3
                                mem == PD_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
                 hipStreamSynchronize(e->stream) != hipSuccess) { pd_set_error("image read-back failed"); r = 1; }
         }
-        e->arena.top = 0;
+        return r;
+    });
+}
+
+// AutoencoderKL.encode (autoencoder.py:83-87): Encoder.forward (model.py:508-544) -> quant_conv -> DiagonalGaussianDistribution
+// (distributions.py:24-62), the posterior reduced on the device to what `what` asks for (PD_VAE_*)
+int pd_engine::vae_encoder_forward(const float* images_dev, int B, int H, int W, int what, const float* noise_dev, float* out_dev) {
+    VaeEncW& v = vae_enc;
+    const int cin = cfg.vae_out_ch, z = cfg.in_channels;
+    Act x = new_act(B, H, W, v.conv_in.m.cin_pad, T);
+    if (!arena.dry) {
+        PD_TRY(check_arena());
+        ++launches;
+        if (launch_nchw_to_nhwc(images_dev, x.p, T, B, cin, H, W, x.C, stream)) { pd_set_error("image upload launch failed"); return 1; }
     }
-    std::swap(e->arena, e->arena2);
-    return r;
+    Act hcur = new_act(B, H, W, cfg.vae_ch, S);
+    PD_TRY(conv(v.conv_in, x, hcur));
+    Act t;
+    for (VaeEncLevel& L : v.levels) {
+        for (ResW& r : L.blocks) {
+            PD_TRY(resblock(r, hcur, t, nullptr, 0));
+            hcur = t;
+        }
+        if (L.down) {   // Downsample: F.pad(x, (0, 1, 0, 1)) then conv3x3 stride 2, padding 0 (model.py:80-85)
+            Act d = new_act(hcur.B, hcur.H / 2, hcur.W / 2, hcur.C, S);
+            PD_TRY(conv(L.downconv, hcur, d));
+            hcur = d;
+        }
+    }
+    PD_TRY(resblock(v.mid1, hcur, t, nullptr, 0));
+    hcur = t;
+    PD_TRY(vae_attention(v.attn, hcur, t));
+    hcur = t;
+    PD_TRY(resblock(v.mid2, hcur, t, nullptr, 0));
+    hcur = t;
+    // norm_out + swish + conv_out, then quant_conv; the moments stay fp32 from here on
+    Act h = new_act(hcur.B, hcur.H, hcur.W, v.conv_out.m.N, DT_F32);
+    PD_TRY(conv_gn(v.conv_out, hcur, h, v.out_g, v.out_b, 1e-6f, true, nullptr, nullptr, 0));
+    Act mom = new_act(h.B, h.H, h.W, v.quant.m.N, DT_F32);
+    PD_TRY(conv(v.quant, h, mom));
+    if (!arena.dry) {
+        PD_TRY(check_arena());
+        ++launches;
+        if (launch_vae_posterior(mom.p, DT_F32, mom.C, noise_dev, out_dev, B, z, mom.H * mom.W, what, (float)cfg.scale_factor, stream)) {
+            pd_set_error("posterior launch failed");
+            return 1;
+        }
+    }
+    return 0;
+}
+
+extern "C" int pd_vae_encoder_weights_missing(pd_engine* e) {
+    int n = 0;
+    if (e)
+        for (auto& p : e->params) n += (p.group == 4 && !p.loaded) ? 1 : 0;
+    return n;
+}
+
+extern "C" int pd_vae_encode(pd_engine* e, const float* images, int32_t B, int32_t H, int32_t W, int32_t mem, int32_t what,
+                             const float* noise, float* out) {
+    if (!e || !images || !out || B < 1 || H < 1 || W < 1) { pd_set_error("bad argument"); return 1; }
+    if (!e->vae_enc.built) { pd_set_error("this engine was created without a VAE encoder (vae_encoder = 0)"); return 1; }
+    for (auto& p : e->params)
+        if (p.group == 4 && !p.loaded) { pd_set_error("VAE encoder weights not loaded: '%s' (and possibly more)", p.name.c_str()); return 1; }
+    if (e->ses.active) { pd_set_error("pd_vae_encode: end the sampling session first"); return 1; }
+    if (H % 8 || W % 8 || ((H / 8) * (W / 8)) % 64) {
+        pd_set_error("pd_vae_encode: H and W must be multiples of 8 and (H/8)*(W/8) a multiple of 64 (got %d x %d)", H, W);
+        return 1;
+    }
+    if (what != PD_VAE_MEAN && what != PD_VAE_SAMPLE && what != PD_VAE_MOMENTS) {
+        pd_set_error("pd_vae_encode: unknown `what` %d (PD_VAE_MEAN / PD_VAE_SAMPLE / PD_VAE_MOMENTS)", what);
+        return 1;
+    }
+    if (what == PD_VAE_SAMPLE && !noise) { pd_set_error("pd_vae_encode: PD_VAE_SAMPLE needs `noise` [B, z, H/8, W/8]"); return 1; }
+    HIP_OK(hipSetDevice(e->device));
+    const int h = H / 8, w = W / 8, z = e->cfg.in_channels;
+    const size_t n_in = (size_t)B * e->cfg.vae_out_ch * H * W, n_lat = (size_t)B * z * h * w;
+    const size_t n_noise = what == PD_VAE_SAMPLE ? n_lat : 0, n_out = what == PD_VAE_MOMENTS ? 2 * n_lat : n_lat;
+    return e->vae_in_workspace((n_in + n_noise + n_out) * sizeof(float),
+                               [&] { return e->vae_encoder_forward(nullptr, B, H, W, what, nullptr, nullptr); }, [&] {
+        int r = 0;
+        float* din = reinterpret_cast<float*>(e->arena.alloc(n_in * sizeof(float)));
+        float* dnoise = n_noise ? reinterpret_cast<float*>(e->arena.alloc(n_noise * sizeof(float))) : nullptr;
+        float* dout = reinterpret_cast<float*>(e->arena.alloc(n_out * sizeof(float)));
+        const float* src = images;
+        const float* nz = noise;
+        if (mem != PD_MEM_DEVICE) {
+            if (hipMemcpyAsync(din, images, n_in * sizeof(float), hipMemcpyHostToDevice, e->stream) != hipSuccess ||
+                (dnoise && hipMemcpyAsync(dnoise, noise, n_noise * sizeof(float), hipMemcpyHostToDevice, e->stream) != hipSuccess) ||
+                hipStreamSynchronize(e->stream) != hipSuccess) { pd_set_error("image upload failed"); r = 1; }
+            src = din;
+            nz = dnoise;
+        }
+        if (!r) r = e->vae_encoder_forward(src, B, H, W, what, what == PD_VAE_SAMPLE ? nz : nullptr, dout);
+        if (!r) {
+            if (hipMemcpyAsync(out, dout, n_out * sizeof(float), mem == PD_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                               e->stream) != hipSuccess ||
+                hipStreamSynchronize(e->stream) != hipSuccess) { pd_set_error("latent read-back failed"); r = 1; }
+        }
+        return r;
+    });
 }

@@ -15,6 +15,13 @@ reference's; the host synchronises only when it reads latents back.
 ``ucg_schedule`` (per-step guidance, :159-161), ``noise_dropout`` (:232), ``make_schedule(ddim_discretize="quad")`` (util.py:49-50) and
 ``encode`` / ``stochastic_encode`` / ``decode`` (:237-318) are built on the same per-step export; ``score_corrector``,
 ``quantize_x0`` and ``dynamic_threshold`` raise ``NotImplementedError``.
+
+The first stage runs on the engine too (``encode_first_stage`` / ``get_first_stage_encoding`` / ``decode_first_stage``; the
+encoder needs an engine built with ``ModelConfig(vae_encoder=True)``), so the SD img2img recipe is
+
+    init = model.get_first_stage_encoding(model.encode_first_stage(x))
+    z = sampler.stochastic_encode(init, t_enc, noise=...)
+    samples = model.decode_first_stage(sampler.decode(z, cond, t_enc, ...))
 """
 from __future__ import annotations
 
@@ -41,6 +48,31 @@ def _np32(x):
     return np.asarray(x, np.float32)
 
 
+class DiagonalGaussianDistribution:
+    """The posterior of ldm/modules/distributions/distributions.py:24-62 over the engine's quant_conv moments [B, 2z, h, w]:
+    logvar clamped to [-30, 20], std = exp(0.5 logvar), var = exp(logvar), mode() = mean (fp32 on the host)."""
+
+    def __init__(self, parameters, deterministic: bool = False):
+        self.parameters = _np32(parameters)
+        self.mean, self.logvar = np.split(self.parameters, 2, axis=1)
+        self.logvar = np.clip(self.logvar, np.float32(-30.0), np.float32(20.0))
+        self.deterministic = deterministic
+        self.std = np.exp(np.float32(0.5) * self.logvar)
+        self.var = np.exp(self.logvar)
+        if deterministic:
+            self.var = self.std = np.zeros_like(self.mean)
+
+    def sample(self, noise=None, generator: Optional[np.random.Generator] = None):
+        """mean + std * noise; noise defaults to a standard normal draw from `generator` (or NumPy's global one)."""
+        if noise is None:
+            g = generator if generator is not None else np.random
+            noise = g.standard_normal(self.mean.shape).astype(np.float32)
+        return (self.mean + self.std * _np32(noise)).astype(np.float32)
+
+    def mode(self):
+        return self.mean
+
+
 class ControlLDM:
     """The attributes of cldm.cldm.ControlLDM the sampler touches, backed by an Engine."""
 
@@ -50,6 +82,7 @@ class ControlLDM:
         self.only_mid_control = False             # cldm/cldm.py:334
         self.num_timesteps = engine.cfg.timesteps
         self.parameterization = "eps"
+        self.scale_factor = engine.cfg.scale_factor   # cldm_v15.yaml:17
         # DDPM.register_schedule buffers q_sample reads (ddpm.py:138-163): fp64 schedule, stored fp32
         cfg = engine.cfg
         betas = np.linspace(cfg.linear_start ** 0.5, cfg.linear_end ** 0.5, cfg.timesteps, dtype=np.float64) ** 2
@@ -66,6 +99,25 @@ class ControlLDM:
         sa = self.sqrt_alphas_cumprod[t].reshape(-1, 1, 1, 1)
         sb = self.sqrt_one_minus_alphas_cumprod[t].reshape(-1, 1, 1, 1)
         return (sa * x_start + sb * np.asarray(noise, np.float32)).astype(np.float32)
+
+    def encode_first_stage(self, x):
+        """LatentDiffusion.encode_first_stage (ddpm.py:831-832): the KL-VAE encoder on the engine -> the posterior."""
+        return DiagonalGaussianDistribution(_np32(self.engine.vae_encode(x, mode="moments")))
+
+    def get_first_stage_encoding(self, encoder_posterior, noise=None):
+        """ddpm.py:655-662: scale_factor * posterior.sample() (`noise`: the standard normal draw; default a fresh host draw),
+        or scale_factor * tensor."""
+        if isinstance(encoder_posterior, DiagonalGaussianDistribution):
+            z = encoder_posterior.sample(noise)
+        elif E._is_torch(encoder_posterior) or isinstance(encoder_posterior, np.ndarray):
+            z = _np32(encoder_posterior)
+        else:
+            raise NotImplementedError(f"encoder_posterior of type '{type(encoder_posterior)}' not yet implemented")
+        return (np.float32(self.scale_factor) * z).astype(np.float32)
+
+    def decode_first_stage(self, z):
+        """LatentDiffusion.decode_first_stage (ddpm.py:820-828): 1 / scale_factor, post_quant_conv and the decoder, on the engine."""
+        return self.engine.vae_decode(_np32(z))
 
     def apply_model(self, x_noisy, t, cond, *args, **kwargs):
         """eps = apply_model(x, t, cond), cldm/cldm.py:369-382 (one HIP pass through ControlNet + UNet)."""

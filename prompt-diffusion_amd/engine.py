@@ -21,6 +21,8 @@ PRECISIONS = {"bf16": PD_PREC_BF16, "f32": PD_PREC_F32, "fp32": PD_PREC_F32, "f1
 PD_MEM_HOST, PD_MEM_DEVICE = 0, 1
 PD_DT_F32, PD_DT_F16, PD_DT_BF16 = 0, 1, 2
 PD_GET_LATENTS, PD_GET_PRED_X0, PD_GET_EPS = 0, 1, 2
+PD_VAE_MEAN, PD_VAE_SAMPLE, PD_VAE_MOMENTS = 0, 1, 2
+VAE_ENCODE_MODES = {"mean": PD_VAE_MEAN, "sample": PD_VAE_SAMPLE, "moments": PD_VAE_MOMENTS}
 PD_MAX_LEVELS = 8
 PD_NUM_CONTROL = 13
 PD_COMM_ID_BYTES = 128
@@ -45,7 +47,7 @@ class pd_config(C.Structure):
         ("vae_ch", C.c_int32), ("vae_num_levels", C.c_int32), ("vae_ch_mult", C.c_int32 * PD_MAX_LEVELS),
         ("vae_num_res_blocks", C.c_int32), ("vae_out_ch", C.c_int32), ("scale_factor", C.c_double),
         ("text_vocab", C.c_int32), ("text_layers", C.c_int32), ("text_heads", C.c_int32), ("text_ff", C.c_int32),
-        ("reserved", C.c_int32 * 2),
+        ("vae_encoder", C.c_int32), ("reserved", C.c_int32 * 1),
     ]
 
 
@@ -113,6 +115,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.pd_weights_missing.argtypes = [C.c_void_p]
     lib.pd_vae_weights_missing.argtypes = [C.c_void_p]
     lib.pd_vae_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+    lib.pd_vae_encode.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p]
+    lib.pd_vae_encoder_weights_missing.argtypes = [C.c_void_p]
     lib.pd_text_weights_missing.argtypes = [C.c_void_p]
     lib.pd_text_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     lib.pd_text_encode_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
@@ -157,6 +161,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.pd_op_attention.argtypes = [C.c_void_p, fp, fp, fp] + [C.c_int] * 4 + [fp]
     lib.pd_op_spatial_transformer.argtypes = [C.c_void_p, C.c_char_p, fp, fp] + [C.c_int] * 3 + [fp]
     lib.pd_op_time_embed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, fp, fp]
+    lib.pd_op_vae_downsample.argtypes = [C.c_void_p, fp, fp, fp] + [C.c_int] * 4 + [fp]
     if path is None:
         _lib = lib
     return lib
@@ -164,13 +169,15 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
 
 EXPORTS = [
     "pd_last_error", "pd_abi_version", "pd_engine_create", "pd_engine_destroy", "pd_param_count", "pd_param_info",
-    "pd_load_weights", "pd_init_random_weights", "pd_weights_missing", "pd_vae_weights_missing", "pd_vae_decode", "pd_eps", "pd_control_shape", "pd_ddim_sample",
+    "pd_load_weights", "pd_init_random_weights", "pd_weights_missing", "pd_vae_weights_missing", "pd_vae_decode",
+    "pd_vae_encode", "pd_vae_encoder_weights_missing", "pd_eps", "pd_control_shape", "pd_ddim_sample",
     "pd_sample_begin", "pd_sample_step", "pd_sample_get", "pd_sample_set_latents", "pd_sample_set_guidance", "pd_sample_eps_at", "pd_sample_end",
     "pd_unipc_coefficients", "pd_unipc_sample", "pd_sample_begin_unipc",
     "pd_make_schedule", "pd_synchronize", "pd_stream", "pd_wait_stream", "pd_set_option", "pd_get_stat", "pd_bench_conv3x3", "pd_bench_linear", "pd_text_encode", "pd_text_encode_ex", "pd_text_weights_missing",
     "pd_profile_read", "pd_profile_dump", "pd_comm_new_id", "pd_comm_init", "pd_comm_world", "pd_comm_all_gather", "pd_comm_destroy",
     "pd_sd3_configure", "pd_sd3_weights_missing", "pd_sd3_forward", "pd_sd3_control", "pd_sd3_sample", "pd_sd3_down_proj",
     "pd_op_conv2d", "pd_op_linear", "pd_op_linear_fp8", "pd_op_groupnorm", "pd_op_layernorm", "pd_op_attention", "pd_op_spatial_transformer", "pd_op_time_embed",
+    "pd_op_vae_downsample",
 ]
 
 
@@ -200,6 +207,7 @@ def make_config(cfg: ModelConfig, precision: int = PD_PREC_F16, stream_f32: bool
         c.vae_ch_mult[i] = m
     c.vae_num_res_blocks, c.vae_out_ch, c.scale_factor = cfg.vae_num_res_blocks, cfg.vae_out_ch, cfg.scale_factor
     c.text_vocab, c.text_layers, c.text_heads, c.text_ff = cfg.text_vocab, cfg.text_layers, cfg.text_heads, cfg.text_ff
+    c.vae_encoder = 1 if cfg.vae_encoder else 0
     return c
 
 
@@ -332,7 +340,8 @@ class Engine:
 
     def load_state_dict(self, items: Iterable[Tuple[str, np.ndarray]], strict: bool = True) -> None:
         """Walk a reference checkpoint (``model.diffusion_model.*`` / ``control_model.*`` keys,
-        cldm/model.py:12-21); other prefixes (first_stage_model, cond_stage_model) are skipped."""
+        cldm/model.py:12-21); ``first_stage_model.*`` / ``cond_stage_model.*`` tensors load into the parts this engine built
+        (decoder, text transformer, and the encoder with ``vae_encoder=True``), everything else is skipped."""
         known = {n for n, _ in self.param_names()}
         it = items.items() if isinstance(items, dict) else items
         for name, arr in it:
@@ -363,6 +372,39 @@ class Engine:
             op = out.ctypes.data
         self._order_after_torch(b.mem)
         self._check(self.lib.pd_vae_decode(self._h, b.ptr, B, h, w, b.mem, op))
+        return out
+
+    def vae_encoder_weights_missing(self) -> int:
+        return int(self.lib.pd_vae_encoder_weights_missing(self._h))
+
+    def vae_encode(self, images, mode: str = "mean", noise=None):
+        """AutoencoderKL.encode (autoencoder.py:83-87) on the device: images [B,3,H,W] in [-1, 1] (H, W multiples of 8,
+        (H/8)*(W/8) a multiple of 64) ->
+          "mean":    scale_factor * posterior.mode()                        [B,4,H/8,W/8]
+          "sample":  scale_factor * (mean + std * noise), noise [B,4,H/8,W/8] standard normal from the caller
+          "moments": quant_conv output (mean ; logvar), unscaled, unclamped  [B,8,H/8,W/8]
+        NumPy in, NumPy out; CUDA tensors in (images and noise), CUDA tensor out."""
+        if mode not in VAE_ENCODE_MODES:
+            raise ValueError(f"mode must be one of {sorted(VAE_ENCODE_MODES)}")
+        what = VAE_ENCODE_MODES[mode]
+        b = _Buf(images)
+        nb = _Buf(noise)
+        if nb.mem is not None and nb.mem != b.mem:
+            raise PdError("images and noise must live in the same memory space")
+        B, _, H, W = b.owner.shape
+        z = self.cfg.in_channels
+        shape = (B, 2 * z if what == PD_VAE_MOMENTS else z, H // 8, W // 8)
+        if b.mem == PD_MEM_DEVICE:
+            import torch
+            out = torch.empty(shape, dtype=torch.float32, device=b.owner.device)
+            op = out.data_ptr()
+        else:
+            out = np.empty(shape, np.float32)
+            op = out.ctypes.data
+        if nb.owner is not None and tuple(nb.owner.shape) != (B, z, H // 8, W // 8):
+            raise ValueError(f"noise must be [{B}, {z}, {H // 8}, {W // 8}]")
+        self._order_after_torch(b.mem)
+        self._check(self.lib.pd_vae_encode(self._h, b.ptr, B, H, W, b.mem, what, nb.ptr if what == PD_VAE_SAMPLE else None, op))
         return out
 
     def text_weights_missing(self) -> int:
@@ -716,6 +758,16 @@ class Engine:
         o = np.empty_like(q)
         self._check(self.lib.pd_op_attention(self._h, q.ctypes.data, k.ctypes.data, v.ctypes.data, B, Nq, Nk, Cc, o.ctypes.data))
         return o
+
+    def op_vae_downsample(self, x, w, b=None):
+        """Downsample.forward (model.py:80-88): F.pad(x, (0,1,0,1)) then conv3x3 stride 2, padding 0; x [B,C,H,W] -> [B,C,H//2,W//2]."""
+        x = np.ascontiguousarray(x, np.float32); w = np.ascontiguousarray(w, np.float32)
+        B, Cc, H, W = x.shape
+        y = np.empty((B, Cc, H // 2, W // 2), np.float32)
+        bb = None if b is None else np.ascontiguousarray(b, np.float32)
+        self._check(self.lib.pd_op_vae_downsample(self._h, x.ctypes.data, w.ctypes.data, None if bb is None else bb.ctypes.data,
+                                                  B, Cc, H, W, y.ctypes.data))
+        return y
 
     def op_spatial_transformer(self, prefix: str, x, context):
         """SpatialTransformer.forward (attention.py:321-340) of the block loaded under `prefix`, through the sampling code path."""

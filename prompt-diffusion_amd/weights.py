@@ -52,6 +52,8 @@ class ModelConfig:
     vae_num_res_blocks: int = 2
     vae_out_ch: int = 3
     scale_factor: float = 0.18215       # cldm_v15.yaml:17
+    # first-stage KL-VAE encoder (Encoder + quant_conv, ldm/models/autoencoder.py:31-33): opt-in, same vae_* hyper-parameters
+    vae_encoder: bool = False
 
     # cond-stage CLIP text transformer (FrozenCLIPEmbedder -> CLIPTextModel "openai/clip-vit-large-patch14",
     # ldm/modules/encoders/modules.py:88-131): width = context_dim, length = context_len (text_layers = 0: not built)
@@ -294,6 +296,46 @@ def vae_spec(cfg: ModelConfig, prefix: str = VAE_PREFIX) -> List[Spec]:
 
 def synth_vae_state_dict(cfg: ModelConfig, seed: int = 1234) -> Dict[str, np.ndarray]:
     return {n: synth_tensor(n, s, k, seed) for n, s, k in vae_spec(cfg)}
+
+
+def _vattn(prefix: str, ch: int) -> Iterator[Spec]:
+    # AttnBlock, model.py:144-168
+    yield prefix + "norm.weight", (ch,), "gamma"
+    yield prefix + "norm.bias", (ch,), "beta"
+    for n in ("q", "k", "v", "proj_out"):
+        yield from _conv(prefix + f"{n}.", ch, ch, 1)
+
+
+def vae_encoder_spec(cfg: ModelConfig, prefix: str = VAE_PREFIX) -> List[Spec]:
+    """Encoder + quant_conv parameters in the reference's registration order (model.py:452-506 with double_z and
+    attn_resolutions = [], autoencoder.py:33): encoder.conv_in, down.0..N-1 (blocks, downsample.conv on all but the last),
+    mid, norm_out, conv_out, then quant_conv.  Independent of ``cfg.vae_encoder`` (which only decides whether an engine
+    builds it)."""
+    if cfg.vae_ch <= 0:
+        return []
+    e = prefix + "encoder."
+    z2 = 2 * cfg.in_channels
+    out: List[Spec] = list(_conv(e + "conv_in.", cfg.vae_out_ch, cfg.vae_ch, 3))
+    block_in = cfg.vae_ch
+    nl = len(cfg.vae_ch_mult)
+    for lvl, mult in enumerate(cfg.vae_ch_mult):
+        block_out = cfg.vae_ch * mult
+        for j in range(cfg.vae_num_res_blocks):
+            out += list(_vres(e + f"down.{lvl}.block.{j}.", block_in, block_out))
+            block_in = block_out
+        if lvl != nl - 1:
+            out += list(_conv(e + f"down.{lvl}.downsample.conv.", block_in, block_in, 3))
+    out += list(_vres(e + "mid.block_1.", block_in, block_in))
+    out += list(_vattn(e + "mid.attn_1.", block_in))
+    out += list(_vres(e + "mid.block_2.", block_in, block_in))
+    out += [(e + "norm_out.weight", (block_in,), "gamma"), (e + "norm_out.bias", (block_in,), "beta")]
+    out += list(_conv(e + "conv_out.", block_in, z2, 3))
+    out += list(_conv(prefix + "quant_conv.", z2, z2, 1))
+    return out
+
+
+def synth_vae_encoder_state_dict(cfg: ModelConfig, seed: int = 1234) -> Dict[str, np.ndarray]:
+    return {n: synth_tensor(n, s, k, seed) for n, s, k in vae_encoder_spec(cfg)}
 
 
 TEXT_PREFIX = "cond_stage_model.transformer.text_model."
