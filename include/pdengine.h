@@ -139,6 +139,23 @@ int pd_init_random_weights(pd_engine* e, uint64_t seed);
 /* number of UNet + ControlNet tensors not loaded yet (0 = ready to sample); the VAE decoder is counted separately */
 int pd_weights_missing(pd_engine* e);
 int pd_vae_weights_missing(pd_engine* e);
+/* Read one tensor back in the checkpoint layout of pd_load_weights, as fp32 (HOST memory, prod(shape) floats): the exact
+ * inverse of pd_load_weights for values representable in the storage type.  Matrices read back whatever is merged into them. */
+int pd_read_weights(pd_engine* e, const char* name, float* out);
+
+/* LoRA adapters, merged into the matrix weights on the device (any matrix parameter: UNet, ControlNet, text transformer, VAE,
+ * SD3).  W = W0 + sum over the adapters of scale_a * up_a . down_a, rebuilt from the saved base rows W0 at every merge, in the
+ * storage type; the sampling path is unchanged.  None of these may run during a sampling session.
+ * pd_lora_add: register one factor pair of adapter `adapter` (id >= 0, caller-chosen) on tensor `name`; HOST fp32:
+ *   up [up_rows, rank] (= [N, r, 1, 1]) with up_rows the tensor's rows, down [rank, K] or [rank, cin, kh, kw] (K = cin * kh * kw).
+ *   A new adapter starts inactive (scale 0); pd_lora_add changes no weight unless the adapter is already active.
+ * pd_lora_set_scales: scale of adapter id i = scales[i] (i < n), 0 for every id >= n; 0 = inactive.  Merges whatever changed.
+ * pd_lora_remove: forget one adapter (-1: all); parameters no adapter touches any more get W0 back bit-exactly.
+ * pd_load_weights / pd_init_random_weights on an adapted tensor replace its W0 and merge again. */
+int pd_lora_add(pd_engine* e, int32_t adapter, const char* name, const float* up, int32_t up_rows, int32_t rank, const float* down,
+                const int64_t* down_shape, int32_t down_ndim);
+int pd_lora_set_scales(pd_engine* e, const float* scales, int32_t n);
+int pd_lora_remove(pd_engine* e, int32_t adapter);
 
 /* first-stage decode, LatentDiffusion.decode_first_stage (ldm/models/diffusion/ddpm.py:820-828) ->
  * AutoencoderKL.decode (ldm/models/autoencoder.py:89-92) -> Decoder.forward (ldm/modules/diffusionmodules/model.py:619-653):

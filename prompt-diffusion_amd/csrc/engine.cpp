@@ -445,6 +445,63 @@ int pd_engine::load(const char* name, const void* data, const int64_t* shape, in
     p.loaded = true;
     ln_dirty = true;
     sd3_fp8_dirty = true;
+    if (lora.count(it->second)) PD_TRY(lora_rebase(it->second));   // new base weights under an adapter: W0, then merge again
+    return 0;
+}
+
+// pd_read_weights: the inverse of load() -- checkpoint layout, fp32 (GEGLU interleave, row_off, tap order and padding undone)
+int pd_engine::read_param(const Param& p, float* out) {
+    HIP_OK(hipSetDevice(device));
+    HIP_OK(hipStreamSynchronize(stream));
+    if (p.kind == 0) {
+        if (p.geglu_vec) {
+            const int half = p.geglu_half, nb = (half + 79) / 80;
+            std::vector<float> buf((size_t)nb * 160);
+            HIP_OK(hipMemcpy(buf.data(), p.vdst, buf.size() * 4, hipMemcpyDeviceToHost));
+            for (int j = 0; j < half; ++j) {
+                out[j] = buf[(size_t)(j / 80) * 160 + j % 80];
+                out[half + j] = buf[(size_t)(j / 80) * 160 + 80 + j % 80];
+            }
+        } else {
+            HIP_OK(hipMemcpy(out, p.vdst, (size_t)p.shape[0] * 4, hipMemcpyDeviceToHost));
+        }
+        return 0;
+    }
+    const WMat& m = *p.mat;
+    const int EB = (int)dt_size(T);
+    const size_t rowb = (size_t)m.Kpad * EB;
+    const int rows = (int)p.shape[0], cin = m.cin, kk = p.conv ? m.taps : 1;
+    std::vector<char> img((size_t)rows * rowb);
+    if (m.geglu) {
+        std::vector<char> all((size_t)m.N * rowb);
+        HIP_OK(hipMemcpy(all.data(), m.w, all.size(), hipMemcpyDeviceToHost));
+        const int half = m.Nout;
+        for (int r = 0; r < rows; ++r) {
+            const int j = r < half ? r : r - half;
+            const size_t drow = (size_t)(j / 80) * 160 + (r < half ? 0 : 80) + j % 80;
+            memcpy(img.data() + (size_t)r * rowb, all.data() + drow * rowb, rowb);
+        }
+    } else {
+        HIP_OK(hipMemcpy(img.data(), reinterpret_cast<const char*>(m.w) + (size_t)p.row_off * rowb, img.size(), hipMemcpyDeviceToHost));
+    }
+    for (int r = 0; r < rows; ++r) {
+        const char* srow = img.data() + (size_t)r * rowb;
+        for (int tp = 0; tp < kk; ++tp)
+            for (int c = 0; c < cin; ++c) {
+                const size_t k = (size_t)tp * m.cin_pad + c;
+                float v;
+                if (EB == 4) v = reinterpret_cast<const float*>(srow)[k];
+                else {
+                    const uint16_t h = reinterpret_cast<const uint16_t*>(srow)[k];
+                    if (T == DT_F16) v = host_h2f(h);
+                    else {
+                        const uint32_t u = (uint32_t)h << 16;
+                        memcpy(&v, &u, 4);
+                    }
+                }
+                out[p.conv ? ((size_t)r * cin + c) * kk + tp : (size_t)r * cin + c] = v;
+            }
+    }
     return 0;
 }
 
@@ -524,6 +581,7 @@ int pd_engine::init_random(uint64_t seed) {
     HIP_OK(hipStreamSynchronize(stream));
     ln_dirty = true;
     sd3_fp8_dirty = true;
+    if (!lora.empty()) PD_TRY(lora_rebase(-1));
     return 0;
 }
 

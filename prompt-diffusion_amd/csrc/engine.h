@@ -2,6 +2,7 @@
 #pragma once
 #include <cstdint>
 #include <functional>
+#include <map>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -429,6 +430,33 @@ struct pd_engine {
     bool sd3_fp8_dirty = true;
     int sd3_quantize();        // (re)builds the e4m3 weights of those layers after a weight change
     bool opt_gemv = true;     // Linear over <= 4 fp32 rows with a wide output (MMDiT modulation): weight-streaming kernel instead of a GEMM tile
+
+    // LoRA adapters merged in place into matrix parameters (lora.cpp, lora.hip).  A target is one Param that at least one
+    // adapter touches: its base rows W0 in T (all m.N rows of a GEGLU matrix), and every adapter's up^T / down stacked in load
+    // order as the merge kernel's UT [R][rows] / D [R][Kpad] operands.
+    struct LoraEntry { int adapter = 0, r = 0; };
+    struct LoraTarget {
+        void* w0 = nullptr;
+        size_t w0_bytes = 0;
+        float* ut = nullptr;
+        float* d = nullptr;
+        int R = 0;
+        std::vector<LoraEntry> entries;   // column blocks of ut / d, in load order
+        std::vector<float> merged;        // multiplier of each entry that W holds now; empty: W holds W0
+    };
+    std::map<int, LoraTarget> lora;            // by parameter index (ordered: merges launch in registry order)
+    std::map<int, float> lora_scale;           // adapter id -> multiplier (0: inactive)
+    float* lora_scale_dev = nullptr;
+    size_t lora_scale_cap = 0;
+    int lora_add(int adapter, const char* name, const float* up, int up_rows, int rank, const float* down, const int64_t* down_shape,
+                 int down_ndim);
+    int lora_set_scales(const float* scales, int n);
+    int lora_remove(int adapter);
+    int lora_merge(int only_param, bool force);   // only_param -1: every target
+    int lora_rebase(int only_param);              // base weights were written: W -> W0, then merge again
+    void lora_release();
+    size_t lora_bytes(bool base_only) const;
+    int read_param(const Param& p, float* out);
 
     // weights
     int load(const char* name, const void* data, const int64_t* shape, int ndim, int dtype);

@@ -307,6 +307,11 @@ int launch_cfg_unipc(const void* eps, int eps_dt, int eps_C, float* x_state, flo
                      int B, int HW, int C, int Cpad, int use_cfg, const UnipcCoef& k, double* last, double* m_out,
                      const double* const hist[3], hipStream_t s);
 int launch_fill_random(void* p, int dt, long long n, float scale, float shift, uint64_t seed, hipStream_t s);
+// LoRA merge (lora.hip) of one matrix parameter: W rows = round_dt(W0 + (scale . UT)^T D); UT [R][rows], D [R][Kpad] fp32,
+// scale [R]; source row n -> WMat row row_off + n, or the 80 + 80 GEGLU interleave when geglu_half > 0 (row_off 0); W0 holds the
+// destination rows from row_off on.  Kpad must be a multiple of 32.
+int launch_lora_merge(int dt, void* W, const void* W0, int rows, int row_off, int geglu_half, int Kpad, const float* UT,
+                      const float* D, const float* scale, int R, hipStream_t s);
 // DiagonalGaussianDistribution of the first-stage encoder (distributions.py:24-62) from quant_conv's NHWC output `mom` (dtype mom_dt,
 // Cpad >= 2 z channels: mean 0..z-1, logvar z..2z-1) into caller-layout fp32 NCHW: what = PD_VAE_MEAN: scale * mean,
 // PD_VAE_SAMPLE: scale * (mean + exp(0.5 clamp(logvar, -30, 20)) * noise[B, z, HW]), PD_VAE_MOMENTS: the raw [B, 2z, HW] moments

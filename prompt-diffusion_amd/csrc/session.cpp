@@ -554,6 +554,7 @@ void pd_engine_destroy(pd_engine* e) {
     if (e->stream) hipStreamSynchronize(e->stream);
     (void)pd_comm_destroy(e);
     e->clear_graphs();
+    e->lora_release();
     if (e->stream2) { hipStreamSynchronize(e->stream2); hipStreamDestroy(e->stream2); }
     for (hipEvent_t ev : e->sd3_ev) hipEventDestroy(ev);
     if (e->ev_fork) hipEventDestroy(e->ev_fork);
@@ -909,6 +910,9 @@ int64_t pd_get_stat(pd_engine* e, const char* key) {
     if (!strcmp(key, "ring_launches")) return (int64_t)e->ring_launches;   // of which: gemm_ring.hip's persistent ring kernel
     if (!strcmp(key, "steps")) return (int64_t)e->ses.S;
     if (!strcmp(key, "cfg_shared")) return (int64_t)((e->ses.share_u ? 1 : 0) | (e->ses.share_c ? 2 : 0) | (e->ses.cn_cond_only ? 4 : 0));
+    if (!strcmp(key, "lora_base_bytes")) return (int64_t)e->lora_bytes(true);   // base copies W0 of the adapted parameters
+    if (!strcmp(key, "lora_bytes")) return (int64_t)e->lora_bytes(false);        // ... plus the adapters' factors
+    if (!strcmp(key, "lora_targets")) return (int64_t)e->lora.size();
     if (!strcmp(key, "event_overhead_ns")) return (int64_t)(e->prof_overhead_ms * 1e6f);
     return -1;
 }

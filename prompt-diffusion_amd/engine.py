@@ -162,6 +162,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.pd_op_spatial_transformer.argtypes = [C.c_void_p, C.c_char_p, fp, fp] + [C.c_int] * 3 + [fp]
     lib.pd_op_time_embed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, fp, fp]
     lib.pd_op_vae_downsample.argtypes = [C.c_void_p, fp, fp, fp] + [C.c_int] * 4 + [fp]
+    lib.pd_read_weights.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
+    lib.pd_lora_add.argtypes = [C.c_void_p, C.c_int32, C.c_char_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                C.POINTER(C.c_int64), C.c_int32]
+    lib.pd_lora_set_scales.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+    lib.pd_lora_remove.argtypes = [C.c_void_p, C.c_int32]
     if path is None:
         _lib = lib
     return lib
@@ -177,7 +182,7 @@ EXPORTS = [
     "pd_profile_read", "pd_profile_dump", "pd_comm_new_id", "pd_comm_init", "pd_comm_world", "pd_comm_all_gather", "pd_comm_destroy",
     "pd_sd3_configure", "pd_sd3_weights_missing", "pd_sd3_forward", "pd_sd3_control", "pd_sd3_sample", "pd_sd3_down_proj",
     "pd_op_conv2d", "pd_op_linear", "pd_op_linear_fp8", "pd_op_groupnorm", "pd_op_layernorm", "pd_op_attention", "pd_op_spatial_transformer", "pd_op_time_embed",
-    "pd_op_vae_downsample",
+    "pd_op_vae_downsample", "pd_read_weights", "pd_lora_add", "pd_lora_set_scales", "pd_lora_remove",
 ]
 
 
@@ -349,6 +354,46 @@ class Engine:
                 self.load_tensor(name, arr)
         if strict and self.weights_missing():
             raise PdError(f"{self.weights_missing()} tensors missing after load_state_dict")
+
+    def read_weight(self, name: str) -> np.ndarray:
+        """One tensor back in its checkpoint layout as float32 (pd_read_weights): what the engine computes with, adapters
+        merged."""
+        shapes = getattr(self, "_shapes", None)
+        if shapes is None:
+            shapes = self._shapes = dict(self.param_names())
+        if name not in shapes:
+            raise PdError(f"pd_read_weights: unknown tensor '{name}'")
+        out = np.empty(shapes[name], np.float32)
+        self._check(self.lib.pd_read_weights(self._h, name.encode(), out.ctypes.data))
+        return out
+
+    # ------------------------------------------------------------------ LoRA (pd_lora_*)
+    def lora_add(self, adapter: int, name: str, up, down, alpha: Optional[float] = None) -> None:
+        """Register one LoRA factor pair of adapter id `adapter` on tensor `name`: up [N, r] (or [N, r, 1, 1]), down [r, K] or
+        [r, cin, kh, kw].  With `alpha`, up is multiplied by alpha / r first (in float32).  The adapter stays inactive until
+        lora_set_scales gives it a non-zero scale."""
+        up = np.asarray(_to_host(up), np.float32)
+        down = np.ascontiguousarray(np.asarray(_to_host(down), np.float32))
+        if up.ndim == 4 and up.shape[2:] == (1, 1):
+            up = up[:, :, 0, 0]
+        if up.ndim != 2:
+            raise PdError(f"pd_lora_add: '{name}': up must be [N, r] or [N, r, 1, 1], got {up.shape}")
+        r = up.shape[1]
+        if alpha is not None:
+            up = up * np.float32(float(alpha) / r)
+        up = np.ascontiguousarray(up)
+        shp = (C.c_int64 * max(1, down.ndim))(*down.shape)
+        self._check(self.lib.pd_lora_add(self._h, int(adapter), name.encode(), up.ctypes.data, up.shape[0], r, down.ctypes.data,
+                                         shp, down.ndim))
+
+    def lora_set_scales(self, scales: Sequence[float]) -> None:
+        """Scale of adapter id i = scales[i] (0: inactive; ids past the end: 0); merges what changed on the device."""
+        a = np.ascontiguousarray(np.asarray(list(scales), np.float32).reshape(-1))
+        self._check(self.lib.pd_lora_set_scales(self._h, a.ctypes.data if a.size else None, a.size))
+
+    def lora_remove(self, adapter: int = -1) -> None:
+        """Forget adapter id `adapter` (-1: all); tensors no adapter touches get their base weights back bit-exactly."""
+        self._check(self.lib.pd_lora_remove(self._h, int(adapter)))
 
     def init_random_weights(self, seed: int = 1234) -> None:
         self._check(self.lib.pd_init_random_weights(self._h, seed))

@@ -65,6 +65,12 @@ class PromptDiffusionPipeline:
         if self.fuse_scheduler:
             self._check_fusable()
         self._guidance_scale = 7.5
+        # LoRA adapters (load_lora_weights): name -> {"id", "unet", "text_encoder"}; the active set with its weights; the
+        # per-id scales the engine holds merged now (None: nothing merged yet)
+        self._lora_adapters: Dict[str, Dict[str, Any]] = {}
+        self._lora_active: Dict[str, float] = {}
+        self._lora_next_id = 0
+        self._lora_merged: Optional[List[float]] = None
 
     def _check_fusable(self):
         """The fused loop restates this package's UniPC on the engine's own noise schedule; anything else is refused."""
@@ -263,6 +269,100 @@ class PromptDiffusionPipeline:
             ne = np.repeat(_to_numpy(negative_prompt_embeds).astype(np.float32), num_images_per_prompt, axis=0)
         return pe, ne
 
+    # ------------------------------------------------------------------ LoRA (diffusers LoraLoaderMixin surface)
+    def load_lora_weights(self, pretrained_model_name_or_path_or_dict, adapter_name: Optional[str] = None, **kwargs):
+        """Load a LoRA (dict of arrays or a local .safetensors file; kohya, diffusers/PEFT or legacy attention-processor keys)
+        into the engine's UNet and text transformer as a new adapter.  It joins the active set with weight 1.0; the weights
+        are merged on the device at the next call."""
+        from . import lora as L
+        from . import weights as W
+        if kwargs:
+            raise NotImplementedError(f"load_lora_weights: unsupported arguments {sorted(kwargs)}")
+        name = adapter_name if adapter_name is not None else f"default_{self._lora_next_id}"
+        if name in self._lora_adapters:
+            raise ValueError(f"Adapter name {name} already in use")
+        triples = L.parse_lora(pretrained_model_name_or_path_or_dict, self.engine.cfg)
+        te = any(k.startswith(W.TEXT_PREFIX) for k in triples)
+        if te and self.text_encoder is not None and self.text_encoder != self._engine_text_encoder:
+            raise ValueError("this LoRA has text-encoder layers, but a caller-supplied text_encoder is attached; only the engine's "
+                             "own text transformer can take them")
+        aid = self._lora_next_id
+        added = False
+        try:
+            for k, (up, down, alpha) in triples.items():
+                self.engine.lora_add(aid, k, up, down, alpha=alpha)
+                added = True
+        except Exception:
+            if added:
+                self.engine.lora_remove(aid)
+            raise
+        self._lora_next_id += 1
+        self._lora_adapters[name] = dict(id=aid, unet=any(k.startswith(W.UNET_PREFIX) for k in triples), text_encoder=te)
+        self._lora_active[name] = 1.0
+
+    def set_adapters(self, adapter_names: Union[str, List[str]], adapter_weights: Optional[Union[float, List[float]]] = None):
+        """Make exactly these adapters active, with these weights (default 1.0)."""
+        names = [adapter_names] if isinstance(adapter_names, str) else list(adapter_names)
+        if adapter_weights is None:
+            weights = [1.0] * len(names)
+        elif isinstance(adapter_weights, (int, float)):
+            weights = [float(adapter_weights)] * len(names)
+        else:
+            weights = [float(w) for w in adapter_weights]
+        if len(weights) != len(names):
+            raise ValueError(f"Length of adapter names {len(names)} is not equal to the length of their weights {len(weights)}.")
+        for n in names:
+            if n not in self._lora_adapters:
+                raise ValueError(f"Adapter name(s) {n} not in the list of present adapters: {sorted(self._lora_adapters)}.")
+        self._lora_active = dict(zip(names, weights))
+
+    def get_active_adapters(self) -> List[str]:
+        return list(self._lora_active)
+
+    def get_list_adapters(self) -> Dict[str, List[str]]:
+        out: Dict[str, List[str]] = {}
+        for comp in ("unet", "text_encoder"):
+            names = [n for n, a in self._lora_adapters.items() if a[comp]]
+            if names:
+                out[comp] = names
+        return out
+
+    def delete_adapters(self, adapter_names: Union[str, List[str]]):
+        names = [adapter_names] if isinstance(adapter_names, str) else list(adapter_names)
+        for n in names:
+            if n not in self._lora_adapters:
+                raise ValueError(f"Adapter name {n} not in the list of present adapters: {sorted(self._lora_adapters)}.")
+        for n in names:
+            aid = self._lora_adapters.pop(n)["id"]
+            self._lora_active.pop(n, None)
+            self.engine.lora_remove(aid)
+            if self._lora_merged is not None and aid < len(self._lora_merged):
+                self._lora_merged[aid] = 0.0
+
+    def unload_lora_weights(self):
+        if self._lora_adapters:
+            self.engine.lora_remove(-1)
+        self._lora_adapters.clear()
+        self._lora_active.clear()
+        self._lora_merged = None
+
+    def _lora_scales(self, scale: float) -> List[float]:
+        """Effective multiplier per adapter id: its set_adapters weight x the call's cross_attention_kwargs scale
+        (diffusers' scale_lora_layers / lora_scale); 0 for inactive ids."""
+        out = [0.0] * self._lora_next_id
+        for n, w in self._lora_active.items():
+            out[self._lora_adapters[n]["id"]] = float(w) * float(scale)
+        return out
+
+    def _lora_sync(self, scale: float):
+        """Merge on the device only when the effective scales differ from the merged ones."""
+        want = self._lora_scales(scale)
+        if self._lora_merged is None and not any(want):
+            return
+        if want != self._lora_merged:
+            self.engine.lora_set_scales(want)
+            self._lora_merged = want
+
     # ------------------------------------------------------------------ the call
     def __call__(self, prompt: Union[str, List[str]] = None, image=None, image_pair: List = None,
                  height: Optional[int] = None, width: Optional[int] = None, num_inference_steps: int = 50,
@@ -279,8 +379,14 @@ class PromptDiffusionPipeline:
         callback_steps = kwargs.pop("callback_steps", None)
         if ip_adapter_image is not None:
             raise NotImplementedError("ip_adapter_image is outside the hot path this engine replaces")
+        lora_scale = 1.0
         if cross_attention_kwargs:
-            raise NotImplementedError("cross_attention_kwargs (LoRA scale) is outside the hot path this engine replaces")
+            if not self._lora_adapters:
+                raise NotImplementedError("cross_attention_kwargs (LoRA scale) needs a LoRA loaded with load_lora_weights")
+            extra = sorted(set(cross_attention_kwargs) - {"scale"})
+            if extra:
+                raise NotImplementedError(f"cross_attention_kwargs: only 'scale' is supported, got {extra}")
+            lora_scale = float(cross_attention_kwargs.get("scale", 1.0))
         self._clip_skip = clip_skip
         # 0/1. defaults + checks (pipeline :1033-1062)
         if not isinstance(control_guidance_start, list) and isinstance(control_guidance_end, list):
@@ -293,6 +399,8 @@ class PromptDiffusionPipeline:
                           controlnet_conditioning_scale, control_guidance_start, control_guidance_end,
                           callback_on_step_end_tensor_inputs)
         self._guidance_scale = guidance_scale
+        if self._lora_adapters or self._lora_merged is not None:
+            self._lora_sync(lora_scale)     # adapters x cross_attention_kwargs scale, in the UNet and the text transformer
         # 2. call parameters
         if prompt is not None and isinstance(prompt, str):
             batch_size = 1
