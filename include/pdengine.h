@@ -157,6 +157,17 @@ int pd_lora_add(pd_engine* e, int32_t adapter, const char* name, const float* up
 int pd_lora_set_scales(pd_engine* e, const float* scales, int32_t n);
 int pd_lora_remove(pd_engine* e, int32_t adapter);
 
+/* FreeU (diffusers UNet2DConditionModel.enable_freeu / disable_freeu): engine state that every later UNet evaluation applies
+ * (pd_eps, pd_ddim_sample, pd_unipc_sample, the per-step export, captured graphs).  In the decoder blocks of the lowest
+ * resolution (stage 1: s1, b1) and the next one (stage 2: s2, b2), before each skip concat: the first half of the backbone
+ * channels is multiplied by b, and the skip tensor (control residual added) passes through fourier_filter(threshold 1,
+ * scale s).  Any value 0 (all zeros: the disable call) turns it off -- diffusers' `s1 and s2 and b1 and b2` -- and the
+ * decoder then runs exactly what it runs without FreeU.  Non-finite values are rejected.  A call that changes the state drops
+ * the captured graphs; the next UNet evaluation uses the new values.
+ * pd_get_freeu: out[4] = {s1, s2, b1, b2} as set (zeros when disabled); returns 0. */
+int pd_set_freeu(pd_engine* e, float s1, float s2, float b1, float b2);
+int pd_get_freeu(pd_engine* e, float out[4]);
+
 /* first-stage decode, LatentDiffusion.decode_first_stage (ldm/models/diffusion/ddpm.py:820-828) ->
  * AutoencoderKL.decode (ldm/models/autoencoder.py:89-92) -> Decoder.forward (ldm/modules/diffusionmodules/model.py:619-653):
  * latents [B, in_ch, h, w] -> images [B, vae_out_ch, 8h, 8w] in roughly [-1, 1] (fp32, NCHW).  Call after the sampling

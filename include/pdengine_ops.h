@@ -40,6 +40,12 @@ int pd_op_time_embed(pd_engine* e, int net, const int64_t* t, int n, float* temb
 /* Downsample.forward with_conv (model.py:80-88): F.pad(x, (0,1,0,1)) then Conv2d 3x3, stride 2, padding 0; x [B, C, H, W] ->
  * y [B, C, H/2, W/2] (floor), w [C, C, 3, 3], bias [C] or NULL; the implicit-GEMM gather with GemmParams::pad_shift = 1 */
 int pd_op_vae_downsample(pd_engine* e, const float* x, const float* w, const float* bias, int B, int C, int H, int W, float* y);
+/* The FreeU skip concat of a decoder block (freeu_concat_kernel), in the storage type of the residual stream:
+ * y = cat([(h + h_add) with channels < C_h / 2 scaled by b, fourier_filter(skip + skip_add, threshold 1, scale s)], dim=1).
+ * h, h_add [B, C_h, H, W]; skip [skip_B, C_skip, H, W]; skip_add [skip_add_B, C_skip, H, W]; skip_B, skip_add_B are B or B / 2
+ * (read for both halves of the batch); h_add / skip_add may be NULL; y [B, C_h + C_skip, H, W].  C_h, C_skip multiples of 4. */
+int pd_op_freeu_concat(pd_engine* e, const float* h, const float* h_add, const float* skip, const float* skip_add, int B, int C_h,
+                       int C_skip, int H, int W, int skip_B, int skip_add_B, float s, float b, float* y);
 #ifdef __cplusplus
 }
 #endif

@@ -1327,12 +1327,19 @@ int pd_engine::run_unet(const Act& x_in_full, int emb_row, int emb_stride, bool 
         Act cat = new_act(h.B, h.H, h.W, h.C + skip.C, S);
         const Act* a_add = i == 0 ? &ses.control[nctl] : nullptr;
         const Act* b_add = only_mid ? nullptr : &ses.control[nctl - 1 - (int)i];
+        // FreeU (pd_set_freeu): diffusers' up_blocks[0] / [1] are the first two stages of num_res_blocks + 1 decoder blocks
+        const int stage = (int)i / (cfg.num_res_blocks + 1);
+        const bool fu = stage < 2 && freeu_on();
         if (!arena.dry) {
             PD_TRY(check_arena());
             ++launches;
-            if (launch_concat_add(h.p, a_add ? a_add->p : nullptr, skip.p, b_add ? b_add->p : nullptr, cat.p, S, h.rows(), h.C,
-                                  skip.C, stream, skip.rows(), b_add ? b_add->rows() : 0)) {
-                pd_set_error("concat launch failed");
+            const int rc = fu ? launch_freeu_concat(h.p, a_add ? a_add->p : nullptr, skip.p, b_add ? b_add->p : nullptr, cat.p, S,
+                                                    h.B, h.H, h.W, h.C, skip.C, freeu[stage], freeu[2 + stage], stream, skip.rows(),
+                                                    b_add ? b_add->rows() : 0)
+                              : launch_concat_add(h.p, a_add ? a_add->p : nullptr, skip.p, b_add ? b_add->p : nullptr, cat.p, S,
+                                                  h.rows(), h.C, skip.C, stream, skip.rows(), b_add ? b_add->rows() : 0);
+            if (rc) {
+                pd_set_error(fu ? "FreeU concat launch failed" : "concat launch failed");
                 return 1;
             }
         }

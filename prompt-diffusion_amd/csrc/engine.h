@@ -321,6 +321,9 @@ struct pd_engine {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     bool cn_pending = false;
     bool opt_two_streams = true;
+    // FreeU (pd_set_freeu): {s1, s2, b1, b2}, all zero when off; per engine, read by run_unet at every decoder block
+    float freeu[4] = {0.f, 0.f, 0.f, 0.f};
+    bool freeu_on() const { return freeu[0] != 0.f && freeu[1] != 0.f && freeu[2] != 0.f && freeu[3] != 0.f; }
     bool opt_cfg_share = true;   // option "cfg_share": the layers in front of the first cross-attention once per CFG pair (forward_eps)
     void swap_context();
     int join_controlnet();

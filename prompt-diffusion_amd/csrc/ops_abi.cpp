@@ -96,6 +96,36 @@ int pd_op_vae_downsample(pd_engine* e, const float* x, const float* w, const flo
     return from_dev_nhwc(e, out.p, e->T, y, B, C, Ho, Wo, copad);
 }
 
+// The FreeU skip concat of a decoder block (launch_freeu_concat) in the residual-stream type: NCHW fp32 in and out
+int pd_op_freeu_concat(pd_engine* e, const float* h, const float* h_add, const float* skip, const float* skip_add, int B, int C_h,
+                       int C_skip, int H, int W, int skip_B, int skip_add_B, float s, float b, float* y) {
+    if (!e || !h || !skip || !y) { pd_set_error("null argument"); return 1; }
+    if (B < 1 || H < 1 || W < 1 || C_h < 4 || C_skip < 4 || C_h % 4 || C_skip % 4) {
+        pd_set_error("pd_op_freeu_concat: need B, H, W >= 1 and C_h, C_skip positive multiples of 4");
+        return 1;
+    }
+    if ((skip_B != B && 2 * skip_B != B) || (skip_add && skip_add_B != B && 2 * skip_add_B != B)) {
+        pd_set_error("pd_op_freeu_concat: skip_B / skip_add_B must be B or B / 2");
+        return 1;
+    }
+    HIP_OK(hipSetDevice(e->device));
+    const int dt = e->S;
+    const size_t px = (size_t)H * W, es = dt_size(dt);
+    DevBuf dh((size_t)B * px * C_h * es), dha((size_t)B * px * C_h * es), ds((size_t)skip_B * px * C_skip * es),
+        dsa((size_t)(skip_add ? skip_add_B : 1) * px * C_skip * es), dy((size_t)B * px * (C_h + C_skip) * es);
+    if (!dh.p || !dha.p || !ds.p || !dsa.p || !dy.p) { pd_set_error("allocation failed"); return 1; }
+    PD_TRY(to_dev_nhwc(e, h, dh.p, dt, B, C_h, H, W, C_h));
+    if (h_add) PD_TRY(to_dev_nhwc(e, h_add, dha.p, dt, B, C_h, H, W, C_h));
+    PD_TRY(to_dev_nhwc(e, skip, ds.p, dt, skip_B, C_skip, H, W, C_skip));
+    if (skip_add) PD_TRY(to_dev_nhwc(e, skip_add, dsa.p, dt, skip_add_B, C_skip, H, W, C_skip));
+    if (launch_freeu_concat(dh.p, h_add ? dha.p : nullptr, ds.p, skip_add ? dsa.p : nullptr, dy.p, dt, B, H, W, C_h, C_skip, s, b,
+                            e->stream, (long long)skip_B * px, skip_add ? (long long)skip_add_B * px : 0)) {
+        pd_set_error("pd_op_freeu_concat: launch failed");
+        return 1;
+    }
+    return from_dev_nhwc(e, dy.p, dt, y, B, C_h + C_skip, H, W, C_h + C_skip);
+}
+
 // y[M,N] = act(x[M,K] @ w[N,K]^T + b) ; geglu: w [2*N, K] -> y[M,N] = (x w_a + b_a) * gelu(x w_g + b_g)
 int pd_op_linear(pd_engine* e, const float* x, const float* w, const float* bias, int M, int K, int N, int geglu, int a_silu,
                  float* y) {

@@ -293,6 +293,10 @@ int launch_cast_rows(const float* in, void* out, int out_dt, long long rows, int
 int launch_concat_add(const void* a, const void* a_add, const void* b, const void* b_add, void* out, int dt,
                       long long rows, int Ca, int Cb, hipStream_t s, long long b_rows = 0, long long b_add_rows = 0);
 int launch_add_inplace(void* a, const void* b, int dt, long long n, hipStream_t s);
+// FreeU's skip concat (freeu.hip): launch_concat_add's output with the first Ch / 2 backbone channels scaled by b and the skip
+// half passed through fourier_filter(threshold 1, scale s) per (sample, channel) plane; rows = B * H * W
+int launch_freeu_concat(const void* h, const void* h_add, const void* skip, const void* skip_add, void* out, int dt, int B, int H,
+                        int W, int Ch, int Cs, float s, float b, hipStream_t st, long long skip_rows = 0, long long skip_add_rows = 0);
 struct DdimCoef { float sqrt_one_minus_at, sqrt_at, sqrt_a_prev, dir_coef, sigma, cfg_scale; };
 int launch_cfg_ddim(const void* eps, int eps_dt, int eps_C, float* x_state, float* pred_x0, float* eps_guided,
                     void* x_in, const float* noise, int B, int HW, int C, int Cpad, int use_cfg, DdimCoef k,

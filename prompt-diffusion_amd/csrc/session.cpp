@@ -475,6 +475,7 @@ int pd_engine::run_steps_graph() {
     // the solver: a DDIM and a UniPC loop over the same grid and buffers launch the same kernels up to the update
     hash_mix(key, &ses.solver, sizeof(ses.solver));
     hash_mix(key, ses.unipc_coef.data(), ses.unipc_coef.size() * sizeof(double));
+    hash_mix(key, freeu, sizeof(freeu));   // FreeU values are kernel arguments (pd_set_freeu also drops the graphs)
     for (auto& g : graphs)
         if (g.key == key) {
             HIP_OK(hipGraphLaunch(g.exec, stream));
@@ -899,6 +900,24 @@ int pd_set_option(pd_engine* e, const char* key, int64_t value) {
     }
     pd_set_error("unknown option '%s'", key);
     return 1;
+}
+
+int pd_set_freeu(pd_engine* e, float s1, float s2, float b1, float b2) {
+    if (!e) { pd_set_error("null engine"); return 1; }
+    const float v[4] = {s1, s2, b1, b2};
+    for (float x : v)
+        if (!std::isfinite(x)) { pd_set_error("pd_set_freeu: values must be finite (s1 %g, s2 %g, b1 %g, b2 %g)", s1, s2, b1, b2); return 1; }
+    if (!memcmp(v, e->freeu, sizeof(v))) return 0;
+    HIP_OK(hipSetDevice(e->device));
+    e->clear_graphs();   // the values are kernel arguments of the captured loops
+    memcpy(e->freeu, v, sizeof(v));
+    return 0;
+}
+
+int pd_get_freeu(pd_engine* e, float out[4]) {
+    if (!e || !out) { pd_set_error("null argument"); return 1; }
+    memcpy(out, e->freeu, sizeof(e->freeu));
+    return 0;
 }
 
 int64_t pd_get_stat(pd_engine* e, const char* key) {

@@ -167,6 +167,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
                                 C.POINTER(C.c_int64), C.c_int32]
     lib.pd_lora_set_scales.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
     lib.pd_lora_remove.argtypes = [C.c_void_p, C.c_int32]
+    lib.pd_set_freeu.argtypes = [C.c_void_p] + [C.c_float] * 4
+    lib.pd_get_freeu.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    lib.pd_op_freeu_concat.argtypes = [C.c_void_p, fp, fp, fp, fp] + [C.c_int] * 7 + [C.c_float, C.c_float, fp]
     if path is None:
         _lib = lib
     return lib
@@ -183,6 +186,7 @@ EXPORTS = [
     "pd_sd3_configure", "pd_sd3_weights_missing", "pd_sd3_forward", "pd_sd3_control", "pd_sd3_sample", "pd_sd3_down_proj",
     "pd_op_conv2d", "pd_op_linear", "pd_op_linear_fp8", "pd_op_groupnorm", "pd_op_layernorm", "pd_op_attention", "pd_op_spatial_transformer", "pd_op_time_embed",
     "pd_op_vae_downsample", "pd_read_weights", "pd_lora_add", "pd_lora_set_scales", "pd_lora_remove",
+    "pd_set_freeu", "pd_get_freeu", "pd_op_freeu_concat",
 ]
 
 
@@ -394,6 +398,24 @@ class Engine:
     def lora_remove(self, adapter: int = -1) -> None:
         """Forget adapter id `adapter` (-1: all); tensors no adapter touches get their base weights back bit-exactly."""
         self._check(self.lib.pd_lora_remove(self._h, int(adapter)))
+
+    # ------------------------------------------------------------------ FreeU (pd_set_freeu)
+    def set_freeu(self, s1: float, s2: float, b1: float, b2: float) -> None:
+        """FreeU (arXiv:2309.11497) in every later UNet evaluation of this engine, as diffusers' unet.enable_freeu: the first
+        two decoder stages scale half their backbone channels by b1 / b2 and the lowest frequencies of their skip tensors by
+        s1 / s2.  Any value 0 leaves the UNet exactly as without FreeU; non-finite values raise PdError."""
+        self._check(self.lib.pd_set_freeu(self._h, float(s1), float(s2), float(b1), float(b2)))
+
+    def disable_freeu(self) -> None:
+        self._check(self.lib.pd_set_freeu(self._h, 0.0, 0.0, 0.0, 0.0))
+
+    @property
+    def freeu(self) -> Optional[Tuple[float, float, float, float]]:
+        """(s1, s2, b1, b2) as last set (as float32), or None after disable_freeu / before any set_freeu."""
+        out = (C.c_float * 4)()
+        self._check(self.lib.pd_get_freeu(self._h, out))
+        v = tuple(float(x) for x in out)
+        return None if not any(v) else v
 
     def init_random_weights(self, seed: int = 1234) -> None:
         self._check(self.lib.pd_init_random_weights(self._h, seed))
@@ -812,6 +834,20 @@ class Engine:
         bb = None if b is None else np.ascontiguousarray(b, np.float32)
         self._check(self.lib.pd_op_vae_downsample(self._h, x.ctypes.data, w.ctypes.data, None if bb is None else bb.ctypes.data,
                                                   B, Cc, H, W, y.ctypes.data))
+        return y
+
+    def op_freeu_concat(self, h, skip, s: float, b: float, h_add=None, skip_add=None):
+        """FreeU's skip concat of a decoder block (freeu_concat_kernel) in the residual-stream type: h, h_add [B, C_h, H, W];
+        skip, skip_add [B or B/2, C_skip, H, W] -> [B, C_h + C_skip, H, W]."""
+        f = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+        h, skip, h_add, skip_add = f(h), f(skip), f(h_add), f(skip_add)
+        B, Ch, H, W = h.shape
+        Cs = skip.shape[1]
+        y = np.empty((B, Ch + Cs, H, W), np.float32)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        self._check(self.lib.pd_op_freeu_concat(self._h, ptr(h), ptr(h_add), ptr(skip), ptr(skip_add), B, Ch, Cs, H, W,
+                                                skip.shape[0], 0 if skip_add is None else skip_add.shape[0], float(s), float(b),
+                                                y.ctypes.data))
         return y
 
     def op_spatial_transformer(self, prefix: str, x, context):

@@ -346,6 +346,31 @@ class PromptDiffusionPipeline:
         self._lora_active.clear()
         self._lora_merged = None
 
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
+        r"""Enables the FreeU mechanism as in https://arxiv.org/abs/2309.11497.
+
+        The suffixes after the scaling factors represent the stages where they are being applied.
+
+        Please refer to the [official repository](https://github.com/ChenyangSi/FreeU) for combinations of the values
+        that are known to work well for different pipelines such as Stable Diffusion v1, v2, and Stable Diffusion XL.
+
+        Args:
+            s1 (`float`):
+                Scaling factor for stage 1 to attenuate the contributions of the skip features. This is done to
+                mitigate "oversmoothing effect" in the enhanced denoising process.
+            s2 (`float`):
+                Scaling factor for stage 2 to attenuate the contributions of the skip features. This is done to
+                mitigate "oversmoothing effect" in the enhanced denoising process.
+            b1 (`float`): Scaling factor for stage 1 to amplify the contributions of backbone features.
+            b2 (`float`): Scaling factor for stage 2 to amplify the contributions of backbone features.
+        """
+        # engine state (Engine.set_freeu): every UNet evaluation of this engine applies it, whatever the scheduler path
+        self.engine.set_freeu(s1=s1, s2=s2, b1=b1, b2=b2)
+
+    def disable_freeu(self):
+        """Disables the FreeU mechanism if enabled."""
+        self.engine.disable_freeu()
+
     def _lora_scales(self, scale: float) -> List[float]:
         """Effective multiplier per adapter id: its set_adapters weight x the call's cross_attention_kwargs scale
         (diffusers' scale_lora_layers / lora_scale); 0 for inactive ids."""
