@@ -117,8 +117,20 @@ typedef struct pd_sample_args {
                                  (strictly descending) replacing the uniform grid of make_ddim_timesteps -- the (D) pipeline's
                                  `timesteps=` argument (pipeline_prompt_diffusion.py:101-142) and diffusers' leading-spaced
                                  grid for step counts that do not divide 1000 */
-    int32_t reserved[6];
+    /* img2img / inpainting (diffusers' semantics for a 4-channel UNet).  With sa(t) = sqrtf(abar[t]), sb(t) = sqrtf(1 - abar[t])
+     * from the engine's fp32 table and t_0 .. t_{S-1} the grid in sampling order:
+     *   init_latents: x_T is the noise draw eps; the loop starts from sa(t_0) z0 + sb(t_0) eps (from eps itself with
+     *     PD_INIT_PURE_NOISE); per_step_out[0] holds the start latents.
+     *   mask: after the update of step i the latents become (1 - m) k_i + m x (fp32, in this order, no FMA) before anything
+     *     reads them, with k_i = sa(t_{i+1}) z0 + sb(t_{i+1}) eps for i < S - 1 and k_{S-1} = z0; m broadcasts over channels.
+     *     Applies in pd_ddim_sample, pd_unipc_sample and pd_sample_step (also after pd_sample_set_latents), never in
+     *     pd_sample_eps_at (host-driven schedulers blend on the host). */
+    const float* init_latents; /* optional [B, in_ch, h, w] in `mem`: z0 = scale_factor * the init image's latents */
+    const float* mask;         /* optional [B, 1, h, w] in `mem`, needs init_latents; weight of the SAMPLED latents (1 = repaint, 0 = keep) */
+    int32_t init_flags;        /* PD_INIT_PURE_NOISE: start from x_T itself (diffusers' strength == 1 inpainting) */
+    int32_t reserved[1];
 } pd_sample_args;
+#define PD_INIT_PURE_NOISE 1
 
 const char* pd_last_error(void);
 int pd_abi_version(void);

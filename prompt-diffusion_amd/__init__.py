@@ -6,3 +6,12 @@ the reference's ``PromptDiffusionPipeline.__call__`` (pipeline_prompt_diffusion.
 and ``DDIMSampler.sample`` (cldm/ddim_hacked.py:55) surfaces over ctypes.
 """
 __version__ = "0.1.0"
+
+_PIPELINES = ("PromptDiffusionPipeline", "PromptDiffusionImg2ImgPipeline", "PromptDiffusionInpaintPipeline")
+
+
+def __getattr__(name):   # the pipelines, imported on first use (the package itself stays light)
+    if name in _PIPELINES:
+        from . import pipeline
+        return getattr(pipeline, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -282,6 +282,12 @@ struct Session {
     int unipc_ring = 0;              // x0 predictions kept: the solver order
     double* u_last = nullptr;        // [B, HW, C] fp64: corrected sample of the previous step
     double* u_ring[3] = {nullptr, nullptr, nullptr};   // [B, HW, C] fp64 each: m_j in slot j % unipc_ring
+    // img2img / inpainting (pd_sample_args.init_latents / mask): z0 and eps [B, C, HW] and the mask [B, HW], fp32, allocated after
+    // everything else; blend[i] = the coefficients of the blend after step i (fp32 from the engine's fp32 table, on the host)
+    float* init_z0 = nullptr;
+    float* init_eps = nullptr;
+    float* mask = nullptr;
+    std::vector<BlendCoef> blend;
 };
 enum { SOLVER_DDIM = 0, SOLVER_UNIPC = 1 };
 

@@ -310,6 +310,21 @@ struct UnipcCoef { double alpha, sigma, c_last, c_m[4], p_x, p_m[3]; int corr, n
 int launch_cfg_unipc(const void* eps, int eps_dt, int eps_C, float* x_state, float* pred_x0, float* eps_guided, void* x_in,
                      int B, int HW, int C, int Cpad, int use_cfg, const UnipcCoef& k, double* last, double* m_out,
                      const double* const hist[3], hipStream_t s);
+// img2img / inpainting (inpaint.hip; semantics in include/pdengine.h, pd_sample_args.init_latents / mask).  z0, eps: [B, C, HW]
+// fp32 NCHW; mask: [B, HW].  The blend (1 - m) k + m x, k = last ? z0 : sa z0 + sb eps, is evaluated in fp32 without contraction.
+struct BlendCoef { float sa, sb; int last; };
+// start latents: x = pure ? eps : sa z0 + sb eps -> x_state [B, HW, Cpad] (channels >= C zero), x_in (dup copies), and
+// optionally out_nchw [B, C, HW]
+int launch_init_latents(const float* z0, const float* eps, float sa, float sb, int pure, float* x_state, float* x_in, float* out_nchw,
+                        int B, int dup, int C, int Cpad, int HW, hipStream_t s);
+// launch_cfg_ddim / launch_cfg_unipc (do_update 1) with the blend applied to the updated sample before x_state / x_in are written
+int launch_cfg_ddim_blend(const void* eps, int eps_dt, int eps_C, float* x_state, float* pred_x0, float* eps_guided, void* x_in,
+                          const float* noise, int B, int HW, int C, int Cpad, int use_cfg, DdimCoef k, float temperature,
+                          const float* z0, const float* ieps, const float* mask, BlendCoef bc, hipStream_t s);
+int launch_cfg_unipc_blend(const void* eps, int eps_dt, int eps_C, float* x_state, float* pred_x0, float* eps_guided, void* x_in,
+                           int B, int HW, int C, int Cpad, int use_cfg, const UnipcCoef& k, double* last, double* m_out,
+                           const double* const hist[3], const float* z0, const float* ieps, const float* mask, BlendCoef bc,
+                           hipStream_t s);
 int launch_fill_random(void* p, int dt, long long n, float scale, float shift, uint64_t seed, hipStream_t s);
 // LoRA merge (lora.hip) of one matrix parameter: W rows = round_dt(W0 + (scale . UT)^T D); UT [R][rows], D [R][Kpad] fp32,
 // scale [R]; source row n -> WMat row row_off + n, or the 80 + 80 GEGLU interleave when geglu_half > 0 (row_off 0); W0 holds the

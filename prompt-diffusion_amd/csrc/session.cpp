@@ -11,8 +11,21 @@ const char* pd_err_buf();
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 // ------------------------------------------------------------------------------------ schedule
-// make_beta_schedule('linear') util.py:21-25 + register_schedule ddpm.py:138-159 (alphas_cumprod kept
-// as float32) + make_ddim_timesteps util.py:46-60 + make_ddim_sampling_parameters util.py:63-74.
+// make_beta_schedule('linear') util.py:21-25 + register_schedule ddpm.py:138-159: alphas_cumprod, kept as float32
+static void alphas_cumprod_f32(const pd_config& cfg, std::vector<float>& ac) {
+    const int T_ = cfg.timesteps;
+    const double s0 = std::sqrt(cfg.linear_start), s1 = std::sqrt(cfg.linear_end);
+    ac.assign(T_, 0.f);
+    double cp = 1.0;
+    const double st = T_ > 1 ? (s1 - s0) / (double)(T_ - 1) : 0.0;
+    for (int i = 0; i < T_; ++i) {
+        const double b = i == T_ - 1 ? s1 : s0 + st * (double)i;
+        cp *= 1.0 - b * b;
+        ac[i] = (float)cp;
+    }
+}
+
+// make_ddim_timesteps util.py:46-60 + make_ddim_sampling_parameters util.py:63-74 on the table above.
 // custom_desc (optional): `steps` timesteps in sampling order (descending), replacing the uniform grid -- the DDIM parameters
 // are derived from the list the same way (a_prev of an entry = alphas_cumprod at the next entry, alphas_cumprod[0] after the last)
 int pd_engine::make_schedule(int steps, float eta, std::vector<int64_t>& ts, std::vector<float>& al, std::vector<float>& ap,
@@ -22,15 +35,8 @@ int pd_engine::make_schedule(int steps, float eta, std::vector<int64_t>& ts, std
         pd_set_error("steps must be in [1, %d]", T_);
         return 1;
     }
-    const double s0 = std::sqrt(cfg.linear_start), s1 = std::sqrt(cfg.linear_end);
-    std::vector<float> ac(T_);
-    double cp = 1.0;
-    const double st = T_ > 1 ? (s1 - s0) / (double)(T_ - 1) : 0.0;
-    for (int i = 0; i < T_; ++i) {
-        const double b = i == T_ - 1 ? s1 : s0 + st * (double)i;
-        cp *= 1.0 - b * b;
-        ac[i] = (float)cp;
-    }
+    std::vector<float> ac;
+    alphas_cumprod_f32(cfg, ac);
     const int c = T_ / steps;
     ts.clear();
     if (custom_desc) {
@@ -145,6 +151,13 @@ int pd_engine::session_setup(const pd_sample_args& a, const int64_t* t_rows, int
         s.u_last = reinterpret_cast<double*>(arena.alloc((size_t)B * HW * C * 8));
         for (int r = 0; r < s.unipc_ring; ++r) s.u_ring[r] = reinterpret_cast<double*>(arena.alloc((size_t)B * HW * C * 8));
     }
+    // img2img / inpainting inputs, after the UniPC state (a plain session's layout stays as it is)
+    s.init_z0 = s.init_eps = s.mask = nullptr;
+    if (a.init_latents) {
+        s.init_z0 = reinterpret_cast<float*>(arena.alloc((size_t)B * C * HW * 4));
+        s.init_eps = reinterpret_cast<float*>(arena.alloc((size_t)B * C * HW * 4));
+        if (a.mask) s.mask = reinterpret_cast<float*>(arena.alloc((size_t)B * HW * 4));
+    }
     s.session_top = arena.top;
 
     // ---- inputs -> device, NHWC, compute type
@@ -157,7 +170,26 @@ int pd_engine::session_setup(const pd_sample_args& a, const int64_t* t_rows, int
         }
         return dev ? src : d;
     };
-    {
+    if (s.init_z0) {
+        // x_T is the noise draw eps; the start kernel writes the session's latents from z0 and eps
+        if (!arena.dry) {
+            const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+            const size_t n = (size_t)B * C * HW;
+            HIP_OK(hipMemcpyAsync(s.init_eps, a.x_T, n * 4, kind, stream));
+            HIP_OK(hipMemcpyAsync(s.init_z0, a.init_latents, n * 4, kind, stream));
+            if (s.mask) HIP_OK(hipMemcpyAsync(s.mask, a.mask, (size_t)B * HW * 4, kind, stream));
+            HIP_OK(hipStreamSynchronize(stream));
+            const BlendCoef& b0 = s.blend[0];
+            ++launches;
+            if (launch_init_latents(s.init_z0, s.init_eps, b0.sa, b0.sb, (a.init_flags & PD_INIT_PURE_NOISE) ? 1 : 0, s.x_state, s.x_in,
+                                    s.per_step, B, Bf / B, C, 8, HW, stream)) {
+                pd_set_error("start latents launch failed");
+                return 1;
+            }
+        }
+        if (s.noise && !arena.dry)
+            HIP_OK(hipMemcpyAsync(s.noise, a.noise, (size_t)s.S * B * C * HW * 4, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
+    } else {
         const float* xT = stage(a.x_T, (size_t)B * C * HW);
         if (!xT && !arena.dry) { pd_set_error("copy of x_T failed"); return 1; }
         if (!arena.dry) {
@@ -320,6 +352,9 @@ static int check_args(pd_engine* e, const pd_sample_args* a) {
         pd_set_error("eta > 0 needs the noise draws (pd_sample_args.noise: [steps][B, in_ch, h, w])");
         return 1;
     }
+    if (a->mask && !a->init_latents) { pd_set_error("mask needs init_latents (the latents of the region to keep)"); return 1; }
+    if (a->init_flags & ~PD_INIT_PURE_NOISE) { pd_set_error("init_flags: unknown bits 0x%x", (unsigned)(a->init_flags & ~PD_INIT_PURE_NOISE)); return 1; }
+    if ((a->init_flags & PD_INIT_PURE_NOISE) && !a->init_latents) { pd_set_error("init_flags PD_INIT_PURE_NOISE needs init_latents"); return 1; }
     for (auto& p : e->params)
         if (p.group == 0 && !p.loaded) { pd_set_error("weights not loaded: '%s' (and possibly more)", p.name.c_str()); return 1; }
     return 0;
@@ -359,6 +394,19 @@ int pd_engine::begin(const pd_sample_args* a, bool want_per_step, const pd_unipc
         }
     std::vector<int64_t> trows(S_);
     for (int i = 0; i < S_; ++i) trows[i] = ses.timesteps[S_ - 1 - i];  // sampling order = flipped (ddim_hacked.py:144)
+    // img2img / inpainting: blend[i] = (sa, sb) at t_i for i < S (blend[0]: the start), blend[S] = z0 itself (after the last step)
+    ses.blend.clear();
+    if (a->init_latents) {
+        std::vector<float> ac;
+        alphas_cumprod_f32(cfg, ac);
+        ses.blend.resize(S_ + 1);
+        for (int i = 0; i <= S_; ++i) {
+            BlendCoef& b = ses.blend[i];
+            b.last = i == S_;
+            b.sa = b.last ? 1.f : sqrtf(ac[trows[i]]);
+            b.sb = b.last ? 0.f : sqrtf(1.0f - ac[trows[i]]);
+        }
+    }
     PD_TRY(ensure_arena(ses.Bf, a->h, a->w, S_, want_per_step));
     PD_TRY(session_setup(*a, trows.data(), S_, false, want_per_step));
     ses.active = true;
@@ -391,8 +439,14 @@ int pd_engine::step(int i) {
     const int C = cfg.in_channels, HW = a.h * a.w;
     const float* nz = s.noise ? s.noise + (size_t)i * a.batch * C * HW : nullptr;
     ++launches;
-    if (launch_cfg_ddim(eps.p, eps.dt, eps.C, s.x_state, s.pred_x0, s.eps_g, s.x_in, nz, a.batch, HW, C, 8, a.use_cfg, k,
-                        a.temperature, 1, stream)) {
+    if (s.mask) {   // inpainting: the same update with the known region put back (inpaint.hip)
+        if (launch_cfg_ddim_blend(eps.p, eps.dt, eps.C, s.x_state, s.pred_x0, s.eps_g, s.x_in, nz, a.batch, HW, C, 8, a.use_cfg, k,
+                                  a.temperature, s.init_z0, s.init_eps, s.mask, s.blend[i + 1], stream)) {
+            pd_set_error("ddim update (blend) launch failed");
+            return 1;
+        }
+    } else if (launch_cfg_ddim(eps.p, eps.dt, eps.C, s.x_state, s.pred_x0, s.eps_g, s.x_in, nz, a.batch, HW, C, 8, a.use_cfg, k,
+                               a.temperature, 1, stream)) {
         pd_set_error("ddim update launch failed");
         return 1;
     }
@@ -428,8 +482,14 @@ int pd_engine::step_unipc(int i, const Act& eps) {
     for (int j = 0; j < k.n_hist; ++j) hist[j] = s.u_ring[(i - 1 - j) % R];
     const int C = cfg.in_channels, HW = a.h * a.w;
     ++launches;
-    if (launch_cfg_unipc(eps.p, eps.dt, eps.C, s.x_state, s.pred_x0, s.eps_g, s.x_in, a.batch, HW, C, 8, a.use_cfg, k, s.u_last,
-                         s.u_ring[i % R], hist, stream)) {
+    if (s.mask) {   // inpainting: the blend after the predictor (inpaint.hip)
+        if (launch_cfg_unipc_blend(eps.p, eps.dt, eps.C, s.x_state, s.pred_x0, s.eps_g, s.x_in, a.batch, HW, C, 8, a.use_cfg, k,
+                                   s.u_last, s.u_ring[i % R], hist, s.init_z0, s.init_eps, s.mask, s.blend[i + 1], stream)) {
+            pd_set_error("unipc update (blend) launch failed");
+            return 1;
+        }
+    } else if (launch_cfg_unipc(eps.p, eps.dt, eps.C, s.x_state, s.pred_x0, s.eps_g, s.x_in, a.batch, HW, C, 8, a.use_cfg, k, s.u_last,
+                                s.u_ring[i % R], hist, stream)) {
         pd_set_error("unipc update launch failed");
         return 1;
     }
@@ -476,6 +536,12 @@ int pd_engine::run_steps_graph() {
     hash_mix(key, &ses.solver, sizeof(ses.solver));
     hash_mix(key, ses.unipc_coef.data(), ses.unipc_coef.size() * sizeof(double));
     hash_mix(key, freeu, sizeof(freeu));   // FreeU values are kernel arguments (pd_set_freeu also drops the graphs)
+    // img2img / inpainting: the blend kernels and their coefficients (the start runs before the captured loop)
+    const int32_t init[] = {ses.init_z0 ? 1 : 0, ses.mask ? 1 : 0, a.init_flags};
+    const void* iptrs[] = {ses.init_z0, ses.init_eps, ses.mask};
+    hash_mix(key, init, sizeof(init));
+    hash_mix(key, iptrs, sizeof(iptrs));
+    hash_mix(key, ses.blend.data(), ses.blend.size() * sizeof(BlendCoef));
     for (auto& g : graphs)
         if (g.key == key) {
             HIP_OK(hipGraphLaunch(g.exec, stream));

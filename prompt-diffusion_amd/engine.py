@@ -59,8 +59,12 @@ class pd_sample_args(C.Structure):
         ("x_T", C.c_void_p), ("ctx_cond", C.c_void_p), ("ctx_uncond", C.c_void_p), ("pair", C.c_void_p),
         ("query", C.c_void_p), ("pair_uncond", C.c_void_p), ("query_uncond", C.c_void_p),
         ("control_scales", C.c_void_p), ("control_scales_step", C.c_void_p), ("noise", C.c_void_p),
-        ("timesteps", C.c_void_p), ("reserved", C.c_int32 * 6),
+        ("timesteps", C.c_void_p), ("init_latents", C.c_void_p), ("mask", C.c_void_p), ("init_flags", C.c_int32),
+        ("reserved", C.c_int32 * 1),
     ]
+
+
+PD_INIT_PURE_NOISE = 1
 
 
 class pd_unipc_args(C.Structure):
@@ -560,13 +564,27 @@ class Engine:
 
     def _args(self, *, x_T, ctx_cond, ctx_uncond, pair, query, steps, cfg_scale, eta=0.0, use_cfg=True,
               guess_mode=False, only_mid_control=False, temperature=1.0, control_scales=None,
-              control_scales_step=None, noise=None, pair_uncond=None, query_uncond=None, timesteps=None):
+              control_scales_step=None, noise=None, pair_uncond=None, query_uncond=None, timesteps=None,
+              init_latents=None, mask=None, init_pure_noise=False):
+        """init_latents [B,4,h,w] (z0, already times scale_factor) turns x_T into the noise draw of img2img; mask [B,1,h,w] or
+        [1,1,h,w] (1 = repaint) adds the inpainting blend after every step; init_pure_noise starts from x_T itself
+        (pd_sample_args.init_latents / mask / init_flags)."""
+        if mask is not None:
+            B0 = x_T.shape[0]
+            if tuple(mask.shape[1:]) != (1,) + tuple(x_T.shape[2:]) or mask.shape[0] not in (1, B0):
+                raise PdError(f"mask must be [B, 1, h, w] or [1, 1, h, w] with B, h, w of x_T {tuple(x_T.shape)}, got {tuple(mask.shape)}")
+            if mask.shape[0] != B0:      # broadcast over the batch on the host side of the boundary
+                mask = mask.expand(B0, -1, -1, -1) if _is_torch(mask) else np.broadcast_to(mask, (B0,) + tuple(mask.shape[1:]))
         bufs = dict(x_T=_Buf(x_T), ctx_cond=_Buf(ctx_cond), ctx_uncond=_Buf(ctx_uncond), pair=_Buf(pair),
-                    query=_Buf(query), pair_uncond=_Buf(pair_uncond), query_uncond=_Buf(query_uncond), noise=_Buf(noise))
+                    query=_Buf(query), pair_uncond=_Buf(pair_uncond), query_uncond=_Buf(query_uncond), noise=_Buf(noise),
+                    init_latents=_Buf(init_latents), mask=_Buf(mask))
         mems = {b.mem for b in bufs.values() if b.mem is not None}
         if len(mems) != 1:
             raise PdError("all inputs must live in the same memory space (all NumPy or all CUDA tensors)")
+        if init_latents is not None and tuple(init_latents.shape) != tuple(x_T.shape):
+            raise PdError(f"init_latents must have the shape of x_T {tuple(x_T.shape)}, got {tuple(init_latents.shape)}")
         a = pd_sample_args()
+        a.init_flags = PD_INIT_PURE_NOISE if init_pure_noise else 0
         B, _, h, w = bufs["x_T"].owner.shape
         a.batch, a.h, a.w, a.steps = B, h, w, steps
         a.eta, a.cfg_scale, a.use_cfg = eta, cfg_scale, 1 if use_cfg else 0

@@ -43,6 +43,23 @@ def _to_numpy(x):
     return np.asarray(x)
 
 
+def add_noise_coefficients(cfg, timesteps):
+    """(sa, sb) = (sqrt(abar[t]), sqrt(1 - abar[t])) per entry of `timesteps`, fp32 from the engine's fp32 table -- what
+    diffusers' add_noise takes from its float32 alphas_cumprod, and what the engine's start / blend kernels use."""
+    ac = E.alphas_cumprod(cfg).astype(np.float32)[np.asarray(timesteps, np.int64)]
+    return np.sqrt(ac), np.sqrt(np.float32(1.0) - ac)
+
+
+def add_noise(z0, eps, sa, sb):
+    """diffusers' scheduler.add_noise at one timestep, fp32: sa * z0 + sb * eps."""
+    return np.float32(sa) * z0 + np.float32(sb) * eps
+
+
+def blend_latents(known, x, mask):
+    """The inpainting blend of a 4-channel UNet, fp32: (1 - m) * known + m * x (m = 1 repaints)."""
+    return (np.float32(1.0) - mask) * known + mask * x
+
+
 class PromptDiffusionPipeline:
     _callback_tensor_inputs = ["latents", "prompt_embeds", "negative_prompt_embeds"]
     vae_scale_factor = 8
@@ -197,6 +214,102 @@ class PromptDiffusionPipeline:
             latents = _to_numpy(latents).astype(np.float32)
         sigma = float(getattr(self.scheduler, "init_noise_sigma", 1.0)) if self.scheduler is not None else 1.0
         return latents * np.float32(sigma)
+
+    # ------------------------------------------------------------------ img2img / inpainting (the subclasses below)
+    def get_timesteps(self, timesteps, strength):
+        """diffusers' get_timesteps: the last min(int(S * strength), S) entries of the S-entry grid `timesteps` (sampling
+        order) and the index of the first one, which the scheduler learns through set_begin_index when it has it."""
+        S = len(timesteps)
+        init_timestep = min(int(S * strength), S)
+        t_start = max(S - init_timestep, 0)
+        order = int(getattr(self.scheduler, "order", 1)) if self.scheduler is not None else 1
+        grid = [int(t) for t in timesteps[t_start * order:]]
+        if len(grid) < 1:
+            raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of pipeline"
+                             f"steps is {len(grid)} which is < 1 and not appropriate for this pipeline.")
+        if self.scheduler is not None and hasattr(self.scheduler, "set_begin_index"):
+            self.scheduler.set_begin_index(t_start * order)
+        return grid, t_start * order
+
+    def _check_init(self, init):
+        strength = init["strength"]
+        if strength < 0 or strength > 1:
+            raise ValueError(f"The value of strength should in [0.0, 1.0] but is {strength}")
+        for key, what in (("image", "`image` (the init image)"), ("mask", "`mask_image`")):
+            im = init[key]
+            if im is None:
+                if key == "image":
+                    raise ValueError(f"{what} must be passed")
+                continue
+            items = im if isinstance(im, list) else [im]
+            if not items or not all(_is_pil(x) or E._is_torch(x) or isinstance(x, np.ndarray) for x in items):
+                raise TypeError(f"{what} must be a PIL image, numpy array, torch tensor or a list of them, but is {type(im)}")
+
+    @staticmethod
+    def _tile(x, batch_size, what):
+        """diffusers' duplication of init latents / masks to the batch: whole-batch repeats (torch .repeat)."""
+        if x.shape[0] == batch_size:
+            return x
+        if batch_size % x.shape[0] != 0:
+            raise ValueError(f"Cannot duplicate {what} of batch size {x.shape[0]} to {batch_size} images; the batch size must "
+                             "divide it.")
+        return np.tile(x, (batch_size // x.shape[0],) + (1,) * (x.ndim - 1))
+
+    def prepare_mask(self, mask_image, width, height, batch_size):
+        """diffusers' mask processor (grayscale, resize to the image size with LANCZOS, binarize at 0.5), then the
+        nearest-neighbour downsample to the latent size -- pixel (8i, 8j), F.interpolate's default -- and the duplication to the
+        batch: [batch_size, 1, height / 8, width / 8] float32.  Arrays: [H, W], [H, W, 1], [B, H, W] or [B, H, W, 1] (NumPy),
+        [H, W], [B, H, W] or [B, 1, H, W] (torch), in [0, 1] at the image size."""
+        outs = []
+        for im in (mask_image if isinstance(mask_image, list) else [mask_image]):
+            if _is_pil(im):
+                if im.size != (width, height):
+                    from PIL import Image
+                    im = im.resize((width, height), resample=Image.LANCZOS)
+                a = (np.asarray(im.convert("L"), dtype=np.float32) / 255.0)[None, None]
+            else:
+                a = _to_numpy(im).astype(np.float32)
+                if a.ndim == 2:
+                    a = a[None, None]
+                elif a.ndim == 3:
+                    a = a.transpose(2, 0, 1)[None] if isinstance(im, np.ndarray) and a.shape[-1] == 1 else a[:, None]
+                elif a.ndim == 4 and isinstance(im, np.ndarray):
+                    a = a.transpose(0, 3, 1, 2)
+                if a.ndim != 4 or a.shape[1] != 1:
+                    raise ValueError(f"mask_image must have one channel, got an array of shape {_to_numpy(im).shape}")
+            if a.shape[-2:] != (height, width):
+                raise ValueError(f"mask_image is {a.shape[-1]}x{a.shape[-2]}, the image {width}x{height}")
+            outs.append(a)
+        m = np.concatenate(outs, axis=0)
+        m = np.where(m < 0.5, np.float32(0.0), np.float32(1.0)).astype(np.float32)
+        f = self.vae_scale_factor
+        m = np.ascontiguousarray(m[:, :, ::f, ::f])
+        return self._tile(m, batch_size, "`mask_image`")
+
+    def _init_latents(self, image, width, height, batch_size, generator):
+        """z0 = scaling_factor * the init image's latents, [batch_size, 4, height / 8, width / 8]: a 4-channel `image` is taken
+        as latents; anything else is preprocessed as prepare_image does, mapped to [-1, 1] and encoded on the engine with a
+        posterior sample (vae_encode mode "sample", a standard-normal draw from `generator`)."""
+        cfg = self.engine.cfg
+        zc, f = cfg.in_channels, self.vae_scale_factor
+        lat_hw = (height // f, width // f)
+        if (E._is_torch(image) or isinstance(image, np.ndarray)) and image.ndim == 4 and image.shape[1] == zc:
+            z = _to_numpy(image).astype(np.float32)
+            if tuple(z.shape[2:]) != lat_hw:
+                raise ValueError(f"latent `image` must be [B, {zc}, {lat_hw[0]}, {lat_hw[1]}], got {tuple(z.shape)}")
+        else:
+            x = self.prepare_image(image, width, height, 1, 1)
+            if x.shape[-2:] != (height, width):
+                raise ValueError(f"`image` is {x.shape[-1]}x{x.shape[-2]}, the control image {width}x{height}")
+            if not getattr(cfg, "vae_encoder", False) or self.engine.vae_encoder_weights_missing() != 0:
+                raise ValueError("an init `image` needs the engine's VAE encoder (vae_encoder=True and the first_stage_model.encoder.* "
+                                 "/ quant_conv.* weights), or pass its latents as a 4-channel `image`")
+            x = np.ascontiguousarray(x * np.float32(2.0) - np.float32(1.0))
+            Bi = x.shape[0]
+            gen = generator[:Bi] if isinstance(generator, list) else generator
+            noise = self._randn((Bi, zc) + lat_hw, gen)
+            z = _to_numpy(self.engine.vae_encode(x, mode="sample", noise=noise)).astype(np.float32)
+        return np.ascontiguousarray(self._tile(z, batch_size, "`image`"))
 
     @staticmethod
     def _randn(shape, generator):
@@ -400,6 +513,22 @@ class PromptDiffusionPipeline:
                  control_guidance_start: Union[float, List[float]] = 0.0, control_guidance_end: Union[float, List[float]] = 1.0,
                  clip_skip: Optional[int] = None, callback_on_step_end: Optional[Callable] = None,
                  callback_on_step_end_tensor_inputs: List[str] = ["latents"], **kwargs):
+        return self._run(prompt=prompt, image=image, image_pair=image_pair, height=height, width=width,
+                         num_inference_steps=num_inference_steps, timesteps=timesteps, guidance_scale=guidance_scale,
+                         negative_prompt=negative_prompt, num_images_per_prompt=num_images_per_prompt, eta=eta, generator=generator,
+                         latents=latents, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
+                         ip_adapter_image=ip_adapter_image, output_type=output_type, return_dict=return_dict,
+                         cross_attention_kwargs=cross_attention_kwargs, controlnet_conditioning_scale=controlnet_conditioning_scale,
+                         guess_mode=guess_mode, control_guidance_start=control_guidance_start,
+                         control_guidance_end=control_guidance_end, clip_skip=clip_skip, callback_on_step_end=callback_on_step_end,
+                         callback_on_step_end_tensor_inputs=callback_on_step_end_tensor_inputs, kwargs=kwargs)
+
+    def _run(self, prompt, image, image_pair, height, width, num_inference_steps, timesteps, guidance_scale, negative_prompt,
+             num_images_per_prompt, eta, generator, latents, prompt_embeds, negative_prompt_embeds, ip_adapter_image, output_type,
+             return_dict, cross_attention_kwargs, controlnet_conditioning_scale, guess_mode, control_guidance_start,
+             control_guidance_end, clip_skip, callback_on_step_end, callback_on_step_end_tensor_inputs, kwargs, init=None):
+        """The body of __call__.  `image` is the ControlNet query.  init (img2img / inpainting, the subclasses below):
+        dict(image=init image, mask=mask image or None, strength=float); None runs the plain text-to-image loop."""
         callback = kwargs.pop("callback", None)
         callback_steps = kwargs.pop("callback_steps", None)
         if ip_adapter_image is not None:
@@ -423,6 +552,8 @@ class PromptDiffusionPipeline:
         self.check_inputs(prompt, image, image_pair, callback_steps, negative_prompt, prompt_embeds, negative_prompt_embeds,
                           controlnet_conditioning_scale, control_guidance_start, control_guidance_end,
                           callback_on_step_end_tensor_inputs)
+        if init is not None:
+            self._check_init(init)
         self._guidance_scale = guidance_scale
         if self._lora_adapters or self._lora_merged is not None:
             self._lora_sync(lora_scale)     # adapters x cross_attention_kwargs scale, in the UNet and the text transformer
@@ -442,7 +573,10 @@ class PromptDiffusionPipeline:
         query = self.prepare_image(image, width, height, batch_size * num_images_per_prompt, num_images_per_prompt)
         height, width = query.shape[-2:]
         B = batch_size * num_images_per_prompt
-        # 6. latents
+        # 6. latents (img2img / inpainting: the init image's latents first -- its posterior draw comes before the noise draw)
+        if init is not None:
+            m = self.prepare_mask(init["mask"], width, height, B) if init["mask"] is not None else None
+            z0 = self._init_latents(init["image"], width, height, B, generator)
         x_T = self.prepare_latents(B, self.engine.cfg.in_channels, height, width, generator, latents)
         # 7.2 controlnet_keep gating and per-step scales (pipeline :1196-1202, :1229-1235; controlnet :371-378)
         custom_ts = None
@@ -466,6 +600,21 @@ class PromptDiffusionPipeline:
             elif T % num_inference_steps != 0:
                 custom_ts = [int(t) for t in (np.arange(num_inference_steps) * (T // num_inference_steps))[::-1] + 1]
             n_steps = len(custom_ts) if custom_ts is not None else self.engine.num_ddim_steps(num_inference_steps)
+        t_start = 0
+        if init is not None:
+            # get_timesteps: the last int(S * strength) entries of the grid (the engine's DDIM takes them as custom timesteps)
+            if self.scheduler is not None:
+                full = [int(t) for t in self.scheduler.timesteps]
+            elif custom_ts is not None:
+                full = custom_ts
+            else:
+                full = [int(t) for t in self.engine.make_schedule(num_inference_steps)["ddim_timesteps"][::-1]]
+            grid, t_start = self.get_timesteps(full, init["strength"])
+            if self.scheduler is None:
+                custom_ts = grid
+            n_steps = len(grid)
+            sa, sb = add_noise_coefficients(self.engine.cfg, grid)
+            pure = bool(init["mask"] is not None and (init["strength"] == 1.0 or latents is not None))
         keep = [1.0 - float(i / n_steps < control_guidance_start[0] or (i + 1) / n_steps > control_guidance_end[0])
                 for i in range(n_steps)]
         n_ctl = E.PD_NUM_CONTROL
@@ -480,14 +629,24 @@ class PromptDiffusionPipeline:
                   control_scales_step=scales_step, noise=noise)
         if custom_ts is not None:
             kw["timesteps"] = custom_ts
+        host_blend = None
+        if init is not None:
+            if self.scheduler is not None and not self.fuse_scheduler:
+                # a host plug-in scheduler: the start and the per-step blend in NumPy (the engine only evaluates eps)
+                kw["x_T"] = x_T if pure else add_noise(z0, x_T, sa[0], sb[0])
+                if m is not None:
+                    host_blend = dict(z0=z0, eps=x_T, mask=m, sa=sa, sb=sb)
+            else:
+                kw.update(init_latents=z0, mask=m, init_pure_noise=pure)
         eng = self.engine
         if self.fuse_scheduler:
             # the scheduler's update inside the engine's loop: its grid, the per-step controlnet_keep scales; UniPC draws no noise
             self._check_fusable()
             sched = self.scheduler
-            kw.update(timesteps=[int(t) for t in sched.timesteps], eta=0.0, noise=None)
+            kw.update(timesteps=[int(t) for t in sched.timesteps[t_start:]], eta=0.0, noise=None)
+            # disable_corrector indexes the whole grid (as the host scheduler after set_begin_index does); the fused rows the tail
             unipc = dict(order=sched.solver_order, solver_type=sched.solver_type, lower_order_final=sched.lower_order_final,
-                         disable_corrector=list(sched.disable_corrector))
+                         disable_corrector=[d - t_start for d in sched.disable_corrector if d - t_start >= 0])
             if callback_on_step_end is None and callback is None:
                 lat = eng.unipc_sample(**kw, **unipc)
             else:
@@ -497,7 +656,7 @@ class PromptDiffusionPipeline:
             lat = eng.ddim_sample(**kw)                                  # 8. the fused loop
         else:
             lat = self._stepwise(kw, scales_step, callback_on_step_end, callback_on_step_end_tensor_inputs, callback,
-                                 callback_steps, pe, ne, eta, generator)
+                                 callback_steps, pe, ne, eta, generator, t_start=t_start, host_blend=host_blend)
         # 9. post-processing (pipeline :1298-1321); safety checker is forced off there too
         if output_type == "latent":
             images = lat
@@ -520,7 +679,8 @@ class PromptDiffusionPipeline:
         return StableDiffusionPipelineOutput(images=images, nsfw_content_detected=None)
 
     # ------------------------------------------------------------------ per-step driver (callbacks / plug-in schedulers)
-    def _stepwise(self, kw, scales_step, cb_end, cb_inputs, cb_legacy, cb_steps, pe, ne, eta, generator, unipc=None):
+    def _stepwise(self, kw, scales_step, cb_end, cb_inputs, cb_legacy, cb_steps, pe, ne, eta, generator, unipc=None, t_start=0,
+                  host_blend=None):
         eng = self.engine
         sched = self.scheduler
         if unipc is not None:       # fused UniPC: the engine steps on the scheduler's grid (kw["timesteps"])
@@ -533,7 +693,7 @@ class PromptDiffusionPipeline:
         else:
             n = eng.sample_begin(**kw)
         if sched is not None:
-            ts = [int(t) for t in sched.timesteps]       # set_timesteps ran in __call__
+            ts = [int(t) for t in sched.timesteps[t_start:]]     # set_timesteps (and set_begin_index) ran in __call__
             extra = {}
             params = set(inspect.signature(sched.step).parameters.keys())
             if "eta" in params:
@@ -555,7 +715,12 @@ class PromptDiffusionPipeline:
                 cur = eng.sample_get(E.PD_GET_LATENTS)
                 out = sched.step(torch.from_numpy(np.asarray(noise_pred)), t, torch.from_numpy(np.asarray(cur)), **extra,
                                  return_dict=False)[0]
-                eng.sample_set_latents(out.numpy())
+                out = out.numpy()
+                if host_blend is not None:      # inpainting: the known region back at the next step's noise level
+                    hb = host_blend
+                    known = hb["z0"] if i == len(ts) - 1 else add_noise(hb["z0"], hb["eps"], hb["sa"][i + 1], hb["sb"][i + 1])
+                    out = blend_latents(known, out, hb["mask"])
+                eng.sample_set_latents(out)
             if cb_end is not None:
                 lat = eng.sample_get(E.PD_GET_LATENTS)
                 cb_kwargs = {}
@@ -570,3 +735,69 @@ class PromptDiffusionPipeline:
         lat = eng.sample_get(E.PD_GET_LATENTS)
         eng.sample_end()
         return lat
+
+
+class PromptDiffusionImg2ImgPipeline(PromptDiffusionPipeline):
+    """Img2img with Prompt-Diffusion's ControlNet, under diffusers' StableDiffusionControlNetImg2ImgPipeline naming: `image` is
+    the init image (or its 4-channel latents), `control_image` the query, `image_pair` the example pair.  The loop runs the
+    last int(S * strength) steps of the grid from add_noise(z0, eps, t_first) -- strength 1 included.  A given `latents` is
+    taken as that noise draw eps (diffusers ignores it).  Everything else is PromptDiffusionPipeline.__call__."""
+
+    def __call__(self, prompt: Union[str, List[str]] = None, image=None, control_image=None, image_pair: List = None,
+                 height: Optional[int] = None, width: Optional[int] = None, strength: float = 0.8, num_inference_steps: int = 50,
+                 timesteps: List[int] = None, guidance_scale: float = 7.5,
+                 negative_prompt: Optional[Union[str, List[str]]] = None, num_images_per_prompt: Optional[int] = 1,
+                 eta: float = 0.0, generator=None, latents=None, prompt_embeds=None, negative_prompt_embeds=None,
+                 ip_adapter_image=None, output_type: Optional[str] = "pil", return_dict: bool = True,
+                 cross_attention_kwargs: Optional[Dict[str, Any]] = None,
+                 controlnet_conditioning_scale: Union[float, List[float]] = 1.0, guess_mode: bool = False,
+                 control_guidance_start: Union[float, List[float]] = 0.0, control_guidance_end: Union[float, List[float]] = 1.0,
+                 clip_skip: Optional[int] = None, callback_on_step_end: Optional[Callable] = None,
+                 callback_on_step_end_tensor_inputs: List[str] = ["latents"], **kwargs):
+        return self._run(prompt=prompt, image=control_image, image_pair=image_pair, height=height, width=width,
+                         num_inference_steps=num_inference_steps, timesteps=timesteps, guidance_scale=guidance_scale,
+                         negative_prompt=negative_prompt, num_images_per_prompt=num_images_per_prompt, eta=eta, generator=generator,
+                         latents=latents, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
+                         ip_adapter_image=ip_adapter_image, output_type=output_type, return_dict=return_dict,
+                         cross_attention_kwargs=cross_attention_kwargs, controlnet_conditioning_scale=controlnet_conditioning_scale,
+                         guess_mode=guess_mode, control_guidance_start=control_guidance_start,
+                         control_guidance_end=control_guidance_end, clip_skip=clip_skip, callback_on_step_end=callback_on_step_end,
+                         callback_on_step_end_tensor_inputs=callback_on_step_end_tensor_inputs, kwargs=kwargs,
+                         init=dict(image=image, mask=None, strength=strength))
+
+
+class PromptDiffusionInpaintPipeline(PromptDiffusionPipeline):
+    """Inpainting with Prompt-Diffusion's ControlNet and the 4-channel UNet, under diffusers'
+    StableDiffusionControlNetInpaintPipeline naming: `image` is the init image (or its 4-channel latents), `mask_image` the
+    region to repaint (white = 1 = repaint, binarized at 0.5), `control_image` the query.  After every step the kept region is
+    put back at the next step's noise level (z0 itself after the last step); the loop starts from pure noise at strength 1 (or
+    from a given `latents`, which is also the noise draw), from add_noise(z0, eps, t_first) otherwise.  Not built: 9-channel
+    inpainting UNets (masked_image_latents) and padding_mask_crop."""
+
+    def __call__(self, prompt: Union[str, List[str]] = None, image=None, mask_image=None, control_image=None,
+                 image_pair: List = None, height: Optional[int] = None, width: Optional[int] = None, strength: float = 1.0,
+                 num_inference_steps: int = 50, timesteps: List[int] = None, guidance_scale: float = 7.5,
+                 negative_prompt: Optional[Union[str, List[str]]] = None, num_images_per_prompt: Optional[int] = 1,
+                 eta: float = 0.0, generator=None, latents=None, prompt_embeds=None, negative_prompt_embeds=None,
+                 ip_adapter_image=None, output_type: Optional[str] = "pil", return_dict: bool = True,
+                 cross_attention_kwargs: Optional[Dict[str, Any]] = None,
+                 controlnet_conditioning_scale: Union[float, List[float]] = 1.0, guess_mode: bool = False,
+                 control_guidance_start: Union[float, List[float]] = 0.0, control_guidance_end: Union[float, List[float]] = 1.0,
+                 clip_skip: Optional[int] = None, callback_on_step_end: Optional[Callable] = None,
+                 callback_on_step_end_tensor_inputs: List[str] = ["latents"], **kwargs):
+        if kwargs.get("padding_mask_crop") is not None or kwargs.get("masked_image_latents") is not None:
+            raise NotImplementedError("padding_mask_crop / masked_image_latents (9-channel inpainting UNets) are not supported")
+        kwargs.pop("padding_mask_crop", None)
+        kwargs.pop("masked_image_latents", None)
+        if mask_image is None:
+            raise ValueError("`mask_image` must be passed")
+        return self._run(prompt=prompt, image=control_image, image_pair=image_pair, height=height, width=width,
+                         num_inference_steps=num_inference_steps, timesteps=timesteps, guidance_scale=guidance_scale,
+                         negative_prompt=negative_prompt, num_images_per_prompt=num_images_per_prompt, eta=eta, generator=generator,
+                         latents=latents, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
+                         ip_adapter_image=ip_adapter_image, output_type=output_type, return_dict=return_dict,
+                         cross_attention_kwargs=cross_attention_kwargs, controlnet_conditioning_scale=controlnet_conditioning_scale,
+                         guess_mode=guess_mode, control_guidance_start=control_guidance_start,
+                         control_guidance_end=control_guidance_end, clip_skip=clip_skip, callback_on_step_end=callback_on_step_end,
+                         callback_on_step_end_tensor_inputs=callback_on_step_end_tensor_inputs, kwargs=kwargs,
+                         init=dict(image=image, mask=mask_image, strength=strength))

@@ -102,6 +102,15 @@ class UniPCMultistepScheduler:
         self.num_inference_steps = n
         self._reset()
 
+    def set_begin_index(self, begin_index: int = 0):
+        """diffusers' set_begin_index: after set_timesteps, stepping starts at timesteps[begin_index] with fresh solver state
+        (img2img / inpainting run the tail of the grid).  disable_corrector keeps indexing the whole grid."""
+        k = int(begin_index)
+        if not 0 <= k < len(self.timesteps):
+            raise ValueError(f"begin_index {k} outside the {len(self.timesteps)} timesteps")
+        self._reset()
+        self._step_index = k
+
     def scale_model_input(self, sample, timestep=None):
         return sample
 
