@@ -1,4 +1,4 @@
-// Layout conversion, concat, CFG + DDIM / UniPC update and device-side weight initialisation (gfx950).
+// Layout conversion, concat and device-side weight initialisation (gfx950).
 // All of these are HBM-trivial next to the contractions; they exist to keep the whole denoising loop
 // on the device with no host round trip per step.
 #include "../../include/pdengine.h"
@@ -160,110 +160,6 @@ __global__ void add_inplace_kernel(void* __restrict__ a, const void* __restrict_
     }
 }
 
-// Classifier-free guidance + DDIM update, DDIMSampler.p_sample_ddim (cldm/ddim_hacked.py:193,218,229-233),
-// in the reference's own fp32 operation order (no FMA contraction).
-//   eps      [Bf, HW, eps_C] fp32/bf16: UNet output, uncond half first (ddim_hacked.py:189-192)
-//   x_state  [B, HW, Cpad] fp32 (channels >= C are zero)    -> updated in place
-//   x_in     [dup*B, HW, Cpad]: the CFG-duplicated latents the next step's conv_in reads
-__global__ void cfg_ddim_kernel(const void* __restrict__ eps, int eps_dt, int eps_C, float* __restrict__ x_state,
-                                float* __restrict__ pred_x0, float* __restrict__ eps_guided, void* __restrict__ x_in,
-                                int x_in_dt, const float* __restrict__ noise, int B, int HW, int C, int Cpad, int use_cfg,
-                                DdimCoef k, float temperature, int do_update) {
-    const long long total = (long long)B * HW * C;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int c = (int)(i % C);
-        const long long bp = i / C;
-        const int p = (int)(bp % HW);
-        const int b = (int)(bp / HW);
-        auto ld = [&](long long j) {
-            return eps_dt == DT_F32 ? reinterpret_cast<const float*>(eps)[j] : cvt32_rt(reinterpret_cast<const uint16_t*>(eps)[j], eps_dt);
-        };
-        float e;
-        if (use_cfg) {
-            const float eu = ld(((long long)b * HW + p) * eps_C + c);
-            const float ec = ld(((long long)(B + b) * HW + p) * eps_C + c);
-            e = __fadd_rn(eu, __fmul_rn(k.cfg_scale, __fsub_rn(ec, eu)));
-        } else {
-            e = ld(((long long)b * HW + p) * eps_C + c);
-        }
-        eps_guided[i] = e;
-        if (!do_update) continue;
-        const long long xi = ((long long)b * HW + p) * Cpad + c;
-        const float x = x_state[xi];
-        const float pred = __fdiv_rn(__fsub_rn(x, __fmul_rn(k.sqrt_one_minus_at, e)), k.sqrt_at);
-        const float dir = __fmul_rn(k.dir_coef, e);
-        float xp = __fadd_rn(__fmul_rn(k.sqrt_a_prev, pred), dir);
-        if (noise) {
-            const float nz = __fmul_rn(__fmul_rn(k.sigma, noise[((long long)b * C + c) * HW + p]), temperature);
-            xp = __fadd_rn(xp, nz);
-        }
-        pred_x0[i] = pred;
-        x_state[xi] = xp;
-        if (x_in_dt == DT_F32) {
-            float* xo = reinterpret_cast<float*>(x_in);
-            xo[xi] = xp;
-            if (use_cfg) xo[(long long)B * HW * Cpad + xi] = xp;
-        } else {
-            uint16_t* xo = reinterpret_cast<uint16_t*>(x_in);
-            xo[xi] = cvt16_rt(xp, x_in_dt);
-            if (use_cfg) xo[(long long)B * HW * Cpad + xi] = cvt16_rt(xp, x_in_dt);
-        }
-    }
-}
-
-// Classifier-free guidance + one fused UniPC step (data prediction, UniP predictor + UniC corrector; coefficient layout in
-// include/pdengine.h).  The guided eps is cfg_ddim_kernel's, bit for bit; the solver state is fp64 like the host scheduler's
-// (model_outputs / last_sample), and only the returned sample is rounded to fp32, where the scheduler rounds it.
-//   last, m_out, h1..h3  [B, HW, C] fp64, index i; m_out may alias one of h1..h3 (each element is read before it is written)
-__global__ void cfg_unipc_kernel(const void* __restrict__ eps, int eps_dt, int eps_C, float* __restrict__ x_state,
-                                 float* __restrict__ pred_x0, float* __restrict__ eps_guided, void* __restrict__ x_in,
-                                 int x_in_dt, int B, int HW, int C, int Cpad, int use_cfg, UnipcCoef k, double* __restrict__ last,
-                                 double* m_out, const double* h1, const double* h2, const double* h3) {
-    const long long total = (long long)B * HW * C;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int c = (int)(i % C);
-        const long long bp = i / C;
-        const int p = (int)(bp % HW);
-        const int b = (int)(bp / HW);
-        auto ld = [&](long long j) {
-            return eps_dt == DT_F32 ? reinterpret_cast<const float*>(eps)[j] : cvt32_rt(reinterpret_cast<const uint16_t*>(eps)[j], eps_dt);
-        };
-        float e;
-        if (use_cfg) {
-            const float eu = ld(((long long)b * HW + p) * eps_C + c);
-            const float ec = ld(((long long)(B + b) * HW + p) * eps_C + c);
-            e = __fadd_rn(eu, __fmul_rn(k.cfg_scale, __fsub_rn(ec, eu)));
-        } else {
-            e = ld(((long long)b * HW + p) * eps_C + c);
-        }
-        eps_guided[i] = e;
-        const long long xi = ((long long)b * HW + p) * Cpad + c;
-        const double x = (double)x_state[xi];
-        // m_i = (x - sigma e) / alpha, in the scheduler's operation order
-        const double m = __ddiv_rn(__dsub_rn(x, __dmul_rn(k.sigma, (double)e)), k.alpha);
-        const double m1 = k.n_hist > 0 ? h1[i] : 0.0;
-        const double m2 = k.n_hist > 1 ? h2[i] : 0.0;
-        const double m3 = k.n_hist > 2 ? h3[i] : 0.0;
-        double xc = x;
-        if (k.corr) xc = k.c_last * last[i] + k.c_m[0] * m + k.c_m[1] * m1 + k.c_m[2] * m2 + k.c_m[3] * m3;
-        const double xn = k.p_x * xc + k.p_m[0] * m + k.p_m[1] * m1 + k.p_m[2] * m2;
-        last[i] = xc;
-        m_out[i] = m;
-        const float xp = (float)xn;
-        pred_x0[i] = (float)m;
-        x_state[xi] = xp;
-        if (x_in_dt == DT_F32) {
-            float* xo = reinterpret_cast<float*>(x_in);
-            xo[xi] = xp;
-            if (use_cfg) xo[(long long)B * HW * Cpad + xi] = xp;
-        } else {
-            uint16_t* xo = reinterpret_cast<uint16_t*>(x_in);
-            xo[xi] = cvt16_rt(xp, x_in_dt);
-            if (use_cfg) xo[(long long)B * HW * Cpad + xi] = cvt16_rt(xp, x_in_dt);
-        }
-    }
-}
-
 // x_in[d*B + b] = x_state[b] for d < dup   (torch.cat([x]*2), ddim_hacked.py:189)
 __global__ void dup_rows_kernel(const float* __restrict__ x_state, float* __restrict__ x_in, long long n, int dup) {
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
@@ -341,27 +237,7 @@ int launch_add_inplace(void* a, const void* b, int dt, long long n, hipStream_t 
     hipLaunchKernelGGL(add_inplace_kernel, dim3(nblocks(n / 4, TPB, 8192)), dim3(TPB), 0, s, a, b, dt, n / 4);
     CHECK_LAUNCH();
 }
-int launch_cfg_ddim(const void* eps, int eps_dt, int eps_C, float* x_state, float* pred_x0, float* eps_guided, void* x_in,
-                    const float* noise, int B, int HW, int C, int Cpad, int use_cfg, DdimCoef k, float temperature,
-                    int do_update, hipStream_t s) {
-    const long long n = (long long)B * HW * C;
-    hipLaunchKernelGGL(cfg_ddim_kernel, dim3(nblocks(n)), dim3(TPB), 0, s, eps, eps_dt, eps_C, x_state, pred_x0, eps_guided,
-                       x_in, (int)DT_F32, noise, B, HW, C, Cpad, use_cfg, k, temperature, do_update);
-    CHECK_LAUNCH();
-}
-int launch_cfg_unipc(const void* eps, int eps_dt, int eps_C, float* x_state, float* pred_x0, float* eps_guided, void* x_in,
-                     int B, int HW, int C, int Cpad, int use_cfg, const UnipcCoef& k, double* last, double* m_out,
-                     const double* const hist[3], hipStream_t s) {
-    if (k.n_hist < 0 || k.n_hist > 3 || !last || !m_out) return 1;
-    for (int j = 0; j < k.n_hist; ++j)
-        if (!hist[j]) return 1;
-    const long long n = (long long)B * HW * C;
-    hipLaunchKernelGGL(cfg_unipc_kernel, dim3(nblocks(n)), dim3(TPB), 0, s, eps, eps_dt, eps_C, x_state, pred_x0, eps_guided,
-                       x_in, (int)DT_F32, B, HW, C, Cpad, use_cfg, k, last, m_out, hist[0], hist[1], hist[2]);
-    CHECK_LAUNCH();
-}
-int launch_fill_x_in(const float* x_state, float* x_in, int B, int dup, int C, int Cpad, int HW, hipStream_t s) {
-    (void)C;
+int launch_fill_x_in(const float* x_state, float* x_in, int B, int dup, int Cpad, int HW, hipStream_t s) {
     const long long n = (long long)B * HW * Cpad;
     hipLaunchKernelGGL(dup_rows_kernel, dim3(nblocks(n)), dim3(TPB), 0, s, x_state, x_in, n, dup);
     CHECK_LAUNCH();

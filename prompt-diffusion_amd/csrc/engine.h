@@ -503,12 +503,14 @@ struct pd_engine {
     int forward_eps(int emb_row, int emb_stride, const float* scales, Act& eps);
 
     // sessions
-    int ensure_arena(int Bf, int h, int w, int rows, bool per_step);
-    int session_setup(const pd_sample_args& a, const int64_t* t_rows, int n_rows, bool per_sample_t, bool want_per_step);
+    int ensure_arena(int rows, bool per_step);
+    int session_setup(const pd_sample_args& a, const int64_t* t_rows, int n_rows, bool want_per_step);
     int compute_emb(NetW& net, std::vector<float*>& tabs, const int64_t* t, int n, int row0);
     int begin(const pd_sample_args* a, bool want_per_step, const pd_unipc_args* u = nullptr);
-    int step(int i);
-    int step_unipc(int i, const Act& eps);
+    int step(int i);   // eps, then the solver's update launch (step_ddim / step_unipc), then the optional per-step copy
+    UpdateState update_state(const Act& eps) const;
+    int step_ddim(int i, const UpdateState& u, const BlendArgs* bl);
+    int step_unipc(int i, const UpdateState& u, const BlendArgs* bl);
     int make_schedule(int steps, float eta, std::vector<int64_t>& ts, std::vector<float>& a, std::vector<float>& ap,
                       std::vector<float>& sg, std::vector<float>& s1m, const int64_t* custom_desc = nullptr);
 };

@@ -297,34 +297,35 @@ int launch_add_inplace(void* a, const void* b, int dt, long long n, hipStream_t 
 // half passed through fourier_filter(threshold 1, scale s) per (sample, channel) plane; rows = B * H * W
 int launch_freeu_concat(const void* h, const void* h_add, const void* skip, const void* skip_add, void* out, int dt, int B, int H,
                         int W, int Ch, int Cs, float s, float b, hipStream_t st, long long skip_rows = 0, long long skip_add_rows = 0);
+// The end of a denoising step (sampler_update.hip): guidance + solver update (+ inpainting blend) + the next step's x_in.
+// What every update launch of a session shares: the UNet's eps [Bf, HW, eps_C] (uncond half first) in eps_dt, x_state
+// [B, HW, Cpad] fp32 updated in place, pred_x0 / eps_guided [B, HW, C] fp32, x_in [dup * B, HW, Cpad] fp32.
+struct UpdateState {
+    const void* eps; int eps_dt, eps_C;
+    float* x_state; float* pred_x0; float* eps_guided; float* x_in;
+    int B, HW, C, Cpad, use_cfg;
+};
+// img2img / inpainting (semantics in include/pdengine.h, pd_sample_args.init_latents / mask).  z0, ieps: [B, C, HW] fp32 NCHW;
+// mask: [B, HW].  The blend (1 - m) k + m x, k = last ? z0 : sa z0 + sb eps, is evaluated in fp32 without contraction and
+// applied to the updated sample before x_state / x_in are written.
+struct BlendCoef { float sa, sb; int last; };
+struct BlendArgs { const float* z0; const float* ieps; const float* mask; BlendCoef coef; };
 struct DdimCoef { float sqrt_one_minus_at, sqrt_at, sqrt_a_prev, dir_coef, sigma, cfg_scale; };
-int launch_cfg_ddim(const void* eps, int eps_dt, int eps_C, float* x_state, float* pred_x0, float* eps_guided,
-                    void* x_in, const float* noise, int B, int HW, int C, int Cpad, int use_cfg, DdimCoef k,
-                    float temperature, int do_update, hipStream_t s);
+// do_update 0: only eps_guided is written; bl null: no blend
+int launch_cfg_ddim(const UpdateState& u, const DdimCoef& k, const float* noise, float temperature, int do_update, const BlendArgs* bl,
+                    hipStream_t s);
 // Fused UniPC step (include/pdengine.h, PD_UNIPC_NCOEF): one coefficient row, passed by value so a captured graph bakes it in.
 //   c_m[0..3]: corrector weights of m_i, m_{i-1}, m_{i-2}, m_{i-3}; p_m[0..2]: predictor weights of m_i, m_{i-1}, m_{i-2};
 //   n_hist: how many of the history slots m_{i-1}, m_{i-2}, m_{i-3} the step reads (the others may be null)
 struct UnipcCoef { double alpha, sigma, c_last, c_m[4], p_x, p_m[3]; int corr, n_hist; float cfg_scale; };
 // last [B, HW, C] fp64: corrected sample of the previous step (rewritten); m_out [B, HW, C] fp64: m_i (may alias hist[n_hist-1],
-// which is read first); x_state / pred_x0 / eps_guided / x_in as in launch_cfg_ddim
-int launch_cfg_unipc(const void* eps, int eps_dt, int eps_C, float* x_state, float* pred_x0, float* eps_guided, void* x_in,
-                     int B, int HW, int C, int Cpad, int use_cfg, const UnipcCoef& k, double* last, double* m_out,
-                     const double* const hist[3], hipStream_t s);
-// img2img / inpainting (inpaint.hip; semantics in include/pdengine.h, pd_sample_args.init_latents / mask).  z0, eps: [B, C, HW]
-// fp32 NCHW; mask: [B, HW].  The blend (1 - m) k + m x, k = last ? z0 : sa z0 + sb eps, is evaluated in fp32 without contraction.
-struct BlendCoef { float sa, sb; int last; };
+// which is read first)
+int launch_cfg_unipc(const UpdateState& u, const UnipcCoef& k, double* last, double* m_out, const double* const hist[3],
+                     const BlendArgs* bl, hipStream_t s);
 // start latents: x = pure ? eps : sa z0 + sb eps -> x_state [B, HW, Cpad] (channels >= C zero), x_in (dup copies), and
 // optionally out_nchw [B, C, HW]
 int launch_init_latents(const float* z0, const float* eps, float sa, float sb, int pure, float* x_state, float* x_in, float* out_nchw,
                         int B, int dup, int C, int Cpad, int HW, hipStream_t s);
-// launch_cfg_ddim / launch_cfg_unipc (do_update 1) with the blend applied to the updated sample before x_state / x_in are written
-int launch_cfg_ddim_blend(const void* eps, int eps_dt, int eps_C, float* x_state, float* pred_x0, float* eps_guided, void* x_in,
-                          const float* noise, int B, int HW, int C, int Cpad, int use_cfg, DdimCoef k, float temperature,
-                          const float* z0, const float* ieps, const float* mask, BlendCoef bc, hipStream_t s);
-int launch_cfg_unipc_blend(const void* eps, int eps_dt, int eps_C, float* x_state, float* pred_x0, float* eps_guided, void* x_in,
-                           int B, int HW, int C, int Cpad, int use_cfg, const UnipcCoef& k, double* last, double* m_out,
-                           const double* const hist[3], const float* z0, const float* ieps, const float* mask, BlendCoef bc,
-                           hipStream_t s);
 int launch_fill_random(void* p, int dt, long long n, float scale, float shift, uint64_t seed, hipStream_t s);
 // LoRA merge (lora.hip) of one matrix parameter: W rows = round_dt(W0 + (scale . UT)^T D); UT [R][rows], D [R][Kpad] fp32,
 // scale [R]; source row n -> WMat row row_off + n, or the 80 + 80 GEGLU interleave when geglu_half > 0 (row_off 0); W0 holds the
@@ -354,4 +355,5 @@ int launch_timestep_embedding(const float* t_host, int B, float* out, hipStream_
 int launch_pos_crop(const float* table, float* out, int B, int h, int w, int max_size, int D, hipStream_t s);
 int launch_unpatchify(const void* in, int in_dt, int ld, float* nchw, int B, int C, int h, int w, int patch, hipStream_t s);
 int launch_cfg_euler(const float* v, float* x, int B, long long n, float guidance, float dsigma, int use_cfg, hipStream_t s);
-int launch_fill_x_in(const float* x_state_nchw, float* x_in, int B, int dup, int C, int Cpad, int HW, hipStream_t s);
+// x_in[d * B + b] = x_state[b] for d < dup, both [., HW, Cpad] fp32
+int launch_fill_x_in(const float* x_state, float* x_in, int B, int dup, int Cpad, int HW, hipStream_t s);

@@ -1,0 +1,170 @@
+// The end of a denoising step, elementwise over the B x HW x C latents (gfx950): classifier-free guidance, the solver's update
+// (DDIM or fused UniPC), the optional inpainting blend, and the store of the new sample for the next step -- plus the start of
+// an img2img / inpainting session (pd_sample_args.init_latents / mask, include/pdengine.h).  Each piece of arithmetic exists
+// once: the index decomposition, the guidance and the stores in the one kernel template, the two solvers and the blend as
+// __device__ functions it calls; the four kernels are its instantiations over the solver and a compile-time "blend or not".
+//   eps      [Bf, HW, eps_C] fp32 / 16-bit: UNet output, uncond half first (ddim_hacked.py:189-192)
+//   x_state  [B, HW, Cpad] fp32 (channels >= C are zero)    -> updated in place
+//   x_in     [dup*B, HW, Cpad] fp32: the CFG-duplicated latents the next step's conv_in reads
+//   pred_x0, eps_guided  [B, HW, C] fp32, index i
+// z0 / eps / the noise draws of img2img and inpainting are NCHW fp32 (the caller's layout), the mask [B, HW].  With a blend,
+// only x_state and x_in receive the blended value; pred_x0, the guided eps and the UniPC fp64 state (last, the x0 ring) are the
+// update's own.
+#include "../../include/pdengine.h"
+#include "pd_common.h"
+
+namespace {
+
+constexpr int TPB = 256;
+inline int nblocks(long long n, int per = TPB, int cap = 65535 * 16) {
+    long long b = (n + per - 1) / per;
+    if (b < 1) b = 1;
+    if (b > cap) b = cap;
+    return (int)b;
+}
+
+// The solvers: what differs between the kernels.  update() takes the sample x and the guided eps e of element i (NCHW index j),
+// stores pred_x0[i] and its own state, and returns the new sample.
+
+// DDIMSampler.p_sample_ddim (cldm/ddim_hacked.py:218,229-233) in the reference's own fp32 operation order (no FMA contraction).
+// do_update 0: the kernel stops after the guided eps (pd_sample_eps_at).
+struct DdimSolver {
+    DdimCoef k; const float* __restrict__ noise; float temperature; int do_update;
+    __device__ __forceinline__ bool active() const { return do_update != 0; }
+    __device__ __forceinline__ float update(float x, float e, long long i, long long j, float* __restrict__ pred_x0) const {
+        const float pred = __fdiv_rn(__fsub_rn(x, __fmul_rn(k.sqrt_one_minus_at, e)), k.sqrt_at);
+        const float dir = __fmul_rn(k.dir_coef, e);
+        float xp = __fadd_rn(__fmul_rn(k.sqrt_a_prev, pred), dir);
+        if (noise) {
+            const float nz = __fmul_rn(__fmul_rn(k.sigma, noise[j]), temperature);
+            xp = __fadd_rn(xp, nz);
+        }
+        pred_x0[i] = pred;
+        return xp;
+    }
+};
+
+// One fused UniPC step (data prediction, UniP predictor + UniC corrector; coefficient layout in include/pdengine.h).  The solver
+// state is fp64 like the host scheduler's (model_outputs / last_sample), and only the returned sample is rounded to fp32, where
+// the scheduler rounds it.  The corrector and predictor sums are plain fp64 expressions that the compiler contracts into FMAs:
+// their operand order and parentheses decide the last bit of the state, so they stay exactly as written.
+//   last, m_out, h1..h3  [B, HW, C] fp64, index i; m_out may alias one of h1..h3 (each element is read before it is written);
+//   last receives the corrected sample from before any blend (the scheduler's last_sample)
+struct UnipcSolver {
+    UnipcCoef k; double* __restrict__ last; double* m_out; const double* h1; const double* h2; const double* h3;
+    __device__ __forceinline__ bool active() const { return true; }
+    __device__ __forceinline__ float update(float xf, float e, long long i, long long, float* __restrict__ pred_x0) const {
+        const double x = (double)xf;
+        // m_i = (x - sigma e) / alpha, in the scheduler's operation order
+        const double m = __ddiv_rn(__dsub_rn(x, __dmul_rn(k.sigma, (double)e)), k.alpha);
+        const double m1 = k.n_hist > 0 ? h1[i] : 0.0;
+        const double m2 = k.n_hist > 1 ? h2[i] : 0.0;
+        const double m3 = k.n_hist > 2 ? h3[i] : 0.0;
+        double xc = x;
+        if (k.corr) xc = k.c_last * last[i] + k.c_m[0] * m + k.c_m[1] * m1 + k.c_m[2] * m2 + k.c_m[3] * m3;
+        const double xn = k.p_x * xc + k.p_m[0] * m + k.p_m[1] * m1 + k.p_m[2] * m2;
+        last[i] = xc;
+        m_out[i] = m;
+        pred_x0[i] = (float)m;
+        return (float)xn;
+    }
+};
+
+// inpainting: (1 - m) k + m x, k = last ? z0 : sa z0 + sb eps (at the next step's timestep), at NCHW index j and mask index bp.
+// Every operation is a separately rounded fp32 operation (no FMA contraction), so a NumPy fp32 blend of the same sample gives
+// the same bits.
+__device__ __forceinline__ float blend(float x, const BlendArgs& bl, long long j, long long bp) {
+    const float z = bl.z0[j];
+    const float k = bl.coef.last ? z : __fadd_rn(__fmul_rn(bl.coef.sa, z), __fmul_rn(bl.coef.sb, bl.ieps[j]));
+    const float m = bl.mask[bp];
+    return __fadd_rn(__fmul_rn(__fsub_rn(1.0f, m), k), __fmul_rn(m, x));
+}
+
+// The one update kernel: guided eps (eps_uncond + scale (eps_cond - eps_uncond), ddim_hacked.py:193) -> eps_guided, the solver's
+// update, the blend where BLEND (compile-time: the plain instantiations carry nothing of it), and the new sample -> x_state, x_in
+// and x_in's CFG half.
+template <class Solver, bool BLEND>
+__global__ void cfg_update_kernel(UpdateState u, Solver s, BlendArgs bl) {
+    const auto& k = s.k;
+    const long long total = (long long)u.B * u.HW * u.C;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int c = (int)(i % u.C);
+        const long long bp = i / u.C;
+        const int p = (int)(bp % u.HW);
+        const int b = (int)(bp / u.HW);
+        auto ld = [&](long long q) {
+            return u.eps_dt == DT_F32 ? reinterpret_cast<const float*>(u.eps)[q] : cvt32_rt(reinterpret_cast<const uint16_t*>(u.eps)[q], u.eps_dt);
+        };
+        float e;
+        if (u.use_cfg) {
+            const float eu = ld(((long long)b * u.HW + p) * u.eps_C + c);
+            const float ec = ld(((long long)(u.B + b) * u.HW + p) * u.eps_C + c);
+            e = __fadd_rn(eu, __fmul_rn(k.cfg_scale, __fsub_rn(ec, eu)));
+        } else {
+            e = ld(((long long)b * u.HW + p) * u.eps_C + c);
+        }
+        u.eps_guided[i] = e;
+        if (!s.active()) continue;
+        const long long xi = ((long long)b * u.HW + p) * u.Cpad + c;   // NHWC index in x_state / x_in
+        const long long j = ((long long)b * u.C + c) * u.HW + p;       // NCHW index in noise / z0 / the img2img eps
+        float xp = s.update(u.x_state[xi], e, i, j, u.pred_x0);
+        if constexpr (BLEND) xp = blend(xp, bl, j, bp);
+        u.x_state[xi] = xp;
+        u.x_in[xi] = xp;
+        if (u.use_cfg) u.x_in[(long long)u.B * u.HW * u.Cpad + xi] = xp;
+    }
+}
+
+template <class Solver> int launch_update(const UpdateState& u, const Solver& sv, const BlendArgs* bl, hipStream_t s) {
+    if (bl && !(bl->z0 && bl->ieps && bl->mask)) return 1;
+    const dim3 grid(nblocks((long long)u.B * u.HW * u.C));
+    if (bl) hipLaunchKernelGGL((cfg_update_kernel<Solver, true>), grid, dim3(TPB), 0, s, u, sv, *bl);
+    else hipLaunchKernelGGL((cfg_update_kernel<Solver, false>), grid, dim3(TPB), 0, s, u, sv, BlendArgs{});
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+// the start of an img2img / inpainting session: x = pure ? eps : sa z0 + sb eps, replacing nchw_to_nhwc + dup_rows of a plain one
+//   x_state [B, HW, Cpad], x_in [dup * B, HW, Cpad], out_nchw [B, C, HW] (optional)
+__global__ void init_latents_kernel(const float* __restrict__ z0, const float* __restrict__ eps, float sa, float sb, int pure,
+                                    float* __restrict__ x_state, float* __restrict__ x_in, float* __restrict__ out_nchw, int B,
+                                    int dup, int C, int Cpad, int HW) {
+    const long long n = (long long)B * HW * Cpad;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const int c = (int)(i % Cpad);
+        const long long bp = i / Cpad;
+        const int p = (int)(bp % HW);
+        const int b = (int)(bp / HW);
+        float v = 0.f;
+        if (c < C) {
+            const long long j = ((long long)b * C + c) * HW + p;
+            v = pure ? eps[j] : __fadd_rn(__fmul_rn(sa, z0[j]), __fmul_rn(sb, eps[j]));
+            if (out_nchw) out_nchw[j] = v;
+        }
+        x_state[i] = v;
+        for (int d = 0; d < dup; ++d) x_in[(long long)d * n + i] = v;
+    }
+}
+
+}  // namespace
+
+int launch_init_latents(const float* z0, const float* eps, float sa, float sb, int pure, float* x_state, float* x_in, float* out_nchw,
+                        int B, int dup, int C, int Cpad, int HW, hipStream_t s) {
+    if (!eps || (!pure && !z0) || C > Cpad || dup < 1) return 1;
+    const long long n = (long long)B * HW * Cpad;
+    hipLaunchKernelGGL(init_latents_kernel, dim3(nblocks(n)), dim3(TPB), 0, s, z0, eps, sa, sb, pure, x_state, x_in, out_nchw, B, dup,
+                       C, Cpad, HW);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+int launch_cfg_ddim(const UpdateState& u, const DdimCoef& k, const float* noise, float temperature, int do_update, const BlendArgs* bl,
+                    hipStream_t s) {
+    return launch_update(u, DdimSolver{k, noise, temperature, do_update}, bl, s);
+}
+
+int launch_cfg_unipc(const UpdateState& u, const UnipcCoef& k, double* last, double* m_out, const double* const hist[3],
+                     const BlendArgs* bl, hipStream_t s) {
+    if (k.n_hist < 0 || k.n_hist > 3 || !last || !m_out) return 1;
+    for (int j = 0; j < k.n_hist; ++j)
+        if (!hist[j]) return 1;
+    return launch_update(u, UnipcSolver{k, last, m_out, hist[0], hist[1], hist[2]}, bl, s);
+}

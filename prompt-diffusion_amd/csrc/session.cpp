@@ -111,8 +111,7 @@ int pd_engine::compute_emb(NetW& net, std::vector<float*>& tabs, const int64_t* 
 // Allocates the session state from the arena and computes everything that does not change across
 // steps: NHWC copies of the inputs, guided_hint (cldm/cldm.py:306-308), context K/V of every
 // cross-attention, projected time embeddings of every step.
-int pd_engine::session_setup(const pd_sample_args& a, const int64_t* t_rows, int n_rows, bool per_sample_t, bool want_per_step) {
-    (void)per_sample_t;
+int pd_engine::session_setup(const pd_sample_args& a, const int64_t* t_rows, int n_rows, bool want_per_step) {
     Session& s = ses;
     const int B = a.batch, Bf = s.Bf, HW = a.h * a.w, C = cfg.in_channels;
     const int L = cfg.context_len, D = cfg.context_dim, Dp = round_up(D, 8), lpad = round_up(L, 8);
@@ -187,20 +186,18 @@ int pd_engine::session_setup(const pd_sample_args& a, const int64_t* t_rows, int
                 return 1;
             }
         }
-        if (s.noise && !arena.dry)
-            HIP_OK(hipMemcpyAsync(s.noise, a.noise, (size_t)s.S * B * C * HW * 4, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
     } else {
         const float* xT = stage(a.x_T, (size_t)B * C * HW);
         if (!xT && !arena.dry) { pd_set_error("copy of x_T failed"); return 1; }
         if (!arena.dry) {
             if (launch_nchw_to_nhwc(xT, s.x_state, DT_F32, B, C, a.h, a.w, 8, stream)) return 1;
-            if (launch_fill_x_in(s.x_state, s.x_in, B, Bf / B, C, 8, HW, stream)) return 1;
+            if (launch_fill_x_in(s.x_state, s.x_in, B, Bf / B, 8, HW, stream)) return 1;
             launches += 2;
             if (s.per_step) HIP_OK(hipMemcpyAsync(s.per_step, xT, (size_t)B * C * HW * 4, hipMemcpyDeviceToDevice, stream));
         }
-        if (s.noise && !arena.dry)
-            HIP_OK(hipMemcpyAsync(s.noise, a.noise, (size_t)s.S * B * C * HW * 4, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
     }
+    if (s.noise && !arena.dry)
+        HIP_OK(hipMemcpyAsync(s.noise, a.noise, (size_t)s.S * B * C * HW * 4, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
     {
         // context rows: [uncond ; cond] (ddim_hacked.py:191 puts the unconditional half first)
         const size_t per = (size_t)B * L * D;
@@ -292,14 +289,13 @@ int pd_engine::session_setup(const pd_sample_args& a, const int64_t* t_rows, int
     return 0;
 }
 
-int pd_engine::ensure_arena(int Bf, int h, int w, int rows, bool per_step) {
-    (void)Bf; (void)h; (void)w;
+int pd_engine::ensure_arena(int rows, bool per_step) {
     // dry run of setup + one forward to size both workspaces (main and ControlNet context)
     Arena saved = arena, saved2 = arena2;
     arena.base = nullptr; arena.cap = 0; arena.top = 0; arena.peak = 0; arena.dry = true;
     arena2.base = nullptr; arena2.cap = 0; arena2.top = 0; arena2.peak = 0; arena2.dry = true;
     std::vector<int64_t> t(rows, 1);
-    int r = session_setup(ses.a, t.data(), rows, false, per_step);
+    int r = session_setup(ses.a, t.data(), rows, per_step);
     Act eps;
     if (!r) r = forward_eps(0, 0, nullptr, eps);
     const size_t need = arena.peak + (64u << 20), need2 = arena2.peak + (64u << 20);
@@ -407,10 +403,16 @@ int pd_engine::begin(const pd_sample_args* a, bool want_per_step, const pd_unipc
             b.sb = b.last ? 0.f : sqrtf(1.0f - ac[trows[i]]);
         }
     }
-    PD_TRY(ensure_arena(ses.Bf, a->h, a->w, S_, want_per_step));
-    PD_TRY(session_setup(*a, trows.data(), S_, false, want_per_step));
+    PD_TRY(ensure_arena(S_, want_per_step));
+    PD_TRY(session_setup(*a, trows.data(), S_, want_per_step));
     ses.active = true;
     return 0;
+}
+
+// What every update launch of the session shares (sampler_update.hip), for the eps of this evaluation
+UpdateState pd_engine::update_state(const Act& eps) const {
+    const Session& s = ses;
+    return UpdateState{eps.p, eps.dt, eps.C, s.x_state, s.pred_x0, s.eps_g, s.x_in, s.a.batch, s.a.h * s.a.w, cfg.in_channels, 8, s.a.use_cfg};
 }
 
 int pd_engine::step(int i) {
@@ -418,16 +420,27 @@ int pd_engine::step(int i) {
     if (!s.active) { pd_set_error("no active sampling session"); return 1; }
     if (i < 0 || i >= s.S) { pd_set_error("step %d out of range [0,%d)", i, s.S); return 1; }
     const pd_sample_args& a = s.a;
-    const int index = s.S - 1 - i;
     const size_t mk = arena.mark();
     Act eps;
     PD_TRY(forward_eps(i, 0, &s.scales_step[(size_t)i * PD_NUM_CONTROL], eps));
-    if (s.solver == SOLVER_UNIPC) {
-        PD_TRY(step_unipc(i, eps));
-        arena.release(mk);
-        return 0;
+    const UpdateState u = update_state(eps);
+    // inpainting: the same update with the known region put back before the sample is stored
+    const BlendArgs bl{s.init_z0, s.init_eps, s.mask, s.mask ? s.blend[i + 1] : BlendCoef{}};
+    ++launches;
+    PD_TRY(s.solver == SOLVER_UNIPC ? step_unipc(i, u, s.mask ? &bl : nullptr) : step_ddim(i, u, s.mask ? &bl : nullptr));
+    if (s.per_step) {
+        ++launches;
+        if (launch_nhwc_to_nchw(s.x_state, DT_F32, s.per_step + (size_t)(i + 1) * u.B * u.C * u.HW, u.B, u.C, a.h, a.w, 8, 1.f, stream))
+            return 1;
     }
-    // p_sample_ddim, ddim_hacked.py:206-233, scalars in float32 as torch.full materialises them
+    arena.release(mk);
+    return 0;
+}
+
+// p_sample_ddim, ddim_hacked.py:206-233, scalars in float32 as torch.full materialises them
+int pd_engine::step_ddim(int i, const UpdateState& u, const BlendArgs* bl) {
+    const Session& s = ses;
+    const int index = s.S - 1 - i;
     DdimCoef k;
     const float a_t = s.alphas[index], a_prev = s.alphas_prev[index], sig = s.sigmas[index];
     k.sqrt_one_minus_at = s.sqrt_1m[index];
@@ -435,35 +448,19 @@ int pd_engine::step(int i) {
     k.sqrt_a_prev = std::sqrt(a_prev);
     k.dir_coef = std::sqrt(1.0f - a_prev - sig * sig);
     k.sigma = sig;
-    k.cfg_scale = a.cfg_scale;
-    const int C = cfg.in_channels, HW = a.h * a.w;
-    const float* nz = s.noise ? s.noise + (size_t)i * a.batch * C * HW : nullptr;
-    ++launches;
-    if (s.mask) {   // inpainting: the same update with the known region put back (inpaint.hip)
-        if (launch_cfg_ddim_blend(eps.p, eps.dt, eps.C, s.x_state, s.pred_x0, s.eps_g, s.x_in, nz, a.batch, HW, C, 8, a.use_cfg, k,
-                                  a.temperature, s.init_z0, s.init_eps, s.mask, s.blend[i + 1], stream)) {
-            pd_set_error("ddim update (blend) launch failed");
-            return 1;
-        }
-    } else if (launch_cfg_ddim(eps.p, eps.dt, eps.C, s.x_state, s.pred_x0, s.eps_g, s.x_in, nz, a.batch, HW, C, 8, a.use_cfg, k,
-                               a.temperature, 1, stream)) {
+    k.cfg_scale = s.a.cfg_scale;
+    const float* nz = s.noise ? s.noise + (size_t)i * u.B * u.C * u.HW : nullptr;
+    if (launch_cfg_ddim(u, k, nz, s.a.temperature, 1, bl, stream)) {
         pd_set_error("ddim update launch failed");
         return 1;
     }
-    if (s.per_step) {
-        ++launches;
-        if (launch_nhwc_to_nchw(s.x_state, DT_F32, s.per_step + (size_t)(i + 1) * a.batch * C * HW, a.batch, C, a.h, a.w, 8, 1.f, stream))
-            return 1;
-    }
-    arena.release(mk);
     return 0;
 }
 
 // One fused UniPC step on the eps of step i: the coefficient row of multistep.cpp by value, the x0 predictions in a ring of
 // `order` slots (m_j in slot j % order; the step reads m_{i-1}.. before it writes m_i over the oldest).
-int pd_engine::step_unipc(int i, const Act& eps) {
+int pd_engine::step_unipc(int i, const UpdateState& u, const BlendArgs* bl) {
     Session& s = ses;
-    const pd_sample_args& a = s.a;
     const double* row = &s.unipc_coef[(size_t)i * PD_UNIPC_NCOEF];
     UnipcCoef k{};
     k.alpha = row[0];
@@ -475,28 +472,14 @@ int pd_engine::step_unipc(int i, const Act& eps) {
     for (int j = 0; j < 3; ++j) k.p_m[j] = row[9 + j];
     const int p_order = (int)row[12], c_order = (int)row[13];
     k.n_hist = std::max(p_order - 1, k.corr ? c_order : 0);
-    k.cfg_scale = a.cfg_scale;
+    k.cfg_scale = s.a.cfg_scale;
     const int R = s.unipc_ring;
     if (k.n_hist > R || k.n_hist > i) { pd_set_error("unipc: step %d needs %d earlier x0 predictions", i, k.n_hist); return 1; }
     const double* hist[3] = {nullptr, nullptr, nullptr};
     for (int j = 0; j < k.n_hist; ++j) hist[j] = s.u_ring[(i - 1 - j) % R];
-    const int C = cfg.in_channels, HW = a.h * a.w;
-    ++launches;
-    if (s.mask) {   // inpainting: the blend after the predictor (inpaint.hip)
-        if (launch_cfg_unipc_blend(eps.p, eps.dt, eps.C, s.x_state, s.pred_x0, s.eps_g, s.x_in, a.batch, HW, C, 8, a.use_cfg, k,
-                                   s.u_last, s.u_ring[i % R], hist, s.init_z0, s.init_eps, s.mask, s.blend[i + 1], stream)) {
-            pd_set_error("unipc update (blend) launch failed");
-            return 1;
-        }
-    } else if (launch_cfg_unipc(eps.p, eps.dt, eps.C, s.x_state, s.pred_x0, s.eps_g, s.x_in, a.batch, HW, C, 8, a.use_cfg, k, s.u_last,
-                                s.u_ring[i % R], hist, stream)) {
+    if (launch_cfg_unipc(u, k, s.u_last, s.u_ring[i % R], hist, bl, stream)) {
         pd_set_error("unipc update launch failed");
         return 1;
-    }
-    if (s.per_step) {
-        ++launches;
-        if (launch_nhwc_to_nchw(s.x_state, DT_F32, s.per_step + (size_t)(i + 1) * a.batch * C * HW, a.batch, C, a.h, a.w, 8, 1.f, stream))
-            return 1;
     }
     return 0;
 }
@@ -716,8 +699,8 @@ int pd_eps(pd_engine* e, const float* x, const int64_t* t, const float* ctx, con
     s.a = a;
     s.Bf = Bf;
     s.S = 1;
-    PD_TRY(e->ensure_arena(Bf, h, w, Bf, false));
-    PD_TRY(e->session_setup(a, th.data(), Bf, true, false));
+    PD_TRY(e->ensure_arena(Bf, false));
+    PD_TRY(e->session_setup(a, th.data(), Bf, false));
     const size_t mk = e->arena.mark();
     Act eps;
     PD_TRY(e->forward_eps(0, 1, scales, eps));
@@ -801,7 +784,7 @@ int pd_sample_set_latents(pd_engine* e, int32_t mem, const float* latents) {
         src = tmp;
     }
     if (launch_nchw_to_nhwc(src, s.x_state, DT_F32, B, C, h, w, 8, e->stream)) return 1;
-    if (launch_fill_x_in(s.x_state, s.x_in, B, s.Bf / B, C, 8, h * w, e->stream)) return 1;
+    if (launch_fill_x_in(s.x_state, s.x_in, B, s.Bf / B, 8, h * w, e->stream)) return 1;
     HIP_OK(hipStreamSynchronize(e->stream));
     e->arena.release(mk);
     return 0;
@@ -819,10 +802,7 @@ int pd_sample_eps_at(pd_engine* e, int64_t t, const float* scales13) {
     PD_TRY(e->forward_eps(row, 0, scales13, eps));
     DdimCoef k{};
     k.cfg_scale = s.a.cfg_scale;
-    const int C = e->cfg.in_channels, HW = s.a.h * s.a.w;
-    if (launch_cfg_ddim(eps.p, eps.dt, eps.C, s.x_state, s.pred_x0, s.eps_g, s.x_in, nullptr, s.a.batch, HW, C, 8, s.a.use_cfg,
-                        k, 1.f, 0, e->stream))
-        return 1;
+    if (launch_cfg_ddim(e->update_state(eps), k, nullptr, 1.f, 0, nullptr, e->stream)) return 1;
     e->arena.release(mk);
     return 0;
 }
@@ -834,30 +814,10 @@ int pd_sample_end(pd_engine* e) {
     return 0;
 }
 
-int pd_ddim_sample(pd_engine* e, const pd_sample_args* args, int32_t mem_out, float* latents_out, float* per_step_out) {
-    if (!e || !latents_out) { pd_set_error("null argument"); return 1; }
-    PD_TRY(e->begin(args, per_step_out != nullptr));
-    if (e->opt_graph && !e->profiling) {
-        PD_TRY(e->run_steps_graph());
-    } else {
-        for (int i = 0; i < e->ses.S; ++i) PD_TRY(e->step(i));
-    }
-    PD_TRY(pd_sample_get(e, PD_GET_LATENTS, mem_out, latents_out));
-    if (per_step_out) {
-        const size_t n = (size_t)(e->ses.S + 1) * args->batch * e->cfg.in_channels * args->h * args->w;
-        PD_TRY(copy_out(e, e->ses.per_step, per_step_out, n, mem_out));
-    }
-    return pd_sample_end(e);
-}
-
-int pd_sample_begin_unipc(pd_engine* e, const pd_sample_args* args, const pd_unipc_args* u) {
-    if (!e || !u) { pd_set_error("null argument"); return 1; }
-    return e->begin(args, false, u);
-}
-
-int pd_unipc_sample(pd_engine* e, const pd_sample_args* args, const pd_unipc_args* u, int32_t mem_out, float* latents_out,
-                    float* per_step_out) {
-    if (!e || !u || !latents_out) { pd_set_error("null argument"); return 1; }
+// begin, the S steps (replayed from a captured graph where that is on), latents and optional per-step samples out, end;
+// u null: DDIM, else the fused UniPC loop
+static int run_sample(pd_engine* e, const pd_sample_args* args, const pd_unipc_args* u, int32_t mem_out, float* latents_out,
+                      float* per_step_out) {
     PD_TRY(e->begin(args, per_step_out != nullptr, u));
     if (e->opt_graph && !e->profiling) {
         PD_TRY(e->run_steps_graph());
@@ -870,6 +830,22 @@ int pd_unipc_sample(pd_engine* e, const pd_sample_args* args, const pd_unipc_arg
         PD_TRY(copy_out(e, e->ses.per_step, per_step_out, n, mem_out));
     }
     return pd_sample_end(e);
+}
+
+int pd_ddim_sample(pd_engine* e, const pd_sample_args* args, int32_t mem_out, float* latents_out, float* per_step_out) {
+    if (!e || !latents_out) { pd_set_error("null argument"); return 1; }
+    return run_sample(e, args, nullptr, mem_out, latents_out, per_step_out);
+}
+
+int pd_sample_begin_unipc(pd_engine* e, const pd_sample_args* args, const pd_unipc_args* u) {
+    if (!e || !u) { pd_set_error("null argument"); return 1; }
+    return e->begin(args, false, u);
+}
+
+int pd_unipc_sample(pd_engine* e, const pd_sample_args* args, const pd_unipc_args* u, int32_t mem_out, float* latents_out,
+                    float* per_step_out) {
+    if (!e || !u || !latents_out) { pd_set_error("null argument"); return 1; }
+    return run_sample(e, args, u, mem_out, latents_out, per_step_out);
 }
 
 int pd_synchronize(pd_engine* e) {

@@ -612,11 +612,8 @@ class Engine:
         self._order_after_torch(a.mem)
         return a, keep, (B, h, w)
 
-    def ddim_sample(self, *, return_intermediates: bool = False, **kw):
-        """The fused loop (DDIMSampler.sample, cldm/ddim_hacked.py:55-178): returns latents [B,4,h,w]
-        (NumPy, or a CUDA tensor when the inputs were CUDA tensors) and optionally x_inter [S+1,B,4,h,w]."""
-        a, keep, (B, h, w) = self._args(**kw)
-        S = a.steps if a.timesteps else self.num_ddim_steps(a.steps)
+    def _sample_out(self, a, keep, B, h, w, S, return_intermediates):
+        """out [B,4,h,w] and optionally inter [S+1,B,4,h,w] in the memory space of the inputs, and their addresses."""
         Cc = self.cfg.in_channels
         if a.mem == PD_MEM_DEVICE:
             import torch
@@ -628,6 +625,14 @@ class Engine:
             out = np.empty((B, Cc, h, w), np.float32)
             inter = np.empty((S + 1, B, Cc, h, w), np.float32) if return_intermediates else None
             op, ip = out.ctypes.data, (inter.ctypes.data if inter is not None else None)
+        return out, inter, op, ip
+
+    def ddim_sample(self, *, return_intermediates: bool = False, **kw):
+        """The fused loop (DDIMSampler.sample, cldm/ddim_hacked.py:55-178): returns latents [B,4,h,w]
+        (NumPy, or a CUDA tensor when the inputs were CUDA tensors) and optionally x_inter [S+1,B,4,h,w]."""
+        a, keep, (B, h, w) = self._args(**kw)
+        S = a.steps if a.timesteps else self.num_ddim_steps(a.steps)
+        out, inter, op, ip = self._sample_out(a, keep, B, h, w, S, return_intermediates)
         self._check(self.lib.pd_ddim_sample(self._h, C.byref(a), a.mem, op, ip))
         del keep
         return (out, inter) if return_intermediates else out
@@ -638,21 +643,14 @@ class Engine:
         sampling order) is required; otherwise the arguments and returns of ddim_sample."""
         a, keep, (B, h, w) = self._args(**kw)
         u, dc = _unipc_args(order, solver_type, lower_order_final, disable_corrector)
-        S = a.steps
-        Cc = self.cfg.in_channels
-        if a.mem == PD_MEM_DEVICE:
-            import torch
-            dev = keep[0].owner.device
-            out = torch.empty((B, Cc, h, w), dtype=torch.float32, device=dev)
-            inter = torch.empty((S + 1, B, Cc, h, w), dtype=torch.float32, device=dev) if return_intermediates else None
-            op, ip = out.data_ptr(), (inter.data_ptr() if inter is not None else None)
-        else:
-            out = np.empty((B, Cc, h, w), np.float32)
-            inter = np.empty((S + 1, B, Cc, h, w), np.float32) if return_intermediates else None
-            op, ip = out.ctypes.data, (inter.ctypes.data if inter is not None else None)
+        out, inter, op, ip = self._sample_out(a, keep, B, h, w, a.steps, return_intermediates)
         self._check(self.lib.pd_unipc_sample(self._h, C.byref(a), C.byref(u), a.mem, op, ip))
         del keep, dc
         return (out, inter) if return_intermediates else out
+
+    def _session_begun(self, a, keep, shape) -> None:
+        self._keep = keep   # the staged copies stay alive until sample_end()
+        self._ses = (shape, a.mem, keep[0].owner if a.mem == PD_MEM_DEVICE else None)
 
     def sample_begin_unipc(self, *, order: int = 2, solver_type: str = "bh2", lower_order_final: bool = True,
                            disable_corrector: Sequence[int] = (), **kw) -> int:
@@ -661,15 +659,13 @@ class Engine:
         u, dc = _unipc_args(order, solver_type, lower_order_final, disable_corrector)
         self._check(self.lib.pd_sample_begin_unipc(self._h, C.byref(a), C.byref(u)))
         del dc
-        self._keep = keep
-        self._ses = (shape, a.mem, keep[0].owner if a.mem == PD_MEM_DEVICE else None)
+        self._session_begun(a, keep, shape)
         return a.steps
 
     def sample_begin(self, **kw) -> int:
         a, keep, shape = self._args(**kw)
         self._check(self.lib.pd_sample_begin(self._h, C.byref(a)))
-        self._keep = keep   # the staged copies stay alive until sample_end()
-        self._ses = (shape, a.mem, keep[0].owner if a.mem == PD_MEM_DEVICE else None)
+        self._session_begun(a, keep, shape)
         return a.steps if a.timesteps else self.num_ddim_steps(a.steps)
 
     def sample_step(self, i: int) -> None:

@@ -1,4 +1,4 @@
-"""img2img / inpainting inside the engine's loop (pd_sample_args.init_latents / mask / init_flags, inpaint.hip) and the
+"""img2img / inpainting inside the engine's loop (pd_sample_args.init_latents / mask / init_flags, sampler_update.hip) and the
 PromptDiffusionImg2ImgPipeline / PromptDiffusionInpaintPipeline on the GPU: the fused loops against the stepwise loop with
 the blend done in NumPy (bit-identical for DDIM), against the host UniPC scheduler, and against tests/inpaint_ref.py."""
 import dataclasses

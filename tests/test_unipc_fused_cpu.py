@@ -26,7 +26,7 @@ def fake_eps(x, t):
 
 
 def run_rows(coef, ts, x_T):
-    """The device kernel's update (cfg_unipc_kernel) in fp64 NumPy."""
+    """The device kernel's update (UnipcSolver::update, sampler_update.hip) in fp64 NumPy."""
     x = np.asarray(x_T, np.float64)
     ring, last, out = {}, None, []
     for i, t in enumerate(ts):
