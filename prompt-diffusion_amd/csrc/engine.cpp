@@ -673,260 +673,234 @@ Act pd_engine::new_act(int B, int H, int W, int C, int dt) {
     return a;
 }
 
-int pd_engine::gemm(const WMat& m, const Act& in, Act& out, int stride, int ups, int act, float scale, const Act* R,
-                    const float* rowvec, int rowvec_stride, bool a_silu, void* VT, int vt_begin, int vt_ld, int ldc_override,
-                    const float* gn_coef, bool gn_silu, const LnStats* ln_in, LnStats* ln_out) {
-    if (in.C != m.cin_pad) {
-        pd_set_error("gemm: input has %d channels, layer expects %d", in.C, m.cin_pad);
-        return 1;
-    }
-    GemmParams p{};
-    p.A = in.p; p.W = m.w; p.bias = m.bias; p.C = out.p;
-    p.R = R ? R->p : nullptr;
-    p.rowvec = rowvec;
-    p.VT = VT;
-    p.M = (int)out.rows(); p.N = m.N; p.K = m.K; p.Kpad = m.Kpad;
-    p.lda = in.C;
-    p.ldc = ldc_override ? ldc_override : out.C;
-    p.ldr = R ? R->C : 0;
-    p.a_dt = in.dt; p.c_dt = out.dt; p.r_dt = R ? R->dt : DT_F32;
-    p.taps = m.taps; p.Cin = m.cin_pad;
-    p.Hin = in.H; p.Win = in.W; p.Hout = out.H; p.Wout = out.W; p.stride = stride; p.ups = ups;
-    p.rows_per_sample = out.H * out.W;
-    p.rowvec_stride = rowvec_stride;
-    p.act = m.geglu ? 2 : act;
-    p.a_silu = a_silu ? 1 : 0;
-    p.out_scale = scale;
-    p.vt_begin = VT ? vt_begin : INT_MAX;
-    p.vt_ld = vt_ld;
-    p.Nout = m.Nout;
-    p.splitk = 1;
-    p.slab = nullptr;
-    p.gn_coef = gn_coef;
-    p.gn_silu = gn_silu ? 1 : 0;
-    p.gate = gx.gate; p.gate_stride = gx.gate_stride;
-    p.c_sample_rows = gx.c_sample_rows; p.c_row_off = gx.c_row_off; p.vt_tok_off = gx.vt_tok_off;
-    p.a_sample_rows = gx.a_sample_rows; p.a_row_off = gx.a_row_off;
-    p.c_scale = gx.c_scale;
-    p.pad_shift = gx.pad_shift;
-    if (out.dt == DT_FP8 && !gx.c_scale) { pd_set_error("internal: fp8 output without row scales"); return 1; }
+// gemm: check + fill
+int pd_engine::check_gemm(const WMat& m, const Act& in, const Act& out, const GemmCall& c) const {
+    if (in.C != m.cin_pad) { pd_set_error("gemm: input has %d channels, layer expects %d", in.C, m.cin_pad); return 1; }
+    if (out.dt == DT_FP8 && !c.c_scale) { pd_set_error("internal: fp8 output without row scales"); return 1; }
     // a shifted window exists in the implicit-GEMM gather only: never hand it to a kernel that would pad symmetrically
-    if (p.pad_shift && (m.taps != 9 || ups || gn_coef || in.dt == DT_FP8 || m.geglu || VT)) {
+    if (c.pad_shift && (m.taps != 9 || c.ups || c.gn_coef || in.dt == DT_FP8 || m.geglu || c.VT)) {
         pd_set_error("gemm: asymmetric conv padding needs a plain conv3x3 (no upsample / fused GroupNorm / fp8 / GEGLU / V^T)");
         return 1;
     }
-    const bool fp8 = in.dt == DT_FP8;
-    if (fp8) {   // e4m3 operands with per-row scales: the layer's quantised copy
-        if (!m.w8 || !gx.a_scale || m.taps != 1 || m.geglu) { pd_set_error("internal: fp8 GEMM without quantised weights / row scales"); return 1; }
-        p.W = m.w8; p.Kpad = m.Kpad8; p.w_scale = m.wscale; p.a_scale = gx.a_scale;
+    // e4m3 operands with per-row scales: the layer's quantised copy
+    if (in.dt == DT_FP8 && (!m.w8 || !c.a_scale || m.taps != 1 || m.geglu)) { pd_set_error("internal: fp8 GEMM without quantised weights / row scales"); return 1; }
+    if (c.ln_in && !m.w_ln) { pd_set_error("internal: folded LayerNorm weights missing"); return 1; }
+    if (f32 && in.dt != DT_F32) { pd_set_error("gemm: fp32 mode needs fp32 activations"); return 1; }
+    return 0;
+}
+
+GemmParams pd_engine::fill_gemm(const WMat& m, const Act& in, const Act& out, const GemmCall& c) {
+    GemmParams p{};
+    p.A = in.p; p.W = m.w; p.bias = m.bias; p.C = out.p;
+    p.R = c.R ? c.R->p : nullptr; p.rowvec = c.rowvec; p.VT = c.VT;
+    p.M = (int)out.rows(); p.N = m.N; p.K = m.K; p.Kpad = m.Kpad;
+    p.lda = in.C; p.ldc = c.ldc ? c.ldc : out.C; p.ldr = c.R ? c.R->C : 0;
+    p.a_dt = in.dt; p.c_dt = out.dt; p.r_dt = c.R ? c.R->dt : DT_F32;
+    p.taps = m.taps; p.Cin = m.cin_pad;
+    p.Hin = in.H; p.Win = in.W; p.Hout = out.H; p.Wout = out.W; p.stride = c.stride; p.ups = c.ups;
+    p.rows_per_sample = out.H * out.W; p.rowvec_stride = c.rowvec_stride;
+    p.act = m.geglu ? ACT_GEGLU : c.act; p.a_silu = c.a_silu ? 1 : 0; p.out_scale = c.scale;
+    p.vt_begin = c.VT ? c.vt_begin : INT_MAX; p.vt_ld = c.vt_ld;
+    p.Nout = m.Nout;
+    p.splitk = 1;
+    p.gn_coef = c.gn_coef; p.gn_silu = c.gn_silu ? 1 : 0;
+    p.gate = c.gate; p.gate_stride = c.gate_stride;
+    p.c_sample_rows = c.c_sample_rows; p.c_row_off = c.c_row_off; p.vt_tok_off = c.vt_tok_off;
+    p.a_sample_rows = c.a_sample_rows; p.a_row_off = c.a_row_off;
+    p.c_scale = c.c_scale;
+    p.pad_shift = c.pad_shift;
+    if (in.dt == DT_FP8) { p.W = m.w8; p.Kpad = m.Kpad8; p.w_scale = m.wscale; p.a_scale = c.a_scale; }
+    if (c.ln_in) {   // LayerNorm of `in` folded into this layer: raw A, folded weights, statistics from the producer
+        p.W = m.w_ln; p.bias = m.bias_ln; p.ln_colsum = m.colsum;
+        p.ln_stats = c.ln_in->stats; p.ln_parts = c.ln_in->parts; p.ln_C = c.ln_in->C; p.ln_eps = 1e-5f;
     }
-    const bool plain = !gx.gate && !gx.c_sample_rows && !gx.a_sample_rows && !gx.c_scale;
-    gx = GemmExtra{};
-    SlabDefer* defer = gx_defer;
-    gx_defer = nullptr;
-    if (defer) defer->active = false;
+    return p;
+}
+
+// gemm: plan.  Which kernel family / tile / split a launch takes, from shapes, options and ncu alone (p: fill_gemm's, splitk 1).
+int pd_engine::patch_tiles(const GemmParams& p) const {
+    return (opt_patch && !p.pad_shift) ? conv_patch_tiles(p, P) : 0;   // the patch kernels pad 1 on every side
+}
+// conv3x3 with enough 16x16 patches to fill the chip: LDS-patch kernel (conv_patch.hip)
+bool pd_engine::patch_unsplit(int ptiles) const {
+    return ptiles >= ncu * 3 / 4;   // (192 of 256 CUs: a launch that fills three quarters of the chip takes the patch kernel unsplit)
+}
+
+GemmPlan pd_engine::plan_gemm(const GemmParams& p, const WMat& m, const GemmCall& c, bool allow_splitk) const {
+    GemmPlan pl;
+    const int in_dt = p.a_dt, out_dt = p.c_dt;
+    const bool fp8 = in_dt == DT_FP8;
+    const bool plain = !c.gate && !c.c_sample_rows && !c.a_sample_rows && !c.c_scale;
+    // the caller's SlabDefer can be honoured: plain bias / time-embedding epilogue only
+    const bool may_defer = c.defer && c.defer->allow && plain && c.act == 0 && c.scale == 1.f && !c.R && !c.VT && !c.ln_in && !c.ln_out;
     // a handful of fp32 rows against a wide weight matrix: stream the weights once (gemm.hip's tiles would spend a 128-row
     // tile on <= 4 rows and run at a third of the HBM rate)
-    if (opt_gemv && plain && p.M <= 4 && m.taps == 1 && in.dt == DT_F32 && out.dt == DT_F32 && !R && !rowvec && !VT && act == 0 &&
-        !m.geglu && scale == 1.f && !ln_in && !ln_out && m.K % 8 == 0 && m.K <= 2048 && m.N >= 4096) {
-        if (arena.dry) return 0;
-        PD_TRY(check_arena());
-        ++launches;
-        ProfRec rec{};
-        if (profiling) {
-            prof_begin(rec, 1, 2.0 * (double)p.M * (double)m.Nout * (double)m.cin);
-            rec.M = p.M; rec.N = p.N; rec.K = p.K; rec.taps = 10;
-        }
-        const int r = launch_gemv(reinterpret_cast<const float*>(in.p), in.C, m.w, T, m.Kpad, m.bias, reinterpret_cast<float*>(out.p), p.ldc,
-                                  p.M, m.N, m.K, a_silu ? 1 : 0, stream);
-        if (profiling) prof_end(rec);
-        if (r) { pd_set_error("gemv launch failed"); return 1; }
-        return 0;
+    if (opt_gemv && plain && p.M <= 4 && m.taps == 1 && in_dt == DT_F32 && out_dt == DT_F32 && !c.R && !c.rowvec && !c.VT && c.act == 0 &&
+        !m.geglu && c.scale == 1.f && !c.ln_in && !c.ln_out && m.K % 8 == 0 && m.K <= 2048 && m.N >= 4096) {
+        pl.family = GEMM_GEMV;
+        return pl;
     }
-    if (ln_in) {   // LayerNorm of `in` folded into this layer: raw A, folded weights, statistics from the producer
-        if (!m.w_ln) { pd_set_error("internal: folded LayerNorm weights missing"); return 1; }
-        p.W = m.w_ln;
-        p.bias = m.bias_ln;
-        p.ln_stats = ln_in->stats;
-        p.ln_parts = ln_in->parts;
-        p.ln_colsum = m.colsum;
-        p.ln_C = ln_in->C;
-        p.ln_eps = 1e-5f;
-    }
-    // conv3x3 with enough 16x16 patches to fill the chip: LDS-patch kernel (conv_patch.hip)
-    const int ptiles = (opt_patch && !p.pad_shift) ? conv_patch_tiles(p, P) : 0;   // the patch kernels pad 1 on every side
-    bool use_patch = ptiles >= ncu * 3 / 4;   // (192 of 256 CUs: a launch that fills three quarters of the chip takes the patch kernel unsplit)
+    const int ptiles = patch_tiles(p);
+    bool use_patch = patch_unsplit(ptiles);
     // 16x16-level convs: too few 16x16 patches for the chip, but the patch kernel still beats the generic gather when the
     // channel chunks are split across 2-4 slices (fp32 slabs + the same deterministic finalize pass as the GEMM's split-K)
-    int patch_split = 1;
-    if (!use_patch && opt_patch_split && ptiles >= opt_patch_split_tiles && !gn_coef && m.N % 4 == 0) {
+    if (!use_patch && opt_patch_split && ptiles >= opt_patch_split_tiles && !c.gn_coef && m.N % 4 == 0) {
         const int chunks = p.Cin / (f32 ? 32 : 64);
         int sk = (opt_patch_split_fill + ptiles - 1) / ptiles;
         if (sk > chunks / opt_patch_split_min) sk = chunks / opt_patch_split_min;   // at least this many channel chunks per slice
         if (sk > 4) sk = 4;
         while (sk >= 2 && (sk - 1) * ((chunks + sk - 1) / sk) >= chunks) --sk;       // no empty slice
-        if (sk >= 2) { use_patch = true; patch_split = sk; }
+        if (sk >= 2) { use_patch = true; pl.splitk = sk; }
     }
-    if (gn_coef && !use_patch) {
-        pd_set_error("internal: fused GroupNorm requested for a conv that is not patch-eligible");
-        return 1;
+    if (use_patch) {
+        pl.defer_finalize = pl.splitk > 1 && may_defer;
+        // second-generation (wave-specialised) patch kernel where it measures faster: many blocks per CU (its longer prologue
+        // amortises) or the split-K 16x16 level; the 2-round 64x64 launches stay on the first generation (152 vs 142 us)
+        const bool patch2 = opt_patch2 && !f32 && !c.gn_coef && (pl.splitk > 1 || ptiles >= opt_patch2_tiles);
+        // fourth generation (4 waves per block, one per SIMD, 32x32x16 MFMAs, LDS-DMA operands): every unsplit 2-byte launch (-4..-8 % at
+        // batch 8, -17..-19 % at batch 1 against the faster of the first two; split-K launches tie and stay on the second)
+        const bool patch4 = opt_patch4 && pl.splitk == 1 && conv_patch4_eligible(p, P);
+        pl.family = patch4 ? GEMM_PATCH4 : patch2 ? GEMM_PATCH2 : GEMM_PATCH1;
+        return pl;
     }
     // otherwise split K when the tile grid cannot fill the chip (8x8 / 16x16 levels, time-embedding GEMMs)
-    bool use_ring = false;
-    int ring_tile = 0;
-    if (!use_patch) {
-        const size_t mk = arena.mark();
-        const int tiles = gemm_tiles(p.M, m.N);
-        const int ktiles = fp8 ? m.Kpad8 / 128 : m.Kpad / (128 / (int)dt_size(T));
-        int splitk = 1;
-        // small-M linear layers (the 8x8 level's M = 1024: 64 tiles of 128 x 160): 64 x 80 ring tiles fill the chip without split-K slabs and
-        // a finalize pass (every CU then streams 1 / 16 of the weight matrix once instead of 1 / 8 of a K slice + the slab traffic)
-        const bool small_ring = opt_ring > 0 && opt_ring_small && m.taps == 1 && !fp8 && !m.geglu && in.dt == T && ktiles <= opt_ring && tiles * opt_ring_small <= ncu &&
-                                ((p.M + 63) / 64) * ((m.N + 79) / 80) >= ncu / 2 && ring_gemm_eligible(p, P);
-        // linear layers with a short K and at least half a chip of tiles: one 8-wave block per CU instead of split-K
-        const bool dense8 = opt_dense_k > 0 && m.taps == 1 && in.dt == T && !fp8 && !m.geglu && ktiles <= opt_dense_k && tiles >= opt_dense_tiles;
-        const int kmin = fp8 ? 8 : 16, kper = fp8 ? 4 : 8;   // an e4m3 K step carries twice the K of a 2-byte one
-        if (!small_ring && !dense8 && !m.geglu && !VT && tiles < opt_splitk_tiles && tiles <= kTileCnt && ktiles >= kmin && m.N % 4 == 0) {
-            splitk = (2 * ncu + tiles - 1) / tiles;   // about two blocks per CU
-            if (splitk > ktiles / kper) splitk = ktiles / kper;
-            if (splitk > opt_splitk_max) splitk = opt_splitk_max;
-            if (splitk < 1) splitk = 1;
+    const int tiles = gemm_tiles(p.M, m.N);
+    const int ktiles = fp8 ? m.Kpad8 / 128 : m.Kpad / (128 / (int)dt_size(T));
+    int splitk = 1;
+    // small-M linear layers (the 8x8 level's M = 1024: 64 tiles of 128 x 160): 64 x 80 ring tiles fill the chip without split-K slabs and
+    // a finalize pass (every CU then streams 1 / 16 of the weight matrix once instead of 1 / 8 of a K slice + the slab traffic)
+    const bool small_ring = opt_ring > 0 && opt_ring_small && m.taps == 1 && !fp8 && !m.geglu && in_dt == T && ktiles <= opt_ring && tiles * opt_ring_small <= ncu &&
+                            ((p.M + 63) / 64) * ((m.N + 79) / 80) >= ncu / 2 && ring_gemm_eligible(p, P);
+    // linear layers with a short K and at least half a chip of tiles: one 8-wave block per CU instead of split-K
+    const bool dense8 = opt_dense_k > 0 && m.taps == 1 && in_dt == T && !fp8 && !m.geglu && ktiles <= opt_dense_k && tiles >= opt_dense_tiles;
+    const int kmin = fp8 ? 8 : 16, kper = fp8 ? 4 : 8;   // an e4m3 K step carries twice the K of a 2-byte one
+    if (allow_splitk && !small_ring && !dense8 && !m.geglu && !c.VT && tiles < opt_splitk_tiles && tiles <= kTileCnt && ktiles >= kmin && m.N % 4 == 0) {
+        splitk = (2 * ncu + tiles - 1) / tiles;   // about two blocks per CU
+        if (splitk > ktiles / kper) splitk = ktiles / kper;
+        if (splitk > opt_splitk_max) splitk = opt_splitk_max;
+        if (splitk < 1) splitk = 1;
+    }
+    pl.splitk = splitk;
+    pl.fused_tile_cnt = splitk > 1 && opt_splitk_fused;
+    // split-K conv3x3 with at least 1024 rows (the 8x8 level at batch 8): 256-row tiles halve the weight bytes each slice streams
+    // (every M tile reads the whole [160 x K / splitk] weight panel) when 256-row tiles x slices still give every CU a block
+    const bool sk256 = opt_splitk_big && splitk > 1 && !pl.fused_tile_cnt && m.taps == 9 && !f32 && p.M >= 1024 &&
+                       ((p.M + 255) / 256) * ((m.N + 159) / 160) * splitk >= ncu;
+    // the consumer sums the slabs itself (SlabDefer)
+    pl.defer_finalize = may_defer && splitk > 1 && !pl.fused_tile_cnt && !m.geglu;
+    // 256-row tiles when they still give every CU a block (1 block of 8 waves per CU)
+    pl.big_tile = ((opt_bigtile && splitk == 1 && ((p.M + 255) / 256) * ((m.N + 159) / 160) >= ncu) || sk256) ? 1 : 0;
+    if (dense8 && tiles < opt_splitk_tiles) pl.big_tile = 2;
+    // 256 x 320 tiles for linear layers that still give (almost) every CU a block
+    {
+        const int t3 = ((p.M + 255) / 256) * ((m.N + 319) / 320);
+        const int rounds = (t3 + ncu - 1) / ncu;
+        if (opt_wide && splitk == 1 && m.taps == 1 && in_dt == T && t3 >= ncu && t3 * 100 >= rounds * ncu * 85) pl.big_tile = 3;
+    }
+    // short-K linear layers are HBM-bound (K <= 1280: 1.5-2.5x their traffic floor): what they need is loads and
+    // stores of one tile overlapping the MFMAs of others, i.e. many waves per CU rather than a big tile -- the
+    // 128 x 160 tile on 8 waves at <= 128 VGPRs runs 2 blocks = 16 waves per CU (+0.6 % end-to-end, interleaved A/B)
+    if (opt_short_k > 0 && splitk == 1 && m.taps == 1 && in_dt == T && !m.geglu && ktiles <= opt_short_k) pl.big_tile = 2;
+    // widths that are multiples of 192 but not of 160 (MMDiT hidden size 1536 and its 3x / 4x): the 256 x 192 tile
+    if (opt_tile192 && !f32 && P != PREC_F16X2 && splitk == 1 && m.taps == 1 && (in_dt == T || fp8) && !m.geglu && m.N % 192 == 0 && m.N % 160 != 0 &&
+        ((p.M + 255) / 256) * (m.N / 192) >= ncu * 3 / 4)
+        pl.big_tile = 4;
+    if (P == PREC_F16X2 && m.geglu && pl.big_tile == 3) pl.big_tile = 1;   // the 256 x 320 GEGLU tile spills with the split-operand fragments
+    // short reductions over 2-byte operands: the persistent ring kernel (gemm_ring.hip); 256-row tiles when they give
+    // (almost) every CU one
+    if (opt_ring > 0 && splitk == 1 && !fp8 && ktiles <= opt_ring && (p.act != 2 || opt_ring_geglu) && ring_gemm_eligible(p, P)) {
+        pl.family = GEMM_RING;
+        pl.ring_tile = opt_ring_tile >= 0 ? opt_ring_tile : small_ring ? 4 : (((p.M + 255) / 256) * ((m.N + 159) / 160) >= ncu * 7 / 8 ? 1 : 0);
+        // ping-pong form (two wave groups half a K step apart; bit-identical): -10..-14 % on long reductions and -3..-5 % on one
+        // 256-row tile per CU; +6..+13 % where a block walks several short tiles (the groups' epilogues serialise) -- tools/micro/ring_pp.hip
+        if (opt_ring_pp && pl.ring_tile < 2 && p.act != 2 && !small_ring) {
+            const int bm = pl.ring_tile ? 256 : 128;
+            const int nblk = ((p.M + bm - 1) / bm) * ((m.N + 159) / 160);
+            if (ktiles >= 40 || (pl.ring_tile == 1 && nblk <= ncu)) pl.ring_tile += 2;
         }
-        if (splitk > 1) {
-            p.slab = arena.alloc((size_t)splitk * p.M * m.N * sizeof(float));
-            if (!arena.dry && arena.top > arena.cap) { splitk = 1; p.slab = nullptr; arena.overflow = false; }  // no room (op hooks outside a session): unsplit
-        }
-        p.splitk = splitk;
-        p.tile_cnt = (splitk > 1 && opt_splitk_fused) ? tile_cnt : nullptr;
-        // split-K conv3x3 with at least 1024 rows (the 8x8 level at batch 8): 256-row tiles halve the weight bytes each slice streams
-        // (every M tile reads the whole [160 x K / splitk] weight panel) when 256-row tiles x slices still give every CU a block
-        const bool sk256 = opt_splitk_big && splitk > 1 && !p.tile_cnt && m.taps == 9 && !f32 && p.M >= 1024 &&
-                           ((p.M + 255) / 256) * ((m.N + 159) / 160) * splitk >= ncu;
-        // the consumer sums the slabs itself (SlabDefer): plain bias / time-embedding epilogue only
-        if (defer && defer->allow && splitk > 1 && !p.tile_cnt && p.slab && plain && act == 0 && scale == 1.f && !R && !VT && !ln_in && !ln_out && !m.geglu) {
-            p.defer_finalize = 1;
-            defer->active = true;
-        }
-        // 256-row tiles when they still give every CU a block (1 block of 8 waves per CU)
-        p.big_tile = ((opt_bigtile && splitk == 1 && ((p.M + 255) / 256) * ((m.N + 159) / 160) >= ncu) || sk256) ? 1 : 0;
-        if (dense8 && tiles < opt_splitk_tiles) p.big_tile = 2;
-        // 256 x 320 tiles for linear layers that still give (almost) every CU a block
-        {
-            const int t3 = ((p.M + 255) / 256) * ((m.N + 319) / 320);
-            const int rounds = (t3 + ncu - 1) / ncu;
-            if (opt_wide && splitk == 1 && m.taps == 1 && in.dt == T && t3 >= ncu && t3 * 100 >= rounds * ncu * 85) p.big_tile = 3;
-        }
-        // short-K linear layers are HBM-bound (K <= 1280: 1.5-2.5x their traffic floor): what they need is loads and
-        // stores of one tile overlapping the MFMAs of others, i.e. many waves per CU rather than a big tile -- the
-        // 128 x 160 tile on 8 waves at <= 128 VGPRs runs 2 blocks = 16 waves per CU (+0.6 % end-to-end, interleaved A/B)
-        if (opt_short_k > 0 && splitk == 1 && m.taps == 1 && in.dt == T && !m.geglu && ktiles <= opt_short_k) p.big_tile = 2;
-        // widths that are multiples of 192 but not of 160 (MMDiT hidden size 1536 and its 3x / 4x): the 256 x 192 tile
-        if (opt_tile192 && !f32 && P != PREC_F16X2 && splitk == 1 && m.taps == 1 && (in.dt == T || fp8) && !m.geglu && m.N % 192 == 0 && m.N % 160 != 0 &&
-            ((p.M + 255) / 256) * (m.N / 192) >= ncu * 3 / 4)
-            p.big_tile = 4;
-        if (P == PREC_F16X2 && m.geglu && p.big_tile == 3) p.big_tile = 1;   // the 256 x 320 GEGLU tile spills with the split-operand fragments
-        if (!p.defer_finalize) arena.release(mk);  // stream-ordered: the slab is dead once this GEMM's finalize pass has run
-        // short reductions over 2-byte operands: the persistent ring kernel (gemm_ring.hip); 256-row tiles when they give
-        // (almost) every CU one
-        if (opt_ring > 0 && splitk == 1 && !fp8 && ktiles <= opt_ring && (p.act != 2 || opt_ring_geglu) && ring_gemm_eligible(p, P)) {
-            use_ring = true;
-            ring_tile = opt_ring_tile >= 0 ? opt_ring_tile : small_ring ? 4 : (((p.M + 255) / 256) * ((m.N + 159) / 160) >= ncu * 7 / 8 ? 1 : 0);
-            // ping-pong form (two wave groups half a K step apart; bit-identical): -10..-14 % on long reductions and -3..-5 % on one
-            // 256-row tile per CU; +6..+13 % where a block walks several short tiles (the groups' epilogues serialise) -- tools/micro/ring_pp.hip
-            if (opt_ring_pp && ring_tile < 2 && p.act != 2 && !small_ring) {
-                const int bm = ring_tile ? 256 : 128;
-                const int nblk = ((p.M + bm - 1) / bm) * ((m.N + 159) / 160);
-                if (ktiles >= 40 || (ring_tile == 1 && nblk <= ncu)) ring_tile += 2;
-            }
-            p.big_tile = 0;
-        }
-        if (ln_out && splitk == 1 && !m.geglu && !VT) {   // this launch's own epilogue leaves the row statistics
-            // the tile launch_prec (gemm.hip) takes for this launch: 256 x 320 only for linear layers over operands of the compute
-            // type, otherwise big_tile 3 falls back to 256 x 160; launch_one rejects a part count that disagrees with its tile
-            const bool wide = p.big_tile == 3 && m.taps == 1 && in.dt == T;
-            const int bn_cols = wide ? 320 : p.big_tile == 4 ? 192 : 160;
-            ln_out->parts = ((m.N + bn_cols - 1) / bn_cols) * 2;   // 2 waves across N in every non-GEGLU tile
-            if (use_ring && ring_tile == 4) ln_out->parts = (m.N + 79) / 80;   // ... but one in the 64 x 80 ring tile
-            if (ln_out->cap_parts && ln_out->parts > ln_out->cap_parts) {
-                pd_set_error("internal: %d LayerNorm statistics partials per row, buffer holds %d", ln_out->parts, ln_out->cap_parts);
-                return 1;
-            }
-            ln_out->C = m.Nout;
-            p.stats_out = ln_out->stats;
-            p.stats_parts = ln_out->parts;
+        pl.big_tile = 0;
+    }
+    if (c.ln_out && splitk == 1 && !m.geglu && !c.VT) {   // this launch's own epilogue leaves the row statistics: as many per row as its tile has waves across N
+        GemmParams q = p;
+        q.big_tile = pl.big_tile;
+        pl.stats_parts = pl.family == GEMM_RING ? ring_gemm_stats_parts(q, P, pl.ring_tile) : gemm_stats_parts(q, fp8 ? PREC_FP8 : P);
+    }
+    return pl;
+}
+
+// gemm: run (workspace, launch, profiling)
+int pd_engine::gemm(const WMat& m, const Act& in, Act& out, const GemmCall& c) {
+    PD_TRY(check_gemm(m, in, out, c));
+    GemmParams p = fill_gemm(m, in, out, c);
+    GemmPlan pl = plan_gemm(p, m, c);
+    if (c.defer) c.defer->active = false;
+    if (c.gn_coef && !pl.patch()) { pd_set_error("internal: fused GroupNorm requested for a conv that is not patch-eligible"); return 1; }
+    const size_t mk = arena.mark();
+    if (pl.splitk > 1) {
+        p.slab = arena.alloc((size_t)pl.splitk * p.M * m.N * sizeof(float));
+        if (!arena.dry && arena.top > arena.cap) {
+            if (pl.patch()) { pd_set_error("no workspace for the conv split-K slabs"); return 1; }
+            p.slab = nullptr; arena.overflow = false;   // no room (op hooks outside a session): unsplit
+            pl = plan_gemm(p, m, c, false);
         }
     }
-    if (use_patch && patch_split > 1) {
-        const size_t mk = arena.mark();
-        p.slab = arena.alloc((size_t)patch_split * p.M * m.N * sizeof(float));
-        p.splitk = patch_split;
-        if (!arena.dry && arena.top > arena.cap) { pd_set_error("no workspace for the conv split-K slabs"); return 1; }
-        if (defer && defer->allow && plain && act == 0 && scale == 1.f && !R && !VT && !ln_in && !ln_out) {
-            p.defer_finalize = 1;
-            defer->active = true;
-        } else {
-            arena.release(mk);   // stream-ordered: dead once the finalize pass has run
-        }
+    p.splitk = pl.splitk; p.big_tile = pl.big_tile; p.defer_finalize = pl.defer_finalize ? 1 : 0;
+    p.tile_cnt = pl.fused_tile_cnt ? tile_cnt : nullptr;
+    if (pl.defer_finalize) c.defer->active = true;
+    else arena.release(mk);   // stream-ordered: the slab is dead once this GEMM's finalize pass has run
+    if (pl.stats_parts) {
+        LnStats& st = *c.ln_out;
+        st.parts = p.stats_parts = pl.stats_parts; st.C = m.Nout; p.stats_out = st.stats;
+        if (st.cap_parts && st.parts > st.cap_parts) { pd_set_error("internal: %d LayerNorm statistics partials per row, buffer holds %d", st.parts, st.cap_parts); return 1; }
     }
     if (arena.dry) return 0;
     PD_TRY(check_arena());
-    if (f32 && in.dt != DT_F32) {
-        pd_set_error("gemm: fp32 mode needs fp32 activations");
-        return 1;
-    }
-    const int prec = fp8 ? PREC_FP8 : P;
+    const bool gemv = pl.family == GEMM_GEMV, ring = pl.family == GEMM_RING;
     ++launches;
     ProfRec rec{};
-    if (profiling) {
+    if (profiling && gemv) {
+        prof_begin(rec, 1, 2.0 * (double)p.M * (double)m.Nout * (double)m.cin);
+        rec.M = p.M; rec.N = p.N; rec.K = p.K; rec.taps = 10;
+    } else if (profiling) {
         // algorithmic flops: 2 * M * N * K with the logical (unpadded) channel counts
         const double n_log = m.geglu ? 2.0 * m.Nout : (double)m.Nout;
-        prof_begin(rec, m.taps == 9 ? 0 : 1, 2.0 * (double)p.M * n_log * (double)m.taps * (double)m.cin);
+        prof_begin(rec, pl.patch() ? 3 : m.taps == 9 ? 0 : 1, 2.0 * (double)p.M * n_log * (double)m.taps * (double)m.cin);
         rec.M = p.M; rec.N = p.N; rec.K = p.K; rec.taps = p.taps * 10 + p.stride + (p.ups ? 5 : 0);
     }
-    hipEvent_t mid = nullptr;
-    if (profiling && !use_patch) { mid = next_event(); rec.klass = m.taps == 9 ? 0 : 1; }
-    if (profiling && use_patch) rec.klass = 3;
-    // second-generation (wave-specialised) patch kernel where it measures faster: many blocks per CU (its longer prologue
-    // amortises) or the split-K 16x16 level; the 2-round 64x64 launches stay on the first generation (152 vs 142 us)
-    const bool patch2 = use_patch && opt_patch2 && !f32 && !gn_coef && (patch_split > 1 || ptiles >= opt_patch2_tiles);
-    // fourth generation (4 waves per block, one per SIMD, 32x32x16 MFMAs, LDS-DMA operands): every unsplit 2-byte launch (-4..-8 % at
-    // batch 8, -17..-19 % at batch 1 against the faster of the first two; split-K launches tie and stay on the second)
-    const bool patch4 = use_patch && opt_patch4 && patch_split == 1 && conv_patch4_eligible(p, P);
+    hipEvent_t mid = (profiling && !gemv && !pl.patch()) ? next_event() : nullptr;
+    if (gemv) {
+        const int r = launch_gemv(reinterpret_cast<const float*>(in.p), in.C, m.w, T, m.Kpad, m.bias, reinterpret_cast<float*>(out.p), p.ldc,
+                                  p.M, m.N, m.K, p.a_silu, stream);
+        if (profiling) prof_end(rec);
+        if (r) { pd_set_error("gemv launch failed"); return 1; }
+        return 0;
+    }
+    static const char* const family_name[] = {"gemv", "patch1", "patch2", "patch4", "ring", "igemm"};
     if (verbose >= 2)   // dispatch trace (option "verbose" 2): which kernel family / tile / split a launch takes
         fprintf(stderr, "[pdengine] gemm M %d N %d K %d taps %d stride %d ups %d: %s splitk %d big_tile %d ring_tile %d act %d R %d ln_in %d ln_out %d\n", p.M, p.N, p.K, p.taps,
-                p.stride, p.ups, use_patch ? (patch4 ? "patch4" : patch2 ? "patch2" : "patch1") : use_ring ? "ring" : "igemm", p.splitk, p.big_tile, ring_tile, p.act,
-                p.R ? 1 : 0, p.ln_stats ? 1 : 0, p.stats_out ? 1 : 0);
-    if (use_patch ? (patch4 ? launch_conv_patch4(p, P, stream) : patch2 ? launch_conv_patch2(p, P, stream) : launch_conv_patch(p, P, stream))
-                  : use_ring ? launch_ring_gemm(p, prec, ring_tile, stream) : launch_gemm(p, prec, stream, mid)) {
-        pd_set_error("gemm launch failed: %s", hipGetErrorString(hipGetLastError()));
-        return 1;
-    }
-    if (use_ring) ++ring_launches;
-    if (defer && defer->active) {
-        defer->slabs = reinterpret_cast<const float*>(p.slab); defer->nslab = p.splitk;
-        defer->bias = p.bias; defer->rowvec = p.rowvec; defer->rowvec_stride = p.rowvec_stride;
-    }
-    if (profiling && mid && use_ring) HIP_OK(hipEventRecord(mid, stream));
+                p.stride, p.ups, family_name[pl.family], p.splitk, p.big_tile, pl.ring_tile, p.act, p.R ? 1 : 0, p.ln_stats ? 1 : 0, p.stats_out ? 1 : 0);
+    const int prec = in.dt == DT_FP8 ? PREC_FP8 : P;
+    const int r = pl.family == GEMM_PATCH4 ? launch_conv_patch4(p, P, stream) : pl.family == GEMM_PATCH2 ? launch_conv_patch2(p, P, stream) :
+                  pl.family == GEMM_PATCH1 ? launch_conv_patch(p, P, stream) : ring ? launch_ring_gemm(p, prec, pl.ring_tile, stream) : launch_gemm(p, prec, stream, mid);
+    if (r) { pd_set_error("gemm launch failed: %s", hipGetErrorString(hipGetLastError())); return 1; }
+    if (ring) ++ring_launches;
+    if (pl.defer_finalize) *c.defer = SlabDefer{true, true, reinterpret_cast<const float*>(p.slab), p.splitk, p.bias, p.rowvec, p.rowvec_stride};
+    if (profiling && mid && ring) HIP_OK(hipEventRecord(mid, stream));
     if (profiling) {
         if (mid) { rec.b = mid; prof.push_back(rec); }   // bracket = the contraction kernel only (no split-K finalize)
         else prof_end(rec);
     }
-    if (ln_out && !p.stats_out) {   // split-K / patch launches finish in another kernel: one statistics pass over the output
-        ln_out->parts = 1;
-        ln_out->C = m.Nout;
+    if (c.ln_out && !p.stats_out) {   // split-K / patch launches finish in another kernel: one statistics pass over the output
+        c.ln_out->parts = 1; c.ln_out->C = m.Nout;
         ++launches;
-        if (launch_row_stats(out.p, out.dt, ln_out->stats, (int)out.rows(), out.C, stream)) {
-            pd_set_error("row statistics launch failed");
-            return 1;
-        }
+        if (launch_row_stats(out.p, out.dt, c.ln_out->stats, (int)out.rows(), out.C, stream)) { pd_set_error("row statistics launch failed"); return 1; }
     }
     return 0;
 }
 
-int pd_engine::conv(const ConvW& c, const Act& in, Act& out, int act, float scale, const Act* R, const float* rowvec,
-                    int rowvec_stride, int ups) {
-    gx.pad_shift = c.pad_shift;
-    return gemm(c.m, in, out, c.stride, ups, act, scale, R, rowvec, rowvec_stride, false, nullptr, 0, 0);
+int pd_engine::conv(const ConvW& c, const Act& in, Act& out, GemmCall call) {
+    call.stride = c.stride; call.pad_shift = c.pad_shift;
+    return gemm(c.m, in, out, call);
 }
 
 int pd_engine::gn_stats(const Act& x, int& nchunk) {
@@ -982,19 +956,16 @@ int pd_engine::groupnorm(const Act& x, Act& y, const float* g, const float* b, f
 
 // conv3x3(act(GroupNorm(x))): when the conv runs on the LDS-patch kernel the normalisation (+SiLU) is applied while
 // the input patch is staged, so the normalised tensor is never written to HBM; otherwise GroupNorm runs as its own pass.
-int pd_engine::conv_gn(const ConvW& c, const Act& x, Act& out, const float* g, const float* b, float eps, bool silu,
-                       const Act* R, const float* rowvec, int rowvec_stride, SlabDefer* out_defer, const SlabDefer* in_slabs) {
-    GemmParams q{};
-    q.M = (int)out.rows(); q.N = c.m.N; q.K = c.m.K; q.taps = c.m.taps; q.Cin = c.m.cin_pad; q.stride = c.stride;
-    q.Hin = x.H; q.Win = x.W; q.Hout = out.H; q.Wout = out.W; q.a_dt = x.dt; q.vt_begin = INT_MAX; q.splitk = 1;
-    const bool fuse = opt_gn_fuse && opt_patch && !c.pad_shift && x.C == c.m.cin_pad && conv_patch_tiles(q, P) >= ncu * 3 / 4;
+int pd_engine::conv_gn(const ConvW& c, const Act& x, Act& out, const float* g, const float* b, float eps, bool silu, GemmCall call,
+                       const SlabDefer* in_slabs) {
+    call.stride = c.stride; call.pad_shift = c.pad_shift;
+    const bool fuse = opt_gn_fuse && x.C == c.m.cin_pad && patch_unsplit(patch_tiles(fill_gemm(c.m, x, out, call)));
     if (!fuse) {
         const size_t mk = arena.mark();
         Act a = new_act(x.B, x.H, x.W, x.C, T);
         PD_TRY(groupnorm(x, a, g, b, eps, silu, in_slabs));
-        gx_defer = out_defer;
-        PD_TRY(conv(c, a, out, 0, 1.f, R, rowvec, rowvec_stride));
-        if (!(out_defer && out_defer->active)) arena.release(mk);   // deferred: the slabs sit above `a`; the caller's mark frees both
+        PD_TRY(gemm(c.m, a, out, call));
+        if (!(call.defer && call.defer->active)) arena.release(mk);   // deferred: the slabs sit above `a`; the caller's mark frees both
         return 0;
     }
     if (in_slabs && in_slabs->active) { pd_set_error("internal: deferred split-K slabs in front of a GroupNorm-fused conv"); return 1; }
@@ -1004,12 +975,10 @@ int pd_engine::conv_gn(const ConvW& c, const Act& x, Act& out, const float* g, c
     float* coef = reinterpret_cast<float*>(arena.alloc((size_t)x.B * x.C * 2 * sizeof(float)));
     if (!arena.dry) {
         ++launches;
-        if (launch_gn_coef(gn_partial, g, b, coef, x.B, x.H * x.W, x.C, 32, nchunk, eps, stream)) {
-            pd_set_error("groupnorm coefficient launch failed");
-            return 1;
-        }
+        if (launch_gn_coef(gn_partial, g, b, coef, x.B, x.H * x.W, x.C, 32, nchunk, eps, stream)) { pd_set_error("groupnorm coefficient launch failed"); return 1; }
     }
-    PD_TRY(gemm(c.m, x, out, c.stride, 0, 0, 1.f, R, rowvec, rowvec_stride, false, nullptr, 0, 0, 0, coef, silu));
+    call.gn_coef = coef; call.gn_silu = silu; call.defer = nullptr;
+    PD_TRY(gemm(c.m, x, out, call));
     arena.release(mk);
     return 0;
 }
@@ -1066,13 +1035,13 @@ int pd_engine::resblock(const ResW& r, const Act& x, Act& out, const float* embr
     // kernel sums the slabs itself -- no finalize pass, h is never written
     SlabDefer d;
     d.allow = opt_slab_gn && !opt_gn_fuse && opt_gn_single && h.dt == T && gn_fused_bundle(T, x.H * x.W, r.cout, 32) > 0;
-    PD_TRY(conv_gn(r.conv1, x, h, r.gn1_g, r.gn1_b, r.eps, true, nullptr, embrow, emb_stride, &d));
+    PD_TRY(conv_gn(r.conv1, x, h, r.gn1_g, r.gn1_b, r.eps, true, {.rowvec = embrow, .rowvec_stride = emb_stride, .defer = &d}));
     Act skip = x;
     if (r.has_skip) {
         skip = new_act(x.B, x.H, x.W, r.cout, S);
         PD_TRY(conv(r.skip, x, skip));
     }
-    PD_TRY(conv_gn(r.conv2, h, out, r.gn2_g, r.gn2_b, r.eps, true, &skip, nullptr, 0, nullptr, &d));
+    PD_TRY(conv_gn(r.conv2, h, out, r.gn2_g, r.gn2_b, r.eps, true, {.R = &skip}, &d));
     arena.release(mk);
     return 0;
 }
@@ -1132,7 +1101,7 @@ int pd_engine::transformer(const STW& s, const Act& x, Act& out, const KVSlot& k
         st1.stats = reinterpret_cast<float*>(arena.alloc(cap));
     }
     h = new_act(B, H, W, C, S);
-    PD_TRY(gemm(s.proj_in.m, a, h, 1, 0, 0, 1.f, nullptr, nullptr, 0, false, nullptr, 0, 0, 0, nullptr, false, nullptr, fuse ? &st0 : nullptr));
+    PD_TRY(gemm(s.proj_in.m, a, h, {.ln_out = fuse ? &st0 : nullptr}));
     // self-attention: fused QKV projection; V stored transposed for the attention kernel
     if (!fuse) {
         ln = new_act(B, H, W, C, T);
@@ -1140,7 +1109,7 @@ int pd_engine::transformer(const STW& s, const Act& x, Act& out, const KVSlot& k
     }
     qk = new_act(B, H, W, 2 * C, T);
     vt = new_act(B, C, 1, npad, T);
-    PD_TRY(gemm(s.qkv, fuse ? h : ln, qk, 1, 0, 0, 1.f, nullptr, nullptr, 0, false, vt.p, 2 * C, npad, 0, nullptr, false, fuse ? &st0 : nullptr));
+    PD_TRY(gemm(s.qkv, fuse ? h : ln, qk, {.VT = vt.p, .vt_begin = 2 * C, .vt_ld = npad, .ln_in = fuse ? &st0 : nullptr}));
     }
     Act att = new_act(B, H, W, C, T);
     const size_t eb = dt_size(T);
@@ -1164,11 +1133,11 @@ int pd_engine::transformer(const STW& s, const Act& x, Act& out, const KVSlot& k
         return 0;
     }
     Act h1 = new_act(B, H, W, C, S);
-    PD_TRY(gemm(s.out1, att, h1, 1, 0, 0, 1.f, &h, nullptr, 0, false, nullptr, 0, 0, 0, nullptr, false, nullptr, fuse ? &st1 : nullptr));
+    PD_TRY(gemm(s.out1, att, h1, {.R = &h, .ln_out = fuse ? &st1 : nullptr}));
     // cross-attention against the hoisted context K / V^T
     if (!fuse) PD_TRY(layernorm(h1, ln, s.ln_g[1], s.ln_b[1]));
     Act q2 = new_act(B, H, W, C, T);
-    PD_TRY(gemm(s.q2, fuse ? h1 : ln, q2, 1, 0, 0, 1.f, nullptr, nullptr, 0, false, nullptr, 0, 0, 0, nullptr, false, fuse ? &st1 : nullptr));
+    PD_TRY(gemm(s.q2, fuse ? h1 : ln, q2, {.ln_in = fuse ? &st1 : nullptr}));
     const int L = cfg.context_len, lpad = round_up(L, 8);
     Act xr = x;   // the block's residual at the output batch
     if (reps > 1) {
@@ -1184,15 +1153,15 @@ int pd_engine::transformer(const STW& s, const Act& x, Act& out, const KVSlot& k
     PD_TRY(attention(q2.p, C, kv.K, C, kv.VT, lpad, att.p, C, B, N, L, C));
     B = out_B;
     Act h2 = new_act(B, H, W, C, S);
-    PD_TRY(gemm(s.out2, att, h2, 1, 0, 0, 1.f, &h1, nullptr, 0, false, nullptr, 0, 0));
+    PD_TRY(gemm(s.out2, att, h2, {.R = &h1}));
     // GEGLU feed-forward (norm3 as a kernel: see fold_layernorms)
     if (fuse || reps > 1) ln = new_act(B, H, W, C, T);
     PD_TRY(layernorm(h2, ln, s.ln_g[2], s.ln_b[2]));
     Act g = new_act(B, H, W, 4 * C, T);
-    PD_TRY(gemm(s.ff1, ln, g, 1, 0, 0, 1.f, nullptr, nullptr, 0, false, nullptr, 0, 0));
+    PD_TRY(gemm(s.ff1, ln, g));
     Act h3 = new_act(B, H, W, C, S);
-    PD_TRY(gemm(s.ff2, g, h3, 1, 0, 0, 1.f, &h2, nullptr, 0, false, nullptr, 0, 0));
-    PD_TRY(conv(s.proj_out, h3, out, 0, 1.f, &xr));
+    PD_TRY(gemm(s.ff2, g, h3, {.R = &h2}));
+    PD_TRY(conv(s.proj_out, h3, out, {.R = &xr}));
     arena.release(mk);
     return 0;
 }
@@ -1249,7 +1218,7 @@ int pd_engine::run_controlnet(const Act& x_in_full, int emb_row, int emb_stride,
         Act o;
         if (b.kind == 0) {
             o = new_act(x_in.B, x_in.H, x_in.W, b.cout, S);
-            PD_TRY(conv(b.conv, x_in, o, 0, 1.f, &hint));  // h = conv_in(x) + guided_hint, :315-317
+            PD_TRY(conv(b.conv, x_in, o, {.R = &hint}));  // h = conv_in(x) + guided_hint, :315-317
         } else if (b.kind == 2) {
             o = new_act(h.B, h.H / 2, h.W / 2, b.cout, S);
             PD_TRY(conv(b.conv, h, o));
@@ -1264,7 +1233,7 @@ int pd_engine::run_controlnet(const Act& x_in_full, int emb_row, int emb_stride,
         h = o;
         Act c = ctl((int)i);
         if (c.B != h.B) { pd_set_error("internal: control tensor %d sized for batch %d, block output has %d", (int)i, c.B, h.B); return 1; }
-        PD_TRY(conv(n.zero[i], h, c, 0, scales ? scales[i] : 1.f));
+        PD_TRY(conv(n.zero[i], h, c, {.scale = scales ? scales[i] : 1.f}));
     }
     Act m0, m1, m2;
     PD_TRY(resblock(n.mid0, h, m0, emb_ptr(ses.emb_c, n.mid0, emb_row), emb_stride ? n.mid0.cout : 0));
@@ -1272,7 +1241,7 @@ int pd_engine::run_controlnet(const Act& x_in_full, int emb_row, int emb_stride,
     PD_TRY(resblock(n.mid2, m1, m2, emb_ptr(ses.emb_c, n.mid2, emb_row), emb_stride ? n.mid2.cout : 0));
     const int last = (int)n.enc.size();
     Act cl = ctl(last);
-    PD_TRY(conv(n.mid_out, m2, cl, 0, scales ? scales[last] : 1.f));
+    PD_TRY(conv(n.mid_out, m2, cl, {.scale = scales ? scales[last] : 1.f}));
     return 0;
 }
 
@@ -1352,13 +1321,13 @@ int pd_engine::run_unet(const Act& x_in_full, int emb_row, int emb_stride, bool 
         }
         if (b.up) {
             Act o3 = new_act(o.B, o.H * 2, o.W * 2, o.C, S);
-            PD_TRY(conv(b.upconv, o, o3, 0, 1.f, nullptr, nullptr, 0, /*ups=*/1));  // Upsample: nearest x2 then conv, :115-117
+            PD_TRY(conv(b.upconv, o, o3, {.ups = 1}));  // Upsample: nearest x2 then conv, :115-117
             o = o3;
         }
         h = o;
     }
     eps = new_act(h.B, h.H, h.W, round_up(cfg.out_channels, 4), DT_F32);
-    PD_TRY(conv_gn(n.outconv, h, eps, n.out_g, n.out_b, 1e-5f, true, nullptr, nullptr, 0));
+    PD_TRY(conv_gn(n.outconv, h, eps, n.out_g, n.out_b, 1e-5f, true));
     return 0;
 }
 

@@ -247,6 +247,41 @@ struct Arena {
     void release(size_t m) { top = m; }
 };
 
+// A split-K conv whose only consumer is a single-kernel GroupNorm (resblock conv1 -> norm2 at the 16x16 / 8x8 levels) leaves its
+// slabs un-summed: `allow` is set by the caller of gemm(), `active` by gemm() when it did skip the finalize pass; the slabs
+// stay on the workspace stack until the caller's own mark is released.
+struct SlabDefer { bool allow = false, active = false; const float* slabs = nullptr; int nslab = 0; const float* bias = nullptr; const float* rowvec = nullptr; int rowvec_stride = 0; };
+
+// Everything a gemm() / conv() call says besides the weight, the input and the output; the defaults are a plain linear layer.
+struct GemmCall {
+    int stride = 1, ups = 0;                                  // conv geometry (conv() takes the stride from its ConvW); ups: nearest x2 in the gather
+    Activation act = ACT_NONE;                                // (a GEGLU weight matrix implies ACT_GEGLU)
+    float scale = 1.f;
+    const Act* R = nullptr;                                   // residual
+    const float* rowvec = nullptr; int rowvec_stride = 0;     // per-sample row vector (time embedding)
+    bool a_silu = false;                                      // SiLU on the input while it is loaded
+    void* VT = nullptr; int vt_begin = 0, vt_ld = 0;          // V^T side output of the columns from vt_begin on
+    int ldc = 0;                                              // output row stride (0: out.C)
+    const float* gn_coef = nullptr; bool gn_silu = false;     // GroupNorm applied while staging (patch conv)
+    const LnStats* ln_in = nullptr; LnStats* ln_out = nullptr;   // LayerNorm of the input folded in / row statistics of the output wanted
+    const float *a_scale = nullptr, *c_scale = nullptr;       // fp8 row scales of the input / the output
+    const float* gate = nullptr;                              // MMDiT: gated residual, joint-buffer row remaps (GemmParams)
+    int gate_stride = 0, c_sample_rows = 0, c_row_off = 0, vt_tok_off = 0, a_sample_rows = 0, a_row_off = 0;
+    int pad_shift = 0;                                        // ConvW::pad_shift, set by conv()
+    SlabDefer* defer = nullptr;
+};
+
+// Which kernel a gemm() call takes (pd_engine::plan_gemm): the verbose-2 dispatch trace prints exactly this.
+enum GemmFamily { GEMM_GEMV, GEMM_PATCH1, GEMM_PATCH2, GEMM_PATCH4, GEMM_RING, GEMM_IGEMM };
+struct GemmPlan {
+    GemmFamily family = GEMM_IGEMM;
+    int splitk = 1, big_tile = 0, ring_tile = 0;   // K (igemm) or channel-chunk (patch) slices; GemmParams::big_tile (igemm); launch_ring_gemm's tile (ring)
+    bool fused_tile_cnt = false;  // split-K finalize in the last-arriving slice (option "splitk_fused")
+    bool defer_finalize = false;  // the caller's SlabDefer is honoured: no finalize pass
+    int stats_parts = 0;          // LayerNorm-statistics partials per row from this launch's own epilogue (0: none)
+    bool patch() const { return family == GEMM_PATCH1 || family == GEMM_PATCH2 || family == GEMM_PATCH4; }
+};
+
 struct KVSlot { void* K = nullptr; void* VT = nullptr; void* P = nullptr; };   // P: K / V^T in st_tail.hip's fragment order (fused blocks)
 
 struct Session {
@@ -426,15 +461,7 @@ struct pd_engine {
     int sd3_embed(Sd3NetW& net, const Sd3Io& io, bool controlnet, Act& hs, Act& c, Act& modbuf);
     int sd3_block(const Sd3BlockW& b, Act& x, Act& c, const Act& modbuf, const Act& qk, const Act& vt, const Act* pre_add = nullptr);
     int sd3_forward(const Sd3Io& io, float* v_out_dev, int control_index, float* control_out_dev);
-    // one-shot extras of the next gemm() call (MMDiT: gated residual, joint-buffer row remap)
-    // A split-K conv whose only consumer is a single-kernel GroupNorm (resblock conv1 -> norm2 at the 16x16 / 8x8 levels) leaves its
-    // slabs un-summed: `allow` is set by the caller of gemm(), `active` by gemm() when it did skip the finalize pass; the slabs
-    // stay on the workspace stack until the caller's own mark is released.
-    struct SlabDefer { bool allow = false, active = false; const float* slabs = nullptr; int nslab = 0; const float* bias = nullptr; const float* rowvec = nullptr; int rowvec_stride = 0; };
-    SlabDefer* gx_defer = nullptr;   // one-shot, like gx: consumed (and cleared) by the next gemm()
-    int opt_slab_gn = 1;             // the fusion above (option "slab_gn")
-    struct GemmExtra { const float* a_scale = nullptr; const float* c_scale = nullptr; const float* gate = nullptr; int gate_stride = 0, c_sample_rows = 0, c_row_off = 0, vt_tok_off = 0, a_sample_rows = 0, a_row_off = 0;
-                       int pad_shift = 0; } gx;   // pad_shift: ConvW::pad_shift, set by conv()
+    int opt_slab_gn = 1;             // split-K conv1 -> single-kernel norm2 without a finalize pass (SlabDefer; option "slab_gn")
     int opt_sd3_fp8 = 0;       // 0 off, 1: the AdaLN-fed projections, 2: also the feed-forward-out projections (e4m3 GELU output under a norm bound)  // SD3 path: QKV and feed-forward-in projections in PREC_FP8 (e4m3 operands, per-row scales)
     bool sd3_fp8_dirty = true;
     int sd3_quantize();        // (re)builds the e4m3 weights of those layers after a weight change
@@ -475,19 +502,23 @@ struct pd_engine {
 
     // primitive ops (enqueue on stream; honour arena.dry)
     Act new_act(int B, int H, int W, int C, int dt);
-    int gemm(const WMat& m, const Act& in, Act& out, int taps_stride, int ups, int act, float scale, const Act* R,
-             const float* rowvec, int rowvec_stride, bool a_silu, void* VT, int vt_begin, int vt_ld, int ldc_override = 0,
-             const float* gn_coef = nullptr, bool gn_silu = false, const LnStats* ln_in = nullptr, LnStats* ln_out = nullptr);
+    // gemm() = check + fill (call -> GemmParams), plan (which kernel: shapes, options and ncu only), run (workspace, launch, profiling)
+    int gemm(const WMat& m, const Act& in, Act& out, const GemmCall& c = {});
+    int check_gemm(const WMat& m, const Act& in, const Act& out, const GemmCall& c) const;
+    static GemmParams fill_gemm(const WMat& m, const Act& in, const Act& out, const GemmCall& c);
+    GemmPlan plan_gemm(const GemmParams& p, const WMat& m, const GemmCall& c, bool allow_splitk = true) const;
+    int patch_tiles(const GemmParams& p) const; bool patch_unsplit(int ptiles) const;
     int fold_layernorms();     // (re)builds the folded weights of every transformer block after a weight change
     bool ln_dirty = true;
     int opt_ln_fuse = -1;      // -1: on in the 2-byte modes, off in the fp32-storage modes; 0 / 1: forced
     bool opt_st_fuse = true;   // 320-channel SpatialTransformer blocks: one kernel for everything after self-attention (2-byte modes)
     bool st_tail_on(const STW& s, int rows_per_sample) const;
     int gn_stats(const Act& x, int& nchunk);
-    int conv_gn(const ConvW& c, const Act& x, Act& out, const float* g, const float* b, float eps, bool silu, const Act* R,
-                const float* rowvec, int rowvec_stride, SlabDefer* out_defer = nullptr, const SlabDefer* in_slabs = nullptr);
-    int conv(const ConvW& c, const Act& in, Act& out, int act = 0, float scale = 1.f, const Act* R = nullptr,
-             const float* rowvec = nullptr, int rowvec_stride = 0, int ups = 0);
+    // conv3x3 / conv1x1 of `c`: call.stride and call.pad_shift come from the ConvW.  conv_gn: conv(act(GroupNorm(x))); call carries the
+    // residual / row vector / defer pointer of the conv
+    int conv(const ConvW& c, const Act& in, Act& out, GemmCall call = {});
+    int conv_gn(const ConvW& c, const Act& x, Act& out, const float* g, const float* b, float eps, bool silu, GemmCall call = {},
+                const SlabDefer* in_slabs = nullptr);
     int groupnorm(const Act& x, Act& y, const float* g, const float* b, float eps, bool silu, const SlabDefer* from_slabs = nullptr);
     int layernorm(const Act& x, Act& y, const float* g, const float* b);
     int resblock(const ResW& r, const Act& x, Act& out, const float* embrow, int emb_stride);

@@ -506,14 +506,15 @@ __global__ __launch_bounds__(256) void splitk_finalize_kernel(GemmParams p) {
 }
 
 template <int P, int BM, int BN, int WM, int WN, bool CONV, bool AF32, bool GG = false, bool MM = false>
-int launch_one(const GemmParams& p, hipStream_t s, hipEvent_t mid) {
+int launch_one(const GemmParams& p, hipStream_t s, hipEvent_t mid, int* parts) {
     constexpr int NTHREADS = WM * WN * 64;
     constexpr int SMEM_BYTES = 2 * (BM + BN) * BKB + ((GG || MM) ? 0 : BM * 8);   // staging buffers + {mean, rstd} of the block's rows (LayerNorm fold)
     static unsigned long long attr_done = 0;
+    const int mtiles = (p.M + BM - 1) / BM, ntiles = (p.N + BN - 1) / BN;
+    if (parts) { *parts = ntiles * WN; return 0; }   // gemm_stats_parts: which tile, no launch
     auto kfn = igemm_kernel<P, BM, BN, WM, WN, CONV, AF32, GG, MM>;
     if (ensure_dyn_smem(reinterpret_cast<const void*>(kfn), SMEM_BYTES, &attr_done)) return 1;
-    const int mtiles = (p.M + BM - 1) / BM, ntiles = (p.N + BN - 1) / BN;
-    if (p.stats_out && p.stats_parts != ntiles * WN) return 1;   // the caller sized the statistics rows for another tile
+    if (p.stats_out && p.stats_parts != ntiles * WN) return 1;   // the statistics rows were sized for another tile
     dim3 grid(mtiles * ntiles, p.splitk > 1 ? p.splitk : 1);
     hipLaunchKernelGGL(kfn, grid, dim3(NTHREADS), SMEM_BYTES, s, p);
     if (hipGetLastError() != hipSuccess) return 1;
@@ -543,16 +544,16 @@ int gemm_tiles(int M, int N) { return ((M + 127) / 128) * ((N + 159) / 160); }
 
 namespace {
 // PREC_FP8: linear layers with the MMDiT epilogue only (the SD3 path's QKV and feed-forward-in projections)
-int launch_fp8(const GemmParams& p, hipStream_t s, hipEvent_t mid) {
+int launch_fp8(const GemmParams& p, hipStream_t s, hipEvent_t mid, int* parts) {
     if (p.taps != 1 || p.a_dt != DT_FP8 || !p.a_scale || !p.w_scale || p.act == 2 || p.Kpad % 128) return 1;
-    if (p.splitk > 1) return launch_one<PREC_FP8, 128, 160, 2, 2, false, false, false, true>(p, s, mid);   // fp32 slabs; the finalize pass applies the scales
-    if (p.big_tile == 4) return launch_one<PREC_FP8, 256, 192, 4, 2, false, false, false, true>(p, s, mid);
-    if (p.big_tile == 1 || p.big_tile == 3) return launch_one<PREC_FP8, 256, 160, 4, 2, false, false, false, true>(p, s, mid);
-    return launch_one<PREC_FP8, 128, 160, 2, 2, false, false, false, true>(p, s, mid);
+    if (p.splitk > 1) return launch_one<PREC_FP8, 128, 160, 2, 2, false, false, false, true>(p, s, mid, parts);   // fp32 slabs; the finalize pass applies the scales
+    if (p.big_tile == 4) return launch_one<PREC_FP8, 256, 192, 4, 2, false, false, false, true>(p, s, mid, parts);
+    if (p.big_tile == 1 || p.big_tile == 3) return launch_one<PREC_FP8, 256, 160, 4, 2, false, false, false, true>(p, s, mid, parts);
+    return launch_one<PREC_FP8, 128, 160, 2, 2, false, false, false, true>(p, s, mid, parts);
 }
 
 template <int P>
-int launch_prec(const GemmParams& p, hipStream_t s, hipEvent_t mid) {
+int launch_prec(const GemmParams& p, hipStream_t s, hipEvent_t mid, int* parts) {
     constexpr bool F = prec_f32_storage(P);
     const bool conv = p.taps != 1;
     const bool af32 = !F && p.a_dt == DT_F32;          // 2-byte compute reading an fp32 A (converted while staging)
@@ -564,17 +565,17 @@ int launch_prec(const GemmParams& p, hipStream_t s, hipEvent_t mid) {
         // 256 x 320 on 4 x 2 waves (wave tile 64 x 160 = one GEGLU block): 14 fragment reads per 40 MFMAs.  Round 1 ran it on
         // 8 x 1 waves (32 x 320: 22 reads per 40 MFMAs, every wave re-reading all weight fragments), which made the tile
         // LDS-read bound (352 KB per K step = 1375 LDS cycles against 1280 MFMA cycles).
-        if (tile == 3) return launch_one<P, 256, 320, 4, 2, false, false, true>(p, s, mid);
-        if (tile == 1) return launch_one<P, 256, 160, 8, 1, false, false, true>(p, s, mid);
-        return launch_one<P, 128, 160, 4, 1, false, false, true>(p, s, mid);
+        if (tile == 3) return launch_one<P, 256, 320, 4, 2, false, false, true>(p, s, mid, parts);
+        if (tile == 1) return launch_one<P, 256, 160, 8, 1, false, false, true>(p, s, mid, parts);
+        return launch_one<P, 128, 160, 4, 1, false, false, true>(p, s, mid, parts);
     }
     if constexpr (!F) {
         // 256 x 192 on 4 x 2 waves: the tile of widths that are multiples of 192 but not of 160 (MMDiT: 1536 = 8 x 192,
         // 4608, 6144) -- no padded columns, and 8192 rows x 1536 columns is exactly one block per CU
         if (tile == 4) {
             if (conv || af32) return 1;
-            if (p.act == 4 || p.gate || p.c_sample_rows || p.a_sample_rows) return launch_one<P, 256, 192, 4, 2, false, false, false, true>(p, s, mid);
-            return launch_one<P, 256, 192, 4, 2, false, false, false, false>(p, s, mid);
+            if (p.act == 4 || p.gate || p.c_sample_rows || p.a_sample_rows) return launch_one<P, 256, 192, 4, 2, false, false, false, true>(p, s, mid, parts);
+            return launch_one<P, 256, 192, 4, 2, false, false, false, false>(p, s, mid, parts);
         }
     }
     // (measured and dropped: 128 x 192 four-wave blocks, two per CU so that one block's epilogue runs under the other's K loop
@@ -583,41 +584,46 @@ int launch_prec(const GemmParams& p, hipStream_t s, hipEvent_t mid) {
         if (p.ln_stats || p.stats_out) return 1;   // no LayerNorm fold in the MM instantiations: linear layers over operands of the compute type
         if (conv || af32) return 1;
         if constexpr (F) {
-            if (tile == 1 || tile == 3) return launch_one<P, 256, 160, 4, 2, false, false, false, true>(p, s, mid);
-            return launch_one<P, 128, 160, 2, 2, false, false, false, true>(p, s, mid);
+            if (tile == 1 || tile == 3) return launch_one<P, 256, 160, 4, 2, false, false, false, true>(p, s, mid, parts);
+            return launch_one<P, 128, 160, 2, 2, false, false, false, true>(p, s, mid, parts);
         } else {
             // (the 256 x 320 tile spills 896 B per lane with the extras compiled in: its launches take the 256 x 160 tile)
-            if (tile == 2) return launch_one<P, 128, 160, 4, 2, false, false, false, true>(p, s, mid);
-            if (tile == 1 || tile == 3) return launch_one<P, 256, 160, 4, 2, false, false, false, true>(p, s, mid);
-            return launch_one<P, 128, 160, 2, 2, false, false, false, true>(p, s, mid);
+            if (tile == 2) return launch_one<P, 128, 160, 4, 2, false, false, false, true>(p, s, mid, parts);
+            if (tile == 1 || tile == 3) return launch_one<P, 256, 160, 4, 2, false, false, false, true>(p, s, mid, parts);
+            return launch_one<P, 128, 160, 2, 2, false, false, false, true>(p, s, mid, parts);
         }
     }
     if constexpr (F) {   // fp32 mode: the 128x160 / 256x160 four-wave-group tiles only
-        if (tile == 1 || tile == 3) return conv ? launch_one<P, 256, 160, 4, 2, true, false>(p, s, mid) : launch_one<P, 256, 160, 4, 2, false, false>(p, s, mid);
-        return conv ? launch_one<P, 128, 160, 2, 2, true, false>(p, s, mid) : launch_one<P, 128, 160, 2, 2, false, false>(p, s, mid);
+        if (tile == 1 || tile == 3) return conv ? launch_one<P, 256, 160, 4, 2, true, false>(p, s, mid, parts) : launch_one<P, 256, 160, 4, 2, false, false>(p, s, mid, parts);
+        return conv ? launch_one<P, 128, 160, 2, 2, true, false>(p, s, mid, parts) : launch_one<P, 128, 160, 2, 2, false, false>(p, s, mid, parts);
     } else {
-        if (tile == 3 && !conv && !af32) return launch_one<P, 256, 320, 4, 2, false, false>(p, s, mid);
-        if (tile == 2 && !conv && !af32) return launch_one<P, 128, 160, 4, 2, false, false>(p, s, mid);
+        if (tile == 3 && !conv && !af32) return launch_one<P, 256, 320, 4, 2, false, false>(p, s, mid, parts);
+        if (tile == 2 && !conv && !af32) return launch_one<P, 128, 160, 4, 2, false, false>(p, s, mid, parts);
         if (tile == 1 || tile == 3) {
-            if (conv) return af32 ? launch_one<P, 256, 160, 4, 2, true, true>(p, s, mid) : launch_one<P, 256, 160, 4, 2, true, false>(p, s, mid);
-            return af32 ? launch_one<P, 256, 160, 4, 2, false, true>(p, s, mid) : launch_one<P, 256, 160, 4, 2, false, false>(p, s, mid);
+            if (conv) return af32 ? launch_one<P, 256, 160, 4, 2, true, true>(p, s, mid, parts) : launch_one<P, 256, 160, 4, 2, true, false>(p, s, mid, parts);
+            return af32 ? launch_one<P, 256, 160, 4, 2, false, true>(p, s, mid, parts) : launch_one<P, 256, 160, 4, 2, false, false>(p, s, mid, parts);
         }
-        if (conv) return af32 ? launch_one<P, 128, 160, 2, 2, true, true>(p, s, mid) : launch_one<P, 128, 160, 2, 2, true, false>(p, s, mid);
-        return af32 ? launch_one<P, 128, 160, 2, 2, false, true>(p, s, mid) : launch_one<P, 128, 160, 2, 2, false, false>(p, s, mid);
+        if (conv) return af32 ? launch_one<P, 128, 160, 2, 2, true, true>(p, s, mid, parts) : launch_one<P, 128, 160, 2, 2, true, false>(p, s, mid, parts);
+        return af32 ? launch_one<P, 128, 160, 2, 2, false, true>(p, s, mid, parts) : launch_one<P, 128, 160, 2, 2, false, false>(p, s, mid, parts);
     }
 }
 }  // namespace
 
-int launch_gemm(const GemmParams& p, int prec, hipStream_t s, hipEvent_t mid) {
+int launch_gemm(const GemmParams& p, int prec, hipStream_t s, hipEvent_t mid, int* parts) {
     if (p.M <= 0 || p.N <= 0) return 0;
     if (p.splitk > 1 && (p.act == 2 || p.vt_begin < p.N || !p.slab || p.N % 4)) return 1;
-    if (prec == PREC_FP8) return launch_fp8(p, s, mid);
+    if (prec == PREC_FP8) return launch_fp8(p, s, mid, parts);
     if (prec_f32_storage(prec) ? p.a_dt != DT_F32 : (p.a_dt != DT_F32 && p.a_dt != prec)) return 1;   // operand type must match the mode
     switch (prec) {
-        case DT_F32: return launch_prec<DT_F32>(p, s, mid);
-        case PREC_F16X2: return launch_prec<PREC_F16X2>(p, s, mid);
-        case DT_BF16: return launch_prec<DT_BF16>(p, s, mid);
-        case DT_F16: return launch_prec<DT_F16>(p, s, mid);
+        case DT_F32: return launch_prec<DT_F32>(p, s, mid, parts);
+        case PREC_F16X2: return launch_prec<PREC_F16X2>(p, s, mid, parts);
+        case DT_BF16: return launch_prec<DT_BF16>(p, s, mid, parts);
+        case DT_F16: return launch_prec<DT_F16>(p, s, mid, parts);
         default: return 1;
     }
+}
+
+int gemm_stats_parts(const GemmParams& p, int prec) {
+    int parts = 0;
+    return launch_gemm(p, prec, nullptr, nullptr, &parts) ? 0 : parts;
 }

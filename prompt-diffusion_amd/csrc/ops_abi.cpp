@@ -68,7 +68,7 @@ int pd_op_conv2d(pd_engine* e, const float* x, const float* w, const float* bias
     o.p = out.p; o.B = B; o.H = Ho; o.W = Wo; o.C = copad; o.dt = odt;
     r = o; r.p = res.p; r.dt = e->S;
     if (residual) PD_TRY(to_dev_nhwc(e, residual, res.p, e->S, B, Cout, Ho, Wo, copad));
-    PD_TRY(e->conv(c, a, o, act_silu, scale, residual ? &r : nullptr, nullptr, 0, upsample));
+    PD_TRY(e->conv(c, a, o, {.ups = upsample, .act = act_silu ? ACT_SILU : ACT_NONE, .scale = scale, .R = residual ? &r : nullptr}));
     return from_dev_nhwc(e, out.p, odt, y, B, Cout, Ho, Wo, copad);
 }
 
@@ -151,7 +151,7 @@ int pd_op_linear(pd_engine* e, const float* x, const float* w, const float* bias
     Act a, o;
     a.p = in.p; a.B = M; a.H = 1; a.W = 1; a.C = K; a.dt = adt;
     o.p = out.p; o.B = M; o.H = 1; o.W = 1; o.C = round_up(N, 4); o.dt = DT_F32;
-    PD_TRY(e->gemm(m, a, o, 1, 0, 0, 1.f, nullptr, nullptr, 0, a_silu != 0, nullptr, 0, 0));
+    PD_TRY(e->gemm(m, a, o, {.a_silu = a_silu != 0}));
     HIP_OK(hipStreamSynchronize(e->stream));
     std::vector<float> host((size_t)M * o.C);
     HIP_OK(hipMemcpy(host.data(), out.p, host.size() * 4, hipMemcpyDeviceToHost));
@@ -189,8 +189,7 @@ int pd_op_linear_fp8(pd_engine* e, const float* x, const float* w, const float* 
     Act a, o;
     a.p = x8.p; a.B = M; a.H = 1; a.W = 1; a.C = m.Kpad8; a.dt = DT_FP8;
     o.p = out.p; o.B = M; o.H = 1; o.W = 1; o.C = round_up(N, 4); o.dt = DT_F32;
-    e->gx.a_scale = reinterpret_cast<float*>(xs.p);
-    PD_TRY(e->gemm(m, a, o, 1, 0, act, 1.f, nullptr, nullptr, 0, false, nullptr, 0, 0));
+    PD_TRY(e->gemm(m, a, o, {.act = (Activation)act, .a_scale = reinterpret_cast<float*>(xs.p)}));
     HIP_OK(hipStreamSynchronize(e->stream));
     std::vector<float> host((size_t)M * o.C);
     HIP_OK(hipMemcpy(host.data(), out.p, host.size() * 4, hipMemcpyDeviceToHost));
@@ -297,7 +296,7 @@ int pd_op_spatial_transformer(pd_engine* e, const char* prefix, const float* x, 
         Act c, k;
         c.p = cdev.p; c.B = B; c.H = L; c.W = 1; c.C = Dp; c.dt = e->T;
         k.p = kbuf.p; k.B = B; k.H = L; k.W = 1; k.C = C; k.dt = e->T;
-        if ((rc = e->gemm(st->kv2, c, k, 1, 0, 0, 1.f, nullptr, nullptr, 0, false, vtbuf.p, C, lpad))) break;
+        if ((rc = e->gemm(st->kv2, c, k, {.VT = vtbuf.p, .vt_begin = C, .vt_ld = lpad}))) break;
         KVSlot kv;
         kv.K = kbuf.p; kv.VT = vtbuf.p;
         if (e->st_tail_on(*st, N) && st->tail_w) {
@@ -332,8 +331,8 @@ int pd_op_time_embed(pd_engine* e, int net, const int64_t* t, int n, float* temb
     te.p = a.p; te.B = n; te.H = te.W = 1; te.C = mc; te.dt = DT_F32;
     e1 = te; e1.p = b.p; e1.C = td;
     e2 = e1; e2.p = c.p;
-    PD_TRY(e->gemm(nw.te0, te, e1, 1, 0, /*silu*/ 1, 1.f, nullptr, nullptr, 0, false, nullptr, 0, 0));
-    PD_TRY(e->gemm(nw.te2, e1, e2, 1, 0, 0, 1.f, nullptr, nullptr, 0, false, nullptr, 0, 0));
+    PD_TRY(e->gemm(nw.te0, te, e1, {.act = ACT_SILU}));
+    PD_TRY(e->gemm(nw.te2, e1, e2));
     HIP_OK(hipStreamSynchronize(e->stream));
     HIP_OK(hipMemcpy(emb, c.p, (size_t)n * td * 4, hipMemcpyDeviceToHost));
     return 0;

@@ -145,6 +145,7 @@ static inline int ensure_dyn_smem(const void* fn, int bytes, unsigned long long*
 // ---------------------------------------------------------------------------------------------
 // Implicit-GEMM convolution / linear:  C[M,N] = epilogue( A_gather[M,K] x W[N,K]^T )
 // ---------------------------------------------------------------------------------------------
+enum Activation { ACT_NONE = 0, ACT_SILU = 1, ACT_GEGLU = 2, ACT_QUICK_GELU = 3, ACT_TANH_GELU = 4 };   // GemmParams::act (the kernels compare against the values)
 struct GemmParams {
     const void* A;        // activations, NHWC (conv) or [M, lda] rows (linear)
     const void* W;        // weights [Nw][Kpad] in the compute type, K-contiguous (taps x Cin)
@@ -162,7 +163,7 @@ struct GemmParams {
     int Hin, Win, Hout, Wout, stride, ups;  // conv geometry; ups=1: nearest x2 upsample fused in the gather
     int rows_per_sample;  // Hout*Wout (conv) or tokens per sample (linear)
     int rowvec_stride;    // elements between samples in rowvec (0: one row for all)
-    int act;              // 0 none, 1 SiLU, 2 GEGLU (weights pre-interleaved in 80+80 blocks), 3 quick-GELU, 4 tanh-GELU
+    int act;              // Activation: 0 none, 1 SiLU, 2 GEGLU (weights pre-interleaved in 80+80 blocks), 3 quick-GELU, 4 tanh-GELU
     int a_silu;           // apply SiLU to A on load (emb_layers)
     float out_scale;      // applied to (acc + bias [+ rowvec]) before the residual
     int vt_begin, vt_ld;  // see VT
@@ -221,10 +222,14 @@ struct AttnParams {
     int causal;  // keys after the query are masked (CLIP text transformer)
 };
 
-int launch_gemm(const GemmParams& p, int prec, hipStream_t s, hipEvent_t mid = nullptr);   // prec: the compute type (DT_*)
+int launch_gemm(const GemmParams& p, int prec, hipStream_t s, hipEvent_t mid = nullptr, int* parts = nullptr);   // prec: the compute type (DT_*)
+// LayerNorm-statistics partials per row (GemmParams::stats_parts) that launch_gemm / launch_ring_gemm write for this launch:
+// column tiles x waves across N of the tile their dispatch takes (parts != null runs that dispatch without launching); 0: none
+int gemm_stats_parts(const GemmParams& p, int prec);
+int ring_gemm_stats_parts(const GemmParams& p, int prec, int tile);
 // gemm_ring.hip: persistent LDS-DMA ring GEMM for plain linear layers over 2-byte operands (tile 0: 128 x 160, 1: 256 x 160)
 bool ring_gemm_eligible(const GemmParams& p, int prec);
-int launch_ring_gemm(const GemmParams& p, int prec, int tile, hipStream_t s);
+int launch_ring_gemm(const GemmParams& p, int prec, int tile, hipStream_t s, int* parts = nullptr);
 // fp8 (e4m3) rows with one scale per row: dst[r][k] = e4m3(src[r][k] / scale[r]), scale[r] = max_k |src[r][k]| / 448 (weights of
 // the SD3 linear layers that run in PREC_FP8); src in dtype src_dt with row stride src_ld, dst row stride dst_ld >= K (pad zeroed)
 int launch_quant_rows(const void* src, int src_dt, int src_ld, void* dst, int dst_ld, float* scale, int rows, int K, hipStream_t s);

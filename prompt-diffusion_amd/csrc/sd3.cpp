@@ -145,7 +145,7 @@ int pd_engine::sd3_embed(Sd3NetW& net, const Sd3Io& io, bool controlnet, Act& hs
             return 1;
         }
     }
-    PD_TRY(gemm(pe, rows, hs, 1, 0, 0, 1.f, &pos, nullptr, 0, false, nullptr, 0, 0));
+    PD_TRY(gemm(pe, rows, hs, {.R = &pos}));
     if (controlnet) {   // hidden_states + pos_embed_input(cond) + pos_embed_input(example pair)   (:440)
         WMat pi = net.pe_in;
         pi.taps = 1; pi.cin = pi.cin_pad = net.pe_in.K;
@@ -158,7 +158,7 @@ int pd_engine::sd3_embed(Sd3NetW& net, const Sd3Io& io, bool controlnet, Act& hs
                     return 1;
                 }
             }
-            PD_TRY(gemm(pi, rows, hs, 1, 0, 0, 1.f, &hs, nullptr, 0, false, nullptr, 0, 0));   // in place: R == C element-wise
+            PD_TRY(gemm(pi, rows, hs, {.R = &hs}));   // in place: R == C element-wise
         }
     }
     // temb = MLP(sinusoid(t)) + MLP(pooled)
@@ -177,12 +177,12 @@ int pd_engine::sd3_embed(Sd3NetW& net, const Sd3Io& io, bool controlnet, Act& hs
             HIP_OK(hipMemcpy2DAsync(pooled.p, (size_t)pooled.C * 4, src, (size_t)sd3.pooled_dim * 4, (size_t)sd3.pooled_dim * 4, B,
                                     hipMemcpyDeviceToDevice, stream));
     }
-    PD_TRY(gemm(net.t1, sin_t, u, 1, 0, /*SiLU*/ 1, 1.f, nullptr, nullptr, 0, false, nullptr, 0, 0));
-    PD_TRY(gemm(net.t2, u, temb, 1, 0, 0, 1.f, nullptr, nullptr, 0, false, nullptr, 0, 0));
-    PD_TRY(gemm(net.p1, pooled, u, 1, 0, 1, 1.f, nullptr, nullptr, 0, false, nullptr, 0, 0));
-    PD_TRY(gemm(net.p2, u, temb, 1, 0, 0, 1.f, &temb, nullptr, 0, false, nullptr, 0, 0));
+    PD_TRY(gemm(net.t1, sin_t, u, {.act = ACT_SILU}));
+    PD_TRY(gemm(net.t2, u, temb));
+    PD_TRY(gemm(net.p1, pooled, u, {.act = ACT_SILU}));
+    PD_TRY(gemm(net.p2, u, temb, {.R = &temb}));
     // every AdaLN modulation of the net: Linear(SiLU(temb)) stacked
-    PD_TRY(gemm(net.mod, temb, modbuf, 1, 0, 0, 1.f, nullptr, nullptr, 0, /*a_silu=*/true, nullptr, 0, 0));
+    PD_TRY(gemm(net.mod, temb, modbuf, {.a_silu = true}));
     // context_embedder
     if (net.single) { arena.release(mk); return 0; }
     Act ctx = new_act(B, io.S, 1, round_up(sd3.joint_dim, 8), T);
@@ -193,7 +193,7 @@ int pd_engine::sd3_embed(Sd3NetW& net, const Sd3Io& io, bool controlnet, Act& hs
             return 1;
         }
     }
-    PD_TRY(gemm(net.ctx_emb, ctx, c, 1, 0, 0, 1.f, nullptr, nullptr, 0, false, nullptr, 0, 0));
+    PD_TRY(gemm(net.ctx_emb, ctx, c));
     arena.release(mk);
     return 0;
 }
@@ -257,12 +257,10 @@ int pd_engine::sd3_block(const Sd3BlockW& b, Act& x, Act& c, const Act& modbuf, 
     // both QKV GEMMs store straight into the joint buffers
     {
         Act o = qk; o.H = N;
-        gx.c_sample_rows = Nt; gx.c_row_off = 0; gx.vt_tok_off = 0; gx.a_scale = xs;
-        PD_TRY(gemm(b.qkv, xn, o, 1, 0, 0, 1.f, nullptr, nullptr, 0, false, vt.p, 2 * D, vt_ld));
+        PD_TRY(gemm(b.qkv, xn, o, {.VT = vt.p, .vt_begin = 2 * D, .vt_ld = vt_ld, .a_scale = xs, .c_sample_rows = Nt}));
         if (ctx_stream) {
             o.H = Sx;
-            gx.c_sample_rows = Nt; gx.c_row_off = N; gx.vt_tok_off = N; gx.a_scale = cs;
-            PD_TRY(gemm(b.qkv_c, cn, o, 1, 0, 0, 1.f, nullptr, nullptr, 0, false, vt.p, 2 * D, vt_ld));
+            PD_TRY(gemm(b.qkv_c, cn, o, {.VT = vt.p, .vt_begin = 2 * D, .vt_ld = vt_ld, .a_scale = cs, .c_sample_rows = Nt, .c_row_off = N, .vt_tok_off = N}));
         }
     }
     PD_TRY(qk_norm(qk, Nt, N, b.nq, b.nk, b.naq, b.nak));   // per-head RMSNorm of q and k, own weights per stream
@@ -273,22 +271,19 @@ int pd_engine::sd3_block(const Sd3BlockW& b, Act& x, Act& c, const Act& modbuf, 
     const int Nq = b.pre_only ? N : Nt;
     Act att = new_act(B, Nt, 1, D, T);
     PD_TRY(attention(qkp, 2 * D, qkp + (size_t)D * eb, 2 * D, vt.p, vt_ld, att.p, D, B, Nq, Nt, D, heads, false, bs, bs, (long long)Nt * D));
-    gx.gate = mod + b.mod_off + 2 * D; gx.gate_stride = ms; gx.a_sample_rows = Nt; gx.a_row_off = 0;
-    PD_TRY(gemm(b.out, att, x, 1, 0, 0, 1.f, &x, nullptr, 0, false, nullptr, 0, 0));       // x += gate_msa * to_out(o_x)
+    PD_TRY(gemm(b.out, att, x, {.R = &x, .gate = mod + b.mod_off + 2 * D, .gate_stride = ms, .a_sample_rows = Nt}));       // x += gate_msa * to_out(o_x)
     if (!b.pre_only && ctx_stream) {
-        gx.gate = mod + b.mod_c_off + 2 * D; gx.gate_stride = ms; gx.a_sample_rows = Nt; gx.a_row_off = N;
-        PD_TRY(gemm(b.out_c, att, c, 1, 0, 0, 1.f, &c, nullptr, 0, false, nullptr, 0, 0));
+        PD_TRY(gemm(b.out_c, att, c, {.R = &c, .gate = mod + b.mod_c_off + 2 * D, .gate_stride = ms, .a_sample_rows = Nt, .a_row_off = N}));
     }
     if (b.dual) {   // x += gate_msa2 * attn2(norm_hidden_states2): self-attention over the image tokens alone
         const int vl2 = round_up(N, 8);
         Act qk2 = new_act(B, N, 1, 2 * D, T), vt2 = new_act(B, D, 1, vl2, T), att2 = new_act(B, N, 1, D, T);
         if (!arena.dry && vl2 != N) HIP_OK(hipMemsetAsync(vt2.p, 0, vt2.bytes(), stream));
-        PD_TRY(gemm(b.qkv2, xn2, qk2, 1, 0, 0, 1.f, nullptr, nullptr, 0, false, vt2.p, 2 * D, vl2));
+        PD_TRY(gemm(b.qkv2, xn2, qk2, {.VT = vt2.p, .vt_begin = 2 * D, .vt_ld = vl2}));
         PD_TRY(qk_norm(qk2, N, N, b.nq2, b.nk2, nullptr, nullptr));
         const char* q2p = reinterpret_cast<const char*>(qk2.p);
         PD_TRY(attention(q2p, 2 * D, q2p + (size_t)D * eb, 2 * D, vt2.p, vl2, att2.p, D, B, N, N, D, heads));
-        gx.gate = mod + b.mod_off + 8 * D; gx.gate_stride = ms;
-        PD_TRY(gemm(b.out2, att2, x, 1, 0, 0, 1.f, &x, nullptr, 0, false, nullptr, 0, 0));
+        PD_TRY(gemm(b.out2, att2, x, {.R = &x, .gate = mod + b.mod_off + 8 * D, .gate_stride = ms}));
     }
     arena.release(mk);
     // feed-forward of each stream
@@ -298,10 +293,8 @@ int pd_engine::sd3_block(const Sd3BlockW& b, Act& x, Act& c, const Act& modbuf, 
         float* fs = f8b ? scales(B * N) : nullptr;
         PD_TRY(adaln(x, n2, b.mod_off + 3 * D, b.mod_off + 4 * D, ns, nullptr, fs, f8b ? &b.ff1 : nullptr));
         Act f = new_act(B, N, 1, 4 * D, f8b ? DT_FP8 : T);
-        gx.a_scale = ns; gx.c_scale = fs;
-        PD_TRY(gemm(b.ff1, n2, f, 1, 0, /*tanh-GELU*/ 4, 1.f, nullptr, nullptr, 0, false, nullptr, 0, 0));
-        gx.gate = mod + b.mod_off + 5 * D; gx.gate_stride = ms; gx.a_scale = fs;
-        PD_TRY(gemm(b.ff2, f, x, 1, 0, 0, 1.f, &x, nullptr, 0, false, nullptr, 0, 0));
+        PD_TRY(gemm(b.ff1, n2, f, {.act = ACT_TANH_GELU, .a_scale = ns, .c_scale = fs}));
+        PD_TRY(gemm(b.ff2, f, x, {.R = &x, .a_scale = fs, .gate = mod + b.mod_off + 5 * D, .gate_stride = ms}));
         arena.release(mk);
     }
     if (!b.pre_only && ctx_stream) {
@@ -310,10 +303,8 @@ int pd_engine::sd3_block(const Sd3BlockW& b, Act& x, Act& c, const Act& modbuf, 
         float* fs = f8b ? scales(B * Sx) : nullptr;
         PD_TRY(adaln(c, n2, b.mod_c_off + 3 * D, b.mod_c_off + 4 * D, ns, nullptr, fs, f8b ? &b.ffc1 : nullptr));
         Act f = new_act(B, Sx, 1, 4 * D, f8b ? DT_FP8 : T);
-        gx.a_scale = ns; gx.c_scale = fs;
-        PD_TRY(gemm(b.ffc1, n2, f, 1, 0, 4, 1.f, nullptr, nullptr, 0, false, nullptr, 0, 0));
-        gx.gate = mod + b.mod_c_off + 5 * D; gx.gate_stride = ms; gx.a_scale = fs;
-        PD_TRY(gemm(b.ffc2, f, c, 1, 0, 0, 1.f, &c, nullptr, 0, false, nullptr, 0, 0));
+        PD_TRY(gemm(b.ffc1, n2, f, {.act = ACT_TANH_GELU, .a_scale = ns, .c_scale = fs}));
+        PD_TRY(gemm(b.ffc2, f, c, {.R = &c, .a_scale = fs, .gate = mod + b.mod_c_off + 5 * D, .gate_stride = ms}));
         arena.release(mk);
     }
     return 0;
@@ -414,7 +405,7 @@ int pd_engine::sd3_forward(const Sd3Io& io, float* v_out, int control_index, flo
                         }
                     }
                 }
-                PD_TRY(gemm(net.zero[i], in, control[i], 1, 0, 0, io.scale, nullptr, nullptr, 0, false, nullptr, 0, 0));
+                PD_TRY(gemm(net.zero[i], in, control[i], {.scale = io.scale}));
                 if (two && !arena.dry) HIP_OK(hipEventRecord(sd3_ev[i], stream));   // residual i is ready (`stream` is stream2 here)
             }
             arena.release(mk);
@@ -468,7 +459,7 @@ int pd_engine::sd3_forward(const Sd3Io& io, float* v_out, int control_index, flo
             return 1;
         }
     }
-    PD_TRY(gemm(net.proj_out, nx, out, 1, 0, 0, 1.f, nullptr, nullptr, 0, false, nullptr, 0, 0));
+    PD_TRY(gemm(net.proj_out, nx, out));
     if (!arena.dry) {
         ++launches;
         if (launch_unpatchify(out.p, DT_F32, out.C, v_out, B, sd3.out_channels, h, w, ps, stream)) {

@@ -96,13 +96,13 @@ int pd_engine::compute_emb(NetW& net, std::vector<float*>& tabs, const int64_t* 
         HIP_OK(hipStreamSynchronize(stream));
     }
     Act e1 = new_act(n, 1, 1, temb, DT_F32), e2 = new_act(n, 1, 1, temb, DT_F32);
-    PD_TRY(gemm(net.te0, te, e1, 1, 0, /*silu*/ 1, 1.f, nullptr, nullptr, 0, false, nullptr, 0, 0));
-    PD_TRY(gemm(net.te2, e1, e2, 1, 0, 0, 1.f, nullptr, nullptr, 0, false, nullptr, 0, 0));
+    PD_TRY(gemm(net.te0, te, e1, {.act = ACT_SILU}));
+    PD_TRY(gemm(net.te2, e1, e2));
     for (ResW* r : net.res_list) {
         Act o;
         o.B = n; o.H = 1; o.W = 1; o.C = r->cout; o.dt = DT_F32;
         o.p = tabs[r->emb_slot] + (size_t)row0 * r->cout;
-        PD_TRY(gemm(r->emb, e2, o, 1, 0, 0, 1.f, nullptr, nullptr, 0, /*a_silu*/ true, nullptr, 0, 0));
+        PD_TRY(gemm(r->emb, e2, o, {.a_silu = true}));
     }
     arena.release(mk);
     return 0;
@@ -222,7 +222,7 @@ int pd_engine::session_setup(const pd_sample_args& a, const int64_t* t_rows, int
         for (STW* st : net.st_list) {
             Act k;
             k.p = kv[st->kv_slot].K; k.B = Bf; k.H = L; k.W = 1; k.C = st->C; k.dt = T;
-            PD_TRY(gemm(st->kv2, ctx, k, 1, 0, 0, 1.f, nullptr, nullptr, 0, false, kv[st->kv_slot].VT, st->C, lpad));
+            PD_TRY(gemm(st->kv2, ctx, k, {.VT = kv[st->kv_slot].VT, .vt_begin = st->C, .vt_ld = lpad}));
             if (kv[st->kv_slot].P && !arena.dry) {   // the same K / V^T in the fused tail's fragment order
                 ++launches;
                 if (launch_st_tail_kv_pack(k.p, kv[st->kv_slot].VT, kv[st->kv_slot].P, Bf, L, lpad, stream)) {
@@ -268,13 +268,13 @@ int pd_engine::session_setup(const pd_sample_args& a, const int64_t* t_rows, int
                 if (l < 7) {
                     Act o = new_act(hb, Ho, Wo, round_up(c.cout, 8), T);
                     if (o.C != c.cout) { pd_set_error("hint widths must be multiples of 8"); return 1; }
-                    PD_TRY(conv(c, cur, o, /*silu*/ 1));
+                    PD_TRY(conv(c, cur, o, {.act = ACT_SILU}));
                     cur = o;
                 } else if (which == 0) {
                     prev_out = new_act(hb, Ho, Wo, c.cout, S);
                     PD_TRY(conv(c, cur, prev_out));
                 } else {
-                    PD_TRY(conv(c, cur, hint_out, 0, 1.f, &prev_out));
+                    PD_TRY(conv(c, cur, hint_out, {.R = &prev_out}));
                 }
             }
         }
@@ -1085,12 +1085,12 @@ int pd_bench_linear(pd_engine* e, int32_t M, int32_t K, int32_t N, int32_t resid
     o.p = out; o.B = 1; o.H = M; o.W = 1; o.C = N; o.dt = e->T;
     rr = o; rr.p = res;
     int r = 0;
-    for (int i = 0; i < 3 && !r; ++i) r = e->gemm(m, a, o, 1, 0, 0, 1.f, res ? &rr : nullptr, nullptr, 0, false, nullptr, 0, 0);
+    for (int i = 0; i < 3 && !r; ++i) r = e->gemm(m, a, o, {.R = res ? &rr : nullptr});
     hipEvent_t e0, e1;
     HIP_OK(hipEventCreate(&e0));
     HIP_OK(hipEventCreate(&e1));
     HIP_OK(hipEventRecord(e0, e->stream));
-    for (int i = 0; i < iters && !r; ++i) r = e->gemm(m, a, o, 1, 0, 0, 1.f, res ? &rr : nullptr, nullptr, 0, false, nullptr, 0, 0);
+    for (int i = 0; i < iters && !r; ++i) r = e->gemm(m, a, o, {.R = res ? &rr : nullptr});
     HIP_OK(hipEventRecord(e1, e->stream));
     HIP_OK(hipEventSynchronize(e1));
     float t = 0.f;

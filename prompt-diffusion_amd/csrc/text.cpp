@@ -76,17 +76,17 @@ int pd_engine::text_forward(const int* ids_dev, int B, float* out_dev, int clip_
         Act qk = new_act(B, L, 1, 2 * C, T);
         Act vt = new_act(B, C, 1, lpad, T);
         if (!arena.dry && lpad != L) HIP_OK(hipMemsetAsync(vt.p, 0, vt.bytes(), stream));   // pad keys of V^T must read as 0
-        PD_TRY(gemm(l.qkv, ln, qk, 1, 0, 0, 1.f, nullptr, nullptr, 0, false, vt.p, 2 * C, lpad));
+        PD_TRY(gemm(l.qkv, ln, qk, {.VT = vt.p, .vt_begin = 2 * C, .vt_ld = lpad}));
         Act att = new_act(B, L, 1, C, T);
         PD_TRY(attention(qk.p, 2 * C, reinterpret_cast<char*>(qk.p) + (size_t)C * eb, 2 * C, vt.p, lpad, att.p, C, B, L, L, C, H,
                          /*causal=*/true));
         Act h1 = new_act(B, L, 1, C, S);
-        PD_TRY(gemm(l.out, att, h1, 1, 0, 0, 1.f, &x, nullptr, 0, false, nullptr, 0, 0));
+        PD_TRY(gemm(l.out, att, h1, {.R = &x}));
         PD_TRY(layernorm(h1, ln, l.ln2_g, l.ln2_b));
         Act f = new_act(B, L, 1, F, T);
-        PD_TRY(gemm(l.fc1, ln, f, 1, 0, /*act=quick_gelu*/ 3, 1.f, nullptr, nullptr, 0, false, nullptr, 0, 0));
+        PD_TRY(gemm(l.fc1, ln, f, {.act = ACT_QUICK_GELU}));
         Act h2 = new_act(B, L, 1, C, S);
-        PD_TRY(gemm(l.fc2, f, h2, 1, 0, 0, 1.f, &h1, nullptr, 0, false, nullptr, 0, 0));
+        PD_TRY(gemm(l.fc2, f, h2, {.R = &h1}));
         // carry the block output down to the slot below this block's temporaries
         if (!arena.dry) HIP_OK(hipMemcpyAsync(x.p, h2.p, x.bytes(), hipMemcpyDeviceToDevice, stream));
         arena.release(mk);

@@ -132,7 +132,7 @@ int pd_engine::vae_attention(const VaeAttnW& v, const Act& x, Act& out) {
     Act qk = new_act(B, H, W, 2 * C, T);
     const int npad = round_up(N, 8);
     Act vt = new_act(B, C, 1, npad, T);
-    PD_TRY(gemm(v.qkv, a, qk, 1, 0, 0, 1.f, nullptr, nullptr, 0, false, vt.p, 2 * C, npad));
+    PD_TRY(gemm(v.qkv, a, qk, {.VT = vt.p, .vt_begin = 2 * C, .vt_ld = npad}));
     Act att = new_act(B, H, W, C, T);
     float* sc = reinterpret_cast<float*>(arena.alloc((size_t)N * N * sizeof(float)));
     void* pr = arena.alloc((size_t)N * npad * dt_size(T));
@@ -165,7 +165,7 @@ int pd_engine::vae_attention(const VaeAttnW& v, const Act& x, Act& out) {
             launches += 3;
         }
     }
-    PD_TRY(conv(v.proj_out, att, out, 0, 1.f, &x));
+    PD_TRY(conv(v.proj_out, att, out, {.R = &x}));
     arena.release(mk);
     return 0;
 }
@@ -196,12 +196,12 @@ int pd_engine::vae_forward(const float* latents_dev, int B, int h, int w, float*
         }
         if (L.up) {
             Act u = new_act(hcur.B, hcur.H * 2, hcur.W * 2, hcur.C, S);
-            PD_TRY(conv(L.upconv, hcur, u, 0, 1.f, nullptr, nullptr, 0, /*ups=*/1));   // nearest x2 then conv, model.py:62-64
+            PD_TRY(conv(L.upconv, hcur, u, {.ups = 1}));   // nearest x2 then conv, model.py:62-64
             hcur = u;
         }
     }
     Act img = new_act(hcur.B, hcur.H, hcur.W, round_up(cfg.vae_out_ch, 4), DT_F32);
-    PD_TRY(conv_gn(v.conv_out, hcur, img, v.out_g, v.out_b, 1e-6f, true, nullptr, nullptr, 0));
+    PD_TRY(conv_gn(v.conv_out, hcur, img, v.out_g, v.out_b, 1e-6f, true));
     if (!arena.dry) {
         ++launches;
         if (launch_nhwc_to_nchw(img.p, DT_F32, out_dev, B, cfg.vae_out_ch, img.H, img.W, img.C, 1.f, stream)) return 1;
@@ -307,7 +307,7 @@ int pd_engine::vae_encoder_forward(const float* images_dev, int B, int H, int W,
     hcur = t;
     // norm_out + swish + conv_out, then quant_conv; the moments stay fp32 from here on
     Act h = new_act(hcur.B, hcur.H, hcur.W, v.conv_out.m.N, DT_F32);
-    PD_TRY(conv_gn(v.conv_out, hcur, h, v.out_g, v.out_b, 1e-6f, true, nullptr, nullptr, 0));
+    PD_TRY(conv_gn(v.conv_out, hcur, h, v.out_g, v.out_b, 1e-6f, true));
     Act mom = new_act(h.B, h.H, h.W, v.quant.m.N, DT_F32);
     PD_TRY(conv(v.quant, h, mom));
     if (!arena.dry) {
