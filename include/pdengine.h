@@ -269,6 +269,68 @@ int pd_unipc_sample(pd_engine* e, const pd_sample_args* args, const pd_unipc_arg
  * m_i of the last step, PD_GET_EPS its guided eps. */
 int pd_sample_begin_unipc(pd_engine* e, const pd_sample_args* args, const pd_unipc_args* u);
 
+/* Linear multistep solvers inside the engine's loop.  Once the grid is fixed, PLMS (PLMSSampler, ldm/models/diffusion/plms.py)
+ * and DPM-Solver++ multistep (DPM_Solver.sample(method="multistep"), ldm/models/diffusion/dpm_solver/dpm_solver.py) are linear
+ * in a base sample and a short history of model outputs, so one evaluation ends in one elementwise kernel driven by a
+ * coefficient row computed on the host in fp64.  The device state -- a ring of three earlier model outputs and one kept
+ * sample -- is fp64; only the sample and pred_x0 a row returns are rounded to fp32.  eta must be 0 and noise NULL.
+ * One row = one UNet evaluation.  A row may or may not complete a sampling step: PLMS's first step takes two evaluations
+ * (plms.py:227-231), so PLMS over S steps has S + 1 rows at the times t_0, t_1, t_1, t_2, ..; per_step_out still has S + 1
+ * entries (x_T and the sample after every completed step), the inpainting blend and control_scales_step follow completed
+ * steps, and pd_sample_step(i) indexes rows. */
+#define PD_LMS_PLMS  0 /* PLMSSampler: Adams-Bashforth on eps, orders 1..4 by warm-up, pseudo improved Euler first step */
+#define PD_LMS_DPMPP 1 /* DPM-Solver++ multistep (data prediction), order 1..3 */
+#define PD_LMS_ROWS  2 /* the caller's own rows / row_times / n_rows */
+#define PD_LMS_DPM_SOLVER 0 /* solver_type "dpm_solver" (diffusers "midpoint") */
+#define PD_LMS_TAYLOR     1 /* solver_type "taylor" (diffusers "heun") */
+typedef struct pd_lms_args {
+    int32_t kind;               /* PD_LMS_* */
+    int32_t order;              /* DPMPP: 1..3 */
+    int32_t solver_type;        /* DPMPP: PD_LMS_DPM_SOLVER / PD_LMS_TAYLOR (the second-order update; order 3 has one form) */
+    int32_t lower_order_final;  /* DPMPP: order of evaluation i is min(order, i + 1, steps - i) instead of min(order, i + 1) */
+    /* DPMPP, optional, HOST [steps + 1], strictly descending, inside [0, cfg->timesteps - 1]: the model times of the `steps`
+     * evaluations and, last, the point the loop lands on -- the reference's continuous grid, (t - 1/N) * 1000 of
+     * model_wrapper.  log(alpha) is interpolated linearly between the integer points as NoiseScheduleVP('discrete') does, and
+     * the UNet is fed the fractional time.  When NULL the grid is pd_sample_args.timesteps (int64, `steps` entries, strictly
+     * descending) and the loop lands on sigma = 0 (alpha = 1), the diffusers-style grid, with a first-order last step.
+     * init_latents / mask need the integer grid. */
+    const double* model_times;
+    const double* rows;         /* PD_LMS_ROWS: HOST [n_rows][PD_LMS_NCOEF] */
+    const double* row_times;    /* PD_LMS_ROWS: HOST [n_rows] model time of every evaluation */
+    int32_t n_rows;             /* PD_LMS_ROWS: rows; the rows flagged "completes a step" must number pd_sample_args.steps */
+    int32_t reserved[3];
+} pd_lms_args;
+/* One coefficient row per evaluation i, fp64.  m_i is the model output of this evaluation: the x0 prediction
+ * (x - sigma_i eps) / alpha_i with PD_LMS_F_DATA_PRED, else the guided eps.  base is the current sample x, or the kept
+ * sample with PD_LMS_F_BASE_KEEP.
+ *   [0] alpha_i   [1] sigma_i   [2] flags (sum of PD_LMS_F_*)
+ *   [3..7]  x_next  = [3] base + [4] m_i + [5] m_{i-1} + [6] m_{i-2} + [7] m_{i-3}
+ *   [8..12] pred_x0 = [8] base + [9] m_i + [10] m_{i-1} + [11] m_{i-2} + [12] m_{i-3}
+ *   [13] how many of m_{i-1}, m_{i-2}, m_{i-3} the row reads (at most the rows pushed so far)   [14], [15] zero
+ * m_{i-k} counts pushed outputs only: an evaluation without PD_LMS_F_PUSH never enters the history. */
+#define PD_LMS_NCOEF 16
+#define PD_LMS_F_DATA_PRED  1 /* m_i is the x0 prediction */
+#define PD_LMS_F_BASE_KEEP  2 /* base is the kept sample */
+#define PD_LMS_F_STORE_KEEP 4 /* keep the current sample before updating */
+#define PD_LMS_F_PUSH       8 /* push m_i into the history */
+#define PD_LMS_F_STEP      16 /* the row completes a sampling step (per_step_out entry, inpainting blend) */
+/* Host only (no engine, no GPU): rows [n][PD_LMS_NCOEF] and row_times [n] with *n_rows = n <= steps + 1 (size both for
+ * steps + 1) for the grid `timesteps` (or u->model_times, then `timesteps` may be NULL); alphas_cumprod derived from cfg in
+ * fp64 as for pd_unipc_coefficients.  PLMS: a_prev of a step is alphas_cumprod at the next grid point and alphas_cumprod[0]
+ * after the last (make_ddim_sampling_parameters).  PD_LMS_ROWS checks the caller's rows and copies them; with more than steps + 1 of them it fails and writes nothing (the engine
+ * itself, pd_lms_sample / pd_sample_begin_lms, takes up to 4 * cfg->timesteps rows). */
+int pd_lms_coefficients(const pd_config* cfg, const pd_lms_args* u, const int64_t* timesteps, int32_t steps, double* rows,
+                        double* row_times, int32_t* n_rows);
+/* The fused loop: begin + every row + read-back, blocking; latents_out / per_step_out as in pd_ddim_sample.  Option "graph"
+ * captures it like the DDIM loop. */
+int pd_lms_sample(pd_engine* e, const pd_sample_args* args, const pd_lms_args* u, int32_t mem_out, float* latents_out,
+                  float* per_step_out);
+/* Stepwise form: pd_sample_step(i) runs row i (i = 0 .. pd_sample_rows(e) - 1); _get / _set_latents / _set_guidance / _end work
+ * as for DDIM.  PD_GET_PRED_X0 is the row's pred_x0, PD_GET_EPS its guided eps. */
+int pd_sample_begin_lms(pd_engine* e, const pd_sample_args* args, const pd_lms_args* u);
+/* rows of the active session (steps for DDIM / UniPC) */
+int32_t pd_sample_rows(pd_engine* e);
+
 /* schedule exactly as DDIMSampler.make_schedule derives it (cldm/ddim_hacked.py:23-52):
  * fills timesteps[S] (ascending), alphas[S], alphas_prev[S], sigmas[S], sqrt_one_minus_alphas[S] */
 int pd_make_schedule(pd_engine* e, int32_t steps, float eta, int64_t* timesteps, float* alphas,

@@ -37,6 +37,10 @@ int pd_op_spatial_transformer(pd_engine* e, const char* prefix, const float* x, 
  * and time_embed(temb) = Linear -> SiLU -> Linear of the loaded network (net 0: UNet, 1: ControlNet; openaimodel.py:526-531) -> emb
  * [n][4 * model_channels]; exactly what the sampler computes once per call for all its steps (pd_engine::compute_emb). */
 int pd_op_time_embed(pd_engine* e, int net, const int64_t* t, int n, float* temb, float* emb);
+/* Host only (no engine, no GPU): the sinusoidal timestep_embedding [n, dim] the engine feeds its time_embed MLP, from integer
+ * timesteps and from the fractional model times of a linear multistep loop ((float)t * freqs; the same bits for integers). */
+int pd_op_timestep_embedding_i(const int64_t* t, int n, int dim, float* out);
+int pd_op_timestep_embedding_f(const double* t, int n, int dim, float* out);
 /* Downsample.forward with_conv (model.py:80-88): F.pad(x, (0,1,0,1)) then Conv2d 3x3, stride 2, padding 0; x [B, C, H, W] ->
  * y [B, C, H/2, W/2] (floor), w [C, C, 3, 3], bias [C] or NULL; the implicit-GEMM gather with GemmParams::pad_shift = 1 */
 int pd_op_vae_downsample(pd_engine* e, const float* x, const float* w, const float* bias, int B, int C, int H, int W, float* y);

@@ -13,6 +13,10 @@
 void pd_set_error(const char* fmt, ...);
 // timestep_embedding (util.py:154-174) of n timesteps on the host: [cos | sin] halves, fp32 like the reference
 void pd_host_timestep_embedding(const int64_t* t, int n, int dim, std::vector<float>& out);
+// its sibling for fractional model times (the reference's timesteps[:, None].float() * freqs): the same bits for integer values
+void pd_host_timestep_embedding_f(const double* t, int n, int dim, std::vector<float>& out);
+// rows [n_rows][PD_LMS_NCOEF] and the model time of every row for a linear multistep loop over n steps (multistep.cpp)
+int pd_lms_table(const pd_config& cfg, const pd_lms_args& u, const int64_t* ts, int n, std::vector<double>& rows, std::vector<double>& times);
 // coefficient rows [n][PD_UNIPC_NCOEF] of the fused UniPC loop (multistep.cpp; pd_unipc_coefficients)
 int pd_unipc_table(const pd_config& cfg, const pd_unipc_args& u, const int64_t* ts, int n, std::vector<double>& coef);
 
@@ -284,6 +288,8 @@ struct GemmPlan {
 
 struct KVSlot { void* K = nullptr; void* VT = nullptr; void* P = nullptr; };   // P: K / V^T in st_tail.hip's fragment order (fused blocks)
 
+enum { SOLVER_DDIM = 0, SOLVER_UNIPC = 1, SOLVER_LMS = 2 };
+
 struct Session {
     bool active = false;
     pd_sample_args a{};
@@ -312,11 +318,21 @@ struct Session {
     bool hint_shared = false, share_u = false, share_c = false;
     bool cn_cond_only = false;   // guess mode under guidance: this evaluation runs the ControlNet on the conditional half only (run_controlnet)
     // solver of step(): DDIM, or the fused UniPC loop (pd_sample_begin_unipc / pd_unipc_sample)
-    int solver = 0;                  // SOLVER_DDIM / SOLVER_UNIPC
+    int solver = 0;                  // SOLVER_DDIM / SOLVER_UNIPC / SOLVER_LMS
     std::vector<double> unipc_coef;  // [S][PD_UNIPC_NCOEF] (multistep.cpp)
     int unipc_ring = 0;              // x0 predictions kept: the solver order
     double* u_last = nullptr;        // [B, HW, C] fp64: corrected sample of the previous step
     double* u_ring[3] = {nullptr, nullptr, nullptr};   // [B, HW, C] fp64 each: m_j in slot j % unipc_ring
+    // linear multistep loop (pd_sample_begin_lms / pd_lms_sample): one row per evaluation, S completed steps
+    std::vector<double> lms_coef;    // [n_rows][PD_LMS_NCOEF] (multistep.cpp)
+    std::vector<double> lms_times;   // [n_rows] model time of every evaluation
+    std::vector<int> lms_step;       // [n_rows] steps completed before the row
+    std::vector<int> lms_pushed;     // [n_rows] model outputs pushed before the row
+    int lms_ring = 0;                // history slots: the deepest n_hist of the rows (at least 1)
+    bool lms_keep = false;           // some row keeps a sample
+    double* l_keep = nullptr;        // [B, HW, C] fp64
+    double* l_ring[3] = {nullptr, nullptr, nullptr};   // [B, HW, C] fp64 each: pushed output j in slot j % lms_ring
+    int rows() const { return solver == SOLVER_LMS ? (int)lms_times.size() : S; }   // evaluations of the loop
     // img2img / inpainting (pd_sample_args.init_latents / mask): z0 and eps [B, C, HW] and the mask [B, HW], fp32, allocated after
     // everything else; blend[i] = the coefficients of the blend after step i (fp32 from the engine's fp32 table, on the host)
     float* init_z0 = nullptr;
@@ -324,7 +340,6 @@ struct Session {
     float* mask = nullptr;
     std::vector<BlendCoef> blend;
 };
-enum { SOLVER_DDIM = 0, SOLVER_UNIPC = 1 };
 
 struct pd_engine {
     pd_config cfg{};
@@ -535,13 +550,14 @@ struct pd_engine {
 
     // sessions
     int ensure_arena(int rows, bool per_step);
-    int session_setup(const pd_sample_args& a, const int64_t* t_rows, int n_rows, bool want_per_step);
-    int compute_emb(NetW& net, std::vector<float*>& tabs, const int64_t* t, int n, int row0);
-    int begin(const pd_sample_args* a, bool want_per_step, const pd_unipc_args* u = nullptr);
-    int step(int i);   // eps, then the solver's update launch (step_ddim / step_unipc), then the optional per-step copy
+    int session_setup(const pd_sample_args& a, const int64_t* t_rows, int n_rows, bool want_per_step, const double* t_rows_f = nullptr);
+    int compute_emb(NetW& net, std::vector<float*>& tabs, const int64_t* t, int n, int row0, const double* tf = nullptr);   // tf: fractional times instead of t
+    int begin(const pd_sample_args* a, bool want_per_step, const pd_unipc_args* u = nullptr, const pd_lms_args* l = nullptr);
+    int step(int i);   // eps, then the solver's update launch (step_ddim / step_unipc / step_lms), then the optional per-step copy
     UpdateState update_state(const Act& eps) const;
     int step_ddim(int i, const UpdateState& u, const BlendArgs* bl);
     int step_unipc(int i, const UpdateState& u, const BlendArgs* bl);
+    int step_lms(int i, const UpdateState& u, const BlendArgs* bl);
     int make_schedule(int steps, float eta, std::vector<int64_t>& ts, std::vector<float>& a, std::vector<float>& ap,
                       std::vector<float>& sg, std::vector<float>& s1m, const int64_t* custom_desc = nullptr);
 };

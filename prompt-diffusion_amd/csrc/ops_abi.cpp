@@ -315,6 +315,22 @@ int pd_op_spatial_transformer(pd_engine* e, const char* prefix, const float* x, 
 
 
 // timestep_embedding + time_embed MLP of a loaded network: the first two stages of pd_engine::compute_emb
+int pd_op_timestep_embedding_i(const int64_t* t, int n, int dim, float* out) {
+    if (!t || !out || n < 1 || dim < 2) { pd_set_error("bad argument"); return 1; }
+    std::vector<float> host;
+    pd_host_timestep_embedding(t, n, dim, host);
+    std::memcpy(out, host.data(), host.size() * sizeof(float));
+    return 0;
+}
+
+int pd_op_timestep_embedding_f(const double* t, int n, int dim, float* out) {
+    if (!t || !out || n < 1 || dim < 2) { pd_set_error("bad argument"); return 1; }
+    std::vector<float> host;
+    pd_host_timestep_embedding_f(t, n, dim, host);
+    std::memcpy(out, host.data(), host.size() * sizeof(float));
+    return 0;
+}
+
 int pd_op_time_embed(pd_engine* e, int net, const int64_t* t, int n, float* temb, float* emb) {
     if (!e || !t || n < 1 || (!temb && !emb)) { pd_set_error("null argument"); return 1; }
     HIP_OK(hipSetDevice(e->device));

@@ -327,6 +327,14 @@ struct UnipcCoef { double alpha, sigma, c_last, c_m[4], p_x, p_m[3]; int corr, n
 // which is read first)
 int launch_cfg_unipc(const UpdateState& u, const UnipcCoef& k, double* last, double* m_out, const double* const hist[3],
                      const BlendArgs* bl, hipStream_t s);
+// One row of a linear multistep solver (include/pdengine.h, PD_LMS_NCOEF), by value like UnipcCoef.
+//   x_next = c_x base + sum_k c_m[k] m_{i-k},  pred_x0 = q_x base + sum_k q_m[k] m_{i-k},  base = base_keep ? keep : x;
+//   data_pred: m_i = (x - sigma eps) / alpha, else m_i = eps; store_keep: keep = x before the update; push: m_i -> m_out;
+//   n_hist: how many of m_{i-1}, m_{i-2}, m_{i-3} the row reads
+struct LmsCoef { double alpha, sigma, c_x, c_m[4], q_x, q_m[4]; int data_pred, base_keep, store_keep, push, n_hist; float cfg_scale; };
+// keep [B, HW, C] fp64: the kept sample (null when no flag uses it); m_out / hist as in launch_cfg_unipc
+int launch_cfg_lms(const UpdateState& u, const LmsCoef& k, double* keep, double* m_out, const double* const hist[3], const BlendArgs* bl,
+                   hipStream_t s);
 // start latents: x = pure ? eps : sa z0 + sb eps -> x_state [B, HW, Cpad] (channels >= C zero), x_in (dup copies), and
 // optionally out_nchw [B, C, HW]
 int launch_init_latents(const float* z0, const float* eps, float sa, float sb, int pure, float* x_state, float* x_in, float* out_nchw,

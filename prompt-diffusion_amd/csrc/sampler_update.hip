@@ -1,15 +1,15 @@
 // The end of a denoising step, elementwise over the B x HW x C latents (gfx950): classifier-free guidance, the solver's update
-// (DDIM or fused UniPC), the optional inpainting blend, and the store of the new sample for the next step -- plus the start of
+// (DDIM, fused UniPC or a linear multistep row), the optional inpainting blend, and the store of the new sample for the next step -- plus the start of
 // an img2img / inpainting session (pd_sample_args.init_latents / mask, include/pdengine.h).  Each piece of arithmetic exists
-// once: the index decomposition, the guidance and the stores in the one kernel template, the two solvers and the blend as
-// __device__ functions it calls; the four kernels are its instantiations over the solver and a compile-time "blend or not".
+// once: the index decomposition, the guidance and the stores in the one kernel template, the three solvers and the blend as
+// __device__ functions it calls; the six kernels are its instantiations over the solver and a compile-time "blend or not".
 //   eps      [Bf, HW, eps_C] fp32 / 16-bit: UNet output, uncond half first (ddim_hacked.py:189-192)
 //   x_state  [B, HW, Cpad] fp32 (channels >= C are zero)    -> updated in place
 //   x_in     [dup*B, HW, Cpad] fp32: the CFG-duplicated latents the next step's conv_in reads
 //   pred_x0, eps_guided  [B, HW, C] fp32, index i
 // z0 / eps / the noise draws of img2img and inpainting are NCHW fp32 (the caller's layout), the mask [B, HW].  With a blend,
 // only x_state and x_in receive the blended value; pred_x0, the guided eps and the UniPC fp64 state (last, the x0 ring) are the
-// update's own.
+// update's own (so are the linear multistep solver's history ring and kept sample).
 #include "../../include/pdengine.h"
 #include "pd_common.h"
 
@@ -66,6 +66,33 @@ struct UnipcSolver {
         last[i] = xc;
         m_out[i] = m;
         pred_x0[i] = (float)m;
+        return (float)xn;
+    }
+};
+
+// One row of a linear multistep solver (PLMS, DPM-Solver++ multistep, or rows the caller brought; layout PD_LMS_NCOEF in
+// include/pdengine.h).  With the grid fixed, the new sample and the reported pred_x0 are linear in a base sample -- the current
+// one or the kept one -- and the model outputs m_i .. m_{i-3}; m_i is the x0 prediction (data prediction) or the guided eps
+// itself.  State is fp64 like UnipcSolver's and only the two results are rounded to fp32; the sums are plain fp64 expressions
+// that the compiler contracts into FMAs, so their operand order and parentheses stay exactly as written.
+//   keep, m_out, h1..h3  [B, HW, C] fp64, index i; m_out may alias one of h1..h3 (each element is read before it is written);
+//   keep is read / written only by rows whose flags say so and may be null otherwise
+struct LmsSolver {
+    LmsCoef k; double* keep; double* m_out; const double* h1; const double* h2; const double* h3;
+    __device__ __forceinline__ bool active() const { return true; }
+    __device__ __forceinline__ float update(float xf, float e, long long i, long long, float* __restrict__ pred_x0) const {
+        const double x = (double)xf;
+        // m_i: (x - sigma e) / alpha in the operation order of UnipcSolver, or eps
+        const double m = k.data_pred ? __ddiv_rn(__dsub_rn(x, __dmul_rn(k.sigma, (double)e)), k.alpha) : (double)e;
+        const double m1 = k.n_hist > 0 ? h1[i] : 0.0;
+        const double m2 = k.n_hist > 1 ? h2[i] : 0.0;
+        const double m3 = k.n_hist > 2 ? h3[i] : 0.0;
+        if (k.store_keep) keep[i] = x;
+        const double base = k.base_keep ? keep[i] : x;
+        const double xn = k.c_x * base + k.c_m[0] * m + k.c_m[1] * m1 + k.c_m[2] * m2 + k.c_m[3] * m3;
+        const double p0 = k.q_x * base + k.q_m[0] * m + k.q_m[1] * m1 + k.q_m[2] * m2 + k.q_m[3] * m3;
+        if (k.push) m_out[i] = m;
+        pred_x0[i] = (float)p0;
         return (float)xn;
     }
 };
@@ -167,4 +194,12 @@ int launch_cfg_unipc(const UpdateState& u, const UnipcCoef& k, double* last, dou
     for (int j = 0; j < k.n_hist; ++j)
         if (!hist[j]) return 1;
     return launch_update(u, UnipcSolver{k, last, m_out, hist[0], hist[1], hist[2]}, bl, s);
+}
+
+int launch_cfg_lms(const UpdateState& u, const LmsCoef& k, double* keep, double* m_out, const double* const hist[3], const BlendArgs* bl,
+                   hipStream_t s) {
+    if (k.n_hist < 0 || k.n_hist > 3 || (k.push && !m_out) || ((k.store_keep || k.base_keep) && !keep)) return 1;
+    for (int j = 0; j < k.n_hist; ++j)
+        if (!hist[j]) return 1;
+    return launch_update(u, LmsSolver{k, keep, m_out, hist[0], hist[1], hist[2]}, bl, s);
 }

@@ -1,4 +1,4 @@
-// pdengine: sampling sessions (DDIM / fused UniPC loop state, hoisted loop invariants) and the C ABI.
+// pdengine: sampling sessions (DDIM / fused UniPC / linear multistep loop state, hoisted loop invariants) and the C ABI.
 // Follows DDIMSampler.{make_schedule, sample, ddim_sampling, p_sample_ddim}, cldm/ddim_hacked.py:23-234.
 #include <algorithm>
 #include <cmath>
@@ -83,15 +83,30 @@ void pd_host_timestep_embedding(const int64_t* t, int n, int dim, std::vector<fl
         }
 }
 
+// the same for fractional times: (float)t * f as the reference's timesteps[:, None].float() * freqs (util.py:165)
+void pd_host_timestep_embedding_f(const double* t, int n, int dim, std::vector<float>& out) {
+    const int half = dim / 2;
+    out.assign((size_t)n * dim, 0.f);
+    const float lg = -std::log(10000.0f);
+    for (int r = 0; r < n; ++r)
+        for (int i = 0; i < half; ++i) {
+            const float f = std::exp(lg * (float)i / (float)half);
+            const float a = (float)t[r] * f;
+            out[(size_t)r * dim + i] = std::cos(a);
+            out[(size_t)r * dim + half + i] = std::sin(a);
+        }
+}
+
 // time_embed MLP + every ResBlock's emb_layers for n timesteps at once (they do not depend on the
 // latents, so the sampler hoists them out of the step loop).
-int pd_engine::compute_emb(NetW& net, std::vector<float*>& tabs, const int64_t* t, int n, int row0) {
+int pd_engine::compute_emb(NetW& net, std::vector<float*>& tabs, const int64_t* t, int n, int row0, const double* tf) {
     const int mc = cfg.model_channels, temb = mc * 4;
     const size_t mk = arena.mark();
     Act te = new_act(n, 1, 1, mc, DT_F32);
     if (!arena.dry) {
         std::vector<float> host;
-        pd_host_timestep_embedding(t, n, mc, host);
+        if (tf) pd_host_timestep_embedding_f(tf, n, mc, host);
+        else pd_host_timestep_embedding(t, n, mc, host);
         HIP_OK(hipMemcpyAsync(te.p, host.data(), host.size() * 4, hipMemcpyHostToDevice, stream));
         HIP_OK(hipStreamSynchronize(stream));
     }
@@ -111,7 +126,7 @@ int pd_engine::compute_emb(NetW& net, std::vector<float*>& tabs, const int64_t* 
 // Allocates the session state from the arena and computes everything that does not change across
 // steps: NHWC copies of the inputs, guided_hint (cldm/cldm.py:306-308), context K/V of every
 // cross-attention, projected time embeddings of every step.
-int pd_engine::session_setup(const pd_sample_args& a, const int64_t* t_rows, int n_rows, bool want_per_step) {
+int pd_engine::session_setup(const pd_sample_args& a, const int64_t* t_rows, int n_rows, bool want_per_step, const double* t_rows_f) {
     Session& s = ses;
     const int B = a.batch, Bf = s.Bf, HW = a.h * a.w, C = cfg.in_channels;
     const int L = cfg.context_len, D = cfg.context_dim, Dp = round_up(D, 8), lpad = round_up(L, 8);
@@ -149,6 +164,13 @@ int pd_engine::session_setup(const pd_sample_args& a, const int64_t* t_rows, int
     if (s.solver == SOLVER_UNIPC) {
         s.u_last = reinterpret_cast<double*>(arena.alloc((size_t)B * HW * C * 8));
         for (int r = 0; r < s.unipc_ring; ++r) s.u_ring[r] = reinterpret_cast<double*>(arena.alloc((size_t)B * HW * C * 8));
+    }
+    // linear multistep state: the kept sample and the history ring
+    s.l_keep = nullptr;
+    for (double*& r : s.l_ring) r = nullptr;
+    if (s.solver == SOLVER_LMS) {
+        if (s.lms_keep) s.l_keep = reinterpret_cast<double*>(arena.alloc((size_t)B * HW * C * 8));
+        for (int r = 0; r < s.lms_ring; ++r) s.l_ring[r] = reinterpret_cast<double*>(arena.alloc((size_t)B * HW * C * 8));
     }
     // img2img / inpainting inputs, after the UniPC state (a plain session's layout stays as it is)
     s.init_z0 = s.init_eps = s.mask = nullptr;
@@ -282,8 +304,8 @@ int pd_engine::session_setup(const pd_sample_args& a, const int64_t* t_rows, int
             HIP_OK(hipMemcpyAsync(reinterpret_cast<char*>(s.hint.p) + hint_out.bytes(), s.hint.p, hint_out.bytes(), hipMemcpyDeviceToDevice, stream));
     }
     // ---- projected time embeddings for all rows
-    PD_TRY(compute_emb(unet, s.emb_u, t_rows, n_rows, 0));
-    PD_TRY(compute_emb(cnet, s.emb_c, t_rows, n_rows, 0));
+    PD_TRY(compute_emb(unet, s.emb_u, t_rows, n_rows, 0, t_rows_f));
+    PD_TRY(compute_emb(cnet, s.emb_c, t_rows, n_rows, 0, t_rows_f));
     arena.release(mk);
     if (arena.top != s.session_top) arena.top = s.session_top;
     return 0;
@@ -356,12 +378,42 @@ static int check_args(pd_engine* e, const pd_sample_args* a) {
     return 0;
 }
 
-int pd_engine::begin(const pd_sample_args* a, bool want_per_step, const pd_unipc_args* u) {
+int pd_engine::begin(const pd_sample_args* a, bool want_per_step, const pd_unipc_args* u, const pd_lms_args* l) {
     PD_TRY(check_args(this, a));
     ses.active = false;
     ses.solver = SOLVER_DDIM;
     ses.unipc_coef.clear();
     ses.unipc_ring = 0;
+    ses.lms_coef.clear();
+    ses.lms_times.clear();
+    ses.lms_step.clear();
+    ses.lms_pushed.clear();
+    ses.lms_ring = 0;
+    ses.lms_keep = false;
+    if (l) {
+        if (a->eta != 0.f || a->noise) { pd_set_error("lms: eta must be 0 and noise NULL (a linear multistep solver draws no noise)"); return 1; }
+        if (a->init_latents && (l->model_times || l->kind == PD_LMS_ROWS || !a->timesteps)) {
+            pd_set_error("lms: init_latents / mask need the integer grid (pd_sample_args.timesteps)");
+            return 1;
+        }
+        PD_TRY(pd_lms_table(cfg, *l, a->timesteps, a->steps, ses.lms_coef, ses.lms_times));
+        ses.solver = SOLVER_LMS;
+        const int nr = (int)ses.lms_times.size();
+        ses.lms_step.resize(nr);
+        ses.lms_pushed.resize(nr);
+        int done = 0, pushed = 0, ring = 1;
+        for (int r = 0; r < nr; ++r) {
+            const double* row = &ses.lms_coef[(size_t)r * PD_LMS_NCOEF];
+            const int fl = (int)row[2];
+            ses.lms_step[r] = done;
+            ses.lms_pushed[r] = pushed;
+            ring = std::max(ring, (int)row[13]);
+            if (fl & (PD_LMS_F_STORE_KEEP | PD_LMS_F_BASE_KEEP)) ses.lms_keep = true;
+            if (fl & PD_LMS_F_STEP) ++done;
+            if (fl & PD_LMS_F_PUSH) ++pushed;
+        }
+        ses.lms_ring = ring;
+    }
     if (u) {
         if (a->eta != 0.f || a->noise) { pd_set_error("unipc: eta must be 0 and noise NULL (UniPC draws no noise)"); return 1; }
         if (!a->timesteps) { pd_set_error("unipc: the timestep grid (pd_sample_args.timesteps) is required"); return 1; }
@@ -376,9 +428,16 @@ int pd_engine::begin(const pd_sample_args* a, bool want_per_step, const pd_unipc
     ses.custom_ts.clear();
     if (a->timesteps) ses.custom_ts.assign(a->timesteps, a->timesteps + a->steps);   // always HOST memory
     ses.a.timesteps = nullptr;
-    PD_TRY(make_schedule(a->steps, a->eta, ses.timesteps, ses.alphas, ses.alphas_prev, ses.sigmas, ses.sqrt_1m,
-                         ses.custom_ts.empty() ? nullptr : ses.custom_ts.data()));
-    ses.S = (int)ses.timesteps.size();
+    if (l && !a->timesteps) {
+        // a linear multistep loop on fractional model times: no DDIM table to derive (nothing of it is read)
+        ses.timesteps.clear();
+        ses.alphas.clear(); ses.alphas_prev.clear(); ses.sigmas.clear(); ses.sqrt_1m.clear();
+        ses.S = a->steps;
+    } else {
+        PD_TRY(make_schedule(a->steps, a->eta, ses.timesteps, ses.alphas, ses.alphas_prev, ses.sigmas, ses.sqrt_1m,
+                             ses.custom_ts.empty() ? nullptr : ses.custom_ts.data()));
+        ses.S = (int)ses.timesteps.size();
+    }
     const int S_ = ses.S;
     const int nc = (int)cnet.enc.size() + 1;
     ses.scales_step.assign((size_t)S_ * PD_NUM_CONTROL, 1.0f);
@@ -389,7 +448,8 @@ int pd_engine::begin(const pd_sample_args* a, bool want_per_step, const pd_unipc
             ses.scales_step[(size_t)i * PD_NUM_CONTROL + j] = v;
         }
     std::vector<int64_t> trows(S_);
-    for (int i = 0; i < S_; ++i) trows[i] = ses.timesteps[S_ - 1 - i];  // sampling order = flipped (ddim_hacked.py:144)
+    if (!ses.timesteps.empty())   // (empty: a linear multistep loop on fractional model times, which reads no DDIM table)
+        for (int i = 0; i < S_; ++i) trows[i] = ses.timesteps[S_ - 1 - i];  // sampling order = flipped (ddim_hacked.py:144)
     // img2img / inpainting: blend[i] = (sa, sb) at t_i for i < S (blend[0]: the start), blend[S] = z0 itself (after the last step)
     ses.blend.clear();
     if (a->init_latents) {
@@ -403,8 +463,14 @@ int pd_engine::begin(const pd_sample_args* a, bool want_per_step, const pd_unipc
             b.sb = b.last ? 0.f : sqrtf(1.0f - ac[trows[i]]);
         }
     }
-    PD_TRY(ensure_arena(S_, want_per_step));
-    PD_TRY(session_setup(*a, trows.data(), S_, want_per_step));
+    if (l) {   // one time-embedding row per evaluation, from the rows' own (possibly fractional) model times
+        const int nr = ses.rows();
+        PD_TRY(ensure_arena(nr, want_per_step));
+        PD_TRY(session_setup(*a, nullptr, nr, want_per_step, ses.lms_times.data()));
+    } else {
+        PD_TRY(ensure_arena(S_, want_per_step));
+        PD_TRY(session_setup(*a, trows.data(), S_, want_per_step));
+    }
     ses.active = true;
     return 0;
 }
@@ -418,19 +484,25 @@ UpdateState pd_engine::update_state(const Act& eps) const {
 int pd_engine::step(int i) {
     Session& s = ses;
     if (!s.active) { pd_set_error("no active sampling session"); return 1; }
-    if (i < 0 || i >= s.S) { pd_set_error("step %d out of range [0,%d)", i, s.S); return 1; }
+    if (i < 0 || i >= s.rows()) { pd_set_error("step %d out of range [0,%d)", i, s.rows()); return 1; }
     const pd_sample_args& a = s.a;
+    // a linear multistep row is one evaluation of the sampling step `si` and may leave it unfinished; DDIM / UniPC: row = step
+    const bool lms = s.solver == SOLVER_LMS;
+    const int si = lms ? s.lms_step[i] : i;
+    const bool done = lms ? ((int)s.lms_coef[(size_t)i * PD_LMS_NCOEF + 2] & PD_LMS_F_STEP) != 0 : true;
     const size_t mk = arena.mark();
     Act eps;
-    PD_TRY(forward_eps(i, 0, &s.scales_step[(size_t)i * PD_NUM_CONTROL], eps));
+    PD_TRY(forward_eps(i, 0, &s.scales_step[(size_t)si * PD_NUM_CONTROL], eps));
     const UpdateState u = update_state(eps);
     // inpainting: the same update with the known region put back before the sample is stored
-    const BlendArgs bl{s.init_z0, s.init_eps, s.mask, s.mask ? s.blend[i + 1] : BlendCoef{}};
+    const bool blend_on = s.mask && done;
+    const BlendArgs bl{s.init_z0, s.init_eps, s.mask, blend_on ? s.blend[si + 1] : BlendCoef{}};
+    const BlendArgs* blp = blend_on ? &bl : nullptr;
     ++launches;
-    PD_TRY(s.solver == SOLVER_UNIPC ? step_unipc(i, u, s.mask ? &bl : nullptr) : step_ddim(i, u, s.mask ? &bl : nullptr));
-    if (s.per_step) {
+    PD_TRY(lms ? step_lms(i, u, blp) : s.solver == SOLVER_UNIPC ? step_unipc(i, u, blp) : step_ddim(i, u, blp));
+    if (s.per_step && done) {
         ++launches;
-        if (launch_nhwc_to_nchw(s.x_state, DT_F32, s.per_step + (size_t)(i + 1) * u.B * u.C * u.HW, u.B, u.C, a.h, a.w, 8, 1.f, stream))
+        if (launch_nhwc_to_nchw(s.x_state, DT_F32, s.per_step + (size_t)(si + 1) * u.B * u.C * u.HW, u.B, u.C, a.h, a.w, 8, 1.f, stream))
             return 1;
     }
     arena.release(mk);
@@ -484,6 +556,35 @@ int pd_engine::step_unipc(int i, const UpdateState& u, const BlendArgs* bl) {
     return 0;
 }
 
+// One linear multistep row on the eps of evaluation i: the coefficient row of multistep.cpp by value, the pushed model outputs
+// in a ring of lms_ring slots (output j in slot j % lms_ring; the row reads its history before it writes over the oldest).
+int pd_engine::step_lms(int i, const UpdateState& u, const BlendArgs* bl) {
+    Session& s = ses;
+    const double* row = &s.lms_coef[(size_t)i * PD_LMS_NCOEF];
+    const int fl = (int)row[2];
+    LmsCoef k{};
+    k.alpha = row[0];
+    k.sigma = row[1];
+    k.c_x = row[3];
+    k.q_x = row[8];
+    for (int j = 0; j < 4; ++j) { k.c_m[j] = row[4 + j]; k.q_m[j] = row[9 + j]; }
+    k.data_pred = (fl & PD_LMS_F_DATA_PRED) != 0;
+    k.base_keep = (fl & PD_LMS_F_BASE_KEEP) != 0;
+    k.store_keep = (fl & PD_LMS_F_STORE_KEEP) != 0;
+    k.push = (fl & PD_LMS_F_PUSH) != 0;
+    k.n_hist = (int)row[13];
+    k.cfg_scale = s.a.cfg_scale;
+    const int R = s.lms_ring, np = s.lms_pushed[i];
+    if (k.n_hist > R || k.n_hist > np) { pd_set_error("lms: row %d needs %d earlier model outputs", i, k.n_hist); return 1; }
+    const double* hist[3] = {nullptr, nullptr, nullptr};
+    for (int j = 0; j < k.n_hist; ++j) hist[j] = s.l_ring[(np - 1 - j) % R];
+    if (launch_cfg_lms(u, k, s.l_keep, s.l_ring[np % R], hist, bl, stream)) {
+        pd_set_error("lms update launch failed");
+        return 1;
+    }
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------ captured step loop
 // The S steps of a call differ only in kernel ARGUMENTS (time-embedding row, DDIM coefficients, control scales, noise
 // slice); every buffer they touch is carved out of the two workspaces in a deterministic order by begin().  So the
@@ -518,6 +619,8 @@ int pd_engine::run_steps_graph() {
     // the solver: a DDIM and a UniPC loop over the same grid and buffers launch the same kernels up to the update
     hash_mix(key, &ses.solver, sizeof(ses.solver));
     hash_mix(key, ses.unipc_coef.data(), ses.unipc_coef.size() * sizeof(double));
+    hash_mix(key, ses.lms_coef.data(), ses.lms_coef.size() * sizeof(double));
+    hash_mix(key, ses.lms_times.data(), ses.lms_times.size() * sizeof(double));
     hash_mix(key, freeu, sizeof(freeu));   // FreeU values are kernel arguments (pd_set_freeu also drops the graphs)
     // img2img / inpainting: the blend kernels and their coefficients (the start runs before the captured loop)
     const int32_t init[] = {ses.init_z0 ? 1 : 0, ses.mask ? 1 : 0, a.init_flags};
@@ -533,11 +636,11 @@ int pd_engine::run_steps_graph() {
     GraphEntry ge{key, nullptr, nullptr};
     if (hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
         (void)hipGetLastError();
-        for (int i = 0; i < ses.S; ++i) PD_TRY(step(i));   // capture unavailable: run eagerly
+        for (int i = 0; i < ses.rows(); ++i) PD_TRY(step(i));   // capture unavailable: run eagerly
         return 0;
     }
     int rc = 0;
-    for (int i = 0; i < ses.S && !rc; ++i) rc = step(i);
+    for (int i = 0; i < ses.rows() && !rc; ++i) rc = step(i);
     const hipError_t ec = hipStreamEndCapture(stream, &ge.graph);
     if (rc || ec != hipSuccess || !ge.graph) {
         if (ge.graph) hipGraphDestroy(ge.graph);
@@ -815,14 +918,14 @@ int pd_sample_end(pd_engine* e) {
 }
 
 // begin, the S steps (replayed from a captured graph where that is on), latents and optional per-step samples out, end;
-// u null: DDIM, else the fused UniPC loop
-static int run_sample(pd_engine* e, const pd_sample_args* args, const pd_unipc_args* u, int32_t mem_out, float* latents_out,
-                      float* per_step_out) {
-    PD_TRY(e->begin(args, per_step_out != nullptr, u));
+// u and l null: DDIM, else the fused UniPC loop / the linear multistep loop
+static int run_sample(pd_engine* e, const pd_sample_args* args, const pd_unipc_args* u, const pd_lms_args* l, int32_t mem_out,
+                      float* latents_out, float* per_step_out) {
+    PD_TRY(e->begin(args, per_step_out != nullptr, u, l));
     if (e->opt_graph && !e->profiling) {
         PD_TRY(e->run_steps_graph());
     } else {
-        for (int i = 0; i < e->ses.S; ++i) PD_TRY(e->step(i));
+        for (int i = 0; i < e->ses.rows(); ++i) PD_TRY(e->step(i));
     }
     PD_TRY(pd_sample_get(e, PD_GET_LATENTS, mem_out, latents_out));
     if (per_step_out) {
@@ -834,7 +937,7 @@ static int run_sample(pd_engine* e, const pd_sample_args* args, const pd_unipc_a
 
 int pd_ddim_sample(pd_engine* e, const pd_sample_args* args, int32_t mem_out, float* latents_out, float* per_step_out) {
     if (!e || !latents_out) { pd_set_error("null argument"); return 1; }
-    return run_sample(e, args, nullptr, mem_out, latents_out, per_step_out);
+    return run_sample(e, args, nullptr, nullptr, mem_out, latents_out, per_step_out);
 }
 
 int pd_sample_begin_unipc(pd_engine* e, const pd_sample_args* args, const pd_unipc_args* u) {
@@ -845,8 +948,21 @@ int pd_sample_begin_unipc(pd_engine* e, const pd_sample_args* args, const pd_uni
 int pd_unipc_sample(pd_engine* e, const pd_sample_args* args, const pd_unipc_args* u, int32_t mem_out, float* latents_out,
                     float* per_step_out) {
     if (!e || !u || !latents_out) { pd_set_error("null argument"); return 1; }
-    return run_sample(e, args, u, mem_out, latents_out, per_step_out);
+    return run_sample(e, args, u, nullptr, mem_out, latents_out, per_step_out);
 }
+
+int pd_sample_begin_lms(pd_engine* e, const pd_sample_args* args, const pd_lms_args* u) {
+    if (!e || !u) { pd_set_error("null argument"); return 1; }
+    return e->begin(args, false, nullptr, u);
+}
+
+int pd_lms_sample(pd_engine* e, const pd_sample_args* args, const pd_lms_args* u, int32_t mem_out, float* latents_out,
+                  float* per_step_out) {
+    if (!e || !u || !latents_out) { pd_set_error("null argument"); return 1; }
+    return run_sample(e, args, nullptr, u, mem_out, latents_out, per_step_out);
+}
+
+int32_t pd_sample_rows(pd_engine* e) { return e && e->ses.active ? e->ses.rows() : 0; }
 
 int pd_synchronize(pd_engine* e) {
     if (!e) { pd_set_error("null engine"); return 1; }

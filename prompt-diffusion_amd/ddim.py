@@ -238,6 +238,28 @@ class DDIMSampler:
         eng.sample_end()
         return samples, {"x_inter": x_inter, "pred_x0": preds}
 
+    def _lms_call(self, conditioning, batch_size, shape, x_T, scale, uc, unsupported):
+        """The engine arguments PLMSSampler / DPMSolverSampler share with sample() above; both apply guidance only when the
+        scale differs from 1 (plms.py:185, dpm_solver.py:305)."""
+        if conditioning is None or not isinstance(conditioning, dict):
+            raise NotImplementedError("conditioning must be the ControlLDM dict (c_crossattn / example_pair / query)")
+        for name, val in unsupported:
+            if val:
+                raise NotImplementedError(f"{name} is not supported by the HIP sampler")
+        C, H, W = shape
+        if x_T is None:
+            x_T = np.random.standard_normal((batch_size, C, H, W)).astype(np.float32)
+        cfg_on = uc is not None and float(scale) != 1.0
+        kw = dict(x_T=x_T, ctx_cond=_cat(conditioning["c_crossattn"]), pair=_cat(conditioning["example_pair"]),
+                  query=conditioning["query"][0], cfg_scale=float(scale), use_cfg=cfg_on, control_scales=self.model.control_scales,
+                  only_mid_control=self.model.only_mid_control, ctx_uncond=_cat(uc["c_crossattn"]) if cfg_on else None)
+        if cfg_on:
+            if uc["example_pair"][0] is not conditioning["example_pair"][0]:
+                kw["pair_uncond"] = _cat(uc["example_pair"])
+            if uc["query"][0] is not conditioning["query"][0]:
+                kw["query_uncond"] = uc["query"][0]
+        return kw
+
     # ------------------------------------------------------------------ encode / decode (ddim_hacked.py:237-318)
     def _session(self, x, cond, uc, scale, timesteps):
         """one engine session over a custom descending timestep list (context K/V, hint embedders and time embeddings hoisted once)"""
@@ -323,3 +345,66 @@ class DDIMSampler:
         x_dec = eng.sample_get(E.PD_GET_LATENTS)
         eng.sample_end()
         return x_dec
+
+
+class PLMSSampler(DDIMSampler):
+    """ldm/models/diffusion/plms.py:12 PLMSSampler over the HIP engine: the whole loop runs inside the engine (pd_lms_sample,
+    kind PLMS) on the grid of make_schedule.  Returns (samples, {'x_inter', 'pred_x0'}) like the reference.  Not built, as in
+    DDIMSampler: quantize_x0, score_corrector, dynamic_threshold; also mask / x0 (the reference re-draws q_sample noise at
+    every step) and eta != 0, which the reference refuses too (plms.py:26-27)."""
+
+    def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0.0, verbose=True):
+        if ddim_eta != 0:
+            raise ValueError("ddim_eta must be 0 for PLMS")      # plms.py:26-27
+        super().make_schedule(ddim_num_steps, ddim_discretize=ddim_discretize, ddim_eta=0.0, verbose=verbose)
+
+    def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
+               quantize_x0=False, eta=0.0, mask=None, x0=None, temperature=1.0, noise_dropout=0.0, score_corrector=None,
+               corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.0,
+               unconditional_conditioning=None, dynamic_threshold=None, **kwargs):
+        kw = self._lms_call(conditioning, batch_size, shape, x_T, unconditional_guidance_scale, unconditional_conditioning,
+                            (("quantize_x0", quantize_x0), ("score_corrector", score_corrector is not None),
+                             ("dynamic_threshold", dynamic_threshold is not None), ("mask", mask is not None)))
+        self.make_schedule(S, ddim_eta=eta, verbose=verbose)
+        eng = self.model.engine
+        grid = [int(t) for t in np.flip(self.ddim_timesteps)]
+        rows, _ = eng.lms_coefficients(grid, kind="plms")
+        n = eng.sample_begin_lms(kind="plms", timesteps=grid, **kw)
+        total = len(grid)
+        x_inter, preds, done = [kw["x_T"]], [kw["x_T"]], 0
+        for r in range(n):
+            eng.sample_step(r)
+            if not int(rows[r, 2]) & E.PD_LMS_F_STEP:
+                continue                                         # the first evaluation of the pseudo improved Euler step
+            index = total - done - 1
+            if callback:
+                callback(done)
+            if img_callback:
+                img_callback(eng.sample_get(E.PD_GET_PRED_X0), done)
+            if index % log_every_t == 0 or index == total - 1:
+                x_inter.append(eng.sample_get(E.PD_GET_LATENTS))
+                preds.append(eng.sample_get(E.PD_GET_PRED_X0))
+            done += 1
+        samples = eng.sample_get(E.PD_GET_LATENTS)
+        eng.sample_end()
+        return samples, {"x_inter": x_inter, "pred_x0": preds}
+
+
+class DPMSolverSampler(DDIMSampler):
+    """ldm/models/diffusion/dpm_solver/sampler.py:13 DPMSolverSampler over the HIP engine: DPM-Solver++ multistep, order 2,
+    lower_order_final, on the reference's time-uniform continuous grid t = linspace(1, 1/N, S + 1), which reaches the UNet
+    as the fractional model times (t - 1/N) * 1000 (pd_lms_args.model_times).  Returns (samples, None) like the reference,
+    which ignores mask / x0 / callbacks / eta there as well; options that would change the result raise."""
+
+    def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
+               quantize_x0=False, eta=0.0, mask=None, x0=None, temperature=1.0, noise_dropout=0.0, score_corrector=None,
+               corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.0,
+               unconditional_conditioning=None, **kwargs):
+        kw = self._lms_call(conditioning, batch_size, shape, x_T, unconditional_guidance_scale, unconditional_conditioning,
+                            (("quantize_x0", quantize_x0), ("score_corrector", score_corrector is not None)))
+        N = self.ddpm_num_timesteps
+        t = np.linspace(1.0, 1.0 / N, int(S) + 1)
+        model_times = np.maximum((t - 1.0 / N) * 1000.0, 0.0)
+        samples = self.model.engine.lms_sample(kind="dpmsolver++", order=2, solver_type="dpm_solver",
+                                               lower_order_final=int(S) < 15, model_times=model_times, **kw)
+        return samples, None

@@ -76,6 +76,22 @@ class pd_unipc_args(C.Structure):
 
 PD_UNIPC_NCOEF = 16
 
+
+class pd_lms_args(C.Structure):
+    _fields_ = [
+        ("kind", C.c_int32), ("order", C.c_int32), ("solver_type", C.c_int32), ("lower_order_final", C.c_int32),
+        ("model_times", C.c_void_p), ("rows", C.c_void_p), ("row_times", C.c_void_p), ("n_rows", C.c_int32),
+        ("reserved", C.c_int32 * 3),
+    ]
+
+
+PD_LMS_NCOEF = 16
+PD_LMS_PLMS, PD_LMS_DPMPP, PD_LMS_ROWS = 0, 1, 2
+PD_LMS_F_DATA_PRED, PD_LMS_F_BASE_KEEP, PD_LMS_F_STORE_KEEP, PD_LMS_F_PUSH, PD_LMS_F_STEP = 1, 2, 4, 8, 16
+_LMS_KINDS = {"plms": PD_LMS_PLMS, "dpmsolver++": PD_LMS_DPMPP, "rows": PD_LMS_ROWS}
+# DPM_Solver's names and the names diffusers gives the same two second-order updates
+_LMS_SOLVER_TYPES = {"dpm_solver": 0, "dpmsolver": 0, "midpoint": 0, "taylor": 1, "heun": 1}
+
 _lib = None
 
 
@@ -139,6 +155,12 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.pd_unipc_sample.argtypes = [C.c_void_p, C.POINTER(pd_sample_args), C.POINTER(pd_unipc_args), C.c_int32, C.c_void_p,
                                     C.c_void_p]
     lib.pd_sample_begin_unipc.argtypes = [C.c_void_p, C.POINTER(pd_sample_args), C.POINTER(pd_unipc_args)]
+    lib.pd_lms_coefficients.argtypes = [C.POINTER(pd_config), C.POINTER(pd_lms_args), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                        C.POINTER(C.c_int32)]
+    lib.pd_lms_sample.argtypes = [C.c_void_p, C.POINTER(pd_sample_args), C.POINTER(pd_lms_args), C.c_int32, C.c_void_p, C.c_void_p]
+    lib.pd_sample_begin_lms.argtypes = [C.c_void_p, C.POINTER(pd_sample_args), C.POINTER(pd_lms_args)]
+    lib.pd_sample_rows.argtypes = [C.c_void_p]
+    lib.pd_sample_rows.restype = C.c_int32
     lib.pd_synchronize.argtypes = [C.c_void_p]
     lib.pd_stream.argtypes = [C.c_void_p]
     lib.pd_stream.restype = C.c_void_p
@@ -185,11 +207,12 @@ EXPORTS = [
     "pd_vae_encode", "pd_vae_encoder_weights_missing", "pd_eps", "pd_control_shape", "pd_ddim_sample",
     "pd_sample_begin", "pd_sample_step", "pd_sample_get", "pd_sample_set_latents", "pd_sample_set_guidance", "pd_sample_eps_at", "pd_sample_end",
     "pd_unipc_coefficients", "pd_unipc_sample", "pd_sample_begin_unipc",
+    "pd_lms_coefficients", "pd_lms_sample", "pd_sample_begin_lms", "pd_sample_rows",
     "pd_make_schedule", "pd_synchronize", "pd_stream", "pd_wait_stream", "pd_set_option", "pd_get_stat", "pd_bench_conv3x3", "pd_bench_linear", "pd_text_encode", "pd_text_encode_ex", "pd_text_weights_missing",
     "pd_profile_read", "pd_profile_dump", "pd_comm_new_id", "pd_comm_init", "pd_comm_world", "pd_comm_all_gather", "pd_comm_destroy",
     "pd_sd3_configure", "pd_sd3_weights_missing", "pd_sd3_forward", "pd_sd3_control", "pd_sd3_sample", "pd_sd3_down_proj",
     "pd_op_conv2d", "pd_op_linear", "pd_op_linear_fp8", "pd_op_groupnorm", "pd_op_layernorm", "pd_op_attention", "pd_op_spatial_transformer", "pd_op_time_embed",
-    "pd_op_vae_downsample", "pd_read_weights", "pd_lora_add", "pd_lora_set_scales", "pd_lora_remove",
+    "pd_op_timestep_embedding_i", "pd_op_timestep_embedding_f", "pd_op_vae_downsample", "pd_read_weights", "pd_lora_add", "pd_lora_set_scales", "pd_lora_remove",
     "pd_set_freeu", "pd_get_freeu", "pd_op_freeu_concat",
 ]
 
@@ -259,6 +282,64 @@ def unipc_coefficients(cfg: ModelConfig, timesteps, order: int = 2, solver_type:
         raise PdError(lib.pd_last_error().decode(errors="replace"))
     del dc
     return out[:len(ts)]
+
+
+def _lms_args(kind: str, order: int, solver_type: str, lower_order_final: bool, model_times=None, rows=None, row_times=None):
+    """pd_lms_args and the arrays it points to (keep them alive for the call)."""
+    if kind not in _LMS_KINDS:
+        raise ValueError(f"kind must be one of {sorted(_LMS_KINDS)}")
+    if solver_type not in _LMS_SOLVER_TYPES:
+        raise ValueError(f"solver_type must be one of {sorted(_LMS_SOLVER_TYPES)}")
+    u = pd_lms_args()
+    u.kind, u.order = _LMS_KINDS[kind], int(order)
+    u.solver_type, u.lower_order_final = _LMS_SOLVER_TYPES[solver_type], 1 if lower_order_final else 0
+    keep = []
+    if model_times is not None:
+        mt = np.ascontiguousarray(_to_host(model_times), dtype=np.float64).reshape(-1)
+        u.model_times = mt.ctypes.data
+        keep.append(mt)
+    if kind == "rows":
+        r = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, PD_LMS_NCOEF)
+        rt = np.ascontiguousarray(row_times, dtype=np.float64).reshape(-1)
+        if len(r) != len(rt):
+            raise ValueError("rows and row_times must have one entry per evaluation")
+        u.rows, u.row_times, u.n_rows = r.ctypes.data, rt.ctypes.data, len(rt)
+        keep += [r, rt]
+    return u, keep
+
+
+def _lms_steps(timesteps, model_times, steps) -> int:
+    if model_times is not None:
+        return len(np.asarray(_to_host(model_times)).reshape(-1)) - 1
+    if timesteps is not None:
+        return len(np.asarray(_to_host(timesteps)).reshape(-1))
+    if steps is None:
+        raise ValueError("a linear multistep loop needs timesteps, model_times or (with its own rows) steps")
+    return int(steps)
+
+
+def lms_coefficients(cfg: ModelConfig, timesteps=None, kind: str = "dpmsolver++", order: int = 2, solver_type: str = "dpm_solver",
+                     lower_order_final: bool = True, model_times=None, rows=None, row_times=None, steps: Optional[int] = None):
+    """(rows [n_rows, PD_LMS_NCOEF], row_times [n_rows]) in fp64 of a linear multistep loop: `kind` "plms" or "dpmsolver++" over
+    the grid `timesteps` (sampling order; lands on sigma = 0 for dpmsolver++), or dpmsolver++ over `model_times` (steps + 1
+    possibly fractional times, the last one the landing point).  Row layout in include/pdengine.h.  Host only: needs the
+    library, not a GPU."""
+    lib = load_library()
+    n = _lms_steps(timesteps, model_times, steps)
+    ts = None if timesteps is None else np.ascontiguousarray(_to_host(timesteps), dtype=np.int64).reshape(-1)
+    u, keep = _lms_args(kind, order, solver_type, lower_order_final, model_times, rows, row_times)
+    c = make_config(cfg)
+    if u.n_rows > n + 1:
+        raise PdError(f"lms: {u.n_rows} rows do not fit the steps + 1 = {n + 1} that pd_lms_coefficients returns")
+    cap = n + 1
+    out = np.zeros((cap, PD_LMS_NCOEF), np.float64)
+    times = np.zeros(cap, np.float64)
+    nr = C.c_int32(0)
+    if lib.pd_lms_coefficients(C.byref(c), C.byref(u), ts.ctypes.data if ts is not None and len(ts) else None, n, out.ctypes.data,
+                               times.ctypes.data, C.byref(nr)) != 0:
+        raise PdError(lib.pd_last_error().decode(errors="replace"))
+    del keep
+    return out[:nr.value], times[:nr.value]
 
 
 def _is_torch(x) -> bool:
@@ -647,6 +728,45 @@ class Engine:
         self._check(self.lib.pd_unipc_sample(self._h, C.byref(a), C.byref(u), a.mem, op, ip))
         del keep, dc
         return (out, inter) if return_intermediates else out
+
+    def _lms_call(self, kw, kind, order, solver_type, lower_order_final, model_times, rows, row_times):
+        """pd_sample_args + pd_lms_args of a linear multistep call; the step count comes from the grid."""
+        kw = dict(kw)
+        kw["steps"] = n = _lms_steps(kw.get("timesteps"), model_times, kw.get("steps"))
+        css = kw.pop("control_scales_step", None)      # one row per sampling step of this grid, not of a DDIM schedule
+        a, keep, shape = self._args(**kw)
+        a.steps = n
+        if css is not None:
+            css = np.ascontiguousarray(css, dtype=np.float32)
+            if css.shape != (n, PD_NUM_CONTROL):
+                raise PdError(f"control_scales_step must be [{n}, {PD_NUM_CONTROL}], got {css.shape}")
+            a.control_scales_step = css.ctypes.data
+            keep.append(css)
+        u, lkeep = _lms_args(kind, order, solver_type, lower_order_final, model_times, rows, row_times)
+        return a, keep + lkeep, shape, u
+
+    def lms_sample(self, *, return_intermediates: bool = False, kind: str = "dpmsolver++", order: int = 2,
+                   solver_type: str = "dpm_solver", lower_order_final: bool = True, model_times=None, rows=None, row_times=None,
+                   **kw):
+        """The fused linear multistep loop (PLMS, DPM-Solver++ multistep, or the caller's own rows; see lms_coefficients):
+        `timesteps` or `model_times` is the grid; otherwise the arguments and returns of ddim_sample.  x_inter has one entry
+        per completed step, however many evaluations ran."""
+        a, keep, (B, h, w), u = self._lms_call(kw, kind, order, solver_type, lower_order_final, model_times, rows, row_times)
+        out, inter, op, ip = self._sample_out(a, keep, B, h, w, a.steps, return_intermediates)
+        self._check(self.lib.pd_lms_sample(self._h, C.byref(a), C.byref(u), a.mem, op, ip))
+        del keep
+        return (out, inter) if return_intermediates else out
+
+    def lms_coefficients(self, timesteps=None, **kw):
+        return lms_coefficients(self.cfg, timesteps, **kw)
+
+    def sample_begin_lms(self, *, kind: str = "dpmsolver++", order: int = 2, solver_type: str = "dpm_solver",
+                         lower_order_final: bool = True, model_times=None, rows=None, row_times=None, **kw) -> int:
+        """Stepwise form of lms_sample; returns the number of rows: sample_step(i) runs evaluation i."""
+        a, keep, shape, u = self._lms_call(kw, kind, order, solver_type, lower_order_final, model_times, rows, row_times)
+        self._check(self.lib.pd_sample_begin_lms(self._h, C.byref(a), C.byref(u)))
+        self._session_begun(a, keep, shape)
+        return int(self.lib.pd_sample_rows(self._h))
 
     def _session_begun(self, a, keep, shape) -> None:
         self._keep = keep   # the staged copies stay alive until sample_end()

@@ -67,8 +67,9 @@ class PromptDiffusionPipeline:
 
     def __init__(self, engine: E.Engine, text_encoder: Optional[Callable] = None, vae_decode: Optional[Callable] = None,
                  scheduler: Any = None, tokenizer: Any = None, fuse_scheduler: bool = False):
-        """fuse_scheduler: run a UniPCMultistepScheduler's update inside the engine's loop (pd_unipc_sample) instead of on
-        the host between eps evaluations; same grid, same controlnet_keep scales, same callback semantics."""
+        """fuse_scheduler: run the update of a UniPCMultistepScheduler (pd_unipc_sample), DPMSolverMultistepScheduler or
+        PNDMScheduler (pd_lms_sample) inside the engine's loop instead of on the host between eps evaluations; same grid, same
+        controlnet_keep scales, same callback semantics."""
         self.engine = engine
         self.tokenizer = tokenizer
         if text_encoder is None and tokenizer is not None:
@@ -90,11 +91,12 @@ class PromptDiffusionPipeline:
         self._lora_merged: Optional[List[float]] = None
 
     def _check_fusable(self):
-        """The fused loop restates this package's UniPC on the engine's own noise schedule; anything else is refused."""
-        from .schedulers import UniPCMultistepScheduler
+        """The fused loops restate this package's schedulers on the engine's own noise schedule; anything else is refused."""
+        from .schedulers import DPMSolverMultistepScheduler, PNDMScheduler, UniPCMultistepScheduler
         sched = self.scheduler
-        if type(sched) is not UniPCMultistepScheduler:
-            raise ValueError(f"fuse_scheduler=True needs prompt_diffusion_amd.schedulers.UniPCMultistepScheduler, got {type(sched)}")
+        if type(sched) not in (UniPCMultistepScheduler, DPMSolverMultistepScheduler, PNDMScheduler):
+            raise ValueError("fuse_scheduler=True needs prompt_diffusion_amd.schedulers.UniPCMultistepScheduler, "
+                             f"DPMSolverMultistepScheduler or PNDMScheduler, got {type(sched)}")
         cfg = self.engine.cfg
         if sched.num_train_timesteps != cfg.timesteps:
             raise ValueError(f"fuse_scheduler=True: scheduler num_train_timesteps {sched.num_train_timesteps} != the engine's "
@@ -588,7 +590,8 @@ class PromptDiffusionPipeline:
                 self.scheduler.set_timesteps(timesteps=timesteps)
             else:
                 self.scheduler.set_timesteps(num_inference_steps)
-            n_steps = len(self.scheduler.timesteps)
+            plan = self._eval_plan(0)
+            n_steps = len(plan["grid"])
         else:
             # the engine's own DDIM loop with diffusers' DDIMScheduler grid for SD1.5 (timestep_spacing "leading",
             # steps_offset 1): exactly num_inference_steps entries arange(S) * (T // S) + 1.  For S dividing T this IS the
@@ -612,6 +615,11 @@ class PromptDiffusionPipeline:
             grid, t_start = self.get_timesteps(full, init["strength"])
             if self.scheduler is None:
                 custom_ts = grid
+            else:
+                # set_begin_index ran: the evaluations and the step grid are what the scheduler holds from t_start on (a
+                # scheduler with two evaluations in its first step rebuilds its tail there), not a slice of the old list
+                plan = self._eval_plan(t_start)
+                grid = plan["grid"]
             n_steps = len(grid)
             sa, sb = add_noise_coefficients(self.engine.cfg, grid)
             pure = bool(init["mask"] is not None and (init["strength"] == 1.0 or latents is not None))
@@ -643,20 +651,30 @@ class PromptDiffusionPipeline:
             # the scheduler's update inside the engine's loop: its grid, the per-step controlnet_keep scales; UniPC draws no noise
             self._check_fusable()
             sched = self.scheduler
-            kw.update(timesteps=[int(t) for t in sched.timesteps[t_start:]], eta=0.0, noise=None)
-            # disable_corrector indexes the whole grid (as the host scheduler after set_begin_index does); the fused rows the tail
-            unipc = dict(order=sched.solver_order, solver_type=sched.solver_type, lower_order_final=sched.lower_order_final,
-                         disable_corrector=[d - t_start for d in sched.disable_corrector if d - t_start >= 0])
+            kw.update(eta=0.0, noise=None)
+            if hasattr(sched, "fused_lms"):
+                # a linear multistep scheduler: its step grid and options as pd_lms_args; one engine row per evaluation
+                fused = dict(solver="lms", args=sched.fused_lms(t_start), rows=plan["rows"])
+                kw.pop("timesteps", None)
+                kw.pop("steps", None)
+            else:
+                kw.update(timesteps=[int(t) for t in sched.timesteps[t_start:]])
+                # disable_corrector indexes the whole grid (as the host scheduler after set_begin_index does); the fused rows the tail
+                fused = dict(solver="unipc", rows=plan["rows"],
+                             args=dict(order=sched.solver_order, solver_type=sched.solver_type, lower_order_final=sched.lower_order_final,
+                                       disable_corrector=[d - t_start for d in sched.disable_corrector if d - t_start >= 0]))
             if callback_on_step_end is None and callback is None:
-                lat = eng.unipc_sample(**kw, **unipc)
+                run = eng.lms_sample if fused["solver"] == "lms" else eng.unipc_sample
+                lat = run(**kw, **fused["args"])
             else:
                 lat = self._stepwise(kw, scales_step, callback_on_step_end, callback_on_step_end_tensor_inputs, callback,
-                                     callback_steps, pe, ne, eta, generator, unipc=unipc)
+                                     callback_steps, pe, ne, eta, generator, fused=fused)
         elif self.scheduler is None and callback_on_step_end is None and callback is None:
             lat = eng.ddim_sample(**kw)                                  # 8. the fused loop
         else:
             lat = self._stepwise(kw, scales_step, callback_on_step_end, callback_on_step_end_tensor_inputs, callback,
-                                 callback_steps, pe, ne, eta, generator, t_start=t_start, host_blend=host_blend)
+                                 callback_steps, pe, ne, eta, generator, host_blend=host_blend,
+                                 plan=plan if self.scheduler is not None else None)
         # 9. post-processing (pipeline :1298-1321); safety checker is forced off there too
         if output_type == "latent":
             images = lat
@@ -679,13 +697,38 @@ class PromptDiffusionPipeline:
         return StableDiffusionPipelineOutput(images=images, nsfw_content_detected=None)
 
     # ------------------------------------------------------------------ per-step driver (callbacks / plug-in schedulers)
-    def _stepwise(self, kw, scales_step, cb_end, cb_inputs, cb_legacy, cb_steps, pe, ne, eta, generator, unipc=None, t_start=0,
-                  host_blend=None):
+    def _eval_plan(self, t_start):
+        """The evaluations the plug-in scheduler makes from timesteps[t_start] on, and the sampling steps they form.  Most
+        schedulers take one evaluation per step; one that says otherwise through completes_step(index) (PNDMScheduler: two
+        evaluations in its first step, at a repeated timestep) has fewer steps than evaluations.  rows: the timestep of every
+        evaluation; ends: whether it completes a step; step: the step it belongs to; grid: one timestep per step.  The
+        controlnet_keep scales and the inpainting blend follow steps, in the host loop as in the engine's."""
+        sched = self.scheduler
+        ts = sched.timesteps[t_start:]
+        rows = [t.item() if hasattr(t, "item") else t for t in ts]
+        rows = [int(t) if float(t) == int(t) else float(t) for t in rows]
+        if hasattr(sched, "completes_step"):
+            ends = [bool(sched.completes_step(t_start + i)) for i in range(len(rows))]
+        else:
+            ends = [True] * len(rows)
+        step, grid, done = [], [], 0
+        for i, e in enumerate(ends):
+            if i == 0 or ends[i - 1]:
+                grid.append(rows[i])     # the first evaluation of a step is at the step's own timestep
+            step.append(done)
+            done += int(e)
+        return dict(rows=rows, ends=ends, step=step, grid=grid[:done])
+
+    def _stepwise(self, kw, scales_step, cb_end, cb_inputs, cb_legacy, cb_steps, pe, ne, eta, generator, fused=None,
+                  host_blend=None, plan=None):
         eng = self.engine
         sched = self.scheduler
-        if unipc is not None:       # fused UniPC: the engine steps on the scheduler's grid (kw["timesteps"])
+        if fused is not None:       # the scheduler's update inside the engine: one engine row per evaluation of the scheduler
             sched = None
-            n = eng.sample_begin_unipc(**kw, **unipc)
+            begin = eng.sample_begin_lms if fused["solver"] == "lms" else eng.sample_begin_unipc
+            n = begin(**kw, **fused["args"])
+            assert n == len(fused["rows"])
+            kw = dict(kw, timesteps=fused["rows"])
         elif sched is not None:     # the engine only evaluates eps at the scheduler's timesteps: no DDIM tables needed
             kw = {k: v for k, v in kw.items() if k not in ("control_scales_step", "noise")}
             kw["eta"] = 0.0
@@ -693,7 +736,7 @@ class PromptDiffusionPipeline:
         else:
             n = eng.sample_begin(**kw)
         if sched is not None:
-            ts = [int(t) for t in sched.timesteps[t_start:]]     # set_timesteps (and set_begin_index) ran in __call__
+            ts = plan["rows"]                                    # set_timesteps (and set_begin_index) ran in __call__
             extra = {}
             params = set(inspect.signature(sched.step).parameters.keys())
             if "eta" in params:
@@ -711,14 +754,15 @@ class PromptDiffusionPipeline:
             else:
                 # scheduler.scale_model_input is the identity for the DDIM / UniPC families used with SD1.5
                 import torch
-                noise_pred = eng.sample_eps_at(t, scales_step[min(i, len(scales_step) - 1)])
+                j = plan["step"][i]                              # the sampling step this evaluation belongs to
+                noise_pred = eng.sample_eps_at(t, scales_step[min(j, len(scales_step) - 1)])
                 cur = eng.sample_get(E.PD_GET_LATENTS)
                 out = sched.step(torch.from_numpy(np.asarray(noise_pred)), t, torch.from_numpy(np.asarray(cur)), **extra,
                                  return_dict=False)[0]
                 out = out.numpy()
-                if host_blend is not None:      # inpainting: the known region back at the next step's noise level
+                if host_blend is not None and plan["ends"][i]:   # inpainting: the known region back at the next step's noise level
                     hb = host_blend
-                    known = hb["z0"] if i == len(ts) - 1 else add_noise(hb["z0"], hb["eps"], hb["sa"][i + 1], hb["sb"][i + 1])
+                    known = hb["z0"] if j == len(plan["grid"]) - 1 else add_noise(hb["z0"], hb["eps"], hb["sa"][j + 1], hb["sb"][j + 1])
                     out = blend_latents(known, out, hb["mask"])
                 eng.sample_set_latents(out)
             if cb_end is not None:
