@@ -102,7 +102,7 @@ typedef struct pd_sample_args {
     int32_t only_mid_control; /* cldm/cldm.py:38 */
     float temperature;        /* ddim_hacked.py:230 */
     int32_t mem;              /* PD_MEM_* of every pointer below */
-    const float* x_T;         /* [B, in_ch, h, w] initial latents (required) */
+    const float* x_T;         /* [B, in_ch, h, w] initial latents (required unless PD_XT_FROM_SEED) */
     const float* ctx_cond;    /* [B, L, D] */
     const float* ctx_uncond;  /* [B, L, D] (use_cfg) */
     const float* pair;        /* [B, hint_ch, 8h, 8w] example pair */
@@ -112,7 +112,8 @@ typedef struct pd_sample_args {
     const float* control_scales;      /* [13] or NULL (= all 1.0), cldm/cldm.py:335,379 */
     const float* control_scales_step; /* optional [steps][13]: per-step scales in sampling order
                                          (controlnet_keep gating, pipeline :1196-1202,:1229-1235) */
-    const float* noise;       /* eta > 0: [steps][B, in_ch, h, w] standard normal draws (required then: ddim_hacked.py:230) */
+    const float* noise;       /* eta > 0: [steps][B, in_ch, h, w] standard normal draws (required then: ddim_hacked.py:230),
+                                 or NULL with PD_NOISE_FROM_SEED */
     const int64_t* timesteps; /* optional, HOST memory whatever `mem` says: [steps] custom DDIM timesteps in sampling order
                                  (strictly descending) replacing the uniform grid of make_ddim_timesteps -- the (D) pipeline's
                                  `timesteps=` argument (pipeline_prompt_diffusion.py:101-142) and diffusers' leading-spaced
@@ -127,10 +128,15 @@ typedef struct pd_sample_args {
      *     pd_sample_eps_at (host-driven schedulers blend on the host). */
     const float* init_latents; /* optional [B, in_ch, h, w] in `mem`: z0 = scale_factor * the init image's latents */
     const float* mask;         /* optional [B, 1, h, w] in `mem`, needs init_latents; weight of the SAMPLED latents (1 = repaint, 0 = keep) */
-    int32_t init_flags;        /* PD_INIT_PURE_NOISE: start from x_T itself (diffusers' strength == 1 inpainting) */
+    int32_t init_flags;        /* PD_INIT_PURE_NOISE: start from x_T itself (diffusers' strength == 1 inpainting);
+                                  PD_NOISE_FROM_SEED / PD_XT_FROM_SEED: see "Seeded noise" below */
     int32_t reserved[1];
 } pd_sample_args;
 #define PD_INIT_PURE_NOISE 1
+#define PD_NOISE_FROM_SEED 2 /* the per-step draws (eta > 0 DDIM, multistep rows with [14] != 0) come from the engine's generator;
+                                `noise` must be NULL */
+#define PD_XT_FROM_SEED    4 /* x_T must be NULL: the session's start kernel draws it (stream PD_RNG_XT, draw 0); per_step_out[0]
+                                reports it; with init_latents it is the img2img noise eps, exactly as a caller's x_T is */
 
 const char* pd_last_error(void);
 int pd_abi_version(void);
@@ -180,6 +186,33 @@ int pd_lora_remove(pd_engine* e, int32_t adapter);
 int pd_set_freeu(pd_engine* e, float s1, float s2, float b1, float b2);
 int pd_get_freeu(pd_engine* e, float out[4]);
 
+/* Seeded noise.  The engine draws standard normals itself with the counter-based generator Philox4x32-10 (multipliers
+ * 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85, ten rounds): one block maps (counter[4], key[2]) to four
+ * uint32 r0..r3, and Box-Muller in fp32 turns them into four normals:
+ *   u(r) = (float)r * 2^-32 + 2^-33                                   in (0, 1]
+ *   (z0, z1) = sqrtf(-2 logf(u(r0))) * (cospif, sinpif)(2 u(r1)),     (z2, z3) the same from r2, r3
+ * Addressing -- the contract; a value depends on nothing else (not on the batch split, the grid or the kernel that draws it):
+ *   key     = (seed low 32 bits, seed high 32 bits)
+ *   counter = (q, sample, draw, stream),  the element takes z[lane]
+ *   q = e / 4 (low 32 bits), lane = e % 4, e = the element's index within its sample in the caller's NCHW layout (c * HW + p)
+ *   sample  = sample_base + b: a 64-bit add of which the low 32 bits are used, so samples 2^32 apart share their draws
+ *   draw    = the step (DDIM) or row (linear multistep) index; 0 for x_T and the VAE posterior
+ *   stream  = PD_RNG_XT, PD_RNG_STEP, PD_RNG_VAE, or PD_RNG_USER + k (k >= 0) for a caller's own draws through pd_randn
+ * pd_philox4x32_10: one block on the host (no engine, no GPU).
+ * pd_set_rng / pd_get_rng: engine state like FreeU, default (0, 0).  The two values live in a small device buffer the kernels
+ *   read, updated by a copy ordered on the engine's stream: a captured graph (option "graph") replays with the new seed, it is
+ *   neither dropped nor captured again.
+ * pd_randn: out[B][per_sample] (fp32, `mem`) = the values the loop draws at (stream, draw, sample_base + b, e); any
+ *   per_sample >= 1. */
+#define PD_RNG_XT   0
+#define PD_RNG_STEP 1
+#define PD_RNG_VAE  2
+#define PD_RNG_USER 16
+void pd_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
+int pd_set_rng(pd_engine* e, uint64_t seed, uint64_t sample_base);
+int pd_get_rng(pd_engine* e, uint64_t* seed, uint64_t* sample_base);
+int pd_randn(pd_engine* e, int32_t stream, int32_t draw, int32_t B, int64_t per_sample, int32_t mem, float* out);
+
 /* first-stage decode, LatentDiffusion.decode_first_stage (ldm/models/diffusion/ddpm.py:820-828) ->
  * AutoencoderKL.decode (ldm/models/autoencoder.py:89-92) -> Decoder.forward (ldm/modules/diffusionmodules/model.py:619-653):
  * latents [B, in_ch, h, w] -> images [B, vae_out_ch, 8h, 8w] in roughly [-1, 1] (fp32, NCHW).  Call after the sampling
@@ -191,12 +224,13 @@ int pd_vae_decode(pd_engine* e, const float* latents, int32_t B, int32_t h, int3
  * (ldm/modules/distributions/distributions.py:24-62; logvar clamped to [-30, 20], std = exp(0.5 logvar)).
  * images [B, vae_out_ch, H, W] in [-1, 1], NCHW fp32; H and W multiples of 8 with (H/8)*(W/8) a multiple of 64.  `images`,
  * `noise` and `out` live in `mem`.  Needs an engine created with vae_encoder = 1, its first_stage_model.encoder.* /
- * first_stage_model.quant_conv.* weights, and no active sampling session.  Random draws come from the caller: */
+ * first_stage_model.quant_conv.* weights, and no active sampling session.  Random draws come from the caller, or, with
+ * `noise` NULL, from the engine's generator at (PD_RNG_VAE, draw 0): */
 #define PD_VAE_MEAN    0  /* scale_factor * posterior.mode()                        -> [B, z, H/8, W/8]   */
-#define PD_VAE_SAMPLE  1  /* scale_factor * posterior.sample() with caller `noise`  -> [B, z, H/8, W/8]   */
+#define PD_VAE_SAMPLE  1  /* scale_factor * posterior.sample() (`noise` or seeded)  -> [B, z, H/8, W/8]   */
 #define PD_VAE_MOMENTS 2  /* quant_conv output (mean ; logvar), unscaled            -> [B, 2z, H/8, W/8]  */
 int pd_vae_encode(pd_engine* e, const float* images, int32_t B, int32_t H, int32_t W, int32_t mem, int32_t what,
-                  const float* noise /* [B, z, H/8, W/8], SAMPLE only */, float* out);
+                  const float* noise /* [B, z, H/8, W/8] or NULL, SAMPLE only */, float* out);
 /* number of encoder tensors not loaded yet (0 when the encoder is not built) */
 int pd_vae_encoder_weights_missing(pd_engine* e);
 
@@ -273,7 +307,8 @@ int pd_sample_begin_unipc(pd_engine* e, const pd_sample_args* args, const pd_uni
  * and DPM-Solver++ multistep (DPM_Solver.sample(method="multistep"), ldm/models/diffusion/dpm_solver/dpm_solver.py) are linear
  * in a base sample and a short history of model outputs, so one evaluation ends in one elementwise kernel driven by a
  * coefficient row computed on the host in fp64.  The device state -- a ring of three earlier model outputs and one kept
- * sample -- is fp64; only the sample and pred_x0 a row returns are rounded to fp32.  eta must be 0 and noise NULL.
+ * sample -- is fp64; only the sample and pred_x0 a row returns are rounded to fp32.  eta must be 0 and noise NULL; a stochastic
+ * solver adds seeded noise through slot [14] of its rows (PD_NOISE_FROM_SEED).
  * One row = one UNet evaluation.  A row may or may not complete a sampling step: PLMS's first step takes two evaluations
  * (plms.py:227-231), so PLMS over S steps has S + 1 rows at the times t_0, t_1, t_1, t_2, ..; per_step_out still has S + 1
  * entries (x_T and the sample after every completed step), the inpainting blend and control_scales_step follow completed
@@ -281,6 +316,12 @@ int pd_sample_begin_unipc(pd_engine* e, const pd_sample_args* args, const pd_uni
 #define PD_LMS_PLMS  0 /* PLMSSampler: Adams-Bashforth on eps, orders 1..4 by warm-up, pseudo improved Euler first step */
 #define PD_LMS_DPMPP 1 /* DPM-Solver++ multistep (data prediction), order 1..3 */
 #define PD_LMS_ROWS  2 /* the caller's own rows / row_times / n_rows */
+#define PD_LMS_EULER_A 3 /* Euler ancestral (k-diffusion sample_euler_ancestral, eta = 1) in the engine's VP variables; needs
+                            PD_NOISE_FROM_SEED.  With alpha = sqrt(abar), sigma = sqrt(1 - abar), s = sigma / alpha, for the step from
+                            t_i to t_{i+1} (s = 0 after the last): s_up = sqrt(s_to^2 (s_from^2 - s_to^2) / s_from^2),
+                            s_down = sqrt(s_to^2 - s_up^2); one row per step with m_i = eps: [3] = alpha_to / alpha_from,
+                            [4] = alpha_to (s_down - s_from), [14] = alpha_to s_up, [8] = 1 / alpha_from,
+                            [9] = -sigma_from / alpha_from, flags PD_LMS_F_STEP; the last row has [14] = 0 */
 #define PD_LMS_DPM_SOLVER 0 /* solver_type "dpm_solver" (diffusers "midpoint") */
 #define PD_LMS_TAYLOR     1 /* solver_type "taylor" (diffusers "heun") */
 typedef struct pd_lms_args {
@@ -306,7 +347,10 @@ typedef struct pd_lms_args {
  *   [0] alpha_i   [1] sigma_i   [2] flags (sum of PD_LMS_F_*)
  *   [3..7]  x_next  = [3] base + [4] m_i + [5] m_{i-1} + [6] m_{i-2} + [7] m_{i-3}
  *   [8..12] pred_x0 = [8] base + [9] m_i + [10] m_{i-1} + [11] m_{i-2} + [12] m_{i-3}
- *   [13] how many of m_{i-1}, m_{i-2}, m_{i-3} the row reads (at most the rows pushed so far)   [14], [15] zero
+ *   [13] how many of m_{i-1}, m_{i-2}, m_{i-3} the row reads (at most the rows pushed so far)
+ *   [14] noise coefficient: x_next += [14] z, z the seeded normal at (PD_RNG_STEP, draw = row index), added in fp64 after the
+ *        sum above (a row with [14] == 0 computes exactly what it did without the slot); pred_x0 takes no noise; a non-zero
+ *        [14] needs PD_NOISE_FROM_SEED   [15] zero
  * m_{i-k} counts pushed outputs only: an evaluation without PD_LMS_F_PUSH never enters the history. */
 #define PD_LMS_NCOEF 16
 #define PD_LMS_F_DATA_PRED  1 /* m_i is the x0 prediction */
@@ -396,7 +440,8 @@ int pd_comm_destroy(pd_engine* e); /* also done by pd_engine_destroy */
  *   GroupNorm that reads them instead of running a finalize pass, 1; bit-identical), "patch_split_min" (patch-conv split-K: at
  *   least this many 128-byte channel chunks per slice, 4). */
 int pd_set_option(pd_engine* e, const char* key, int64_t value);
-/* "workspace_bytes", "weight_bytes", "launches" (engine launches, split-K finalize passes not counted), "ring_launches" / "gn_from_slabs"
+/* "graph_captures" / "graph_replays" (step loops captured / replayed from a captured graph since the engine was created),
+ * "workspace_bytes", "weight_bytes", "launches" (engine launches, split-K finalize passes not counted), "ring_launches" / "gn_from_slabs"
  * (of which: gemm_ring.hip / GroupNorm fed by split-K slabs), "steps", "event_overhead_ns", "cfg_shared" (see option "cfg_share") */
 int64_t pd_get_stat(pd_engine* e, const char* key);
 /* Per-launch timing: while option "profile" is 1 the engine brackets every contraction launch with HIP

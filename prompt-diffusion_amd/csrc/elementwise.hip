@@ -3,6 +3,7 @@
 // on the device with no host round trip per step.
 #include "../../include/pdengine.h"
 #include "pd_common.h"
+#include "pd_philox.h"
 
 namespace {
 
@@ -88,7 +89,7 @@ __global__ void nhwc_to_nchw_kernel(const void* __restrict__ in, int in_dt, floa
 // One thread per output element, fp32 arithmetic throughout; reads of `mom` are strided by Cpad (8 floats = 32 bytes for the
 // SD VAE), the NCHW writes and noise reads are contiguous.  Tiny next to the encoder's convolutions.
 __global__ void vae_posterior_kernel(const void* __restrict__ mom, int mom_dt, int Cpad, const float* __restrict__ noise,
-                                     float* __restrict__ out, int B, int z, int HW, int what, float scale) {
+                                     float* __restrict__ out, int B, int z, int HW, int what, float scale, PdRng rng) {
     const int Cout = what == PD_VAE_MOMENTS ? 2 * z : z;
     const long long total = (long long)B * Cout * HW;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
@@ -107,7 +108,9 @@ __global__ void vae_posterior_kernel(const void* __restrict__ mom, int mom_dt, i
         } else if (what == PD_VAE_SAMPLE) {
             const float lv = fminf(fmaxf(ld(j + z), -30.0f), 20.0f);
             const float sd = expf(0.5f * lv);   // std = exp(0.5 * logvar) (distributions.py:28-29)
-            v = scale * (m + sd * noise[((long long)b * z + c) * HW + p]);
+            // the caller's draw, or the engine's own at (PD_RNG_VAE, draw 0)
+            const float nz = noise ? noise[((long long)b * z + c) * HW + p] : pd_rng_normal(rng, PD_RNG_VAE, 0u, (uint32_t)b, (long long)c * HW + p);
+            v = scale * (m + sd * nz);
         } else {
             v = scale * m;
         }
@@ -212,10 +215,11 @@ int launch_nhwc_to_nchw(const void* in, int in_dt, float* out, int B, int C, int
     CHECK_LAUNCH();
 }
 int launch_vae_posterior(const void* mom, int mom_dt, int Cpad, const float* noise, float* out, int B, int z, int HW, int what, float scale,
-                         hipStream_t s) {
-    if (Cpad < 2 * z || (what == PD_VAE_SAMPLE && !noise) || (what != PD_VAE_MEAN && what != PD_VAE_SAMPLE && what != PD_VAE_MOMENTS)) return 1;
+                         hipStream_t s, const uint32_t* rng_state) {
+    if (Cpad < 2 * z || (what == PD_VAE_SAMPLE && !noise && !rng_state) || (what != PD_VAE_MEAN && what != PD_VAE_SAMPLE && what != PD_VAE_MOMENTS)) return 1;
     const long long n = (long long)B * (what == PD_VAE_MOMENTS ? 2 * z : z) * HW;
-    hipLaunchKernelGGL(vae_posterior_kernel, dim3(nblocks(n)), dim3(TPB), 0, s, mom, mom_dt, Cpad, noise, out, B, z, HW, what, scale);
+    hipLaunchKernelGGL(vae_posterior_kernel, dim3(nblocks(n)), dim3(TPB), 0, s, mom, mom_dt, Cpad, noise, out, B, z, HW, what, scale,
+                       PdRng{rng_state});
     CHECK_LAUNCH();
 }
 int launch_cast_rows(const float* in, void* out, int out_dt, long long rows, int C, int Cpad, hipStream_t s) {

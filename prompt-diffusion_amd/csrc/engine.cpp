@@ -321,6 +321,7 @@ int pd_engine::build() {
     gn_partial2 = reinterpret_cast<double*>(dmalloc(gn_partial_cap));
     tile_cnt = reinterpret_cast<int*>(dmalloc(kTileCnt * sizeof(int)));    // dmalloc zero-fills
     tile_cnt2 = reinterpret_cast<int*>(dmalloc(kTileCnt * sizeof(int)));
+    rng_dev = reinterpret_cast<uint32_t*>(dmalloc(4 * sizeof(uint32_t)));   // seed 0, sample_base 0
     if (hipStreamCreateWithFlags(&stream2, hipStreamNonBlocking) != hipSuccess) stream2 = nullptr;
     if (hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&ev_join, hipEventDisableTiming) != hipSuccess) {

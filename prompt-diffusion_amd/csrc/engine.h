@@ -305,6 +305,7 @@ struct Session {
     float* pred_x0 = nullptr;   // [B, HW, C]
     float* eps_g = nullptr;     // [B, HW, C]
     float* noise = nullptr;     // [S][B, C, HW] or null
+    bool noise_seeded = false;  // PD_NOISE_FROM_SEED: the update kernels draw the per-step noise themselves (no arena for it)
     void* ctx = nullptr;        // [Bf, L, Dpad] compute type
     Act hint;                   // guided_hint [Bf, h, w, C0]
     std::vector<KVSlot> kv_u, kv_c;
@@ -380,6 +381,12 @@ struct pd_engine {
     // FreeU (pd_set_freeu): {s1, s2, b1, b2}, all zero when off; per engine, read by run_unet at every decoder block
     float freeu[4] = {0.f, 0.f, 0.f, 0.f};
     bool freeu_on() const { return freeu[0] != 0.f && freeu[1] != 0.f && freeu[2] != 0.f && freeu[3] != 0.f; }
+    // seeded noise (pd_set_rng; addressing in include/pdengine.h): {seed_lo, seed_hi, base_lo, base_hi} on the device, read by the
+    // update / start / posterior / fill kernels, rewritten by a copy ordered on `stream` (captured graphs see the new values)
+    uint32_t* rng_dev = nullptr;
+    uint32_t rng_host[4] = {0u, 0u, 0u, 0u};
+    uint64_t rng_seed = 0, rng_base = 0;
+    long long graph_captures = 0, graph_replays = 0;   // stats: step loops captured / replayed
     bool opt_cfg_share = true;   // option "cfg_share": the layers in front of the first cross-attention once per CFG pair (forward_eps)
     void swap_context();
     int join_controlnet();

@@ -340,6 +340,38 @@ int dpmpp_rows(const pd_config& cfg, const pd_lms_args& u, const int64_t* ts, in
     return 0;
 }
 
+// Euler ancestral: k-diffusion's sample_euler_ancestral (eta = 1) restated in the engine's VP variables.  With x~ = x / alpha the
+// sample of the variance-exploding form and s = sigma / alpha its noise level, d = (x~ - denoised) / s is the guided eps, and
+//   x~' = x~ + d (s_down - s_from) + z s_up,  s_up = sqrt(s_to^2 (s_from^2 - s_to^2) / s_from^2),  s_down = sqrt(s_to^2 - s_up^2);
+// multiplied by alpha_to this is one row with m_i = eps and the noise coefficient in slot [14].  The loop lands on s = 0, where
+// s_up = s_down = 0 and the row returns the x0 prediction.
+int euler_a_rows(const pd_config& cfg, const int64_t* ts, int n, std::vector<double>& rows, std::vector<double>& times) {
+    PD_TRY(check_desc_grid(cfg, ts, n, "euler_a"));
+    std::vector<double> ac;
+    alphas_cumprod_f64(cfg, ac);
+    rows.assign((size_t)n * PD_LMS_NCOEF, 0.0);
+    times.assign(n, 0.0);
+    for (int i = 0; i < n; ++i) {
+        double* r = &rows[(size_t)i * PD_LMS_NCOEF];
+        const double a_from = std::sqrt(ac[ts[i]]), sg_from = std::sqrt(1.0 - ac[ts[i]]), s_from = sg_from / a_from;
+        const bool last = i + 1 == n;
+        const double a_to = last ? 1.0 : std::sqrt(ac[ts[i + 1]]);
+        const double s_to = last ? 0.0 : std::sqrt(1.0 - ac[ts[i + 1]]) / a_to;
+        const double s_up = std::sqrt(s_to * s_to * (s_from * s_from - s_to * s_to) / (s_from * s_from));
+        const double s_down = std::sqrt(s_to * s_to - s_up * s_up);
+        r[0] = a_from;
+        r[1] = sg_from;
+        r[2] = PD_LMS_F_STEP;
+        r[3] = a_to / a_from;
+        r[4] = a_to * (s_down - s_from);
+        r[8] = 1.0 / a_from;
+        r[9] = -sg_from / a_from;
+        r[14] = last ? 0.0 : a_to * s_up;
+        times[i] = (double)ts[i];
+    }
+    return 0;
+}
+
 }  // namespace
 
 // checks rows a caller brought (or the generators made): flags, history depth against the pushes so far, the step count
@@ -357,6 +389,7 @@ static int lms_check_rows(const std::vector<double>& rows, int n_rows, int steps
         if ((fl & PD_LMS_F_BASE_KEEP) && !kept) { pd_set_error("lms: row %d reads the kept sample before any row stored it", i); return 1; }
         for (int k = 0; k < PD_LMS_NCOEF; ++k)
             if (!std::isfinite(r[k])) { pd_set_error("lms: row %d holds a non-finite coefficient", i); return 1; }
+        if (r[15] != 0.0) { pd_set_error("lms: row %d: slot [15] must be zero (got %g)", i, r[15]); return 1; }
         if (fl & PD_LMS_F_PUSH) ++pushed;
         if (fl & PD_LMS_F_STEP) ++done;
     }
@@ -372,6 +405,9 @@ int pd_lms_table(const pd_config& cfg, const pd_lms_args& u, const int64_t* ts, 
         PD_TRY(plms_rows(cfg, ts, n, rows, times));
     } else if (u.kind == PD_LMS_DPMPP) {
         PD_TRY(dpmpp_rows(cfg, u, ts, n, rows, times));
+    } else if (u.kind == PD_LMS_EULER_A) {
+        if (u.model_times) { pd_set_error("euler_a: runs on the integer grid (model_times is for dpm-solver++)"); return 1; }
+        PD_TRY(euler_a_rows(cfg, ts, n, rows, times));
     } else if (u.kind == PD_LMS_ROWS) {
         if (!u.rows || !u.row_times || u.n_rows < 1 || u.n_rows > 4 * cfg.timesteps) { pd_set_error("lms: rows, row_times and n_rows are required"); return 1; }
         rows.assign(u.rows, u.rows + (size_t)u.n_rows * PD_LMS_NCOEF);

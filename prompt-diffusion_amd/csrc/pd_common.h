@@ -316,9 +316,10 @@ struct UpdateState {
 struct BlendCoef { float sa, sb; int last; };
 struct BlendArgs { const float* z0; const float* ieps; const float* mask; BlendCoef coef; };
 struct DdimCoef { float sqrt_one_minus_at, sqrt_at, sqrt_a_prev, dir_coef, sigma, cfg_scale; };
-// do_update 0: only eps_guided is written; bl null: no blend
+// do_update 0: only eps_guided is written; bl null: no blend.  rng_state (the engine's device RNG state, pd_set_rng) non-null:
+// the draw comes from the generator at (PD_RNG_STEP, draw) and noise must be null
 int launch_cfg_ddim(const UpdateState& u, const DdimCoef& k, const float* noise, float temperature, int do_update, const BlendArgs* bl,
-                    hipStream_t s);
+                    hipStream_t s, const uint32_t* rng_state = nullptr, uint32_t draw = 0);
 // Fused UniPC step (include/pdengine.h, PD_UNIPC_NCOEF): one coefficient row, passed by value so a captured graph bakes it in.
 //   c_m[0..3]: corrector weights of m_i, m_{i-1}, m_{i-2}, m_{i-3}; p_m[0..2]: predictor weights of m_i, m_{i-1}, m_{i-2};
 //   n_hist: how many of the history slots m_{i-1}, m_{i-2}, m_{i-3} the step reads (the others may be null)
@@ -331,14 +332,19 @@ int launch_cfg_unipc(const UpdateState& u, const UnipcCoef& k, double* last, dou
 //   x_next = c_x base + sum_k c_m[k] m_{i-k},  pred_x0 = q_x base + sum_k q_m[k] m_{i-k},  base = base_keep ? keep : x;
 //   data_pred: m_i = (x - sigma eps) / alpha, else m_i = eps; store_keep: keep = x before the update; push: m_i -> m_out;
 //   n_hist: how many of m_{i-1}, m_{i-2}, m_{i-3} the row reads
-struct LmsCoef { double alpha, sigma, c_x, c_m[4], q_x, q_m[4]; int data_pred, base_keep, store_keep, push, n_hist; float cfg_scale; };
+//   c_z: x_next += c_z z with z the seeded normal at (PD_RNG_STEP, draw); needs rng_state when non-zero
+struct LmsCoef { double alpha, sigma, c_x, c_m[4], q_x, q_m[4]; int data_pred, base_keep, store_keep, push, n_hist; float cfg_scale; double c_z; };
 // keep [B, HW, C] fp64: the kept sample (null when no flag uses it); m_out / hist as in launch_cfg_unipc
 int launch_cfg_lms(const UpdateState& u, const LmsCoef& k, double* keep, double* m_out, const double* const hist[3], const BlendArgs* bl,
-                   hipStream_t s);
+                   hipStream_t s, const uint32_t* rng_state = nullptr, uint32_t draw = 0);
 // start latents: x = pure ? eps : sa z0 + sb eps -> x_state [B, HW, Cpad] (channels >= C zero), x_in (dup copies), and
-// optionally out_nchw [B, C, HW]
+// optionally out_nchw [B, C, HW].  rng_state non-null: eps is drawn at (PD_RNG_XT, draw 0) instead of read, and stored to
+// eps_out [B, C, HW] when that is non-null
 int launch_init_latents(const float* z0, const float* eps, float sa, float sb, int pure, float* x_state, float* x_in, float* out_nchw,
-                        int B, int dup, int C, int Cpad, int HW, hipStream_t s);
+                        int B, int dup, int C, int Cpad, int HW, hipStream_t s, const uint32_t* rng_state = nullptr,
+                        float* eps_out = nullptr);
+// out [B][per_sample] fp32 = the seeded normals at (stream, draw, sample b, element e) (pd_philox.h; pd_randn)
+int launch_randn(const uint32_t* rng_state, uint32_t stream, uint32_t draw, int B, long long per_sample, float* out, hipStream_t s);
 int launch_fill_random(void* p, int dt, long long n, float scale, float shift, uint64_t seed, hipStream_t s);
 // LoRA merge (lora.hip) of one matrix parameter: W rows = round_dt(W0 + (scale . UT)^T D); UT [R][rows], D [R][Kpad] fp32,
 // scale [R]; source row n -> WMat row row_off + n, or the 80 + 80 GEGLU interleave when geglu_half > 0 (row_off 0); W0 holds the
@@ -348,8 +354,9 @@ int launch_lora_merge(int dt, void* W, const void* W0, int rows, int row_off, in
 // DiagonalGaussianDistribution of the first-stage encoder (distributions.py:24-62) from quant_conv's NHWC output `mom` (dtype mom_dt,
 // Cpad >= 2 z channels: mean 0..z-1, logvar z..2z-1) into caller-layout fp32 NCHW: what = PD_VAE_MEAN: scale * mean,
 // PD_VAE_SAMPLE: scale * (mean + exp(0.5 clamp(logvar, -30, 20)) * noise[B, z, HW]), PD_VAE_MOMENTS: the raw [B, 2z, HW] moments
+// noise null with PD_VAE_SAMPLE: the seeded normals at (PD_RNG_VAE, draw 0) from rng_state
 int launch_vae_posterior(const void* mom, int mom_dt, int Cpad, const float* noise, float* out, int B, int z, int HW, int what, float scale,
-                         hipStream_t s);
+                         hipStream_t s, const uint32_t* rng_state = nullptr);
 // sd3_kernels.hip: element-wise pieces of the MMDiT path
 // y_dt == DT_FP8: y holds e4m3 bytes and y_scale[row] the row's scale (max |value| / 448); add: x <- x + add first (written back)
 int launch_adaln(const void* x, int x_dt, void* y, int y_dt, const float* mod, int mod_stride, int shift_off, int scale_off, int rows,

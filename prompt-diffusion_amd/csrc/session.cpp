@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "engine.h"
+#include "pd_philox.h"
 
 const char* pd_err_buf();
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
@@ -132,6 +133,7 @@ int pd_engine::session_setup(const pd_sample_args& a, const int64_t* t_rows, int
     const int L = cfg.context_len, D = cfg.context_dim, Dp = round_up(D, 8), lpad = round_up(L, 8);
     const int IH = a.h * 8, IW = a.w * 8;
     const bool dev = a.mem == PD_MEM_DEVICE;
+    const bool xt_seeded = (a.init_flags & PD_XT_FROM_SEED) != 0;
     arena.top = 0;
     arena.overflow = false;
     s.x_state = reinterpret_cast<float*>(arena.alloc((size_t)B * HW * 8 * 4));
@@ -196,14 +198,24 @@ int pd_engine::session_setup(const pd_sample_args& a, const int64_t* t_rows, int
         if (!arena.dry) {
             const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
             const size_t n = (size_t)B * C * HW;
-            HIP_OK(hipMemcpyAsync(s.init_eps, a.x_T, n * 4, kind, stream));
+            if (!xt_seeded) HIP_OK(hipMemcpyAsync(s.init_eps, a.x_T, n * 4, kind, stream));
             HIP_OK(hipMemcpyAsync(s.init_z0, a.init_latents, n * 4, kind, stream));
             if (s.mask) HIP_OK(hipMemcpyAsync(s.mask, a.mask, (size_t)B * HW * 4, kind, stream));
             HIP_OK(hipStreamSynchronize(stream));
             const BlendCoef& b0 = s.blend[0];
             ++launches;
             if (launch_init_latents(s.init_z0, s.init_eps, b0.sa, b0.sb, (a.init_flags & PD_INIT_PURE_NOISE) ? 1 : 0, s.x_state, s.x_in,
-                                    s.per_step, B, Bf / B, C, 8, HW, stream)) {
+                                    s.per_step, B, Bf / B, C, 8, HW, stream, xt_seeded ? rng_dev : nullptr, s.init_eps)) {
+                pd_set_error("start latents launch failed");
+                return 1;
+            }
+        }
+    } else if (xt_seeded) {
+        // x_T drawn by the start kernel itself: no staging copy, no layout conversion
+        if (!arena.dry) {
+            ++launches;
+            if (launch_init_latents(nullptr, nullptr, 1.f, 0.f, 1, s.x_state, s.x_in, s.per_step, B, Bf / B, C, 8, HW, stream, rng_dev,
+                                    nullptr)) {
                 pd_set_error("start latents launch failed");
                 return 1;
             }
@@ -362,16 +374,24 @@ static int check_args(pd_engine* e, const pd_sample_args* a) {
                      e->cfg.num_levels - 1);
         return 1;
     }
-    if (!a->x_T || !a->ctx_cond || !a->pair || !a->query) { pd_set_error("x_T, ctx_cond, pair and query are required"); return 1; }
+    if (a->init_flags & PD_XT_FROM_SEED) {
+        if (a->x_T) { pd_set_error("init_flags PD_XT_FROM_SEED: x_T must be NULL (the engine draws it)"); return 1; }
+    } else if (!a->x_T) { pd_set_error("x_T, ctx_cond, pair and query are required"); return 1; }
+    if (!a->ctx_cond || !a->pair || !a->query) { pd_set_error("x_T, ctx_cond, pair and query are required"); return 1; }
+    if ((a->init_flags & PD_NOISE_FROM_SEED) && a->noise) {
+        pd_set_error("init_flags PD_NOISE_FROM_SEED: noise must be NULL (the engine draws the per-step noise)");
+        return 1;
+    }
     if (a->use_cfg && !a->ctx_uncond) { pd_set_error("use_cfg needs ctx_uncond"); return 1; }
-    if (a->eta > 0.f && !a->noise) {
+    if (a->eta > 0.f && !a->noise && !(a->init_flags & PD_NOISE_FROM_SEED)) {
         // the reference always draws noise when eta > 0 (ddim_hacked.py:230); running the eta > 0 coefficients without
         // it would deflate the sample variance silently
         pd_set_error("eta > 0 needs the noise draws (pd_sample_args.noise: [steps][B, in_ch, h, w])");
         return 1;
     }
     if (a->mask && !a->init_latents) { pd_set_error("mask needs init_latents (the latents of the region to keep)"); return 1; }
-    if (a->init_flags & ~PD_INIT_PURE_NOISE) { pd_set_error("init_flags: unknown bits 0x%x", (unsigned)(a->init_flags & ~PD_INIT_PURE_NOISE)); return 1; }
+    const int32_t known_flags = PD_INIT_PURE_NOISE | PD_NOISE_FROM_SEED | PD_XT_FROM_SEED;
+    if (a->init_flags & ~known_flags) { pd_set_error("init_flags: unknown bits 0x%x", (unsigned)(a->init_flags & ~known_flags)); return 1; }
     if ((a->init_flags & PD_INIT_PURE_NOISE) && !a->init_latents) { pd_set_error("init_flags PD_INIT_PURE_NOISE needs init_latents"); return 1; }
     for (auto& p : e->params)
         if (p.group == 0 && !p.loaded) { pd_set_error("weights not loaded: '%s' (and possibly more)", p.name.c_str()); return 1; }
@@ -390,6 +410,7 @@ int pd_engine::begin(const pd_sample_args* a, bool want_per_step, const pd_unipc
     ses.lms_pushed.clear();
     ses.lms_ring = 0;
     ses.lms_keep = false;
+    ses.noise_seeded = !l && !u && (a->init_flags & PD_NOISE_FROM_SEED) && a->eta > 0.f;
     if (l) {
         if (a->eta != 0.f || a->noise) { pd_set_error("lms: eta must be 0 and noise NULL (a linear multistep solver draws no noise)"); return 1; }
         if (a->init_latents && (l->model_times || l->kind == PD_LMS_ROWS || !a->timesteps)) {
@@ -411,6 +432,13 @@ int pd_engine::begin(const pd_sample_args* a, bool want_per_step, const pd_unipc
             if (fl & (PD_LMS_F_STORE_KEEP | PD_LMS_F_BASE_KEEP)) ses.lms_keep = true;
             if (fl & PD_LMS_F_STEP) ++done;
             if (fl & PD_LMS_F_PUSH) ++pushed;
+            if (row[14] != 0.0) {
+                if (!(a->init_flags & PD_NOISE_FROM_SEED)) {
+                    pd_set_error("lms: row %d adds noise ([14] = %g): the session needs init_flags PD_NOISE_FROM_SEED", r, row[14]);
+                    return 1;
+                }
+                ses.noise_seeded = true;
+            }
         }
         ses.lms_ring = ring;
     }
@@ -522,7 +550,7 @@ int pd_engine::step_ddim(int i, const UpdateState& u, const BlendArgs* bl) {
     k.sigma = sig;
     k.cfg_scale = s.a.cfg_scale;
     const float* nz = s.noise ? s.noise + (size_t)i * u.B * u.C * u.HW : nullptr;
-    if (launch_cfg_ddim(u, k, nz, s.a.temperature, 1, bl, stream)) {
+    if (launch_cfg_ddim(u, k, nz, s.a.temperature, 1, bl, stream, s.noise_seeded ? rng_dev : nullptr, (uint32_t)i)) {
         pd_set_error("ddim update launch failed");
         return 1;
     }
@@ -573,12 +601,13 @@ int pd_engine::step_lms(int i, const UpdateState& u, const BlendArgs* bl) {
     k.store_keep = (fl & PD_LMS_F_STORE_KEEP) != 0;
     k.push = (fl & PD_LMS_F_PUSH) != 0;
     k.n_hist = (int)row[13];
+    k.c_z = row[14];
     k.cfg_scale = s.a.cfg_scale;
     const int R = s.lms_ring, np = s.lms_pushed[i];
     if (k.n_hist > R || k.n_hist > np) { pd_set_error("lms: row %d needs %d earlier model outputs", i, k.n_hist); return 1; }
     const double* hist[3] = {nullptr, nullptr, nullptr};
     for (int j = 0; j < k.n_hist; ++j) hist[j] = s.l_ring[(np - 1 - j) % R];
-    if (launch_cfg_lms(u, k, s.l_keep, s.l_ring[np % R], hist, bl, stream)) {
+    if (launch_cfg_lms(u, k, s.l_keep, s.l_ring[np % R], hist, bl, stream, k.c_z != 0.0 ? rng_dev : nullptr, (uint32_t)i)) {
         pd_set_error("lms update launch failed");
         return 1;
     }
@@ -607,8 +636,9 @@ static inline void hash_mix(uint64_t& h, const void* p, size_t n) {
 int pd_engine::run_steps_graph() {
     const pd_sample_args& a = ses.a;
     uint64_t key = 1469598103934665603ull;
+    // (where the noise comes from is part of the key -- another kernel --, the seed is not: the kernels read it from rng_dev)
     const int32_t ints[] = {a.batch, a.h, a.w, a.steps, a.use_cfg, a.guess_mode, a.only_mid_control, ses.noise ? 1 : 0,
-                            ses.per_step ? 1 : 0, opt_two_streams ? 1 : 0, ses.S, opt_cfg_share ? 1 : 0};
+                            ses.per_step ? 1 : 0, opt_two_streams ? 1 : 0, ses.S, opt_cfg_share ? 1 : 0, ses.noise_seeded ? 1 : 0};
     const float flts[] = {a.eta, a.cfg_scale, a.temperature};
     const void* ptrs[] = {arena.base, arena2.base, ses.x_state, ses.per_step};
     hash_mix(key, ints, sizeof(ints));
@@ -631,6 +661,7 @@ int pd_engine::run_steps_graph() {
     for (auto& g : graphs)
         if (g.key == key) {
             HIP_OK(hipGraphLaunch(g.exec, stream));
+            ++graph_replays;
             return 0;
         }
     GraphEntry ge{key, nullptr, nullptr};
@@ -654,6 +685,7 @@ int pd_engine::run_steps_graph() {
     }
     if (graphs.size() >= 8) clear_graphs();
     graphs.push_back(ge);
+    ++graph_captures;
     HIP_OK(hipGraphLaunch(ge.exec, stream));
     return 0;
 }
@@ -1078,8 +1110,57 @@ int pd_get_freeu(pd_engine* e, float out[4]) {
     return 0;
 }
 
+void pd_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
+    pd_philox4x32_10_block(ctr[0], ctr[1], ctr[2], ctr[3], key[0], key[1], out);
+}
+
+// The seed and the sample base are data the kernels read, not kernel arguments: the copy below is ordered on the engine's
+// stream after every launch already enqueued, and a captured step loop replays against whatever the buffer holds by then.
+int pd_set_rng(pd_engine* e, uint64_t seed, uint64_t sample_base) {
+    if (!e) { pd_set_error("null engine"); return 1; }
+    HIP_OK(hipSetDevice(e->device));
+    e->rng_seed = seed;
+    e->rng_base = sample_base;
+    e->rng_host[0] = (uint32_t)seed;
+    e->rng_host[1] = (uint32_t)(seed >> 32);
+    e->rng_host[2] = (uint32_t)sample_base;
+    e->rng_host[3] = (uint32_t)(sample_base >> 32);
+    HIP_OK(hipMemcpyAsync(e->rng_dev, e->rng_host, sizeof(e->rng_host), hipMemcpyHostToDevice, e->stream));
+    return 0;
+}
+
+int pd_get_rng(pd_engine* e, uint64_t* seed, uint64_t* sample_base) {
+    if (!e) { pd_set_error("null engine"); return 1; }
+    if (seed) *seed = e->rng_seed;
+    if (sample_base) *sample_base = e->rng_base;
+    return 0;
+}
+
+int pd_randn(pd_engine* e, int32_t stream, int32_t draw, int32_t B, int64_t per_sample, int32_t mem, float* out) {
+    if (!e || !out) { pd_set_error("null argument"); return 1; }
+    if (stream < 0 || draw < 0 || B < 1 || per_sample < 1) {
+        pd_set_error("pd_randn: stream and draw must be >= 0, B and per_sample >= 1 (got %d, %d, %d, %lld)", stream, draw, B, (long long)per_sample);
+        return 1;
+    }
+    HIP_OK(hipSetDevice(e->device));
+    const size_t n = (size_t)B * (size_t)per_sample;
+    float* dst = out;
+    if (mem != PD_MEM_DEVICE) HIP_OK(hipMalloc(reinterpret_cast<void**>(&dst), n * sizeof(float)));   // not on any hot path
+    int rc = launch_randn(e->rng_dev, (uint32_t)stream, (uint32_t)draw, B, per_sample, dst, e->stream);
+    if (rc) pd_set_error("pd_randn: launch failed");
+    if (!rc && mem != PD_MEM_DEVICE && hipMemcpyAsync(out, dst, n * sizeof(float), hipMemcpyDeviceToHost, e->stream) != hipSuccess) {
+        pd_set_error("pd_randn: read-back failed");
+        rc = 1;
+    }
+    if (hipStreamSynchronize(e->stream) != hipSuccess && !rc) { pd_set_error("pd_randn: hipStreamSynchronize failed"); rc = 1; }
+    if (mem != PD_MEM_DEVICE) (void)hipFree(dst);
+    return rc;
+}
+
 int64_t pd_get_stat(pd_engine* e, const char* key) {
     if (!e || !key) return -1;
+    if (!strcmp(key, "graph_captures")) return (int64_t)e->graph_captures;
+    if (!strcmp(key, "graph_replays")) return (int64_t)e->graph_replays;
     if (!strcmp(key, "workspace_bytes")) return (int64_t)e->arena.cap;
     if (!strcmp(key, "weight_bytes")) return (int64_t)e->weight_bytes;
     if (!strcmp(key, "launches")) return (int64_t)e->launches;

@@ -313,7 +313,8 @@ int pd_engine::vae_encoder_forward(const float* images_dev, int B, int H, int W,
     if (!arena.dry) {
         PD_TRY(check_arena());
         ++launches;
-        if (launch_vae_posterior(mom.p, DT_F32, mom.C, noise_dev, out_dev, B, z, mom.H * mom.W, what, (float)cfg.scale_factor, stream)) {
+        if (launch_vae_posterior(mom.p, DT_F32, mom.C, noise_dev, out_dev, B, z, mom.H * mom.W, what, (float)cfg.scale_factor, stream,
+                                 rng_dev)) {
             pd_set_error("posterior launch failed");
             return 1;
         }
@@ -343,11 +344,11 @@ extern "C" int pd_vae_encode(pd_engine* e, const float* images, int32_t B, int32
         pd_set_error("pd_vae_encode: unknown `what` %d (PD_VAE_MEAN / PD_VAE_SAMPLE / PD_VAE_MOMENTS)", what);
         return 1;
     }
-    if (what == PD_VAE_SAMPLE && !noise) { pd_set_error("pd_vae_encode: PD_VAE_SAMPLE needs `noise` [B, z, H/8, W/8]"); return 1; }
     HIP_OK(hipSetDevice(e->device));
     const int h = H / 8, w = W / 8, z = e->cfg.in_channels;
     const size_t n_in = (size_t)B * e->cfg.vae_out_ch * H * W, n_lat = (size_t)B * z * h * w;
-    const size_t n_noise = what == PD_VAE_SAMPLE ? n_lat : 0, n_out = what == PD_VAE_MOMENTS ? 2 * n_lat : n_lat;
+    // (noise NULL with PD_VAE_SAMPLE: the posterior kernel draws at (PD_RNG_VAE, draw 0) itself)
+    const size_t n_noise = (what == PD_VAE_SAMPLE && noise) ? n_lat : 0, n_out = what == PD_VAE_MOMENTS ? 2 * n_lat : n_lat;
     return e->vae_in_workspace((n_in + n_noise + n_out) * sizeof(float),
                                [&] { return e->vae_encoder_forward(nullptr, B, H, W, what, nullptr, nullptr); }, [&] {
         int r = 0;

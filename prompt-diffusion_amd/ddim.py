@@ -167,7 +167,10 @@ class DDIMSampler:
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
                quantize_x0=False, eta=0.0, mask=None, x0=None, temperature=1.0, noise_dropout=0.0, score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.0,
-               unconditional_conditioning=None, dynamic_threshold=None, ucg_schedule=None, noise=None, **kwargs):
+               unconditional_conditioning=None, dynamic_threshold=None, ucg_schedule=None, noise=None, seed=None, **kwargs):
+        """seed: seeds the engine's generator (Engine.set_rng, keeping its sample_base).  With eta > 0 and no `noise`, an
+        engine whose generator the caller has seeded -- here or through set_rng -- draws the per-step noise in its update
+        kernel instead of the host drawing and uploading it; noise_dropout keeps the host draw."""
         if conditioning is None or not isinstance(conditioning, dict):
             raise NotImplementedError("conditioning must be the ControlLDM dict (c_crossattn / example_pair / query)")
         for name, val in (("score_corrector", score_corrector), ("dynamic_threshold", dynamic_threshold)):
@@ -186,6 +189,10 @@ class DDIMSampler:
             x_T = np.random.standard_normal((batch_size, C, H, W)).astype(np.float32)
         eng = self.model.engine
         n_steps = eng.num_ddim_steps(S)
+        if seed is not None:
+            eng.set_rng(seed, eng.rng[1])
+        if eta > 0.0 and noise is None and eng._rng_set and not noise_dropout > 0.0:
+            noise = "engine"
         if eta > 0.0 and noise is None:
             noise = np.random.standard_normal((n_steps, batch_size, C, H, W)).astype(np.float32)
         if eta > 0.0 and noise_dropout > 0.0:
@@ -261,9 +268,9 @@ class DDIMSampler:
         return kw
 
     # ------------------------------------------------------------------ encode / decode (ddim_hacked.py:237-318)
-    def _session(self, x, cond, uc, scale, timesteps):
+    def _session(self, x, cond, uc, scale, timesteps, noise=None):
         """one engine session over a custom descending timestep list (context K/V, hint embedders and time embeddings hoisted once)"""
-        kw = dict(x_T=x, ctx_cond=_cat(cond["c_crossattn"]), pair=_cat(cond["example_pair"]), query=cond["query"][0],
+        kw = dict(noise=noise, x_T=x, ctx_cond=_cat(cond["c_crossattn"]), pair=_cat(cond["example_pair"]), query=cond["query"][0],
                   steps=len(timesteps), cfg_scale=float(scale), eta=self.ddim_eta, use_cfg=uc is not None, temperature=1.0,
                   control_scales=self.model.control_scales, only_mid_control=self.model.only_mid_control, timesteps=timesteps,
                   ctx_uncond=_cat(uc["c_crossattn"]) if uc is not None else None)
@@ -327,17 +334,20 @@ class DDIMSampler:
         return (sa * x0 + sb * _np32(noise)).astype(np.float32)
 
     def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
-               use_original_steps=False, callback=None):
+               use_original_steps=False, callback=None, seed=None):
         """ddim_hacked.py:301-318: p_sample_ddim over the first t_start timesteps of the current schedule, in the engine's own
-        step loop (custom timestep grid)."""
+        step loop (custom timestep grid).  With eta > 0 the fresh noise of every step is the engine's own seeded draw: pass
+        `seed`, or seed the engine's generator first (Engine.set_rng); otherwise eta > 0 raises as before."""
         if use_original_steps:
             raise NotImplementedError("use_original_steps needs the full 1000-step buffers of DDPM; not built")
-        if self.ddim_eta > 0.0:
+        eng = self.model.engine
+        if seed is not None:
+            eng.set_rng(seed, eng.rng[1])
+        if self.ddim_eta > 0.0 and not eng._rng_set:
             raise NotImplementedError("decode with eta > 0 draws fresh noise per step in the reference; pass eta = 0 to make_schedule")
         timesteps = np.asarray(self.ddim_timesteps)[:t_start]
-        eng = self.model.engine
         n = self._session(_np32(x_latent), cond, unconditional_conditioning, unconditional_guidance_scale,
-                          [int(t) for t in np.flip(timesteps)])
+                          [int(t) for t in np.flip(timesteps)], noise="engine" if self.ddim_eta > 0.0 else None)
         for i in range(n):
             eng.sample_step(i)
             if callback:

@@ -23,6 +23,13 @@ def shard_range(n: int, rank: int, world: int) -> Tuple[int, int]:
     return lo, lo + base + (1 if rank < rem else 0)
 
 
+def seed_shard(engine, seed: int, n: int, rank: int, world: int) -> None:
+    """Seed this rank's engine for its shard of an n-image batch: the shard's first global index becomes the generator's
+    sample_base, so image b of the sharded run draws exactly what image b of the unsharded run draws (Engine.set_rng)."""
+    lo, _ = shard_range(n, rank, world)
+    engine.set_rng(seed, sample_base=lo)
+
+
 def shard_batch(inputs: Dict[str, "np.ndarray"], rank: int, world: int) -> Dict[str, "np.ndarray"]:
     """Slice every batch-major input ([B, ...]) to this rank's contiguous shard."""
     n = next(iter(inputs.values())).shape[0]

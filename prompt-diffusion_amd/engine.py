@@ -64,7 +64,10 @@ class pd_sample_args(C.Structure):
     ]
 
 
-PD_INIT_PURE_NOISE = 1
+PD_INIT_PURE_NOISE, PD_NOISE_FROM_SEED, PD_XT_FROM_SEED = 1, 2, 4
+# streams of the engine's seeded generator (include/pdengine.h, "Seeded noise")
+PD_RNG_XT, PD_RNG_STEP, PD_RNG_VAE, PD_RNG_USER = 0, 1, 2, 16
+RNG_STREAMS = {"xt": PD_RNG_XT, "step": PD_RNG_STEP, "vae": PD_RNG_VAE}
 
 
 class pd_unipc_args(C.Structure):
@@ -86,9 +89,9 @@ class pd_lms_args(C.Structure):
 
 
 PD_LMS_NCOEF = 16
-PD_LMS_PLMS, PD_LMS_DPMPP, PD_LMS_ROWS = 0, 1, 2
+PD_LMS_PLMS, PD_LMS_DPMPP, PD_LMS_ROWS, PD_LMS_EULER_A = 0, 1, 2, 3
 PD_LMS_F_DATA_PRED, PD_LMS_F_BASE_KEEP, PD_LMS_F_STORE_KEEP, PD_LMS_F_PUSH, PD_LMS_F_STEP = 1, 2, 4, 8, 16
-_LMS_KINDS = {"plms": PD_LMS_PLMS, "dpmsolver++": PD_LMS_DPMPP, "rows": PD_LMS_ROWS}
+_LMS_KINDS = {"plms": PD_LMS_PLMS, "dpmsolver++": PD_LMS_DPMPP, "rows": PD_LMS_ROWS, "euler_a": PD_LMS_EULER_A}
 # DPM_Solver's names and the names diffusers gives the same two second-order updates
 _LMS_SOLVER_TYPES = {"dpm_solver": 0, "dpmsolver": 0, "midpoint": 0, "taylor": 1, "heun": 1}
 
@@ -196,6 +199,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.pd_set_freeu.argtypes = [C.c_void_p] + [C.c_float] * 4
     lib.pd_get_freeu.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     lib.pd_op_freeu_concat.argtypes = [C.c_void_p, fp, fp, fp, fp] + [C.c_int] * 7 + [C.c_float, C.c_float, fp]
+    lib.pd_philox4x32_10.argtypes = [C.POINTER(C.c_uint32)] * 3
+    lib.pd_philox4x32_10.restype = None
+    lib.pd_set_rng.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
+    lib.pd_get_rng.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.pd_randn.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_void_p]
     if path is None:
         _lib = lib
     return lib
@@ -214,7 +222,18 @@ EXPORTS = [
     "pd_op_conv2d", "pd_op_linear", "pd_op_linear_fp8", "pd_op_groupnorm", "pd_op_layernorm", "pd_op_attention", "pd_op_spatial_transformer", "pd_op_time_embed",
     "pd_op_timestep_embedding_i", "pd_op_timestep_embedding_f", "pd_op_vae_downsample", "pd_read_weights", "pd_lora_add", "pd_lora_set_scales", "pd_lora_remove",
     "pd_set_freeu", "pd_get_freeu", "pd_op_freeu_concat",
+    "pd_philox4x32_10", "pd_set_rng", "pd_get_rng", "pd_randn",
 ]
+
+
+def philox4x32_10(counter: Sequence[int], key: Sequence[int]) -> Tuple[int, int, int, int]:
+    """One Philox4x32-10 block on the host (pd_philox4x32_10): the generator behind Engine.randn and the in-kernel draws."""
+    lib = load_library()
+    c = (C.c_uint32 * 4)(*[int(v) & 0xFFFFFFFF for v in counter])
+    k = (C.c_uint32 * 2)(*[int(v) & 0xFFFFFFFF for v in key])
+    out = (C.c_uint32 * 4)()
+    lib.pd_philox4x32_10(c, k, out)
+    return tuple(int(v) for v in out)
 
 
 def make_config(cfg: ModelConfig, precision: int = PD_PREC_F16, stream_f32: bool = False) -> pd_config:
@@ -384,6 +403,7 @@ class Engine:
         c = make_config(cfg, self.precision, stream_f32)
         self._check(self.lib.pd_engine_create(C.byref(c), device, C.byref(self._h)))
         self._keep: List[_Buf] = []
+        self._rng_set = False    # the caller has chosen a seed (set_rng): draws nobody supplied may come from the engine
 
     # ------------------------------------------------------------------ plumbing
     def _check(self, rc: int):
@@ -502,6 +522,37 @@ class Engine:
         v = tuple(float(x) for x in out)
         return None if not any(v) else v
 
+    # ------------------------------------------------------------------ seeded noise (pd_set_rng / pd_randn)
+    def set_rng(self, seed: int, sample_base: int = 0) -> None:
+        """Seed of the engine's Philox generator and the global index of this engine's first sample: the draw of sample b is
+        that of sample `sample_base + b` of an unsharded run.  Takes effect for everything enqueued afterwards, captured
+        graphs included (they are kept)."""
+        self._check(self.lib.pd_set_rng(self._h, int(seed) & (2 ** 64 - 1), int(sample_base) & (2 ** 64 - 1)))
+        self._rng_set = True
+
+    @property
+    def rng(self) -> Tuple[int, int]:
+        """(seed, sample_base) as last set; (0, 0) on a new engine."""
+        s, b = C.c_uint64(), C.c_uint64()
+        self._check(self.lib.pd_get_rng(self._h, C.byref(s), C.byref(b)))
+        return int(s.value), int(b.value)
+
+    def randn(self, shape, stream="step", draw: int = 0, device=None):
+        """The standard normals the engine draws at (stream, draw) for shape[0] samples of prod(shape[1:]) elements each (NCHW
+        order within a sample): stream "xt" (the start latents), "step" (draw = step / row index), "vae" (the posterior
+        sample) or an int (PD_RNG_USER + k for draws of the caller's own).  NumPy, or a CUDA tensor with device=."""
+        st = RNG_STREAMS[stream] if isinstance(stream, str) else int(stream)
+        shape = tuple(int(v) for v in shape)
+        B, per = shape[0], int(np.prod(shape[1:], dtype=np.int64))
+        if device is not None:
+            import torch
+            out = torch.empty(shape, dtype=torch.float32, device=device)
+            self._check(self.lib.pd_randn(self._h, st, int(draw), B, per, PD_MEM_DEVICE, out.data_ptr()))
+        else:
+            out = np.empty(shape, np.float32)
+            self._check(self.lib.pd_randn(self._h, st, int(draw), B, per, PD_MEM_HOST, out.ctypes.data))
+        return out
+
     def init_random_weights(self, seed: int = 1234) -> None:
         self._check(self.lib.pd_init_random_weights(self._h, seed))
 
@@ -533,12 +584,20 @@ class Engine:
         """AutoencoderKL.encode (autoencoder.py:83-87) on the device: images [B,3,H,W] in [-1, 1] (H, W multiples of 8,
         (H/8)*(W/8) a multiple of 64) ->
           "mean":    scale_factor * posterior.mode()                        [B,4,H/8,W/8]
-          "sample":  scale_factor * (mean + std * noise), noise [B,4,H/8,W/8] standard normal from the caller
+          "sample":  scale_factor * (mean + std * noise), noise [B,4,H/8,W/8] standard normal from the caller, or drawn
+                     by the engine (randn(..., "vae")) with noise="engine" -- also with noise=None once set_rng has been called
           "moments": quant_conv output (mean ; logvar), unscaled, unclamped  [B,8,H/8,W/8]
         NumPy in, NumPy out; CUDA tensors in (images and noise), CUDA tensor out."""
         if mode not in VAE_ENCODE_MODES:
             raise ValueError(f"mode must be one of {sorted(VAE_ENCODE_MODES)}")
         what = VAE_ENCODE_MODES[mode]
+        if isinstance(noise, str):
+            if noise != "engine":
+                raise ValueError("noise must be an array or \"engine\"")
+            noise = None
+        elif noise is None and what == PD_VAE_SAMPLE and not self._rng_set:
+            raise PdError("pd_vae_encode: PD_VAE_SAMPLE needs `noise` [B, z, H/8, W/8] (or noise=\"engine\" / Engine.set_rng "
+                          "for the engine's own seeded draw)")
         b = _Buf(images)
         nb = _Buf(noise)
         if nb.mem is not None and nb.mem != b.mem:
@@ -646,14 +705,32 @@ class Engine:
     def _args(self, *, x_T, ctx_cond, ctx_uncond, pair, query, steps, cfg_scale, eta=0.0, use_cfg=True,
               guess_mode=False, only_mid_control=False, temperature=1.0, control_scales=None,
               control_scales_step=None, noise=None, pair_uncond=None, query_uncond=None, timesteps=None,
-              init_latents=None, mask=None, init_pure_noise=False):
-        """init_latents [B,4,h,w] (z0, already times scale_factor) turns x_T into the noise draw of img2img; mask [B,1,h,w] or
+              init_latents=None, mask=None, init_pure_noise=False, seed_x_T=False):
+        """noise="engine": the per-step draws (eta > 0 DDIM, multistep rows with a noise coefficient) come from the engine's
+        generator (set_rng; PD_NOISE_FROM_SEED).  x_T=None with seed_x_T=True: the engine draws the start latents too
+        (PD_XT_FROM_SEED); batch and latent size then come from init_latents, or from ctx_cond and pair.
+        init_latents [B,4,h,w] (z0, already times scale_factor) turns x_T into the noise draw of img2img; mask [B,1,h,w] or
         [1,1,h,w] (1 = repaint) adds the inpainting blend after every step; init_pure_noise starts from x_T itself
         (pd_sample_args.init_latents / mask / init_flags)."""
+        flags = PD_INIT_PURE_NOISE if init_pure_noise else 0
+        if isinstance(noise, str):
+            if noise != "engine":
+                raise ValueError("noise must be an array or \"engine\"")
+            noise, flags = None, flags | PD_NOISE_FROM_SEED
+        if seed_x_T:
+            if x_T is not None:
+                raise PdError("seed_x_T: x_T must be None (PD_XT_FROM_SEED: the engine draws it)")
+            flags |= PD_XT_FROM_SEED
+            xs = tuple(init_latents.shape) if init_latents is not None else \
+                (ctx_cond.shape[0], self.cfg.in_channels, pair.shape[2] // 8, pair.shape[3] // 8)
+        elif x_T is None:
+            raise PdError("x_T is required (or seed_x_T=True for the engine's own draw)")
+        else:
+            xs = tuple(x_T.shape)
         if mask is not None:
-            B0 = x_T.shape[0]
-            if tuple(mask.shape[1:]) != (1,) + tuple(x_T.shape[2:]) or mask.shape[0] not in (1, B0):
-                raise PdError(f"mask must be [B, 1, h, w] or [1, 1, h, w] with B, h, w of x_T {tuple(x_T.shape)}, got {tuple(mask.shape)}")
+            B0 = xs[0]
+            if tuple(mask.shape[1:]) != (1,) + xs[2:] or mask.shape[0] not in (1, B0):
+                raise PdError(f"mask must be [B, 1, h, w] or [1, 1, h, w] with B, h, w of x_T {xs}, got {tuple(mask.shape)}")
             if mask.shape[0] != B0:      # broadcast over the batch on the host side of the boundary
                 mask = mask.expand(B0, -1, -1, -1) if _is_torch(mask) else np.broadcast_to(mask, (B0,) + tuple(mask.shape[1:]))
         bufs = dict(x_T=_Buf(x_T), ctx_cond=_Buf(ctx_cond), ctx_uncond=_Buf(ctx_uncond), pair=_Buf(pair),
@@ -662,18 +739,18 @@ class Engine:
         mems = {b.mem for b in bufs.values() if b.mem is not None}
         if len(mems) != 1:
             raise PdError("all inputs must live in the same memory space (all NumPy or all CUDA tensors)")
-        if init_latents is not None and tuple(init_latents.shape) != tuple(x_T.shape):
-            raise PdError(f"init_latents must have the shape of x_T {tuple(x_T.shape)}, got {tuple(init_latents.shape)}")
+        if init_latents is not None and tuple(init_latents.shape) != xs:
+            raise PdError(f"init_latents must have the shape of x_T {xs}, got {tuple(init_latents.shape)}")
         a = pd_sample_args()
-        a.init_flags = PD_INIT_PURE_NOISE if init_pure_noise else 0
-        B, _, h, w = bufs["x_T"].owner.shape
+        a.init_flags = flags
+        B, _, h, w = xs
         a.batch, a.h, a.w, a.steps = B, h, w, steps
         a.eta, a.cfg_scale, a.use_cfg = eta, cfg_scale, 1 if use_cfg else 0
         a.guess_mode, a.only_mid_control, a.temperature = int(guess_mode), int(only_mid_control), temperature
         a.mem = mems.pop()
         for k, b in bufs.items():
             setattr(a, k, b.ptr)
-        keep = list(bufs.values())
+        keep = [bufs["ctx_cond"]] + list(bufs.values())    # keep[0]: an input that always exists (memory space / device of the outputs)
         n_steps = self.num_ddim_steps(steps)
         if timesteps is not None:       # custom grid, sampling order (descending); a.steps = its length
             ts = np.ascontiguousarray(_to_host(timesteps), dtype=np.int64).reshape(-1)
@@ -733,6 +810,8 @@ class Engine:
         """pd_sample_args + pd_lms_args of a linear multistep call; the step count comes from the grid."""
         kw = dict(kw)
         kw["steps"] = n = _lms_steps(kw.get("timesteps"), model_times, kw.get("steps"))
+        if kind == "euler_a" and kw.get("noise") is None:
+            kw["noise"] = "engine"     # an ancestral sampler always draws; the only source is the engine's generator
         css = kw.pop("control_scales_step", None)      # one row per sampling step of this grid, not of a DDIM schedule
         a, keep, shape = self._args(**kw)
         a.steps = n
@@ -748,7 +827,8 @@ class Engine:
     def lms_sample(self, *, return_intermediates: bool = False, kind: str = "dpmsolver++", order: int = 2,
                    solver_type: str = "dpm_solver", lower_order_final: bool = True, model_times=None, rows=None, row_times=None,
                    **kw):
-        """The fused linear multistep loop (PLMS, DPM-Solver++ multistep, or the caller's own rows; see lms_coefficients):
+        """The fused linear multistep loop (PLMS, DPM-Solver++ multistep, Euler ancestral -- kind "euler_a", whose noise the
+        engine draws (set_rng) --, or the caller's own rows, with noise="engine" when they carry a noise coefficient; see lms_coefficients):
         `timesteps` or `model_times` is the grid; otherwise the arguments and returns of ddim_sample.  x_inter has one entry
         per completed step, however many evaluations ran."""
         a, keep, (B, h, w), u = self._lms_call(kw, kind, order, solver_type, lower_order_final, model_times, rows, row_times)

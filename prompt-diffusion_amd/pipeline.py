@@ -60,6 +60,28 @@ def blend_latents(known, x, mask):
     return (np.float32(1.0) - mask) * known + mask * x
 
 
+class EngineGenerator:
+    """generator=EngineGenerator(seed, sample_base=0): every random number of a pipeline call comes from the engine's seeded
+    Philox generator (Engine.set_rng) -- the start latents, the eta > 0 DDIM draws (drawn inside the update kernel, no noise
+    tensor is made or uploaded), the img2img noise, the VAE posterior sample, and the draws of an Euler ancestral scheduler,
+    fused or on the host.  A sample's numbers depend on (seed, sample_base + its index in the batch) alone, so a sharded run
+    that passes each shard's first global index as sample_base reproduces the unsharded images."""
+
+    def __init__(self, seed: int, sample_base: int = 0):
+        self.seed, self.sample_base = int(seed), int(sample_base)
+        self.engine = None
+
+    def bind(self, engine: E.Engine) -> "EngineGenerator":
+        self.engine = engine
+        engine.set_rng(self.seed, self.sample_base)
+        return self
+
+    def randn(self, shape, stream="step", draw: int = 0):
+        if self.engine is None:
+            raise ValueError("EngineGenerator is not bound to an engine yet (the pipeline binds it at the start of a call)")
+        return self.engine.randn(shape, stream=stream, draw=draw)
+
+
 class PromptDiffusionPipeline:
     _callback_tensor_inputs = ["latents", "prompt_embeds", "negative_prompt_embeds"]
     vae_scale_factor = 8
@@ -92,9 +114,10 @@ class PromptDiffusionPipeline:
 
     def _check_fusable(self):
         """The fused loops restate this package's schedulers on the engine's own noise schedule; anything else is refused."""
-        from .schedulers import DPMSolverMultistepScheduler, PNDMScheduler, UniPCMultistepScheduler
+        from .schedulers import (DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, PNDMScheduler,
+                                 UniPCMultistepScheduler)
         sched = self.scheduler
-        if type(sched) not in (UniPCMultistepScheduler, DPMSolverMultistepScheduler, PNDMScheduler):
+        if type(sched) not in (UniPCMultistepScheduler, DPMSolverMultistepScheduler, PNDMScheduler, EulerAncestralDiscreteScheduler):
             raise ValueError("fuse_scheduler=True needs prompt_diffusion_amd.schedulers.UniPCMultistepScheduler, "
                              f"DPMSolverMultistepScheduler or PNDMScheduler, got {type(sched)}")
         cfg = self.engine.cfg
@@ -309,7 +332,8 @@ class PromptDiffusionPipeline:
             x = np.ascontiguousarray(x * np.float32(2.0) - np.float32(1.0))
             Bi = x.shape[0]
             gen = generator[:Bi] if isinstance(generator, list) else generator
-            noise = self._randn((Bi, zc) + lat_hw, gen)
+            # (an EngineGenerator: the posterior kernel draws at stream "vae" itself)
+            noise = "engine" if isinstance(gen, EngineGenerator) else self._randn((Bi, zc) + lat_hw, gen)
             z = _to_numpy(self.engine.vae_encode(x, mode="sample", noise=noise)).astype(np.float32)
         return np.ascontiguousarray(self._tile(z, batch_size, "`image`"))
 
@@ -317,6 +341,8 @@ class PromptDiffusionPipeline:
     def _randn(shape, generator):
         if generator is None:
             return np.random.standard_normal(shape).astype(np.float32)
+        if isinstance(generator, EngineGenerator):     # the start latents / the img2img noise: stream "xt"
+            return np.asarray(generator.randn(shape, stream="xt"), np.float32)
         if isinstance(generator, np.random.Generator):
             return generator.standard_normal(shape, dtype=np.float32)
         import torch
@@ -575,6 +601,8 @@ class PromptDiffusionPipeline:
         query = self.prepare_image(image, width, height, batch_size * num_images_per_prompt, num_images_per_prompt)
         height, width = query.shape[-2:]
         B = batch_size * num_images_per_prompt
+        if isinstance(generator, EngineGenerator):
+            generator.bind(self.engine)
         # 6. latents (img2img / inpainting: the init image's latents first -- its posterior draw comes before the noise draw)
         if init is not None:
             m = self.prepare_mask(init["mask"], width, height, B) if init["mask"] is not None else None
@@ -630,7 +658,9 @@ class PromptDiffusionPipeline:
         scales_step = np.stack([base * np.float32(controlnet_conditioning_scale) * np.float32(k) for k in keep])
         noise = None
         if eta > 0.0:
-            if self.scheduler is None:   # a plug-in scheduler draws its own noise (`generator` is forwarded to step())
+            if self.scheduler is None and isinstance(generator, EngineGenerator):
+                noise = "engine"         # drawn in the update kernel at (stream "step", draw = step): nothing to make or upload
+            elif self.scheduler is None:   # a plug-in scheduler draws its own noise (`generator` is forwarded to step())
                 noise = self._randn((n_steps,) + x_T.shape, generator if not isinstance(generator, list) else None)
         kw = dict(x_T=x_T, ctx_cond=pe, ctx_uncond=ne, pair=pair, query=query, steps=num_inference_steps,
                   cfg_scale=float(guidance_scale), eta=float(eta), use_cfg=do_cfg, guess_mode=guess_mode,
@@ -652,6 +682,10 @@ class PromptDiffusionPipeline:
             self._check_fusable()
             sched = self.scheduler
             kw.update(eta=0.0, noise=None)
+            if getattr(sched, "fused_lms", None) is not None and sched.fused_lms(t_start).get("kind") == "euler_a" \
+                    and not isinstance(generator, EngineGenerator):
+                raise ValueError("fuse_scheduler=True with EulerAncestralDiscreteScheduler draws its noise inside the engine: pass "
+                                 "generator=EngineGenerator(seed)")
             if hasattr(sched, "fused_lms"):
                 # a linear multistep scheduler: its step grid and options as pd_lms_args; one engine row per evaluation
                 fused = dict(solver="lms", args=sched.fused_lms(t_start), rows=plan["rows"])

@@ -504,3 +504,108 @@ class PNDMScheduler:
         """Arguments of Engine.lms_sample that run this scheduler's remaining steps inside the engine."""
         rest = [int(t) for t in self.timesteps[t_start:]]
         return dict(kind="plms", timesteps=[t for j, t in enumerate(rest) if j == 0 or t != rest[j - 1]])
+
+
+class EulerAncestralDiscreteScheduler:
+    """Euler ancestral ("Euler a"): k-diffusion's sample_euler_ancestral with eta = 1, written in the VP variables the engine
+    samples in, so `init_noise_sigma` is 1 and `scale_model_input` the identity.  With alpha = sqrt(abar), sigma = sqrt(1 - abar)
+    and s = sigma / alpha, a step from t_i to t_{i+1} (s = 0 after the last) is
+        s_up = sqrt(s_to^2 (s_from^2 - s_to^2) / s_from^2),  s_down = sqrt(s_to^2 - s_up^2)
+        x' = (alpha_to / alpha_from) x + alpha_to (s_down - s_from) eps + alpha_to s_up z,   z ~ N(0, 1)
+    -- the rows of PD_LMS_EULER_A (include/pdengine.h).  No counterpart ships in the reference tree: the formula is
+    k-diffusion's published one, UNPINNED like the other grids here.  `step(..., generator=)` draws z through whatever it is
+    given: a NumPy Generator, a torch.Generator, or an object with randn(shape, stream=, draw=) such as the pipeline's
+    EngineGenerator, which is asked for (stream "step", draw = the step's index from the first step run) -- the addresses the
+    fused loop draws at.
+    """
+    order = 1
+    init_noise_sigma = 1.0
+
+    def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
+                 beta_schedule: str = "scaled_linear", prediction_type: str = "epsilon", timestep_spacing: str = "leading",
+                 steps_offset: int = 1):
+        if prediction_type != "epsilon":
+            raise NotImplementedError("the Prompt-Diffusion UNet predicts epsilon (ddpm.py:71)")
+        if timestep_spacing not in ("leading", "trailing"):
+            raise ValueError(f"timestep_spacing {timestep_spacing!r}: 'leading' or 'trailing'")
+        self.num_train_timesteps = num_train_timesteps
+        self.alphas_cumprod = np.cumprod(1.0 - _betas(beta_schedule, beta_start, beta_end, num_train_timesteps))
+        self.timestep_spacing = timestep_spacing
+        self.steps_offset = steps_offset
+        self.timesteps = np.zeros((0,), np.int64)
+        self._step_index = self._begin = 0
+
+    def set_timesteps(self, num_inference_steps: Optional[int] = None, device=None, timesteps=None):
+        T = self.num_train_timesteps
+        if timesteps is not None:
+            ts = np.asarray([int(t) for t in timesteps], np.int64)
+        else:
+            n = int(num_inference_steps)
+            if n < 1 or n > T:
+                raise ValueError("num_inference_steps out of range")
+            if self.timestep_spacing == "leading":      # diffusers: arange(n) * (T // n) + steps_offset, descending
+                ts = ((np.arange(0, n) * (T // n)).round()[::-1] + self.steps_offset).astype(np.int64)
+            else:
+                ts = _spaced_timesteps("trailing", T, n, 0)
+        if len(ts) < 1 or np.any(np.diff(ts) >= 0) or ts.min() < 0 or ts.max() >= T:
+            raise ValueError("timesteps must be strictly descending inside [0, num_train_timesteps)")
+        self.timesteps = ts
+        self.num_inference_steps = len(ts)
+        self._step_index = self._begin = 0
+
+    def set_begin_index(self, begin_index: int = 0):
+        k = int(begin_index)
+        if not 0 <= k < len(self.timesteps):
+            raise ValueError(f"begin_index {k} outside the {len(self.timesteps)} timesteps")
+        self._step_index = self._begin = k
+
+    def scale_model_input(self, sample, timestep=None):
+        return sample
+
+    def coefficients(self, i: int):
+        """(c_x, c_eps, c_z, alpha_from, sigma_from) of step i in fp64: x' = c_x x + c_eps eps + c_z z."""
+        ac, ts = self.alphas_cumprod, self.timesteps
+        a_from, sg_from = math.sqrt(ac[ts[i]]), math.sqrt(1.0 - ac[ts[i]])
+        s_from = sg_from / a_from
+        last = i + 1 == len(ts)
+        a_to = 1.0 if last else math.sqrt(ac[ts[i + 1]])
+        s_to = 0.0 if last else math.sqrt(1.0 - ac[ts[i + 1]]) / a_to
+        s_up = math.sqrt(s_to * s_to * (s_from * s_from - s_to * s_to) / (s_from * s_from))
+        s_down = math.sqrt(s_to * s_to - s_up * s_up)
+        return a_to / a_from, a_to * (s_down - s_from), 0.0 if last else a_to * s_up, a_from, sg_from
+
+    @staticmethod
+    def _draw(shape, generator, draw):
+        if generator is None:
+            return np.random.standard_normal(shape)
+        if isinstance(generator, np.random.Generator):
+            return generator.standard_normal(shape)
+        if hasattr(generator, "randn"):
+            return np.asarray(generator.randn(shape, stream="step", draw=draw))
+        import torch
+        return torch.randn(tuple(shape), generator=generator, device=generator.device).cpu().numpy()
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict: bool = True, **_):
+        if len(self.timesteps) == 0:
+            raise ValueError("call set_timesteps first")
+        eps, like = _to_np(model_output)
+        x, like_x = _to_np(sample)
+        like = like_x if like_x is not None else like
+        out_dtype = x.dtype
+        eps, x = eps.astype(np.float64), x.astype(np.float64)
+        i = self._step_index
+        if float(timestep) != float(self.timesteps[i]):
+            raise ValueError(f"step {i} expects timestep {self.timesteps[i]}, got {timestep}")
+        c_x, c_eps, c_z, a_from, sg_from = self.coefficients(i)
+        prev = c_x * x + c_eps * eps
+        if c_z != 0.0:
+            z = np.asarray(self._draw(x.shape, generator, i - self._begin), np.float64)
+            prev = prev + c_z * z
+        self.pred_original_sample = (x - sg_from * eps) / a_from
+        self._step_index += 1
+        return _wrap_out(prev, out_dtype, like, return_dict)
+
+    def fused_lms(self, t_start: int = 0):
+        """Arguments of Engine.lms_sample that run this scheduler's remaining steps inside the engine (PD_LMS_EULER_A); the
+        noise is the engine's own seeded draw."""
+        return dict(kind="euler_a", timesteps=[int(t) for t in self.timesteps[t_start:]])
