@@ -130,8 +130,10 @@ typedef struct pd_sample_args {
     const float* mask;         /* optional [B, 1, h, w] in `mem`, needs init_latents; weight of the SAMPLED latents (1 = repaint, 0 = keep) */
     int32_t init_flags;        /* PD_INIT_PURE_NOISE: start from x_T itself (diffusers' strength == 1 inpainting);
                                   PD_NOISE_FROM_SEED / PD_XT_FROM_SEED: see "Seeded noise" below */
-    int32_t reserved[1];
+    int32_t context_len;       /* L of ctx_cond / ctx_uncond, 1 .. PD_MAX_CONTEXT_LEN; 0: pd_config.context_len.  (The text transformer
+                                  keeps pd_config.context_len positions: longer contexts are several of its windows side by side.) */
 } pd_sample_args;
+#define PD_MAX_CONTEXT_LEN 1024   /* sanity bound of pd_sample_args.context_len */
 #define PD_INIT_PURE_NOISE 1
 #define PD_NOISE_FROM_SEED 2 /* the per-step draws (eta > 0 DDIM, multistep rows with [14] != 0) come from the engine's generator;
                                 `noise` must be NULL */
@@ -241,6 +243,10 @@ int pd_vae_encoder_weights_missing(pd_engine* e);
 int pd_eps(pd_engine* e, const float* x, const int64_t* t, const float* ctx, const float* pair,
            const float* query, const float* scales, int32_t Bf, int32_t h, int32_t w, int32_t mem,
            float* eps_out, float* residuals_out);
+/* ... with ctx [Bf, context_len, context_dim]: context_len as in pd_sample_args (0: pd_config.context_len) */
+int pd_eps_ctx(pd_engine* e, const float* x, const int64_t* t, const float* ctx, int32_t context_len, const float* pair,
+               const float* query, const float* scales, int32_t Bf, int32_t h, int32_t w, int32_t mem,
+               float* eps_out, float* residuals_out);
 int pd_control_shape(pd_engine* e, int index, int32_t h, int32_t w, int32_t* C, int32_t* H, int32_t* W);
 
 /* the fused loop: begin + S steps + read-back; blocking (stream-synchronised on return).

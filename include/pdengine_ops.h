@@ -33,6 +33,10 @@ int pd_op_attention(pd_engine* e, const float* q, const float* k, const float* v
  * x [B, C, H, W], context [B, context_len, context_dim], y [B, C, H, W]; the same code path as a sampling step (2-byte modes at
  * 320 channels: self-attention + the fused tail kernel). */
 int pd_op_spatial_transformer(pd_engine* e, const char* prefix, const float* x, const float* context, int B, int H, int W, float* y);
+/* ... with a context of any length: context [B, L, context_dim], 1 <= L <= PD_MAX_CONTEXT_LEN.  At 320 channels the fused tail takes
+ * L <= 288 (one to three 96-key windows, st_tail.hip); longer contexts take the per-layer path.  pd_op_spatial_transformer is this call
+ * with L = pd_config.context_len. */
+int pd_op_spatial_transformer_ctx(pd_engine* e, const char* prefix, const float* x, const float* context, int B, int H, int W, int L, float* y);
 /* timestep_embedding(t, model_channels) (util.py:154-174: [cos | sin], max_period 10000, frequencies i / half) -> temb [n][model_channels],
  * and time_embed(temb) = Linear -> SiLU -> Linear of the loaded network (net 0: UNet, 1: ControlNet; openaimodel.py:526-531) -> emb
  * [n][4 * model_channels]; exactly what the sampler computes once per call for all its steps (pd_engine::compute_emb). */

@@ -589,8 +589,8 @@ int pd_engine::init_random(uint64_t seed) {
 // LayerNorm folded into its consumer (attention.py:271-275: x + attn1(norm1(x)), + attn2(norm2(x)), + ff(norm3(x))):
 // LN(x) . W^T = rstd * (x . (W diag(gamma))^T - mean * colsum) + beta . W^T, so the consumer GEMM reads the residual stream
 // itself and the normalised tensor is never written.  Built once per weight change.
-bool pd_engine::st_tail_on(const STW& s, int rows_per_sample) const {
-    return opt_st_fuse && S == T && st_tail_eligible(P, s.C, cfg.num_heads, rows_per_sample, cfg.context_len);
+bool pd_engine::st_tail_on(const STW& s, int rows_per_sample, int L) const {
+    return opt_st_fuse && S == T && st_tail_eligible(P, s.C, cfg.num_heads, rows_per_sample, L);
 }
 
 int pd_engine::fold_layernorms() {
@@ -613,8 +613,9 @@ int pd_engine::fold_layernorms() {
     for (int which = 0; which < 2; ++which) {
         NetW& net = which ? cnet : unet;
         for (STW* st : net.st_list) {
-            // the shape gate of the fused tail that does not depend on the call (320 channels, 8 heads of 40, <= 96 context keys)
-            const bool fused = tail && st_tail_eligible(P, st->C, cfg.num_heads, 128, cfg.context_len);
+            // the shape gate of the fused tail that does not depend on the call (320 channels, 8 heads of 40); the context length is
+            // the session's (st_tail_on)
+            const bool fused = tail && st_tail_eligible(P, st->C, cfg.num_heads, 128, 1);
             if (on || fused) PD_TRY(fold(st->qkv, st->ln_g[0], st->ln_b[0]));   // norm1 -> to_q/k/v
             if (on || fused) PD_TRY(fold(st->q2, st->ln_g[1], st->ln_b[1])); // norm2 -> attn2.to_q
             if (!fused) continue;   // (norm3 stays a kernel in front of the GEGLU tile of gemm.hip)
@@ -1061,7 +1062,8 @@ int pd_engine::transformer(const STW& s, const Act& x, Act& out, const KVSlot& k
     const int reps = out_B / B;
     out = new_act(out_B, H, W, C, S);
     const size_t mk = arena.mark();
-    const bool fused = st_tail_on(s, N) && s.tail_w && s.front_w && kv.P;
+    const int L = kv.L > 0 ? kv.L : cfg.context_len, lpad = round_up(L, 8);   // context keys of this call
+    const bool fused = st_tail_on(s, N, L) && s.tail_w && s.front_w && kv.P;
     const int npad = round_up(N, 8);
     Act h, qk, vt, ln;
     LnStats st0, st1;
@@ -1122,10 +1124,10 @@ int pd_engine::transformer(const STW& s, const Act& x, Act& out, const KVSlot& k
             ++launches;
             ProfRec rec{};
             if (profiling) {
-                prof_begin(rec, 4, st_tail_flops((long long)out_B * N, cfg.context_len));
+                prof_begin(rec, 4, st_tail_flops((long long)out_B * N, L));
                 rec.M = out_B * N; rec.N = C; rec.K = C; rec.taps = 0;
             }
-            const int r = launch_st_tail(att.p, h.p, x.p, out.p, s.tail_w, s.tail_vec, kv.P, (long long)out_B * N, N, cfg.context_len, S,
+            const int r = launch_st_tail(att.p, h.p, x.p, out.p, s.tail_w, s.tail_vec, kv.P, (long long)out_B * N, N, L, S,
                                          (float)(1.0 / std::sqrt((double)(C / cfg.num_heads))), P, stream, (long long)B * N);
             if (profiling) prof_end(rec);
             if (r) { pd_set_error("fused transformer-tail launch failed: %s", hipGetErrorString(hipGetLastError())); return 1; }
@@ -1139,7 +1141,6 @@ int pd_engine::transformer(const STW& s, const Act& x, Act& out, const KVSlot& k
     if (!fuse) PD_TRY(layernorm(h1, ln, s.ln_g[1], s.ln_b[1]));
     Act q2 = new_act(B, H, W, C, T);
     PD_TRY(gemm(s.q2, fuse ? h1 : ln, q2, {.ln_in = fuse ? &st1 : nullptr}));
-    const int L = cfg.context_len, lpad = round_up(L, 8);
     Act xr = x;   // the block's residual at the output batch
     if (reps > 1) {
         // the shared queries meet each half's own context keys: one launch per half; from here on the batch is out_B
@@ -1206,10 +1207,10 @@ int pd_engine::run_controlnet(const Act& x_in_full, int emb_row, int emb_stride,
         KVSlot k = ses.kv_c[st.kv_slot];
         if (s0) {
             const size_t eb = dt_size(T);
-            const int L = cfg.context_len, lpad = round_up(L, 8);
+            const int L = k.L > 0 ? k.L : cfg.context_len, lpad = round_up(L, 8);
             k.K = reinterpret_cast<char*>(k.K) + (size_t)s0 * L * st.C * eb;
             k.VT = reinterpret_cast<char*>(k.VT) + (size_t)s0 * st.C * lpad * eb;
-            if (k.P) k.P = reinterpret_cast<char*>(k.P) + st_tail_kv_bytes(s0);
+            if (k.P) k.P = reinterpret_cast<char*>(k.P) + st_tail_kv_bytes(s0, L);
         }
         return k;
     };

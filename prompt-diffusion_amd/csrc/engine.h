@@ -286,7 +286,8 @@ struct GemmPlan {
     bool patch() const { return family == GEMM_PATCH1 || family == GEMM_PATCH2 || family == GEMM_PATCH4; }
 };
 
-struct KVSlot { void* K = nullptr; void* VT = nullptr; void* P = nullptr; };   // P: K / V^T in st_tail.hip's fragment order (fused blocks)
+// K [B][L][C], V^T [B][C][round_up(L, 8)]; P: the same in st_tail.hip's fragment order (fused blocks); L: context keys per sample (0: cfg.context_len)
+struct KVSlot { void* K = nullptr; void* VT = nullptr; void* P = nullptr; int L = 0; };
 
 enum { SOLVER_DDIM = 0, SOLVER_UNIPC = 1, SOLVER_LMS = 2 };
 
@@ -295,6 +296,7 @@ struct Session {
     pd_sample_args a{};
     int Bf = 0;
     int S = 0;
+    int L = 0;                       // context tokens per sample of this session (pd_sample_args.context_len, or cfg.context_len)
     std::vector<int64_t> timesteps;  // ascending (ddim_timesteps)
     std::vector<int64_t> custom_ts;  // copy of pd_sample_args.timesteps (descending), empty = uniform grid
     std::vector<float> alphas, alphas_prev, sigmas, sqrt_1m;
@@ -534,7 +536,7 @@ struct pd_engine {
     bool ln_dirty = true;
     int opt_ln_fuse = -1;      // -1: on in the 2-byte modes, off in the fp32-storage modes; 0 / 1: forced
     bool opt_st_fuse = true;   // 320-channel SpatialTransformer blocks: one kernel for everything after self-attention (2-byte modes)
-    bool st_tail_on(const STW& s, int rows_per_sample) const;
+    bool st_tail_on(const STW& s, int rows_per_sample, int L) const;   // L: context keys of the call
     int gn_stats(const Act& x, int& nchunk);
     // conv3x3 / conv1x1 of `c`: call.stride and call.pad_shift come from the ConvW.  conv_gn: conv(act(GroupNorm(x))); call carries the
     // residual / row vector / defer pointer of the conv

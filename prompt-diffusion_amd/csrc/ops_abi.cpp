@@ -262,7 +262,14 @@ int pd_op_attention(pd_engine* e, const float* q, const float* k, const float* v
 // x [B, C, H, W] and context [B, context_len, context_dim], through exactly the code path a sampling step takes -- including the fused
 // tail kernel (st_tail.hip) where it is eligible.
 int pd_op_spatial_transformer(pd_engine* e, const char* prefix, const float* x, const float* ctx, int B, int H, int W, float* y) {
+    if (!e) { pd_set_error("null argument"); return 1; }
+    return pd_op_spatial_transformer_ctx(e, prefix, x, ctx, B, H, W, e->cfg.context_len, y);
+}
+
+// ... on a context of any length: [B, L, context_dim], 1 <= L <= PD_MAX_CONTEXT_LEN
+int pd_op_spatial_transformer_ctx(pd_engine* e, const char* prefix, const float* x, const float* ctx, int B, int H, int W, int L, float* y) {
     if (!e || !prefix || !x || !ctx || !y) { pd_set_error("null argument"); return 1; }
+    if (L < 1 || L > PD_MAX_CONTEXT_LEN) { pd_set_error("context length %d out of range 1 .. %d", L, PD_MAX_CONTEXT_LEN); return 1; }
     HIP_OK(hipSetDevice(e->device));
     const std::string pre(prefix);
     auto it = e->index.find(pre + "norm.weight");
@@ -277,12 +284,12 @@ int pd_op_spatial_transformer(pd_engine* e, const char* prefix, const float* x, 
         if (!p.loaded && p.name.compare(0, pre.size(), pre) == 0) { pd_set_error("weights not loaded: '%s'", p.name.c_str()); return 1; }
     e->ln_dirty = true;
     PD_TRY(e->fold_layernorms());
-    const int C = st->C, L = e->cfg.context_len, D = e->cfg.context_dim, Dp = round_up(D, 8), lpad = round_up(L, 8), N = H * W;
+    const int C = st->C, D = e->cfg.context_dim, Dp = round_up(D, 8), lpad = round_up(L, 8), N = H * W;
     const size_t eb = dt_size(e->T);
     // a private workspace for this call (op hooks run outside a session)
     const size_t ws = (size_t)64 << 20, act = (size_t)B * N * C * 4;
     DevBuf work(ws + 48 * act), cin((size_t)B * L * D * 4), cdev((size_t)B * L * Dp * eb), kbuf((size_t)B * L * C * eb), vtbuf((size_t)B * C * lpad * eb),
-        kvp(st_tail_kv_bytes(B)), xin((size_t)B * N * C * dt_size(e->S));
+        kvp(e->st_tail_on(*st, H * W, L) ? st_tail_kv_bytes(B, L) : 256), xin((size_t)B * N * C * dt_size(e->S));
     if (!work.p || !cin.p || !cdev.p || !kbuf.p || !vtbuf.p || !kvp.p || !xin.p) { pd_set_error("allocation failed"); return 1; }
     const Arena saved = e->arena;
     e->arena = Arena{};
@@ -298,8 +305,8 @@ int pd_op_spatial_transformer(pd_engine* e, const char* prefix, const float* x, 
         k.p = kbuf.p; k.B = B; k.H = L; k.W = 1; k.C = C; k.dt = e->T;
         if ((rc = e->gemm(st->kv2, c, k, {.VT = vtbuf.p, .vt_begin = C, .vt_ld = lpad}))) break;
         KVSlot kv;
-        kv.K = kbuf.p; kv.VT = vtbuf.p;
-        if (e->st_tail_on(*st, N) && st->tail_w) {
+        kv.K = kbuf.p; kv.VT = vtbuf.p; kv.L = L;
+        if (e->st_tail_on(*st, N, L) && st->tail_w) {
             if ((rc = launch_st_tail_kv_pack(kbuf.p, vtbuf.p, kvp.p, B, L, lpad, e->stream))) break;
             kv.P = kvp.p;
         }

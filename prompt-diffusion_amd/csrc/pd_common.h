@@ -250,7 +250,8 @@ int launch_attention(const AttnParams& p, int prec, hipStream_t s);
 bool st_tail_eligible(int prec, int C, int heads, int rows_per_sample, int Nk);
 size_t st_tail_weight_bytes();
 size_t st_tail_vec_floats();
-size_t st_tail_kv_bytes(int B);
+size_t st_tail_kv_bytes(int B, int Nk);   // B samples' context K / V in fragment order, ceil(Nk / 96) windows each
+int st_tail_windows(int Nk);
 double st_tail_flops(long long M, int Nk);
 // ... and its front: GroupNorm apply + proj_in + norm1 + to_q / to_k / to_v (h, q | k and V^T out)
 size_t st_front_weight_bytes();

@@ -130,7 +130,7 @@ int pd_engine::compute_emb(NetW& net, std::vector<float*>& tabs, const int64_t* 
 int pd_engine::session_setup(const pd_sample_args& a, const int64_t* t_rows, int n_rows, bool want_per_step, const double* t_rows_f) {
     Session& s = ses;
     const int B = a.batch, Bf = s.Bf, HW = a.h * a.w, C = cfg.in_channels;
-    const int L = cfg.context_len, D = cfg.context_dim, Dp = round_up(D, 8), lpad = round_up(L, 8);
+    const int L = s.L, D = cfg.context_dim, Dp = round_up(D, 8), lpad = round_up(L, 8);   // the session's context length
     const int IH = a.h * 8, IW = a.w * 8;
     const bool dev = a.mem == PD_MEM_DEVICE;
     const bool xt_seeded = (a.init_flags & PD_XT_FROM_SEED) != 0;
@@ -152,7 +152,8 @@ int pd_engine::session_setup(const pd_sample_args& a, const int64_t* t_rows, int
         for (STW* st : net.st_list) {
             kv[st->kv_slot].K = arena.alloc((size_t)Bf * L * st->C * dt_size(T));
             kv[st->kv_slot].VT = arena.alloc((size_t)Bf * st->C * lpad * dt_size(T));
-            kv[st->kv_slot].P = (st_tail_on(*st, 128) && st->tail_w) ? arena.alloc(st_tail_kv_bytes(Bf)) : nullptr;
+            kv[st->kv_slot].P = (st_tail_on(*st, 128, L) && st->tail_w) ? arena.alloc(st_tail_kv_bytes(Bf, L)) : nullptr;
+            kv[st->kv_slot].L = L;
         }
     }
     s.emb_rows = n_rows + 1;  // last row: scratch for pd_sample_eps_at
@@ -383,6 +384,10 @@ static int check_args(pd_engine* e, const pd_sample_args* a) {
         return 1;
     }
     if (a->use_cfg && !a->ctx_uncond) { pd_set_error("use_cfg needs ctx_uncond"); return 1; }
+    if (a->context_len != 0 && (a->context_len < 1 || a->context_len > PD_MAX_CONTEXT_LEN)) {
+        pd_set_error("context_len %d out of range: 0 (the configured %d) or 1 .. %d", a->context_len, e->cfg.context_len, PD_MAX_CONTEXT_LEN);
+        return 1;
+    }
     if (a->eta > 0.f && !a->noise && !(a->init_flags & PD_NOISE_FROM_SEED)) {
         // the reference always draws noise when eta > 0 (ddim_hacked.py:230); running the eta > 0 coefficients without
         // it would deflate the sample variance silently
@@ -452,6 +457,7 @@ int pd_engine::begin(const pd_sample_args* a, bool want_per_step, const pd_unipc
     HIP_OK(hipSetDevice(device));
     PD_TRY(fold_layernorms());
     ses.a = *a;
+    ses.L = a->context_len ? a->context_len : cfg.context_len;
     ses.Bf = a->use_cfg ? 2 * a->batch : a->batch;
     ses.custom_ts.clear();
     if (a->timesteps) ses.custom_ts.assign(a->timesteps, a->timesteps + a->steps);   // always HOST memory
@@ -638,7 +644,7 @@ int pd_engine::run_steps_graph() {
     uint64_t key = 1469598103934665603ull;
     // (where the noise comes from is part of the key -- another kernel --, the seed is not: the kernels read it from rng_dev)
     const int32_t ints[] = {a.batch, a.h, a.w, a.steps, a.use_cfg, a.guess_mode, a.only_mid_control, ses.noise ? 1 : 0,
-                            ses.per_step ? 1 : 0, opt_two_streams ? 1 : 0, ses.S, opt_cfg_share ? 1 : 0, ses.noise_seeded ? 1 : 0};
+                            ses.per_step ? 1 : 0, opt_two_streams ? 1 : 0, ses.S, opt_cfg_share ? 1 : 0, ses.noise_seeded ? 1 : 0, ses.L};
     const float flts[] = {a.eta, a.cfg_scale, a.temperature};
     const void* ptrs[] = {arena.base, arena2.base, ses.x_state, ses.per_step};
     hash_mix(key, ints, sizeof(ints));
@@ -818,8 +824,14 @@ static int copy_out(pd_engine* e, const float* dev_src, float* dst, size_t n, in
 
 int pd_eps(pd_engine* e, const float* x, const int64_t* t, const float* ctx, const float* pair, const float* query,
            const float* scales, int32_t Bf, int32_t h, int32_t w, int32_t mem, float* eps_out, float* residuals_out) {
+    return pd_eps_ctx(e, x, t, ctx, 0, pair, query, scales, Bf, h, w, mem, eps_out, residuals_out);
+}
+
+int pd_eps_ctx(pd_engine* e, const float* x, const int64_t* t, const float* ctx, int32_t context_len, const float* pair, const float* query,
+               const float* scales, int32_t Bf, int32_t h, int32_t w, int32_t mem, float* eps_out, float* residuals_out) {
     if (!e || !x || !t || !ctx || !pair || !query || !eps_out) { pd_set_error("null argument"); return 1; }
     pd_sample_args a{};
+    a.context_len = context_len;
     a.batch = Bf; a.h = h; a.w = w; a.steps = 1; a.eta = 0.f; a.cfg_scale = 1.f; a.use_cfg = 0; a.temperature = 1.f;
     a.mem = mem; a.x_T = x; a.ctx_cond = ctx; a.pair = pair; a.query = query; a.control_scales = scales;
     PD_TRY(check_args(e, &a));
@@ -832,6 +844,7 @@ int pd_eps(pd_engine* e, const float* x, const int64_t* t, const float* ctx, con
     s.active = false;
     s.solver = SOLVER_DDIM;
     s.a = a;
+    s.L = context_len ? context_len : e->cfg.context_len;
     s.Bf = Bf;
     s.S = 1;
     PD_TRY(e->ensure_arena(Bf, false));

@@ -4,7 +4,8 @@
 // the block's residual (attention.py:338-340) for 128 tokens per workgroup, without touching HBM in between:
 //     h1 = att . Wo1^T + b + h            (attn1.to_out + residual)
 //     q  = LN2(h1) . Wq^T                 (attn2.to_q; gamma / beta folded into the weights / a bias)
-//     o  = softmax(q k^T dh^-0.5) v       (8 heads x 40, the <= 96 context keys of this sample, fp32 logits and statistics)
+//     o  = softmax(q k^T dh^-0.5) v       (8 heads x 40, the context keys of this sample in NW <= 3 windows of 96, fp32 logits and
+//                                          statistics; NW > 1: an online softmax across the windows)
 //     h2 = o . Wo2^T + b + h1
 //     h3 = (x * gelu(gate)) . W2^T + b + h2,   [x | gate] = LN3(h2) . W1^T + b      (GEGLU feed-forward, exact-erf GELU)
 //     out = h3 . Wp^T + b + x_in          (proj_out + the SpatialTransformer residual)
@@ -19,7 +20,8 @@
 // streamed through a 6 x 20 KB LDS ring by LDS-DMA (global_load_lds_dwordx4), 5 steps ahead of their use, one barrier per 20
 // fragments placed in the MIDDLE of a step so that the fragment reads (4 in flight) run across step boundaries.  Every fragment
 // feeds exactly one MFMA of each of the 4 waves.  The context K / V^T of the sample travel through the same ring
-// (st_tail_kv_pack_kernel lays them out per head pair).  tests/st_tail_emul.py restates every index map of this file in NumPy.
+// (st_tail_kv_pack_kernel lays them out per head pair and 96-key window).  tests/st_tail_emul.py restates every index map of this file
+// in NumPy, tests/st_tail_mw_emul.py the multi-window ones (template parameter NW).
 #include "pd_common.h"
 #include "pd_mma.h"
 
@@ -62,9 +64,13 @@ constexpr int RING_BYTES = NS * STEP_BYTES;
 // software-pipelined order: W1(0), {W1(c+1), W2(c)} for c = 0..38, W2(39) | D proj_out
 constexpr int WF_A = TNT * TKS, WF_PAIR = 120, WF_B = 4 * WF_PAIR, WF_CHUNK = 60, WF_C = TNCHUNK * WF_CHUNK, WF_D = TNT * TKS;
 constexpr int WF_TOTAL = WF_A + WF_B + WF_C + WF_D;   // 3280
-constexpr int KV_PAIR = 60;      // fragments per head pair: [K h0 9][V h0 12][K h1 9][V h1 12][pad 18]
-constexpr int STEPS_A = 10, STEPS_PAIR = 9, STEPS_CHUNK = 3, STEPS_D = 10;
-constexpr int STEPS_TOTAL = STEPS_A + 4 * STEPS_PAIR + TNCHUNK * STEPS_CHUNK + STEPS_D;   // 176
+constexpr int KV_PAIR = 60;      // fragments per (head pair, 96-key window): [K h0 9][V h0 12][K h1 9][V h1 12][pad 18]
+constexpr int KWIN = 96;         // context keys per window
+constexpr int MAX_NW = 3;        // windows the kernel is instantiated for: Nk <= 288
+constexpr int STEPS_A = 10, STEPS_CHUNK = 3, STEPS_D = 10;
+// a head pair: 3 steps of q weights, 3 steps per window of the pair's K / V group, 3 steps of attn2.to_out weights
+__host__ __device__ constexpr int steps_pair(int nw) { return 6 + 3 * nw; }
+__host__ __device__ constexpr int steps_total(int nw) { return STEPS_A + 4 * steps_pair(nw) + TNCHUNK * STEPS_CHUNK + STEPS_D; }   // 176 at nw = 1
 // fp32 vectors in LDS behind the ring
 constexpr int V_BO1 = 0, V_BQ = 320, V_BO2 = V_BQ + 384, V_B1 = V_BO2 + 320, V_B2 = V_B1 + TNCHUNK * 2 * 32, V_BP = V_B2 + 320, V_TOTAL = V_BP + 320;
 
@@ -114,7 +120,7 @@ struct StTailArgs {
     void* out;            // [M][320] stream type
     const char* wpk;      // WF_TOTAL fragments
     const float* vec;     // V_TOTAL floats
-    const char* kvp;      // [B][4][KV_PAIR] fragments
+    const char* kvp;      // [B][4][NW][KV_PAIR] fragments
     int rows_per_sample, Nk;
     float scale_log2e;    // dh^-0.5 * log2(e)
     int in_rows;          // att / h / x_in hold this many rows; output row r reads input row r % in_rows (the shared front of a CFG pair: pd_engine::transformer)
@@ -125,7 +131,7 @@ constexpr int FR_STEPS = 40, FR_WF = FR_STEPS * SF;
 constexpr int FV_BPI = 0, FV_BQKV = 320, FV_COEF = FV_BQKV + 960, FV_TOTAL = FV_COEF + 640;
 
 // the ring: one wave-uniform cursor; step st lives in slot st % NS
-template <int KIND>
+template <int KIND, int NW = 1>
 struct Pipe {
     const char* wsrc;   // weight stream (wave-uniform)
     const char* kvsrc;  // this sample's K / V fragments (wave-uniform)
@@ -143,13 +149,14 @@ struct Pipe {
     }
     __device__ __forceinline__ const char* step_src(int s) const {
         if constexpr (KIND == 1) return wsrc + (size_t)(s < FR_STEPS ? s : FR_STEPS - 1) * STEP_BYTES;
+        constexpr int STEPS_PAIR = steps_pair(NW), STEPS_TOTAL = steps_total(NW);
         if (s >= STEPS_TOTAL) s = STEPS_TOTAL - 1;   // past the end: keep the request count per step uniform (harmless re-reads)
         if (s < STEPS_A) return wsrc + (size_t)s * STEP_BYTES;
         if (s < STEPS_A + 4 * STEPS_PAIR) {
             const int p = (s - STEPS_A) / STEPS_PAIR, r = (s - STEPS_A) - p * STEPS_PAIR;
             if (r < 3) return wsrc + (size_t)(WF_A + p * WF_PAIR + r * SF) * 1024;
-            if (r < 6) return kvsrc + (size_t)(p * KV_PAIR + (r - 3) * SF) * 1024;
-            return wsrc + (size_t)(WF_A + p * WF_PAIR + 60 + (r - 6) * SF) * 1024;
+            if (r < 3 + 3 * NW) return kvsrc + (size_t)(p * (NW * KV_PAIR) + (r - 3) * SF) * 1024;   // the pair's NW window groups are consecutive
+            return wsrc + (size_t)(WF_A + p * WF_PAIR + 60 + (r - 3 - 3 * NW) * SF) * 1024;
         }
         return wsrc + (size_t)(WF_A + WF_B + (s - STEPS_A - 4 * STEPS_PAIR) * SF) * 1024;
     }
@@ -259,7 +266,7 @@ template <int P, bool F32> __device__ __forceinline__ void store_row16(void* bas
     }
 }
 
-template <int P, bool SF32>
+template <int P, bool SF32, int NW>
 __global__ __launch_bounds__(256, 1) void st_tail_kernel(StTailArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int hh = lane >> 5;
@@ -273,9 +280,9 @@ __global__ __launch_bounds__(256, 1) void st_tail_kernel(StTailArgs a) {
     }
 
     PD_STAMP_AT(0);
-    Pipe<0> pp;
+    Pipe<0, NW> pp;
     pp.wsrc = a.wpk;
-    pp.kvsrc = a.kvp + (size_t)((blockIdx.x * 128) / a.rows_per_sample) * (4 * KV_PAIR * 1024);
+    pp.kvsrc = a.kvp + (size_t)((blockIdx.x * 128) / a.rows_per_sample) * (4 * NW * KV_PAIR * 1024);
     pp.st = 0;
     pp.lane16 = lane * 16;
     pp.lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
@@ -328,33 +335,54 @@ __global__ __launch_bounds__(256, 1) void st_tail_kernel(StTailArgs a) {
             qf[2 * tl] = acc_frag<P, 0>(qa);
             qf[2 * tl + 1] = acc_frag<P, 1>(qa);
         });
-        // per head: S^T = K . q^T (keys on the accumulator rows: key 32 kt + 16 hh + r; tokens on the lanes), softmax over the
-        // keys, O^T = V^T . P^T (head dim on the rows: d = 32 dt + 16 hh + r, 40 of the 64 real).  The pair's 60 fragments are
+        // per head: S^T = K . q^T (keys on the accumulator rows: key 96 w + 32 kt + 16 hh + r; tokens on the lanes), softmax over the
+        // keys, O^T = V^T . P^T (head dim on the rows: d = 32 dt + 16 hh + r, 40 of the 64 real).  A window's 60 fragments are
         // [K h0 9][V h0 12][K h1 9][V h1 12][pad 18]; the softmax of a head sits in front of its first V fragment.
-        f32x16 S[3], O[2];
+        // NW > 1: the pair's windows follow each other, so both heads' O accumulators (and their running max / sum) live across
+        // the windows: in front of a window's V fragments O is rescaled by exp2((m_old - m_new) * scale) -- 1 when the max stayed.
+        constexpr int NO = NW > 1 ? 2 : 1;   // O accumulators alive at once: one per head, or one reused (a single window ends head 0 before head 1)
+        f32x16 S[3], O[NO][2];
         uint4 pf[6], of[2][3];
         float linv = 0.f;
+        float mrun[NO], lrun[NO];   // NW > 1: running max (raw logits) and sum of the lane pair's row, per head
         auto zero_s = [&]() __attribute__((always_inline)) {
 #pragma unroll
             for (int kt = 0; kt < 3; ++kt)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) S[kt][r] = 0.f;
+        };
+        auto zero_o = [&](auto HO) __attribute__((always_inline)) {
+            constexpr int ho = decltype(HO)::value;
 #pragma unroll
             for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) O[dt][r] = 0.f;
+                for (int r = 0; r < 16; ++r) O[ho][dt][r] = 0.f;
         };
-        auto softmax = [&]() __attribute__((always_inline)) {
+        auto softmax = [&](auto WI, auto HL) __attribute__((always_inline)) {
+            constexpr int wi = decltype(WI)::value, hl = decltype(HL)::value;
             float m = -INFINITY;
 #pragma unroll
             for (int kt = 0; kt < 3; ++kt)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const bool ok = 32 * kt + 16 * hh + r < a.Nk;
-                    S[kt][r] = ok ? S[kt][r] : -INFINITY;
+                    if constexpr (wi == NW - 1) {   // keys >= Nk exist in the last window only
+                        const bool ok = KWIN * wi + 32 * kt + 16 * hh + r < a.Nk;
+                        S[kt][r] = ok ? S[kt][r] : -INFINITY;
+                    }
                     m = fmaxf(m, S[kt][r]);
                 }
             m = fmaxf(m, xor32(m));
+            if constexpr (NW > 1 && wi > 0) {
+                // online softmax: the new running max, then O and the running sum of the windows so far move to it
+                const float mo = mrun[hl];
+                m = fmaxf(m, mo);
+                const float al = __builtin_amdgcn_exp2f((mo - m) * a.scale_log2e);
+                lrun[hl] *= al;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) O[hl][0][r] *= al;
+#pragma unroll
+                for (int r = 0; r < 8; ++r) O[hl][1][r] *= al;
+            }
             const float mc = m * a.scale_log2e;
             float l = 0.f;
 #pragma unroll
@@ -366,7 +394,11 @@ __global__ __launch_bounds__(256, 1) void st_tail_kernel(StTailArgs a) {
                     l += e;
                 }
             l += xor32(l);
-            linv = __builtin_amdgcn_rcpf(l);
+            if constexpr (NW == 1) linv = __builtin_amdgcn_rcpf(l);
+            else {
+                mrun[hl] = m;
+                if constexpr (wi == 0) lrun[hl] = l; else lrun[hl] += l;
+            }
 #pragma unroll
             for (int kt = 0; kt < 3; ++kt) {
                 pf[2 * kt] = acc_frag<P, 0>(S[kt]);
@@ -374,35 +406,41 @@ __global__ __launch_bounds__(256, 1) void st_tail_kernel(StTailArgs a) {
             }
         };
         auto finish_o = [&](auto HL) __attribute__((always_inline)) {
-            constexpr int hl = decltype(HL)::value;
+            constexpr int hl = decltype(HL)::value, ho = NW > 1 ? hl : 0;
+            if constexpr (NW > 1) linv = __builtin_amdgcn_rcpf(lrun[hl]);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) O[0][r] *= linv;
+            for (int r = 0; r < 16; ++r) O[ho][0][r] *= linv;
 #pragma unroll
-            for (int r = 0; r < 8; ++r) O[1][r] *= linv;
-            of[hl][0] = acc_frag<P, 0>(O[0]);
-            of[hl][1] = acc_frag<P, 1>(O[0]);
-            of[hl][2] = acc_frag<P, 0>(O[1]);
+            for (int r = 0; r < 8; ++r) O[ho][1][r] *= linv;
+            of[hl][0] = acc_frag<P, 0>(O[ho][0]);
+            of[hl][1] = acc_frag<P, 1>(O[ho][0]);
+            of[hl][2] = acc_frag<P, 0>(O[ho][1]);
         };
         zero_s();
-        static_for<3>([&](auto SG) __attribute__((always_inline)) {
+        static_for<NO>([&](auto HO) __attribute__((always_inline)) { zero_o(HO); });
+        static_for<3 * NW>([&](auto SG) __attribute__((always_inline)) {
             constexpr int sg = decltype(SG)::value;
             run_step(pp, [&](auto I, const uint4& w) __attribute__((always_inline)) {
-                constexpr int o = sg * SF + decltype(I)::value;
+                constexpr int og = sg * SF + decltype(I)::value;
+                constexpr int wi = og / KV_PAIR, o = og % KV_PAIR;   // window, fragment of its group
+                constexpr bool last = wi == NW - 1;
                 if constexpr (o < 42) {
-                    constexpr int hl = o / 21, q = o % 21;
+                    constexpr int hl = o / 21, q = o % 21, ho = NW > 1 ? hl : 0;
                     if constexpr (q < 9) {
                         if constexpr (q == 0 && hl == 1) {
-                            finish_o(std::integral_constant<int, 0>{});
+                            if constexpr (last) finish_o(std::integral_constant<int, 0>{});
                             zero_s();
+                            if constexpr (NW == 1) zero_o(std::integral_constant<int, 0>{});
                         }
+                        if constexpr (q == 0 && hl == 0 && wi > 0) zero_s();
                         mfma32<P>(w, qf[3 * hl + q % 3], S[q / 3]);
                     } else {
-                        if constexpr (q == 9) softmax();
-                        mfma32<P>(w, pf[(q - 9) % 6], O[(q - 9) / 6]);
+                        if constexpr (q == 9) softmax(std::integral_constant<int, wi>{}, std::integral_constant<int, hl>{});
+                        mfma32<P>(w, pf[(q - 9) % 6], O[ho][(q - 9) / 6]);
                     }
                     return true;
                 } else {
-                    if constexpr (o == 42) finish_o(std::integral_constant<int, 1>{});
+                    if constexpr (o == 42 && last) finish_o(std::integral_constant<int, 1>{});
                     return false;
                 }
             });
@@ -739,19 +777,20 @@ __global__ __launch_bounds__(256) void st_tail_vec_kernel(StVecArgs a) {
     a.dst[i] = v;
 }
 
-// context K [B][Nk][320] / V^T [B][320][lpad] -> [B][4][KV_PAIR] fragments; one thread per (fragment, lane)
-__global__ __launch_bounds__(256) void st_tail_kv_pack_kernel(const uint16_t* K, const uint16_t* VT, uint16_t* dst, int B, int Nk, int lpad) {
+// context K [B][Nk][320] / V^T [B][320][lpad] -> [B][4][NW][KV_PAIR] fragments (NW = ceil(Nk / 96) windows, window w holds keys
+// 96 w .. 96 w + 95; keys >= Nk are zeros); one thread per (fragment, lane)
+__global__ __launch_bounds__(256) void st_tail_kv_pack_kernel(const uint16_t* K, const uint16_t* VT, uint16_t* dst, int B, int Nk, int lpad, int NW) {
     const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
     const int lane = (int)(gid & 63);
     const long long FF = gid >> 6;
-    if (FF >= (long long)B * 4 * KV_PAIR) return;
-    const int F = (int)(FF % KV_PAIR), pr = (int)((FF / KV_PAIR) % 4), b = (int)(FF / (4 * KV_PAIR));
+    if (FF >= (long long)B * 4 * NW * KV_PAIR) return;
+    const int F = (int)(FF % KV_PAIR), wi = (int)((FF / KV_PAIR) % NW), pr = (int)((FF / (KV_PAIR * NW)) % 4), b = (int)(FF / (4 * NW * KV_PAIR));
     const int i = lane & 31, hk = lane >> 5;
     uint16_t e[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const int hl = F / 21, q = F % 21;
     if (F < 42 && q < 9) {
         const int kt = q / 3, ks = q % 3;
-        const int key = 32 * kt + sigma(i), d0 = 16 * ks + 8 * hk;
+        const int key = KWIN * wi + 32 * kt + sigma(i), d0 = 16 * ks + 8 * hk;
         if (key < Nk && d0 < TDH) {
             const uint16_t* s = K + ((size_t)b * Nk + key) * TC + (2 * pr + hl) * TDH + d0;
 #pragma unroll
@@ -759,7 +798,7 @@ __global__ __launch_bounds__(256) void st_tail_kv_pack_kernel(const uint16_t* K,
         }
     } else if (F < 42) {
         const int o = q - 9, dt = o / 6, kk = o % 6;
-        const int d = 32 * dt + sigma(i), key0 = 32 * (kk >> 1) + 16 * hk + 8 * (kk & 1);
+        const int d = 32 * dt + sigma(i), key0 = KWIN * wi + 32 * (kk >> 1) + 16 * hk + 8 * (kk & 1);
         if (d < TDH) {
             const uint16_t* s = VT + ((size_t)b * TC + (2 * pr + hl) * TDH + d) * lpad;
 #pragma unroll
@@ -801,12 +840,13 @@ int launch_st_front(const void* x, const float* coef, void* h, void* qk, void* v
 
 size_t st_tail_weight_bytes() { return (size_t)WF_TOTAL * 1024; }
 size_t st_tail_vec_floats() { return V_TOTAL; }
-size_t st_tail_kv_bytes(int B) { return (size_t)B * 4 * KV_PAIR * 1024; }
+int st_tail_windows(int Nk) { return (Nk + KWIN - 1) / KWIN; }
+size_t st_tail_kv_bytes(int B, int Nk) { return (size_t)B * 4 * st_tail_windows(Nk) * KV_PAIR * 1024; }
 double st_tail_flops(long long M, int Nk) {   // algorithmic: the six linear layers + QK^T and PV over the real keys and head dim
     return 2.0 * (double)M * TC * (4.0 * TC + 8.0 * TC + 4.0 * TC) + 4.0 * (double)M * Nk * TC;
 }
 bool st_tail_eligible(int prec, int C, int heads, int rows_per_sample, int Nk) {
-    return (prec == DT_F16 || prec == DT_BF16) && C == TC && heads == THD && rows_per_sample % 128 == 0 && Nk >= 1 && Nk <= 96;
+    return (prec == DT_F16 || prec == DT_BF16) && C == TC && heads == THD && rows_per_sample % 128 == 0 && Nk >= 1 && Nk <= MAX_NW * KWIN;
 }
 
 int launch_st_tail_pack(const void* wo1, const void* wq_ln, const void* wo2, const void* w1_ln, const void* w2, const void* wp, int ld_c, int ld_w2,
@@ -824,27 +864,30 @@ int launch_st_tail_vec(const float* bo1, const float* bq_ln, const float* bo2, c
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 int launch_st_tail_kv_pack(const void* K, const void* VT, void* dst, int B, int Nk, int lpad, hipStream_t s) {
-    const long long n = (long long)B * 4 * KV_PAIR * 64;
+    if (Nk < 1 || Nk > MAX_NW * KWIN) return 1;
+    const int NW = st_tail_windows(Nk);
+    const long long n = (long long)B * 4 * NW * KV_PAIR * 64;
     hipLaunchKernelGGL(st_tail_kv_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const uint16_t*>(K),
-                       reinterpret_cast<const uint16_t*>(VT), reinterpret_cast<uint16_t*>(dst), B, Nk, lpad);
+                       reinterpret_cast<const uint16_t*>(VT), reinterpret_cast<uint16_t*>(dst), B, Nk, lpad, NW);
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 int launch_st_tail(const void* att, const void* h, const void* x_in, void* out, const void* wpk, const float* vec, const void* kvp, long long M,
                    int rows_per_sample, int Nk, int s_dt, float scale, int prec, hipStream_t s, long long in_rows) {
     if (in_rows <= 0) in_rows = M;
-    if (M % 128 || M > 0x7fffffff || rows_per_sample % 128 || Nk < 1 || Nk > 96 || in_rows % 128 || M % in_rows) return 1;
+    if (M % 128 || M > 0x7fffffff || rows_per_sample % 128 || Nk < 1 || Nk > MAX_NW * KWIN || in_rows % 128 || M % in_rows) return 1;
     StTailArgs a{att, h, x_in, out, reinterpret_cast<const char*>(wpk), vec, reinterpret_cast<const char*>(kvp), rows_per_sample, Nk,
                  scale * 1.4426950408889634f, (int)in_rows};
     constexpr int SMEM = RING_BYTES + V_TOTAL * 4;
-    static unsigned long long done[2] = {0, 0};
+    static unsigned long long done[2 * MAX_NW] = {};
     if (s_dt != prec) return 1;   // the stream type is the compute type here (option stream_f32 keeps the per-layer path: an fp32 stream's
                                   // loads in flight next to the 240 resident registers spill)
     void (*kfn)(StTailArgs) = nullptr;
     int slot = 0;
-    if (prec == DT_F16) { kfn = st_tail_kernel<DT_F16, false>; slot = 0; }
-    else if (prec == DT_BF16) { kfn = st_tail_kernel<DT_BF16, false>; slot = 1; }
+    const int NW = st_tail_windows(Nk);   // 96-key windows of the context
+    if (prec == DT_F16) { kfn = NW == 1 ? st_tail_kernel<DT_F16, false, 1> : NW == 2 ? st_tail_kernel<DT_F16, false, 2> : st_tail_kernel<DT_F16, false, 3>; slot = 0; }
+    else if (prec == DT_BF16) { kfn = NW == 1 ? st_tail_kernel<DT_BF16, false, 1> : NW == 2 ? st_tail_kernel<DT_BF16, false, 2> : st_tail_kernel<DT_BF16, false, 3>; slot = 1; }
     else return 1;
-    if (ensure_dyn_smem(reinterpret_cast<const void*>(kfn), SMEM, &done[slot])) return 1;
+    if (ensure_dyn_smem(reinterpret_cast<const void*>(kfn), SMEM, &done[slot * MAX_NW + NW - 1])) return 1;
     hipLaunchKernelGGL(kfn, dim3((unsigned)(M / 128)), dim3(256), SMEM, s, a);
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }

@@ -22,6 +22,12 @@ encoder needs an engine built with ``ModelConfig(vae_encoder=True)``), so the SD
     init = model.get_first_stage_encoding(model.encode_first_stage(x))
     z = sampler.stochastic_encode(init, t_enc, noise=...)
     samples = model.decode_first_stage(sampler.decode(z, cond, t_enc, ...))
+
+``c_crossattn`` tensors of any length L <= engine.PD_MAX_CONTEXT_LEN flow through every sampler and through ``encode`` / ``decode``
+(the engine takes the context length per call); the conditional and the unconditional one must have the same L, as the reference's
+``torch.cat`` of the two halves demands.  ``ControlLDM(engine, tokenizer)`` also has the cond stage: ``get_learned_conditioning`` on
+the engine's CLIP, and ``hack_everything(clip_skip)`` for the reference's long prompts (cldm/hack.py: three 75-token windows ->
+a [B, 231, 768] context) with the reference's clip_skip count.
 """
 from __future__ import annotations
 
@@ -76,8 +82,15 @@ class DiagonalGaussianDistribution:
 class ControlLDM:
     """The attributes of cldm.cldm.ControlLDM the sampler touches, backed by an Engine."""
 
-    def __init__(self, engine: E.Engine):
+    def __init__(self, engine: E.Engine, tokenizer=None, long_prompts=None, clip_skip: int = 0):
+        """tokenizer: a transformers CLIPTokenizer (or a look-alike) for get_learned_conditioning.  long_prompts / clip_skip: as
+        hack_everything(clip_skip) sets them -- clip_skip counts like the REFERENCE's (cldm/hack.py: hidden_states[-clip_skip] for
+        clip_skip > 1, the last layer for 0 and 1), one higher than diffusers' / PromptDiffusionPipeline's clip_skip."""
+        from .pipeline import _window_count
         self.engine = engine
+        self.tokenizer = tokenizer
+        self.long_prompt_windows = _window_count(long_prompts)
+        self.clip_skip = int(clip_skip)
         self.control_scales = [1.0] * 13          # cldm/cldm.py:335
         self.only_mid_control = False             # cldm/cldm.py:334
         self.num_timesteps = engine.cfg.timesteps
@@ -118,6 +131,29 @@ class ControlLDM:
     def decode_first_stage(self, z):
         """LatentDiffusion.decode_first_stage (ddpm.py:820-828): 1 / scale_factor, post_quant_conv and the decoder, on the engine."""
         return self.engine.vae_decode(_np32(z))
+
+    def hack_everything(self, clip_skip: int = 0, windows: int = 3):
+        """cldm/hack.py hack_everything: long prompts (three 75-token windows, each BOS / EOS wrapped and padded to 77, encoded as one
+        batch and concatenated to [B, 231, D]) and the reference's clip_skip for get_learned_conditioning."""
+        from .pipeline import _window_count
+        self.long_prompt_windows = _window_count(windows)
+        self.clip_skip = int(clip_skip)
+
+    def get_learned_conditioning(self, c):
+        """LatentDiffusion.get_learned_conditioning (ddpm.py:555-565) with FrozenCLIPEmbedder.forward (modules.py:118-131) or, after
+        hack_everything, _hacked_clip_forward: prompts -> [B, L, D] fp32 on the engine's CLIP text transformer."""
+        from .pipeline import reference_clip_skip, tokenize_long
+        if self.tokenizer is None:
+            raise ValueError("get_learned_conditioning needs ControlLDM(engine, tokenizer=...)")
+        prompts = [c] if isinstance(c, str) else list(c)
+        L = self.engine.cfg.context_len
+        if self.long_prompt_windows:
+            n = self.long_prompt_windows
+            z = self.engine.text_encode(tokenize_long(self.tokenizer, prompts, n, L), clip_skip=reference_clip_skip(self.clip_skip))
+            return z.reshape(len(prompts), n * L, z.shape[-1])
+        # (the unhacked FrozenCLIPEmbedder has no clip_skip: last_hidden_state)
+        ids = self.tokenizer(prompts, truncation=True, max_length=L, padding="max_length", return_tensors="np")["input_ids"]
+        return self.engine.text_encode(np.asarray(ids, np.int32))
 
     def apply_model(self, x_noisy, t, cond, *args, **kwargs):
         """eps = apply_model(x, t, cond), cldm/cldm.py:369-382 (one HIP pass through ControlNet + UNet)."""

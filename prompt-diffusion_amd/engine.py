@@ -25,6 +25,7 @@ PD_VAE_MEAN, PD_VAE_SAMPLE, PD_VAE_MOMENTS = 0, 1, 2
 VAE_ENCODE_MODES = {"mean": PD_VAE_MEAN, "sample": PD_VAE_SAMPLE, "moments": PD_VAE_MOMENTS}
 PD_MAX_LEVELS = 8
 PD_NUM_CONTROL = 13
+PD_MAX_CONTEXT_LEN = 1024
 PD_COMM_ID_BYTES = 128
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
@@ -51,7 +52,13 @@ class pd_config(C.Structure):
     ]
 
 
+class _ContextLen(C.Union):
+    """pd_sample_args.context_len; `reserved` is the field's name before it had a meaning, kept as an alias of the same four bytes"""
+    _fields_ = [("context_len", C.c_int32), ("reserved", C.c_int32 * 1)]
+
+
 class pd_sample_args(C.Structure):
+    _anonymous_ = ("_ctx",)
     _fields_ = [
         ("batch", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("steps", C.c_int32),
         ("eta", C.c_float), ("cfg_scale", C.c_float), ("use_cfg", C.c_int32), ("guess_mode", C.c_int32),
@@ -60,7 +67,7 @@ class pd_sample_args(C.Structure):
         ("query", C.c_void_p), ("pair_uncond", C.c_void_p), ("query_uncond", C.c_void_p),
         ("control_scales", C.c_void_p), ("control_scales_step", C.c_void_p), ("noise", C.c_void_p),
         ("timesteps", C.c_void_p), ("init_latents", C.c_void_p), ("mask", C.c_void_p), ("init_flags", C.c_int32),
-        ("reserved", C.c_int32 * 1),
+        ("_ctx", _ContextLen),
     ]
 
 
@@ -144,6 +151,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.pd_text_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     lib.pd_text_encode_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
     lib.pd_eps.argtypes = [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p]
+    lib.pd_eps_ctx.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p]
     lib.pd_control_shape.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_int32] + [C.POINTER(C.c_int32)] * 3
     lib.pd_ddim_sample.argtypes = [C.c_void_p, C.POINTER(pd_sample_args), C.c_int32, C.c_void_p, C.c_void_p]
     lib.pd_sample_begin.argtypes = [C.c_void_p, C.POINTER(pd_sample_args)]
@@ -189,6 +197,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.pd_op_layernorm.argtypes = [C.c_void_p, fp, fp, fp, C.c_int, C.c_int, fp]
     lib.pd_op_attention.argtypes = [C.c_void_p, fp, fp, fp] + [C.c_int] * 4 + [fp]
     lib.pd_op_spatial_transformer.argtypes = [C.c_void_p, C.c_char_p, fp, fp] + [C.c_int] * 3 + [fp]
+    lib.pd_op_spatial_transformer_ctx.argtypes = [C.c_void_p, C.c_char_p, fp, fp] + [C.c_int] * 4 + [fp]
     lib.pd_op_time_embed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, fp, fp]
     lib.pd_op_vae_downsample.argtypes = [C.c_void_p, fp, fp, fp] + [C.c_int] * 4 + [fp]
     lib.pd_read_weights.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
@@ -212,14 +221,14 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
 EXPORTS = [
     "pd_last_error", "pd_abi_version", "pd_engine_create", "pd_engine_destroy", "pd_param_count", "pd_param_info",
     "pd_load_weights", "pd_init_random_weights", "pd_weights_missing", "pd_vae_weights_missing", "pd_vae_decode",
-    "pd_vae_encode", "pd_vae_encoder_weights_missing", "pd_eps", "pd_control_shape", "pd_ddim_sample",
+    "pd_vae_encode", "pd_vae_encoder_weights_missing", "pd_eps", "pd_eps_ctx", "pd_control_shape", "pd_ddim_sample",
     "pd_sample_begin", "pd_sample_step", "pd_sample_get", "pd_sample_set_latents", "pd_sample_set_guidance", "pd_sample_eps_at", "pd_sample_end",
     "pd_unipc_coefficients", "pd_unipc_sample", "pd_sample_begin_unipc",
     "pd_lms_coefficients", "pd_lms_sample", "pd_sample_begin_lms", "pd_sample_rows",
     "pd_make_schedule", "pd_synchronize", "pd_stream", "pd_wait_stream", "pd_set_option", "pd_get_stat", "pd_bench_conv3x3", "pd_bench_linear", "pd_text_encode", "pd_text_encode_ex", "pd_text_weights_missing",
     "pd_profile_read", "pd_profile_dump", "pd_comm_new_id", "pd_comm_init", "pd_comm_world", "pd_comm_all_gather", "pd_comm_destroy",
     "pd_sd3_configure", "pd_sd3_weights_missing", "pd_sd3_forward", "pd_sd3_control", "pd_sd3_sample", "pd_sd3_down_proj",
-    "pd_op_conv2d", "pd_op_linear", "pd_op_linear_fp8", "pd_op_groupnorm", "pd_op_layernorm", "pd_op_attention", "pd_op_spatial_transformer", "pd_op_time_embed",
+    "pd_op_conv2d", "pd_op_linear", "pd_op_linear_fp8", "pd_op_groupnorm", "pd_op_layernorm", "pd_op_attention", "pd_op_spatial_transformer", "pd_op_spatial_transformer_ctx", "pd_op_time_embed",
     "pd_op_timestep_embedding_i", "pd_op_timestep_embedding_f", "pd_op_vae_downsample", "pd_read_weights", "pd_lora_add", "pd_lora_set_scales", "pd_lora_remove",
     "pd_set_freeu", "pd_get_freeu", "pd_op_freeu_concat",
     "pd_philox4x32_10", "pd_set_rng", "pd_get_rng", "pd_randn",
@@ -655,9 +664,11 @@ class Engine:
         return out
 
     def eps(self, x, t, ctx, pair, query, scales: Optional[Sequence[float]] = None, return_control: bool = False):
-        """apply_model (cldm/cldm.py:369-382): eps [Bf,4,h,w] (and the 13 scaled control tensors)."""
+        """apply_model (cldm/cldm.py:369-382): eps [Bf,4,h,w] (and the 13 scaled control tensors).  ctx [Bf, L, context_dim] of any
+        length L <= PD_MAX_CONTEXT_LEN."""
         xb, cb, pb, qb = _Buf(x), _Buf(ctx), _Buf(pair), _Buf(query)
         Bf, _, h, w = xb.owner.shape
+        L = self._context_len(cb.owner, Bf, "ctx")
         mem = xb.mem
         if any(b.mem != mem for b in (cb, pb, qb)):
             raise PdError("all inputs must live in the same memory space")
@@ -677,8 +688,8 @@ class Engine:
             res = np.empty(sum(Bf * c * a * b for c, a, b in shapes), np.float32) if return_control else None
             ep, rp = eps.ctypes.data, (res.ctypes.data if res is not None else None)
         self._order_after_torch(mem)
-        self._check(self.lib.pd_eps(self._h, xb.ptr, tb.ptr, cb.ptr, pb.ptr, qb.ptr,
-                                    None if sc is None else sc.ctypes.data, Bf, h, w, mem, ep, rp))
+        self._check(self.lib.pd_eps_ctx(self._h, xb.ptr, tb.ptr, cb.ptr, L, pb.ptr, qb.ptr,
+                                        None if sc is None else sc.ctypes.data, Bf, h, w, mem, ep, rp))
         if not return_control:
             return eps
         outs, off = [], 0
@@ -687,6 +698,15 @@ class Engine:
             outs.append(res[off:off + n].reshape(Bf, c, a, b))
             off += n
         return eps, outs
+
+    def _context_len(self, ctx, batch: int, what: str) -> int:
+        """L of a context tensor [batch, L, context_dim] (pd_sample_args.context_len)."""
+        sh = tuple(ctx.shape)
+        if len(sh) != 3 or sh[0] != batch or sh[2] != self.cfg.context_dim:
+            raise ValueError(f"{what} must be [{batch}, L, {self.cfg.context_dim}], got {sh}")
+        if not 1 <= sh[1] <= PD_MAX_CONTEXT_LEN:
+            raise ValueError(f"{what}: context length {sh[1]} out of range 1 .. {PD_MAX_CONTEXT_LEN}")
+        return int(sh[1])
 
     # ------------------------------------------------------------------ sampling
     def num_ddim_steps(self, steps: int) -> int:
@@ -711,7 +731,8 @@ class Engine:
         (PD_XT_FROM_SEED); batch and latent size then come from init_latents, or from ctx_cond and pair.
         init_latents [B,4,h,w] (z0, already times scale_factor) turns x_T into the noise draw of img2img; mask [B,1,h,w] or
         [1,1,h,w] (1 = repaint) adds the inpainting blend after every step; init_pure_noise starts from x_T itself
-        (pd_sample_args.init_latents / mask / init_flags)."""
+        (pd_sample_args.init_latents / mask / init_flags).
+        ctx_cond / ctx_uncond are [B, L, context_dim] with any equal L <= PD_MAX_CONTEXT_LEN (pd_sample_args.context_len)."""
         flags = PD_INIT_PURE_NOISE if init_pure_noise else 0
         if isinstance(noise, str):
             if noise != "engine":
@@ -744,6 +765,11 @@ class Engine:
         a = pd_sample_args()
         a.init_flags = flags
         B, _, h, w = xs
+        a.context_len = self._context_len(bufs["ctx_cond"].owner, B, "ctx_cond")
+        cu = bufs["ctx_uncond"].owner
+        if cu is not None and tuple(cu.shape) != tuple(bufs["ctx_cond"].owner.shape):
+            # (the reference's torch.cat of the two halves, ddim_hacked.py:191, raises as well)
+            raise ValueError(f"ctx_uncond {tuple(cu.shape)} must have the shape of ctx_cond {tuple(bufs['ctx_cond'].owner.shape)}")
         a.batch, a.h, a.w, a.steps = B, h, w, steps
         a.eta, a.cfg_scale, a.use_cfg = eta, cfg_scale, 1 if use_cfg else 0
         a.guess_mode, a.only_mid_control, a.temperature = int(guess_mode), int(only_mid_control), temperature
@@ -1065,9 +1091,11 @@ class Engine:
         return y
 
     def op_spatial_transformer(self, prefix: str, x, context):
-        """SpatialTransformer.forward (attention.py:321-340) of the block loaded under `prefix`, through the sampling code path."""
+        """SpatialTransformer.forward (attention.py:321-340) of the block loaded under `prefix`, through the sampling code path;
+        context [B, L, context_dim] of any length L <= PD_MAX_CONTEXT_LEN."""
         x = np.ascontiguousarray(x, np.float32); ctx = np.ascontiguousarray(context, np.float32)
         B, Cc, H, W = x.shape
+        L = self._context_len(ctx, B, "context")
         y = np.empty_like(x)
-        self._check(self.lib.pd_op_spatial_transformer(self._h, prefix.encode(), x.ctypes.data, ctx.ctypes.data, B, H, W, y.ctypes.data))
+        self._check(self.lib.pd_op_spatial_transformer_ctx(self._h, prefix.encode(), x.ctypes.data, ctx.ctypes.data, B, H, W, L, y.ctypes.data))
         return y

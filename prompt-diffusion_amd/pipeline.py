@@ -11,7 +11,9 @@ Either side of the hot path:
   * the text encoder: ``tokenizer=`` (a transformers CLIPTokenizer or a callable prompts -> ids [B, 77]) runs the CLIP text
     transformer inside the engine (``pd_text_encode``) when the checkpoint's ``cond_stage_model.*`` tensors are
     loaded; a ``text_encoder(list_of_prompts) -> [B, 77, 768]`` callable overrides it; with neither pass ``prompt_embeds`` /
-    ``negative_prompt_embeds`` (the north star consumes the CLIP embedding as a fixed context tensor);
+    ``negative_prompt_embeds`` (the north star consumes the CLIP embedding as a fixed context tensor) -- of any equal length
+    L <= 1024: the engine takes the context length per call.  ``enable_long_prompts()`` makes the engine's encoder build the
+    reference's long-prompt context (cldm/hack.py: three 75-token windows -> [B, 231, 768]);
   * the VAE decoder: built into the engine (``pd_vae_decode``) when the checkpoint's ``first_stage_model.*``
     tensors are loaded; a ``vae_decode(latents / scaling_factor) -> images in [-1, 1]`` callable overrides it; with
     neither use ``output_type="latent"``.
@@ -82,14 +84,67 @@ class EngineGenerator:
         return self.engine.randn(shape, stream=stream, draw=draw)
 
 
+def split_long_prompt(raw_ids, bos: int, eos: int, pad: int, windows: int = 3, width: int = 77) -> np.ndarray:
+    """The reference's long-prompt windows (cldm/hack.py, _hacked_clip_forward): the untruncated token ids of one prompt, without
+    special tokens, are cut into `windows` runs of width - 2 (tokens past (width - 2) * windows are dropped, as its split() drops
+    them); each run becomes [BOS] + run + [EOS], cut or padded to `width` with the pad token.  Every prompt gets all `windows`
+    windows, empty ones included.  Returns int32 [windows, width]."""
+    raw = [int(t) for t in raw_ids]
+    run = width - 2
+    out = np.empty((windows, width), np.int32)
+    for f in range(windows):
+        x = [bos] + raw[run * f:run * (f + 1)] + [eos]
+        out[f] = x[:width] if len(x) >= width else x + [pad] * (width - len(x))
+    return out
+
+
+def reference_clip_skip(clip_skip: int) -> int:
+    """cldm/hack.py's clip_skip -> the engine's (= diffusers'): the reference takes hidden_states[-clip_skip] for clip_skip > 1 (and
+    the last layer for 0 and 1), the engine's text_encode(clip_skip=k) takes hidden_states[-(k + 1)] -- so c > 1 maps to c - 1
+    and 0 / 1 map to 0."""
+    c = int(clip_skip)
+    if c < 0:
+        raise ValueError(f"clip_skip must be >= 0, got {clip_skip}")
+    return c - 1 if c > 1 else 0
+
+
+def _window_count(value) -> int:
+    """long_prompts= of the constructors: None / False -> 0 (off), True -> 3 (the reference's), n -> n"""
+    if value is None or value is False:
+        return 0
+    n = 3 if value is True else int(value)
+    if n < 1:
+        raise ValueError(f"long prompts need at least one window, got {value}")
+    return n
+
+
+def tokenize_long(tokenizer, prompts: List[str], windows: int, width: int) -> np.ndarray:
+    """prompts -> int32 [B * windows, width] window ids (split_long_prompt of every prompt, prompt-major: the reference's
+    '(b f) i' batch).  The tokenizer is called as the reference calls it -- truncation=False, add_special_tokens=False -- and
+    supplies bos_token_id / eos_token_id / pad_token_id."""
+    for attr in ("bos_token_id", "eos_token_id", "pad_token_id"):
+        if getattr(tokenizer, attr, None) is None:
+            raise ValueError(f"long prompts need a tokenizer with {attr} (a transformers CLIPTokenizer has it)")
+    raw = tokenizer(list(prompts), truncation=False, add_special_tokens=False)["input_ids"]
+    if len(raw) != len(prompts):
+        raise ValueError(f"tokenizer returned {len(raw)} id lists for {len(prompts)} prompts")
+    return np.concatenate([split_long_prompt(r, tokenizer.bos_token_id, tokenizer.eos_token_id, tokenizer.pad_token_id, windows, width)
+                           for r in raw]) if len(raw) else np.zeros((0, width), np.int32)
+
+
 class PromptDiffusionPipeline:
     _callback_tensor_inputs = ["latents", "prompt_embeds", "negative_prompt_embeds"]
     vae_scale_factor = 8
     vae_scaling_factor = 0.18215      # models/cldm_v15.yaml:17
 
     def __init__(self, engine: E.Engine, text_encoder: Optional[Callable] = None, vae_decode: Optional[Callable] = None,
-                 scheduler: Any = None, tokenizer: Any = None, fuse_scheduler: bool = False):
-        """fuse_scheduler: run the update of a UniPCMultistepScheduler (pd_unipc_sample), DPMSolverMultistepScheduler or
+                 scheduler: Any = None, tokenizer: Any = None, fuse_scheduler: bool = False, long_prompts=None):
+        """long_prompts: True / a window count = enable_long_prompts() at construction.
+        prompt_embeds / negative_prompt_embeds of any equal length L <= engine.PD_MAX_CONTEXT_LEN are accepted by every path
+        (fused DDIM, fuse_scheduler=True, host schedulers, callbacks): the engine takes the context length per call.
+        clip_skip of __call__ has diffusers' meaning (the hidden state of layer -(clip_skip + 1)); the reference's own
+        hack_everything(clip_skip=c) counts one higher -- reference_clip_skip(c) converts, and the (L) facade in ddim.py takes c.
+        fuse_scheduler: run the update of a UniPCMultistepScheduler (pd_unipc_sample), DPMSolverMultistepScheduler or
         PNDMScheduler (pd_lms_sample) inside the engine's loop instead of on the host between eps evaluations; same grid, same
         controlnet_keep scales, same callback semantics."""
         self.engine = engine
@@ -104,6 +159,9 @@ class PromptDiffusionPipeline:
         self.fuse_scheduler = bool(fuse_scheduler)
         if self.fuse_scheduler:
             self._check_fusable()
+        self._long_windows = 0
+        if _window_count(long_prompts):
+            self.enable_long_prompts(long_prompts)
         self._guidance_scale = 7.5
         # LoRA adapters (load_lora_weights): name -> {"id", "unet", "text_encoder"}; the active set with its weights; the
         # per-id scales the engine holds merged now (None: nothing merged yet)
@@ -182,6 +240,10 @@ class PromptDiffusionPipeline:
             if tuple(prompt_embeds.shape) != tuple(negative_prompt_embeds.shape):
                 raise ValueError("`prompt_embeds` and `negative_prompt_embeds` must have the same shape when passed directly, but"
                                  f" got: `prompt_embeds` {prompt_embeds.shape} != `negative_prompt_embeds` {negative_prompt_embeds.shape}.")
+        for name, emb in (("prompt_embeds", prompt_embeds), ("negative_prompt_embeds", negative_prompt_embeds)):
+            # any context length the engine takes per call (pd_sample_args.context_len)
+            if emb is not None and (len(emb.shape) != 3 or not 1 <= emb.shape[1] <= E.PD_MAX_CONTEXT_LEN):
+                raise ValueError(f"`{name}` must be [batch, L, dim] with 1 <= L <= {E.PD_MAX_CONTEXT_LEN}, got {tuple(emb.shape)}.")
         self.check_image(image, prompt, prompt_embeds)
         if len(image_pair) == 2:
             for im in image_pair:
@@ -364,10 +426,31 @@ class PromptDiffusionPipeline:
             raise ValueError(f"tokenizer must return ids of shape [{len(prompts)}, {L}], got {ids.shape}")
         return ids
 
+    def enable_long_prompts(self, windows: int = 3):
+        """Prompts longer than 77 tokens as the reference does them (cldm/hack.py, hack_everything -> _hacked_clip_forward): the
+        tokenizer runs without truncation and special tokens, the ids are split into `windows` runs of 75, each wrapped in BOS / EOS
+        and padded to 77 (split_long_prompt); the [B * windows, 77] ids go through the engine's CLIP in one text_encode call and
+        are viewed as a [B, 77 * windows, D] context.  Every prompt, the negative one included, gets `windows` windows.  Needs the
+        engine's own text encoder (a tokenizer, no text_encoder callable)."""
+        n = _window_count(windows)
+        if self.tokenizer is None or self.text_encoder != self._engine_text_encoder:
+            raise ValueError("long prompts are built by the engine's own text encoder: construct the pipeline with `tokenizer=` and "
+                             "without a `text_encoder` callable (or pass `prompt_embeds` of the long context)")
+        if n * self.engine.cfg.context_len > E.PD_MAX_CONTEXT_LEN:
+            raise ValueError(f"{n} windows of {self.engine.cfg.context_len} tokens exceed PD_MAX_CONTEXT_LEN {E.PD_MAX_CONTEXT_LEN}")
+        self._long_windows = n
+
+    def disable_long_prompts(self):
+        self._long_windows = 0
+
     def _engine_text_encoder(self, prompts: List[str], clip_skip: Optional[int] = None):
         if self.engine.text_weights_missing() != 0:
             raise ValueError("a string `prompt` needs the cond_stage_model.transformer.text_model.* weights in the engine "
                              "(or a text_encoder callable, or `prompt_embeds`)")
+        if self._long_windows:
+            L, n = self.engine.cfg.context_len, self._long_windows
+            z = self.engine.text_encode(tokenize_long(self.tokenizer, prompts, n, L), clip_skip=clip_skip or 0)
+            return z.reshape(len(prompts), n * L, z.shape[-1])     # '(b f) i c -> b (f i) c'
         return self.engine.text_encode(self._tokenize(prompts), clip_skip=clip_skip or 0)
 
     def _encode_text(self, prompts: List[str], clip_skip: Optional[int]):

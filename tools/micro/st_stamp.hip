@@ -48,10 +48,10 @@ int main() {
     float *coef, *vf, *vtl;
     unsigned long long* stamps;
     hipMalloc(&x, M * C * 2); hipMalloc(&h, M * C * 2); hipMalloc(&qk, M * C * 4); hipMalloc(&vt, M * C * 2); hipMalloc(&att, M * C * 2); hipMalloc(&out, M * C * 2);
-    hipMalloc(&wf, st_front_weight_bytes()); hipMalloc(&wt, st_tail_weight_bytes()); hipMalloc(&kv, st_tail_kv_bytes(B));
+    hipMalloc(&wf, st_front_weight_bytes()); hipMalloc(&wt, st_tail_weight_bytes()); hipMalloc(&kv, st_tail_kv_bytes(B, 77));
     hipMalloc(&coef, B * C * 2 * 4); hipMalloc(&vf, st_front_vec_floats() * 4); hipMalloc(&vtl, st_tail_vec_floats() * 4);
     hipMalloc(&stamps, 512 * 16 * 8);
-    fill(x, M * C * 2, 1); fill(att, M * C * 2, 2); fill(wf, st_front_weight_bytes(), 3); fill(wt, st_tail_weight_bytes(), 4); fill(kv, st_tail_kv_bytes(B), 5);
+    fill(x, M * C * 2, 1); fill(att, M * C * 2, 2); fill(wf, st_front_weight_bytes(), 3); fill(wt, st_tail_weight_bytes(), 4); fill(kv, st_tail_kv_bytes(B, 77), 5);
     std::vector<float> ones(B * C * 2, 0.5f), zeros(8192, 0.01f);
     hipMemcpy(coef, ones.data(), ones.size() * 4, hipMemcpyHostToDevice);
     hipMemcpy(vf, zeros.data(), st_front_vec_floats() * 4, hipMemcpyHostToDevice);
