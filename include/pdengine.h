@@ -236,6 +236,22 @@ int pd_vae_encode(pd_engine* e, const float* images, int32_t B, int32_t H, int32
 /* number of encoder tensors not loaded yet (0 when the encoder is not built) */
 int pd_vae_encoder_weights_missing(pd_engine* e);
 
+/* HED edge detector: the annotator that turns a photograph into the condition map of `query` / `pair` (apply_hed of the reference's
+ * demo; HEDdetector.__call__ and Network.forward, annotator/hed/__init__.py:71-114): a VGG-16 trunk of 13 conv3x3 + ReLU in five
+ * stages, one conv1x1 score head per stage, the five score maps upsampled bilinearly (align_corners = False) to the input size,
+ * a 5 -> 1 combine and a sigmoid.
+ * pd_hed_configure registers its 38 tensors on an existing engine (any pd_config; a registry group of its own, like
+ * pd_sd3_configure) under "hed." + Network's names: hed.netVggOne.0.weight .. hed.netCombine.0.bias.  Calling it again does nothing.
+ * pd_hed_detect: images [B, 3, H, W] fp32 NCHW, RGB in [0, 1] (the (D) pipeline's image convention); the BGR flip and the
+ * x * 255 - (104.00698793, 116.66876762, 122.67891434) of the reference happen inside, in fp32.  H and W multiples of 16 (four
+ * 2x2 max-pools; the reference's resize_image gives multiples of 64).  `images` and `out` live in `mem`.  Needs all hed.* weights
+ * and no active sampling session. */
+#define PD_HED_EDGE  0   /* sigmoid(netCombine(cat(5 upsampled side maps)))  -> [B, 1, H, W] in [0, 1] */
+#define PD_HED_SIDES 1   /* the five bilinearly upsampled score maps, pre-combine -> [B, 5, H, W]        */
+int pd_hed_configure(pd_engine* e);
+int pd_hed_weights_missing(pd_engine* e);    /* 0 when not configured */
+int pd_hed_detect(pd_engine* e, const float* images, int32_t B, int32_t H, int32_t W, int32_t mem, int32_t what, float* out);
+
 /* operator boundary: eps = apply_model(x, t, cond), cldm/cldm.py:369-382.
  *   x [Bf,in_ch,h,w], t [Bf] (int64), ctx [Bf,L,D], pair [Bf,hint_ch,8h,8w], query [Bf,q_ch,8h,8w],
  *   scales [13] or NULL.  eps_out [Bf,out_ch,h,w].  residuals_out (optional): the 13 scaled

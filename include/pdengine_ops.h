@@ -54,6 +54,15 @@ int pd_op_vae_downsample(pd_engine* e, const float* x, const float* w, const flo
  * (read for both halves of the batch); h_add / skip_add may be NULL; y [B, C_h + C_skip, H, W].  C_h, C_skip multiples of 4. */
 int pd_op_freeu_concat(pd_engine* e, const float* h, const float* h_add, const float* skip, const float* skip_add, int B, int C_h,
                        int C_skip, int H, int W, int skip_B, int skip_add_B, float s, float b, float* y);
+/* The per-stage tail of the HED edge detector (hed_stage_tail_kernel), in the engine's compute type: x [B, C, H, W] ->
+ * score [B, H, W] = conv1x1(x, w [C], bias[0]) with fp32 accumulation and, when pooled is non-NULL (H, W even),
+ * pooled [B, C, H/2, W/2] = max_pool2d(x, 2, 2).  C a multiple of 8. */
+int pd_op_hed_stage_tail(pd_engine* e, const float* x, const float* w, const float* bias, int B, int C, int H, int W, float* score,
+                         float* pooled);
+/* The end of the HED edge detector (hed_fuse_kernel), fp32 in every mode: scores = the five score maps back to back, map i
+ * [B, H >> i, W >> i] (H, W multiples of 16); cw [5], cb [1]; what PD_HED_EDGE: out [B, 1, H, W] = sigmoid(cb + sum_i cw[i] up_i),
+ * PD_HED_SIDES: out [B, 5, H, W] = up_i, the bilinear upsamples (align_corners = False) to H x W. */
+int pd_op_hed_fuse(pd_engine* e, const float* scores, const float* cw, const float* cb, int B, int H, int W, int what, float* out);
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,71 @@
+"""Annotators: photographs -> the condition maps Prompt-Diffusion takes as ``query`` and inside ``example_pair``.
+
+``HEDdetector`` is the reference's ``annotator.hed.HEDdetector`` with the network on the engine (``Engine.hed``: the VGG trunk,
+the five side outputs and their fusion are gfx950 kernels behind ``pd_hed_detect``); only the uint8 ends stay on the host.
+``HWC3`` and ``resize_image`` restate ``annotator/util.py`` in NumPy + PIL.  ``nms`` (cv2 blur / dilate) and the other annotators
+(MiDaS, UniFormer, Canny) are not built.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+
+def HWC3(x: np.ndarray) -> np.ndarray:
+    """uint8 HW, HW1, HW3 or HW4 -> HW3 (grey replicated; alpha composited over white), as annotator/util.py:9-25."""
+    if x.dtype != np.uint8:
+        raise ValueError("HWC3 expects uint8")
+    if x.ndim == 2:
+        x = x[:, :, None]
+    if x.ndim != 3 or x.shape[2] not in (1, 3, 4):
+        raise ValueError(f"HWC3 expects HW, HW1, HW3 or HW4, got {x.shape}")
+    C = x.shape[2]
+    if C == 3:
+        return x
+    if C == 1:
+        return np.concatenate([x, x, x], axis=2)
+    color = x[:, :, 0:3].astype(np.float32)
+    alpha = x[:, :, 3:4].astype(np.float32) / 255.0
+    y = color * alpha + 255.0 * (1.0 - alpha)
+    return y.clip(0, 255).astype(np.uint8)
+
+
+def resize_image(input_image: np.ndarray, resolution: int) -> np.ndarray:
+    """The short side to `resolution`, both sides rounded to multiples of 64 (annotator/util.py:28-38).  The target size is the
+    reference's; the pixels are not: the reference resamples with cv2 (INTER_LANCZOS4 up, INTER_AREA down), this uses PIL
+    (LANCZOS up, BOX down), whose kernels and rounding differ.  Parity of the resize is unpinned."""
+    from PIL import Image
+    H, W = float(input_image.shape[0]), float(input_image.shape[1])
+    k = float(resolution) / min(H, W)
+    H = int(np.round(H * k / 64.0)) * 64
+    W = int(np.round(W * k / 64.0)) * 64
+    img = Image.fromarray(input_image).resize((W, H), Image.LANCZOS if k > 1 else Image.BOX)
+    return np.asarray(img)
+
+
+def edge_to_uint8(edge: np.ndarray) -> np.ndarray:
+    """The reference's float -> uint8 step, ``(edge * 255.0).clip(0, 255).astype(np.uint8)`` (annotator/hed/__init__.py:113):
+    float32 arithmetic, truncation towards zero."""
+    return (np.asarray(edge, np.float32) * 255.0).clip(0, 255).astype(np.uint8)
+
+
+class HEDdetector:
+    """``annotator.hed.HEDdetector`` on an engine built with ``ModelConfig(hed=True)`` whose hed.* weights are loaded
+    (``Engine.load_hed_state_dict``)."""
+
+    def __init__(self, engine):
+        self.engine = engine
+
+    def detect(self, images) -> np.ndarray:
+        """Batched form: uint8 [B, H, W, 3] RGB -> uint8 [B, H, W]; H and W multiples of 16."""
+        x = np.asarray(images)
+        if x.dtype != np.uint8 or x.ndim != 4 or x.shape[3] != 3:
+            raise ValueError(f"detect expects uint8 [B, H, W, 3], got {x.dtype} {x.shape}")
+        # the reference divides the float32 image by 255 on its way in (:109-111); the engine flips RGB -> BGR itself
+        x = np.ascontiguousarray(x.transpose(0, 3, 1, 2)).astype(np.float32) / np.float32(255.0)
+        return edge_to_uint8(self.engine.hed(x, what="edge")[:, 0])
+
+    def __call__(self, input_image: np.ndarray) -> np.ndarray:
+        """uint8 HWC RGB -> uint8 HW, as the reference's ``__call__``."""
+        if np.asarray(input_image).ndim != 3:
+            raise ValueError("HEDdetector expects one HWC image")
+        return self.detect(np.asarray(input_image)[None])[0]

@@ -49,7 +49,7 @@ struct PatchGeom {
     static constexpr int SMEM = 2 * P_BYTES + 2 * W_TILE;
 };
 
-template <int P, int UPS, bool GN>
+template <int P, int UPS, bool GN, bool RELU = false>
 __global__ __launch_bounds__(NT) void conv3x3_patch_kernel(GemmParams p) {
     using G = PatchGeom<UPS>;
     constexpr bool F32 = prec_f32_storage(P);
@@ -305,7 +305,7 @@ __global__ __launch_bounds__(NT) void conv3x3_patch_kernel(GemmParams p) {
 #pragma unroll
             for (int n = 0; n < 5; ++n) {
                 const int gn = min(bn * BN + wn * 80 + n * 16 + fq * 4, p.N - 4);
-                acc[n][m] = epilogue4_value(p, gm, gn, sample, acc[n][m]);
+                acc[n][m] = epilogue4_value<false, RELU>(p, gm, gn, sample, acc[n][m]);
             }
         }
     }
@@ -326,11 +326,11 @@ __global__ __launch_bounds__(NT) void conv3x3_patch_kernel(GemmParams p) {
 
 constexpr int COEF_BYTES_MAX = 24 * 1024;   // [Cin <= 3072][2] floats behind the staging buffers
 
-template <int P, int UPS, bool GN>
+template <int P, int UPS, bool GN, bool RELU = false>
 int launch_patch(const GemmParams& p, hipStream_t s) {
     using G = PatchGeom<UPS>;
     static unsigned long long attr_done = 0;
-    auto kfn = conv3x3_patch_kernel<P, UPS, GN>;
+    auto kfn = conv3x3_patch_kernel<P, UPS, GN, RELU>;
     const int smem = G::SMEM + (GN ? COEF_BYTES_MAX : 0);
     if (GN && p.Cin * 8 > COEF_BYTES_MAX) return 1;
     if (ensure_dyn_smem(reinterpret_cast<const void*>(kfn), smem, &attr_done)) return 1;
@@ -349,6 +349,7 @@ int conv_patch_tiles(const GemmParams& p, int prec) {
     if (p.Hout % TP || p.Wout % TP || p.Cin % bke || p.K != 9 * p.Cin || p.act == 2 || p.vt_begin < p.N) return 0;
     if (p.a_dt != (prec_f32_storage(prec) ? (int)DT_F32 : prec) || p.a_silu) return 0;
     if (p.Cin * 8 > 24 * 1024) return 0;
+    if (p.act == 5 && (p.ups || p.gn_coef)) return 0;   // ACT_RELU is instantiated for the plain conv only
     if ((p.Hin << p.ups) != p.Hout || (p.Win << p.ups) != p.Wout) return 0;
     return (p.M / (p.Hout * p.Wout)) * (p.Hout / TP) * (p.Wout / TP) * ((p.N + BN - 1) / BN);
 }
@@ -356,6 +357,7 @@ int conv_patch_tiles(const GemmParams& p, int prec) {
 namespace {
 template <int P>
 int launch_patch_prec(const GemmParams& p, hipStream_t s) {
+    if (p.act == 5) return (p.gn_coef || p.ups) ? 1 : launch_patch<P, 0, false, true>(p, s);   // ACT_RELU: the plain conv only
     if (p.gn_coef) {
         if (p.ups) return 1;   // GroupNorm never feeds an upsampling conv in this network
         return launch_patch<P, 0, true>(p, s);

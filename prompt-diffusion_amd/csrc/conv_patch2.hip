@@ -48,7 +48,7 @@ struct Geom2 {
     static constexpr int SMEM = 2 * P_BYTES + NWB * W_TILE;
 };
 
-template <int P, int UPS>
+template <int P, int UPS, bool RELU = false>
 __global__ __launch_bounds__(NT) void conv3x3_patch2_kernel(GemmParams p) {
     using G = Geom2<UPS>;
     constexpr int PW = G::PW;
@@ -312,7 +312,7 @@ __global__ __launch_bounds__(NT) void conv3x3_patch2_kernel(GemmParams p) {
 #pragma unroll
             for (int n = 0; n < 10; ++n) {
                 const int gn = min(bn * BN + n * 16 + fq * 4, p.N - 4);
-                acc[n][m] = epilogue4_value(p, gm, gn, sample, acc[n][m]);
+                acc[n][m] = epilogue4_value<false, RELU>(p, gm, gn, sample, acc[n][m]);
             }
         }
     }
@@ -331,11 +331,11 @@ __global__ __launch_bounds__(NT) void conv3x3_patch2_kernel(GemmParams p) {
     }
 }
 
-template <int P, int UPS>
+template <int P, int UPS, bool RELU = false>
 int launch_patch2(const GemmParams& p, hipStream_t s) {
     using G = Geom2<UPS>;
     static unsigned long long attr_done = 0;
-    auto kfn = conv3x3_patch2_kernel<P, UPS>;
+    auto kfn = conv3x3_patch2_kernel<P, UPS, RELU>;
     if (ensure_dyn_smem(reinterpret_cast<const void*>(kfn), G::SMEM, &attr_done)) return 1;
     const int mtiles = (p.M / (p.Hout * p.Wout)) * (p.Hout / TP) * (p.Wout / TP), ntiles = (p.N + BN - 1) / BN;
     hipLaunchKernelGGL(kfn, dim3(mtiles * ntiles, p.splitk > 1 ? p.splitk : 1), dim3(NT), G::SMEM, s, p);
@@ -348,6 +348,10 @@ int launch_patch2(const GemmParams& p, hipStream_t s) {
 // same eligibility as conv_patch_tiles(); 2-byte compute types only, no fused GroupNorm
 int launch_conv_patch2(const GemmParams& p, int prec, hipStream_t s) {
     if (p.gn_coef || (prec != DT_BF16 && prec != DT_F16)) return 1;
+    if (p.act == 5) {   // ACT_RELU: the plain conv only
+        if (p.ups) return 1;
+        return prec == DT_F16 ? launch_patch2<DT_F16, 0, true>(p, s) : launch_patch2<DT_BF16, 0, true>(p, s);
+    }
     if (prec == DT_F16) return p.ups ? launch_patch2<DT_F16, 1>(p, s) : launch_patch2<DT_F16, 0>(p, s);
     return p.ups ? launch_patch2<DT_BF16, 1>(p, s) : launch_patch2<DT_BF16, 0>(p, s);
 }

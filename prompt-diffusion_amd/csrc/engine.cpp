@@ -464,7 +464,9 @@ int pd_engine::read_param(const Param& p, float* out) {
                 out[half + j] = buf[(size_t)(j / 80) * 160 + 80 + j % 80];
             }
         } else {
-            HIP_OK(hipMemcpy(out, p.vdst, (size_t)p.shape[0] * 4, hipMemcpyDeviceToHost));
+            size_t n = 1;   // (HED's score heads are vectors under a [1, C, 1, 1] checkpoint shape)
+            for (int64_t d : p.shape) n *= (size_t)d;
+            HIP_OK(hipMemcpy(out, p.vdst, n * 4, hipMemcpyDeviceToHost));
         }
         return 0;
     }

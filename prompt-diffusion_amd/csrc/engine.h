@@ -171,6 +171,16 @@ struct VaeEncW {
     int top = 0;
 };
 
+// HED edge detector (pd_hed_configure, hed.cpp): annotator/hed/__init__.py Network -- the 13 conv3x3 + ReLU of the VGG-16 trunk in five
+// stages (2, 2, 3, 3, 3), one conv1x1 C -> 1 score head per stage and the 5 -> 1 combine; heads and combine are fp32 vectors
+struct HedW {
+    bool built = false;
+    ConvW conv[13];
+    float* score_w[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    float* score_b[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    float *comb_w = nullptr, *comb_b = nullptr;
+};
+
 // CLIP text transformer
 struct TextLayerW {
     float *ln1_g = nullptr, *ln1_b = nullptr, *ln2_g = nullptr, *ln2_b = nullptr;
@@ -223,7 +233,7 @@ struct Param {
     bool conv = false;  // OIHW source
     char init = 'w';    // recipe class for pd_init_random_weights: w, b, g(amma), e(beta)
     bool loaded = false;
-    int group = 0;      // 0: UNet + ControlNet (needed to sample), 1: VAE decoder, 2: text transformer, 3: SD3 networks, 4: VAE encoder
+    int group = 0;      // 0: UNet + ControlNet (needed to sample), 1: VAE decoder, 2: text transformer, 3: SD3 networks, 4: VAE encoder, 5: HED
 };
 
 struct Act {
@@ -469,6 +479,11 @@ struct pd_engine {
     // pd_vae_decode / pd_vae_encode: `sizing` (a dry pass of the forward) measures the workspace, which is the ControlNet
     // context's (arena2, idle outside a sampling step) grown to that plus io_bytes if needed; then `run` enqueues for real
     int vae_in_workspace(size_t io_bytes, const std::function<int()>& sizing, const std::function<int()>& run);
+
+    // HED edge detector (hed.cpp): registered by pd_hed_configure, runs in the same workspace as the first stage
+    HedW hed;
+    void build_hed();
+    int hed_forward(const float* images_dev, int B, int H, int W, int what, float* out_dev);
 
     // SD3 / MMDiT path (sd3.cpp)
     pd_sd3_config sd3{};

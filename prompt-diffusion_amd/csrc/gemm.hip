@@ -39,7 +39,7 @@ __device__ __forceinline__ int swz(int row, int chunk) { return (row * BKB) + ((
 // are contiguous).  AF32: 2-byte compute with an fp32 A source (converted while staging; only meaningful when P != DT_F32).
 // GG: the GEGLU epilogue (act == 2) instead of the plain one -- a wave's WTN columns are whole [80 x | 80 gate] blocks.
 // MM: the MMDiT epilogue extras (pd_mma.h epilogue4<true>), linear layers of the SD3 path only.
-template <int P, int BM, int BN, int WM, int WN, bool CONV, bool AF32, bool GG = false, bool MM = false>
+template <int P, int BM, int BN, int WM, int WN, bool CONV, bool AF32, bool GG = false, bool MM = false, bool RELU = false>
 __global__ __launch_bounds__(WM * WN * 64, (BM == 128 && WM * WN == 8) ? 4 : 2) void igemm_kernel(GemmParams p) {
     constexpr bool F32 = prec_f32_storage(P);
     // register prefetch depth: two K steps ahead (two named staging sets) unless the fp32->bf16 staging
@@ -416,7 +416,7 @@ __global__ __launch_bounds__(WM * WN * 64, (BM == 128 && WM * WN == 8) ? 4 : 2) 
 #pragma unroll
             for (int n = 0; n < NT; ++n) {
                 const int gn = min(bn * BN + wn * WTN + n * 16 + fq * 4, p.N - 4);
-                acc[n][m] = epilogue4_value<MM>(p, gm, gn, sample, acc[n][m], ln_mean, ln_rstd);
+                acc[n][m] = epilogue4_value<MM, RELU>(p, gm, gn, sample, acc[n][m], ln_mean, ln_rstd);
             }
         }
     }
@@ -467,7 +467,7 @@ __global__ __launch_bounds__(WM * WN * 64, (BM == 128 && WM * WN == 8) ? 4 : 2) 
                         ln_rstd = t.y;
                     }
                 }
-                v = epilogue4<MM>(p, gm, gn, sample, tok, v, ln_mean, ln_rstd);
+                v = epilogue4<MM, RELU>(p, gm, gn, sample, tok, v, ln_mean, ln_rstd);
             }
             if constexpr (LNF) {
                 if (p.stats_out) {
@@ -501,18 +501,19 @@ __global__ __launch_bounds__(256) void splitk_finalize_kernel(GemmParams p) {
         const int sample = gm / p.rows_per_sample;
         float ln_mean = 0.f, ln_rstd = 0.f;
         if (p.ln_stats) ln_row_stats(p, gm, ln_mean, ln_rstd);
-        epilogue4<true>(p, gm, gn, sample, gm - sample * p.rows_per_sample, v, ln_mean, ln_rstd);
+        if (p.act == 5) epilogue4<true, true>(p, gm, gn, sample, gm - sample * p.rows_per_sample, v, ln_mean, ln_rstd);   // ACT_RELU
+        else epilogue4<true>(p, gm, gn, sample, gm - sample * p.rows_per_sample, v, ln_mean, ln_rstd);
     }
 }
 
-template <int P, int BM, int BN, int WM, int WN, bool CONV, bool AF32, bool GG = false, bool MM = false>
+template <int P, int BM, int BN, int WM, int WN, bool CONV, bool AF32, bool GG = false, bool MM = false, bool RELU = false>
 int launch_one(const GemmParams& p, hipStream_t s, hipEvent_t mid, int* parts) {
     constexpr int NTHREADS = WM * WN * 64;
     constexpr int SMEM_BYTES = 2 * (BM + BN) * BKB + ((GG || MM) ? 0 : BM * 8);   // staging buffers + {mean, rstd} of the block's rows (LayerNorm fold)
     static unsigned long long attr_done = 0;
     const int mtiles = (p.M + BM - 1) / BM, ntiles = (p.N + BN - 1) / BN;
     if (parts) { *parts = ntiles * WN; return 0; }   // gemm_stats_parts: which tile, no launch
-    auto kfn = igemm_kernel<P, BM, BN, WM, WN, CONV, AF32, GG, MM>;
+    auto kfn = igemm_kernel<P, BM, BN, WM, WN, CONV, AF32, GG, MM, RELU>;
     if (ensure_dyn_smem(reinterpret_cast<const void*>(kfn), SMEM_BYTES, &attr_done)) return 1;
     if (p.stats_out && p.stats_parts != ntiles * WN) return 1;   // the statistics rows were sized for another tile
     dim3 grid(mtiles * ntiles, p.splitk > 1 ? p.splitk : 1);
@@ -560,6 +561,11 @@ int launch_prec(const GemmParams& p, hipStream_t s, hipEvent_t mid, int* parts) 
     // 0: 128x160, 1: 256x160, 2: 128x160 on 8 waves, 3: 256x320; split-K launches: 128x160, or 256x160 when the engine asks for it
     // (plain slab stores work from any tile; the in-kernel finalize of option splitk_fused exists for the 128x160 tile only)
     const int tile = p.splitk == 1 ? p.big_tile : ((p.big_tile == 1 && !p.tile_cnt) ? 1 : 0);
+    if (p.act == 5) {   // ACT_RELU: conv3x3 over operands of the storage type, in instantiations of its own
+        if (!conv || af32 || p.ln_stats || p.stats_out) return 1;
+        if (tile == 1 || tile == 3) return launch_one<P, 256, 160, 4, 2, true, false, false, false, true>(p, s, mid, parts);
+        return launch_one<P, 128, 160, 2, 2, true, false, false, false, true>(p, s, mid, parts);
+    }
     if (p.act == 2) {
         if (conv || af32 || p.ln_stats || p.stats_out) return 1;
         // 256 x 320 on 4 x 2 waves (wave tile 64 x 160 = one GEGLU block): 14 fragment reads per 40 MFMAs.  Round 1 ran it on

@@ -360,4 +360,58 @@ int pd_op_time_embed(pd_engine* e, int net, const int64_t* t, int n, float* temb
     HIP_OK(hipMemcpy(emb, c.p, (size_t)n * td * 4, hipMemcpyDeviceToHost));
     return 0;
 }
+
+// HED stage tail (launch_hed_stage_tail) in the compute type: NCHW fp32 in, score [B, H, W] and pooled NCHW fp32 out
+int pd_op_hed_stage_tail(pd_engine* e, const float* x, const float* w, const float* bias, int B, int C, int H, int W, float* score,
+                         float* pooled) {
+    if (!e || !x || !w || !bias || !score) { pd_set_error("null argument"); return 1; }
+    if (B < 1 || C < 8 || C % 8 || H < 1 || W < 1 || (pooled && ((H | W) & 1))) {
+        pd_set_error("pd_op_hed_stage_tail: need B, H, W >= 1, C a positive multiple of 8, and even H, W with a pooled output");
+        return 1;
+    }
+    HIP_OK(hipSetDevice(e->device));
+    const int dt = e->T;
+    const size_t px = (size_t)B * H * W;
+    DevBuf dx(px * C * dt_size(dt)), dw((size_t)(C + 4) * 4), db(16), ds(px * 4), dp(px / 4 * C * dt_size(dt));
+    if (!dx.p || !dw.p || !db.p || !ds.p || !dp.p) { pd_set_error("allocation failed"); return 1; }
+    PD_TRY(to_dev_nhwc(e, x, dx.p, dt, B, C, H, W, C));
+    HIP_OK(hipMemcpy(dw.p, w, (size_t)C * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(db.p, bias, 4, hipMemcpyHostToDevice));
+    if (launch_hed_stage_tail(dx.p, dt, reinterpret_cast<const float*>(dw.p), reinterpret_cast<const float*>(db.p), reinterpret_cast<float*>(ds.p),
+                              pooled ? dp.p : nullptr, B, H, W, C, e->stream)) {
+        pd_set_error("pd_op_hed_stage_tail: launch failed");
+        return 1;
+    }
+    HIP_OK(hipStreamSynchronize(e->stream));
+    HIP_OK(hipMemcpy(score, ds.p, px * 4, hipMemcpyDeviceToHost));
+    return pooled ? from_dev_nhwc(e, dp.p, dt, pooled, B, C, H / 2, W / 2, C) : 0;
+}
+
+// HED fuse (launch_hed_fuse): fp32 score maps in, fp32 NCHW out
+int pd_op_hed_fuse(pd_engine* e, const float* scores, const float* cw, const float* cb, int B, int H, int W, int what, float* out) {
+    if (!e || !scores || !cw || !cb || !out) { pd_set_error("null argument"); return 1; }
+    if (B < 1 || H < 16 || W < 16 || H % 16 || W % 16 || (what != PD_HED_EDGE && what != PD_HED_SIDES)) {
+        pd_set_error("pd_op_hed_fuse: need B >= 1, H and W positive multiples of 16, what PD_HED_EDGE / PD_HED_SIDES");
+        return 1;
+    }
+    HIP_OK(hipSetDevice(e->device));
+    size_t off[6] = {0};
+    for (int i = 0; i < 5; ++i) off[i + 1] = off[i] + (size_t)B * (H >> i) * (W >> i);
+    const size_t n_out = (size_t)B * (what == PD_HED_SIDES ? 5 : 1) * H * W;
+    DevBuf ds(off[5] * 4), dc(32), dout(n_out * 4);
+    if (!ds.p || !dc.p || !dout.p) { pd_set_error("allocation failed"); return 1; }
+    HIP_OK(hipMemcpy(ds.p, scores, off[5] * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(dc.p, cw, 5 * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(reinterpret_cast<float*>(dc.p) + 5, cb, 4, hipMemcpyHostToDevice));
+    const float* maps[5];
+    for (int i = 0; i < 5; ++i) maps[i] = reinterpret_cast<const float*>(ds.p) + off[i];
+    if (launch_hed_fuse(maps, reinterpret_cast<const float*>(dc.p), reinterpret_cast<const float*>(dc.p) + 5, reinterpret_cast<float*>(dout.p), B, H,
+                        W, what, e->stream)) {
+        pd_set_error("pd_op_hed_fuse: launch failed");
+        return 1;
+    }
+    HIP_OK(hipStreamSynchronize(e->stream));
+    HIP_OK(hipMemcpy(out, dout.p, n_out * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
 }  // extern "C"

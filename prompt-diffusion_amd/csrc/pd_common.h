@@ -145,7 +145,10 @@ static inline int ensure_dyn_smem(const void* fn, int bytes, unsigned long long*
 // ---------------------------------------------------------------------------------------------
 // Implicit-GEMM convolution / linear:  C[M,N] = epilogue( A_gather[M,K] x W[N,K]^T )
 // ---------------------------------------------------------------------------------------------
-enum Activation { ACT_NONE = 0, ACT_SILU = 1, ACT_GEGLU = 2, ACT_QUICK_GELU = 3, ACT_TANH_GELU = 4 };   // GemmParams::act (the kernels compare against the values)
+// GemmParams::act (the kernels compare against the values).  ACT_RELU is compiled into instantiations of its own (pd_mma.h epilogue4_value<MM, RELU>:
+// plain conv3x3 on igemm / patch1 / patch2, and the split-K finalize pass), so no other launch carries a branch for it; the ring GEMM, the 4-wave
+// patch conv and every linear layer refuse it
+enum Activation { ACT_NONE = 0, ACT_SILU = 1, ACT_GEGLU = 2, ACT_QUICK_GELU = 3, ACT_TANH_GELU = 4, ACT_RELU = 5 };
 struct GemmParams {
     const void* A;        // activations, NHWC (conv) or [M, lda] rows (linear)
     const void* W;        // weights [Nw][Kpad] in the compute type, K-contiguous (taps x Cin)
@@ -163,7 +166,7 @@ struct GemmParams {
     int Hin, Win, Hout, Wout, stride, ups;  // conv geometry; ups=1: nearest x2 upsample fused in the gather
     int rows_per_sample;  // Hout*Wout (conv) or tokens per sample (linear)
     int rowvec_stride;    // elements between samples in rowvec (0: one row for all)
-    int act;              // Activation: 0 none, 1 SiLU, 2 GEGLU (weights pre-interleaved in 80+80 blocks), 3 quick-GELU, 4 tanh-GELU
+    int act;              // Activation: 0 none, 1 SiLU, 2 GEGLU (weights pre-interleaved in 80+80 blocks), 3 quick-GELU, 4 tanh-GELU, 5 ReLU
     int a_silu;           // apply SiLU to A on load (emb_layers)
     float out_scale;      // applied to (acc + bias [+ rowvec]) before the residual
     int vt_begin, vt_ld;  // see VT
@@ -358,6 +361,17 @@ int launch_lora_merge(int dt, void* W, const void* W0, int rows, int row_off, in
 // noise null with PD_VAE_SAMPLE: the seeded normals at (PD_RNG_VAE, draw 0) from rng_state
 int launch_vae_posterior(const void* mom, int mom_dt, int Cpad, const float* noise, float* out, int B, int z, int HW, int what, float scale,
                          hipStream_t s, const uint32_t* rng_state = nullptr);
+// hed.hip: the element-wise kernels of the HED edge detector (hed.cpp)
+// images [B][3][H][W] fp32 RGB in [0, 1] -> out [B][H][W][Cpad] in out_dt: channel c < 3 = image channel 2 - c (BGR) * 255 - the VGG mean of
+// channel c, in fp32, rounded once; channels >= 3 zero.  Cpad a multiple of 4
+int launch_hed_upload(const float* in, void* out, int out_dt, int B, int H, int W, int Cpad, hipStream_t s);
+// x [B][H][W][C] in dt (C a multiple of 16 bytes) -> score [B][H][W] fp32 = x . sw + sb[0] (fp32 accumulation) and, when pooled is non-null
+// (H, W even), pooled [B][H/2][W/2][C] in dt = max_pool2d(x, 2, 2); x is read once
+int launch_hed_stage_tail(const void* x, int dt, const float* sw, const float* sb, float* score, void* pooled, int B, int H, int W, int C,
+                          hipStream_t s);
+// scores[i] [B][H >> i][W >> i] fp32 (H, W multiples of 16), cw [5], cb [1] -> what 0: out [B][1][H][W] = sigmoid(cb + sum_i cw[i] up_i),
+// what 1: out [B][5][H][W] = up_i; up_i the bilinear upsample (align_corners = False) of map i by 2^i
+int launch_hed_fuse(const float* const scores[5], const float* cw, const float* cb, float* out, int B, int H, int W, int what, hipStream_t s);
 // sd3_kernels.hip: element-wise pieces of the MMDiT path
 // y_dt == DT_FP8: y holds e4m3 bytes and y_scale[row] the row's scale (max |value| / 448); add: x <- x + add first (written back)
 int launch_adaln(const void* x, int x_dt, void* y, int y_dt, const float* mod, int mod_stride, int shift_off, int scale_off, int rows,

@@ -152,7 +152,8 @@ __device__ __forceinline__ f32x4 ln_apply4(const GemmParams& p, int gn, f32x4 v,
 // ring GEMM: 23 k of a block's 53 k cycles, 13 k once the reads went first).
 // MM: the MMDiT extras (tanh-GELU, per-sample gate, joint-buffer row remap) -- compile-time, because even as untaken branches
 // they push the 256 x 320 tile and the wave-specialised patch conv (both at the VGPR cap) into scratch.
-template <bool MM = false>
+// RELU: ACT_RELU -- compile-time as well, in instantiations of their own (conv3x3 only), so that no other launch carries the branch.
+template <bool MM = false, bool RELU = false>
 __device__ __forceinline__ f32x4 epilogue4_value(const GemmParams& p, int gm, int gn, int sample, f32x4 v, float ln_mean = 0.f, float ln_rstd = 0.f) {
     if constexpr (MM) {
         if (p.a_scale) {   // PREC_FP8: per-token x per-channel operand scales
@@ -171,6 +172,10 @@ __device__ __forceinline__ f32x4 epilogue4_value(const GemmParams& p, int gm, in
     } else if (p.act == 3) {   // quick_gelu: x * sigmoid(1.702 x)  (CLIP MLP)
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = v[j] / (1.0f + __expf(-1.702f * v[j]));
+    }
+    if constexpr (RELU) {   // ACT_RELU (HED's VGG trunk)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
     }
     if constexpr (MM) {
         if (p.act == 4) {   // tanh-GELU (MMDiT feed-forward): 0.5 x (1 + tanh(u)) = x / (1 + exp(-2u))
@@ -223,10 +228,10 @@ __device__ __forceinline__ void epilogue4_store(const GemmParams& p, int gm, int
     }
 }
 // both halves for one group (the split-K finalize pass: one group per thread)
-template <bool MM = false>
+template <bool MM = false, bool RELU = false>
 __device__ __forceinline__ f32x4 epilogue4(const GemmParams& p, int gm, int gn, int sample, int tok, f32x4 v, float ln_mean = 0.f,
                                            float ln_rstd = 0.f) {
-    v = epilogue4_value<MM>(p, gm, gn, sample, v, ln_mean, ln_rstd);
+    v = epilogue4_value<MM, RELU>(p, gm, gn, sample, v, ln_mean, ln_rstd);
     epilogue4_store<MM>(p, gm, gn, sample, tok, v);
     return v;
 }

@@ -13,7 +13,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .weights import ModelConfig, SD15
+from .weights import ModelConfig, SD15, hed_key
 
 PD_PREC_BF16, PD_PREC_F32, PD_PREC_F16, PD_PREC_F16X2 = 0, 1, 2, 3
 PRECISIONS = {"bf16": PD_PREC_BF16, "f32": PD_PREC_F32, "fp32": PD_PREC_F32, "f16": PD_PREC_F16, "fp16": PD_PREC_F16,
@@ -23,6 +23,8 @@ PD_DT_F32, PD_DT_F16, PD_DT_BF16 = 0, 1, 2
 PD_GET_LATENTS, PD_GET_PRED_X0, PD_GET_EPS = 0, 1, 2
 PD_VAE_MEAN, PD_VAE_SAMPLE, PD_VAE_MOMENTS = 0, 1, 2
 VAE_ENCODE_MODES = {"mean": PD_VAE_MEAN, "sample": PD_VAE_SAMPLE, "moments": PD_VAE_MOMENTS}
+PD_HED_EDGE, PD_HED_SIDES = 0, 1
+HED_OUTPUTS = {"edge": PD_HED_EDGE, "sides": PD_HED_SIDES}
 PD_MAX_LEVELS = 8
 PD_NUM_CONTROL = 13
 PD_MAX_CONTEXT_LEN = 1024
@@ -147,6 +149,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.pd_vae_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
     lib.pd_vae_encode.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p]
     lib.pd_vae_encoder_weights_missing.argtypes = [C.c_void_p]
+    lib.pd_hed_configure.argtypes = [C.c_void_p]
+    lib.pd_hed_weights_missing.argtypes = [C.c_void_p]
+    lib.pd_hed_detect.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p]
     lib.pd_text_weights_missing.argtypes = [C.c_void_p]
     lib.pd_text_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     lib.pd_text_encode_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
@@ -200,6 +205,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.pd_op_spatial_transformer_ctx.argtypes = [C.c_void_p, C.c_char_p, fp, fp] + [C.c_int] * 4 + [fp]
     lib.pd_op_time_embed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, fp, fp]
     lib.pd_op_vae_downsample.argtypes = [C.c_void_p, fp, fp, fp] + [C.c_int] * 4 + [fp]
+    lib.pd_op_hed_stage_tail.argtypes = [C.c_void_p, fp, fp, fp] + [C.c_int] * 4 + [fp, fp]
+    lib.pd_op_hed_fuse.argtypes = [C.c_void_p, fp, fp, fp] + [C.c_int] * 4 + [fp]
     lib.pd_read_weights.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
     lib.pd_lora_add.argtypes = [C.c_void_p, C.c_int32, C.c_char_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                 C.POINTER(C.c_int64), C.c_int32]
@@ -232,6 +239,7 @@ EXPORTS = [
     "pd_op_timestep_embedding_i", "pd_op_timestep_embedding_f", "pd_op_vae_downsample", "pd_read_weights", "pd_lora_add", "pd_lora_set_scales", "pd_lora_remove",
     "pd_set_freeu", "pd_get_freeu", "pd_op_freeu_concat",
     "pd_philox4x32_10", "pd_set_rng", "pd_get_rng", "pd_randn",
+    "pd_hed_configure", "pd_hed_weights_missing", "pd_hed_detect", "pd_op_hed_stage_tail", "pd_op_hed_fuse",
 ]
 
 
@@ -411,6 +419,8 @@ class Engine:
         self._h = C.c_void_p()
         c = make_config(cfg, self.precision, stream_f32)
         self._check(self.lib.pd_engine_create(C.byref(c), device, C.byref(self._h)))
+        if getattr(cfg, "hed", False):
+            self._check(self.lib.pd_hed_configure(self._h))
         self._keep: List[_Buf] = []
         self._rng_set = False    # the caller has chosen a seed (set_rng): draws nobody supplied may come from the engine
 
@@ -625,6 +635,45 @@ class Engine:
             raise ValueError(f"noise must be [{B}, {z}, {H // 8}, {W // 8}]")
         self._order_after_torch(b.mem)
         self._check(self.lib.pd_vae_encode(self._h, b.ptr, B, H, W, b.mem, what, nb.ptr if what == PD_VAE_SAMPLE else None, op))
+        return out
+
+    # ------------------------------------------------------------------ HED edge detector (pd_hed_*)
+    def hed_weights_missing(self) -> int:
+        return int(self.lib.pd_hed_weights_missing(self._h))
+
+    def load_hed_state_dict(self, sd) -> None:
+        """Load the HED ``Network``'s 38 tensors from the checkpoint's ``module...`` keys (network-bsds500.pth), ``Network``'s own
+        ``net...`` keys or the registry's ``hed.net...`` names; an unknown key raises PdError."""
+        it = sd.items() if isinstance(sd, dict) else sd
+        for name, arr in it:
+            try:
+                key = hed_key(name)
+            except KeyError as ex:
+                raise PdError(f"load_hed_state_dict: {ex.args[0]}") from None
+            self.load_tensor(key, arr)
+
+    def hed(self, images, what: str = "edge"):
+        """HED edge detection (annotator/hed/__init__.py: HEDdetector.__call__ + Network.forward) on the device: images
+        [B,3,H,W] float32 RGB in [0, 1], H and W multiples of 16 ->
+          "edge":  sigmoid(netCombine(...)) in [0, 1]                          [B,1,H,W]
+          "sides": the five score maps, upsampled to H x W, before netCombine  [B,5,H,W]
+        NumPy in, NumPy out; CUDA tensor in, CUDA tensor out.  Needs ModelConfig(hed=True) and the hed.* weights."""
+        if what not in HED_OUTPUTS:
+            raise ValueError(f"what must be one of {sorted(HED_OUTPUTS)}")
+        b = _Buf(images)
+        if b.owner.ndim != 4 or b.owner.shape[1] != 3:
+            raise ValueError(f"images must be [B, 3, H, W], got {tuple(b.owner.shape)}")
+        B, _, H, W = b.owner.shape
+        shape = (B, 5 if what == "sides" else 1, H, W)
+        if b.mem == PD_MEM_DEVICE:
+            import torch
+            out = torch.empty(shape, dtype=torch.float32, device=b.owner.device)
+            op = out.data_ptr()
+        else:
+            out = np.empty(shape, np.float32)
+            op = out.ctypes.data
+        self._order_after_torch(b.mem)
+        self._check(self.lib.pd_hed_detect(self._h, b.ptr, B, H, W, b.mem, HED_OUTPUTS[what], op))
         return out
 
     def text_weights_missing(self) -> int:
@@ -1075,6 +1124,41 @@ class Engine:
         self._check(self.lib.pd_op_vae_downsample(self._h, x.ctypes.data, w.ctypes.data, None if bb is None else bb.ctypes.data,
                                                   B, Cc, H, W, y.ctypes.data))
         return y
+
+    def op_hed_stage_tail(self, x, w, b, pool: bool = True):
+        """One stage tail of the HED detector (hed_stage_tail_kernel) in the compute type: x [B,C,H,W], w [C] (or [1,C,1,1]), b [1] ->
+        (score [B,H,W], max_pool2d(x, 2, 2) [B,C,H//2,W//2] or None)."""
+        x = np.ascontiguousarray(x, np.float32)
+        w = np.ascontiguousarray(np.asarray(w, np.float32).reshape(-1))
+        bb = np.ascontiguousarray(np.asarray(b, np.float32).reshape(-1))
+        B, Cc, H, W = x.shape
+        if w.size != Cc or bb.size != 1:
+            raise ValueError("w must hold C values and b one")
+        score = np.empty((B, H, W), np.float32)
+        pooled = np.empty((B, Cc, H // 2, W // 2), np.float32) if pool else None
+        self._check(self.lib.pd_op_hed_stage_tail(self._h, x.ctypes.data, w.ctypes.data, bb.ctypes.data, B, Cc, H, W, score.ctypes.data,
+                                                  None if pooled is None else pooled.ctypes.data))
+        return score, pooled
+
+    def op_hed_fuse(self, scores, cw, cb, what: str = "edge"):
+        """The end of the HED detector (hed_fuse_kernel): scores = five maps [B,H>>i,W>>i] (or [B,1,H>>i,W>>i]), cw [5], cb [1] ->
+        "edge" [B,1,H,W] = sigmoid(cb + sum_i cw[i] up_i) or "sides" [B,5,H,W] = the bilinear upsamples up_i."""
+        maps = [np.ascontiguousarray(s, np.float32) for s in scores]
+        if len(maps) != 5:
+            raise ValueError("five score maps expected")
+        B, H, W = maps[0].shape[0], maps[0].shape[-2], maps[0].shape[-1]
+        for i, m in enumerate(maps):
+            if m.size != B * (H >> i) * (W >> i) or m.shape[-1] != W >> i:
+                raise ValueError(f"score map {i} must be [{B}, {H >> i}, {W >> i}]")
+        flat = np.ascontiguousarray(np.concatenate([m.reshape(-1) for m in maps]))
+        cw = np.ascontiguousarray(np.asarray(cw, np.float32).reshape(-1))
+        cb = np.ascontiguousarray(np.asarray(cb, np.float32).reshape(-1))
+        if cw.size != 5 or cb.size != 1:
+            raise ValueError("cw must hold 5 values and cb one")
+        out = np.empty((B, 5 if what == "sides" else 1, H, W), np.float32)
+        self._check(self.lib.pd_op_hed_fuse(self._h, flat.ctypes.data, cw.ctypes.data, cb.ctypes.data, B, H, W, HED_OUTPUTS[what],
+                                            out.ctypes.data))
+        return out
 
     def op_freeu_concat(self, h, skip, s: float, b: float, h_add=None, skip_add=None):
         """FreeU's skip concat of a decoder block (freeu_concat_kernel) in the residual-stream type: h, h_add [B, C_h, H, W];

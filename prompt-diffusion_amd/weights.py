@@ -62,6 +62,9 @@ class ModelConfig:
     text_heads: int = 12
     text_ff: int = 3072
 
+    # HED edge detector (annotator/hed/__init__.py): opt-in, fixed architecture, registered through pd_hed_configure
+    hed: bool = False
+
     @property
     def time_embed_dim(self) -> int:
         return 4 * self.model_channels
@@ -336,6 +339,58 @@ def vae_encoder_spec(cfg: ModelConfig, prefix: str = VAE_PREFIX) -> List[Spec]:
 
 def synth_vae_encoder_state_dict(cfg: ModelConfig, seed: int = 1234) -> Dict[str, np.ndarray]:
     return {n: synth_tensor(n, s, k, seed) for n, s, k in vae_encoder_spec(cfg)}
+
+
+HED_PREFIX = "hed."
+_HED_STAGES = (("One", 64, 2), ("Two", 128, 2), ("Thr", 256, 3), ("Fou", 512, 3), ("Fiv", 512, 3))
+
+
+def hed_spec(prefix: str = HED_PREFIX) -> List[Spec]:
+    """The 38 tensors of the HED ``Network`` (annotator/hed/__init__.py:13-67) in its state-dict order, under ``hed.`` + the
+    module's own names: the VGG-16 trunk (13 conv3x3; ``Sequential`` indices 0, 2 in stage one and 1, 3(, 5) behind the
+    MaxPool2d of the later stages), five conv1x1 score heads, the 5 -> 1 combine."""
+    out: List[Spec] = []
+    cin = 3
+    for s, (tag, width, n) in enumerate(_HED_STAGES):
+        for j in range(n):
+            out += list(_conv(f"{prefix}netVgg{tag}.{2 * j + (1 if s else 0)}.", cin, width, 3))
+            cin = width
+    for tag, width, _ in _HED_STAGES:
+        out += list(_conv(f"{prefix}netScore{tag}.", width, 1, 1))
+    out += list(_conv(prefix + "netCombine.0.", 5, 1, 1))
+    return out
+
+
+def synth_hed_state_dict(seed: int = 1234) -> Dict[str, np.ndarray]:
+    """Seeded HED weights.  The plain recipe saturates the detector (13 ReLU layers without a normalisation halve the activation
+    power each, the score heads then see std ~ 26 and the sigmoid sits at 0), so the trunk weights carry the He gain sqrt(2),
+    which keeps the activations level, and the score heads are scaled by 0.02, which leaves the side maps at std ~ 1."""
+    sd = {}
+    for n, s, k in hed_spec():
+        x = synth_tensor(n, s, k, seed)
+        if k == "w" and ".netVgg" in n:
+            x = x * np.float32(np.sqrt(2.0))
+        elif k == "w" and ".netScore" in n:
+            x = x * np.float32(0.02)
+        sd[n] = x
+    return sd
+
+
+def hed_key(name: str) -> str:
+    """A HED tensor's name in the engine's registry from the checkpoint's ``module...`` key (network-bsds500.pth), ``Network``'s
+    own ``net...`` key, or the registry name itself; raises KeyError for anything else."""
+    k = name
+    if k.startswith(HED_PREFIX):
+        k = k[len(HED_PREFIX):]
+    if k.startswith("module"):
+        k = "net" + k[len("module"):]       # Network.__init__: strKey.replace('module', 'net')
+    k = HED_PREFIX + k
+    if k not in _HED_NAMES:
+        raise KeyError(f"not a HED tensor: '{name}'")
+    return k
+
+
+_HED_NAMES = frozenset(n for n, _, _ in hed_spec())
 
 
 TEXT_PREFIX = "cond_stage_model.transformer.text_model."

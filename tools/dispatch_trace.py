@@ -1,5 +1,6 @@
 """Which kernel family / tile / split every contraction launch of one denoising step takes (engine option verbose = 2, stderr):
 python tools/dispatch_trace.py [--batch 8] [--size 512] [--precision f16|bf16|f32|f16x2];  prints the distinct lines with their counts.
+--hed traces the 13 trunk convs of the HED edge detector (Engine.hed on a batch of size x size images) instead.
 PDENGINE_LIB=/path/to/libpdengine.so traces another build of the library (engine.load_library): diff the two outputs to compare builds."""
 import argparse, collections, os, subprocess, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -17,12 +18,31 @@ if len(sys.argv) > 1 and sys.argv[1] == "--child":
     e.set_option("verbose", 0)
     e.sample_end()
     sys.exit(0)
+if len(sys.argv) > 1 and sys.argv[1] == "--child-hed":
+    import dataclasses
+    import numpy as np
+    from prompt_diffusion_amd import engine as E, weights as W
+    B = int(sys.argv[2]); L = int(sys.argv[3])
+    e = E.Engine(dataclasses.replace(W.TINY, hed=True), precision=sys.argv[4])
+    e.load_hed_state_dict(W.synth_hed_state_dict())
+    x = np.random.default_rng(0).uniform(0, 1, (B, 3, L, L)).astype(np.float32)
+    e.hed(x)
+    e.set_option("verbose", 2)
+    e.hed(x)
+    e.set_option("verbose", 0)
+    sys.exit(0)
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=8)
 ap.add_argument("--size", type=int, default=512)
 ap.add_argument("--precision", default="f16", choices=["f16", "bf16", "f32", "f16x2"])
+ap.add_argument("--hed", action="store_true", help="the HED edge detector's trunk instead of a denoising step (launch order kept)")
 a = ap.parse_args()
-r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", str(a.batch), str(a.size), a.precision], capture_output=True, text=True)
+r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-hed" if a.hed else "--child", str(a.batch), str(a.size), a.precision], capture_output=True, text=True)
+if a.hed:   # 13 launches, in network order
+    for l in r.stderr.splitlines():
+        if l.startswith("[pdengine] gemm"):
+            print(l[len("[pdengine] gemm "):])
+    sys.exit(r.returncode)
 cnt = collections.Counter(l for l in r.stderr.splitlines() if l.startswith("[pdengine] gemm"))
 for l, n in sorted(cnt.items(), key=lambda kv: (kv[0].split(":")[1].split()[0], -kv[1])):
     print(f"{n:3d} x {l[len('[pdengine] gemm '):]}")
