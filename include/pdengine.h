@@ -464,7 +464,14 @@ int pd_comm_destroy(pd_engine* e); /* also done by pd_engine_destroy */
 int pd_set_option(pd_engine* e, const char* key, int64_t value);
 /* "graph_captures" / "graph_replays" (step loops captured / replayed from a captured graph since the engine was created),
  * "workspace_bytes", "weight_bytes", "launches" (engine launches, split-K finalize passes not counted), "ring_launches" / "gn_from_slabs"
- * (of which: gemm_ring.hip / GroupNorm fed by split-K slabs), "steps", "event_overhead_ns", "cfg_shared" (see option "cfg_share") */
+ * (of which: gemm_ring.hip / GroupNorm fed by split-K slabs), "steps", "event_overhead_ns", "cfg_shared" (see option "cfg_share"),
+ * "gn_kernel" (which kernel the engine's last GroupNorm launch took: PD_GN_TWO_PASS = gn_stats + gn_apply, PD_GN_LDS_SLAB = the
+ * single LDS-slab kernel, PD_GN_REGISTER = the register-resident kernel of the 2-byte modes; 0 before the first launch.  The choice
+ * depends on the storage type, H * W, C / 32, a 100 KB LDS budget and the options "gn_single" / "gn_reg"; pd_op_groupnorm and
+ * pd_op_groupnorm_slabs set it, so a test can assert that a shape ran on the kernel it was chosen for) */
+#define PD_GN_TWO_PASS 1
+#define PD_GN_LDS_SLAB 2
+#define PD_GN_REGISTER 3
 int64_t pd_get_stat(pd_engine* e, const char* key);
 /* Per-launch timing: while option "profile" is 1 the engine brackets every contraction launch with HIP
  * events on its stream.  klass 0 = igemm_kernel on a conv3x3, 1 = igemm_kernel / rgemm_kernel on a conv1x1/linear,

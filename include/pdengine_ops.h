@@ -7,6 +7,8 @@
  *   pd_op_linear_fp8 the e4m3 form of nn.Linear used by the SD3 path's sd3_fp8 option
  *   pd_op_groupnorm  GroupNorm32 (+SiLU)                                           util.py:217-219, attention.py:88-89
  *   pd_op_layernorm  nn.LayerNorm                                                  attention.py:263-265
+ *   pd_op_groupnorm_slabs / pd_op_groupnorm_coef  the derived forms of GroupNorm32 (split-K slab input; {scale, shift} coefficients)
+ *   pd_op_ln_linear  nn.LayerNorm -> nn.Linear as a kernel pair and as the folded GEMM   attention.py:271-275
  *   pd_op_attention  softmax(q k^T dh^-0.5) v, heads from the engine config        attention.py:171-193
  *   pd_op_spatial_transformer  one SpatialTransformer block of the loaded networks  attention.py:271-275,321-340
  *   pd_op_time_embed timestep_embedding + the time_embed MLP of a loaded network    util.py:154-174, openaimodel.py:526-531
@@ -28,6 +30,32 @@ int pd_op_linear_fp8(pd_engine* e, const float* x, const float* w, const float* 
 int pd_op_groupnorm(pd_engine* e, const float* x, const float* gamma, const float* beta, int B, int C, int H, int W, float eps,
                     int silu, float* y);
 int pd_op_layernorm(pd_engine* e, const float* x, const float* gamma, const float* beta, int rows, int C, float* y);
+/* GroupNorm32 (+SiLU) of a tensor that exists only as the fp32 partial sums of a split-K GEMM (option "slab_gn"): slabs
+ * [nslab][B * H * W][C] (pixel rows, channels last), bias [C] or NULL, row [B][C] (the per-sample time-embedding row) or NULL.  The
+ * kernel rebuilds x = round_S(slab_0 + slab_1 + ... + bias + row), summed in fp32 in that order (splitk_finalize_kernel's), S the
+ * residual-stream type, and normalises it: bit-identical to pd_op_groupnorm of that x.  Runs launch_gn_fused_slabs (the register kernel
+ * or the LDS-slab kernel, stat "gn_kernel"); an error where no single-kernel GroupNorm applies to the shape.  y [B, C, H, W]. */
+int pd_op_groupnorm_slabs(pd_engine* e, const float* slabs, int nslab, const float* bias, const float* row, const float* gamma,
+                          const float* beta, int B, int C, int H, int W, float eps, int silu, float* y);
+/* The coefficient form of GroupNorm32 (gn_stats_kernel + gn_coef_kernel) that the GroupNorm-fused patch conv and the fused
+ * SpatialTransformer front apply while staging: x [B, C, H, W] -> coef [B][C][2] = {a, b} with GroupNorm(x)[b, c] = x * a + b. */
+int pd_op_groupnorm_coef(pd_engine* e, const float* x, const float* gamma, const float* beta, int B, int C, int H, int W, float eps,
+                         float* coef);
+/* y [M][N] = Linear(LayerNorm(h)) (eps 1e-5; gamma, beta [K]; w [N][K]; bias [N] or NULL) the three ways a transformer block computes
+ * it, through the engine's own gemm(); h [M][K] lives in the residual-stream type, y is written in the compute type.
+ *   mode 0: layernorm_kernel, then the GEMM on the normalised rows;
+ *   mode 1: the fold -- the GEMM reads h itself against round(w * gamma) and its epilogue applies rstd * (acc - mean * colsum) + bias',
+ *           with {sum, sum of squares} of every row from row_stats_kernel;
+ *   mode 2: the fold with the statistics left by the producing GEMM's epilogue: h = x [M][K] . w1 [K][K]^T + b1 (+ residual [M][K]) is
+ *           computed here (h is ignored; b1, residual may be NULL) and h_out [M][K], when non-NULL, receives h as it was stored -- what
+ *           the consumer read.
+ * x, w1, b1, residual are ignored in modes 0 / 1.  K a multiple of 8, at most 2048.
+ * stats_parts (may be NULL) receives how many {sum, sum of squares} partials per row fed the fold: 0 in mode 0, 1 from row_stats_kernel
+ * (mode 1, and mode 2 where the producer ran split-K and left no statistics of its own), the producing tile's wave columns otherwise.
+ * row_stats [M][2] (may be NULL; modes 1 / 2) receives those partials summed per row in fp32, in their order, as ln_row_stats does. */
+int pd_op_ln_linear(pd_engine* e, int mode, const float* h, const float* x, const float* w1, const float* b1, const float* residual,
+                    const float* gamma, const float* beta, const float* w, const float* bias, int M, int K, int N, float* h_out, float* y,
+                    int* stats_parts, float* row_stats);
 int pd_op_attention(pd_engine* e, const float* q, const float* k, const float* v, int B, int Nq, int Nk, int C, float* o);
 /* SpatialTransformer.forward of the block whose weights were loaded under `prefix` (reference state-dict prefix ending in '.'),
  * x [B, C, H, W], context [B, context_len, context_dim], y [B, C, H, W]; the same code path as a sampling step (2-byte modes at

@@ -931,7 +931,7 @@ int pd_engine::groupnorm(const Act& x, Act& y, const float* g, const float* b, f
         ++launches;
         ++gn_from_slabs;
         if (launch_gn_fused_slabs(from_slabs->slabs, from_slabs->nslab, from_slabs->bias, from_slabs->rowvec, from_slabs->rowvec_stride, x.dt, y.p, y.dt, g, b,
-                                  x.B, x.H * x.W, x.C, 32, eps, silu ? 1 : 0, stream)) {
+                                  x.B, x.H * x.W, x.C, 32, eps, silu ? 1 : 0, stream, &gn_kernel)) {
             pd_set_error("groupnorm (single kernel, split-K slabs) launch failed (C=%d)", x.C);
             return 1;
         }
@@ -941,7 +941,7 @@ int pd_engine::groupnorm(const Act& x, Act& y, const float* g, const float* b, f
         if (arena.dry) return 0;
         PD_TRY(check_arena());
         ++launches;
-        if (launch_gn_fused(x.p, x.dt, y.p, y.dt, g, b, x.B, x.H * x.W, x.C, 32, eps, silu ? 1 : 0, stream)) {
+        if (launch_gn_fused(x.p, x.dt, y.p, y.dt, g, b, x.B, x.H * x.W, x.C, 32, eps, silu ? 1 : 0, stream, &gn_kernel)) {
             pd_set_error("groupnorm (single kernel) launch failed (C=%d)", x.C);
             return 1;
         }
@@ -951,6 +951,7 @@ int pd_engine::groupnorm(const Act& x, Act& y, const float* g, const float* b, f
     PD_TRY(gn_stats(x, nchunk));
     if (arena.dry) return 0;
     ++launches;
+    gn_kernel = GN_KIND_TWO_PASS;
     if (launch_gn_apply(x.p, x.dt, y.p, y.dt, gn_partial, g, b, x.B, x.H * x.W, x.C, 32, nchunk, eps, silu ? 1 : 0, stream)) {
         pd_set_error("groupnorm launch failed (C=%d)", x.C);
         return 1;

@@ -17,6 +17,24 @@ namespace {
 
 constexpr int GN_THREADS = 256;
 
+// Statistics: var = E[x^2] - mean^2 from {sum, sum of squares} in fp64, fixed order.  Uncentred fp32 partial sums lose the variance as a
+// group's |mean| / std grows, so what feeds fp64 depends on the input type (measurements and the reasons: DESIGN.md section 2, "The
+// normalisation kernels, per element"):
+//   fp32: x and x * x go to fp64 from the first element.
+//   bf16: fp32 runs of 16 values per (thread, channel); 16-bit squares sum exactly where the cancellation is.
+//   fp16: the same runs {s, q}, and next to q the squares pq of x - pivot (the run's first value; the difference is exact in fp32).
+//         A run that sits off centre -- q above 8 x its sum of squared deviations -- hands fp64 pq put back around the pivot in
+//         place of q; a centred run hands over the bits it always did.  8 is the largest factor with which the emulated scheme meets
+//         the bound at every ratio from 0 to 16; it keeps most fp16 results bit for bit, not all (SD1.5 activations have such runs).
+__device__ __forceinline__ void gn_run_flush(double& ds, double& dq, float s, float q, float pq, float pivot, int n) {
+    const float sd = s - (float)n * pivot;          // sum of x - pivot
+    const float dev = pq - sd * sd / (float)n;      // the run's sum of squared deviations
+    const bool refine = n >= 8 && q > 8.f * dev;    // (fewer than 8 squares of 22 bits in a binade or two still sum exactly)
+    const double p = (double)pivot, np = (double)n * p, d = (double)s - np;
+    ds += (double)s;
+    dq += refine ? (double)pq + p * (2.0 * d + np) : (double)q;
+}
+
 template <int XD>
 __global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const void* __restrict__ x, double* __restrict__ partial,
                                                                int HW, int C, int groups, int nchunk) {
@@ -42,6 +60,7 @@ __global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const void* __rest
             double ds[VEC], dq[VEC];
 #pragma unroll
             for (int j = 0; j < VEC; ++j) { ds[j] = 0.0; dq[j] = 0.0; }
+            [[maybe_unused]] float pv[VEC], pq[VEC];   // fp16 input: the squares of x - pivot next to the plain run
             int cnt = 0;
             for (int p = p0 + pr; p < p1; p += rows_par) {
                 const size_t idx = ((size_t)b * HW + p) * C + (size_t)v * VEC;
@@ -54,18 +73,40 @@ __global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const void* __rest
                     const uint4 t = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(x) + idx);
                     unpack8<XD>(t, f);
                 }
+                if constexpr (XF32) {
+                    // fp32 input: fp64 from the first element (see the note above gn_stats_kernel)
 #pragma unroll
-                for (int j = 0; j < VEC; ++j) { s[j] += f[j]; q[j] = fmaf(f[j], f[j], q[j]); }
-                if (++cnt == 16) {  // flush short fp32 runs into fp64
+                    for (int j = 0; j < VEC; ++j) { const double d = (double)f[j]; ds[j] += d; dq[j] = fma(d, d, dq[j]); }
+                } else {
+                    if constexpr (XD == DT_F16) {
+                        if (cnt == 0) {
 #pragma unroll
-                    for (int j = 0; j < VEC; ++j) { ds[j] += s[j]; dq[j] += q[j]; s[j] = 0.f; q[j] = 0.f; }
-                    cnt = 0;
+                            for (int j = 0; j < VEC; ++j) { pv[j] = f[j]; pq[j] = 0.f; }
+                        }
+#pragma unroll
+                        for (int j = 0; j < VEC; ++j) { const float d = f[j] - pv[j]; pq[j] = fmaf(d, d, pq[j]); }
+                    }
+#pragma unroll
+                    for (int j = 0; j < VEC; ++j) { s[j] += f[j]; q[j] = fmaf(f[j], f[j], q[j]); }
+                    if (++cnt == 16) {  // flush short fp32 runs into fp64
+#pragma unroll
+                        for (int j = 0; j < VEC; ++j) {
+                            if constexpr (XD == DT_F16) gn_run_flush(ds[j], dq[j], s[j], q[j], pq[j], pv[j], 16);
+                            else { ds[j] += s[j]; dq[j] += q[j]; }
+                            s[j] = 0.f; q[j] = 0.f;
+                        }
+                        cnt = 0;
+                    }
                 }
             }
 #pragma unroll
             for (int j = 0; j < VEC; ++j) {
-                ds[j] += s[j];
-                dq[j] += q[j];
+                if constexpr (XD == DT_F16) {
+                    if (cnt) gn_run_flush(ds[j], dq[j], s[j], q[j], pq[j], pv[j], cnt);
+                } else {
+                    ds[j] += s[j];
+                    dq[j] += q[j];
+                }
                 const int g = (v * VEC + j) / cpg;
                 atomicAdd(&s_sum[g], ds[j]);
                 atomicAdd(&s_sq[g], dq[j]);
@@ -218,6 +259,7 @@ __global__ __launch_bounds__(GNF_THREADS) void gn_fused_kernel(const void* __res
     float s[VEC], q[VEC];
 #pragma unroll
     for (int j = 0; j < VEC; ++j) { ds[j] = 0.0; dq[j] = 0.0; s[j] = 0.f; q[j] = 0.f; }
+    [[maybe_unused]] float pv[VEC], pq[VEC];   // fp16 input: the squares of x - pivot next to the plain run
     int cnt = 0;
     for (int p = pr; p < HW; p += rows_par) {
         uint4 raw;
@@ -246,12 +288,36 @@ __global__ __launch_bounds__(GNF_THREADS) void gn_fused_kernel(const void* __res
         } else {
             unpack8<XD>(raw, f);
         }
+        if constexpr (XF32) {
+            // fp32 input: fp64 from the first element (see the note above gn_stats_kernel); the same code for both input forms
 #pragma unroll
-        for (int j = 0; j < VEC; ++j) { s[j] += f[j]; q[j] = fmaf(f[j], f[j], q[j]); }
-        if (++cnt == 16) {
+            for (int j = 0; j < VEC; ++j) { const double d = (double)f[j]; ds[j] += d; dq[j] = fma(d, d, dq[j]); }
+        } else {
+            if constexpr (XD == DT_F16) {
+                if (cnt == 0) {
 #pragma unroll
-            for (int j = 0; j < VEC; ++j) { ds[j] += s[j]; dq[j] += q[j]; s[j] = 0.f; q[j] = 0.f; }
-            cnt = 0;
+                    for (int j = 0; j < VEC; ++j) { pv[j] = f[j]; pq[j] = 0.f; }
+                }
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) { const float d = f[j] - pv[j]; pq[j] = fmaf(d, d, pq[j]); }
+            }
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) { s[j] += f[j]; q[j] = fmaf(f[j], f[j], q[j]); }
+            if (++cnt == 16) {
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) {
+                    if constexpr (XD == DT_F16) gn_run_flush(ds[j], dq[j], s[j], q[j], pq[j], pv[j], 16);
+                    else { ds[j] += s[j]; dq[j] += q[j]; }
+                    s[j] = 0.f; q[j] = 0.f;
+                }
+                cnt = 0;
+            }
+        }
+    }
+    if constexpr (XD == DT_F16) {   // the unfinished run (the plain path below then adds zeros)
+        if (cnt) {
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) { gn_run_flush(ds[j], dq[j], s[j], q[j], pq[j], pv[j], cnt); s[j] = 0.f; q[j] = 0.f; }
         }
     }
     // this thread's contribution to each group of the bundle
@@ -534,6 +600,14 @@ __global__ __launch_bounds__(NL == 16 ? 512 : 1024) void gn_reg_kernel(const voi
     float s[EV], q2[EV];
 #pragma unroll
     for (int j = 0; j < EV; ++j) { s[j] = 0.f; q2[j] = 0.f; }
+    constexpr bool PIV = XD == DT_F16 && NL >= 8;   // fp16 runs long enough to lose bits: the squares of x - pivot as well (gn_run_flush)
+    [[maybe_unused]] float pv[EV], pq[EV];
+    if constexpr (PIV) {
+#pragma unroll
+        for (int w = 0; w < NW; ++w) unpack2<XD>(raw[0][w], pv[2 * w], pv[2 * w + 1]);
+#pragma unroll
+        for (int j = 0; j < EV; ++j) pq[j] = 0.f;
+    }
 #pragma unroll
     for (int i = 0; i < NL; ++i)
 #pragma unroll
@@ -542,10 +616,18 @@ __global__ __launch_bounds__(NL == 16 ? 512 : 1024) void gn_reg_kernel(const voi
             unpack2<XD>(raw[i][w], lo, hi);
             s[2 * w] += lo; q2[2 * w] = fmaf(lo, lo, q2[2 * w]);
             s[2 * w + 1] += hi; q2[2 * w + 1] = fmaf(hi, hi, q2[2 * w + 1]);
+            if constexpr (PIV) {
+                lo -= pv[2 * w]; hi -= pv[2 * w + 1];
+                pq[2 * w] = fmaf(lo, lo, pq[2 * w]);
+                pq[2 * w + 1] = fmaf(hi, hi, pq[2 * w + 1]);
+            }
         }
     double gs = 0.0, gq = 0.0;
 #pragma unroll
-    for (int j = 0; j < EV; ++j) { gs += (double)s[j]; gq += (double)q2[j]; }
+    for (int j = 0; j < EV; ++j) {
+        if constexpr (PIV) gn_run_flush(gs, gq, s[j], q2[j], pq[j], pv[j], NL);
+        else { gs += (double)s[j]; gq += (double)q2[j]; }
+    }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { gs += __shfl_xor(gs, o); gq += __shfl_xor(gq, o); }
     if ((tid & 63) == 0) { red[tid >> 6][0] = gs; red[tid >> 6][1] = gq; }
@@ -689,13 +771,17 @@ static int gn_slab_bundle(int x_dt, int HW, int C, int groups) {
 }
 
 int launch_gn_fused(const void* x, int x_dt, void* y, int y_dt, const float* gamma, const float* beta, int B, int HW, int C, int groups,
-                    float eps, int do_silu, hipStream_t s) {
+                    float eps, int do_silu, hipStream_t s, int* kind) {
+    if (kind) *kind = 0;
     // (the same eligibility rule for both input forms: a shape must take the same kernel -- the same summation order -- whether its input
     // is a stored tensor or a split-K GEMM's slabs: test_split_k_slabs_into_groupnorm_is_bit_identical)
-    if (g_gn_reg && gn_reg_vb(x_dt, y_dt, HW, C, groups, true))
+    if (g_gn_reg && gn_reg_vb(x_dt, y_dt, HW, C, groups, true)) {
+        if (kind) *kind = GN_KIND_REGISTER;
         return launch_gn_reg<false>(x, x_dt, y, gamma, beta, B, HW, C, groups, eps, do_silu, GnSlabSrc{}, s);
+    }
     const int BC = gn_slab_bundle(x_dt, HW, C, groups);
     if (!BC) return 1;
+    if (kind) *kind = GN_KIND_LDS_SLAB;
     const int EX = x_dt == DT_F32 ? 4 : 2;
     const size_t smem = (size_t)HW * BC * EX + (GNF_THREADS / 64) * 4 * 2 * sizeof(double);
     const dim3 grid(B * (C / BC));
@@ -710,13 +796,17 @@ int launch_gn_fused(const void* x, int x_dt, void* y, int y_dt, const float* gam
 }
 
 int launch_gn_fused_slabs(const float* slabs, int nslab, const float* bias, const float* rowvec, int rowvec_stride, int x_dt, void* y, int y_dt,
-                          const float* gamma, const float* beta, int B, int HW, int C, int groups, float eps, int do_silu, hipStream_t s) {
+                          const float* gamma, const float* beta, int B, int HW, int C, int groups, float eps, int do_silu, hipStream_t s, int* kind) {
+    if (kind) *kind = 0;
     if (!slabs || nslab < 1 || C % 4) return 1;
-    if (g_gn_reg && gn_reg_vb(x_dt, y_dt, HW, C, groups, true))
+    if (g_gn_reg && gn_reg_vb(x_dt, y_dt, HW, C, groups, true)) {
+        if (kind) *kind = GN_KIND_REGISTER;
         return launch_gn_reg<true>(nullptr, x_dt, y, gamma, beta, B, HW, C, groups, eps, do_silu,
                                    GnSlabSrc{slabs, (long long)B * HW * C, bias, rowvec, nslab, rowvec_stride}, s);
+    }
     const int BC = gn_slab_bundle(x_dt, HW, C, groups);
     if (!BC) return 1;
+    if (kind) *kind = GN_KIND_LDS_SLAB;
     const int EX = x_dt == DT_F32 ? 4 : 2;
     const size_t smem = (size_t)HW * BC * EX + (GNF_THREADS / 64) * 4 * 2 * sizeof(double);
     const dim3 grid(B * (C / BC));

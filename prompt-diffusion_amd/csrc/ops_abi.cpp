@@ -213,6 +213,151 @@ int pd_op_groupnorm(pd_engine* e, const float* x, const float* gamma, const floa
     return from_dev_nhwc(e, out.p, e->T, y, B, C, H, W, C);
 }
 
+// GroupNorm (32 groups) of a tensor that exists only as a split-K GEMM's fp32 slabs: launch_gn_fused_slabs on host arrays
+int pd_op_groupnorm_slabs(pd_engine* e, const float* slabs, int nslab, const float* bias, const float* row, const float* gamma,
+                          const float* beta, int B, int C, int H, int W, float eps, int silu, float* y) {
+    if (!e || !slabs || !gamma || !beta || !y) { pd_set_error("null argument"); return 1; }
+    if (nslab < 1 || B < 1 || C < 32 || C % 32 || H < 1 || W < 1) { pd_set_error("pd_op_groupnorm_slabs: need nslab, B, H, W >= 1 and C a positive multiple of 32"); return 1; }
+    HIP_OK(hipSetDevice(e->device));
+    const int HW = H * W;
+    if (!gn_fused_bundle(e->S, HW, C, 32)) { pd_set_error("pd_op_groupnorm_slabs: no single-kernel GroupNorm for C=%d HW=%d in this mode", C, HW); return 1; }
+    const size_t n = (size_t)B * HW * C;
+    DevBuf sl((size_t)nslab * n * 4), bi((size_t)C * 4 + 16), ro((size_t)B * C * 4 + 16), out(n * dt_size(e->T)), g((size_t)C * 4 + 16), b((size_t)C * 4 + 16);
+    if (!sl.p || !bi.p || !ro.p || !out.p || !g.p || !b.p) { pd_set_error("allocation failed"); return 1; }
+    HIP_OK(hipMemcpy(sl.p, slabs, (size_t)nslab * n * 4, hipMemcpyHostToDevice));
+    if (bias) HIP_OK(hipMemcpy(bi.p, bias, (size_t)C * 4, hipMemcpyHostToDevice));
+    if (row) HIP_OK(hipMemcpy(ro.p, row, (size_t)B * C * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(g.p, gamma, (size_t)C * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(b.p, beta, (size_t)C * 4, hipMemcpyHostToDevice));
+    if (launch_gn_fused_slabs(reinterpret_cast<const float*>(sl.p), nslab, bias ? reinterpret_cast<const float*>(bi.p) : nullptr,
+                              row ? reinterpret_cast<const float*>(ro.p) : nullptr, C, e->S, out.p, e->T, reinterpret_cast<const float*>(g.p),
+                              reinterpret_cast<const float*>(b.p), B, HW, C, 32, eps, silu ? 1 : 0, e->stream, &e->gn_kernel)) {
+        pd_set_error("pd_op_groupnorm_slabs: launch failed");
+        return 1;
+    }
+    return from_dev_nhwc(e, out.p, e->T, y, B, C, H, W, C);
+}
+
+// gn_stats + gn_coef_kernel: the per-(sample, channel) {a, b} of y = x * a + b that the GroupNorm-fused convs and st_front_kernel apply
+int pd_op_groupnorm_coef(pd_engine* e, const float* x, const float* gamma, const float* beta, int B, int C, int H, int W, float eps,
+                         float* coef) {
+    if (!e || !x || !gamma || !beta || !coef) { pd_set_error("null argument"); return 1; }
+    if (B < 1 || C < 32 || C % 32 || H < 1 || W < 1) { pd_set_error("pd_op_groupnorm_coef: need B, H, W >= 1 and C a positive multiple of 32"); return 1; }
+    HIP_OK(hipSetDevice(e->device));
+    DevBuf in((size_t)B * H * W * C * dt_size(e->S)), co((size_t)B * C * 2 * 4), g((size_t)C * 4 + 16), b((size_t)C * 4 + 16);
+    if (!in.p || !co.p || !g.p || !b.p) { pd_set_error("allocation failed"); return 1; }
+    HIP_OK(hipMemcpy(g.p, gamma, (size_t)C * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(b.p, beta, (size_t)C * 4, hipMemcpyHostToDevice));
+    PD_TRY(to_dev_nhwc(e, x, in.p, e->S, B, C, H, W, C));
+    Act a;
+    a.p = in.p; a.B = B; a.H = H; a.W = W; a.C = C; a.dt = e->S;
+    int nchunk = 1;
+    PD_TRY(e->gn_stats(a, nchunk));
+    if (launch_gn_coef(e->gn_partial, reinterpret_cast<const float*>(g.p), reinterpret_cast<const float*>(b.p), reinterpret_cast<float*>(co.p), B,
+                       H * W, C, 32, nchunk, eps, e->stream)) {
+        pd_set_error("pd_op_groupnorm_coef: launch failed");
+        return 1;
+    }
+    HIP_OK(hipStreamSynchronize(e->stream));
+    HIP_OK(hipMemcpy(coef, co.p, (size_t)B * C * 2 * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// y = Linear(LayerNorm(h)) the three ways a transformer block computes it (pd_engine::transformer): h in the residual-stream type,
+// y in the compute type, both through pd_engine::gemm
+int pd_op_ln_linear(pd_engine* e, int mode, const float* h, const float* x, const float* w1, const float* b1, const float* residual,
+                    const float* gamma, const float* beta, const float* w, const float* bias, int M, int K, int N, float* h_out, float* y,
+                    int* stats_parts, float* row_stats) {
+    if (!e || !gamma || !beta || !w || !y) { pd_set_error("null argument"); return 1; }
+    if (mode < 0 || mode > 2 || (mode < 2 ? !h : (!x || !w1))) { pd_set_error("pd_op_ln_linear: mode 0 / 1 take h, mode 2 takes x and w1"); return 1; }
+    if (M < 1 || N < 1 || K < 8 || K % 8 || K > 2048) { pd_set_error("pd_op_ln_linear: need M, N >= 1 and K a multiple of 8, at most 2048"); return 1; }
+    HIP_OK(hipSetDevice(e->device));
+    TempMat guard(e);
+    const int Np = round_up(N, 4);
+    const size_t sb = dt_size(e->S), tb = dt_size(e->T);
+    WMat m, m1;
+    e->make_mat(m, N, K, 1, K, true);
+    if (!m.w) { pd_set_error("allocation failed"); return 1; }
+    PD_TRY(e->upload_rows(m, 0, w, N, false));
+    if (bias) PD_TRY(e->upload_vec(m.bias, bias, N, false, 0));
+    DevBuf tmp((size_t)M * K * 4), hs((size_t)M * K * sb), a1((size_t)M * K * tb), rs((size_t)M * K * sb), ln((size_t)M * K * tb), out((size_t)M * Np * tb),
+        g((size_t)K * 4 + 16), b((size_t)K * 4 + 16), f32out((size_t)M * (Np > K ? Np : K) * 4);
+    const int cap_parts = ((K + 159) / 160) * 2;   // pd_engine::transformer's sizing of the statistics rows
+    DevBuf stats((size_t)M * cap_parts * 2 * 4);
+    if (!tmp.p || !hs.p || !a1.p || !rs.p || !ln.p || !out.p || !g.p || !b.p || !f32out.p || !stats.p) { pd_set_error("allocation failed"); return 1; }
+    HIP_OK(hipMemcpy(g.p, gamma, (size_t)K * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(b.p, beta, (size_t)K * 4, hipMemcpyHostToDevice));
+    auto put = [&](const float* src, void* dst, int dt) -> int {   // host fp32 [M][K] -> device rows in dt
+        HIP_OK(hipMemcpy(tmp.p, src, (size_t)M * K * 4, hipMemcpyHostToDevice));
+        if (launch_cast_rows(reinterpret_cast<const float*>(tmp.p), dst, dt, M, K, K, e->stream)) { pd_set_error("cast launch failed"); return 1; }
+        HIP_OK(hipStreamSynchronize(e->stream));
+        return 0;
+    };
+    auto get = [&](const void* src, int dt, int ld, int cols, float* dst) -> int {   // device rows in dt -> host fp32 [M][cols]
+        if (launch_nhwc_to_nchw(src, dt, reinterpret_cast<float*>(f32out.p), 1, 1, 1, M * ld, 1, 1.f, e->stream)) { pd_set_error("cast launch failed"); return 1; }
+        HIP_OK(hipStreamSynchronize(e->stream));
+        std::vector<float> host((size_t)M * ld);
+        HIP_OK(hipMemcpy(host.data(), f32out.p, host.size() * 4, hipMemcpyDeviceToHost));
+        for (int i = 0; i < M; ++i) memcpy(dst + (size_t)i * cols, host.data() + (size_t)i * ld, (size_t)cols * 4);
+        return 0;
+    };
+    Act hA, o;
+    hA.p = hs.p; hA.B = M; hA.H = 1; hA.W = 1; hA.C = K; hA.dt = e->S;
+    o.p = out.p; o.B = M; o.H = 1; o.W = 1; o.C = Np; o.dt = e->T;
+    LnStats st;
+    st.stats = reinterpret_cast<float*>(stats.p);
+    st.cap_parts = cap_parts;
+    if (mode == 2) {   // the producer writes h and leaves the row statistics (proj_in / attn1.to_out with its residual)
+        e->make_mat(m1, K, K, 1, K, true);
+        if (!m1.w) { pd_set_error("allocation failed"); return 1; }
+        PD_TRY(e->upload_rows(m1, 0, w1, K, false));
+        if (b1) PD_TRY(e->upload_vec(m1.bias, b1, K, false, 0));
+        PD_TRY(put(x, a1.p, e->T));
+        Act a, r;
+        a = hA; a.p = a1.p; a.dt = e->T;
+        r = hA; r.p = rs.p;
+        if (residual) PD_TRY(put(residual, rs.p, e->S));
+        PD_TRY(e->gemm(m1, a, hA, {.R = residual ? &r : nullptr, .ln_out = &st}));
+    } else {
+        PD_TRY(put(h, hs.p, e->S));
+    }
+    if (mode == 0) {
+        Act l = hA;
+        l.p = ln.p; l.dt = e->T;
+        PD_TRY(e->layernorm(hA, l, reinterpret_cast<float*>(g.p), reinterpret_cast<float*>(b.p)));
+        PD_TRY(e->gemm(m, l, o));
+    } else {
+        m.w_ln = e->dmalloc((size_t)m.N * m.Kpad * tb);
+        m.colsum = reinterpret_cast<float*>(e->dmalloc((size_t)(m.N + 4) * sizeof(float)));
+        m.bias_ln = reinterpret_cast<float*>(e->dmalloc((size_t)(m.N + 4) * sizeof(float)));
+        if (!m.w_ln || !m.colsum || !m.bias_ln) { pd_set_error("allocation failed"); return 1; }
+        if (launch_ln_fold(m.w, m.w_ln, e->T, m.N, m.K, m.Kpad, reinterpret_cast<float*>(g.p), reinterpret_cast<float*>(b.p), m.bias, m.colsum,
+                           m.bias_ln, e->stream)) {
+            pd_set_error("LayerNorm fold launch failed");
+            return 1;
+        }
+        if (mode == 1) {
+            st.parts = 1; st.C = K;
+            if (launch_row_stats(hs.p, e->S, st.stats, M, K, e->stream)) { pd_set_error("row statistics launch failed"); return 1; }
+        }
+        PD_TRY(e->gemm(m, hA, o, {.ln_in = &st}));
+    }
+    HIP_OK(hipStreamSynchronize(e->stream));
+    if (stats_parts) *stats_parts = mode ? st.parts : 0;
+    if (row_stats && mode) {   // what the consumer's ln_row_stats folds: the partials of every row, summed here in their order
+        if (st.parts < 1 || st.parts > cap_parts) { pd_set_error("pd_op_ln_linear: %d statistics partials per row", st.parts); return 1; }
+        std::vector<float> hp((size_t)M * st.parts * 2);
+        HIP_OK(hipMemcpy(hp.data(), stats.p, hp.size() * 4, hipMemcpyDeviceToHost));
+        for (int i = 0; i < M; ++i) {
+            float sum = 0.f, sq = 0.f;
+            for (int k = 0; k < st.parts; ++k) { sum += hp[((size_t)i * st.parts + k) * 2]; sq += hp[((size_t)i * st.parts + k) * 2 + 1]; }
+            row_stats[2 * i] = sum; row_stats[2 * i + 1] = sq;
+        }
+    }
+    if (h_out) PD_TRY(get(hs.p, e->S, K, K, h_out));
+    return get(out.p, e->T, Np, N, y);
+}
+
 int pd_op_layernorm(pd_engine* e, const float* x, const float* gamma, const float* beta, int rows, int C, float* y) {
     if (!e || !x || !gamma || !beta || !y) { pd_set_error("null argument"); return 1; }
     HIP_OK(hipSetDevice(e->device));

@@ -274,13 +274,15 @@ int launch_gn_stats(const void* x, int x_dt, double* partial, int B, int HW, int
 int launch_gn_apply(const void* x, int x_dt, void* y, int y_dt, const double* partial, const float* gamma,
                     const float* beta, int B, int HW, int C, int groups, int nchunk, float eps, int silu, hipStream_t s);
 extern int g_gn_reg;   // norm.hip
+// which kernel a GroupNorm launch took (stat "gn_kernel": PD_GN_* in include/pdengine.h)
+enum { GN_KIND_TWO_PASS = 1, GN_KIND_LDS_SLAB = 2, GN_KIND_REGISTER = 3 };
 int gn_fused_bundle(int x_dt, int HW, int C, int groups);   // norm.hip: > 0 when the single-kernel GroupNorm applies
 int launch_gn_fused(const void* x, int x_dt, void* y, int y_dt, const float* gamma, const float* beta, int B, int HW, int C, int groups,
-                    float eps, int do_silu, hipStream_t s);
+                    float eps, int do_silu, hipStream_t s, int* kind = nullptr);   // kind: which kernel took it (GN_KIND_*)
 // the same kernel fed by a split-K GEMM's fp32 slabs instead of a stored tensor: x[row][c] = round_T(sum_s slab[s][row][c] + bias[c] +
 // rowvec[sample][c]) -- splitk_finalize_kernel's arithmetic and rounding, so the result is bit-identical to finalize + launch_gn_fused
 int launch_gn_fused_slabs(const float* slabs, int nslab, const float* bias, const float* rowvec, int rowvec_stride, int x_dt, void* y, int y_dt,
-                          const float* gamma, const float* beta, int B, int HW, int C, int groups, float eps, int do_silu, hipStream_t s);
+                          const float* gamma, const float* beta, int B, int HW, int C, int groups, float eps, int do_silu, hipStream_t s, int* kind = nullptr);
 int launch_gn_coef(const double* partial, const float* gamma, const float* beta, float* coef, int B, int HW, int C, int groups,
                    int nchunk, float eps, hipStream_t s);
 // {sum, sum of squares} of every row: the single-part form of the LayerNorm statistics above (producers whose epilogue

@@ -123,8 +123,11 @@ __device__ __forceinline__ uint4 cvt8(const uint4& lo, const uint4& hi, bool do_
 
 // LayerNorm statistics of row gm of a folded GEMM's A operand: {mean, rstd} from the producer's column-range partials
 __device__ __forceinline__ void ln_row_stats(const GemmParams& p, int gm, float& mean, float& rstd) {
-    // fp32 is enough here: <= 16 partials of <= 1280 channels each, and var = E[x^2] - mean^2 loses precision only when
-    // |mean| >> std (relative error ~ 1e-7 * mean^2 / var); the residual stream this normalises is far from that regime
+    // fp32 statistics: <= 16 partials of <= 1280 channels each, and var = E[x^2] - mean^2 loses precision as |mean| / std of the row
+    // grows (relative error of rstd ~ 1e-7 * mean^2 / var: 3e-6 at a ratio of 4, 5e-5 at 16, 8e-4 -- past an fp16 ulp -- at 64).
+    // tests/test_norm_gpu.py::test_layernorm_linear holds the folded GEMMs to their per-element bound up to a ratio of 16, in every mode
+    // and behind both statistics sources, and prints the error at 64; nothing bounds the ratio of the residual
+    // stream itself, so a network whose rows sit further out than 16 stds wants option ln_fuse 0
     float s = 0.f, q = 0.f;
     const float* st = p.ln_stats + (size_t)gm * p.ln_parts * 2;
     for (int i = 0; i < p.ln_parts; ++i) {

@@ -1179,6 +1179,10 @@ int64_t pd_get_stat(pd_engine* e, const char* key) {
     if (!strcmp(key, "launches")) return (int64_t)e->launches;
     if (!strcmp(key, "gn_from_slabs")) return (int64_t)e->gn_from_slabs;
     if (!strcmp(key, "ring_launches")) return (int64_t)e->ring_launches;   // of which: gemm_ring.hip's persistent ring kernel
+    if (!strcmp(key, "gn_kernel")) {   // which kernel the last pd_engine::groupnorm launch took
+        static_assert(GN_KIND_TWO_PASS == PD_GN_TWO_PASS && GN_KIND_LDS_SLAB == PD_GN_LDS_SLAB && GN_KIND_REGISTER == PD_GN_REGISTER, "pdengine.h");
+        return (int64_t)e->gn_kernel;
+    }
     if (!strcmp(key, "steps")) return (int64_t)e->ses.S;
     if (!strcmp(key, "cfg_shared")) return (int64_t)((e->ses.share_u ? 1 : 0) | (e->ses.share_c ? 2 : 0) | (e->ses.cn_cond_only ? 4 : 0));
     if (!strcmp(key, "lora_base_bytes")) return (int64_t)e->lora_bytes(true);   // base copies W0 of the adapted parameters

@@ -200,6 +200,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.pd_op_linear_fp8.argtypes = [C.c_void_p, fp, fp, fp] + [C.c_int] * 4 + [fp]
     lib.pd_op_groupnorm.argtypes = [C.c_void_p, fp, fp, fp] + [C.c_int] * 4 + [C.c_float, C.c_int, fp]
     lib.pd_op_layernorm.argtypes = [C.c_void_p, fp, fp, fp, C.c_int, C.c_int, fp]
+    lib.pd_op_groupnorm_slabs.argtypes = [C.c_void_p, fp, C.c_int, fp, fp, fp, fp] + [C.c_int] * 4 + [C.c_float, C.c_int, fp]
+    lib.pd_op_groupnorm_coef.argtypes = [C.c_void_p, fp, fp, fp] + [C.c_int] * 4 + [C.c_float, fp]
+    lib.pd_op_ln_linear.argtypes = [C.c_void_p, C.c_int] + [fp] * 9 + [C.c_int] * 3 + [fp, fp, C.POINTER(C.c_int), fp]
     lib.pd_op_attention.argtypes = [C.c_void_p, fp, fp, fp] + [C.c_int] * 4 + [fp]
     lib.pd_op_spatial_transformer.argtypes = [C.c_void_p, C.c_char_p, fp, fp] + [C.c_int] * 3 + [fp]
     lib.pd_op_spatial_transformer_ctx.argtypes = [C.c_void_p, C.c_char_p, fp, fp] + [C.c_int] * 4 + [fp]
@@ -235,7 +238,7 @@ EXPORTS = [
     "pd_make_schedule", "pd_synchronize", "pd_stream", "pd_wait_stream", "pd_set_option", "pd_get_stat", "pd_bench_conv3x3", "pd_bench_linear", "pd_text_encode", "pd_text_encode_ex", "pd_text_weights_missing",
     "pd_profile_read", "pd_profile_dump", "pd_comm_new_id", "pd_comm_init", "pd_comm_world", "pd_comm_all_gather", "pd_comm_destroy",
     "pd_sd3_configure", "pd_sd3_weights_missing", "pd_sd3_forward", "pd_sd3_control", "pd_sd3_sample", "pd_sd3_down_proj",
-    "pd_op_conv2d", "pd_op_linear", "pd_op_linear_fp8", "pd_op_groupnorm", "pd_op_layernorm", "pd_op_attention", "pd_op_spatial_transformer", "pd_op_spatial_transformer_ctx", "pd_op_time_embed",
+    "pd_op_conv2d", "pd_op_linear", "pd_op_linear_fp8", "pd_op_groupnorm", "pd_op_layernorm", "pd_op_groupnorm_slabs", "pd_op_groupnorm_coef", "pd_op_ln_linear", "pd_op_attention", "pd_op_spatial_transformer", "pd_op_spatial_transformer_ctx", "pd_op_time_embed",
     "pd_op_timestep_embedding_i", "pd_op_timestep_embedding_f", "pd_op_vae_downsample", "pd_read_weights", "pd_lora_add", "pd_lora_set_scales", "pd_lora_remove",
     "pd_set_freeu", "pd_get_freeu", "pd_op_freeu_concat",
     "pd_philox4x32_10", "pd_set_rng", "pd_get_rng", "pd_randn",
@@ -1097,6 +1100,52 @@ class Engine:
         y = np.empty_like(x)
         self._check(self.lib.pd_op_layernorm(self._h, x.ctypes.data, g.ctypes.data, b.ctypes.data, rows, Cc, y.ctypes.data))
         return y
+
+    def op_groupnorm_slabs(self, slabs, gamma, beta, bias=None, row=None, eps=1e-5, silu=False):
+        """GroupNorm32 of round(slab_0 + slab_1 + ... + bias + row): slabs [nslab, B, H, W, C] (channels last), bias [C], row [B, C]
+        -> [B, C, H, W] (pd_op_groupnorm_slabs)."""
+        slabs = np.ascontiguousarray(slabs, np.float32)
+        nslab, B, H, W, Cc = slabs.shape
+        g = np.ascontiguousarray(gamma, np.float32); b = np.ascontiguousarray(beta, np.float32)
+        bb = None if bias is None else np.ascontiguousarray(bias, np.float32)
+        rr = None if row is None else np.ascontiguousarray(row, np.float32)
+        assert g.shape == (Cc,) and b.shape == (Cc,) and (bb is None or bb.shape == (Cc,)) and (rr is None or rr.shape == (B, Cc))
+        y = np.empty((B, Cc, H, W), np.float32)
+        self._check(self.lib.pd_op_groupnorm_slabs(self._h, slabs.ctypes.data, nslab, None if bb is None else bb.ctypes.data,
+                                                   None if rr is None else rr.ctypes.data, g.ctypes.data, b.ctypes.data, B, Cc, H, W, eps,
+                                                   int(silu), y.ctypes.data))
+        return y
+
+    def op_groupnorm_coef(self, x, gamma, beta, eps=1e-5):
+        """The {a, b} of GroupNorm32(x) = x * a + b per (sample, channel): [B, C, 2] (pd_op_groupnorm_coef)."""
+        x = np.ascontiguousarray(x, np.float32)
+        g = np.ascontiguousarray(gamma, np.float32); b = np.ascontiguousarray(beta, np.float32)
+        B, Cc, H, W = x.shape
+        assert g.shape == (Cc,) and b.shape == (Cc,)
+        coef = np.empty((B, Cc, 2), np.float32)
+        self._check(self.lib.pd_op_groupnorm_coef(self._h, x.ctypes.data, g.ctypes.data, b.ctypes.data, B, Cc, H, W, eps, coef.ctypes.data))
+        return coef
+
+    def op_ln_linear(self, mode, gamma, beta, w, bias=None, h=None, x=None, w1=None, b1=None, residual=None):
+        """Linear(LayerNorm(h)) (pd_op_ln_linear): mode 0 the kernel pair, 1 the fold with row_stats_kernel's statistics (both on h
+        [M, K]), 2 the fold behind the producer h = x @ w1.T + b1 (+ residual).  Returns (y [M, N], h as the consumer read it,
+        statistics partials per row that fed the fold, their per-row sums [M, 2] = {sum, sum of squares})."""
+        f = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+        g, b, w, bias, h, x, w1, b1, residual = (f(a) for a in (gamma, beta, w, bias, h, x, w1, b1, residual))
+        N, K = w.shape
+        src = x if mode == 2 else h
+        M = src.shape[0]
+        assert src.shape == (M, K) and g.shape == (K,) and b.shape == (K,) and (bias is None or bias.shape == (N,))
+        if mode == 2:
+            assert w1.shape == (K, K) and (b1 is None or b1.shape == (K,)) and (residual is None or residual.shape == (M, K))
+        p = lambda a: None if a is None else a.ctypes.data
+        y = np.empty((M, N), np.float32)
+        h_out = np.empty((M, K), np.float32)
+        parts = C.c_int(0)
+        row_stats = np.zeros((M, 2), np.float32)
+        self._check(self.lib.pd_op_ln_linear(self._h, int(mode), p(h), p(x), p(w1), p(b1), p(residual), p(g), p(b), p(w), p(bias), M, K, N,
+                                             h_out.ctypes.data, y.ctypes.data, C.byref(parts), row_stats.ctypes.data))
+        return y, h_out, int(parts.value), row_stats
 
     def op_time_embed(self, t, net: int = 0, want_emb: bool = True):
         """(timestep_embedding(t, model_channels), time_embed(...)) of the loaded UNet (net 0) / ControlNet (net 1)."""
