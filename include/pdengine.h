@@ -468,10 +468,20 @@ int pd_set_option(pd_engine* e, const char* key, int64_t value);
  * "gn_kernel" (which kernel the engine's last GroupNorm launch took: PD_GN_TWO_PASS = gn_stats + gn_apply, PD_GN_LDS_SLAB = the
  * single LDS-slab kernel, PD_GN_REGISTER = the register-resident kernel of the 2-byte modes; 0 before the first launch.  The choice
  * depends on the storage type, H * W, C / 32, a 100 KB LDS budget and the options "gn_single" / "gn_reg"; pd_op_groupnorm and
- * pd_op_groupnorm_slabs set it, so a test can assert that a shape ran on the kernel it was chosen for) */
+ * pd_op_groupnorm_slabs set it, so a test can assert that a shape ran on the kernel it was chosen for),
+ * "gemm_family" (which kernel family the engine's last convolution / linear launch took, PD_GEMM_* in the order of the names the
+ * option "verbose" 2 dispatch trace prints: the weight-streaming GEMV, the LDS-patch conv3x3 generations 1 / 2 / 4, the ring GEMM, the
+ * implicit GEMM; -1 before the first launch.  pd_op_conv2d and pd_op_linear set it through the same dispatch as the network, so a
+ * test can assert that an option setting put a shape on the kernel it names) */
 #define PD_GN_TWO_PASS 1
 #define PD_GN_LDS_SLAB 2
 #define PD_GN_REGISTER 3
+#define PD_GEMM_GEMV 0
+#define PD_GEMM_PATCH1 1
+#define PD_GEMM_PATCH2 2
+#define PD_GEMM_PATCH4 3
+#define PD_GEMM_RING 4
+#define PD_GEMM_IGEMM 5
 int64_t pd_get_stat(pd_engine* e, const char* key);
 /* Per-launch timing: while option "profile" is 1 the engine brackets every contraction launch with HIP
  * events on its stream.  klass 0 = igemm_kernel on a conv3x3, 1 = igemm_kernel / rgemm_kernel on a conv1x1/linear,

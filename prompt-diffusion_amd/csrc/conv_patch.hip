@@ -16,36 +16,30 @@
 // for any start row.  Swapped operands / 4-channel-per-lane epilogue / fp32 mode as in gemm.hip.
 #include <type_traits>
 
-#include "pd_common.h"
-#include "pd_mma.h"
+#include "conv_patch_common.h"
 
 namespace {
+using namespace patch_conv;
 
-constexpr int TP = 16;             // patch is TP x TP output pixels
-constexpr int BN = 160;
 constexpr int NT = 512;            // threads
-constexpr int ROWB = 128;          // bytes of K per LDS row
-constexpr int W_TILE = BN * ROWB;  // 20480
 constexpr int W_SLOTS = BN * 8;    // 16-byte chunks of a weight tile
 constexpr int W_ITERS = (W_SLOTS + NT - 1) / NT;  // 3 (last one half masked)
 
 // LDS rows are 128 B = 8 chunks of 16 B; a row's chunks are permuted by XORing bits 1-2 of the chunk index with (row >> 1) & 3.
 // A ds_read_b128 is served in four groups of 16 lanes, and a group of this kernel's fragment reads is 16 CONSECUTIVE rows of
 // which 8 read chunk c and 8 chunk c + 1 (c even); bit 0 is left alone, so the two halves never meet, and inside a half the four
-// rows of either parity differ in (row >> 1) & 3 -- conflict-free for ANY start row.  (gemm.hip's swizzle XORs all three bits with
+// rows of either parity differ in (row >> 1) & 3 -- conflict-free for ANY start row.  (pd_common.h's swz8 XORs all three bits with
 // (row >> 1) & 7: conflict-free for start rows that are multiples of 16, as in a GEMM tile and the weight tile here, but 2-way
 // conflicts on two patch reads in three -- the start row moves with the tap: 6.7 instead of 4 LDS cycles per read on average.
 // conv_patch2.hip keeps the old form: with its loader / compute wave split the new one measured 0.5 % slower end to end.)
 __device__ __forceinline__ int swzp(int row, int chunk) { return (row * ROWB) + ((chunk ^ (((row >> 1) & 3) << 1)) << 4); }
 
 template <int UPS>
-struct PatchGeom {
-    static constexpr int PW = UPS ? TP / 2 + 2 : TP + 2;   // patch rows/cols held in LDS (source resolution)
-    static constexpr int PROWS = PW * PW;
+struct PatchGeom : PatchGeomBase<UPS> {
+    using PatchGeomBase<UPS>::PROWS;
+    using PatchGeomBase<UPS>::P_BYTES;
     static constexpr int P_SLOTS = PROWS * 8;
     static constexpr int P_ITERS = (P_SLOTS + NT - 1) / NT;
-    static constexpr int P_HALF = (P_ITERS + 1) / 2;   // pieces staged per half (registers are reused)
-    static constexpr int P_BYTES = PROWS * ROWB;
     static constexpr int SMEM = 2 * P_BYTES + 2 * W_TILE;
 };
 
@@ -56,7 +50,6 @@ __global__ __launch_bounds__(NT) void conv3x3_patch_kernel(GemmParams p) {
     constexpr int EB = F32 ? 4 : 2;
     constexpr int VEC = 16 / EB;
     constexpr int BKE = ROWB / EB;
-    constexpr int PW = G::PW;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* sP = smem;                    // [2][PROWS][128]
     char* sW = smem + 2 * G::P_BYTES;   // [2][160][128]
@@ -66,27 +59,16 @@ __global__ __launch_bounds__(NT) void conv3x3_patch_kernel(GemmParams p) {
     const int wm = wave >> 1, wn = wave & 1;
     const int fr = lane & 15, fq = lane >> 4;
 
-    const int ptx = p.Wout / TP, pty = p.Hout / TP;
-    const int mtiles = (p.M / (p.Hout * p.Wout)) * ptx * pty, ntiles = (p.N + BN - 1) / BN;
-    const int nblk = mtiles * ntiles;
-    int bid = blockIdx.x;
-    {
-        const int q = nblk >> 3, r = nblk & 7, x = bid & 7;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-    }
-    const int bm = bid / ntiles, bn = bid % ntiles;
-    const int sample = bm / (ptx * pty);
-    const int prem = bm - sample * (ptx * pty);
-    const int y0 = (prem / ptx) * TP, x0 = (prem - (prem / ptx) * ptx) * TP;  // patch origin (output coords)
-    // source-resolution origin of the staged patch (row/col of LDS patch index 0)
-    const int sy0 = (y0 - 1) >> UPS, sx0 = (x0 - 1) >> UPS;
+    // the tile as plain ints: the three uses below are this kernel's own text (conv_patch_common.h says why)
+    const PatchTile t = patch_tile<UPS>(p);
+    const int bn = t.bn, sample = t.sample, y0 = t.y0, x0 = t.x0, sy0 = t.sy0, sx0 = t.sx0;
 
-    // ---- staging assignments (32-bit byte offsets; masks and LDS addresses of the patch are recomputed
+    // ---- staging assignments: source and LDS slot of patch piece j (32-bit byte offsets; masks and LDS addresses of the patch are recomputed
     //      at store time, once per chunk, to keep registers for the accumulators)
     auto patch_slot = [&](int j, int& lds, bool& ok, unsigned& off) __attribute__((always_inline)) {
         const int s = tid + NT * j;
         const int prow = s >> 3, ch = s & 7;
-        const int iy = prow / PW, ix = prow - iy * PW;
+        const int iy = prow / G::PW, ix = prow - iy * G::PW;
         const int gy = sy0 + iy, gx = sx0 + ix;
         ok = s < G::P_SLOTS && (unsigned)gy < (unsigned)p.Hin && (unsigned)gx < (unsigned)p.Win;
         off = ok ? (unsigned)((((size_t)(sample * p.Hin + gy) * p.Win + gx) * p.lda + ch * VEC) * EB) : 0u;
@@ -113,13 +95,8 @@ __global__ __launch_bounds__(NT) void conv3x3_patch_kernel(GemmParams p) {
     const char* Ab = reinterpret_cast<const char*>(p.A);
     const char* Wb = reinterpret_cast<const char*>(p.W);
     // split-K (blockIdx.y): this slice owns the channel chunks [c0, c0 + nchunks); units are counted from the slice's start
-    const int chunks_all = p.Cin / BKE;
-    int c0 = 0, nchunks = chunks_all;
-    if (p.splitk > 1) {
-        const int per = (chunks_all + p.splitk - 1) / p.splitk;
-        c0 = blockIdx.y * per;
-        nchunks = min(chunks_all, c0 + per) - c0;
-    }
+    const ChunkSlice sl = patch_chunk_slice(p.Cin / BKE, p.splitk, blockIdx.y);
+    const int c0 = sl.c0, nchunks = sl.nchunks;
     const int U = nchunks * 9;  // (chunk, tap) units of this slice; weights of a unit start at element tap*Cin + chunk*BKE
 
     // staging registers as named scalars (hipcc leaves small indexed arrays captured by these lambdas in scratch)
@@ -250,7 +227,7 @@ __global__ __launch_bounds__(NT) void conv3x3_patch_kernel(GemmParams p) {
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
                 const int py = wm * 4 + m;
-                const int prow = (((y0 - 1 + py + ky) >> UPS) - sy0) * PW + (((x0 - 1 + frv + kx) >> UPS) - sx0);
+                const int prow = (((y0 - 1 + py + ky) >> UPS) - sy0) * G::PW + (((x0 - 1 + frv + kx) >> UPS) - sx0);
                 af[m] = prep_x2(*reinterpret_cast<const uint4*>(pa + swzp(prow, fq)), *reinterpret_cast<const uint4*>(pa + swzp(prow, 4 + fq)));
             }
             const char* w0 = wa + swzp(wn * 80 + frv, fq);
@@ -268,7 +245,7 @@ __global__ __launch_bounds__(NT) void conv3x3_patch_kernel(GemmParams p) {
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
                 const int py = wm * 4 + m;
-                const int prow = (((y0 - 1 + py + ky) >> UPS) - sy0) * PW + (((x0 - 1 + frv + kx) >> UPS) - sx0);
+                const int prow = (((y0 - 1 + py + ky) >> UPS) - sy0) * G::PW + (((x0 - 1 + frv + kx) >> UPS) - sx0);
                 af[m] = prep_a<P>(*reinterpret_cast<const uint4*>(pa + swzp(prow, ks * 4 + fq)));
             }
             // the swizzle term (row>>1)&3 of a weight row wn*80 + n*16 + fr does not depend on n or wn: one base + n*2048
@@ -328,31 +305,14 @@ constexpr int COEF_BYTES_MAX = 24 * 1024;   // [Cin <= 3072][2] floats behind th
 
 template <int P, int UPS, bool GN, bool RELU = false>
 int launch_patch(const GemmParams& p, hipStream_t s) {
-    using G = PatchGeom<UPS>;
-    static unsigned long long attr_done = 0;
-    auto kfn = conv3x3_patch_kernel<P, UPS, GN, RELU>;
-    const int smem = G::SMEM + (GN ? COEF_BYTES_MAX : 0);
     if (GN && p.Cin * 8 > COEF_BYTES_MAX) return 1;
-    if (ensure_dyn_smem(reinterpret_cast<const void*>(kfn), smem, &attr_done)) return 1;
-    const int mtiles = (p.M / (p.Hout * p.Wout)) * (p.Hout / TP) * (p.Wout / TP), ntiles = (p.N + BN - 1) / BN;
-    hipLaunchKernelGGL(kfn, dim3(mtiles * ntiles, p.splitk > 1 ? p.splitk : 1), dim3(NT), smem, s, p);
-    if (hipGetLastError() != hipSuccess) return 1;
-    return (p.splitk > 1 && !p.defer_finalize) ? launch_splitk_finalize(p, s) : 0;
+    return launch_patch_grid<conv3x3_patch_kernel<P, UPS, GN, RELU>, NT>(p, PatchGeom<UPS>::SMEM + (GN ? COEF_BYTES_MAX : 0), s);
 }
 
 }  // namespace
 
 // number of blocks the patch kernel would launch, or 0 when the shape does not qualify
-int conv_patch_tiles(const GemmParams& p, int prec) {
-    const int bke = prec_f32_storage(prec) ? 32 : 64;
-    if (p.taps != 9 || p.stride != 1) return 0;
-    if (p.Hout % TP || p.Wout % TP || p.Cin % bke || p.K != 9 * p.Cin || p.act == 2 || p.vt_begin < p.N) return 0;
-    if (p.a_dt != (prec_f32_storage(prec) ? (int)DT_F32 : prec) || p.a_silu) return 0;
-    if (p.Cin * 8 > 24 * 1024) return 0;
-    if (p.act == 5 && (p.ups || p.gn_coef)) return 0;   // ACT_RELU is instantiated for the plain conv only
-    if ((p.Hin << p.ups) != p.Hout || (p.Win << p.ups) != p.Wout) return 0;
-    return (p.M / (p.Hout * p.Wout)) * (p.Hout / TP) * (p.Wout / TP) * ((p.N + BN - 1) / BN);
-}
+int conv_patch_tiles(const GemmParams& p, int prec) { return patch_eligible_tiles(p, prec); }
 
 namespace {
 template <int P>

@@ -15,43 +15,31 @@
 // before unit u+1 starts), so the pipe does not drain at a barrier.
 #include <type_traits>
 
-#include "pd_common.h"
-#include "pd_mma.h"
-
-#ifndef PATCH2_DIAG
-#define PATCH2_DIAG 0
-#endif
+#include "conv_patch_common.h"
 
 namespace {
+using namespace patch_conv;
 
-constexpr int TP = 16;             // patch is TP x TP output pixels
-constexpr int BN = 160;
 constexpr int NT = 512;            // threads: 4 compute waves + 4 loader waves
 constexpr int NL = 256;            // loader threads
-constexpr int ROWB = 128;          // bytes of K per LDS row (64 two-byte channels)
-constexpr int BKE = 64;
-constexpr int W_TILE = BN * ROWB;  // 20480
+constexpr int BKE = 64;            // two-byte channels per LDS row
 constexpr int W_IT = BN * 8 / NL;  // 5 16-byte pieces per loader thread and weight tile
 constexpr int NWB = 3;             // weight tile buffers
 
-__device__ __forceinline__ int swz2(int row, int chunk) { return (row * ROWB) + (((chunk ^ (row >> 1)) & 7) << 4); }
-
 template <int UPS>
-struct Geom2 {
-    static constexpr int PW = UPS ? TP / 2 + 2 : TP + 2;   // patch rows/cols held in LDS (source resolution)
-    static constexpr int PROWS = PW * PW;
+struct Geom2 : PatchGeomBase<UPS> {
+    using PatchGeomBase<UPS>::PROWS;
+    using PatchGeomBase<UPS>::P_BYTES;
     static constexpr int P_SLOTS = PROWS * 8;
     static constexpr int P_IT = (P_SLOTS + NL - 1) / NL;   // 11 (plain) / 4 (upsampling) pieces per loader thread
     static constexpr int PA = P_IT < 6 ? P_IT : 6;         // first batch (requested at tap 0, stored at tap 2)
     static constexpr int PB = P_IT - PA;                   // second batch (requested at tap 2, stored at tap 4)
-    static constexpr int P_BYTES = PROWS * ROWB;
     static constexpr int SMEM = 2 * P_BYTES + NWB * W_TILE;
 };
 
 template <int P, int UPS, bool RELU = false>
 __global__ __launch_bounds__(NT) void conv3x3_patch2_kernel(GemmParams p) {
     using G = Geom2<UPS>;
-    constexpr int PW = G::PW;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* sP = smem;                    // [2][PROWS][128]
     char* sW = smem + 2 * G::P_BYTES;   // [3][160][128]
@@ -60,28 +48,13 @@ __global__ __launch_bounds__(NT) void conv3x3_patch2_kernel(GemmParams p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 15, fq = lane >> 4;
 
-    const int ptx = p.Wout / TP, pty = p.Hout / TP;
-    const int mtiles = (p.M / (p.Hout * p.Wout)) * ptx * pty, ntiles = (p.N + BN - 1) / BN;
-    const int nblk = mtiles * ntiles;
-    int bid = blockIdx.x;
-    {   // XCD-aware tile order (gemm.hip)
-        const int q = nblk >> 3, r = nblk & 7, x = bid & 7;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-    }
-    const int bm = bid / ntiles, bn = bid % ntiles;
-    const int sample = bm / (ptx * pty);
-    const int prem = bm - sample * (ptx * pty);
-    const int y0 = (prem / ptx) * TP, x0 = (prem - (prem / ptx) * ptx) * TP;  // patch origin (output coords)
-    const int sy0 = (y0 - 1) >> UPS, sx0 = (x0 - 1) >> UPS;                   // source-resolution origin of LDS patch index 0
+    // the tile as plain ints: the three uses below are this kernel's own text (conv_patch_common.h says why)
+    const PatchTile t = patch_tile<UPS>(p);
+    const int bn = t.bn, sample = t.sample, y0 = t.y0, x0 = t.x0, sy0 = t.sy0, sx0 = t.sx0;
 
     // split-K (blockIdx.y): this slice owns the channel chunks [c0, c0 + nchunks)
-    const int chunks_all = p.Cin / BKE;
-    int c0 = 0, nchunks = chunks_all;
-    if (p.splitk > 1) {
-        const int per = (chunks_all + p.splitk - 1) / p.splitk;
-        c0 = blockIdx.y * per;
-        nchunks = min(chunks_all, c0 + per) - c0;
-    }
+    const ChunkSlice sl = patch_chunk_slice(p.Cin / BKE, p.splitk, blockIdx.y);
+    const int c0 = sl.c0, nchunks = sl.nchunks;
     const int U = nchunks * 9;  // (chunk, tap) units; weights of unit (lc, tap) start at element tap*Cin + (c0+lc)*BKE
 
     if (wave >= 4) {
@@ -98,17 +71,17 @@ __global__ __launch_bounds__(NT) void conv3x3_patch2_kernel(GemmParams p) {
             int n = bn * BN + row;
             n = n < p.N ? n : p.N - 1;      // channels >= N are never stored
             w_off[j] = (unsigned)(((size_t)n * p.Kpad + ch * 8) * 2);
-            w_lds[j] = swz2(row, ch);
+            w_lds[j] = swz8(row, ch);
         }
         // patch slot j of this thread: LDS offset (-1: none), in-image flag, byte offset of channel chunk 0 in A
         auto patch_slot = [&](int j, int& lds, bool& ok, unsigned& off) __attribute__((always_inline)) {
             const int s = lt + NL * j;
             const int prow = s >> 3, ch = s & 7;
-            const int iy = prow / PW, ix = prow - iy * PW;
+            const int iy = prow / G::PW, ix = prow - iy * G::PW;
             const int gy = sy0 + iy, gx = sx0 + ix;
             ok = s < G::P_SLOTS && (unsigned)gy < (unsigned)p.Hin && (unsigned)gx < (unsigned)p.Win;
             off = ok ? (unsigned)((((size_t)(sample * p.Hin + gy) * p.Win + gx) * p.lda + ch * 8) * 2) : 0u;
-            lds = s < G::P_SLOTS ? swz2(prow, ch) : -1;
+            lds = s < G::P_SLOTS ? swz8(prow, ch) : -1;
         };
         unsigned p_off[G::P_IT];
 #pragma unroll
@@ -165,10 +138,6 @@ __global__ __launch_bounds__(NT) void conv3x3_patch2_kernel(GemmParams p) {
 #pragma unroll
             for (int tap = 0; tap < 9; ++tap) {
                 const int u = lc * 9 + tap;
-#if PATCH2_DIAG == 1   /* timing diagnostic: loaders only keep the barrier count */
-                __syncthreads();
-                continue;
-#endif
                 // weight tile of unit u+2 first (L2), HBM-latency patch pieces after it: vmcnt retires in issue order
                 const char* bw = w_base(u + 2);
                 PD_W5(W_LD)
@@ -210,11 +179,11 @@ __global__ __launch_bounds__(NT) void conv3x3_patch2_kernel(GemmParams p) {
     // A fragment of patch row py = wm*4+m for tap (ky,kx), k-step ks: 16 consecutive LDS patch rows (16 x of one patch row)
     auto af_off = [&](int m, int ky, int kx, int ks, int frv) __attribute__((always_inline)) {
         const int py = wm * 4 + m;
-        const int prow = (((y0 - 1 + py + ky) >> UPS) - sy0) * PW + (((x0 - 1 + frv + kx) >> UPS) - sx0);
-        return swz2(prow, ks * 4 + fq);
+        const int prow = (((y0 - 1 + py + ky) >> UPS) - sy0) * G::PW + (((x0 - 1 + frv + kx) >> UPS) - sx0);
+        return swz8(prow, ks * 4 + fq);
     };
     // W fragment of channel tile n: (row>>1)&7 of row n*16+fr does not depend on n -> one base + n*2048
-    auto wf_off = [&](int ks, int frv) __attribute__((always_inline)) { return swz2(frv, ks * 4 + fq); };
+    auto wf_off = [&](int ks, int frv) __attribute__((always_inline)) { return swz8(frv, ks * 4 + fq); };
 
     uint4 afA[4], afB[4];   // A fragments of the ks = 0 / ks = 1 half-unit
     // weight fragments: a ring of 4, requested 3 MFMA groups (192 MFMA cycles) ahead of their use -- a ds_read_b128 issued
@@ -272,12 +241,8 @@ __global__ __launch_bounds__(NT) void conv3x3_patch2_kernel(GemmParams p) {
             if constexpr (g < 4) afB[g] = *reinterpret_cast<const uint4*>(pa + af_off(g, ky, kx, 1, frv));
             if constexpr (g >= 12 && g < 16) afA[g - 12] = *reinterpret_cast<const uint4*>(pan2 + af_off(g - 12, nky, nkx, 0, frv));
             const uint4 wc = WR(GI);
-#if PATCH2_DIAG != 2   /* 2: timing diagnostic, compute waves issue no MFMAs */
 #pragma unroll
             for (int m = 0; m < 4; ++m) mma<P>(wc, ks ? afB[m] : afA[m], acc[n][m]);
-#else
-            acc[n][0][0] += __uint_as_float(wc.x);
-#endif
         });
         // pin the interleave: per MFMA group of 4, the LDS reads issued in front of it (1 weight fragment 3 groups ahead,
         // plus one A fragment in groups 0-3 and 12-15).  hipcc otherwise sinks every read next to its first use (it is at
@@ -333,25 +298,15 @@ __global__ __launch_bounds__(NT) void conv3x3_patch2_kernel(GemmParams p) {
 
 template <int P, int UPS, bool RELU = false>
 int launch_patch2(const GemmParams& p, hipStream_t s) {
-    using G = Geom2<UPS>;
-    static unsigned long long attr_done = 0;
-    auto kfn = conv3x3_patch2_kernel<P, UPS, RELU>;
-    if (ensure_dyn_smem(reinterpret_cast<const void*>(kfn), G::SMEM, &attr_done)) return 1;
-    const int mtiles = (p.M / (p.Hout * p.Wout)) * (p.Hout / TP) * (p.Wout / TP), ntiles = (p.N + BN - 1) / BN;
-    hipLaunchKernelGGL(kfn, dim3(mtiles * ntiles, p.splitk > 1 ? p.splitk : 1), dim3(NT), G::SMEM, s, p);
-    if (hipGetLastError() != hipSuccess) return 1;
-    return (p.splitk > 1 && !p.defer_finalize) ? launch_splitk_finalize(p, s) : 0;
+    return launch_patch_grid<conv3x3_patch2_kernel<P, UPS, RELU>, NT>(p, Geom2<UPS>::SMEM, s);
 }
 
 }  // namespace
 
-// same eligibility as conv_patch_tiles(); 2-byte compute types only, no fused GroupNorm
 int launch_conv_patch2(const GemmParams& p, int prec, hipStream_t s) {
-    if (p.gn_coef || (prec != DT_BF16 && prec != DT_F16)) return 1;
-    if (p.act == 5) {   // ACT_RELU: the plain conv only
-        if (p.ups) return 1;
+    if (!conv_patch_eligible_2byte(p, prec)) return 1;
+    if (p.act == 5)   // ACT_RELU: the plain conv only (patch_eligible_tiles)
         return prec == DT_F16 ? launch_patch2<DT_F16, 0, true>(p, s) : launch_patch2<DT_BF16, 0, true>(p, s);
-    }
     if (prec == DT_F16) return p.ups ? launch_patch2<DT_F16, 1>(p, s) : launch_patch2<DT_F16, 0>(p, s);
     return p.ups ? launch_patch2<DT_BF16, 1>(p, s) : launch_patch2<DT_BF16, 0>(p, s);
 }

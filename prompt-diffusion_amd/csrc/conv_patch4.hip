@@ -4,7 +4,7 @@
 // Why: on this chip ONE wave issues v_mfma_f32_16x16x32 every 27 cycles (16 would be the pipe's rate; two waves per SIMD reach 17)
 // but v_mfma_f32_32x32x16 every 32-33 -- the pipe's full rate (tools/micro/mfma_issue.hip: 1.11-1.19 against 1.59-1.65 PFLOP/s).
 // The 8-wave generations keep two waves per SIMD in lockstep (request, read, MFMA, barrier: 2.6 k cycles per (chunk, tap) unit whose
-// MFMAs need 1.28 k) or half a unit apart (conv_patch3.hip: the load phase of 24 fragment reads + LDS-DMA requests takes 1.1 k cycles
+// MFMAs need 1.28 k) or half a unit apart (the retired ping-pong experiment, the skipped column of tools/micro/conv_pp.hip: the load phase of 24 fragment reads + LDS-DMA requests takes 1.1 k cycles
 // against 0.68 k of MFMAs).  Here a wave owns 4 patch rows (64 pixels) x all 160 channels = 2 x 5 accumulator tiles of 32 x 32
 // (160 registers), so a weight fragment feeds two MFMAs and a pixel fragment five (28 fragment reads per 40 MFMAs, 112 KB of LDS reads
 // per unit and block instead of 144-192), and its own instruction stream overlaps everything: the fragments of K step t + 2 (16
@@ -13,7 +13,7 @@
 //
 // Padding: the patch pieces are buffer loads to LDS (buffer_load_dwordx4 ... lds) whose lanes outside the image carry an offset past
 // the descriptor's range -- the hardware writes zeros for them; no lane masks, no zeroed buffer.
-// Same block tiling, LDS images and K order as conv_patch3.hip (a block owns a 16x16 patch of output pixels of one
+// Same block tiling (conv_patch_common.h), LDS images and K order as conv_patch2.hip (a block owns a 16x16 patch of output pixels of one
 // sample x 160 output channels; per 128-byte channel chunk the (16+2)^2 input patch sits in LDS once and all 9 taps run from it; the
 // [160 x 128 B] weight tile of each unit streams from L2 through a ring of 3); results are bit-identical to the other generations (the
 // MFMA shapes sum the same exact products in the same order).
@@ -25,22 +25,16 @@
 //        step 4 u - 1; patch pieces of chunk c + 1 go to the other patch buffer, last read in chunk c - 1.
 #include <type_traits>
 
-#include "pd_common.h"
-#include "pd_mma.h"
+#include "conv_patch_common.h"
 #include "pd_stamp.h"
 
 namespace {
+using namespace patch_conv;
 
-constexpr int TP = 16;             // patch is TP x TP output pixels
-constexpr int BN = 160;
 constexpr int NT = 256;            // threads: 4 waves, one per SIMD
-constexpr int ROWB = 128;          // bytes of K per LDS row (64 two-byte channels)
-constexpr int BKE = 64;
-constexpr int W_TILE = BN * ROWB;  // 20480
+constexpr int BKE = 64;            // two-byte channels per LDS row
 constexpr int NWB = 3;             // weight tile ring
 
-// 16-byte chunk index ^= (row >> 1) & 7 (conv_patch3.hip)
-__device__ __forceinline__ int swz4(int row, int chunk) { return (row * ROWB) + (((chunk ^ (row >> 1)) & 7) << 4); }
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 template <int P> __device__ __forceinline__ void mma32(const uint4& w, const uint4& a, f32x16& acc) {
     if constexpr (P == DT_F16) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, w), __builtin_bit_cast(f16x8, a), acc, 0, 0, 0);
@@ -48,13 +42,13 @@ template <int P> __device__ __forceinline__ void mma32(const uint4& w, const uin
 }
 
 template <int UPS>
-struct Geom4 {
-    static constexpr int PW = UPS ? TP / 2 + 2 : TP + 2;   // patch rows/cols held in LDS (source resolution)
-    static constexpr int PROWS = PW * PW;
+struct Geom4 : PatchGeomBase<UPS> {
+    using PatchGeomBase<UPS>::PROWS;
     static constexpr int P_PIECES = (PROWS + 7) / 8;       // 41 (plain) / 13 (upsampling) LDS-DMA pieces of 8 rows
     static constexpr int P_PER_WAVE = (P_PIECES + 3) / 4;  // 11 / 4: wave w requests pieces w + 4 j
-    static constexpr int P_BYTES = 4 * P_PER_WAVE * 8 * ROWB;   // whole pieces for every (wave, j): the ones past the patch are lanes out of range (zeros)
+    static constexpr int P_BYTES = 4 * P_PER_WAVE * 8 * ROWB;   // (not the base's PROWS * ROWB) whole pieces for every (wave, j): the ones past the patch are lanes out of range (zeros)
     static constexpr int SMEM = 2 * P_BYTES + NWB * W_TILE;
+    static_assert(SMEM <= 160 * 1024, "LDS");
     // the next chunk's patch: taps 1-7 request per_tap(tap) <= 2 pieces per wave, the larger counts first (11 = 2 2 2 2 1 1 1); the
     // counted waits retire the last one in front of the barrier of tap 8
     static constexpr int per_tap(int tap) { return tap >= 1 && tap <= 7 ? (P_PER_WAVE + 7 - tap) / 7 : 0; }
@@ -91,9 +85,7 @@ PD_T_ONLY(__device__ unsigned long long* g_w4_stamps = nullptr;)
 template <int P, int UPS>
 __global__ __launch_bounds__(NT, 1) void conv3x3_w4_kernel(GemmParams p) {
     using G = Geom4<UPS>;
-    constexpr int PW = G::PW;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-
 
     const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
 
@@ -101,28 +93,13 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_w4_kernel(GemmParams p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, lh = lane >> 5;   // operand row / column of the 32x32x16 MFMA, K half
 
-    const int ptx = p.Wout / TP, pty = p.Hout / TP;
-    const int mtiles = (p.M / (p.Hout * p.Wout)) * ptx * pty, ntiles = (p.N + BN - 1) / BN;
-    const int nblk = mtiles * ntiles;
-    int bid = blockIdx.x;
-    {   // XCD-aware tile order (gemm.hip)
-        const int q = nblk >> 3, r = nblk & 7, x = bid & 7;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-    }
-    const int bm = bid / ntiles, bn = bid % ntiles;
-    const int sample = bm / (ptx * pty);
-    const int prem = bm - sample * (ptx * pty);
-    const int y0 = (prem / ptx) * TP, x0 = (prem - (prem / ptx) * ptx) * TP;  // patch origin (output coords)
-    const int sy0 = (y0 - 1) >> UPS, sx0 = (x0 - 1) >> UPS;                   // source-resolution origin of LDS patch index 0
+    // the tile as plain ints: the patch-piece source and the LDS patch row below are this kernel's own text (conv_patch_common.h says why)
+    const PatchTile t = patch_tile<UPS>(p);
+    const int bn = t.bn, sample = t.sample, y0 = t.y0, x0 = t.x0, sy0 = t.sy0, sx0 = t.sx0;
 
     // split-K (blockIdx.y): this slice owns the channel chunks [c0, c0 + nchunks); units are counted from the slice's start
-    const int chunks_all = p.Cin / BKE;
-    int c0 = 0, nchunks = chunks_all;
-    if (p.splitk > 1) {
-        const int per = (chunks_all + p.splitk - 1) / p.splitk;
-        c0 = blockIdx.y * per;
-        nchunks = min(chunks_all, c0 + per) - c0;
-    }
+    const ChunkSlice sl = patch_chunk_slice(p.Cin / BKE, p.splitk, blockIdx.y);
+    const int c0 = sl.c0, nchunks = sl.nchunks;
     [[maybe_unused]] const int U = nchunks * 9;
 
     // ---- this lane's LDS-DMA sources.  A piece is 8 LDS rows; lane l writes row 8 * piece + (l >> 3), slot l & 7, and fetches the
@@ -132,7 +109,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_w4_kernel(GemmParams p) {
 #pragma unroll
     for (int j = 0; j < 5; ++j) {
         const int row = (wave + 4 * j) * 8 + lrow;
-        const int chunk = (lslot ^ (row >> 1)) & 7;
+        const int chunk = swz8_chunk(row, lslot);
         const int n = min(bn * BN + row, p.N - 1);
         w_off[j] = (unsigned)(((size_t)n * p.Kpad + chunk * 8) * 2);
     }
@@ -142,8 +119,8 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_w4_kernel(GemmParams p) {
 #pragma unroll
     for (int j = 0; j < G::P_PER_WAVE; ++j) {
         const int prow = (wave + 4 * j) * 8 + lrow;
-        const int chunk = (lslot ^ (prow >> 1)) & 7;
-        const int iy = prow / PW, ix = prow - iy * PW;
+        const int chunk = swz8_chunk(prow, lslot);
+        const int iy = prow / G::PW, ix = prow - iy * G::PW;
         const int gy = sy0 + iy, gx = sx0 + ix;
         const bool ok = prow < G::PROWS && (unsigned)gy < (unsigned)p.Hin && (unsigned)gx < (unsigned)p.Win;
         p_off[j] = ok ? (unsigned)((((size_t)(sample * p.Hin + gy) * p.Win + gx) * p.lda + chunk * 8) * 2) : OOB;
@@ -191,7 +168,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_w4_kernel(GemmParams p) {
     // Fragment addresses.  Chunk 2 s + lh of a row whose swizzle term is x sits at ((2 s + lh) ^ x) & 7 = (2 s) ^ ((lh ^ x) & 7): per row one
     // base and one pre-shifted y = ((lh ^ x) & 7) << 4, per step one v_xad (y ^ 32 s) + base.
     struct ReadCtx { unsigned pb[2], py[2], wb; };   // LDS byte addresses
-    const unsigned wy = (unsigned)(((lh ^ (l31 >> 1)) & 7) << 4);   // channel row 32 n + l31: (row >> 1) & 7 = (l31 >> 1) & 7 for every n
+    const unsigned wy = (unsigned)(swz8_chunk(l31, lh) << 4);   // channel row 32 n + l31: (row >> 1) & 7 = (l31 >> 1) & 7 for every n
     auto read_ctx = [&](auto TAPC, int lc) __attribute__((always_inline)) -> ReadCtx {
         constexpr int tap = decltype(TAPC)::value;
         constexpr int ky = tap / 3, kx = tap % 3;
@@ -200,9 +177,9 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_w4_kernel(GemmParams p) {
         asm volatile("" : "+v"(lv));   // keep the per-tap addresses out of loop-invariant hoisting (they would occupy registers for the whole kernel)
 #pragma unroll
         for (int m = 0; m < 2; ++m) {  // pixel l31 of tile m: patch row 4 * wave + 2 m + (l31 >> 4), column l31 & 15
-            const int prow = (((y0 - 1 + 4 * wave + 2 * m + (lv >> 4) + ky) >> UPS) - sy0) * PW + (((x0 - 1 + (lv & 15) + kx) >> UPS) - sx0);
+            const int prow = (((y0 - 1 + 4 * wave + 2 * m + (lv >> 4) + ky) >> UPS) - sy0) * G::PW + (((x0 - 1 + (lv & 15) + kx) >> UPS) - sx0);
             r.pb[m] = (unsigned)((lc & 1) * G::P_BYTES + prow * ROWB);
-            r.py[m] = (unsigned)(((lh ^ (prow >> 1)) & 7) << 4);
+            r.py[m] = (unsigned)(swz8_chunk(prow, lh) << 4);
         }
         r.wb = (unsigned)(2 * G::P_BYTES + (tap % NWB) * W_TILE + lv * ROWB);   // 9 units per chunk keep unit % 3 == tap % 3
         return r;
@@ -447,24 +424,14 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_w4_kernel(GemmParams p) {
 
 template <int P, int UPS>
 int launch_w4(const GemmParams& p, hipStream_t s) {
-    using G = Geom4<UPS>;
-    static_assert(G::SMEM <= 160 * 1024, "LDS");
-    static unsigned long long attr_done = 0;
-    auto kfn = conv3x3_w4_kernel<P, UPS>;
-    if (ensure_dyn_smem(reinterpret_cast<const void*>(kfn), G::SMEM, &attr_done)) return 1;
-    const int mtiles = (p.M / (p.Hout * p.Wout)) * (p.Hout / TP) * (p.Wout / TP), ntiles = (p.N + BN - 1) / BN;
-    hipLaunchKernelGGL(kfn, dim3(mtiles * ntiles, p.splitk > 1 ? p.splitk : 1), dim3(NT), G::SMEM, s, p);
-    if (hipGetLastError() != hipSuccess) return 1;
-    return (p.splitk > 1 && !p.defer_finalize) ? launch_splitk_finalize(p, s) : 0;
+    return launch_patch_grid<conv3x3_w4_kernel<P, UPS>, NT>(p, Geom4<UPS>::SMEM, s);
 }
 
 }  // namespace
 
-// shapes conv_patch_tiles() accepts, 2-byte compute types, no fused GroupNorm, plain epilogue; 31-bit byte ranges inside each operand
-// (buffer descriptors) and 32-bit weight offsets
+// what generation 2 takes, with a plain epilogue, 31-bit byte ranges inside each operand (buffer descriptors) and 32-bit weight offsets
 bool conv_patch4_eligible(const GemmParams& p, int prec) {
-    if (prec != DT_F16 && prec != DT_BF16) return false;
-    if (p.gn_coef || p.a_dt != prec || p.Cin % BKE || p.K != 9 * p.Cin || p.act != 0) return false;
+    if (!conv_patch_eligible_2byte(p, prec) || p.act != 0) return false;
     const unsigned long long a_bytes = (unsigned long long)(p.M / (p.Hout * p.Wout)) * p.Hin * p.Win * (unsigned)p.lda * 2ull;
     const unsigned long long w_bytes = (unsigned long long)p.N * (unsigned)p.Kpad * 2ull;
     const unsigned long long c_bytes = (unsigned long long)p.M * (unsigned)(p.ldc > p.ldr ? p.ldc : p.ldr) * 4ull;

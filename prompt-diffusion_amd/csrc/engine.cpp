@@ -861,6 +861,7 @@ int pd_engine::gemm(const WMat& m, const Act& in, Act& out, const GemmCall& c) {
     PD_TRY(check_arena());
     const bool gemv = pl.family == GEMM_GEMV, ring = pl.family == GEMM_RING;
     ++launches;
+    gemm_family = pl.family;
     ProfRec rec{};
     if (profiling && gemv) {
         prof_begin(rec, 1, 2.0 * (double)p.M * (double)m.Nout * (double)m.cin);

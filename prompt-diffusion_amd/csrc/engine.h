@@ -441,6 +441,7 @@ struct pd_engine {
     long long gn_from_slabs = 0;   // GroupNorm launches that summed a split-K GEMM's slabs (stat "gn_from_slabs")
     long long ring_launches = 0;   // launches that took gemm_ring.hip (stat "ring_launches")
     int gn_kernel = 0;             // GN_KIND_* of the last groupnorm() launch (stat "gn_kernel"), set where the launch is decided
+    int gemm_family = -1;          // GemmFamily of the last gemm() launch (stat "gemm_family"), set where gemm() launches; -1: none yet
     // optional per-launch timing (bench.py roofline leg): HIP events around every contraction launch
     struct ProfRec { hipEvent_t a, b; int klass; double flops; int M, N, K, taps; };
     bool profiling = false;

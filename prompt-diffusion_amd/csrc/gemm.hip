@@ -33,7 +33,7 @@ constexpr int BKB = 128;  // bytes of K per LDS row
 // Two block shapes: 128 x 160 with 4 waves (2 blocks per CU) and 256 x 160 with 8 waves (1 block per CU,
 // 1.4x fewer operand bytes per FLOP) for layers with enough rows to fill the chip with the big tile.
 
-__device__ __forceinline__ int swz(int row, int chunk) { return (row * BKB) + (((chunk ^ (row >> 1)) & 7) << 4); }
+static_assert(BKB == 128, "swz8 (pd_common.h) is the swizzle of 128-byte rows");
 
 // P: compute type (DT_F32: fp32 MFMA mode; DT_BF16 / DT_F16: 2-byte operands).  CONV: 3x3 gather (else rows of A
 // are contiguous).  AF32: 2-byte compute with an fp32 A source (converted while staging; only meaningful when P != DT_F32).
@@ -65,12 +65,7 @@ __global__ __launch_bounds__(WM * WN * 64, (BM == 128 && WM * WN == 8) ? 4 : 2) 
     // XCD-aware tile order: blocks b and b+8 share an XCD/L2; give each XCD a contiguous run of
     // tiles (n fastest) so neighbouring tiles that share the A rows hit the same L2.
     const int mtiles = (p.M + BM - 1) / BM, ntiles = (p.N + BN - 1) / BN;
-    const int nblk = mtiles * ntiles;
-    int bid = blockIdx.x;
-    {
-        const int q = nblk >> 3, r = nblk & 7, x = bid & 7;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-    }
+    const int bid = xcd_tile_order(blockIdx.x, mtiles * ntiles);
     // (a 4 x 8 super-tile order inside each XCD's run -- the ~32 blocks in flight sharing 4 A panels and 8 weight panels --
     // measured within noise on the widest layers, 24-32 tiles across, and was dropped)
     const int bm = bid / ntiles, bn = bid % ntiles;
@@ -223,12 +218,12 @@ __global__ __launch_bounds__(WM * WN * 64, (BM == 128 && WM * WN == 8) ? 4 : 2) 
                 v = RA(S, I);
             }
             if (!(rmask & (1u << i))) v = make_uint4(0, 0, 0, 0);
-            *reinterpret_cast<uint4*>(sa + swz(row0 + ROWS_PER_IT * i, chunk)) = v;
+            *reinterpret_cast<uint4*>(sa + swz8(row0 + ROWS_PER_IT * i, chunk)) = v;
         });
         static_for<B_ITERS>([&](auto I) __attribute__((always_inline)) {
             constexpr int i = decltype(I)::value;
             if (BN % ROWS_PER_IT == 0 || row0 + ROWS_PER_IT * i < BN)
-                *reinterpret_cast<uint4*>(sb + swz(row0 + ROWS_PER_IT * i, chunk)) = RB(S, I);
+                *reinterpret_cast<uint4*>(sb + swz8(row0 + ROWS_PER_IT * i, chunk)) = RB(S, I);
         });
     };
 
@@ -247,12 +242,12 @@ __global__ __launch_bounds__(WM * WN * 64, (BM == 128 && WM * WN == 8) ? 4 : 2) 
             i32x8 af[MT];
 #pragma unroll
             for (int m = 0; m < MT; ++m)
-                af[m] = prep_f8(*reinterpret_cast<const uint4*>(sa + swz(wm * WTM + m * 16 + fr, fq)),
-                                *reinterpret_cast<const uint4*>(sa + swz(wm * WTM + m * 16 + fr, 4 + fq)));
+                af[m] = prep_f8(*reinterpret_cast<const uint4*>(sa + swz8(wm * WTM + m * 16 + fr, fq)),
+                                *reinterpret_cast<const uint4*>(sa + swz8(wm * WTM + m * 16 + fr, 4 + fq)));
 #pragma unroll
             for (int n = 0; n < NT; ++n) {
-                const i32x8 wf = prep_f8(*reinterpret_cast<const uint4*>(sb + swz(wn * WTN + n * 16 + fr, fq)),
-                                         *reinterpret_cast<const uint4*>(sb + swz(wn * WTN + n * 16 + fr, 4 + fq)));
+                const i32x8 wf = prep_f8(*reinterpret_cast<const uint4*>(sb + swz8(wn * WTN + n * 16 + fr, fq)),
+                                         *reinterpret_cast<const uint4*>(sb + swz8(wn * WTN + n * 16 + fr, 4 + fq)));
 #pragma unroll
                 for (int m = 0; m < MT; ++m) mma_f8(wf, af[m], acc[n][m]);
             }
@@ -262,12 +257,12 @@ __global__ __launch_bounds__(WM * WN * 64, (BM == 128 && WM * WN == 8) ? 4 : 2) 
             FragX2 af[MT], wf[NT];
 #pragma unroll
             for (int m = 0; m < MT; ++m)
-                af[m] = prep_x2(*reinterpret_cast<const uint4*>(sa + swz(wm * WTM + m * 16 + fr, fq)),
-                                *reinterpret_cast<const uint4*>(sa + swz(wm * WTM + m * 16 + fr, 4 + fq)));
+                af[m] = prep_x2(*reinterpret_cast<const uint4*>(sa + swz8(wm * WTM + m * 16 + fr, fq)),
+                                *reinterpret_cast<const uint4*>(sa + swz8(wm * WTM + m * 16 + fr, 4 + fq)));
 #pragma unroll
             for (int n = 0; n < NT; ++n)
-                wf[n] = prep_x2(*reinterpret_cast<const uint4*>(sb + swz(wn * WTN + n * 16 + fr, fq)),
-                                *reinterpret_cast<const uint4*>(sb + swz(wn * WTN + n * 16 + fr, 4 + fq)));
+                wf[n] = prep_x2(*reinterpret_cast<const uint4*>(sb + swz8(wn * WTN + n * 16 + fr, fq)),
+                                *reinterpret_cast<const uint4*>(sb + swz8(wn * WTN + n * 16 + fr, 4 + fq)));
 #pragma unroll
             for (int n = 0; n < NT; ++n)
 #pragma unroll
@@ -280,9 +275,9 @@ __global__ __launch_bounds__(WM * WN * 64, (BM == 128 && WM * WN == 8) ? 4 : 2) 
             typename Frag<P>::A af[MT];
             typename Frag<P>::W wf[NT];
 #pragma unroll
-            for (int m = 0; m < MT; ++m) af[m] = prep_a<P>(*reinterpret_cast<const uint4*>(sa + swz(wm * WTM + m * 16 + fr, ks * 4 + fq)));
+            for (int m = 0; m < MT; ++m) af[m] = prep_a<P>(*reinterpret_cast<const uint4*>(sa + swz8(wm * WTM + m * 16 + fr, ks * 4 + fq)));
 #pragma unroll
-            for (int n = 0; n < NT; ++n) wf[n] = prep_w<P>(*reinterpret_cast<const uint4*>(sb + swz(wn * WTN + n * 16 + fr, ks * 4 + fq)));
+            for (int n = 0; n < NT; ++n) wf[n] = prep_w<P>(*reinterpret_cast<const uint4*>(sb + swz8(wn * WTN + n * 16 + fr, ks * 4 + fq)));
 #pragma unroll
             for (int n = 0; n < NT; ++n)
 #pragma unroll

@@ -239,11 +239,7 @@ __global__ __launch_bounds__(GNF_THREADS) void gn_fused_kernel(const void* __res
     extern __shared__ __attribute__((aligned(16))) char slab[];   // [HW][BC] raw input, then [waves][4][2] doubles
     const int nb = C / BC;
     // consecutive bundles of a sample (which share 128-byte lines) on the same XCD: blocks b and b+8 share an L2
-    int bid = blockIdx.x;
-    {
-        const int total = gridDim.x, q = total >> 3, r = total & 7, xk = bid & 7;
-        bid = (xk < r ? xk * (q + 1) : r * (q + 1) + (xk - r) * q) + (bid >> 3);
-    }
+    const int bid = xcd_tile_order(blockIdx.x, gridDim.x);
     const int b = bid / nb, bundle = bid - b * nb;
     const int tid = threadIdx.x;
     const int nvec = BC / VEC;              // vectors per pixel in this bundle
@@ -554,11 +550,8 @@ __global__ __launch_bounds__(NL == 16 ? 512 : 1024) void gn_reg_kernel(const voi
     constexpr int EV = VB / 2;           // channels per vector
     constexpr int NW = VB / 4;           // dwords per vector
     __shared__ double red[16][2];
-    int bid = blockIdx.x;
-    {   // consecutive groups of a sample (they share 128-byte lines) on the same XCD: blocks b and b + 8 share an L2
-        const int total = gridDim.x, q = total >> 3, r = total & 7, xk = bid & 7;
-        bid = (xk < r ? xk * (q + 1) : r * (q + 1) + (xk - r) * q) + (bid >> 3);
-    }
+    // consecutive groups of a sample (they share 128-byte lines) on the same XCD
+    const int bid = xcd_tile_order(blockIdx.x, gridDim.x);
     const int b = bid / groups, g = bid - b * groups;
     const int tid = threadIdx.x;
     const int v = tid % nv, pr = tid / nv;          // pr < 64

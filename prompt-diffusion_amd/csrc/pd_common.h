@@ -94,6 +94,19 @@ __device__ __forceinline__ float gelu_fast(float x) {
     return 0.5f * x * (1.0f + copysignf(erfz, x));
 }
 
+// XCD-aware block order: blocks b and b + 8 share an XCD / L2, so hardware block `bid` of `nblk` takes the work item that gives each
+// XCD one contiguous run of items -- neighbours that share operand rows or 128-byte lines then hit the same L2.  (gemm_ring.hip's
+// persistent blocks walk a run per XCD instead: a different scheme.)
+__device__ __forceinline__ int xcd_tile_order(int bid, int nblk) {
+    const int q = nblk >> 3, r = nblk & 7, x = bid & 7;
+    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
+}
+// Byte offset of 16-byte chunk `chunk` of row `row` in an LDS tile of 128-byte rows whose chunks are permuted by XORing the chunk
+// index with (row >> 1) & 7: fragment reads of 16 consecutive rows starting at a multiple of 16 are conflict-free.  swz8_chunk: the
+// slot a chunk sits in (and, the XOR being an involution, the chunk a slot holds).
+__device__ __forceinline__ int swz8_chunk(int row, int chunk) { return (chunk ^ (row >> 1)) & 7; }
+__device__ __forceinline__ int swz8(int row, int chunk) { return (row * 128) + (swz8_chunk(row, chunk) << 4); }
+
 // 4 consecutive elements of a [.., C] row, as floats, from an f32 or bf16 buffer
 __device__ __forceinline__ f32x4 load4(const void* base, size_t idx, int dt) {
     f32x4 r;

@@ -1183,6 +1183,11 @@ int64_t pd_get_stat(pd_engine* e, const char* key) {
         static_assert(GN_KIND_TWO_PASS == PD_GN_TWO_PASS && GN_KIND_LDS_SLAB == PD_GN_LDS_SLAB && GN_KIND_REGISTER == PD_GN_REGISTER, "pdengine.h");
         return (int64_t)e->gn_kernel;
     }
+    if (!strcmp(key, "gemm_family")) {   // which kernel family the last pd_engine::gemm launch took
+        static_assert(GEMM_GEMV == PD_GEMM_GEMV && GEMM_PATCH1 == PD_GEMM_PATCH1 && GEMM_PATCH2 == PD_GEMM_PATCH2 && GEMM_PATCH4 == PD_GEMM_PATCH4 &&
+                      GEMM_RING == PD_GEMM_RING && GEMM_IGEMM == PD_GEMM_IGEMM, "pdengine.h");
+        return (int64_t)e->gemm_family;
+    }
     if (!strcmp(key, "steps")) return (int64_t)e->ses.S;
     if (!strcmp(key, "cfg_shared")) return (int64_t)((e->ses.share_u ? 1 : 0) | (e->ses.share_c ? 2 : 0) | (e->ses.cn_cond_only ? 4 : 0));
     if (!strcmp(key, "lora_base_bytes")) return (int64_t)e->lora_bytes(true);   // base copies W0 of the adapted parameters

@@ -126,6 +126,49 @@ def test_conv2d_patch4_matches_first_generation(eng, B, Cin, H, Cout, ups):
     assert np.array_equal(y1, y0) and np.array_equal(y1r, y0r)
 
 
+PATCH1, PATCH2, PATCH4 = 1, 2, 3     # PD_GEMM_* of include/pdengine.h (stat "gemm_family")
+PATCH_UNSPLIT = [({"patch4": 1}, PATCH4), ({"patch4": 0, "conv_patch2_tiles": 1}, PATCH2), ({"patch4": 0, "conv_patch2": 0}, PATCH1)]
+PATCH_SPLIT = [({"patch_split_tiles": 1, "conv_patch2": 1}, PATCH2), ({"patch_split_tiles": 1, "conv_patch2": 0}, PATCH1)]
+PATCH_DEFAULTS = {"patch4": 1, "conv_patch2": 1, "conv_patch2_tiles": 768, "patch_split_tiles": 64}
+
+
+@pytest.mark.parametrize("B,Cin,H,Cout,ups,settings", [
+    (24, 128, 32, 164, False, PATCH_UNSPLIT),   # 192 blocks, two channel chunks, ragged second channel tile, N % 8 != 0
+    (48, 64, 16, 96, True, PATCH_UNSPLIT),      # 192 blocks, fused nearest-x2 upsample: source patch 10 x 10
+    (2, 576, 16, 168, False, PATCH_SPLIT),      # split: 9 chunks (2-byte modes) in 2 slices of 5 and 4, the uneven case of the slice
+])
+def test_conv2d_patch_generations_agree(eng, B, Cin, H, Cout, ups, settings):
+    """The three LDS-patch conv generations share their tile geometry (csrc/conv_patch_common.h): every option setting runs the
+    generation it names (stat "gemm_family"; the fp32-storage modes have the first generation only) and, in the 2-byte modes, all
+    of them agree bit for bit -- they sum the same products in the same order and end in the same epilogue arithmetic -- plain and
+    with the scale + residual epilogue.  No oracle here: test_conv2d and the two tests above hold these kernels to it."""
+    g = rng(23)
+    x = g.standard_normal((B, Cin, H, H), dtype=np.float32)
+    w = (g.standard_normal((Cout, Cin, 3, 3), dtype=np.float32) / np.sqrt(Cin * 9)).astype(np.float32)
+    b = g.standard_normal(Cout, dtype=np.float32) * 0.1
+    Ho = 2 * H if ups else H
+    r = g.standard_normal((B, Cout, Ho, Ho), dtype=np.float32)
+    two_byte = eng.prec in ("bf16", "f16")
+    got = []
+    try:
+        for opts, family in settings:
+            for k, v in opts.items():
+                eng.set_option(k, v)
+            y = eng.op_conv2d(x, w, b, upsample=ups)
+            ran = eng.stat("gemm_family")
+            yr = eng.op_conv2d(x, w, b, upsample=ups, scale=0.75, residual=r, stream_out=True)
+            got.append((opts, family if two_byte else PATCH1, ran, eng.stat("gemm_family"), y, yr))
+    finally:
+        for k, v in PATCH_DEFAULTS.items():
+            eng.set_option(k, v)
+    for opts, want, ran, ran_r, y, yr in got:
+        assert ran == want and ran_r == want, f"{opts}: ran family {ran} / {ran_r}, this setting is about {want}"
+    if two_byte:
+        for opts, _, _, _, y, yr in got[1:]:
+            assert np.array_equal(y, got[0][4]), f"{opts} differs from {got[0][0]}"
+            assert np.array_equal(yr, got[0][5]), f"{opts} differs from {got[0][0]} (scale + residual)"
+
+
 def test_conv2d_epilogues(eng):
     g = rng(2)
     x = g.standard_normal((2, 64, 8, 8), dtype=np.float32)
