@@ -252,6 +252,59 @@ int pd_hed_configure(pd_engine* e);
 int pd_hed_weights_missing(pd_engine* e);    /* 0 when not configured */
 int pd_hed_detect(pd_engine* e, const float* images, int32_t B, int32_t H, int32_t W, int32_t mem, int32_t what, float* out);
 
+/* Image ends: the uint8 pictures at both ends of a call, on the device.  Every step is integer or single-rounding fp32 arithmetic,
+ * so the results are bit-identical to the host code they replace (Pillow's 8-bit Image.resize, NumPy's / 255, clip, round).
+ *
+ * pd_resample_coefficients: the tables of Pillow's 8-bit resampler (Resample.c: precompute_coeffs + normalize_coeffs_8bpc) along
+ * one axis; host only (no engine, no GPU).  All of it in double until the last line:
+ *   scale = in / out, fs = max(scale, 1), support = S fs (S = 3 Lanczos, 0.5 box), *ksize = 2 ceil(support) + 1; per output xx:
+ *   center = (xx + 0.5) scale, xmin = max((int)(center - support + 0.5), 0), xmax = min((int)(center + support + 0.5), in),
+ *   w[x] = f((x + xmin - center + 0.5) * (1 / fs)) for x < xmax - xmin (Pillow multiplies by the reciprocal), divided by their sum
+ *   when that is non-zero; kk = (int)(w 2^22 + 0.5) for w >= 0, (int)(w 2^22 - 0.5) for w < 0 (truncation towards zero).
+ *   Lanczos f(t) = sinc(t) sinc(t / 3) for -3 <= t < 3 (sinc(t) = sin(pi t) / (pi t), 1 at 0), else 0; box f(t) = 1 for -0.5 < t <= 0.5.
+ * With bounds and kk NULL only *ksize is written; otherwise bounds[out_size][2] = (xmin, xmax - xmin) and kk[out_size][*ksize], zero
+ * padded.  Reductions beyond in_size > PD_RESAMPLE_MAX_SCALE * out_size are refused (callers keep their host path), as are unknown filters.
+ * A pass computes clip8((2^21 + sum pixel * kk) >> 22) in int32 (arithmetic shift) and stores uint8; the horizontal pass runs first
+ * and its rounded bytes feed the vertical one; a pass whose sizes are equal is skipped. */
+#define PD_RESAMPLE_LANCZOS 1   /* PIL.Image.LANCZOS */
+#define PD_RESAMPLE_BOX     4   /* PIL.Image.BOX */
+#define PD_RESAMPLE_MAX_SCALE 8
+int pd_resample_coefficients(int32_t in_size, int32_t out_size, int32_t filter, int32_t* ksize, int32_t* bounds, int32_t* kk);
+
+/* pd_image_load: uint8 pictures [Bs, Hs, Ws, 3] (NHWC) -> channels c_off .. c_off + 2 of an fp32 NCHW tensor [B, C, H, W]; the other
+ * channels are not touched (the two halves of an example pair land in one [B, 6, H, W] tensor).  Resampled to H x W with the tables
+ * above when the sizes differ, then y = v * mul + add with v = (float)u8 / 255.0f correctly rounded, the product and the sum each
+ * rounded once (the semantics of __fmul_rn / __fadd_rn; the kernels compile these lines with FP contraction off, because hipcc fuses
+ * even those two intrinsics into an FMA): (1, 0) gives [0, 1], (2, -1) gives [-1, 1], as NumPy's float32
+ * (a / 255) * mul + add does for any mul / add.  Bs == B, or Bs divides B: PD_IMAGE_REPEAT reads source b / (B / Bs) (np.repeat),
+ * PD_IMAGE_TILE source b % Bs (whole-batch repeats).  src and dst each live in their own memory space.  Tables, the intermediate
+ * picture of the horizontal pass and the staging of host buffers are engine-owned and grow on demand: a repeated call at the same
+ * shapes allocates nothing (stat "image_allocs" counts the allocations).  Runs on the engine's stream, synchronised on return. */
+#define PD_IMAGE_REPEAT 0
+#define PD_IMAGE_TILE   1
+typedef struct pd_image_load_args {
+    const uint8_t* src;       /* [Bs, Hs, Ws, 3] */
+    int32_t Bs, Hs, Ws;
+    int32_t mem_src;          /* PD_MEM_* of src */
+    float* dst;               /* [B, C, H, W] */
+    int32_t B, C, H, W;
+    int32_t c_off;            /* 0 <= c_off, c_off + 3 <= C */
+    int32_t mem_dst;          /* PD_MEM_* of dst */
+    int32_t filter;           /* PD_RESAMPLE_*; only read when the sizes differ */
+    int32_t batch_mode;       /* PD_IMAGE_*; only read when Bs != B */
+    float mul, add;
+    int32_t reserved[4];      /* zero */
+} pd_image_load_args;
+int pd_image_load(pd_engine* e, const pd_image_load_args* args);
+
+/* pd_image_store: fp32 NCHW [B, C, H, W], C in {1, 3} -> uint8 NHWC [B, H, W, C]: u = min(max(x * mul + add, 0), 1) * 255 in fp32
+ * (each operation rounded once), then PD_ROUND_NEAREST_EVEN (np.round: the pipeline's (im * 255).round()) or PD_ROUND_TRUNC
+ * (astype(uint8): the annotators' edge maps).  Inputs are finite.  Runs on the engine's stream, synchronised on return. */
+#define PD_ROUND_NEAREST_EVEN 0
+#define PD_ROUND_TRUNC        1
+int pd_image_store(pd_engine* e, const float* src, int32_t B, int32_t C, int32_t H, int32_t W, int32_t mem_src, float mul, float add,
+                   int32_t rounding, uint8_t* dst, int32_t mem_dst);
+
 /* operator boundary: eps = apply_model(x, t, cond), cldm/cldm.py:369-382.
  *   x [Bf,in_ch,h,w], t [Bf] (int64), ctx [Bf,L,D], pair [Bf,hint_ch,8h,8w], query [Bf,q_ch,8h,8w],
  *   scales [13] or NULL.  eps_out [Bf,out_ch,h,w].  residuals_out (optional): the 13 scaled

@@ -1,7 +1,8 @@
 """Annotators: photographs -> the condition maps Prompt-Diffusion takes as ``query`` and inside ``example_pair``.
 
 ``HEDdetector`` is the reference's ``annotator.hed.HEDdetector`` with the network on the engine (``Engine.hed``: the VGG trunk,
-the five side outputs and their fusion are gfx950 kernels behind ``pd_hed_detect``); only the uint8 ends stay on the host.
+the five side outputs and their fusion are gfx950 kernels behind ``pd_hed_detect``); the uint8 ends stay on the host, or run on
+the GPU as well with ``detect(..., device=True)``.
 ``HWC3`` and ``resize_image`` restate ``annotator/util.py`` in NumPy + PIL.  ``nms`` (cv2 blur / dilate) and the other annotators
 (MiDaS, UniFormer, Canny) are not built.
 """
@@ -55,11 +56,16 @@ class HEDdetector:
     def __init__(self, engine):
         self.engine = engine
 
-    def detect(self, images) -> np.ndarray:
-        """Batched form: uint8 [B, H, W, 3] RGB -> uint8 [B, H, W]; H and W multiples of 16."""
+    def detect(self, images, device: bool = False) -> np.ndarray:
+        """Batched form: uint8 [B, H, W, 3] RGB -> uint8 [B, H, W]; H and W multiples of 16.  device: the uint8 ends on the GPU
+        too -- Engine.image_load(1, 0), Engine.hed on the CUDA tensor, Engine.image_store(1, 0, "trunc") -- with the same bytes
+        out; only uint8 crosses the bus."""
         x = np.asarray(images)
         if x.dtype != np.uint8 or x.ndim != 4 or x.shape[3] != 3:
             raise ValueError(f"detect expects uint8 [B, H, W, 3], got {x.dtype} {x.shape}")
+        if device:
+            edge = self.engine.hed(self.engine.image_load(x, mul=1.0, add=0.0), what="edge")
+            return self.engine.image_store(edge, mul=1.0, add=0.0, rounding="trunc", host=True)[:, :, :, 0]
         # the reference divides the float32 image by 255 on its way in (:109-111); the engine flips RGB -> BGR itself
         x = np.ascontiguousarray(x.transpose(0, 3, 1, 2)).astype(np.float32) / np.float32(255.0)
         return edge_to_uint8(self.engine.hed(x, what="edge")[:, 0])

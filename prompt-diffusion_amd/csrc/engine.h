@@ -487,6 +487,18 @@ struct pd_engine {
     void build_hed();
     int hed_forward(const float* images_dev, int B, int H, int W, int what, float* out_dev);
 
+    // Image ends (image_host.cpp, image_io.hip): buffers of pd_image_load / pd_image_store that grow on demand and never shrink
+    struct ImageBuf { void* p = nullptr; size_t cap = 0; };
+    ImageBuf img_u8;     // the source pictures of a host caller (load) / the bytes on their way to a host caller (store)
+    ImageBuf img_tmp;    // the picture between the horizontal and the vertical pass
+    ImageBuf img_f32;    // the float tensor of a host caller
+    ImageBuf img_tab;    // both axes' tables: bounds + kk of the horizontal pass, then of the vertical one
+    std::vector<int32_t> img_tab_host;
+    int32_t img_tab_key[5] = {0, 0, 0, 0, 0};   // (Ws, W, Hs, H, filter) the device tables hold now; all zero: none
+    long long image_allocs = 0;                 // stat "image_allocs"
+    int image_grow(ImageBuf& b, size_t bytes);
+    void image_release();
+
     // SD3 / MMDiT path (sd3.cpp)
     pd_sd3_config sd3{};
     Sd3NetW sd3_tr, sd3_cn;

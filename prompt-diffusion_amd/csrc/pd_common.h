@@ -387,6 +387,16 @@ int launch_hed_stage_tail(const void* x, int dt, const float* sw, const float* s
 // scores[i] [B][H >> i][W >> i] fp32 (H, W multiples of 16), cw [5], cb [1] -> what 0: out [B][1][H][W] = sigmoid(cb + sum_i cw[i] up_i),
 // what 1: out [B][5][H][W] = up_i; up_i the bilinear upsample (align_corners = False) of map i by 2^i
 int launch_hed_fuse(const float* const scores[5], const float* cw, const float* cb, float* out, int B, int H, int W, int what, hipStream_t s);
+// image_io.hip: the image ends (image_host.cpp; include/pdengine.h "Image ends")
+// Pillow's horizontal 8-bit pass: src [rows][Ws][3] u8 -> out [rows][W][3] u8 with bounds [W][2] = (xmin, count <= ksize), kk [W][ksize]
+int launch_image_hpass(const uint8_t* src, uint8_t* out, const int* bounds, const int* kk, int ksize, long long rows, int Ws, int W,
+                       hipStream_t s);
+// src [Bs][Hs][W][3] u8 -> channels c_off .. c_off + 2 of dst [B][C][H][W] fp32 = (u8 / 255) * mul + add; the vertical pass first when
+// bounds is non-null (bounds [H][2], kk [H][ksize]), else Hs == H; B a multiple of Bs: sample b reads b / (B / Bs), or b % Bs with `tile`
+int launch_image_vpass(const uint8_t* src, float* dst, const int* bounds, const int* kk, int ksize, int Bs, int Hs, int H, int W, int B,
+                       int C, int c_off, int tile, float mul, float add, hipStream_t s);
+// src [B][C][H][W] fp32, C in {1, 3} -> dst [B][H][W][C] u8 = round(min(max(x * mul + add, 0), 1) * 255), half to even or truncated
+int launch_image_store(const float* src, uint8_t* dst, int B, int C, int H, int W, float mul, float add, int trunc, hipStream_t s);
 // sd3_kernels.hip: element-wise pieces of the MMDiT path
 // y_dt == DT_FP8: y holds e4m3 bytes and y_scale[row] the row's scale (max |value| / 448); add: x <- x + add first (written back)
 int launch_adaln(const void* x, int x_dt, void* y, int y_dt, const float* mod, int mod_stride, int shift_off, int scale_off, int rows,

@@ -746,6 +746,7 @@ void pd_engine_destroy(pd_engine* e) {
     (void)pd_comm_destroy(e);
     e->clear_graphs();
     e->lora_release();
+    e->image_release();
     if (e->stream2) { hipStreamSynchronize(e->stream2); hipStreamDestroy(e->stream2); }
     for (hipEvent_t ev : e->sd3_ev) hipEventDestroy(ev);
     if (e->ev_fork) hipEventDestroy(e->ev_fork);
@@ -1177,6 +1178,7 @@ int64_t pd_get_stat(pd_engine* e, const char* key) {
     if (!strcmp(key, "workspace_bytes")) return (int64_t)e->arena.cap;
     if (!strcmp(key, "weight_bytes")) return (int64_t)e->weight_bytes;
     if (!strcmp(key, "launches")) return (int64_t)e->launches;
+    if (!strcmp(key, "image_allocs")) return (int64_t)e->image_allocs;   // device allocations of pd_image_load / pd_image_store so far
     if (!strcmp(key, "gn_from_slabs")) return (int64_t)e->gn_from_slabs;
     if (!strcmp(key, "ring_launches")) return (int64_t)e->ring_launches;   // of which: gemm_ring.hip's persistent ring kernel
     if (!strcmp(key, "gn_kernel")) {   // which kernel the last pd_engine::groupnorm launch took

@@ -25,6 +25,14 @@ PD_VAE_MEAN, PD_VAE_SAMPLE, PD_VAE_MOMENTS = 0, 1, 2
 VAE_ENCODE_MODES = {"mean": PD_VAE_MEAN, "sample": PD_VAE_SAMPLE, "moments": PD_VAE_MOMENTS}
 PD_HED_EDGE, PD_HED_SIDES = 0, 1
 HED_OUTPUTS = {"edge": PD_HED_EDGE, "sides": PD_HED_SIDES}
+# image ends (include/pdengine.h, "Image ends"): the filters carry PIL's own numbers
+PD_RESAMPLE_LANCZOS, PD_RESAMPLE_BOX = 1, 4
+PD_RESAMPLE_MAX_SCALE = 8
+RESAMPLE_FILTERS = {"lanczos": PD_RESAMPLE_LANCZOS, "box": PD_RESAMPLE_BOX}
+PD_IMAGE_REPEAT, PD_IMAGE_TILE = 0, 1
+IMAGE_BATCH_MODES = {"repeat": PD_IMAGE_REPEAT, "tile": PD_IMAGE_TILE}
+PD_ROUND_NEAREST_EVEN, PD_ROUND_TRUNC = 0, 1
+IMAGE_ROUNDINGS = {"nearest_even": PD_ROUND_NEAREST_EVEN, "trunc": PD_ROUND_TRUNC}
 PD_MAX_LEVELS = 8
 PD_NUM_CONTROL = 13
 PD_MAX_CONTEXT_LEN = 1024
@@ -87,6 +95,15 @@ class pd_unipc_args(C.Structure):
 
 
 PD_UNIPC_NCOEF = 16
+
+
+class pd_image_load_args(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p), ("Bs", C.c_int32), ("Hs", C.c_int32), ("Ws", C.c_int32), ("mem_src", C.c_int32),
+        ("dst", C.c_void_p), ("B", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("c_off", C.c_int32),
+        ("mem_dst", C.c_int32), ("filter", C.c_int32), ("batch_mode", C.c_int32), ("mul", C.c_float), ("add", C.c_float),
+        ("reserved", C.c_int32 * 4),
+    ]
 
 
 class pd_lms_args(C.Structure):
@@ -223,6 +240,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.pd_set_rng.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
     lib.pd_get_rng.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.pd_randn.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_void_p]
+    lib.pd_resample_coefficients.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]
+    lib.pd_image_load.argtypes = [C.c_void_p, C.POINTER(pd_image_load_args)]
+    lib.pd_image_store.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_int32]
     if path is None:
         _lib = lib
     return lib
@@ -243,6 +263,7 @@ EXPORTS = [
     "pd_set_freeu", "pd_get_freeu", "pd_op_freeu_concat",
     "pd_philox4x32_10", "pd_set_rng", "pd_get_rng", "pd_randn",
     "pd_hed_configure", "pd_hed_weights_missing", "pd_hed_detect", "pd_op_hed_stage_tail", "pd_op_hed_fuse",
+    "pd_resample_coefficients", "pd_image_load", "pd_image_store",
 ]
 
 
@@ -254,6 +275,37 @@ def philox4x32_10(counter: Sequence[int], key: Sequence[int]) -> Tuple[int, int,
     out = (C.c_uint32 * 4)()
     lib.pd_philox4x32_10(c, k, out)
     return tuple(int(v) for v in out)
+
+
+def _filter_code(filter) -> int:
+    return RESAMPLE_FILTERS[filter] if isinstance(filter, str) else int(filter)
+
+
+def resample_ksize(in_size: int, out_size: int, filter="lanczos") -> int:
+    """Taps per output of Pillow's 8-bit resampler along one axis (pd_resample_coefficients' size query); PdError for a
+    reduction beyond PD_RESAMPLE_MAX_SCALE or an unknown filter."""
+    lib = load_library()
+    ks = C.c_int32()
+    if lib.pd_resample_coefficients(int(in_size), int(out_size), _filter_code(filter), C.byref(ks), None, None):
+        raise PdError(lib.pd_last_error().decode(errors="replace"))
+    return int(ks.value)
+
+
+def resample_coefficients(in_size: int, out_size: int, filter="lanczos") -> Tuple[np.ndarray, np.ndarray]:
+    """(bounds [out_size, 2] = (xmin, count), kk [out_size, ksize], zero padded; both int32): the tables of Pillow's 8-bit
+    Image.resize along one axis (pd_resample_coefficients; host only, no engine).  filter: "lanczos" / "box" or PIL's number."""
+    lib = load_library()
+    ks = C.c_int32(resample_ksize(in_size, out_size, filter))
+    bounds = np.zeros((int(out_size), 2), np.int32)
+    kk = np.zeros((int(out_size), ks.value), np.int32)
+    if lib.pd_resample_coefficients(int(in_size), int(out_size), _filter_code(filter), C.byref(ks), bounds.ctypes.data, kk.ctypes.data):
+        raise PdError(lib.pd_last_error().decode(errors="replace"))
+    return bounds, kk
+
+
+def resample_supported(src_hw, dst_hw) -> bool:
+    """Whether pd_image_load resamples src_hw = (Hs, Ws) to dst_hw = (H, W): no axis reduced beyond PD_RESAMPLE_MAX_SCALE."""
+    return all(int(i) >= 1 and int(o) >= 1 and int(i) <= PD_RESAMPLE_MAX_SCALE * int(o) for i, o in zip(src_hw, dst_hw))
 
 
 def make_config(cfg: ModelConfig, precision: int = PD_PREC_F16, stream_f32: bool = False) -> pd_config:
@@ -677,6 +729,90 @@ class Engine:
             op = out.ctypes.data
         self._order_after_torch(b.mem)
         self._check(self.lib.pd_hed_detect(self._h, b.ptr, B, H, W, b.mem, HED_OUTPUTS[what], op))
+        return out
+
+    # ------------------------------------------------------------------ image ends (pd_image_load / pd_image_store)
+    def _torch_device(self):
+        import torch
+        return torch.device("cuda", self.device)
+
+    @staticmethod
+    def _u8_source(x):
+        """uint8 NumPy array or uint8 torch tensor -> (owner, pointer, mem, shape)"""
+        if _is_torch(x):
+            import torch
+            if x.dtype != torch.uint8:
+                raise ValueError(f"expected a uint8 tensor, got {x.dtype}")
+            t = x.detach().contiguous()
+            return t, t.data_ptr(), PD_MEM_DEVICE if t.is_cuda else PD_MEM_HOST, tuple(t.shape)
+        a = np.asarray(x)
+        if a.dtype != np.uint8:
+            raise ValueError(f"expected a uint8 array, got {a.dtype}")
+        a = np.ascontiguousarray(a)
+        return a, a.ctypes.data, PD_MEM_HOST, a.shape
+
+    def image_load(self, images, size=None, *, out=None, c_off: int = 0, channels: int = 3, batch: Optional[int] = None,
+                   batch_mode: str = "repeat", mul: float = 1.0, add: float = 0.0, filter="lanczos", host: bool = False):
+        """uint8 pictures [Bs, Hs, Ws, 3] (NumPy, or a CPU / CUDA torch tensor) -> float32 [B, channels, H, W], written into
+        channels c_off .. c_off + 2 (pd_image_load): resampled to size = (H, W) exactly as PIL's Image.resize(filter) does
+        when the sizes differ, then (u8 / 255) * mul + add in float32 -- (1, 0) for [0, 1], (2, -1) for [-1, 1].  batch: B, a
+        multiple of Bs; batch_mode "repeat" reads source b // (B // Bs) (np.repeat), "tile" source b % Bs.  out: an existing
+        contiguous float32 tensor (CUDA) or array (NumPy) [B, channels, H, W] to write into; its other channels keep their
+        values.  Without `out` a CUDA tensor is made (a NumPy array with host=True; channels other than the three written are
+        then uninitialised)."""
+        owner, sp, smem, sh = self._u8_source(images)
+        if len(sh) != 4 or sh[3] != 3:
+            raise ValueError(f"images must be uint8 [B, H, W, 3], got {sh}")
+        Bs, Hs, Ws = int(sh[0]), int(sh[1]), int(sh[2])
+        H, W = (Hs, Ws) if size is None else (int(size[0]), int(size[1]))
+        B = Bs if batch is None else int(batch)
+        if out is not None:
+            if tuple(out.shape) != (B, out.shape[1], H, W):
+                raise ValueError(f"out must be [{B}, C, {H}, {W}], got {tuple(out.shape)}")
+            if _is_torch(out):
+                import torch
+                if out.dtype != torch.float32 or not out.is_contiguous():
+                    raise ValueError("out must be a contiguous float32 tensor")
+                dp, dmem = out.data_ptr(), PD_MEM_DEVICE if out.is_cuda else PD_MEM_HOST
+            else:
+                if out.dtype != np.float32 or not out.flags.c_contiguous:
+                    raise ValueError("out must be a C-contiguous float32 array")
+                dp, dmem = out.ctypes.data, PD_MEM_HOST
+            channels = int(out.shape[1])
+        elif host:
+            out = np.empty((B, channels, H, W), np.float32)
+            dp, dmem = out.ctypes.data, PD_MEM_HOST
+        else:
+            import torch
+            out = torch.empty((B, channels, H, W), dtype=torch.float32, device=self._torch_device())
+            dp, dmem = out.data_ptr(), PD_MEM_DEVICE
+        a = pd_image_load_args()
+        a.src, a.Bs, a.Hs, a.Ws, a.mem_src = sp, Bs, Hs, Ws, smem
+        a.dst, a.B, a.C, a.H, a.W, a.c_off, a.mem_dst = dp, B, channels, H, W, int(c_off), dmem
+        a.filter, a.batch_mode = _filter_code(filter), IMAGE_BATCH_MODES[batch_mode]
+        a.mul, a.add = float(mul), float(add)
+        self._order_after_torch(PD_MEM_DEVICE if PD_MEM_DEVICE in (smem, dmem) else PD_MEM_HOST)
+        self._check(self.lib.pd_image_load(self._h, C.byref(a)))
+        del owner
+        return out
+
+    def image_store(self, x, *, mul: float = 1.0, add: float = 0.0, rounding: str = "nearest_even", host: bool = False):
+        """float32 [B, C, H, W], C 1 or 3 (NumPy or torch) -> uint8 [B, H, W, C] (pd_image_store):
+        min(max(x * mul + add, 0), 1) * 255 in float32, then rounding "nearest_even" (np.round) or "trunc" (astype(uint8)).
+        A CUDA tensor comes out, a NumPy array with host=True."""
+        b = _Buf(x)
+        if b.owner.ndim != 4 or b.owner.shape[1] not in (1, 3):
+            raise ValueError(f"x must be [B, 1 or 3, H, W], got {tuple(b.owner.shape)}")
+        B, Cc, H, W = (int(v) for v in b.owner.shape)
+        if host:
+            out = np.empty((B, H, W, Cc), np.uint8)
+            dp, dmem = out.ctypes.data, PD_MEM_HOST
+        else:
+            import torch
+            out = torch.empty((B, H, W, Cc), dtype=torch.uint8, device=b.owner.device if b.mem == PD_MEM_DEVICE else self._torch_device())
+            dp, dmem = out.data_ptr(), PD_MEM_DEVICE
+        self._order_after_torch(PD_MEM_DEVICE if PD_MEM_DEVICE in (b.mem, dmem) else PD_MEM_HOST)
+        self._check(self.lib.pd_image_store(self._h, b.ptr, B, Cc, H, W, b.mem, float(mul), float(add), IMAGE_ROUNDINGS[rounding], dp, dmem))
         return out
 
     def text_weights_missing(self) -> int:

@@ -138,8 +138,10 @@ class PromptDiffusionPipeline:
     vae_scaling_factor = 0.18215      # models/cldm_v15.yaml:17
 
     def __init__(self, engine: E.Engine, text_encoder: Optional[Callable] = None, vae_decode: Optional[Callable] = None,
-                 scheduler: Any = None, tokenizer: Any = None, fuse_scheduler: bool = False, long_prompts=None):
+                 scheduler: Any = None, tokenizer: Any = None, fuse_scheduler: bool = False, long_prompts=None,
+                 device_images: bool = False):
         """long_prompts: True / a window count = enable_long_prompts() at construction.
+        device_images: True = enable_device_images() at construction (the image ends of a call on the GPU; off by default).
         prompt_embeds / negative_prompt_embeds of any equal length L <= engine.PD_MAX_CONTEXT_LEN are accepted by every path
         (fused DDIM, fuse_scheduler=True, host schedulers, callbacks): the engine takes the context length per call.
         clip_skip of __call__ has diffusers' meaning (the hidden state of layer -(clip_skip + 1)); the reference's own
@@ -163,6 +165,7 @@ class PromptDiffusionPipeline:
         if _window_count(long_prompts):
             self.enable_long_prompts(long_prompts)
         self._guidance_scale = 7.5
+        self._device_images = bool(device_images)
         # LoRA adapters (load_lora_weights): name -> {"id", "unet", "text_encoder"}; the active set with its weights; the
         # per-id scales the engine holds merged now (None: nothing merged yet)
         self._lora_adapters: Dict[str, Dict[str, Any]] = {}
@@ -265,6 +268,50 @@ class PromptDiffusionPipeline:
             if end > 1.0:
                 raise ValueError(f"control guidance end: {end} can't be larger than 1.0.")
 
+    # ------------------------------------------------------------------ image ends on the device
+    def enable_device_images(self):
+        """Both image ends of a call on the GPU (Engine.image_load / image_store), bit-identical to the host code they replace:
+        mode-"RGB" PIL images given as `image`, `image_pair` or an img2img / inpainting init `image` are uploaded as uint8,
+        resampled there as PIL's LANCZOS resize does it and written straight into the engine's float layout (the pair as one
+        6-channel tensor); the other sampling inputs are uploaded once and the loop runs on device pointers; output_type="pil"
+        decodes on the device and downloads uint8 only.  Every other kind of input (arrays, tensors, other PIL modes, masks, a
+        reduction beyond engine.PD_RESAMPLE_MAX_SCALE) keeps the host code and is uploaded.  Applies where the loop runs inside
+        the engine (fused DDIM, fuse_scheduler=True, img2img, inpainting); the per-step driver (host schedulers, callbacks)
+        builds the tensors the same way and brings them to the host once.  "np" and "latent" outputs are unchanged."""
+        self._device_images = True
+
+    def disable_device_images(self):
+        self._device_images = False
+
+    def _device_image(self, image, width, height, batch_size, num_images_per_prompt, out=None, c_off=0, channels=3, mul=1.0,
+                      add=0.0):
+        """prepare_image on the device: a new CUDA tensor [B, channels, H, W], or `out`, with channels c_off .. c_off + 2
+        written; None when the input is not the device path's kind -- the caller then takes prepare_image."""
+        items = image if isinstance(image, list) else [image]
+        if not items or not all(_is_pil(im) and im.mode == "RGB" for im in items) or len({im.size for im in items}) != 1:
+            return None
+        Ws, Hs = items[0].size
+        H, W = (height, width) if height is not None and width is not None else (Hs, Ws)
+        if not E.resample_supported((Hs, Ws), (H, W)):
+            return None
+        repeat_by = batch_size if len(items) == 1 else num_images_per_prompt
+        B = len(items) * repeat_by
+        if out is not None and (out.shape[0], out.shape[2], out.shape[3]) != (B, H, W):
+            return None
+        src = np.stack([np.asarray(im) for im in items])
+        return self.engine.image_load(src, (H, W), out=out, c_off=c_off, channels=channels, batch=B, batch_mode="repeat", mul=mul,
+                                      add=add)
+
+    def _to_device(self, x):
+        """A sampling input on the engine's GPU: arrays and CPU tensors are uploaded as float32, None / "engine" pass through."""
+        if x is None or isinstance(x, str):
+            return x
+        import torch
+        dev = torch.device("cuda", self.engine.device)
+        if E._is_torch(x):
+            return x.detach().to(device=dev, dtype=torch.float32)
+        return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
+
     # ------------------------------------------------------------------ host pre-processing
     def prepare_image(self, image, width, height, batch_size, num_images_per_prompt):
         """VaeImageProcessor(do_normalize=False).preprocess + repeat (pipeline :236-238, :760-788): [B,3,H,W] in [0,1]."""
@@ -340,6 +387,8 @@ class PromptDiffusionPipeline:
         if batch_size % x.shape[0] != 0:
             raise ValueError(f"Cannot duplicate {what} of batch size {x.shape[0]} to {batch_size} images; the batch size must "
                              "divide it.")
+        if E._is_torch(x):
+            return x.repeat((batch_size // x.shape[0],) + (1,) * (x.ndim - 1))
         return np.tile(x, (batch_size // x.shape[0],) + (1,) * (x.ndim - 1))
 
     def prepare_mask(self, mask_image, width, height, batch_size):
@@ -373,10 +422,11 @@ class PromptDiffusionPipeline:
         m = np.ascontiguousarray(m[:, :, ::f, ::f])
         return self._tile(m, batch_size, "`mask_image`")
 
-    def _init_latents(self, image, width, height, batch_size, generator):
+    def _init_latents(self, image, width, height, batch_size, generator, device=False):
         """z0 = scaling_factor * the init image's latents, [batch_size, 4, height / 8, width / 8]: a 4-channel `image` is taken
         as latents; anything else is preprocessed as prepare_image does, mapped to [-1, 1] and encoded on the engine with a
-        posterior sample (vae_encode mode "sample", a standard-normal draw from `generator`)."""
+        posterior sample (vae_encode mode "sample", a standard-normal draw from `generator`).  device: RGB PIL images go
+        through Engine.image_load(2, -1) straight into vae_encode and z0 stays a CUDA tensor."""
         cfg = self.engine.cfg
         zc, f = cfg.in_channels, self.vae_scale_factor
         lat_hw = (height // f, width // f)
@@ -385,17 +435,23 @@ class PromptDiffusionPipeline:
             if tuple(z.shape[2:]) != lat_hw:
                 raise ValueError(f"latent `image` must be [B, {zc}, {lat_hw[0]}, {lat_hw[1]}], got {tuple(z.shape)}")
         else:
-            x = self.prepare_image(image, width, height, 1, 1)
-            if x.shape[-2:] != (height, width):
+            x = self._device_image(image, width, height, 1, 1, mul=2.0, add=-1.0) if device else None
+            on_device = x is not None
+            if not on_device:
+                x = self.prepare_image(image, width, height, 1, 1)
+            if tuple(x.shape[-2:]) != (height, width):
                 raise ValueError(f"`image` is {x.shape[-1]}x{x.shape[-2]}, the control image {width}x{height}")
             if not getattr(cfg, "vae_encoder", False) or self.engine.vae_encoder_weights_missing() != 0:
                 raise ValueError("an init `image` needs the engine's VAE encoder (vae_encoder=True and the first_stage_model.encoder.* "
                                  "/ quant_conv.* weights), or pass its latents as a 4-channel `image`")
-            x = np.ascontiguousarray(x * np.float32(2.0) - np.float32(1.0))
+            if not on_device:
+                x = np.ascontiguousarray(x * np.float32(2.0) - np.float32(1.0))
             Bi = x.shape[0]
             gen = generator[:Bi] if isinstance(generator, list) else generator
             # (an EngineGenerator: the posterior kernel draws at stream "vae" itself)
             noise = "engine" if isinstance(gen, EngineGenerator) else self._randn((Bi, zc) + lat_hw, gen)
+            if on_device:
+                return self._tile(self.engine.vae_encode(x, mode="sample", noise=self._to_device(noise)), batch_size, "`image`").contiguous()
             z = _to_numpy(self.engine.vae_encode(x, mode="sample", noise=noise)).astype(np.float32)
         return np.ascontiguousarray(self._tile(z, batch_size, "`image`"))
 
@@ -679,17 +735,28 @@ class PromptDiffusionPipeline:
         # 3. text context
         pe, ne = self.encode_prompt(prompt, num_images_per_prompt, do_cfg, negative_prompt, prompt_embeds, negative_prompt_embeds)
         # 3.1 / 4. images: [B,6,H,W] example pair and [B,3,H,W] query, both in [0,1]
-        pair = np.concatenate([self.prepare_image(im, width, height, batch_size * num_images_per_prompt, num_images_per_prompt)
-                               for im in image_pair], axis=1)
-        query = self.prepare_image(image, width, height, batch_size * num_images_per_prompt, num_images_per_prompt)
-        height, width = query.shape[-2:]
         B = batch_size * num_images_per_prompt
+        # device_images: the image ends on the GPU.  in_engine: the loop runs inside the engine, so its inputs stay there
+        dev_images = self._device_images
+        in_engine = dev_images and callback_on_step_end is None and callback is None and (self.scheduler is None or self.fuse_scheduler)
+        pair = query = None
+        if dev_images:
+            query = self._device_image(image, width, height, B, num_images_per_prompt)
+            # both halves into one 6-channel tensor, no concat: the first call makes it, the second fills channels 3 .. 5
+            pair = self._device_image(image_pair[0], width, height, B, num_images_per_prompt, channels=6)
+            if pair is not None and self._device_image(image_pair[1], width, height, B, num_images_per_prompt, out=pair, c_off=3) is None:
+                pair = None
+        if pair is None:
+            pair = np.concatenate([self.prepare_image(im, width, height, B, num_images_per_prompt) for im in image_pair], axis=1)
+        if query is None:
+            query = self.prepare_image(image, width, height, B, num_images_per_prompt)
+        height, width = (int(v) for v in query.shape[-2:])
         if isinstance(generator, EngineGenerator):
             generator.bind(self.engine)
         # 6. latents (img2img / inpainting: the init image's latents first -- its posterior draw comes before the noise draw)
         if init is not None:
             m = self.prepare_mask(init["mask"], width, height, B) if init["mask"] is not None else None
-            z0 = self._init_latents(init["image"], width, height, B, generator)
+            z0 = self._init_latents(init["image"], width, height, B, generator, device=dev_images)
         x_T = self.prepare_latents(B, self.engine.cfg.in_channels, height, width, generator, latents)
         # 7.2 controlnet_keep gating and per-step scales (pipeline :1196-1202, :1229-1235; controlnet :371-378)
         custom_ts = None
@@ -745,6 +812,14 @@ class PromptDiffusionPipeline:
                 noise = "engine"         # drawn in the update kernel at (stream "step", draw = step): nothing to make or upload
             elif self.scheduler is None:   # a plug-in scheduler draws its own noise (`generator` is forwarded to step())
                 noise = self._randn((n_steps,) + x_T.shape, generator if not isinstance(generator, list) else None)
+        if in_engine:     # every pointer of pd_sample_args on the device: uploaded once, here
+            x_T, pe, ne, pair, query, noise = (self._to_device(v) for v in (x_T, pe, ne, pair, query, noise))
+            if init is not None:
+                z0, m = self._to_device(z0), self._to_device(m)
+        elif dev_images:  # the per-step driver works on the host: bring what was built on the device back once
+            pair, query = _to_numpy(pair), _to_numpy(query)
+            if init is not None:
+                z0 = _to_numpy(z0)
         kw = dict(x_T=x_T, ctx_cond=pe, ctx_uncond=ne, pair=pair, query=query, steps=num_inference_steps,
                   cfg_scale=float(guidance_scale), eta=float(eta), use_cfg=do_cfg, guess_mode=guess_mode,
                   control_scales_step=scales_step, noise=noise)
@@ -794,8 +869,17 @@ class PromptDiffusionPipeline:
                                  plan=plan if self.scheduler is not None else None)
         # 9. post-processing (pipeline :1298-1321); safety checker is forced off there too
         if output_type == "latent":
-            images = lat
+            images = _to_numpy(lat) if in_engine else lat
+        elif (dev_images and output_type == "pil" and self.vae_decode is None and getattr(self.engine.cfg, "vae_ch", 0) > 0
+              and self.engine.vae_weights_missing() == 0):
+            # decode, denormalize, clip, round and the NHWC transpose on the device; only the uint8 pictures come back
+            from PIL import Image
+            u8 = self.engine.image_store(self.engine.vae_decode(self._to_device(lat)), mul=0.5, add=0.5, rounding="nearest_even",
+                                         host=True)
+            images = [Image.fromarray(im) for im in u8]
         else:
+            if in_engine:
+                lat = _to_numpy(lat)
             if self.vae_decode is not None:
                 img = _to_numpy(self.vae_decode(lat / np.float32(self.vae_scaling_factor)))
             elif getattr(self.engine.cfg, "vae_ch", 0) > 0 and self.engine.vae_weights_missing() == 0:
