@@ -634,6 +634,63 @@ int pd_sd3_sample(pd_engine* e, const pd_sd3_args* args, const float* sigmas, in
  * pair = cat([cond, gt], 1) [B, 6, H, W] -> out [B, 3, H, W] (fp32, `mem` as in pd_sd3_args). */
 int pd_sd3_down_proj(pd_engine* e, const float* pair, int32_t B, int32_t H, int32_t W, int32_t mem, float* out);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * SD3 text encoders: what the reference's encode_prompt runs (promptdiffusioncontrolnetpipeline_sd3.py:238-545) -- CLIP-L and CLIP-G
+ * (transformers' CLIPTextModelWithProjection) and the T5 encoder (T5EncoderModel).  Tokenisation stays with the caller: the boundary
+ * takes token ids.  Parameter names are the checkpoint's: "text_encoder.text_model.*" + "text_encoder.text_projection.weight", the same
+ * under "text_encoder_2.", and "text_encoder_3.shared.weight", "text_encoder_3.encoder.block.N.layer.0.SelfAttention.{q,k,v,o}.weight",
+ * "...block.0.layer.0.SelfAttention.relative_attention_bias.weight", "...layer.0.layer_norm.weight",
+ * "...layer.1.DenseReluDense.{wi_0,wi_1,wo}.weight", "...layer.1.layer_norm.weight", "text_encoder_3.encoder.final_layer_norm.weight"
+ * (the tied "text_encoder_3.encoder.embed_tokens.weight" is not a parameter: loaders skip it).  The residual streams of all three
+ * encoders are fp32 in every precision mode; T5's gated product is formed in fp32 and saturates to +-65504 on an fp16 store.
+ * Whether fp16 is usable with real T5-XXL weights is unmeasured: prefer bf16 for the T5 slot. */
+#define PD_CLIP_ACT_QUICK_GELU 0   /* CLIP-L */
+#define PD_CLIP_ACT_GELU 1         /* CLIP-G: exact (erf) GELU */
+typedef struct pd_sd3_clip_config {
+    int32_t vocab, hidden, ff, heads, layers;   /* layers == 0: this encoder is absent; hidden / heads must be 64 */
+    int32_t max_positions;                       /* 77 */
+    int32_t proj_dim;                            /* rows of text_projection.weight [proj_dim, hidden] (no bias) */
+    int32_t eos_token_id;                        /* 2 (both SD3 configs): pooled row = argmax(ids); else the first ids == eos_token_id */
+    int32_t act;                                 /* PD_CLIP_ACT_* */
+} pd_sd3_clip_config;
+typedef struct pd_sd3_t5_config {
+    int32_t vocab, d_model, d_kv, heads, d_ff, layers;   /* layers == 0: absent; d_kv must be 64; heads * d_kv need not equal d_model */
+    int32_t num_buckets, max_distance;                    /* relative_attention_num_buckets 32, relative_attention_max_distance 128 */
+    float eps;                                            /* layer_norm_epsilon 1e-6 */
+} pd_sd3_t5_config;
+typedef struct pd_sd3_text_config {
+    pd_sd3_clip_config clip_l, clip_g;
+    pd_sd3_t5_config t5;
+    int32_t joint_dim;       /* row width of prompt_embeds: >= clip_l.hidden + clip_g.hidden, and == t5.d_model when T5 is present */
+    int32_t reserved[3];
+} pd_sd3_text_config;
+typedef struct pd_sd3_text_args {
+    int32_t batch;               /* B */
+    int32_t t5_len;              /* Lt in [1, 512] (ignored without a T5 encoder) */
+    int32_t clip_skip;           /* >= 0; the hidden state is hidden_states[-(clip_skip + 2)], without the final LayerNorm */
+    int32_t mem;                 /* PD_MEM_HOST / PD_MEM_DEVICE of the ids and of both outputs */
+    const int32_t* ids_clip_l;   /* [B, 77] */
+    const int32_t* ids_clip_g;   /* [B, 77] */
+    const int32_t* ids_t5;       /* [B, Lt] */
+    int64_t reserved[3];
+} pd_sd3_text_args;
+/* Registers the encoders' parameters (registry group of their own) on an existing engine and allocates their weights.  Once per engine;
+ * an engine that never calls it is unchanged. */
+int pd_sd3_text_configure(pd_engine* e, const pd_sd3_text_config* cfg);
+int pd_sd3_text_weights_missing(pd_engine* e);
+/* encode_prompt after tokenisation.  prompt_embeds [B, 77 + Lt, joint_dim] fp32: rows 0..76 hold the CLIP-L hidden state in columns
+ * [0, hidden_l), CLIP-G's in [hidden_l, hidden_l + hidden_g) and zeros up to joint_dim; rows 77.. hold T5's last_hidden_state.  Without
+ * a T5 encoder the output is [B, 77, joint_dim] (the reference appends its zero block of 77 more rows itself).  pooled
+ * [B, proj_l + proj_g] fp32 = cat(text_embeds_l, text_embeds_g).  Both CLIP encoders must be configured. */
+int pd_sd3_encode_prompt(pd_engine* e, const pd_sd3_text_args* args, float* prompt_embeds, float* pooled);
+/* One encoder alone.  which 0 / 1 (CLIP-L / CLIP-G): ids [B, 77] -> hidden [B, 77, hidden] (as above) and pooled [B, proj_dim], either
+ * may be NULL; which 2 (T5): ids [B, len] -> hidden [B, len, d_model], pooled must be NULL.  len is read for T5 only. */
+int pd_sd3_text_encoder(pd_engine* e, int32_t which, const int32_t* ids, int32_t B, int32_t len, int32_t clip_skip, int32_t mem,
+                        float* hidden, float* pooled);
+/* T5Attention._relative_position_bucket (bidirectional) on the host: out[i] = bucket of relative position (key - query) = i - (L - 1)
+ * for i in [0, 2 L - 1).  Needs no engine and no GPU. */
+int pd_t5_relative_buckets(int32_t L, int32_t num_buckets, int32_t max_distance, int32_t* out);
+
 #ifdef __cplusplus
 }
 #endif

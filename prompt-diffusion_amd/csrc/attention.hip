@@ -16,6 +16,7 @@
 // the O^T rescale uses the lane's own alpha.
 #include "pd_common.h"
 #include "pd_mma.h"
+#include <type_traits>
 
 namespace {
 
@@ -59,8 +60,13 @@ struct AttnCfg {
     static_assert((DH * EB) % 16 == 0, "head dim must fill whole 16-byte chunks");
 };
 
-template <int P, int DH>
-__global__ __launch_bounds__(256) void attn_kernel(AttnParams p) {
+// PT = AttnBiasParams (BIAS): T5's additive relative-position bias (sd3_text.cpp).  It depends on key - query only, so the caller hands over one row of
+// 2 Nk - 1 values per head, relbias[h][key - query + Nk - 1], already in exp2 units (times log2 e, like the logits after sl2);
+// a lane's four keys of a 16-key S^T tile are four consecutive floats of its query's window.  Nq == Nk.
+struct AttnBiasParams : AttnParams { const float* relbias; };
+template <int P, int DH, class PT = AttnParams>
+__global__ __launch_bounds__(256) void attn_kernel(PT p) {
+    constexpr bool BIAS = !std::is_same<PT, AttnParams>::value;
     using Cfg = AttnCfg<P, DH>;
     constexpr bool F32 = prec_f32_storage(P);
     constexpr int EB = Cfg::EB, VEC = Cfg::VEC, NCH = Cfg::NCH, KS = Cfg::KS, NTD = Cfg::NTD;
@@ -159,6 +165,12 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnParams p) {
                 for (int j = 0; j < 4; ++j) {
                     const int key = t0 + kt * 16 + fq * 4 + j;
                     float v = s[kt][qt][j] * sl2;
+                    if constexpr (BIAS) {
+                        // rows past Nq are clamped copies (computed, never stored): no negative offset; pad keys of a ragged tile
+                        // would index past 2 Nk - 2: not read, and masked below like in every other instantiation
+                        const int qc = min(q0 + qt * 16 + fr, p.Nq - 1);
+                        if (key < p.Nk) v += p.relbias[(size_t)h * (2 * p.Nk - 1) + (key - qc + p.Nk - 1)];
+                    }
                     v = (key < p.Nk && (!p.causal || key <= q0 + qt * 16 + fr)) ? v : -INFINITY;
                     s[kt][qt][j] = v;
                     mx = fmaxf(mx, v);
@@ -626,6 +638,20 @@ int launch_dh(const AttnParams& p, hipStream_t s) {
 }
 
 template <int P>
+int launch_bias(const AttnParams& p, const float* relbias, hipStream_t s) {
+    using Cfg = AttnCfg<P, 64>;
+    auto kfn = attn_kernel<P, 64, AttnBiasParams>;
+    static unsigned long long attr_done = 0;
+    if (ensure_dyn_smem(reinterpret_cast<const void*>(kfn), Cfg::SMEM, &attr_done)) return 1;
+    dim3 grid((p.Nq + 127) / 128, p.B * p.heads);
+    AttnBiasParams pb;
+    static_cast<AttnParams&>(pb) = p;
+    pb.relbias = relbias;
+    hipLaunchKernelGGL(kfn, grid, dim3(256), Cfg::SMEM, s, pb);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+template <int P>
 int launch_prec(const AttnParams& p, hipStream_t s) {
     if constexpr (!prec_f32_storage(P)) {
         if (!p.legacy && !p.causal) {
@@ -662,6 +688,19 @@ int launch_attention(const AttnParams& p, int prec, hipStream_t s) {
         case PREC_F16X2: return launch_prec<PREC_F16X2>(p, s);
         case DT_BF16: return launch_prec<DT_BF16>(p, s);
         case DT_F16: return launch_prec<DT_F16>(p, s);
+        default: return 1;
+    }
+}
+
+// softmax(Q K^T * scale + bias) V with the Toeplitz bias rows relbias [heads][2 Nk - 1] fp32 (see attn_body): dh 64, Nq == Nk, not causal
+int launch_attention_bias(const AttnParams& p, const float* relbias, int prec, hipStream_t s) {
+    if (p.Nq <= 0 || p.Nk <= 0) return 0;
+    if (!relbias || p.dh != 64 || p.Nq != p.Nk || p.causal) return 2;
+    switch (prec) {
+        case DT_F32: return launch_bias<DT_F32>(p, relbias, s);
+        case PREC_F16X2: return launch_bias<PREC_F16X2>(p, relbias, s);
+        case DT_BF16: return launch_bias<DT_BF16>(p, relbias, s);
+        case DT_F16: return launch_bias<DT_F16>(p, relbias, s);
         default: return 1;
     }
 }

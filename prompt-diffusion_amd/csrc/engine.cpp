@@ -5,6 +5,7 @@
 // and the control flow of cldm/cldm.py:23-45 / :302-325 / :369-382.
 #include "engine.h"
 
+#include <algorithm>
 #include <climits>
 #include <cmath>
 #include <cstdarg>
@@ -480,8 +481,9 @@ int pd_engine::read_param(const Param& p, float* out) {
         HIP_OK(hipMemcpy(all.data(), m.w, all.size(), hipMemcpyDeviceToHost));
         const int half = m.Nout;
         for (int r = 0; r < rows; ++r) {
-            const int j = r < half ? r : r - half;
-            const size_t drow = (size_t)(j / 80) * 160 + (r < half ? 0 : 80) + j % 80;
+            const int lr = p.row_off + r;   // (row_off != 0: one half registered as a tensor of its own)
+            const int j = lr < half ? lr : lr - half;
+            const size_t drow = (size_t)(j / 80) * 160 + (lr < half ? 0 : 80) + j % 80;
             memcpy(img.data() + (size_t)r * rowb, all.data() + drow * rowb, rowb);
         }
     } else {
@@ -540,7 +542,18 @@ int pd_engine::upload_rows(WMat& m, int row_off, const float* src, int rows, boo
             }
     }
     const size_t rowb = (size_t)m.Kpad * EB;
-    if (m.geglu) {
+    if (m.geglu && rows != 2 * m.Nout) {
+        // one half (or any row range) of a GEGLU matrix whose halves are separate checkpoint tensors: logical row row_off + r, copied in
+        // runs that stay inside one 80-row block
+        const int half = m.Nout;
+        for (int r = 0; r < rows;) {
+            const int lr = row_off + r, j = lr < half ? lr : lr - half;
+            const int run = std::min(rows - r, std::min(80 - j % 80, (lr < half ? half : 2 * half) - lr));
+            const size_t drow = (size_t)(j / 80) * 160 + (lr < half ? 0 : 80) + j % 80;
+            HIP_OK(hipMemcpy(reinterpret_cast<char*>(m.w) + drow * rowb, img.data() + (size_t)r * rowb, (size_t)run * rowb, hipMemcpyHostToDevice));
+            r += run;
+        }
+    } else if (m.geglu) {
         // destination rows are interleaved in 80 + 80 blocks (x | gate), see gemm.hip
         const int half = m.Nout;
         std::vector<char> perm((size_t)m.N * rowb, 0);
@@ -703,7 +716,7 @@ GemmParams pd_engine::fill_gemm(const WMat& m, const Act& in, const Act& out, co
     p.taps = m.taps; p.Cin = m.cin_pad;
     p.Hin = in.H; p.Win = in.W; p.Hout = out.H; p.Wout = out.W; p.stride = c.stride; p.ups = c.ups;
     p.rows_per_sample = out.H * out.W; p.rowvec_stride = c.rowvec_stride;
-    p.act = m.geglu ? ACT_GEGLU : c.act; p.a_silu = c.a_silu ? 1 : 0; p.out_scale = c.scale;
+    p.act = m.geglu ? (c.act == ACT_GATED_TANH_GELU ? ACT_GATED_TANH_GELU : ACT_GEGLU) : c.act; p.a_silu = c.a_silu ? 1 : 0; p.out_scale = c.scale;
     p.vt_begin = c.VT ? c.vt_begin : INT_MAX; p.vt_ld = c.vt_ld;
     p.Nout = m.Nout;
     p.splitk = 1;
@@ -1001,7 +1014,8 @@ int pd_engine::layernorm(const Act& x, Act& y, const float* g, const float* b) {
 }
 
 int pd_engine::attention(const void* Q, int ldq, const void* K, int ldk, const void* VT, int vt_ld, void* O, int ldo, int B,
-                         int Nq, int Nk, int C, int heads, bool causal, long long q_bs, long long k_bs, long long o_bs) {
+                         int Nq, int Nk, int C, int heads, bool causal, long long q_bs, long long k_bs, long long o_bs, const float* relbias,
+                         float scale) {
     if (heads <= 0) heads = cfg.num_heads;
     if (arena.dry) return 0;
     PD_TRY(check_arena());
@@ -1015,6 +1029,7 @@ int pd_engine::attention(const void* Q, int ldq, const void* K, int ldk, const v
     p.Nq = Nq; p.Nk = Nk; p.heads = heads; p.dh = C / heads;
     p.causal = causal ? 1 : 0;
     p.scale = (float)(1.0 / std::sqrt((double)p.dh));
+    if (scale != 0.f) p.scale = scale;
     p.B = B;
     p.legacy = opt_attn_legacy ? 1 : 0;
     ++launches;
@@ -1023,7 +1038,7 @@ int pd_engine::attention(const void* Q, int ldq, const void* K, int ldk, const v
         prof_begin(rec, 2, 4.0 * (double)B * heads * (double)Nq * (double)Nk * (double)p.dh);
         rec.M = Nq; rec.N = Nk; rec.K = p.dh; rec.taps = B;
     }
-    const int r = launch_attention(p, P, stream);
+    const int r = relbias ? launch_attention_bias(p, relbias, P, stream) : launch_attention(p, P, stream);
     if (profiling) prof_end(rec);
     if (r) {
         pd_set_error(r == 2 ? "attention: unsupported head dim %d" : "attention launch failed (dh %d)", p.dh);

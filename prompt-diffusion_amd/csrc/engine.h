@@ -193,6 +193,27 @@ struct TextW {
     float *fln_g = nullptr, *fln_b = nullptr;
 };
 
+// SD3 text encoders (sd3_text.cpp): a CLIP text transformer with its projection head (CLIP-L / CLIP-G) ...
+struct Sd3ClipW {
+    bool built = false;
+    pd_sd3_clip_config c{};
+    WMat tok, pos, proj;
+    std::vector<TextLayerW> layers;
+    float *fln_g = nullptr, *fln_b = nullptr;
+};
+// ... and the T5 encoder stack: no biases anywhere, RMSNorm weights only, wi = [wi_1 | wi_0] packed like a GEGLU matrix
+struct T5LayerW {
+    float *ln1 = nullptr, *ln2 = nullptr;
+    WMat qkv, o, wi, wo;
+};
+struct Sd3T5W {
+    bool built = false;
+    pd_sd3_t5_config c{};
+    WMat tok, relbias;    // shared.weight; block 0's relative_attention_bias.weight [num_buckets][heads]
+    std::vector<T5LayerW> layers;
+    float* fln = nullptr;
+};
+
 // SD3 / MMDiT: one JointTransformerBlock
 struct Sd3BlockW {
     WMat qkv, qkv_c;     // to_q|to_k|to_v and add_q_proj|add_k_proj|add_v_proj, rows [0,D) q, [D,2D) k, [2D,3D) v
@@ -233,7 +254,7 @@ struct Param {
     bool conv = false;  // OIHW source
     char init = 'w';    // recipe class for pd_init_random_weights: w, b, g(amma), e(beta)
     bool loaded = false;
-    int group = 0;      // 0: UNet + ControlNet (needed to sample), 1: VAE decoder, 2: text transformer, 3: SD3 networks, 4: VAE encoder, 5: HED
+    int group = 0;      // 0: UNet + ControlNet (needed to sample), 1: VAE decoder, 2: text transformer, 3: SD3 networks, 4: VAE encoder, 5: HED, 6: SD3 text encoders
 };
 
 struct Act {
@@ -514,6 +535,20 @@ struct pd_engine {
     int sd3_embed(Sd3NetW& net, const Sd3Io& io, bool controlnet, Act& hs, Act& c, Act& modbuf);
     int sd3_block(const Sd3BlockW& b, Act& x, Act& c, const Act& modbuf, const Act& qk, const Act& vt, const Act* pre_add = nullptr);
     int sd3_forward(const Sd3Io& io, float* v_out_dev, int control_index, float* control_out_dev);
+    // SD3 text encoders (sd3_text.cpp; pd_sd3_text_configure): CLIP-L, CLIP-G, T5.  Residual streams are fp32 in every mode.
+    Sd3ClipW sd3_clip[2];
+    Sd3T5W sd3_t5;
+    int sd3_text_joint = 0;
+    std::vector<int32_t> t5_bucket_host;   // bucket of every distance -(L - 1) .. L - 1 of the last T5 call (kept alive for the upload)
+    void build_sd3_clip(const std::string& prefix, Sd3ClipW& w);
+    void build_sd3_t5(const std::string& prefix);
+    // hidden (hidden_states[-(clip_skip + 2)], no final LayerNorm) -> columns [c_off, c_off + width) of hid [B][hid_rows][hid_ld] (columns past the
+    // encoder's own are zeroed); pooled (text_embeds) -> pooled [B][pooled_ld]; either destination may be null
+    int sd3_clip_forward(Sd3ClipW& w, const int* ids_dev, int B, int clip_skip, float* hid, int hid_rows, int hid_ld, int c_off, int width,
+                         float* pooled, int pooled_ld);
+    // last_hidden_state -> rows [row_off, row_off + Lt) of out [B][out_rows][d_model]
+    int sd3_t5_forward(const int* ids_dev, int B, int Lt, float* out, int out_rows, int row_off);
+    int rmsnorm(const Act& x, void* y, int y_dt, const float* w, float eps, int y_sample_rows = 0, int y_row_off = 0, int y_ld = 0);
     int opt_slab_gn = 1;             // split-K conv1 -> single-kernel norm2 without a finalize pass (SlabDefer; option "slab_gn")
     int opt_sd3_fp8 = 0;       // 0 off, 1: the AdaLN-fed projections, 2: also the feed-forward-out projections (e4m3 GELU output under a norm bound)  // SD3 path: QKV and feed-forward-in projections in PREC_FP8 (e4m3 operands, per-row scales)
     bool sd3_fp8_dirty = true;
@@ -579,7 +614,8 @@ struct pd_engine {
     int repeat_act(const Act& src, int reps, Act& dst);
     static Act batch_view(const Act& a, int first, int count);
     int attention(const void* Q, int ldq, const void* K, int ldk, const void* VT, int vt_ld, void* O, int ldo, int B, int Nq,
-                  int Nk, int C, int heads = 0, bool causal = false, long long q_bs = 0, long long k_bs = 0, long long o_bs = 0);
+                  int Nk, int C, int heads = 0, bool causal = false, long long q_bs = 0, long long k_bs = 0, long long o_bs = 0,
+                  const float* relbias = nullptr, float scale = 0.f);   // relbias: T5's Toeplitz bias rows (launch_attention_bias); scale 0: dh^-0.5
 
     // networks
     int run_controlnet(const Act& x_in, int emb_row, int emb_stride, const float* scales);

@@ -39,7 +39,8 @@ static_assert(BKB == 128, "swz8 (pd_common.h) is the swizzle of 128-byte rows");
 // are contiguous).  AF32: 2-byte compute with an fp32 A source (converted while staging; only meaningful when P != DT_F32).
 // GG: the GEGLU epilogue (act == 2) instead of the plain one -- a wave's WTN columns are whole [80 x | 80 gate] blocks.
 // MM: the MMDiT epilogue extras (pd_mma.h epilogue4<true>), linear layers of the SD3 path only.
-template <int P, int BM, int BN, int WM, int WN, bool CONV, bool AF32, bool GG = false, bool MM = false, bool RELU = false>
+// GT (with GG): ACT_GATED_TANH_GELU instead of GEGLU's erf-GELU gate -- T5's feed-forward, instantiations of their own.
+template <int P, int BM, int BN, int WM, int WN, bool CONV, bool AF32, bool GG = false, bool MM = false, bool RELU = false, bool GT = false>
 __global__ __launch_bounds__(WM * WN * 64, (BM == 128 && WM * WN == 8) ? 4 : 2) void igemm_kernel(GemmParams p) {
     constexpr bool F32 = prec_f32_storage(P);
     // register prefetch depth: two K steps ahead (two named staging sets) unless the fp32->bf16 staging
@@ -438,7 +439,15 @@ __global__ __launch_bounds__(WM * WN * 64, (BM == 128 && WM * WN == 8) ? 4 : 2) 
                     }
                     f32x4 o;
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) o[j] = x[j] * (F32 ? gelu_f(g[j]) : gelu_fast(g[j]));
+                    for (int j = 0; j < 4; ++j) {
+                        if constexpr (GT) {   // NewGELUActivation(gate) * x in fp32 (T5-XXL's products leave the fp16 range: saturate, never inf)
+                            const float u = 0.7978845608028654f * fmaf(0.044715f * g[j] * g[j], g[j], g[j]);
+                            o[j] = x[j] * (g[j] / (1.0f + __expf(-2.0f * u)));
+                            if (p.c_dt == DT_F16) o[j] = fminf(fmaxf(o[j], -65504.f), 65504.f);
+                        } else {
+                            o[j] = x[j] * (F32 ? gelu_f(g[j]) : gelu_fast(g[j]));
+                        }
+                    }
                     store4(p.C, (size_t)gm * p.ldc + on, p.c_dt, o);
                 }
             }
@@ -501,14 +510,14 @@ __global__ __launch_bounds__(256) void splitk_finalize_kernel(GemmParams p) {
     }
 }
 
-template <int P, int BM, int BN, int WM, int WN, bool CONV, bool AF32, bool GG = false, bool MM = false, bool RELU = false>
+template <int P, int BM, int BN, int WM, int WN, bool CONV, bool AF32, bool GG = false, bool MM = false, bool RELU = false, bool GT = false>
 int launch_one(const GemmParams& p, hipStream_t s, hipEvent_t mid, int* parts) {
     constexpr int NTHREADS = WM * WN * 64;
     constexpr int SMEM_BYTES = 2 * (BM + BN) * BKB + ((GG || MM) ? 0 : BM * 8);   // staging buffers + {mean, rstd} of the block's rows (LayerNorm fold)
     static unsigned long long attr_done = 0;
     const int mtiles = (p.M + BM - 1) / BM, ntiles = (p.N + BN - 1) / BN;
     if (parts) { *parts = ntiles * WN; return 0; }   // gemm_stats_parts: which tile, no launch
-    auto kfn = igemm_kernel<P, BM, BN, WM, WN, CONV, AF32, GG, MM, RELU>;
+    auto kfn = igemm_kernel<P, BM, BN, WM, WN, CONV, AF32, GG, MM, RELU, GT>;
     if (ensure_dyn_smem(reinterpret_cast<const void*>(kfn), SMEM_BYTES, &attr_done)) return 1;
     if (p.stats_out && p.stats_parts != ntiles * WN) return 1;   // the statistics rows were sized for another tile
     dim3 grid(mtiles * ntiles, p.splitk > 1 ? p.splitk : 1);
@@ -528,7 +537,7 @@ int launch_one(const GemmParams& p, hipStream_t s, hipEvent_t mid, int* parts) {
 }  // namespace
 
 int launch_splitk_finalize(const GemmParams& p, hipStream_t s) {
-    if (p.splitk <= 1 || !p.slab || p.N % 4 || p.act == 2 || p.vt_begin < p.N) return 1;
+    if (p.splitk <= 1 || !p.slab || p.N % 4 || p.act == 2 || p.act == 7 || p.vt_begin < p.N) return 1;
     long long total = (long long)p.M * (p.N / 4);
     int nb = (int)((total + 255) / 256);
     if (nb > 4096) nb = 4096;
@@ -561,6 +570,11 @@ int launch_prec(const GemmParams& p, hipStream_t s, hipEvent_t mid, int* parts) 
         if (tile == 1 || tile == 3) return launch_one<P, 256, 160, 4, 2, true, false, false, false, true>(p, s, mid, parts);
         return launch_one<P, 128, 160, 2, 2, true, false, false, false, true>(p, s, mid, parts);
     }
+    if (p.act == 7) {   // ACT_GATED_TANH_GELU: the 4 x 1 / 8 x 1 GEGLU tiles with the tanh gate (a 256 x 320 request takes the 256 x 160 one)
+        if (conv || af32 || p.ln_stats || p.stats_out) return 1;
+        if (tile == 1 || tile == 3) return launch_one<P, 256, 160, 8, 1, false, false, true, false, false, true>(p, s, mid, parts);
+        return launch_one<P, 128, 160, 4, 1, false, false, true, false, false, true>(p, s, mid, parts);
+    }
     if (p.act == 2) {
         if (conv || af32 || p.ln_stats || p.stats_out) return 1;
         // 256 x 320 on 4 x 2 waves (wave tile 64 x 160 = one GEGLU block): 14 fragment reads per 40 MFMAs.  Round 1 ran it on
@@ -575,13 +589,13 @@ int launch_prec(const GemmParams& p, hipStream_t s, hipEvent_t mid, int* parts) 
         // 4608, 6144) -- no padded columns, and 8192 rows x 1536 columns is exactly one block per CU
         if (tile == 4) {
             if (conv || af32) return 1;
-            if (p.act == 4 || p.gate || p.c_sample_rows || p.a_sample_rows) return launch_one<P, 256, 192, 4, 2, false, false, false, true>(p, s, mid, parts);
+            if (p.act == 4 || p.act == 6 || p.gate || p.c_sample_rows || p.a_sample_rows) return launch_one<P, 256, 192, 4, 2, false, false, false, true>(p, s, mid, parts);
             return launch_one<P, 256, 192, 4, 2, false, false, false, false>(p, s, mid, parts);
         }
     }
     // (measured and dropped: 128 x 192 four-wave blocks, two per CU so that one block's epilogue runs under the other's K loop
     // -- 43 % more operand bytes per FLOP through L2 cost more than the overlap gains: SD3 step 36.1 -> 37.4 ms)
-    if (p.act == 4 || p.gate || p.c_sample_rows || p.a_sample_rows) {   // MMDiT epilogue extras
+    if (p.act == 4 || p.act == 6 || p.gate || p.c_sample_rows || p.a_sample_rows) {   // MMDiT epilogue extras (and ACT_ERF_GELU, which lives with them)
         if (p.ln_stats || p.stats_out) return 1;   // no LayerNorm fold in the MM instantiations: linear layers over operands of the compute type
         if (conv || af32) return 1;
         if constexpr (F) {
@@ -612,7 +626,7 @@ int launch_prec(const GemmParams& p, hipStream_t s, hipEvent_t mid, int* parts) 
 
 int launch_gemm(const GemmParams& p, int prec, hipStream_t s, hipEvent_t mid, int* parts) {
     if (p.M <= 0 || p.N <= 0) return 0;
-    if (p.splitk > 1 && (p.act == 2 || p.vt_begin < p.N || !p.slab || p.N % 4)) return 1;
+    if (p.splitk > 1 && (p.act == 2 || p.act == 7 || p.vt_begin < p.N || !p.slab || p.N % 4)) return 1;
     if (prec == PREC_FP8) return launch_fp8(p, s, mid, parts);
     if (prec_f32_storage(prec) ? p.a_dt != DT_F32 : (p.a_dt != DT_F32 && p.a_dt != prec)) return 1;   // operand type must match the mode
     switch (prec) {

@@ -407,7 +407,7 @@ int launch_ring(const GemmParams& p, hipStream_t s, int* parts) {
 // what rgemm_kernel covers: plain linear layers over 2-byte operands of the compute type
 bool ring_gemm_eligible(const GemmParams& p, int prec) {
     if (prec != DT_F16 && prec != DT_BF16) return false;
-    if (p.taps != 1 || p.a_dt != prec || p.a_silu || p.splitk > 1 || p.act == 4 || p.act == 5 || p.rowvec) return false;
+    if (p.taps != 1 || p.a_dt != prec || p.a_silu || p.splitk > 1 || p.act >= 4 || p.rowvec) return false;   // (tanh-GELU, ReLU, erf-GELU, the gated tanh-GELU: gemm.hip)
     // GEGLU: whole 160-column blocks, nothing else in the epilogue
     if (p.act == 2 && (p.N % 160 || p.R || p.ln_stats || p.stats_out || p.vt_begin < p.N || p.out_scale != 1.f)) return false;
     if (p.R && (dt_size(p.r_dt) != 2 || (unsigned long long)p.M * (unsigned)p.ldr * 2ull >= (1ull << 31))) return false;   // the prefetched residual values are 2-byte, 32-bit offsets

@@ -161,7 +161,10 @@ static inline int ensure_dyn_smem(const void* fn, int bytes, unsigned long long*
 // GemmParams::act (the kernels compare against the values).  ACT_RELU is compiled into instantiations of its own (pd_mma.h epilogue4_value<MM, RELU>:
 // plain conv3x3 on igemm / patch1 / patch2, and the split-K finalize pass), so no other launch carries a branch for it; the ring GEMM, the 4-wave
 // patch conv and every linear layer refuse it
-enum Activation { ACT_NONE = 0, ACT_SILU = 1, ACT_GEGLU = 2, ACT_QUICK_GELU = 3, ACT_TANH_GELU = 4, ACT_RELU = 5 };
+// ACT_ERF_GELU (CLIP-G's fc1) lives in the MM instantiations like ACT_TANH_GELU; ACT_GATED_TANH_GELU (T5's wi_0 / wi_1 pair, packed like a GEGLU
+// matrix: x half = wi_1, gate half = wi_0) is gelu_new(gate) * x formed in fp32, saturated to the fp16 range on an fp16 store, in GG instantiations
+// of its own (gemm.hip GT).  Neither runs on the ring GEMM.
+enum Activation { ACT_NONE = 0, ACT_SILU = 1, ACT_GEGLU = 2, ACT_QUICK_GELU = 3, ACT_TANH_GELU = 4, ACT_RELU = 5, ACT_ERF_GELU = 6, ACT_GATED_TANH_GELU = 7 };
 struct GemmParams {
     const void* A;        // activations, NHWC (conv) or [M, lda] rows (linear)
     const void* W;        // weights [Nw][Kpad] in the compute type, K-contiguous (taps x Cin)
@@ -261,6 +264,8 @@ int launch_conv_patch2(const GemmParams& p, int prec, hipStream_t s);   // conv_
 bool conv_patch4_eligible(const GemmParams& p, int prec);              // conv_patch4.hip: 4 waves per block, one per SIMD, 32x32x16 MFMAs, LDS-DMA operands (2-byte types)
 int launch_conv_patch4(const GemmParams& p, int prec, hipStream_t s);
 int launch_attention(const AttnParams& p, int prec, hipStream_t s);
+// T5 self-attention: softmax(Q K^T * scale + bias) V, bias[h][q][k] = relbias[h][k - q + Nk - 1] (fp32, in exp2 units: times log2 e); dh 64, Nq == Nk
+int launch_attention_bias(const AttnParams& p, const float* relbias, int prec, hipStream_t s);
 // st_tail.hip: everything after the self-attention product of a 320-channel SpatialTransformer block in one kernel (attn1.to_out +
 // residual, norm2, attn2 against the hoisted context K / V, norm3, GEGLU feed-forward, proj_out + the block residual)
 bool st_tail_eligible(int prec, int C, int heads, int rows_per_sample, int Nk);
@@ -313,6 +318,22 @@ int launch_softmax_rows(const float* in, void* out, int out_dt, int rows, int n,
 int launch_embed_tokens(const int* ids, const void* tok, int tok_ld, const void* pos, int pos_ld, int dt, void* out, int out_dt,
                         int B, int L, int C, int vocab, hipStream_t s);
 int launch_nhwc_to_nchw(const void* in, int in_dt, float* out, int B, int C, int H, int W, int Cpad, float scale, hipStream_t s);
+// sd3_text.hip: the small kernels of the SD3 text encoders (sd3_text.cpp)
+// out[row][:] = tok[clamp(ids[row])][:] (table rows [vocab][tok_ld] in dt) -> fp32 [rows][C]: T5's token embedding (no positions)
+int launch_embed_rows(const int* ids, const void* tok, int tok_ld, int dt, float* out, long long rows, int C, int vocab, hipStream_t s);
+// T5LayerNorm: y = w * x * rsqrt(mean(x^2) + eps), statistics in fp32, x fp32 [rows][C]; row r of y lands at
+// y + ((r / rows_per_sample) * y_sample_rows + y_row_off + r % rows_per_sample) * y_ld (y_sample_rows 0: row r), in y_dt
+int launch_rmsnorm_rows(const float* x, void* y, int y_dt, const float* w, long long rows, int C, float eps, int rows_per_sample, int y_sample_rows,
+                        int y_row_off, int y_ld, hipStream_t s);
+// relbias[h][i] = log2(e) * table[bucket[i]][h] for i < 2 L - 1 (bucket: host-made, pd_t5_relative_buckets); table [num_buckets][ld] in dt
+int launch_t5_relbias(const int* bucket, const void* table, int ld, int dt, float* relbias, int heads, int n, hipStream_t s);
+// dst[(b * dst_sample_rows + r) * dst_ld + c_off + c] = c < C ? src[(b * rows_per_sample + r) * C + c] : 0 for c < width: one encoder's hidden
+// state (and, with width > C, the zero pad behind it) into the joint [B, 77 + Lt, joint_dim] layout
+int launch_joint_write(const float* src, float* dst, int B, int rows_per_sample, int C, int width, int dst_sample_rows, int dst_ld, int c_off,
+                       hipStream_t s);
+// out[b][:] = x[b * L + pos(b)][:], pos = argmax(ids[b]) (first maximum) when eos_id == 2, else the first ids == eos_id (0 when absent):
+// transformers' CLIPTextTransformer pooling
+int launch_eos_gather(const int* ids, const float* x, float* out, int B, int L, int C, int eos_id, hipStream_t s);
 int launch_cast_rows(const float* in, void* out, int out_dt, long long rows, int C, int Cpad, hipStream_t s);
 int launch_concat_add(const void* a, const void* a_add, const void* b, const void* b_add, void* out, int dt,
                       long long rows, int Ca, int Cb, hipStream_t s, long long b_rows = 0, long long b_add_rows = 0);

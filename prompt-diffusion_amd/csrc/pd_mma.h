@@ -191,6 +191,10 @@ __device__ __forceinline__ f32x4 epilogue4_value(const GemmParams& p, int gm, in
                 const float d = 1.0f + __expf(-2.0f * u);
                 v[j] = fast ? v[j] * __builtin_amdgcn_rcpf(d) : v[j] / d;
             }
+        } else if (p.act == 6) {   // exact (erf) GELU, CLIP-G's fc1: erf to 1.5e-7 absolute in every mode (libm's erff would cost these
+            // instantiations, which the MMDiT path shares, ~45 instructions and their registers per value)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = gelu_fast(v[j]);
         }
     }
     v *= p.out_scale;

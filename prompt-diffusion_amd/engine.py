@@ -264,6 +264,7 @@ EXPORTS = [
     "pd_philox4x32_10", "pd_set_rng", "pd_get_rng", "pd_randn",
     "pd_hed_configure", "pd_hed_weights_missing", "pd_hed_detect", "pd_op_hed_stage_tail", "pd_op_hed_fuse",
     "pd_resample_coefficients", "pd_image_load", "pd_image_store",
+    "pd_sd3_text_configure", "pd_sd3_text_weights_missing", "pd_sd3_encode_prompt", "pd_sd3_text_encoder", "pd_t5_relative_buckets",
 ]
 
 

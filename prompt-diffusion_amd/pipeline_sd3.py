@@ -11,6 +11,12 @@ reference does with modules outside the path is injected as callables (the bound
   vae_decode(latents) -> images in [-1, 1]                                       (vae.decode, :1270)
   down_proj(pair [B, 6, H, W]) -> [B, 3, H, W]                                   (controlnet.down_proj, encode_support_pair :189-198)
 
+Without an injected `encode_prompt`, an engine with text encoders (`SD3Engine.configure_text`) and `tokenizers=(tok_l, tok_g, tok_t5)`
+-- callables taking `(list[str], max_length)` and returning int ids `[B, max_length]`; `tok_t5` may be None on an engine without T5 --
+make `prompt=` strings work: the pipeline does what the reference's encode_prompt (:351-545) does around the encoders (prompt_2 / prompt_3
+fallbacks, the negative prompt with its checks, the negative pass at clip_skip None, the per-image repeat, max_sequence_length) and the
+engine encodes (`SD3Engine.encode_prompt_ids`).  An injected `encode_prompt` keeps precedence.
+
 The three steps of the loop body (controlnet, transformer, CFG + scheduler.step; :1192-1245) run inside the engine
 (`SD3Engine.sample`); with `callback_on_step_end` the loop is driven step by step from here (`SD3Engine.forward` + the same
 Euler update) so that the callback can replace the latents or the embeddings (:1247-1258).  Arrays are NumPy (torch tensors
@@ -35,8 +41,10 @@ class StableDiffusion3PromptDiffusionPipeline:
 
     def __init__(self, engine: SD3Engine, encode_prompt: Optional[Callable] = None, vae_encode: Optional[Callable] = None,
                  vae_decode: Optional[Callable] = None, down_proj: Optional[Callable] = None, vae_scaling_factor: float = 1.5305,
-                 vae_shift_factor: float = 0.0609, vae_scale_factor: int = 8, shift: float = 3.0):
+                 vae_shift_factor: float = 0.0609, vae_scale_factor: int = 8, shift: float = 3.0, tokenizers=None,
+                 tokenizer_max_length: int = 77):
         self.engine = engine
+        self.tokenizers, self.tokenizer_max_length = tokenizers, tokenizer_max_length
         self.encode_prompt, self.vae_encode, self.vae_decode, self.down_proj = encode_prompt, vae_encode, vae_decode, down_proj
         self.vae_scaling_factor, self.vae_shift_factor, self.vae_scale_factor = vae_scaling_factor, vae_shift_factor, vae_scale_factor
         self.shift = shift
@@ -93,6 +101,53 @@ class StableDiffusion3PromptDiffusionPipeline:
             raise ValueError("If `negative_prompt_embeds` are provided, `negative_pooled_prompt_embeds` also have to be passed.")
         if max_sequence_length is not None and max_sequence_length > 512:
             raise ValueError(f"`max_sequence_length` cannot be greater than 512 but is {max_sequence_length}")
+
+    # ------------------------------------------------------------------ encode_prompt (:351-545) over the engine's encoders
+    def _engine_encodes(self) -> bool:
+        return self.tokenizers is not None and getattr(self.engine, "text_cfg", None) is not None
+
+    def _encode_ids(self, prompt, prompt_2, prompt_3, clip_skip, max_sequence_length):
+        """_get_clip_prompt_embeds x 2 + _get_t5_prompt_embeds + the cat / pad / cat of :457-471, for lists of strings."""
+        tok_l, tok_g, tok_t5 = self.tokenizers
+        ids_l = np.asarray(tok_l(prompt, self.tokenizer_max_length))
+        ids_g = np.asarray(tok_g(prompt_2, self.tokenizer_max_length))
+        ids_t5 = None
+        if self.engine.text_cfg.t5 is not None:
+            if tok_t5 is None:
+                raise ValueError("the engine has a T5 encoder: `tokenizers` needs its tokenizer as third entry")
+            ids_t5 = np.asarray(tok_t5(prompt_3, max_sequence_length))
+        pe, pooled = self.engine.encode_prompt_ids(ids_l, ids_g, ids_t5, clip_skip=clip_skip)
+        return _np(pe), _np(pooled)
+
+    def _encode_prompt_engine(self, prompt, prompt_2, prompt_3, negative_prompt, negative_prompt_2, negative_prompt_3,
+                              do_classifier_free_guidance, num_images_per_prompt, clip_skip, max_sequence_length, skip_negative=False):
+        prompt = [prompt] if isinstance(prompt, str) else prompt
+        batch_size = len(prompt)
+        prompt_2 = prompt_2 or prompt
+        prompt_2 = [prompt_2] if isinstance(prompt_2, str) else prompt_2
+        prompt_3 = prompt_3 or prompt
+        prompt_3 = [prompt_3] if isinstance(prompt_3, str) else prompt_3
+        pe, ppe = self._encode_ids(prompt, prompt_2, prompt_3, clip_skip, max_sequence_length)
+        # repeat(1, n, 1).view(B * n, L, -1) (:289-290, :342-346): the copies of one prompt are neighbours
+        pe, ppe = np.repeat(pe, num_images_per_prompt, 0), np.repeat(ppe, num_images_per_prompt, 0)
+        npe = nppe = None
+        if do_classifier_free_guidance and not skip_negative:
+            negative_prompt = negative_prompt or ""
+            negative_prompt_2 = negative_prompt_2 or negative_prompt
+            negative_prompt_3 = negative_prompt_3 or negative_prompt
+            negative_prompt = batch_size * [negative_prompt] if isinstance(negative_prompt, str) else negative_prompt
+            negative_prompt_2 = batch_size * [negative_prompt_2] if isinstance(negative_prompt_2, str) else negative_prompt_2
+            negative_prompt_3 = batch_size * [negative_prompt_3] if isinstance(negative_prompt_3, str) else negative_prompt_3
+            if prompt is not None and type(prompt) is not type(negative_prompt):
+                raise TypeError(f"`negative_prompt` should be the same type to `prompt`, but got {type(negative_prompt)} !="
+                                f" {type(prompt)}.")
+            elif batch_size != len(negative_prompt):
+                raise ValueError(f"`negative_prompt`: {negative_prompt} has batch size {len(negative_prompt)}, but `prompt`:"
+                                 f" {prompt} has batch size {batch_size}. Please make sure that passed `negative_prompt` matches"
+                                 " the batch size of `prompt`.")
+            npe, nppe = self._encode_ids(negative_prompt, negative_prompt_2, negative_prompt_3, None, max_sequence_length)
+            npe, nppe = np.repeat(npe, num_images_per_prompt, 0), np.repeat(nppe, num_images_per_prompt, 0)
+        return pe, npe, ppe, nppe
 
     # ------------------------------------------------------------------ host pieces of steps 3 and 5
     def prepare_image(self, image, batch_size, num_images_per_prompt):
@@ -217,12 +272,18 @@ class StableDiffusion3PromptDiffusionPipeline:
             batch_size = prompt_embeds.shape[0]
         cfg_on = self.do_classifier_free_guidance
         if prompt is not None:
-            if self.encode_prompt is None:
+            if self.encode_prompt is None and not self._engine_encodes():
                 raise ValueError("text prompts need the `encode_prompt` callable; pass `prompt_embeds` / `pooled_prompt_embeds` otherwise")
-            prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds = self.encode_prompt(
+            encode = self.encode_prompt if self.encode_prompt is not None else self._encode_prompt_engine
+            given_negative = (negative_prompt_embeds, negative_pooled_prompt_embeds)
+            extra = {"skip_negative": True} if self.encode_prompt is None and negative_prompt_embeds is not None else {}
+            prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds = encode(
                 prompt=prompt, prompt_2=prompt_2, prompt_3=prompt_3, negative_prompt=negative_prompt, negative_prompt_2=negative_prompt_2,
                 negative_prompt_3=negative_prompt_3, do_classifier_free_guidance=cfg_on, num_images_per_prompt=num_images_per_prompt,
-                clip_skip=clip_skip, max_sequence_length=max_sequence_length)
+                clip_skip=clip_skip, max_sequence_length=max_sequence_length, **extra)
+            if self.encode_prompt is None and given_negative[0] is not None:
+                # negative embeddings given next to prompt strings are returned as they came (:473: only a missing one is encoded)
+                negative_prompt_embeds, negative_pooled_prompt_embeds = given_negative
             rep = 1
         else:
             rep = num_images_per_prompt          # encode_prompt repeats given embeddings per image (:397-399 of diffusers' encode_prompt)

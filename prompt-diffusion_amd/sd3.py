@@ -2,9 +2,9 @@
 
 Mirrors, at the tensor level, what the reference's SD3 pipeline does per denoising step
 (promptdiffusioncontrolnetpipeline_sd3.py:1192-1245): ControlNet (promptdiffusioncontrolnet_sd3.py:362-483), transformer
-with ``block_controlnet_hidden_states``, classifier-free guidance, FlowMatchEuler step.  Text encoders (CLIP-L, CLIP-G, T5),
-the VAE and ``down_proj`` / ``encode_support_pair`` stay with the caller: the boundary takes prompt embeddings and condition
-LATENTS.  PARITY UNPINNED (diffusers is absent offline): checked against oracle/sd3_oracle.py only."""
+with ``block_controlnet_hidden_states``, classifier-free guidance, FlowMatchEuler step.  The VAE stays with the caller: the
+boundary takes prompt embeddings and condition LATENTS.  The text encoders (CLIP-L, CLIP-G, T5; pipeline :238-545) are opt-in on the
+same engine (``SD3Engine.configure_text`` / ``encode_prompt_ids``: token ids in, prompt embeddings out; tokenisation is the caller's).  PARITY UNPINNED (diffusers is absent offline): checked against oracle/sd3_oracle.py only."""
 import ctypes as C
 import math
 from dataclasses import dataclass
@@ -61,6 +61,169 @@ class pd_sd3_args(C.Structure):
                 ("conditioning_scale", C.c_float),
                 ("latents", C.c_void_p), ("timestep", C.c_void_p), ("context", C.c_void_p), ("pooled", C.c_void_p),
                 ("cond", C.c_void_p), ("pair", C.c_void_p), ("cn_pooled", C.c_void_p), ("reserved", C.c_int64 * 3)]
+
+
+@dataclass(frozen=True)
+class CLIPTextConfig:
+    """One CLIPTextModelWithProjection (transformers' CLIPTextConfig names in the comments)."""
+    vocab: int = 49408
+    hidden: int = 768              # hidden_size; head dim hidden / heads must be 64
+    ff: int = 3072                 # intermediate_size
+    heads: int = 12
+    layers: int = 12
+    max_positions: int = 77
+    proj_dim: int = 768            # projection_dim
+    eos_token_id: int = 2          # 2 (both SD3 checkpoints): pooled row = argmax(ids); else the first ids == eos_token_id
+    act: str = "quick_gelu"        # hidden_act: "quick_gelu" (CLIP-L) or "gelu" (CLIP-G)
+
+
+@dataclass(frozen=True)
+class T5Config:
+    """The T5EncoderModel of SD3 (T5 v1.1 XXL: gated-gelu feed-forward, no biases, relative-position bias in block 0)."""
+    vocab: int = 32128
+    d_model: int = 4096
+    d_kv: int = 64
+    heads: int = 64
+    d_ff: int = 10240
+    layers: int = 24
+    num_buckets: int = 32
+    max_distance: int = 128
+    eps: float = 1e-6
+
+
+@dataclass(frozen=True)
+class SD3TextConfig:
+    clip_l: CLIPTextConfig = CLIPTextConfig()
+    clip_g: CLIPTextConfig = CLIPTextConfig(hidden=1280, ff=5120, heads=20, layers=32, proj_dim=1280, act="gelu")
+    t5: Optional[T5Config] = T5Config()    # None: no T5 encoder (prompt_embeds is then [B, 77, joint_dim])
+    joint_dim: int = 4096                  # row width of prompt_embeds; equals t5.d_model when T5 is present
+
+    @property
+    def pooled_dim(self) -> int:
+        return self.clip_l.proj_dim + self.clip_g.proj_dim
+
+
+SD3_MEDIUM_TEXT = SD3TextConfig()
+# the smallest shapes that exercise each risk: dh 64 everywhere; CLIP "g" with erf-GELU and an eos id != 2 (the first-match pooling rule);
+# T5 with heads * d_kv = 128 != d_model; 64 pad columns behind the 128 + 192 CLIP columns
+SD3_TINY_TEXT = SD3TextConfig(
+    clip_l=CLIPTextConfig(vocab=100, hidden=128, ff=256, heads=2, layers=3, proj_dim=96, eos_token_id=2, act="quick_gelu"),
+    clip_g=CLIPTextConfig(vocab=100, hidden=192, ff=320, heads=3, layers=4, proj_dim=160, eos_token_id=7, act="gelu"),
+    t5=T5Config(vocab=100, d_model=384, d_kv=64, heads=2, d_ff=320, layers=2), joint_dim=384)
+
+_CLIP_ACTS = {"quick_gelu": 0, "gelu": 1}
+
+
+class pd_sd3_clip_config(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("vocab", "hidden", "ff", "heads", "layers", "max_positions", "proj_dim", "eos_token_id", "act")]
+
+
+class pd_sd3_t5_config(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("vocab", "d_model", "d_kv", "heads", "d_ff", "layers", "num_buckets", "max_distance")] + \
+               [("eps", C.c_float)]
+
+
+class pd_sd3_text_config(C.Structure):
+    _fields_ = [("clip_l", pd_sd3_clip_config), ("clip_g", pd_sd3_clip_config), ("t5", pd_sd3_t5_config), ("joint_dim", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
+class pd_sd3_text_args(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("t5_len", C.c_int32), ("clip_skip", C.c_int32), ("mem", C.c_int32),
+                ("ids_clip_l", C.c_void_p), ("ids_clip_g", C.c_void_p), ("ids_t5", C.c_void_p), ("reserved", C.c_int64 * 3)]
+
+
+def sd3_text_spec(cfg: SD3TextConfig):
+    """(name, shape, kind) of every text-encoder tensor under the SD3 checkpoint's names: text_encoder. (CLIP-L), text_encoder_2. (CLIP-G),
+    text_encoder_3. (T5; the tied encoder.embed_tokens.weight is not listed)."""
+    out = []
+    for prefix, c in (("text_encoder.", cfg.clip_l), ("text_encoder_2.", cfg.clip_g)):
+        if c is None or c.layers == 0:
+            continue
+        P, Cc, F = prefix + "text_model.", c.hidden, c.ff
+        out.append((P + "embeddings.token_embedding.weight", (c.vocab, Cc), "w"))
+        out.append((P + "embeddings.position_embedding.weight", (c.max_positions, Cc), "w"))
+        for i in range(c.layers):
+            L = f"{P}encoder.layers.{i}."
+            for nm in ("k_proj", "v_proj", "q_proj", "out_proj"):
+                out += [(L + f"self_attn.{nm}.weight", (Cc, Cc), "w"), (L + f"self_attn.{nm}.bias", (Cc,), "b")]
+            out += [(L + "layer_norm1.weight", (Cc,), "gamma"), (L + "layer_norm1.bias", (Cc,), "beta")]
+            out += [(L + "mlp.fc1.weight", (F, Cc), "w"), (L + "mlp.fc1.bias", (F,), "b")]
+            out += [(L + "mlp.fc2.weight", (Cc, F), "w"), (L + "mlp.fc2.bias", (Cc,), "b")]
+            out += [(L + "layer_norm2.weight", (Cc,), "gamma"), (L + "layer_norm2.bias", (Cc,), "beta")]
+        out += [(P + "final_layer_norm.weight", (Cc,), "gamma"), (P + "final_layer_norm.bias", (Cc,), "beta")]
+        out.append((prefix + "text_projection.weight", (c.proj_dim, Cc), "w"))
+    t = cfg.t5
+    if t is not None and t.layers > 0:
+        P, D, I, F = "text_encoder_3.", t.d_model, t.heads * t.d_kv, t.d_ff
+        out.append((P + "shared.weight", (t.vocab, D), "w"))
+        for i in range(t.layers):
+            Bp = f"{P}encoder.block.{i}."
+            for nm in ("q", "k", "v"):
+                out.append((Bp + f"layer.0.SelfAttention.{nm}.weight", (I, D), "w"))
+            out.append((Bp + "layer.0.SelfAttention.o.weight", (D, I), "w"))
+            if i == 0:
+                out.append((Bp + "layer.0.SelfAttention.relative_attention_bias.weight", (t.num_buckets, t.heads), "w"))
+            out.append((Bp + "layer.0.layer_norm.weight", (D,), "gamma"))
+            out += [(Bp + "layer.1.DenseReluDense.wi_0.weight", (F, D), "w"), (Bp + "layer.1.DenseReluDense.wi_1.weight", (F, D), "w"),
+                    (Bp + "layer.1.DenseReluDense.wo.weight", (D, F), "w")]
+            out.append((Bp + "layer.1.layer_norm.weight", (D,), "gamma"))
+        out.append((P + "encoder.final_layer_norm.weight", (D,), "gamma"))
+    return out
+
+
+def synth_sd3_text_state_dict(cfg: SD3TextConfig, seed: int = 1234) -> Dict[str, np.ndarray]:
+    """Deterministic NumPy weights in the style of weights.synth_text_state_dict (w: N(0, 1 / fan_in), b: N(0, 0.02^2), gamma: 1 + N(0, 0.1^2),
+    beta: N(0, 0.1^2)).  T5 has no dh^-0.5 in its attention: like its own initialisation the query projection carries it (x d_kv^-0.5), and the
+    token embedding is N(0, 1)."""
+    sd = {}
+    for n, s, k in sd3_text_spec(cfg):
+        a = W.synth_tensor(n, s, k, seed)
+        if n.endswith("SelfAttention.q.weight"):
+            a = a * np.float32(cfg.t5.d_kv ** -0.5)
+        elif n == "text_encoder_3.shared.weight":
+            a = a * np.float32(math.sqrt(s[1]))
+        sd[n] = a
+    return sd
+
+
+def synth_sd3_token_ids(cfg: SD3TextConfig, batch: int, t5_len: int = 20, seed: int = 7):
+    """Synthetic (ids_l, ids_g, ids_t5), int32.  CLIP rows: BOS, a run of random tokens, EOS padding (as CLIPTokenizer pads); CLIP-L's EOS is
+    the largest id (the argmax rule), CLIP-G's is its eos_token_id, which no other token takes.  T5 rows: random tokens, 1 (</s>), 0 padding."""
+    g = np.random.default_rng(seed)
+    out = []
+    for c in (cfg.clip_l, cfg.clip_g):
+        argmax = c.eos_token_id == 2
+        eos = c.vocab - 1 if argmax else c.eos_token_id
+        ids = np.full((batch, c.max_positions), eos, np.int32)
+        ids[:, 0] = c.vocab - 2
+        for b in range(batch):
+            n = int(g.integers(3, c.max_positions - 4))
+            body = g.integers(8, c.vocab - 2, n)
+            ids[b, 1:1 + n] = body
+        out.append(ids)
+    t = cfg.t5
+    if t is None:
+        out.append(None)
+    else:
+        ids = np.zeros((batch, t5_len), np.int32)
+        for b in range(batch):
+            n = int(g.integers(1, max(2, t5_len - 1)))
+            ids[b, :n] = g.integers(2, t.vocab, n)
+            ids[b, n] = 1
+        out.append(ids)
+    return tuple(out)
+
+
+def t5_relative_buckets(length: int, num_buckets: int = 32, max_distance: int = 128, lib_path: Optional[str] = None) -> np.ndarray:
+    """T5Attention._relative_position_bucket (bidirectional) for the relative positions -(length - 1) .. length - 1, as the engine's host
+    function computes them (pd_t5_relative_buckets; no GPU involved)."""
+    lib = E.load_library(lib_path)
+    lib.pd_t5_relative_buckets.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+    out = np.empty(2 * length - 1, np.int32)
+    if lib.pd_t5_relative_buckets(length, num_buckets, max_distance, out.ctypes.data):
+        raise E.PdError(lib.pd_last_error().decode(errors="replace"))
+    return out
 
 
 def flow_match_sigmas(steps: int, shift: float = 3.0, num_train_timesteps: int = 1000) -> np.ndarray:
@@ -186,6 +349,11 @@ class SD3Engine:
         lib.pd_sd3_control.argtypes = [C.c_void_p, C.POINTER(pd_sd3_args), C.c_int32, C.c_void_p]
         lib.pd_sd3_sample.argtypes = [C.c_void_p, C.POINTER(pd_sd3_args), C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]
         lib.pd_sd3_down_proj.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+        lib.pd_sd3_text_configure.argtypes = [C.c_void_p, C.POINTER(pd_sd3_text_config)]
+        lib.pd_sd3_text_weights_missing.argtypes = [C.c_void_p]
+        lib.pd_sd3_encode_prompt.argtypes = [C.c_void_p, C.POINTER(pd_sd3_text_args), C.c_void_p, C.c_void_p]
+        lib.pd_sd3_text_encoder.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+        self.text_cfg: Optional[SD3TextConfig] = None
         c = pd_sd3_config(cfg.in_channels, cfg.out_channels, cfg.patch, cfg.heads, cfg.head_dim, cfg.layers, cfg.cn_layers,
                           cfg.joint_dim, cfg.pooled_dim, cfg.pos_embed_max_size, cfg.cn_pos_embed_max_size,
                           1 if cfg.force_zeros_for_pooled_projection else 0, 1 if cfg.qk_norm else 0,
@@ -206,8 +374,12 @@ class SD3Engine:
         known = {n for n, _ in self.base.param_names()}
         unexpected = []
         for name, arr in (sd.items() if isinstance(sd, dict) else sd):
-            if not (name.startswith("transformer.") or name.startswith("controlnet.")):
+            if not name.startswith(("transformer.", "controlnet.", "text_encoder.", "text_encoder_2.", "text_encoder_3.")):
                 continue
+            if name.startswith("text_encoder"):
+                # encoders this engine has not configured, and T5's tied copy of shared.weight, are not its tensors
+                if self.text_cfg is None or name == "text_encoder_3.encoder.embed_tokens.weight" or name not in known:
+                    continue
             if name in known:
                 self.base.load_tensor(name, arr)
             else:
@@ -217,6 +389,108 @@ class SD3Engine:
                             "this engine does not implement (qk_norm / dual_attention_layers?)")
         if strict and self.weights_missing():
             raise E.PdError(f"{self.weights_missing()} SD3 tensors missing after load_state_dict")
+
+    # ------------------------------------------------------------------ text encoders
+    def configure_text(self, cfg: SD3TextConfig = SD3_MEDIUM_TEXT) -> None:
+        """Registers CLIP-L, CLIP-G and (unless cfg.t5 is None) the T5 encoder on this engine; their tensors then load through
+        load_state_dict under the checkpoint's text_encoder. / text_encoder_2. / text_encoder_3. names.  Once per engine."""
+        if cfg.joint_dim != self.cfg.joint_dim or cfg.pooled_dim != self.cfg.pooled_dim:
+            raise ValueError(f"text encoders give joint_dim {cfg.joint_dim} / pooled_dim {cfg.pooled_dim}, the SD3 networks take "
+                             f"{self.cfg.joint_dim} / {self.cfg.pooled_dim}")
+        for c in (cfg.clip_l, cfg.clip_g):
+            if c.act not in _CLIP_ACTS:
+                raise ValueError(f"CLIP hidden_act {c.act!r}: only {sorted(_CLIP_ACTS)} are built")
+        c = pd_sd3_text_config()
+        for dst, src in ((c.clip_l, cfg.clip_l), (c.clip_g, cfg.clip_g)):
+            (dst.vocab, dst.hidden, dst.ff, dst.heads, dst.layers, dst.max_positions, dst.proj_dim, dst.eos_token_id, dst.act) = (
+                src.vocab, src.hidden, src.ff, src.heads, src.layers, src.max_positions, src.proj_dim, src.eos_token_id, _CLIP_ACTS[src.act])
+        if cfg.t5 is not None:
+            t = cfg.t5
+            (c.t5.vocab, c.t5.d_model, c.t5.d_kv, c.t5.heads, c.t5.d_ff, c.t5.layers, c.t5.num_buckets, c.t5.max_distance, c.t5.eps) = (
+                t.vocab, t.d_model, t.d_kv, t.heads, t.d_ff, t.layers, t.num_buckets, t.max_distance, t.eps)
+        c.joint_dim = cfg.joint_dim
+        self.base._check(self.base.lib.pd_sd3_text_configure(self.base._h, C.byref(c)))
+        self.text_cfg = cfg
+
+    def text_weights_missing(self) -> int:
+        return int(self.base.lib.pd_sd3_text_weights_missing(self.base._h))
+
+    def _ids(self, ids, length, what):
+        """int32 [B, length] ids as (owner, pointer, mem)."""
+        if E._is_torch(ids):
+            import torch
+            t = ids.detach().to(torch.int32).contiguous()
+            if t.is_cuda:
+                if t.ndim != 2 or (length and t.shape[1] != length):
+                    raise ValueError(f"{what} must be [B, {length or 'L'}]")
+                return t, t.data_ptr(), E.PD_MEM_DEVICE
+            ids = t.numpy()
+        a = np.ascontiguousarray(ids, np.int32)
+        if a.ndim != 2 or (length and a.shape[1] != length):
+            raise ValueError(f"{what} must be [B, {length or 'L'}]")
+        return a, a.ctypes.data, E.PD_MEM_HOST
+
+    def encode_prompt_ids(self, ids_l, ids_g, ids_t5=None, clip_skip: Optional[int] = None, zero_t5_rows: bool = False):
+        """encode_prompt after tokenisation (promptdiffusioncontrolnetpipeline_sd3.py:443-471): token ids [B, 77] x 2 and [B, Lt] ->
+        (prompt_embeds [B, 77 + Lt, joint_dim], pooled [B, pooled_dim]), fp32; NumPy in, NumPy out, CUDA torch in, CUDA torch out.
+        clip_skip None = 0: hidden_states[-2].  Without a T5 encoder the result is [B, 77, joint_dim]; zero_t5_rows appends the
+        [B, 77, joint_dim] zero block the reference concatenates in that case."""
+        if self.text_cfg is None:
+            raise E.PdError("this engine has no text encoders: call configure_text first")
+        cfg = self.text_cfg
+        has_t5 = cfg.t5 is not None
+        if has_t5 and ids_t5 is None:
+            raise ValueError("ids_t5 is required: this engine has a T5 encoder")
+        keep = [self._ids(ids_l, cfg.clip_l.max_positions, "ids_l"), self._ids(ids_g, cfg.clip_g.max_positions, "ids_g")]
+        if has_t5:
+            keep.append(self._ids(ids_t5, 0, "ids_t5"))
+        mems = {k[2] for k in keep}
+        Bn = keep[0][0].shape[0]
+        if len(mems) != 1 or any(k[0].shape[0] != Bn for k in keep):
+            raise ValueError("all id arrays of one call must share the batch size and the memory space")
+        mem = mems.pop()
+        Lt = keep[2][0].shape[1] if has_t5 else 0
+        if has_t5 and not 1 <= Lt <= 512:
+            raise ValueError(f"ids_t5 must hold 1 to 512 tokens per row, got {Lt}")
+        a = pd_sd3_text_args()
+        a.batch, a.t5_len, a.clip_skip, a.mem = Bn, Lt, int(clip_skip or 0), mem
+        a.ids_clip_l, a.ids_clip_g = keep[0][1], keep[1][1]
+        a.ids_t5 = keep[2][1] if has_t5 else None
+        pe, pe_ptr = self._out(mem, keep[0][0], (Bn, 77 + Lt, cfg.joint_dim))
+        po, po_ptr = self._out(mem, keep[0][0], (Bn, cfg.pooled_dim))
+        self.base._order_after_torch(mem)
+        self.base._check(self.base.lib.pd_sd3_encode_prompt(self.base._h, C.byref(a), pe_ptr, po_ptr))
+        if zero_t5_rows and not has_t5:
+            if mem == E.PD_MEM_DEVICE:
+                import torch
+                pe = torch.cat([pe, torch.zeros_like(pe)], 1)
+            else:
+                pe = np.concatenate([pe, np.zeros_like(pe)], 1)
+        return pe, po
+
+    def text_encoder(self, which: str, ids, clip_skip: Optional[int] = None):
+        """One encoder alone.  which "clip_l" / "clip_g": ids [B, 77] -> (hidden_states[-(clip_skip + 2)] [B, 77, hidden], text_embeds
+        [B, proj_dim]); "t5": ids [B, Lt] -> last_hidden_state [B, Lt, d_model]."""
+        if self.text_cfg is None:
+            raise E.PdError("this engine has no text encoders: call configure_text first")
+        idx = {"clip_l": 0, "clip_g": 1, "t5": 2}[which]
+        if idx == 2:
+            if self.text_cfg.t5 is None:
+                raise E.PdError("this engine has no T5 encoder")
+            owner, ptr, mem = self._ids(ids, 0, "ids")
+            Bn, L = owner.shape
+            out, optr = self._out(mem, owner, (Bn, L, self.text_cfg.t5.d_model))
+            self.base._order_after_torch(mem)
+            self.base._check(self.base.lib.pd_sd3_text_encoder(self.base._h, 2, ptr, Bn, L, 0, mem, optr, None))
+            return out
+        c = (self.text_cfg.clip_l, self.text_cfg.clip_g)[idx]
+        owner, ptr, mem = self._ids(ids, c.max_positions, "ids")
+        Bn = owner.shape[0]
+        hid, hptr = self._out(mem, owner, (Bn, c.max_positions, c.hidden))
+        po, pptr = self._out(mem, owner, (Bn, c.proj_dim))
+        self.base._order_after_torch(mem)
+        self.base._check(self.base.lib.pd_sd3_text_encoder(self.base._h, idx, ptr, Bn, c.max_positions, int(clip_skip or 0), mem, hptr, pptr))
+        return hid, po
 
     def init_random_weights(self, seed: int = 1234) -> None:
         self.base.init_random_weights(seed)
@@ -244,7 +518,9 @@ class SD3Engine:
         return out
 
     def weights_missing(self) -> int:
-        return int(self.base.lib.pd_sd3_weights_missing(self.base._h))
+        """SD3 tensors still unloaded: both networks, plus the text encoders once configure_text registered them."""
+        n = int(self.base.lib.pd_sd3_weights_missing(self.base._h))
+        return n + (self.text_weights_missing() if self.text_cfg is not None else 0)
 
     # ------------------------------------------------------------------ calls
     def _args(self, latents, context, pooled, cond, pair, scale, timestep=None, rows=None, cn_pooled=None):
