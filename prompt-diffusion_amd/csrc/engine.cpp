@@ -343,7 +343,46 @@ int pd_engine::check_arena() {
     return 1;
 }
 
+int pd_engine::in_side_workspace(const char* what, size_t io_bytes, const std::function<int()>& sizing, const std::function<int()>& run) {
+    std::swap(arena, arena2);
+    Arena saved = arena;
+    arena.base = nullptr; arena.cap = 0; arena.top = 0; arena.peak = 0; arena.dry = true;
+    int r = sizing();
+    const size_t need = arena.peak + io_bytes + (64u << 20);
+    arena = saved;
+    arena.dry = false;
+    if (!r && need > arena.cap) {
+        hipStreamSynchronize(stream);
+        if (stream2) hipStreamSynchronize(stream2);
+        clear_graphs();   // captured step loops point into this workspace
+        if (arena.base) hipFree(arena.base);
+        arena.base = nullptr; arena.cap = 0;
+        void* p = nullptr;
+        if (hipMalloc(&p, need) != hipSuccess) { pd_set_error("%s workspace allocation of %.2f GiB failed", what, (double)need / (1 << 30)); r = 1; }
+        else { arena.base = reinterpret_cast<char*>(p); arena.cap = need; }
+    }
+    if (!r) {
+        arena.top = 0; arena.peak = 0;
+        r = run();
+        arena.top = 0;
+    }
+    std::swap(arena, arena2);
+    return r;
+}
+
 // ------------------------------------------------------------------------------------ weights
+int pd_engine::missing(WeightGroup g) const {
+    int n = 0;
+    for (auto& p : params) n += (p.group == g && !p.loaded) ? 1 : 0;
+    return n;
+}
+
+int pd_engine::require_loaded(WeightGroup g, const char* what) {
+    for (auto& p : params)
+        if (p.group == g && !p.loaded) { pd_set_error("%s%sweights not loaded: '%s' (and possibly more)", what, *what ? " " : "", p.name.c_str()); return 1; }
+    return 0;
+}
+
 static inline uint16_t host_f2bf(float f) {
     uint32_t u;
     memcpy(&u, &f, 4);

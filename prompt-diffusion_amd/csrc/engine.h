@@ -181,27 +181,22 @@ struct HedW {
     float *comb_w = nullptr, *comb_b = nullptr;
 };
 
-// CLIP text transformer
+// CLIP text transformer (text.cpp): the SD1.5 cond stage and SD3's CLIP-L / CLIP-G are this one stack
 struct TextLayerW {
     float *ln1_g = nullptr, *ln1_b = nullptr, *ln2_g = nullptr, *ln2_b = nullptr;
     WMat qkv, out, fc1, fc2;
 };
-struct TextW {
+struct ClipW {
     bool built = false;
-    WMat tok, pos;
-    std::vector<TextLayerW> layers;
-    float *fln_g = nullptr, *fln_b = nullptr;
-};
-
-// SD3 text encoders (sd3_text.cpp): a CLIP text transformer with its projection head (CLIP-L / CLIP-G) ...
-struct Sd3ClipW {
-    bool built = false;
-    pd_sd3_clip_config c{};
+    int vocab = 0, hidden = 0, ff = 0, heads = 0, positions = 0;
+    int proj_dim = 0;                      // rows of text_projection.weight; 0: no projection head (SD1.5)
+    int eos_token_id = 0;                  // pooled row (pd_sd3_clip_config)
+    Activation act = ACT_QUICK_GELU;       // of the MLP
     WMat tok, pos, proj;
-    std::vector<TextLayerW> layers;
+    std::vector<TextLayerW> layers;        // sized by the caller of build_clip, never resized again (Params point into it)
     float *fln_g = nullptr, *fln_b = nullptr;
 };
-// ... and the T5 encoder stack: no biases anywhere, RMSNorm weights only, wi = [wi_1 | wi_0] packed like a GEGLU matrix
+// SD3's T5 encoder stack (sd3_text.cpp): no biases anywhere, RMSNorm weights only, wi = [wi_1 | wi_0] packed like a GEGLU matrix
 struct T5LayerW {
     float *ln1 = nullptr, *ln2 = nullptr;
     WMat qkv, o, wi, wo;
@@ -240,6 +235,17 @@ struct Sd3NetW {
     int mod_rows = 0, norm_out_off = 0;
 };
 
+// Param::group: the weights a family of entry points needs loaded (its *_weights_missing count, its "not loaded" refusal)
+enum WeightGroup {
+    GROUP_SAMPLER = 0,       // UNet + ControlNet (needed to sample)
+    GROUP_VAE = 1,           // VAE decoder
+    GROUP_TEXT = 2,          // SD1.5 text transformer
+    GROUP_SD3 = 3,           // SD3 networks
+    GROUP_VAE_ENCODER = 4,
+    GROUP_HED = 5,
+    GROUP_SD3_TEXT = 6,      // SD3 text encoders
+};
+
 struct Param {
     std::string name;
     std::vector<int64_t> shape;
@@ -254,7 +260,7 @@ struct Param {
     bool conv = false;  // OIHW source
     char init = 'w';    // recipe class for pd_init_random_weights: w, b, g(amma), e(beta)
     bool loaded = false;
-    int group = 0;      // 0: UNet + ControlNet (needed to sample), 1: VAE decoder, 2: text transformer, 3: SD3 networks, 4: VAE encoder, 5: HED, 6: SD3 text encoders
+    WeightGroup group = GROUP_SAMPLER;
 };
 
 struct Act {
@@ -391,13 +397,15 @@ struct pd_engine {
     NetW unet, cnet;
     VaeW vae;
     VaeEncW vae_enc;
-    TextW text;
+    ClipW text;
     // captured step loops (option "graph"): key = everything a step's kernel arguments depend on
     struct GraphEntry { uint64_t key; hipGraph_t graph; hipGraphExec_t exec; };
     std::vector<GraphEntry> graphs;
     void clear_graphs();
     int run_steps_graph();
-    int reg_group = 0;
+    WeightGroup reg_group = GROUP_SAMPLER;   // group of the parameters being registered
+    int missing(WeightGroup g) const;        // parameters of g not loaded yet
+    int require_loaded(WeightGroup g, const char* what);   // non-zero, with "<what> weights not loaded: '<name>' (and possibly more)" set
     std::vector<void*> owned;  // device allocations (weights)
     bool alloc_failed = false; // a hipMalloc in dmalloc() failed (reported by build() / the bench hooks)
     int check_arena();         // non-zero (with the error set) when a workspace allocation overflowed
@@ -494,14 +502,27 @@ struct pd_engine {
     void build_vattn(const std::string& prefix, VaeAttnW& a, int C);
     void build_vae();
     void build_vae_encoder();
-    void build_text();
-    int text_forward(const int* ids_dev, int B, float* out_dev, int clip_skip);
     int vae_forward(const float* latents_dev, int B, int h, int w, float* out_dev);
     int vae_encoder_forward(const float* images_dev, int B, int H, int W, int what, const float* noise_dev, float* out_dev);
     int vae_attention(const VaeAttnW& a, const Act& x, Act& out);
-    // pd_vae_decode / pd_vae_encode: `sizing` (a dry pass of the forward) measures the workspace, which is the ControlNet
-    // context's (arena2, idle outside a sampling step) grown to that plus io_bytes if needed; then `run` enqueues for real
-    int vae_in_workspace(size_t io_bytes, const std::function<int()>& sizing, const std::function<int()>& run);
+    // Everything that runs outside a sampling step (first stage, HED, text encoders): `sizing` (a dry pass of the forward) measures the
+    // workspace, which is the ControlNet context's (arena2, idle outside a sampling step) grown to that plus io_bytes if needed; then `run`
+    // enqueues for real on the main stream.  `what` names the caller in the allocation-failure message.
+    int in_side_workspace(const char* what, size_t io_bytes, const std::function<int()>& sizing, const std::function<int()>& run);
+
+    // CLIP text stack (text.cpp).  build_clip registers one CLIPTextModel under `prefix` (its "text_model."); the caller has filled the
+    // dimensions and sized w.layers.  clip_blocks runs blocks [first, last) on the residual stream x, whose type the block's sums follow.
+    void build_clip(const std::string& prefix, ClipW& w);
+    void build_text();
+    int clip_embed(const ClipW& w, const int* ids_dev, Act& x);
+    // att (allocated here) = attention over q | k and V^T of ln, projected by `qkv` [3 * inner rows]; relbias / scale as in attention()
+    int self_attention(const WMat& qkv, const Act& ln, int inner, int heads, bool causal, const float* relbias, float scale, Act& att);
+    int clip_block(const TextLayerW& l, Act& x, int heads, Activation act);
+    int clip_blocks(const ClipW& w, int first, int last, Act& x);
+    int text_forward(const int* ids_dev, int B, float* out_dev, int clip_skip);
+    // token ids (int32, `mem` space) -> a workspace allocation; fp32 results back to the caller's `mem` space (both on the main stream)
+    int upload_ids(const int32_t* ids, size_t n, int mem, int** dev);
+    int download(float* dst, const float* src, size_t n, int mem);
 
     // HED edge detector (hed.cpp): registered by pd_hed_configure, runs in the same workspace as the first stage
     HedW hed;
@@ -535,19 +556,19 @@ struct pd_engine {
     int sd3_embed(Sd3NetW& net, const Sd3Io& io, bool controlnet, Act& hs, Act& c, Act& modbuf);
     int sd3_block(const Sd3BlockW& b, Act& x, Act& c, const Act& modbuf, const Act& qk, const Act& vt, const Act* pre_add = nullptr);
     int sd3_forward(const Sd3Io& io, float* v_out_dev, int control_index, float* control_out_dev);
-    // SD3 text encoders (sd3_text.cpp; pd_sd3_text_configure): CLIP-L, CLIP-G, T5.  Residual streams are fp32 in every mode.
-    Sd3ClipW sd3_clip[2];
+    // SD3 text encoders (pd_sd3_text_configure): CLIP-L, CLIP-G (text.cpp's stack) and T5 (sd3_text.cpp).  Residual streams are fp32 in every mode.
+    ClipW sd3_clip[2];
     Sd3T5W sd3_t5;
     int sd3_text_joint = 0;
     std::vector<int32_t> t5_bucket_host;   // bucket of every distance -(L - 1) .. L - 1 of the last T5 call (kept alive for the upload)
-    void build_sd3_clip(const std::string& prefix, Sd3ClipW& w);
     void build_sd3_t5(const std::string& prefix);
     // hidden (hidden_states[-(clip_skip + 2)], no final LayerNorm) -> columns [c_off, c_off + width) of hid [B][hid_rows][hid_ld] (columns past the
     // encoder's own are zeroed); pooled (text_embeds) -> pooled [B][pooled_ld]; either destination may be null
-    int sd3_clip_forward(Sd3ClipW& w, const int* ids_dev, int B, int clip_skip, float* hid, int hid_rows, int hid_ld, int c_off, int width,
+    int sd3_clip_forward(ClipW& w, const int* ids_dev, int B, int clip_skip, float* hid, int hid_rows, int hid_ld, int c_off, int width,
                          float* pooled, int pooled_ld);
     // last_hidden_state -> rows [row_off, row_off + Lt) of out [B][out_rows][d_model]
     int sd3_t5_forward(const int* ids_dev, int B, int Lt, float* out, int out_rows, int row_off);
+    int t5_block(const T5LayerW& l, Act& x, const float* relbias);
     int rmsnorm(const Act& x, void* y, int y_dt, const float* w, float eps, int y_sample_rows = 0, int y_row_off = 0, int y_ld = 0);
     int opt_slab_gn = 1;             // split-K conv1 -> single-kernel norm2 without a finalize pass (SlabDefer; option "slab_gn")
     int opt_sd3_fp8 = 0;       // 0 off, 1: the AdaLN-fed projections, 2: also the feed-forward-out projections (e4m3 GELU output under a norm bound)  // SD3 path: QKV and feed-forward-in projections in PREC_FP8 (e4m3 operands, per-row scales)

@@ -10,13 +10,12 @@ namespace {
 const char* const kStage[5] = {"One", "Two", "Thr", "Fou", "Fiv"};
 const int kConvs[5] = {2, 2, 3, 3, 3};
 const int kWidth[5] = {64, 128, 256, 512, 512};
-constexpr int kHedGroup = 5;
 }  // namespace
 
 // Registered in the order Network.__init__ creates the modules (= state_dict order): netVggOne .. netVggFiv, netScoreOne .. netScoreFiv,
 // netCombine; "hed." + Network's own names (the checkpoint's "module" prefix is "net", :69)
 void pd_engine::build_hed() {
-    reg_group = kHedGroup;
+    reg_group = GROUP_HED;
     HedW& v = hed;
     int ci = 0, cin = 3;
     for (int s = 0; s < 5; ++s) {
@@ -38,7 +37,7 @@ void pd_engine::build_hed() {
     params.back().shape = {1, 5, 1, 1};
     reg_vec("hed.netCombine.0.bias", 1, &v.comb_b, 'b');
     v.built = true;
-    reg_group = 0;
+    reg_group = GROUP_SAMPLER;
 }
 
 extern "C" int pd_hed_configure(pd_engine* e) {
@@ -52,12 +51,7 @@ extern "C" int pd_hed_configure(pd_engine* e) {
     return 0;
 }
 
-extern "C" int pd_hed_weights_missing(pd_engine* e) {
-    int n = 0;
-    if (e)
-        for (auto& p : e->params) n += (p.group == kHedGroup && !p.loaded) ? 1 : 0;
-    return n;
-}
+extern "C" int pd_hed_weights_missing(pd_engine* e) { return e ? e->missing(GROUP_HED) : 0; }
 
 // Network.forward on [B, 3, H, W] RGB in [0, 1] (fp32, device) -> out [B, 1, H, W] (PD_HED_EDGE) or [B, 5, H, W] (PD_HED_SIDES)
 int pd_engine::hed_forward(const float* images_dev, int B, int H, int W, int what, float* out_dev) {
@@ -112,8 +106,7 @@ int pd_engine::hed_forward(const float* images_dev, int B, int H, int W, int wha
 extern "C" int pd_hed_detect(pd_engine* e, const float* images, int32_t B, int32_t H, int32_t W, int32_t mem, int32_t what, float* out) {
     if (!e || !images || !out || B < 1 || H < 1 || W < 1) { pd_set_error("bad argument"); return 1; }
     if (!e->hed.built) { pd_set_error("this engine has no HED edge detector (pd_hed_configure)"); return 1; }
-    for (auto& p : e->params)
-        if (p.group == kHedGroup && !p.loaded) { pd_set_error("HED weights not loaded: '%s' (and possibly more)", p.name.c_str()); return 1; }
+    PD_TRY(e->require_loaded(GROUP_HED, "HED"));
     if (e->ses.active) { pd_set_error("pd_hed_detect: end the sampling session first"); return 1; }
     if (H % 16 || W % 16) {
         pd_set_error("pd_hed_detect: H and W must be multiples of 16, the four 2x2 max-pools (got %d x %d; resize_image gives multiples of 64)", H, W);
@@ -126,7 +119,7 @@ extern "C" int pd_hed_detect(pd_engine* e, const float* images, int32_t B, int32
     if ((long long)B * H * W * 5 >= (1ll << 31)) { pd_set_error("pd_hed_detect: B * H * W too large (%d x %d x %d); split the batch", B, H, W); return 1; }
     HIP_OK(hipSetDevice(e->device));
     const size_t n_in = (size_t)B * 3 * H * W, n_out = (size_t)B * (what == PD_HED_SIDES ? 5 : 1) * H * W;
-    return e->vae_in_workspace((n_in + n_out) * sizeof(float), [&] { return e->hed_forward(nullptr, B, H, W, what, nullptr); }, [&] {
+    return e->in_side_workspace("HED", (n_in + n_out) * sizeof(float), [&] { return e->hed_forward(nullptr, B, H, W, what, nullptr); }, [&] {
         int r = 0;
         float* din = reinterpret_cast<float*>(e->arena.alloc(n_in * sizeof(float)));
         float* dout = reinterpret_cast<float*>(e->arena.alloc(n_out * sizeof(float)));

@@ -318,7 +318,7 @@ int launch_softmax_rows(const float* in, void* out, int out_dt, int rows, int n,
 int launch_embed_tokens(const int* ids, const void* tok, int tok_ld, const void* pos, int pos_ld, int dt, void* out, int out_dt,
                         int B, int L, int C, int vocab, hipStream_t s);
 int launch_nhwc_to_nchw(const void* in, int in_dt, float* out, int B, int C, int H, int W, int Cpad, float scale, hipStream_t s);
-// sd3_text.hip: the small kernels of the SD3 text encoders (sd3_text.cpp)
+// sd3_text_kernels.hip: the small kernels of the SD3 text encoders (T5: sd3_text.cpp; the CLIP pooling and the joint write: text.cpp)
 // out[row][:] = tok[clamp(ids[row])][:] (table rows [vocab][tok_ld] in dt) -> fp32 [rows][C]: T5's token embedding (no positions)
 int launch_embed_rows(const int* ids, const void* tok, int tok_ld, int dt, float* out, long long rows, int C, int vocab, hipStream_t s);
 // T5LayerNorm: y = w * x * rsqrt(mean(x^2) + eps), statistics in fp32, x fp32 [rows][C]; row r of y lands at

@@ -495,20 +495,15 @@ extern "C" int pd_sd3_configure(pd_engine* e, const pd_sd3_config* c) {
     HIP_OK(hipSetDevice(e->device));
     e->sd3 = *c;
     e->alloc_failed = false;
-    e->reg_group = 3;
+    e->reg_group = GROUP_SD3;
     e->build_sd3_net("transformer.", e->sd3_tr, false);
     if (c->cn_layers > 0) e->build_sd3_net("controlnet.", e->sd3_cn, true);
-    e->reg_group = 0;
+    e->reg_group = GROUP_SAMPLER;
     if (e->alloc_failed) { pd_set_error("pd_sd3_configure: weight allocation failed"); return 1; }
     return 0;
 }
 
-extern "C" int pd_sd3_weights_missing(pd_engine* e) {
-    int n = 0;
-    if (e)
-        for (auto& p : e->params) n += (p.group == 3 && !p.loaded) ? 1 : 0;
-    return n;
-}
+extern "C" int pd_sd3_weights_missing(pd_engine* e) { return e ? e->missing(GROUP_SD3) : 0; }
 
 namespace {
 // One SD3 call: staged inputs in the workspace, a dry run to size it, the evaluation(s), read-back.
@@ -522,8 +517,7 @@ int sd3_check(pd_engine* e, const pd_sd3_args* a, bool need_cond) {
     if (!e || !a) { pd_set_error("bad argument"); return 1; }
     if (!e->sd3_tr.built) { pd_set_error("SD3 path not configured (pd_sd3_configure)"); return 1; }
     if (e->ses.active) { pd_set_error("pd_sd3: end the sampling session first"); return 1; }
-    for (auto& p : e->params)
-        if (p.group == 3 && !p.loaded) { pd_set_error("SD3 weights not loaded: '%s' (and possibly more)", p.name.c_str()); return 1; }
+    PD_TRY(e->require_loaded(GROUP_SD3, "SD3"));
     const int ps = e->sd3.patch_size;
     if (a->batch > 32) { pd_set_error("pd_sd3: batch %d exceeds 32 per call (the guided loop doubles it; shard larger batches)", a->batch); return 1; }
     if (a->batch < 1 || a->height < ps || a->width < ps || a->height % ps || a->width % ps || a->context_len < 1) {
@@ -685,7 +679,7 @@ extern "C" int pd_sd3_down_proj(pd_engine* e, const float* pair, int32_t B, int3
     if (!e || !pair || !out || B < 1 || H < 1 || W < 1) { pd_set_error("pd_sd3_down_proj: bad argument"); return 1; }
     if (!e->sd3_cn.built) { pd_set_error("pd_sd3_down_proj: this engine has no SD3 ControlNet"); return 1; }
     for (auto& p : e->params)
-        if (p.group == 3 && !p.loaded && p.name.find("down_proj") != std::string::npos) { pd_set_error("weights not loaded: '%s'", p.name.c_str()); return 1; }
+        if (p.group == GROUP_SD3 && !p.loaded && p.name.find("down_proj") != std::string::npos) { pd_set_error("weights not loaded: '%s'", p.name.c_str()); return 1; }
     HIP_OK(hipSetDevice(e->device));
     const ConvW& c = e->sd3_cn.down_proj;
     const size_t n_in = (size_t)B * 6 * H * W, n_out = (size_t)B * 3 * H * W, px = (size_t)B * H * W;

@@ -1,61 +1,15 @@
 // pdengine: the SD3 text encoders -- what the reference's encode_prompt runs around its tokenizers.
-//   _get_clip_prompt_embeds   promptdiffusioncontrolnetpipeline_sd3.py:295-348  (hidden_states[-(clip_skip + 2)] and text_embeds of
-//                                                                                CLIPTextModelWithProjection, twice: CLIP-L, CLIP-G)
+//   _get_clip_prompt_embeds   promptdiffusioncontrolnetpipeline_sd3.py:295-348  (the CLIP stack of text.cpp, twice: CLIP-L, CLIP-G)
 //   _get_t5_prompt_embeds     promptdiffusioncontrolnetpipeline_sd3.py:238-292  (T5EncoderModel(ids)[0], no attention mask)
 //   encode_prompt             promptdiffusioncontrolnetpipeline_sd3.py:457-471  (cat / pad / cat: written in place here, no host concat)
-// The CLIP stacks are text.cpp's block with an fp32 residual stream and a per-encoder MLP activation; one pass serves both outputs (the
-// hidden state is captured at the skip layer, the stack carries on to the final LayerNorm, EOS row and text_projection).  T5: token
-// embedding without positions, pre-RMSNorm blocks, softmax(Q K^T + bias) V with scale 1 and the Toeplitz bias rows of attention.hip's
-// BIAS instantiation (block 0's table, shared by all blocks), feed-forward wo(gelu_new(wi_0 x) * wi_1 x) in one gated GEMM epilogue.
-#include <algorithm>
-
+// T5: token embedding without positions, pre-RMSNorm blocks, softmax(Q K^T + bias) V with scale 1 (text.cpp's self_attention with the
+// Toeplitz bias rows of attention.hip's BIAS instantiation: block 0's table, shared by all blocks), feed-forward
+// wo(gelu_new(wi_0 x) * wi_1 x) in one gated GEMM epilogue.
 #include "engine.h"
 
 namespace {
-constexpr int kTextGroup = 6;
 constexpr int kClipLen = 77;
-inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 }  // namespace
-
-void pd_engine::build_sd3_clip(const std::string& prefix, Sd3ClipW& t) {
-    const pd_sd3_clip_config& c = t.c;
-    const std::string P = prefix + "text_model.";
-    const int C = c.hidden, F = c.ff, L = c.max_positions;
-    make_mat(t.tok, c.vocab, C, 1, C, false);
-    reg_mat(P + "embeddings.token_embedding.weight", {c.vocab, C}, &t.tok, 0, false);
-    make_mat(t.pos, L, C, 1, C, false);
-    reg_mat(P + "embeddings.position_embedding.weight", {L, C}, &t.pos, 0, false);
-    t.layers.resize(c.layers);   // never resized again (Params point into it)
-    for (int i = 0; i < c.layers; ++i) {
-        TextLayerW& l = t.layers[i];
-        const std::string Lp = P + "encoder.layers." + std::to_string(i) + ".";
-        make_mat(l.qkv, 3 * C, C, 1, C, true);   // rows [0,C) q, [C,2C) k, [2C,3C) v -- the attention kernel's layout
-        const char* nm[3] = {"k_proj", "v_proj", "q_proj"};   // module order of the checkpoint
-        const int off[3] = {C, 2 * C, 0};
-        for (int j = 0; j < 3; ++j) {
-            reg_mat(Lp + "self_attn." + nm[j] + ".weight", {C, C}, &l.qkv, off[j], false);
-            reg_bias(Lp + "self_attn." + nm[j] + ".bias", &l.qkv, off[j], C);
-        }
-        make_mat(l.out, C, C, 1, C, true);
-        reg_mat(Lp + "self_attn.out_proj.weight", {C, C}, &l.out, 0, false);
-        reg_bias(Lp + "self_attn.out_proj.bias", &l.out, 0, C);
-        reg_vec(Lp + "layer_norm1.weight", C, &l.ln1_g, 'g');
-        reg_vec(Lp + "layer_norm1.bias", C, &l.ln1_b, 'e');
-        make_mat(l.fc1, F, C, 1, C, true);
-        reg_mat(Lp + "mlp.fc1.weight", {F, C}, &l.fc1, 0, false);
-        reg_bias(Lp + "mlp.fc1.bias", &l.fc1, 0, F);
-        make_mat(l.fc2, C, F, 1, F, true);
-        reg_mat(Lp + "mlp.fc2.weight", {C, F}, &l.fc2, 0, false);
-        reg_bias(Lp + "mlp.fc2.bias", &l.fc2, 0, C);
-        reg_vec(Lp + "layer_norm2.weight", C, &l.ln2_g, 'g');
-        reg_vec(Lp + "layer_norm2.bias", C, &l.ln2_b, 'e');
-    }
-    reg_vec(P + "final_layer_norm.weight", C, &t.fln_g, 'g');
-    reg_vec(P + "final_layer_norm.bias", C, &t.fln_b, 'e');
-    make_mat(t.proj, c.proj_dim, C, 1, C, false);
-    reg_mat(prefix + "text_projection.weight", {c.proj_dim, C}, &t.proj, 0, false);
-    t.built = true;
-}
 
 void pd_engine::build_sd3_t5(const std::string& prefix) {
     Sd3T5W& t = sd3_t5;
@@ -117,23 +71,28 @@ extern "C" int pd_sd3_text_configure(pd_engine* e, const pd_sd3_text_config* c) 
     if (c->joint_dim < clip_width || c->joint_dim % 4) { pd_set_error("pd_sd3_text_configure: joint_dim %d must be a multiple of 4 and hold both CLIP hidden states (%d)", c->joint_dim, clip_width); return 1; }
     HIP_OK(hipSetDevice(e->device));
     e->alloc_failed = false;
-    e->reg_group = kTextGroup;
+    e->reg_group = GROUP_SD3_TEXT;
     e->sd3_text_joint = c->joint_dim;
-    const char* prefix[2] = {"text_encoder.", "text_encoder_2."};
-    for (int i = 0; i < 2; ++i)
-        if (cl[i]->layers > 0) { e->sd3_clip[i].c = *cl[i]; e->build_sd3_clip(prefix[i], e->sd3_clip[i]); }
+    const std::string prefix[2] = {"text_encoder.", "text_encoder_2."};
+    for (int i = 0; i < 2; ++i) {
+        const pd_sd3_clip_config& k = *cl[i];
+        if (k.layers == 0) continue;
+        ClipW& w = e->sd3_clip[i];
+        w.vocab = k.vocab; w.hidden = k.hidden; w.ff = k.ff; w.heads = k.heads; w.positions = k.max_positions;
+        w.proj_dim = k.proj_dim; w.eos_token_id = k.eos_token_id;
+        w.act = k.act == PD_CLIP_ACT_GELU ? ACT_ERF_GELU : ACT_QUICK_GELU;
+        w.layers.resize(k.layers);
+        e->build_clip(prefix[i] + "text_model.", w);
+        e->make_mat(w.proj, w.proj_dim, w.hidden, 1, w.hidden, false);
+        e->reg_mat(prefix[i] + "text_projection.weight", {w.proj_dim, w.hidden}, &w.proj, 0, false);
+    }
     if (t.layers > 0) { e->sd3_t5.c = t; e->build_sd3_t5("text_encoder_3."); }
-    e->reg_group = 0;
+    e->reg_group = GROUP_SAMPLER;
     if (e->alloc_failed) { pd_set_error("pd_sd3_text_configure: weight allocation failed"); return 1; }
     return 0;
 }
 
-extern "C" int pd_sd3_text_weights_missing(pd_engine* e) {
-    int n = 0;
-    if (e)
-        for (auto& p : e->params) n += (p.group == kTextGroup && !p.loaded) ? 1 : 0;
-    return n;
-}
+extern "C" int pd_sd3_text_weights_missing(pd_engine* e) { return e ? e->missing(GROUP_SD3_TEXT) : 0; }
 
 int pd_engine::rmsnorm(const Act& x, void* y, int y_dt, const float* w, float eps, int y_sample_rows, int y_row_off, int y_ld) {
     if (arena.dry) return 0;
@@ -147,89 +106,29 @@ int pd_engine::rmsnorm(const Act& x, void* y, int y_dt, const float* w, float ep
     return 0;
 }
 
-int pd_engine::sd3_clip_forward(Sd3ClipW& t, const int* ids_dev, int B, int clip_skip, float* hid, int hid_rows, int hid_ld, int c_off, int width,
-                                float* pooled, int pooled_ld) {
-    const pd_sd3_clip_config& c = t.c;
-    const int C = c.hidden, F = c.ff, L = c.max_positions, H = c.heads, n = c.layers;
-    const Activation act = c.act == PD_CLIP_ACT_GELU ? ACT_ERF_GELU : ACT_QUICK_GELU;
-    const size_t eb = dt_size(T);
-    const size_t mk0 = arena.mark();
-    Act x = new_act(B, L, 1, C, DT_F32);   // the residual stream: fp32 in every mode
-    if (!arena.dry) {
-        PD_TRY(check_arena());
-        ++launches;
-        if (launch_embed_tokens(ids_dev, t.tok.w, t.tok.Kpad, t.pos.w, t.pos.Kpad, T, x.p, DT_F32, B, L, C, c.vocab, stream)) {
-            pd_set_error("CLIP embedding launch failed");
-            return 1;
-        }
-    }
-    const int lpad = round_up(L, 8);
-    const int capture = n - 1 - clip_skip;   // blocks run before hidden_states[-(clip_skip + 2)] is complete
-    auto write_hidden = [&]() -> int {
-        if (!hid || arena.dry) return 0;
-        ++launches;
-        if (launch_joint_write(reinterpret_cast<const float*>(x.p), hid, B, L, C, width, hid_rows, hid_ld, c_off, stream)) {
-            pd_set_error("CLIP hidden-state write launch failed");
-            return 1;
-        }
-        return 0;
-    };
-    if (capture == 0) PD_TRY(write_hidden());
-    const int n_run = pooled ? n : capture;   // the pooled output needs the whole stack
-    for (int li = 0; li < n_run; ++li) {
-        TextLayerW& l = t.layers[li];
-        const size_t mk = arena.mark();
-        Act ln = new_act(B, L, 1, C, T);
-        PD_TRY(layernorm(x, ln, l.ln1_g, l.ln1_b));
-        Act qk = new_act(B, L, 1, 2 * C, T);
-        Act vt = new_act(B, C, 1, lpad, T);
-        if (!arena.dry && lpad != L) HIP_OK(hipMemsetAsync(vt.p, 0, vt.bytes(), stream));   // pad keys of V^T must read as 0
-        PD_TRY(gemm(l.qkv, ln, qk, {.VT = vt.p, .vt_begin = 2 * C, .vt_ld = lpad}));
-        Act att = new_act(B, L, 1, C, T);
-        PD_TRY(attention(qk.p, 2 * C, reinterpret_cast<char*>(qk.p) + (size_t)C * eb, 2 * C, vt.p, lpad, att.p, C, B, L, L, C, H, /*causal=*/true));
-        Act h1 = new_act(B, L, 1, C, DT_F32);
-        PD_TRY(gemm(l.out, att, h1, {.R = &x}));
-        PD_TRY(layernorm(h1, ln, l.ln2_g, l.ln2_b));
-        Act f = new_act(B, L, 1, F, T);
-        PD_TRY(gemm(l.fc1, ln, f, {.act = act}));
-        Act h2 = new_act(B, L, 1, C, DT_F32);
-        PD_TRY(gemm(l.fc2, f, h2, {.R = &h1}));
-        if (!arena.dry) HIP_OK(hipMemcpyAsync(x.p, h2.p, x.bytes(), hipMemcpyDeviceToDevice, stream));
-        arena.release(mk);
-        if (li + 1 == capture) PD_TRY(write_hidden());
-    }
-    if (pooled) {
-        // last_hidden_state[b, eos(b)] @ text_projection^T: LayerNorm is per row, so the EOS rows are gathered first
-        Act rows = new_act(B, 1, 1, C, DT_F32), lnr = new_act(B, 1, 1, C, DT_F32);
-        if (!arena.dry) {
-            PD_TRY(check_arena());
-            ++launches;
-            if (launch_eos_gather(ids_dev, reinterpret_cast<const float*>(x.p), reinterpret_cast<float*>(rows.p), B, L, C, c.eos_token_id, stream)) {
-                pd_set_error("CLIP EOS gather launch failed");
-                return 1;
-            }
-        }
-        PD_TRY(layernorm(rows, lnr, t.fln_g, t.fln_b));
-        if (!arena.dry) {
-            for (int b0 = 0; b0 < B; b0 += 4) {   // launch_gemv streams the weights once per <= 4 rows
-                ++launches;
-                if (launch_gemv(reinterpret_cast<const float*>(lnr.p) + (size_t)b0 * C, C, t.proj.w, T, t.proj.Kpad, nullptr, pooled + (size_t)b0 * pooled_ld,
-                                pooled_ld, std::min(4, B - b0), c.proj_dim, C, 0, stream)) {
-                    pd_set_error("CLIP text_projection launch failed");
-                    return 1;
-                }
-            }
-        }
-    }
-    arena.release(mk0);
+int pd_engine::t5_block(const T5LayerW& l, Act& x, const float* relbias) {
+    const pd_sd3_t5_config& c = sd3_t5.c;
+    const int B = x.B, L = x.H, D = x.C;
+    const size_t mk = arena.mark();
+    Act ln = new_act(B, L, 1, D, T), att;
+    PD_TRY(rmsnorm(x, ln.p, T, l.ln1, c.eps));
+    PD_TRY(self_attention(l.qkv, ln, c.heads * c.d_kv, c.heads, /*causal=*/false, relbias, /*scale=*/1.0f, att));
+    Act h1 = new_act(B, L, 1, D, DT_F32);
+    PD_TRY(gemm(l.o, att, h1, {.R = &x}));
+    PD_TRY(rmsnorm(h1, ln.p, T, l.ln2, c.eps));
+    Act f = new_act(B, L, 1, c.d_ff, T);
+    PD_TRY(gemm(l.wi, ln, f, {.act = ACT_GATED_TANH_GELU}));
+    Act h2 = new_act(B, L, 1, D, DT_F32);
+    PD_TRY(gemm(l.wo, f, h2, {.R = &h1}));
+    if (!arena.dry) HIP_OK(hipMemcpyAsync(x.p, h2.p, x.bytes(), hipMemcpyDeviceToDevice, stream));
+    arena.release(mk);
     return 0;
 }
 
 int pd_engine::sd3_t5_forward(const int* ids_dev, int B, int Lt, float* out, int out_rows, int row_off) {
     Sd3T5W& t = sd3_t5;
     const pd_sd3_t5_config& c = t.c;
-    const int D = c.d_model, I = c.heads * c.d_kv, F = c.d_ff, H = c.heads, L = Lt;
-    const size_t eb = dt_size(T);
+    const int D = c.d_model, H = c.heads, L = Lt;
     const size_t mk0 = arena.mark();
     // the bias rows of this call: relbias[h][key - query + L - 1] (130 KB at XXL, L = 256), instead of [H, L, L] re-read by every block
     const int nrel = 2 * L - 1;
@@ -249,29 +148,7 @@ int pd_engine::sd3_t5_forward(const int* ids_dev, int B, int Lt, float* out, int
             return 1;
         }
     }
-    const int lpad = round_up(L, 8);
-    for (size_t li = 0; li < t.layers.size(); ++li) {
-        T5LayerW& l = t.layers[li];
-        const size_t mk = arena.mark();
-        Act ln = new_act(B, L, 1, D, T);
-        PD_TRY(rmsnorm(x, ln.p, T, l.ln1, c.eps));
-        Act qk = new_act(B, L, 1, 2 * I, T);
-        Act vt = new_act(B, I, 1, lpad, T);
-        if (!arena.dry && lpad != L) HIP_OK(hipMemsetAsync(vt.p, 0, vt.bytes(), stream));   // pad keys of V^T must read as 0
-        PD_TRY(gemm(l.qkv, ln, qk, {.VT = vt.p, .vt_begin = 2 * I, .vt_ld = lpad}));
-        Act att = new_act(B, L, 1, I, T);
-        PD_TRY(attention(qk.p, 2 * I, reinterpret_cast<char*>(qk.p) + (size_t)I * eb, 2 * I, vt.p, lpad, att.p, I, B, L, L, I, H, /*causal=*/false, 0, 0, 0,
-                         relbias, /*scale=*/1.0f));
-        Act h1 = new_act(B, L, 1, D, DT_F32);
-        PD_TRY(gemm(l.o, att, h1, {.R = &x}));
-        PD_TRY(rmsnorm(h1, ln.p, T, l.ln2, c.eps));
-        Act f = new_act(B, L, 1, F, T);
-        PD_TRY(gemm(l.wi, ln, f, {.act = ACT_GATED_TANH_GELU}));
-        Act h2 = new_act(B, L, 1, D, DT_F32);
-        PD_TRY(gemm(l.wo, f, h2, {.R = &h1}));
-        if (!arena.dry) HIP_OK(hipMemcpyAsync(x.p, h2.p, x.bytes(), hipMemcpyDeviceToDevice, stream));
-        arena.release(mk);
-    }
+    for (const T5LayerW& l : t.layers) PD_TRY(t5_block(l, x, relbias));
     PD_TRY(rmsnorm(x, out, DT_F32, t.fln, c.eps, out_rows, row_off, D));
     arena.release(mk0);
     return 0;
@@ -280,27 +157,7 @@ int pd_engine::sd3_t5_forward(const int* ids_dev, int B, int Lt, float* out, int
 namespace {
 int text_ready(pd_engine* e, const char* who) {
     if (e->ses.active) { pd_set_error("%s: end the sampling session first", who); return 1; }
-    for (auto& p : e->params)
-        if (p.group == kTextGroup && !p.loaded) { pd_set_error("SD3 text-encoder weights not loaded: '%s' (and possibly more)", p.name.c_str()); return 1; }
-    return 0;
-}
-// ids to the workspace (int32, `mem` space) -> device pointer
-int upload_ids(pd_engine* e, const int32_t* ids, size_t n, int mem, int** dev) {
-    *dev = reinterpret_cast<int*>(e->arena.alloc(n * sizeof(int)));
-    if (e->arena.dry) return 0;
-    PD_TRY(e->check_arena());
-    if (hipMemcpyAsync(*dev, ids, n * sizeof(int), mem == PD_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, e->stream) != hipSuccess) {
-        pd_set_error("token upload failed");
-        return 1;
-    }
-    return 0;
-}
-int download(pd_engine* e, float* dst, const float* src, size_t n, int mem) {
-    if (hipMemcpyAsync(dst, src, n * sizeof(float), mem == PD_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, e->stream) != hipSuccess) {
-        pd_set_error("embedding read-back failed");
-        return 1;
-    }
-    return 0;
+    return e->require_loaded(GROUP_SD3_TEXT, "SD3 text-encoder");
 }
 }  // namespace
 
@@ -316,17 +173,17 @@ extern "C" int pd_sd3_encode_prompt(pd_engine* e, const pd_sd3_text_args* a, flo
         return 1;
     }
     for (int i = 0; i < 2; ++i)
-        if (a->clip_skip > e->sd3_clip[i].c.layers - 1) { pd_set_error("pd_sd3_encode_prompt: clip_skip %d out of range [0, %d]", a->clip_skip, e->sd3_clip[i].c.layers - 1); return 1; }
+        if (a->clip_skip > (int)e->sd3_clip[i].layers.size() - 1) { pd_set_error("pd_sd3_encode_prompt: clip_skip %d out of range [0, %d]", a->clip_skip, (int)e->sd3_clip[i].layers.size() - 1); return 1; }
     PD_TRY(text_ready(e, "pd_sd3_encode_prompt"));
     HIP_OK(hipSetDevice(e->device));
     const int B = a->batch, Lt = t5 ? a->t5_len : 0, J = e->sd3_text_joint, rows = kClipLen + Lt;
-    const int Cl = e->sd3_clip[0].c.hidden, Pl = e->sd3_clip[0].c.proj_dim, Pg = e->sd3_clip[1].c.proj_dim;
+    const int Cl = e->sd3_clip[0].hidden, Pl = e->sd3_clip[0].proj_dim, Pg = e->sd3_clip[1].proj_dim;
     const size_t n_pe = (size_t)B * rows * J, n_po = (size_t)B * (Pl + Pg), n_ids = (size_t)B * (2 * kClipLen + Lt);
     auto body = [&](bool dry) -> int {
         int *il = nullptr, *ig = nullptr, *it = nullptr;
-        PD_TRY(upload_ids(e, a->ids_clip_l, (size_t)B * kClipLen, a->mem, &il));
-        PD_TRY(upload_ids(e, a->ids_clip_g, (size_t)B * kClipLen, a->mem, &ig));
-        if (t5) PD_TRY(upload_ids(e, a->ids_t5, (size_t)B * Lt, a->mem, &it));
+        PD_TRY(e->upload_ids(a->ids_clip_l, (size_t)B * kClipLen, a->mem, &il));
+        PD_TRY(e->upload_ids(a->ids_clip_g, (size_t)B * kClipLen, a->mem, &ig));
+        if (t5) PD_TRY(e->upload_ids(a->ids_t5, (size_t)B * Lt, a->mem, &it));
         float* dpe = reinterpret_cast<float*>(e->arena.alloc(n_pe * sizeof(float)));
         float* dpo = reinterpret_cast<float*>(e->arena.alloc(n_po * sizeof(float)));
         // rows 0..76: CLIP-L | CLIP-G | zeros up to joint_dim (the second write carries the pad); rows 77..: T5
@@ -334,12 +191,12 @@ extern "C" int pd_sd3_encode_prompt(pd_engine* e, const pd_sd3_text_args* a, flo
         PD_TRY(e->sd3_clip_forward(e->sd3_clip[1], ig, B, a->clip_skip, dpe, rows, J, Cl, J - Cl, dpo + Pl, Pl + Pg));
         if (t5) PD_TRY(e->sd3_t5_forward(it, B, Lt, dpe, rows, kClipLen));
         if (dry) return 0;
-        PD_TRY(download(e, prompt_embeds, dpe, n_pe, a->mem));
-        PD_TRY(download(e, pooled, dpo, n_po, a->mem));
+        PD_TRY(e->download(prompt_embeds, dpe, n_pe, a->mem));
+        PD_TRY(e->download(pooled, dpo, n_po, a->mem));
         HIP_OK(hipStreamSynchronize(e->stream));
         return 0;
     };
-    return e->vae_in_workspace((n_pe + n_po) * sizeof(float) + n_ids * sizeof(int) + 4096, [&] { return body(true); }, [&] { return body(false); });
+    return e->in_side_workspace("SD3 text", (n_pe + n_po) * sizeof(float) + n_ids * sizeof(int) + 4096, [&] { return body(true); }, [&] { return body(false); });
 }
 
 extern "C" int pd_sd3_text_encoder(pd_engine* e, int32_t which, const int32_t* ids, int32_t B, int32_t len, int32_t clip_skip, int32_t mem,
@@ -348,23 +205,23 @@ extern "C" int pd_sd3_text_encoder(pd_engine* e, int32_t which, const int32_t* i
     const bool t5 = which == 2;
     if (t5 ? !e->sd3_t5.built : !e->sd3_clip[which].built) { pd_set_error("pd_sd3_text_encoder: encoder %d is not configured (pd_sd3_text_configure)", which); return 1; }
     if (t5 && (pooled || !hidden || len < 1 || len > 512)) { pd_set_error("pd_sd3_text_encoder: T5 has no pooled output and takes 1 to 512 tokens"); return 1; }
-    if (!t5 && clip_skip > e->sd3_clip[which].c.layers - 1) { pd_set_error("pd_sd3_text_encoder: clip_skip %d out of range [0, %d]", clip_skip, e->sd3_clip[which].c.layers - 1); return 1; }
+    if (!t5 && clip_skip > (int)e->sd3_clip[which].layers.size() - 1) { pd_set_error("pd_sd3_text_encoder: clip_skip %d out of range [0, %d]", clip_skip, (int)e->sd3_clip[which].layers.size() - 1); return 1; }
     PD_TRY(text_ready(e, "pd_sd3_text_encoder"));
     HIP_OK(hipSetDevice(e->device));
-    const int L = t5 ? len : kClipLen, C = t5 ? e->sd3_t5.c.d_model : e->sd3_clip[which].c.hidden, Pd = t5 ? 0 : e->sd3_clip[which].c.proj_dim;
+    const int L = t5 ? len : kClipLen, C = t5 ? e->sd3_t5.c.d_model : e->sd3_clip[which].hidden, Pd = t5 ? 0 : e->sd3_clip[which].proj_dim;
     const size_t n_h = hidden ? (size_t)B * L * C : 0, n_p = pooled ? (size_t)B * Pd : 0;
     auto body = [&](bool dry) -> int {
         int* di = nullptr;
-        PD_TRY(upload_ids(e, ids, (size_t)B * L, mem, &di));
+        PD_TRY(e->upload_ids(ids, (size_t)B * L, mem, &di));
         float* dh = hidden ? reinterpret_cast<float*>(e->arena.alloc(n_h * sizeof(float))) : nullptr;
         float* dp = pooled ? reinterpret_cast<float*>(e->arena.alloc(n_p * sizeof(float))) : nullptr;
         if (t5) PD_TRY(e->sd3_t5_forward(di, B, L, dh, L, 0));
         else PD_TRY(e->sd3_clip_forward(e->sd3_clip[which], di, B, clip_skip, dh, L, C, 0, C, dp, Pd));
         if (dry) return 0;
-        if (hidden) PD_TRY(download(e, hidden, dh, n_h, mem));
-        if (pooled) PD_TRY(download(e, pooled, dp, n_p, mem));
+        if (hidden) PD_TRY(e->download(hidden, dh, n_h, mem));
+        if (pooled) PD_TRY(e->download(pooled, dp, n_p, mem));
         HIP_OK(hipStreamSynchronize(e->stream));
         return 0;
     };
-    return e->vae_in_workspace((n_h + n_p) * sizeof(float) + (size_t)B * L * sizeof(int) + 4096, [&] { return body(true); }, [&] { return body(false); });
+    return e->in_side_workspace("SD3 text", (n_h + n_p) * sizeof(float) + (size_t)B * L * sizeof(int) + 4096, [&] { return body(true); }, [&] { return body(false); });
 }

@@ -1,4 +1,4 @@
-// Small kernels of the SD3 text encoders (sd3_text.cpp): T5's token embedding, row RMSNorm, the Toeplitz rows of its relative-position
+// Small kernels of the SD3 text encoders (sd3_text.cpp, and text.cpp for the two CLIP ones): T5's token embedding, row RMSNorm, the Toeplitz rows of its relative-position
 // bias, the EOS-row gather of the CLIP pooling and the strided write into the joint prompt_embeds layout.  All HBM-trivial next to the
 // encoders' GEMMs; the contractions and the attention are the shared kernels (gemm.hip, attention.hip).
 #include "pd_common.h"

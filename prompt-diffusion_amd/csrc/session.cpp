@@ -398,9 +398,7 @@ static int check_args(pd_engine* e, const pd_sample_args* a) {
     const int32_t known_flags = PD_INIT_PURE_NOISE | PD_NOISE_FROM_SEED | PD_XT_FROM_SEED;
     if (a->init_flags & ~known_flags) { pd_set_error("init_flags: unknown bits 0x%x", (unsigned)(a->init_flags & ~known_flags)); return 1; }
     if ((a->init_flags & PD_INIT_PURE_NOISE) && !a->init_latents) { pd_set_error("init_flags PD_INIT_PURE_NOISE needs init_latents"); return 1; }
-    for (auto& p : e->params)
-        if (p.group == 0 && !p.loaded) { pd_set_error("weights not loaded: '%s' (and possibly more)", p.name.c_str()); return 1; }
-    return 0;
+    return e->require_loaded(GROUP_SAMPLER, "");
 }
 
 int pd_engine::begin(const pd_sample_args* a, bool want_per_step, const pd_unipc_args* u, const pd_lms_args* l) {
@@ -781,12 +779,7 @@ int pd_init_random_weights(pd_engine* e, uint64_t seed) {
     return e->init_random(seed);
 }
 
-int pd_weights_missing(pd_engine* e) {
-    int n = 0;
-    if (e)
-        for (auto& p : e->params) n += (p.group == 0 && !p.loaded) ? 1 : 0;
-    return n;
-}
+int pd_weights_missing(pd_engine* e) { return e ? e->missing(GROUP_SAMPLER) : 0; }
 
 int pd_make_schedule(pd_engine* e, int32_t steps, float eta, int64_t* timesteps, float* alphas, float* alphas_prev,
                      float* sigmas, float* sqrt_one_minus_alphas) {

@@ -1,29 +1,26 @@
-// pdengine: cond-stage CLIP text transformer (SURVEY.md §8f "next" row N3), built from the same kernels as the loop.
+// pdengine: the CLIP text transformer (SURVEY.md §8f "next" row N3), built from the same kernels as the loop.  One stack serves the
+// SD1.5 cond stage and SD3's CLIP-L / CLIP-G (configured and called from sd3_text.cpp):
 //   FrozenCLIPEmbedder.forward            ldm/modules/encoders/modules.py:118-128  (layer "last": last_hidden_state)
 //   (D) PromptDiffusionPipeline.encode_prompt  pipeline_prompt_diffusion.py:308-487 (text_encoder(ids)[0])
-// The module behind both is transformers' CLIPTextModel ("openai/clip-vit-large-patch14"): token + position
-// embeddings, 12 pre-LN blocks (causal multi-head self-attention with biased q/k/v/out projections, quick-GELU MLP),
-// final LayerNorm.  Weight names are the checkpoint's: cond_stage_model.transformer.text_model.*.
+//   _get_clip_prompt_embeds   promptdiffusioncontrolnetpipeline_sd3.py:295-348  (hidden_states[-(clip_skip + 2)] and text_embeds of
+//                                                                                CLIPTextModelWithProjection, twice: CLIP-L, CLIP-G)
+// The module behind all of them is transformers' CLIPTextModel: token + position embeddings, pre-LN blocks (causal multi-head
+// self-attention with biased q/k/v/out projections, quick-GELU or erf-GELU MLP), final LayerNorm.  SD1.5 ("openai/clip-vit-large-patch14",
+// weights cond_stage_model.transformer.text_model.*) keeps the residual stream in the engine's stream type; the SD3 encoders keep it in fp32.
 // Tokenisation (BPE vocabulary files) stays with the caller: the boundary takes token ids.
-#include <climits>
-#include <cmath>
+#include <algorithm>
 
 #include "engine.h"
 
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
-void pd_engine::build_text() {
-    if (cfg.text_layers <= 0) return;
-    reg_group = 2;
-    const std::string P = "cond_stage_model.transformer.text_model.";
-    const int C = cfg.context_dim, F = cfg.text_ff, L = cfg.context_len;
-    TextW& t = text;
-    make_mat(t.tok, cfg.text_vocab, C, 1, C, false);
-    reg_mat(P + "embeddings.token_embedding.weight", {cfg.text_vocab, C}, &t.tok, 0, false);
+void pd_engine::build_clip(const std::string& P, ClipW& t) {
+    const int C = t.hidden, F = t.ff, L = t.positions;
+    make_mat(t.tok, t.vocab, C, 1, C, false);
+    reg_mat(P + "embeddings.token_embedding.weight", {t.vocab, C}, &t.tok, 0, false);
     make_mat(t.pos, L, C, 1, C, false);
     reg_mat(P + "embeddings.position_embedding.weight", {L, C}, &t.pos, 0, false);
-    t.layers.resize(cfg.text_layers);   // never resized again (Params point into it)
-    for (int i = 0; i < cfg.text_layers; ++i) {
+    for (size_t i = 0; i < t.layers.size(); ++i) {
         TextLayerW& l = t.layers[i];
         const std::string Lp = P + "encoder.layers." + std::to_string(i) + ".";
         make_mat(l.qkv, 3 * C, C, 1, C, true);   // rows [0,C) q, [C,2C) k, [2C,3C) v -- the attention kernel's layout
@@ -50,59 +47,142 @@ void pd_engine::build_text() {
     reg_vec(P + "final_layer_norm.weight", C, &t.fln_g, 'g');
     reg_vec(P + "final_layer_norm.bias", C, &t.fln_b, 'e');
     t.built = true;
-    reg_group = 0;
+}
+
+void pd_engine::build_text() {
+    if (cfg.text_layers <= 0) return;
+    ClipW& t = text;
+    t.vocab = cfg.text_vocab; t.hidden = cfg.context_dim; t.ff = cfg.text_ff; t.heads = cfg.text_heads; t.positions = cfg.context_len;
+    t.layers.resize(cfg.text_layers);
+    reg_group = GROUP_TEXT;
+    build_clip("cond_stage_model.transformer.text_model.", t);
+    reg_group = GROUP_SAMPLER;
+}
+
+// token + position embeddings of ids [B, L] int32 (device) -> the residual stream x [B, L, 1, C]
+int pd_engine::clip_embed(const ClipW& t, const int* ids_dev, Act& x) {
+    if (arena.dry) return 0;
+    PD_TRY(check_arena());
+    ++launches;
+    if (launch_embed_tokens(ids_dev, t.tok.w, t.tok.Kpad, t.pos.w, t.pos.Kpad, T, x.p, x.dt, x.B, x.H, x.C, t.vocab, stream)) {
+        pd_set_error("CLIP embedding launch failed");
+        return 1;
+    }
+    return 0;
+}
+
+int pd_engine::self_attention(const WMat& qkv, const Act& ln, int inner, int heads, bool causal, const float* relbias, float scale, Act& att) {
+    const int B = ln.B, L = ln.H, lpad = round_up(L, 8);
+    Act qk = new_act(B, L, 1, 2 * inner, T);
+    Act vt = new_act(B, inner, 1, lpad, T);
+    if (!arena.dry && lpad != L) HIP_OK(hipMemsetAsync(vt.p, 0, vt.bytes(), stream));   // pad keys of V^T must read as 0
+    PD_TRY(gemm(qkv, ln, qk, {.VT = vt.p, .vt_begin = 2 * inner, .vt_ld = lpad}));
+    att = new_act(B, L, 1, inner, T);
+    const void* K = reinterpret_cast<char*>(qk.p) + (size_t)inner * dt_size(T);   // q | k rows: k starts `inner` columns in
+    return attention(qk.p, 2 * inner, K, 2 * inner, vt.p, lpad, att.p, inner, B, L, L, inner, heads, causal, 0, 0, 0, relbias, scale);
+}
+
+int pd_engine::clip_block(const TextLayerW& l, Act& x, int heads, Activation act) {
+    const int B = x.B, L = x.H, C = x.C;
+    const size_t mk = arena.mark();
+    Act ln = new_act(B, L, 1, C, T), att;
+    PD_TRY(layernorm(x, ln, l.ln1_g, l.ln1_b));
+    PD_TRY(self_attention(l.qkv, ln, C, heads, /*causal=*/true, nullptr, 0.f, att));
+    Act h1 = new_act(B, L, 1, C, x.dt);
+    PD_TRY(gemm(l.out, att, h1, {.R = &x}));
+    PD_TRY(layernorm(h1, ln, l.ln2_g, l.ln2_b));
+    Act f = new_act(B, L, 1, l.fc1.Nout, T);
+    PD_TRY(gemm(l.fc1, ln, f, {.act = act}));
+    Act h2 = new_act(B, L, 1, C, x.dt);
+    PD_TRY(gemm(l.fc2, f, h2, {.R = &h1}));
+    // carry the block output down to the slot below this block's temporaries
+    if (!arena.dry) HIP_OK(hipMemcpyAsync(x.p, h2.p, x.bytes(), hipMemcpyDeviceToDevice, stream));
+    arena.release(mk);
+    return 0;
+}
+
+int pd_engine::clip_blocks(const ClipW& t, int first, int last, Act& x) {
+    for (int li = first; li < last; ++li) PD_TRY(clip_block(t.layers[li], x, t.heads, t.act));
+    return 0;
 }
 
 // tokens [B, L] int32 (device) -> last_hidden_state [B, L, C] fp32 (device)
 int pd_engine::text_forward(const int* ids_dev, int B, float* out_dev, int clip_skip) {
-    TextW& t = text;
-    const int C = cfg.context_dim, F = cfg.text_ff, L = cfg.context_len, H = cfg.text_heads;
-    const size_t eb = dt_size(T);
-    Act x = new_act(B, L, 1, C, S);
-    if (!arena.dry) {
-        ++launches;
-        if (launch_embed_tokens(ids_dev, t.tok.w, t.tok.Kpad, t.pos.w, t.pos.Kpad, T, x.p, S, B, L, C, cfg.text_vocab, stream)) {
-            pd_set_error("text embedding launch failed");
-            return 1;
-        }
-    }
-    const int lpad = round_up(L, 8);
-    const int n_run = (int)t.layers.size() - clip_skip;   // hidden_states[-(clip_skip+1)]: output of block n - clip_skip
-    for (int li = 0; li < n_run; ++li) {
-        TextLayerW& l = t.layers[li];
-        const size_t mk = arena.mark();
-        Act ln = new_act(B, L, 1, C, T);
-        PD_TRY(layernorm(x, ln, l.ln1_g, l.ln1_b));
-        Act qk = new_act(B, L, 1, 2 * C, T);
-        Act vt = new_act(B, C, 1, lpad, T);
-        if (!arena.dry && lpad != L) HIP_OK(hipMemsetAsync(vt.p, 0, vt.bytes(), stream));   // pad keys of V^T must read as 0
-        PD_TRY(gemm(l.qkv, ln, qk, {.VT = vt.p, .vt_begin = 2 * C, .vt_ld = lpad}));
-        Act att = new_act(B, L, 1, C, T);
-        PD_TRY(attention(qk.p, 2 * C, reinterpret_cast<char*>(qk.p) + (size_t)C * eb, 2 * C, vt.p, lpad, att.p, C, B, L, L, C, H,
-                         /*causal=*/true));
-        Act h1 = new_act(B, L, 1, C, S);
-        PD_TRY(gemm(l.out, att, h1, {.R = &x}));
-        PD_TRY(layernorm(h1, ln, l.ln2_g, l.ln2_b));
-        Act f = new_act(B, L, 1, F, T);
-        PD_TRY(gemm(l.fc1, ln, f, {.act = ACT_QUICK_GELU}));
-        Act h2 = new_act(B, L, 1, C, S);
-        PD_TRY(gemm(l.fc2, f, h2, {.R = &h1}));
-        // carry the block output down to the slot below this block's temporaries
-        if (!arena.dry) HIP_OK(hipMemcpyAsync(x.p, h2.p, x.bytes(), hipMemcpyDeviceToDevice, stream));
-        arena.release(mk);
-    }
-    Act out = new_act(B, L, 1, C, DT_F32);
+    ClipW& t = text;
+    Act x = new_act(B, t.positions, 1, t.hidden, S);
+    PD_TRY(clip_embed(t, ids_dev, x));
+    PD_TRY(clip_blocks(t, 0, (int)t.layers.size() - clip_skip, x));   // hidden_states[-(clip_skip+1)]: output of block n - clip_skip
+    Act out = new_act(B, t.positions, 1, t.hidden, DT_F32);
     PD_TRY(layernorm(x, out, t.fln_g, t.fln_b));
     if (!arena.dry) HIP_OK(hipMemcpyAsync(out_dev, out.p, out.bytes(), hipMemcpyDeviceToDevice, stream));
     return 0;
 }
 
-extern "C" int pd_text_weights_missing(pd_engine* e) {
-    int n = 0;
-    if (e)
-        for (auto& p : e->params) n += (p.group == 2 && !p.loaded) ? 1 : 0;
-    return n;
+// One pass serves both outputs: the hidden state is written at the skip layer; the pooled output carries on through the rest of the
+// stack to the final LayerNorm, EOS row and text_projection.
+int pd_engine::sd3_clip_forward(ClipW& t, const int* ids_dev, int B, int clip_skip, float* hid, int hid_rows, int hid_ld, int c_off, int width,
+                                float* pooled, int pooled_ld) {
+    const int C = t.hidden, L = t.positions, n = (int)t.layers.size();
+    const size_t mk0 = arena.mark();
+    Act x = new_act(B, L, 1, C, DT_F32);   // the residual stream: fp32 in every mode
+    PD_TRY(clip_embed(t, ids_dev, x));
+    const int capture = n - 1 - clip_skip;   // blocks run before hidden_states[-(clip_skip + 2)] is complete
+    PD_TRY(clip_blocks(t, 0, capture, x));
+    if (hid && !arena.dry) {
+        ++launches;
+        if (launch_joint_write(reinterpret_cast<const float*>(x.p), hid, B, L, C, width, hid_rows, hid_ld, c_off, stream)) {
+            pd_set_error("CLIP hidden-state write launch failed");
+            return 1;
+        }
+    }
+    if (pooled) {
+        PD_TRY(clip_blocks(t, capture, n, x));
+        // last_hidden_state[b, eos(b)] @ text_projection^T: LayerNorm is per row, so the EOS rows are gathered first
+        Act rows = new_act(B, 1, 1, C, DT_F32), lnr = new_act(B, 1, 1, C, DT_F32);
+        if (!arena.dry) {
+            PD_TRY(check_arena());
+            ++launches;
+            if (launch_eos_gather(ids_dev, reinterpret_cast<const float*>(x.p), reinterpret_cast<float*>(rows.p), B, L, C, t.eos_token_id, stream)) {
+                pd_set_error("CLIP EOS gather launch failed");
+                return 1;
+            }
+        }
+        PD_TRY(layernorm(rows, lnr, t.fln_g, t.fln_b));
+        if (!arena.dry) {
+            for (int b0 = 0; b0 < B; b0 += 4) {   // launch_gemv streams the weights once per <= 4 rows
+                ++launches;
+                if (launch_gemv(reinterpret_cast<const float*>(lnr.p) + (size_t)b0 * C, C, t.proj.w, T, t.proj.Kpad, nullptr, pooled + (size_t)b0 * pooled_ld,
+                                pooled_ld, std::min(4, B - b0), t.proj_dim, C, 0, stream)) {
+                    pd_set_error("CLIP text_projection launch failed");
+                    return 1;
+                }
+            }
+        }
+    }
+    arena.release(mk0);
+    return 0;
 }
+
+int pd_engine::upload_ids(const int32_t* ids, size_t n, int mem, int** dev) {
+    *dev = reinterpret_cast<int*>(arena.alloc(n * sizeof(int)));
+    if (arena.dry) return 0;
+    PD_TRY(check_arena());
+    if (hipMemcpyAsync(*dev, ids, n * sizeof(int), mem == PD_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream) != hipSuccess) {
+        pd_set_error("token upload failed");
+        return 1;
+    }
+    return 0;
+}
+
+int pd_engine::download(float* dst, const float* src, size_t n, int mem) {
+    if (hipMemcpyAsync(dst, src, n * sizeof(float), mem == PD_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream) != hipSuccess) {
+        pd_set_error("embedding read-back failed");
+        return 1;
+    }
+    return 0;
+}
+
+extern "C" int pd_text_weights_missing(pd_engine* e) { return e ? e->missing(GROUP_TEXT) : 0; }
 
 extern "C" int pd_text_encode_ex(pd_engine* e, const int32_t* ids, int32_t B, int32_t mem, int32_t clip_skip, float* out) {
     if (!e || !ids || !out || B < 1) { pd_set_error("bad argument"); return 1; }
@@ -112,45 +192,18 @@ extern "C" int pd_text_encode_ex(pd_engine* e, const int32_t* ids, int32_t B, in
     }
     if (!e->text.built) { pd_set_error("this engine was created without a text transformer (text_layers = 0)"); return 1; }
     if (e->ses.active) { pd_set_error("pd_text_encode: end the sampling session first"); return 1; }
-    for (auto& p : e->params)
-        if (p.group == 2 && !p.loaded) { pd_set_error("text transformer weights not loaded: '%s' (and possibly more)", p.name.c_str()); return 1; }
+    PD_TRY(e->require_loaded(GROUP_TEXT, "text transformer"));
     HIP_OK(hipSetDevice(e->device));
-    const int L = e->cfg.context_len, C = e->cfg.context_dim;
-    const size_t n_in = (size_t)B * L, n_out = (size_t)B * L * C;
-    // like the VAE decoder: the ControlNet context's workspace (idle outside a sampling step), main stream
-    std::swap(e->arena, e->arena2);
-    Arena saved = e->arena;
-    e->arena.base = nullptr; e->arena.cap = 0; e->arena.top = 0; e->arena.peak = 0; e->arena.dry = true;
-    int r = e->text_forward(nullptr, B, nullptr, 0);
-    const size_t need = e->arena.peak + n_in * sizeof(int) + n_out * sizeof(float) + (64u << 20);
-    e->arena = saved;
-    e->arena.dry = false;
-    if (!r && need > e->arena.cap) {
-        hipStreamSynchronize(e->stream);
-        if (e->stream2) hipStreamSynchronize(e->stream2);
-        e->clear_graphs();   // captured step loops point into this workspace
-        if (e->arena.base) hipFree(e->arena.base);
-        e->arena.base = nullptr; e->arena.cap = 0;
-        void* p = nullptr;
-        if (hipMalloc(&p, need) != hipSuccess) { pd_set_error("text workspace allocation of %.2f GiB failed", (double)need / (1 << 30)); r = 1; }
-        else { e->arena.base = reinterpret_cast<char*>(p); e->arena.cap = need; }
-    }
-    if (!r) {
-        e->arena.top = 0; e->arena.peak = 0;
-        int* din = reinterpret_cast<int*>(e->arena.alloc(n_in * sizeof(int)));
+    const size_t n_in = (size_t)B * e->text.positions, n_out = n_in * e->text.hidden;
+    return e->in_side_workspace("text", n_in * sizeof(int) + n_out * sizeof(float), [&] { return e->text_forward(nullptr, B, nullptr, 0); }, [&] {
+        int* din = nullptr;
+        PD_TRY(e->upload_ids(ids, n_in, mem, &din));
         float* dout = reinterpret_cast<float*>(e->arena.alloc(n_out * sizeof(float)));
-        if (hipMemcpyAsync(din, ids, n_in * sizeof(int), mem == PD_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-                           e->stream) != hipSuccess) { pd_set_error("token upload failed"); r = 1; }
-        if (!r) r = e->text_forward(din, B, dout, clip_skip);
-        if (!r) {
-            if (hipMemcpyAsync(out, dout, n_out * sizeof(float), mem == PD_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
-                               e->stream) != hipSuccess ||
-                hipStreamSynchronize(e->stream) != hipSuccess) { pd_set_error("embedding read-back failed"); r = 1; }
-        }
-        e->arena.top = 0;
-    }
-    std::swap(e->arena, e->arena2);
-    return r;
+        PD_TRY(e->text_forward(din, B, dout, clip_skip));
+        PD_TRY(e->download(out, dout, n_out, mem));
+        HIP_OK(hipStreamSynchronize(e->stream));
+        return 0;
+    });
 }
 
 extern "C" int pd_text_encode(pd_engine* e, const int32_t* ids, int32_t B, int32_t mem, float* out) {

@@ -42,7 +42,7 @@ void pd_engine::build_vattn(const std::string& prefix, VaeAttnW& a, int C) {
 
 void pd_engine::build_vae() {
     if (cfg.vae_ch <= 0) return;
-    reg_group = 1;
+    reg_group = GROUP_VAE;
     const std::string P = "first_stage_model.", D = P + "decoder.";
     const int nl = cfg.vae_num_levels;
     const int top = cfg.vae_ch * cfg.vae_ch_mult[nl - 1];
@@ -80,14 +80,14 @@ void pd_engine::build_vae() {
     build_conv(D + "conv_out.", v.conv_out, cfg.vae_ch, cfg.vae_out_ch, 3, 1);
     build_conv(P + "post_quant_conv.", v.post_quant, cfg.in_channels, cfg.in_channels, 1, 1);
     v.built = true;
-    reg_group = 0;
+    reg_group = GROUP_SAMPLER;
 }
 
 // Encoder.__init__ (model.py:452-506) with double_z and attn_resolutions = [] (models/cldm_v15.yaml:64-85), then quant_conv =
 // Conv2d(2 z, 2 embed_dim, 1) (autoencoder.py:33).  Registered in module order under the checkpoint's names.
 void pd_engine::build_vae_encoder() {
     if (!cfg.vae_encoder || cfg.vae_ch <= 0) return;
-    reg_group = 4;
+    reg_group = GROUP_VAE_ENCODER;
     const std::string P = "first_stage_model.", E = P + "encoder.";
     const int nl = cfg.vae_num_levels, z2 = 2 * cfg.in_channels;
     VaeEncW& v = vae_enc;
@@ -118,7 +118,7 @@ void pd_engine::build_vae_encoder() {
     build_conv(E + "conv_out.", v.conv_out, block_in, z2, 3, 1);
     build_conv(P + "quant_conv.", v.quant, z2, z2, 1, 1);
     v.built = true;
-    reg_group = 0;
+    reg_group = GROUP_SAMPLER;
 }
 
 // AttnBlock.forward: one head over all C channels, N = H*W tokens.  Scores are materialised per sample (fp32
@@ -209,52 +209,18 @@ int pd_engine::vae_forward(const float* latents_dev, int B, int h, int w, float*
     return 0;
 }
 
-extern "C" int pd_vae_weights_missing(pd_engine* e) {
-    int n = 0;
-    if (e)
-        for (auto& p : e->params) n += (p.group == 1 && !p.loaded) ? 1 : 0;
-    return n;
-}
-
-int pd_engine::vae_in_workspace(size_t io_bytes, const std::function<int()>& sizing, const std::function<int()>& run) {
-    // the first stage runs in the ControlNet context's workspace (idle outside a sampling step) on the main stream
-    std::swap(arena, arena2);
-    Arena saved = arena;
-    arena.base = nullptr; arena.cap = 0; arena.top = 0; arena.peak = 0; arena.dry = true;
-    int r = sizing();
-    const size_t need = arena.peak + io_bytes + (64u << 20);
-    arena = saved;
-    arena.dry = false;
-    if (!r && need > arena.cap) {
-        hipStreamSynchronize(stream);
-        if (stream2) hipStreamSynchronize(stream2);
-        clear_graphs();   // captured step loops point into this workspace
-        if (arena.base) hipFree(arena.base);
-        arena.base = nullptr; arena.cap = 0;
-        void* p = nullptr;
-        if (hipMalloc(&p, need) != hipSuccess) { pd_set_error("VAE workspace allocation of %.2f GiB failed", (double)need / (1 << 30)); r = 1; }
-        else { arena.base = reinterpret_cast<char*>(p); arena.cap = need; }
-    }
-    if (!r) {
-        arena.top = 0; arena.peak = 0;
-        r = run();
-        arena.top = 0;
-    }
-    std::swap(arena, arena2);
-    return r;
-}
+extern "C" int pd_vae_weights_missing(pd_engine* e) { return e ? e->missing(GROUP_VAE) : 0; }
 
 extern "C" int pd_vae_decode(pd_engine* e, const float* latents, int32_t B, int32_t h, int32_t w, int32_t mem, float* images_out) {
     if (!e || !latents || !images_out || B < 1 || h < 1 || w < 1) { pd_set_error("bad argument"); return 1; }
     if (!e->vae.built) { pd_set_error("this engine was created without a VAE decoder (vae_ch = 0)"); return 1; }
     if (e->ses.active) { pd_set_error("pd_vae_decode: end the sampling session first"); return 1; }
     if ((h * w) % 64) { pd_set_error("pd_vae_decode: h*w must be a multiple of 64 (latents of 64x64-pixel multiples)"); return 1; }
-    for (auto& p : e->params)
-        if (p.group == 1 && !p.loaded) { pd_set_error("VAE weights not loaded: '%s' (and possibly more)", p.name.c_str()); return 1; }
+    PD_TRY(e->require_loaded(GROUP_VAE, "VAE"));
     HIP_OK(hipSetDevice(e->device));
     const int H = 8 * h, W = 8 * w;
     const size_t n_in = (size_t)B * e->cfg.in_channels * h * w, n_out = (size_t)B * e->cfg.vae_out_ch * H * W;
-    return e->vae_in_workspace((n_in + n_out) * sizeof(float), [&] { return e->vae_forward(nullptr, B, h, w, nullptr); }, [&] {
+    return e->in_side_workspace("VAE", (n_in + n_out) * sizeof(float), [&] { return e->vae_forward(nullptr, B, h, w, nullptr); }, [&] {
         int r = 0;
         float* din = reinterpret_cast<float*>(e->arena.alloc(n_in * sizeof(float)));
         float* dout = reinterpret_cast<float*>(e->arena.alloc(n_out * sizeof(float)));
@@ -322,19 +288,13 @@ int pd_engine::vae_encoder_forward(const float* images_dev, int B, int H, int W,
     return 0;
 }
 
-extern "C" int pd_vae_encoder_weights_missing(pd_engine* e) {
-    int n = 0;
-    if (e)
-        for (auto& p : e->params) n += (p.group == 4 && !p.loaded) ? 1 : 0;
-    return n;
-}
+extern "C" int pd_vae_encoder_weights_missing(pd_engine* e) { return e ? e->missing(GROUP_VAE_ENCODER) : 0; }
 
 extern "C" int pd_vae_encode(pd_engine* e, const float* images, int32_t B, int32_t H, int32_t W, int32_t mem, int32_t what,
                              const float* noise, float* out) {
     if (!e || !images || !out || B < 1 || H < 1 || W < 1) { pd_set_error("bad argument"); return 1; }
     if (!e->vae_enc.built) { pd_set_error("this engine was created without a VAE encoder (vae_encoder = 0)"); return 1; }
-    for (auto& p : e->params)
-        if (p.group == 4 && !p.loaded) { pd_set_error("VAE encoder weights not loaded: '%s' (and possibly more)", p.name.c_str()); return 1; }
+    PD_TRY(e->require_loaded(GROUP_VAE_ENCODER, "VAE encoder"));
     if (e->ses.active) { pd_set_error("pd_vae_encode: end the sampling session first"); return 1; }
     if (H % 8 || W % 8 || ((H / 8) * (W / 8)) % 64) {
         pd_set_error("pd_vae_encode: H and W must be multiples of 8 and (H/8)*(W/8) a multiple of 64 (got %d x %d)", H, W);
@@ -349,8 +309,8 @@ extern "C" int pd_vae_encode(pd_engine* e, const float* images, int32_t B, int32
     const size_t n_in = (size_t)B * e->cfg.vae_out_ch * H * W, n_lat = (size_t)B * z * h * w;
     // (noise NULL with PD_VAE_SAMPLE: the posterior kernel draws at (PD_RNG_VAE, draw 0) itself)
     const size_t n_noise = (what == PD_VAE_SAMPLE && noise) ? n_lat : 0, n_out = what == PD_VAE_MOMENTS ? 2 * n_lat : n_lat;
-    return e->vae_in_workspace((n_in + n_noise + n_out) * sizeof(float),
-                               [&] { return e->vae_encoder_forward(nullptr, B, H, W, what, nullptr, nullptr); }, [&] {
+    return e->in_side_workspace("VAE", (n_in + n_noise + n_out) * sizeof(float),
+                                [&] { return e->vae_encoder_forward(nullptr, B, H, W, what, nullptr, nullptr); }, [&] {
         int r = 0;
         float* din = reinterpret_cast<float*>(e->arena.alloc(n_in * sizeof(float)));
         float* dnoise = n_noise ? reinterpret_cast<float*>(e->arena.alloc(n_noise * sizeof(float))) : nullptr;

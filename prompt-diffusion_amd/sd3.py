@@ -140,19 +140,8 @@ def sd3_text_spec(cfg: SD3TextConfig):
     for prefix, c in (("text_encoder.", cfg.clip_l), ("text_encoder_2.", cfg.clip_g)):
         if c is None or c.layers == 0:
             continue
-        P, Cc, F = prefix + "text_model.", c.hidden, c.ff
-        out.append((P + "embeddings.token_embedding.weight", (c.vocab, Cc), "w"))
-        out.append((P + "embeddings.position_embedding.weight", (c.max_positions, Cc), "w"))
-        for i in range(c.layers):
-            L = f"{P}encoder.layers.{i}."
-            for nm in ("k_proj", "v_proj", "q_proj", "out_proj"):
-                out += [(L + f"self_attn.{nm}.weight", (Cc, Cc), "w"), (L + f"self_attn.{nm}.bias", (Cc,), "b")]
-            out += [(L + "layer_norm1.weight", (Cc,), "gamma"), (L + "layer_norm1.bias", (Cc,), "beta")]
-            out += [(L + "mlp.fc1.weight", (F, Cc), "w"), (L + "mlp.fc1.bias", (F,), "b")]
-            out += [(L + "mlp.fc2.weight", (Cc, F), "w"), (L + "mlp.fc2.bias", (Cc,), "b")]
-            out += [(L + "layer_norm2.weight", (Cc,), "gamma"), (L + "layer_norm2.bias", (Cc,), "beta")]
-        out += [(P + "final_layer_norm.weight", (Cc,), "gamma"), (P + "final_layer_norm.bias", (Cc,), "beta")]
-        out.append((prefix + "text_projection.weight", (c.proj_dim, Cc), "w"))
+        out += W.clip_text_spec(prefix + "text_model.", c.vocab, c.max_positions, c.hidden, c.ff, c.layers)
+        out.append((prefix + "text_projection.weight", (c.proj_dim, c.hidden), "w"))
     t = cfg.t5
     if t is not None and t.layers > 0:
         P, D, I, F = "text_encoder_3.", t.d_model, t.heads * t.d_kv, t.d_ff

@@ -396,18 +396,15 @@ _HED_NAMES = frozenset(n for n, _, _ in hed_spec())
 TEXT_PREFIX = "cond_stage_model.transformer.text_model."
 
 
-def text_spec(cfg: ModelConfig, prefix: str = TEXT_PREFIX) -> List[Spec]:
-    """Parameters of the CLIP text transformer under the names the SD1.5 checkpoint stores them
-    (`FrozenCLIPEmbedder.transformer` = transformers' `CLIPTextModel`, ldm/modules/encoders/modules.py:98), in module
-    order: embeddings, encoder.layers.i.{self_attn.{k,v,q,out}_proj, layer_norm1, mlp.fc1/fc2, layer_norm2},
-    final_layer_norm."""
+def clip_text_spec(prefix: str, vocab: int, positions: int, hidden: int, ff: int, layers: int) -> List[Spec]:
+    """Parameters of one transformers `CLIPTextModel` under `prefix` (its `text_model.`), in module order: embeddings,
+    encoder.layers.i.{self_attn.{k,v,q,out}_proj, layer_norm1, mlp.fc1/fc2, layer_norm2}, final_layer_norm.  The SD1.5
+    text transformer (text_spec) and the SD3 CLIP encoders (sd3.sd3_text_spec) are both this list."""
+    C, F = hidden, ff
     out: List[Spec] = []
-    if cfg.text_layers <= 0:
-        return out
-    C, F = cfg.context_dim, cfg.text_ff
-    out.append((prefix + "embeddings.token_embedding.weight", (cfg.text_vocab, C), "w"))
-    out.append((prefix + "embeddings.position_embedding.weight", (cfg.context_len, C), "w"))
-    for i in range(cfg.text_layers):
+    out.append((prefix + "embeddings.token_embedding.weight", (vocab, C), "w"))
+    out.append((prefix + "embeddings.position_embedding.weight", (positions, C), "w"))
+    for i in range(layers):
         L = f"{prefix}encoder.layers.{i}."
         for nm in ("k_proj", "v_proj", "q_proj", "out_proj"):
             out.append((L + f"self_attn.{nm}.weight", (C, C), "w"))
@@ -418,6 +415,14 @@ def text_spec(cfg: ModelConfig, prefix: str = TEXT_PREFIX) -> List[Spec]:
         out += [(L + "layer_norm2.weight", (C,), "gamma"), (L + "layer_norm2.bias", (C,), "beta")]
     out += [(prefix + "final_layer_norm.weight", (C,), "gamma"), (prefix + "final_layer_norm.bias", (C,), "beta")]
     return out
+
+
+def text_spec(cfg: ModelConfig, prefix: str = TEXT_PREFIX) -> List[Spec]:
+    """Parameters of the CLIP text transformer under the names the SD1.5 checkpoint stores them
+    (`FrozenCLIPEmbedder.transformer` = transformers' `CLIPTextModel`, ldm/modules/encoders/modules.py:98)."""
+    if cfg.text_layers <= 0:
+        return []
+    return clip_text_spec(prefix, cfg.text_vocab, cfg.context_len, cfg.context_dim, cfg.text_ff, cfg.text_layers)
 
 
 def synth_text_state_dict(cfg: ModelConfig, seed: int = 1234) -> Dict[str, np.ndarray]:

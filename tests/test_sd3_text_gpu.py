@@ -1,4 +1,4 @@
-"""SD3 text encoders on the engine (CLIP-L, CLIP-G, T5; sd3_text.cpp) against tests/golden/sd3_text.npz -- computed by transformers itself,
+"""SD3 text encoders on the engine (CLIP-L, CLIP-G: text.cpp; T5: sd3_text.cpp) against tests/golden/sd3_text.npz -- computed by transformers itself,
 tests/golden/make_golden_sd3_text.py -- and, at the T5 lengths the fixture does not hold, against the NumPy restatement that the CPU suite
 pins to the same fixture (tests/sd3_text_ref.py).  Nothing here imports transformers.  Configuration: sd3.SD3_TINY_TEXT (why its T5 width
 is 384: tests/test_sd3_text_cpu.py).
@@ -175,6 +175,50 @@ def test_pooled_row_follows_the_eos_token(eng, sd):
         assert not np.array_equal(pooled[0], pooled[3])              # moving the EOS moves the row
         assert R.eos_positions(ids, c.eos_token_id).tolist() == [9, 9, 9, 30]
         check(f"{which} pooled at moved EOS", pooled, R.clip_forward(sd, c, prefix, ids)[1], eng.prec)
+
+
+# 4b --------------------------------------------------------------------------------------------------- where the stack stops
+@pytest.fixture(scope="module")
+def clip_refs(sd, gold):
+    """(hidden_states, text_embeds) of the NumPy restatement for the fixture's CLIP ids, computed once."""
+    return {which: R.clip_forward(sd, c, prefix, gold[key])
+            for which, c, prefix, key in (("clip_l", TCFG.clip_l, "text_encoder.", "ids_l"), ("clip_g", TCFG.clip_g, "text_encoder_2.", "ids_g"))}
+
+
+def test_capture_before_any_block(eng, gold, clip_refs):
+    """clip_skip = layers - 1 asks for hidden_states[0]: the token + position embeddings, written before any block has run, while the
+    pooled output still takes the whole stack and so does not depend on clip_skip."""
+    for which, c, key in (("clip_l", TCFG.clip_l, "ids_l"), ("clip_g", TCFG.clip_g, "ids_g")):
+        hs, pooled_ref = clip_refs[which]
+        hid, pooled = eng.text_encoder(which, gold[key], clip_skip=c.layers - 1)
+        check(f"{which} embeddings (skip {c.layers - 1})", hid, hs[0], eng.prec)
+        check(f"{which} pooled (skip {c.layers - 1})", pooled, pooled_ref, eng.prec)
+        assert np.array_equal(pooled, eng.text_encoder(which, gold[key], clip_skip=0)[1])
+
+
+def test_one_output_only(eng, gold, clip_refs):
+    """pd_sd3_text_encoder with pooled = NULL or hidden = NULL (the Python wrapper always asks for both): each output is the same bits as
+    in the two-output call, and without the pooled output the stack stops at the capture layer, so fewer kernels are launched."""
+    c, skip, base = TCFG.clip_l, 1, eng.base
+    ids = np.ascontiguousarray(gold["ids_l"][:2], np.int32)
+
+    def call(want_hidden, want_pooled):
+        hid, po = np.zeros((2, 77, c.hidden), np.float32), np.zeros((2, c.proj_dim), np.float32)
+        n0 = base.stat("launches")
+        base._check(base.lib.pd_sd3_text_encoder(base._h, 0, ids.ctypes.data, 2, 77, skip, E.PD_MEM_HOST,
+                                                 hid.ctypes.data if want_hidden else None, po.ctypes.data if want_pooled else None))
+        return hid, po, base.stat("launches") - n0
+
+    hid, po, n_both = call(True, True)
+    hs, pooled_ref = clip_refs["clip_l"]
+    check("clip_l hidden skip1, batch 2", hid, hs[-(skip + 2)][:2], eng.prec)
+    check("clip_l pooled, batch 2", po, pooled_ref[:2], eng.prec)
+    hid_only, untouched, n_hidden = call(True, False)
+    assert np.array_equal(hid_only, hid) and not untouched.any()
+    untouched, po_only, n_pooled = call(False, True)
+    assert np.array_equal(po_only, po) and not untouched.any()
+    print(f"[sd3_text] launches: both {n_both}, hidden only {n_hidden}, pooled only {n_pooled}")
+    assert 0 < n_hidden < n_both and 0 < n_pooled <= n_both
 
 
 # 5 ---------------------------------------------------------------------------------------------------- causality
