@@ -513,18 +513,22 @@ int pd_comm_destroy(pd_engine* e); /* also done by pd_engine_destroy */
  *   on 64x80 ring tiles without split-K slabs and a finalize pass: 0 off, d = where the 128x160 grid fills at most 1/d of the chip, 4), "ring_pp" (its ping-pong form -- two wave groups half a K step apart -- for K >= 2560 and for one
  *   256-row tile per CU, 1; bit-identical), "slab_gn" (a ResBlock conv1 that runs split-K hands its fp32 slabs to the single-kernel
  *   GroupNorm that reads them instead of running a finalize pass, 1; bit-identical), "patch_split_min" (patch-conv split-K: at
- *   least this many 128-byte channel chunks per slice, 4). */
+ *   least this many 128-byte channel chunks per slice, 4), "ups_fold" / "ups_fold_tiles" (2-byte modes: a UNet decoder Upsample conv --
+ *   conv3x3 of a nearest-x2 upsampled tensor, bias only, source height and width multiples of 16 -- runs as four 2x2-tap phase
+ *   convolutions over the source with folded weights, conv_upfold.hip, 4/9 of the products, when its phase grid has at least that many
+ *   blocks: 1 / -1 = three quarters of the CUs, the block count at which a patch conv runs unsplit.  Not bit-identical to the nine-tap
+ *   path: every folded weight is rounded once more; stat "ups_fold_launches" counts the launches that took it). */
 int pd_set_option(pd_engine* e, const char* key, int64_t value);
 /* "graph_captures" / "graph_replays" (step loops captured / replayed from a captured graph since the engine was created),
- * "workspace_bytes", "weight_bytes", "launches" (engine launches, split-K finalize passes not counted), "ring_launches" / "gn_from_slabs"
- * (of which: gemm_ring.hip / GroupNorm fed by split-K slabs), "steps", "event_overhead_ns", "cfg_shared" (see option "cfg_share"),
+ * "workspace_bytes", "weight_bytes", "launches" (engine launches, split-K finalize passes not counted), "ring_launches" / "gn_from_slabs" / "ups_fold_launches"
+ * (of which: gemm_ring.hip / GroupNorm fed by split-K slabs / the four-phase upsample conv), "steps", "event_overhead_ns", "cfg_shared" (see option "cfg_share"),
  * "gn_kernel" (which kernel the engine's last GroupNorm launch took: PD_GN_TWO_PASS = gn_stats + gn_apply, PD_GN_LDS_SLAB = the
  * single LDS-slab kernel, PD_GN_REGISTER = the register-resident kernel of the 2-byte modes; 0 before the first launch.  The choice
  * depends on the storage type, H * W, C / 32, a 100 KB LDS budget and the options "gn_single" / "gn_reg"; pd_op_groupnorm and
  * pd_op_groupnorm_slabs set it, so a test can assert that a shape ran on the kernel it was chosen for),
  * "gemm_family" (which kernel family the engine's last convolution / linear launch took, PD_GEMM_* in the order of the names the
  * option "verbose" 2 dispatch trace prints: the weight-streaming GEMV, the LDS-patch conv3x3 generations 1 / 2 / 4, the ring GEMM, the
- * implicit GEMM; -1 before the first launch.  pd_op_conv2d and pd_op_linear set it through the same dispatch as the network, so a
+ * implicit GEMM, the four-phase upsample conv; -1 before the first launch.  pd_op_conv2d and pd_op_linear set it through the same dispatch as the network, so a
  * test can assert that an option setting put a shape on the kernel it names) */
 #define PD_GN_TWO_PASS 1
 #define PD_GN_LDS_SLAB 2
@@ -535,6 +539,7 @@ int pd_set_option(pd_engine* e, const char* key, int64_t value);
 #define PD_GEMM_PATCH4 3
 #define PD_GEMM_RING 4
 #define PD_GEMM_IGEMM 5
+#define PD_GEMM_UPFOLD 6
 int64_t pd_get_stat(pd_engine* e, const char* key);
 /* Per-launch timing: while option "profile" is 1 the engine brackets every contraction launch with HIP
  * events on its stream.  klass 0 = igemm_kernel on a conv3x3, 1 = igemm_kernel / rgemm_kernel on a conv1x1/linear,

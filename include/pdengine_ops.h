@@ -3,6 +3,7 @@
  * Each hook runs exactly one kernel family of the hot path on host fp32 arrays in the reference's
  * layouts, in the engine's precision mode, so tests/ can compare it with the oracle:
  *   pd_op_conv2d     nn.Conv2d 3x3/1x1 (stride 1/2, fused nearest-x2 upsample)   openaimodel.py:90-159,200-240
+ *   pd_op_conv2d_upfold  Upsample's conv3x3(nearest_x2(x)) through the weight fold and the four-phase kernel   openaimodel.py:115-117
  *   pd_op_linear     nn.Linear / GEGLU / SiLU->Linear (emb_layers)                 attention.py:49-76, openaimodel.py:217-223
  *   pd_op_linear_fp8 the e4m3 form of nn.Linear used by the SD3 path's sd3_fp8 option
  *   pd_op_groupnorm  GroupNorm32 (+SiLU)                                           util.py:217-219, attention.py:88-89
@@ -22,6 +23,13 @@ extern "C" {
 #endif
 int pd_op_conv2d(pd_engine* e, const float* x, const float* w, const float* bias, const float* residual, int B, int Cin, int H,
                  int W, int Cout, int k, int stride, int upsample, int act_silu, float scale, int stream_out, float* y);
+/* conv3x3(nearest_x2(x)) + bias [+ residual] with ad-hoc weights through the decoder Upsample's own call path: the weights are folded
+ * into the four phase matrices (option "ups_fold") and the call goes through the engine's dispatch, which must put it on the four-phase
+ * kernel (PD_GEMM_UPFOLD; option "ups_fold_tiles" is the grid threshold).  A call the dispatch would send elsewhere -- a source height
+ * or width that is no multiple of 16, a residual, an fp32-storage mode, the option off, too small a grid -- is an error, not a
+ * fall-back.  x [B, Cin, H, W], w [Cout, Cin, 3, 3], y [B, Cout, 2H, 2W]. */
+int pd_op_conv2d_upfold(pd_engine* e, const float* x, const float* w, const float* bias, const float* residual, int B, int Cin, int H,
+                        int W, int Cout, float* y);
 int pd_op_linear(pd_engine* e, const float* x, const float* w, const float* bias, int M, int K, int N, int geglu, int a_silu,
                  float* y);
 /* the SD3 path's PREC_FP8 linear layer (option sd3_fp8): e4m3 operands quantised on the device with one scale per row of x

@@ -82,6 +82,23 @@ __device__ __forceinline__ PatchTile patch_tile(const GemmParams& p) {
     return t;
 }
 
+// The phase conv's tile (conv_upfold.hip): the grid is 4 x the plain grid over the source image, phase slowest -- the blocks in
+// flight share one phase's weight panels -- and each phase's run of blocks takes the XCD order of a plain launch.
+__device__ __forceinline__ PatchTile patch_phase_tile(const GemmParams& p, int& phase) {
+    const int ptx = p.Wout / TP, pty = p.Hout / TP;
+    const int mtiles = (p.M / (p.Hout * p.Wout)) * ptx * pty, ntiles = (p.N + BN - 1) / BN;
+    phase = blockIdx.x / (mtiles * ntiles);
+    const int bid = xcd_tile_order(blockIdx.x - phase * (mtiles * ntiles), mtiles * ntiles);
+    const int bm = bid / ntiles;
+    PatchTile t;
+    t.bn = bid % ntiles;
+    t.sample = bm / (ptx * pty);
+    const int prem = bm - t.sample * (ptx * pty);
+    t.y0 = (prem / ptx) * TP; t.x0 = (prem - (prem / ptx) * ptx) * TP;
+    t.sy0 = t.y0 - 1; t.sx0 = t.x0 - 1;
+    return t;
+}
+
 // split-K (blockIdx.y): slice `slice` of `splitk` owns the channel chunks [c0, c0 + nchunks) of chunks_all = Cin / BKE; the last
 // slice may be shorter, none is empty (pd_engine::plan_gemm)
 struct ChunkSlice { int c0, nchunks; };

@@ -647,10 +647,37 @@ bool pd_engine::st_tail_on(const STW& s, int rows_per_sample, int L) const {
     return opt_st_fuse && S == T && st_tail_eligible(P, s.C, cfg.num_heads, rows_per_sample, L);
 }
 
+// conv3x3(nearest_x2(x)) = four 2x2-tap convs over x, one per output parity, whose weights are sums of the nine (conv_upfold.hip).  Derived
+// weights like the folded LayerNorms: rebuilt under the same dirty flag.  2-byte modes only -- f32 and f16x2 keep the reference's
+// operation order -- and only for matrices the phase kernel can take (whole 128-byte channel chunks, 4-channel store groups).
+bool pd_engine::upfold_wanted(const WMat& m) const {
+    return opt_ups_fold && (P == DT_F16 || P == DT_BF16) && T == P && m.taps == 9 && m.cin_pad % 64 == 0 && m.N % 4 == 0 && m.K == 9 * m.cin_pad;
+}
+int pd_engine::fold_upconv(WMat& m) {
+    if (!upfold_wanted(m)) return 0;
+    if (!m.w_up) {
+        m.w_up = dmalloc((size_t)16 * m.N * m.cin_pad * dt_size(T));
+        if (!m.w_up) { pd_set_error("allocation of the folded upsample-conv weights failed"); return 1; }
+    }
+    if (launch_upfold_weights(m.w, m.w_up, T, m.N, m.cin_pad, m.Kpad, stream)) { pd_set_error("upsample-conv weight fold launch failed"); return 1; }
+    return 0;
+}
+int pd_engine::fold_upconvs() {
+    for (DecBlock& b : unet.dec)
+        if (b.up) PD_TRY(fold_upconv(b.upconv.m));
+    return 0;
+}
+
 int pd_engine::fold_layernorms() {
     const bool on = opt_ln_fuse < 0 ? !f32 : opt_ln_fuse != 0;
     const bool tail = opt_st_fuse && S == T && (P == DT_F16 || P == DT_BF16);
-    if ((!on && !tail) || !ln_dirty) return 0;
+    if (!ln_dirty) return 0;
+    PD_TRY(fold_upconvs());
+    if (!on && !tail) {
+        HIP_OK(hipStreamSynchronize(stream));
+        ln_dirty = false;
+        return 0;
+    }
     auto fold = [&](WMat& m, const float* g, const float* b) -> int {
         if (!m.w_ln) {
             m.w_ln = dmalloc((size_t)m.N * m.Kpad * dt_size(T));
@@ -796,6 +823,13 @@ GemmPlan pd_engine::plan_gemm(const GemmParams& p, const WMat& m, const GemmCall
         pl.family = GEMM_GEMV;
         return pl;
     }
+    // a decoder Upsample conv (bias only) with folded weights: four 2x2-tap phase convs over the source, 4/9 of the products, where the
+    // phase grid fills the chip like an unsplit patch launch (the 8x8 -> 16x16 level, batch-1 grids and every ad-hoc weight stay below)
+    if (opt_ups_fold && c.ups == 1 && m.w_up && plain && !c.ln_in && !c.ln_out && conv_upfold_eligible(p, P) &&
+        (opt_ups_fold_tiles < 0 ? patch_unsplit(conv_upfold_tiles(p)) : conv_upfold_tiles(p) >= opt_ups_fold_tiles)) {
+        pl.family = GEMM_UPFOLD;
+        return pl;
+    }
     const int ptiles = patch_tiles(p);
     bool use_patch = patch_unsplit(ptiles);
     // 16x16-level convs: too few 16x16 patches for the chip, but the patch kernel still beats the generic gather when the
@@ -921,10 +955,12 @@ int pd_engine::gemm(const WMat& m, const Act& in, Act& out, const GemmCall& c) {
     } else if (profiling) {
         // algorithmic flops: 2 * M * N * K with the logical (unpadded) channel counts
         const double n_log = m.geglu ? 2.0 * m.Nout : (double)m.Nout;
-        prof_begin(rec, pl.patch() ? 3 : m.taps == 9 ? 0 : 1, 2.0 * (double)p.M * n_log * (double)m.taps * (double)m.cin);
-        rec.M = p.M; rec.N = p.N; rec.K = p.K; rec.taps = p.taps * 10 + p.stride + (p.ups ? 5 : 0);
+        // (the four-phase upsample conv executes 4 of the 9 taps: its record counts what it runs)
+        const bool upfold = pl.family == GEMM_UPFOLD;
+        prof_begin(rec, pl.patch() || upfold ? 3 : m.taps == 9 ? 0 : 1, 2.0 * (double)p.M * n_log * (double)(upfold ? 4 : m.taps) * (double)m.cin);
+        rec.M = p.M; rec.N = p.N; rec.K = upfold ? 4 * p.Cin : p.K; rec.taps = (upfold ? 4 : p.taps) * 10 + p.stride + (p.ups ? 5 : 0);
     }
-    hipEvent_t mid = (profiling && !gemv && !pl.patch()) ? next_event() : nullptr;
+    hipEvent_t mid = (profiling && !gemv && !pl.patch() && pl.family != GEMM_UPFOLD) ? next_event() : nullptr;
     if (gemv) {
         const int r = launch_gemv(reinterpret_cast<const float*>(in.p), in.C, m.w, T, m.Kpad, m.bias, reinterpret_cast<float*>(out.p), p.ldc,
                                   p.M, m.N, m.K, p.a_silu, stream);
@@ -932,15 +968,16 @@ int pd_engine::gemm(const WMat& m, const Act& in, Act& out, const GemmCall& c) {
         if (r) { pd_set_error("gemv launch failed"); return 1; }
         return 0;
     }
-    static const char* const family_name[] = {"gemv", "patch1", "patch2", "patch4", "ring", "igemm"};
+    static const char* const family_name[] = {"gemv", "patch1", "patch2", "patch4", "ring", "igemm", "upfold"};
     if (verbose >= 2)   // dispatch trace (option "verbose" 2): which kernel family / tile / split a launch takes
         fprintf(stderr, "[pdengine] gemm M %d N %d K %d taps %d stride %d ups %d: %s splitk %d big_tile %d ring_tile %d act %d R %d ln_in %d ln_out %d\n", p.M, p.N, p.K, p.taps,
                 p.stride, p.ups, family_name[pl.family], p.splitk, p.big_tile, pl.ring_tile, p.act, p.R ? 1 : 0, p.ln_stats ? 1 : 0, p.stats_out ? 1 : 0);
     const int prec = in.dt == DT_FP8 ? PREC_FP8 : P;
-    const int r = pl.family == GEMM_PATCH4 ? launch_conv_patch4(p, P, stream) : pl.family == GEMM_PATCH2 ? launch_conv_patch2(p, P, stream) :
+    const int r = pl.family == GEMM_UPFOLD ? launch_conv_upfold(p, m.w_up, P, stream) : pl.family == GEMM_PATCH4 ? launch_conv_patch4(p, P, stream) : pl.family == GEMM_PATCH2 ? launch_conv_patch2(p, P, stream) :
                   pl.family == GEMM_PATCH1 ? launch_conv_patch(p, P, stream) : ring ? launch_ring_gemm(p, prec, pl.ring_tile, stream) : launch_gemm(p, prec, stream, mid);
     if (r) { pd_set_error("gemm launch failed: %s", hipGetErrorString(hipGetLastError())); return 1; }
     if (ring) ++ring_launches;
+    if (pl.family == GEMM_UPFOLD) ++ups_fold_launches;
     if (pl.defer_finalize) *c.defer = SlabDefer{true, true, reinterpret_cast<const float*>(p.slab), p.splitk, p.bias, p.rowvec, p.rowvec_stride};
     if (profiling && mid && ring) HIP_OK(hipEventRecord(mid, stream));
     if (profiling) {

@@ -50,6 +50,8 @@ struct WMat {
     void* w_ln = nullptr;
     float* colsum = nullptr;
     float* bias_ln = nullptr;
+    // conv3x3 behind a nearest-x2 upsample (pd_engine::fold_upconv): the four phase matrices [4][N][4 * cin_pad], conv_upfold.hip
+    void* w_up = nullptr;
     // e4m3 copy with one scale per output row (pd_engine::sd3_quantize): the PREC_FP8 form of this layer
     void* w8 = nullptr;
     float* wscale = nullptr;
@@ -313,7 +315,7 @@ struct GemmCall {
 };
 
 // Which kernel a gemm() call takes (pd_engine::plan_gemm): the verbose-2 dispatch trace prints exactly this.
-enum GemmFamily { GEMM_GEMV, GEMM_PATCH1, GEMM_PATCH2, GEMM_PATCH4, GEMM_RING, GEMM_IGEMM };
+enum GemmFamily { GEMM_GEMV, GEMM_PATCH1, GEMM_PATCH2, GEMM_PATCH4, GEMM_RING, GEMM_IGEMM, GEMM_UPFOLD };
 struct GemmPlan {
     GemmFamily family = GEMM_IGEMM;
     int splitk = 1, big_tile = 0, ring_tile = 0;   // K (igemm) or channel-chunk (patch) slices; GemmParams::big_tile (igemm); launch_ring_gemm's tile (ring)
@@ -452,6 +454,8 @@ struct pd_engine {
     int opt_short_k = 20;      // linear layers with at most this many K steps: 8-wave 128x160 tile at 16 waves per CU
     bool opt_patch_split = true;      // LDS-patch conv with the channel chunks split over 2-4 slices (16x16 level)
     int opt_patch_split_tiles = 64;
+    bool opt_ups_fold = true;      // decoder Upsample convs as four 2x2-tap phase convs (2-byte modes)
+    int opt_ups_fold_tiles = -1;   // ... when the phase grid has at least this many blocks; -1: where patch_unsplit() admits an unsplit launch
     int opt_patch_split_min = 4;      // ... each slice at least this many 128-byte channel chunks.  (min 1 / tiles 32 measured +2.3 % at batch 1 and
                                       // neutral at batch 8, but re-associates the sums of the 256x256 parity fixture's convs: its step-0 latent error
                                       // moves from 7.4e-4 to 1.02e-3 -- same arithmetic, other rounding pattern -- so the defaults stay)
@@ -470,6 +474,7 @@ struct pd_engine {
     long long gn_from_slabs = 0;   // GroupNorm launches that summed a split-K GEMM's slabs (stat "gn_from_slabs")
     long long ring_launches = 0;   // launches that took gemm_ring.hip (stat "ring_launches")
     int gn_kernel = 0;             // GN_KIND_* of the last groupnorm() launch (stat "gn_kernel"), set where the launch is decided
+    long long ups_fold_launches = 0;   // launches that took conv_upfold.hip (stat "ups_fold_launches")
     int gemm_family = -1;          // GemmFamily of the last gemm() launch (stat "gemm_family"), set where gemm() launches; -1: none yet
     // optional per-launch timing (bench.py roofline leg): HIP events around every contraction launch
     struct ProfRec { hipEvent_t a, b; int klass; double flops; int M, N, K, taps; };
@@ -617,6 +622,9 @@ struct pd_engine {
     static GemmParams fill_gemm(const WMat& m, const Act& in, const Act& out, const GemmCall& c);
     GemmPlan plan_gemm(const GemmParams& p, const WMat& m, const GemmCall& c, bool allow_splitk = true) const;
     int patch_tiles(const GemmParams& p) const; bool patch_unsplit(int ptiles) const;
+    int fold_upconv(WMat& m);   // (re)builds m.w_up from m.w; fold_upconvs(): for every UNet decoder Upsample conv the dispatch can take
+    int fold_upconvs();
+    bool upfold_wanted(const WMat& m) const;
     int fold_layernorms();     // (re)builds the folded weights of every transformer block after a weight change
     bool ln_dirty = true;
     int opt_ln_fuse = -1;      // -1: on in the 2-byte modes, off in the fp32-storage modes; 0 / 1: forced

@@ -72,6 +72,42 @@ int pd_op_conv2d(pd_engine* e, const float* x, const float* w, const float* bias
     return from_dev_nhwc(e, out.p, odt, y, B, Cout, Ho, Wo, copad);
 }
 
+// y = conv3x3(nearest_x2(x)) + bias [+ residual] through fold_upconv and the dispatch; an error unless the plan is the four-phase kernel
+int pd_op_conv2d_upfold(pd_engine* e, const float* x, const float* w, const float* bias, const float* residual, int B, int Cin, int H,
+                        int W, int Cout, float* y) {
+    if (!e || !x || !w || !y) { pd_set_error("null argument"); return 1; }
+    if (B < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1) { pd_set_error("pd_op_conv2d_upfold: need B, Cin, Cout, H, W >= 1"); return 1; }
+    HIP_OK(hipSetDevice(e->device));
+    TempMat guard(e);
+    ConvW c;
+    c.cin = Cin; c.cout = Cout; c.k = 3; c.stride = 1;
+    e->make_mat(c.m, Cout, Cin * 9, 9, Cin, true);
+    if (!c.m.w) { pd_set_error("allocation failed"); return 1; }
+    PD_TRY(e->upload_rows(c.m, 0, w, Cout, true));
+    if (bias) PD_TRY(e->upload_vec(c.m.bias, bias, Cout, false, 0));
+    PD_TRY(e->fold_upconv(c.m));
+    const int Ho = 2 * H, Wo = 2 * W;
+    const int cpad = c.m.cin_pad, copad = round_up(Cout, 4);
+    DevBuf in((size_t)B * H * W * cpad * dt_size(e->T)), out((size_t)B * Ho * Wo * copad * dt_size(e->T)),
+        res((size_t)B * Ho * Wo * copad * dt_size(e->S));
+    if (!in.p || !out.p || !res.p) { pd_set_error("allocation failed"); return 1; }
+    PD_TRY(to_dev_nhwc(e, x, in.p, e->T, B, Cin, H, W, cpad));
+    Act a, o, r;
+    a.p = in.p; a.B = B; a.H = H; a.W = W; a.C = cpad; a.dt = e->T;
+    o.p = out.p; o.B = B; o.H = Ho; o.W = Wo; o.C = copad; o.dt = e->T;
+    r = o; r.p = res.p; r.dt = e->S;
+    if (residual) PD_TRY(to_dev_nhwc(e, residual, res.p, e->S, B, Cout, Ho, Wo, copad));
+    GemmCall call{.ups = 1, .R = residual ? &r : nullptr};
+    PD_TRY(e->check_gemm(c.m, a, o, call));
+    if (e->plan_gemm(e->fill_gemm(c.m, a, o, call), c.m, call).family != GEMM_UPFOLD) {
+        pd_set_error("pd_op_conv2d_upfold: B %d Cin %d %dx%d Cout %d%s is not eligible for the four-phase upsample conv (mode, options, shape or epilogue)", B, Cin,
+                     H, W, Cout, residual ? " + residual" : "");
+        return 1;
+    }
+    PD_TRY(e->conv(c, a, o, call));
+    return from_dev_nhwc(e, out.p, e->T, y, B, Cout, Ho, Wo, copad);
+}
+
 // y = Downsample(x) of the KL-VAE encoder: zero row / column appended at the bottom / right, then conv3x3 stride 2 padding 0
 int pd_op_vae_downsample(pd_engine* e, const float* x, const float* w, const float* bias, int B, int C, int H, int W, float* y) {
     if (!e || !x || !w || !y) { pd_set_error("null argument"); return 1; }

@@ -263,6 +263,11 @@ int launch_conv_patch(const GemmParams& p, int prec, hipStream_t s);
 int launch_conv_patch2(const GemmParams& p, int prec, hipStream_t s);   // conv_patch2.hip: compute / loader wave specialisation (2-byte types)
 bool conv_patch4_eligible(const GemmParams& p, int prec);              // conv_patch4.hip: 4 waves per block, one per SIMD, 32x32x16 MFMAs, LDS-DMA operands (2-byte types)
 int launch_conv_patch4(const GemmParams& p, int prec, hipStream_t s);
+// conv_upfold.hip: conv3x3(nearest_x2(x)) as four 2x2-tap phase convs over the source (2-byte types, bias-only epilogue); p is the nine-tap call's
+bool conv_upfold_eligible(const GemmParams& p, int prec);
+int conv_upfold_tiles(const GemmParams& p);   // blocks of the phase launch
+int launch_conv_upfold(const GemmParams& p, const void* w_up, int prec, hipStream_t s);
+int launch_upfold_weights(const void* w, void* w_up, int dt, int N, int cin_pad, int Kpad, hipStream_t s);   // [N][9][cin_pad] -> [4][N][4][cin_pad]
 int launch_attention(const AttnParams& p, int prec, hipStream_t s);
 // T5 self-attention: softmax(Q K^T * scale + bias) V, bias[h][q][k] = relbias[h][k - q + Nk - 1] (fp32, in exp2 units: times log2 e); dh 64, Nq == Nk
 int launch_attention_bias(const AttnParams& p, const float* relbias, int prec, hipStream_t s);

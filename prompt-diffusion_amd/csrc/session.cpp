@@ -1061,6 +1061,8 @@ int pd_set_option(pd_engine* e, const char* key, int64_t value) {
     if (!strcmp(key, "patch_split_fill")) { e->opt_patch_split_fill = (int)value; return 0; }
     if (!strcmp(key, "patch_split_min")) { if (value < 1) { pd_set_error("patch_split_min must be >= 1"); return 1; } e->opt_patch_split_min = (int)value; return 0; }
     if (!strcmp(key, "patch_split_tiles")) { e->opt_patch_split_tiles = (int)value; return 0; }
+    if (!strcmp(key, "ups_fold")) { e->opt_ups_fold = value != 0; e->ln_dirty = true; return 0; }
+    if (!strcmp(key, "ups_fold_tiles")) { e->opt_ups_fold_tiles = (int)value; return 0; }
     if (!strcmp(key, "dense_tiles")) { e->opt_dense_tiles = (int)value; return 0; }
     if (!strcmp(key, "dense_k")) { e->opt_dense_k = (int)value; return 0; }
     if (!strcmp(key, "big_tile")) { e->opt_bigtile = value != 0; return 0; }
@@ -1173,6 +1175,7 @@ int64_t pd_get_stat(pd_engine* e, const char* key) {
     if (!strcmp(key, "launches")) return (int64_t)e->launches;
     if (!strcmp(key, "image_allocs")) return (int64_t)e->image_allocs;   // device allocations of pd_image_load / pd_image_store so far
     if (!strcmp(key, "gn_from_slabs")) return (int64_t)e->gn_from_slabs;
+    if (!strcmp(key, "ups_fold_launches")) return (int64_t)e->ups_fold_launches;   // of which: conv_upfold.hip's four-phase upsample conv
     if (!strcmp(key, "ring_launches")) return (int64_t)e->ring_launches;   // of which: gemm_ring.hip's persistent ring kernel
     if (!strcmp(key, "gn_kernel")) {   // which kernel the last pd_engine::groupnorm launch took
         static_assert(GN_KIND_TWO_PASS == PD_GN_TWO_PASS && GN_KIND_LDS_SLAB == PD_GN_LDS_SLAB && GN_KIND_REGISTER == PD_GN_REGISTER, "pdengine.h");
@@ -1180,7 +1183,7 @@ int64_t pd_get_stat(pd_engine* e, const char* key) {
     }
     if (!strcmp(key, "gemm_family")) {   // which kernel family the last pd_engine::gemm launch took
         static_assert(GEMM_GEMV == PD_GEMM_GEMV && GEMM_PATCH1 == PD_GEMM_PATCH1 && GEMM_PATCH2 == PD_GEMM_PATCH2 && GEMM_PATCH4 == PD_GEMM_PATCH4 &&
-                      GEMM_RING == PD_GEMM_RING && GEMM_IGEMM == PD_GEMM_IGEMM, "pdengine.h");
+                      GEMM_RING == PD_GEMM_RING && GEMM_IGEMM == PD_GEMM_IGEMM && GEMM_UPFOLD == PD_GEMM_UPFOLD, "pdengine.h");
         return (int64_t)e->gemm_family;
     }
     if (!strcmp(key, "steps")) return (int64_t)e->ses.S;

@@ -213,6 +213,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     # per-op parity hooks (include/pdengine_ops.h)
     fp = C.c_void_p
     lib.pd_op_conv2d.argtypes = [C.c_void_p, fp, fp, fp, fp] + [C.c_int] * 9 + [C.c_float, C.c_int, fp]
+    if hasattr(lib, "pd_op_conv2d_upfold"):   # (an older build handed in through PDENGINE_LIB for an A/B run lacks it)
+        lib.pd_op_conv2d_upfold.argtypes = [C.c_void_p, fp, fp, fp, fp] + [C.c_int] * 5 + [fp]
     lib.pd_op_linear.argtypes = [C.c_void_p, fp, fp, fp] + [C.c_int] * 5 + [fp]
     lib.pd_op_linear_fp8.argtypes = [C.c_void_p, fp, fp, fp] + [C.c_int] * 4 + [fp]
     lib.pd_op_groupnorm.argtypes = [C.c_void_p, fp, fp, fp] + [C.c_int] * 4 + [C.c_float, C.c_int, fp]
@@ -258,7 +260,7 @@ EXPORTS = [
     "pd_make_schedule", "pd_synchronize", "pd_stream", "pd_wait_stream", "pd_set_option", "pd_get_stat", "pd_bench_conv3x3", "pd_bench_linear", "pd_text_encode", "pd_text_encode_ex", "pd_text_weights_missing",
     "pd_profile_read", "pd_profile_dump", "pd_comm_new_id", "pd_comm_init", "pd_comm_world", "pd_comm_all_gather", "pd_comm_destroy",
     "pd_sd3_configure", "pd_sd3_weights_missing", "pd_sd3_forward", "pd_sd3_control", "pd_sd3_sample", "pd_sd3_down_proj",
-    "pd_op_conv2d", "pd_op_linear", "pd_op_linear_fp8", "pd_op_groupnorm", "pd_op_layernorm", "pd_op_groupnorm_slabs", "pd_op_groupnorm_coef", "pd_op_ln_linear", "pd_op_attention", "pd_op_spatial_transformer", "pd_op_spatial_transformer_ctx", "pd_op_time_embed",
+    "pd_op_conv2d", "pd_op_conv2d_upfold", "pd_op_linear", "pd_op_linear_fp8", "pd_op_groupnorm", "pd_op_layernorm", "pd_op_groupnorm_slabs", "pd_op_groupnorm_coef", "pd_op_ln_linear", "pd_op_attention", "pd_op_spatial_transformer", "pd_op_spatial_transformer_ctx", "pd_op_time_embed",
     "pd_op_timestep_embedding_i", "pd_op_timestep_embedding_f", "pd_op_vae_downsample", "pd_read_weights", "pd_lora_add", "pd_lora_set_scales", "pd_lora_remove",
     "pd_set_freeu", "pd_get_freeu", "pd_op_freeu_concat",
     "pd_philox4x32_10", "pd_set_rng", "pd_get_rng", "pd_randn",
@@ -1198,6 +1200,20 @@ class Engine:
         self._check(self.lib.pd_op_conv2d(self._h, x.ctypes.data, w.ctypes.data, None if bb is None else bb.ctypes.data,
                                           None if rr is None else rr.ctypes.data, B, Cin, H, W, Cout, k, stride,
                                           int(upsample), int(silu), scale, int(stream_out), y.ctypes.data))
+        return y
+
+    def op_conv2d_upfold(self, x, w, b=None, residual=None):
+        """conv3x3(nearest_x2(x)) through the weight fold and the four-phase kernel (option 'ups_fold'); raises where the dispatch
+        would not take that kernel instead of falling back."""
+        x = np.ascontiguousarray(x, np.float32); w = np.ascontiguousarray(w, np.float32)
+        B, Cin, H, W = x.shape
+        Cout = w.shape[0]
+        assert w.shape == (Cout, Cin, 3, 3), w.shape
+        y = np.empty((B, Cout, 2 * H, 2 * W), np.float32)
+        bb = None if b is None else np.ascontiguousarray(b, np.float32)
+        rr = None if residual is None else np.ascontiguousarray(residual, np.float32)
+        self._check(self.lib.pd_op_conv2d_upfold(self._h, x.ctypes.data, w.ctypes.data, None if bb is None else bb.ctypes.data,
+                                                 None if rr is None else rr.ctypes.data, B, Cin, H, W, Cout, y.ctypes.data))
         return y
 
     def op_linear(self, x, w, b=None, geglu=False, a_silu=False):
