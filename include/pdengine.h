@@ -517,10 +517,15 @@ int pd_comm_destroy(pd_engine* e); /* also done by pd_engine_destroy */
  *   conv3x3 of a nearest-x2 upsampled tensor, bias only, source height and width multiples of 16 -- runs as four 2x2-tap phase
  *   convolutions over the source with folded weights, conv_upfold.hip, 4/9 of the products, when its phase grid has at least that many
  *   blocks: 1 / -1 = three quarters of the CUs, the block count at which a patch conv runs unsplit.  Not bit-identical to the nine-tap
- *   path: every folded weight is rounded once more; stat "ups_fold_launches" counts the launches that took it). */
+ *   path: every folded weight is rounded once more; stat "ups_fold_launches" counts the launches that took it),
+ *   "vae_flash" (2-byte modes: the first stage's mid-block attention on the single-head flash kernel, vae_attention.hip, instead of
+ *   the materialised [N, N] scores: -1 = per VAE -- never for the SD1.5 first stage; for SD3's VAE where the score buffers would pass 2 GiB
+ *   (past about 1100^2 pixels; below that the materialised launches measure faster) or h * w is no multiple of 8; 0 / 1 force both.  The
+ *   fp32-storage modes always materialise; stat "vae_flash_launches" counts the launches that took the kernel). */
 int pd_set_option(pd_engine* e, const char* key, int64_t value);
 /* "graph_captures" / "graph_replays" (step loops captured / replayed from a captured graph since the engine was created),
- * "workspace_bytes", "weight_bytes", "launches" (engine launches, split-K finalize passes not counted), "ring_launches" / "gn_from_slabs" / "ups_fold_launches"
+ * "workspace_bytes", "side_workspace_bytes" (the workspace of everything outside a sampling step -- first stage, HED, text encoders, SD3's VAE:
+ * it grows to the largest call so far and holds that call's intermediates, I/O staging and 64 MiB of slack), "vae_flash_launches", "weight_bytes", "launches" (engine launches, split-K finalize passes not counted), "ring_launches" / "gn_from_slabs" / "ups_fold_launches"
  * (of which: gemm_ring.hip / GroupNorm fed by split-K slabs / the four-phase upsample conv), "steps", "event_overhead_ns", "cfg_shared" (see option "cfg_share"),
  * "gn_kernel" (which kernel the engine's last GroupNorm launch took: PD_GN_TWO_PASS = gn_stats + gn_apply, PD_GN_LDS_SLAB = the
  * single LDS-slab kernel, PD_GN_REGISTER = the register-resident kernel of the 2-byte modes; 0 before the first launch.  The choice
@@ -567,6 +572,10 @@ int pd_text_weights_missing(pd_engine* e);
 
 /* Same for one Linear / conv1x1 layer ([M,K] x [N,K]^T, optional residual add) in isolation. */
 int pd_bench_linear(pd_engine* e, int32_t M, int32_t K, int32_t N, int32_t residual, int32_t iters, float* ms);
+/* The first stage's mid-block attention product alone, softmax(q k^T C^-0.5) v with one head over C channels for B samples of N tokens
+ * (N a multiple of 8) on random data: flash 1 = the single-head flash kernel, 0 = the three launches per sample through the [N, N] score
+ * buffers; ms per call over `iters` back-to-back calls, score_bytes (may be NULL) = the bytes of those buffers. */
+int pd_bench_vae_attention(pd_engine* e, int32_t B, int32_t N, int32_t C, int32_t flash, int32_t iters, float* ms, int64_t* score_bytes);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * SD3 / MMDiT variant of the path.  Replaces, per denoising step,
@@ -695,6 +704,35 @@ int pd_sd3_text_encoder(pd_engine* e, int32_t which, const int32_t* ids, int32_t
 /* T5Attention._relative_position_bucket (bidirectional) on the host: out[i] = bucket of relative position (key - query) = i - (L - 1)
  * for i in [0, 2 L - 1).  Needs no engine and no GPU. */
 int pd_t5_relative_buckets(int32_t L, int32_t num_buckets, int32_t max_distance, int32_t* out);
+
+/* ---- SD3's VAE (diffusers AutoencoderKL: 16 latent channels, no quant convs, scaling and shift) ----
+ * The three places the reference's SD3 pipeline calls its VAE (promptdiffusioncontrolnetpipeline_sd3.py): vae.encode(control_image)
+ * .latent_dist.sample(), then (z - shift) * scaling (:1132-1133); the same on the down-projected example pair (:1112-1115); and
+ * vae.decode(latents / scaling + shift) (:1271-1273).  Same layers as the SD1.5 first stage (pd_vae_decode / pd_vae_encode), with a
+ * description of its own; parameters are registered under diffusers' names, prefix "vae." (encoder.down_blocks.{i}.resnets.{j}.*,
+ * {encoder,decoder}.mid_block.{resnets.{0,1},attentions.0.{group_norm,to_q,to_k,to_v,to_out.0}}, decoder.up_blocks.{i}.*,
+ * conv_norm_out, ...; to_q / to_k / to_v / to_out.0 are Linear [C, C]).  In the 2-byte modes the mid-block attention runs the single-head flash
+ * kernel (vae_attention.hip) where its score buffers would pass 2 GiB or h * w is no multiple of 8, and whenever option "vae_flash" is 1. */
+typedef struct pd_sd3_vae_config {
+    int32_t ch, num_levels, ch_mult[PD_MAX_LEVELS], num_res_blocks, z_channels, out_ch;   /* 128, 4, {1,2,4,4}, 2, 16, 3 */
+    int32_t encoder;                        /* 0: decoder only */
+    int32_t quant_conv, post_quant_conv;    /* 0 for SD3 (use_quant_conv / use_post_quant_conv false) */
+    double scaling_factor, shift_factor;    /* 1.5305, 0.0609 */
+} pd_sd3_vae_config;
+/* Registers the VAE's parameters (registry group of their own) on an existing engine and allocates their weights.  Once per engine; an
+ * engine that never calls it is unchanged. */
+int pd_sd3_vae_configure(pd_engine* e, const pd_sd3_vae_config* cfg);
+int pd_sd3_vae_weights_missing(pd_engine* e);
+/* sizeof(pd_sd3_vae_config) and the byte offsets of scaling_factor / shift_factor as this library was compiled: what a binding checks
+ * its own struct against.  Needs no engine and no GPU. */
+int pd_sd3_vae_config_layout(int32_t* size, int32_t* off_scaling, int32_t* off_shift);
+/* latents [B, z, h, w] -> images [B, out_ch, 8h, 8w] (2^(num_levels - 1) per side), fp32 in `mem` space: decode(latents / scaling +
+ * shift); raw != 0: decode(latents).  Any h, w >= 1 in the 2-byte modes; the fp32-storage modes (and option "vae_flash" 0) need h * w a multiple of 8. */
+int pd_sd3_vae_decode(pd_engine* e, const float* latents, int32_t B, int32_t h, int32_t w, int32_t mem, int32_t raw, float* images);
+/* images [B, out_ch, H, W] (H, W multiples of 8) -> PD_VAE_MEAN / PD_VAE_SAMPLE: (z - shift) * scaling, [B, z, H/8, W/8] (raw != 0: z
+ * itself); PD_VAE_MOMENTS: the unscaled [B, 2z, H/8, W/8] moments.  noise as in pd_vae_encode (NULL with PD_VAE_SAMPLE: the seeded draw). */
+int pd_sd3_vae_encode(pd_engine* e, const float* images, int32_t B, int32_t H, int32_t W, int32_t mem, int32_t what, const float* noise,
+                      int32_t raw, float* out);
 
 #ifdef __cplusplus
 }

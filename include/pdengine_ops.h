@@ -11,6 +11,7 @@
  *   pd_op_groupnorm_slabs / pd_op_groupnorm_coef  the derived forms of GroupNorm32 (split-K slab input; {scale, shift} coefficients)
  *   pd_op_ln_linear  nn.LayerNorm -> nn.Linear as a kernel pair and as the folded GEMM   attention.py:271-275
  *   pd_op_attention  softmax(q k^T dh^-0.5) v, heads from the engine config        attention.py:171-193
+ *   pd_op_vae_attention  the first stage's single-head attention (flash / materialised)   ldm/modules/diffusionmodules/model.py:171-202
  *   pd_op_spatial_transformer  one SpatialTransformer block of the loaded networks  attention.py:271-275,321-340
  *   pd_op_time_embed timestep_embedding + the time_embed MLP of a loaded network    util.py:154-174, openaimodel.py:526-531
  *   pd_op_vae_downsample  the KL-VAE encoder's Downsample (asymmetric pad)          ldm/modules/diffusionmodules/model.py:68-88
@@ -65,6 +66,11 @@ int pd_op_ln_linear(pd_engine* e, int mode, const float* h, const float* x, cons
                     const float* gamma, const float* beta, const float* w, const float* bias, int M, int K, int N, float* h_out, float* y,
                     int* stats_parts, float* row_stats);
 int pd_op_attention(pd_engine* e, const float* q, const float* k, const float* v, int B, int Nq, int Nk, int C, float* o);
+/* softmax(q k^T C^-0.5) v with one head over all C channels -- the first stage's AttnBlock (model.py:171-202) between its projections;
+ * q, k, v, o [B, N, C].  Option "vae_flash" 1: the single-head flash kernel (vae_attention.hip; 2-byte modes, C = 128 or 512, any
+ * N >= 1 -- another mode or C is an error); 0 / -1: the materialised path (score GEMM, row softmax, value GEMM per sample; every mode,
+ * N a multiple of 8). */
+int pd_op_vae_attention(pd_engine* e, const float* q, const float* k, const float* v, int B, int N, int C, float* o);
 /* SpatialTransformer.forward of the block whose weights were loaded under `prefix` (reference state-dict prefix ending in '.'),
  * x [B, C, H, W], context [B, context_len, context_dim], y [B, C, H, W]; the same code path as a sampling step (2-byte modes at
  * 320 channels: self-attention + the fused tail kernel). */

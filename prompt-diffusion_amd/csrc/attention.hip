@@ -16,6 +16,7 @@
 // the O^T rescale uses the lane's own alpha.
 #include "pd_common.h"
 #include "pd_mma.h"
+#include "attn_vt.h"
 #include <type_traits>
 
 namespace {
@@ -27,9 +28,8 @@ constexpr int TK = 64;  // keys per tile
 // registers) are 16 contiguous bytes, with the 16-byte chunks XOR-swizzled like the GEMM's operand rows: one conflict-free
 // ds_read_b128 per fragment.  (Round 1 read two 8-byte halves from 144-byte rows; hipcc merged them into a ds_read2_b64,
 // which is banked mod 32: 2-way conflicts, 47 % of the kernel's LDS cycles.)
-//   slot(key) = 32*(key/32) + 8*((key%16)/4) + 4*((key%32)/16) + key%4        (a 2-byte element index inside the row)
+//   slot(key): vt_slot of attn_vt.h (a 2-byte element index inside the row)
 constexpr int VT_ROW = 128;
-__device__ __forceinline__ int vt_slot(int k0) { return (k0 & ~31) + (((k0 & 15) >> 2) << 3) + (((k0 & 31) >> 4) << 2); }
 __device__ __forceinline__ int vt_chunk(int row, int chunk) { return row * VT_ROW + (((chunk ^ (row >> 1)) & 7) << 4); }
 // a staged 16-byte chunk = 8 consecutive keys starting at k0 (multiple of 8) lands as two 8-byte halves
 __device__ __forceinline__ void vt_store(char* tile, int row, int k0, const uint4& v) {

@@ -16,14 +16,15 @@ inline int nblocks(long long n, int per = TPB, int cap = 65535 * 16) {
 }
 
 __global__ void nchw_to_nhwc_kernel(const float* __restrict__ in, void* __restrict__ out, int out_dt, int B, int C,
-                                    int HW, int Cpad, float scale) {
+                                    int HW, int Cpad, float scale, float shift) {
     const long long total = (long long)B * HW * Cpad;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const int c = (int)(i % Cpad);
         const long long bp = i / Cpad;
         const int p = (int)(bp % HW);
         const int b = (int)(bp / HW);
-        const float v = c < C ? scale * in[((long long)b * C + c) * HW + p] : 0.f;
+        float v = c < C ? scale * in[((long long)b * C + c) * HW + p] : 0.f;
+        if (shift != 0.f && c < C) v += shift;   // (shift 0 keeps the product's own bits, -0 included)
         if (out_dt == DT_F32) reinterpret_cast<float*>(out)[i] = v;
         else reinterpret_cast<uint16_t*>(out)[i] = cvt16_rt(v, out_dt);
     }
@@ -89,7 +90,7 @@ __global__ void nhwc_to_nchw_kernel(const void* __restrict__ in, int in_dt, floa
 // One thread per output element, fp32 arithmetic throughout; reads of `mom` are strided by Cpad (8 floats = 32 bytes for the
 // SD VAE), the NCHW writes and noise reads are contiguous.  Tiny next to the encoder's convolutions.
 __global__ void vae_posterior_kernel(const void* __restrict__ mom, int mom_dt, int Cpad, const float* __restrict__ noise,
-                                     float* __restrict__ out, int B, int z, int HW, int what, float scale, PdRng rng) {
+                                     float* __restrict__ out, int B, int z, int HW, int what, float scale, float shift, PdRng rng) {
     const int Cout = what == PD_VAE_MOMENTS ? 2 * z : z;
     const long long total = (long long)B * Cout * HW;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
@@ -110,9 +111,9 @@ __global__ void vae_posterior_kernel(const void* __restrict__ mom, int mom_dt, i
             const float sd = expf(0.5f * lv);   // std = exp(0.5 * logvar) (distributions.py:28-29)
             // the caller's draw, or the engine's own at (PD_RNG_VAE, draw 0)
             const float nz = noise ? noise[((long long)b * z + c) * HW + p] : pd_rng_normal(rng, PD_RNG_VAE, 0u, (uint32_t)b, (long long)c * HW + p);
-            v = scale * (m + sd * nz);
+            v = scale * ((m + sd * nz) - shift);   // x - 0 is x, bit for bit
         } else {
-            v = scale * m;
+            v = scale * (m - shift);
         }
         out[i] = v;
     }
@@ -194,9 +195,9 @@ __global__ void fill_random_kernel(void* __restrict__ p, int dt, long long n, fl
 
 #define CHECK_LAUNCH() return hipGetLastError() == hipSuccess ? 0 : 1
 
-int launch_nchw_to_nhwc(const float* in, void* out, int out_dt, int B, int C, int H, int W, int Cpad, hipStream_t s, float scale) {
+int launch_nchw_to_nhwc(const float* in, void* out, int out_dt, int B, int C, int H, int W, int Cpad, hipStream_t s, float scale, float shift) {
     const long long n = (long long)B * H * W * Cpad;
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(nblocks(n)), dim3(TPB), 0, s, in, out, out_dt, B, C, H * W, Cpad, scale);
+    hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(nblocks(n)), dim3(TPB), 0, s, in, out, out_dt, B, C, H * W, Cpad, scale, shift);
     CHECK_LAUNCH();
 }
 int launch_softmax_rows(const float* in, void* out, int out_dt, int rows, int n, hipStream_t s) {
@@ -215,11 +216,11 @@ int launch_nhwc_to_nchw(const void* in, int in_dt, float* out, int B, int C, int
     CHECK_LAUNCH();
 }
 int launch_vae_posterior(const void* mom, int mom_dt, int Cpad, const float* noise, float* out, int B, int z, int HW, int what, float scale,
-                         hipStream_t s, const uint32_t* rng_state) {
+                         hipStream_t s, const uint32_t* rng_state, float shift) {
     if (Cpad < 2 * z || (what == PD_VAE_SAMPLE && !noise && !rng_state) || (what != PD_VAE_MEAN && what != PD_VAE_SAMPLE && what != PD_VAE_MOMENTS)) return 1;
     const long long n = (long long)B * (what == PD_VAE_MOMENTS ? 2 * z : z) * HW;
     hipLaunchKernelGGL(vae_posterior_kernel, dim3(nblocks(n)), dim3(TPB), 0, s, mom, mom_dt, Cpad, noise, out, B, z, HW, what, scale,
-                       PdRng{rng_state});
+                       shift, PdRng{rng_state});
     CHECK_LAUNCH();
 }
 int launch_cast_rows(const float* in, void* out, int out_dt, long long rows, int C, int Cpad, hipStream_t s) {

@@ -147,8 +147,19 @@ struct VaeLevel {
     ConvW upconv;
     int ch = 0;
 };
+// What a first stage is made of (the SD1.5 instance is filled from pd_config, SD3's from pd_sd3_vae_config)
+struct VaeDesc {
+    int z = 0, zpad = 0;                       // latent channels; round_up(z, 8): the channel width of the latent activations
+    int ch = 0, num_levels = 0, ch_mult[PD_MAX_LEVELS] = {0}, num_res_blocks = 0, out_ch = 0;
+    bool quant = true;                         // post_quant_conv (decoder) / quant_conv (encoder) present
+    double scaling = 1.0, shift = 0.0;         // decode(z / scaling + shift); encode: (z - shift) * scaling
+    bool flash_auto = false;                   // option "vae_flash" at -1: false = never, true = where the score buffers pass 2 GiB (vae_flash_on)
+    bool diffusers = false;                    // parameter names: diffusers AutoencoderKL instead of ldm
+    int group = 0, enc_group = 0;              // WeightGroup of the decoder / the encoder
+};
 struct VaeW {
     bool built = false;
+    VaeDesc d;
     ConvW post_quant, conv_in, conv_out;
     ResW mid1, mid2;
     VaeAttnW attn;
@@ -165,6 +176,7 @@ struct VaeEncLevel {
 };
 struct VaeEncW {
     bool built = false;
+    VaeDesc d;
     ConvW conv_in, conv_out, quant;
     std::vector<VaeEncLevel> levels;
     ResW mid1, mid2;
@@ -246,6 +258,8 @@ enum WeightGroup {
     GROUP_VAE_ENCODER = 4,
     GROUP_HED = 5,
     GROUP_SD3_TEXT = 6,      // SD3 text encoders
+    GROUP_SD3_VAE = 7,       // SD3's VAE decoder
+    GROUP_SD3_VAE_ENCODER = 8,
 };
 
 struct Param {
@@ -503,13 +517,31 @@ struct pd_engine {
     void build_st(const std::string& prefix, STW& s, int ch, NetW& net);
     void build_encoder(const std::string& prefix, NetW& net);
     void build_middle(const std::string& prefix, NetW& net);
-    void build_vres(const std::string& prefix, ResW& r, int cin, int cout);
-    void build_vattn(const std::string& prefix, VaeAttnW& a, int C);
-    void build_vae();
+    void build_vres(const std::string& prefix, ResW& r, int cin, int cout, bool diffusers = false);
+    void build_vattn(const std::string& prefix, VaeAttnW& a, int C, bool diffusers = false);
+    void build_vae();           // the SD1.5 first stage from pd_config: fills vae.d, then build_vae_decoder
     void build_vae_encoder();
-    int vae_forward(const float* latents_dev, int B, int h, int w, float* out_dev);
-    int vae_encoder_forward(const float* images_dev, int B, int H, int W, int what, const float* noise_dev, float* out_dev);
-    int vae_attention(const VaeAttnW& a, const Act& x, Act& out);
+    void build_vae_decoder(VaeW& v, const std::string& prefix);      // v.d filled by the caller; prefix "first_stage_model." / "vae."
+    void build_vae_encoder(VaeEncW& v, const std::string& prefix);
+    // SD3's VAE (sd3_vae.cpp, pd_sd3_vae_configure): the same layers under a description of its own
+    VaeW sd3_vae;
+    VaeEncW sd3_vae_enc;
+    int opt_vae_flash = -1;          // option "vae_flash": -1 per VAE (VaeDesc::flash_auto), 0 / 1 forced; 2-byte modes only
+    long long vae_flash_launches = 0;
+    bool vae_flash_on(const VaeDesc& d, int C, long long N) const;   // N: tokens per sample
+    // scale / shift: what the layout kernel applies to the latents (decode) or the posterior kernel to z (encode)
+    int vae_forward(VaeW& v, const float* latents_dev, int B, int h, int w, float* out_dev, float scale, float shift);
+    int vae_encoder_forward(VaeEncW& v, const float* images_dev, int B, int H, int W, int what, const float* noise_dev, float* out_dev, float scale,
+                            float shift);
+    int vae_attention(const VaeAttnW& a, const VaeDesc& d, const Act& x, Act& out);
+    // softmax(q k^T C^-0.5) v of B samples: q | k rows [B][N][ld] (k = q + C elements), vt [B][C][npad], att [B][N][C], all in T.  flash: one
+    // launch of vae_attention.hip, any N; else three launches per sample through sc [N][N] fp32 and pr [N][npad] T (N a multiple of 8,
+    // npad = round_up(N, 64), the pad columns of vt and pr zero)
+    int vae_attn_product(const void* qk, int ld, const void* vt, int npad, void* att, int B, int N, int C, bool flash, float* sc, void* pr);
+    // decode / encode behind the C ABI, shared by pd_vae_* and pd_sd3_vae_*
+    int vae_decode_call(VaeW& v, const float* latents, int B, int h, int w, int mem, float scale, float shift, float* images_out);
+    int vae_encode_call(VaeEncW& v, const float* images, int B, int H, int W, int mem, int what, const float* noise, float scale, float shift,
+                        float* out);
     // Everything that runs outside a sampling step (first stage, HED, text encoders): `sizing` (a dry pass of the forward) measures the
     // workspace, which is the ControlNet context's (arena2, idle outside a sampling step) grown to that plus io_bytes if needed; then `run`
     // enqueues for real on the main stream.  `what` names the caller in the allocation-failure message.

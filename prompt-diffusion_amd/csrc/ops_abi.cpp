@@ -438,6 +438,44 @@ int pd_op_attention(pd_engine* e, const float* q, const float* k, const float* v
     return 0;
 }
 
+// softmax(q k^T C^-0.5) v with ONE head over all C channels (the first stage's AttnBlock); q, k, v, o [B, N, C] fp32.  Runs what
+// pd_engine::vae_attention runs between its two projections: vae_attention.hip where option "vae_flash" is 1 (2-byte modes, C 128 / 512:
+// anything else is an error, not a fall-back), the three-launch materialised path where it is 0 or -1 (N a multiple of 8)
+int pd_op_vae_attention(pd_engine* e, const float* q, const float* k, const float* v, int B, int N, int C, float* o) {
+    if (!e || !q || !k || !v || !o) { pd_set_error("null argument"); return 1; }
+    if (B < 1 || N < 1 || C < 8 || C % 8) { pd_set_error("pd_op_vae_attention: need B, N >= 1 and C a multiple of 8"); return 1; }
+    HIP_OK(hipSetDevice(e->device));
+    const bool flash = e->opt_vae_flash > 0;
+    if (flash && (e->f32 || !vae_attention_eligible(e->T, C))) {
+        pd_set_error("pd_op_vae_attention: the flash kernel takes the 2-byte modes at C = 128 or 512 (got C = %d)", C);
+        return 1;
+    }
+    if (!flash && N % 8) { pd_set_error("pd_op_vae_attention: the materialised path needs N a multiple of 8 (got %d)", N); return 1; }
+    const int npad = flash ? round_up(N, 8) : round_up(N, 64);
+    const size_t eb = dt_size(e->T);
+    // q | k interleaved per token like the fused projection's output [B][N][2C]; V transposed and zero-padded [B][C][npad]
+    std::vector<float> qk((size_t)B * N * 2 * C), vt((size_t)B * C * npad, 0.f);
+    for (size_t r = 0; r < (size_t)B * N; ++r) {
+        memcpy(&qk[r * 2 * C], q + r * C, (size_t)C * 4);
+        memcpy(&qk[r * 2 * C + C], k + r * C, (size_t)C * 4);
+    }
+    for (int b = 0; b < B; ++b)
+        for (int n = 0; n < N; ++n)
+            for (int c = 0; c < C; ++c) vt[((size_t)b * C + c) * npad + n] = v[((size_t)b * N + n) * C + c];
+    DevBuf tqk(qk.size() * 4), tv(vt.size() * 4), dqk(qk.size() * eb), dv(vt.size() * eb), dout((size_t)B * N * C * eb), fo((size_t)B * N * C * 4);
+    DevBuf sc(flash ? 0 : (size_t)N * N * 4), pr(flash ? 0 : (size_t)N * npad * eb);   // (DevBuf zero-fills: the pad columns of pr)
+    if (!tqk.p || !tv.p || !dqk.p || !dv.p || !dout.p || !fo.p || !sc.p || !pr.p) { pd_set_error("allocation failed"); return 1; }
+    HIP_OK(hipMemcpy(tqk.p, qk.data(), qk.size() * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(tv.p, vt.data(), vt.size() * 4, hipMemcpyHostToDevice));
+    if (launch_cast_rows(reinterpret_cast<const float*>(tqk.p), dqk.p, e->T, (long long)B * N, 2 * C, 2 * C, e->stream)) return 1;
+    if (launch_cast_rows(reinterpret_cast<const float*>(tv.p), dv.p, e->T, (long long)B * C, npad, npad, e->stream)) return 1;
+    PD_TRY(e->vae_attn_product(dqk.p, 2 * C, dv.p, npad, dout.p, B, N, C, flash, reinterpret_cast<float*>(sc.p), pr.p));
+    if (launch_nhwc_to_nchw(dout.p, e->T, reinterpret_cast<float*>(fo.p), 1, 1, 1, B * N * C, 1, 1.f, e->stream)) return 1;
+    HIP_OK(hipStreamSynchronize(e->stream));
+    HIP_OK(hipMemcpy(o, fo.p, (size_t)B * N * C * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // One whole SpatialTransformer block of the engine's own networks (GroupNorm eps 1e-6, proj_in, BasicTransformerBlock, proj_out, + x;
 // attention.py:321-340 and :271-275) with the weights loaded under `prefix` (e.g. "model.diffusion_model.input_blocks.1.1.") on
 // x [B, C, H, W] and context [B, context_len, context_dim], through exactly the code path a sampling step takes -- including the fused

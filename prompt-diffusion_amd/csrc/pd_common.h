@@ -269,6 +269,18 @@ int conv_upfold_tiles(const GemmParams& p);   // blocks of the phase launch
 int launch_conv_upfold(const GemmParams& p, const void* w_up, int prec, hipStream_t s);
 int launch_upfold_weights(const void* w, void* w_up, int dt, int N, int cin_pad, int Kpad, hipStream_t s);   // [N][9][cin_pad] -> [4][N][4][cin_pad]
 int launch_attention(const AttnParams& p, int prec, hipStream_t s);
+// vae_attention.hip: softmax(Q K^T * scale) V with one head over all C channels (the first stage's AttnBlock), C = 128 / 512, 2-byte modes.
+// Q, K [B][N][..] token-major (ldq / ldk elements between tokens), VT [B][C][vt_ld] with vt_ld >= round_up(N, 8), O [B][N][ldo]; *_bs:
+// elements between samples.  Any N >= 1.  One launch for the batch.  Returns 2 for a (mode, C) that has no instantiation.
+struct VaeAttnParams {
+    const void* Q; const void* K; const void* VT; void* O;
+    int ldq, ldk, ldo, vt_ld;
+    long long q_bs, k_bs, vt_bs, o_bs;
+    int B, N, C;
+    float scale;
+};
+bool vae_attention_eligible(int prec, int C);
+int launch_vae_attention(const VaeAttnParams& p, int prec, hipStream_t s);
 // T5 self-attention: softmax(Q K^T * scale + bias) V, bias[h][q][k] = relbias[h][k - q + Nk - 1] (fp32, in exp2 units: times log2 e); dh 64, Nq == Nk
 int launch_attention_bias(const AttnParams& p, const float* relbias, int prec, hipStream_t s);
 // st_tail.hip: everything after the self-attention product of a 320-channel SpatialTransformer block in one kernel (attn1.to_out +
@@ -316,8 +328,9 @@ int launch_ln_fold(const void* W, void* Wout, int dt, int N, int K, int Kpad, co
                    float* colsum, float* bias_out, hipStream_t s);
 int launch_layernorm(const void* x, int x_dt, void* y, int y_dt, const float* gamma, const float* beta,
                      int rows, int C, float eps, hipStream_t s);
+// out[b][p][c] = scale * in[b][c][p] + shift for c < C, 0 for the pad channels
 int launch_nchw_to_nhwc(const float* in, void* out, int out_dt, int B, int C, int H, int W, int Cpad, hipStream_t s,
-                        float scale = 1.0f);
+                        float scale = 1.0f, float shift = 0.0f);
 int launch_softmax_rows(const float* in, void* out, int out_dt, int rows, int n, hipStream_t s);
 // out[b,l,:] = tok[ids[b,l]] + pos[l]  (CLIP text embeddings); tables are [rows][ld] in dtype dt
 int launch_embed_tokens(const int* ids, const void* tok, int tok_ld, const void* pos, int pos_ld, int dt, void* out, int out_dt,
@@ -399,9 +412,10 @@ int launch_lora_merge(int dt, void* W, const void* W0, int rows, int row_off, in
 // DiagonalGaussianDistribution of the first-stage encoder (distributions.py:24-62) from quant_conv's NHWC output `mom` (dtype mom_dt,
 // Cpad >= 2 z channels: mean 0..z-1, logvar z..2z-1) into caller-layout fp32 NCHW: what = PD_VAE_MEAN: scale * mean,
 // PD_VAE_SAMPLE: scale * (mean + exp(0.5 clamp(logvar, -30, 20)) * noise[B, z, HW]), PD_VAE_MOMENTS: the raw [B, 2z, HW] moments
-// noise null with PD_VAE_SAMPLE: the seeded normals at (PD_RNG_VAE, draw 0) from rng_state
+// noise null with PD_VAE_SAMPLE: the seeded normals at (PD_RNG_VAE, draw 0) from rng_state.  shift: MEAN and SAMPLE become
+// scale * (x - shift), SD3's (z - shift_factor) * scaling_factor
 int launch_vae_posterior(const void* mom, int mom_dt, int Cpad, const float* noise, float* out, int B, int z, int HW, int what, float scale,
-                         hipStream_t s, const uint32_t* rng_state = nullptr);
+                         hipStream_t s, const uint32_t* rng_state = nullptr, float shift = 0.0f);
 // hed.hip: the element-wise kernels of the HED edge detector (hed.cpp)
 // images [B][3][H][W] fp32 RGB in [0, 1] -> out [B][H][W][Cpad] in out_dt: channel c < 3 = image channel 2 - c (BGR) * 255 - the VGG mean of
 // channel c, in fp32, rounded once; channels >= 3 zero.  Cpad a multiple of 4

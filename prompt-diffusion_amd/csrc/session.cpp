@@ -1062,6 +1062,7 @@ int pd_set_option(pd_engine* e, const char* key, int64_t value) {
     if (!strcmp(key, "patch_split_min")) { if (value < 1) { pd_set_error("patch_split_min must be >= 1"); return 1; } e->opt_patch_split_min = (int)value; return 0; }
     if (!strcmp(key, "patch_split_tiles")) { e->opt_patch_split_tiles = (int)value; return 0; }
     if (!strcmp(key, "ups_fold")) { e->opt_ups_fold = value != 0; e->ln_dirty = true; return 0; }
+    if (!strcmp(key, "vae_flash")) { e->opt_vae_flash = value < 0 ? -1 : value != 0; return 0; }
     if (!strcmp(key, "ups_fold_tiles")) { e->opt_ups_fold_tiles = (int)value; return 0; }
     if (!strcmp(key, "dense_tiles")) { e->opt_dense_tiles = (int)value; return 0; }
     if (!strcmp(key, "dense_k")) { e->opt_dense_k = (int)value; return 0; }
@@ -1171,10 +1172,12 @@ int64_t pd_get_stat(pd_engine* e, const char* key) {
     if (!strcmp(key, "graph_captures")) return (int64_t)e->graph_captures;
     if (!strcmp(key, "graph_replays")) return (int64_t)e->graph_replays;
     if (!strcmp(key, "workspace_bytes")) return (int64_t)e->arena.cap;
+    if (!strcmp(key, "side_workspace_bytes")) return (int64_t)e->arena2.cap;   // what the first stage / HED / text encoders run in (in_side_workspace)
     if (!strcmp(key, "weight_bytes")) return (int64_t)e->weight_bytes;
     if (!strcmp(key, "launches")) return (int64_t)e->launches;
     if (!strcmp(key, "image_allocs")) return (int64_t)e->image_allocs;   // device allocations of pd_image_load / pd_image_store so far
     if (!strcmp(key, "gn_from_slabs")) return (int64_t)e->gn_from_slabs;
+    if (!strcmp(key, "vae_flash_launches")) return (int64_t)e->vae_flash_launches;   // of which: vae_attention.hip
     if (!strcmp(key, "ups_fold_launches")) return (int64_t)e->ups_fold_launches;   // of which: conv_upfold.hip's four-phase upsample conv
     if (!strcmp(key, "ring_launches")) return (int64_t)e->ring_launches;   // of which: gemm_ring.hip's persistent ring kernel
     if (!strcmp(key, "gn_kernel")) {   // which kernel the last pd_engine::groupnorm launch took
@@ -1325,4 +1328,47 @@ int pd_bench_linear(pd_engine* e, int32_t M, int32_t K, int32_t N, int32_t resid
     return r;
 }
 
+
+// The first stage's mid-block attention product alone (pd_engine::vae_attn_product) on random q | k [B][N][2C] and V^T: `iters` back-to-back
+// calls between two events.  flash 1: vae_attention.hip; 0: the three launches per sample through the [N, N] score buffers, whose bytes come
+// back in score_bytes (0 for the flash kernel)
+int pd_bench_vae_attention(pd_engine* e, int32_t B, int32_t N, int32_t C, int32_t flash, int32_t iters, float* ms, int64_t* score_bytes) {
+    if (!e || !ms || iters < 1 || B < 1 || N < 8 || N % 8 || C < 8 || C % 8) { pd_set_error("bad argument"); return 1; }
+    if (flash && (e->f32 || !vae_attention_eligible(e->T, C))) { pd_set_error("pd_bench_vae_attention: no flash kernel for this mode / C = %d", C); return 1; }
+    HIP_OK(hipSetDevice(e->device));
+    const size_t eb = dt_size(e->T);
+    const int npad = flash ? N : (N + 63) / 64 * 64;
+    const size_t n_sc = flash ? 0 : (size_t)N * N * sizeof(float), n_pr = flash ? 0 : (size_t)N * npad * eb;
+    void *qk = nullptr, *vt = nullptr, *att = nullptr, *sc = nullptr, *pr = nullptr;
+    HIP_OK(hipMalloc(&qk, (size_t)B * N * 2 * C * eb));
+    HIP_OK(hipMalloc(&vt, (size_t)B * C * npad * eb));
+    HIP_OK(hipMalloc(&att, (size_t)B * N * C * eb));
+    if (!flash) {
+        HIP_OK(hipMalloc(&sc, n_sc));
+        HIP_OK(hipMalloc(&pr, n_pr));
+        HIP_OK(hipMemsetAsync(pr, 0, n_pr, e->stream));
+    }
+    HIP_OK(hipMemsetAsync(vt, 0, (size_t)B * C * npad * eb, e->stream));
+    launch_fill_random(qk, e->T, (long long)B * N * 2 * C, 1.f, 0.f, 1, e->stream);
+    launch_fill_random(vt, e->T, (long long)B * C * N, 1.f, 0.f, 2, e->stream);   // (npad == N unless N is no multiple of 64: then rows interleave, still finite)
+    int r = 0;
+    for (int i = 0; i < 3 && !r; ++i) r = e->vae_attn_product(qk, 2 * C, vt, npad, att, B, N, C, flash != 0, reinterpret_cast<float*>(sc), pr);
+    hipEvent_t e0, e1;
+    HIP_OK(hipEventCreate(&e0));
+    HIP_OK(hipEventCreate(&e1));
+    HIP_OK(hipEventRecord(e0, e->stream));
+    for (int i = 0; i < iters && !r; ++i) r = e->vae_attn_product(qk, 2 * C, vt, npad, att, B, N, C, flash != 0, reinterpret_cast<float*>(sc), pr);
+    HIP_OK(hipEventRecord(e1, e->stream));
+    HIP_OK(hipEventSynchronize(e1));
+    float t = 0.f;
+    HIP_OK(hipEventElapsedTime(&t, e0, e1));
+    *ms = t / (float)iters;
+    if (score_bytes) *score_bytes = (int64_t)(n_sc + n_pr);
+    hipEventDestroy(e0);
+    hipEventDestroy(e1);
+    hipFree(qk); hipFree(vt); hipFree(att);
+    if (sc) hipFree(sc);
+    if (pr) hipFree(pr);
+    return r;
+}
 }  // extern "C"

@@ -13,7 +13,7 @@
 
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
-void pd_engine::build_vres(const std::string& prefix, ResW& r, int cin, int cout) {
+void pd_engine::build_vres(const std::string& prefix, ResW& r, int cin, int cout, bool diffusers) {
     r.cin = cin;
     r.cout = cout;
     r.eps = 1e-6f;
@@ -24,41 +24,69 @@ void pd_engine::build_vres(const std::string& prefix, ResW& r, int cin, int cout
     reg_vec(prefix + "norm2.bias", cout, &r.gn2_b, 'e');
     build_conv(prefix + "conv2.", r.conv2, cout, cout, 3, 1);
     r.has_skip = cin != cout;
-    if (r.has_skip) build_conv(prefix + "nin_shortcut.", r.skip, cin, cout, 1, 1);
+    if (r.has_skip) build_conv(prefix + (diffusers ? "conv_shortcut." : "nin_shortcut."), r.skip, cin, cout, 1, 1);
 }
 
-void pd_engine::build_vattn(const std::string& prefix, VaeAttnW& a, int C) {
+// diffusers' Attention keeps ldm's four 1x1 convs as Linear layers: the same rows, shape [C, C] instead of [C, C, 1, 1]
+void pd_engine::build_vattn(const std::string& prefix, VaeAttnW& a, int C, bool diffusers) {
     a.C = C;
-    reg_vec(prefix + "norm.weight", C, &a.g, 'g');
-    reg_vec(prefix + "norm.bias", C, &a.b, 'e');
+    reg_vec(prefix + (diffusers ? "group_norm.weight" : "norm.weight"), C, &a.g, 'g');
+    reg_vec(prefix + (diffusers ? "group_norm.bias" : "norm.bias"), C, &a.b, 'e');
     make_mat(a.qkv, 3 * C, C, 1, C, true);
     const char* nm[3] = {"q", "k", "v"};
+    const char* nd[3] = {"to_q", "to_k", "to_v"};
     for (int i = 0; i < 3; ++i) {
-        reg_mat(prefix + nm[i] + ".weight", {C, C, 1, 1}, &a.qkv, i * C, true);
-        reg_bias(prefix + nm[i] + ".bias", &a.qkv, i * C, C);
+        const std::string n = prefix + (diffusers ? nd[i] : nm[i]);
+        if (diffusers) reg_mat(n + ".weight", {C, C}, &a.qkv, i * C, false);
+        else reg_mat(n + ".weight", {C, C, 1, 1}, &a.qkv, i * C, true);
+        reg_bias(n + ".bias", &a.qkv, i * C, C);
     }
-    build_conv(prefix + "proj_out.", a.proj_out, C, C, 1, 1);
+    if (diffusers) {
+        ConvW& c = a.proj_out;
+        c.cin = C; c.cout = C; c.k = 1; c.stride = 1;
+        make_mat(c.m, C, C, 1, C, true);
+        reg_mat(prefix + "to_out.0.weight", {C, C}, &c.m, 0, false);
+        reg_bias(prefix + "to_out.0.bias", &c.m, 0, C);
+    } else {
+        build_conv(prefix + "proj_out.", a.proj_out, C, C, 1, 1);
+    }
 }
 
 void pd_engine::build_vae() {
     if (cfg.vae_ch <= 0) return;
-    reg_group = GROUP_VAE;
-    const std::string P = "first_stage_model.", D = P + "decoder.";
-    const int nl = cfg.vae_num_levels;
-    const int top = cfg.vae_ch * cfg.vae_ch_mult[nl - 1];
-    VaeW& v = vae;
+    VaeDesc& d = vae.d;
+    d.z = cfg.in_channels;
+    d.zpad = 8;
+    d.ch = cfg.vae_ch;
+    d.num_levels = cfg.vae_num_levels;
+    for (int i = 0; i < PD_MAX_LEVELS; ++i) d.ch_mult[i] = cfg.vae_ch_mult[i];
+    d.num_res_blocks = cfg.vae_num_res_blocks;
+    d.out_ch = cfg.vae_out_ch;
+    d.scaling = cfg.scale_factor;
+    d.group = GROUP_VAE;
+    d.enc_group = GROUP_VAE_ENCODER;
+    build_vae_decoder(vae, "first_stage_model.");
+}
+
+void pd_engine::build_vae_decoder(VaeW& v, const std::string& P) {
+    const VaeDesc& d = v.d;
+    const bool dif = d.diffusers;
+    reg_group = (WeightGroup)d.group;
+    const std::string D = P + "decoder.";
+    const int nl = d.num_levels;
+    const int top = d.ch * d.ch_mult[nl - 1];
     v.top = top;
-    build_conv(D + "conv_in.", v.conv_in, cfg.in_channels, top, 3, 1);
-    build_vres(D + "mid.block_1.", v.mid1, top, top);
-    build_vattn(D + "mid.attn_1.", v.attn, top);
-    build_vres(D + "mid.block_2.", v.mid2, top, top);
+    build_conv(D + "conv_in.", v.conv_in, d.z, top, 3, 1);
+    build_vres(D + (dif ? "mid_block.resnets.0." : "mid.block_1."), v.mid1, top, top, dif);
+    build_vattn(D + (dif ? "mid_block.attentions.0." : "mid.attn_1."), v.attn, top, dif);
+    build_vres(D + (dif ? "mid_block.resnets.1." : "mid.block_2."), v.mid2, top, top, dif);
     // parameters are registered in module order up.0 .. up.N-1; execution runs the highest level first
     std::vector<std::vector<std::pair<int, int>>> io(nl);
     std::vector<int> chs(nl);
     int block_in = top;
     for (int lvl = nl - 1; lvl >= 0; --lvl) {
-        const int block_out = cfg.vae_ch * cfg.vae_ch_mult[lvl];
-        for (int j = 0; j <= cfg.vae_num_res_blocks; ++j) {
+        const int block_out = d.ch * d.ch_mult[lvl];
+        for (int j = 0; j <= d.num_res_blocks; ++j) {
             io[lvl].push_back({block_in, block_out});
             block_in = block_out;
         }
@@ -69,16 +97,17 @@ void pd_engine::build_vae() {
         VaeLevel& L = v.levels[nl - 1 - lvl];
         L.blocks.resize(io[lvl].size());   // never resized again
         L.ch = chs[lvl];
+        // diffusers numbers the levels in execution order: up_blocks.{i} is ldm's up.{nl - 1 - i}
+        const std::string pl = dif ? D + "up_blocks." + std::to_string(nl - 1 - lvl) + "." : D + "up." + std::to_string(lvl) + ".";
         for (size_t j = 0; j < io[lvl].size(); ++j)
-            build_vres(D + "up." + std::to_string(lvl) + ".block." + std::to_string(j) + ".", L.blocks[j], io[lvl][j].first,
-                       io[lvl][j].second);
+            build_vres(pl + (dif ? "resnets." : "block.") + std::to_string(j) + ".", L.blocks[j], io[lvl][j].first, io[lvl][j].second, dif);
         L.up = lvl != 0;
-        if (L.up) build_conv(D + "up." + std::to_string(lvl) + ".upsample.conv.", L.upconv, L.ch, L.ch, 3, 1);
+        if (L.up) build_conv(pl + (dif ? "upsamplers.0.conv." : "upsample.conv."), L.upconv, L.ch, L.ch, 3, 1);
     }
-    reg_vec(D + "norm_out.weight", cfg.vae_ch, &v.out_g, 'g');
-    reg_vec(D + "norm_out.bias", cfg.vae_ch, &v.out_b, 'e');
-    build_conv(D + "conv_out.", v.conv_out, cfg.vae_ch, cfg.vae_out_ch, 3, 1);
-    build_conv(P + "post_quant_conv.", v.post_quant, cfg.in_channels, cfg.in_channels, 1, 1);
+    reg_vec(D + (dif ? "conv_norm_out.weight" : "norm_out.weight"), d.ch, &v.out_g, 'g');
+    reg_vec(D + (dif ? "conv_norm_out.bias" : "norm_out.bias"), d.ch, &v.out_b, 'e');
+    build_conv(D + "conv_out.", v.conv_out, d.ch, d.out_ch, 3, 1);
+    if (d.quant) build_conv(P + "post_quant_conv.", v.post_quant, d.z, d.z, 1, 1);
     v.built = true;
     reg_group = GROUP_SAMPLER;
 }
@@ -87,105 +116,150 @@ void pd_engine::build_vae() {
 // Conv2d(2 z, 2 embed_dim, 1) (autoencoder.py:33).  Registered in module order under the checkpoint's names.
 void pd_engine::build_vae_encoder() {
     if (!cfg.vae_encoder || cfg.vae_ch <= 0) return;
-    reg_group = GROUP_VAE_ENCODER;
-    const std::string P = "first_stage_model.", E = P + "encoder.";
-    const int nl = cfg.vae_num_levels, z2 = 2 * cfg.in_channels;
-    VaeEncW& v = vae_enc;
-    build_conv(E + "conv_in.", v.conv_in, cfg.vae_out_ch, cfg.vae_ch, 3, 1);
+    vae_enc.d = vae.d;
+    build_vae_encoder(vae_enc, "first_stage_model.");
+}
+
+void pd_engine::build_vae_encoder(VaeEncW& v, const std::string& P) {
+    const VaeDesc& d = v.d;
+    const bool dif = d.diffusers;
+    reg_group = (WeightGroup)d.enc_group;
+    const std::string E = P + "encoder.";
+    const int nl = d.num_levels, z2 = 2 * d.z;
+    build_conv(E + "conv_in.", v.conv_in, d.out_ch, d.ch, 3, 1);
     v.levels.resize(nl);   // never resized again
-    int block_in = cfg.vae_ch;
+    int block_in = d.ch;
     for (int lvl = 0; lvl < nl; ++lvl) {
         VaeEncLevel& L = v.levels[lvl];
-        const int block_out = cfg.vae_ch * cfg.vae_ch_mult[lvl];
-        L.blocks.resize(cfg.vae_num_res_blocks);
-        const std::string pl = E + "down." + std::to_string(lvl) + ".";
-        for (int j = 0; j < cfg.vae_num_res_blocks; ++j) {
-            build_vres(pl + "block." + std::to_string(j) + ".", L.blocks[j], block_in, block_out);
+        const int block_out = d.ch * d.ch_mult[lvl];
+        L.blocks.resize(d.num_res_blocks);
+        const std::string pl = E + (dif ? "down_blocks." : "down.") + std::to_string(lvl) + ".";
+        for (int j = 0; j < d.num_res_blocks; ++j) {
+            build_vres(pl + (dif ? "resnets." : "block.") + std::to_string(j) + ".", L.blocks[j], block_in, block_out, dif);
             block_in = block_out;
         }
         L.down = lvl != nl - 1;
         if (L.down) {
-            build_conv(pl + "downsample.conv.", L.downconv, block_in, block_in, 3, 2);
+            build_conv(pl + (dif ? "downsamplers.0.conv." : "downsample.conv."), L.downconv, block_in, block_in, 3, 2);
             L.downconv.pad_shift = 1;   // F.pad(x, (0, 1, 0, 1)), padding 0 (model.py:80-85)
         }
     }
     v.top = block_in;
-    build_vres(E + "mid.block_1.", v.mid1, block_in, block_in);
-    build_vattn(E + "mid.attn_1.", v.attn, block_in);
-    build_vres(E + "mid.block_2.", v.mid2, block_in, block_in);
-    reg_vec(E + "norm_out.weight", block_in, &v.out_g, 'g');
-    reg_vec(E + "norm_out.bias", block_in, &v.out_b, 'e');
+    build_vres(E + (dif ? "mid_block.resnets.0." : "mid.block_1."), v.mid1, block_in, block_in, dif);
+    build_vattn(E + (dif ? "mid_block.attentions.0." : "mid.attn_1."), v.attn, block_in, dif);
+    build_vres(E + (dif ? "mid_block.resnets.1." : "mid.block_2."), v.mid2, block_in, block_in, dif);
+    reg_vec(E + (dif ? "conv_norm_out.weight" : "norm_out.weight"), block_in, &v.out_g, 'g');
+    reg_vec(E + (dif ? "conv_norm_out.bias" : "norm_out.bias"), block_in, &v.out_b, 'e');
     build_conv(E + "conv_out.", v.conv_out, block_in, z2, 3, 1);
-    build_conv(P + "quant_conv.", v.quant, z2, z2, 1, 1);
+    if (d.quant) build_conv(P + "quant_conv.", v.quant, z2, z2, 1, 1);
     v.built = true;
     reg_group = GROUP_SAMPLER;
 }
 
-// AttnBlock.forward: one head over all C channels, N = H*W tokens.  Scores are materialised per sample (fp32
-// [N,N]) exactly like the reference's bmm + softmax; at 512x512 that is 64 MiB per sample, once per image.
-int pd_engine::vae_attention(const VaeAttnW& v, const Act& x, Act& out) {
+// Which path the mid-block attention takes.  Measured on an MI355X at C = 512 (profiles/sd3_vae_bench.json): the flash kernel is SLOWER
+// than the three materialised launches where those fit comfortably -- 3.57 ms against 1.88 ms at N = 16384 (1024^2 images), 0.45 against
+// 0.19 at N = 4096 -- so by itself it only takes over where the score buffers (fp32 [N, N] + compute-type [N, npad]) pass 2 GiB, or where
+// the materialised GEMMs cannot run at all (N no multiple of 8).
+bool pd_engine::vae_flash_on(const VaeDesc& d, int C, long long N) const {
+    if (f32 || !vae_attention_eligible(T, C)) return false;
+    if (opt_vae_flash >= 0) return opt_vae_flash != 0;
+    if (!d.flash_auto) return false;
+    const long long score_bytes = N * N * 4 + N * ((N + 63) / 64 * 64) * (long long)dt_size(T);
+    return score_bytes > (2ll << 30) || N % 8 != 0;
+}
+
+int pd_engine::vae_attn_product(const void* qk, int ld, const void* vt, int npad, void* att, int B, int N, int C, bool flash, float* sc, void* pr) {
+    const size_t eb = dt_size(T);
+    if (flash) {
+        VaeAttnParams a{};
+        a.Q = qk; a.K = reinterpret_cast<const char*>(qk) + (size_t)C * eb; a.VT = vt; a.O = att;
+        a.ldq = ld; a.ldk = ld; a.ldo = C; a.vt_ld = npad;
+        a.q_bs = (long long)N * ld; a.k_bs = a.q_bs; a.vt_bs = (long long)C * npad; a.o_bs = (long long)N * C;
+        a.B = B; a.N = N; a.C = C; a.scale = (float)(1.0 / std::sqrt((double)C));
+        if (launch_vae_attention(a, T, stream)) { pd_set_error("vae attention: flash kernel launch failed (N %d, C %d)", N, C); return 1; }
+        ++launches;
+        ++vae_flash_launches;
+        return 0;
+    }
+    const int bke = 128 / (int)eb;
+    for (int b = 0; b < B; ++b) {
+        const char* qb = reinterpret_cast<const char*>(qk) + (size_t)b * N * ld * eb;
+        GemmParams p{};
+        // scores = (q k^T) * C^-0.5 : A = q rows, "weights" = k rows of the same buffer (row stride ld)
+        p.A = qb; p.W = qb + (size_t)C * eb; p.C = sc;
+        p.M = N; p.N = N; p.K = C; p.Kpad = round_up(C, bke); p.ldw = ld;
+        p.lda = ld; p.ldc = N; p.a_dt = T; p.c_dt = DT_F32; p.r_dt = DT_F32;
+        p.taps = 1; p.Cin = C; p.Hin = N; p.Win = 1; p.Hout = N; p.Wout = 1; p.stride = 1;
+        p.rows_per_sample = N; p.out_scale = (float)(1.0 / std::sqrt((double)C));
+        p.vt_begin = INT_MAX; p.Nout = N; p.splitk = 1; p.big_tile = N >= 1024 ? 1 : 0;
+        if (launch_gemm(p, P, stream)) { pd_set_error("vae attention: score GEMM launch failed"); return 1; }
+        if (launch_softmax_rows(sc, pr, T, N, N, stream)) { pd_set_error("vae attention: softmax launch failed"); return 1; }
+        // out = P v : A = P [N, N], "weights" = V^T [C][npad]; the K tiles past N read zeros on both sides
+        GemmParams o{};
+        o.A = pr; o.W = reinterpret_cast<const char*>(vt) + (size_t)b * C * npad * eb;
+        o.C = reinterpret_cast<char*>(att) + (size_t)b * N * C * eb;
+        o.M = N; o.N = C; o.K = N; o.Kpad = round_up(N, bke); o.ldw = npad;
+        o.lda = N; o.ldc = C; o.a_dt = T; o.c_dt = T; o.r_dt = DT_F32;
+        o.taps = 1; o.Cin = N; o.Hin = N; o.Win = 1; o.Hout = N; o.Wout = 1; o.stride = 1;
+        o.rows_per_sample = N; o.out_scale = 1.f; o.vt_begin = INT_MAX; o.Nout = C; o.splitk = 1;
+        o.big_tile = N >= 1024 ? 1 : 0;
+        if (launch_gemm(o, P, stream)) { pd_set_error("vae attention: value GEMM launch failed"); return 1; }
+        launches += 3;
+    }
+    return 0;
+}
+
+// AttnBlock.forward: one head over all C channels, N = H*W tokens.  Materialised: the scores of one sample at a time (fp32 [N,N])
+// exactly like the reference's bmm + softmax; at 512x512 that is 64 MiB, once per image.  Flash (vae_flash_on): no score buffers.
+int pd_engine::vae_attention(const VaeAttnW& v, const VaeDesc& d, const Act& x, Act& out) {
     const int B = x.B, H = x.H, W = x.W, C = v.C, N = H * W;
+    const bool flash = vae_flash_on(d, C, N);
+    if (!flash && N % 8) { pd_set_error("vae attention: the materialised path needs h * w a multiple of 8 (got %d x %d)", H, W); return 1; }
     out = new_act(B, H, W, C, S);
     const size_t mk = arena.mark();
     Act a = new_act(B, H, W, C, T);
     PD_TRY(groupnorm(x, a, v.g, v.b, 1e-6f, false));
     Act qk = new_act(B, H, W, 2 * C, T);
-    const int npad = round_up(N, 8);
+    const int npad = flash ? round_up(N, 8) : round_up(N, 64);
     Act vt = new_act(B, C, 1, npad, T);
+    if (!arena.dry && !flash && npad != N) HIP_OK(hipMemsetAsync(vt.p, 0, vt.bytes(), stream));   // the value GEMM's K tiles run to npad
     PD_TRY(gemm(v.qkv, a, qk, {.VT = vt.p, .vt_begin = 2 * C, .vt_ld = npad}));
     Act att = new_act(B, H, W, C, T);
-    float* sc = reinterpret_cast<float*>(arena.alloc((size_t)N * N * sizeof(float)));
-    void* pr = arena.alloc((size_t)N * npad * dt_size(T));
+    float* sc = nullptr;
+    void* pr = nullptr;
+    if (!flash) {
+        sc = reinterpret_cast<float*>(arena.alloc((size_t)N * N * sizeof(float)));
+        pr = arena.alloc((size_t)N * npad * dt_size(T));
+    }
     if (!arena.dry) {
-        if (npad != N) HIP_OK(hipMemsetAsync(pr, 0, (size_t)N * npad * dt_size(T), stream));
-        const size_t eb = dt_size(T);
-        const int bke = 128 / (int)eb;
-        for (int b = 0; b < B; ++b) {
-            const char* qb = reinterpret_cast<const char*>(qk.p) + (size_t)b * N * 2 * C * eb;
-            GemmParams p{};
-            // scores = (q k^T) * C^-0.5 : A = q rows, "weights" = k rows of the same buffer (row stride 2C)
-            p.A = qb; p.W = qb + (size_t)C * eb; p.C = sc;
-            p.M = N; p.N = N; p.K = C; p.Kpad = round_up(C, bke); p.ldw = 2 * C;
-            p.lda = 2 * C; p.ldc = N; p.a_dt = T; p.c_dt = DT_F32; p.r_dt = DT_F32;
-            p.taps = 1; p.Cin = C; p.Hin = N; p.Win = 1; p.Hout = N; p.Wout = 1; p.stride = 1;
-            p.rows_per_sample = N; p.out_scale = (float)(1.0 / std::sqrt((double)C));
-            p.vt_begin = INT_MAX; p.Nout = N; p.splitk = 1; p.big_tile = N >= 1024 ? 1 : 0;
-            if (launch_gemm(p, P, stream)) { pd_set_error("vae attention: score GEMM launch failed"); return 1; }
-            if (launch_softmax_rows(sc, pr, T, N, N, stream)) { pd_set_error("vae attention: softmax launch failed"); return 1; }
-            // out = P v : A = P [N, N] (row stride npad when padded), "weights" = V^T [C][npad]
-            GemmParams o{};
-            o.A = pr; o.W = reinterpret_cast<const char*>(vt.p) + (size_t)b * C * npad * eb;
-            o.C = reinterpret_cast<char*>(att.p) + (size_t)b * N * C * eb;
-            o.M = N; o.N = C; o.K = N; o.Kpad = round_up(N, bke); o.ldw = npad;
-            o.lda = N; o.ldc = C; o.a_dt = T; o.c_dt = T; o.r_dt = DT_F32;
-            o.taps = 1; o.Cin = N; o.Hin = N; o.Win = 1; o.Hout = N; o.Wout = 1; o.stride = 1;
-            o.rows_per_sample = N; o.out_scale = 1.f; o.vt_begin = INT_MAX; o.Nout = C; o.splitk = 1;
-            o.big_tile = N >= 1024 ? 1 : 0;
-            if (launch_gemm(o, P, stream)) { pd_set_error("vae attention: value GEMM launch failed"); return 1; }
-            launches += 3;
-        }
+        PD_TRY(check_arena());
+        if (!flash && npad != N) HIP_OK(hipMemsetAsync(pr, 0, (size_t)N * npad * dt_size(T), stream));
+        PD_TRY(vae_attn_product(qk.p, 2 * C, vt.p, npad, att.p, B, N, C, flash, sc, pr));
     }
     PD_TRY(conv(v.proj_out, att, out, {.R = &x}));
     arena.release(mk);
     return 0;
 }
 
-int pd_engine::vae_forward(const float* latents_dev, int B, int h, int w, float* out_dev) {
-    VaeW& v = vae;
-    Act z = new_act(B, h, w, 8, T);
+int pd_engine::vae_forward(VaeW& v, const float* latents_dev, int B, int h, int w, float* out_dev, float scale, float shift) {
+    const VaeDesc& d = v.d;
+    Act z = new_act(B, h, w, d.zpad, T);
     if (!arena.dry) {
         ++launches;
-        if (launch_nchw_to_nhwc(latents_dev, z.p, T, B, cfg.in_channels, h, w, 8, stream, (float)(1.0 / cfg.scale_factor))) return 1;
+        if (launch_nchw_to_nhwc(latents_dev, z.p, T, B, d.z, h, w, d.zpad, stream, scale, shift)) return 1;
     }
-    Act zq = new_act(B, h, w, 8, T);   // post_quant_conv writes channels 0..in_ch-1; the pad channels must read as 0
-    if (!arena.dry) HIP_OK(hipMemsetAsync(zq.p, 0, zq.bytes(), stream));
-    PD_TRY(conv(v.post_quant, z, zq));
+    Act zq = z;
+    if (d.quant) {
+        zq = new_act(B, h, w, d.zpad, T);   // post_quant_conv writes channels 0..z-1; the pad channels must read as 0
+        if (!arena.dry) HIP_OK(hipMemsetAsync(zq.p, 0, zq.bytes(), stream));
+        PD_TRY(conv(v.post_quant, z, zq));
+    }
     Act hcur = new_act(B, h, w, v.top, S);
     PD_TRY(conv(v.conv_in, zq, hcur));
     Act t;
     PD_TRY(resblock(v.mid1, hcur, t, nullptr, 0));
     hcur = t;
-    PD_TRY(vae_attention(v.attn, hcur, t));
+    PD_TRY(vae_attention(v.attn, d, hcur, t));
     hcur = t;
     PD_TRY(resblock(v.mid2, hcur, t, nullptr, 0));
     hcur = t;
@@ -200,16 +274,41 @@ int pd_engine::vae_forward(const float* latents_dev, int B, int h, int w, float*
             hcur = u;
         }
     }
-    Act img = new_act(hcur.B, hcur.H, hcur.W, round_up(cfg.vae_out_ch, 4), DT_F32);
+    Act img = new_act(hcur.B, hcur.H, hcur.W, round_up(d.out_ch, 4), DT_F32);
     PD_TRY(conv_gn(v.conv_out, hcur, img, v.out_g, v.out_b, 1e-6f, true));
     if (!arena.dry) {
         ++launches;
-        if (launch_nhwc_to_nchw(img.p, DT_F32, out_dev, B, cfg.vae_out_ch, img.H, img.W, img.C, 1.f, stream)) return 1;
+        if (launch_nhwc_to_nchw(img.p, DT_F32, out_dev, B, d.out_ch, img.H, img.W, img.C, 1.f, stream)) return 1;
     }
     return 0;
 }
 
 extern "C" int pd_vae_weights_missing(pd_engine* e) { return e ? e->missing(GROUP_VAE) : 0; }
+
+int pd_engine::vae_decode_call(VaeW& v, const float* latents, int B, int h, int w, int mem, float scale, float shift, float* images_out) {
+    HIP_OK(hipSetDevice(device));
+    const int up = 1 << (v.d.num_levels - 1);
+    const int H = up * h, W = up * w;
+    const size_t n_in = (size_t)B * v.d.z * h * w, n_out = (size_t)B * v.d.out_ch * H * W;
+    return in_side_workspace("VAE", (n_in + n_out) * sizeof(float), [&] { return vae_forward(v, nullptr, B, h, w, nullptr, scale, shift); }, [&] {
+        int r = 0;
+        float* din = reinterpret_cast<float*>(arena.alloc(n_in * sizeof(float)));
+        float* dout = reinterpret_cast<float*>(arena.alloc(n_out * sizeof(float)));
+        const float* src = latents;
+        if (mem != PD_MEM_DEVICE) {
+            if (hipMemcpyAsync(din, latents, n_in * sizeof(float), hipMemcpyHostToDevice, stream) != hipSuccess ||
+                hipStreamSynchronize(stream) != hipSuccess) { pd_set_error("latent upload failed"); r = 1; }
+            src = din;
+        }
+        if (!r) r = vae_forward(v, src, B, h, w, dout, scale, shift);
+        if (!r) {
+            if (hipMemcpyAsync(images_out, dout, n_out * sizeof(float),
+                               mem == PD_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream) != hipSuccess ||
+                hipStreamSynchronize(stream) != hipSuccess) { pd_set_error("image read-back failed"); r = 1; }
+        }
+        return r;
+    });
+}
 
 extern "C" int pd_vae_decode(pd_engine* e, const float* latents, int32_t B, int32_t h, int32_t w, int32_t mem, float* images_out) {
     if (!e || !latents || !images_out || B < 1 || h < 1 || w < 1) { pd_set_error("bad argument"); return 1; }
@@ -217,41 +316,22 @@ extern "C" int pd_vae_decode(pd_engine* e, const float* latents, int32_t B, int3
     if (e->ses.active) { pd_set_error("pd_vae_decode: end the sampling session first"); return 1; }
     if ((h * w) % 64) { pd_set_error("pd_vae_decode: h*w must be a multiple of 64 (latents of 64x64-pixel multiples)"); return 1; }
     PD_TRY(e->require_loaded(GROUP_VAE, "VAE"));
-    HIP_OK(hipSetDevice(e->device));
-    const int H = 8 * h, W = 8 * w;
-    const size_t n_in = (size_t)B * e->cfg.in_channels * h * w, n_out = (size_t)B * e->cfg.vae_out_ch * H * W;
-    return e->in_side_workspace("VAE", (n_in + n_out) * sizeof(float), [&] { return e->vae_forward(nullptr, B, h, w, nullptr); }, [&] {
-        int r = 0;
-        float* din = reinterpret_cast<float*>(e->arena.alloc(n_in * sizeof(float)));
-        float* dout = reinterpret_cast<float*>(e->arena.alloc(n_out * sizeof(float)));
-        const float* src = latents;
-        if (mem != PD_MEM_DEVICE) {
-            if (hipMemcpyAsync(din, latents, n_in * sizeof(float), hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-                hipStreamSynchronize(e->stream) != hipSuccess) { pd_set_error("latent upload failed"); r = 1; }
-            src = din;
-        }
-        if (!r) r = e->vae_forward(src, B, h, w, dout);
-        if (!r) {
-            if (hipMemcpyAsync(images_out, dout, n_out * sizeof(float),
-                               mem == PD_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
-                hipStreamSynchronize(e->stream) != hipSuccess) { pd_set_error("image read-back failed"); r = 1; }
-        }
-        return r;
-    });
+    return e->vae_decode_call(e->vae, latents, B, h, w, mem, (float)(1.0 / e->cfg.scale_factor), 0.f, images_out);
 }
 
 // AutoencoderKL.encode (autoencoder.py:83-87): Encoder.forward (model.py:508-544) -> quant_conv -> DiagonalGaussianDistribution
 // (distributions.py:24-62), the posterior reduced on the device to what `what` asks for (PD_VAE_*)
-int pd_engine::vae_encoder_forward(const float* images_dev, int B, int H, int W, int what, const float* noise_dev, float* out_dev) {
-    VaeEncW& v = vae_enc;
-    const int cin = cfg.vae_out_ch, z = cfg.in_channels;
+int pd_engine::vae_encoder_forward(VaeEncW& v, const float* images_dev, int B, int H, int W, int what, const float* noise_dev, float* out_dev,
+                                   float scale, float shift) {
+    const VaeDesc& d = v.d;
+    const int cin = d.out_ch, z = d.z;
     Act x = new_act(B, H, W, v.conv_in.m.cin_pad, T);
     if (!arena.dry) {
         PD_TRY(check_arena());
         ++launches;
         if (launch_nchw_to_nhwc(images_dev, x.p, T, B, cin, H, W, x.C, stream)) { pd_set_error("image upload launch failed"); return 1; }
     }
-    Act hcur = new_act(B, H, W, cfg.vae_ch, S);
+    Act hcur = new_act(B, H, W, d.ch, S);
     PD_TRY(conv(v.conv_in, x, hcur));
     Act t;
     for (VaeEncLevel& L : v.levels) {
@@ -267,20 +347,22 @@ int pd_engine::vae_encoder_forward(const float* images_dev, int B, int H, int W,
     }
     PD_TRY(resblock(v.mid1, hcur, t, nullptr, 0));
     hcur = t;
-    PD_TRY(vae_attention(v.attn, hcur, t));
+    PD_TRY(vae_attention(v.attn, d, hcur, t));
     hcur = t;
     PD_TRY(resblock(v.mid2, hcur, t, nullptr, 0));
     hcur = t;
     // norm_out + swish + conv_out, then quant_conv; the moments stay fp32 from here on
     Act h = new_act(hcur.B, hcur.H, hcur.W, v.conv_out.m.N, DT_F32);
     PD_TRY(conv_gn(v.conv_out, hcur, h, v.out_g, v.out_b, 1e-6f, true));
-    Act mom = new_act(h.B, h.H, h.W, v.quant.m.N, DT_F32);
-    PD_TRY(conv(v.quant, h, mom));
+    Act mom = h;
+    if (d.quant) {
+        mom = new_act(h.B, h.H, h.W, v.quant.m.N, DT_F32);
+        PD_TRY(conv(v.quant, h, mom));
+    }
     if (!arena.dry) {
         PD_TRY(check_arena());
         ++launches;
-        if (launch_vae_posterior(mom.p, DT_F32, mom.C, noise_dev, out_dev, B, z, mom.H * mom.W, what, (float)cfg.scale_factor, stream,
-                                 rng_dev)) {
+        if (launch_vae_posterior(mom.p, DT_F32, mom.C, noise_dev, out_dev, B, z, mom.H * mom.W, what, scale, stream, rng_dev, shift)) {
             pd_set_error("posterior launch failed");
             return 1;
         }
@@ -289,6 +371,39 @@ int pd_engine::vae_encoder_forward(const float* images_dev, int B, int H, int W,
 }
 
 extern "C" int pd_vae_encoder_weights_missing(pd_engine* e) { return e ? e->missing(GROUP_VAE_ENCODER) : 0; }
+
+int pd_engine::vae_encode_call(VaeEncW& v, const float* images, int B, int H, int W, int mem, int what, const float* noise, float scale, float shift,
+                               float* out) {
+    HIP_OK(hipSetDevice(device));
+    const int dn = 1 << (v.d.num_levels - 1);
+    const int h = H / dn, w = W / dn, z = v.d.z;
+    const size_t n_in = (size_t)B * v.d.out_ch * H * W, n_lat = (size_t)B * z * h * w;
+    // (noise NULL with PD_VAE_SAMPLE: the posterior kernel draws at (PD_RNG_VAE, draw 0) itself)
+    const size_t n_noise = (what == PD_VAE_SAMPLE && noise) ? n_lat : 0, n_out = what == PD_VAE_MOMENTS ? 2 * n_lat : n_lat;
+    return in_side_workspace("VAE", (n_in + n_noise + n_out) * sizeof(float),
+                             [&] { return vae_encoder_forward(v, nullptr, B, H, W, what, nullptr, nullptr, scale, shift); }, [&] {
+        int r = 0;
+        float* din = reinterpret_cast<float*>(arena.alloc(n_in * sizeof(float)));
+        float* dnoise = n_noise ? reinterpret_cast<float*>(arena.alloc(n_noise * sizeof(float))) : nullptr;
+        float* dout = reinterpret_cast<float*>(arena.alloc(n_out * sizeof(float)));
+        const float* src = images;
+        const float* nz = noise;
+        if (mem != PD_MEM_DEVICE) {
+            if (hipMemcpyAsync(din, images, n_in * sizeof(float), hipMemcpyHostToDevice, stream) != hipSuccess ||
+                (dnoise && hipMemcpyAsync(dnoise, noise, n_noise * sizeof(float), hipMemcpyHostToDevice, stream) != hipSuccess) ||
+                hipStreamSynchronize(stream) != hipSuccess) { pd_set_error("image upload failed"); r = 1; }
+            src = din;
+            nz = dnoise;
+        }
+        if (!r) r = vae_encoder_forward(v, src, B, H, W, what, what == PD_VAE_SAMPLE ? nz : nullptr, dout, scale, shift);
+        if (!r) {
+            if (hipMemcpyAsync(out, dout, n_out * sizeof(float), mem == PD_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                               stream) != hipSuccess ||
+                hipStreamSynchronize(stream) != hipSuccess) { pd_set_error("latent read-back failed"); r = 1; }
+        }
+        return r;
+    });
+}
 
 extern "C" int pd_vae_encode(pd_engine* e, const float* images, int32_t B, int32_t H, int32_t W, int32_t mem, int32_t what,
                              const float* noise, float* out) {
@@ -304,32 +419,5 @@ extern "C" int pd_vae_encode(pd_engine* e, const float* images, int32_t B, int32
         pd_set_error("pd_vae_encode: unknown `what` %d (PD_VAE_MEAN / PD_VAE_SAMPLE / PD_VAE_MOMENTS)", what);
         return 1;
     }
-    HIP_OK(hipSetDevice(e->device));
-    const int h = H / 8, w = W / 8, z = e->cfg.in_channels;
-    const size_t n_in = (size_t)B * e->cfg.vae_out_ch * H * W, n_lat = (size_t)B * z * h * w;
-    // (noise NULL with PD_VAE_SAMPLE: the posterior kernel draws at (PD_RNG_VAE, draw 0) itself)
-    const size_t n_noise = (what == PD_VAE_SAMPLE && noise) ? n_lat : 0, n_out = what == PD_VAE_MOMENTS ? 2 * n_lat : n_lat;
-    return e->in_side_workspace("VAE", (n_in + n_noise + n_out) * sizeof(float),
-                                [&] { return e->vae_encoder_forward(nullptr, B, H, W, what, nullptr, nullptr); }, [&] {
-        int r = 0;
-        float* din = reinterpret_cast<float*>(e->arena.alloc(n_in * sizeof(float)));
-        float* dnoise = n_noise ? reinterpret_cast<float*>(e->arena.alloc(n_noise * sizeof(float))) : nullptr;
-        float* dout = reinterpret_cast<float*>(e->arena.alloc(n_out * sizeof(float)));
-        const float* src = images;
-        const float* nz = noise;
-        if (mem != PD_MEM_DEVICE) {
-            if (hipMemcpyAsync(din, images, n_in * sizeof(float), hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-                (dnoise && hipMemcpyAsync(dnoise, noise, n_noise * sizeof(float), hipMemcpyHostToDevice, e->stream) != hipSuccess) ||
-                hipStreamSynchronize(e->stream) != hipSuccess) { pd_set_error("image upload failed"); r = 1; }
-            src = din;
-            nz = dnoise;
-        }
-        if (!r) r = e->vae_encoder_forward(src, B, H, W, what, what == PD_VAE_SAMPLE ? nz : nullptr, dout);
-        if (!r) {
-            if (hipMemcpyAsync(out, dout, n_out * sizeof(float), mem == PD_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
-                               e->stream) != hipSuccess ||
-                hipStreamSynchronize(e->stream) != hipSuccess) { pd_set_error("latent read-back failed"); r = 1; }
-        }
-        return r;
-    });
+    return e->vae_encode_call(e->vae_enc, images, B, H, W, mem, what, noise, (float)e->cfg.scale_factor, 0.f, out);
 }

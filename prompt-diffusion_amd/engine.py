@@ -223,6 +223,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.pd_op_groupnorm_coef.argtypes = [C.c_void_p, fp, fp, fp] + [C.c_int] * 4 + [C.c_float, fp]
     lib.pd_op_ln_linear.argtypes = [C.c_void_p, C.c_int] + [fp] * 9 + [C.c_int] * 3 + [fp, fp, C.POINTER(C.c_int), fp]
     lib.pd_op_attention.argtypes = [C.c_void_p, fp, fp, fp] + [C.c_int] * 4 + [fp]
+    lib.pd_op_vae_attention.argtypes = [C.c_void_p, fp, fp, fp] + [C.c_int] * 3 + [fp]
+    lib.pd_bench_vae_attention.argtypes = [C.c_void_p] + [C.c_int32] * 5 + [C.POINTER(C.c_float), C.POINTER(C.c_int64)]
     lib.pd_op_spatial_transformer.argtypes = [C.c_void_p, C.c_char_p, fp, fp] + [C.c_int] * 3 + [fp]
     lib.pd_op_spatial_transformer_ctx.argtypes = [C.c_void_p, C.c_char_p, fp, fp] + [C.c_int] * 4 + [fp]
     lib.pd_op_time_embed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, fp, fp]
@@ -267,6 +269,7 @@ EXPORTS = [
     "pd_hed_configure", "pd_hed_weights_missing", "pd_hed_detect", "pd_op_hed_stage_tail", "pd_op_hed_fuse",
     "pd_resample_coefficients", "pd_image_load", "pd_image_store",
     "pd_sd3_text_configure", "pd_sd3_text_weights_missing", "pd_sd3_encode_prompt", "pd_sd3_text_encoder", "pd_t5_relative_buckets",
+    "pd_sd3_vae_configure", "pd_sd3_vae_weights_missing", "pd_sd3_vae_config_layout", "pd_sd3_vae_decode", "pd_sd3_vae_encode", "pd_op_vae_attention", "pd_bench_vae_attention",
 ]
 
 
@@ -1315,6 +1318,17 @@ class Engine:
         Nk = k.shape[1]
         o = np.empty_like(q)
         self._check(self.lib.pd_op_attention(self._h, q.ctypes.data, k.ctypes.data, v.ctypes.data, B, Nq, Nk, Cc, o.ctypes.data))
+        return o
+
+    def op_vae_attention(self, q, k, v):
+        """softmax(q k^T C^-0.5) v with one head over all C channels (the first stage's AttnBlock); q, k, v [B, N, C].  Option
+        "vae_flash" 1: the single-head flash kernel (2-byte modes, C 128 / 512); 0: the materialised three-launch path."""
+        q = np.ascontiguousarray(q, np.float32); k = np.ascontiguousarray(k, np.float32); v = np.ascontiguousarray(v, np.float32)
+        B, N, Cc = q.shape
+        if k.shape != q.shape or v.shape != q.shape:
+            raise ValueError("q, k and v must share one shape [B, N, C]")
+        o = np.empty_like(q)
+        self._check(self.lib.pd_op_vae_attention(self._h, q.ctypes.data, k.ctypes.data, v.ctypes.data, B, N, Cc, o.ctypes.data))
         return o
 
     def op_vae_downsample(self, x, w, b=None):

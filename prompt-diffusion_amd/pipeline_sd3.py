@@ -17,6 +17,11 @@ make `prompt=` strings work: the pipeline does what the reference's encode_promp
 fallbacks, the negative prompt with its checks, the negative pass at clip_skip None, the per-image repeat, max_sequence_length) and the
 engine encodes (`SD3Engine.encode_prompt_ids`).  An injected `encode_prompt` keeps precedence.
 
+Likewise the image ends: without injected `vae_encode` / `vae_decode` / `down_proj`, an engine with SD3's VAE (`SD3Engine.configure_vae`)
+encodes `control_image` images and image pairs (`vae_encode(..., raw=True)`, `encode_support_pair`) and decodes for `output_type` "pil",
+"np" and "pt" (`vae_decode(..., raw=True)`).  The shift / scaling arithmetic stays here in both cases, applied once; the two factors
+default to the engine's VAE configuration.  Injected callables keep precedence; with neither, the ValueErrors below stay.
+
 The three steps of the loop body (controlnet, transformer, CFG + scheduler.step; :1192-1245) run inside the engine
 (`SD3Engine.sample`); with `callback_on_step_end` the loop is driven step by step from here (`SD3Engine.forward` + the same
 Euler update) so that the callback can replace the latents or the embeddings (:1247-1258).  Arrays are NumPy (torch tensors
@@ -36,16 +41,33 @@ def _np(x, dtype=np.float32):
     return None if x is None else np.ascontiguousarray(E._to_host(x), dtype=dtype)
 
 
+def _image_array(x):
+    """PIL images (one or a list) and uint8 arrays become float arrays in [0, 1] (VaeImageProcessor's pil_to_numpy); everything else
+    passes through."""
+    if isinstance(x, (list, tuple)) and x and hasattr(x[0], "convert"):
+        return np.stack([np.asarray(i.convert("RGB"), np.float32) / 255.0 for i in x])
+    if hasattr(x, "convert"):
+        return np.asarray(x.convert("RGB"), np.float32)[None] / 255.0
+    if isinstance(x, np.ndarray) and x.dtype == np.uint8:
+        return x.astype(np.float32) / 255.0
+    return x
+
+
 class StableDiffusion3PromptDiffusionPipeline:
     _callback_tensor_inputs = _CALLBACK_TENSOR_INPUTS
 
     def __init__(self, engine: SD3Engine, encode_prompt: Optional[Callable] = None, vae_encode: Optional[Callable] = None,
-                 vae_decode: Optional[Callable] = None, down_proj: Optional[Callable] = None, vae_scaling_factor: float = 1.5305,
-                 vae_shift_factor: float = 0.0609, vae_scale_factor: int = 8, shift: float = 3.0, tokenizers=None,
+                 vae_decode: Optional[Callable] = None, down_proj: Optional[Callable] = None, vae_scaling_factor: Optional[float] = None,
+                 vae_shift_factor: Optional[float] = None, vae_scale_factor: int = 8, shift: float = 3.0, tokenizers=None,
                  tokenizer_max_length: int = 77):
         self.engine = engine
         self.tokenizers, self.tokenizer_max_length = tokenizers, tokenizer_max_length
         self.encode_prompt, self.vae_encode, self.vae_decode, self.down_proj = encode_prompt, vae_encode, vae_decode, down_proj
+        vcfg = getattr(engine, "vae_cfg", None)   # None: the published SD3 values
+        if vae_scaling_factor is None:
+            vae_scaling_factor = vcfg.scaling_factor if vcfg is not None else 1.5305
+        if vae_shift_factor is None:
+            vae_shift_factor = vcfg.shift_factor if vcfg is not None else 0.0609
         self.vae_scaling_factor, self.vae_shift_factor, self.vae_scale_factor = vae_scaling_factor, vae_shift_factor, vae_scale_factor
         self.shift = shift
         self._guidance_scale, self._clip_skip, self._num_timesteps, self._interrupt = 7.0, None, 0, False
@@ -155,7 +177,7 @@ class StableDiffusion3PromptDiffusionPipeline:
         like in the reference; other arrays ([B, H, W, 3] or [B, 3, H, W] in [0, 1]) get VaeImageProcessor's normalisation to
         [-1, 1].  Resizing is the caller's."""
         as_is = E._is_torch(image)
-        img = _np(image)
+        img = _np(_image_array(image))
         if img.ndim == 3:
             img = img[None]
         if img.shape[-1] == 3 and img.shape[1] != 3:
@@ -165,17 +187,37 @@ class StableDiffusion3PromptDiffusionPipeline:
         repeat_by = batch_size if img.shape[0] == 1 else num_images_per_prompt
         return np.ascontiguousarray(np.repeat(img, repeat_by, axis=0), np.float32)
 
+    # ------------------------------------------------------------------ the image ends: injected callables first, then the engine's VAE
+    def _engine_has_vae(self, encoder: bool) -> bool:
+        return getattr(self.engine, "vae_cfg", None) is not None and (not encoder or getattr(self.engine, "vae_has_encoder", False))
+
+    def _vae_encode_fn(self):
+        if self.vae_encode is not None:
+            return self.vae_encode
+        if self._engine_has_vae(True):
+            return lambda x: self.engine.vae_encode(x, mode="sample", raw=True)   # shift and scaling are applied here
+        return None
+
+    def _vae_decode_fn(self):
+        if self.vae_decode is not None:
+            return self.vae_decode
+        if self._engine_has_vae(False):
+            return lambda z: self.engine.vae_decode(z, raw=True)
+        return None
+
     def _to_latents(self, x, batch_size, num_images_per_prompt, shift, pair=False):
         """Control conditions: 16-channel arrays are taken as latents already; images go through (down_proj +) vae_encode and
         (x - shift_factor) * scaling_factor (:1112-1127)."""
         C = self.engine.cfg.in_channels
         if not pair:
+            x, known_image = _image_array(x), _image_array(x) is not x      # a PIL / uint8 input is an image whatever its size
             a = _np(x)
-            if a.ndim == 4 and a.shape[1] == C:
+            if not known_image and a.ndim == 4 and a.shape[1] == C:
                 return np.ascontiguousarray(np.repeat(a, batch_size * num_images_per_prompt if a.shape[0] == 1 else num_images_per_prompt, axis=0))
-            if self.vae_encode is None:
+            encode = self._vae_encode_fn()
+            if encode is None:
                 raise ValueError(f"`control_image` must be [{C}]-channel latents unless the pipeline was given `vae_encode`")
-            lat = _np(self.vae_encode(self.prepare_image(a, batch_size * num_images_per_prompt, num_images_per_prompt)))
+            lat = _np(encode(self.prepare_image(x, batch_size * num_images_per_prompt, num_images_per_prompt)))
             return ((lat - shift) * self.vae_scaling_factor).astype(np.float32)
         if not isinstance(x, (list, tuple)):
             a = _np(x)
@@ -184,10 +226,16 @@ class StableDiffusion3PromptDiffusionPipeline:
             raise ValueError("`control_image_pair` must be a list of two images (or pair latents)")
         if len(x) != 2:
             raise ValueError("`control_image_pair` must hold exactly two images")
-        if self.vae_encode is None or self.down_proj is None:
+        encode = self._vae_encode_fn()
+        if encode is None or (self.down_proj is None and not self._engine_has_vae(True)):
             raise ValueError("image pairs need `vae_encode` and `down_proj`; pass pair latents otherwise")
         imgs = [self.prepare_image(i, batch_size * num_images_per_prompt, num_images_per_prompt) for i in x]
-        lat = _np(self.vae_encode(_np(self.down_proj(np.concatenate(imgs, axis=1)))))      # encode_support_pair (:189-198)
+        if self.down_proj is not None:
+            lat = _np(encode(_np(self.down_proj(np.concatenate(imgs, axis=1)))))      # encode_support_pair (:189-198)
+        elif self.vae_encode is not None:
+            lat = _np(encode(_np(self.engine.down_proj(imgs[0], imgs[1]))))
+        else:
+            lat = _np(self.engine.encode_support_pair(imgs[0], imgs[1]))              # down_proj, then vae_encode(raw=True)
         return ((lat - shift) * self.vae_scaling_factor).astype(np.float32)
 
     def prepare_latents(self, batch_size, num_channels_latents, height, width, generator, latents=None):
@@ -239,10 +287,12 @@ class StableDiffusion3PromptDiffusionPipeline:
         if control_image is None or control_image_pair is None:
             raise ValueError("`control_image` and `control_image_pair` are required (the reference asserts a SD3PromptDiffusionModel)")
         # default size: the control latents / image decide (the reference overrides height, width from the control image, :1123)
-        ci = _np(control_image)
+        ci = _np(_image_array(control_image))
         if ci.ndim == 3:
             ci = ci[None]
-        if ci.shape[1] == cfg.in_channels:
+        if _image_array(control_image) is not control_image:
+            h_img, w_img = ci.shape[1:3]                                   # PIL / uint8: [B, H, W, 3]
+        elif ci.shape[1] == cfg.in_channels:
             h_img, w_img = ci.shape[-2] * self.vae_scale_factor, ci.shape[-1] * self.vae_scale_factor
         elif ci.shape[1] == 3:
             h_img, w_img = ci.shape[-2:]
@@ -346,9 +396,10 @@ class StableDiffusion3PromptDiffusionPipeline:
         if output_type == "latent":
             image = latents
         else:
-            if self.vae_decode is None:
+            decode = self._vae_decode_fn()
+            if decode is None:
                 raise ValueError('output_type other than "latent" needs the `vae_decode` callable')
-            image = _np(self.vae_decode(latents / self.vae_scaling_factor + self.vae_shift_factor))
+            image = _np(decode(latents / self.vae_scaling_factor + self.vae_shift_factor))
             image = np.clip(image / 2 + 0.5, 0.0, 1.0)            # postprocess (:823-851)
             if output_type != "pt":
                 image = image.transpose(0, 2, 3, 1)

@@ -2,13 +2,14 @@
 
 Mirrors, at the tensor level, what the reference's SD3 pipeline does per denoising step
 (promptdiffusioncontrolnetpipeline_sd3.py:1192-1245): ControlNet (promptdiffusioncontrolnet_sd3.py:362-483), transformer
-with ``block_controlnet_hidden_states``, classifier-free guidance, FlowMatchEuler step.  The VAE stays with the caller: the
-boundary takes prompt embeddings and condition LATENTS.  The text encoders (CLIP-L, CLIP-G, T5; pipeline :238-545) are opt-in on the
+with ``block_controlnet_hidden_states``, classifier-free guidance, FlowMatchEuler step.  The boundary takes prompt embeddings and
+condition LATENTS; SD3's VAE is opt-in on the same engine (``SD3Engine.configure_vae`` / ``vae_encode`` / ``vae_decode``: images in,
+latents out and back).  The text encoders (CLIP-L, CLIP-G, T5; pipeline :238-545) are opt-in on the
 same engine (``SD3Engine.configure_text`` / ``encode_prompt_ids``: token ids in, prompt embeddings out; tokenisation is the caller's).  PARITY UNPINNED (diffusers is absent offline): checked against oracle/sd3_oracle.py only."""
 import ctypes as C
 import math
 from dataclasses import dataclass
-from typing import Dict, Optional
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 
@@ -131,6 +132,99 @@ class pd_sd3_text_config(C.Structure):
 class pd_sd3_text_args(C.Structure):
     _fields_ = [("batch", C.c_int32), ("t5_len", C.c_int32), ("clip_skip", C.c_int32), ("mem", C.c_int32),
                 ("ids_clip_l", C.c_void_p), ("ids_clip_g", C.c_void_p), ("ids_t5", C.c_void_p), ("reserved", C.c_int64 * 3)]
+
+
+@dataclass(frozen=True)
+class SD3VaeConfig:
+    """diffusers AutoencoderKL as SD3 ships it (vae/config.json): block_out_channels = ch * ch_mult, layers_per_block = num_res_blocks,
+    latent_channels = z_channels, use_quant_conv = use_post_quant_conv = False, one mid-block attention head over all channels."""
+    ch: int = 128
+    ch_mult: Tuple[int, ...] = (1, 2, 4, 4)
+    num_res_blocks: int = 2
+    z_channels: int = 16
+    out_ch: int = 3
+    quant_conv: bool = False
+    post_quant_conv: bool = False
+    scaling_factor: float = 1.5305
+    shift_factor: float = 0.0609
+
+    @property
+    def downscale(self) -> int:
+        return 1 << (len(self.ch_mult) - 1)
+
+
+SD3_MEDIUM_VAE = SD3VaeConfig()
+SD3_TINY_VAE = SD3VaeConfig(ch=32)     # mid-block attention over 128 channels: the flash kernel's small instantiation
+
+
+class pd_sd3_vae_config(C.Structure):
+    _fields_ = [("ch", C.c_int32), ("num_levels", C.c_int32), ("ch_mult", C.c_int32 * E.PD_MAX_LEVELS), ("num_res_blocks", C.c_int32),
+                ("z_channels", C.c_int32), ("out_ch", C.c_int32), ("encoder", C.c_int32), ("quant_conv", C.c_int32),
+                ("post_quant_conv", C.c_int32), ("scaling_factor", C.c_double), ("shift_factor", C.c_double)]
+
+
+def _sd3_vres(prefix, cin, cout):
+    out = [(prefix + "norm1.weight", (cin,), "gamma"), (prefix + "norm1.bias", (cin,), "beta")]
+    out += list(W._conv(prefix + "conv1.", cin, cout, 3))
+    out += [(prefix + "norm2.weight", (cout,), "gamma"), (prefix + "norm2.bias", (cout,), "beta")]
+    out += list(W._conv(prefix + "conv2.", cout, cout, 3))
+    if cin != cout:
+        out += list(W._conv(prefix + "conv_shortcut.", cin, cout, 1))
+    return out
+
+
+def _sd3_vmid(prefix, ch):
+    out = _sd3_vres(prefix + "resnets.0.", ch, ch)
+    a = prefix + "attentions.0."
+    out += [(a + "group_norm.weight", (ch,), "gamma"), (a + "group_norm.bias", (ch,), "beta")]
+    for n in ("to_q", "to_k", "to_v", "to_out.0"):      # Linear [C, C]: ldm's 1x1 convs q / k / v / proj_out without the trailing 1, 1
+        out += [(a + n + ".weight", (ch, ch), "w"), (a + n + ".bias", (ch,), "b")]
+    return out + _sd3_vres(prefix + "resnets.1.", ch, ch)
+
+
+def sd3_vae_spec(cfg: SD3VaeConfig, encoder: bool = True, prefix: str = "vae."):
+    """(name, shape, kind) of every VAE tensor under diffusers' AutoencoderKL names (written from its published layout: diffusers is
+    absent offline, so the names are UNPINNED): decoder (conv_in, mid_block, up_blocks.{i} in execution order, conv_norm_out, conv_out),
+    post_quant_conv if any, then the encoder (conv_in, down_blocks.{i}, mid_block, conv_norm_out, conv_out) and quant_conv if any."""
+    nl = len(cfg.ch_mult)
+    top = cfg.ch * cfg.ch_mult[-1]
+    d = prefix + "decoder."
+    out = list(W._conv(d + "conv_in.", cfg.z_channels, top, 3)) + _sd3_vmid(d + "mid_block.", top)
+    block_in = top
+    for i in range(nl):                                   # up_blocks.{i} is ldm's up.{nl - 1 - i}
+        block_out = cfg.ch * cfg.ch_mult[nl - 1 - i]
+        for j in range(cfg.num_res_blocks + 1):
+            out += _sd3_vres(d + f"up_blocks.{i}.resnets.{j}.", block_in, block_out)
+            block_in = block_out
+        if i != nl - 1:
+            out += list(W._conv(d + f"up_blocks.{i}.upsamplers.0.conv.", block_in, block_in, 3))
+    out += [(d + "conv_norm_out.weight", (cfg.ch,), "gamma"), (d + "conv_norm_out.bias", (cfg.ch,), "beta")]
+    out += list(W._conv(d + "conv_out.", cfg.ch, cfg.out_ch, 3))
+    if cfg.post_quant_conv:
+        out += list(W._conv(prefix + "post_quant_conv.", cfg.z_channels, cfg.z_channels, 1))
+    if not encoder:
+        return out
+    e = prefix + "encoder."
+    z2 = 2 * cfg.z_channels
+    out += list(W._conv(e + "conv_in.", cfg.out_ch, cfg.ch, 3))
+    block_in = cfg.ch
+    for i, mult in enumerate(cfg.ch_mult):
+        for j in range(cfg.num_res_blocks):
+            out += _sd3_vres(e + f"down_blocks.{i}.resnets.{j}.", block_in, cfg.ch * mult)
+            block_in = cfg.ch * mult
+        if i != nl - 1:
+            out += list(W._conv(e + f"down_blocks.{i}.downsamplers.0.conv.", block_in, block_in, 3))
+    out += _sd3_vmid(e + "mid_block.", block_in)
+    out += [(e + "conv_norm_out.weight", (block_in,), "gamma"), (e + "conv_norm_out.bias", (block_in,), "beta")]
+    out += list(W._conv(e + "conv_out.", block_in, z2, 3))
+    if cfg.quant_conv:
+        out += list(W._conv(prefix + "quant_conv.", z2, z2, 1))
+    return out
+
+
+def synth_sd3_vae_state_dict(cfg: SD3VaeConfig, seed: int = 1234, encoder: bool = True) -> Dict[str, np.ndarray]:
+    """Deterministic NumPy weights in the style of weights.synth_vae_state_dict."""
+    return {n: W.synth_tensor(n, s, k, seed) for n, s, k in sd3_vae_spec(cfg, encoder)}
 
 
 def sd3_text_spec(cfg: SD3TextConfig):
@@ -342,7 +436,13 @@ class SD3Engine:
         lib.pd_sd3_text_weights_missing.argtypes = [C.c_void_p]
         lib.pd_sd3_encode_prompt.argtypes = [C.c_void_p, C.POINTER(pd_sd3_text_args), C.c_void_p, C.c_void_p]
         lib.pd_sd3_text_encoder.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+        lib.pd_sd3_vae_configure.argtypes = [C.c_void_p, C.POINTER(pd_sd3_vae_config)]
+        lib.pd_sd3_vae_weights_missing.argtypes = [C.c_void_p]
+        lib.pd_sd3_vae_decode.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p]
+        lib.pd_sd3_vae_encode.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_int32, C.c_void_p]
         self.text_cfg: Optional[SD3TextConfig] = None
+        self.vae_cfg: Optional[SD3VaeConfig] = None
+        self.vae_has_encoder = False
         c = pd_sd3_config(cfg.in_channels, cfg.out_channels, cfg.patch, cfg.heads, cfg.head_dim, cfg.layers, cfg.cn_layers,
                           cfg.joint_dim, cfg.pooled_dim, cfg.pos_embed_max_size, cfg.cn_pos_embed_max_size,
                           1 if cfg.force_zeros_for_pooled_projection else 0, 1 if cfg.qk_norm else 0,
@@ -363,8 +463,10 @@ class SD3Engine:
         known = {n for n, _ in self.base.param_names()}
         unexpected = []
         for name, arr in (sd.items() if isinstance(sd, dict) else sd):
-            if not name.startswith(("transformer.", "controlnet.", "text_encoder.", "text_encoder_2.", "text_encoder_3.")):
+            if not name.startswith(("transformer.", "controlnet.", "text_encoder.", "text_encoder_2.", "text_encoder_3.", "vae.")):
                 continue
+            if name.startswith("vae.") and (self.vae_cfg is None or name not in known):
+                continue   # no VAE on this engine, or its encoder half was not configured: not its tensors
             if name.startswith("text_encoder"):
                 # encoders this engine has not configured, and T5's tied copy of shared.weight, are not its tensors
                 if self.text_cfg is None or name == "text_encoder_3.encoder.embed_tokens.weight" or name not in known:
@@ -481,13 +583,90 @@ class SD3Engine:
         self.base._check(self.base.lib.pd_sd3_text_encoder(self.base._h, idx, ptr, Bn, c.max_positions, int(clip_skip or 0), mem, hptr, pptr))
         return hid, po
 
+    # ------------------------------------------------------------------ VAE
+    def configure_vae(self, cfg: SD3VaeConfig = SD3_MEDIUM_VAE, encoder: bool = True) -> None:
+        """Registers SD3's VAE (decoder, and the encoder unless encoder=False) on this engine; its tensors then load through
+        load_state_dict under the checkpoint's ``vae.`` names.  Once per engine."""
+        if len(cfg.ch_mult) > E.PD_MAX_LEVELS:
+            raise ValueError(f"at most {E.PD_MAX_LEVELS} levels")
+        if cfg.z_channels != self.cfg.in_channels:
+            raise ValueError(f"the VAE has {cfg.z_channels} latent channels, the SD3 networks take {self.cfg.in_channels}")
+        c = pd_sd3_vae_config()
+        c.ch, c.num_levels, c.num_res_blocks, c.z_channels, c.out_ch = cfg.ch, len(cfg.ch_mult), cfg.num_res_blocks, cfg.z_channels, cfg.out_ch
+        for i, m in enumerate(cfg.ch_mult):
+            c.ch_mult[i] = m
+        c.encoder, c.quant_conv, c.post_quant_conv = int(bool(encoder)), int(cfg.quant_conv), int(cfg.post_quant_conv)
+        c.scaling_factor, c.shift_factor = float(cfg.scaling_factor), float(cfg.shift_factor)
+        self.base._check(self.base.lib.pd_sd3_vae_configure(self.base._h, C.byref(c)))
+        self.vae_cfg, self.vae_has_encoder = cfg, bool(encoder)
+
+    def vae_weights_missing(self) -> int:
+        return int(self.base.lib.pd_sd3_vae_weights_missing(self.base._h))
+
+    def _need_vae(self, encoder: bool = False):
+        if self.vae_cfg is None or (encoder and not self.vae_has_encoder):
+            raise E.PdError("this engine has no SD3 VAE" + (" encoder" if encoder else "") + ": call configure_vae first")
+        return self.vae_cfg
+
+    def vae_decode(self, latents, raw: bool = False):
+        """vae.decode(latents / scaling_factor + shift_factor) (promptdiffusioncontrolnetpipeline_sd3.py:1271-1273): latents
+        [B, z, h, w] -> images [B, 3, 8h, 8w] in about [-1, 1]; raw=True decodes the latents as they are.  NumPy in, NumPy out; CUDA
+        tensor in, CUDA tensor out."""
+        cfg = self._need_vae()
+        b = E._Buf(latents)
+        if b.owner.ndim != 4 or b.owner.shape[1] != cfg.z_channels:
+            raise ValueError(f"latents must be [B, {cfg.z_channels}, h, w]")
+        Bn, _, h, w = b.owner.shape
+        out, optr = self._out(b.mem, b.owner, (Bn, cfg.out_ch, cfg.downscale * h, cfg.downscale * w))
+        self.base._order_after_torch(b.mem)
+        self.base._check(self.base.lib.pd_sd3_vae_decode(self.base._h, b.ptr, Bn, h, w, b.mem, int(bool(raw)), optr))
+        return out
+
+    def vae_encode(self, images, mode: str = "sample", noise=None, raw: bool = False):
+        """vae.encode(images).latent_dist, then (z - shift_factor) * scaling_factor (promptdiffusioncontrolnetpipeline_sd3.py:1132-1133):
+        images [B, 3, H, W] in [-1, 1] ->
+          "sample":  mean + std * noise, noise [B, z, H/8, W/8] from the caller or, with noise=None, the engine's seeded draw (set_rng)
+          "mean":    the posterior's mode
+          "moments": the encoder's (mean ; logvar) [B, 2z, H/8, W/8], unscaled
+        raw=True leaves the shift and the scaling to the caller (what encode_support_pair returns)."""
+        cfg = self._need_vae(encoder=True)
+        if mode not in E.VAE_ENCODE_MODES:
+            raise ValueError(f"mode must be one of {sorted(E.VAE_ENCODE_MODES)}")
+        what = E.VAE_ENCODE_MODES[mode]
+        b, nb = E._Buf(images), E._Buf(noise)
+        if nb.mem is not None and nb.mem != b.mem:
+            raise E.PdError("images and noise must live in the same memory space")
+        if b.owner.ndim != 4 or b.owner.shape[1] != cfg.out_ch:
+            raise ValueError(f"images must be [B, {cfg.out_ch}, H, W]")
+        Bn, _, H, Wd = b.owner.shape
+        ds, z = cfg.downscale, cfg.z_channels
+        if H % ds or Wd % ds:
+            raise ValueError(f"H and W must be multiples of {ds}")
+        if nb.owner is not None and tuple(nb.owner.shape) != (Bn, z, H // ds, Wd // ds):
+            raise ValueError(f"noise must be [{Bn}, {z}, {H // ds}, {Wd // ds}]")
+        out, optr = self._out(b.mem, b.owner, (Bn, 2 * z if what == E.PD_VAE_MOMENTS else z, H // ds, Wd // ds))
+        self.base._order_after_torch(b.mem)
+        self.base._check(self.base.lib.pd_sd3_vae_encode(self.base._h, b.ptr, Bn, H, Wd, b.mem, what,
+                                                         nb.ptr if what == E.PD_VAE_SAMPLE else None, int(bool(raw)), optr))
+        return out
+
     def init_random_weights(self, seed: int = 1234) -> None:
         self.base.init_random_weights(seed)
 
     def encode_support_pair(self, cond, gt, vae=None):
         """SD3PromptDiffusionModel.encode_support_pair (promptdiffusioncontrolnet_sd3.py:189-198): down_proj (Conv2d 6 -> 3, 3x3)
         over cat([cond, gt], 1) on the engine; with a `vae` the caller's encoder turns the result into latents
-        (``vae.encode(x).latent_dist.sample()``), as the reference does."""
+        (``vae.encode(x).latent_dist.sample()``), as the reference does; without one, an engine with a VAE encoder does the same itself
+        (``vae_encode(x, raw=True)``: scaling stays with the caller, as in the reference); an engine without returns the projection."""
+        out = self.down_proj(cond, gt)
+        if vae is not None:
+            return vae.encode(out).latent_dist.sample()
+        if self.vae_cfg is not None and self.vae_has_encoder:
+            return self.vae_encode(out, mode="sample", raw=True)
+        return out
+
+    def down_proj(self, cond, gt):
+        """controlnet.down_proj (Conv2d 6 -> 3, 3x3) over cat([cond, gt], 1): cond, gt [B, 3, H, W] -> [B, 3, H, W]."""
         b0, b1 = E._Buf(cond), E._Buf(gt)
         if b0.mem != b1.mem or tuple(b0.owner.shape) != tuple(b1.owner.shape) or b0.owner.shape[1] != 3:
             raise ValueError("cond and gt must be [B, 3, H, W] in the same memory space")
@@ -502,14 +681,13 @@ class SD3Engine:
             pair = np.ascontiguousarray(np.concatenate([b0.owner, b1.owner], 1), np.float32)
             out = np.empty((Bn, 3, H, Wd), np.float32)
             self.base._check(self.base.lib.pd_sd3_down_proj(self.base._h, pair.ctypes.data, Bn, H, Wd, b0.mem, out.ctypes.data))
-        if vae is not None:
-            return vae.encode(out).latent_dist.sample()
         return out
 
     def weights_missing(self) -> int:
-        """SD3 tensors still unloaded: both networks, plus the text encoders once configure_text registered them."""
+        """SD3 tensors still unloaded: both networks, plus the text encoders / the VAE once configure_text / configure_vae registered them."""
         n = int(self.base.lib.pd_sd3_weights_missing(self.base._h))
-        return n + (self.text_weights_missing() if self.text_cfg is not None else 0)
+        n += self.text_weights_missing() if self.text_cfg is not None else 0
+        return n + (self.vae_weights_missing() if self.vae_cfg is not None else 0)
 
     # ------------------------------------------------------------------ calls
     def _args(self, latents, context, pooled, cond, pair, scale, timestep=None, rows=None, cn_pooled=None):
