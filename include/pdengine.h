@@ -305,6 +305,45 @@ int pd_image_load(pd_engine* e, const pd_image_load_args* args);
 int pd_image_store(pd_engine* e, const float* src, int32_t B, int32_t C, int32_t H, int32_t W, int32_t mem_src, float mul, float add,
                    int32_t rounding, uint8_t* dst, int32_t mem_dst);
 
+/* Canny edge detector: the annotator of the reference's `canny` task (annotator/canny/__init__.py: cv2.Canny(img, low, high), called
+ * with 100 and 200).  It has no weights and every step is integer arithmetic, so the result is pinned byte for byte -- to a
+ * restatement of OpenCV's portable C++ path (canny.cpp, aperture 3, L2gradient = false), which tests/canny_ref.py states in NumPy:
+ *   lo = floor(low), hi = floor(high), swapped if lo > hi.  Per channel, 3x3 Sobel in int32 over replicated borders:
+ *   dx = (p[-1,+1] + 2 p[0,+1] + p[+1,+1]) - (p[-1,-1] + 2 p[0,-1] + p[+1,-1]) ([row, col] offsets), dy its transpose, n = |dx| + |dy|.
+ *   With C = 3 a pixel takes dx, dy and m = n from the channel with the largest n (the lowest index on a tie).  m is 0 outside the
+ *   picture.  A pixel is a candidate iff m > lo and, with x = |dx|, y = |dy| << 15, t22 = 13573 x, t67 = t22 + (x << 16):
+ *     y < t22:        m > m[0,-1] and m >= m[0,+1]
+ *     else y > t67:   m > m[-1,0] and m >= m[+1,0]
+ *     else:           s = (dx ^ dy) < 0 ? -1 : +1;  m > m[-1,-s] and m > m[+1,+s]
+ *   A candidate with m > hi is strong, the others are weak.  The output is 255 at every candidate that is 8-connected, through
+ *   candidates, to a strong one, and 0 elsewhere.
+ * The connection is found on the GPU: a kernel that promotes weak pixels next to strong ones inside 64 x 64 tiles is relaunched
+ * until a launch changes nothing (at most one launch per pixel, else an error).  Promotion is monotone, so the result is the same
+ * bytes in every run; only the number of launches (stat "canny_sweeps", of the last call) may differ.
+ * src: uint8 [B, H, W, C] (NHWC), C 1 or 3, H, W >= 1.  At least one destination: dst_u8 [B, H, W] uint8 (0 / 255) and / or dst_f, an
+ * fp32 NCHW tensor [B, Cf, H, W] whose channels c_off .. c_off + 2 all receive (v / 255) * mul + add with pd_image_load's rounding
+ * (the reference's HWC3 of a grey map, in the layout of `query` and of one half of the pair); its other channels are not touched.
+ * Every pointer lives in its own memory space.  The state map, the sweep flags and the staging of host buffers are engine-owned
+ * and grow on demand (counted in stat "image_allocs"): a repeated call at the same shape allocates nothing.  Runs on the engine's
+ * stream, synchronised on return. */
+#define PD_CANNY_NONE   0   /* states of the intermediate map (pd_op_canny_hysteresis): not a candidate */
+#define PD_CANNY_WEAK   1   /* a candidate with m <= hi */
+#define PD_CANNY_STRONG 2   /* a candidate with m > hi, or a weak one that the hysteresis reached */
+typedef struct pd_canny_args {
+    const uint8_t* src;       /* [B, H, W, C] */
+    int32_t B, H, W, C;
+    int32_t mem_src;          /* PD_MEM_* of src */
+    float low, high;          /* finite */
+    uint8_t* dst_u8;          /* [B, H, W] or NULL */
+    int32_t mem_u8;           /* PD_MEM_* of dst_u8 */
+    int32_t Cf, c_off;        /* 0 <= c_off, c_off + 3 <= Cf; only read with dst_f */
+    float* dst_f;             /* [B, Cf, H, W] or NULL */
+    float mul, add;
+    int32_t mem_f;            /* PD_MEM_* of dst_f */
+    int32_t reserved[4];      /* zero */
+} pd_canny_args;
+int pd_canny(pd_engine* e, const pd_canny_args* args);
+
 /* operator boundary: eps = apply_model(x, t, cond), cldm/cldm.py:369-382.
  *   x [Bf,in_ch,h,w], t [Bf] (int64), ctx [Bf,L,D], pair [Bf,hint_ch,8h,8w], query [Bf,q_ch,8h,8w],
  *   scales [13] or NULL.  eps_out [Bf,out_ch,h,w].  residuals_out (optional): the 13 scaled
@@ -548,7 +587,8 @@ int pd_set_option(pd_engine* e, const char* key, int64_t value);
 int64_t pd_get_stat(pd_engine* e, const char* key);
 /* Per-launch timing: while option "profile" is 1 the engine brackets every contraction launch with HIP
  * events on its stream.  klass 0 = igemm_kernel on a conv3x3, 1 = igemm_kernel / rgemm_kernel on a conv1x1/linear,
- * 2 = attention, 3 = the conv3x3 patch kernels (all generations), 4 = st_front / st_tail, -1 = all.  One bracket = one launch (split-K finalize excluded).
+ * 2 = attention, 3 = the conv3x3 patch kernels (all generations), 4 = st_front / st_tail, 5 / 6 / 7 = pd_canny's suppression, sweep and
+ * emit kernels, -1 = all.  One bracket = one launch (split-K finalize excluded).
  * Returns summed device time, launch count and algorithmic FLOPs (2*M*N*K, logical channel counts).  The elapsed time of
  * a bracket around an empty one-block kernel, calibrated when "profile" is switched on (stat "event_overhead_ns"), is
  * taken off every bracket. */

@@ -15,6 +15,7 @@
  *   pd_op_spatial_transformer  one SpatialTransformer block of the loaded networks  attention.py:271-275,321-340
  *   pd_op_time_embed timestep_embedding + the time_embed MLP of a loaded network    util.py:154-174, openaimodel.py:526-531
  *   pd_op_vae_downsample  the KL-VAE encoder's Downsample (asymmetric pad)          ldm/modules/diffusionmodules/model.py:68-88
+ *   pd_op_canny_hysteresis  the flood of cv2.Canny's hysteresis on a given state map  annotator/canny/__init__.py
  */
 #ifndef PDENGINE_OPS_H
 #define PDENGINE_OPS_H
@@ -105,6 +106,11 @@ int pd_op_hed_stage_tail(pd_engine* e, const float* x, const float* w, const flo
  * [B, H >> i, W >> i] (H, W multiples of 16); cw [5], cb [1]; what PD_HED_EDGE: out [B, 1, H, W] = sigmoid(cb + sum_i cw[i] up_i),
  * PD_HED_SIDES: out [B, 5, H, W] = up_i, the bilinear upsamples (align_corners = False) to H x W. */
 int pd_op_hed_fuse(pd_engine* e, const float* scores, const float* cw, const float* cb, int B, int H, int W, int what, float* out);
+/* The hysteresis of the Canny edge detector (canny_hysteresis_kernel and its sweep loop, as pd_canny runs them) on a caller's state
+ * map: states [B, H, W] uint8 of PD_CANNY_NONE (0), PD_CANNY_WEAK (1), PD_CANNY_STRONG (2) -- any other value counts as NONE and is
+ * passed through -> out [B, H, W], the same map with every weak pixel that is 8-connected, through weak pixels, to a strong one set
+ * to PD_CANNY_STRONG.  states and out live in `mem`.  Stat "canny_sweeps" holds the launches it took. */
+int pd_op_canny_hysteresis(pd_engine* e, const uint8_t* states, int B, int H, int W, int mem, uint8_t* out);
 #ifdef __cplusplus
 }
 #endif

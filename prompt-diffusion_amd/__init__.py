@@ -10,11 +10,11 @@ __version__ = "0.1.0"
 _PIPELINES = ("PromptDiffusionPipeline", "PromptDiffusionImg2ImgPipeline", "PromptDiffusionInpaintPipeline")
 
 
-def __getattr__(name):   # the pipelines and the annotator, imported on first use (the package itself stays light)
+def __getattr__(name):   # the pipelines and the annotators, imported on first use (the package itself stays light)
     if name in _PIPELINES:
         from . import pipeline
         return getattr(pipeline, name)
-    if name == "HEDdetector":   # the annotator (annotators.py), NumPy only on import
-        from .annotators import HEDdetector
-        return HEDdetector
+    if name in ("HEDdetector", "CannyDetector"):   # the annotators (annotators.py), NumPy only on import
+        from . import annotators
+        return getattr(annotators, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -3,8 +3,13 @@
 ``HEDdetector`` is the reference's ``annotator.hed.HEDdetector`` with the network on the engine (``Engine.hed``: the VGG trunk,
 the five side outputs and their fusion are gfx950 kernels behind ``pd_hed_detect``); the uint8 ends stay on the host, or run on
 the GPU as well with ``detect(..., device=True)``.
-``HWC3`` and ``resize_image`` restate ``annotator/util.py`` in NumPy + PIL.  ``nms`` (cv2 blur / dilate) and the other annotators
-(MiDaS, UniFormer, Canny) are not built.
+``CannyDetector`` is the reference's ``annotator.canny.CannyDetector`` (``cv2.Canny(img, low, high)``) with all of it on the engine
+(``Engine.canny``: Sobel / non-maximum suppression, the hysteresis flood and the output are gfx950 kernels behind ``pd_canny``).  Its
+arithmetic is integer and pinned byte for byte to a NumPy restatement of OpenCV's algorithm (tests/canny_ref.py), and to ``cv2`` itself
+only where ``cv2`` is installed; neither this module nor the engine needs OpenCV.
+``HWC3`` and ``resize_image`` restate ``annotator/util.py`` in NumPy + PIL.  ``nms`` (the scribble step of ``annotator/hed``, which
+goes through cv2's float ``GaussianBlur``) and the annotators with networks whose code and weights are not at hand (MiDaS,
+UniFormer) are not built.
 """
 from __future__ import annotations
 
@@ -75,3 +80,28 @@ class HEDdetector:
         if np.asarray(input_image).ndim != 3:
             raise ValueError("HEDdetector expects one HWC image")
         return self.detect(np.asarray(input_image)[None])[0]
+
+
+class CannyDetector:
+    """``annotator.canny.CannyDetector`` on an engine (any configuration: the detector has no weights)."""
+
+    def __init__(self, engine):
+        self.engine = engine
+
+    def detect(self, images, low_threshold, high_threshold, device: bool = False):
+        """Batched form: uint8 [B, H, W, 3], [B, H, W, 1] or [B, H, W] (NumPy, or a CPU / CUDA torch tensor) -> uint8 [B, H, W] of
+        0 / 255.  device: the edge map stays on the GPU and comes back as a CUDA tensor (a CUDA tensor in then never leaves it);
+        otherwise a NumPy array comes back."""
+        if not device:
+            return self.engine.canny(images, low_threshold, high_threshold, host=True)
+        if not hasattr(images, "is_cuda"):
+            import torch
+            images = torch.from_numpy(np.array(images))   # (a copy: torch wants a writable array)
+        return self.engine.canny(images, low_threshold, high_threshold)
+
+    def __call__(self, img: np.ndarray, low_threshold, high_threshold) -> np.ndarray:
+        """uint8 HW or HWC -> uint8 HW, as the reference's ``__call__``."""
+        img = np.asarray(img)
+        if img.ndim not in (2, 3):
+            raise ValueError("CannyDetector expects one HW or HWC image")
+        return self.detect(img[None], low_threshold, high_threshold)[0]

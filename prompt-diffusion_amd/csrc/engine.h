@@ -578,6 +578,15 @@ struct pd_engine {
     int image_grow(ImageBuf& b, size_t bytes);
     void image_release();
 
+    // Canny edge detector (canny.cpp, canny.hip): scratch that grows like the image ends' and is counted in image_allocs with it
+    ImageBuf canny_states;                      // the state map [B][H][W]
+    ImageBuf canny_flags;                       // kCannyBatch ints: sweep i of a batch raises flag i
+    int* canny_flags_host = nullptr;            // their pinned copy, read after every batch
+    static constexpr int kCannyBatch = 4;       // sweeps enqueued between two looks at the flags
+    long long canny_sweeps = 0;                 // stat "canny_sweeps": hysteresis launches of the last call
+    // sweeps the device map [B][H][W] to its fixed point: at most B * H * W + 1 launches, else an error
+    int canny_hysteresis(uint8_t* states_dev, int B, int H, int W);
+
     // SD3 / MMDiT path (sd3.cpp)
     pd_sd3_config sd3{};
     Sd3NetW sd3_tr, sd3_cn;

@@ -86,8 +86,9 @@ int pd_engine::image_grow(ImageBuf& b, size_t bytes) {
 }
 
 void pd_engine::image_release() {
-    for (ImageBuf* b : {&img_u8, &img_tmp, &img_f32, &img_tab})
+    for (ImageBuf* b : {&img_u8, &img_tmp, &img_f32, &img_tab, &canny_states, &canny_flags})
         if (b->p) { (void)hipFree(b->p); b->p = nullptr; b->cap = 0; }
+    if (canny_flags_host) { (void)hipHostFree(canny_flags_host); canny_flags_host = nullptr; }
 }
 
 extern "C" int pd_image_load(pd_engine* e, const pd_image_load_args* a) {

@@ -18,14 +18,6 @@ __device__ __forceinline__ int clip8(int acc) {
     return v < 0 ? 0 : (v > 255 ? 255 : v);
 }
 
-// x * m + a with the product and the sum each rounded once.  (hipcc contracts a * b + c into an FMA by default, through __fmul_rn /
-// __fadd_rn as well: they are plain operators in HIP's headers.  The pragma is what keeps the two roundings apart.)
-__device__ __forceinline__ float mul_add_rn(float x, float m, float a) {
-#pragma clang fp contract(off)
-    const float p = x * m;
-    return p + a;
-}
-
 // 3 * n bytes (n <= PX pixels) starting at p; `vec`: p is 4-byte aligned and n == PX -> three dword loads
 __device__ __forceinline__ void load_px(const uint8_t* __restrict__ p, bool vec, int n, int v[3 * PX]) {
     if (vec) {

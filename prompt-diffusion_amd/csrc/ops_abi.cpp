@@ -633,4 +633,19 @@ int pd_op_hed_fuse(pd_engine* e, const float* scores, const float* cw, const flo
     HIP_OK(hipMemcpy(out, dout.p, n_out * 4, hipMemcpyDeviceToHost));
     return 0;
 }
+
+int pd_op_canny_hysteresis(pd_engine* e, const uint8_t* states, int B, int H, int W, int mem, uint8_t* out) {
+    if (!e || !states || !out) { pd_set_error("null argument"); return 1; }
+    if (B < 1 || H < 1 || W < 1) { pd_set_error("pd_op_canny_hysteresis: [%d, %d, %d]: sizes must be >= 1", B, H, W); return 1; }
+    HIP_OK(hipSetDevice(e->device));
+    const size_t n = (size_t)B * H * W;
+    const bool dev = mem == PD_MEM_DEVICE;
+    PD_TRY(e->image_grow(e->canny_states, n));   // the sweeps run in place on the engine's own map
+    uint8_t* map = reinterpret_cast<uint8_t*>(e->canny_states.p);
+    HIP_OK(hipMemcpyAsync(map, states, n, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, e->stream));
+    PD_TRY(e->canny_hysteresis(map, B, H, W));
+    HIP_OK(hipMemcpyAsync(out, map, n, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+    return 0;
+}
 }  // extern "C"

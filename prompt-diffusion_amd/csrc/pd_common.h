@@ -107,6 +107,15 @@ __device__ __forceinline__ int xcd_tile_order(int bid, int nblk) {
 __device__ __forceinline__ int swz8_chunk(int row, int chunk) { return (chunk ^ (row >> 1)) & 7; }
 __device__ __forceinline__ int swz8(int row, int chunk) { return (row * 128) + (swz8_chunk(row, chunk) << 4); }
 
+// x * m + a with the product and the sum each rounded once: the value map of the image ends (image_io.hip) and of the Canny edge map
+// (canny.hip).  (hipcc contracts a * b + c into an FMA by default, through __fmul_rn / __fadd_rn as well: they are plain operators in
+// HIP's headers.  The pragma is what keeps the two roundings apart.)
+__device__ __forceinline__ float mul_add_rn(float x, float m, float a) {
+#pragma clang fp contract(off)
+    const float p = x * m;
+    return p + a;
+}
+
 // 4 consecutive elements of a [.., C] row, as floats, from an f32 or bf16 buffer
 __device__ __forceinline__ f32x4 load4(const void* base, size_t idx, int dt) {
     f32x4 r;
@@ -437,6 +446,16 @@ int launch_image_vpass(const uint8_t* src, float* dst, const int* bounds, const 
                        int C, int c_off, int tile, float mul, float add, hipStream_t s);
 // src [B][C][H][W] fp32, C in {1, 3} -> dst [B][H][W][C] u8 = round(min(max(x * mul + add, 0), 1) * 255), half to even or truncated
 int launch_image_store(const float* src, uint8_t* dst, int B, int C, int H, int W, float mul, float add, int trunc, hipStream_t s);
+// canny.hip: the Canny edge detector (canny.cpp; include/pdengine.h "Canny edge detector").  States: PD_CANNY_NONE / WEAK / STRONG
+constexpr int CANNY_NONE = 0, CANNY_WEAK = 1, CANNY_STRONG = 2;
+// src [B][H][W][C] u8, C in {1, 3} -> states [B][H][W] u8: Sobel, channel select and non-maximum suppression; lo <= hi, both strict
+int launch_canny_nms(const uint8_t* src, uint8_t* states, int B, int H, int W, int C, int lo, int hi, hipStream_t s);
+// one sweep over states [B][H][W]: inside every tile, weak pixels 8-connected to a strong one become strong; *flag = 1 if any tile changed
+int launch_canny_hysteresis(uint8_t* states, int B, int H, int W, int* flag, hipStream_t s);
+// states -> dst_u8 [B][H][W] (255 where strong, else 0; may be null) and / or channels c_off .. c_off + 2 of dst_f [B][Cf][H][W] fp32 =
+// (v / 255) * mul + add (may be null)
+int launch_canny_emit(const uint8_t* states, uint8_t* dst_u8, float* dst_f, int B, int H, int W, int Cf, int c_off, float mul, float add,
+                      hipStream_t s);
 // sd3_kernels.hip: element-wise pieces of the MMDiT path
 // y_dt == DT_FP8: y holds e4m3 bytes and y_scale[row] the row's scale (max |value| / 448); add: x <- x + add first (written back)
 int launch_adaln(const void* x, int x_dt, void* y, int y_dt, const float* mod, int mod_stride, int shift_off, int scale_off, int rows,

@@ -1175,7 +1175,8 @@ int64_t pd_get_stat(pd_engine* e, const char* key) {
     if (!strcmp(key, "side_workspace_bytes")) return (int64_t)e->arena2.cap;   // what the first stage / HED / text encoders run in (in_side_workspace)
     if (!strcmp(key, "weight_bytes")) return (int64_t)e->weight_bytes;
     if (!strcmp(key, "launches")) return (int64_t)e->launches;
-    if (!strcmp(key, "image_allocs")) return (int64_t)e->image_allocs;   // device allocations of pd_image_load / pd_image_store so far
+    if (!strcmp(key, "image_allocs")) return (int64_t)e->image_allocs;   // allocations of pd_image_load / pd_image_store / pd_canny so far
+    if (!strcmp(key, "canny_sweeps")) return (int64_t)e->canny_sweeps;   // hysteresis launches of the last pd_canny / pd_op_canny_hysteresis
     if (!strcmp(key, "gn_from_slabs")) return (int64_t)e->gn_from_slabs;
     if (!strcmp(key, "vae_flash_launches")) return (int64_t)e->vae_flash_launches;   // of which: vae_attention.hip
     if (!strcmp(key, "ups_fold_launches")) return (int64_t)e->ups_fold_launches;   // of which: conv_upfold.hip's four-phase upsample conv
@@ -1199,7 +1200,7 @@ int64_t pd_get_stat(pd_engine* e, const char* key) {
 }
 
 // Per-launch HIP-event timing collected while option "profile" is on.  klass: 0 igemm conv3x3,
-// 1 igemm conv1x1 / linear, 2 attention, 3 conv3x3 LDS-patch kernel, -1 all.
+// 1 igemm conv1x1 / linear, 2 attention, 3 conv3x3 LDS-patch kernel, 4 st_front / st_tail, 5 / 6 / 7 the Canny kernels, -1 all.
 int pd_profile_read(pd_engine* e, int32_t klass, double* total_ms, int64_t* n_launches, double* flops) {
     if (!e) { pd_set_error("null engine"); return 1; }
     HIP_OK(hipStreamSynchronize(e->stream));

@@ -106,6 +106,15 @@ class pd_image_load_args(C.Structure):
     ]
 
 
+class pd_canny_args(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("mem_src", C.c_int32),
+        ("low", C.c_float), ("high", C.c_float), ("dst_u8", C.c_void_p), ("mem_u8", C.c_int32), ("Cf", C.c_int32),
+        ("c_off", C.c_int32), ("dst_f", C.c_void_p), ("mul", C.c_float), ("add", C.c_float), ("mem_f", C.c_int32),
+        ("reserved", C.c_int32 * 4),
+    ]
+
+
 class pd_lms_args(C.Structure):
     _fields_ = [
         ("kind", C.c_int32), ("order", C.c_int32), ("solver_type", C.c_int32), ("lower_order_final", C.c_int32),
@@ -247,6 +256,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.pd_resample_coefficients.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]
     lib.pd_image_load.argtypes = [C.c_void_p, C.POINTER(pd_image_load_args)]
     lib.pd_image_store.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_int32]
+    lib.pd_canny.argtypes = [C.c_void_p, C.POINTER(pd_canny_args)]
+    lib.pd_op_canny_hysteresis.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
     if path is None:
         _lib = lib
     return lib
@@ -267,7 +278,7 @@ EXPORTS = [
     "pd_set_freeu", "pd_get_freeu", "pd_op_freeu_concat",
     "pd_philox4x32_10", "pd_set_rng", "pd_get_rng", "pd_randn",
     "pd_hed_configure", "pd_hed_weights_missing", "pd_hed_detect", "pd_op_hed_stage_tail", "pd_op_hed_fuse",
-    "pd_resample_coefficients", "pd_image_load", "pd_image_store",
+    "pd_resample_coefficients", "pd_image_load", "pd_image_store", "pd_canny", "pd_op_canny_hysteresis",
     "pd_sd3_text_configure", "pd_sd3_text_weights_missing", "pd_sd3_encode_prompt", "pd_sd3_text_encoder", "pd_t5_relative_buckets",
     "pd_sd3_vae_configure", "pd_sd3_vae_weights_missing", "pd_sd3_vae_config_layout", "pd_sd3_vae_decode", "pd_sd3_vae_encode", "pd_op_vae_attention", "pd_bench_vae_attention",
 ]
@@ -819,6 +830,70 @@ class Engine:
             dp, dmem = out.data_ptr(), PD_MEM_DEVICE
         self._order_after_torch(PD_MEM_DEVICE if PD_MEM_DEVICE in (b.mem, dmem) else PD_MEM_HOST)
         self._check(self.lib.pd_image_store(self._h, b.ptr, B, Cc, H, W, b.mem, float(mul), float(add), IMAGE_ROUNDINGS[rounding], dp, dmem))
+        return out
+
+    # ------------------------------------------------------------------ Canny edge detector (pd_canny)
+    def canny(self, images, low: float, high: float, *, out=None, c_off: int = 0, mul: float = 1.0, add: float = 0.0, host: bool = False):
+        """cv2.Canny(img, low, high) (aperture 3, L1 magnitude; annotator/canny/__init__.py) on the device, byte for byte:
+        uint8 pictures [B, H, W, C] with C 1 or 3, or [B, H, W] (NumPy, or a CPU / CUDA torch tensor) -> uint8 [B, H, W] of 0 / 255
+        (pd_canny).  A CUDA tensor comes out; a NumPy array with host=True or for a NumPy input.  out: an existing contiguous
+        float32 [B, Cf, H, W] (CUDA tensor, CPU tensor or NumPy array) whose channels c_off .. c_off + 2 also receive the edge map as
+        (edge / 255) * mul + add in float32, replicated to three channels (HWC3 of the grey map); its other channels keep their
+        values."""
+        owner, sp, smem, sh = self._u8_source(images)
+        if len(sh) == 3:
+            sh = tuple(sh) + (1,)
+        if len(sh) != 4:
+            raise ValueError(f"images must be uint8 [B, H, W, C] or [B, H, W], got {tuple(sh)}")
+        B, H, W, Cs = (int(v) for v in sh)   # pd_canny refuses a C other than 1 or 3
+        a = pd_canny_args()
+        a.src, a.B, a.H, a.W, a.C, a.mem_src = sp, B, H, W, Cs, smem
+        a.low, a.high = float(low), float(high)
+        any_dev = smem == PD_MEM_DEVICE
+        if out is not None:
+            if len(out.shape) != 4 or tuple(out.shape) != (B, out.shape[1], H, W):
+                raise ValueError(f"out must be [{B}, Cf, {H}, {W}], got {tuple(out.shape)}")
+            if _is_torch(out):
+                import torch
+                if out.dtype != torch.float32 or not out.is_contiguous():
+                    raise ValueError("out must be a contiguous float32 tensor")
+                a.dst_f, a.mem_f = out.data_ptr(), PD_MEM_DEVICE if out.is_cuda else PD_MEM_HOST
+            else:
+                if out.dtype != np.float32 or not out.flags.c_contiguous:
+                    raise ValueError("out must be a C-contiguous float32 array")
+                a.dst_f, a.mem_f = out.ctypes.data, PD_MEM_HOST
+            a.Cf, a.c_off, a.mul, a.add = int(out.shape[1]), int(c_off), float(mul), float(add)
+            any_dev = any_dev or a.mem_f == PD_MEM_DEVICE
+        if host or not _is_torch(images):
+            edges = np.empty((B, H, W), np.uint8)
+            a.dst_u8, a.mem_u8 = edges.ctypes.data, PD_MEM_HOST
+        else:
+            import torch
+            edges = torch.empty((B, H, W), dtype=torch.uint8, device=owner.device if smem == PD_MEM_DEVICE else self._torch_device())
+            a.dst_u8, a.mem_u8 = edges.data_ptr(), PD_MEM_DEVICE
+            any_dev = True
+        self._order_after_torch(PD_MEM_DEVICE if any_dev else PD_MEM_HOST)
+        self._check(self.lib.pd_canny(self._h, C.byref(a)))
+        del owner
+        return edges
+
+    def canny_hysteresis(self, states):
+        """The hysteresis step alone on a state map (pd_op_canny_hysteresis): uint8 [B, H, W] of 0 (not a candidate), 1 (weak),
+        2 (strong) -> the same map with every weak pixel 8-connected, through weak pixels, to a strong one set to 2.  NumPy in,
+        NumPy out; CUDA tensor in, CUDA tensor out.  stat("canny_sweeps") holds the launches it took."""
+        owner, sp, smem, sh = self._u8_source(states)
+        if len(sh) != 3:
+            raise ValueError(f"states must be uint8 [B, H, W], got {tuple(sh)}")
+        if _is_torch(states) and smem == PD_MEM_DEVICE:
+            import torch
+            out = torch.empty(tuple(sh), dtype=torch.uint8, device=owner.device)
+            op = out.data_ptr()
+        else:
+            out = np.empty(tuple(sh), np.uint8)
+            op = out.ctypes.data
+        self._order_after_torch(smem)
+        self._check(self.lib.pd_op_canny_hysteresis(self._h, sp, int(sh[0]), int(sh[1]), int(sh[2]), smem, op))
+        del owner
         return out
 
     def text_weights_missing(self) -> int:
