@@ -236,6 +236,53 @@ int pd_vae_encode(pd_engine* e, const float* images, int32_t B, int32_t H, int32
 /* number of encoder tensors not loaded yet (0 when the encoder is not built) */
 int pd_vae_encoder_weights_missing(pd_engine* e);
 
+/* Tiled and sliced VAE calls (diffusers AutoencoderKL.enable_tiling / enable_slicing; the reference's pipeline_prompt_diffusion.py:242-272).
+ * Opt-in engine state like pd_set_freeu: with both switches off every call runs exactly what it ran before.  `which` selects the VAE:
+ * PD_VAE_SD15 (pd_vae_decode / pd_vae_encode) or PD_VAE_SD3 (pd_sd3_vae_decode / pd_sd3_vae_encode).
+ *
+ * Tiling, with T = tile_latent, f = overlap_factor, u = 2^(num_levels - 1) = 8 (all of it diffusers' tiled_decode / tiled_encode):
+ *   decode of z [B, C, h, w], only when h > T or w > T:  ov = int(T (1 - f)), be = int(T u f), limit = T u - be.  For i in range(0, h, ov),
+ *   j in range(0, w, ov): tile = decoder(post_quant_conv(z[:, :, i:i+T, j:j+T])) (truncated at the border).  Then in row-major order and in
+ *   place: tile = blend_v(tile above, tile, be) if i > 0; tile = blend_h(tile to the left, tile, be) if j > 0; the output is the
+ *   concatenation of tile[:, :, :limit, :limit].  blend_v(a, b, e): e = min(a.H, b.H, e); b[y] = a[a.H - e + y] * (1 - y / e) + b[y] * (y / e)
+ *   for y < e, the two weights computed in double and rounded to fp32, both products and the sum rounded to fp32 on their own; blend_h
+ *   the same along W.
+ *   encode of x [B, 3, H, W], only when H > T u or W > T u:  ov = int(T u (1 - f)), be = int(T f), limit = T - be; a tile is
+ *   quant_conv(encoder(window)), the moments; blend and crop run on the moments and the posterior is taken once from the assembled ones.
+ * The last row / column of the grid may be a remainder of a single latent pixel; e then shrinks through the min.  Accepted: 0 < f <= 1/3
+ * and T f an integer (so that limit = ov u, which diffusers assumes silently); then each output value depends on at most four raw tiles and
+ * the engine assembles the output in one kernel, byte-identical in fp32 to the sequential procedure applied to the same tiles.
+ * Tiles of equal shape run through the layers as one batch, tile_batch tiles at a time.  A tile whose h_t * w_t is no multiple of 8 takes the
+ * flash attention kernel (2-byte modes); the fp32-storage modes reject such a call and name the tile.
+ *
+ * Slicing: with B > 1 every sample is decoded / encoded on its own, in order (and tiled, with both switches on); noise and seeded draws
+ * address the samples as in the unsliced call.
+ *
+ * pd_vae_set_tiling: with on != 0, tile_latent / overlap_factor / tile_batch replace the stored parameters, 0 = the default (T 64 for
+ * SD1.5 and 128 for SD3 -- 512 / 1024 pixels, diffusers' tile_sample_min_size = sample_size; f 0.25; tile_batch 4).  With on = 0 tiling
+ * is switched off and an argument of 0 KEEPS the stored parameter (pd_vae_set_tiling(e, which, 0, 0, 0, 0) is the plain disable call);
+ * a non-zero argument still replaces it.  A refused call changes nothing.
+ * pd_vae_get_tiling: the state with defaults resolved; any pointer may be NULL. */
+#define PD_VAE_SD15 0
+#define PD_VAE_SD3  1
+int pd_vae_set_tiling(pd_engine* e, int32_t which, int32_t on, int32_t tile_latent, double overlap_factor, int32_t tile_batch);
+int pd_vae_set_slicing(pd_engine* e, int32_t which, int32_t on);
+int pd_vae_get_tiling(pd_engine* e, int32_t which, int32_t* tiling, int32_t* slicing, int32_t* tile_latent, double* overlap_factor,
+                      int32_t* tile_batch);
+/* The tile grid of one tiled call; host only (no engine, no GPU).  decode (encode = 0): h, w are the latent size; encode (encode = 1): the
+ * image size, multiples of u.  *rows = *cols = 0 when the call is not tiled (h <= T and w <= T, resp. T u).  With tiles non-NULL (cap >=
+ * rows * cols entries, row-major): the input window (y0, x0, h, w) in input pixels, the kept output rectangle (oy, ox, oh, ow) and the
+ * tile's own output size (th, tw) in output pixels, the blend extents ev / eh against the tile above / to the left (0 in the first row /
+ * column) and cls, the index of the tile's shape class (tiles of equal h and w; numbered in order of first appearance, *classes of them). */
+typedef struct pd_vae_tile {
+    int32_t y0, x0, h, w;
+    int32_t oy, ox, oh, ow;
+    int32_t th, tw, ev, eh;
+    int32_t cls, reserved[3];
+} pd_vae_tile;
+int pd_vae_tile_plan(int32_t h, int32_t w, int32_t tile_latent, double overlap_factor, int32_t u, int32_t encode, int32_t* rows, int32_t* cols,
+                     int32_t* classes, pd_vae_tile* tiles, int32_t cap);
+
 /* HED edge detector: the annotator that turns a photograph into the condition map of `query` / `pair` (apply_hed of the reference's
  * demo; HEDdetector.__call__ and Network.forward, annotator/hed/__init__.py:71-114): a VGG-16 trunk of 13 conv3x3 + ReLU in five
  * stages, one conv1x1 score head per stage, the five score maps upsampled bilinearly (align_corners = False) to the input size,

@@ -111,6 +111,12 @@ int pd_op_hed_fuse(pd_engine* e, const float* scores, const float* cw, const flo
  * passed through -> out [B, H, W], the same map with every weak pixel that is 8-connected, through weak pixels, to a strong one set
  * to PD_CANNY_STRONG.  states and out live in `mem`.  Stat "canny_sweeps" holds the launches it took. */
 int pd_op_canny_hysteresis(pd_engine* e, const uint8_t* states, int B, int H, int W, int mem, uint8_t* out);
+/* The assembling kernel of a tiled VAE call (vae_tile_blend_kernel) alone, on a caller's tiles: plan = the rows x cols entries of
+ * pd_vae_tile_plan (th, tw, ev, eh, oh, ow are read); tiles = the tiles back to back in plan order, each fp32 [B][th][tw][Cpad] (NHWC, Cpad
+ * a multiple of 4).  nchw != 0: out [B][C][H][W] (the decode side, channels >= C dropped); else out [B][H][W][Cpad] (the encode side's
+ * moments); H x W is the sum of the kept rectangles.  fp32 in every mode, host arrays. */
+int pd_op_vae_tile_blend(pd_engine* e, const float* tiles, const pd_vae_tile* plan, int rows, int cols, int B, int C, int Cpad, int nchw,
+                         float* out);
 #ifdef __cplusplus
 }
 #endif

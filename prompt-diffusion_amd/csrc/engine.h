@@ -185,6 +185,23 @@ struct VaeEncW {
     int top = 0;
 };
 
+// The tile grid of a tiled VAE call (vae_tile.cpp: vae_make_tile_plan, what pd_vae_tile_plan returns) and what one run of it holds
+struct VaeTilePlan {
+    bool tiled = false;
+    int nrow = 0, ncol = 0, limit = 0, be = 0, nclass = 0;   // limit, be in output pixels
+    std::vector<pd_vae_tile> tiles;                          // row-major
+    std::vector<std::vector<int>> members;                   // per shape class: tile indices, row-major
+};
+struct VaeTileRun {
+    std::vector<float*> res;        // per class: the tile results, fp32 [members][B][th][tw][cpad]
+    long long* tile_off = nullptr;  // device tables (VaeBlendParams) ...
+    int *rows = nullptr, *cols = nullptr, *origins = nullptr;   // ... origins: (y0, x0) per tile, class by class
+    float* wtab = nullptr;
+    std::vector<int> origin_at;     // per class: its first entry in origins
+};
+// non-zero with the error set when (T, f) is not accepted; p.tiled false when the size needs no tiling
+int vae_make_tile_plan(int h, int w, int T, double f, int u, bool encode, VaeTilePlan& p);
+
 // HED edge detector (pd_hed_configure, hed.cpp): annotator/hed/__init__.py Network -- the 13 conv3x3 + ReLU of the VGG-16 trunk in five
 // stages (2, 2, 3, 3, 3), one conv1x1 C -> 1 score head per stage and the 5 -> 1 combine; heads and combine are fp32 vectors
 struct HedW {
@@ -538,10 +555,26 @@ struct pd_engine {
     // launch of vae_attention.hip, any N; else three launches per sample through sc [N][N] fp32 and pr [N][npad] T (N a multiple of 8,
     // npad = round_up(N, 64), the pad columns of vt and pr zero)
     int vae_attn_product(const void* qk, int ld, const void* vt, int npad, void* att, int B, int N, int C, bool flash, float* sc, void* pr);
-    // decode / encode behind the C ABI, shared by pd_vae_* and pd_sd3_vae_*
-    int vae_decode_call(VaeW& v, const float* latents, int B, int h, int w, int mem, float scale, float shift, float* images_out);
-    int vae_encode_call(VaeEncW& v, const float* images, int B, int H, int W, int mem, int what, const float* noise, float scale, float shift,
-                        float* out);
+    // the layers between the two layout kernels: z / x in the compute type (NHWC), img / mom fp32 NHWC allocated by the caller
+    int vae_decode_layers(VaeW& v, const Act& z, Act& img);
+    int vae_encode_layers(VaeEncW& v, const Act& x, Act& mom);
+    // decode / encode behind the C ABI, shared by pd_vae_* and pd_sd3_vae_*; which: PD_VAE_SD15 / PD_VAE_SD3 (the tiling state)
+    int vae_decode_call(VaeW& v, int which, const float* latents, int B, int h, int w, int mem, float scale, float shift, float* images_out);
+    int vae_encode_call(VaeEncW& v, int which, const float* images, int B, int H, int W, int mem, int what, const float* noise, float scale,
+                        float shift, float* out);
+    // Tiled / sliced calls (vae_tile.cpp; pd_vae_set_tiling, pd_vae_set_slicing).  All zero = off: the calls above then run as ever.
+    struct VaeTiling { bool tiling = false, slicing = false; int tile = 0; double overlap = 0.0; int batch = 0; };
+    VaeTiling vae_tiling[2];
+    bool vae_tile_odd_flash = false;   // set while tiles run: a tile with N % 8 != 0 takes the flash kernel on a VAE without flash_auto
+    std::vector<char> vae_tile_blob;   // host image of the device tables of the running tiled call (alive until the call's final sync)
+    long long vae_tiles_run = 0;       // stat "vae_tiles": tiles decoded / encoded so far
+    VaeTilePlan vae_plan_for(int which, int h, int w, int u, bool encode) const;   // .tiled false when the state or the size says no
+    int vae_check_tiles(const VaeTilePlan& p, const VaeDesc& d, int C, const char* who) const;
+    int vae_tile_setup(const VaeTilePlan& p, int B, int cpad, VaeTileRun& run);
+    int vae_tile_blend(const VaeTilePlan& p, const VaeTileRun& run, int B, int C, int cpad, bool nchw, float* out);
+    int vae_decode_managed(VaeW& v, int which, const float* src, int B, int h, int w, float* dout, float scale, float shift);
+    int vae_encode_managed(VaeEncW& v, int which, const float* src, int B, int H, int W, int what, const float* noise, float* dout, float scale,
+                           float shift);
     // Everything that runs outside a sampling step (first stage, HED, text encoders): `sizing` (a dry pass of the forward) measures the
     // workspace, which is the ControlNet context's (arena2, idle outside a sampling step) grown to that plus io_bytes if needed; then `run`
     // enqueues for real on the main stream.  `what` names the caller in the allocation-failure message.

@@ -345,6 +345,20 @@ int launch_softmax_rows(const float* in, void* out, int out_dt, int rows, int n,
 int launch_embed_tokens(const int* ids, const void* tok, int tok_ld, const void* pos, int pos_ld, int dt, void* out, int out_dt,
                         int B, int L, int C, int vocab, hipStream_t s);
 int launch_nhwc_to_nchw(const void* in, int in_dt, float* out, int B, int C, int H, int W, int Cpad, float scale, hipStream_t s);
+// vae_tile.hip: the two ends of a tiled VAE call (pd_vae_set_tiling)
+// out[t * B + b][y][x][c] = scale * in[b][c][origins[2t] + y][origins[2t + 1] + x] + shift for c < C, 0 for the pad channels; in is
+// [B][C][H][W] fp32, every window [th][tw] must lie inside it (the caller checks)
+int launch_vae_tile_gather(const float* in, void* out, int out_dt, const int* origins, int ntile, int B, int C, int H, int W, int th, int tw,
+                           int Cpad, float scale, float shift, hipStream_t s);
+// Tile (ti, tj) of the nrow x ncol grid is fp32 [B][rows[4 ti]][cols[4 tj]][Cpad] at tiles + tile_off[ti * ncol + tj] (a multiple of 4
+// floats) and owns the output rectangle from (ti * limit, tj * limit).  rows[4 ti + 1] is its blend extent against the tile above (0 in
+// row 0) and rows[4 ti + 2] the offset in wtab of that extent's 2 e weights (1 - y / e, then y / e); cols the same along x.
+struct VaeBlendParams {
+    const float* tiles; const long long* tile_off; const int* rows; const int* cols; const float* wtab;
+    float* out;          // nchw: [B][C][H][W]; else [B][H][W][Cpad]
+    int B, C, Cpad, H, W, nrow, ncol, limit, nchw;
+};
+int launch_vae_tile_blend(const VaeBlendParams& p, hipStream_t s);
 // sd3_text_kernels.hip: the small kernels of the SD3 text encoders (T5: sd3_text.cpp; the CLIP pooling and the joint write: text.cpp)
 // out[row][:] = tok[clamp(ids[row])][:] (table rows [vocab][tok_ld] in dt) -> fp32 [rows][C]: T5's token embedding (no positions)
 int launch_embed_rows(const int* ids, const void* tok, int tok_ld, int dt, float* out, long long rows, int C, int vocab, hipStream_t s);

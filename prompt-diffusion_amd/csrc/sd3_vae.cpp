@@ -67,12 +67,12 @@ extern "C" int pd_sd3_vae_decode(pd_engine* e, const float* latents, int32_t B, 
     VaeW& v = e->sd3_vae;
     if (!v.built) { pd_set_error("pd_sd3_vae_decode: no SD3 VAE on this engine (pd_sd3_vae_configure)"); return 1; }
     if (e->ses.active) { pd_set_error("pd_sd3_vae_decode: end the sampling session first"); return 1; }
-    if (!e->vae_flash_on(v.d, v.attn.C, (long long)h * w) && (h * w) % 8) {
+    if (!e->vae_plan_for(PD_VAE_SD3, h, w, 1 << (v.d.num_levels - 1), false).tiled && !e->vae_flash_on(v.d, v.attn.C, (long long)h * w) && (h * w) % 8) {
         pd_set_error("pd_sd3_vae_decode: h * w must be a multiple of 8 where the mid-block attention materialises its scores (got %d x %d)", h, w);
         return 1;
     }
     PD_TRY(e->require_loaded(GROUP_SD3_VAE, "SD3 VAE"));
-    return e->vae_decode_call(v, latents, B, h, w, mem, raw ? 1.f : (float)(1.0 / v.d.scaling), raw ? 0.f : (float)v.d.shift, images);
+    return e->vae_decode_call(v, PD_VAE_SD3, latents, B, h, w, mem, raw ? 1.f : (float)(1.0 / v.d.scaling), raw ? 0.f : (float)v.d.shift, images);
 }
 
 extern "C" int pd_sd3_vae_encode(pd_engine* e, const float* images, int32_t B, int32_t H, int32_t W, int32_t mem, int32_t what, const float* noise,
@@ -84,7 +84,7 @@ extern "C" int pd_sd3_vae_encode(pd_engine* e, const float* images, int32_t B, i
     if (e->ses.active) { pd_set_error("pd_sd3_vae_encode: end the sampling session first"); return 1; }
     const int dn = 1 << (v.d.num_levels - 1);
     if (H % dn || W % dn) { pd_set_error("pd_sd3_vae_encode: H and W must be multiples of %d (got %d x %d)", dn, H, W); return 1; }
-    if (!e->vae_flash_on(v.d, v.attn.C, (long long)(H / dn) * (W / dn)) && ((H / dn) * (W / dn)) % 8) {
+    if (!e->vae_plan_for(PD_VAE_SD3, H, W, dn, true).tiled && !e->vae_flash_on(v.d, v.attn.C, (long long)(H / dn) * (W / dn)) && ((H / dn) * (W / dn)) % 8) {
         pd_set_error("pd_sd3_vae_encode: (H/%d)*(W/%d) must be a multiple of 8 where the mid-block attention materialises its scores (got %d x %d)", dn, dn, H, W);
         return 1;
     }
@@ -92,5 +92,5 @@ extern "C" int pd_sd3_vae_encode(pd_engine* e, const float* images, int32_t B, i
         pd_set_error("pd_sd3_vae_encode: unknown `what` %d (PD_VAE_MEAN / PD_VAE_SAMPLE / PD_VAE_MOMENTS)", what);
         return 1;
     }
-    return e->vae_encode_call(v, images, B, H, W, mem, what, noise, raw ? 1.f : (float)v.d.scaling, raw ? 0.f : (float)v.d.shift, out);
+    return e->vae_encode_call(v, PD_VAE_SD3, images, B, H, W, mem, what, noise, raw ? 1.f : (float)v.d.scaling, raw ? 0.f : (float)v.d.shift, out);
 }

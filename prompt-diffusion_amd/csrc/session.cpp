@@ -1178,6 +1178,7 @@ int64_t pd_get_stat(pd_engine* e, const char* key) {
     if (!strcmp(key, "image_allocs")) return (int64_t)e->image_allocs;   // allocations of pd_image_load / pd_image_store / pd_canny so far
     if (!strcmp(key, "canny_sweeps")) return (int64_t)e->canny_sweeps;   // hysteresis launches of the last pd_canny / pd_op_canny_hysteresis
     if (!strcmp(key, "gn_from_slabs")) return (int64_t)e->gn_from_slabs;
+    if (!strcmp(key, "vae_tiles")) return (int64_t)e->vae_tiles_run;   // tiles run by tiled VAE calls (pd_vae_set_tiling)
     if (!strcmp(key, "vae_flash_launches")) return (int64_t)e->vae_flash_launches;   // of which: vae_attention.hip
     if (!strcmp(key, "ups_fold_launches")) return (int64_t)e->ups_fold_launches;   // of which: conv_upfold.hip's four-phase upsample conv
     if (!strcmp(key, "ring_launches")) return (int64_t)e->ring_launches;   // of which: gemm_ring.hip's persistent ring kernel

@@ -163,7 +163,7 @@ void pd_engine::build_vae_encoder(VaeEncW& v, const std::string& P) {
 bool pd_engine::vae_flash_on(const VaeDesc& d, int C, long long N) const {
     if (f32 || !vae_attention_eligible(T, C)) return false;
     if (opt_vae_flash >= 0) return opt_vae_flash != 0;
-    if (!d.flash_auto) return false;
+    if (!d.flash_auto) return vae_tile_odd_flash && N % 8 != 0;   // (a tile of a tiled call that cannot materialise its scores)
     const long long score_bytes = N * N * 4 + N * ((N + 63) / 64 * 64) * (long long)dt_size(T);
     return score_bytes > (2ll << 30) || N % 8 != 0;
 }
@@ -248,13 +248,25 @@ int pd_engine::vae_forward(VaeW& v, const float* latents_dev, int B, int h, int 
         ++launches;
         if (launch_nchw_to_nhwc(latents_dev, z.p, T, B, d.z, h, w, d.zpad, stream, scale, shift)) return 1;
     }
+    Act img = new_act(B, h << (d.num_levels - 1), w << (d.num_levels - 1), round_up(d.out_ch, 4), DT_F32);
+    PD_TRY(vae_decode_layers(v, z, img));
+    if (!arena.dry) {
+        ++launches;
+        if (launch_nhwc_to_nchw(img.p, DT_F32, out_dev, B, d.out_ch, img.H, img.W, img.C, 1.f, stream)) return 1;
+    }
+    return 0;
+}
+
+// post_quant_conv and conv_in .. conv_out of Decoder.forward on z, into the caller's img
+int pd_engine::vae_decode_layers(VaeW& v, const Act& z, Act& img) {
+    const VaeDesc& d = v.d;
     Act zq = z;
     if (d.quant) {
-        zq = new_act(B, h, w, d.zpad, T);   // post_quant_conv writes channels 0..z-1; the pad channels must read as 0
+        zq = new_act(z.B, z.H, z.W, d.zpad, T);   // post_quant_conv writes channels 0..z-1; the pad channels must read as 0
         if (!arena.dry) HIP_OK(hipMemsetAsync(zq.p, 0, zq.bytes(), stream));
         PD_TRY(conv(v.post_quant, z, zq));
     }
-    Act hcur = new_act(B, h, w, v.top, S);
+    Act hcur = new_act(zq.B, zq.H, zq.W, v.top, S);
     PD_TRY(conv(v.conv_in, zq, hcur));
     Act t;
     PD_TRY(resblock(v.mid1, hcur, t, nullptr, 0));
@@ -274,23 +286,24 @@ int pd_engine::vae_forward(VaeW& v, const float* latents_dev, int B, int h, int 
             hcur = u;
         }
     }
-    Act img = new_act(hcur.B, hcur.H, hcur.W, round_up(d.out_ch, 4), DT_F32);
+    if (img.B != hcur.B || img.H != hcur.H || img.W != hcur.W) { pd_set_error("internal: VAE decoder output is %d x %d, the caller expects %d x %d", hcur.H, hcur.W, img.H, img.W); return 1; }
     PD_TRY(conv_gn(v.conv_out, hcur, img, v.out_g, v.out_b, 1e-6f, true));
-    if (!arena.dry) {
-        ++launches;
-        if (launch_nhwc_to_nchw(img.p, DT_F32, out_dev, B, d.out_ch, img.H, img.W, img.C, 1.f, stream)) return 1;
-    }
     return 0;
 }
 
 extern "C" int pd_vae_weights_missing(pd_engine* e) { return e ? e->missing(GROUP_VAE) : 0; }
 
-int pd_engine::vae_decode_call(VaeW& v, const float* latents, int B, int h, int w, int mem, float scale, float shift, float* images_out) {
+int pd_engine::vae_decode_call(VaeW& v, int which, const float* latents, int B, int h, int w, int mem, float scale, float shift, float* images_out) {
     HIP_OK(hipSetDevice(device));
     const int up = 1 << (v.d.num_levels - 1);
     const int H = up * h, W = up * w;
     const size_t n_in = (size_t)B * v.d.z * h * w, n_out = (size_t)B * v.d.out_ch * H * W;
-    return in_side_workspace("VAE", (n_in + n_out) * sizeof(float), [&] { return vae_forward(v, nullptr, B, h, w, nullptr, scale, shift); }, [&] {
+    // tiling / slicing (pd_vae_set_tiling): vae_decode_managed; with both off, vae_forward as ever
+    const bool managed = vae_tiling[which].tiling || vae_tiling[which].slicing;
+    auto fwd = [&](const float* s, float* o) {
+        return managed ? vae_decode_managed(v, which, s, B, h, w, o, scale, shift) : vae_forward(v, s, B, h, w, o, scale, shift);
+    };
+    return in_side_workspace("VAE", (n_in + n_out) * sizeof(float), [&] { return fwd(nullptr, nullptr); }, [&] {
         int r = 0;
         float* din = reinterpret_cast<float*>(arena.alloc(n_in * sizeof(float)));
         float* dout = reinterpret_cast<float*>(arena.alloc(n_out * sizeof(float)));
@@ -300,7 +313,7 @@ int pd_engine::vae_decode_call(VaeW& v, const float* latents, int B, int h, int 
                 hipStreamSynchronize(stream) != hipSuccess) { pd_set_error("latent upload failed"); r = 1; }
             src = din;
         }
-        if (!r) r = vae_forward(v, src, B, h, w, dout, scale, shift);
+        if (!r) r = fwd(src, dout);
         if (!r) {
             if (hipMemcpyAsync(images_out, dout, n_out * sizeof(float),
                                mem == PD_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream) != hipSuccess ||
@@ -314,9 +327,13 @@ extern "C" int pd_vae_decode(pd_engine* e, const float* latents, int32_t B, int3
     if (!e || !latents || !images_out || B < 1 || h < 1 || w < 1) { pd_set_error("bad argument"); return 1; }
     if (!e->vae.built) { pd_set_error("this engine was created without a VAE decoder (vae_ch = 0)"); return 1; }
     if (e->ses.active) { pd_set_error("pd_vae_decode: end the sampling session first"); return 1; }
-    if ((h * w) % 64) { pd_set_error("pd_vae_decode: h*w must be a multiple of 64 (latents of 64x64-pixel multiples)"); return 1; }
+    // (a tiled call checks its tiles instead: vae_check_tiles)
+    if (!e->vae_plan_for(PD_VAE_SD15, h, w, 8, false).tiled && (h * w) % 64) {
+        pd_set_error("pd_vae_decode: h*w must be a multiple of 64 (latents of 64x64-pixel multiples)");
+        return 1;
+    }
     PD_TRY(e->require_loaded(GROUP_VAE, "VAE"));
-    return e->vae_decode_call(e->vae, latents, B, h, w, mem, (float)(1.0 / e->cfg.scale_factor), 0.f, images_out);
+    return e->vae_decode_call(e->vae, PD_VAE_SD15, latents, B, h, w, mem, (float)(1.0 / e->cfg.scale_factor), 0.f, images_out);
 }
 
 // AutoencoderKL.encode (autoencoder.py:83-87): Encoder.forward (model.py:508-544) -> quant_conv -> DiagonalGaussianDistribution
@@ -331,7 +348,24 @@ int pd_engine::vae_encoder_forward(VaeEncW& v, const float* images_dev, int B, i
         ++launches;
         if (launch_nchw_to_nhwc(images_dev, x.p, T, B, cin, H, W, x.C, stream)) { pd_set_error("image upload launch failed"); return 1; }
     }
-    Act hcur = new_act(B, H, W, d.ch, S);
+    const int dn = 1 << (d.num_levels - 1);
+    Act mom = new_act(B, H / dn, W / dn, d.quant ? v.quant.m.N : v.conv_out.m.N, DT_F32);
+    PD_TRY(vae_encode_layers(v, x, mom));
+    if (!arena.dry) {
+        PD_TRY(check_arena());
+        ++launches;
+        if (launch_vae_posterior(mom.p, DT_F32, mom.C, noise_dev, out_dev, B, z, mom.H * mom.W, what, scale, stream, rng_dev, shift)) {
+            pd_set_error("posterior launch failed");
+            return 1;
+        }
+    }
+    return 0;
+}
+
+// conv_in .. conv_out of Encoder.forward and quant_conv on x, into the caller's mom (the moments stay fp32)
+int pd_engine::vae_encode_layers(VaeEncW& v, const Act& x, Act& mom) {
+    const VaeDesc& d = v.d;
+    Act hcur = new_act(x.B, x.H, x.W, d.ch, S);
     PD_TRY(conv(v.conv_in, x, hcur));
     Act t;
     for (VaeEncLevel& L : v.levels) {
@@ -352,36 +386,28 @@ int pd_engine::vae_encoder_forward(VaeEncW& v, const float* images_dev, int B, i
     PD_TRY(resblock(v.mid2, hcur, t, nullptr, 0));
     hcur = t;
     // norm_out + swish + conv_out, then quant_conv; the moments stay fp32 from here on
+    if (mom.B != hcur.B || mom.H != hcur.H || mom.W != hcur.W) { pd_set_error("internal: VAE encoder output is %d x %d, the caller expects %d x %d", hcur.H, hcur.W, mom.H, mom.W); return 1; }
+    if (!d.quant) return conv_gn(v.conv_out, hcur, mom, v.out_g, v.out_b, 1e-6f, true);
     Act h = new_act(hcur.B, hcur.H, hcur.W, v.conv_out.m.N, DT_F32);
     PD_TRY(conv_gn(v.conv_out, hcur, h, v.out_g, v.out_b, 1e-6f, true));
-    Act mom = h;
-    if (d.quant) {
-        mom = new_act(h.B, h.H, h.W, v.quant.m.N, DT_F32);
-        PD_TRY(conv(v.quant, h, mom));
-    }
-    if (!arena.dry) {
-        PD_TRY(check_arena());
-        ++launches;
-        if (launch_vae_posterior(mom.p, DT_F32, mom.C, noise_dev, out_dev, B, z, mom.H * mom.W, what, scale, stream, rng_dev, shift)) {
-            pd_set_error("posterior launch failed");
-            return 1;
-        }
-    }
-    return 0;
+    return conv(v.quant, h, mom);
 }
 
 extern "C" int pd_vae_encoder_weights_missing(pd_engine* e) { return e ? e->missing(GROUP_VAE_ENCODER) : 0; }
 
-int pd_engine::vae_encode_call(VaeEncW& v, const float* images, int B, int H, int W, int mem, int what, const float* noise, float scale, float shift,
-                               float* out) {
+int pd_engine::vae_encode_call(VaeEncW& v, int which, const float* images, int B, int H, int W, int mem, int what, const float* noise, float scale,
+                               float shift, float* out) {
     HIP_OK(hipSetDevice(device));
     const int dn = 1 << (v.d.num_levels - 1);
     const int h = H / dn, w = W / dn, z = v.d.z;
     const size_t n_in = (size_t)B * v.d.out_ch * H * W, n_lat = (size_t)B * z * h * w;
     // (noise NULL with PD_VAE_SAMPLE: the posterior kernel draws at (PD_RNG_VAE, draw 0) itself)
     const size_t n_noise = (what == PD_VAE_SAMPLE && noise) ? n_lat : 0, n_out = what == PD_VAE_MOMENTS ? 2 * n_lat : n_lat;
-    return in_side_workspace("VAE", (n_in + n_noise + n_out) * sizeof(float),
-                             [&] { return vae_encoder_forward(v, nullptr, B, H, W, what, nullptr, nullptr, scale, shift); }, [&] {
+    const bool managed = vae_tiling[which].tiling || vae_tiling[which].slicing;
+    auto fwd = [&](const float* s, const float* n, float* o) {
+        return managed ? vae_encode_managed(v, which, s, B, H, W, what, n, o, scale, shift) : vae_encoder_forward(v, s, B, H, W, what, n, o, scale, shift);
+    };
+    return in_side_workspace("VAE", (n_in + n_noise + n_out) * sizeof(float), [&] { return fwd(nullptr, nullptr, nullptr); }, [&] {
         int r = 0;
         float* din = reinterpret_cast<float*>(arena.alloc(n_in * sizeof(float)));
         float* dnoise = n_noise ? reinterpret_cast<float*>(arena.alloc(n_noise * sizeof(float))) : nullptr;
@@ -395,7 +421,7 @@ int pd_engine::vae_encode_call(VaeEncW& v, const float* images, int B, int H, in
             src = din;
             nz = dnoise;
         }
-        if (!r) r = vae_encoder_forward(v, src, B, H, W, what, what == PD_VAE_SAMPLE ? nz : nullptr, dout, scale, shift);
+        if (!r) r = fwd(src, what == PD_VAE_SAMPLE ? nz : nullptr, dout);
         if (!r) {
             if (hipMemcpyAsync(out, dout, n_out * sizeof(float), mem == PD_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
                                stream) != hipSuccess ||
@@ -411,7 +437,7 @@ extern "C" int pd_vae_encode(pd_engine* e, const float* images, int32_t B, int32
     if (!e->vae_enc.built) { pd_set_error("this engine was created without a VAE encoder (vae_encoder = 0)"); return 1; }
     PD_TRY(e->require_loaded(GROUP_VAE_ENCODER, "VAE encoder"));
     if (e->ses.active) { pd_set_error("pd_vae_encode: end the sampling session first"); return 1; }
-    if (H % 8 || W % 8 || ((H / 8) * (W / 8)) % 64) {
+    if (H % 8 || W % 8 || (!e->vae_plan_for(PD_VAE_SD15, H, W, 8, true).tiled && ((H / 8) * (W / 8)) % 64)) {
         pd_set_error("pd_vae_encode: H and W must be multiples of 8 and (H/8)*(W/8) a multiple of 64 (got %d x %d)", H, W);
         return 1;
     }
@@ -419,5 +445,5 @@ extern "C" int pd_vae_encode(pd_engine* e, const float* images, int32_t B, int32
         pd_set_error("pd_vae_encode: unknown `what` %d (PD_VAE_MEAN / PD_VAE_SAMPLE / PD_VAE_MOMENTS)", what);
         return 1;
     }
-    return e->vae_encode_call(e->vae_enc, images, B, H, W, mem, what, noise, (float)e->cfg.scale_factor, 0.f, out);
+    return e->vae_encode_call(e->vae_enc, PD_VAE_SD15, images, B, H, W, mem, what, noise, (float)e->cfg.scale_factor, 0.f, out);
 }

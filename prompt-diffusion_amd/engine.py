@@ -7,6 +7,7 @@ torch CUDA tensors as device pointers.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
@@ -175,6 +176,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.pd_vae_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
     lib.pd_vae_encode.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p]
     lib.pd_vae_encoder_weights_missing.argtypes = [C.c_void_p]
+    lib.pd_vae_set_tiling.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32]
+    lib.pd_vae_set_slicing.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+    lib.pd_vae_get_tiling.argtypes = [C.c_void_p, C.c_int32] + [C.POINTER(C.c_int32)] * 3 + [C.POINTER(C.c_double), C.POINTER(C.c_int32)]
+    lib.pd_vae_tile_plan.argtypes = [C.c_int32] * 3 + [C.c_double, C.c_int32, C.c_int32] + [C.POINTER(C.c_int32)] * 3 + [C.c_void_p, C.c_int32]
+    lib.pd_op_vae_tile_blend.argtypes = [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p]
     lib.pd_hed_configure.argtypes = [C.c_void_p]
     lib.pd_hed_weights_missing.argtypes = [C.c_void_p]
     lib.pd_hed_detect.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p]
@@ -266,7 +272,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
 EXPORTS = [
     "pd_last_error", "pd_abi_version", "pd_engine_create", "pd_engine_destroy", "pd_param_count", "pd_param_info",
     "pd_load_weights", "pd_init_random_weights", "pd_weights_missing", "pd_vae_weights_missing", "pd_vae_decode",
-    "pd_vae_encode", "pd_vae_encoder_weights_missing", "pd_eps", "pd_eps_ctx", "pd_control_shape", "pd_ddim_sample",
+    "pd_vae_encode", "pd_vae_encoder_weights_missing", "pd_vae_set_tiling", "pd_vae_set_slicing", "pd_vae_get_tiling", "pd_vae_tile_plan",
+    "pd_op_vae_tile_blend", "pd_eps", "pd_eps_ctx", "pd_control_shape", "pd_ddim_sample",
     "pd_sample_begin", "pd_sample_step", "pd_sample_get", "pd_sample_set_latents", "pd_sample_set_guidance", "pd_sample_eps_at", "pd_sample_end",
     "pd_unipc_coefficients", "pd_unipc_sample", "pd_sample_begin_unipc",
     "pd_lms_coefficients", "pd_lms_sample", "pd_sample_begin_lms", "pd_sample_rows",
@@ -296,6 +303,36 @@ def philox4x32_10(counter: Sequence[int], key: Sequence[int]) -> Tuple[int, int,
 
 def _filter_code(filter) -> int:
     return RESAMPLE_FILTERS[filter] if isinstance(filter, str) else int(filter)
+
+
+PD_VAE_SD15, PD_VAE_SD3 = 0, 1
+VAE_TILE_DEFAULTS = {PD_VAE_SD15: 64, PD_VAE_SD3: 128}   # tile_latent; overlap_factor 0.25 for both
+
+
+class pd_vae_tile(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("y0", "x0", "h", "w", "oy", "ox", "oh", "ow", "th", "tw", "ev", "eh", "cls")] + [("reserved", C.c_int32 * 3)]
+
+
+VaeTile = collections.namedtuple("VaeTile", "y0 x0 h w oy ox oh ow th tw ev eh cls")
+VaeTilePlan = collections.namedtuple("VaeTilePlan", "rows cols classes tiles")
+VaeTilingState = collections.namedtuple("VaeTilingState", "tiling slicing tile_latent overlap_factor tile_batch")
+
+
+def vae_tile_plan(h: int, w: int, tile_latent: int = 64, overlap_factor: float = 0.25, u: int = 8, encode: bool = False) -> VaeTilePlan:
+    """The tile grid of a tiled VAE call (pd_vae_tile_plan; host only, no engine): diffusers' tiled_decode on a latent of h x w, or with
+    encode=True tiled_encode on an image of h x w pixels.  rows = cols = 0 and no tiles when the size is not tiled; tiles in row-major
+    order (input window, kept output rectangle, the tile's own output size, blend extents, shape class).  PdError for an overlap_factor
+    outside (0, 1/3] or a tile_latent * overlap_factor that is no integer."""
+    lib = load_library()
+    r, c, k = C.c_int32(), C.c_int32(), C.c_int32()
+    args = (int(h), int(w), int(tile_latent), float(overlap_factor), int(u), int(bool(encode)))
+    if lib.pd_vae_tile_plan(*args, C.byref(r), C.byref(c), C.byref(k), None, 0):
+        raise PdError(lib.pd_last_error().decode())
+    n = r.value * c.value
+    buf = (pd_vae_tile * max(n, 1))()
+    if n and lib.pd_vae_tile_plan(*args, C.byref(r), C.byref(c), C.byref(k), C.addressof(buf), n):
+        raise PdError(lib.pd_last_error().decode())
+    return VaeTilePlan(r.value, c.value, k.value, [VaeTile(*(getattr(buf[i], f) for f in VaeTile._fields)) for i in range(n)])
 
 
 def resample_ksize(in_size: int, out_size: int, filter="lanczos") -> int:
@@ -670,6 +707,53 @@ class Engine:
 
     def vae_encoder_weights_missing(self) -> int:
         return int(self.lib.pd_vae_encoder_weights_missing(self._h))
+
+    # ------------------------------------------------------------------ tiled / sliced VAE calls (pd_vae_set_tiling)
+    _vae_which = PD_VAE_SD15
+
+    def set_vae_tiling(self, on: bool = True, tile_latent: Optional[int] = None, overlap_factor: Optional[float] = None,
+                       tile_batch: Optional[int] = None) -> None:
+        """diffusers' vae.enable_tiling / disable_tiling for every later vae_decode / vae_encode of this engine: a latent larger than
+        tile_latent (an image larger than 8 * tile_latent) per side is cut into overlapping tiles that run through the VAE on their own
+        and are blended over overlap_factor of a tile; smaller calls run exactly as without.  With on=True the three parameters replace
+        what was set, None: the default (64 latent pixels, 0.25, 4 tiles per batch); with on=False a None keeps what was set.  The result
+        is diffusers' tiled one, not the untiled image."""
+        self._check(self.lib.pd_vae_set_tiling(self._h, self._vae_which, int(bool(on)), int(tile_latent or 0), float(overlap_factor or 0.0),
+                                               int(tile_batch or 0)))
+
+    def set_vae_slicing(self, on: bool = True) -> None:
+        """diffusers' vae.enable_slicing / disable_slicing: with more than one sample, each is decoded / encoded on its own."""
+        self._check(self.lib.pd_vae_set_slicing(self._h, self._vae_which, int(bool(on))))
+
+    @property
+    def vae_tiling(self) -> VaeTilingState:
+        """(tiling, slicing, tile_latent, overlap_factor, tile_batch) with the defaults resolved."""
+        t, s, n, b, f = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_double()
+        self._check(self.lib.pd_vae_get_tiling(self._h, self._vae_which, C.byref(t), C.byref(s), C.byref(n), C.byref(f), C.byref(b)))
+        return VaeTilingState(bool(t.value), bool(s.value), int(n.value), float(f.value), int(b.value))
+
+    def vae_tile_plan(self, h: int, w: int, encode: bool = False) -> VaeTilePlan:
+        """The grid a vae_decode of an h x w latent (encode=True: a vae_encode of an h x w image) takes with the tiling parameters as
+        set, whether or not tiling is switched on; rows = cols = 0 where the size is not tiled."""
+        st = self.vae_tiling
+        return vae_tile_plan(h, w, st.tile_latent, st.overlap_factor, 8, encode)
+
+    def op_vae_tile_blend(self, tiles, plan: VaeTilePlan, C_out: int, nchw: bool = True):
+        """vae_tile_blend_kernel alone (pd_op_vae_tile_blend): tiles = one fp32 array [B, th, tw, Cpad] per tile of the plan, row-major;
+        -> [B, C_out, H, W] (nchw) or [B, H, W, Cpad]."""
+        n = plan.rows * plan.cols
+        buf = (pd_vae_tile * n)()
+        for i, t in enumerate(plan.tiles):
+            for f in VaeTile._fields:
+                setattr(buf[i], f, int(getattr(t, f)))
+        B, cpad = int(tiles[0].shape[0]), int(tiles[0].shape[3])
+        flat = np.concatenate([np.ascontiguousarray(t, np.float32).reshape(-1) for t in tiles])
+        last = plan.tiles[-1]
+        H, Wd = last.oy + last.oh, last.ox + last.ow
+        out = np.empty((B, C_out, H, Wd) if nchw else (B, H, Wd, cpad), np.float32)
+        self._check(self.lib.pd_op_vae_tile_blend(self._h, flat.ctypes.data, C.addressof(buf), plan.rows, plan.cols, B, int(C_out), cpad,
+                                                  int(bool(nchw)), out.ctypes.data))
+        return out
 
     def vae_encode(self, images, mode: str = "mean", noise=None):
         """AutoencoderKL.encode (autoencoder.py:83-87) on the device: images [B,3,H,W] in [-1, 1] (H, W multiples of 8,

@@ -651,6 +651,47 @@ class PromptDiffusionPipeline:
         """Disables the FreeU mechanism if enabled."""
         self.engine.disable_freeu()
 
+    def _engine_vae(self, what: str):
+        """The engine whose VAE the four switches below act on; ValueError where decoding is the caller's."""
+        if self.vae_decode is not None and getattr(self.engine.cfg, "vae_ch", 0) <= 0:
+            raise ValueError(f"{what} acts on the engine's VAE, but this pipeline decodes through the injected `vae_decode` callable and its "
+                             "engine was built without one (vae_ch = 0): switch tiling / slicing on in that callable's own VAE")
+        if getattr(self.engine.cfg, "vae_ch", 0) <= 0:
+            raise ValueError(f"{what} needs an engine with a VAE (vae_ch > 0)")
+        return self.engine
+
+    def enable_vae_slicing(self):
+        r"""
+        Enable sliced VAE decoding. When this option is enabled, the VAE will split the input tensor in slices to
+        compute decoding in several steps. This is useful to save some memory and allow larger batch sizes.
+        """
+        # engine state (Engine.set_vae_slicing): every later vae_decode / vae_encode of this engine, the device-image path included
+        self._engine_vae("enable_vae_slicing").set_vae_slicing(True)
+
+    def disable_vae_slicing(self):
+        r"""
+        Disable sliced VAE decoding. If `enable_vae_slicing` was previously enabled, this method will go back to
+        computing decoding in one step.
+        """
+        self._engine_vae("disable_vae_slicing").set_vae_slicing(False)
+
+    def enable_vae_tiling(self):
+        r"""
+        Enable tiled VAE decoding. When this option is enabled, the VAE will split the input tensor into tiles to
+        compute decoding and encoding in several steps. This is useful for saving a large amount of memory and to allow
+        processing larger images.
+        """
+        st = self._engine_vae("enable_vae_tiling").vae_tiling   # (keeps tile size, overlap and tile batch as set on the engine)
+        self.engine.set_vae_tiling(True, st.tile_latent, st.overlap_factor, st.tile_batch)
+
+    def disable_vae_tiling(self):
+        r"""
+        Disable tiled VAE decoding. If `enable_vae_tiling` was previously enabled, this method will go back to
+        computing decoding in one step.
+        """
+        st = self._engine_vae("disable_vae_tiling").vae_tiling
+        self.engine.set_vae_tiling(False, st.tile_latent, st.overlap_factor, st.tile_batch)
+
     def _lora_scales(self, scale: float) -> List[float]:
         """Effective multiplier per adapter id: its set_adapters weight x the call's cross_attention_kwargs scale
         (diffusers' scale_lora_layers / lora_scale); 0 for inactive ids."""

@@ -191,6 +191,31 @@ class StableDiffusion3PromptDiffusionPipeline:
     def _engine_has_vae(self, encoder: bool) -> bool:
         return getattr(self.engine, "vae_cfg", None) is not None and (not encoder or getattr(self.engine, "vae_has_encoder", False))
 
+    def _engine_vae(self, what: str):
+        """The engine whose VAE the four switches below act on; ValueError where the VAE is the caller's."""
+        if not self._engine_has_vae(False):
+            if self.vae_decode is not None or self.vae_encode is not None:
+                raise ValueError(f"{what} acts on the engine's VAE, but this pipeline runs the injected `vae_decode` / `vae_encode` callables "
+                                 "and its engine has no VAE (SD3Engine.configure_vae): switch tiling / slicing on in the callables' own VAE")
+            raise ValueError(f"{what} needs an engine with SD3's VAE (SD3Engine.configure_vae)")
+        return self.engine
+
+    def enable_vae_slicing(self):
+        """vae.enable_slicing(): each sample of a batch is decoded / encoded on its own (SD3Engine.set_vae_slicing)."""
+        self._engine_vae("enable_vae_slicing").set_vae_slicing(True)
+
+    def disable_vae_slicing(self):
+        self._engine_vae("disable_vae_slicing").set_vae_slicing(False)
+
+    def enable_vae_tiling(self):
+        """vae.enable_tiling(): images above 1024 pixels per side are decoded / encoded in overlapping tiles (SD3Engine.set_vae_tiling)."""
+        st = self._engine_vae("enable_vae_tiling").vae_tiling
+        self.engine.set_vae_tiling(True, st.tile_latent, st.overlap_factor, st.tile_batch)
+
+    def disable_vae_tiling(self):
+        st = self._engine_vae("disable_vae_tiling").vae_tiling
+        self.engine.set_vae_tiling(False, st.tile_latent, st.overlap_factor, st.tile_batch)
+
     def _vae_encode_fn(self):
         if self.vae_encode is not None:
             return self.vae_encode

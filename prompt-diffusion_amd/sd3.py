@@ -608,6 +608,28 @@ class SD3Engine:
             raise E.PdError("this engine has no SD3 VAE" + (" encoder" if encoder else "") + ": call configure_vae first")
         return self.vae_cfg
 
+    # tiled / sliced VAE calls (pd_vae_set_tiling with PD_VAE_SD3): Engine's four, on this engine's own VAE state
+    def set_vae_tiling(self, on: bool = True, tile_latent: Optional[int] = None, overlap_factor: Optional[float] = None,
+                       tile_batch: Optional[int] = None) -> None:
+        """vae.enable_tiling / disable_tiling for every later vae_decode / vae_encode (encode_support_pair included): latents above
+        tile_latent (default 128, 1024 pixels) per side run as overlapping tiles blended over overlap_factor (default 0.25) of a tile.  on=True replaces the three parameters
+        (None: the default); on=False keeps what a None stands for."""
+        self.base._check(self.base.lib.pd_vae_set_tiling(self.base._h, E.PD_VAE_SD3, int(bool(on)), int(tile_latent or 0),
+                                                         float(overlap_factor or 0.0), int(tile_batch or 0)))
+
+    def set_vae_slicing(self, on: bool = True) -> None:
+        self.base._check(self.base.lib.pd_vae_set_slicing(self.base._h, E.PD_VAE_SD3, int(bool(on))))
+
+    @property
+    def vae_tiling(self) -> "E.VaeTilingState":
+        t, s, n, b, f = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_double()
+        self.base._check(self.base.lib.pd_vae_get_tiling(self.base._h, E.PD_VAE_SD3, C.byref(t), C.byref(s), C.byref(n), C.byref(f), C.byref(b)))
+        return E.VaeTilingState(bool(t.value), bool(s.value), int(n.value), float(f.value), int(b.value))
+
+    def vae_tile_plan(self, h: int, w: int, encode: bool = False) -> "E.VaeTilePlan":
+        st = self.vae_tiling
+        return E.vae_tile_plan(h, w, st.tile_latent, st.overlap_factor, 8, encode)
+
     def vae_decode(self, latents, raw: bool = False):
         """vae.decode(latents / scaling_factor + shift_factor) (promptdiffusioncontrolnetpipeline_sd3.py:1271-1273): latents
         [B, z, h, w] -> images [B, 3, 8h, 8w] in about [-1, 1]; raw=True decodes the latents as they are.  NumPy in, NumPy out; CUDA
