@@ -620,7 +620,12 @@ int pd_set_option(pd_engine* e, const char* key, int64_t value);
  * "gemm_family" (which kernel family the engine's last convolution / linear launch took, PD_GEMM_* in the order of the names the
  * option "verbose" 2 dispatch trace prints: the weight-streaming GEMV, the LDS-patch conv3x3 generations 1 / 2 / 4, the ring GEMM, the
  * implicit GEMM, the four-phase upsample conv; -1 before the first launch.  pd_op_conv2d and pd_op_linear set it through the same dispatch as the network, so a
- * test can assert that an option setting put a shape on the kernel it names) */
+ * test can assert that an option setting put a shape on the kernel it names),
+ * "attn_kernel" (which kernel family the engine's last multi-head attention launch took: PD_ATTN_GENERIC = attn_kernel, every mode,
+ * head dim, causal mask and relative-position bias; PD_ATTN_PIPELINED = the double-buffered attn2_kernel of the 2-byte modes, which
+ * takes every launch without mask and bias unless option "attn_legacy" is 1; 0 before the first launch) */
+#define PD_ATTN_GENERIC 1
+#define PD_ATTN_PIPELINED 2
 #define PD_GN_TWO_PASS 1
 #define PD_GN_LDS_SLAB 2
 #define PD_GN_REGISTER 3

@@ -11,6 +11,7 @@
  *   pd_op_groupnorm_slabs / pd_op_groupnorm_coef  the derived forms of GroupNorm32 (split-K slab input; {scale, shift} coefficients)
  *   pd_op_ln_linear  nn.LayerNorm -> nn.Linear as a kernel pair and as the folded GEMM   attention.py:271-275
  *   pd_op_attention  softmax(q k^T dh^-0.5) v, heads from the engine config        attention.py:171-193
+ *   pd_op_attention_ex  the same kernels with heads, causal mask, scale, relative-position bias, strided q | k rows and padding fills
  *   pd_op_vae_attention  the first stage's single-head attention (flash / materialised)   ldm/modules/diffusionmodules/model.py:171-202
  *   pd_op_spatial_transformer  one SpatialTransformer block of the loaded networks  attention.py:271-275,321-340
  *   pd_op_time_embed timestep_embedding + the time_embed MLP of a loaded network    util.py:154-174, openaimodel.py:526-531
@@ -67,6 +68,23 @@ int pd_op_ln_linear(pd_engine* e, int mode, const float* h, const float* x, cons
                     const float* gamma, const float* beta, const float* w, const float* bias, int M, int K, int N, float* h_out, float* y,
                     int* stats_parts, float* row_stats);
 int pd_op_attention(pd_engine* e, const float* q, const float* k, const float* v, int B, int Nq, int Nk, int C, float* o);
+/* pd_engine::attention in every form its callers launch; pd_op_attention is this call with everything after C at 0 / NULL.
+ * q [B, Nq, C], k, v [B, Nk, C], o [B, Nq, C] host fp32.
+ *   heads     0: pd_config.num_heads; dh = C / heads must be one of the built head dims (8, 16, 32, 40, 64, 80, 160)
+ *   causal    keys after the query are masked (Nq == Nk)
+ *   scale     0: dh^-0.5
+ *   relbias   NULL, or the Toeplitz bias rows [heads][2 Nk - 1] in natural-log units: logit(query, key) += relbias[h][key - query + Nk - 1]
+ *             (T5); converted to the kernel's exp2 units by the T5 path's own kernel.  dh 64, Nq == Nk, not causal.
+ *   layout    0: q and k contiguous (row stride C).  1: one device buffer [B][Nk][2C] holding q | k, as a fused projection leaves them;
+ *             the queries are its first Nq <= Nk rows, the row stride of q and k is 2C, their sample stride Nk * 2C, and the output buffer
+ *             is [B][Nk][C] with sample stride Nk * C (the MMDiT joint block, and its context_pre_only form where Nq < Nk).
+ *   vt_extra  keys of V^T row padding beyond round_up(Nk, 8); a multiple of 8
+ *   pad_fill  written (NaN allowed) into every V^T pad column and, in layout 1, into the q half of the rows >= Nq and into the whole
+ *             output buffer before the launch
+ *   touched   may be NULL; layout 1: the number of elements in the output rows >= Nq whose bytes the launch changed (0 in layout 0)
+ * Sets stat "attn_kernel".  A combination the engine does not launch is an error, not a fall-back. */
+int pd_op_attention_ex(pd_engine* e, const float* q, const float* k, const float* v, int B, int Nq, int Nk, int C, int heads, int causal,
+                       float scale, const float* relbias, int layout, int vt_extra, float pad_fill, float* o, int64_t* touched);
 /* softmax(q k^T C^-0.5) v with one head over all C channels -- the first stage's AttnBlock (model.py:171-202) between its projections;
  * q, k, v, o [B, N, C].  Option "vae_flash" 1: the single-head flash kernel (vae_attention.hip; 2-byte modes, C = 128 or 512, any
  * N >= 1 -- another mode or C is an error); 0 / -1: the materialised path (score GEMM, row softmax, value GEMM per sample; every mode,

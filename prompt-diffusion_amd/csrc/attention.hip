@@ -652,9 +652,10 @@ int launch_bias(const AttnParams& p, const float* relbias, hipStream_t s) {
 }
 
 template <int P>
-int launch_prec(const AttnParams& p, hipStream_t s) {
+int launch_prec(const AttnParams& p, hipStream_t s, int* kind) {
     if constexpr (!prec_f32_storage(P)) {
         if (!p.legacy && !p.causal) {
+            if (kind) *kind = ATTN_KIND_PIPELINED;
             switch (p.dh) {
                 case 8: return launch_attn2<8, P>(p, s);
                 case 16: return launch_attn2<16, P>(p, s);
@@ -667,6 +668,7 @@ int launch_prec(const AttnParams& p, hipStream_t s) {
             }
         }
     }
+    if (kind) *kind = ATTN_KIND_GENERIC;
     switch (p.dh) {
         case 8: return launch_dh<P, 8>(p, s);
         case 16: return launch_dh<P, 16>(p, s);
@@ -681,21 +683,24 @@ int launch_prec(const AttnParams& p, hipStream_t s) {
 
 }  // namespace
 
-int launch_attention(const AttnParams& p, int prec, hipStream_t s) {
+int launch_attention(const AttnParams& p, int prec, hipStream_t s, int* kind) {
+    if (kind) *kind = 0;
     if (p.Nq <= 0 || p.Nk <= 0) return 0;
     switch (prec) {
-        case DT_F32: return launch_prec<DT_F32>(p, s);
-        case PREC_F16X2: return launch_prec<PREC_F16X2>(p, s);
-        case DT_BF16: return launch_prec<DT_BF16>(p, s);
-        case DT_F16: return launch_prec<DT_F16>(p, s);
+        case DT_F32: return launch_prec<DT_F32>(p, s, kind);
+        case PREC_F16X2: return launch_prec<PREC_F16X2>(p, s, kind);
+        case DT_BF16: return launch_prec<DT_BF16>(p, s, kind);
+        case DT_F16: return launch_prec<DT_F16>(p, s, kind);
         default: return 1;
     }
 }
 
 // softmax(Q K^T * scale + bias) V with the Toeplitz bias rows relbias [heads][2 Nk - 1] fp32 (see attn_body): dh 64, Nq == Nk, not causal
-int launch_attention_bias(const AttnParams& p, const float* relbias, int prec, hipStream_t s) {
+int launch_attention_bias(const AttnParams& p, const float* relbias, int prec, hipStream_t s, int* kind) {
+    if (kind) *kind = 0;
     if (p.Nq <= 0 || p.Nk <= 0) return 0;
     if (!relbias || p.dh != 64 || p.Nq != p.Nk || p.causal) return 2;
+    if (kind) *kind = ATTN_KIND_GENERIC;
     switch (prec) {
         case DT_F32: return launch_bias<DT_F32>(p, relbias, s);
         case PREC_F16X2: return launch_bias<PREC_F16X2>(p, relbias, s);

@@ -1114,7 +1114,7 @@ int pd_engine::attention(const void* Q, int ldq, const void* K, int ldk, const v
         prof_begin(rec, 2, 4.0 * (double)B * heads * (double)Nq * (double)Nk * (double)p.dh);
         rec.M = Nq; rec.N = Nk; rec.K = p.dh; rec.taps = B;
     }
-    const int r = relbias ? launch_attention_bias(p, relbias, P, stream) : launch_attention(p, P, stream);
+    const int r = relbias ? launch_attention_bias(p, relbias, P, stream, &attn_kernel) : launch_attention(p, P, stream, &attn_kernel);
     if (profiling) prof_end(rec);
     if (r) {
         pd_set_error(r == 2 ? "attention: unsupported head dim %d" : "attention launch failed (dh %d)", p.dh);

@@ -506,6 +506,7 @@ struct pd_engine {
     long long ring_launches = 0;   // launches that took gemm_ring.hip (stat "ring_launches")
     int gn_kernel = 0;             // GN_KIND_* of the last groupnorm() launch (stat "gn_kernel"), set where the launch is decided
     long long ups_fold_launches = 0;   // launches that took conv_upfold.hip (stat "ups_fold_launches")
+    int attn_kernel = 0;           // ATTN_KIND_* of the last attention() launch (stat "attn_kernel"), set by the launcher; 0: none yet
     int gemm_family = -1;          // GemmFamily of the last gemm() launch (stat "gemm_family"), set where gemm() launches; -1: none yet
     // optional per-launch timing (bench.py roofline leg): HIP events around every contraction launch
     struct ProfRec { hipEvent_t a, b; int klass; double flops; int M, N, K, taps; };

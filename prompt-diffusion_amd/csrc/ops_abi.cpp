@@ -414,27 +414,103 @@ int pd_op_layernorm(pd_engine* e, const float* x, const float* gamma, const floa
 
 // softmax(q k^T dh^-0.5) v per head; q [B,Nq,C], k/v [B,Nk,C] fp32, C = heads*dh (heads from the engine config)
 int pd_op_attention(pd_engine* e, const float* q, const float* k, const float* v, int B, int Nq, int Nk, int C, float* o) {
+    return pd_op_attention_ex(e, q, k, v, B, Nq, Nk, C, 0, 0, 0.f, nullptr, 0, 0, 0.f, o, nullptr);
+}
+
+// pd_engine::attention with everything its callers pass (see pdengine_ops.h): heads, causal mask, scale, Toeplitz bias rows, the strided
+// q | k arrangement of a fused projection, extra V^T row padding, and a fill value for every byte the kernel must not let through
+int pd_op_attention_ex(pd_engine* e, const float* q, const float* k, const float* v, int B, int Nq, int Nk, int C, int heads, int causal,
+                       float scale, const float* relbias, int layout, int vt_extra, float pad_fill, float* o, int64_t* touched) {
     if (!e || !q || !k || !v || !o) { pd_set_error("null argument"); return 1; }
+    if (heads <= 0) heads = e->cfg.num_heads;
+    if (B < 1 || Nq < 1 || Nk < 1 || C < 1 || heads < 1 || C % heads) { pd_set_error("pd_op_attention_ex: need B, Nq, Nk >= 1 and C a multiple of heads"); return 1; }
+    const int dh = C / heads;
+    if (layout != 0 && layout != 1) { pd_set_error("pd_op_attention_ex: layout %d (0 contiguous, 1 q | k rows of one buffer)", layout); return 1; }
+    if (layout == 1 && Nq > Nk) { pd_set_error("pd_op_attention_ex: layout 1 takes the queries from the first Nq <= Nk rows (Nq %d, Nk %d)", Nq, Nk); return 1; }
+    if (vt_extra < 0 || vt_extra % 8) { pd_set_error("pd_op_attention_ex: vt_extra %d must be a non-negative multiple of 8", vt_extra); return 1; }
+    if (!(scale >= 0.f)) { pd_set_error("pd_op_attention_ex: scale must be positive (0: dh^-0.5)"); return 1; }
+    if (causal && Nq != Nk) { pd_set_error("pd_op_attention_ex: the causal mask needs Nq == Nk (got %d, %d)", Nq, Nk); return 1; }
+    if (relbias && (dh != 64 || Nq != Nk || causal)) {
+        pd_set_error("pd_op_attention_ex: the bias kernel takes dh 64, Nq == Nk, no causal mask (got dh %d, Nq %d, Nk %d, causal %d)", dh, Nq, Nk, causal);
+        return 1;
+    }
     HIP_OK(hipSetDevice(e->device));
-    const int lpad = round_up(Nk, 8);
+    const int lpad = round_up(Nk, 8) + vt_extra;
     const size_t eb = dt_size(e->T);
-    std::vector<float> vt((size_t)B * C * lpad, 0.f);
+    const int ld = layout ? 2 * C : C;          // row stride of q and of k
+    const int qrows = layout ? Nk : Nq;         // rows per sample of the query and of the output buffer
+    std::vector<float> vt((size_t)B * C * lpad, pad_fill);
     for (int b = 0; b < B; ++b)
         for (int n = 0; n < Nk; ++n)
             for (int c = 0; c < C; ++c) vt[((size_t)b * C + c) * lpad + n] = v[((size_t)b * Nk + n) * C + c];
-    DevBuf tq((size_t)B * Nq * C * 4), tk((size_t)B * Nk * C * 4), tv(vt.size() * 4);
-    DevBuf dq((size_t)B * Nq * C * eb), dk((size_t)B * Nk * C * eb), dv(vt.size() * eb), dout((size_t)B * Nq * C * eb), fo((size_t)B * Nq * C * 4);
+    // layout 0: hq = q, hk = k as they came; layout 1: hq [B][Nk][2C] holds q | k, the q half of rows >= Nq filled
+    std::vector<float> hqk;
+    if (layout) {
+        hqk.assign((size_t)B * Nk * 2 * C, pad_fill);
+        for (int b = 0; b < B; ++b)
+            for (int n = 0; n < Nk; ++n) {
+                float* row = &hqk[((size_t)b * Nk + n) * 2 * C];
+                if (n < Nq) memcpy(row, q + ((size_t)b * Nq + n) * C, (size_t)C * 4);
+                memcpy(row + C, k + ((size_t)b * Nk + n) * C, (size_t)C * 4);
+            }
+    }
+    const size_t nq = (size_t)B * qrows * ld, nk = layout ? 0 : (size_t)B * Nk * C, no = (size_t)B * qrows * C;
+    std::vector<float> fill(no, pad_fill);
+    DevBuf tq(nq * 4), tk(nk * 4), tv(vt.size() * 4), fo(no * 4);
+    DevBuf dq(nq * eb), dk(nk * eb), dv(vt.size() * eb), dout(no * eb);
     if (!tq.p || !tk.p || !tv.p || !dq.p || !dk.p || !dv.p || !dout.p || !fo.p) { pd_set_error("allocation failed"); return 1; }
-    HIP_OK(hipMemcpy(tq.p, q, (size_t)B * Nq * C * 4, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(tk.p, k, (size_t)B * Nk * C * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(tq.p, layout ? hqk.data() : q, nq * 4, hipMemcpyHostToDevice));
+    if (!layout) HIP_OK(hipMemcpy(tk.p, k, nk * 4, hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(tv.p, vt.data(), vt.size() * 4, hipMemcpyHostToDevice));
-    if (launch_cast_rows(reinterpret_cast<const float*>(tq.p), dq.p, e->T, (long long)B * Nq, C, C, e->stream)) return 1;
-    if (launch_cast_rows(reinterpret_cast<const float*>(tk.p), dk.p, e->T, (long long)B * Nk, C, C, e->stream)) return 1;
+    HIP_OK(hipMemcpy(fo.p, fill.data(), no * 4, hipMemcpyHostToDevice));
+    if (launch_cast_rows(reinterpret_cast<const float*>(tq.p), dq.p, e->T, (long long)B * qrows, ld, ld, e->stream)) return 1;
+    if (!layout && launch_cast_rows(reinterpret_cast<const float*>(tk.p), dk.p, e->T, (long long)B * Nk, C, C, e->stream)) return 1;
     if (launch_cast_rows(reinterpret_cast<const float*>(tv.p), dv.p, e->T, (long long)B * C, lpad, lpad, e->stream)) return 1;
-    PD_TRY(e->attention(dq.p, C, dk.p, C, dv.p, lpad, dout.p, C, B, Nq, Nk, C));
-    if (launch_nhwc_to_nchw(dout.p, e->T, reinterpret_cast<float*>(fo.p), 1, 1, 1, B * Nq * C, 1, 1.f, e->stream)) return 1;
+    if (layout && launch_cast_rows(reinterpret_cast<const float*>(fo.p), dout.p, e->T, (long long)B * qrows, C, C, e->stream)) return 1;
+    std::vector<unsigned char> before, after;
+    if (layout) {   // the output buffer as the launch finds it
+        before.resize(no * eb); after.resize(no * eb);
+        HIP_OK(hipStreamSynchronize(e->stream));
+        HIP_OK(hipMemcpy(before.data(), dout.p, no * eb, hipMemcpyDeviceToHost));
+    }
+    // Toeplitz bias rows: natural-log units in, exp2 units to the kernel through T5's own conversion (launch_t5_relbias with the identity
+    // bucket map over a [2 Nk - 1][heads] fp32 table)
+    const int nrel = 2 * Nk - 1;
+    DevBuf btab(relbias ? (size_t)nrel * heads * 4 : 0), bidx(relbias ? (size_t)nrel * 4 : 0), brel(relbias ? (size_t)nrel * heads * 4 : 0);
+    if (relbias) {
+        if (!btab.p || !bidx.p || !brel.p) { pd_set_error("allocation failed"); return 1; }
+        std::vector<float> tab((size_t)nrel * heads);
+        std::vector<int> idx(nrel);
+        for (int i = 0; i < nrel; ++i) {
+            idx[i] = i;
+            for (int h = 0; h < heads; ++h) tab[(size_t)i * heads + h] = relbias[(size_t)h * nrel + i];
+        }
+        HIP_OK(hipMemcpy(btab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(bidx.p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
+        if (launch_t5_relbias(reinterpret_cast<const int*>(bidx.p), btab.p, heads, DT_F32, reinterpret_cast<float*>(brel.p), heads, nrel, e->stream)) {
+            pd_set_error("pd_op_attention_ex: bias conversion launch failed");
+            return 1;
+        }
+    }
+    const void* kp = layout ? reinterpret_cast<const char*>(dq.p) + (size_t)C * eb : dk.p;
+    const long long in_bs = layout ? (long long)Nk * 2 * C : 0, out_bs = layout ? (long long)Nk * C : 0;
+    PD_TRY(e->attention(dq.p, ld, kp, ld, dv.p, lpad, dout.p, C, B, Nq, Nk, C, heads, causal != 0, in_bs, in_bs, out_bs,
+                        relbias ? reinterpret_cast<const float*>(brel.p) : nullptr, scale));
+    if (launch_nhwc_to_nchw(dout.p, e->T, reinterpret_cast<float*>(fo.p), 1, 1, 1, (int)no, 1, 1.f, e->stream)) return 1;
     HIP_OK(hipStreamSynchronize(e->stream));
-    HIP_OK(hipMemcpy(o, fo.p, (size_t)B * Nq * C * 4, hipMemcpyDeviceToHost));
+    if (!layout) {
+        HIP_OK(hipMemcpy(o, fo.p, no * 4, hipMemcpyDeviceToHost));
+        if (touched) *touched = 0;
+        return 0;
+    }
+    for (int b = 0; b < B; ++b)
+        HIP_OK(hipMemcpy(o + (size_t)b * Nq * C, reinterpret_cast<const float*>(fo.p) + (size_t)b * Nk * C, (size_t)Nq * C * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(after.data(), dout.p, no * eb, hipMemcpyDeviceToHost));
+    int64_t changed = 0;   // elements of the rows >= Nq whose bytes differ from what the launch found
+    for (int b = 0; b < B; ++b)
+        for (size_t i = ((size_t)b * Nk + Nq) * C; i < ((size_t)b * Nk + Nk) * C; ++i)
+            if (memcmp(&before[i * eb], &after[i * eb], eb)) ++changed;
+    if (touched) *touched = changed;
     return 0;
 }
 

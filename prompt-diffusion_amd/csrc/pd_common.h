@@ -277,7 +277,10 @@ bool conv_upfold_eligible(const GemmParams& p, int prec);
 int conv_upfold_tiles(const GemmParams& p);   // blocks of the phase launch
 int launch_conv_upfold(const GemmParams& p, const void* w_up, int prec, hipStream_t s);
 int launch_upfold_weights(const void* w, void* w_up, int dt, int N, int cin_pad, int Kpad, hipStream_t s);   // [N][9][cin_pad] -> [4][N][4][cin_pad]
-int launch_attention(const AttnParams& p, int prec, hipStream_t s);
+// which kernel family an attention launch took (stat "attn_kernel": PD_ATTN_* in include/pdengine.h): attn_kernel, at every mode, head
+// dim, mask and bias, or the double-buffered attn2_kernel of the 2-byte modes (not causal, no bias, AttnParams::legacy 0)
+enum { ATTN_KIND_GENERIC = 1, ATTN_KIND_PIPELINED = 2 };
+int launch_attention(const AttnParams& p, int prec, hipStream_t s, int* kind = nullptr);   // kind: which family took it (ATTN_KIND_*; 0: no launch)
 // vae_attention.hip: softmax(Q K^T * scale) V with one head over all C channels (the first stage's AttnBlock), C = 128 / 512, 2-byte modes.
 // Q, K [B][N][..] token-major (ldq / ldk elements between tokens), VT [B][C][vt_ld] with vt_ld >= round_up(N, 8), O [B][N][ldo]; *_bs:
 // elements between samples.  Any N >= 1.  One launch for the batch.  Returns 2 for a (mode, C) that has no instantiation.
@@ -291,7 +294,7 @@ struct VaeAttnParams {
 bool vae_attention_eligible(int prec, int C);
 int launch_vae_attention(const VaeAttnParams& p, int prec, hipStream_t s);
 // T5 self-attention: softmax(Q K^T * scale + bias) V, bias[h][q][k] = relbias[h][k - q + Nk - 1] (fp32, in exp2 units: times log2 e); dh 64, Nq == Nk
-int launch_attention_bias(const AttnParams& p, const float* relbias, int prec, hipStream_t s);
+int launch_attention_bias(const AttnParams& p, const float* relbias, int prec, hipStream_t s, int* kind = nullptr);
 // st_tail.hip: everything after the self-attention product of a 320-channel SpatialTransformer block in one kernel (attn1.to_out +
 // residual, norm2, attn2 against the hoisted context K / V, norm3, GEGLU feed-forward, proj_out + the block residual)
 bool st_tail_eligible(int prec, int C, int heads, int rows_per_sample, int Nk);

@@ -1186,6 +1186,10 @@ int64_t pd_get_stat(pd_engine* e, const char* key) {
         static_assert(GN_KIND_TWO_PASS == PD_GN_TWO_PASS && GN_KIND_LDS_SLAB == PD_GN_LDS_SLAB && GN_KIND_REGISTER == PD_GN_REGISTER, "pdengine.h");
         return (int64_t)e->gn_kernel;
     }
+    if (!strcmp(key, "attn_kernel")) {   // which kernel family the last pd_engine::attention launch took
+        static_assert(ATTN_KIND_GENERIC == PD_ATTN_GENERIC && ATTN_KIND_PIPELINED == PD_ATTN_PIPELINED, "pdengine.h");
+        return (int64_t)e->attn_kernel;
+    }
     if (!strcmp(key, "gemm_family")) {   // which kernel family the last pd_engine::gemm launch took
         static_assert(GEMM_GEMV == PD_GEMM_GEMV && GEMM_PATCH1 == PD_GEMM_PATCH1 && GEMM_PATCH2 == PD_GEMM_PATCH2 && GEMM_PATCH4 == PD_GEMM_PATCH4 &&
                       GEMM_RING == PD_GEMM_RING && GEMM_IGEMM == PD_GEMM_IGEMM && GEMM_UPFOLD == PD_GEMM_UPFOLD, "pdengine.h");

@@ -238,6 +238,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.pd_op_groupnorm_coef.argtypes = [C.c_void_p, fp, fp, fp] + [C.c_int] * 4 + [C.c_float, fp]
     lib.pd_op_ln_linear.argtypes = [C.c_void_p, C.c_int] + [fp] * 9 + [C.c_int] * 3 + [fp, fp, C.POINTER(C.c_int), fp]
     lib.pd_op_attention.argtypes = [C.c_void_p, fp, fp, fp] + [C.c_int] * 4 + [fp]
+    lib.pd_op_attention_ex.argtypes = [C.c_void_p, fp, fp, fp] + [C.c_int] * 6 + [C.c_float, fp, C.c_int, C.c_int, C.c_float, fp, C.POINTER(C.c_int64)]
     lib.pd_op_vae_attention.argtypes = [C.c_void_p, fp, fp, fp] + [C.c_int] * 3 + [fp]
     lib.pd_bench_vae_attention.argtypes = [C.c_void_p] + [C.c_int32] * 5 + [C.POINTER(C.c_float), C.POINTER(C.c_int64)]
     lib.pd_op_spatial_transformer.argtypes = [C.c_void_p, C.c_char_p, fp, fp] + [C.c_int] * 3 + [fp]
@@ -280,7 +281,7 @@ EXPORTS = [
     "pd_make_schedule", "pd_synchronize", "pd_stream", "pd_wait_stream", "pd_set_option", "pd_get_stat", "pd_bench_conv3x3", "pd_bench_linear", "pd_text_encode", "pd_text_encode_ex", "pd_text_weights_missing",
     "pd_profile_read", "pd_profile_dump", "pd_comm_new_id", "pd_comm_init", "pd_comm_world", "pd_comm_all_gather", "pd_comm_destroy",
     "pd_sd3_configure", "pd_sd3_weights_missing", "pd_sd3_forward", "pd_sd3_control", "pd_sd3_sample", "pd_sd3_down_proj",
-    "pd_op_conv2d", "pd_op_conv2d_upfold", "pd_op_linear", "pd_op_linear_fp8", "pd_op_groupnorm", "pd_op_layernorm", "pd_op_groupnorm_slabs", "pd_op_groupnorm_coef", "pd_op_ln_linear", "pd_op_attention", "pd_op_spatial_transformer", "pd_op_spatial_transformer_ctx", "pd_op_time_embed",
+    "pd_op_conv2d", "pd_op_conv2d_upfold", "pd_op_linear", "pd_op_linear_fp8", "pd_op_groupnorm", "pd_op_layernorm", "pd_op_groupnorm_slabs", "pd_op_groupnorm_coef", "pd_op_ln_linear", "pd_op_attention", "pd_op_attention_ex", "pd_op_spatial_transformer", "pd_op_spatial_transformer_ctx", "pd_op_time_embed",
     "pd_op_timestep_embedding_i", "pd_op_timestep_embedding_f", "pd_op_vae_downsample", "pd_read_weights", "pd_lora_add", "pd_lora_set_scales", "pd_lora_remove",
     "pd_set_freeu", "pd_get_freeu", "pd_op_freeu_concat",
     "pd_philox4x32_10", "pd_set_rng", "pd_get_rng", "pd_randn",
@@ -1478,6 +1479,32 @@ class Engine:
         o = np.empty_like(q)
         self._check(self.lib.pd_op_attention(self._h, q.ctypes.data, k.ctypes.data, v.ctypes.data, B, Nq, Nk, Cc, o.ctypes.data))
         return o
+
+    def op_attention_ex(self, q, k, v, heads: int = 0, causal: bool = False, scale: float = 0.0, relbias=None, layout: int = 0,
+                        vt_extra: int = 0, pad_fill: float = 0.0):
+        """pd_engine::attention in the forms its callers launch (pd_op_attention_ex): q [B, Nq, C], k, v [B, Nk, C] -> (o [B, Nq, C],
+        touched).  heads 0: the config's; scale 0: dh^-0.5; relbias [heads, 2 Nk - 1] in natural-log units (dh 64, Nq == Nk, not causal);
+        layout 1: q | k as rows of one [B, Nk, 2C] buffer, the queries its first Nq rows, the output buffer [B, Nk, C]; vt_extra: more V^T
+        row padding (a multiple of 8 keys); pad_fill: what every pad column of V^T and, in layout 1, the q rows >= Nq and the output
+        buffer hold before the launch.  touched: elements of the output rows >= Nq the launch changed (layout 1).  Stat "attn_kernel"
+        says which kernel family ran."""
+        q = np.ascontiguousarray(q, np.float32); k = np.ascontiguousarray(k, np.float32); v = np.ascontiguousarray(v, np.float32)
+        B, Nq, Cc = q.shape
+        Nk = k.shape[1]
+        if k.shape != (B, Nk, Cc) or v.shape != k.shape:
+            raise ValueError("q [B, Nq, C], k and v [B, Nk, C]")
+        h = int(heads) if heads else self.cfg.num_heads
+        rb = None
+        if relbias is not None:
+            rb = np.ascontiguousarray(relbias, np.float32)
+            if rb.shape != (h, 2 * Nk - 1):
+                raise ValueError("relbias must be [heads, 2 Nk - 1]")
+        o = np.empty_like(q)
+        touched = C.c_int64(0)
+        self._check(self.lib.pd_op_attention_ex(self._h, q.ctypes.data, k.ctypes.data, v.ctypes.data, B, Nq, Nk, Cc, int(heads), int(bool(causal)),
+                                                float(scale), None if rb is None else rb.ctypes.data, int(layout), int(vt_extra), float(pad_fill),
+                                                o.ctypes.data, C.byref(touched)))
+        return o, int(touched.value)
 
     def op_vae_attention(self, q, k, v):
         """softmax(q k^T C^-0.5) v with one head over all C channels (the first stage's AttnBlock); q, k, v [B, N, C].  Option
