@@ -736,6 +736,32 @@ int pd_sd3_control(pd_engine* e, const pd_sd3_args* args, int32_t index, float* 
  * ControlNet (its residuals would be all zero).  latents_out: [B, C, H, W]. */
 int pd_sd3_sample(pd_engine* e, const pd_sd3_args* args, const float* sigmas, int32_t steps, float guidance,
                   const float* step_scales, float* latents_out);
+/* Img2img, inpainting and seeded noise inside that loop (diffusers' SD3 img2img pipeline and the 16-channel path of its SD3
+ * inpainting pipeline -- absent offline, so PARITY UNPINNED like the rest of the SD3 path).  sigma_0 .. sigma_steps are the
+ * `sigmas` of the call: truncating the grid by `strength` is the caller's (the loop just gets the tail), and so is
+ * controlnet_keep over the remaining steps (step_scales).  eps [B, C, H, W] is `noise` when set, else args->latents, else -- with
+ * PD_XT_FROM_SEED, where both must be NULL -- the engine's draw at (PD_RNG_XT, draw 0, sample_base + b, element), "Seeded noise"
+ * above, evaluated inside the kernel that consumes it: no eps tensor exists then.
+ *   init_latents  z0 [B, C, H, W] = (vae.encode(image) - shift_factor) * scaling_factor.  The loop starts from
+ *                 x = sigma_0 eps + (1 - sigma_0) z0 (FlowMatchEulerDiscreteScheduler.scale_noise), or from eps itself with
+ *                 PD_INIT_PURE_NOISE.  NULL: the loop starts from eps (with PD_XT_FROM_SEED: start latents the engine draws).
+ *   mask          m [B, 1, H, W], needs init_latents; 1 = repaint, 0 = keep, values in between allowed, broadcast over the
+ *                 channels.  After the Euler update of step i to x' the state becomes (1 - m) k_i + m x' with
+ *                 k_i = (1 - sigma_{i+1}) z0 + sigma_{i+1} eps -- the same eps at every step; k is z0 itself at sigma = 0.
+ * All of it is fp32, every operation rounded on its own in the written order (no FMA), so a NumPy float32 restatement has the
+ * same bits; the CFG + Euler update in front of it is the plain loop's own code.  One launch (sd3_update_kernel) per step and one
+ * for the start state write the state and both halves of the next step's doubled input: no device-to-device copies.
+ * A `loop` that is NULL or sets nothing is pd_sd3_sample, kernel for kernel. */
+typedef struct pd_sd3_loop_args {
+    const float* init_latents; /* [B, C, H, W] in args->mem, or NULL */
+    const float* mask;         /* [B, 1, H, W] in args->mem, or NULL */
+    const float* noise;        /* [B, C, H, W] in args->mem, or NULL: eps is args->latents (or the seeded draw) */
+    int32_t flags;             /* PD_INIT_PURE_NOISE (needs init_latents) | PD_XT_FROM_SEED (noise and args->latents NULL) */
+    int32_t reserved0;
+    int64_t reserved[4];
+} pd_sd3_loop_args;
+int pd_sd3_sample_ex(pd_engine* e, const pd_sd3_args* args, const pd_sd3_loop_args* loop, const float* sigmas, int32_t steps,
+                     float guidance, const float* step_scales, float* latents_out);
 /* SD3PromptDiffusionModel.down_proj (promptdiffusioncontrolnet_sd3.py:114, :189-194): Conv2d(6, 3, kernel 3, padding 1) over
  * pair = cat([cond, gt], 1) [B, 6, H, W] -> out [B, 3, H, W] (fp32, `mem` as in pd_sd3_args). */
 int pd_sd3_down_proj(pd_engine* e, const float* pair, int32_t B, int32_t H, int32_t W, int32_t mem, float* out);

@@ -17,6 +17,7 @@
  *   pd_op_time_embed timestep_embedding + the time_embed MLP of a loaded network    util.py:154-174, openaimodel.py:526-531
  *   pd_op_vae_downsample  the KL-VAE encoder's Downsample (asymmetric pad)          ldm/modules/diffusionmodules/model.py:68-88
  *   pd_op_canny_hysteresis  the flood of cv2.Canny's hysteresis on a given state map  annotator/canny/__init__.py
+ *   pd_op_sd3_update  the update kernel of the SD3 img2img / inpainting / seeded loops (start state, CFG + Euler, blend)
  */
 #ifndef PDENGINE_OPS_H
 #define PDENGINE_OPS_H
@@ -135,6 +136,15 @@ int pd_op_canny_hysteresis(pd_engine* e, const uint8_t* states, int B, int H, in
  * moments); H x W is the sum of the kept rectangles.  fp32 in every mode, host arrays. */
 int pd_op_vae_tile_blend(pd_engine* e, const float* tiles, const pd_vae_tile* plan, int rows, int cols, int B, int C, int Cpad, int nchw,
                          float* out);
+/* One launch of the SD3 loop's update kernel (sd3_update_kernel; arithmetic under pd_sd3_loop_args in pdengine.h) on a caller's
+ * tensors, fp32 in `mem`.  v NULL: the start state, x_out = pure ? eps : sigma eps + (1 - sigma) z0 (x is not read).  v set
+ * ([2B, C, H, W] = [negative ; positive] with use_cfg, else [B, C, H, W]): x_out = the CFG + Euler update of x [B, C, H, W] by
+ * dsigma and, with a mask [B, 1, H, W] (needs z0), its blend with k = (1 - sigma) z0 + sigma eps.  eps [B, C, H, W], or NULL with
+ * seeded != 0: drawn from the engine's generator at (PD_RNG_XT, 0).  x_in_out (may be NULL) [2B, C, H, W]: the doubled input
+ * of the next step as the kernel stores it (both halves). */
+int pd_op_sd3_update(pd_engine* e, const float* v, const float* x, const float* z0, const float* mask, const float* eps, int B, int C,
+                     int H, int W, int use_cfg, float guidance, float dsigma, float sigma, int pure, int seeded, int mem, float* x_out,
+                     float* x_in_out);
 #ifdef __cplusplus
 }
 #endif

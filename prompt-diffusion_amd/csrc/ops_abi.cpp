@@ -724,4 +724,41 @@ int pd_op_canny_hysteresis(pd_engine* e, const uint8_t* states, int B, int H, in
     HIP_OK(hipStreamSynchronize(e->stream));
     return 0;
 }
+
+// sd3_update_kernel alone (launch_sd3_update) on copies of the caller's tensors
+int pd_op_sd3_update(pd_engine* e, const float* v, const float* x, const float* z0, const float* mask, const float* eps, int B, int C,
+                     int H, int W, int use_cfg, float guidance, float dsigma, float sigma, int pure, int seeded, int mem, float* x_out,
+                     float* x_in_out) {
+    if (!e || !x_out) { pd_set_error("null argument"); return 1; }
+    if (B < 1 || C < 1 || H < 1 || W < 1 || B > 32) { pd_set_error("pd_op_sd3_update: bad shape (batch %d, latent %dx%dx%d)", B, C, H, W); return 1; }
+    const bool step = v != nullptr, need_eps = !step || mask;
+    if (step && !x) { pd_set_error("pd_op_sd3_update: a step needs x"); return 1; }
+    if (mask && (!step || !z0)) { pd_set_error("pd_op_sd3_update: a mask needs v and z0"); return 1; }
+    if (!step && !pure && !z0) { pd_set_error("pd_op_sd3_update: the start state needs z0 unless pure"); return 1; }
+    if (seeded && eps) { pd_set_error("pd_op_sd3_update: seeded draws and an eps tensor exclude each other"); return 1; }
+    if (need_eps && !seeded && !eps) { pd_set_error("pd_op_sd3_update: eps is required (or seeded)"); return 1; }
+    HIP_OK(hipSetDevice(e->device));
+    const size_t n = (size_t)B * C * H * W, nm = (size_t)B * H * W, nv = (use_cfg ? 2 : 1) * n;
+    const hipMemcpyKind kin = mem == PD_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    const hipMemcpyKind kout = mem == PD_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    DevBuf dv(nv * 4), dx(n * 4), dz(n * 4), dm(nm * 4), de(n * 4), dxin(2 * n * 4);
+    if (!dv.p || !dx.p || !dz.p || !dm.p || !de.p || !dxin.p) { pd_set_error("allocation failed"); return 1; }
+    auto up = [&](void* dst, const float* src, size_t cnt) { return src ? hipMemcpyAsync(dst, src, cnt * 4, kin, e->stream) : hipSuccess; };
+    HIP_OK(up(dv.p, v, nv));
+    HIP_OK(up(dx.p, x, n));
+    HIP_OK(up(dz.p, z0, n));
+    HIP_OK(up(dm.p, mask, nm));
+    HIP_OK(up(de.p, eps, n));
+    auto fp = [](const DevBuf& b, const void* given) { return given ? reinterpret_cast<float*>(b.p) : nullptr; };
+    Sd3Update u;
+    u.v = fp(dv, v); u.x = reinterpret_cast<float*>(dx.p); u.x_in = fp(dxin, x_in_out); u.z0 = fp(dz, z0); u.mask = fp(dm, mask);
+    u.eps = fp(de, eps); u.rng_state = seeded ? e->rng_dev : nullptr;
+    u.B = B; u.HW = H * W; u.per = (long long)C * H * W;
+    u.guidance = guidance; u.dsigma = dsigma; u.sigma = sigma; u.use_cfg = use_cfg ? 1 : 0; u.pure = pure ? 1 : 0;
+    if (launch_sd3_update(u, e->stream)) { pd_set_error("pd_op_sd3_update: launch failed"); return 1; }
+    HIP_OK(hipMemcpyAsync(x_out, dx.p, n * 4, kout, e->stream));
+    if (x_in_out) HIP_OK(hipMemcpyAsync(x_in_out, dxin.p, 2 * n * 4, kout, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+    return 0;
+}
 }  // extern "C"

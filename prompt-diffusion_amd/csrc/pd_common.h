@@ -491,5 +491,25 @@ int launch_timestep_embedding(const float* t_host, int B, float* out, hipStream_
 int launch_pos_crop(const float* table, float* out, int B, int h, int w, int max_size, int D, hipStream_t s);
 int launch_unpatchify(const void* in, int in_dt, int ld, float* nchw, int B, int C, int h, int w, int patch, hipStream_t s);
 int launch_cfg_euler(const float* v, float* x, int B, long long n, float guidance, float dsigma, int use_cfg, hipStream_t s);
+// One launch of sd3_update_kernel (the img2img / inpainting / seeded forms of the SD3 loop; include/pdengine.h, pd_sd3_loop_args).
+// Everything is fp32 NCHW, `per` = C * HW elements per sample.
+//   v null  -- the start state: x = pure ? eps : sigma eps + (1 - sigma) z0
+//   v set   -- one step: x' = cfg_euler_kernel's update of x; with a mask x = (1 - m) k + m x', k = (1 - sigma) z0 + sigma eps
+// eps is read from `eps`, or drawn at (PD_RNG_XT, draw 0, sample_base + b, element) when rng_state is set (then eps must be null).
+// The result goes to x and, when x_in is set (the CFG loop), to both halves of x_in [2B, per].
+struct Sd3Update {
+    const float* v = nullptr;      // [B or 2B, per]: [negative ; positive] under use_cfg
+    float* x = nullptr;            // [B, per]
+    float* x_in = nullptr;         // [2B, per] or null
+    const float* z0 = nullptr;     // [B, per]; needed unless pure (start) / without a mask (step)
+    const float* mask = nullptr;   // [B, HW]; step launches only
+    const float* eps = nullptr;    // [B, per]
+    const uint32_t* rng_state = nullptr;
+    int B = 0, HW = 0;
+    long long per = 0;
+    float guidance = 0.f, dsigma = 0.f, sigma = 0.f;   // sigma: sigma_0 for the start, sigma_{i+1} for the blend of step i
+    int use_cfg = 0, pure = 0;
+};
+int launch_sd3_update(const Sd3Update& u, hipStream_t s);
 // x_in[d * B + b] = x_state[b] for d < dup, both [., HW, Cpad] fp32
 int launch_fill_x_in(const float* x_state, float* x_in, int B, int dup, int Cpad, int HW, hipStream_t s);

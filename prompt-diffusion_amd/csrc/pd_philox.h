@@ -44,6 +44,20 @@ __device__ __forceinline__ float pd_philox_normal_lane(const uint32_t r[4], int 
     return rad * ((lane & 1) ? sn : cs);
 }
 
+// all four lanes of one block at once, for a kernel whose thread owns elements 4q .. 4q + 3 of a sample: the two radii and the two
+// sincospif are each evaluated once, on the operands pd_philox_normal_lane gives them, so z[l] has that function's bits
+__device__ __forceinline__ void pd_philox_normal4(const uint32_t r[4], float z[4]) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const float u0 = pd_philox_u01(r[2 * h]), u1 = pd_philox_u01(r[2 * h + 1]);
+        const float rad = sqrtf(-2.0f * logf(u0));
+        float sn, cs;
+        sincospif(2.0f * u1, &sn, &cs);
+        z[2 * h] = rad * cs;
+        z[2 * h + 1] = rad * sn;
+    }
+}
+
 // the draw at (stream, draw, sample b of this call, element e of the sample in the caller's NCHW order)
 __device__ __forceinline__ float pd_rng_normal(const PdRng& g, uint32_t stream, uint32_t draw, uint32_t b, long long e) {
     uint32_t r[4];

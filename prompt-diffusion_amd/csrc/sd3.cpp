@@ -513,7 +513,7 @@ struct Sd3Call {
     int Bf;   // rows of context / pooled / timestep: B, or 2B under guidance
 };
 
-int sd3_check(pd_engine* e, const pd_sd3_args* a, bool need_cond) {
+int sd3_check(pd_engine* e, const pd_sd3_args* a, bool need_cond, bool need_latents = true) {
     if (!e || !a) { pd_set_error("bad argument"); return 1; }
     if (!e->sd3_tr.built) { pd_set_error("SD3 path not configured (pd_sd3_configure)"); return 1; }
     if (e->ses.active) { pd_set_error("pd_sd3: end the sampling session first"); return 1; }
@@ -529,16 +529,17 @@ int sd3_check(pd_engine* e, const pd_sd3_args* a, bool need_cond) {
         pd_set_error("pd_sd3: latent %dx%d exceeds pos_embed_max_size", a->height, a->width);
         return 1;
     }
-    if (!a->latents || !a->context || !a->pooled) { pd_set_error("pd_sd3: latents, context and pooled are required"); return 1; }
+    if ((need_latents && !a->latents) || !a->context || !a->pooled) { pd_set_error("pd_sd3: latents, context and pooled are required"); return 1; }
     if ((a->cond != nullptr) != (a->pair != nullptr)) { pd_set_error("pd_sd3: cond and pair come together"); return 1; }
     if (a->cond && !e->sd3_cn.built) { pd_set_error("pd_sd3: this engine has no SD3 ControlNet (cn_layers = 0)"); return 1; }
     if (need_cond && !a->cond) { pd_set_error("pd_sd3_control: cond and pair are required"); return 1; }
     return 0;
 }
 
-// steps < 0: single evaluation (v_out or control residual); otherwise the Euler loop
+// steps < 0: single evaluation (v_out or control residual); otherwise the Euler loop.  lp (loop only): the img2img / inpainting /
+// seeded form of the loop (pd_sd3_loop_args) -- sd3_update_kernel in place of cfg_euler_kernel and the two copies; null: the plain loop
 int sd3_run(pd_engine* e, const pd_sd3_args* a, const float* sigmas, int steps, float guidance, const float* step_scales,
-            int control_index, float* out) {
+            int control_index, float* out, const pd_sd3_loop_args* lp = nullptr) {
     HIP_OK(hipSetDevice(e->device));
     PD_TRY(e->sd3_quantize());
     const bool loop = steps >= 0;
@@ -563,7 +564,7 @@ int sd3_run(pd_engine* e, const pd_sd3_args* a, const float* sigmas, int steps, 
     e->arena.base = nullptr; e->arena.cap = 0; e->arena.top = 0; e->arena.peak = 0; e->arena.dry = true; e->arena.overflow = false;
     e->arena2 = e->arena;
     int r = e->sd3_forward(io, nullptr, control_index, nullptr);
-    const size_t staged = (n_lat * 8 + n_ctx + 2 * n_pool + n_v + n_out) * sizeof(float) + 16 * 256;
+    const size_t staged = (n_lat * (lp ? 11 : 8) + n_ctx + 2 * n_pool + n_v + n_out) * sizeof(float) + 16 * 256;   // lp: + z0, eps, mask
     const size_t need = e->arena.peak + staged + (64u << 20);
     const size_t need2 = e->arena2.peak ? e->arena2.peak + (16u << 20) : 0;   // the ControlNet stream's workspace
     e->arena = saved;
@@ -606,7 +607,30 @@ int sd3_run(pd_engine* e, const pd_sd3_args* a, const float* sigmas, int steps, 
     float* v = falloc(n_v);
     float* res = control_index >= 0 ? falloc(n_out) : nullptr;
     hipStream_t st = e->stream;
-    HIP_OK(hipMemcpyAsync(x, a->latents, n_lat * 4, kin, st));
+    // img2img / inpainting / seeded loop: z0, the mask and eps staged once behind everything the plain loop allocates; the start
+    // launch replaces the upload of the start latents
+    Sd3Update up;
+    if (lp) {
+        const bool seeded = (lp->flags & PD_XT_FROM_SEED) != 0;
+        const float* eps_src = lp->noise ? lp->noise : a->latents;
+        const bool keep_eps = lp->mask != nullptr;   // the blend reads eps at every step
+        float* z0 = lp->init_latents ? falloc(n_lat) : nullptr;
+        float* mask = lp->mask ? falloc((size_t)B * H * W) : nullptr;
+        float* eps = seeded ? nullptr : (lp->init_latents ? falloc(n_lat) : x);   // without z0 the start state is eps itself
+        if (z0) HIP_OK(hipMemcpyAsync(z0, lp->init_latents, n_lat * 4, kin, st));
+        if (mask) HIP_OK(hipMemcpyAsync(mask, lp->mask, (size_t)B * H * W * 4, kin, st));
+        if (eps) HIP_OK(hipMemcpyAsync(eps, eps_src, n_lat * 4, kin, st));
+        up.x = x; up.x_in = cfg ? xin : nullptr; up.z0 = z0; up.eps = eps; up.rng_state = seeded ? e->rng_dev : nullptr;
+        up.B = B; up.HW = H * W; up.per = (long long)C * H * W;
+        up.sigma = sigmas[0]; up.pure = (!z0 || (lp->flags & PD_INIT_PURE_NOISE)) ? 1 : 0;
+        ++e->launches;
+        if (launch_sd3_update(up, st)) { pd_set_error("sd3: start-state launch failed"); e->arena.top = 0; e->arena2.top = 0; return 1; }
+        up.mask = mask;
+        up.guidance = guidance; up.use_cfg = cfg ? 1 : 0; up.pure = 0;
+        if (!keep_eps) { up.eps = nullptr; up.rng_state = nullptr; }
+    } else {
+        HIP_OK(hipMemcpyAsync(x, a->latents, n_lat * 4, kin, st));
+    }
     HIP_OK(hipMemcpyAsync(ctx, a->context, n_ctx * 4, kin, st));
     HIP_OK(hipMemcpyAsync(pool, a->pooled, n_pool * 4, kin, st));
     if (cn_pool && cn_pool != pool) HIP_OK(hipMemcpyAsync(cn_pool, a->cn_pooled, n_pool * 4, kin, st));
@@ -627,7 +651,7 @@ int sd3_run(pd_engine* e, const pd_sd3_args* a, const float* sigmas, int steps, 
         }
     } else {
         for (int i = 0; i < steps && !r; ++i) {
-            if (cfg) {
+            if (cfg && !lp) {
                 HIP_OK(hipMemcpyAsync(xin, x, n_lat * 4, hipMemcpyDeviceToDevice, st));
                 HIP_OK(hipMemcpyAsync(xin + n_lat, x, n_lat * 4, hipMemcpyDeviceToDevice, st));
             }
@@ -636,7 +660,13 @@ int sd3_run(pd_engine* e, const pd_sd3_args* a, const float* sigmas, int steps, 
             r = e->sd3_forward(io, v, -1, nullptr);
             if (r) break;
             ++e->launches;
-            if (launch_cfg_euler(v, x, B, (long long)n_lat, guidance, sigmas[i + 1] - sigmas[i], cfg ? 1 : 0, st)) {
+            if (lp) {
+                up.v = v; up.dsigma = sigmas[i + 1] - sigmas[i]; up.sigma = sigmas[i + 1];
+                if (launch_sd3_update(up, st)) {
+                    pd_set_error("sd3: update launch failed");
+                    r = 1;
+                }
+            } else if (launch_cfg_euler(v, x, B, (long long)n_lat, guidance, sigmas[i + 1] - sigmas[i], cfg ? 1 : 0, st)) {
                 pd_set_error("sd3: Euler step launch failed");
                 r = 1;
             }
@@ -672,6 +702,21 @@ extern "C" int pd_sd3_sample(pd_engine* e, const pd_sd3_args* a, const float* si
     PD_TRY(sd3_check(e, a, false));
     if (!sigmas || steps < 1 || !latents_out) { pd_set_error("pd_sd3_sample: sigmas, steps >= 1 and latents_out are required"); return 1; }
     return sd3_run(e, a, sigmas, steps, guidance, step_scales, -1, latents_out);
+}
+
+extern "C" int pd_sd3_sample_ex(pd_engine* e, const pd_sd3_args* a, const pd_sd3_loop_args* lp, const float* sigmas, int32_t steps,
+                                float guidance, const float* step_scales, float* latents_out) {
+    if (!lp || (!lp->init_latents && !lp->mask && !lp->noise && !lp->flags)) return pd_sd3_sample(e, a, sigmas, steps, guidance, step_scales, latents_out);
+    const bool seeded = (lp->flags & PD_XT_FROM_SEED) != 0;
+    PD_TRY(sd3_check(e, a, false, false));
+    if (!sigmas || steps < 1 || !latents_out) { pd_set_error("pd_sd3_sample_ex: sigmas, steps >= 1 and latents_out are required"); return 1; }
+    if (lp->flags & ~(PD_INIT_PURE_NOISE | PD_XT_FROM_SEED)) { pd_set_error("pd_sd3_sample_ex: unknown flags 0x%x (PD_INIT_PURE_NOISE, PD_XT_FROM_SEED)", lp->flags); return 1; }
+    if (lp->mask && !lp->init_latents) { pd_set_error("pd_sd3_sample_ex: mask needs init_latents"); return 1; }
+    if ((lp->flags & PD_INIT_PURE_NOISE) && !lp->init_latents) { pd_set_error("pd_sd3_sample_ex: PD_INIT_PURE_NOISE needs init_latents"); return 1; }
+    if (seeded && (lp->noise || a->latents)) { pd_set_error("pd_sd3_sample_ex: PD_XT_FROM_SEED draws the noise itself: noise and latents must be NULL"); return 1; }
+    if (!seeded && !lp->noise && !a->latents) { pd_set_error("pd_sd3_sample_ex: the noise is required: latents, noise or PD_XT_FROM_SEED"); return 1; }
+    if (lp->noise && !lp->init_latents) { pd_set_error("pd_sd3_sample_ex: noise needs init_latents (the start latents of a plain call are args->latents)"); return 1; }
+    return sd3_run(e, a, sigmas, steps, guidance, step_scales, -1, latents_out, lp);
 }
 
 // SD3PromptDiffusionModel.down_proj, promptdiffusioncontrolnet_sd3.py:114,189-194: Conv2d(6, 3, 3, padding=1) on the example pair

@@ -1,6 +1,9 @@
 // pdengine: element-wise kernels of the SD3 / MMDiT path (SURVEY.md §8f "next" row N4; host side in sd3.cpp).
 // All HBM-bound single passes; the contractions run on the igemm / attention kernels of the UNet path.
+#include <cstdint>
+
 #include "pd_common.h"
+#include "pd_philox.h"
 
 // v_cvt_pk_fp8_f32 turns |x| > 448 into NaN: saturate first (the scales map the row maximum onto 448, so this only absorbs rounding)
 __device__ __forceinline__ float clamp448(float x) { return fminf(fmaxf(x, -448.0f), 448.0f); }
@@ -199,14 +202,22 @@ int launch_unpatchify(const void* in, int in_dt, int ld, float* nchw, int B, int
     return hipGetLastError() != hipSuccess;
 }
 
-// classifier-free guidance + flow-matching Euler step: v holds [negative ; positive] halves of n elements each when use_cfg,
-// x <- x + dsigma * (v_neg + g * (v_pos - v_neg))
+// classifier-free guidance + flow-matching Euler step of one element: x + dsigma * (v_neg + g * (v_pos - v_neg)).  Both kernels
+// below call this one function, and it does not leave the choice of FMAs to the compiler: contraction is off and the operations
+// are spelled as cfg_euler_kernel has always been compiled -- the difference rounded on its own, then two fused multiply-adds --
+// so the two loops give the same bits wherever the new terms are absent.
+__device__ __forceinline__ float cfg_euler(float x, float v_neg, float v_pos, float g, float ds, int use_cfg) {
+#pragma clang fp contract(off)
+    const float vv = use_cfg ? __builtin_fmaf(g, __fsub_rn(v_pos, v_neg), v_neg) : v_neg;
+    return __builtin_fmaf(ds, vv, x);
+}
+
+// v holds [negative ; positive] halves of n elements each when use_cfg, x <- cfg_euler(x, ...)
 __global__ __launch_bounds__(256) void cfg_euler_kernel(const float* __restrict__ v, float* __restrict__ x, long long n, float g, float ds,
                                                          int use_cfg) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        float vv = v[i];
-        if (use_cfg) vv = vv + g * (v[n + i] - vv);
-        x[i] = x[i] + ds * vv;
+        const float vn = v[i];
+        x[i] = cfg_euler(x[i], vn, use_cfg ? v[n + i] : 0.f, g, ds, use_cfg);
     }
 }
 
@@ -215,6 +226,116 @@ int launch_cfg_euler(const float* v, float* x, int B, long long n, float guidanc
     if (n < 1) return 1;
     const int blocks = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
     hipLaunchKernelGGL(cfg_euler_kernel, dim3(blocks), dim3(256), 0, s, v, x, n, guidance, dsigma, use_cfg);
+    return hipGetLastError() != hipSuccess;
+}
+
+// The update of the img2img / inpainting / seeded SD3 loops (Sd3Update in pd_common.h; arithmetic in include/pdengine.h,
+// pd_sd3_loop_args): the start state, or cfg_euler plus the optional inpainting blend, stored to the state and to both halves of
+// the next step's doubled input.  One thread per group of four consecutive elements of a sample: one 16-byte access per tensor
+// and, where eps is drawn (SEEDED), one Philox block -- its four normals are the group's.  blockIdx.y is the sample, the groups of a
+// sample are walked grid-stride in x; no LDS.
+//   vec       per % 4 == 0 and every pointer 16-byte aligned: vector accesses.  Otherwise the same groups element by element, the
+//             last group of a sample holding per % 4 elements.
+//   vec_mask  the mask [B, HW] is read as a vector too (HW % 4 == 0: a group then lies within one channel)
+// The start state and the blend are separately rounded fp32 operations in the written order (no FMA): mix2 below, with contraction
+// off in its body -- the __fmul_rn / __fadd_rn wrappers are plain operators that the default contraction mode still fuses (this
+// kernel compiled to v_pk_fma_f32 with them).  The instantiation that draws nothing carries nothing of the generator.
+__device__ __forceinline__ float mix2(float a, float x, float b, float y) {
+#pragma clang fp contract(off)
+    return a * x + b * y;
+}
+__device__ __forceinline__ float one_minus_f(float m) {
+#pragma clang fp contract(off)
+    return 1.0f - m;
+}
+
+template <bool SEEDED>
+__global__ __launch_bounds__(256) void sd3_update_kernel(Sd3Update u, int vec, int vec_mask) {
+    const int per = (int)u.per, nq = (per + 3) >> 2, b = blockIdx.y;   // blockIdx.y: the sample (per < 2^31, checked by the launcher)
+    const long long n = (long long)u.B * u.per;
+    const float one_minus = one_minus_f(u.sigma);
+    const bool step = u.v != nullptr, blend = step && u.mask != nullptr;
+    for (int q = blockIdx.x * 256 + threadIdx.x; q < nq; q += gridDim.x * 256) {
+        const int e0 = q << 2, cnt = per - e0 < 4 ? per - e0 : 4;
+        const long long i0 = (long long)b * u.per + e0;
+        auto ld = [&](const float* p) {
+            if (vec) return *reinterpret_cast<const f32x4*>(p + i0);
+            f32x4 r{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int l = 0; l < 4; ++l)
+                if (l < cnt) r[l] = p[i0 + l];
+            return r;
+        };
+        auto st = [&](float* p, const f32x4& r) {
+            if (vec) { *reinterpret_cast<f32x4*>(p + i0) = r; return; }
+#pragma unroll
+            for (int l = 0; l < 4; ++l)
+                if (l < cnt) p[i0 + l] = r[l];
+        };
+        f32x4 xv{0.f, 0.f, 0.f, 0.f};
+        if (step) {
+            const f32x4 x0 = ld(u.x), vn = ld(u.v), vp = u.use_cfg ? ld(u.v + n) : vn;
+#pragma unroll
+            for (int l = 0; l < 4; ++l) xv[l] = cfg_euler(x0[l], vn[l], vp[l], u.guidance, u.dsigma, u.use_cfg);
+        }
+        if (!step || blend) {
+            f32x4 ev;
+            if constexpr (SEEDED) {
+                uint32_t r[4];
+                float z[4];
+                pd_philox4x32_10_block((uint32_t)q, u.rng_state[2] + (uint32_t)b, 0u, PD_RNG_XT, u.rng_state[0], u.rng_state[1], r);
+                pd_philox_normal4(r, z);
+                ev = f32x4{z[0], z[1], z[2], z[3]};
+            } else {
+                ev = ld(u.eps);
+            }
+            if (!step) {
+                if (u.pure) {
+                    xv = ev;
+                } else {
+                    const f32x4 z0 = ld(u.z0);
+#pragma unroll
+                    for (int l = 0; l < 4; ++l) xv[l] = mix2(u.sigma, ev[l], one_minus, z0[l]);
+                }
+            } else {
+                const f32x4 z0 = ld(u.z0);
+                const long long m0 = (long long)b * u.HW;
+                f32x4 m{0.f, 0.f, 0.f, 0.f};
+                if (vec_mask) {
+                    m = *reinterpret_cast<const f32x4*>(u.mask + m0 + e0 % u.HW);
+                } else {
+#pragma unroll
+                    for (int l = 0; l < 4; ++l)
+                        if (l < cnt) m[l] = u.mask[m0 + (e0 + l) % u.HW];
+                }
+#pragma unroll
+                for (int l = 0; l < 4; ++l) {
+                    const float k = mix2(one_minus, z0[l], u.sigma, ev[l]);
+                    xv[l] = mix2(one_minus_f(m[l]), k, m[l], xv[l]);
+                }
+            }
+        }
+        st(u.x, xv);
+        if (u.x_in) {
+            st(u.x_in, xv);
+            st(u.x_in + n, xv);
+        }
+    }
+}
+
+int launch_sd3_update(const Sd3Update& u, hipStream_t s) {
+    const bool step = u.v != nullptr, blend = step && u.mask, need_eps = !step || blend;
+    if (u.B < 1 || u.B > 65535 || u.HW < 1 || u.per < 1 || u.per > 0x7ffffff0ll || u.per % u.HW || !u.x) return 1;
+    if (u.mask && (!step || !u.z0)) return 1;
+    if (!step && !u.pure && !u.z0) return 1;
+    if (need_eps && (u.eps != nullptr) == (u.rng_state != nullptr)) return 1;   // exactly one source of eps
+    auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };   // (a null pointer counts as aligned)
+    const int vec = u.per % 4 == 0 && al(u.v) && al(u.x) && al(u.x_in) && al(u.z0) && al(u.eps);
+    const int vec_mask = vec && u.HW % 4 == 0 && al(u.mask);
+    const long long groups = (u.per + 3) / 4;   // per sample
+    const int blocks = (int)((groups + 255) / 256 < 1024 ? (groups + 255) / 256 : 1024);
+    if (need_eps && u.rng_state) hipLaunchKernelGGL(sd3_update_kernel<true>, dim3(blocks, u.B), dim3(256), 0, s, u, vec, vec_mask);
+    else hipLaunchKernelGGL(sd3_update_kernel<false>, dim3(blocks, u.B), dim3(256), 0, s, u, vec, vec_mask);
     return hipGetLastError() != hipSuccess;
 }
 

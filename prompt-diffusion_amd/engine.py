@@ -265,6 +265,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.pd_image_store.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_int32]
     lib.pd_canny.argtypes = [C.c_void_p, C.POINTER(pd_canny_args)]
     lib.pd_op_canny_hysteresis.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    lib.pd_op_sd3_update.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_float] * 3 + [C.c_int] * 3 + [C.c_void_p] * 2
     if path is None:
         _lib = lib
     return lib
@@ -280,7 +281,8 @@ EXPORTS = [
     "pd_lms_coefficients", "pd_lms_sample", "pd_sample_begin_lms", "pd_sample_rows",
     "pd_make_schedule", "pd_synchronize", "pd_stream", "pd_wait_stream", "pd_set_option", "pd_get_stat", "pd_bench_conv3x3", "pd_bench_linear", "pd_text_encode", "pd_text_encode_ex", "pd_text_weights_missing",
     "pd_profile_read", "pd_profile_dump", "pd_comm_new_id", "pd_comm_init", "pd_comm_world", "pd_comm_all_gather", "pd_comm_destroy",
-    "pd_sd3_configure", "pd_sd3_weights_missing", "pd_sd3_forward", "pd_sd3_control", "pd_sd3_sample", "pd_sd3_down_proj",
+    "pd_sd3_configure", "pd_sd3_weights_missing", "pd_sd3_forward", "pd_sd3_control", "pd_sd3_sample", "pd_sd3_sample_ex", "pd_sd3_down_proj",
+    "pd_op_sd3_update",
     "pd_op_conv2d", "pd_op_conv2d_upfold", "pd_op_linear", "pd_op_linear_fp8", "pd_op_groupnorm", "pd_op_layernorm", "pd_op_groupnorm_slabs", "pd_op_groupnorm_coef", "pd_op_ln_linear", "pd_op_attention", "pd_op_attention_ex", "pd_op_spatial_transformer", "pd_op_spatial_transformer_ctx", "pd_op_time_embed",
     "pd_op_timestep_embedding_i", "pd_op_timestep_embedding_f", "pd_op_vae_downsample", "pd_read_weights", "pd_lora_add", "pd_lora_set_scales", "pd_lora_remove",
     "pd_set_freeu", "pd_get_freeu", "pd_op_freeu_concat",
@@ -1575,6 +1577,24 @@ class Engine:
                                                 skip.shape[0], 0 if skip_add is None else skip_add.shape[0], float(s), float(b),
                                                 y.ctypes.data))
         return y
+
+    def op_sd3_update(self, shape, v=None, x=None, z0=None, mask=None, eps=None, use_cfg: bool = False, guidance: float = 1.0,
+                      dsigma: float = 0.0, sigma: float = 0.0, pure: bool = False, seeded: bool = False, want_x_in: bool = False):
+        """One launch of the SD3 loop's update kernel (pd_op_sd3_update) on [B, C, H, W] = shape, NumPy fp32.  v None: the start state
+        from z0 / eps (or eps itself with pure); v [2B or B, C, H, W]: the CFG + Euler update of x by dsigma, blended with
+        k = (1 - sigma) z0 + sigma eps under mask [B, 1, H, W].  seeded: eps is the engine's draw at ("xt", 0).  Returns the new
+        state, and with want_x_in also the doubled input [2B, C, H, W] the kernel stores."""
+        B, Cc, H, W = (int(s) for s in shape)
+        f = lambda a, shp: None if a is None else np.ascontiguousarray(a, np.float32).reshape(shp)
+        v = f(v, ((2 if use_cfg else 1) * B, Cc, H, W))
+        x, z0, eps, mask = f(x, (B, Cc, H, W)), f(z0, (B, Cc, H, W)), f(eps, (B, Cc, H, W)), f(mask, (B, 1, H, W))
+        ptr = lambda a: None if a is None else a.ctypes.data
+        out = np.empty((B, Cc, H, W), np.float32)
+        x_in = np.empty((2 * B, Cc, H, W), np.float32) if want_x_in else None
+        self._check(self.lib.pd_op_sd3_update(self._h, ptr(v), ptr(x), ptr(z0), ptr(mask), ptr(eps), B, Cc, H, W, int(bool(use_cfg)),
+                                              float(guidance), float(dsigma), float(sigma), int(bool(pure)), int(bool(seeded)), PD_MEM_HOST,
+                                              ptr(out), ptr(x_in)))
+        return (out, x_in) if want_x_in else out
 
     def op_spatial_transformer(self, prefix: str, x, context):
         """SpatialTransformer.forward (attention.py:321-340) of the block loaded under `prefix`, through the sampling code path;

@@ -132,6 +132,38 @@ def tokenize_long(tokenizer, prompts: List[str], windows: int, width: int) -> np
                            for r in raw]) if len(raw) else np.zeros((0, width), np.int32)
 
 
+def prepare_inpaint_mask(mask_image, width, height, batch_size, scale_factor):
+    """diffusers' mask processor (grayscale, resize to the image size with LANCZOS, binarize at 0.5), then the
+    nearest-neighbour downsample to the latent size -- pixel (f i, f j) for scale_factor f, F.interpolate's default -- and the
+    duplication to the batch: [batch_size, 1, height / f, width / f] float32.  Arrays: [H, W], [H, W, 1], [B, H, W] or [B, H, W, 1]
+    (NumPy), [H, W], [B, H, W] or [B, 1, H, W] (torch), in [0, 1] at the image size.  Shared by the SD1.5 and SD3 inpaint pipelines."""
+    outs = []
+    for im in (mask_image if isinstance(mask_image, list) else [mask_image]):
+        if _is_pil(im):
+            if im.size != (width, height):
+                from PIL import Image
+                im = im.resize((width, height), resample=Image.LANCZOS)
+            a = (np.asarray(im.convert("L"), dtype=np.float32) / 255.0)[None, None]
+        else:
+            a = _to_numpy(im).astype(np.float32)
+            if a.ndim == 2:
+                a = a[None, None]
+            elif a.ndim == 3:
+                a = a.transpose(2, 0, 1)[None] if isinstance(im, np.ndarray) and a.shape[-1] == 1 else a[:, None]
+            elif a.ndim == 4 and isinstance(im, np.ndarray):
+                a = a.transpose(0, 3, 1, 2)
+            if a.ndim != 4 or a.shape[1] != 1:
+                raise ValueError(f"mask_image must have one channel, got an array of shape {_to_numpy(im).shape}")
+        if a.shape[-2:] != (height, width):
+            raise ValueError(f"mask_image is {a.shape[-1]}x{a.shape[-2]}, the image {width}x{height}")
+        outs.append(a)
+    m = np.concatenate(outs, axis=0)
+    m = np.where(m < 0.5, np.float32(0.0), np.float32(1.0)).astype(np.float32)
+    f = scale_factor
+    m = np.ascontiguousarray(m[:, :, ::f, ::f])
+    return PromptDiffusionPipeline._tile(m, batch_size, "`mask_image`")
+
+
 class PromptDiffusionPipeline:
     _callback_tensor_inputs = ["latents", "prompt_embeds", "negative_prompt_embeds"]
     vae_scale_factor = 8
@@ -396,31 +428,7 @@ class PromptDiffusionPipeline:
         nearest-neighbour downsample to the latent size -- pixel (8i, 8j), F.interpolate's default -- and the duplication to the
         batch: [batch_size, 1, height / 8, width / 8] float32.  Arrays: [H, W], [H, W, 1], [B, H, W] or [B, H, W, 1] (NumPy),
         [H, W], [B, H, W] or [B, 1, H, W] (torch), in [0, 1] at the image size."""
-        outs = []
-        for im in (mask_image if isinstance(mask_image, list) else [mask_image]):
-            if _is_pil(im):
-                if im.size != (width, height):
-                    from PIL import Image
-                    im = im.resize((width, height), resample=Image.LANCZOS)
-                a = (np.asarray(im.convert("L"), dtype=np.float32) / 255.0)[None, None]
-            else:
-                a = _to_numpy(im).astype(np.float32)
-                if a.ndim == 2:
-                    a = a[None, None]
-                elif a.ndim == 3:
-                    a = a.transpose(2, 0, 1)[None] if isinstance(im, np.ndarray) and a.shape[-1] == 1 else a[:, None]
-                elif a.ndim == 4 and isinstance(im, np.ndarray):
-                    a = a.transpose(0, 3, 1, 2)
-                if a.ndim != 4 or a.shape[1] != 1:
-                    raise ValueError(f"mask_image must have one channel, got an array of shape {_to_numpy(im).shape}")
-            if a.shape[-2:] != (height, width):
-                raise ValueError(f"mask_image is {a.shape[-1]}x{a.shape[-2]}, the image {width}x{height}")
-            outs.append(a)
-        m = np.concatenate(outs, axis=0)
-        m = np.where(m < 0.5, np.float32(0.0), np.float32(1.0)).astype(np.float32)
-        f = self.vae_scale_factor
-        m = np.ascontiguousarray(m[:, :, ::f, ::f])
-        return self._tile(m, batch_size, "`mask_image`")
+        return prepare_inpaint_mask(mask_image, width, height, batch_size, self.vae_scale_factor)
 
     def _init_latents(self, image, width, height, batch_size, generator, device=False):
         """z0 = scaling_factor * the init image's latents, [batch_size, 4, height / 8, width / 8]: a 4-channel `image` is taken

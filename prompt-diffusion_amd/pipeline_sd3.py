@@ -26,13 +26,20 @@ The three steps of the loop body (controlnet, transformer, CFG + scheduler.step;
 (`SD3Engine.sample`); with `callback_on_step_end` the loop is driven step by step from here (`SD3Engine.forward` + the same
 Euler update) so that the callback can replace the latents or the embeddings (:1247-1258).  Arrays are NumPy (torch tensors
 are converted).  Not supported, raising NotImplementedError like the SD1.5 mirror does for options outside the path:
-`ip_adapter_image(_embeds)`, `joint_attention_kwargs` (LoRA scale)."""
+`ip_adapter_image(_embeds)`, `joint_attention_kwargs` (LoRA scale).
+
+`StableDiffusion3PromptDiffusionImg2ImgPipeline(image=, strength=)` and `StableDiffusion3PromptDiffusionInpaintPipeline(image=,
+mask_image=, strength=)` add diffusers' SD3 img2img and (16-channel) inpainting to the same call: the grid is truncated by `strength`,
+the loop starts from sigma_0 eps + (1 - sigma_0) z0 and, with a mask, every step ends with (1 - m) k_i + m x (include/pdengine.h,
+pd_sd3_loop_args) -- inside the engine's loop, or in NumPy float32 in the same order on the callback path.  `generator=EngineGenerator(seed)`
+makes every draw the engine's (the start latents of the plain pipeline too); in the edited loops eps is then drawn inside the update kernel."""
 from typing import Any, Callable, Dict, List, Optional, Union
 
 import numpy as np
 
 from . import engine as E
-from .sd3 import SD3Engine, flow_match_sigmas
+from .pipeline import EngineGenerator, prepare_inpaint_mask
+from .sd3 import SD3Engine, flow_match_sigmas, img2img_start
 
 _CALLBACK_TENSOR_INPUTS = ["latents", "prompt_embeds", "negative_prompt_embeds", "negative_pooled_prompt_embeds"]
 
@@ -278,10 +285,44 @@ class StableDiffusion3PromptDiffusionPipeline:
 
     @staticmethod
     def _randn(g, shape):
+        if isinstance(g, EngineGenerator):          # bound by __call__; the start latents / the img2img noise: stream "xt"
+            return np.asarray(g.randn(shape, stream="xt"), np.float32)
         if isinstance(g, np.random.Generator):
             return g.standard_normal(shape).astype(np.float32)
         import torch   # a torch.Generator, as the reference takes
         return torch.randn(shape, generator=g, device=g.device).float().cpu().numpy()
+
+    def _init_z0(self, image, batch, height, width, generator):
+        """z0 of img2img / inpainting, [batch, C, height / 8, width / 8]: C-channel arrays are latents and taken as they are (as diffusers
+        does); images (PIL, uint8, float arrays in [0, 1]) are encoded -- by the injected `vae_encode`, else by the engine's VAE with a
+        posterior sample drawn from `generator` -- and become (latents - shift_factor) * scaling_factor, always with the VAE's real
+        shift factor.  Fewer images than `batch` are repeated as a whole (diffusers' torch.cat of the init latents)."""
+        C, f = self.engine.cfg.in_channels, self.vae_scale_factor
+        x = _image_array(image)
+        a = _np(x)
+        if x is image and a.ndim == 4 and a.shape[1] == C:
+            z = a
+        else:
+            img = self.prepare_image(x, 1, 1)
+            if tuple(img.shape[-2:]) != (height, width):
+                raise ValueError(f"`image` is {img.shape[-1]}x{img.shape[-2]}, the control image {width}x{height}")
+            if self.vae_encode is not None:
+                lat = _np(self.vae_encode(img))
+            elif self._engine_has_vae(True):
+                gen = generator[:img.shape[0]] if isinstance(generator, list) else generator
+                # an EngineGenerator: the posterior kernel draws at stream "vae" itself
+                noise = None if isinstance(gen, EngineGenerator) else self.prepare_latents(img.shape[0], C, height, width, gen)
+                lat = _np(self.engine.vae_encode(img, mode="sample", noise=noise, raw=True))
+            else:
+                raise ValueError(f"an init `image` needs `vae_encode` or an engine with SD3's VAE encoder; pass [{C}]-channel latents otherwise")
+            z = ((lat - self.vae_shift_factor) * self.vae_scaling_factor).astype(np.float32)
+        if tuple(z.shape[1:]) != (C, height // f, width // f):
+            raise ValueError(f"`image` latents must be [B, {C}, {height // f}, {width // f}], got {list(z.shape)}")
+        if z.shape[0] != batch:
+            if batch % z.shape[0]:
+                raise ValueError(f"Cannot duplicate `image` of batch size {z.shape[0]} to {batch} images; the batch size must divide it.")
+            z = np.tile(z, (batch // z.shape[0], 1, 1, 1))
+        return np.ascontiguousarray(z, np.float32)
 
     def _sigmas(self, num_inference_steps, sigmas):
         """retrieve_timesteps(scheduler, num_inference_steps, sigmas=sigmas) on FlowMatchEulerDiscreteScheduler: custom sigmas
@@ -303,7 +344,8 @@ class StableDiffusion3PromptDiffusionPipeline:
                  negative_pooled_prompt_embeds=None, ip_adapter_image=None, ip_adapter_image_embeds=None,
                  output_type: Optional[str] = "pil", return_dict: bool = True, joint_attention_kwargs: Optional[Dict[str, Any]] = None,
                  clip_skip: Optional[int] = None, callback_on_step_end: Optional[Callable] = None,
-                 callback_on_step_end_tensor_inputs: List[str] = ["latents"], max_sequence_length: int = 256):
+                 callback_on_step_end_tensor_inputs: List[str] = ["latents"], max_sequence_length: int = 256, _edit: Optional[dict] = None):
+        """_edit: set by the img2img / inpaint subclasses -- {"image", "strength", "mask_image"}."""
         if ip_adapter_image is not None or ip_adapter_image_embeds is not None:
             raise NotImplementedError("ip_adapter_image / ip_adapter_image_embeds are outside the engine's path")
         if joint_attention_kwargs:
@@ -379,11 +421,28 @@ class StableDiffusion3PromptDiffusionPipeline:
         height, width = cond_lat.shape[-2] * self.vae_scale_factor, cond_lat.shape[-1] * self.vae_scale_factor
         # 4. timesteps
         sig, num_inference_steps = self._sigmas(num_inference_steps, sigmas)
+        if _edit is not None:        # get_timesteps of diffusers' SD3 img2img: the loop runs on the tail of the grid
+            t_start = img2img_start(num_inference_steps, _edit["strength"])
+            sig, num_inference_steps = np.ascontiguousarray(sig[t_start:]), num_inference_steps - t_start
         self._num_timesteps = num_inference_steps
         # 5. latents
-        latents = self.prepare_latents(B, cfg.in_channels, height, width, generator, latents)
-        if tuple(latents.shape) != tuple(cond_lat.shape):
-            raise ValueError(f"latents {tuple(latents.shape)} and control latents {tuple(cond_lat.shape)} differ")
+        if isinstance(generator, EngineGenerator):
+            generator.bind(self.engine)
+        z0 = mask = None
+        from_seed = False
+        if _edit is not None:
+            # z0 first, then the noise, in the order diffusers' prepare_latents draws them; `latents`, when given, is the noise eps
+            z0 = self._init_z0(_edit["image"], B, height, width, generator)
+            if _edit.get("mask_image") is not None:
+                mask = prepare_inpaint_mask(_edit["mask_image"], width, height, B, self.vae_scale_factor)
+            # the engine's generator in the fused loop: eps is drawn inside the update kernel, no tensor is made
+            from_seed = isinstance(generator, EngineGenerator) and latents is None and callback_on_step_end is None
+            if tuple(z0.shape) != tuple(cond_lat.shape):
+                raise ValueError(f"`image` latents {tuple(z0.shape)} and control latents {tuple(cond_lat.shape)} differ")
+        if not from_seed:
+            latents = self.prepare_latents(B, cfg.in_channels, height, width, generator, latents)
+            if tuple(latents.shape) != tuple(cond_lat.shape):
+                raise ValueError(f"latents {tuple(latents.shape)} and control latents {tuple(cond_lat.shape)} differ")
         cn_pooled = None
         if not cfg.force_zeros_for_pooled_projection and controlnet_pooled_projections is not None:
             cn_pooled = _np(controlnet_pooled_projections)
@@ -393,9 +452,13 @@ class StableDiffusion3PromptDiffusionPipeline:
                                          num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                                          controlnet_conditioning_scale=controlnet_conditioning_scale, sigmas=sig,
                                          control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end,
-                                         controlnet_pooled_projections=cn_pooled)
+                                         controlnet_pooled_projections=cn_pooled, init_latents=z0, mask=mask, from_seed=from_seed)
         else:
             n = num_inference_steps
+            one = np.float32(1.0)
+            if z0 is not None:       # the start state and, below, the blend: float32, in the order of the engine's update kernel
+                eps = latents
+                latents = sig[0] * eps + (one - sig[0]) * z0
             for i in range(n):
                 if self._interrupt:
                     continue
@@ -410,6 +473,9 @@ class StableDiffusion3PromptDiffusionPipeline:
                 if cfg_on:
                     v = v[:B] + np.float32(guidance_scale) * (v[B:] - v[:B])
                 latents = (latents + (sig[i + 1] - sig[i]) * v).astype(np.float32)
+                if mask is not None:
+                    known = (one - sig[i + 1]) * z0 + sig[i + 1] * eps
+                    latents = (one - mask) * known + mask * latents
                 kw = {k: {"latents": latents, "prompt_embeds": pe, "negative_prompt_embeds": npe,
                           "negative_pooled_prompt_embeds": nppe}[k] for k in callback_on_step_end_tensor_inputs}
                 out = callback_on_step_end(self, i, float(sig[i] * 1000.0), kw) or {}
@@ -434,3 +500,25 @@ class StableDiffusion3PromptDiffusionPipeline:
         if not return_dict:
             return (image,)
         return {"images": image}
+
+
+class StableDiffusion3PromptDiffusionImg2ImgPipeline(StableDiffusion3PromptDiffusionPipeline):
+    """diffusers' StableDiffusion3Img2ImgPipeline on the Prompt-Diffusion ControlNet path: every argument of the base __call__, plus
+    `image` (PIL, uint8 / float arrays, or [B, C, h, w] latents used as z0 directly) and `strength`: the loop runs the last
+    int(min(n * strength, n)) steps of the grid from sigma_0 eps + (1 - sigma_0) z0.  `latents`, when given, is the noise eps."""
+
+    def __call__(self, *args, image=None, strength: float = 0.6, **kwargs):
+        if image is None:
+            raise ValueError("`image` must be passed")
+        return super().__call__(*args, _edit={"image": image, "strength": float(strength)}, **kwargs)
+
+
+class StableDiffusion3PromptDiffusionInpaintPipeline(StableDiffusion3PromptDiffusionPipeline):
+    """diffusers' StableDiffusion3InpaintPipeline for a 16-channel transformer (no masked_image_latents): the img2img pipeline plus
+    `mask_image` (white = repaint; grayscale, binarised at 0.5, nearest resize to the latent grid, as the SD1.5 inpaint pipeline prepares
+    it).  After every step the kept region is reset to z0 noised to the next sigma with the call's one eps; at the end it is z0."""
+
+    def __call__(self, *args, image=None, mask_image=None, strength: float = 0.6, **kwargs):
+        if image is None or mask_image is None:
+            raise ValueError("`image` and `mask_image` must be passed")
+        return super().__call__(*args, _edit={"image": image, "mask_image": mask_image, "strength": float(strength)}, **kwargs)

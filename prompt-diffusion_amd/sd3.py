@@ -64,6 +64,27 @@ class pd_sd3_args(C.Structure):
                 ("cond", C.c_void_p), ("pair", C.c_void_p), ("cn_pooled", C.c_void_p), ("reserved", C.c_int64 * 3)]
 
 
+class pd_sd3_loop_args(C.Structure):
+    _fields_ = [("init_latents", C.c_void_p), ("mask", C.c_void_p), ("noise", C.c_void_p), ("flags", C.c_int32), ("reserved0", C.c_int32),
+                ("reserved", C.c_int64 * 4)]
+
+
+PD_INIT_PURE_NOISE, PD_XT_FROM_SEED = 1, 4      # pd_sd3_loop_args.flags (the SD1.5 loop's init_flags values)
+
+
+def img2img_start(num_inference_steps: int, strength: float) -> int:
+    """diffusers' SD3 img2img get_timesteps: the index t_start of the first kept step; the loop runs on sigmas[t_start:] and has
+    num_inference_steps - t_start steps.  ValueError for a strength outside [0, 1] or one that leaves no step."""
+    if not 0.0 <= strength <= 1.0:
+        raise ValueError(f"The value of strength should in [0.0, 1.0] but is {strength}")
+    n = int(num_inference_steps)
+    t_start = int(max(n - min(n * strength, n), 0))
+    if n - t_start < 1:
+        raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of pipeline steps is "
+                         f"{n - t_start} which is < 1 and not appropriate for this pipeline.")
+    return t_start
+
+
 @dataclass(frozen=True)
 class CLIPTextConfig:
     """One CLIPTextModelWithProjection (transformers' CLIPTextConfig names in the comments)."""
@@ -431,6 +452,8 @@ class SD3Engine:
         lib.pd_sd3_forward.argtypes = [C.c_void_p, C.POINTER(pd_sd3_args), C.c_void_p]
         lib.pd_sd3_control.argtypes = [C.c_void_p, C.POINTER(pd_sd3_args), C.c_int32, C.c_void_p]
         lib.pd_sd3_sample.argtypes = [C.c_void_p, C.POINTER(pd_sd3_args), C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]
+        lib.pd_sd3_sample_ex.argtypes = [C.c_void_p, C.POINTER(pd_sd3_args), C.POINTER(pd_sd3_loop_args), C.c_void_p, C.c_int32, C.c_float,
+                                         C.c_void_p, C.c_void_p]
         lib.pd_sd3_down_proj.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
         lib.pd_sd3_text_configure.argtypes = [C.c_void_p, C.POINTER(pd_sd3_text_config)]
         lib.pd_sd3_text_weights_missing.argtypes = [C.c_void_p]
@@ -712,13 +735,14 @@ class SD3Engine:
         return n + (self.vae_weights_missing() if self.vae_cfg is not None else 0)
 
     # ------------------------------------------------------------------ calls
-    def _args(self, latents, context, pooled, cond, pair, scale, timestep=None, rows=None, cn_pooled=None):
+    def _args(self, latents, context, pooled, cond, pair, scale, timestep=None, rows=None, cn_pooled=None, like=None):
+        """like: the tensor whose shape stands in for `latents` when a seeded or img2img call passes none"""
         bufs = [E._Buf(x) for x in (latents, context, pooled, cond, pair, cn_pooled)]
         mems = {b.mem for b in bufs if b.mem is not None}
         if len(mems) != 1:
             raise ValueError("all tensors of one call must live in the same memory space (NumPy / CPU or one CUDA device)")
         mem = mems.pop()
-        lat = bufs[0].owner
+        lat = bufs[0].owner if bufs[0].owner is not None else like
         B, _, H, Wd = lat.shape
         rows = rows or B
         if tuple(bufs[1].owner.shape[::2]) != (rows, self.cfg.joint_dim) or tuple(bufs[2].owner.shape) != (rows, self.cfg.pooled_dim):
@@ -774,9 +798,33 @@ class SD3Engine:
     def sample(self, latents, prompt_embeds, pooled_prompt_embeds, negative_prompt_embeds=None, negative_pooled_prompt_embeds=None,
                control_latents=None, pair_latents=None, num_inference_steps: int = 28, guidance_scale: float = 7.0,
                controlnet_conditioning_scale: float = 1.0, shift: float = 3.0, sigmas=None, control_guidance_start: float = 0.0,
-               control_guidance_end: float = 1.0, controlnet_pooled_projections=None):
+               control_guidance_end: float = 1.0, controlnet_pooled_projections=None, init_latents=None, mask=None, noise=None,
+               from_seed: bool = False):
         """The denoising loop of the reference's __call__ (promptdiffusioncontrolnetpipeline_sd3.py:1192-1245) from initial
-        noise `latents` to final latents.  guidance_scale > 1 needs the negative embeddings (batch [negative ; positive])."""
+        noise `latents` to final latents.  guidance_scale > 1 needs the negative embeddings (batch [negative ; positive]).
+
+        Img2img / inpainting / seeded noise (pd_sd3_sample_ex; arithmetic in include/pdengine.h, pd_sd3_loop_args), on the `sigmas`
+        given -- truncating the grid by a strength is the caller's (img2img_start):
+          init_latents [B, C, h, w]  z0: the loop starts from sigmas[0] eps + (1 - sigmas[0]) z0, eps = `noise`, else `latents`
+          mask [B, 1, h, w] (or [B, h, w])  needs init_latents; after every step x <- (1 - m) k + m x, 1 = repaint
+          from_seed                  eps (without init_latents: the start latents) is the engine's draw at ("xt", 0) under set_rng;
+                                     `latents` and `noise` must be None
+        A call that uses none of the four runs the plain loop exactly as before."""
+        edit = init_latents is not None or mask is not None or noise is not None or from_seed
+        if edit:
+            if mask is not None and init_latents is None:
+                raise ValueError("`mask` needs `init_latents`")
+            if noise is not None and init_latents is None:
+                raise ValueError("`noise` needs `init_latents` (the start latents of a plain call are `latents`)")
+            if from_seed and (latents is not None or noise is not None):
+                raise ValueError("from_seed draws the noise in the engine: `latents` and `noise` must be None")
+            if not from_seed and latents is None and noise is None:
+                raise ValueError("the noise is required: `latents`, `noise` or from_seed=True")
+            if noise is not None:
+                latents = None                       # eps is `noise`; pd_sd3_sample_ex ignores args->latents then
+        like = next((t for t in (latents, noise, init_latents, control_latents) if t is not None), None)
+        if like is None:
+            raise ValueError("from_seed without `init_latents` needs `control_latents` to give the latent shape")
         cfg_on = guidance_scale > 1.0
         if cfg_on and (negative_prompt_embeds is None or negative_pooled_prompt_embeds is None):
             raise ValueError("guidance_scale > 1 needs negative_prompt_embeds and negative_pooled_prompt_embeds")
@@ -793,15 +841,49 @@ class SD3Engine:
         sig = flow_match_sigmas(num_inference_steps, shift) if sigmas is None else np.ascontiguousarray(sigmas, np.float32)
         if sig.shape != (num_inference_steps + 1,):
             raise ValueError("sigmas must hold num_inference_steps + 1 values")
-        B = latents.shape[0]
+        B = like.shape[0]
         a, keep, mem, lat = self._args(latents, ctx, pooled, control_latents, pair_latents, controlnet_conditioning_scale,
-                                       rows=2 * B if cfg_on else B, cn_pooled=controlnet_pooled_projections)
+                                       rows=2 * B if cfg_on else B, cn_pooled=controlnet_pooled_projections, like=like)
+        loop = None
+        if edit:
+            if mask is not None and len(mask.shape) == 3:
+                mask = mask[:, None]
+            extra = [E._Buf(t) for t in (init_latents, mask, noise)]
+            for b, shp, what in zip(extra, (tuple(lat.shape), (B, 1) + tuple(lat.shape[2:]), tuple(lat.shape)), ("init_latents", "mask", "noise")):
+                if b.owner is None:
+                    continue
+                if b.mem != mem:
+                    raise ValueError("all tensors of one call must live in the same memory space (NumPy / CPU or one CUDA device)")
+                if tuple(b.owner.shape) != shp:
+                    raise ValueError(f"`{what}` must be {list(shp)}, got {list(b.owner.shape)}")
+            keep = keep + extra
+            loop = pd_sd3_loop_args()
+            loop.init_latents, loop.mask, loop.noise = (b.ptr for b in extra)
+            loop.flags = PD_XT_FROM_SEED if from_seed else 0
+            self.base._order_after_torch(mem)
         # controlnet_keep (pipeline :1155-1162): the ControlNet acts on the steps inside [start, end] of the schedule
         n = num_inference_steps
         keep_steps = np.array([1.0 - float(i / n < control_guidance_start or (i + 1) / n > control_guidance_end) for i in range(n)],
                               np.float32)
         scales = np.ascontiguousarray(keep_steps * np.float32(controlnet_conditioning_scale))
         out, ptr = self._out(mem, lat, tuple(lat.shape))
+        if loop is not None:
+            self.base._check(self.base.lib.pd_sd3_sample_ex(self.base._h, C.byref(a), C.byref(loop), sig.ctypes.data, num_inference_steps,
+                                                            float(guidance_scale), scales.ctypes.data, ptr))
+            return out
         self.base._check(self.base.lib.pd_sd3_sample(self.base._h, C.byref(a), sig.ctypes.data, num_inference_steps,
                                                      float(guidance_scale), scales.ctypes.data, ptr))
         return out
+
+    def set_rng(self, seed: int, sample_base: int = 0) -> None:
+        """Seed and first global sample index of the engine's Philox generator (Engine.set_rng): what from_seed and
+        vae_encode(mode="sample") without noise draw from."""
+        self.base.set_rng(seed, sample_base)
+
+    @property
+    def rng(self) -> Tuple[int, int]:
+        return self.base.rng
+
+    def randn(self, shape, stream="step", draw: int = 0, device=None):
+        """The standard normals the engine draws at (stream, draw) (Engine.randn); from_seed consumes ("xt", 0)."""
+        return self.base.randn(shape, stream=stream, draw=draw, device=device)
