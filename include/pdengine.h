@@ -299,6 +299,43 @@ int pd_hed_configure(pd_engine* e);
 int pd_hed_weights_missing(pd_engine* e);    /* 0 when not configured */
 int pd_hed_detect(pd_engine* e, const float* images, int32_t B, int32_t H, int32_t W, int32_t mem, int32_t what, float* out);
 
+/* M-LSD line detector: the annotator behind the reference's "mlsd" task, the straight-line condition map (MLSDdetector.__call__,
+ * annotator/mlsd/__init__.py:27-39; pred_lines, annotator/mlsd/utils.py:47-86; MobileV2_MLSD_Large, models/mbv2_mlsd_large.py):
+ * MobileNetV2 features 0..13 (depthwise conv3x3 + pointwise conv1x1), a top-down decoder (blocks 15..23: conv1x1 pairs into a
+ * concat, bilinear x2 upsamples with align_corners = True, conv3x3 pairs, one conv3x3 of dilation 5), then on the [B, 9, H/2, W/2]
+ * map: 3x3 non-maximum suppression of the centre channel, the 200 best peaks, score and length thresholds, end points, cv2.line.
+ * pd_mlsd_configure registers the network on an existing engine (any pd_config; a registry group of its own) under "mlsd." + the
+ * checkpoint's keys.  Every BatchNorm is FOLDED into the conv in front of it, and the registry holds the folded form only: per conv its
+ * weight under the conv's own key ("mlsd.backbone.features.0.0.weight", [32, 4, 3, 3]) and one bias under the key of the BatchNorm's
+ * bias ("mlsd.backbone.features.0.1.bias"); block23.conv3, which has no BatchNorm, keeps its own weight and bias.  With s = gamma /
+ * sqrt(running_var + 1e-5): weight' = weight * s[:, None, None, None], bias' = (conv_bias - running_mean) * s + beta (conv_bias 0
+ * where the conv has none).  A host folds before pd_load_weights (the Python Engine.load_mlsd_state_dict does, in fp64, rounding once);
+ * pd_read_weights returns folded tensors.  Calling pd_mlsd_configure again does nothing.
+ * pd_mlsd_detect: images [B, H, W, 3] uint8 RGB; the constant-one fourth channel and x / 127.5 - 1 happen inside, in fp32.  H and W
+ * multiples of 32 (five stride-2 layers; the reference's resize_image gives multiples of 64).  The reference handles one image per call
+ * with input_shape = the image's own shape; a batch is B independent images.  thr_v >= 0.  `images` and `out` live in `mem`.  Needs all
+ * mlsd.* weights and no active sampling session.  The rasteriser restates cv2.line (thickness 1, LINE_8: clipLine, then LineIterator);
+ * its byte parity with OpenCV itself is unverified where OpenCV is absent. */
+#define PD_MLSD_TPMAP    0   /* the network output, channels 7..15 of block23   -> float [B, 9, H/2, W/2]                            */
+#define PD_MLSD_SEGMENTS 1   /* the kept segments, best score first             -> int32 [B, 200, 4] (x0, y0, x1, y1), then int32 [B] counts */
+#define PD_MLSD_LINES    2   /* the segments drawn white on black               -> uint8 [B, H, W] of 0 / 255                        */
+int pd_mlsd_configure(pd_engine* e);
+int pd_mlsd_weights_missing(pd_engine* e);   /* 0 when not configured */
+int pd_mlsd_detect(pd_engine* e, const uint8_t* images, int32_t B, int32_t H, int32_t W, int32_t mem, int32_t what, float thr_v, float thr_d,
+                   void* out);
+/* ... with, for PD_MLSD_LINES, the float form pd_canny also gives: channels c_off .. c_off + 2 of dst_f [B, Cf, H, W] fp32 (in mem_f)
+ * receive (v / 255) * mul + add, the other channels keep their values; out may then be NULL.  dst_f NULL: pd_mlsd_detect. */
+typedef struct pd_mlsd_args {
+    const uint8_t* images;
+    int32_t B, H, W, mem, what;
+    float thr_v, thr_d;
+    void* out;
+    float* dst_f;
+    int32_t mem_f, Cf, c_off;
+    float mul, add;
+} pd_mlsd_args;
+int pd_mlsd_detect_ex(pd_engine* e, const pd_mlsd_args* a);
+
 /* Image ends: the uint8 pictures at both ends of a call, on the device.  Every step is integer or single-rounding fp32 arithmetic,
  * so the results are bit-identical to the host code they replace (Pillow's 8-bit Image.resize, NumPy's / 255, clip, round).
  *

@@ -130,6 +130,25 @@ int pd_op_hed_fuse(pd_engine* e, const float* scores, const float* cw, const flo
  * passed through -> out [B, H, W], the same map with every weak pixel that is 8-connected, through weak pixels, to a strong one set
  * to PD_CANNY_STRONG.  states and out live in `mem`.  Stat "canny_sweeps" holds the launches it took. */
 int pd_op_canny_hysteresis(pd_engine* e, const uint8_t* states, int B, int H, int W, int mem, uint8_t* out);
+/* The M-LSD line detector's own kernels (mlsd.hip), one at a time.
+ * pd_op_dwconv3x3: depthwise conv3x3 + bias + ReLU6 in the compute type; x [B, C, H, W], w [C, 1, 3, 3], bias [C] -> y [B, C, Ho, Wo].
+ *   stride 1: padding 1, Ho = H; stride 2: F.pad(x, (0, 1, 0, 1)) + padding 0, Ho = H / 2 (H, W even).  in_relu6 != 0: the kernel reads
+ *   min(max(x, 0), 6) (the ReLU6 of the producing layer, applied while loading).  C a multiple of 8.
+ * pd_op_upcat_bilinear: F.interpolate(x, scale_factor=2, mode="bilinear", align_corners=True) of x [B, C, h, w] into channels
+ *   c_off .. c_off + C - 1 of y [B, Cy, 2h, 2w], which is read (in the compute type), written in place and returned: its other channels
+ *   must come back as they went in.  C, Cy, c_off multiples of 8.
+ * pd_op_conv2d_dilated: nn.Conv2d(Cin, Cout, 3, padding=d, dilation=d) (+ ReLU) through the engine's dispatch, which sends a dilated
+ *   conv to the implicit-GEMM gather (GemmParams::dil_m1).
+ * pd_op_mlsd_decode: tp [B, 9, h, w] fp32 -> segs int32 [B, 200, 4], count int32 [B]: pred_lines' decode (3x3 NMS of channel 0, the
+ *   200 best, score > thr_v and length > thr_d, end points 2 (x + disp) truncated), fp32 in every mode.
+ * pd_op_draw_lines: segs int32 [B, n, 4], count [B] -> out uint8 [B, H, W]: cv2.line(thickness 1, LINE_8) of each, 255 on 0. */
+int pd_op_dwconv3x3(pd_engine* e, const float* x, const float* w, const float* bias, int B, int C, int H, int W, int stride, int in_relu6,
+                    float* y);
+int pd_op_upcat_bilinear(pd_engine* e, const float* x, int B, int C, int h, int w, int Cy, int c_off, float* y);
+int pd_op_conv2d_dilated(pd_engine* e, const float* x, const float* w, const float* bias, int B, int Cin, int H, int W, int Cout, int dilation,
+                         int relu, float* y);
+int pd_op_mlsd_decode(pd_engine* e, const float* tp, int B, int h, int w, float thr_v, float thr_d, int32_t* segs, int32_t* count);
+int pd_op_draw_lines(pd_engine* e, const int32_t* segs, const int32_t* count, int B, int n, int H, int W, uint8_t* out);
 /* The assembling kernel of a tiled VAE call (vae_tile_blend_kernel) alone, on a caller's tiles: plan = the rows x cols entries of
  * pd_vae_tile_plan (th, tw, ev, eh, oh, ow are read); tiles = the tiles back to back in plan order, each fp32 [B][th][tw][Cpad] (NHWC, Cpad
  * a multiple of 4).  nchw != 0: out [B][C][H][W] (the decode side, channels >= C dropped); else out [B][H][W][Cpad] (the encode side's

@@ -19,7 +19,7 @@ def __getattr__(name):   # the pipelines and the annotators, imported on first u
     if name in _SD3_PIPELINES:
         from . import pipeline_sd3
         return getattr(pipeline_sd3, name)
-    if name in ("HEDdetector", "CannyDetector"):   # the annotators (annotators.py), NumPy only on import
+    if name in ("HEDdetector", "CannyDetector", "MLSDdetector"):   # the annotators (annotators.py), NumPy only on import
         from . import annotators
         return getattr(annotators, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -7,9 +7,13 @@ the GPU as well with ``detect(..., device=True)``.
 (``Engine.canny``: Sobel / non-maximum suppression, the hysteresis flood and the output are gfx950 kernels behind ``pd_canny``).  Its
 arithmetic is integer and pinned byte for byte to a NumPy restatement of OpenCV's algorithm (tests/canny_ref.py), and to ``cv2`` itself
 only where ``cv2`` is installed; neither this module nor the engine needs OpenCV.
+``MLSDdetector`` is the reference's ``annotator.mlsd.MLSDdetector`` with all of it on the engine (``Engine.mlsd``: MobileNetV2's
+depthwise convs, the decoder, the peak decode and the line rasteriser are gfx950 kernels behind ``pd_mlsd_detect``; only uint8 comes
+back).  Its decode and rasteriser are pinned to a NumPy restatement (tests/mlsd_ref.py) and, through the fixture, to the reference's
+own ``pred_lines``; byte parity of the rasteriser with ``cv2.line`` itself is checked only where ``cv2`` is installed.
 ``HWC3`` and ``resize_image`` restate ``annotator/util.py`` in NumPy + PIL.  ``nms`` (the scribble step of ``annotator/hed``, which
-goes through cv2's float ``GaussianBlur``) and the annotators with networks whose code and weights are not at hand (MiDaS,
-UniFormer) are not built.
+goes through cv2's float ``GaussianBlur``) and the annotators whose networks need packages that are not at hand (MiDaS: timm;
+UniFormer: mmcv's compiled extension) are not built.
 """
 from __future__ import annotations
 
@@ -105,3 +109,34 @@ class CannyDetector:
         if img.ndim not in (2, 3):
             raise ValueError("CannyDetector expects one HW or HWC image")
         return self.detect(img[None], low_threshold, high_threshold)[0]
+
+
+class MLSDdetector:
+    """``annotator.mlsd.MLSDdetector`` on an engine built with ``ModelConfig(mlsd=True)`` whose mlsd.* weights are loaded
+    (``Engine.load_mlsd_state_dict``)."""
+
+    def __init__(self, engine):
+        self.engine = engine
+
+    def detect(self, images, thr_v, thr_d, device: bool = False):
+        """Batched form: uint8 [B, H, W, 3] RGB (NumPy, or a CPU / CUDA torch tensor) -> uint8 [B, H, W] of 0 / 255; H and W
+        multiples of 32.  Every image is handled on its own.  device: the line map stays on the GPU and comes back as a CUDA tensor
+        (a CUDA tensor in then never leaves it); otherwise a NumPy array comes back."""
+        sh = tuple(images.shape)
+        if len(sh) != 4 or sh[3] != 3:
+            raise ValueError(f"detect expects uint8 [B, H, W, 3], got {sh}")
+        if not device:
+            return self.engine.mlsd(images, thr_v, thr_d, what="lines", host=True)
+        if not hasattr(images, "is_cuda"):
+            import torch
+            images = torch.from_numpy(np.array(images))   # (a copy: torch wants a writable array)
+        return self.engine.mlsd(images, thr_v, thr_d, what="lines")
+
+    def __call__(self, input_image: np.ndarray, thr_v, thr_d) -> np.ndarray:
+        """uint8 HWC RGB -> uint8 HW, as the reference's ``__call__``."""
+        img = np.asarray(input_image)
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError("MLSDdetector expects one HWC image with three channels")
+        if img.dtype != np.uint8:
+            raise ValueError("MLSDdetector expects uint8")
+        return self.detect(img[None], thr_v, thr_d)[0]

@@ -765,6 +765,10 @@ int pd_engine::check_gemm(const WMat& m, const Act& in, const Act& out, const Ge
         pd_set_error("gemm: asymmetric conv padding needs a plain conv3x3 (no upsample / fused GroupNorm / fp8 / GEGLU / V^T)");
         return 1;
     }
+    if (c.dilation != 1 && (c.dilation < 1 || m.taps != 9 || c.stride != 1 || c.ups || c.gn_coef || in.dt == DT_FP8 || m.geglu || c.VT)) {
+        pd_set_error("gemm: a dilated conv needs a plain conv3x3 of stride 1 (no upsample / fused GroupNorm / fp8 / GEGLU / V^T)");
+        return 1;
+    }
     // e4m3 operands with per-row scales: the layer's quantised copy
     if (in.dt == DT_FP8 && (!m.w8 || !c.a_scale || m.taps != 1 || m.geglu)) { pd_set_error("internal: fp8 GEMM without quantised weights / row scales"); return 1; }
     if (c.ln_in && !m.w_ln) { pd_set_error("internal: folded LayerNorm weights missing"); return 1; }
@@ -792,6 +796,7 @@ GemmParams pd_engine::fill_gemm(const WMat& m, const Act& in, const Act& out, co
     p.a_sample_rows = c.a_sample_rows; p.a_row_off = c.a_row_off;
     p.c_scale = c.c_scale;
     p.pad_shift = c.pad_shift;
+    p.dil_m1 = c.dilation - 1;
     if (in.dt == DT_FP8) { p.W = m.w8; p.Kpad = m.Kpad8; p.w_scale = m.wscale; p.a_scale = c.a_scale; }
     if (c.ln_in) {   // LayerNorm of `in` folded into this layer: raw A, folded weights, statistics from the producer
         p.W = m.w_ln; p.bias = m.bias_ln; p.ln_colsum = m.colsum;
@@ -802,7 +807,7 @@ GemmParams pd_engine::fill_gemm(const WMat& m, const Act& in, const Act& out, co
 
 // gemm: plan.  Which kernel family / tile / split a launch takes, from shapes, options and ncu alone (p: fill_gemm's, splitk 1).
 int pd_engine::patch_tiles(const GemmParams& p) const {
-    return (opt_patch && !p.pad_shift) ? conv_patch_tiles(p, P) : 0;   // the patch kernels pad 1 on every side
+    return (opt_patch && !p.pad_shift && !p.dil_m1) ? conv_patch_tiles(p, P) : 0;   // the patch kernels pad 1 on every side, taps one pixel apart
 }
 // conv3x3 with enough 16x16 patches to fill the chip: LDS-patch kernel (conv_patch.hip)
 bool pd_engine::patch_unsplit(int ptiles) const {
@@ -993,7 +998,7 @@ int pd_engine::gemm(const WMat& m, const Act& in, Act& out, const GemmCall& c) {
 }
 
 int pd_engine::conv(const ConvW& c, const Act& in, Act& out, GemmCall call) {
-    call.stride = c.stride; call.pad_shift = c.pad_shift;
+    call.stride = c.stride; call.pad_shift = c.pad_shift; call.dilation = c.dilation;
     return gemm(c.m, in, out, call);
 }
 
@@ -1053,7 +1058,7 @@ int pd_engine::groupnorm(const Act& x, Act& y, const float* g, const float* b, f
 // the input patch is staged, so the normalised tensor is never written to HBM; otherwise GroupNorm runs as its own pass.
 int pd_engine::conv_gn(const ConvW& c, const Act& x, Act& out, const float* g, const float* b, float eps, bool silu, GemmCall call,
                        const SlabDefer* in_slabs) {
-    call.stride = c.stride; call.pad_shift = c.pad_shift;
+    call.stride = c.stride; call.pad_shift = c.pad_shift; call.dilation = c.dilation;
     const bool fuse = opt_gn_fuse && x.C == c.m.cin_pad && patch_unsplit(patch_tiles(fill_gemm(c.m, x, out, call)));
     if (!fuse) {
         const size_t mk = arena.mark();

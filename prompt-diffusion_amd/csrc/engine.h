@@ -71,6 +71,7 @@ struct ConvW {
     WMat m;
     int cin = 0, cout = 0, k = 1, stride = 1;
     int pad_shift = 0;   // GemmParams::pad_shift: 1 = the encoder Downsample's F.pad(x, (0, 1, 0, 1)) + padding 0
+    int dilation = 1;    // conv3x3 only: taps `dilation` pixels apart, padding = dilation (GemmParams::dil_m1)
 };
 
 struct ResW {
@@ -212,6 +213,23 @@ struct HedW {
     float *comb_w = nullptr, *comb_b = nullptr;
 };
 
+// M-LSD line detector (pd_mlsd_configure, mlsd.cpp): annotator/mlsd/models/mbv2_mlsd_large.py MobileV2_MLSD_Large -- MobileNetV2
+// features 0..13 and the decoder blocks 15..23, every BatchNorm folded into its conv by the loader
+struct MlsdDw { float* w = nullptr; float* b = nullptr; int C = 0, stride = 1; };   // depthwise conv3x3 [C][9] + folded bias, fp32
+struct MlsdIR {                 // InvertedResidual: (expand 1x1 + ReLU6)? -> depthwise + ReLU6 -> project 1x1 (+ x)
+    bool expand = false, res = false;
+    ConvW pw1, pw2;
+    MlsdDw dw;
+};
+struct MlsdW {
+    bool built = false;
+    ConvW conv0;                // features.0: conv3x3 stride 2 (pad_shift 1), 4 -> 32
+    MlsdIR ir[13];              // features.1 .. features.13
+    ConvW a1[4], a2[4];         // BlockTypeA 15, 17, 19, 21: conv1 (deep input), conv2 (skip input)
+    ConvW b1[4], b2[4];         // BlockTypeB 16, 18, 20, 22
+    ConvW c1, c2, c3;           // BlockTypeC 23
+};
+
 // CLIP text transformer (text.cpp): the SD1.5 cond stage and SD3's CLIP-L / CLIP-G are this one stack
 struct TextLayerW {
     float *ln1_g = nullptr, *ln1_b = nullptr, *ln2_g = nullptr, *ln2_b = nullptr;
@@ -277,6 +295,7 @@ enum WeightGroup {
     GROUP_SD3_TEXT = 6,      // SD3 text encoders
     GROUP_SD3_VAE = 7,       // SD3's VAE decoder
     GROUP_SD3_VAE_ENCODER = 8,
+    GROUP_MLSD = 9,
 };
 
 struct Param {
@@ -343,6 +362,7 @@ struct GemmCall {
     int gate_stride = 0, c_sample_rows = 0, c_row_off = 0, vt_tok_off = 0, a_sample_rows = 0, a_row_off = 0;
     int pad_shift = 0;                                        // ConvW::pad_shift, set by conv()
     SlabDefer* defer = nullptr;
+    int dilation = 1;                                         // ConvW::dilation, set by conv()
 };
 
 // Which kernel a gemm() call takes (pd_engine::plan_gemm): the verbose-2 dispatch trace prints exactly this.
@@ -599,6 +619,17 @@ struct pd_engine {
     HedW hed;
     void build_hed();
     int hed_forward(const float* images_dev, int B, int H, int W, int what, float* out_dev);
+
+    // M-LSD line detector (mlsd.cpp): registered by pd_mlsd_configure, runs in the same workspace as the first stage
+    MlsdW mlsd;
+    void build_mlsd();
+    void build_conv_bn(const std::string& conv, const std::string& bn, ConvW& c, int cin, int cout, int k, int stride);
+    void build_dw_bn(const std::string& conv, const std::string& bn, MlsdDw& d, int C, int stride);
+    int mlsd_dwconv(const MlsdDw& d, const Act& x, Act& y);
+    // images_dev [B][H][W][3] u8 -> tp_dev [B][9][H/2][W/2] fp32
+    int mlsd_forward(const uint8_t* images_dev, int B, int H, int W, float* tp_dev);
+    // tp [B][9][h][w] -> segs [B][200][4], count [B] (both device, allocated by the caller)
+    int mlsd_decode(const float* tp_dev, int B, int h, int w, float thr_v, float thr_d, int* segs_dev, int* count_dev);
 
     // Image ends (image_host.cpp, image_io.hip): buffers of pd_image_load / pd_image_store that grow on demand and never shrink
     struct ImageBuf { void* p = nullptr; size_t cap = 0; };

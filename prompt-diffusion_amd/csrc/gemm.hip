@@ -89,8 +89,8 @@ __global__ __launch_bounds__(WM * WN * 64, (BM == 128 && WM * WN == 8) ? 4 : 2) 
             const int rem = mm - b * p.rows_per_sample;
             const int oy = rem / p.Wout;
             a_pix[i] = b * p.Hin;
-            a_y[i] = oy * p.stride - 1 + p.pad_shift;
-            a_x[i] = (rem - oy * p.Wout) * p.stride - 1 + p.pad_shift;
+            a_y[i] = oy * p.stride - 1 - p.dil_m1 + p.pad_shift;   // padding = dilation
+            a_x[i] = (rem - oy * p.Wout) * p.stride - 1 - p.dil_m1 + p.pad_shift;
             a_base[i] = 0;
         } else {
             a_base[i] = (size_t)mm * p.lda;
@@ -174,6 +174,8 @@ __global__ __launch_bounds__(WM * WN * 64, (BM == 128 && WM * WN == 8) ? 4 : 2) 
             cof = k0 - tap * p.Cin;
             ky = tap / 3;
             kx = tap - ky * 3;
+            ky += ky * p.dil_m1;   // taps `dilation` pixels apart
+            kx += kx * p.dil_m1;
         }
         rmask = 0;
         static_for<A_ITERS>([&](auto I) __attribute__((always_inline)) {
@@ -565,8 +567,12 @@ int launch_prec(const GemmParams& p, hipStream_t s, hipEvent_t mid, int* parts) 
     // 0: 128x160, 1: 256x160, 2: 128x160 on 8 waves, 3: 256x320; split-K launches: 128x160, or 256x160 when the engine asks for it
     // (plain slab stores work from any tile; the in-kernel finalize of option splitk_fused exists for the 128x160 tile only)
     const int tile = p.splitk == 1 ? p.big_tile : ((p.big_tile == 1 && !p.tile_cnt) ? 1 : 0);
-    if (p.act == 5) {   // ACT_RELU: conv3x3 over operands of the storage type, in instantiations of its own
-        if (!conv || af32 || p.ln_stats || p.stats_out) return 1;
+    if (p.act == 5) {   // ACT_RELU: conv3x3 (HED, M-LSD) and conv1x1 (M-LSD) over operands of the storage type, in instantiations of their own
+        if (af32 || p.ln_stats || p.stats_out) return 1;
+        if (!conv) {
+            if (tile == 1 || tile == 3) return launch_one<P, 256, 160, 4, 2, false, false, false, false, true>(p, s, mid, parts);
+            return launch_one<P, 128, 160, 2, 2, false, false, false, false, true>(p, s, mid, parts);
+        }
         if (tile == 1 || tile == 3) return launch_one<P, 256, 160, 4, 2, true, false, false, false, true>(p, s, mid, parts);
         return launch_one<P, 128, 160, 2, 2, true, false, false, false, true>(p, s, mid, parts);
     }

@@ -710,6 +710,117 @@ int pd_op_hed_fuse(pd_engine* e, const float* scores, const float* cw, const flo
     return 0;
 }
 
+// M-LSD depthwise conv3x3 + bias + ReLU6 (launch_mlsd_dwconv) in the compute type: NCHW fp32 in and out
+int pd_op_dwconv3x3(pd_engine* e, const float* x, const float* w, const float* bias, int B, int C, int H, int W, int stride, int in_relu6,
+                    float* y) {
+    if (!e || !x || !w || !bias || !y) { pd_set_error("null argument"); return 1; }
+    if (B < 1 || C < 8 || C % 8 || H < 1 || W < 1 || (stride != 1 && stride != 2) || (stride == 2 && ((H | W) & 1))) {
+        pd_set_error("pd_op_dwconv3x3: need B, H, W >= 1, C a positive multiple of 8, stride 1 or 2, and even H, W at stride 2");
+        return 1;
+    }
+    HIP_OK(hipSetDevice(e->device));
+    const int dt = e->T, Ho = stride == 1 ? H : H / 2, Wo = stride == 1 ? W : W / 2;
+    DevBuf dx((size_t)B * H * W * C * dt_size(dt)), dy((size_t)B * Ho * Wo * C * dt_size(dt)), dw((size_t)C * 9 * 4), db((size_t)C * 4);
+    if (!dx.p || !dy.p || !dw.p || !db.p) { pd_set_error("allocation failed"); return 1; }
+    PD_TRY(to_dev_nhwc(e, x, dx.p, dt, B, C, H, W, C));
+    HIP_OK(hipMemcpy(dw.p, w, (size_t)C * 9 * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(db.p, bias, (size_t)C * 4, hipMemcpyHostToDevice));
+    if (launch_mlsd_dwconv(dx.p, dy.p, dt, reinterpret_cast<const float*>(dw.p), reinterpret_cast<const float*>(db.p), B, H, W, C, stride,
+                           in_relu6, e->stream)) {
+        pd_set_error("pd_op_dwconv3x3: launch failed");
+        return 1;
+    }
+    return from_dev_nhwc(e, dy.p, dt, y, B, C, Ho, Wo, C);
+}
+
+// M-LSD upsample into a concat buffer (launch_mlsd_upcat): y goes to the device, the kernel writes its channel range, y comes back
+int pd_op_upcat_bilinear(pd_engine* e, const float* x, int B, int C, int h, int w, int Cy, int c_off, float* y) {
+    if (!e || !x || !y) { pd_set_error("null argument"); return 1; }
+    if (B < 1 || h < 1 || w < 1 || C < 8 || C % 8 || Cy % 8 || c_off % 8 || c_off < 0 || c_off + C > Cy) {
+        pd_set_error("pd_op_upcat_bilinear: need B, h, w >= 1, C, Cy and c_off multiples of 8, and c_off + C <= Cy");
+        return 1;
+    }
+    HIP_OK(hipSetDevice(e->device));
+    const int dt = e->T;
+    DevBuf dx((size_t)B * h * w * C * dt_size(dt)), dy((size_t)B * 4 * h * w * Cy * dt_size(dt));
+    if (!dx.p || !dy.p) { pd_set_error("allocation failed"); return 1; }
+    PD_TRY(to_dev_nhwc(e, x, dx.p, dt, B, C, h, w, C));
+    PD_TRY(to_dev_nhwc(e, y, dy.p, dt, B, Cy, 2 * h, 2 * w, Cy));
+    if (launch_mlsd_upcat(dx.p, C, reinterpret_cast<char*>(dy.p) + (size_t)c_off * dt_size(dt), Cy, dt, B, h, w, C, e->stream)) {
+        pd_set_error("pd_op_upcat_bilinear: launch failed");
+        return 1;
+    }
+    return from_dev_nhwc(e, dy.p, dt, y, B, Cy, 2 * h, 2 * w, Cy);
+}
+
+// y = [relu](conv2d(x, w, b, padding = dilation, dilation)); x NCHW fp32, w OIHW
+int pd_op_conv2d_dilated(pd_engine* e, const float* x, const float* w, const float* bias, int B, int Cin, int H, int W, int Cout, int dilation,
+                         int relu, float* y) {
+    if (!e || !x || !w || !y) { pd_set_error("null argument"); return 1; }
+    if (B < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1 || dilation < 1) { pd_set_error("pd_op_conv2d_dilated: need B, Cin, Cout, H, W, dilation >= 1"); return 1; }
+    HIP_OK(hipSetDevice(e->device));
+    TempMat guard(e);
+    ConvW c;
+    c.cin = Cin; c.cout = Cout; c.k = 3; c.stride = 1; c.dilation = dilation;
+    e->make_mat(c.m, Cout, Cin * 9, 9, Cin, true);
+    if (!c.m.w) { pd_set_error("allocation failed"); return 1; }
+    PD_TRY(e->upload_rows(c.m, 0, w, Cout, true));
+    if (bias) PD_TRY(e->upload_vec(c.m.bias, bias, Cout, false, 0));
+    const int cpad = c.m.cin_pad, copad = round_up(Cout, 4);
+    DevBuf in((size_t)B * H * W * cpad * dt_size(e->T)), out((size_t)B * H * W * copad * dt_size(e->T));
+    if (!in.p || !out.p) { pd_set_error("allocation failed"); return 1; }
+    PD_TRY(to_dev_nhwc(e, x, in.p, e->T, B, Cin, H, W, cpad));
+    Act a, o;
+    a.p = in.p; a.B = B; a.H = H; a.W = W; a.C = cpad; a.dt = e->T;
+    o.p = out.p; o.B = B; o.H = H; o.W = W; o.C = copad; o.dt = e->T;
+    PD_TRY(e->conv(c, a, o, {.act = relu ? ACT_RELU : ACT_NONE}));
+    return from_dev_nhwc(e, out.p, e->T, y, B, Cout, H, W, copad);
+}
+
+int pd_op_mlsd_decode(pd_engine* e, const float* tp, int B, int h, int w, float thr_v, float thr_d, int32_t* segs, int32_t* count) {
+    if (!e || !tp || !segs || !count) { pd_set_error("null argument"); return 1; }
+    if (B < 1 || h < 1 || w < 1 || !std::isfinite(thr_v) || !std::isfinite(thr_d) || thr_v < 0.f) {
+        pd_set_error("pd_op_mlsd_decode: need B, h, w >= 1 and finite thresholds with thr_v >= 0");
+        return 1;
+    }
+    HIP_OK(hipSetDevice(e->device));
+    const size_t n_tp = (size_t)B * 9 * h * w, n_seg = (size_t)B * MLSD_TOPK * 4;
+    DevBuf dtp(n_tp * 4), dc((size_t)B * h * w * 8), dn((size_t)B * 4), ds(n_seg * 4), dk((size_t)B * 4);
+    if (!dtp.p || !dc.p || !dn.p || !ds.p || !dk.p) { pd_set_error("allocation failed"); return 1; }
+    HIP_OK(hipMemcpy(dtp.p, tp, n_tp * 4, hipMemcpyHostToDevice));
+    if (launch_mlsd_decode(reinterpret_cast<const float*>(dtp.p), reinterpret_cast<unsigned long long*>(dc.p), reinterpret_cast<int*>(dn.p),
+                           reinterpret_cast<int*>(ds.p), reinterpret_cast<int*>(dk.p), B, h, w, thr_v, thr_d, e->stream)) {
+        pd_set_error("pd_op_mlsd_decode: launch failed");
+        return 1;
+    }
+    HIP_OK(hipStreamSynchronize(e->stream));
+    HIP_OK(hipMemcpy(segs, ds.p, n_seg * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(count, dk.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int pd_op_draw_lines(pd_engine* e, const int32_t* segs, const int32_t* count, int B, int n, int H, int W, uint8_t* out) {
+    if (!e || !segs || !count || !out) { pd_set_error("null argument"); return 1; }
+    if (B < 1 || n < 1 || H < 1 || W < 1) { pd_set_error("pd_op_draw_lines: need B, n, H, W >= 1"); return 1; }
+    for (int b = 0; b < B; ++b)
+        if (count[b] < 0 || count[b] > n) { pd_set_error("pd_op_draw_lines: count[%d] = %d outside 0 .. %d", b, count[b], n); return 1; }
+    HIP_OK(hipSetDevice(e->device));
+    const size_t n_px = (size_t)B * H * W;
+    DevBuf ds((size_t)B * n * 16), dk((size_t)B * 4), dm(n_px), d8(n_px);
+    if (!ds.p || !dk.p || !dm.p || !d8.p) { pd_set_error("allocation failed"); return 1; }
+    HIP_OK(hipMemcpy(ds.p, segs, (size_t)B * n * 16, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(dk.p, count, (size_t)B * 4, hipMemcpyHostToDevice));
+    if (launch_mlsd_draw(reinterpret_cast<const int*>(ds.p), reinterpret_cast<const int*>(dk.p), n, reinterpret_cast<uint8_t*>(dm.p), B, H, W,
+                         e->stream) ||
+        launch_canny_emit(reinterpret_cast<const uint8_t*>(dm.p), reinterpret_cast<uint8_t*>(d8.p), nullptr, B, H, W, 0, 0, 1.f, 0.f, e->stream)) {
+        pd_set_error("pd_op_draw_lines: launch failed");
+        return 1;
+    }
+    HIP_OK(hipStreamSynchronize(e->stream));
+    HIP_OK(hipMemcpy(out, d8.p, n_px, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int pd_op_canny_hysteresis(pd_engine* e, const uint8_t* states, int B, int H, int W, int mem, uint8_t* out) {
     if (!e || !states || !out) { pd_set_error("null argument"); return 1; }
     if (B < 1 || H < 1 || W < 1) { pd_set_error("pd_op_canny_hysteresis: [%d, %d, %d]: sizes must be >= 1", B, H, W); return 1; }

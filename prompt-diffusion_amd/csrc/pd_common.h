@@ -168,8 +168,8 @@ static inline int ensure_dyn_smem(const void* fn, int bytes, unsigned long long*
 // Implicit-GEMM convolution / linear:  C[M,N] = epilogue( A_gather[M,K] x W[N,K]^T )
 // ---------------------------------------------------------------------------------------------
 // GemmParams::act (the kernels compare against the values).  ACT_RELU is compiled into instantiations of its own (pd_mma.h epilogue4_value<MM, RELU>:
-// plain conv3x3 on igemm / patch1 / patch2, and the split-K finalize pass), so no other launch carries a branch for it; the ring GEMM, the 4-wave
-// patch conv and every linear layer refuse it
+// plain conv3x3 on igemm / patch1 / patch2, conv1x1 on igemm (M-LSD), and the split-K finalize pass), so no other launch carries a branch for
+// it; the ring GEMM and the 4-wave patch conv refuse it
 // ACT_ERF_GELU (CLIP-G's fc1) lives in the MM instantiations like ACT_TANH_GELU; ACT_GATED_TANH_GELU (T5's wi_0 / wi_1 pair, packed like a GEGLU
 // matrix: x half = wi_1, gate half = wi_0) is gelu_new(gate) * x formed in fp32, saturated to the fp16 range on an fp16 store, in GG instantiations
 // of its own (gemm.hip GT).  Neither runs on the ring GEMM.
@@ -235,6 +235,9 @@ struct GemmParams {
     // the symmetric pad 1 of every other conv; 1 gives F.pad(x, (0, 1, 0, 1)) + padding 0, the KL-VAE encoder's Downsample
     // (model.py:80-88) -- the bounds check already reads row Hin / column Win as the bottom / right zero.
     int pad_shift;
+    // conv3x3 in the implicit-GEMM gather only: dilation - 1 (0 everywhere but M-LSD's block23.conv1, dilation 5): the taps sit
+    // dilation pixels apart and the padding is dilation on every side, so the output keeps the input's size
+    int dil_m1;
 };
 
 // element-wise / norm / attention launchers (definitions in the .hip files)
@@ -453,6 +456,29 @@ int launch_hed_stage_tail(const void* x, int dt, const float* sw, const float* s
 // scores[i] [B][H >> i][W >> i] fp32 (H, W multiples of 16), cw [5], cb [1] -> what 0: out [B][1][H][W] = sigmoid(cb + sum_i cw[i] up_i),
 // what 1: out [B][5][H][W] = up_i; up_i the bilinear upsample (align_corners = False) of map i by 2^i
 int launch_hed_fuse(const float* const scores[5], const float* cw, const float* cb, float* out, int B, int H, int W, int what, hipStream_t s);
+// mlsd.hip: the kernels of the M-LSD line detector that are no contraction (mlsd.cpp; include/pdengine.h "M-LSD line detector")
+// images [B][H][W][3] u8 -> out [B][H][W][8] in out_dt: channels 0..2 = u8 / 127.5 - 1 (fp32, each operation rounded once), channel 3 =
+// 1 / 127.5 - 1 (the reference's constant-one plane through the same map), channels 4..7 zero
+int launch_mlsd_upload(const uint8_t* in, void* out, int out_dt, int B, int H, int W, hipStream_t s);
+// depthwise conv3x3 + bias + ReLU6 on NHWC rows in dt: x [B][H][W][C] -> y [B][Ho][Wo][C]; w [C][9] fp32 (the checkpoint's [C, 1, 3, 3]),
+// bias [C] fp32; stride 1: padding 1, Ho = H; stride 2: a zero row / column at the bottom / right only, Ho = H / 2 (H, W even).
+// in_relu6: min(max(x, 0), 6) while loading (the producer's ReLU6; it stored max(x, 0)).  C a multiple of 16 bytes of dt
+int launch_mlsd_dwconv(const void* x, void* y, int dt, const float* w, const float* bias, int B, int H, int W, int C, int stride, int in_relu6,
+                       hipStream_t s);
+// F.interpolate(x, scale_factor=2, mode="bilinear", align_corners=True) of x [B][h][w][C] (row stride ldx) into channels of a wider
+// buffer: y [B][2h][2w][ldy] + the caller's channel offset; fp32 arithmetic, one rounding to dt.  C, ldx, ldy multiples of 16 bytes
+int launch_mlsd_upcat(const void* x, int ldx, void* y, int ldy, int dt, int B, int h, int w, int C, hipStream_t s);
+// x [B][h][w][16] fp32 NHWC -> tp [B][9][h][w] fp32: channels 7..15 (MobileV2_MLSD_Large.forward's x[:, 7:])
+int launch_mlsd_tpmap(const float* x, float* tp, int B, int h, int w, hipStream_t s);
+constexpr int MLSD_TOPK = 200;
+// tp [B][9][h][w] fp32 -> segs [B][MLSD_TOPK][4] int32 (x0, y0, x1, y1 in input pixels), count [B]; cand [B][h * w] and ncand [B] are
+// scratch (ncand zeroed by the launcher).  Two launches: peaks of the 3x3 non-maximum suppression, then per image the 200 best and
+// their thresholds and endpoints
+int launch_mlsd_decode(const float* tp, unsigned long long* cand, int* ncand, int* segs, int* count, int B, int h, int w, float thr_v,
+                       float thr_d, hipStream_t s);
+// segs / count as above -> map [B][H][W] u8 (zeroed by the launcher): CANNY_STRONG on every pixel of cv2.line(p0, p1, thickness 1,
+// LINE_8) -- clipped to the image, then the 8-connected Bresenham walk
+int launch_mlsd_draw(const int* segs, const int* count, int max_segs, uint8_t* map, int B, int H, int W, hipStream_t s);
 // image_io.hip: the image ends (image_host.cpp; include/pdengine.h "Image ends")
 // Pillow's horizontal 8-bit pass: src [rows][Ws][3] u8 -> out [rows][W][3] u8 with bounds [W][2] = (xmin, count <= ksize), kk [W][ksize]
 int launch_image_hpass(const uint8_t* src, uint8_t* out, const int* bounds, const int* kk, int ksize, long long rows, int Ws, int W,

@@ -14,7 +14,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .weights import ModelConfig, SD15, hed_key
+from .weights import ModelConfig, SD15, fold_mlsd_state_dict, hed_key
 
 PD_PREC_BF16, PD_PREC_F32, PD_PREC_F16, PD_PREC_F16X2 = 0, 1, 2, 3
 PRECISIONS = {"bf16": PD_PREC_BF16, "f32": PD_PREC_F32, "fp32": PD_PREC_F32, "f16": PD_PREC_F16, "fp16": PD_PREC_F16,
@@ -26,6 +26,9 @@ PD_VAE_MEAN, PD_VAE_SAMPLE, PD_VAE_MOMENTS = 0, 1, 2
 VAE_ENCODE_MODES = {"mean": PD_VAE_MEAN, "sample": PD_VAE_SAMPLE, "moments": PD_VAE_MOMENTS}
 PD_HED_EDGE, PD_HED_SIDES = 0, 1
 HED_OUTPUTS = {"edge": PD_HED_EDGE, "sides": PD_HED_SIDES}
+PD_MLSD_TPMAP, PD_MLSD_SEGMENTS, PD_MLSD_LINES = 0, 1, 2
+MLSD_OUTPUTS = {"tpmap": PD_MLSD_TPMAP, "segments": PD_MLSD_SEGMENTS, "lines": PD_MLSD_LINES}
+MLSD_TOPK = 200
 # image ends (include/pdengine.h, "Image ends"): the filters carry PIL's own numbers
 PD_RESAMPLE_LANCZOS, PD_RESAMPLE_BOX = 1, 4
 PD_RESAMPLE_MAX_SCALE = 8
@@ -105,6 +108,12 @@ class pd_image_load_args(C.Structure):
         ("mem_dst", C.c_int32), ("filter", C.c_int32), ("batch_mode", C.c_int32), ("mul", C.c_float), ("add", C.c_float),
         ("reserved", C.c_int32 * 4),
     ]
+
+
+class pd_mlsd_args(C.Structure):
+    _fields_ = [("images", C.c_void_p), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("mem", C.c_int32), ("what", C.c_int32),
+                ("thr_v", C.c_float), ("thr_d", C.c_float), ("out", C.c_void_p), ("dst_f", C.c_void_p), ("mem_f", C.c_int32),
+                ("Cf", C.c_int32), ("c_off", C.c_int32), ("mul", C.c_float), ("add", C.c_float)]
 
 
 class pd_canny_args(C.Structure):
@@ -265,6 +274,15 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.pd_image_store.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_int32]
     lib.pd_canny.argtypes = [C.c_void_p, C.POINTER(pd_canny_args)]
     lib.pd_op_canny_hysteresis.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    lib.pd_mlsd_configure.argtypes = [C.c_void_p]
+    lib.pd_mlsd_weights_missing.argtypes = [C.c_void_p]
+    lib.pd_mlsd_detect.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_float, C.c_float, C.c_void_p]
+    lib.pd_mlsd_detect_ex.argtypes = [C.c_void_p, C.POINTER(pd_mlsd_args)]
+    lib.pd_op_dwconv3x3.argtypes = [C.c_void_p, fp, fp, fp] + [C.c_int] * 6 + [fp]
+    lib.pd_op_upcat_bilinear.argtypes = [C.c_void_p, fp] + [C.c_int] * 6 + [fp]
+    lib.pd_op_conv2d_dilated.argtypes = [C.c_void_p, fp, fp, fp] + [C.c_int] * 7 + [fp]
+    lib.pd_op_mlsd_decode.argtypes = [C.c_void_p, fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
+    lib.pd_op_draw_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]
     lib.pd_op_sd3_update.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_float] * 3 + [C.c_int] * 3 + [C.c_void_p] * 2
     if path is None:
         _lib = lib
@@ -288,6 +306,8 @@ EXPORTS = [
     "pd_set_freeu", "pd_get_freeu", "pd_op_freeu_concat",
     "pd_philox4x32_10", "pd_set_rng", "pd_get_rng", "pd_randn",
     "pd_hed_configure", "pd_hed_weights_missing", "pd_hed_detect", "pd_op_hed_stage_tail", "pd_op_hed_fuse",
+    "pd_mlsd_configure", "pd_mlsd_weights_missing", "pd_mlsd_detect", "pd_mlsd_detect_ex", "pd_op_dwconv3x3", "pd_op_upcat_bilinear", "pd_op_conv2d_dilated",
+    "pd_op_mlsd_decode", "pd_op_draw_lines",
     "pd_resample_coefficients", "pd_image_load", "pd_image_store", "pd_canny", "pd_op_canny_hysteresis",
     "pd_sd3_text_configure", "pd_sd3_text_weights_missing", "pd_sd3_encode_prompt", "pd_sd3_text_encoder", "pd_t5_relative_buckets",
     "pd_sd3_vae_configure", "pd_sd3_vae_weights_missing", "pd_sd3_vae_config_layout", "pd_sd3_vae_decode", "pd_sd3_vae_encode", "pd_op_vae_attention", "pd_bench_vae_attention",
@@ -533,6 +553,8 @@ class Engine:
         self._check(self.lib.pd_engine_create(C.byref(c), device, C.byref(self._h)))
         if getattr(cfg, "hed", False):
             self._check(self.lib.pd_hed_configure(self._h))
+        if getattr(cfg, "mlsd", False):
+            self._check(self.lib.pd_mlsd_configure(self._h))
         self._keep: List[_Buf] = []
         self._rng_set = False    # the caller has chosen a seed (set_rng): draws nobody supplied may come from the engine
 
@@ -834,6 +856,84 @@ class Engine:
         self._order_after_torch(b.mem)
         self._check(self.lib.pd_hed_detect(self._h, b.ptr, B, H, W, b.mem, HED_OUTPUTS[what], op))
         return out
+
+    # ------------------------------------------------------------------ M-LSD line detector (pd_mlsd_*)
+    def mlsd_weights_missing(self) -> int:
+        return int(self.lib.pd_mlsd_weights_missing(self._h))
+
+    def load_mlsd_state_dict(self, sd) -> None:
+        """Load an M-LSD checkpoint (mlsd_large_512_fp32.pth) as it is: ``MobileV2_MLSD_Large.state_dict()`` keys, with or without the
+        registry's ``mlsd.`` prefix -- conv weights (and biases), BatchNorm weight / bias / running_mean / running_var (eps 1e-5;
+        num_batches_tracked is ignored).  Every BatchNorm is folded into the conv in front of it in float64, rounded once to float32
+        (weights.fold_mlsd_state_dict), and one weight and one bias per conv are uploaded."""
+        try:
+            folded = fold_mlsd_state_dict(sd)
+        except (KeyError, ValueError) as ex:
+            raise PdError(f"load_mlsd_state_dict: {ex.args[0]}") from None
+        for name, arr in folded.items():
+            self.load_tensor(name, arr)
+
+    def mlsd(self, images, thr_v: float = 0.1, thr_d: float = 0.1, what: str = "lines", *, out=None, c_off: int = 0, mul: float = 1.0,
+             add: float = 0.0, host: bool = False):
+        """M-LSD line detection (annotator/mlsd: MLSDdetector.__call__, pred_lines, MobileV2_MLSD_Large) on the device: uint8
+        pictures [B, H, W, 3] RGB (NumPy, or a CPU / CUDA torch tensor), H and W multiples of 32 ->
+          "lines":    the kept segments drawn white on black (cv2.line, thickness 1)    uint8 [B, H, W] of 0 / 255
+          "segments": (int32 [B, 200, 4] of (x0, y0, x1, y1), best score first; int32 [B] counts)
+          "tpmap":    the network output                                                float32 [B, 9, H/2, W/2]
+        The constant-one fourth channel and x / 127.5 - 1 happen inside.  Every image of the batch is handled on its own, as the
+        reference handles its one.  A CUDA tensor comes out; NumPy with host=True or for a NumPy input.  out ("lines" only): an existing
+        contiguous float32 [B, Cf, H, W] whose channels c_off .. c_off + 2 also receive (lines / 255) * mul + add, as Engine.canny's.
+        Needs ModelConfig(mlsd=True) and the mlsd.* weights."""
+        if what not in MLSD_OUTPUTS:
+            raise ValueError(f"what must be one of {sorted(MLSD_OUTPUTS)}")
+        owner, sp, smem, sh = self._u8_source(images)
+        if len(sh) != 4 or sh[3] != 3:
+            raise ValueError(f"images must be uint8 [B, H, W, 3], got {tuple(sh)}")
+        B, H, W = int(sh[0]), int(sh[1]), int(sh[2])
+        a = pd_mlsd_args()
+        a.images, a.B, a.H, a.W, a.mem, a.what = sp, B, H, W, smem, MLSD_OUTPUTS[what]
+        a.thr_v, a.thr_d, a.mul, a.add = float(thr_v), float(thr_d), 1.0, 0.0
+        if out is not None:
+            if what != "lines":
+                raise ValueError("out goes with what='lines'")
+            if len(out.shape) != 4 or tuple(out.shape) != (B, out.shape[1], H, W):
+                raise ValueError(f"out must be [{B}, Cf, {H}, {W}], got {tuple(out.shape)}")
+            if _is_torch(out):
+                import torch
+                if out.dtype != torch.float32 or not out.is_contiguous():
+                    raise ValueError("out must be a contiguous float32 tensor")
+                a.dst_f, a.mem_f = out.data_ptr(), PD_MEM_DEVICE if out.is_cuda else PD_MEM_HOST
+            else:
+                if out.dtype != np.float32 or not out.flags.c_contiguous:
+                    raise ValueError("out must be a C-contiguous float32 array")
+                a.dst_f, a.mem_f = out.ctypes.data, PD_MEM_HOST
+            a.Cf, a.c_off, a.mul, a.add = int(out.shape[1]), int(c_off), float(mul), float(add)
+        # the C entry keeps `out` in the memory space of `images`: a host result for a CUDA input is copied down afterwards
+        on_dev = smem == PD_MEM_DEVICE
+        if what == "tpmap":
+            shape, dt = (B, 9, H // 2, W // 2), np.float32
+        elif what == "segments":
+            shape, dt = (B * MLSD_TOPK * 4 + B,), np.int32
+        else:
+            shape, dt = (B, H, W), np.uint8
+        if on_dev:
+            import torch
+            res = torch.empty(shape, dtype={np.float32: torch.float32, np.int32: torch.int32, np.uint8: torch.uint8}[dt], device=owner.device)
+            a.out = res.data_ptr()
+        else:
+            res = np.empty(shape, dt)
+            a.out = res.ctypes.data
+        self._order_after_torch(PD_MEM_DEVICE if on_dev or (out is not None and a.mem_f == PD_MEM_DEVICE) else PD_MEM_HOST)
+        self._check(self.lib.pd_mlsd_detect_ex(self._h, C.byref(a)))
+        del owner
+        if on_dev and host:
+            res = res.cpu().numpy()
+        elif not on_dev and not host and _is_torch(images):
+            import torch
+            res = torch.from_numpy(res).to(self._torch_device())
+        if what == "segments":
+            return res[:B * MLSD_TOPK * 4].reshape(B, MLSD_TOPK, 4), res[B * MLSD_TOPK * 4:]
+        return res
 
     # ------------------------------------------------------------------ image ends (pd_image_load / pd_image_store)
     def _torch_device(self):
@@ -1562,6 +1662,64 @@ class Engine:
         out = np.empty((B, 5 if what == "sides" else 1, H, W), np.float32)
         self._check(self.lib.pd_op_hed_fuse(self._h, flat.ctypes.data, cw.ctypes.data, cb.ctypes.data, B, H, W, HED_OUTPUTS[what],
                                             out.ctypes.data))
+        return out
+
+    def op_dwconv3x3(self, x, w, b, stride: int = 1, in_relu6: bool = False):
+        """The M-LSD depthwise conv3x3 + bias + ReLU6 (mlsd_dwconv_kernel) in the compute type: x [B,C,H,W], w [C,1,3,3], b [C] ->
+        [B,C,Ho,Wo]; stride 2 pads a zero row / column at the bottom / right only.  in_relu6: min(max(x, 0), 6) while loading."""
+        x = np.ascontiguousarray(x, np.float32)
+        w = np.ascontiguousarray(np.asarray(w, np.float32).reshape(-1))
+        b = np.ascontiguousarray(np.asarray(b, np.float32).reshape(-1))
+        B, Cc, H, W = x.shape
+        if w.size != Cc * 9 or b.size != Cc:
+            raise ValueError("w must be [C, 1, 3, 3] and b [C]")
+        y = np.empty((B, Cc, H // stride, W // stride), np.float32)
+        self._check(self.lib.pd_op_dwconv3x3(self._h, x.ctypes.data, w.ctypes.data, b.ctypes.data, B, Cc, H, W, int(stride), int(bool(in_relu6)),
+                                             y.ctypes.data))
+        return y
+
+    def op_upcat_bilinear(self, x, y, c_off: int):
+        """The M-LSD upsample into a concat buffer (mlsd_upcat_kernel): x [B,C,h,w] -> channels c_off .. c_off + C - 1 of a copy of
+        y [B,Cy,2h,2w] (stored in the compute type), which is returned; its other channels come back as they went in."""
+        x = np.ascontiguousarray(x, np.float32)
+        y = np.array(y, np.float32, order="C")
+        B, Cc, h, w = x.shape
+        if y.shape != (B, y.shape[1], 2 * h, 2 * w):
+            raise ValueError(f"y must be [{B}, Cy, {2 * h}, {2 * w}]")
+        self._check(self.lib.pd_op_upcat_bilinear(self._h, x.ctypes.data, B, Cc, h, w, int(y.shape[1]), int(c_off), y.ctypes.data))
+        return y
+
+    def op_conv2d_dilated(self, x, w, b, dilation: int, relu: bool = False):
+        """nn.Conv2d(Cin, Cout, 3, padding=dilation, dilation=dilation) (+ ReLU) through the engine's dispatch."""
+        x = np.ascontiguousarray(x, np.float32); w = np.ascontiguousarray(w, np.float32)
+        bb = None if b is None else np.ascontiguousarray(b, np.float32)
+        B, Cin, H, W = x.shape
+        y = np.empty((B, w.shape[0], H, W), np.float32)
+        self._check(self.lib.pd_op_conv2d_dilated(self._h, x.ctypes.data, w.ctypes.data, None if bb is None else bb.ctypes.data, B, Cin, H, W,
+                                                  int(w.shape[0]), int(dilation), int(bool(relu)), y.ctypes.data))
+        return y
+
+    def op_mlsd_decode(self, tp, thr_v: float, thr_d: float):
+        """pred_lines' decode (mlsd_peaks_kernel + mlsd_select_kernel) of tp [B,9,h,w] float32 -> a list of int32 [n_b, 4] per image."""
+        tp = np.ascontiguousarray(tp, np.float32)
+        B, nine, h, w = tp.shape
+        if nine != 9:
+            raise ValueError("tp must be [B, 9, h, w]")
+        segs = np.zeros((B, MLSD_TOPK, 4), np.int32)
+        count = np.zeros(B, np.int32)
+        self._check(self.lib.pd_op_mlsd_decode(self._h, tp.ctypes.data, B, h, w, float(thr_v), float(thr_d), segs.ctypes.data, count.ctypes.data))
+        return [segs[b, :int(count[b])].copy() for b in range(B)]
+
+    def op_draw_lines(self, segs, H: int, W: int):
+        """cv2.line(thickness 1) of every segment (mlsd_draw_kernel): segs = one int [n_b, 4] array per image -> uint8 [B, H, W]."""
+        segs = [np.asarray(s, np.int32).reshape(-1, 4) for s in segs]
+        B, n = len(segs), max(1, max(len(s) for s in segs))
+        flat = np.zeros((B, n, 4), np.int32)
+        for b, s in enumerate(segs):
+            flat[b, :len(s)] = s
+        count = np.array([len(s) for s in segs], np.int32)
+        out = np.empty((B, H, W), np.uint8)
+        self._check(self.lib.pd_op_draw_lines(self._h, flat.ctypes.data, count.ctypes.data, B, n, int(H), int(W), out.ctypes.data))
         return out
 
     def op_freeu_concat(self, h, skip, s: float, b: float, h_add=None, skip_add=None):

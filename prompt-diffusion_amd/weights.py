@@ -64,6 +64,8 @@ class ModelConfig:
 
     # HED edge detector (annotator/hed/__init__.py): opt-in, fixed architecture, registered through pd_hed_configure
     hed: bool = False
+    # M-LSD line detector (annotator/mlsd): opt-in, fixed architecture, registered through pd_mlsd_configure
+    mlsd: bool = False
 
     @property
     def time_embed_dim(self) -> int:
@@ -391,6 +393,139 @@ def hed_key(name: str) -> str:
 
 
 _HED_NAMES = frozenset(n for n, _, _ in hed_spec())
+
+
+MLSD_PREFIX = "mlsd."
+_MLSD_SETTING = ((1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1))   # t, c, n, s (mbv2_mlsd_large.py:173-182)
+_MLSD_SKIP = (64, 32, 24, 16)    # in_c1 of blocks 15, 17, 19, 21
+MLSD_BN_EPS = 1e-5
+
+
+def _bn(prefix: str, c: int) -> Iterator[Spec]:
+    yield prefix + "weight", (c,), "bn_gamma"
+    yield prefix + "bias", (c,), "bn_beta"
+    yield prefix + "running_mean", (c,), "bn_mean"
+    yield prefix + "running_var", (c,), "bn_var"
+    yield prefix + "num_batches_tracked", (), "bn_count"
+
+
+def mlsd_layers() -> List[dict]:
+    """Every conv of ``MobileV2_MLSD_Large`` in ``state_dict()`` order: conv (key prefix), bn (key prefix of the BatchNorm behind it,
+    or None), cin, cout, k, groups, bias (the conv has one of its own)."""
+    out = []
+    f = "backbone.features."
+    add = lambda conv, bn, cin, cout, k, groups=1, bias=False: out.append(dict(conv=conv, bn=bn, cin=cin, cout=cout, k=k, groups=groups, bias=bias))
+    add(f + "0.0.", f + "0.1.", 4, 32, 3)
+    cin, idx = 32, 1
+    for t, c, n, s in _MLSD_SETTING:
+        for i in range(n):
+            p, hidden, j = f"{f}{idx}.conv.", cin * t, 0
+            if t != 1:
+                add(p + "0.0.", p + "0.1.", cin, hidden, 1)
+                j = 1
+            add(f"{p}{j}.0.", f"{p}{j}.1.", hidden, hidden, 3, groups=hidden)
+            add(f"{p}{j + 1}.", f"{p}{j + 2}.", hidden, c, 1)
+            cin, idx = c, idx + 1
+    for j in range(4):
+        a, b = f"block{15 + 2 * j}.", f"block{16 + 2 * j}."
+        add(a + "conv1.0.", a + "conv1.1.", 96 if j == 0 else 64, 64, 1, bias=True)
+        add(a + "conv2.0.", a + "conv2.1.", _MLSD_SKIP[j], 64, 1, bias=True)
+        add(b + "conv1.0.", b + "conv1.1.", 128, 128, 3, bias=True)
+        add(b + "conv2.0.", b + "conv2.1.", 128, 64, 3, bias=True)
+    add("block23.conv1.0.", "block23.conv1.1.", 64, 64, 3, bias=True)
+    add("block23.conv2.0.", "block23.conv2.1.", 64, 64, 3, bias=True)
+    add("block23.conv3.", None, 64, 16, 1, bias=True)
+    return out
+
+
+def mlsd_spec(prefix: str = MLSD_PREFIX) -> List[Spec]:
+    """The checkpoint inventory of ``MobileV2_MLSD_Large`` (annotator/mlsd/models/mbv2_mlsd_large.py; mlsd_large_512_fp32.pth) in
+    ``state_dict()`` order under ``mlsd.`` + its own keys: conv weights (and biases in the decoder blocks), and per BatchNorm
+    weight / bias / running_mean / running_var / num_batches_tracked."""
+    out: List[Spec] = []
+    for L in mlsd_layers():
+        out.append((prefix + L["conv"] + "weight", (L["cout"], L["cin"] // L["groups"], L["k"], L["k"]), "w"))
+        if L["bias"]:
+            out.append((prefix + L["conv"] + "bias", (L["cout"],), "b"))
+        if L["bn"]:
+            out += list(_bn(prefix + L["bn"], L["cout"]))
+    return out
+
+
+def mlsd_engine_spec(prefix: str = MLSD_PREFIX) -> List[Tuple[str, Tuple[int, ...]]]:
+    """What the engine registers (pd_mlsd_configure): per conv its weight under the conv's key and one bias under the key of the
+    BatchNorm's bias (block23.conv3: its own) -- the folded form ``fold_mlsd_state_dict`` produces."""
+    out = []
+    for L in mlsd_layers():
+        out.append((prefix + L["conv"] + "weight", (L["cout"], L["cin"] // L["groups"], L["k"], L["k"])))
+        out.append((prefix + (L["bn"] or L["conv"]) + "bias", (L["cout"],)))
+    return out
+
+
+# block23.conv3 of the seeded recipe: with the plain initialisation the reference's output is nearly flat (centre-logit std 0.017,
+# displacements +-0.4), which no test could see an error in; tests/golden/make_golden_mlsd.py asserts what these reach
+MLSD_HEAD_SCALE = {"center": 9.0, "center_shift": -1.9, "disp": 10.0, "other": 1.0}
+MLSD_GAMMA = 0.8    # mean of the BatchNorm weights: with 1 / sqrt(running_var) ~ 1.3 the activations neither die nor grow through the 60 layers
+
+
+def synth_mlsd_state_dict(seed: int = 1234) -> Dict[str, np.ndarray]:
+    """Seeded M-LSD checkpoint.  The BatchNorm tensors are all away from their initial values: gamma = MLSD_GAMMA + 0.2 N, beta = 0.1 + 0.2 N, running_mean = 0.2 N, running_var = 0.5 + 0.09 N^2.
+    block23.conv3's rows are scaled by MLSD_HEAD_SCALE (row 7: the centre logit, whose bias is also shifted; rows 8..11: the
+    displacements)."""
+    sd: Dict[str, np.ndarray] = {}
+    for n, s, k in mlsd_spec():
+        if k == "bn_count":
+            sd[n] = np.zeros((), np.int64)
+        elif k == "bn_gamma":
+            sd[n] = np.float32(MLSD_GAMMA) + np.float32(2.0) * synth_tensor(n, s, "beta", seed)
+        elif k == "bn_beta":
+            sd[n] = np.float32(0.1) + np.float32(2.0) * synth_tensor(n, s, "beta", seed)
+        elif k == "bn_mean":
+            sd[n] = np.float32(2.0) * synth_tensor(n, s, "beta", seed)
+        elif k == "bn_var":
+            sd[n] = np.float32(0.5) + (np.float32(3.0) * synth_tensor(n, s, "beta", seed)) ** 2
+        else:
+            x = synth_tensor(n, s, k, seed)
+            sd[n] = x
+    w, b = sd[MLSD_PREFIX + "block23.conv3.weight"], sd[MLSD_PREFIX + "block23.conv3.bias"]
+    scale = np.full(16, MLSD_HEAD_SCALE["other"], np.float32)
+    scale[7] = MLSD_HEAD_SCALE["center"]
+    scale[8:12] = MLSD_HEAD_SCALE["disp"]
+    sd[MLSD_PREFIX + "block23.conv3.weight"] = w * scale[:, None, None, None]
+    sd[MLSD_PREFIX + "block23.conv3.bias"] = b * scale
+    sd[MLSD_PREFIX + "block23.conv3.bias"][7] += np.float32(MLSD_HEAD_SCALE["center_shift"])
+    return sd
+
+
+def fold_mlsd_state_dict(sd) -> Dict[str, np.ndarray]:
+    """Checkpoint (keys with or without the ``mlsd.`` prefix; NumPy arrays or torch tensors) -> the engine's tensors
+    (``mlsd_engine_spec``): every BatchNorm folded into the conv in front of it, in float64, rounded once to float32.
+      s = gamma / sqrt(running_var + 1e-5);  weight' = weight * s[:, None, None, None];  bias' = (conv_bias - running_mean) * s + beta
+    ``num_batches_tracked`` is ignored; a missing tensor raises KeyError, an unknown key ValueError."""
+    src = {}
+    for k, v in (sd.items() if hasattr(sd, "items") else sd):
+        if hasattr(v, "detach"):
+            v = v.detach().cpu().numpy()
+        src[k if k.startswith(MLSD_PREFIX) else MLSD_PREFIX + k] = np.asarray(v)
+    known = {n for n, _, _ in mlsd_spec()}
+    extra = sorted(set(src) - known)
+    if extra:
+        raise ValueError(f"not an M-LSD tensor: '{extra[0]}'")
+    get = lambda k: src[k].astype(np.float64)
+    out: Dict[str, np.ndarray] = {}
+    for L in mlsd_layers():
+        conv = MLSD_PREFIX + L["conv"]
+        w = get(conv + "weight")
+        b = get(conv + "bias") if L["bias"] else np.zeros(L["cout"], np.float64)
+        if L["bn"]:
+            bn = MLSD_PREFIX + L["bn"]
+            s = get(bn + "weight") / np.sqrt(get(bn + "running_var") + MLSD_BN_EPS)
+            w = w * s[:, None, None, None]
+            b = (b - get(bn + "running_mean")) * s + get(bn + "bias")
+            out[conv + "weight"], out[bn + "bias"] = w.astype(np.float32), b.astype(np.float32)
+        else:
+            out[conv + "weight"], out[conv + "bias"] = w.astype(np.float32), b.astype(np.float32)
+    return out
 
 
 TEXT_PREFIX = "cond_stage_model.transformer.text_model."

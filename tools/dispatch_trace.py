@@ -1,6 +1,7 @@
 """Which kernel family / tile / split every contraction launch of one denoising step takes (engine option verbose = 2, stderr):
 python tools/dispatch_trace.py [--batch 8] [--size 512] [--precision f16|bf16|f32|f16x2];  prints the distinct lines with their counts.
 --hed traces the 13 trunk convs of the HED edge detector (Engine.hed on a batch of size x size images) instead.
+--mlsd traces the 45 contraction launches of the M-LSD line detector (Engine.mlsd) instead, in network order.
 PDENGINE_LIB=/path/to/libpdengine.so traces another build of the library (engine.load_library): diff the two outputs to compare builds."""
 import argparse, collections, os, subprocess, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -31,14 +32,28 @@ if len(sys.argv) > 1 and sys.argv[1] == "--child-hed":
     e.hed(x)
     e.set_option("verbose", 0)
     sys.exit(0)
+if len(sys.argv) > 1 and sys.argv[1] == "--child-mlsd":
+    import dataclasses
+    import numpy as np
+    from prompt_diffusion_amd import engine as E, weights as W
+    B = int(sys.argv[2]); L = int(sys.argv[3])
+    e = E.Engine(dataclasses.replace(W.TINY, mlsd=True), precision=sys.argv[4])
+    e.load_mlsd_state_dict(W.synth_mlsd_state_dict())
+    x = np.random.default_rng(0).integers(0, 256, (B, L, L, 3), dtype=np.uint8)
+    e.mlsd(x, what="tpmap")
+    e.set_option("verbose", 2)
+    e.mlsd(x, what="tpmap")
+    e.set_option("verbose", 0)
+    sys.exit(0)
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=8)
 ap.add_argument("--size", type=int, default=512)
 ap.add_argument("--precision", default="f16", choices=["f16", "bf16", "f32", "f16x2"])
 ap.add_argument("--hed", action="store_true", help="the HED edge detector's trunk instead of a denoising step (launch order kept)")
+ap.add_argument("--mlsd", action="store_true", help="the M-LSD line detector's contractions instead (launch order kept)")
 a = ap.parse_args()
-r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-hed" if a.hed else "--child", str(a.batch), str(a.size), a.precision], capture_output=True, text=True)
-if a.hed:   # 13 launches, in network order
+r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-mlsd" if a.mlsd else "--child-hed" if a.hed else "--child", str(a.batch), str(a.size), a.precision], capture_output=True, text=True)
+if a.hed or a.mlsd:   # in network order
     for l in r.stderr.splitlines():
         if l.startswith("[pdengine] gemm"):
             print(l[len("[pdengine] gemm "):])
