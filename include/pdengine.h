@@ -644,7 +644,13 @@ int pd_comm_destroy(pd_engine* e); /* also done by pd_engine_destroy */
  *   "vae_flash" (2-byte modes: the first stage's mid-block attention on the single-head flash kernel, vae_attention.hip, instead of
  *   the materialised [N, N] scores: -1 = per VAE -- never for the SD1.5 first stage; for SD3's VAE where the score buffers would pass 2 GiB
  *   (past about 1100^2 pixels; below that the materialised launches measure faster) or h * w is no multiple of 8; 0 / 1 force both.  The
- *   fp32-storage modes always materialise; stat "vae_flash_launches" counts the launches that took the kernel). */
+ *   fp32-storage modes always materialise; stat "vae_flash_launches" counts the launches that took the kernel),
+ *   "gemm_tile" / "gemm_splitk" (test surface, -1 / -1 = the plan's own: the tile -- 0 = 128x160, 1 = 256x160, 2 = 128x160 on 8 waves,
+ *   3 = 256x320, 4 = 256x192 -- and the K slices -- 1 never, n >= 2 that many, at most one per K step -- of every launch the dispatch
+ *   sends to the implicit-GEMM family.  A launch the kernels do not have in that form is then an error: a split GEGLU or V^T launch; the
+ *   256x192 tile on a conv; and every tile the launcher would replace by another -- 2 / 3 / 4 in the fp32-storage modes, which have 0 and
+ *   1; 256x320 with a gate, a row remap, tanh- or erf-GELU, or on a conv (256x160 runs there); 2 / 3 / 4 on a split launch.  The plan's
+ *   own tile requests are mapped in the same way without an error; stat "gemm_tile" reports the tile that ran.  The defaults leave every plan as it is). */
 int pd_set_option(pd_engine* e, const char* key, int64_t value);
 /* "graph_captures" / "graph_replays" (step loops captured / replayed from a captured graph since the engine was created),
  * "workspace_bytes", "side_workspace_bytes" (the workspace of everything outside a sampling step -- first stage, HED, text encoders, SD3's VAE:
@@ -658,6 +664,9 @@ int pd_set_option(pd_engine* e, const char* key, int64_t value);
  * option "verbose" 2 dispatch trace prints: the weight-streaming GEMV, the LDS-patch conv3x3 generations 1 / 2 / 4, the ring GEMM, the
  * implicit GEMM, the four-phase upsample conv; -1 before the first launch.  pd_op_conv2d and pd_op_linear set it through the same dispatch as the network, so a
  * test can assert that an option setting put a shape on the kernel it names),
+ * "gemm_tile" / "gemm_splitk" (the tile of the instantiation that launch ran, as option "gemm_tile" numbers them -- not the plan's request
+ * where the launcher maps it to another; 0 outside the implicit-GEMM family -- and its K or channel-chunk slices),
+ * "gemm_ring_tile" (a ring GEMM launch: its tile, 0 = 128x160, 1 = 256x160, 2 / 3 their ping-pong forms, 4 = 64x80; -1 otherwise),
  * "attn_kernel" (which kernel family the engine's last multi-head attention launch took: PD_ATTN_GENERIC = attn_kernel, every mode,
  * head dim, causal mask and relative-position bias; PD_ATTN_PIPELINED = the double-buffered attn2_kernel of the 2-byte modes, which
  * takes every launch without mask and bias unless option "attn_legacy" is 1; 0 before the first launch) */

@@ -5,6 +5,7 @@
  *   pd_op_conv2d     nn.Conv2d 3x3/1x1 (stride 1/2, fused nearest-x2 upsample)   openaimodel.py:90-159,200-240
  *   pd_op_conv2d_upfold  Upsample's conv3x3(nearest_x2(x)) through the weight fold and the four-phase kernel   openaimodel.py:115-117
  *   pd_op_linear     nn.Linear / GEGLU / SiLU->Linear (emb_layers)                 attention.py:49-76, openaimodel.py:217-223
+ *   pd_op_linear_ex / pd_op_conv2d_ex  the same launches with every epilogue and addressing form the networks pass (pd_gemm_ex_args)
  *   pd_op_linear_fp8 the e4m3 form of nn.Linear used by the SD3 path's sd3_fp8 option
  *   pd_op_groupnorm  GroupNorm32 (+SiLU)                                           util.py:217-219, attention.py:88-89
  *   pd_op_layernorm  nn.LayerNorm                                                  attention.py:263-265
@@ -36,6 +37,41 @@ int pd_op_conv2d_upfold(pd_engine* e, const float* x, const float* w, const floa
                         int W, int Cout, float* y);
 int pd_op_linear(pd_engine* e, const float* x, const float* w, const float* bias, int M, int K, int N, int geglu, int a_silu,
                  float* y);
+/* pd_engine::gemm on a linear layer in every form its callers launch; pd_op_linear is this call with everything else at 0 / NULL.
+ * Host fp32 arrays in and out; the call goes through check_gemm / fill_gemm / plan_gemm / gemm() like a network's, so the options
+ * ("gemm_tile", "gemm_splitk", "ring", "ring_tile", ...) decide the kernel and the stats "gemm_family" / "gemm_tile" / "gemm_splitk" say
+ * which one ran.  A combination the kernels refuse or would ignore is an error, not a fall-back.
+ *   x [M][K], w [N][K] (act 2 / 7: [2N][K] packed [x | gate], bias [2N]), bias [N] or NULL; K a multiple of 8
+ *   act       Activation of pd_common.h: 0 none, 1 SiLU, 2 GEGLU, 3 quick-GELU, 4 tanh-GELU, 5 ReLU, 6 erf-GELU, 7 gated tanh-GELU
+ *   a_silu    SiLU on x while it is loaded (x then stays fp32 on the device)
+ *   scale     0: 1
+ *   dtype codes (res_dt, out_dt): 0 fp32, 1 the compute type T, 2 the residual-stream type S
+ *   residual  [M][N] or NULL, held in res_dt with row stride N; added after scale and gate, read at the call's own row m
+ *   rows_per_sample  tokens per sample (0: M, one sample); M = B x tokens
+ *   rowvec, gate     [B][N] or NULL: added before the activation / multiplied in after scale
+ *   vt_begin  0: none; else a multiple of 4: the columns >= vt_begin go transposed to vt [B][N - vt_begin][tokens] instead of y.  The
+ *             device V^T rows are round_up(vt_tok_off + tokens, 8) + vt_extra long and token t lands at vt_tok_off + t.
+ *   c_sample_rows / c_row_off   0 / 0: row m of C; else row m = (b, t) lands at b * c_sample_rows + c_row_off + t of a joint buffer
+ *   a_sample_rows / a_row_off   the same for the rows of A: the hook scatters x into a joint buffer whose other rows hold NaN
+ *   ldc_extra  the output row stride is N + ldc_extra (a multiple of 4)
+ *   ln_gamma, ln_beta  [K] or NULL: LayerNorm(x) folded into the layer as pd_op_ln_linear's mode 1 does (x then lives in S; K <= 2048)
+ * Before the launch every output buffer is filled with NaN: C with the other stream's rows, its pad columns and the columns >= vt_begin,
+ * V^T with the pad tokens and the other stream's.  y [M][N] (its columns >= vt_begin come back as the NaN fill of C) and vt receive the call's
+ * own elements; `touched` the number of elements outside them whose bytes the launch changed. */
+typedef struct pd_gemm_ex_args {
+    const float *x, *w, *bias, *residual, *rowvec, *gate, *ln_gamma, *ln_beta;
+    int32_t M, K, N, act, a_silu, res_dt, out_dt, rows_per_sample;
+    int32_t vt_begin, vt_extra, vt_tok_off, c_sample_rows, c_row_off, a_sample_rows, a_row_off, ldc_extra;
+    float scale;
+    float *y, *vt;
+    int64_t touched;
+} pd_gemm_ex_args;
+int pd_op_linear_ex(pd_engine* e, pd_gemm_ex_args* a);
+/* pd_op_conv2d plus the per-sample row of a ResBlock's time embedding (rowvec [B][Cout] or NULL, added before the activation) and
+ * act 5 (ReLU; act 0 / 1 as act_silu 0 / 1) -- through the dispatch, so igemm, its split-K finalize pass and the patch generations all
+ * take it; the dispatch keeps an activation away from the family that has none (the 4-wave patch conv). */
+int pd_op_conv2d_ex(pd_engine* e, const float* x, const float* w, const float* bias, const float* residual, const float* rowvec, int B, int Cin,
+                    int H, int W, int Cout, int k, int stride, int upsample, int act, float scale, int stream_out, float* y);
 /* the SD3 path's PREC_FP8 linear layer (option sd3_fp8): e4m3 operands quantised on the device with one scale per row of x
  * and of w, block-scaled MFMA, scales applied in the epilogue; act 0 or 4 (tanh-GELU).  2-byte engine modes only. */
 int pd_op_linear_fp8(pd_engine* e, const float* x, const float* w, const float* bias, int M, int K, int N, int act, float* y);

@@ -915,6 +915,17 @@ GemmPlan pd_engine::plan_gemm(const GemmParams& p, const WMat& m, const GemmCall
         }
         pl.big_tile = 0;
     }
+    // options "gemm_tile" / "gemm_splitk" (test surface; -1 by default): the tile and the slice count of an igemm-family launch
+    if (pl.family == GEMM_IGEMM && opt_gemm_tile >= 0) pl.big_tile = opt_gemm_tile;
+    if (pl.family == GEMM_IGEMM && opt_gemm_splitk >= 1) {
+        int want = allow_splitk ? opt_gemm_splitk : 1;
+        if (want > ktiles) want = ktiles;   // no more slices than K steps (what launch_gemm does not split -- GEGLU, a V^T side output -- it refuses)
+        if (want != splitk) {
+            splitk = pl.splitk = want;
+            pl.fused_tile_cnt = splitk > 1 && opt_splitk_fused && tiles <= kTileCnt;
+            pl.defer_finalize = may_defer && splitk > 1 && !pl.fused_tile_cnt;
+        }
+    }
     if (c.ln_out && splitk == 1 && !m.geglu && !c.VT) {   // this launch's own epilogue leaves the row statistics: as many per row as its tile has waves across N
         GemmParams q = p;
         q.big_tile = pl.big_tile;
@@ -952,7 +963,13 @@ int pd_engine::gemm(const WMat& m, const Act& in, Act& out, const GemmCall& c) {
     PD_TRY(check_arena());
     const bool gemv = pl.family == GEMM_GEMV, ring = pl.family == GEMM_RING;
     ++launches;
-    gemm_family = pl.family;
+    gemm_family = pl.family; gemm_splitk = p.splitk;
+    gemm_ring_tile = ring ? pl.ring_tile : -1;
+    gemm_tile = pl.family == GEMM_IGEMM ? gemm_launched_tile(p, in.dt == DT_FP8 ? PREC_FP8 : P) : 0;
+    if (opt_gemm_tile >= 0 && pl.family == GEMM_IGEMM && gemm_tile != opt_gemm_tile) {   // option "gemm_tile": no quiet move to another tile
+        pd_set_error("gemm: option gemm_tile %d, but this launch (mode, operands, epilogue, %d slices) has the tile %d instantiation only", opt_gemm_tile, p.splitk, gemm_tile);
+        return 1;
+    }
     ProfRec rec{};
     if (profiling && gemv) {
         prof_begin(rec, 1, 2.0 * (double)p.M * (double)m.Nout * (double)m.cin);

@@ -499,6 +499,8 @@ struct pd_engine {
     bool opt_graph = false;    // pd_ddim_sample: capture the step loop in a hipGraph and replay it on later calls with the same arguments
     int opt_ring = 80;         // linear layers with at most this many K steps (0: off) take gemm_ring.hip's persistent LDS-DMA ring kernel
     int opt_ring_tile = -1;    // its tile: -1 auto, 0 = 128 x 160, 1 = 256 x 160
+    int opt_gemm_tile = -1;    // test surface: GemmPlan::big_tile of every igemm-family launch (-1: the plan's own)
+    int opt_gemm_splitk = -1;  // ... its K slices: -1 the plan's own, 1 never, n >= 2 that many where launch_gemm takes a split launch
     int opt_ring_pp = 1;       // its ping-pong form where it measures faster (long K, or one 256-row tile per CU)
     int opt_ring_geglu = 1;    // GEGLU projections too (256 x 160 on 8 x 1 waves)
     int opt_ring_small = 4;    // small-M linear layers on 64 x 80 ring tiles instead of split-K (option "ring_small"): 0 off, d: where the 128 x 160 grid fills at most 1 / d of the chip
@@ -527,6 +529,8 @@ struct pd_engine {
     int gn_kernel = 0;             // GN_KIND_* of the last groupnorm() launch (stat "gn_kernel"), set where the launch is decided
     long long ups_fold_launches = 0;   // launches that took conv_upfold.hip (stat "ups_fold_launches")
     int attn_kernel = 0;           // ATTN_KIND_* of the last attention() launch (stat "attn_kernel"), set by the launcher; 0: none yet
+    int gemm_tile = -1, gemm_splitk = -1;   // the tile of the instantiation that launch took (gemm_launched_tile; 0 outside the igemm family) and its slices (stats "gemm_tile", "gemm_splitk")
+    int gemm_ring_tile = -1;                // launch_ring_gemm's tile of that launch, 2 / 3 the ping-pong forms; -1: not a ring launch (stat "gemm_ring_tile")
     int gemm_family = -1;          // GemmFamily of the last gemm() launch (stat "gemm_family"), set where gemm() launches; -1: none yet
     // optional per-launch timing (bench.py roofline leg): HIP events around every contraction launch
     struct ProfRec { hipEvent_t a, b; int klass; double flops; int M, N, K, taps; };

@@ -644,6 +644,22 @@ int launch_gemm(const GemmParams& p, int prec, hipStream_t s, hipEvent_t mid, in
     }
 }
 
+// The tile of the instantiation launch_gemm takes for p (GemmParams::big_tile numbering): launch_prec / launch_fp8 map a request the
+// instantiation set does not hold -- 2 / 3 / 4 in the fp32-storage modes, 256 x 320 with the MM extras or on a conv, any big tile on a split
+// launch with tile counters -- to the 128 x 160 or 256 x 160 one.  Mirrors their branches; stat "gemm_tile" reports it.
+int gemm_launched_tile(const GemmParams& p, int prec) {
+    const int tile = p.splitk == 1 ? p.big_tile : ((p.big_tile == 1 && !p.tile_cnt) ? 1 : 0);
+    const int t01 = (tile == 1 || tile == 3) ? 1 : 0;
+    if (prec == PREC_FP8) return p.splitk > 1 ? 0 : tile == 4 ? 4 : t01;
+    const bool F = prec_f32_storage(prec), conv = p.taps != 1, af32 = !F && p.a_dt == DT_F32;
+    if (p.act == 5 || p.act == 7) return t01;
+    if (p.act == 2) return tile == 3 ? 3 : tile == 1 ? 1 : 0;
+    if (!F && tile == 4) return 4;
+    if (p.act == 4 || p.act == 6 || p.gate || p.c_sample_rows || p.a_sample_rows) return (!F && tile == 2) ? 2 : t01;
+    if (F || conv || af32) return t01;
+    return tile == 3 ? 3 : tile == 2 ? 2 : t01;
+}
+
 int gemm_stats_parts(const GemmParams& p, int prec) {
     int parts = 0;
     return launch_gemm(p, prec, nullptr, nullptr, &parts) ? 0 : parts;

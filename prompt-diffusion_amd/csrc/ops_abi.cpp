@@ -47,7 +47,14 @@ extern "C" {
 // y = conv2d(x, w, b, stride, padding = k/2) [+ SiLU] [* scale] [+ residual]; x NCHW fp32, w OIHW.
 int pd_op_conv2d(pd_engine* e, const float* x, const float* w, const float* bias, const float* residual, int B, int Cin, int H,
                  int W, int Cout, int k, int stride, int upsample, int act_silu, float scale, int stream_out, float* y) {
+    return pd_op_conv2d_ex(e, x, w, bias, residual, nullptr, B, Cin, H, W, Cout, k, stride, upsample, act_silu ? ACT_SILU : ACT_NONE, scale, stream_out, y);
+}
+
+// ... with the per-sample row of a ResBlock's time embedding (rowvec [B][Cout]) and act 0 / 1 / 5 (none / SiLU / ReLU)
+int pd_op_conv2d_ex(pd_engine* e, const float* x, const float* w, const float* bias, const float* residual, const float* rowvec, int B, int Cin,
+                    int H, int W, int Cout, int k, int stride, int upsample, int act, float scale, int stream_out, float* y) {
     if (!e || !x || !w || !y) { pd_set_error("null argument"); return 1; }
+    if (act != ACT_NONE && act != ACT_SILU && act != ACT_RELU) { pd_set_error("pd_op_conv2d_ex: act %d (a conv takes 0 none, 1 SiLU, 5 ReLU)", act); return 1; }
     HIP_OK(hipSetDevice(e->device));
     TempMat guard(e);
     ConvW c;
@@ -68,7 +75,11 @@ int pd_op_conv2d(pd_engine* e, const float* x, const float* w, const float* bias
     o.p = out.p; o.B = B; o.H = Ho; o.W = Wo; o.C = copad; o.dt = odt;
     r = o; r.p = res.p; r.dt = e->S;
     if (residual) PD_TRY(to_dev_nhwc(e, residual, res.p, e->S, B, Cout, Ho, Wo, copad));
-    PD_TRY(e->conv(c, a, o, {.ups = upsample, .act = act_silu ? ACT_SILU : ACT_NONE, .scale = scale, .R = residual ? &r : nullptr}));
+    DevBuf rv((size_t)B * copad * 4);   // (DevBuf zero-fills: the pad columns of the row)
+    if (!rv.p) { pd_set_error("allocation failed"); return 1; }
+    if (rowvec) HIP_OK(hipMemcpy2D(rv.p, (size_t)copad * 4, rowvec, (size_t)Cout * 4, (size_t)Cout * 4, B, hipMemcpyHostToDevice));
+    PD_TRY(e->conv(c, a, o, {.ups = upsample, .act = (Activation)act, .scale = scale, .R = residual ? &r : nullptr,
+                             .rowvec = rowvec ? reinterpret_cast<const float*>(rv.p) : nullptr, .rowvec_stride = rowvec ? copad : 0}));
     return from_dev_nhwc(e, out.p, odt, y, B, Cout, Ho, Wo, copad);
 }
 
@@ -165,33 +176,158 @@ int pd_op_freeu_concat(pd_engine* e, const float* h, const float* h_add, const f
 // y[M,N] = act(x[M,K] @ w[N,K]^T + b) ; geglu: w [2*N, K] -> y[M,N] = (x w_a + b_a) * gelu(x w_g + b_g)
 int pd_op_linear(pd_engine* e, const float* x, const float* w, const float* bias, int M, int K, int N, int geglu, int a_silu,
                  float* y) {
-    if (!e || !x || !w || !y) { pd_set_error("null argument"); return 1; }
+    pd_gemm_ex_args a{};
+    a.x = x; a.w = w; a.bias = bias; a.M = M; a.K = K; a.N = N; a.act = geglu ? ACT_GEGLU : ACT_NONE; a.a_silu = a_silu; a.y = y;
+    return pd_op_linear_ex(e, &a);
+}
+
+namespace {
+int ex_dt(const pd_engine* e, int code) { return code == 1 ? e->T : code == 2 ? e->S : DT_F32; }
+// host fp32 -> a device buffer of n elements in dt, and back
+int put_flat(pd_engine* e, const std::vector<float>& host, void* dst, int dt) {
+    DevBuf tmp(host.size() * 4);
+    if (!tmp.p) { pd_set_error("allocation failed"); return 1; }
+    HIP_OK(hipMemcpy(tmp.p, host.data(), host.size() * 4, hipMemcpyHostToDevice));
+    if (launch_cast_rows(reinterpret_cast<const float*>(tmp.p), dst, dt, 1, (int)host.size(), (int)host.size(), e->stream)) { pd_set_error("cast launch failed"); return 1; }
+    HIP_OK(hipStreamSynchronize(e->stream));
+    return 0;
+}
+int get_flat(pd_engine* e, const void* src, int dt, std::vector<float>& host) {
+    DevBuf tmp(host.size() * 4);
+    if (!tmp.p) { pd_set_error("allocation failed"); return 1; }
+    if (launch_nhwc_to_nchw(src, dt, reinterpret_cast<float*>(tmp.p), 1, 1, 1, (int)host.size(), 1, 1.f, e->stream)) { pd_set_error("cast launch failed"); return 1; }
+    HIP_OK(hipStreamSynchronize(e->stream));
+    HIP_OK(hipMemcpy(host.data(), tmp.p, host.size() * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+}  // namespace
+
+// pd_engine::gemm on a linear layer with everything its callers pass (see pdengine_ops.h): activation, scale, residual in any of its types,
+// 2-byte output, per-sample row / gate, the V^T side output, joint-buffer row remaps of C and A, an output row stride, and a NaN fill of
+// every output element the launch must leave alone
+int pd_op_linear_ex(pd_engine* e, pd_gemm_ex_args* g) {
+    if (!e || !g || !g->x || !g->w || !g->y) { pd_set_error("null argument"); return 1; }
+    const int M = g->M, K = g->K, N = g->N, act = g->act;
+    if (M < 1 || K < 1 || N < 1) { pd_set_error("pd_op_linear_ex: need M, K, N >= 1"); return 1; }
+    if (K % 8) { pd_set_error("K must be a multiple of 8"); return 1; }
+    if (act < 0 || act > ACT_GATED_TANH_GELU) { pd_set_error("pd_op_linear_ex: act %d out of range", act); return 1; }
+    const bool packed = act == ACT_GEGLU || act == ACT_GATED_TANH_GELU;
+    const int tokens = g->rows_per_sample > 0 ? g->rows_per_sample : M;
+    if (M % tokens) { pd_set_error("pd_op_linear_ex: M %d is no multiple of rows_per_sample %d", M, tokens); return 1; }
+    const int B = M / tokens;
+    const float scale = g->scale == 0.f ? 1.f : g->scale;
+    const bool remap = g->c_sample_rows || g->a_sample_rows;
+    const bool side = g->residual || g->rowvec || g->gate || g->vt_begin || remap || g->ldc_extra || g->out_dt;
+    if (N % 4 && side) { pd_set_error("pd_op_linear_ex: N %d must be a multiple of 4 with anything beyond bias / activation", N); return 1; }
+    if ((unsigned)g->res_dt > 2u || (unsigned)g->out_dt > 2u) { pd_set_error("pd_op_linear_ex: dtype codes are 0 fp32, 1 compute type, 2 stream type"); return 1; }
+    if (g->vt_begin) {
+        if (g->vt_begin < 0 || g->vt_begin % 4 || g->vt_begin >= N) { pd_set_error("pd_op_linear_ex: vt_begin %d must be a multiple of 4 in (0, N)", g->vt_begin); return 1; }
+        if (!g->vt || g->vt_extra < 0 || g->vt_extra % 8 || g->vt_tok_off < 0) { pd_set_error("pd_op_linear_ex: V^T needs an output array, vt_extra a multiple of 8, vt_tok_off >= 0"); return 1; }
+    } else if (g->vt_extra || g->vt_tok_off) { pd_set_error("pd_op_linear_ex: vt_extra / vt_tok_off without vt_begin"); return 1; }
+    if (g->ldc_extra < 0 || g->ldc_extra % 4) { pd_set_error("pd_op_linear_ex: ldc_extra %d must be a non-negative multiple of 4", g->ldc_extra); return 1; }
+    if (g->c_sample_rows ? (g->c_row_off < 0 || g->c_row_off + tokens > g->c_sample_rows) : g->c_row_off != 0) { pd_set_error("pd_op_linear_ex: c_row_off + tokens must fit c_sample_rows"); return 1; }
+    if (g->a_sample_rows ? (g->a_row_off < 0 || g->a_row_off + tokens > g->a_sample_rows) : g->a_row_off != 0) { pd_set_error("pd_op_linear_ex: a_row_off + tokens must fit a_sample_rows"); return 1; }
+    // what an instantiation would leave out without saying so (pd_mma.h: the extras are compile-time; gemm.hip: the GEGLU tiles add the bias only)
+    const bool mm = g->gate || remap || act == ACT_TANH_GELU || act == ACT_ERF_GELU;
+    if (packed && (g->residual || g->rowvec || g->gate || g->vt_begin || remap || scale != 1.f || g->a_silu || g->ln_gamma)) {
+        pd_set_error("pd_op_linear_ex: a GEGLU / gated tanh-GELU layer takes a bias and nothing else");
+        return 1;
+    }
+    if (act == ACT_RELU && mm) { pd_set_error("pd_op_linear_ex: the ReLU instantiations carry no gate / row remap"); return 1; }
+    if (g->vt_tok_off && !mm) { pd_set_error("pd_op_linear_ex: vt_tok_off exists in the instantiations with the gate / row remaps only"); return 1; }
+    if (g->ln_gamma && (!g->ln_beta || K > 2048 || g->a_silu)) { pd_set_error("pd_op_linear_ex: the LayerNorm fold needs gamma and beta, K <= 2048, no a_silu"); return 1; }
     HIP_OK(hipSetDevice(e->device));
     TempMat guard(e);
     WMat m;
-    const int rows = geglu ? 2 * N : N;
-    e->make_mat(m, rows, K, 1, K, true, geglu != 0);
+    const int wrows = packed ? 2 * N : N;
+    e->make_mat(m, wrows, K, 1, K, true, packed);
     if (!m.w) { pd_set_error("allocation failed"); return 1; }
-    if (K % 8) { pd_set_error("K must be a multiple of 8"); return 1; }
-    PD_TRY(e->upload_rows(m, 0, w, rows, false));
-    if (bias) PD_TRY(e->upload_vec(m.bias, bias, rows, geglu != 0, N));
-    const int adt = a_silu ? DT_F32 : e->T;
-    DevBuf in((size_t)M * K * 4), out((size_t)M * round_up(N, 4) * 4);
-    if (!in.p || !out.p) { pd_set_error("allocation failed"); return 1; }
+    PD_TRY(e->upload_rows(m, 0, g->w, wrows, false));
+    if (g->bias) PD_TRY(e->upload_vec(m.bias, g->bias, wrows, packed, N));
+    const int adt = g->a_silu ? DT_F32 : g->ln_gamma ? e->S : e->T, odt = ex_dt(e, g->out_dt), rdt = ex_dt(e, g->res_dt);
+    const int Np = round_up(N, 4), ldc = Np + g->ldc_extra, ncol = g->vt_begin ? g->vt_begin : Np;   // ncol: the columns of C this call owns
+    const int arows = g->a_sample_rows ? B * g->a_sample_rows : M, crows = g->c_sample_rows ? B * g->c_sample_rows : M;
+    const int nvt = g->vt_begin ? N - g->vt_begin : 0, vt_ld = round_up(g->vt_tok_off + tokens, 8) + g->vt_extra;
+    const float nan = std::nanf("");
+    auto arow = [&](int i) { return g->a_sample_rows ? (i / tokens) * g->a_sample_rows + g->a_row_off + i % tokens : i; };
+    auto crow = [&](int i) { return g->c_sample_rows ? (i / tokens) * g->c_sample_rows + g->c_row_off + i % tokens : i; };
+    const size_t ob = dt_size(odt), nc = (size_t)crows * ldc, nv = (size_t)B * nvt * vt_ld;
+    DevBuf in((size_t)arows * K * dt_size(adt)), out(nc * ob), vt(nv * ob), res((size_t)M * Np * dt_size(rdt)), rv((size_t)B * Np * 4), gt((size_t)B * Np * 4);
+    if (!in.p || !out.p || !vt.p || !res.p || !rv.p || !gt.p) { pd_set_error("allocation failed"); return 1; }
     {
-        DevBuf tmp((size_t)M * K * 4);
-        HIP_OK(hipMemcpy(tmp.p, x, (size_t)M * K * 4, hipMemcpyHostToDevice));
-        if (launch_cast_rows(reinterpret_cast<const float*>(tmp.p), in.p, adt, M, K, K, e->stream)) return 1;
-        HIP_OK(hipStreamSynchronize(e->stream));
+        std::vector<float> h((size_t)arows * K, g->a_sample_rows ? nan : 0.f);
+        for (int i = 0; i < M; ++i) memcpy(&h[(size_t)arow(i) * K], g->x + (size_t)i * K, (size_t)K * 4);
+        PD_TRY(put_flat(e, h, in.p, adt));
     }
-    Act a, o;
-    a.p = in.p; a.B = M; a.H = 1; a.W = 1; a.C = K; a.dt = adt;
-    o.p = out.p; o.B = M; o.H = 1; o.W = 1; o.C = round_up(N, 4); o.dt = DT_F32;
-    PD_TRY(e->gemm(m, a, o, {.a_silu = a_silu != 0}));
+    auto pad_cols = [&](const float* src, int rows, void* dst, int dt) -> int {   // [rows][N] -> [rows][Np]
+        std::vector<float> h((size_t)rows * Np, 0.f);
+        for (int i = 0; i < rows; ++i) memcpy(&h[(size_t)i * Np], src + (size_t)i * N, (size_t)N * 4);
+        return put_flat(e, h, dst, dt);
+    };
+    if (g->residual) PD_TRY(pad_cols(g->residual, M, res.p, rdt));
+    if (g->rowvec) PD_TRY(pad_cols(g->rowvec, B, rv.p, DT_F32));
+    if (g->gate) PD_TRY(pad_cols(g->gate, B, gt.p, DT_F32));
+    PD_TRY(put_flat(e, std::vector<float>(nc, nan), out.p, odt));
+    if (nv) PD_TRY(put_flat(e, std::vector<float>(nv, nan), vt.p, odt));
+    std::vector<unsigned char> c0(nc * ob), c1(nc * ob), v0(nv * ob), v1(nv * ob);   // the output buffers as the launch finds and leaves them
+    HIP_OK(hipMemcpy(c0.data(), out.p, nc * ob, hipMemcpyDeviceToHost));
+    if (nv) HIP_OK(hipMemcpy(v0.data(), vt.p, nv * ob, hipMemcpyDeviceToHost));
+    Act a, o, r;
+    a.p = in.p; a.B = B; a.H = tokens; a.W = 1; a.C = K; a.dt = adt;
+    o.p = out.p; o.B = B; o.H = tokens; o.W = 1; o.C = Np; o.dt = odt;
+    r = o; r.p = res.p; r.dt = rdt;
+    GemmCall call;
+    call.act = act == ACT_GEGLU ? ACT_NONE : (Activation)act;   // (a GEGLU weight matrix implies ACT_GEGLU)
+    call.scale = scale;
+    call.a_silu = g->a_silu != 0;
+    if (g->residual) call.R = &r;
+    if (g->rowvec) { call.rowvec = reinterpret_cast<const float*>(rv.p); call.rowvec_stride = Np; }
+    if (g->gate) { call.gate = reinterpret_cast<const float*>(gt.p); call.gate_stride = Np; }
+    if (nvt) { call.VT = vt.p; call.vt_begin = g->vt_begin; call.vt_ld = vt_ld; call.vt_tok_off = g->vt_tok_off; }
+    if (g->ldc_extra) call.ldc = ldc;
+    call.c_sample_rows = g->c_sample_rows; call.c_row_off = g->c_row_off;
+    call.a_sample_rows = g->a_sample_rows; call.a_row_off = g->a_row_off;
+    LnStats st;
+    DevBuf stats((size_t)arows * 2 * 4), lg((size_t)K * 4 + 16), lb((size_t)K * 4 + 16);
+    if (g->ln_gamma) {   // LayerNorm of x folded into the layer, statistics from row_stats_kernel (pd_op_ln_linear mode 1)
+        if (!stats.p || !lg.p || !lb.p) { pd_set_error("allocation failed"); return 1; }
+        HIP_OK(hipMemcpy(lg.p, g->ln_gamma, (size_t)K * 4, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(lb.p, g->ln_beta, (size_t)K * 4, hipMemcpyHostToDevice));
+        m.w_ln = e->dmalloc((size_t)m.N * m.Kpad * dt_size(e->T));
+        m.colsum = reinterpret_cast<float*>(e->dmalloc((size_t)(m.N + 4) * sizeof(float)));
+        m.bias_ln = reinterpret_cast<float*>(e->dmalloc((size_t)(m.N + 4) * sizeof(float)));
+        if (!m.w_ln || !m.colsum || !m.bias_ln) { pd_set_error("allocation failed"); return 1; }
+        if (launch_ln_fold(m.w, m.w_ln, e->T, m.N, m.K, m.Kpad, reinterpret_cast<float*>(lg.p), reinterpret_cast<float*>(lb.p), m.bias, m.colsum, m.bias_ln, e->stream) ||
+            launch_row_stats(in.p, adt, reinterpret_cast<float*>(stats.p), arows, K, e->stream)) {
+            pd_set_error("LayerNorm fold launch failed");
+            return 1;
+        }
+        st.stats = reinterpret_cast<float*>(stats.p); st.parts = 1; st.C = K;
+        call.ln_in = &st;
+    }
+    PD_TRY(e->gemm(m, a, o, call));
     HIP_OK(hipStreamSynchronize(e->stream));
-    std::vector<float> host((size_t)M * o.C);
-    HIP_OK(hipMemcpy(host.data(), out.p, host.size() * 4, hipMemcpyDeviceToHost));
-    for (int i = 0; i < M; ++i) memcpy(y + (size_t)i * N, host.data() + (size_t)i * o.C, (size_t)N * 4);
+    HIP_OK(hipMemcpy(c1.data(), out.p, nc * ob, hipMemcpyDeviceToHost));
+    if (nv) HIP_OK(hipMemcpy(v1.data(), vt.p, nv * ob, hipMemcpyDeviceToHost));
+    std::vector<float> hc(nc), hv(nv);
+    PD_TRY(get_flat(e, out.p, odt, hc));
+    if (nv) PD_TRY(get_flat(e, vt.p, odt, hv));
+    for (int i = 0; i < M; ++i) memcpy(g->y + (size_t)i * N, &hc[(size_t)crow(i) * ldc], (size_t)N * 4);
+    for (int b = 0; b < B; ++b)
+        for (int c = 0; c < nvt; ++c)
+            memcpy(g->vt + ((size_t)b * nvt + c) * tokens, &hv[((size_t)b * nvt + c) * vt_ld + g->vt_tok_off], (size_t)tokens * 4);
+    // elements outside the call's own rows / columns / tokens whose bytes changed
+    std::vector<char> own((size_t)crows, 0);
+    for (int i = 0; i < M; ++i) own[crow(i)] = 1;
+    int64_t changed = 0;
+    for (int rr = 0; rr < crows; ++rr)
+        for (int c = 0; c < ldc; ++c)
+            if (!(own[rr] && c < ncol) && memcmp(&c0[((size_t)rr * ldc + c) * ob], &c1[((size_t)rr * ldc + c) * ob], ob)) ++changed;
+    for (size_t i = 0; i < nv; ++i) {
+        const int t = (int)(i % vt_ld);
+        if (!(t >= g->vt_tok_off && t < g->vt_tok_off + tokens) && memcmp(&v0[i * ob], &v1[i * ob], ob)) ++changed;
+    }
+    g->touched = changed;
     return 0;
 }
 

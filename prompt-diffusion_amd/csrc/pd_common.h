@@ -257,6 +257,7 @@ int launch_gemm(const GemmParams& p, int prec, hipStream_t s, hipEvent_t mid = n
 // LayerNorm-statistics partials per row (GemmParams::stats_parts) that launch_gemm / launch_ring_gemm write for this launch:
 // column tiles x waves across N of the tile their dispatch takes (parts != null runs that dispatch without launching); 0: none
 int gemm_stats_parts(const GemmParams& p, int prec);
+int gemm_launched_tile(const GemmParams& p, int prec);   // the tile (GemmParams::big_tile numbering) of the instantiation launch_gemm takes for p
 int ring_gemm_stats_parts(const GemmParams& p, int prec, int tile);
 // gemm_ring.hip: persistent LDS-DMA ring GEMM for plain linear layers over 2-byte operands (tile 0: 128 x 160, 1: 256 x 160)
 bool ring_gemm_eligible(const GemmParams& p, int prec);

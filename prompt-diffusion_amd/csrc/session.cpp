@@ -1056,6 +1056,14 @@ int pd_set_option(pd_engine* e, const char* key, int64_t value) {
     if (!strcmp(key, "ring_small")) { e->opt_ring_small = (int)value; return 0; }
     if (!strcmp(key, "short_k")) { e->opt_short_k = (int)value; return 0; }
     if (!strcmp(key, "patch_split")) { e->opt_patch_split = value != 0; return 0; }
+    if (!strcmp(key, "gemm_tile")) {
+        if (value < -1 || value > 4) { pd_set_error("option gemm_tile: -1 (the plan's own) or a tile 0 .. 4"); return 1; }
+        e->opt_gemm_tile = (int)value; return 0;
+    }
+    if (!strcmp(key, "gemm_splitk")) {
+        if (value < -1 || value == 0 || value > 64) { pd_set_error("option gemm_splitk: -1 (the plan's own), 1 (never) or 2 .. 64 slices"); return 1; }
+        e->opt_gemm_splitk = (int)value; return 0;
+    }
     if (!strcmp(key, "ring_pp")) { e->opt_ring_pp = (int)value; return 0; }
     if (!strcmp(key, "patch4")) { e->opt_patch4 = value != 0; return 0; }
     if (!strcmp(key, "patch_split_fill")) { e->opt_patch_split_fill = (int)value; return 0; }
@@ -1195,6 +1203,9 @@ int64_t pd_get_stat(pd_engine* e, const char* key) {
                       GEMM_RING == PD_GEMM_RING && GEMM_IGEMM == PD_GEMM_IGEMM && GEMM_UPFOLD == PD_GEMM_UPFOLD, "pdengine.h");
         return (int64_t)e->gemm_family;
     }
+    if (!strcmp(key, "gemm_tile")) return (int64_t)e->gemm_tile;       // the tile of the instantiation that launch took
+    if (!strcmp(key, "gemm_ring_tile")) return (int64_t)e->gemm_ring_tile;   // the ring kernel's tile (2 / 3: ping-pong), -1: not a ring launch
+    if (!strcmp(key, "gemm_splitk")) return (int64_t)e->gemm_splitk;   // ... and its K / channel-chunk slices
     if (!strcmp(key, "steps")) return (int64_t)e->ses.S;
     if (!strcmp(key, "cfg_shared")) return (int64_t)((e->ses.share_u ? 1 : 0) | (e->ses.share_c ? 2 : 0) | (e->ses.cn_cond_only ? 4 : 0));
     if (!strcmp(key, "lora_base_bytes")) return (int64_t)e->lora_bytes(true);   // base copies W0 of the adapted parameters

@@ -160,6 +160,14 @@ def _torch_runtime_first():
         pass
 
 
+class pd_gemm_ex_args(C.Structure):
+    """include/pdengine_ops.h"""
+    _fields_ = [(n, C.c_void_p) for n in ("x", "w", "bias", "residual", "rowvec", "gate", "ln_gamma", "ln_beta")] + \
+               [(n, C.c_int32) for n in ("M", "K", "N", "act", "a_silu", "res_dt", "out_dt", "rows_per_sample", "vt_begin", "vt_extra", "vt_tok_off",
+                                         "c_sample_rows", "c_row_off", "a_sample_rows", "a_row_off", "ldc_extra")] + \
+               [("scale", C.c_float), ("y", C.c_void_p), ("vt", C.c_void_p), ("touched", C.c_int64)]
+
+
 def load_library(path: Optional[str] = None) -> C.CDLL:
     """dlopen libpdengine.so and declare the prototypes of include/pdengine.h."""
     global _lib
@@ -240,6 +248,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     if hasattr(lib, "pd_op_conv2d_upfold"):   # (an older build handed in through PDENGINE_LIB for an A/B run lacks it)
         lib.pd_op_conv2d_upfold.argtypes = [C.c_void_p, fp, fp, fp, fp] + [C.c_int] * 5 + [fp]
     lib.pd_op_linear.argtypes = [C.c_void_p, fp, fp, fp] + [C.c_int] * 5 + [fp]
+    if hasattr(lib, "pd_op_linear_ex"):
+        lib.pd_op_linear_ex.argtypes = [C.c_void_p, C.POINTER(pd_gemm_ex_args)]
+        lib.pd_op_conv2d_ex.argtypes = [C.c_void_p, fp, fp, fp, fp, fp] + [C.c_int] * 9 + [C.c_float, C.c_int, fp]
     lib.pd_op_linear_fp8.argtypes = [C.c_void_p, fp, fp, fp] + [C.c_int] * 4 + [fp]
     lib.pd_op_groupnorm.argtypes = [C.c_void_p, fp, fp, fp] + [C.c_int] * 4 + [C.c_float, C.c_int, fp]
     lib.pd_op_layernorm.argtypes = [C.c_void_p, fp, fp, fp, C.c_int, C.c_int, fp]
@@ -301,7 +312,7 @@ EXPORTS = [
     "pd_profile_read", "pd_profile_dump", "pd_comm_new_id", "pd_comm_init", "pd_comm_world", "pd_comm_all_gather", "pd_comm_destroy",
     "pd_sd3_configure", "pd_sd3_weights_missing", "pd_sd3_forward", "pd_sd3_control", "pd_sd3_sample", "pd_sd3_sample_ex", "pd_sd3_down_proj",
     "pd_op_sd3_update",
-    "pd_op_conv2d", "pd_op_conv2d_upfold", "pd_op_linear", "pd_op_linear_fp8", "pd_op_groupnorm", "pd_op_layernorm", "pd_op_groupnorm_slabs", "pd_op_groupnorm_coef", "pd_op_ln_linear", "pd_op_attention", "pd_op_attention_ex", "pd_op_spatial_transformer", "pd_op_spatial_transformer_ctx", "pd_op_time_embed",
+    "pd_op_conv2d", "pd_op_conv2d_ex", "pd_op_conv2d_upfold", "pd_op_linear", "pd_op_linear_ex", "pd_op_linear_fp8", "pd_op_groupnorm", "pd_op_layernorm", "pd_op_groupnorm_slabs", "pd_op_groupnorm_coef", "pd_op_ln_linear", "pd_op_attention", "pd_op_attention_ex", "pd_op_spatial_transformer", "pd_op_spatial_transformer_ctx", "pd_op_time_embed",
     "pd_op_timestep_embedding_i", "pd_op_timestep_embedding_f", "pd_op_vae_downsample", "pd_read_weights", "pd_lora_add", "pd_lora_set_scales", "pd_lora_remove",
     "pd_set_freeu", "pd_get_freeu", "pd_op_freeu_concat",
     "pd_philox4x32_10", "pd_set_rng", "pd_get_rng", "pd_randn",
@@ -1489,6 +1500,60 @@ class Engine:
         bb = None if b is None else np.ascontiguousarray(b, np.float32)
         self._check(self.lib.pd_op_linear(self._h, x.ctypes.data, w.ctypes.data, None if bb is None else bb.ctypes.data,
                                           M, K, N, int(geglu), int(a_silu), y.ctypes.data))
+        return y
+
+    DTYPE_CODES = {"f32": 0, "T": 1, "S": 2}     # pd_gemm_ex_args.res_dt / out_dt: fp32, the compute type, the residual-stream type
+
+    def op_linear_ex(self, x, w, b=None, act: int = 0, a_silu: bool = False, scale: float = 1.0, residual=None, res_dt: str = "f32",
+                     out_dt: str = "f32", rows_per_sample: int = 0, rowvec=None, gate=None, vt_begin: int = 0, vt_extra: int = 0,
+                     vt_tok_off: int = 0, c_sample_rows: int = 0, c_row_off: int = 0, a_sample_rows: int = 0, a_row_off: int = 0,
+                     ldc_extra: int = 0, ln=None):
+        """pd_engine::gemm on a linear layer in the forms its callers launch (pd_op_linear_ex): x [M, K], w [N, K] (act 2 / 7: [2N, K]
+        packed [x | gate]) -> (y [M, N or vt_begin], vt [B, N - vt_begin, tokens] or None, touched).  act: Activation of pd_common.h;
+        residual [M, N] held in res_dt; out_dt the type of C and V^T ("f32", "T" compute type, "S" stream type); rows_per_sample: tokens
+        per sample (M = B x tokens); rowvec, gate [B, N]; the columns >= vt_begin go transposed to vt, behind vt_tok_off tokens and with
+        vt_extra more pad tokens per row; c_ / a_sample_rows, _row_off: the rows of C / A sit at b * sample_rows + row_off + t of a joint
+        buffer; ldc_extra: more output row stride; ln = (gamma, beta): LayerNorm(x) folded into the layer.  Every output buffer is
+        filled with NaN first; touched counts the elements outside the call's own that the launch changed.  Stats "gemm_family",
+        "gemm_tile", "gemm_splitk" say which kernel ran."""
+        f = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+        x, w, b, residual, rowvec, gate = (f(a) for a in (x, w, b, residual, rowvec, gate))
+        lg, lb = (f(ln[0]), f(ln[1])) if ln is not None else (None, None)
+        M, K = x.shape
+        packed = act in (2, 7)
+        N = w.shape[0] // 2 if packed else w.shape[0]
+        tokens = rows_per_sample or M
+        B = M // tokens
+        if w.shape != ((2 * N if packed else N), K) or (b is not None and b.shape != (w.shape[0],)) or (residual is not None and residual.shape != (M, N)) \
+                or any(a is not None and a.shape != (B, N) for a in (rowvec, gate)) or (ln is not None and (lg.shape != (K,) or lb.shape != (K,))):
+            raise ValueError("x [M, K], w [N, K], b [N], residual [M, N], rowvec / gate [B, N], ln ([K], [K])")
+        y = np.empty((M, N), np.float32)
+        vt = np.empty((B, N - vt_begin, tokens), np.float32) if vt_begin else None
+        p = lambda a: None if a is None else a.ctypes.data
+        a = pd_gemm_ex_args(x=p(x), w=p(w), bias=p(b), residual=p(residual), rowvec=p(rowvec), gate=p(gate), ln_gamma=p(lg), ln_beta=p(lb),
+                            M=M, K=K, N=N, act=int(act), a_silu=int(bool(a_silu)), res_dt=self.DTYPE_CODES[res_dt], out_dt=self.DTYPE_CODES[out_dt],
+                            rows_per_sample=int(rows_per_sample), vt_begin=int(vt_begin), vt_extra=int(vt_extra), vt_tok_off=int(vt_tok_off),
+                            c_sample_rows=int(c_sample_rows), c_row_off=int(c_row_off), a_sample_rows=int(a_sample_rows), a_row_off=int(a_row_off),
+                            ldc_extra=int(ldc_extra), scale=float(scale), y=p(y), vt=p(vt), touched=0)
+        self._check(self.lib.pd_op_linear_ex(self._h, C.byref(a)))
+        return (y[:, :vt_begin] if vt_begin else y), vt, int(a.touched)
+
+    def op_conv2d_ex(self, x, w, b=None, residual=None, rowvec=None, stride=1, upsample=False, act: int = 0, scale=1.0, stream_out=False):
+        """op_conv2d plus rowvec [B, Cout] (the per-sample time-embedding row, added before the activation) and act 0 / 1 / 5 (none /
+        SiLU / ReLU) (pd_op_conv2d_ex)."""
+        x = np.ascontiguousarray(x, np.float32); w = np.ascontiguousarray(w, np.float32)
+        B, Cin, H, W = x.shape
+        Cout, _, k, _ = w.shape
+        Hv, Wv = (H * 2, W * 2) if upsample else (H, W)
+        Ho, Wo = ((Hv + 1) // 2, (Wv + 1) // 2) if stride == 2 else (Hv, Wv)
+        y = np.empty((B, Cout, Ho, Wo), np.float32)
+        f = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+        bb, rr, rv = f(b), f(residual), f(rowvec)
+        if rv is not None and rv.shape != (B, Cout):
+            raise ValueError("rowvec [B, Cout]")
+        p = lambda a: None if a is None else a.ctypes.data
+        self._check(self.lib.pd_op_conv2d_ex(self._h, x.ctypes.data, w.ctypes.data, p(bb), p(rr), p(rv), B, Cin, H, W, Cout, k, stride,
+                                             int(upsample), int(act), scale, int(stream_out), y.ctypes.data))
         return y
 
     def op_linear_fp8(self, x, w, b=None, gelu_tanh=False):
