@@ -176,6 +176,26 @@ int pd_lora_add(pd_engine* e, int32_t adapter, const char* name, const float* up
                 const int64_t* down_shape, int32_t down_ndim);
 int pd_lora_set_scales(pd_engine* e, const float* scales, int32_t n);
 int pd_lora_remove(pd_engine* e, int32_t adapter);
+/* Adapters that are not a plain factor pair (DESIGN.md §7 "LoRA adapters" has the formulas).  An adapter contributes
+ *   E = s * D                                      without a magnitude,
+ *   E = (m / n) (.) (W0 + s * D) - W0, row-wise,   with one (DoRA); n[o] = || (W0 + s * D)[o, :] ||_2 in fp32, factor 0 where n = 0,
+ * with s its pd_lora_set_scales scale and D by kind (N rows, K = cin * kh * kw columns in checkpoint order [.., cin, kh, kw]):
+ *   PD_LORA_PAIR  D = scale * up . down                      up [N, rank], down [rank, K]
+ *   PD_LORA_HADA  D = scale * (up . down) (.) (up2 . down2)  up2 [N, rank2], down2 [rank2, K]
+ *   PD_LORA_KRON  D[i * c + p, j * d + q, y, x] = scale * w1[i, j] * w2[p, q, y, x]
+ *                 up = w1 [kron_a, kron_b], down = w2 [c, d, kh, kw] with kron_a * c = N and kron_b * d = cin.
+ * W = round_T(W0 + (plain pd_lora_add columns) + E_1 + E_2 + ...), the E in load order, summed in fp32 and rounded once.
+ * A PD_LORA_PAIR without a magnitude is what pd_lora_add registers (scale is multiplied into up first, in fp32).  HOST fp32. */
+enum { PD_LORA_PAIR = 0, PD_LORA_HADA = 1, PD_LORA_KRON = 2 };
+typedef struct pd_lora_factors {
+    int32_t kind;             /* PD_LORA_* */
+    int32_t rank, rank2;      /* PAIR / HADA: inner dimension of up . down (and of up2 . down2) */
+    int32_t kron_a, kron_b;   /* KRON: shape of w1 */
+    float scale;              /* alpha / r (1 where the format has none) */
+    const float *up, *down, *up2, *down2;
+    const float* magnitude;   /* [N], or NULL */
+} pd_lora_factors;
+int pd_lora_add_ex(pd_engine* e, int32_t adapter, const char* name, const pd_lora_factors* f);
 
 /* FreeU (diffusers UNet2DConditionModel.enable_freeu / disable_freeu): engine state that every later UNet evaluation applies
  * (pd_eps, pd_ddim_sample, pd_unipc_sample, the per-step export, captured graphs).  In the decoder blocks of the lowest

@@ -695,6 +695,15 @@ struct pd_engine {
     // adapter touches: its base rows W0 in T (all m.N rows of a GEGLU matrix), and every adapter's up^T / down stacked in load
     // order as the merge kernel's UT [R][rows] / D [R][Kpad] operands.
     struct LoraEntry { int adapter = 0, r = 0; };
+    // One adapter that is not a stack of rank-1 columns.  PAIR (under a magnitude) / HADA: ut1 [r1][rows], d1 [r1][Kpad] (and
+    // ut2 / d2 [r2]...) laid out like ut / d; KRON: ut1 = w1 [ka][kb], d1 = w2 [rows / ka][taps][cin / kb].  mag [rows] or null.
+    // All of it lives in the one device allocation `buf`; the format's alpha / r is already multiplied into ut1.
+    struct LoraForm {
+        int adapter = 0, kind = 0, r1 = 0, r2 = 0, ka = 0, kb = 0;
+        float* buf = nullptr;
+        size_t bytes = 0;
+        float *ut1 = nullptr, *d1 = nullptr, *ut2 = nullptr, *d2 = nullptr, *mag = nullptr;
+    };
     struct LoraTarget {
         void* w0 = nullptr;
         size_t w0_bytes = 0;
@@ -703,7 +712,14 @@ struct pd_engine {
         int R = 0;
         std::vector<LoraEntry> entries;   // column blocks of ut / d, in load order
         std::vector<float> merged;        // multiplier of each entry that W holds now; empty: W holds W0
+        std::vector<LoraForm> forms;      // pd_lora_add_ex adapters (Hadamard, Kronecker, magnitude), in load order
+        std::vector<float> fmerged;       // multiplier of each form that W holds now; cleared together with `merged`
     };
+    float* lora_tmp = nullptr;                 // fp32 scratch of a merge with forms: one adapter's delta, and the running sum
+    float* lora_sum = nullptr;
+    size_t lora_tmp_cap = 0;                   // floats in each
+    int lora_add_ex(int adapter, const char* name, const pd_lora_factors& f);
+    int lora_target_base(int pi);              // the first adapter on a parameter saves its rows as W0
     std::map<int, LoraTarget> lora;            // by parameter index (ordered: merges launch in registry order)
     std::map<int, float> lora_scale;           // adapter id -> multiplier (0: inactive)
     float* lora_scale_dev = nullptr;

@@ -4,10 +4,13 @@
 // W0 (in the storage type T, in the WMat's own row layout), and each adapter's factors are kept on the device as up^T
 // [r][rows] and down [r][Kpad] (laid out like upload_rows lays out a row: k = tap * cin_pad + c, zero pad columns).  A merge
 // rebuilds W from W0 with lora_merge_kernel (lora.hip), so the weights never depend on the order of earlier scale changes;
-// it then marks the derived copies stale (folded LayerNorm weights, fused st_tail packs, SD3 e4m3 copies), drops captured
+// adapters that are not a stack of rank-1 columns (pd_lora_add_ex: Hadamard and Kronecker products, a DoRA magnitude) are
+// kept as LoraForm records and merged after the plain columns, in load order, by the form kernels of lora.hip.  A merge
+// then marks the derived copies stale (folded LayerNorm weights, fused st_tail packs, SD3 e4m3 copies), drops captured
 // graphs, refolds the LayerNorms and synchronises.  The sampling path itself is unchanged.
 #include "engine.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 
@@ -61,6 +64,9 @@ int pd_engine::lora_add(int adapter, const char* name, const float* up, int up_r
     if (tit != lora.end())
         for (const LoraEntry& en : tit->second.entries)
             if (en.adapter == adapter) { pd_set_error("pd_lora_add: '%s' already has adapter %d", name, adapter); return 3; }
+    if (tit != lora.end())
+        for (const LoraForm& fo : tit->second.forms)
+            if (fo.adapter == adapter) { pd_set_error("pd_lora_add: '%s' already has adapter %d", name, adapter); return 3; }
     HIP_OK(hipSetDevice(device));
     // host layout of the new columns
     std::vector<float> ut((size_t)rank * rows), d((size_t)rank * m.Kpad, 0.f);
@@ -69,14 +75,8 @@ int pd_engine::lora_add(int adapter, const char* name, const float* up, int up_r
     for (int j = 0; j < rank; ++j)
         for (int c = 0; c < cin; ++c)
             for (int tp = 0; tp < kk; ++tp) d[(size_t)j * m.Kpad + (size_t)tp * m.cin_pad + c] = down[((size_t)j * cin + c) * kk + tp];
+    PD_TRY(lora_target_base(pi));
     LoraTarget& t = lora[pi];
-    const size_t rowb = (size_t)m.Kpad * dt_size(T);
-    if (!t.w0) {   // first adapter on this parameter: W holds the base weights now
-        t.w0_bytes = (size_t)base_rows(p) * rowb;
-        if (dev_alloc(&t.w0, t.w0_bytes)) { lora.erase(pi); return 1; }
-        HIP_OK(hipMemcpyAsync(t.w0, reinterpret_cast<char*>(m.w) + (size_t)(m.geglu ? 0 : p.row_off) * rowb, t.w0_bytes,
-                              hipMemcpyDeviceToDevice, stream));
-    }
     void *nut = nullptr, *nd = nullptr;
     const int R = t.R + rank;
     PD_TRY(dev_alloc(&nut, (size_t)R * rows * 4));
@@ -94,7 +94,124 @@ int pd_engine::lora_add(int adapter, const char* name, const float* up, int up_r
     t.d = reinterpret_cast<float*>(nd);
     t.R = R;
     t.entries.push_back({adapter, rank});
-    if (!t.merged.empty()) t.merged.push_back(0.f);   // W does not hold the new columns yet
+    if (!t.merged.empty() || !t.fmerged.empty()) t.merged.push_back(0.f);   // W does not hold the new columns yet
+    lora_scale.emplace(adapter, 0.f);
+    return lora_merge(pi, false);   // a no-op unless the adapter is already active
+}
+
+int pd_engine::lora_target_base(int pi) {
+    const Param& p = params[pi];
+    WMat& m = *p.mat;
+    LoraTarget& t = lora[pi];
+    if (t.w0) return 0;
+    const size_t rowb = (size_t)m.Kpad * dt_size(T);
+    t.w0_bytes = (size_t)base_rows(p) * rowb;   // first adapter on this parameter: W holds the base weights now
+    if (dev_alloc(&t.w0, t.w0_bytes)) { lora.erase(pi); return 1; }
+    HIP_OK(hipMemcpyAsync(t.w0, reinterpret_cast<char*>(m.w) + (size_t)(m.geglu ? 0 : p.row_off) * rowb, t.w0_bytes,
+                          hipMemcpyDeviceToDevice, stream));
+    return 0;
+}
+
+// up [rows][r] -> up^T [r][rows] times `scale`; down [r][cin][taps] -> [r][Kpad] in the WMat's column layout
+static void lay_pair(const WMat& m, int rows, int r, float scale, const float* up, const float* down, float* ut, float* d) {
+    for (int n = 0; n < rows; ++n)
+        for (int j = 0; j < r; ++j) ut[(size_t)j * rows + n] = scale * up[(size_t)n * r + j];
+    for (int j = 0; j < r; ++j)
+        for (int c = 0; c < m.cin; ++c)
+            for (int tp = 0; tp < m.taps; ++tp)
+                d[(size_t)j * m.Kpad + (size_t)tp * m.cin_pad + c] = down[((size_t)j * m.cin + c) * m.taps + tp];
+}
+
+int pd_engine::lora_add_ex(int adapter, const char* name, const pd_lora_factors& f) {
+    if (ses.active) { pd_set_error("pd_lora_add_ex: end the sampling session first"); return 1; }
+    if (adapter < 0) { pd_set_error("pd_lora_add_ex: '%s': adapter id %d must be >= 0", name, adapter); return 1; }
+    auto it = index.find(name);
+    if (it == index.end()) { pd_set_error("pd_lora_add_ex: unknown tensor '%s'", name); return 2; }
+    const int pi = it->second;
+    const Param& p = params[pi];
+    if (p.kind != 1) { pd_set_error("pd_lora_add_ex: '%s' is a vector parameter (bias / norm); adapters apply to matrices", name); return 3; }
+    if (f.kind != PD_LORA_PAIR && f.kind != PD_LORA_HADA && f.kind != PD_LORA_KRON) {
+        pd_set_error("pd_lora_add_ex: '%s': unknown kind %d", name, f.kind);
+        return 3;
+    }
+    if (!f.up || !f.down || (f.kind == PD_LORA_HADA && (!f.up2 || !f.down2))) { pd_set_error("pd_lora_add_ex: '%s': null factor", name); return 3; }
+    if (!std::isfinite(f.scale)) { pd_set_error("pd_lora_add_ex: '%s': non-finite scale", name); return 3; }
+    WMat& m = *p.mat;
+    const int rows = (int)p.shape[0], kk = m.taps, cin = m.cin;
+    const size_t K = (size_t)cin * kk;
+    const bool kron = f.kind == PD_LORA_KRON, hada = f.kind == PD_LORA_HADA;
+    size_t n_u1, n_d1, n_u2 = 0, n_d2 = 0;   // floats of each host factor
+    if (kron) {
+        if (f.kron_a <= 0 || f.kron_b <= 0 || rows % f.kron_a != 0 || cin % f.kron_b != 0) {
+            pd_set_error("pd_lora_add_ex: '%s': w1 [%d, %d] does not divide the parameter's [%d, %d] (a * c = N and b * d = cin)", name,
+                         f.kron_a, f.kron_b, rows, cin);
+            return 3;
+        }
+        n_u1 = (size_t)f.kron_a * f.kron_b;
+        n_d1 = (size_t)(rows / f.kron_a) * (cin / f.kron_b) * kk;
+    } else {
+        if (f.rank <= 0 || (hada && f.rank2 <= 0)) { pd_set_error("pd_lora_add_ex: '%s': rank %d must be positive", name, hada && f.rank > 0 ? f.rank2 : f.rank); return 3; }
+        n_u1 = (size_t)rows * f.rank;
+        n_d1 = (size_t)f.rank * K;
+        if (hada) { n_u2 = (size_t)rows * f.rank2; n_d2 = (size_t)f.rank2 * K; }
+    }
+    if (!all_finite(f.up, n_u1) || !all_finite(f.down, n_d1) || (hada && (!all_finite(f.up2, n_u2) || !all_finite(f.down2, n_d2))) ||
+        (f.magnitude && !all_finite(f.magnitude, rows))) {
+        pd_set_error("pd_lora_add_ex: '%s': factors hold non-finite values", name);
+        return 3;
+    }
+    if (f.kind == PD_LORA_PAIR && !f.magnitude) {   // a plain pair: the stacked columns of pd_lora_add
+        std::vector<float> up(n_u1);
+        for (size_t i = 0; i < n_u1; ++i) up[i] = f.scale * f.up[i];
+        const int64_t ds[2] = {f.rank, (int64_t)K};
+        return lora_add(adapter, name, up.data(), rows, f.rank, f.down, ds, 2);
+    }
+    auto tit = lora.find(pi);
+    if (tit != lora.end()) {
+        bool dup = false;
+        for (const LoraEntry& en : tit->second.entries) dup = dup || en.adapter == adapter;
+        for (const LoraForm& fo : tit->second.forms) dup = dup || fo.adapter == adapter;
+        if (dup) { pd_set_error("pd_lora_add_ex: '%s' already has adapter %d", name, adapter); return 3; }
+    }
+    HIP_OK(hipSetDevice(device));
+    // device layout, every part a multiple of 4 floats
+    auto up4 = [](size_t n) { return (n + 3) & ~(size_t)3; };
+    const size_t o_u1 = 0, s_u1 = kron ? n_u1 : (size_t)f.rank * rows;
+    const size_t o_d1 = o_u1 + up4(s_u1), s_d1 = kron ? n_d1 : (size_t)f.rank * m.Kpad;
+    const size_t o_u2 = o_d1 + up4(s_d1), s_u2 = hada ? (size_t)f.rank2 * rows : 0;
+    const size_t o_d2 = o_u2 + up4(s_u2), s_d2 = hada ? (size_t)f.rank2 * m.Kpad : 0;
+    const size_t o_mg = o_d2 + up4(s_d2), total = o_mg + up4(f.magnitude ? rows : 0);
+    std::vector<float> h(total, 0.f);
+    if (kron) {
+        const int c = rows / f.kron_a, d = cin / f.kron_b;
+        for (size_t i = 0; i < n_u1; ++i) h[o_u1 + i] = f.scale * f.up[i];
+        for (int pp = 0; pp < c; ++pp)
+            for (int q = 0; q < d; ++q)
+                for (int tp = 0; tp < kk; ++tp) h[o_d1 + ((size_t)pp * kk + tp) * d + q] = f.down[((size_t)pp * d + q) * kk + tp];
+    } else {
+        lay_pair(m, rows, f.rank, f.scale, f.up, f.down, &h[o_u1], &h[o_d1]);
+        if (hada) lay_pair(m, rows, f.rank2, 1.f, f.up2, f.down2, &h[o_u2], &h[o_d2]);
+    }
+    if (f.magnitude) memcpy(&h[o_mg], f.magnitude, (size_t)rows * 4);
+    PD_TRY(lora_target_base(pi));
+    LoraTarget& t = lora[pi];
+    void* q = nullptr;
+    PD_TRY(dev_alloc(&q, total * 4));
+    LoraForm fo;
+    fo.adapter = adapter; fo.kind = f.kind; fo.r1 = kron ? 0 : f.rank; fo.r2 = hada ? f.rank2 : 0;
+    fo.ka = kron ? f.kron_a : 0; fo.kb = kron ? f.kron_b : 0;
+    fo.buf = reinterpret_cast<float*>(q);
+    fo.bytes = total * 4;
+    fo.ut1 = fo.buf + o_u1; fo.d1 = fo.buf + o_d1;
+    if (hada) { fo.ut2 = fo.buf + o_u2; fo.d2 = fo.buf + o_d2; }
+    if (f.magnitude) fo.mag = fo.buf + o_mg;
+    if (hipMemcpyAsync(q, h.data(), total * 4, hipMemcpyHostToDevice, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
+        hipFree(q);
+        pd_set_error("pd_lora_add_ex: '%s': upload failed", name);
+        return 1;
+    }
+    t.forms.push_back(fo);
+    if (!t.merged.empty() || !t.fmerged.empty()) t.fmerged.push_back(0.f);   // W does not hold the new adapter yet
     lora_scale.emplace(adapter, 0.f);
     return lora_merge(pi, false);   // a no-op unless the adapter is already active
 }
@@ -112,36 +229,56 @@ int pd_engine::lora_set_scales(const float* scales, int n) {
 
 // restores / merges every target (or one) whose adapters' multipliers differ from what W holds
 int pd_engine::lora_merge(int only, bool force) {
-    struct Job { int pi; LoraTarget* t; size_t off; };
+    struct Job { int pi; LoraTarget* t; size_t off; bool plain, forms; };
     std::vector<Job> jobs;
     std::vector<float> cols;
     bool changed = false;
+    size_t scratch = 0;
     HIP_OK(hipSetDevice(device));
     for (auto& kv : lora) {
         if (only >= 0 && kv.first != only) continue;
         LoraTarget& t = kv.second;
-        std::vector<float> want(t.entries.size());
-        bool any = false;
+        std::vector<float> want(t.entries.size()), fwant(t.forms.size());
+        bool plain = false, forms = false;
         for (size_t i = 0; i < t.entries.size(); ++i) {
             want[i] = lora_scale[t.entries[i].adapter];
-            any = any || want[i] != 0.f;
+            plain = plain || want[i] != 0.f;
         }
-        if (!any) want.clear();
-        if (!force && want == t.merged) continue;
+        for (size_t i = 0; i < t.forms.size(); ++i) {
+            fwant[i] = lora_scale[t.forms[i].adapter];
+            forms = forms || fwant[i] != 0.f;
+        }
+        if (!plain && !forms) { want.clear(); fwant.clear(); }
+        if (!force && want == t.merged && fwant == t.fmerged) continue;
         const Param& p = params[kv.first];
         WMat& m = *p.mat;
         const size_t rowb = (size_t)m.Kpad * dt_size(T);
-        if (want.empty()) {   // no active adapter: W0 exactly
+        if (!plain && !forms) {   // no active adapter: W0 exactly
             HIP_OK(hipMemcpyAsync(reinterpret_cast<char*>(m.w) + (size_t)(m.geglu ? 0 : p.row_off) * rowb, t.w0, t.w0_bytes,
                                   hipMemcpyDeviceToDevice, stream));
         } else {
-            jobs.push_back({kv.first, &t, cols.size()});
+            jobs.push_back({kv.first, &t, cols.size(), plain, forms});
             for (size_t i = 0; i < t.entries.size(); ++i) cols.insert(cols.end(), (size_t)t.entries[i].r, want[i]);
+            if (forms) scratch = std::max(scratch, (size_t)p.shape[0] * m.Kpad);
         }
         t.merged = want;
+        t.fmerged = fwant;
         changed = true;
     }
     if (!changed) return 0;
+    if (scratch > lora_tmp_cap) {
+        HIP_OK(hipStreamSynchronize(stream));
+        if (lora_tmp) hipFree(lora_tmp);
+        if (lora_sum) hipFree(lora_sum);
+        lora_tmp = lora_sum = nullptr;
+        lora_tmp_cap = 0;
+        void *q0 = nullptr, *q1 = nullptr;
+        PD_TRY(dev_alloc(&q0, scratch * 4));
+        if (dev_alloc(&q1, scratch * 4)) { hipFree(q0); return 1; }
+        lora_tmp = reinterpret_cast<float*>(q0);
+        lora_sum = reinterpret_cast<float*>(q1);
+        lora_tmp_cap = scratch;
+    }
     if (!jobs.empty()) {
         if (cols.size() > lora_scale_cap) {
             HIP_OK(hipStreamSynchronize(stream));
@@ -152,12 +289,38 @@ int pd_engine::lora_merge(int only, bool force) {
             lora_scale_dev = reinterpret_cast<float*>(q);
             lora_scale_cap = cols.size();
         }
-        HIP_OK(hipMemcpyAsync(lora_scale_dev, cols.data(), cols.size() * 4, hipMemcpyHostToDevice, stream));
+        if (!cols.empty()) HIP_OK(hipMemcpyAsync(lora_scale_dev, cols.data(), cols.size() * 4, hipMemcpyHostToDevice, stream));
         for (const Job& j : jobs) {
             const Param& p = params[j.pi];
             WMat& m = *p.mat;
-            if (launch_lora_merge(T, m.w, j.t->w0, (int)p.shape[0], m.geglu ? 0 : p.row_off, m.geglu ? m.Nout : 0, m.Kpad, j.t->ut, j.t->d,
-                                  lora_scale_dev + j.off, j.t->R, stream)) {
+            const int rows = (int)p.shape[0], row_off = m.geglu ? 0 : p.row_off, half = m.geglu ? m.Nout : 0;
+            int rc = 0;
+            if (!j.forms) {   // plain adapters only: the one merge kernel
+                rc = launch_lora_merge(T, m.w, j.t->w0, rows, row_off, half, m.Kpad, j.t->ut, j.t->d, lora_scale_dev + j.off, j.t->R, stream);
+            } else {          // W0, then the plain columns, then each active form in load order, in fp32; rounded once by the last
+                int left = j.plain ? 1 : 0, first = 1;
+                for (float s : j.t->fmerged) left += s != 0.f;
+                if (j.plain) {
+                    rc = launch_lora_form_delta(lora_tmp, rows, m.Kpad, j.t->ut, j.t->d, lora_scale_dev + j.off, 0.f, j.t->R, nullptr, nullptr, 0,
+                                                stream) ||
+                         launch_lora_form_apply(T, m.w, j.t->w0, lora_sum, lora_tmp, nullptr, rows, row_off, half, m.Kpad, first, --left == 0,
+                                                stream);
+                    first = 0;
+                }
+                for (size_t i = 0; i < j.t->forms.size() && !rc; ++i) {
+                    const LoraForm& fo = j.t->forms[i];
+                    const float s = j.t->fmerged[i];
+                    if (s == 0.f) continue;
+                    if (fo.kind == PD_LORA_KRON)
+                        rc = launch_lora_kron_delta(lora_tmp, rows, m.Kpad, m.cin, m.cin_pad, m.taps, fo.ut1, fo.d1, s, fo.ka, fo.kb, stream);
+                    else
+                        rc = launch_lora_form_delta(lora_tmp, rows, m.Kpad, fo.ut1, fo.d1, nullptr, s, fo.r1, fo.ut2, fo.d2, fo.r2, stream);
+                    rc = rc || launch_lora_form_apply(T, m.w, j.t->w0, lora_sum, lora_tmp, fo.mag, rows, row_off, half, m.Kpad, first,
+                                                      --left == 0, stream);
+                    first = 0;
+                }
+            }
+            if (rc) {
                 pd_set_error("LoRA merge launch failed for '%s'", p.name.c_str());
                 return 1;
             }
@@ -195,17 +358,34 @@ int pd_engine::lora_remove(int adapter) {
         LoraTarget& t = kv.second;
         bool hit = false;
         for (const LoraEntry& en : t.entries) hit = hit || adapter == -1 || en.adapter == adapter;
+        for (const LoraForm& fo : t.forms) hit = hit || adapter == -1 || fo.adapter == adapter;
         if (!hit) continue;
         const Param& p = params[kv.first];
         WMat& m = *p.mat;
         std::vector<LoraEntry> keep;
         for (const LoraEntry& en : t.entries)
             if (adapter != -1 && en.adapter != adapter) keep.push_back(en);
-        if (keep.empty()) {
+        std::vector<LoraForm> fkeep;
+        for (const LoraForm& fo : t.forms) {   // (every merge ends synchronised: nothing in flight reads a form's buffer)
+            if (adapter != -1 && fo.adapter != adapter) fkeep.push_back(fo);
+            else hipFree(fo.buf);
+        }
+        t.forms = fkeep;
+        if (keep.empty() && fkeep.empty()) {
             const size_t rowb = (size_t)m.Kpad * dt_size(T);
             HIP_OK(hipMemcpyAsync(reinterpret_cast<char*>(m.w) + (size_t)(m.geglu ? 0 : p.row_off) * rowb, t.w0, t.w0_bytes,
                                   hipMemcpyDeviceToDevice, stream));
             emptied.push_back(kv.first);
+            continue;
+        }
+        restack.push_back(kv.first);
+        if (keep.size() == t.entries.size()) continue;   // only a form left
+        if (keep.empty()) {
+            hipFree(t.ut);
+            hipFree(t.d);
+            t.ut = t.d = nullptr;
+            t.R = 0;
+            t.entries.clear();
             continue;
         }
         // restack the kept adapters' columns, in their load order
@@ -233,7 +413,6 @@ int pd_engine::lora_remove(int adapter) {
         t.d = reinterpret_cast<float*>(nd);
         t.R = R;
         t.entries = keep;
-        restack.push_back(kv.first);
     }
     HIP_OK(hipStreamSynchronize(stream));
     for (int pi : emptied) {
@@ -261,7 +440,12 @@ void pd_engine::lora_release() {
         if (kv.second.w0) hipFree(kv.second.w0);
         if (kv.second.ut) hipFree(kv.second.ut);
         if (kv.second.d) hipFree(kv.second.d);
+        for (const LoraForm& fo : kv.second.forms) hipFree(fo.buf);
     }
+    if (lora_tmp) hipFree(lora_tmp);
+    if (lora_sum) hipFree(lora_sum);
+    lora_tmp = lora_sum = nullptr;
+    lora_tmp_cap = 0;
     lora.clear();
     lora_scale.clear();
     if (lora_scale_dev) hipFree(lora_scale_dev);
@@ -274,6 +458,8 @@ size_t pd_engine::lora_bytes(bool base_only) const {
     for (const auto& kv : lora) {
         b += kv.second.w0_bytes;
         if (!base_only) b += (size_t)kv.second.R * ((size_t)params[kv.first].shape[0] + params[kv.first].mat->Kpad) * 4;
+        if (!base_only)
+            for (const LoraForm& fo : kv.second.forms) b += fo.bytes;
     }
     return b;
 }
@@ -283,6 +469,11 @@ int pd_lora_add(pd_engine* e, int32_t adapter, const char* name, const float* up
                 const int64_t* down_shape, int32_t down_ndim) {
     if (!e || !name || !up || !down || !down_shape) { pd_set_error("null argument"); return 1; }
     return e->lora_add(adapter, name, up, up_rows, rank, down, down_shape, down_ndim);
+}
+
+int pd_lora_add_ex(pd_engine* e, int32_t adapter, const char* name, const pd_lora_factors* f) {
+    if (!e || !name || !f) { pd_set_error("null argument"); return 1; }
+    return e->lora_add_ex(adapter, name, *f);
 }
 
 int pd_lora_set_scales(pd_engine* e, const float* scales, int32_t n) {

@@ -439,6 +439,18 @@ int launch_fill_random(void* p, int dt, long long n, float scale, float shift, u
 // destination rows from row_off on.  Kpad must be a multiple of 32.
 int launch_lora_merge(int dt, void* W, const void* W0, int rows, int row_off, int geglu_half, int Kpad, const float* UT,
                       const float* D, const float* scale, int R, hipStream_t s);
+// Adapter forms beyond a stack of rank-1 columns (lora.hip).  The delta launches write fp32 out [rows][Kpad] in source-row order:
+//   form: out = (sum_j mul_j UT1[j] (x) D1[j]) (.) (sum_j UT2[j] (x) D2[j]) (the second product only when UT2 is given); mul_j = scale[j],
+//         or s when scale is null;
+//   kron: out[i * c + p, tap * cin_pad + j * d + q] = (s * w1[i, j]) * w2[p, tap, q], w1 [a][b], w2 [rows / a][taps][cin / b]; pad columns 0.
+// apply: sum = (first ? W0 : sum) + E, E = delta, or (mag[n] / |W0 + delta|_2)(W0 + delta) - W0 per row when mag is given; with `last`
+// the sum is rounded to dt and written to W through launch_lora_merge's row mapping instead.  `sum` is fp32 [rows][Kpad].
+int launch_lora_form_delta(float* out, int rows, int Kpad, const float* UT1, const float* D1, const float* scale, float s, int R1,
+                           const float* UT2, const float* D2, int R2, hipStream_t st);
+int launch_lora_kron_delta(float* out, int rows, int Kpad, int cin, int cin_pad, int taps, const float* w1, const float* w2, float s, int a,
+                           int b, hipStream_t st);
+int launch_lora_form_apply(int dt, void* W, const void* W0, float* sum, const float* delta, const float* mag, int rows, int row_off,
+                           int geglu_half, int Kpad, int first, int last, hipStream_t st);
 // DiagonalGaussianDistribution of the first-stage encoder (distributions.py:24-62) from quant_conv's NHWC output `mom` (dtype mom_dt,
 // Cpad >= 2 z channels: mean 0..z-1, logvar z..2z-1) into caller-layout fp32 NCHW: what = PD_VAE_MEAN: scale * mean,
 // PD_VAE_SAMPLE: scale * (mean + exp(0.5 clamp(logvar, -30, 20)) * noise[B, z, HW]), PD_VAE_MOMENTS: the raw [B, 2z, HW] moments

@@ -116,6 +116,16 @@ class pd_mlsd_args(C.Structure):
                 ("Cf", C.c_int32), ("c_off", C.c_int32), ("mul", C.c_float), ("add", C.c_float)]
 
 
+PD_LORA_PAIR, PD_LORA_HADA, PD_LORA_KRON = 0, 1, 2
+LORA_KINDS = {"pair": PD_LORA_PAIR, "hada": PD_LORA_HADA, "kron": PD_LORA_KRON}
+
+
+class LoraFactors(C.Structure):   # pd_lora_factors
+    _fields_ = [("kind", C.c_int32), ("rank", C.c_int32), ("rank2", C.c_int32), ("kron_a", C.c_int32), ("kron_b", C.c_int32),
+                ("scale", C.c_float), ("up", C.c_void_p), ("down", C.c_void_p), ("up2", C.c_void_p), ("down2", C.c_void_p),
+                ("magnitude", C.c_void_p)]
+
+
 class pd_canny_args(C.Structure):
     _fields_ = [
         ("src", C.c_void_p), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("mem_src", C.c_int32),
@@ -270,6 +280,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.pd_read_weights.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
     lib.pd_lora_add.argtypes = [C.c_void_p, C.c_int32, C.c_char_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                 C.POINTER(C.c_int64), C.c_int32]
+    lib.pd_lora_add_ex.argtypes = [C.c_void_p, C.c_int32, C.c_char_p, C.POINTER(LoraFactors)]
     lib.pd_lora_set_scales.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
     lib.pd_lora_remove.argtypes = [C.c_void_p, C.c_int32]
     lib.pd_set_freeu.argtypes = [C.c_void_p] + [C.c_float] * 4
@@ -313,7 +324,7 @@ EXPORTS = [
     "pd_sd3_configure", "pd_sd3_weights_missing", "pd_sd3_forward", "pd_sd3_control", "pd_sd3_sample", "pd_sd3_sample_ex", "pd_sd3_down_proj",
     "pd_op_sd3_update",
     "pd_op_conv2d", "pd_op_conv2d_ex", "pd_op_conv2d_upfold", "pd_op_linear", "pd_op_linear_ex", "pd_op_linear_fp8", "pd_op_groupnorm", "pd_op_layernorm", "pd_op_groupnorm_slabs", "pd_op_groupnorm_coef", "pd_op_ln_linear", "pd_op_attention", "pd_op_attention_ex", "pd_op_spatial_transformer", "pd_op_spatial_transformer_ctx", "pd_op_time_embed",
-    "pd_op_timestep_embedding_i", "pd_op_timestep_embedding_f", "pd_op_vae_downsample", "pd_read_weights", "pd_lora_add", "pd_lora_set_scales", "pd_lora_remove",
+    "pd_op_timestep_embedding_i", "pd_op_timestep_embedding_f", "pd_op_vae_downsample", "pd_read_weights", "pd_lora_add", "pd_lora_add_ex", "pd_lora_set_scales", "pd_lora_remove",
     "pd_set_freeu", "pd_get_freeu", "pd_op_freeu_concat",
     "pd_philox4x32_10", "pd_set_rng", "pd_get_rng", "pd_randn",
     "pd_hed_configure", "pd_hed_weights_missing", "pd_hed_detect", "pd_op_hed_stage_tail", "pd_op_hed_fuse",
@@ -658,6 +669,74 @@ class Engine:
         shp = (C.c_int64 * max(1, down.ndim))(*down.shape)
         self._check(self.lib.pd_lora_add(self._h, int(adapter), name.encode(), up.ctypes.data, up.shape[0], r, down.ctypes.data,
                                          shp, down.ndim))
+
+    def lora_add_ex(self, adapter: int, name: str, kind: str, up, down, up2=None, down2=None, scale: float = 1.0,
+                    magnitude=None) -> None:
+        """Register one adapter factor set that is not (only) a plain pair (pd_lora_add_ex).  With N, K = cin * kh * kw the
+        tensor's rows and columns, the delta D is, by `kind`:
+          "pair": scale * up @ down                         up [N, r], down [r, K] or [r, cin, kh, kw]
+          "hada": scale * (up @ down) * (up2 @ down2)       (LoHa: w1_a, w1_b, w2_a, w2_b)
+          "kron": scale * kron(up, down)                    up = w1 [a, b], down = w2 [c, d] or [c, d, kh, kw]; a c = N, b d = cin
+        and `magnitude` [N] (DoRA) turns the contribution into (m / |W0 + s D|_row) (W0 + s D) - W0."""
+        if kind not in LORA_KINDS:
+            raise PdError(f"pd_lora_add_ex: '{name}': kind must be one of {sorted(LORA_KINDS)}, got {kind!r}")
+        shapes = getattr(self, "_shapes", None)
+        if shapes is None:
+            shapes = self._shapes = dict(self.param_names())
+        if name not in shapes:
+            raise PdError(f"pd_lora_add_ex: unknown tensor '{name}'")
+        shp = tuple(shapes[name])
+        if len(shp) < 2:
+            raise PdError(f"pd_lora_add_ex: '{name}' is a vector parameter (bias / norm); adapters apply to matrices")
+        N, cin, tail = shp[0], shp[1], tuple(shp[2:])
+        K = int(np.prod(shp[1:]))
+        arr = lambda a: np.ascontiguousarray(np.asarray(_to_host(a), np.float32))
+        f = LoraFactors(kind=LORA_KINDS[kind], scale=float(scale))
+        keep = []
+
+        def pair(u, d, what):
+            u, d = arr(u), arr(d)
+            if u.ndim == 4 and u.shape[2:] == (1, 1):
+                u = np.ascontiguousarray(u[:, :, 0, 0])
+            ok = u.ndim == 2 and u.shape[0] == N and d.ndim in (2, 4) and d.shape[0] == u.shape[1] and d.size == u.shape[1] * K
+            if ok and d.ndim == 4:
+                ok = d.shape[1] == cin and (not tail or tuple(d.shape[2:]) == tail)
+            if not ok or u.shape[1] == 0:
+                raise PdError(f"pd_lora_add_ex: '{name}': {what} {u.shape} / {d.shape} are not [{N}, r] and [r, {K}] (or [r, {cin}, kh, kw])")
+            keep.extend((u, d))
+            return u, d
+
+        if kind == "kron":
+            w1, w2 = arr(up), arr(down)
+            taps = int(np.prod(tail)) if tail else 1
+            if w2.ndim == 2 and taps > 1 and w2.shape[1] % taps == 0:   # a decomposed w2: [c, d * kh * kw]
+                w2 = w2.reshape(w2.shape[0], -1, *tail)
+            ok = w1.ndim == 2 and w2.ndim in (2, 4)
+            if ok and w2.ndim == 4:
+                ok = (tuple(w2.shape[2:]) == tail) if tail else w2.shape[2:] == (1, 1)
+            if ok and w2.ndim == 2 and tail:
+                ok = int(np.prod(tail)) == 1
+            if not ok or w1.shape[0] * w2.shape[0] != N or w1.shape[1] * w2.shape[1] != cin:
+                raise PdError(f"pd_lora_add_ex: '{name}': w1 {w1.shape} / w2 {w2.shape} do not satisfy a * c = {N} and b * d = {cin} "
+                              f"with the kernel size {tail or (1, 1)}")
+            keep.extend((w1, w2))
+            f.kron_a, f.kron_b = w1.shape
+            f.up, f.down = w1.ctypes.data, w2.ctypes.data
+        else:
+            u, d = pair(up, down, "up / down")
+            f.rank, f.up, f.down = u.shape[1], u.ctypes.data, d.ctypes.data
+            if kind == "hada":
+                if up2 is None or down2 is None:
+                    raise PdError(f"pd_lora_add_ex: '{name}': a Hadamard adapter needs up2 / down2")
+                u2, d2 = pair(up2, down2, "up2 / down2")
+                f.rank2, f.up2, f.down2 = u2.shape[1], u2.ctypes.data, d2.ctypes.data
+        if magnitude is not None:
+            m = arr(magnitude).reshape(-1)
+            if m.size != N:
+                raise PdError(f"pd_lora_add_ex: '{name}': the magnitude has {m.size} elements, the parameter has {N} rows")
+            keep.append(m)
+            f.magnitude = m.ctypes.data
+        self._check(self.lib.pd_lora_add_ex(self._h, int(adapter), name.encode(), C.byref(f)))
 
     def lora_set_scales(self, scales: Sequence[float]) -> None:
         """Scale of adapter id i = scales[i] (0: inactive; ids past the end: 0); merges what changed on the device."""

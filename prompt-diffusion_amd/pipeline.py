@@ -27,6 +27,7 @@ from typing import Any, Callable, Dict, List, Optional, Sequence, Union
 import numpy as np
 
 from . import engine as E
+from .lora_pipeline import AdapterMixin
 
 
 @dataclasses.dataclass
@@ -164,7 +165,7 @@ def prepare_inpaint_mask(mask_image, width, height, batch_size, scale_factor):
     return PromptDiffusionPipeline._tile(m, batch_size, "`mask_image`")
 
 
-class PromptDiffusionPipeline:
+class PromptDiffusionPipeline(AdapterMixin):
     _callback_tensor_inputs = ["latents", "prompt_embeds", "negative_prompt_embeds"]
     vae_scale_factor = 8
     vae_scaling_factor = 0.18215      # models/cldm_v15.yaml:17
@@ -198,12 +199,7 @@ class PromptDiffusionPipeline:
             self.enable_long_prompts(long_prompts)
         self._guidance_scale = 7.5
         self._device_images = bool(device_images)
-        # LoRA adapters (load_lora_weights): name -> {"id", "unet", "text_encoder"}; the active set with its weights; the
-        # per-id scales the engine holds merged now (None: nothing merged yet)
-        self._lora_adapters: Dict[str, Dict[str, Any]] = {}
-        self._lora_active: Dict[str, float] = {}
-        self._lora_next_id = 0
-        self._lora_merged: Optional[List[float]] = None
+        self._lora_init()      # LoRA adapters (load_lora_weights; lora_pipeline.AdapterMixin)
 
     def _check_fusable(self):
         """The fused loops restate this package's schedulers on the engine's own noise schedule; anything else is refused."""
@@ -557,82 +553,21 @@ class PromptDiffusionPipeline:
             ne = np.repeat(_to_numpy(negative_prompt_embeds).astype(np.float32), num_images_per_prompt, axis=0)
         return pe, ne
 
-    # ------------------------------------------------------------------ LoRA (diffusers LoraLoaderMixin surface)
-    def load_lora_weights(self, pretrained_model_name_or_path_or_dict, adapter_name: Optional[str] = None, **kwargs):
-        """Load a LoRA (dict of arrays or a local .safetensors file; kohya, diffusers/PEFT or legacy attention-processor keys)
-        into the engine's UNet and text transformer as a new adapter.  It joins the active set with weight 1.0; the weights
-        are merged on the device at the next call."""
+    # ------------------------------------------------------------------ LoRA (diffusers LoraLoaderMixin surface; lora_pipeline.py)
+    _lora_component_names = ("unet", "text_encoder")
+
+    def _lora_parse(self, src):
+        """kohya, diffusers/PEFT or legacy attention-processor keys -> the engine's UNet and text transformer tensors"""
         from . import lora as L
+        return L.parse_adapters(src, self.engine.cfg)
+
+    def _lora_components(self, names):
         from . import weights as W
-        if kwargs:
-            raise NotImplementedError(f"load_lora_weights: unsupported arguments {sorted(kwargs)}")
-        name = adapter_name if adapter_name is not None else f"default_{self._lora_next_id}"
-        if name in self._lora_adapters:
-            raise ValueError(f"Adapter name {name} already in use")
-        triples = L.parse_lora(pretrained_model_name_or_path_or_dict, self.engine.cfg)
-        te = any(k.startswith(W.TEXT_PREFIX) for k in triples)
+        te = any(k.startswith(W.TEXT_PREFIX) for k in names)
         if te and self.text_encoder is not None and self.text_encoder != self._engine_text_encoder:
             raise ValueError("this LoRA has text-encoder layers, but a caller-supplied text_encoder is attached; only the engine's "
                              "own text transformer can take them")
-        aid = self._lora_next_id
-        added = False
-        try:
-            for k, (up, down, alpha) in triples.items():
-                self.engine.lora_add(aid, k, up, down, alpha=alpha)
-                added = True
-        except Exception:
-            if added:
-                self.engine.lora_remove(aid)
-            raise
-        self._lora_next_id += 1
-        self._lora_adapters[name] = dict(id=aid, unet=any(k.startswith(W.UNET_PREFIX) for k in triples), text_encoder=te)
-        self._lora_active[name] = 1.0
-
-    def set_adapters(self, adapter_names: Union[str, List[str]], adapter_weights: Optional[Union[float, List[float]]] = None):
-        """Make exactly these adapters active, with these weights (default 1.0)."""
-        names = [adapter_names] if isinstance(adapter_names, str) else list(adapter_names)
-        if adapter_weights is None:
-            weights = [1.0] * len(names)
-        elif isinstance(adapter_weights, (int, float)):
-            weights = [float(adapter_weights)] * len(names)
-        else:
-            weights = [float(w) for w in adapter_weights]
-        if len(weights) != len(names):
-            raise ValueError(f"Length of adapter names {len(names)} is not equal to the length of their weights {len(weights)}.")
-        for n in names:
-            if n not in self._lora_adapters:
-                raise ValueError(f"Adapter name(s) {n} not in the list of present adapters: {sorted(self._lora_adapters)}.")
-        self._lora_active = dict(zip(names, weights))
-
-    def get_active_adapters(self) -> List[str]:
-        return list(self._lora_active)
-
-    def get_list_adapters(self) -> Dict[str, List[str]]:
-        out: Dict[str, List[str]] = {}
-        for comp in ("unet", "text_encoder"):
-            names = [n for n, a in self._lora_adapters.items() if a[comp]]
-            if names:
-                out[comp] = names
-        return out
-
-    def delete_adapters(self, adapter_names: Union[str, List[str]]):
-        names = [adapter_names] if isinstance(adapter_names, str) else list(adapter_names)
-        for n in names:
-            if n not in self._lora_adapters:
-                raise ValueError(f"Adapter name {n} not in the list of present adapters: {sorted(self._lora_adapters)}.")
-        for n in names:
-            aid = self._lora_adapters.pop(n)["id"]
-            self._lora_active.pop(n, None)
-            self.engine.lora_remove(aid)
-            if self._lora_merged is not None and aid < len(self._lora_merged):
-                self._lora_merged[aid] = 0.0
-
-    def unload_lora_weights(self):
-        if self._lora_adapters:
-            self.engine.lora_remove(-1)
-        self._lora_adapters.clear()
-        self._lora_active.clear()
-        self._lora_merged = None
+        return dict(unet=any(k.startswith(W.UNET_PREFIX) for k in names), text_encoder=te)
 
     def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
         r"""Enables the FreeU mechanism as in https://arxiv.org/abs/2309.11497.
@@ -699,23 +634,6 @@ class PromptDiffusionPipeline:
         """
         st = self._engine_vae("disable_vae_tiling").vae_tiling
         self.engine.set_vae_tiling(False, st.tile_latent, st.overlap_factor, st.tile_batch)
-
-    def _lora_scales(self, scale: float) -> List[float]:
-        """Effective multiplier per adapter id: its set_adapters weight x the call's cross_attention_kwargs scale
-        (diffusers' scale_lora_layers / lora_scale); 0 for inactive ids."""
-        out = [0.0] * self._lora_next_id
-        for n, w in self._lora_active.items():
-            out[self._lora_adapters[n]["id"]] = float(w) * float(scale)
-        return out
-
-    def _lora_sync(self, scale: float):
-        """Merge on the device only when the effective scales differ from the merged ones."""
-        want = self._lora_scales(scale)
-        if self._lora_merged is None and not any(want):
-            return
-        if want != self._lora_merged:
-            self.engine.lora_set_scales(want)
-            self._lora_merged = want
 
     # ------------------------------------------------------------------ the call
     def __call__(self, prompt: Union[str, List[str]] = None, image=None, image_pair: List = None,

@@ -26,7 +26,7 @@ The three steps of the loop body (controlnet, transformer, CFG + scheduler.step;
 (`SD3Engine.sample`); with `callback_on_step_end` the loop is driven step by step from here (`SD3Engine.forward` + the same
 Euler update) so that the callback can replace the latents or the embeddings (:1247-1258).  Arrays are NumPy (torch tensors
 are converted).  Not supported, raising NotImplementedError like the SD1.5 mirror does for options outside the path:
-`ip_adapter_image(_embeds)`, `joint_attention_kwargs` (LoRA scale).
+`ip_adapter_image(_embeds)`.  `joint_attention_kwargs={"scale": s}` scales the adapters of `load_lora_weights`.
 
 `StableDiffusion3PromptDiffusionImg2ImgPipeline(image=, strength=)` and `StableDiffusion3PromptDiffusionInpaintPipeline(image=,
 mask_image=, strength=)` add diffusers' SD3 img2img and (16-channel) inpainting to the same call: the grid is truncated by `strength`,
@@ -38,6 +38,7 @@ from typing import Any, Callable, Dict, List, Optional, Union
 import numpy as np
 
 from . import engine as E
+from .lora_pipeline import AdapterMixin
 from .pipeline import EngineGenerator, prepare_inpaint_mask
 from .sd3 import SD3Engine, flow_match_sigmas, img2img_start
 
@@ -60,7 +61,7 @@ def _image_array(x):
     return x
 
 
-class StableDiffusion3PromptDiffusionPipeline:
+class StableDiffusion3PromptDiffusionPipeline(AdapterMixin):
     _callback_tensor_inputs = _CALLBACK_TENSOR_INPUTS
 
     def __init__(self, engine: SD3Engine, encode_prompt: Optional[Callable] = None, vae_encode: Optional[Callable] = None,
@@ -78,6 +79,23 @@ class StableDiffusion3PromptDiffusionPipeline:
         self.vae_scaling_factor, self.vae_shift_factor, self.vae_scale_factor = vae_scaling_factor, vae_shift_factor, vae_scale_factor
         self.shift = shift
         self._guidance_scale, self._clip_skip, self._num_timesteps, self._interrupt = 7.0, None, 0, False
+        self._lora_init()      # adapters (load_lora_weights; lora_pipeline.AdapterMixin)
+
+    # ------------------------------------------------------------------ LoRA (diffusers SD3LoraLoaderMixin surface)
+    _lora_component_names = ("transformer", "text_encoder", "text_encoder_2")
+
+    def _lora_parse(self, src):
+        """diffusers / PEFT keys (transformer., text_encoder., text_encoder_2.) -> the engine's tensors; T5 and the ControlNet are
+        not targets"""
+        from . import lora as L
+        return L.parse_sd3_adapters(src, self.engine.cfg, getattr(self.engine, "text_cfg", None))
+
+    def _lora_components(self, names):
+        comps = {c: any(k.startswith(c + ".") for k in names) for c in self._lora_component_names}
+        if (comps["text_encoder"] or comps["text_encoder_2"]) and self.encode_prompt is not None:
+            raise ValueError("this LoRA has text-encoder layers, but an `encode_prompt` callable is attached; only the engine's own "
+                             "text encoders can take them")
+        return comps
 
     # ------------------------------------------------------------------ properties of the reference pipeline
     @property
@@ -348,8 +366,15 @@ class StableDiffusion3PromptDiffusionPipeline:
         """_edit: set by the img2img / inpaint subclasses -- {"image", "strength", "mask_image"}."""
         if ip_adapter_image is not None or ip_adapter_image_embeds is not None:
             raise NotImplementedError("ip_adapter_image / ip_adapter_image_embeds are outside the engine's path")
+        lora_scale = 1.0
         if joint_attention_kwargs:
-            raise NotImplementedError("joint_attention_kwargs (LoRA scale) is outside the engine's path")
+            if not self._lora_adapters:
+                raise NotImplementedError("joint_attention_kwargs (LoRA scale) needs a LoRA loaded with load_lora_weights")
+            if set(joint_attention_kwargs) - {"scale"}:
+                raise NotImplementedError(f"joint_attention_kwargs: only 'scale' is supported, got {sorted(joint_attention_kwargs)}")
+            lora_scale = float(joint_attention_kwargs.get("scale", 1.0))
+        if self._lora_adapters or self._lora_merged is not None:
+            self._lora_sync(lora_scale)     # adapters x joint_attention_kwargs scale, in the transformer and the CLIP encoders
         cfg = self.engine.cfg
         if control_image is None or control_image_pair is None:
             raise ValueError("`control_image` and `control_image_pair` are required (the reference asserts a SD3PromptDiffusionModel)")

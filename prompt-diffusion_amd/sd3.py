@@ -505,6 +505,23 @@ class SD3Engine:
             raise E.PdError(f"{self.weights_missing()} SD3 tensors missing after load_state_dict")
 
     # ------------------------------------------------------------------ text encoders
+    # ------------------------------------------------------------------ adapters (pd_lora_*): the base engine's registry holds the SD3 tensors
+    def lora_add(self, adapter: int, name: str, up, down, alpha: Optional[float] = None) -> None:
+        self.base.lora_add(adapter, name, up, down, alpha=alpha)
+
+    def lora_add_ex(self, adapter: int, name: str, kind: str, up, down, up2=None, down2=None, scale: float = 1.0, magnitude=None) -> None:
+        self.base.lora_add_ex(adapter, name, kind, up, down, up2=up2, down2=down2, scale=scale, magnitude=magnitude)
+
+    def lora_set_scales(self, scales) -> None:
+        self.base.lora_set_scales(scales)
+
+    def lora_remove(self, adapter: int = -1) -> None:
+        self.base.lora_remove(adapter)
+
+    def read_weight(self, name: str) -> np.ndarray:
+        """One tensor back under its state-dict name as float32, adapters merged (pd_read_weights)."""
+        return self.base.read_weight(name)
+
     def configure_text(self, cfg: SD3TextConfig = SD3_MEDIUM_TEXT) -> None:
         """Registers CLIP-L, CLIP-G and (unless cfg.t5 is None) the T5 encoder on this engine; their tensors then load through
         load_state_dict under the checkpoint's text_encoder. / text_encoder_2. / text_encoder_3. names.  Once per engine."""
@@ -524,6 +541,7 @@ class SD3Engine:
                 t.vocab, t.d_model, t.d_kv, t.heads, t.d_ff, t.layers, t.num_buckets, t.max_distance, t.eps)
         c.joint_dim = cfg.joint_dim
         self.base._check(self.base.lib.pd_sd3_text_configure(self.base._h, C.byref(c)))
+        self.base._shapes = None      # (the registry grew: read_weight / lora_add_ex look names up again)
         self.text_cfg = cfg
 
     def text_weights_missing(self) -> int:
@@ -621,6 +639,7 @@ class SD3Engine:
         c.encoder, c.quant_conv, c.post_quant_conv = int(bool(encoder)), int(cfg.quant_conv), int(cfg.post_quant_conv)
         c.scaling_factor, c.shift_factor = float(cfg.scaling_factor), float(cfg.shift_factor)
         self.base._check(self.base.lib.pd_sd3_vae_configure(self.base._h, C.byref(c)))
+        self.base._shapes = None      # (the registry grew: read_weight / lora_add_ex look names up again)
         self.vae_cfg, self.vae_has_encoder = cfg, bool(encoder)
 
     def vae_weights_missing(self) -> int:
