@@ -409,6 +409,115 @@ int pd_image_load(pd_engine* e, const pd_image_load_args* args);
 int pd_image_store(pd_engine* e, const float* src, int32_t B, int32_t C, int32_t H, int32_t W, int32_t mem_src, float mul, float add,
                    int32_t rounding, uint8_t* dst, int32_t mem_dst);
 
+/* PIL.Image.BICUBIC for the 8-bit resampler: Pillow's bicubic kernel with a = -0.5, support 2 --
+ *   f(t) = ((a + 2) |t| - (a + 3)) t^2 + 1 for |t| < 1, (((|t| - 5) |t| + 8) |t| - 4) a for |t| < 2, else 0
+ * through the same precompute_coeffs / normalize_coeffs_8bpc arithmetic as above.  pd_resample_coefficients and pd_image_load keep
+ * their two filters (and keep refusing 3); pd_resample_coefficients_ex takes LANCZOS, BOX and BICUBIC, same arguments, same tables for
+ * the first two. */
+#define PD_RESAMPLE_BICUBIC 3   /* PIL.Image.BICUBIC */
+int pd_resample_coefficients_ex(int32_t in_size, int32_t out_size, int32_t filter, int32_t* ksize, int32_t* bounds, int32_t* kk);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * CLIP image tower (transformers' CLIPVisionModelWithProjection): what the reference pipeline's image_encoder / encode_image
+ * (pipeline_prompt_diffusion.py:490-513) and safety_checker / run_safety_checker (:514-528) rest on.  Opt-in: an engine that never
+ * calls pd_clip_vision_configure is unchanged.
+ *
+ * pd_clip_preprocess: CLIPImageProcessor() with its defaults on uint8 pictures [B, H, W, 3] --
+ *   1. resize the shortest edge to image_size: (H, W) -> (S, (int)(S * W / H)) for H <= W, ((int)(S * H / W), S) otherwise
+ *      (get_resize_output_image_size; 96 x 160 -> 224 x 373), PIL BICUBIC on uint8, horizontal pass first, its rounded bytes feed the
+ *      vertical pass; 2. centre crop to S x S (top = (Hr - S) / 2, left = (Wr - S) / 2); 3. (v / 255 - mean) / std in fp32, every
+ *      operation rounded once.
+ * Only the columns and rows that survive the crop are resampled.  pd_clip_preprocess_geometry gives (Hr, Wr, top, left); host only.
+ * out_mode:
+ *   PD_CLIP_OUT_PIXEL_VALUES  fp32 [B, 3, S, S]
+ *   PD_CLIP_OUT_PATCHES       the patch GEMM's operand: [B * (S / patch)^2, Kw] in the engine's operand type (fp32 in the fp32-storage
+ *                             modes, else f16 / bf16), Kw = round_up(3 patch^2, 8) = pd_clip_patch_width(patch), element k = c patch^2 +
+ *                             py patch + px of patch row b (S / patch)^2 + ty (S / patch) + tx (the flattened Conv2d weight's order), columns
+ *                             past 3 patch^2 zero.  S must be a multiple of patch.
+ *   PD_CLIP_OUT_BYTES         uint8 [B, S, S, 3]: the resized and cropped picture before normalisation
+ * Reductions beyond PD_RESAMPLE_MAX_SCALE are refused (callers keep their host processor). */
+#define PD_CLIP_OUT_PIXEL_VALUES 0
+#define PD_CLIP_OUT_PATCHES      1
+#define PD_CLIP_OUT_BYTES        2
+typedef struct pd_clip_preprocess_args {
+    const uint8_t* src;       /* [B, H, W, 3] */
+    int32_t B, H, W;
+    int32_t mem_src;          /* PD_MEM_* of src */
+    int32_t image_size;       /* S */
+    int32_t patch;            /* read for PD_CLIP_OUT_PATCHES only */
+    int32_t out_mode;         /* PD_CLIP_OUT_* */
+    int32_t mem_dst;          /* PD_MEM_* of dst */
+    void* dst;
+    float mean[3], std[3];    /* image_mean / image_std (OpenAI's: 0.48145466, 0.4578275, 0.40821073 / 0.26862954, 0.26130258, 0.27577711) */
+    int32_t reserved[4];      /* zero */
+} pd_clip_preprocess_args;
+int pd_clip_preprocess(pd_engine* e, const pd_clip_preprocess_args* args);
+int pd_clip_preprocess_geometry(int32_t H, int32_t W, int32_t image_size, int32_t* Hr, int32_t* Wr, int32_t* top, int32_t* left);
+int pd_clip_patch_width(int32_t patch);
+
+/* The tower.  pd_clip_vision_configure registers one CLIPVisionModelWithProjection on an existing engine (any pd_config) in a registry
+ * group of its own; up to two towers per engine, told apart by `prefix` ("safety_checker.vision_model." and "image_encoder." in a
+ * diffusers checkpoint).  Configuring a prefix again does nothing.  Tensors carry transformers' names under the prefix (its
+ * "pre_layrnorm" spelling included):
+ *   <prefix>vision_model.embeddings.class_embedding [C], ...patch_embedding.weight [C, 3, p, p] (no bias), ...position_embedding.weight
+ *   [P + 1, C], <prefix>vision_model.pre_layrnorm.{weight,bias}, <prefix>vision_model.encoder.layers.N.* (as the text stack),
+ *   <prefix>vision_model.post_layernorm.{weight,bias}, and visual_projection.weight [D, C] next to the outermost "vision_model.":
+ *   "image_encoder.visual_projection.weight", "safety_checker.visual_projection.weight" (a trailing "vision_model." of the prefix is
+ *   dropped for it).
+ * hidden = heads * dh with dh one of the attention kernels' head dims (64: ViT-L/14, 80: ViT-H/14); hidden <= 2048, hidden and ff
+ * multiples of 8; image_size a multiple of patch.  stream_f32 != 0 keeps the residual stream in fp32 in every precision mode (the choice
+ * of the SD3 text encoders; for image_encoder); 0 keeps it in the engine's stream type (the SD1.5 text encoder's; for the safety tower). */
+typedef struct pd_clip_vision_config {
+    int32_t hidden, layers, heads, ff, patch, image_size, proj_dim;
+    int32_t act;              /* PD_CLIP_ACT_* */
+    float eps;                /* layer_norm_eps, 1e-5 */
+    int32_t stream_f32;
+    float mean[3], std[3];    /* of the uint8 input path */
+    char prefix[64];
+    int32_t reserved[4];      /* zero */
+} pd_clip_vision_config;
+int pd_clip_vision_configure(pd_engine* e, const pd_clip_vision_config* cfg);
+int pd_clip_vision_weights_missing(pd_engine* e, const char* prefix);   /* 0 when that prefix is not configured */
+/* One forward pass.  input: uint8 pictures [B, H, W, 3] (PD_CLIP_IN_U8: through pd_clip_preprocess's patch-matrix path, no fp32 picture
+ * is written) or fp32 pixel_values [B, 3, S, S] (PD_CLIP_IN_PIXEL_VALUES; H = W = image_size).  Outputs, each NULL or a buffer in `mem`:
+ *   image_embeds  [B, D]        visual_projection(pooler_output)
+ *   pooler_output [B, C]        post_layernorm(last_hidden_state[:, 0])
+ *   hidden        [B, P + 1, C] hidden_states[hidden_layer]: 0 = the output of pre_layrnorm, k = after k blocks, negative values count
+ *                               from the end (-1 = after the last block, -2 = encode_image's); never through post_layernorm. */
+#define PD_CLIP_IN_U8           0
+#define PD_CLIP_IN_PIXEL_VALUES 1
+typedef struct pd_clip_vision_args {
+    const char* prefix;
+    const void* input;
+    int32_t input_kind;       /* PD_CLIP_IN_* */
+    int32_t B, H, W;
+    int32_t mem;              /* PD_MEM_* of input and of every output */
+    int32_t hidden_layer;     /* read when hidden != NULL */
+    float* image_embeds;
+    float* pooler_output;
+    float* hidden;
+    int64_t reserved[2];      /* zero */
+} pd_clip_vision_args;
+int pd_clip_vision_forward(pd_engine* e, const pd_clip_vision_args* args);
+
+/* Safety checker: diffusers' StableDiffusionSafetyChecker.forward on the image_embeds of the tower under "safety_checker.vision_model."
+ * (which must be configured first).  pd_safety_configure registers, in a group of its own, safety_checker.concept_embeds [17, D],
+ * safety_checker.special_care_embeds [3, D], safety_checker.concept_embeds_weights [17], safety_checker.special_care_embeds_weights [3].
+ * pd_safety_check, everything in fp32, one block per image: cosines of the L2-normalised embedding against the L2-normalised rows;
+ * adj = 0; for the special-care rows j = 0, 1, 2 in order: s = cos - thr_j + adj, and adj becomes 0.01 once an s counts as positive
+ * (carried into the later rows, as diffusers' loop does); then for the 17 concept rows s = cos - thr_j + adj; flag = any concept score
+ * positive.  diffusers rounds with Python's round(s, 3) before `> 0`: a score is positive iff it exceeds 0.0005 (no fp32 value equals
+ * that boundary).  embeds [B, D] and flags int32 [B] live in `mem`; scores (NULL, or [B, 20] = 3 special then 17 concept, unrounded) too.
+ * pd_safety_blank writes `value` over every element of the flagged images of a DEVICE batch [B][per_image] fp32 (flags in mem_flags):
+ * 0 is what the checker itself writes; a caller whose pd_image_store denormalises with (mul, add) passes -add / mul so that the
+ * stored picture is black, which is what the reference's postprocess(do_denormalize = [not nsfw]) makes of the zeroed image. */
+#define PD_SAFETY_CONCEPTS 17
+#define PD_SAFETY_SPECIAL  3
+int pd_safety_configure(pd_engine* e);
+int pd_safety_weights_missing(pd_engine* e);   /* 0 when not configured */
+int pd_safety_check(pd_engine* e, const float* embeds, int32_t B, int32_t mem, int32_t* flags, float* scores);
+int pd_safety_blank(pd_engine* e, float* images, int32_t B, int64_t per_image, const int32_t* flags, int32_t mem_flags, float value);
+
 /* Canny edge detector: the annotator of the reference's `canny` task (annotator/canny/__init__.py: cv2.Canny(img, low, high), called
  * with 100 and 200).  It has no weights and every step is integer arithmetic, so the result is pinned byte for byte -- to a
  * restatement of OpenCV's portable C++ path (canny.cpp, aperture 3, L2gradient = false), which tests/canny_ref.py states in NumPy:

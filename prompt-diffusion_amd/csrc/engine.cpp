@@ -1100,11 +1100,11 @@ int pd_engine::conv_gn(const ConvW& c, const Act& x, Act& out, const float* g, c
     return 0;
 }
 
-int pd_engine::layernorm(const Act& x, Act& y, const float* g, const float* b) {
+int pd_engine::layernorm(const Act& x, Act& y, const float* g, const float* b, float eps) {
     if (arena.dry) return 0;
     PD_TRY(check_arena());
     ++launches;
-    if (launch_layernorm(x.p, x.dt, y.p, y.dt, g, b, (int)x.rows(), x.C, 1e-5f, stream)) {
+    if (launch_layernorm(x.p, x.dt, y.p, y.dt, g, b, (int)x.rows(), x.C, eps, stream)) {
         pd_set_error("layernorm launch failed (C=%d)", x.C);
         return 1;
     }

@@ -18,6 +18,8 @@ void pd_host_timestep_embedding_f(const double* t, int n, int dim, std::vector<f
 // rows [n_rows][PD_LMS_NCOEF] and the model time of every row for a linear multistep loop over n steps (multistep.cpp)
 int pd_lms_table(const pd_config& cfg, const pd_lms_args& u, const int64_t* ts, int n, std::vector<double>& rows, std::vector<double>& times);
 // coefficient rows [n][PD_UNIPC_NCOEF] of the fused UniPC loop (multistep.cpp; pd_unipc_coefficients)
+// bounds [out_size][2] and kk [out_size][*ksize] of one axis (image_host.cpp; LANCZOS, BOX or BICUBIC); non-zero with the error set on a refusal
+int pd_resample_axis(int in_size, int out_size, int filter, int* ksize, std::vector<int32_t>& bounds, std::vector<int32_t>& kk);
 int pd_unipc_table(const pd_config& cfg, const pd_unipc_args& u, const int64_t* ts, int n, std::vector<double>& coef);
 
 #define HIP_OK(expr)                                                                            \
@@ -241,10 +243,33 @@ struct ClipW {
     int proj_dim = 0;                      // rows of text_projection.weight; 0: no projection head (SD1.5)
     int eos_token_id = 0;                  // pooled row (pd_sd3_clip_config)
     Activation act = ACT_QUICK_GELU;       // of the MLP
+    bool causal = true;                    // the text encoders' mask; false in the image tower (clip_vision.cpp)
+    float eps = 1e-5f;                     // layer_norm_eps of the blocks
     WMat tok, pos, proj;
     std::vector<TextLayerW> layers;        // sized by the caller of build_clip, never resized again (Params point into it)
     float *fln_g = nullptr, *fln_b = nullptr;
 };
+// CLIP image tower (clip_vision.cpp; pd_clip_vision_configure): the text stack's blocks without the mask, behind a patch embedding.
+// t carries the blocks, post_layernorm (fln_*) and visual_projection (proj); t.positions = P + 1
+struct ClipVisionW {
+    bool built = false;
+    bool broken = false;                   // a weight allocation failed while it was registered: the slot is taken, every use is refused
+    std::string prefix;
+    pd_clip_vision_config c{};
+    ClipW t;
+    WMat patch;                            // patch_embedding.weight [C][3 p p] as a linear layer over the patch matrix (no bias)
+    float *cls = nullptr, *pos = nullptr;  // class_embedding [C], position_embedding.weight [P + 1][C], fp32
+    float *pre_g = nullptr, *pre_b = nullptr;
+    int patches = 0;                       // P = (image_size / patch)^2
+    int group = 0;                         // WeightGroup
+};
+// StableDiffusionSafetyChecker's buffers (pd_safety_configure), fp32
+struct SafetyW {
+    bool built = false, broken = false;    // broken: as ClipVisionW's
+    int D = 0;
+    float *cpt = nullptr, *spc = nullptr, *cpt_thr = nullptr, *spc_thr = nullptr;   // concept / special-care rows and thresholds
+};
+
 // SD3's T5 encoder stack (sd3_text.cpp): no biases anywhere, RMSNorm weights only, wi = [wi_1 | wi_0] packed like a GEGLU matrix
 struct T5LayerW {
     float *ln1 = nullptr, *ln2 = nullptr;
@@ -296,6 +321,9 @@ enum WeightGroup {
     GROUP_SD3_VAE = 7,       // SD3's VAE decoder
     GROUP_SD3_VAE_ENCODER = 8,
     GROUP_MLSD = 9,
+    GROUP_CLIP_VISION_0 = 10,   // the two image towers, one group each
+    GROUP_CLIP_VISION_1 = 11,
+    GROUP_SAFETY = 12,
 };
 
 struct Param {
@@ -608,11 +636,12 @@ struct pd_engine {
     // CLIP text stack (text.cpp).  build_clip registers one CLIPTextModel under `prefix` (its "text_model."); the caller has filled the
     // dimensions and sized w.layers.  clip_blocks runs blocks [first, last) on the residual stream x, whose type the block's sums follow.
     void build_clip(const std::string& prefix, ClipW& w);
+    void build_clip_layers(const std::string& prefix, ClipW& w);   // "encoder.layers.N.*" alone (the image tower has other embeddings)
     void build_text();
     int clip_embed(const ClipW& w, const int* ids_dev, Act& x);
     // att (allocated here) = attention over q | k and V^T of ln, projected by `qkv` [3 * inner rows]; relbias / scale as in attention()
     int self_attention(const WMat& qkv, const Act& ln, int inner, int heads, bool causal, const float* relbias, float scale, Act& att);
-    int clip_block(const TextLayerW& l, Act& x, int heads, Activation act);
+    int clip_block(const TextLayerW& l, Act& x, int heads, Activation act, bool causal, float eps = 1e-5f);
     int clip_blocks(const ClipW& w, int first, int last, Act& x);
     int text_forward(const int* ids_dev, int B, float* out_dev, int clip_skip);
     // token ids (int32, `mem` space) -> a workspace allocation; fp32 results back to the caller's `mem` space (both on the main stream)
@@ -655,6 +684,20 @@ struct pd_engine {
     long long canny_sweeps = 0;                 // stat "canny_sweeps": hysteresis launches of the last call
     // sweeps the device map [B][H][W] to its fixed point: at most B * H * W + 1 launches, else an error
     int canny_hysteresis(uint8_t* states_dev, int B, int H, int W);
+
+    // CLIP image tower and safety checker (clip_vision.cpp, clip_vision.hip)
+    ClipVisionW clip_vision[2];
+    SafetyW safety;
+    ImageBuf clip_tmp;     // the picture between the two passes of the preprocessing (crop columns only)
+    ImageBuf clip_tab;     // its tables, crop rows / columns only: bounds_h | kk_h | bounds_v | kk_v
+    ImageBuf clip_out;     // staging of a host destination
+    std::vector<int32_t> clip_tab_host;
+    int32_t clip_tab_key[3] = {0, 0, 0};   // (H, W, image_size) the device tables hold now
+    ClipVisionW* find_clip_vision(const char* prefix);
+    // src_dev [B][H][W][3] u8 -> dst_dev in `mode` (PD_CLIP_OUT_*; patches in T); everything on `stream`, nothing synchronised
+    int clip_preprocess_dev(const uint8_t* src_dev, int B, int H, int W, int S, int patch, const float* mean, const float* stdv, int mode, void* dst_dev);
+    // patches [B * P][Kw] in T -> hidden_states[k] [B][P + 1][C], pooler_output [B][C], image_embeds [B][D] (fp32, device; null: not wanted)
+    int clip_vision_forward(ClipVisionW& v, const void* patches_dev, int B, int k, float* hid_dev, float* pooled_dev, float* embeds_dev);
 
     // SD3 / MMDiT path (sd3.cpp)
     pd_sd3_config sd3{};
@@ -763,7 +806,7 @@ struct pd_engine {
     int conv_gn(const ConvW& c, const Act& x, Act& out, const float* g, const float* b, float eps, bool silu, GemmCall call = {},
                 const SlabDefer* in_slabs = nullptr);
     int groupnorm(const Act& x, Act& y, const float* g, const float* b, float eps, bool silu, const SlabDefer* from_slabs = nullptr);
-    int layernorm(const Act& x, Act& y, const float* g, const float* b);
+    int layernorm(const Act& x, Act& y, const float* g, const float* b, float eps = 1e-5f);
     int resblock(const ResW& r, const Act& x, Act& out, const float* embrow, int emb_stride);
     int transformer(const STW& s, const Act& x, Act& out, const KVSlot& kv, int out_B = 0);
     int repeat_act(const Act& src, int reps, Act& dst);

@@ -14,13 +14,26 @@ double sinc_filter(double x) {
 }
 double lanczos_filter(double x) { return (-3.0 <= x && x < 3.0) ? sinc_filter(x) * sinc_filter(x / 3) : 0.0; }
 double box_filter(double x) { return (x > -0.5 && x <= 0.5) ? 1.0 : 0.0; }
+double bicubic_filter(double x) {   // Pillow's: a = -0.5
+    const double a = -0.5;
+    if (x < 0.0) x = -x;
+    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+    return 0.0;
+}
 
 // support of the filter, or 0 for an unknown one
-double filter_support(int filter) { return filter == PD_RESAMPLE_LANCZOS ? 3.0 : filter == PD_RESAMPLE_BOX ? 0.5 : 0.0; }
+double filter_support(int filter) {
+    return filter == PD_RESAMPLE_LANCZOS ? 3.0 : filter == PD_RESAMPLE_BOX ? 0.5 : filter == PD_RESAMPLE_BICUBIC ? 2.0 : 0.0;
+}
 
-int check_axis(int in_size, int out_size, int filter) {
+// bicubic: PD_RESAMPLE_BICUBIC is accepted too (pd_resample_coefficients_ex and the CLIP preprocessing; the older entries keep their two)
+int check_axis(int in_size, int out_size, int filter, bool bicubic = false) {
     if (in_size < 1 || out_size < 1) { pd_set_error("resample: sizes must be >= 1 (got %d -> %d)", in_size, out_size); return 1; }
-    if (filter_support(filter) == 0.0) { pd_set_error("resample: unknown filter %d (PD_RESAMPLE_LANCZOS / PD_RESAMPLE_BOX)", filter); return 1; }
+    if (filter_support(filter) == 0.0 || (filter == PD_RESAMPLE_BICUBIC && !bicubic)) {
+        pd_set_error("resample: unknown filter %d (PD_RESAMPLE_LANCZOS / PD_RESAMPLE_BOX)", filter);
+        return 1;
+    }
     if ((long long)in_size > (long long)PD_RESAMPLE_MAX_SCALE * out_size) {
         pd_set_error("resample: %d -> %d reduces by more than PD_RESAMPLE_MAX_SCALE = %d", in_size, out_size, PD_RESAMPLE_MAX_SCALE);
         return 1;
@@ -36,7 +49,7 @@ int axis_ksize(int in_size, int out_size, int filter) {
 
 // Resample.c: precompute_coeffs + normalize_coeffs_8bpc
 void axis_tables(int in_size, int out_size, int filter, int ksize, int32_t* bounds, int32_t* kk) {
-    double (*f)(double) = filter == PD_RESAMPLE_LANCZOS ? lanczos_filter : box_filter;
+    double (*f)(double) = filter == PD_RESAMPLE_LANCZOS ? lanczos_filter : filter == PD_RESAMPLE_BICUBIC ? bicubic_filter : box_filter;
     const double scale = (double)in_size / out_size;
     const double fs = scale < 1.0 ? 1.0 : scale;
     const double support = filter_support(filter) * fs;
@@ -75,6 +88,23 @@ extern "C" int pd_resample_coefficients(int32_t in_size, int32_t out_size, int32
     return 0;
 }
 
+extern "C" int pd_resample_coefficients_ex(int32_t in_size, int32_t out_size, int32_t filter, int32_t* ksize, int32_t* bounds, int32_t* kk) {
+    if (!ksize || (bounds == nullptr) != (kk == nullptr)) { pd_set_error("pd_resample_coefficients_ex: bad argument"); return 1; }
+    PD_TRY(check_axis(in_size, out_size, filter, true));
+    *ksize = axis_ksize(in_size, out_size, filter);
+    if (bounds) axis_tables(in_size, out_size, filter, *ksize, bounds, kk);
+    return 0;
+}
+
+int pd_resample_axis(int in_size, int out_size, int filter, int* ksize, std::vector<int32_t>& bounds, std::vector<int32_t>& kk) {
+    PD_TRY(check_axis(in_size, out_size, filter, true));
+    *ksize = axis_ksize(in_size, out_size, filter);
+    bounds.assign((size_t)2 * out_size, 0);
+    kk.assign((size_t)*ksize * out_size, 0);
+    axis_tables(in_size, out_size, filter, *ksize, bounds.data(), kk.data());
+    return 0;
+}
+
 int pd_engine::image_grow(ImageBuf& b, size_t bytes) {
     if (bytes <= b.cap) return 0;
     // (nothing of an earlier call is in flight: every image call synchronises the stream before it returns)
@@ -86,7 +116,7 @@ int pd_engine::image_grow(ImageBuf& b, size_t bytes) {
 }
 
 void pd_engine::image_release() {
-    for (ImageBuf* b : {&img_u8, &img_tmp, &img_f32, &img_tab, &canny_states, &canny_flags})
+    for (ImageBuf* b : {&img_u8, &img_tmp, &img_f32, &img_tab, &canny_states, &canny_flags, &clip_tmp, &clip_tab, &clip_out})
         if (b->p) { (void)hipFree(b->p); b->p = nullptr; b->cap = 0; }
     if (canny_flags_host) { (void)hipHostFree(canny_flags_host); canny_flags_host = nullptr; }
 }

@@ -502,6 +502,29 @@ int launch_image_vpass(const uint8_t* src, float* dst, const int* bounds, const 
                        int C, int c_off, int tile, float mul, float add, hipStream_t s);
 // src [B][C][H][W] fp32, C in {1, 3} -> dst [B][H][W][C] u8 = round(min(max(x * mul + add, 0), 1) * 255), half to even or truncated
 int launch_image_store(const float* src, uint8_t* dst, int B, int C, int H, int W, float mul, float add, int trunc, hipStream_t s);
+// clip_vision.hip: the CLIP image tower's preprocessing and embedding kernels and the safety checker (clip_vision.cpp; include/pdengine.h
+// "CLIP image tower").  Output modes: PD_CLIP_OUT_*; rows of the checker: PD_SAFETY_SPECIAL, then PD_SAFETY_CONCEPTS
+constexpr int CLIPV_OUT_PIXEL_VALUES = 0, CLIPV_OUT_PATCHES = 1, CLIPV_OUT_BYTES = 2;
+constexpr int SAFETY_SPECIAL = 3, SAFETY_CONCEPTS = 17;
+// Pillow's horizontal pass over crop columns only: src [B][H][W][3] u8, rows r0 .. r0 + Hn - 1 of every image -> tmp [B][Hn][S][3] u8;
+// bounds [S][2] / kk [S][ksize]: the crop columns' rows of the axis tables
+int launch_clipv_hpass(const uint8_t* src, uint8_t* tmp, const int* bounds, const int* kk, int ksize, int B, int H, int W, int r0, int Hn,
+                       int S, hipStream_t s);
+// in [B][Hin][Win][3] u8 -> the S x S crop in `mode`: fp32 [B][3][S][S] of (v / 255 - mean) / std, the patch operand rows
+// [B (S / patch)^2][round_up(3 patch^2, 8)] in dt (element c patch^2 + py patch + px, pad columns zero), or the bytes [B][S][S][3].  Crop
+// column x is in's column x_off + x.  bounds non-null: the vertical pass first (bounds [S][2] / kk [S][ksize] of the crop rows, in source
+// rows; in's row 0 is source row row_off); else crop row y is in's row row_off + y
+int launch_clipv_vpass(const uint8_t* in, void* dst, int mode, int dt, const int* bounds, const int* kk, int ksize, int B, int S, int Hin,
+                       int Win, int x_off, int row_off, int patch, const float* mean, const float* sd, hipStream_t s);
+int launch_clipv_patchify(const float* pv, void* out, int out_dt, int B, int S, int patch, hipStream_t s);   // fp32 [B][3][S][S] -> operand rows
+// x [B][P + 1][C] fp32: row 0 = cls + pos[0], row 1 + t = patches[b P + t] + pos[1 + t]; C % 4 == 0
+int launch_clipv_embed(const float* patches, const float* cls, const float* pos, float* x, int B, int P, int C, hipStream_t s);
+// out [B][rows_out][C] fp32 = the first rows_out rows of every sample of x [B][L][C] (dt)
+int launch_clipv_rows(const void* x, int dt, float* out, int B, int L, int C, int rows_out, hipStream_t s);
+// StableDiffusionSafetyChecker.forward on embeds [B][D]: flags [B], scores [B][20] or null; everything fp32
+int launch_safety_check(const float* embeds, const float* special, const float* cpt, const float* special_thr, const float* cpt_thr, int B,
+                        int D, int* flags, float* scores, hipStream_t s);
+int launch_safety_blank(float* images, const int* flags, int B, long long per, float value, hipStream_t s);   // images [B][per] = value where flags[b]
 // canny.hip: the Canny edge detector (canny.cpp; include/pdengine.h "Canny edge detector").  States: PD_CANNY_NONE / WEAK / STRONG
 constexpr int CANNY_NONE = 0, CANNY_WEAK = 1, CANNY_STRONG = 2;
 // src [B][H][W][C] u8, C in {1, 3} -> states [B][H][W] u8: Sobel, channel select and non-maximum suppression; lo <= hi, both strict

@@ -15,11 +15,19 @@
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 void pd_engine::build_clip(const std::string& P, ClipW& t) {
-    const int C = t.hidden, F = t.ff, L = t.positions;
+    const int C = t.hidden, L = t.positions;
     make_mat(t.tok, t.vocab, C, 1, C, false);
     reg_mat(P + "embeddings.token_embedding.weight", {t.vocab, C}, &t.tok, 0, false);
     make_mat(t.pos, L, C, 1, C, false);
     reg_mat(P + "embeddings.position_embedding.weight", {L, C}, &t.pos, 0, false);
+    build_clip_layers(P, t);
+    reg_vec(P + "final_layer_norm.weight", C, &t.fln_g, 'g');
+    reg_vec(P + "final_layer_norm.bias", C, &t.fln_b, 'e');
+    t.built = true;
+}
+
+void pd_engine::build_clip_layers(const std::string& P, ClipW& t) {
+    const int C = t.hidden, F = t.ff;
     for (size_t i = 0; i < t.layers.size(); ++i) {
         TextLayerW& l = t.layers[i];
         const std::string Lp = P + "encoder.layers." + std::to_string(i) + ".";
@@ -44,9 +52,6 @@ void pd_engine::build_clip(const std::string& P, ClipW& t) {
         reg_vec(Lp + "layer_norm2.weight", C, &l.ln2_g, 'g');
         reg_vec(Lp + "layer_norm2.bias", C, &l.ln2_b, 'e');
     }
-    reg_vec(P + "final_layer_norm.weight", C, &t.fln_g, 'g');
-    reg_vec(P + "final_layer_norm.bias", C, &t.fln_b, 'e');
-    t.built = true;
 }
 
 void pd_engine::build_text() {
@@ -82,15 +87,15 @@ int pd_engine::self_attention(const WMat& qkv, const Act& ln, int inner, int hea
     return attention(qk.p, 2 * inner, K, 2 * inner, vt.p, lpad, att.p, inner, B, L, L, inner, heads, causal, 0, 0, 0, relbias, scale);
 }
 
-int pd_engine::clip_block(const TextLayerW& l, Act& x, int heads, Activation act) {
+int pd_engine::clip_block(const TextLayerW& l, Act& x, int heads, Activation act, bool causal, float eps) {
     const int B = x.B, L = x.H, C = x.C;
     const size_t mk = arena.mark();
     Act ln = new_act(B, L, 1, C, T), att;
-    PD_TRY(layernorm(x, ln, l.ln1_g, l.ln1_b));
-    PD_TRY(self_attention(l.qkv, ln, C, heads, /*causal=*/true, nullptr, 0.f, att));
+    PD_TRY(layernorm(x, ln, l.ln1_g, l.ln1_b, eps));
+    PD_TRY(self_attention(l.qkv, ln, C, heads, causal, nullptr, 0.f, att));
     Act h1 = new_act(B, L, 1, C, x.dt);
     PD_TRY(gemm(l.out, att, h1, {.R = &x}));
-    PD_TRY(layernorm(h1, ln, l.ln2_g, l.ln2_b));
+    PD_TRY(layernorm(h1, ln, l.ln2_g, l.ln2_b, eps));
     Act f = new_act(B, L, 1, l.fc1.Nout, T);
     PD_TRY(gemm(l.fc1, ln, f, {.act = act}));
     Act h2 = new_act(B, L, 1, C, x.dt);
@@ -102,7 +107,7 @@ int pd_engine::clip_block(const TextLayerW& l, Act& x, int heads, Activation act
 }
 
 int pd_engine::clip_blocks(const ClipW& t, int first, int last, Act& x) {
-    for (int li = first; li < last; ++li) PD_TRY(clip_block(t.layers[li], x, t.heads, t.act));
+    for (int li = first; li < last; ++li) PD_TRY(clip_block(t.layers[li], x, t.heads, t.act, t.causal, t.eps));
     return 0;
 }
 

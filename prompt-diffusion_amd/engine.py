@@ -14,7 +14,8 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .weights import ModelConfig, SD15, fold_mlsd_state_dict, hed_key
+from .weights import (CLIP_VIT_H14, CLIP_VIT_L14_SAFETY, IMAGE_ENCODER_PREFIX, SAFETY_PREFIX, ClipVisionConfig, ModelConfig, SD15,  # noqa: F401
+                      clip_vision_param_shapes, fold_mlsd_state_dict, hed_key, safety_param_shapes)
 
 PD_PREC_BF16, PD_PREC_F32, PD_PREC_F16, PD_PREC_F16X2 = 0, 1, 2, 3
 PRECISIONS = {"bf16": PD_PREC_BF16, "f32": PD_PREC_F32, "fp32": PD_PREC_F32, "f16": PD_PREC_F16, "fp16": PD_PREC_F16,
@@ -33,6 +34,17 @@ MLSD_TOPK = 200
 PD_RESAMPLE_LANCZOS, PD_RESAMPLE_BOX = 1, 4
 PD_RESAMPLE_MAX_SCALE = 8
 RESAMPLE_FILTERS = {"lanczos": PD_RESAMPLE_LANCZOS, "box": PD_RESAMPLE_BOX}
+# ... plus PIL.Image.BICUBIC, for pd_resample_coefficients_ex and the CLIP preprocessing only (pd_image_load keeps its two)
+PD_RESAMPLE_BICUBIC = 3
+RESAMPLE_FILTERS_EX = dict(RESAMPLE_FILTERS, bicubic=PD_RESAMPLE_BICUBIC)
+# CLIP image tower (include/pdengine.h, "CLIP image tower")
+PD_CLIP_OUT_PIXEL_VALUES, PD_CLIP_OUT_PATCHES, PD_CLIP_OUT_BYTES = 0, 1, 2
+CLIP_PREPROCESS_OUTPUTS = {"pixel_values": PD_CLIP_OUT_PIXEL_VALUES, "patches": PD_CLIP_OUT_PATCHES, "bytes": PD_CLIP_OUT_BYTES}
+PD_CLIP_IN_U8, PD_CLIP_IN_PIXEL_VALUES = 0, 1
+PD_CLIP_ACT_QUICK_GELU, PD_CLIP_ACT_GELU = 0, 1
+CLIP_ACTS = {"quick_gelu": PD_CLIP_ACT_QUICK_GELU, "gelu": PD_CLIP_ACT_GELU}
+CLIP_VISION_OUTPUTS = ("embeds", "pooled", "hidden")
+PD_SAFETY_CONCEPTS, PD_SAFETY_SPECIAL = 17, 3
 PD_IMAGE_REPEAT, PD_IMAGE_TILE = 0, 1
 IMAGE_BATCH_MODES = {"repeat": PD_IMAGE_REPEAT, "tile": PD_IMAGE_TILE}
 PD_ROUND_NEAREST_EVEN, PD_ROUND_TRUNC = 0, 1
@@ -108,6 +120,26 @@ class pd_image_load_args(C.Structure):
         ("mem_dst", C.c_int32), ("filter", C.c_int32), ("batch_mode", C.c_int32), ("mul", C.c_float), ("add", C.c_float),
         ("reserved", C.c_int32 * 4),
     ]
+
+
+class pd_clip_preprocess_args(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("mem_src", C.c_int32), ("image_size", C.c_int32),
+        ("patch", C.c_int32), ("out_mode", C.c_int32), ("mem_dst", C.c_int32), ("dst", C.c_void_p), ("mean", C.c_float * 3),
+        ("std", C.c_float * 3), ("reserved", C.c_int32 * 4),
+    ]
+
+
+class pd_clip_vision_config(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("hidden", "layers", "heads", "ff", "patch", "image_size", "proj_dim", "act")] + \
+               [("eps", C.c_float), ("stream_f32", C.c_int32), ("mean", C.c_float * 3), ("std", C.c_float * 3), ("prefix", C.c_char * 64),
+                ("reserved", C.c_int32 * 4)]
+
+
+class pd_clip_vision_args(C.Structure):
+    _fields_ = [("prefix", C.c_char_p), ("input", C.c_void_p)] + \
+               [(n, C.c_int32) for n in ("input_kind", "B", "H", "W", "mem", "hidden_layer")] + \
+               [("image_embeds", C.c_void_p), ("pooler_output", C.c_void_p), ("hidden", C.c_void_p), ("reserved", C.c_int64 * 2)]
 
 
 class pd_mlsd_args(C.Structure):
@@ -293,6 +325,18 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.pd_randn.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_void_p]
     lib.pd_resample_coefficients.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]
     lib.pd_image_load.argtypes = [C.c_void_p, C.POINTER(pd_image_load_args)]
+    if hasattr(lib, "pd_clip_vision_configure"):   # (an older build handed in through PDENGINE_LIB for an A/B run lacks the image tower)
+        lib.pd_resample_coefficients_ex.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]
+        lib.pd_clip_preprocess.argtypes = [C.c_void_p, C.POINTER(pd_clip_preprocess_args)]
+        lib.pd_clip_preprocess_geometry.argtypes = [C.c_int32] * 3 + [C.POINTER(C.c_int32)] * 4
+        lib.pd_clip_patch_width.argtypes = [C.c_int32]
+        lib.pd_clip_vision_configure.argtypes = [C.c_void_p, C.POINTER(pd_clip_vision_config)]
+        lib.pd_clip_vision_weights_missing.argtypes = [C.c_void_p, C.c_char_p]
+        lib.pd_clip_vision_forward.argtypes = [C.c_void_p, C.POINTER(pd_clip_vision_args)]
+        lib.pd_safety_configure.argtypes = [C.c_void_p]
+        lib.pd_safety_weights_missing.argtypes = [C.c_void_p]
+        lib.pd_safety_check.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+        lib.pd_safety_blank.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_float]
     lib.pd_image_store.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_int32]
     lib.pd_canny.argtypes = [C.c_void_p, C.POINTER(pd_canny_args)]
     lib.pd_op_canny_hysteresis.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
@@ -332,6 +376,8 @@ EXPORTS = [
     "pd_op_mlsd_decode", "pd_op_draw_lines",
     "pd_resample_coefficients", "pd_image_load", "pd_image_store", "pd_canny", "pd_op_canny_hysteresis",
     "pd_sd3_text_configure", "pd_sd3_text_weights_missing", "pd_sd3_encode_prompt", "pd_sd3_text_encoder", "pd_t5_relative_buckets",
+    "pd_resample_coefficients_ex", "pd_clip_preprocess", "pd_clip_preprocess_geometry", "pd_clip_patch_width", "pd_clip_vision_configure",
+    "pd_clip_vision_weights_missing", "pd_clip_vision_forward", "pd_safety_configure", "pd_safety_weights_missing", "pd_safety_check", "pd_safety_blank",
     "pd_sd3_vae_configure", "pd_sd3_vae_weights_missing", "pd_sd3_vae_config_layout", "pd_sd3_vae_decode", "pd_sd3_vae_encode", "pd_op_vae_attention", "pd_bench_vae_attention",
 ]
 
@@ -400,6 +446,41 @@ def resample_coefficients(in_size: int, out_size: int, filter="lanczos") -> Tupl
     if lib.pd_resample_coefficients(int(in_size), int(out_size), _filter_code(filter), C.byref(ks), bounds.ctypes.data, kk.ctypes.data):
         raise PdError(lib.pd_last_error().decode(errors="replace"))
     return bounds, kk
+
+
+def resample_coefficients_ex(in_size: int, out_size: int, filter="bicubic") -> Tuple[np.ndarray, np.ndarray]:
+    """resample_coefficients with PIL.Image.BICUBIC accepted as well (pd_resample_coefficients_ex): "lanczos" / "box" / "bicubic" or
+    PIL's number; the same tables as resample_coefficients for the first two."""
+    lib = load_library()
+    code = RESAMPLE_FILTERS_EX[filter] if isinstance(filter, str) else int(filter)
+    ks = C.c_int32()
+    if lib.pd_resample_coefficients_ex(int(in_size), int(out_size), code, C.byref(ks), None, None):
+        raise PdError(lib.pd_last_error().decode(errors="replace"))
+    bounds = np.zeros((int(out_size), 2), np.int32)
+    kk = np.zeros((int(out_size), ks.value), np.int32)
+    if lib.pd_resample_coefficients_ex(int(in_size), int(out_size), code, C.byref(ks), bounds.ctypes.data, kk.ctypes.data):
+        raise PdError(lib.pd_last_error().decode(errors="replace"))
+    return bounds, kk
+
+
+def clip_preprocess_geometry(H: int, W: int, image_size: int = 224) -> Tuple[int, int, int, int]:
+    """(Hr, Wr, top, left) of CLIPImageProcessor's shortest-edge resize and centre crop (pd_clip_preprocess_geometry; host only)."""
+    lib = load_library()
+    v = [C.c_int32() for _ in range(4)]
+    if lib.pd_clip_preprocess_geometry(int(H), int(W), int(image_size), *[C.byref(x) for x in v]):
+        raise PdError(lib.pd_last_error().decode(errors="replace"))
+    return tuple(int(x.value) for x in v)
+
+
+def clip_patch_width(patch: int) -> int:
+    """Row width of the patch GEMM's operand: 3 patch^2 rounded up to 8 (pd_clip_patch_width)."""
+    return int(load_library().pd_clip_patch_width(int(patch)))
+
+
+def clip_preprocess_supported(H: int, W: int, image_size: int = 224) -> bool:
+    """Whether pd_clip_preprocess takes H x W pictures (no axis reduced beyond PD_RESAMPLE_MAX_SCALE); else keep the host processor."""
+    Hr, Wr, _, _ = clip_preprocess_geometry(H, W, image_size)
+    return resample_supported((H, W), (Hr, Wr))
 
 
 def resample_supported(src_hw, dst_hw) -> bool:
@@ -577,6 +658,11 @@ class Engine:
             self._check(self.lib.pd_hed_configure(self._h))
         if getattr(cfg, "mlsd", False):
             self._check(self.lib.pd_mlsd_configure(self._h))
+        self._clip_vision: Dict[str, ClipVisionConfig] = {}
+        for cv in getattr(cfg, "clip_vision", ()) or ():
+            self.configure_clip_vision(cv)
+        if getattr(cfg, "safety_checker", False):
+            self.configure_safety_checker()
         self._keep: List[_Buf] = []
         self._rng_set = False    # the caller has chosen a seed (set_rng): draws nobody supplied may come from the engine
 
@@ -946,6 +1032,203 @@ class Engine:
         self._order_after_torch(b.mem)
         self._check(self.lib.pd_hed_detect(self._h, b.ptr, B, H, W, b.mem, HED_OUTPUTS[what], op))
         return out
+
+    # ------------------------------------------------------------------ CLIP image tower and safety checker (pd_clip_*, pd_safety_*)
+    def configure_clip_vision(self, cfg: ClipVisionConfig = CLIP_VIT_H14, prefix: Optional[str] = None) -> None:
+        """Register one CLIPVisionModelWithProjection under `prefix` (default: cfg.prefix) -- "image_encoder." or
+        "safety_checker.vision_model." in a diffusers checkpoint; at most two per engine; configuring a prefix again does nothing."""
+        import dataclasses
+        if prefix is not None and prefix != cfg.prefix:
+            cfg = dataclasses.replace(cfg, prefix=prefix)
+        if cfg.act not in CLIP_ACTS:
+            raise ValueError(f"act must be one of {sorted(CLIP_ACTS)}")
+        if len(cfg.prefix.encode()) > 63:
+            raise ValueError("prefix longer than 63 bytes")
+        c = pd_clip_vision_config()
+        c.hidden, c.layers, c.heads, c.ff, c.patch, c.image_size, c.proj_dim = (int(v) for v in (
+            cfg.hidden, cfg.layers, cfg.heads, cfg.ff, cfg.patch, cfg.image_size, cfg.proj_dim))
+        c.act, c.eps, c.stream_f32 = CLIP_ACTS[cfg.act], float(cfg.eps), int(bool(cfg.stream_f32))
+        c.mean = (C.c_float * 3)(*cfg.mean)
+        c.std = (C.c_float * 3)(*cfg.std)
+        c.prefix = cfg.prefix.encode()
+        self._check(self.lib.pd_clip_vision_configure(self._h, C.byref(c)))
+        self._clip_vision.setdefault(cfg.prefix, cfg)
+        self._shapes = None
+
+    def configure_safety_checker(self, cfg: ClipVisionConfig = CLIP_VIT_L14_SAFETY) -> None:
+        """The safety tower (if not there yet) and StableDiffusionSafetyChecker's four buffers (pd_safety_configure)."""
+        if SAFETY_PREFIX not in self._clip_vision:
+            self.configure_clip_vision(cfg, SAFETY_PREFIX)
+        self._check(self.lib.pd_safety_configure(self._h))
+        self._shapes = None
+
+    def _clip_prefix(self, prefix: Optional[str]) -> str:
+        if prefix is None:
+            if len(self._clip_vision) != 1:
+                raise PdError("clip_vision: name the tower (prefix=...): this engine has " + (f"{len(self._clip_vision)}" if self._clip_vision else "none"))
+            return next(iter(self._clip_vision))
+        if prefix not in self._clip_vision:
+            raise PdError(f"clip_vision: no image tower under '{prefix}' (configure_clip_vision)")
+        return prefix
+
+    def clip_vision_weights_missing(self, prefix: Optional[str] = None) -> int:
+        return int(self.lib.pd_clip_vision_weights_missing(self._h, self._clip_prefix(prefix).encode()))
+
+    def safety_weights_missing(self) -> int:
+        return int(self.lib.pd_safety_weights_missing(self._h))
+
+    def load_clip_vision_state_dict(self, sd, prefix: Optional[str] = None, strict: bool = True) -> None:
+        """Load one tower (and, under the safety prefix, the checker's buffers) from a diffusers checkpoint's keys, or from the bare
+        module's own: CLIPVisionModelWithProjection.state_dict() ("vision_model.*", "visual_projection.weight") and
+        StableDiffusionSafetyChecker.state_dict() ("vision_model.vision_model.*", "visual_projection.weight", "concept_embeds", ...)
+        are re-homed under the tower's prefix.  Keys the registry does not know (position_ids, other components) are skipped."""
+        prefix = self._clip_prefix(prefix)
+        cfg = self._clip_vision[prefix]
+        known = set(clip_vision_param_shapes(cfg))
+        if prefix == SAFETY_PREFIX:   # the checker's buffers travel with their tower, where pd_safety_configure registered them
+            registered = {n for n, _ in self.param_names()}
+            known |= {k for k in safety_param_shapes(cfg.proj_dim) if k in registered}
+        outer = cfg.outer_prefix
+        it = sd.items() if isinstance(sd, dict) else sd
+        for name, arr in it:
+            for cand in (name, outer + name, prefix + name):
+                if cand in known:
+                    self.load_tensor(cand, arr)
+                    break
+        if strict:
+            n = self.clip_vision_weights_missing(prefix) + (self.safety_weights_missing() if prefix == SAFETY_PREFIX else 0)
+            if n:
+                raise PdError(f"{n} tensors missing after load_clip_vision_state_dict('{prefix}')")
+
+    def clip_preprocess(self, images, image_size: int = 224, patch: int = 14, what: str = "pixel_values", mean=None, std=None,
+                        host: bool = False):
+        """CLIPImageProcessor() with its defaults on uint8 pictures [B, H, W, 3] (NumPy, or a CPU / CUDA torch tensor), on the device
+        (pd_clip_preprocess): shortest edge to image_size with PIL BICUBIC, centre crop, (v / 255 - mean) / std in float32.
+          "pixel_values": float32 [B, 3, S, S]
+          "patches":      the patch GEMM's operand rows [B (S / patch)^2, round_up(3 patch^2, 8)] in the engine's operand type (float32,
+                          or float16 / bfloat16 bit patterns as uint16 where NumPy comes out)
+          "bytes":        uint8 [B, S, S, 3], the resized and cropped picture
+        A CUDA tensor comes out; NumPy with host=True or for a NumPy input.  PdError for a reduction beyond PD_RESAMPLE_MAX_SCALE
+        (clip_preprocess_supported): callers keep their host processor there."""
+        if what not in CLIP_PREPROCESS_OUTPUTS:
+            raise ValueError(f"what must be one of {sorted(CLIP_PREPROCESS_OUTPUTS)}")
+        owner, sp, smem, sh = self._u8_source(images)
+        if len(sh) != 4 or sh[3] != 3:
+            raise ValueError(f"images must be uint8 [B, H, W, 3], got {tuple(sh)}")
+        B, H, W, S = int(sh[0]), int(sh[1]), int(sh[2]), int(image_size)
+        two_byte = self.precision in (PD_PREC_F16, PD_PREC_BF16)
+        if what == "pixel_values":
+            shape, ndt = (B, 3, S, S), np.float32
+        elif what == "bytes":
+            shape, ndt = (B, S, S, 3), np.uint8
+        else:
+            if S % int(patch):
+                raise ValueError(f"image_size {S} is no multiple of patch {patch}")
+            shape, ndt = (B * (S // int(patch)) ** 2, clip_patch_width(patch)), (np.uint16 if two_byte else np.float32)
+        to_host = host or (smem == PD_MEM_HOST and not _is_torch(images))
+        if to_host:
+            out = np.empty(shape, ndt)
+            dp, dmem = out.ctypes.data, PD_MEM_HOST
+        else:
+            import torch
+            tdt = {np.float32: torch.float32, np.uint8: torch.uint8}.get(ndt)
+            if tdt is None:
+                tdt = torch.float16 if self.precision == PD_PREC_F16 else torch.bfloat16
+            out = torch.empty(shape, dtype=tdt, device=self._torch_device())
+            dp, dmem = out.data_ptr(), PD_MEM_DEVICE
+        a = pd_clip_preprocess_args()
+        a.src, a.B, a.H, a.W, a.mem_src = sp, B, H, W, smem
+        a.image_size, a.patch, a.out_mode, a.mem_dst, a.dst = S, int(patch), CLIP_PREPROCESS_OUTPUTS[what], dmem, dp
+        from .weights import OPENAI_CLIP_MEAN, OPENAI_CLIP_STD
+        a.mean = (C.c_float * 3)(*(OPENAI_CLIP_MEAN if mean is None else mean))
+        a.std = (C.c_float * 3)(*(OPENAI_CLIP_STD if std is None else std))
+        self._order_after_torch(PD_MEM_DEVICE if PD_MEM_DEVICE in (smem, dmem) else PD_MEM_HOST)
+        self._check(self.lib.pd_clip_preprocess(self._h, C.byref(a)))
+        del owner
+        return out
+
+    def clip_vision(self, x, what="embeds", hidden_layer: int = -2, prefix: Optional[str] = None):
+        """One forward pass of an image tower (pd_clip_vision_forward).  x: uint8 pictures [B, H, W, 3] (preprocessed on the device,
+        straight into the patch matrix) or float32 pixel_values [B, 3, S, S]; NumPy or torch.  what: "embeds" (image_embeds [B, D]),
+        "pooled" (pooler_output [B, C]), "hidden" (hidden_states[hidden_layer] [B, P + 1, C]; -2 is encode_image's), or a tuple of
+        them (a tuple comes back).  NumPy in, NumPy out; CUDA tensor in, CUDA tensor out."""
+        prefix = self._clip_prefix(prefix)
+        cfg = self._clip_vision[prefix]
+        names = (what,) if isinstance(what, str) else tuple(what)
+        if not names or any(n not in CLIP_VISION_OUTPUTS for n in names):
+            raise ValueError(f"what must be among {CLIP_VISION_OUTPUTS}")
+        is_u8 = (x.dtype == np.uint8) if not _is_torch(x) else str(x.dtype) == "torch.uint8"
+        if is_u8:
+            owner, ptr, mem, sh = self._u8_source(x)
+            if len(sh) != 4 or sh[3] != 3:
+                raise ValueError(f"pictures must be uint8 [B, H, W, 3], got {tuple(sh)}")
+            B, H, W = int(sh[0]), int(sh[1]), int(sh[2])
+            dev = owner.device if mem == PD_MEM_DEVICE else None
+        else:
+            b = _Buf(x)
+            owner, ptr, mem = b.owner, b.ptr, b.mem
+            if owner.ndim != 4 or owner.shape[1] != 3:
+                raise ValueError(f"pixel_values must be [B, 3, S, S], got {tuple(owner.shape)}")
+            B, H, W = int(owner.shape[0]), int(owner.shape[2]), int(owner.shape[3])
+            dev = owner.device if mem == PD_MEM_DEVICE else None
+        shapes = {"embeds": (B, cfg.proj_dim), "pooled": (B, cfg.hidden), "hidden": (B, cfg.patches + 1, cfg.hidden)}
+        outs = {}
+        for n in names:
+            if mem == PD_MEM_DEVICE:
+                import torch
+                outs[n] = torch.empty(shapes[n], dtype=torch.float32, device=dev)
+            else:
+                outs[n] = np.empty(shapes[n], np.float32)
+        ptr_of = lambda n: None if n not in outs else (outs[n].data_ptr() if mem == PD_MEM_DEVICE else outs[n].ctypes.data)
+        a = pd_clip_vision_args()
+        pre = prefix.encode()
+        a.prefix, a.input, a.input_kind = pre, ptr, PD_CLIP_IN_U8 if is_u8 else PD_CLIP_IN_PIXEL_VALUES
+        a.B, a.H, a.W, a.mem, a.hidden_layer = B, H, W, mem, int(hidden_layer)
+        a.image_embeds, a.pooler_output, a.hidden = ptr_of("embeds"), ptr_of("pooled"), ptr_of("hidden")
+        self._order_after_torch(mem)
+        self._check(self.lib.pd_clip_vision_forward(self._h, C.byref(a)))
+        del owner
+        return outs[names[0]] if isinstance(what, str) else tuple(outs[n] for n in names)
+
+    def safety_check(self, images_or_embeds, return_scores: bool = False):
+        """StableDiffusionSafetyChecker.forward (pd_safety_check).  uint8 pictures [B, H, W, 3] go through the safety tower first;
+        float32 [B, D] is taken as its image_embeds.  Returns the per-image flags as a bool array [B]; with return_scores also the
+        float32 [B, 20] scores (3 special-care, then 17 concept, unrounded).  NumPy out (CUDA inputs are read on the device)."""
+        x = images_or_embeds
+        is_u8 = (x.dtype == np.uint8) if not _is_torch(x) else str(x.dtype) == "torch.uint8"
+        if is_u8:
+            x = self.clip_vision(x, "embeds", prefix=SAFETY_PREFIX)
+        b = _Buf(x)
+        if b.owner.ndim != 2:
+            raise ValueError(f"embeds must be [B, D], got {tuple(b.owner.shape)}")
+        B = int(b.owner.shape[0])
+        if b.mem == PD_MEM_DEVICE:
+            import torch
+            flags = torch.empty((B,), dtype=torch.int32, device=b.owner.device)
+            scores = torch.empty((B, PD_SAFETY_SPECIAL + PD_SAFETY_CONCEPTS), dtype=torch.float32, device=b.owner.device) if return_scores else None
+            fp, sp = flags.data_ptr(), scores.data_ptr() if return_scores else None
+        else:
+            flags = np.empty((B,), np.int32)
+            scores = np.empty((B, PD_SAFETY_SPECIAL + PD_SAFETY_CONCEPTS), np.float32) if return_scores else None
+            fp, sp = flags.ctypes.data, scores.ctypes.data if return_scores else None
+        self._order_after_torch(b.mem)
+        self._check(self.lib.pd_safety_check(self._h, b.ptr, B, b.mem, fp, sp))
+        flags = _to_host(flags).astype(bool)
+        return (flags, _to_host(scores)) if return_scores else flags
+
+    def safety_blank(self, images, flags, value: float = 0.0):
+        """Write `value` over the flagged images of a CUDA float32 batch [B, ...] in place (pd_safety_blank) and return it.  0 is
+        what the checker writes; with image_store(mul, add) behind it, -add / mul makes the stored picture black."""
+        import torch
+        if not (_is_torch(images) and images.is_cuda and images.dtype == torch.float32 and images.is_contiguous()):
+            raise ValueError("images must be a contiguous float32 CUDA tensor")
+        f = np.ascontiguousarray(np.asarray(_to_host(flags)).astype(np.int32))
+        B = int(images.shape[0])
+        if f.shape != (B,):
+            raise ValueError(f"flags must be [{B}]")
+        self._order_after_torch(PD_MEM_DEVICE)
+        self._check(self.lib.pd_safety_blank(self._h, images.data_ptr(), B, int(images[0].numel()), f.ctypes.data, PD_MEM_HOST, float(value)))
+        return images
 
     # ------------------------------------------------------------------ M-LSD line detector (pd_mlsd_*)
     def mlsd_weights_missing(self) -> int:

@@ -172,8 +172,16 @@ class PromptDiffusionPipeline(AdapterMixin):
 
     def __init__(self, engine: E.Engine, text_encoder: Optional[Callable] = None, vae_decode: Optional[Callable] = None,
                  scheduler: Any = None, tokenizer: Any = None, fuse_scheduler: bool = False, long_prompts=None,
-                 device_images: bool = False):
+                 device_images: bool = False, safety_checker: Any = None, feature_extractor: Any = None, image_encoder: Any = None,
+                 requires_safety_checker: bool = False):
         """long_prompts: True / a window count = enable_long_prompts() at construction.
+        safety_checker: None (the default, and what the reference's __call__ runs: it switches its checker off), True = the engine's
+        checker (Engine.configure_safety_checker + its weights: the CLIP ViT-L/14 tower, preprocessing and the concept check on the
+        GPU), or a callable with diffusers' signature safety_checker(images=, clip_input=) -> (images, has_nsfw_concept), which then
+        needs feature_extractor (a CLIPImageProcessor-like callable).  With a checker and output_type != "latent", flagged images
+        come back black and nsfw_content_detected is the list of flags.  image_encoder: True = the engine's tower under
+        "image_encoder." (Engine.configure_clip_vision), or a callable pixel_values -> object with .image_embeds / .hidden_states,
+        for encode_image.  requires_safety_checker is kept as the reference's config flag.
         device_images: True = enable_device_images() at construction (the image ends of a call on the GPU; off by default).
         prompt_embeds / negative_prompt_embeds of any equal length L <= engine.PD_MAX_CONTEXT_LEN are accepted by every path
         (fused DDIM, fuse_scheduler=True, host schedulers, callbacks): the engine takes the context length per call.
@@ -199,6 +207,14 @@ class PromptDiffusionPipeline(AdapterMixin):
             self.enable_long_prompts(long_prompts)
         self._guidance_scale = 7.5
         self._device_images = bool(device_images)
+        if safety_checker is None and requires_safety_checker:
+            raise ValueError("requires_safety_checker=True needs a safety_checker (True for the engine's, or a callable)")
+        if safety_checker is not None and safety_checker is not True and feature_extractor is None:
+            raise ValueError("a safety_checker callable needs a feature_extractor (the reference raises the same)")
+        self.safety_checker = safety_checker
+        self.feature_extractor = feature_extractor
+        self.image_encoder = image_encoder
+        self.requires_safety_checker = bool(requires_safety_checker)
         self._lora_init()      # LoRA adapters (load_lora_weights; lora_pipeline.AdapterMixin)
 
     def _check_fusable(self):
@@ -295,6 +311,99 @@ class PromptDiffusionPipeline(AdapterMixin):
                 raise ValueError(f"control guidance start: {start} can't be smaller than 0.")
             if end > 1.0:
                 raise ValueError(f"control guidance end: {end} can't be larger than 1.0.")
+
+    # ------------------------------------------------------------------ safety checker / image encoder (pipeline :490-528)
+    @staticmethod
+    def _pictures_u8(image):
+        """What the reference hands its feature_extractor, as one uint8 array [B, H, W, 3]: a torch tensor in [-1, 1] goes through
+        postprocess(output_type="pil") (denormalize, clamp, round), an array in [0, 1] through numpy_to_pil ((x * 255).round()), PIL
+        images / uint8 arrays are taken as they are; None when the pictures differ in size."""
+        if E._is_torch(image) and str(image.dtype) == "torch.uint8":      # pictures already: [B, H, W, 3] (or one [H, W, 3])
+            image = image.detach().cpu().numpy()
+        nchw = isinstance(image, np.ndarray) and image.dtype != np.uint8 and image.ndim == 4 and image.shape[1] == 3 and image.shape[3] != 3
+        if E._is_torch(image) or nchw:      # (a float array [B, 3, H, W] is read like the tensor it stands for)
+            x = _to_numpy(image)
+            return (np.clip(x / 2 + 0.5, 0, 1).transpose(0, 2, 3, 1) * 255).round().astype("uint8")
+        if isinstance(image, np.ndarray):
+            if image.dtype == np.uint8:
+                return image if image.ndim == 4 else image[None]
+            x = image if image.ndim == 4 else image[None]
+            return (x * 255).round().astype("uint8")
+        items = image if isinstance(image, (list, tuple)) else [image]
+        arrs = [np.asarray(im.convert("RGB")) if _is_pil(im) else np.asarray(im) for im in items]
+        if len({a.shape for a in arrs}) != 1:
+            return None
+        return np.stack(arrs).astype(np.uint8, copy=False)
+
+    def _host_pixel_values(self, u8_or_image):
+        if self.feature_extractor is None:
+            raise ValueError("these pictures need a feature_extractor: the engine's preprocessing refuses reductions beyond "
+                             f"{E.PD_RESAMPLE_MAX_SCALE}x and pictures of unequal sizes")
+        from PIL import Image
+        pics = [Image.fromarray(im) for im in u8_or_image] if isinstance(u8_or_image, np.ndarray) else u8_or_image
+        return _to_numpy(self.feature_extractor(pics, return_tensors="np").pixel_values).astype(np.float32)
+
+    def run_safety_checker(self, image, device=None, dtype=None):
+        """pipeline :515-527: (image with the flagged pictures zeroed, has_nsfw_concept) -- (image, None) without a checker.  image:
+        a tensor / array [B, 3, H, W] in [-1, 1] or an array [B, H, W, 3] in [0, 1], as in the reference."""
+        if self.safety_checker is None:
+            return image, None
+        u8 = self._pictures_u8(image)
+        if self.safety_checker is True:
+            if u8 is not None and E.clip_preprocess_supported(u8.shape[1], u8.shape[2], self._safety_size()):
+                flags = self.engine.safety_check(u8)
+            else:
+                flags = self.engine.safety_check(self.engine.clip_vision(self._host_pixel_values(u8 if u8 is not None else image), "embeds",
+                                                                         prefix=E.SAFETY_PREFIX))
+            flags = [bool(f) for f in flags]
+            if any(flags):
+                image = image.clone() if E._is_torch(image) else np.array(image, copy=True)
+                for i, f in enumerate(flags):
+                    if f:
+                        image[i] = 0
+            return image, flags
+        clip_input = self._host_pixel_values(u8 if u8 is not None else image)
+        image, flags = self.safety_checker(images=image, clip_input=clip_input)
+        return image, flags
+
+    def _safety_size(self) -> int:
+        cv = getattr(self.engine, "_clip_vision", {}).get(E.SAFETY_PREFIX)
+        return cv.image_size if cv is not None else 224
+
+    def encode_image(self, image, device=None, num_images_per_prompt: int = 1, output_hidden_states=None):
+        """pipeline :490-512: (image_embeds, zeros_like) -- or, with output_hidden_states, hidden_states[-2] of the pictures and of an
+        all-zero pixel_values batch -- each repeat_interleave'd num_images_per_prompt times.  image: PIL pictures / uint8 arrays (the
+        engine preprocesses them) or float pixel_values [B, 3, S, S].  NumPy arrays come back."""
+        if self.image_encoder is None:
+            raise ValueError("encode_image needs an image_encoder (True for the engine's tower, or a callable)")
+        is_pv = (E._is_torch(image) and str(image.dtype) != "torch.uint8") or (isinstance(image, np.ndarray) and image.dtype != np.uint8)
+        if self.image_encoder is True:
+            eng = self.engine
+            cv = eng._clip_vision[E.IMAGE_ENCODER_PREFIX]
+            if is_pv:
+                x = _to_numpy(image).astype(np.float32)
+            else:
+                x = self._pictures_u8(image)
+                if x is None or not E.clip_preprocess_supported(x.shape[1], x.shape[2], cv.image_size):
+                    x = self._host_pixel_values(x if x is not None else image)
+            if output_hidden_states:
+                hid = _to_numpy(eng.clip_vision(x, "hidden", hidden_layer=-2, prefix=E.IMAGE_ENCODER_PREFIX))
+                zeros = np.zeros((x.shape[0], 3, cv.image_size, cv.image_size), np.float32)
+                unc = _to_numpy(eng.clip_vision(zeros, "hidden", hidden_layer=-2, prefix=E.IMAGE_ENCODER_PREFIX))
+                return np.repeat(hid, num_images_per_prompt, axis=0), np.repeat(unc, num_images_per_prompt, axis=0)
+            emb = np.repeat(_to_numpy(eng.clip_vision(x, "embeds", prefix=E.IMAGE_ENCODER_PREFIX)), num_images_per_prompt, axis=0)
+            return emb, np.zeros_like(emb)
+        if is_pv:
+            pv = _to_numpy(image).astype(np.float32)
+        else:
+            u8 = self._pictures_u8(image)
+            pv = self._host_pixel_values(u8 if u8 is not None else image)
+        if output_hidden_states:
+            hid = _to_numpy(self.image_encoder(pv, output_hidden_states=True).hidden_states[-2])
+            unc = _to_numpy(self.image_encoder(np.zeros_like(pv), output_hidden_states=True).hidden_states[-2])
+            return np.repeat(hid, num_images_per_prompt, axis=0), np.repeat(unc, num_images_per_prompt, axis=0)
+        emb = np.repeat(_to_numpy(self.image_encoder(pv).image_embeds), num_images_per_prompt, axis=0)
+        return emb, np.zeros_like(emb)
 
     # ------------------------------------------------------------------ image ends on the device
     def enable_device_images(self):
@@ -834,12 +943,27 @@ class PromptDiffusionPipeline(AdapterMixin):
             lat = self._stepwise(kw, scales_step, callback_on_step_end, callback_on_step_end_tensor_inputs, callback,
                                  callback_steps, pe, ne, eta, generator, host_blend=host_blend,
                                  plan=plan if self.scheduler is not None else None)
-        # 9. post-processing (pipeline :1298-1321); safety checker is forced off there too
+        # 9. post-processing (pipeline :1298-1321).  The reference's __call__ forces its checker off; here it runs when one was given
+        nsfw = None
         if output_type == "latent":
             images = _to_numpy(lat) if in_engine else lat
-        elif (dev_images and output_type == "pil" and self.vae_decode is None and getattr(self.engine.cfg, "vae_ch", 0) > 0
-              and self.engine.vae_weights_missing() == 0):
-            # decode, denormalize, clip, round and the NHWC transpose on the device; only the uint8 pictures come back
+        elif (self.safety_checker is True and dev_images and output_type == "pil" and self.vae_decode is None
+              and getattr(self.engine.cfg, "vae_ch", 0) > 0 and self.engine.vae_weights_missing() == 0
+              and E.clip_preprocess_supported(int(lat.shape[2]) * 8, int(lat.shape[3]) * 8, self._safety_size())):
+            # as below, with the checker in between, all of it on the device: the stored bytes are what the reference's
+            # feature_extractor would be handed; flagged images are overwritten with the value the store maps to black
+            from PIL import Image
+            dec = self.engine.vae_decode(self._to_device(lat))
+            u8 = self.engine.image_store(dec, mul=0.5, add=0.5, rounding="nearest_even")
+            nsfw = [bool(f) for f in self.engine.safety_check(u8)]
+            if any(nsfw):
+                self.engine.safety_blank(dec, nsfw, value=-1.0)
+                u8 = self.engine.image_store(dec, mul=0.5, add=0.5, rounding="nearest_even")
+            images = [Image.fromarray(im) for im in u8.cpu().numpy()]
+        elif (self.safety_checker is None and dev_images and output_type == "pil" and self.vae_decode is None
+              and getattr(self.engine.cfg, "vae_ch", 0) > 0 and self.engine.vae_weights_missing() == 0):
+            # decode, denormalize, clip, round and the NHWC transpose on the device; only the uint8 pictures come back.  (Never with a
+            # checker: a callable one, or pictures the device preprocessing refuses, take the host branch below, which checks them.)
             from PIL import Image
             u8 = self.engine.image_store(self.engine.vae_decode(self._to_device(lat)), mul=0.5, add=0.5, rounding="nearest_even",
                                          host=True)
@@ -855,14 +979,22 @@ class PromptDiffusionPipeline(AdapterMixin):
                 raise ValueError('output_type other than "latent" needs first-stage weights in the engine '
                                  "(first_stage_model.decoder.* / post_quant_conv.*) or a vae_decode callable")
             img = np.clip(img / 2 + 0.5, 0, 1).transpose(0, 2, 3, 1)      # denormalize, NHWC
+            if self.safety_checker is not None:
+                # (the reference checks before it denormalises and then skips the denormalisation of the zeroed images: black either way)
+                img, nsfw = self.run_safety_checker(np.ascontiguousarray(img))
+                img = _to_numpy(img)
+                nsfw = None if nsfw is None else [bool(f) for f in nsfw]
+                if nsfw is not None and any(nsfw):      # (diffusers' checker zeroes them itself; a callable that does not is not trusted to)
+                    img = np.array(img, copy=True)
+                    img[np.asarray(nsfw, bool)] = 0
             if output_type == "pil":
                 from PIL import Image
                 images = [Image.fromarray((im * 255).round().astype("uint8")) for im in img]
             else:
                 images = img
         if not return_dict:
-            return (images, None)
-        return StableDiffusionPipelineOutput(images=images, nsfw_content_detected=None)
+            return (images, nsfw)
+        return StableDiffusionPipelineOutput(images=images, nsfw_content_detected=nsfw)
 
     # ------------------------------------------------------------------ per-step driver (callbacks / plug-in schedulers)
     def _eval_plan(self, t_start):

@@ -66,6 +66,10 @@ class ModelConfig:
     hed: bool = False
     # M-LSD line detector (annotator/mlsd): opt-in, fixed architecture, registered through pd_mlsd_configure
     mlsd: bool = False
+    # CLIP image towers (ClipVisionConfig, at most two: image_encoder / the safety checker's): opt-in, registered through
+    # pd_clip_vision_configure; safety_checker = True also registers StableDiffusionSafetyChecker's buffers (pd_safety_configure)
+    clip_vision: Tuple = ()
+    safety_checker: bool = False
 
     @property
     def time_embed_dim(self) -> int:
@@ -73,6 +77,76 @@ class ModelConfig:
 
 
 SD15 = ModelConfig()
+
+OPENAI_CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
+OPENAI_CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
+SAFETY_PREFIX = "safety_checker.vision_model."
+IMAGE_ENCODER_PREFIX = "image_encoder."
+
+
+@dataclasses.dataclass(frozen=True)
+class ClipVisionConfig:
+    """transformers' CLIPVisionConfig + projection_dim, and where the tower sits in a diffusers checkpoint (`prefix`).  stream_f32:
+    the residual stream stays in float32 in every precision mode (image_encoder); False keeps the engine's stream type (safety tower)."""
+
+    hidden: int = 1024
+    layers: int = 24
+    heads: int = 16
+    ff: int = 4096
+    patch: int = 14
+    image_size: int = 224
+    proj_dim: int = 768
+    act: str = "quick_gelu"             # or "gelu" (erf)
+    eps: float = 1e-5
+    prefix: str = IMAGE_ENCODER_PREFIX
+    stream_f32: bool = True
+    mean: Tuple[float, float, float] = OPENAI_CLIP_MEAN
+    std: Tuple[float, float, float] = OPENAI_CLIP_STD
+
+    @property
+    def patches(self) -> int:
+        return (self.image_size // self.patch) ** 2
+
+    @property
+    def outer_prefix(self) -> str:
+        """Where visual_projection lives: the prefix without a trailing 'vision_model.'"""
+        return self.prefix[:-len("vision_model.")] if self.prefix.endswith("vision_model.") else self.prefix
+
+
+# openai/clip-vit-large-patch14 inside StableDiffusionSafetyChecker; laion/CLIP-ViT-H-14 (the IP-Adapter image_encoder)
+CLIP_VIT_L14_SAFETY = ClipVisionConfig(prefix=SAFETY_PREFIX, stream_f32=False)
+CLIP_VIT_H14 = ClipVisionConfig(hidden=1280, layers=32, heads=16, ff=5120, proj_dim=1024, act="gelu", prefix=IMAGE_ENCODER_PREFIX)
+
+
+def clip_vision_param_shapes(cfg: ClipVisionConfig) -> Dict[str, Tuple[int, ...]]:
+    """Name -> shape of one tower, in registry order: transformers' CLIPVisionModelWithProjection.state_dict() under cfg.prefix."""
+    C, F, p = cfg.hidden, cfg.ff, cfg.patch
+    V = cfg.prefix + "vision_model."
+    out = {V + "embeddings.class_embedding": (C,), V + "embeddings.patch_embedding.weight": (C, 3, p, p),
+           V + "embeddings.position_embedding.weight": (cfg.patches + 1, C), V + "pre_layrnorm.weight": (C,), V + "pre_layrnorm.bias": (C,)}
+    for i in range(cfg.layers):
+        L = f"{V}encoder.layers.{i}."
+        for nm in ("k_proj", "v_proj", "q_proj", "out_proj"):
+            out[L + f"self_attn.{nm}.weight"] = (C, C)
+            out[L + f"self_attn.{nm}.bias"] = (C,)
+        out[L + "layer_norm1.weight"] = (C,)
+        out[L + "layer_norm1.bias"] = (C,)
+        out[L + "mlp.fc1.weight"] = (F, C)
+        out[L + "mlp.fc1.bias"] = (F,)
+        out[L + "mlp.fc2.weight"] = (C, F)
+        out[L + "mlp.fc2.bias"] = (C,)
+        out[L + "layer_norm2.weight"] = (C,)
+        out[L + "layer_norm2.bias"] = (C,)
+    out[V + "post_layernorm.weight"] = (C,)
+    out[V + "post_layernorm.bias"] = (C,)
+    out[cfg.outer_prefix + "visual_projection.weight"] = (cfg.proj_dim, C)
+    return out
+
+
+def safety_param_shapes(proj_dim: int) -> Dict[str, Tuple[int, ...]]:
+    """StableDiffusionSafetyChecker's four buffers."""
+    return {"safety_checker.concept_embeds": (17, proj_dim), "safety_checker.special_care_embeds": (3, proj_dim),
+            "safety_checker.concept_embeds_weights": (17,), "safety_checker.special_care_embeds_weights": (3,)}
 # A reduced network with the same topology (4 levels, attention at ds 1/2/4,
 # 8 heads) used by fast parity tests: channels 64/128/256/256, dh 8/16/32.
 TINY = ModelConfig(model_channels=64, context_dim=96, context_len=77,
