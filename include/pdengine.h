@@ -729,9 +729,13 @@ int pd_comm_init(pd_engine* e, const uint8_t id[PD_COMM_ID_BYTES], int32_t world
 int pd_comm_world(pd_engine* e, int32_t* world, int32_t* rank);
 int pd_comm_all_gather(pd_engine* e, const float* send, float* recv, int64_t count, int32_t mem);
 int pd_comm_destroy(pd_engine* e); /* also done by pd_engine_destroy */
-/* Tuning / instrumentation knobs (defaults are the measured best; tests and tools/ flip them for A/B runs):
- *   "verbose" (1: workspace sizes; 2: one stderr line per contraction launch saying which kernel family / tile / split-K count it takes),
- *   "profile" (HIP events around every contraction launch, see pd_profile_read),
+/* Tuning / instrumentation knobs (defaults are the measured best; tests and tools/ flip them for A/B runs).  Every knob belongs to the
+ * engine it is set on: nothing is process-wide.  The list below has every key of the engine's option table (csrc/options.h, walked by
+ * pd_option_info) in the table's order, each with its default.  Tile-count options -- "splitk_tiles", "dense_tiles", "conv_patch2_tiles",
+ * "patch_split_tiles", "patch_split_fill" -- are given per 256 CUs: the engine stores and reports the value as given and scales it by
+ * ncu / 256 (stat "ncu") where the dispatch plan reads it.
+ *   "verbose" (0; 1: workspace sizes; 2: one stderr line per contraction launch saying which kernel family / tile / split-K count it takes),
+ *   "profile" (a command rather than a stored knob: HIP events around every contraction launch from now on, see pd_profile_read; 0),
  *   "two_streams" (ControlNet on a second stream beside the UNet encoder, default 1),
  *   "cfg_share" (classifier-free guidance feeds both halves of the doubled batch the same latent and timestep, ddim_hacked.py:189-192, and
  *   -- unless pair_uncond / query_uncond say otherwise -- the same example pair and query: the layers in front of the first
@@ -740,18 +744,22 @@ int pd_comm_destroy(pd_engine* e); /* also done by pd_engine_destroy */
  *   last evaluation did: bit 0 UNet, bit 1 ControlNet; bit 2: guess mode under guidance ran the ControlNet on the conditional half only,
  *   as pipeline_prompt_diffusion.py:1220-1224 does, instead of on the doubled batch with the unconditional residuals zeroed afterwards),
  *   "graph" (pd_ddim_sample captures its step loop in a hipGraph and replays it on later calls with equal arguments, 0),
- *   "conv_patch" (LDS-patch conv3x3 kernel, 1), "conv_patch2" (its wave-specialised second generation in the 2-byte modes, 1), "patch4" (the
+ *   "conv_patch" (LDS-patch conv3x3 kernel, 1), "conv_patch2" / "conv_patch2_tiles" (its wave-specialised second generation in the 2-byte modes, for
+ *   launches of at least that many blocks and every split launch, 1 / 768), "patch4" (the
  *   fourth generation -- 4 waves per block, one per SIMD, 32x32x16 MFMAs, LDS-DMA operands -- for every unsplit 2-byte patch conv, 1;
  *   bit-identical to the others), "patch_split" / "patch_split_tiles" (that kernel with the channel chunks
- *   split over 2-4 slices when it has fewer tiles than CUs but at least this many, 1 / 64), "gn_fuse" (GroupNorm applied while the patch is staged, 0),
+ *   split over 2-4 slices when it has fewer tiles than CUs but at least this many, 1 / 64), "patch_split_fill" (the slices are chosen to
+ *   reach about this many blocks, 256), "patch_split_min" (at least this many 128-byte channel chunks per slice, 4; values below 1 are
+ *   refused), "gn_fuse" (GroupNorm applied while the patch is staged, 0),
  *   "ln_fuse" (norm1 / norm2 of a transformer block folded into the to_q/k/v and attn2.to_q GEMMs, row statistics carried
  *   from the producing GEMM's epilogue: -1 = on in the 2-byte modes and off in the fp32-storage modes, 0 / 1 forced),
- *   "gn_single" (single-kernel LDS-slab GroupNorm where a sample's group bundle fits, 1), "gn_reg" (process-wide: its register-resident
+ *   "gn_single" (single-kernel LDS-slab GroupNorm where a sample's group bundle fits, 1), "gn_reg" (its register-resident
  *   form -- one block per (sample, group), the group's slab in registers, one barrier -- for 2-byte tensors of 64 / 256 / 1024 pixels, 1),
  *   "big_tile" / "wide_tile" (256x160 / 256x320 GEMM tiles, 1), "dense_k" / "dense_tiles" (8-wave unsplit tile for
  *   linear layers with at most that many K steps, 40 / 128), "short_k" (8-wave 128x160 tile at 16 waves per CU for
- *   linear layers with at most that many K steps, 20), "splitk_tiles" (split K below this many tiles, 256),
- *   "splitk_fused" (in-kernel split-K finalize, 0), "tile192" (256x192 GEMM tile for widths that divide by 192 but not by
+ *   linear layers with at most that many K steps, 20), "splitk_tiles" (split K below this many tiles, 256), "splitk_max" (into at most
+ *   this many slices, 16), "splitk_big" (a split-K conv3x3 of at least 1024 rows on 256x160 tiles where tiles x slices still give every CU a
+ *   block, 0), "splitk_fused" (in-kernel split-K finalize, 0), "tile192" (256x192 GEMM tile for widths that divide by 192 but not by
  *   160: the MMDiT's 1536 / 4608 / 6144, 1), "gemv" (weight-streaming kernel for a Linear over <= 4 fp32 rows with >= 4096
  *   outputs: the MMDiT modulation matrix, 1),
  *   "sd3_fp8" (SD3 path, 2-byte modes: 0 off; 1 the projections fed by an AdaLN output -- q/k/v of both streams, ff / ff_context
@@ -764,8 +772,7 @@ int pd_comm_destroy(pd_engine* e); /* also done by pd_engine_destroy */
  *   bit-identical to the igemm tiles'), "ring_small" (small-M linear layers -- at most a quarter chip of 128x160 tiles, the 8x8 level's M = 1024 --
  *   on 64x80 ring tiles without split-K slabs and a finalize pass: 0 off, d = where the 128x160 grid fills at most 1/d of the chip, 4), "ring_pp" (its ping-pong form -- two wave groups half a K step apart -- for K >= 2560 and for one
  *   256-row tile per CU, 1; bit-identical), "slab_gn" (a ResBlock conv1 that runs split-K hands its fp32 slabs to the single-kernel
- *   GroupNorm that reads them instead of running a finalize pass, 1; bit-identical), "patch_split_min" (patch-conv split-K: at
- *   least this many 128-byte channel chunks per slice, 4), "ups_fold" / "ups_fold_tiles" (2-byte modes: a UNet decoder Upsample conv --
+ *   GroupNorm that reads them instead of running a finalize pass, 1; bit-identical), "ups_fold" / "ups_fold_tiles" (2-byte modes: a UNet decoder Upsample conv --
  *   conv3x3 of a nearest-x2 upsampled tensor, bias only, source height and width multiples of 16 -- runs as four 2x2-tap phase
  *   convolutions over the source with folded weights, conv_upfold.hip, 4/9 of the products, when its phase grid has at least that many
  *   blocks: 1 / -1 = three quarters of the CUs, the block count at which a patch conv runs unsplit.  Not bit-identical to the nine-tap
@@ -781,7 +788,13 @@ int pd_comm_destroy(pd_engine* e); /* also done by pd_engine_destroy */
  *   1; 256x320 with a gate, a row remap, tanh- or erf-GELU, or on a conv (256x160 runs there); 2 / 3 / 4 on a split launch.  The plan's
  *   own tile requests are mapped in the same way without an error; stat "gemm_tile" reports the tile that ran.  The defaults leave every plan as it is). */
 int pd_set_option(pd_engine* e, const char* key, int64_t value);
-/* "graph_captures" / "graph_replays" (step loops captured / replayed from a captured graph since the engine was created),
+/* The value an option holds now, as pd_set_option stored it (0 / 1 for the on / off knobs; "profile": whether the brackets are on), so a
+ * caller can save and restore a knob without knowing its default. */
+int pd_get_option(pd_engine* e, const char* key, int64_t* value);
+/* Row `index` of the option table: its key (a static string) and its default.  Needs no engine; non-zero past the last row. */
+int pd_option_info(int32_t index, const char** key, int64_t* default_value);
+/* "ncu" (compute units of the engine's device, to which the chip-fill rules of the dispatch are scaled; the option defaults assume 256),
+ * "graph_captures" / "graph_replays" (step loops captured / replayed from a captured graph since the engine was created),
  * "workspace_bytes", "side_workspace_bytes" (the workspace of everything outside a sampling step -- first stage, HED, text encoders, SD3's VAE:
  * it grows to the largest call so far and holds that call's intermediates, I/O staging and 64 MiB of slack), "vae_flash_launches", "weight_bytes", "launches" (engine launches, split-K finalize passes not counted), "ring_launches" / "gn_from_slabs" / "ups_fold_launches"
  * (of which: gemm_ring.hip / GroupNorm fed by split-K slabs / the four-phase upsample conv), "steps", "event_overhead_ns", "cfg_shared" (see option "cfg_share"),

@@ -306,7 +306,7 @@ int pd_engine::build() {
     build_vae();
     build_text();
     build_vae_encoder();   // after the text transformer: a default engine's registry is unchanged
-    if ((int)cnet.enc.size() + 1 != PD_NUM_CONTROL && verbose)
+    if ((int)cnet.enc.size() + 1 != PD_NUM_CONTROL && opt.verbose)
         fprintf(stderr, "[pdengine] note: %zu control tensors (reference SD1.5 has 13)\n", cnet.enc.size() + 1);
     if ((int)cnet.enc.size() + 1 > PD_NUM_CONTROL) {
         pd_set_error("config yields %zu control tensors; at most %d supported", cnet.enc.size() + 1, PD_NUM_CONTROL);
@@ -644,14 +644,14 @@ int pd_engine::init_random(uint64_t seed) {
 // LN(x) . W^T = rstd * (x . (W diag(gamma))^T - mean * colsum) + beta . W^T, so the consumer GEMM reads the residual stream
 // itself and the normalised tensor is never written.  Built once per weight change.
 bool pd_engine::st_tail_on(const STW& s, int rows_per_sample, int L) const {
-    return opt_st_fuse && S == T && st_tail_eligible(P, s.C, cfg.num_heads, rows_per_sample, L);
+    return opt.st_fuse && S == T && st_tail_eligible(P, s.C, cfg.num_heads, rows_per_sample, L);
 }
 
 // conv3x3(nearest_x2(x)) = four 2x2-tap convs over x, one per output parity, whose weights are sums of the nine (conv_upfold.hip).  Derived
 // weights like the folded LayerNorms: rebuilt under the same dirty flag.  2-byte modes only -- f32 and f16x2 keep the reference's
 // operation order -- and only for matrices the phase kernel can take (whole 128-byte channel chunks, 4-channel store groups).
 bool pd_engine::upfold_wanted(const WMat& m) const {
-    return opt_ups_fold && (P == DT_F16 || P == DT_BF16) && T == P && m.taps == 9 && m.cin_pad % 64 == 0 && m.N % 4 == 0 && m.K == 9 * m.cin_pad;
+    return opt.ups_fold && (P == DT_F16 || P == DT_BF16) && T == P && m.taps == 9 && m.cin_pad % 64 == 0 && m.N % 4 == 0 && m.K == 9 * m.cin_pad;
 }
 int pd_engine::fold_upconv(WMat& m) {
     if (!upfold_wanted(m)) return 0;
@@ -669,8 +669,8 @@ int pd_engine::fold_upconvs() {
 }
 
 int pd_engine::fold_layernorms() {
-    const bool on = opt_ln_fuse < 0 ? !f32 : opt_ln_fuse != 0;
-    const bool tail = opt_st_fuse && S == T && (P == DT_F16 || P == DT_BF16);
+    const bool on = opt.ln_fuse < 0 ? !f32 : opt.ln_fuse != 0;
+    const bool tail = opt.st_fuse && S == T && (P == DT_F16 || P == DT_BF16);
     if (!ln_dirty) return 0;
     PD_TRY(fold_upconvs());
     if (!on && !tail) {
@@ -805,17 +805,19 @@ GemmParams pd_engine::fill_gemm(const WMat& m, const Act& in, const Act& out, co
     return p;
 }
 
-// gemm: plan.  Which kernel family / tile / split a launch takes, from shapes, options and ncu alone (p: fill_gemm's, splitk 1).
+// gemm: plan.  Which kernel family / tile / split a launch takes, from shapes, options and ncu alone (p: fill_gemm's, splitk 1); ncu enters
+// through ChipFill only.
 int pd_engine::patch_tiles(const GemmParams& p) const {
-    return (opt_patch && !p.pad_shift && !p.dil_m1) ? conv_patch_tiles(p, P) : 0;   // the patch kernels pad 1 on every side, taps one pixel apart
+    return (opt.conv_patch && !p.pad_shift && !p.dil_m1) ? conv_patch_tiles(p, P) : 0;   // the patch kernels pad 1 on every side, taps one pixel apart
 }
 // conv3x3 with enough 16x16 patches to fill the chip: LDS-patch kernel (conv_patch.hip)
 bool pd_engine::patch_unsplit(int ptiles) const {
-    return ptiles >= ncu * 3 / 4;   // (192 of 256 CUs: a launch that fills three quarters of the chip takes the patch kernel unsplit)
+    return ptiles >= chip_fill().three_quarters;   // (192 of 256 CUs: a launch that fills three quarters of the chip takes the patch kernel unsplit)
 }
 
 GemmPlan pd_engine::plan_gemm(const GemmParams& p, const WMat& m, const GemmCall& c, bool allow_splitk) const {
     GemmPlan pl;
+    const ChipFill fill = chip_fill();
     const int in_dt = p.a_dt, out_dt = p.c_dt;
     const bool fp8 = in_dt == DT_FP8;
     const bool plain = !c.gate && !c.c_sample_rows && !c.a_sample_rows && !c.c_scale;
@@ -823,15 +825,15 @@ GemmPlan pd_engine::plan_gemm(const GemmParams& p, const WMat& m, const GemmCall
     const bool may_defer = c.defer && c.defer->allow && plain && c.act == 0 && c.scale == 1.f && !c.R && !c.VT && !c.ln_in && !c.ln_out;
     // a handful of fp32 rows against a wide weight matrix: stream the weights once (gemm.hip's tiles would spend a 128-row
     // tile on <= 4 rows and run at a third of the HBM rate)
-    if (opt_gemv && plain && p.M <= 4 && m.taps == 1 && in_dt == DT_F32 && out_dt == DT_F32 && !c.R && !c.rowvec && !c.VT && c.act == 0 &&
+    if (opt.gemv && plain && p.M <= 4 && m.taps == 1 && in_dt == DT_F32 && out_dt == DT_F32 && !c.R && !c.rowvec && !c.VT && c.act == 0 &&
         !m.geglu && c.scale == 1.f && !c.ln_in && !c.ln_out && m.K % 8 == 0 && m.K <= 2048 && m.N >= 4096) {
         pl.family = GEMM_GEMV;
         return pl;
     }
     // a decoder Upsample conv (bias only) with folded weights: four 2x2-tap phase convs over the source, 4/9 of the products, where the
     // phase grid fills the chip like an unsplit patch launch (the 8x8 -> 16x16 level, batch-1 grids and every ad-hoc weight stay below)
-    if (opt_ups_fold && c.ups == 1 && m.w_up && plain && !c.ln_in && !c.ln_out && conv_upfold_eligible(p, P) &&
-        (opt_ups_fold_tiles < 0 ? patch_unsplit(conv_upfold_tiles(p)) : conv_upfold_tiles(p) >= opt_ups_fold_tiles)) {
+    if (opt.ups_fold && c.ups == 1 && m.w_up && plain && !c.ln_in && !c.ln_out && conv_upfold_eligible(p, P) &&
+        (opt.ups_fold_tiles < 0 ? patch_unsplit(conv_upfold_tiles(p)) : conv_upfold_tiles(p) >= opt.ups_fold_tiles)) {
         pl.family = GEMM_UPFOLD;
         return pl;
     }
@@ -839,10 +841,10 @@ GemmPlan pd_engine::plan_gemm(const GemmParams& p, const WMat& m, const GemmCall
     bool use_patch = patch_unsplit(ptiles);
     // 16x16-level convs: too few 16x16 patches for the chip, but the patch kernel still beats the generic gather when the
     // channel chunks are split across 2-4 slices (fp32 slabs + the same deterministic finalize pass as the GEMM's split-K)
-    if (!use_patch && opt_patch_split && ptiles >= opt_patch_split_tiles && !c.gn_coef && m.N % 4 == 0) {
+    if (!use_patch && opt.patch_split && ptiles >= fill.patch_split_tiles && !c.gn_coef && m.N % 4 == 0) {
         const int chunks = p.Cin / (f32 ? 32 : 64);
-        int sk = (opt_patch_split_fill + ptiles - 1) / ptiles;
-        if (sk > chunks / opt_patch_split_min) sk = chunks / opt_patch_split_min;   // at least this many channel chunks per slice
+        int sk = (fill.patch_split_fill + ptiles - 1) / ptiles;
+        if (sk > chunks / opt.patch_split_min) sk = chunks / opt.patch_split_min;   // at least this many channel chunks per slice
         if (sk > 4) sk = 4;
         while (sk >= 2 && (sk - 1) * ((chunks + sk - 1) / sk) >= chunks) --sk;       // no empty slice
         if (sk >= 2) { use_patch = true; pl.splitk = sk; }
@@ -851,10 +853,10 @@ GemmPlan pd_engine::plan_gemm(const GemmParams& p, const WMat& m, const GemmCall
         pl.defer_finalize = pl.splitk > 1 && may_defer;
         // second-generation (wave-specialised) patch kernel where it measures faster: many blocks per CU (its longer prologue
         // amortises) or the split-K 16x16 level; the 2-round 64x64 launches stay on the first generation (152 vs 142 us)
-        const bool patch2 = opt_patch2 && !f32 && !c.gn_coef && (pl.splitk > 1 || ptiles >= opt_patch2_tiles);
+        const bool patch2 = opt.conv_patch2 && !f32 && !c.gn_coef && (pl.splitk > 1 || ptiles >= fill.conv_patch2_tiles);
         // fourth generation (4 waves per block, one per SIMD, 32x32x16 MFMAs, LDS-DMA operands): every unsplit 2-byte launch (-4..-8 % at
         // batch 8, -17..-19 % at batch 1 against the faster of the first two; split-K launches tie and stay on the second)
-        const bool patch4 = opt_patch4 && pl.splitk == 1 && conv_patch4_eligible(p, P);
+        const bool patch4 = opt.patch4 && pl.splitk == 1 && conv_patch4_eligible(p, P);
         pl.family = patch4 ? GEMM_PATCH4 : patch2 ? GEMM_PATCH2 : GEMM_PATCH1;
         return pl;
     }
@@ -864,65 +866,65 @@ GemmPlan pd_engine::plan_gemm(const GemmParams& p, const WMat& m, const GemmCall
     int splitk = 1;
     // small-M linear layers (the 8x8 level's M = 1024: 64 tiles of 128 x 160): 64 x 80 ring tiles fill the chip without split-K slabs and
     // a finalize pass (every CU then streams 1 / 16 of the weight matrix once instead of 1 / 8 of a K slice + the slab traffic)
-    const bool small_ring = opt_ring > 0 && opt_ring_small && m.taps == 1 && !fp8 && !m.geglu && in_dt == T && ktiles <= opt_ring && tiles * opt_ring_small <= ncu &&
-                            ((p.M + 63) / 64) * ((m.N + 79) / 80) >= ncu / 2 && ring_gemm_eligible(p, P);
+    const bool small_ring = opt.ring > 0 && opt.ring_small && m.taps == 1 && !fp8 && !m.geglu && in_dt == T && ktiles <= opt.ring && tiles * opt.ring_small <= fill.whole &&
+                            ((p.M + 63) / 64) * ((m.N + 79) / 80) >= fill.half && ring_gemm_eligible(p, P);
     // linear layers with a short K and at least half a chip of tiles: one 8-wave block per CU instead of split-K
-    const bool dense8 = opt_dense_k > 0 && m.taps == 1 && in_dt == T && !fp8 && !m.geglu && ktiles <= opt_dense_k && tiles >= opt_dense_tiles;
+    const bool dense8 = opt.dense_k > 0 && m.taps == 1 && in_dt == T && !fp8 && !m.geglu && ktiles <= opt.dense_k && tiles >= fill.dense_tiles;
     const int kmin = fp8 ? 8 : 16, kper = fp8 ? 4 : 8;   // an e4m3 K step carries twice the K of a 2-byte one
-    if (allow_splitk && !small_ring && !dense8 && !m.geglu && !c.VT && tiles < opt_splitk_tiles && tiles <= kTileCnt && ktiles >= kmin && m.N % 4 == 0) {
-        splitk = (2 * ncu + tiles - 1) / tiles;   // about two blocks per CU
+    if (allow_splitk && !small_ring && !dense8 && !m.geglu && !c.VT && tiles < fill.splitk_tiles && tiles <= kTileCnt && ktiles >= kmin && m.N % 4 == 0) {
+        splitk = (fill.two_per_cu + tiles - 1) / tiles;   // about two blocks per CU
         if (splitk > ktiles / kper) splitk = ktiles / kper;
-        if (splitk > opt_splitk_max) splitk = opt_splitk_max;
+        if (splitk > opt.splitk_max) splitk = opt.splitk_max;
         if (splitk < 1) splitk = 1;
     }
     pl.splitk = splitk;
-    pl.fused_tile_cnt = splitk > 1 && opt_splitk_fused;
+    pl.fused_tile_cnt = splitk > 1 && opt.splitk_fused;
     // split-K conv3x3 with at least 1024 rows (the 8x8 level at batch 8): 256-row tiles halve the weight bytes each slice streams
     // (every M tile reads the whole [160 x K / splitk] weight panel) when 256-row tiles x slices still give every CU a block
-    const bool sk256 = opt_splitk_big && splitk > 1 && !pl.fused_tile_cnt && m.taps == 9 && !f32 && p.M >= 1024 &&
-                       ((p.M + 255) / 256) * ((m.N + 159) / 160) * splitk >= ncu;
+    const bool sk256 = opt.splitk_big && splitk > 1 && !pl.fused_tile_cnt && m.taps == 9 && !f32 && p.M >= 1024 &&
+                       ((p.M + 255) / 256) * ((m.N + 159) / 160) * splitk >= fill.whole;
     // the consumer sums the slabs itself (SlabDefer)
     pl.defer_finalize = may_defer && splitk > 1 && !pl.fused_tile_cnt && !m.geglu;
     // 256-row tiles when they still give every CU a block (1 block of 8 waves per CU)
-    pl.big_tile = ((opt_bigtile && splitk == 1 && ((p.M + 255) / 256) * ((m.N + 159) / 160) >= ncu) || sk256) ? 1 : 0;
-    if (dense8 && tiles < opt_splitk_tiles) pl.big_tile = 2;
+    pl.big_tile = ((opt.big_tile && splitk == 1 && ((p.M + 255) / 256) * ((m.N + 159) / 160) >= fill.whole) || sk256) ? 1 : 0;
+    if (dense8 && tiles < fill.splitk_tiles) pl.big_tile = 2;
     // 256 x 320 tiles for linear layers that still give (almost) every CU a block
     {
         const int t3 = ((p.M + 255) / 256) * ((m.N + 319) / 320);
-        const int rounds = (t3 + ncu - 1) / ncu;
-        if (opt_wide && splitk == 1 && m.taps == 1 && in_dt == T && t3 >= ncu && t3 * 100 >= rounds * ncu * 85) pl.big_tile = 3;
+        const int rounds = (t3 + fill.whole - 1) / fill.whole;
+        if (opt.wide_tile && splitk == 1 && m.taps == 1 && in_dt == T && t3 >= fill.whole && t3 * 100 >= rounds * fill.whole * 85) pl.big_tile = 3;
     }
     // short-K linear layers are HBM-bound (K <= 1280: 1.5-2.5x their traffic floor): what they need is loads and
     // stores of one tile overlapping the MFMAs of others, i.e. many waves per CU rather than a big tile -- the
     // 128 x 160 tile on 8 waves at <= 128 VGPRs runs 2 blocks = 16 waves per CU (+0.6 % end-to-end, interleaved A/B)
-    if (opt_short_k > 0 && splitk == 1 && m.taps == 1 && in_dt == T && !m.geglu && ktiles <= opt_short_k) pl.big_tile = 2;
+    if (opt.short_k > 0 && splitk == 1 && m.taps == 1 && in_dt == T && !m.geglu && ktiles <= opt.short_k) pl.big_tile = 2;
     // widths that are multiples of 192 but not of 160 (MMDiT hidden size 1536 and its 3x / 4x): the 256 x 192 tile
-    if (opt_tile192 && !f32 && P != PREC_F16X2 && splitk == 1 && m.taps == 1 && (in_dt == T || fp8) && !m.geglu && m.N % 192 == 0 && m.N % 160 != 0 &&
-        ((p.M + 255) / 256) * (m.N / 192) >= ncu * 3 / 4)
+    if (opt.tile192 && !f32 && P != PREC_F16X2 && splitk == 1 && m.taps == 1 && (in_dt == T || fp8) && !m.geglu && m.N % 192 == 0 && m.N % 160 != 0 &&
+        ((p.M + 255) / 256) * (m.N / 192) >= fill.three_quarters)
         pl.big_tile = 4;
     if (P == PREC_F16X2 && m.geglu && pl.big_tile == 3) pl.big_tile = 1;   // the 256 x 320 GEGLU tile spills with the split-operand fragments
     // short reductions over 2-byte operands: the persistent ring kernel (gemm_ring.hip); 256-row tiles when they give
     // (almost) every CU one
-    if (opt_ring > 0 && splitk == 1 && !fp8 && ktiles <= opt_ring && (p.act != 2 || opt_ring_geglu) && ring_gemm_eligible(p, P)) {
+    if (opt.ring > 0 && splitk == 1 && !fp8 && ktiles <= opt.ring && (p.act != 2 || opt.ring_geglu) && ring_gemm_eligible(p, P)) {
         pl.family = GEMM_RING;
-        pl.ring_tile = opt_ring_tile >= 0 ? opt_ring_tile : small_ring ? 4 : (((p.M + 255) / 256) * ((m.N + 159) / 160) >= ncu * 7 / 8 ? 1 : 0);
+        pl.ring_tile = opt.ring_tile >= 0 ? opt.ring_tile : small_ring ? 4 : (((p.M + 255) / 256) * ((m.N + 159) / 160) >= fill.seven_eighths ? 1 : 0);
         // ping-pong form (two wave groups half a K step apart; bit-identical): -10..-14 % on long reductions and -3..-5 % on one
         // 256-row tile per CU; +6..+13 % where a block walks several short tiles (the groups' epilogues serialise) -- tools/micro/ring_pp.hip
-        if (opt_ring_pp && pl.ring_tile < 2 && p.act != 2 && !small_ring) {
+        if (opt.ring_pp && pl.ring_tile < 2 && p.act != 2 && !small_ring) {
             const int bm = pl.ring_tile ? 256 : 128;
             const int nblk = ((p.M + bm - 1) / bm) * ((m.N + 159) / 160);
-            if (ktiles >= 40 || (pl.ring_tile == 1 && nblk <= ncu)) pl.ring_tile += 2;
+            if (ktiles >= 40 || (pl.ring_tile == 1 && nblk <= fill.whole)) pl.ring_tile += 2;
         }
         pl.big_tile = 0;
     }
     // options "gemm_tile" / "gemm_splitk" (test surface; -1 by default): the tile and the slice count of an igemm-family launch
-    if (pl.family == GEMM_IGEMM && opt_gemm_tile >= 0) pl.big_tile = opt_gemm_tile;
-    if (pl.family == GEMM_IGEMM && opt_gemm_splitk >= 1) {
-        int want = allow_splitk ? opt_gemm_splitk : 1;
+    if (pl.family == GEMM_IGEMM && opt.gemm_tile >= 0) pl.big_tile = opt.gemm_tile;
+    if (pl.family == GEMM_IGEMM && opt.gemm_splitk >= 1) {
+        int want = allow_splitk ? opt.gemm_splitk : 1;
         if (want > ktiles) want = ktiles;   // no more slices than K steps (what launch_gemm does not split -- GEGLU, a V^T side output -- it refuses)
         if (want != splitk) {
             splitk = pl.splitk = want;
-            pl.fused_tile_cnt = splitk > 1 && opt_splitk_fused && tiles <= kTileCnt;
+            pl.fused_tile_cnt = splitk > 1 && opt.splitk_fused && tiles <= kTileCnt;
             pl.defer_finalize = may_defer && splitk > 1 && !pl.fused_tile_cnt;
         }
     }
@@ -966,8 +968,8 @@ int pd_engine::gemm(const WMat& m, const Act& in, Act& out, const GemmCall& c) {
     gemm_family = pl.family; gemm_splitk = p.splitk;
     gemm_ring_tile = ring ? pl.ring_tile : -1;
     gemm_tile = pl.family == GEMM_IGEMM ? gemm_launched_tile(p, in.dt == DT_FP8 ? PREC_FP8 : P) : 0;
-    if (opt_gemm_tile >= 0 && pl.family == GEMM_IGEMM && gemm_tile != opt_gemm_tile) {   // option "gemm_tile": no quiet move to another tile
-        pd_set_error("gemm: option gemm_tile %d, but this launch (mode, operands, epilogue, %d slices) has the tile %d instantiation only", opt_gemm_tile, p.splitk, gemm_tile);
+    if (opt.gemm_tile >= 0 && pl.family == GEMM_IGEMM && gemm_tile != opt.gemm_tile) {   // option "gemm_tile": no quiet move to another tile
+        pd_set_error("gemm: option gemm_tile %d, but this launch (mode, operands, epilogue, %d slices) has the tile %d instantiation only", opt.gemm_tile, p.splitk, gemm_tile);
         return 1;
     }
     ProfRec rec{};
@@ -991,12 +993,12 @@ int pd_engine::gemm(const WMat& m, const Act& in, Act& out, const GemmCall& c) {
         return 0;
     }
     static const char* const family_name[] = {"gemv", "patch1", "patch2", "patch4", "ring", "igemm", "upfold"};
-    if (verbose >= 2)   // dispatch trace (option "verbose" 2): which kernel family / tile / split a launch takes
+    if (opt.verbose >= 2)   // dispatch trace (option "verbose" 2): which kernel family / tile / split a launch takes
         fprintf(stderr, "[pdengine] gemm M %d N %d K %d taps %d stride %d ups %d: %s splitk %d big_tile %d ring_tile %d act %d R %d ln_in %d ln_out %d\n", p.M, p.N, p.K, p.taps,
                 p.stride, p.ups, family_name[pl.family], p.splitk, p.big_tile, pl.ring_tile, p.act, p.R ? 1 : 0, p.ln_stats ? 1 : 0, p.stats_out ? 1 : 0);
     const int prec = in.dt == DT_FP8 ? PREC_FP8 : P;
     const int r = pl.family == GEMM_UPFOLD ? launch_conv_upfold(p, m.w_up, P, stream) : pl.family == GEMM_PATCH4 ? launch_conv_patch4(p, P, stream) : pl.family == GEMM_PATCH2 ? launch_conv_patch2(p, P, stream) :
-                  pl.family == GEMM_PATCH1 ? launch_conv_patch(p, P, stream) : ring ? launch_ring_gemm(p, prec, pl.ring_tile, stream) : launch_gemm(p, prec, stream, mid);
+                  pl.family == GEMM_PATCH1 ? launch_conv_patch(p, P, stream) : ring ? launch_ring_gemm(p, prec, pl.ring_tile, ncu, stream) : launch_gemm(p, prec, stream, mid);
     if (r) { pd_set_error("gemm launch failed: %s", hipGetErrorString(hipGetLastError())); return 1; }
     if (ring) ++ring_launches;
     if (pl.family == GEMM_UPFOLD) ++ups_fold_launches;
@@ -1037,23 +1039,23 @@ int pd_engine::gn_stats(const Act& x, int& nchunk) {
 
 int pd_engine::groupnorm(const Act& x, Act& y, const float* g, const float* b, float eps, bool silu, const SlabDefer* from_slabs) {
     if (from_slabs && from_slabs->active) {   // x was never written: the producing GEMM's split-K slabs are the input
-        if (!(opt_gn_single && gn_fused_bundle(x.dt, x.H * x.W, x.C, 32))) { pd_set_error("internal: deferred split-K slabs without the single-kernel GroupNorm"); return 1; }
+        if (!(opt.gn_single && gn_fused_bundle(x.dt, x.H * x.W, x.C, 32, opt.gn_reg))) { pd_set_error("internal: deferred split-K slabs without the single-kernel GroupNorm"); return 1; }
         if (arena.dry) return 0;
         PD_TRY(check_arena());
         ++launches;
         ++gn_from_slabs;
         if (launch_gn_fused_slabs(from_slabs->slabs, from_slabs->nslab, from_slabs->bias, from_slabs->rowvec, from_slabs->rowvec_stride, x.dt, y.p, y.dt, g, b,
-                                  x.B, x.H * x.W, x.C, 32, eps, silu ? 1 : 0, stream, &gn_kernel)) {
+                                  x.B, x.H * x.W, x.C, 32, eps, silu ? 1 : 0, opt.gn_reg, stream, &gn_kernel)) {
             pd_set_error("groupnorm (single kernel, split-K slabs) launch failed (C=%d)", x.C);
             return 1;
         }
         return 0;
     }
-    if (opt_gn_single && gn_fused_bundle(x.dt, x.H * x.W, x.C, 32)) {   // slab fits in LDS: one kernel, one read
+    if (opt.gn_single && gn_fused_bundle(x.dt, x.H * x.W, x.C, 32, opt.gn_reg)) {   // slab fits in LDS: one kernel, one read
         if (arena.dry) return 0;
         PD_TRY(check_arena());
         ++launches;
-        if (launch_gn_fused(x.p, x.dt, y.p, y.dt, g, b, x.B, x.H * x.W, x.C, 32, eps, silu ? 1 : 0, stream, &gn_kernel)) {
+        if (launch_gn_fused(x.p, x.dt, y.p, y.dt, g, b, x.B, x.H * x.W, x.C, 32, eps, silu ? 1 : 0, opt.gn_reg, stream, &gn_kernel)) {
             pd_set_error("groupnorm (single kernel) launch failed (C=%d)", x.C);
             return 1;
         }
@@ -1076,7 +1078,7 @@ int pd_engine::groupnorm(const Act& x, Act& y, const float* g, const float* b, f
 int pd_engine::conv_gn(const ConvW& c, const Act& x, Act& out, const float* g, const float* b, float eps, bool silu, GemmCall call,
                        const SlabDefer* in_slabs) {
     call.stride = c.stride; call.pad_shift = c.pad_shift; call.dilation = c.dilation;
-    const bool fuse = opt_gn_fuse && x.C == c.m.cin_pad && patch_unsplit(patch_tiles(fill_gemm(c.m, x, out, call)));
+    const bool fuse = opt.gn_fuse && x.C == c.m.cin_pad && patch_unsplit(patch_tiles(fill_gemm(c.m, x, out, call)));
     if (!fuse) {
         const size_t mk = arena.mark();
         Act a = new_act(x.B, x.H, x.W, x.C, T);
@@ -1129,7 +1131,7 @@ int pd_engine::attention(const void* Q, int ldq, const void* K, int ldk, const v
     p.scale = (float)(1.0 / std::sqrt((double)p.dh));
     if (scale != 0.f) p.scale = scale;
     p.B = B;
-    p.legacy = opt_attn_legacy ? 1 : 0;
+    p.legacy = opt.attn_legacy ? 1 : 0;
     ++launches;
     ProfRec rec{};
     if (profiling) {
@@ -1153,7 +1155,7 @@ int pd_engine::resblock(const ResW& r, const Act& x, Act& out, const float* embr
     // conv1's only reader is norm2: when conv1 runs split-K and norm2 is the single-kernel GroupNorm (16x16 / 8x8 levels), that
     // kernel sums the slabs itself -- no finalize pass, h is never written
     SlabDefer d;
-    d.allow = opt_slab_gn && !opt_gn_fuse && opt_gn_single && h.dt == T && gn_fused_bundle(T, x.H * x.W, r.cout, 32) > 0;
+    d.allow = opt.slab_gn && !opt.gn_fuse && opt.gn_single && h.dt == T && gn_fused_bundle(T, x.H * x.W, r.cout, 32, opt.gn_reg) > 0;
     PD_TRY(conv_gn(r.conv1, x, h, r.gn1_g, r.gn1_b, r.eps, true, {.rowvec = embrow, .rowvec_stride = emb_stride, .defer = &d}));
     Act skip = x;
     if (r.has_skip) {
@@ -1184,7 +1186,7 @@ int pd_engine::transformer(const STW& s, const Act& x, Act& out, const KVSlot& k
     const int npad = round_up(N, 8);
     Act h, qk, vt, ln;
     LnStats st0, st1;
-    const bool fuse = (opt_ln_fuse < 0 ? !f32 : opt_ln_fuse != 0) && s.qkv.w_ln != nullptr;
+    const bool fuse = (opt.ln_fuse < 0 ? !f32 : opt.ln_fuse != 0) && s.qkv.w_ln != nullptr;
     if (fused) {
         // GroupNorm statistics -> per-(sample, channel) {scale, shift}; the apply, proj_in, norm1 and to_q/k/v are one kernel
         int nchunk = 1;
@@ -1487,10 +1489,10 @@ int pd_engine::forward_eps(int emb_row, int emb_stride, const float* scales, Act
     // B samples and are read twice.  Exact; what differs is only which tile shapes a half-size launch picks.  Needs the time embedding of a
     // step to be one row for the whole batch (emb_stride 0: the sampler's own calls).  Guess mode zeroes the unconditional half of every
     // control tensor (join_controlnet) and keeps the ControlNet unshared.
-    const bool share = opt_cfg_share && a.use_cfg && emb_stride == 0 && Bf % 2 == 0;
+    const bool share = opt.cfg_share && a.use_cfg && emb_stride == 0 && Bf % 2 == 0;
     ses.share_u = share;
     ses.share_c = share && ses.hint_shared && !a.guess_mode;
-    ses.cn_cond_only = opt_cfg_share && a.guess_mode && a.use_cfg && emb_stride == 0 && Bf % 2 == 0;
+    ses.cn_cond_only = opt.cfg_share && a.guess_mode && a.use_cfg && emb_stride == 0 && Bf % 2 == 0;
     // the 13 control tensors outlive the ControlNet pass
     int hh = a.h, ww = a.w;
     bool front = ses.share_c;
@@ -1503,7 +1505,7 @@ int pd_engine::forward_eps(int emb_row, int emb_stride, const float* scales, Act
     // ControlNet and the UNet encoder + middle block are independent: ControlNet is enqueued on a second stream with its
     // own workspace so that its kernels overlap the encoder's (different kernels meet on a CU in different phases: MFMA
     // main loops next to VALU-heavy epilogues / softmax).  The decoder waits for it (join_controlnet).
-    const bool two = opt_two_streams && stream2 != nullptr;
+    const bool two = opt.two_streams && stream2 != nullptr;
     if (two && !arena.dry) {
         HIP_OK(hipEventRecord(ev_fork, stream));
         HIP_OK(hipStreamWaitEvent(stream2, ev_fork, 0));

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/pdengine.h"
+#include "options.h"
 #include "pd_common.h"
 
 void pd_set_error(const char* fmt, ...);
@@ -403,6 +404,21 @@ struct GemmPlan {
     int stats_parts = 0;          // LayerNorm-statistics partials per row from this launch's own epilogue (0: none)
     bool patch() const { return family == GEMM_PATCH1 || family == GEMM_PATCH2 || family == GEMM_PATCH4; }
 };
+// The chip-fill rules of plan_gemm, the one place where the CU count enters the dispatch.  The tile-count options are numbers for a
+// 256-CU part and are scaled here (v * ncu / 256); the fractions of the chip that grids are compared against get their names.
+struct ChipFill {
+    int splitk_tiles, dense_tiles, conv_patch2_tiles, patch_split_tiles, patch_split_fill;   // the options of these names, scaled
+    int whole;            // a block for every CU: big_tile, wide_tile, splitk_big's 256-row tiles, ring_small's 1 / d of the chip, the ping-pong ring's one tile per CU
+    int three_quarters;   // a patch conv runs unsplit (192 of 256 CUs); the 256 x 192 tile (tile192)
+    int seven_eighths;    // the ring GEMM's 256-row tile
+    int half;             // ring_small: the 64 x 80 grid fills at least this much
+    int two_per_cu;       // split-K: slices to reach about two blocks per CU
+    ChipFill(const EngineOptions& o, int ncu)
+        : splitk_tiles(scaled(o.splitk_tiles, ncu)), dense_tiles(scaled(o.dense_tiles, ncu)), conv_patch2_tiles(scaled(o.conv_patch2_tiles, ncu)),
+          patch_split_tiles(scaled(o.patch_split_tiles, ncu)), patch_split_fill(scaled(o.patch_split_fill, ncu)), whole(ncu),
+          three_quarters(ncu * 3 / 4), seven_eighths(ncu * 7 / 8), half(ncu / 2), two_per_cu(2 * ncu) {}
+    static int scaled(int v, int ncu) { return (int)((long long)v * ncu / 256); }
+};
 
 // K [B][L][C], V^T [B][C][round_up(L, 8)]; P: the same in st_tail.hip's fragment order (fused blocks); L: context keys per sample (0: cfg.context_len)
 struct KVSlot { void* K = nullptr; void* VT = nullptr; void* P = nullptr; int L = 0; };
@@ -465,7 +481,7 @@ struct Session {
 struct pd_engine {
     pd_config cfg{};
     int device = 0;
-    int ncu = 256;      // compute units of the device (hipDeviceProp_t::multiProcessorCount): the tile / split-K rules scale with it
+    int ncu = 256;      // compute units of the device (hipDeviceProp_t::multiProcessorCount; stat "ncu"): the tile / split-K rules scale with it (ChipFill)
     hipStream_t stream = nullptr;
     void* comm = nullptr;   // ncclComm_t of pd_comm_init (comm.cpp); the final all-gather of a sharded batch
     int comm_world = 1, comm_rank = 0;
@@ -499,7 +515,7 @@ struct pd_engine {
     int* tile_cnt2 = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     bool cn_pending = false;
-    bool opt_two_streams = true;
+    EngineOptions opt;   // every pd_set_option knob (options.h): per engine, stored as given
     // FreeU (pd_set_freeu): {s1, s2, b1, b2}, all zero when off; per engine, read by run_unet at every decoder block
     float freeu[4] = {0.f, 0.f, 0.f, 0.f};
     bool freeu_on() const { return freeu[0] != 0.f && freeu[1] != 0.f && freeu[2] != 0.f && freeu[3] != 0.f; }
@@ -509,48 +525,9 @@ struct pd_engine {
     uint32_t rng_host[4] = {0u, 0u, 0u, 0u};
     uint64_t rng_seed = 0, rng_base = 0;
     long long graph_captures = 0, graph_replays = 0;   // stats: step loops captured / replayed
-    bool opt_cfg_share = true;   // option "cfg_share": the layers in front of the first cross-attention once per CFG pair (forward_eps)
     void swap_context();
     int join_controlnet();
     Session ses;
-    int verbose = 0;
-    bool opt_splitk_fused = false; // split-K sums + epilogue run in the last-arriving slice instead of a finalize kernel
-    int opt_splitk_max = 16;   // (8 until the end of round 4: the 8x8 level at batch 1 -- M = 128, 8 tiles -- then ran on 64 blocks; 16: +1.5 % at batch 1, nothing at batch 8)
-    int opt_splitk_big = 0;       // split-K conv3x3 on 256 x 160 tiles where that still fills the chip (option "splitk_big")
-    int opt_splitk_tiles = 256;   // (x ncu / 256 at build)   // split K when the 128x160 tile grid has fewer blocks than this (one tile per CU needs no split:
-                                  // 384 sent the 16x16 level's 5120 -> 1280 feed-forward-out GEMM -- 256 tiles -- to split-K 2 + a finalize pass, 86 us; the ring
-                                  // GEMM takes it unsplit in ~60: +0.5 % end to end)
-    bool opt_attn_legacy = false;  // debug: single-buffered attention kernel
-    bool opt_wide = true;      // 256 x 320 GEMM tiles for large-M linear layers
-    int opt_dense_tiles = 128;
-    bool opt_gn_single = true; // GroupNorm as one LDS-slab kernel where a sample's group bundle fits (32x32 and below)
-    bool opt_graph = false;    // pd_ddim_sample: capture the step loop in a hipGraph and replay it on later calls with the same arguments
-    int opt_ring = 80;         // linear layers with at most this many K steps (0: off) take gemm_ring.hip's persistent LDS-DMA ring kernel
-    int opt_ring_tile = -1;    // its tile: -1 auto, 0 = 128 x 160, 1 = 256 x 160
-    int opt_gemm_tile = -1;    // test surface: GemmPlan::big_tile of every igemm-family launch (-1: the plan's own)
-    int opt_gemm_splitk = -1;  // ... its K slices: -1 the plan's own, 1 never, n >= 2 that many where launch_gemm takes a split launch
-    int opt_ring_pp = 1;       // its ping-pong form where it measures faster (long K, or one 256-row tile per CU)
-    int opt_ring_geglu = 1;    // GEGLU projections too (256 x 160 on 8 x 1 waves)
-    int opt_ring_small = 4;    // small-M linear layers on 64 x 80 ring tiles instead of split-K (option "ring_small"): 0 off, d: where the 128 x 160 grid fills at most 1 / d of the chip
-    int opt_short_k = 20;      // linear layers with at most this many K steps: 8-wave 128x160 tile at 16 waves per CU
-    bool opt_patch_split = true;      // LDS-patch conv with the channel chunks split over 2-4 slices (16x16 level)
-    int opt_patch_split_tiles = 64;
-    bool opt_ups_fold = true;      // decoder Upsample convs as four 2x2-tap phase convs (2-byte modes)
-    int opt_ups_fold_tiles = -1;   // ... when the phase grid has at least this many blocks; -1: where patch_unsplit() admits an unsplit launch
-    int opt_patch_split_min = 4;      // ... each slice at least this many 128-byte channel chunks.  (min 1 / tiles 32 measured +2.3 % at batch 1 and
-                                      // neutral at batch 8, but re-associates the sums of the 256x256 parity fixture's convs: its step-0 latent error
-                                      // moves from 7.4e-4 to 1.02e-3 -- same arithmetic, other rounding pattern -- so the defaults stay)
-    int opt_patch_split_fill = 256;   // slices are chosen to reach about this many blocks
-    int opt_dense_k = 40;      // linear layers with at most this many K steps and >= opt_dense_tiles tiles: one 8-wave block per CU, no split-K
-    bool opt_bigtile = true;  // 256-row GEMM tiles where the grid still fills the chip
-    bool opt_tile192 = true;  // 256 x 192 GEMM tiles for widths that divide by 192 but not by 160 (MMDiT)
-    // apply GroupNorm(+SiLU) inside the patch conv's staging.  Measured neutral-to-negative in round 1 (the SiLU VALU work
-    // lands on the MFMA waves and the halo is transformed 1.27x redundantly), so it is off by default.
-    bool opt_gn_fuse = false;
-    bool opt_patch = true;  // use the LDS-patch conv3x3 kernel where eligible
-    bool opt_patch2 = true; // 2-byte modes: the wave-specialised second-generation patch kernel (conv_patch2.hip)
-    bool opt_patch4 = true; // 2-byte modes: the 4-wave patch kernel (conv_patch4.hip) for unsplit launches
-    int opt_patch2_tiles = 768;   // ... for launches of at least this many blocks (and every split-K patch launch)
     long long launches = 0;
     long long gn_from_slabs = 0;   // GroupNorm launches that summed a split-K GEMM's slabs (stat "gn_from_slabs")
     long long ring_launches = 0;   // launches that took gemm_ring.hip (stat "ring_launches")
@@ -596,7 +573,6 @@ struct pd_engine {
     // SD3's VAE (sd3_vae.cpp, pd_sd3_vae_configure): the same layers under a description of its own
     VaeW sd3_vae;
     VaeEncW sd3_vae_enc;
-    int opt_vae_flash = -1;          // option "vae_flash": -1 per VAE (VaeDesc::flash_auto), 0 / 1 forced; 2-byte modes only
     long long vae_flash_launches = 0;
     bool vae_flash_on(const VaeDesc& d, int C, long long N) const;   // N: tokens per sample
     // scale / shift: what the layout kernel applies to the latents (decode) or the posterior kernel to z (encode)
@@ -728,11 +704,8 @@ struct pd_engine {
     int sd3_t5_forward(const int* ids_dev, int B, int Lt, float* out, int out_rows, int row_off);
     int t5_block(const T5LayerW& l, Act& x, const float* relbias);
     int rmsnorm(const Act& x, void* y, int y_dt, const float* w, float eps, int y_sample_rows = 0, int y_row_off = 0, int y_ld = 0);
-    int opt_slab_gn = 1;             // split-K conv1 -> single-kernel norm2 without a finalize pass (SlabDefer; option "slab_gn")
-    int opt_sd3_fp8 = 0;       // 0 off, 1: the AdaLN-fed projections, 2: also the feed-forward-out projections (e4m3 GELU output under a norm bound)  // SD3 path: QKV and feed-forward-in projections in PREC_FP8 (e4m3 operands, per-row scales)
-    bool sd3_fp8_dirty = true;
-    int sd3_quantize();        // (re)builds the e4m3 weights of those layers after a weight change
-    bool opt_gemv = true;     // Linear over <= 4 fp32 rows with a wide output (MMDiT modulation): weight-streaming kernel instead of a GEMM tile
+    bool sd3_fp8_dirty = true;   // option "sd3_fp8" or a weight changed: sd3_quantize() has work to do
+    int sd3_quantize();        // (re)builds the e4m3 weights of the layers option "sd3_fp8" names after a weight change
 
     // LoRA adapters merged in place into matrix parameters (lora.cpp, lora.hip).  A target is one Param that at least one
     // adapter touches: its base rows W0 in T (all m.N rows of a GEGLU matrix), and every adapter's up^T / down stacked in load
@@ -790,14 +763,13 @@ struct pd_engine {
     int check_gemm(const WMat& m, const Act& in, const Act& out, const GemmCall& c) const;
     static GemmParams fill_gemm(const WMat& m, const Act& in, const Act& out, const GemmCall& c);
     GemmPlan plan_gemm(const GemmParams& p, const WMat& m, const GemmCall& c, bool allow_splitk = true) const;
+    ChipFill chip_fill() const { return ChipFill(opt, ncu); }
     int patch_tiles(const GemmParams& p) const; bool patch_unsplit(int ptiles) const;
     int fold_upconv(WMat& m);   // (re)builds m.w_up from m.w; fold_upconvs(): for every UNet decoder Upsample conv the dispatch can take
     int fold_upconvs();
     bool upfold_wanted(const WMat& m) const;
     int fold_layernorms();     // (re)builds the folded weights of every transformer block after a weight change
     bool ln_dirty = true;
-    int opt_ln_fuse = -1;      // -1: on in the 2-byte modes, off in the fp32-storage modes; 0 / 1: forced
-    bool opt_st_fuse = true;   // 320-channel SpatialTransformer blocks: one kernel for everything after self-attention (2-byte modes)
     bool st_tail_on(const STW& s, int rows_per_sample, int L) const;   // L: context keys of the call
     int gn_stats(const Act& x, int& nchunk);
     // conv3x3 / conv1x1 of `c`: call.stride and call.pad_shift come from the ConvW.  conv_gn: conv(act(GroupNorm(x))); call carries the

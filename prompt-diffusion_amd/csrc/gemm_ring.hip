@@ -372,21 +372,8 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void rgemm_kernel(GemmParams p) {
     })
 }
 
-int device_ncu() {   // 0: unknown
-    static int ncu_of[64] = {};   // per device id (engines on different devices share the process)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    int& ncu = ncu_of[dev & 63];
-    if (!ncu) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
-        ncu = prop.multiProcessorCount;
-    }
-    return ncu;
-}
-
 template <int P, int BM, int BN, int WM, int WN, int NS, bool GG = false, bool PP = false>
-int launch_ring(const GemmParams& p, hipStream_t s, int* parts) {
+int launch_ring(const GemmParams& p, int ncu, hipStream_t s, int* parts) {
     constexpr int SMEM_BYTES = NS * (BM + BN) * BKB + BM * 8 * (PP ? 2 : 1);
     static_assert(SMEM_BYTES <= 160 * 1024, "LDS");
     static unsigned long long attr_done = 0;
@@ -395,7 +382,6 @@ int launch_ring(const GemmParams& p, hipStream_t s, int* parts) {
     auto kfn = rgemm_kernel<P, BM, BN, WM, WN, NS, GG, PP>;
     if (ensure_dyn_smem(reinterpret_cast<const void*>(kfn), SMEM_BYTES, &attr_done)) return 1;
     if (p.stats_out && p.stats_parts != ntiles * WN) return 1;
-    const int ncu = device_ncu();
     if (ncu < 8) return 1;
     int grid = nblk < ncu ? (nblk + 7) / 8 * 8 : ncu / 8 * 8;
     hipLaunchKernelGGL(kfn, dim3(grid), dim3(WM * WN * 64), SMEM_BYTES, s, p);
@@ -420,23 +406,23 @@ bool ring_gemm_eligible(const GemmParams& p, int prec) {
 
 // tile: 0 = 128 x 160 (4 stages), 1 = 256 x 160 (3 stages); both 4 x 2 waves; 2 / 3 their ping-pong forms; 4 = 64 x 80 on 4 x 1 waves (5 stages).
 // GEGLU layers (act 2): 256 x 160 on 8 x 1 waves.
-int launch_ring_gemm(const GemmParams& p, int prec, int tile, hipStream_t s, int* parts) {
+int launch_ring_gemm(const GemmParams& p, int prec, int tile, int ncu, hipStream_t s, int* parts) {
     if (!ring_gemm_eligible(p, prec)) return 1;
     if (p.act == 2) {   // 256 x 160 on 8 x 1 waves (a wave: 32 rows x one GEGLU block)
-        return prec == DT_F16 ? launch_ring<DT_F16, 256, 160, 8, 1, 3, true>(p, s, parts) : launch_ring<DT_BF16, 256, 160, 8, 1, 3, true>(p, s, parts);
+        return prec == DT_F16 ? launch_ring<DT_F16, 256, 160, 8, 1, 3, true>(p, ncu, s, parts) : launch_ring<DT_BF16, 256, 160, 8, 1, 3, true>(p, ncu, s, parts);
     }
     if (tile == 4) {   // 64 x 80 on 4 x 1 waves (16 rows x 80 columns per wave), 5 stages: small-M layers (the 8x8 level's M = 1024: 256 tiles instead of 64)
-        return prec == DT_F16 ? launch_ring<DT_F16, 64, 80, 4, 1, 5>(p, s, parts) : launch_ring<DT_BF16, 64, 80, 4, 1, 5>(p, s, parts);
+        return prec == DT_F16 ? launch_ring<DT_F16, 64, 80, 4, 1, 5>(p, ncu, s, parts) : launch_ring<DT_BF16, 64, 80, 4, 1, 5>(p, ncu, s, parts);
     }
     if (tile >= 2) {   // ping-pong forms: 2 = 128 x 160, 3 = 256 x 160
-        if (prec == DT_F16) return tile == 3 ? launch_ring<DT_F16, 256, 160, 4, 2, 3, false, true>(p, s, parts) : launch_ring<DT_F16, 128, 160, 4, 2, 4, false, true>(p, s, parts);
-        return tile == 3 ? launch_ring<DT_BF16, 256, 160, 4, 2, 3, false, true>(p, s, parts) : launch_ring<DT_BF16, 128, 160, 4, 2, 4, false, true>(p, s, parts);
+        if (prec == DT_F16) return tile == 3 ? launch_ring<DT_F16, 256, 160, 4, 2, 3, false, true>(p, ncu, s, parts) : launch_ring<DT_F16, 128, 160, 4, 2, 4, false, true>(p, ncu, s, parts);
+        return tile == 3 ? launch_ring<DT_BF16, 256, 160, 4, 2, 3, false, true>(p, ncu, s, parts) : launch_ring<DT_BF16, 128, 160, 4, 2, 4, false, true>(p, ncu, s, parts);
     }
-    if (prec == DT_F16) return tile ? launch_ring<DT_F16, 256, 160, 4, 2, 3>(p, s, parts) : launch_ring<DT_F16, 128, 160, 4, 2, 4>(p, s, parts);
-    return tile ? launch_ring<DT_BF16, 256, 160, 4, 2, 3>(p, s, parts) : launch_ring<DT_BF16, 128, 160, 4, 2, 4>(p, s, parts);
+    if (prec == DT_F16) return tile ? launch_ring<DT_F16, 256, 160, 4, 2, 3>(p, ncu, s, parts) : launch_ring<DT_F16, 128, 160, 4, 2, 4>(p, ncu, s, parts);
+    return tile ? launch_ring<DT_BF16, 256, 160, 4, 2, 3>(p, ncu, s, parts) : launch_ring<DT_BF16, 128, 160, 4, 2, 4>(p, ncu, s, parts);
 }
 
 int ring_gemm_stats_parts(const GemmParams& p, int prec, int tile) {
     int parts = 0;
-    return launch_ring_gemm(p, prec, tile, nullptr, &parts) ? 0 : parts;
+    return launch_ring_gemm(p, prec, tile, 0, nullptr, &parts) ? 0 : parts;   // (the parts-only path reads no ncu)
 }

@@ -11,7 +11,6 @@
 
 #include "pd_common.h"
 
-int g_gn_reg = 1;   // option "gn_reg": the register-resident single-kernel GroupNorm where it applies (process-wide)
 
 namespace {
 
@@ -746,10 +745,11 @@ int launch_gn_apply(const void* x, int x_dt, void* y, int y_dt, const double* pa
 
 // bundle width (channels) for gn_fused_kernel, or 0 when the shape is not eligible (slab beyond the LDS budget)
 static int gn_slab_bundle(int x_dt, int HW, int C, int groups);
-// > 0 when a single-kernel GroupNorm applies to this shape (either input form): the register-resident kernel, or gn_fused_kernel's bundle
-int gn_fused_bundle(int x_dt, int HW, int C, int groups) {
+// > 0 when a single-kernel GroupNorm applies to this shape (either input form): the register-resident kernel (reg: the caller's option
+// "gn_reg"), or gn_fused_kernel's bundle
+int gn_fused_bundle(int x_dt, int HW, int C, int groups, bool reg) {
     if (C % groups) return 0;
-    if (g_gn_reg && gn_reg_vb(x_dt, x_dt, HW, C, groups, true)) return C / groups;
+    if (reg && gn_reg_vb(x_dt, x_dt, HW, C, groups, true)) return C / groups;
     return gn_slab_bundle(x_dt, HW, C, groups);
 }
 static int gn_slab_bundle(int x_dt, int HW, int C, int groups) {
@@ -764,11 +764,11 @@ static int gn_slab_bundle(int x_dt, int HW, int C, int groups) {
 }
 
 int launch_gn_fused(const void* x, int x_dt, void* y, int y_dt, const float* gamma, const float* beta, int B, int HW, int C, int groups,
-                    float eps, int do_silu, hipStream_t s, int* kind) {
+                    float eps, int do_silu, bool reg, hipStream_t s, int* kind) {
     if (kind) *kind = 0;
     // (the same eligibility rule for both input forms: a shape must take the same kernel -- the same summation order -- whether its input
     // is a stored tensor or a split-K GEMM's slabs: test_split_k_slabs_into_groupnorm_is_bit_identical)
-    if (g_gn_reg && gn_reg_vb(x_dt, y_dt, HW, C, groups, true)) {
+    if (reg && gn_reg_vb(x_dt, y_dt, HW, C, groups, true)) {
         if (kind) *kind = GN_KIND_REGISTER;
         return launch_gn_reg<false>(x, x_dt, y, gamma, beta, B, HW, C, groups, eps, do_silu, GnSlabSrc{}, s);
     }
@@ -789,10 +789,10 @@ int launch_gn_fused(const void* x, int x_dt, void* y, int y_dt, const float* gam
 }
 
 int launch_gn_fused_slabs(const float* slabs, int nslab, const float* bias, const float* rowvec, int rowvec_stride, int x_dt, void* y, int y_dt,
-                          const float* gamma, const float* beta, int B, int HW, int C, int groups, float eps, int do_silu, hipStream_t s, int* kind) {
+                          const float* gamma, const float* beta, int B, int HW, int C, int groups, float eps, int do_silu, bool reg, hipStream_t s, int* kind) {
     if (kind) *kind = 0;
     if (!slabs || nslab < 1 || C % 4) return 1;
-    if (g_gn_reg && gn_reg_vb(x_dt, y_dt, HW, C, groups, true)) {
+    if (reg && gn_reg_vb(x_dt, y_dt, HW, C, groups, true)) {
         if (kind) *kind = GN_KIND_REGISTER;
         return launch_gn_reg<true>(nullptr, x_dt, y, gamma, beta, B, HW, C, groups, eps, do_silu,
                                    GnSlabSrc{slabs, (long long)B * HW * C, bias, rowvec, nslab, rowvec_stride}, s);

@@ -392,7 +392,7 @@ int pd_op_groupnorm_slabs(pd_engine* e, const float* slabs, int nslab, const flo
     if (nslab < 1 || B < 1 || C < 32 || C % 32 || H < 1 || W < 1) { pd_set_error("pd_op_groupnorm_slabs: need nslab, B, H, W >= 1 and C a positive multiple of 32"); return 1; }
     HIP_OK(hipSetDevice(e->device));
     const int HW = H * W;
-    if (!gn_fused_bundle(e->S, HW, C, 32)) { pd_set_error("pd_op_groupnorm_slabs: no single-kernel GroupNorm for C=%d HW=%d in this mode", C, HW); return 1; }
+    if (!gn_fused_bundle(e->S, HW, C, 32, e->opt.gn_reg)) { pd_set_error("pd_op_groupnorm_slabs: no single-kernel GroupNorm for C=%d HW=%d in this mode", C, HW); return 1; }
     const size_t n = (size_t)B * HW * C;
     DevBuf sl((size_t)nslab * n * 4), bi((size_t)C * 4 + 16), ro((size_t)B * C * 4 + 16), out(n * dt_size(e->T)), g((size_t)C * 4 + 16), b((size_t)C * 4 + 16);
     if (!sl.p || !bi.p || !ro.p || !out.p || !g.p || !b.p) { pd_set_error("allocation failed"); return 1; }
@@ -403,7 +403,7 @@ int pd_op_groupnorm_slabs(pd_engine* e, const float* slabs, int nslab, const flo
     HIP_OK(hipMemcpy(b.p, beta, (size_t)C * 4, hipMemcpyHostToDevice));
     if (launch_gn_fused_slabs(reinterpret_cast<const float*>(sl.p), nslab, bias ? reinterpret_cast<const float*>(bi.p) : nullptr,
                               row ? reinterpret_cast<const float*>(ro.p) : nullptr, C, e->S, out.p, e->T, reinterpret_cast<const float*>(g.p),
-                              reinterpret_cast<const float*>(b.p), B, HW, C, 32, eps, silu ? 1 : 0, e->stream, &e->gn_kernel)) {
+                              reinterpret_cast<const float*>(b.p), B, HW, C, 32, eps, silu ? 1 : 0, e->opt.gn_reg, e->stream, &e->gn_kernel)) {
         pd_set_error("pd_op_groupnorm_slabs: launch failed");
         return 1;
     }
@@ -657,7 +657,7 @@ int pd_op_vae_attention(pd_engine* e, const float* q, const float* k, const floa
     if (!e || !q || !k || !v || !o) { pd_set_error("null argument"); return 1; }
     if (B < 1 || N < 1 || C < 8 || C % 8) { pd_set_error("pd_op_vae_attention: need B, N >= 1 and C a multiple of 8"); return 1; }
     HIP_OK(hipSetDevice(e->device));
-    const bool flash = e->opt_vae_flash > 0;
+    const bool flash = e->opt.vae_flash > 0;
     if (flash && (e->f32 || !vae_attention_eligible(e->T, C))) {
         pd_set_error("pd_op_vae_attention: the flash kernel takes the 2-byte modes at C = 128 or 512 (got C = %d)", C);
         return 1;

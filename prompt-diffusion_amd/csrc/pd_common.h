@@ -259,9 +259,10 @@ int launch_gemm(const GemmParams& p, int prec, hipStream_t s, hipEvent_t mid = n
 int gemm_stats_parts(const GemmParams& p, int prec);
 int gemm_launched_tile(const GemmParams& p, int prec);   // the tile (GemmParams::big_tile numbering) of the instantiation launch_gemm takes for p
 int ring_gemm_stats_parts(const GemmParams& p, int prec, int tile);
-// gemm_ring.hip: persistent LDS-DMA ring GEMM for plain linear layers over 2-byte operands (tile 0: 128 x 160, 1: 256 x 160)
+// gemm_ring.hip: persistent LDS-DMA ring GEMM for plain linear layers over 2-byte operands (tile 0: 128 x 160, 1: 256 x 160); ncu: the
+// device's compute units (pd_engine::ncu), which size the persistent grid
 bool ring_gemm_eligible(const GemmParams& p, int prec);
-int launch_ring_gemm(const GemmParams& p, int prec, int tile, hipStream_t s, int* parts = nullptr);
+int launch_ring_gemm(const GemmParams& p, int prec, int tile, int ncu, hipStream_t s, int* parts = nullptr);
 // fp8 (e4m3) rows with one scale per row: dst[r][k] = e4m3(src[r][k] / scale[r]), scale[r] = max_k |src[r][k]| / 448 (weights of
 // the SD3 linear layers that run in PREC_FP8); src in dtype src_dt with row stride src_ld, dst row stride dst_ld >= K (pad zeroed)
 int launch_quant_rows(const void* src, int src_dt, int src_ld, void* dst, int dst_ld, float* scale, int rows, int K, hipStream_t s);
@@ -324,16 +325,17 @@ int launch_st_tail(const void* att, const void* h, const void* x_in, void* out, 
 int launch_gn_stats(const void* x, int x_dt, double* partial, int B, int HW, int C, int groups, int nchunk, hipStream_t s);
 int launch_gn_apply(const void* x, int x_dt, void* y, int y_dt, const double* partial, const float* gamma,
                     const float* beta, int B, int HW, int C, int groups, int nchunk, float eps, int silu, hipStream_t s);
-extern int g_gn_reg;   // norm.hip
 // which kernel a GroupNorm launch took (stat "gn_kernel": PD_GN_* in include/pdengine.h)
 enum { GN_KIND_TWO_PASS = 1, GN_KIND_LDS_SLAB = 2, GN_KIND_REGISTER = 3 };
-int gn_fused_bundle(int x_dt, int HW, int C, int groups);   // norm.hip: > 0 when the single-kernel GroupNorm applies
+// norm.hip: > 0 when the single-kernel GroupNorm applies.  reg (here and in the two launchers): the caller's option "gn_reg", the
+// register-resident kernel where the shape has one
+int gn_fused_bundle(int x_dt, int HW, int C, int groups, bool reg);
 int launch_gn_fused(const void* x, int x_dt, void* y, int y_dt, const float* gamma, const float* beta, int B, int HW, int C, int groups,
-                    float eps, int do_silu, hipStream_t s, int* kind = nullptr);   // kind: which kernel took it (GN_KIND_*)
+                    float eps, int do_silu, bool reg, hipStream_t s, int* kind = nullptr);   // kind: which kernel took it (GN_KIND_*)
 // the same kernel fed by a split-K GEMM's fp32 slabs instead of a stored tensor: x[row][c] = round_T(sum_s slab[s][row][c] + bias[c] +
 // rowvec[sample][c]) -- splitk_finalize_kernel's arithmetic and rounding, so the result is bit-identical to finalize + launch_gn_fused
 int launch_gn_fused_slabs(const float* slabs, int nslab, const float* bias, const float* rowvec, int rowvec_stride, int x_dt, void* y, int y_dt,
-                          const float* gamma, const float* beta, int B, int HW, int C, int groups, float eps, int do_silu, hipStream_t s, int* kind = nullptr);
+                          const float* gamma, const float* beta, int B, int HW, int C, int groups, float eps, int do_silu, bool reg, hipStream_t s, int* kind = nullptr);
 int launch_gn_coef(const double* partial, const float* gamma, const float* beta, float* coef, int B, int HW, int C, int groups,
                    int nchunk, float eps, hipStream_t s);
 // {sum, sum of squares} of every row: the single-part form of the LayerNorm statistics above (producers whose epilogue

@@ -211,7 +211,7 @@ int pd_engine::sd3_block(const Sd3BlockW& b, Act& x, Act& c, const Act& modbuf, 
     const size_t mk = arena.mark();
     // option sd3_fp8 (2-byte modes): the AdaLN outputs feeding the QKV and feed-forward-in projections are written as e4m3
     // with one scale per token, and those GEMMs run in PREC_FP8 against the layers' quantised weights
-    const bool f8 = opt_sd3_fp8 && !f32, f8b = opt_sd3_fp8 >= 2 && !f32;
+    const bool f8 = opt.sd3_fp8 && !f32, f8b = opt.sd3_fp8 >= 2 && !f32;
     const int NT = f8 ? DT_FP8 : T;
     // level 2: the feed-forward-out projection reads an e4m3 GELU output too.  No kernel sees a whole row of it before it
     // is written, so its row scale is a bound known beforehand: |GELU(W y + b)|_inf <= |y|_2 max_n |W_n|_2 + max |b|
@@ -312,14 +312,14 @@ int pd_engine::sd3_block(const Sd3BlockW& b, Act& x, Act& c, const Act& modbuf, 
 
 // e4m3 copies (one scale per output row) of the layers option sd3_fp8 runs in PREC_FP8
 int pd_engine::sd3_quantize() {
-    if (!opt_sd3_fp8 || f32 || !sd3_fp8_dirty) return 0;
+    if (!opt.sd3_fp8 || f32 || !sd3_fp8_dirty) return 0;
     float* red = nullptr;   // {max row norm, max |bias|} of one layer
     HIP_OK(hipMalloc(&red, 2 * sizeof(float)));
     int r = 0;
     for (Sd3NetW* net : {&sd3_tr, &sd3_cn}) {
         if (!net->built) continue;
         for (Sd3BlockW& b : net->blocks) {
-            const bool l2 = opt_sd3_fp8 >= 2;
+            const bool l2 = opt.sd3_fp8 >= 2;
             const bool cs = !b.pre_only && !b.single;   // the block has a context feed-forward
             WMat* mats[6] = {&b.qkv, b.single ? nullptr : &b.qkv_c, &b.ff1, cs ? &b.ffc1 : nullptr, l2 ? &b.ff2 : nullptr,
                              (l2 && cs) ? &b.ffc2 : nullptr};
@@ -367,7 +367,7 @@ int pd_engine::sd3_forward(const Sd3Io& io, float* v_out, int control_index, flo
     // transformer needs residual j only after its block ~ j * layers / residuals, so all but the first ControlNet block overlap
     // transformer work -- the two streams fill each other's tails (attention runs 2.2 rounds of blocks) and small launches.
     const bool have_cn = io.cond && (io.scale != 0.f || control_index >= 0);
-    const bool two = have_cn && opt_two_streams && stream2 != nullptr && control_index < 0;
+    const bool two = have_cn && opt.two_streams && stream2 != nullptr && control_index < 0;
     if (have_cn) {
         Sd3NetW& net = sd3_cn;
         for (int i = 0; i < net.layers; ++i) control.push_back(new_act(B, N, 1, D, control_index >= 0 ? DT_F32 : S));

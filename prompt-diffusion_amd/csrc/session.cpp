@@ -273,7 +273,7 @@ int pd_engine::session_setup(const pd_sample_args& a, const int64_t* t_rows, int
         s.hint_shared = a.use_cfg != 0 && (!a.pair_uncond || a.pair_uncond == a.pair) && (!a.query_uncond || a.query_uncond == a.query);
         // both halves of the CFG batch were given the same example pair and query: the hint embedders run on B samples and guided_hint's
         // second half is a copy of the first (option cfg_share; forward_eps)
-        const int hb = (s.hint_shared && opt_cfg_share) ? B : Bf;
+        const int hb = (s.hint_shared && opt.cfg_share) ? B : Bf;
         Act hint_out = s.hint;
         hint_out.B = hb;
         for (int which = 0; which < 2; ++which) {
@@ -352,7 +352,7 @@ int pd_engine::ensure_arena(int rows, bool per_step) {
         }
         a.base = reinterpret_cast<char*>(p);
         a.cap = want;
-        if (verbose) fprintf(stderr, "[pdengine] %s workspace %.2f GiB\n", what, (double)want / (1 << 30));
+        if (opt.verbose) fprintf(stderr, "[pdengine] %s workspace %.2f GiB\n", what, (double)want / (1 << 30));
         return 0;
     };
     if (need > arena.cap || need2 > arena2.cap) {
@@ -642,7 +642,7 @@ int pd_engine::run_steps_graph() {
     uint64_t key = 1469598103934665603ull;
     // (where the noise comes from is part of the key -- another kernel --, the seed is not: the kernels read it from rng_dev)
     const int32_t ints[] = {a.batch, a.h, a.w, a.steps, a.use_cfg, a.guess_mode, a.only_mid_control, ses.noise ? 1 : 0,
-                            ses.per_step ? 1 : 0, opt_two_streams ? 1 : 0, ses.S, opt_cfg_share ? 1 : 0, ses.noise_seeded ? 1 : 0, ses.L};
+                            ses.per_step ? 1 : 0, opt.two_streams ? 1 : 0, ses.S, opt.cfg_share ? 1 : 0, ses.noise_seeded ? 1 : 0, ses.L};
     const float flts[] = {a.eta, a.cfg_scale, a.temperature};
     const void* ptrs[] = {arena.base, arena2.base, ses.x_state, ses.per_step};
     hash_mix(key, ints, sizeof(ints));
@@ -722,10 +722,8 @@ int pd_engine_create(const pd_config* cfg, int device_id, pd_engine** out) {
     e->device = device_id;
     {
         hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device_id) == hipSuccess && prop.multiProcessorCount >= 8) {
-            e->ncu = prop.multiProcessorCount;
-            e->opt_splitk_tiles = e->opt_splitk_tiles * e->ncu / 256;   // the defaults are written for 256 CUs
-        }
+        // (the options stay as written, for 256 CUs: ChipFill scales them where the plan reads them)
+        if (hipGetDeviceProperties(&prop, device_id) == hipSuccess && prop.multiProcessorCount >= 8) e->ncu = prop.multiProcessorCount;
     }
     if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) {
         pd_set_error("hipStreamCreate failed");
@@ -961,7 +959,7 @@ int pd_sample_end(pd_engine* e) {
 static int run_sample(pd_engine* e, const pd_sample_args* args, const pd_unipc_args* u, const pd_lms_args* l, int32_t mem_out,
                       float* latents_out, float* per_step_out) {
     PD_TRY(e->begin(args, per_step_out != nullptr, u, l));
-    if (e->opt_graph && !e->profiling) {
+    if (e->opt.graph && !e->profiling) {
         PD_TRY(e->run_steps_graph());
     } else {
         for (int i = 0; i < e->ses.rows(); ++i) PD_TRY(e->step(i));
@@ -1028,88 +1026,6 @@ int pd_wait_stream(pd_engine* e, void* producer) {
     return 0;
 }
 
-int pd_set_option(pd_engine* e, const char* key, int64_t value) {
-    if (!e || !key) { pd_set_error("null argument"); return 1; }
-    if (!strcmp(key, "verbose")) { e->verbose = (int)value; return 0; }
-    e->clear_graphs();   // every other knob changes what a step launches
-    if (!strcmp(key, "gn_single")) { e->opt_gn_single = value != 0; return 0; }
-    if (!strcmp(key, "gn_reg")) { g_gn_reg = value != 0; return 0; }
-    if (!strcmp(key, "graph")) { e->opt_graph = value != 0; return 0; }
-    if (!strcmp(key, "conv_patch")) { e->opt_patch = value != 0; return 0; }
-    if (!strcmp(key, "conv_patch2")) { e->opt_patch2 = value != 0; return 0; }
-    if (!strcmp(key, "conv_patch2_tiles")) { e->opt_patch2_tiles = (int)value; return 0; }
-    if (!strcmp(key, "splitk_fused")) { e->opt_splitk_fused = value != 0; return 0; }
-    if (!strcmp(key, "splitk_big")) { e->opt_splitk_big = (int)value; return 0; }
-    if (!strcmp(key, "splitk_max")) { e->opt_splitk_max = (int)value; return 0; }
-    if (!strcmp(key, "splitk_tiles")) { e->opt_splitk_tiles = (int)value; return 0; }
-    if (!strcmp(key, "attn_legacy")) { e->opt_attn_legacy = value != 0; return 0; }
-    if (!strcmp(key, "gn_fuse")) { e->opt_gn_fuse = value != 0; return 0; }
-    if (!strcmp(key, "ln_fuse")) { e->opt_ln_fuse = (int)value; e->ln_dirty = true; return 0; }
-    if (!strcmp(key, "st_fuse")) { e->opt_st_fuse = value != 0; e->ln_dirty = true; return 0; }
-    if (!strcmp(key, "two_streams")) { e->opt_two_streams = value != 0; return 0; }
-    if (!strcmp(key, "cfg_share")) { e->opt_cfg_share = value != 0; return 0; }
-    if (!strcmp(key, "wide_tile")) { e->opt_wide = value != 0; return 0; }
-    if (!strcmp(key, "slab_gn")) { e->opt_slab_gn = (int)value; return 0; }
-    if (!strcmp(key, "ring")) { e->opt_ring = (int)value; return 0; }
-    if (!strcmp(key, "ring_tile")) { e->opt_ring_tile = (int)value; return 0; }
-    if (!strcmp(key, "ring_geglu")) { e->opt_ring_geglu = (int)value; return 0; }
-    if (!strcmp(key, "ring_small")) { e->opt_ring_small = (int)value; return 0; }
-    if (!strcmp(key, "short_k")) { e->opt_short_k = (int)value; return 0; }
-    if (!strcmp(key, "patch_split")) { e->opt_patch_split = value != 0; return 0; }
-    if (!strcmp(key, "gemm_tile")) {
-        if (value < -1 || value > 4) { pd_set_error("option gemm_tile: -1 (the plan's own) or a tile 0 .. 4"); return 1; }
-        e->opt_gemm_tile = (int)value; return 0;
-    }
-    if (!strcmp(key, "gemm_splitk")) {
-        if (value < -1 || value == 0 || value > 64) { pd_set_error("option gemm_splitk: -1 (the plan's own), 1 (never) or 2 .. 64 slices"); return 1; }
-        e->opt_gemm_splitk = (int)value; return 0;
-    }
-    if (!strcmp(key, "ring_pp")) { e->opt_ring_pp = (int)value; return 0; }
-    if (!strcmp(key, "patch4")) { e->opt_patch4 = value != 0; return 0; }
-    if (!strcmp(key, "patch_split_fill")) { e->opt_patch_split_fill = (int)value; return 0; }
-    if (!strcmp(key, "patch_split_min")) { if (value < 1) { pd_set_error("patch_split_min must be >= 1"); return 1; } e->opt_patch_split_min = (int)value; return 0; }
-    if (!strcmp(key, "patch_split_tiles")) { e->opt_patch_split_tiles = (int)value; return 0; }
-    if (!strcmp(key, "ups_fold")) { e->opt_ups_fold = value != 0; e->ln_dirty = true; return 0; }
-    if (!strcmp(key, "vae_flash")) { e->opt_vae_flash = value < 0 ? -1 : value != 0; return 0; }
-    if (!strcmp(key, "ups_fold_tiles")) { e->opt_ups_fold_tiles = (int)value; return 0; }
-    if (!strcmp(key, "dense_tiles")) { e->opt_dense_tiles = (int)value; return 0; }
-    if (!strcmp(key, "dense_k")) { e->opt_dense_k = (int)value; return 0; }
-    if (!strcmp(key, "big_tile")) { e->opt_bigtile = value != 0; return 0; }
-    if (!strcmp(key, "tile192")) { e->opt_tile192 = value != 0; return 0; }
-    if (!strcmp(key, "gemv")) { e->opt_gemv = value != 0; return 0; }
-    if (!strcmp(key, "sd3_fp8")) { e->opt_sd3_fp8 = (int)value; e->sd3_fp8_dirty = true; return 0; }
-    if (!strcmp(key, "profile")) {
-        (void)hipStreamSynchronize(e->stream);
-        e->profiling = value != 0;
-        e->prof.clear();
-        e->ev_used = 0;
-        if (e->profiling) {
-            // an event pair around a kernel reads the kernel PLUS the marker packets between them: calibrate that on back-to-back event
-            // pairs with NOTHING between them and take it off every bracket.  (Round 3 calibrated on a pair around an empty launch and
-            // thereby subtracted that launch's own latency too: the per-launch averages came out 8 % under the kernel trace.)
-            const int n = 64;
-            std::vector<hipEvent_t> ev(2 * n);
-            for (auto& x : ev) x = e->next_event();
-            for (int i = 0; i < n; ++i) {
-                (void)hipEventRecord(ev[2 * i], e->stream);
-                (void)hipEventRecord(ev[2 * i + 1], e->stream);
-            }
-            (void)hipStreamSynchronize(e->stream);
-            double tot = 0.0;
-            int cnt = 0;
-            for (int i = n / 2; i < n; ++i) {   // second half: warmed up
-                float t = 0.f;
-                if (ev[2 * i] && ev[2 * i + 1] && hipEventElapsedTime(&t, ev[2 * i], ev[2 * i + 1]) == hipSuccess) { tot += t; ++cnt; }
-            }
-            e->prof_overhead_ms = cnt ? (float)(tot / cnt) : 0.f;
-            e->ev_used = 0;
-        }
-        return 0;
-    }
-    pd_set_error("unknown option '%s'", key);
-    return 1;
-}
-
 int pd_set_freeu(pd_engine* e, float s1, float s2, float b1, float b2) {
     if (!e) { pd_set_error("null engine"); return 1; }
     const float v[4] = {s1, s2, b1, b2};
@@ -1173,89 +1089,6 @@ int pd_randn(pd_engine* e, int32_t stream, int32_t draw, int32_t B, int64_t per_
     if (hipStreamSynchronize(e->stream) != hipSuccess && !rc) { pd_set_error("pd_randn: hipStreamSynchronize failed"); rc = 1; }
     if (mem != PD_MEM_DEVICE) (void)hipFree(dst);
     return rc;
-}
-
-int64_t pd_get_stat(pd_engine* e, const char* key) {
-    if (!e || !key) return -1;
-    if (!strcmp(key, "graph_captures")) return (int64_t)e->graph_captures;
-    if (!strcmp(key, "graph_replays")) return (int64_t)e->graph_replays;
-    if (!strcmp(key, "workspace_bytes")) return (int64_t)e->arena.cap;
-    if (!strcmp(key, "side_workspace_bytes")) return (int64_t)e->arena2.cap;   // what the first stage / HED / text encoders run in (in_side_workspace)
-    if (!strcmp(key, "weight_bytes")) return (int64_t)e->weight_bytes;
-    if (!strcmp(key, "launches")) return (int64_t)e->launches;
-    if (!strcmp(key, "image_allocs")) return (int64_t)e->image_allocs;   // allocations of pd_image_load / pd_image_store / pd_canny so far
-    if (!strcmp(key, "canny_sweeps")) return (int64_t)e->canny_sweeps;   // hysteresis launches of the last pd_canny / pd_op_canny_hysteresis
-    if (!strcmp(key, "gn_from_slabs")) return (int64_t)e->gn_from_slabs;
-    if (!strcmp(key, "vae_tiles")) return (int64_t)e->vae_tiles_run;   // tiles run by tiled VAE calls (pd_vae_set_tiling)
-    if (!strcmp(key, "vae_flash_launches")) return (int64_t)e->vae_flash_launches;   // of which: vae_attention.hip
-    if (!strcmp(key, "ups_fold_launches")) return (int64_t)e->ups_fold_launches;   // of which: conv_upfold.hip's four-phase upsample conv
-    if (!strcmp(key, "ring_launches")) return (int64_t)e->ring_launches;   // of which: gemm_ring.hip's persistent ring kernel
-    if (!strcmp(key, "gn_kernel")) {   // which kernel the last pd_engine::groupnorm launch took
-        static_assert(GN_KIND_TWO_PASS == PD_GN_TWO_PASS && GN_KIND_LDS_SLAB == PD_GN_LDS_SLAB && GN_KIND_REGISTER == PD_GN_REGISTER, "pdengine.h");
-        return (int64_t)e->gn_kernel;
-    }
-    if (!strcmp(key, "attn_kernel")) {   // which kernel family the last pd_engine::attention launch took
-        static_assert(ATTN_KIND_GENERIC == PD_ATTN_GENERIC && ATTN_KIND_PIPELINED == PD_ATTN_PIPELINED, "pdengine.h");
-        return (int64_t)e->attn_kernel;
-    }
-    if (!strcmp(key, "gemm_family")) {   // which kernel family the last pd_engine::gemm launch took
-        static_assert(GEMM_GEMV == PD_GEMM_GEMV && GEMM_PATCH1 == PD_GEMM_PATCH1 && GEMM_PATCH2 == PD_GEMM_PATCH2 && GEMM_PATCH4 == PD_GEMM_PATCH4 &&
-                      GEMM_RING == PD_GEMM_RING && GEMM_IGEMM == PD_GEMM_IGEMM && GEMM_UPFOLD == PD_GEMM_UPFOLD, "pdengine.h");
-        return (int64_t)e->gemm_family;
-    }
-    if (!strcmp(key, "gemm_tile")) return (int64_t)e->gemm_tile;       // the tile of the instantiation that launch took
-    if (!strcmp(key, "gemm_ring_tile")) return (int64_t)e->gemm_ring_tile;   // the ring kernel's tile (2 / 3: ping-pong), -1: not a ring launch
-    if (!strcmp(key, "gemm_splitk")) return (int64_t)e->gemm_splitk;   // ... and its K / channel-chunk slices
-    if (!strcmp(key, "steps")) return (int64_t)e->ses.S;
-    if (!strcmp(key, "cfg_shared")) return (int64_t)((e->ses.share_u ? 1 : 0) | (e->ses.share_c ? 2 : 0) | (e->ses.cn_cond_only ? 4 : 0));
-    if (!strcmp(key, "lora_base_bytes")) return (int64_t)e->lora_bytes(true);   // base copies W0 of the adapted parameters
-    if (!strcmp(key, "lora_bytes")) return (int64_t)e->lora_bytes(false);        // ... plus the adapters' factors
-    if (!strcmp(key, "lora_targets")) return (int64_t)e->lora.size();
-    if (!strcmp(key, "event_overhead_ns")) return (int64_t)(e->prof_overhead_ms * 1e6f);
-    return -1;
-}
-
-// Per-launch HIP-event timing collected while option "profile" is on.  klass: 0 igemm conv3x3,
-// 1 igemm conv1x1 / linear, 2 attention, 3 conv3x3 LDS-patch kernel, 4 st_front / st_tail, 5 / 6 / 7 the Canny kernels, -1 all.
-int pd_profile_read(pd_engine* e, int32_t klass, double* total_ms, int64_t* n_launches, double* flops) {
-    if (!e) { pd_set_error("null engine"); return 1; }
-    HIP_OK(hipStreamSynchronize(e->stream));
-    if (e->stream2) HIP_OK(hipStreamSynchronize(e->stream2));
-    double ms = 0.0, fl = 0.0;
-    int64_t n = 0;
-    for (auto& r : e->prof) {
-        if (klass >= 0 && r.klass != klass) continue;
-        float t = 0.f;
-        if (r.a && r.b && hipEventElapsedTime(&t, r.a, r.b) == hipSuccess) {
-            t -= e->prof_overhead_ms;            // the empty-bracket time (see option "profile")
-            ms += t > 0.f ? t : 0.f;
-            fl += r.flops;
-            ++n;
-        }
-    }
-    if (total_ms) *total_ms = ms;
-    if (n_launches) *n_launches = n;
-    if (flops) *flops = fl;
-    return 0;
-}
-
-// Debug aid: one CSV row per profiled launch (klass, M, N, K, taps-code, ms, flops).
-int pd_profile_dump(pd_engine* e, const char* path) {
-    if (!e || !path) { pd_set_error("null argument"); return 1; }
-    HIP_OK(hipStreamSynchronize(e->stream));
-    if (e->stream2) HIP_OK(hipStreamSynchronize(e->stream2));
-    FILE* f = fopen(path, "w");
-    if (!f) { pd_set_error("cannot open %s", path); return 1; }
-    fprintf(f, "klass,M,N,K,taps,ms,flops\n");
-    for (auto& r : e->prof) {
-        float t = 0.f;
-        if (r.a && r.b && hipEventElapsedTime(&t, r.a, r.b) == hipSuccess) {
-            t -= e->prof_overhead_ms;
-            fprintf(f, "%d,%d,%d,%d,%d,%.6f,%.0f\n", r.klass, r.M, r.N, r.K, r.taps, t > 0.f ? t : 0.f, r.flops);
-        }
-    }
-    fclose(f);
-    return 0;
 }
 
 int pd_bench_conv3x3(pd_engine* e, int32_t Bf, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t iters, float* ms) {

@@ -162,7 +162,7 @@ void pd_engine::build_vae_encoder(VaeEncW& v, const std::string& P) {
 // the materialised GEMMs cannot run at all (N no multiple of 8).
 bool pd_engine::vae_flash_on(const VaeDesc& d, int C, long long N) const {
     if (f32 || !vae_attention_eligible(T, C)) return false;
-    if (opt_vae_flash >= 0) return opt_vae_flash != 0;
+    if (opt.vae_flash >= 0) return opt.vae_flash != 0;
     if (!d.flash_auto) return vae_tile_odd_flash && N % 8 != 0;   // (a tile of a tiled call that cannot materialise its scores)
     const long long score_bytes = N * N * 4 + N * ((N + 63) / 64 * 64) * (long long)dt_size(T);
     return score_bytes > (2ll << 30) || N % 8 != 0;

@@ -140,7 +140,7 @@ int pd_engine::vae_check_tiles(const VaeTilePlan& p, const VaeDesc& d, int C, co
     for (const pd_vae_tile& t : p.tiles) {
         const int lh = std::min<int>(t.h, t.th), lw = std::min<int>(t.w, t.tw);   // the tile at latent resolution, either direction
         if ((lh * lw) % 8 == 0) continue;
-        if (!f32 && vae_attention_eligible(T, C) && opt_vae_flash != 0) continue;
+        if (!f32 && vae_attention_eligible(T, C) && opt.vae_flash != 0) continue;
         pd_set_error("%s: tile at (%d, %d) is %d x %d latent pixels, no multiple of 8 tokens; its mid-block attention needs the flash kernel, "
                      "which this engine does not run (fp32 storage, option \"vae_flash\" 0 or %d channels); choose a size or tile_latent "
                      "that leaves an even remainder", who, t.y0 / (t.h > t.th ? dn : 1), t.x0 / (t.h > t.th ? dn : 1), lh, lw, C);

@@ -273,6 +273,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.pd_stream.restype = C.c_void_p
     lib.pd_wait_stream.argtypes = [C.c_void_p, C.c_void_p]
     lib.pd_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
+    if hasattr(lib, "pd_get_option"):   # (an older build handed in through PDENGINE_LIB for an A/B run lacks the two)
+        lib.pd_get_option.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]
+        lib.pd_option_info.argtypes = [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int64)]
     lib.pd_comm_new_id.argtypes = [C.c_void_p]
     lib.pd_comm_init.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
     lib.pd_comm_world.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
@@ -363,7 +366,7 @@ EXPORTS = [
     "pd_sample_begin", "pd_sample_step", "pd_sample_get", "pd_sample_set_latents", "pd_sample_set_guidance", "pd_sample_eps_at", "pd_sample_end",
     "pd_unipc_coefficients", "pd_unipc_sample", "pd_sample_begin_unipc",
     "pd_lms_coefficients", "pd_lms_sample", "pd_sample_begin_lms", "pd_sample_rows",
-    "pd_make_schedule", "pd_synchronize", "pd_stream", "pd_wait_stream", "pd_set_option", "pd_get_stat", "pd_bench_conv3x3", "pd_bench_linear", "pd_text_encode", "pd_text_encode_ex", "pd_text_weights_missing",
+    "pd_make_schedule", "pd_synchronize", "pd_stream", "pd_wait_stream", "pd_set_option", "pd_get_option", "pd_option_info", "pd_get_stat", "pd_bench_conv3x3", "pd_bench_linear", "pd_text_encode", "pd_text_encode_ex", "pd_text_weights_missing",
     "pd_profile_read", "pd_profile_dump", "pd_comm_new_id", "pd_comm_init", "pd_comm_world", "pd_comm_all_gather", "pd_comm_destroy",
     "pd_sd3_configure", "pd_sd3_weights_missing", "pd_sd3_forward", "pd_sd3_control", "pd_sd3_sample", "pd_sd3_sample_ex", "pd_sd3_down_proj",
     "pd_op_sd3_update",
@@ -380,6 +383,15 @@ EXPORTS = [
     "pd_clip_vision_weights_missing", "pd_clip_vision_forward", "pd_safety_configure", "pd_safety_weights_missing", "pd_safety_check", "pd_safety_blank",
     "pd_sd3_vae_configure", "pd_sd3_vae_weights_missing", "pd_sd3_vae_config_layout", "pd_sd3_vae_decode", "pd_sd3_vae_encode", "pd_op_vae_attention", "pd_bench_vae_attention",
 ]
+
+
+def option_table() -> List[Tuple[str, int]]:
+    """(key, default) of every engine option, in the order of the engine's table (pd_option_info; host only, no engine)."""
+    lib = load_library()
+    rows, k, d = [], C.c_char_p(), C.c_int64()
+    while not lib.pd_option_info(len(rows), C.byref(k), C.byref(d)):
+        rows.append((k.value.decode(), int(d.value)))
+    return rows
 
 
 def philox4x32_10(counter: Sequence[int], key: Sequence[int]) -> Tuple[int, int, int, int]:
@@ -1805,6 +1817,12 @@ class Engine:
 
     def set_option(self, key: str, value: int):
         self._check(self.lib.pd_set_option(self._h, key.encode(), int(value)))
+
+    def option(self, key: str) -> int:
+        """The value the option holds now, as set_option stored it (pd_get_option): save it, flip the knob, put it back."""
+        v = C.c_int64()
+        self._check(self.lib.pd_get_option(self._h, key.encode(), C.byref(v)))
+        return int(v.value)
 
     def profile_read(self, klass: int = -1) -> Tuple[float, int, float]:
         """(device ms, launches, algorithmic FLOPs) of the launches bracketed while option 'profile' was on."""

@@ -86,6 +86,7 @@ def run_groupnorm(eng, shape, variants):
             x, ga, be, ref, anchor = case
             bound = gn_bound(case, kind, eps, u_out)
             for label, opts, want in variants:
+                before = {k: eng.option(k) for k in opts}
                 try:
                     for k, v in opts.items():
                         eng.set_option(k, v)
@@ -93,8 +94,8 @@ def run_groupnorm(eng, shape, variants):
                     ran = eng.stat("gn_kernel")
                     got_silu = eng.op_groupnorm(x, ga, be, eps, True) if kind == 0 else None
                 finally:
-                    for k in opts:
-                        eng.set_option(k, 1)
+                    for k, v in before.items():
+                        eng.set_option(k, v)
                 assert ran == want, f"{shape} {label}: ran {KNAME.get(ran, ran)}, this case is about {KNAME[want]}"
                 r, at = R.check(got, ref, bound)
                 worst[label] = max(worst.get(label, 0.0), r)

@@ -15,6 +15,9 @@ static void fill_random(void* p, size_t bytes, unsigned seed) {
 }
 
 int main() {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, 0) != hipSuccess) return 2;
+    const int ncu = prop.multiProcessorCount;   // sizes the persistent grid
     struct Shape { int M, K, N, res, tile; };
     const Shape shapes[] = {{16384, 640, 640, 0, 1}, {16384, 640, 640, 1, 1}, {16384, 640, 640, 1, 0}, {4096, 1280, 1280, 1, 0}, {16384, 2560, 640, 1, 1}, {16384, 640, 1920, 0, 1}, {16384, 640, 5120, 0, 1}, {65536, 320, 320, 1, 1}};
     hipStream_t st[4];
@@ -45,7 +48,7 @@ int main() {
                         q.M = rows; q.rows_per_sample = rows;
                         q.A = (char*)a + (size_t)s * rows * sh.K * 2; q.C = (char*)c + (size_t)s * rows * sh.N * 2;
                         if (sh.res) q.R = (char*)r + (size_t)s * rows * sh.N * 2;
-                        if (launch_ring_gemm(q, DT_F16, sh.tile, par ? st[s] : st[0])) { printf("launch refused\n"); exit(1); }
+                        if (launch_ring_gemm(q, DT_F16, sh.tile, ncu, par ? st[s] : st[0])) { printf("launch refused\n"); exit(1); }
                     }
                 for (int i = 1; i < slices && par; ++i) { hipEventRecord(ev[i], st[i]); hipStreamWaitEvent(st[0], ev[i], 0); }
                 hipEventRecord(e1, st[0]);

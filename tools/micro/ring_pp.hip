@@ -14,6 +14,9 @@ static void fill_random(void* p, size_t bytes, unsigned seed) {
 }
 
 int main() {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, 0) != hipSuccess) return 2;
+    const int ncu = prop.multiProcessorCount;   // sizes the persistent grid
     struct Shape { int M, K, N, res, tile; };
     const Shape shapes[] = {{16384, 640, 640, 0, 0}, {16384, 640, 640, 0, 1}, {16384, 640, 640, 1, 1}, {4096, 1280, 1280, 1, 0}, {4096, 1280, 1280, 1, 1}, {16384, 2560, 640, 1, 1},
                             {16384, 640, 1920, 0, 1}, {4096, 5120, 1280, 1, 0}, {4096, 1280, 3840, 0, 0}, {65536, 320, 320, 1, 1}, {16384, 5120, 2560, 0, 1}, {8192, 8192, 8192, 0, 1},
@@ -41,9 +44,9 @@ int main() {
             for (int v = 0; v < 2; ++v) {
                 const GemmParams& q = v ? p1 : p0;
                 const int tile = sh.tile + 2 * v;
-                launch_ring_gemm(q, DT_F16, tile, 0);
+                launch_ring_gemm(q, DT_F16, tile, ncu, 0);
                 hipEventRecord(e0, 0);
-                for (int rep = 0; rep < 10; ++rep) launch_ring_gemm(q, DT_F16, tile, 0);
+                for (int rep = 0; rep < 10; ++rep) launch_ring_gemm(q, DT_F16, tile, ncu, 0);
                 hipEventRecord(e1, 0);
                 hipDeviceSynchronize();
                 float ms = 0;

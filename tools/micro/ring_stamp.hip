@@ -18,6 +18,9 @@ static void fill_random(void* p, size_t bytes, unsigned seed) {
 }
 
 int main() {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, 0) != hipSuccess) return 2;
+    const int ncu = prop.multiProcessorCount;   // sizes the persistent grid
     struct Shape { int M, K, N, res, tile; };
     const Shape shapes[] = {{16384, 640, 640, 0, 0}, {16384, 640, 640, 0, 1}, {16384, 640, 640, 1, 1}, {4096, 1280, 1280, 1, 0}, {16384, 2560, 640, 1, 1}, {16384, 640, 1920, 0, 1}, {16384, 5120, 2560, 0, 1}, {8192, 8192, 8192, 0, 1}};
     unsigned long long* stamps;
@@ -38,9 +41,9 @@ int main() {
         p.a_dt = p.c_dt = p.r_dt = DT_F16; p.taps = 1; p.Cin = sh.K; p.rows_per_sample = sh.M; p.out_scale = 1.f; p.vt_begin = sh.N; p.Nout = sh.N; p.splitk = 1;
         hipEvent_t e0, e1;
         hipEventCreate(&e0); hipEventCreate(&e1);
-        for (int rep = 0; rep < 3; ++rep) launch_ring_gemm(p, DT_F16, sh.tile, 0);
+        for (int rep = 0; rep < 3; ++rep) launch_ring_gemm(p, DT_F16, sh.tile, ncu, 0);
         hipEventRecord(e0, 0);
-        for (int rep = 0; rep < 10; ++rep) launch_ring_gemm(p, DT_F16, sh.tile, 0);
+        for (int rep = 0; rep < 10; ++rep) launch_ring_gemm(p, DT_F16, sh.tile, ncu, 0);
         hipEventRecord(e1, 0);
         hipDeviceSynchronize();
         float ms = 0;
