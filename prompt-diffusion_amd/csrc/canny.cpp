@@ -7,21 +7,7 @@
 
 static_assert(CANNY_NONE == PD_CANNY_NONE && CANNY_WEAK == PD_CANNY_WEAK && CANNY_STRONG == PD_CANNY_STRONG, "pdengine.h");
 
-namespace {
-
-// one profiled launch (option "profile"): klass 5 nms, 6 hysteresis sweep, 7 emit
-struct Bracket {
-    pd_engine* e;
-    pd_engine::ProfRec rec{};
-    Bracket(pd_engine* e_, int klass) : e(e_) {
-        if (e->profiling) e->prof_begin(rec, klass, 0.0);
-    }
-    ~Bracket() {
-        if (e->profiling) e->prof_end(rec);
-    }
-};
-
-}  // namespace
+// profiling classes of the launches (Bracket): 5 nms, 6 hysteresis sweep, 7 emit
 
 // Sweeps are enqueued kCannyBatch at a time, sweep i of a batch raising flag i, and the flags are read from pinned memory after the
 // batch.  A sweep that raised no flag found the fixed point (the sweeps behind it in the batch then change nothing either).  Every

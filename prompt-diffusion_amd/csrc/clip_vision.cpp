@@ -170,62 +170,58 @@ extern "C" int pd_clip_vision_configure(pd_engine* e, const pd_clip_vision_confi
         if (old->broken) { pd_set_error("pd_clip_vision_configure: the weight allocation of '%s' failed earlier; create a new engine", c->prefix); return 1; }
         return 0;
     }
-    if (e->ses.active) { pd_set_error("pd_clip_vision_configure: end the sampling session first"); return 1; }
     int slot = -1;
     for (int i = 0; i < 2 && slot < 0; ++i)
         if (!e->clip_vision[i].built) slot = i;
-    if (slot < 0) { pd_set_error("pd_clip_vision_configure: both image towers of this engine are taken"); return 1; }
-    if (c->layers < 1 || c->heads < 1 || c->hidden < 8 || c->hidden % 8 || c->hidden % c->heads || !dh_known(c->hidden / c->heads) || c->hidden > 2048 ||
-        c->ff < 8 || c->ff % 8 || c->patch < 1 || c->image_size < c->patch || c->image_size % c->patch || c->proj_dim < 1 || !(c->eps > 0.f) ||
-        (c->act != PD_CLIP_ACT_QUICK_GELU && c->act != PD_CLIP_ACT_GELU)) {
-        pd_set_error("pd_clip_vision_configure: need hidden = heads * dh <= 2048 with dh in {8, 16, 32, 40, 64, 80, 160}, hidden and ff multiples of 8, "
-                     "image_size a multiple of patch, proj_dim >= 1, eps > 0, a known act");
-        return 1;
-    }
-    for (int k = 0; k < 3; ++k)
-        if (!(c->std[k] > 0.f)) { pd_set_error("pd_clip_vision_configure: std[%d] must be > 0", k); return 1; }
-    HIP_OK(hipSetDevice(e->device));
-    e->alloc_failed = false;
-    ClipVisionW& v = e->clip_vision[slot];
-    v.c = *c;
-    v.prefix = c->prefix;
-    v.group = slot == 0 ? GROUP_CLIP_VISION_0 : GROUP_CLIP_VISION_1;
-    const int C = c->hidden, p = c->patch, G = c->image_size / p;
-    v.patches = G * G;
-    ClipW& t = v.t;
-    t.hidden = C; t.ff = c->ff; t.heads = c->heads; t.positions = v.patches + 1; t.proj_dim = c->proj_dim;
-    t.act = c->act == PD_CLIP_ACT_GELU ? ACT_ERF_GELU : ACT_QUICK_GELU;
-    t.causal = false;
-    t.eps = c->eps;
-    t.layers.resize(c->layers);
-    e->reg_group = (WeightGroup)v.group;
-    const std::string V = v.prefix + "vision_model.";
-    e->reg_vec(V + "embeddings.class_embedding", C, &v.cls, 'b');
-    // Conv2d(3, C, p, stride p) without a bias, as a linear layer over the patch matrix: the flattened [C][3 p p] rows as they are
-    e->make_mat(v.patch, C, 3 * p * p, 1, 3 * p * p, false);
-    e->reg_mat(V + "embeddings.patch_embedding.weight", {C, 3, p, p}, &v.patch, 0, false);
-    e->reg_vec(V + "embeddings.position_embedding.weight", t.positions * C, &v.pos, 'b');
-    e->params.back().shape = {t.positions, C};
-    e->reg_vec(V + "pre_layrnorm.weight", C, &v.pre_g, 'g');
-    e->reg_vec(V + "pre_layrnorm.bias", C, &v.pre_b, 'e');
-    e->build_clip_layers(V, t);
-    e->reg_vec(V + "post_layernorm.weight", C, &t.fln_g, 'g');
-    e->reg_vec(V + "post_layernorm.bias", C, &t.fln_b, 'e');
-    // visual_projection sits next to the outermost vision_model: "safety_checker.vision_model." -> "safety_checker.visual_projection.weight"
-    std::string outer = v.prefix;
-    const std::string tail = "vision_model.";
-    if (outer.size() >= tail.size() && outer.compare(outer.size() - tail.size(), tail.size(), tail) == 0) outer.resize(outer.size() - tail.size());
-    e->make_mat(t.proj, t.proj_dim, C, 1, C, false);
-    e->reg_mat(outer + "visual_projection.weight", {t.proj_dim, C}, &t.proj, 0, false);
-    t.built = true;
-    v.built = true;
-    e->reg_group = GROUP_SAMPLER;
-    if (e->alloc_failed) {   // the names are registered, so the slot stays taken; every later use of it is refused
-        v.broken = true;
-        pd_set_error("pd_clip_vision_configure: weight allocation failed");
-        return 1;
-    }
-    return 0;
+    auto check = [&]() -> int {
+        if (slot < 0) { pd_set_error("pd_clip_vision_configure: both image towers of this engine are taken"); return 1; }
+        if (c->layers < 1 || c->heads < 1 || c->hidden < 8 || c->hidden % 8 || c->hidden % c->heads || !dh_known(c->hidden / c->heads) || c->hidden > 2048 ||
+            c->ff < 8 || c->ff % 8 || c->patch < 1 || c->image_size < c->patch || c->image_size % c->patch || c->proj_dim < 1 || !(c->eps > 0.f) ||
+            (c->act != PD_CLIP_ACT_QUICK_GELU && c->act != PD_CLIP_ACT_GELU)) {
+            pd_set_error("pd_clip_vision_configure: need hidden = heads * dh <= 2048 with dh in {8, 16, 32, 40, 64, 80, 160}, hidden and ff multiples of 8, "
+                         "image_size a multiple of patch, proj_dim >= 1, eps > 0, a known act");
+            return 1;
+        }
+        for (int k = 0; k < 3; ++k)
+            if (!(c->std[k] > 0.f)) { pd_set_error("pd_clip_vision_configure: std[%d] must be > 0", k); return 1; }
+        return 0;
+    };
+    const WeightGroup group = slot == 0 ? GROUP_CLIP_VISION_0 : GROUP_CLIP_VISION_1;
+    return e->configure("pd_clip_vision_configure", group, check, [&] {
+        ClipVisionW& v = e->clip_vision[slot];
+        v.c = *c;
+        v.prefix = c->prefix;
+        v.group = group;
+        const int C = c->hidden, p = c->patch, G = c->image_size / p;
+        v.patches = G * G;
+        ClipW& t = v.t;
+        t.hidden = C; t.ff = c->ff; t.heads = c->heads; t.positions = v.patches + 1; t.proj_dim = c->proj_dim;
+        t.act = c->act == PD_CLIP_ACT_GELU ? ACT_ERF_GELU : ACT_QUICK_GELU;
+        t.causal = false;
+        t.eps = c->eps;
+        t.layers.resize(c->layers);
+        const std::string V = v.prefix + "vision_model.";
+        e->reg_vec(V + "embeddings.class_embedding", C, &v.cls, 'b');
+        // Conv2d(3, C, p, stride p) without a bias, as a linear layer over the patch matrix: the flattened [C][3 p p] rows as they are
+        e->make_mat(v.patch, C, 3 * p * p, 1, 3 * p * p, false);
+        e->reg_mat(V + "embeddings.patch_embedding.weight", {C, 3, p, p}, &v.patch, 0, false);
+        e->reg_vec(V + "embeddings.position_embedding.weight", t.positions * C, &v.pos, 'b');
+        e->params.back().shape = {t.positions, C};
+        e->reg_vec(V + "pre_layrnorm.weight", C, &v.pre_g, 'g');
+        e->reg_vec(V + "pre_layrnorm.bias", C, &v.pre_b, 'e');
+        e->build_clip_layers(V, t);
+        e->reg_vec(V + "post_layernorm.weight", C, &t.fln_g, 'g');
+        e->reg_vec(V + "post_layernorm.bias", C, &t.fln_b, 'e');
+        // visual_projection sits next to the outermost vision_model: "safety_checker.vision_model." -> "safety_checker.visual_projection.weight"
+        std::string outer = v.prefix;
+        const std::string tail = "vision_model.";
+        if (outer.size() >= tail.size() && outer.compare(outer.size() - tail.size(), tail.size(), tail) == 0) outer.resize(outer.size() - tail.size());
+        e->make_mat(t.proj, t.proj_dim, C, 1, C, false);
+        e->reg_mat(outer + "visual_projection.weight", {t.proj_dim, C}, &t.proj, 0, false);
+        t.built = true;
+        v.built = true;
+        v.broken = e->alloc_failed;   // the names are registered, so the slot stays taken; every later use of it is refused
+    });
 }
 
 extern "C" int pd_clip_vision_weights_missing(pd_engine* e, const char* prefix) {
@@ -242,49 +238,27 @@ int pd_engine::clip_vision_forward(ClipVisionW& v, const void* patches, int B, i
     Act po = new_act(B, P, 1, C, DT_F32);
     PD_TRY(gemm(v.patch, pm, po));
     Act e0 = new_act(B, L, 1, C, DT_F32);
-    if (!arena.dry) {
-        PD_TRY(check_arena());
-        ++launches;
-        if (launch_clipv_embed(reinterpret_cast<const float*>(po.p), v.cls, v.pos, reinterpret_cast<float*>(e0.p), B, P, C, stream)) {
-            pd_set_error("CLIP vision embedding launch failed");
-            return 1;
-        }
-    }
+    PD_LAUNCH(this, launch_clipv_embed(reinterpret_cast<const float*>(po.p), v.cls, v.pos, reinterpret_cast<float*>(e0.p), B, P, C, stream),
+              "CLIP vision embedding launch failed");
     Act x = new_act(B, L, 1, C, v.c.stream_f32 ? (int)DT_F32 : S);   // the residual stream
     PD_TRY(layernorm(e0, x, v.pre_g, v.pre_b, t.eps));
     int done = 0;
     if (hid) {
         PD_TRY(clip_blocks(t, 0, k, x));
         done = k;
-        if (!arena.dry) {
-            PD_TRY(check_arena());
-            ++launches;
-            if (launch_clipv_rows(x.p, x.dt, hid, B, L, C, L, stream)) { pd_set_error("CLIP vision hidden-state read-out launch failed"); return 1; }
-        }
+        PD_LAUNCH(this, launch_clipv_rows(x.p, x.dt, hid, B, L, C, L, stream), "CLIP vision hidden-state read-out launch failed");
     }
     if (pooled || embeds) {
         PD_TRY(clip_blocks(t, done, n, x));
         // post_layernorm is per row: gather the class rows first
         Act rows = new_act(B, 1, 1, C, DT_F32), lnr = new_act(B, 1, 1, C, DT_F32);
-        if (!arena.dry) {
-            PD_TRY(check_arena());
-            ++launches;
-            if (launch_clipv_rows(x.p, x.dt, reinterpret_cast<float*>(rows.p), B, L, C, 1, stream)) { pd_set_error("CLIP vision class-row gather launch failed"); return 1; }
-        }
+        PD_LAUNCH(this, launch_clipv_rows(x.p, x.dt, reinterpret_cast<float*>(rows.p), B, L, C, 1, stream), "CLIP vision class-row gather launch failed");
         PD_TRY(layernorm(rows, lnr, t.fln_g, t.fln_b, t.eps));
-        if (!arena.dry) {
-            if (pooled) HIP_OK(hipMemcpyAsync(pooled, lnr.p, lnr.bytes(), hipMemcpyDeviceToDevice, stream));
-            if (embeds) {
-                for (int b0 = 0; b0 < B; b0 += 4) {   // launch_gemv streams the weights once per <= 4 rows
-                    ++launches;
-                    if (launch_gemv(reinterpret_cast<const float*>(lnr.p) + (size_t)b0 * C, C, t.proj.w, T, t.proj.Kpad, nullptr, embeds + (size_t)b0 * t.proj_dim,
-                                    t.proj_dim, std::min(4, B - b0), t.proj_dim, C, 0, stream)) {
-                        pd_set_error("CLIP visual_projection launch failed");
-                        return 1;
-                    }
-                }
-            }
-        }
+        if (pooled && !arena.dry) HIP_OK(hipMemcpyAsync(pooled, lnr.p, lnr.bytes(), hipMemcpyDeviceToDevice, stream));
+        for (int b0 = 0; embeds && b0 < B; b0 += 4)   // launch_gemv streams the weights once per <= 4 rows
+            PD_LAUNCH(this, launch_gemv(reinterpret_cast<const float*>(lnr.p) + (size_t)b0 * C, C, t.proj.w, T, t.proj.Kpad, nullptr,
+                                        embeds + (size_t)b0 * t.proj_dim, t.proj_dim, std::min(4, B - b0), t.proj_dim, C, 0, stream),
+                      "CLIP visual_projection launch failed");
     }
     arena.release(mk0);
     return 0;
@@ -312,44 +286,23 @@ extern "C" int pd_clip_vision_forward(pd_engine* e, const pd_clip_vision_args* a
     PD_TRY(e->require_loaded((WeightGroup)v.group, "CLIP image tower"));
     if (u8) PD_TRY(prep_check(a->H, a->W, S));   // refuse before anything is enqueued
     HIP_OK(hipSetDevice(e->device));
-    const size_t n_in = u8 ? (size_t)B * a->H * a->W * 3 : (size_t)B * 3 * S * S * sizeof(float);
-    const size_t n_pm = (size_t)B * v.patches * v.patch.cin_pad * dt_size(e->T);
-    const size_t n_h = a->hidden ? (size_t)B * L * C : 0, n_p = a->pooler_output ? (size_t)B * C : 0, n_e = a->image_embeds ? (size_t)B * D : 0;
-    auto body = [&](bool dry) -> int {
-        const void* in = a->input;
-        if (a->mem != PD_MEM_DEVICE) {
-            void* din = e->arena.alloc(n_in);
-            if (!dry) {
-                PD_TRY(e->check_arena());
-                HIP_OK(hipMemcpyAsync(din, a->input, n_in, hipMemcpyHostToDevice, e->stream));
-            }
-            in = din;
-        }
-        void* pm = e->arena.alloc(n_pm);
-        float* dh = n_h ? reinterpret_cast<float*>(e->arena.alloc(n_h * sizeof(float))) : nullptr;
-        float* dp = n_p ? reinterpret_cast<float*>(e->arena.alloc(n_p * sizeof(float))) : nullptr;
-        float* de = n_e ? reinterpret_cast<float*>(e->arena.alloc(n_e * sizeof(float))) : nullptr;
-        if (!dry) {
+    const size_t n_in = u8 ? (size_t)B * a->H * a->W * 3 : (size_t)B * 3 * S * S * sizeof(float);   // bytes
+    return e->side_call("CLIP vision", [&](SideCall& f) {
+        const uint8_t* in;
+        PD_TRY(f.src(&in, reinterpret_cast<const uint8_t*>(a->input), n_in, a->mem));
+        void* pm = f.scratch<char>((size_t)B * v.patches * v.patch.cin_pad * dt_size(e->T));
+        float* dh = a->hidden ? f.dst(a->hidden, (size_t)B * L * C, a->mem) : nullptr;
+        float* dp = a->pooler_output ? f.dst(a->pooler_output, (size_t)B * C, a->mem) : nullptr;
+        float* de = a->image_embeds ? f.dst(a->image_embeds, (size_t)B * D, a->mem) : nullptr;
+        if (!u8) {
+            PD_LAUNCH(e, launch_clipv_patchify(reinterpret_cast<const float*>(in), pm, e->T, B, S, v.c.patch, e->stream),
+                      "pd_clip_vision_forward: patchify launch failed");
+        } else if (!e->arena.dry) {   // (takes nothing from the workspace: its resampling tables are made once, in the real pass)
             PD_TRY(e->check_arena());
-            if (u8) {
-                PD_TRY(e->clip_preprocess_dev(reinterpret_cast<const uint8_t*>(in), B, a->H, a->W, S, v.c.patch, v.c.mean, v.c.std, PD_CLIP_OUT_PATCHES, pm));
-            } else {
-                ++e->launches;
-                if (launch_clipv_patchify(reinterpret_cast<const float*>(in), pm, e->T, B, S, v.c.patch, e->stream)) {
-                    pd_set_error("pd_clip_vision_forward: patchify launch failed");
-                    return 1;
-                }
-            }
+            PD_TRY(e->clip_preprocess_dev(in, B, a->H, a->W, S, v.c.patch, v.c.mean, v.c.std, PD_CLIP_OUT_PATCHES, pm));
         }
-        PD_TRY(e->clip_vision_forward(v, pm, B, k, dh, dp, de));
-        if (dry) return 0;
-        if (dh) PD_TRY(e->download(a->hidden, dh, n_h, a->mem));
-        if (dp) PD_TRY(e->download(a->pooler_output, dp, n_p, a->mem));
-        if (de) PD_TRY(e->download(a->image_embeds, de, n_e, a->mem));
-        HIP_OK(hipStreamSynchronize(e->stream));
-        return 0;
-    };
-    return e->in_side_workspace("CLIP vision", n_in + n_pm + (n_h + n_p + n_e) * sizeof(float) + 4096, [&] { return body(true); }, [&] { return body(false); });
+        return e->clip_vision_forward(v, pm, B, k, dh, dp, de);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------------------ the checker
@@ -361,22 +314,18 @@ extern "C" int pd_safety_configure(pd_engine* e) {
     }
     ClipVisionW* v = e->find_clip_vision("safety_checker.vision_model.");
     if (!v || v->broken) { pd_set_error("pd_safety_configure: configure the tower under 'safety_checker.vision_model.' first (pd_clip_vision_configure)"); return 1; }
-    if (e->ses.active) { pd_set_error("pd_safety_configure: end the sampling session first"); return 1; }
-    HIP_OK(hipSetDevice(e->device));
-    e->alloc_failed = false;
-    SafetyW& s = e->safety;
-    s.D = v->t.proj_dim;
-    e->reg_group = GROUP_SAFETY;
-    e->reg_vec("safety_checker.concept_embeds", PD_SAFETY_CONCEPTS * s.D, &s.cpt, 'w');
-    e->params.back().shape = {PD_SAFETY_CONCEPTS, s.D};
-    e->reg_vec("safety_checker.special_care_embeds", PD_SAFETY_SPECIAL * s.D, &s.spc, 'w');
-    e->params.back().shape = {PD_SAFETY_SPECIAL, s.D};
-    e->reg_vec("safety_checker.concept_embeds_weights", PD_SAFETY_CONCEPTS, &s.cpt_thr, 'b');
-    e->reg_vec("safety_checker.special_care_embeds_weights", PD_SAFETY_SPECIAL, &s.spc_thr, 'b');
-    s.built = true;
-    e->reg_group = GROUP_SAMPLER;
-    if (e->alloc_failed) { s.broken = true; pd_set_error("pd_safety_configure: weight allocation failed"); return 1; }
-    return 0;
+    return e->configure("pd_safety_configure", GROUP_SAFETY, [&] {
+        SafetyW& s = e->safety;
+        s.D = v->t.proj_dim;
+        e->reg_vec("safety_checker.concept_embeds", PD_SAFETY_CONCEPTS * s.D, &s.cpt, 'w');
+        e->params.back().shape = {PD_SAFETY_CONCEPTS, s.D};
+        e->reg_vec("safety_checker.special_care_embeds", PD_SAFETY_SPECIAL * s.D, &s.spc, 'w');
+        e->params.back().shape = {PD_SAFETY_SPECIAL, s.D};
+        e->reg_vec("safety_checker.concept_embeds_weights", PD_SAFETY_CONCEPTS, &s.cpt_thr, 'b');
+        e->reg_vec("safety_checker.special_care_embeds_weights", PD_SAFETY_SPECIAL, &s.spc_thr, 'b');
+        s.built = true;
+        s.broken = e->alloc_failed;
+    });
 }
 
 extern "C" int pd_safety_weights_missing(pd_engine* e) { return e && e->safety.built ? e->missing(GROUP_SAFETY) : 0; }
@@ -389,27 +338,14 @@ extern "C" int pd_safety_check(pd_engine* e, const float* embeds, int32_t B, int
     HIP_OK(hipSetDevice(e->device));
     const SafetyW& s = e->safety;
     const int R = PD_SAFETY_SPECIAL + PD_SAFETY_CONCEPTS;
-    const size_t n_e = (size_t)B * s.D, n_s = scores ? (size_t)B * R : 0;
-    auto body = [&](bool dry) -> int {
-        float* de = reinterpret_cast<float*>(e->arena.alloc(n_e * sizeof(float)));
-        int* df = reinterpret_cast<int*>(e->arena.alloc((size_t)B * sizeof(int)));
-        float* ds = n_s ? reinterpret_cast<float*>(e->arena.alloc(n_s * sizeof(float))) : nullptr;
-        if (dry) return 0;
-        PD_TRY(e->check_arena());
-        const float* src = embeds;
-        if (mem != PD_MEM_DEVICE) {
-            HIP_OK(hipMemcpyAsync(de, embeds, n_e * sizeof(float), hipMemcpyHostToDevice, e->stream));
-            src = de;
-        }
-        ++e->launches;
-        if (launch_safety_check(src, s.spc, s.cpt, s.spc_thr, s.cpt_thr, B, s.D, df, ds, e->stream)) { pd_set_error("pd_safety_check: launch failed"); return 1; }
-        const hipMemcpyKind back = mem == PD_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-        HIP_OK(hipMemcpyAsync(flags, df, (size_t)B * sizeof(int), back, e->stream));
-        if (ds) HIP_OK(hipMemcpyAsync(scores, ds, n_s * sizeof(float), back, e->stream));
-        HIP_OK(hipStreamSynchronize(e->stream));
+    return e->side_call("safety checker", [&](SideCall& f) {
+        const float* src;
+        PD_TRY(f.src(&src, embeds, (size_t)B * s.D, mem));
+        int* df = f.dst(flags, (size_t)B, mem);
+        float* ds = scores ? f.dst(scores, (size_t)B * R, mem) : nullptr;
+        PD_LAUNCH(e, launch_safety_check(src, s.spc, s.cpt, s.spc_thr, s.cpt_thr, B, s.D, df, ds, e->stream), "pd_safety_check: launch failed");
         return 0;
-    };
-    return e->in_side_workspace("safety checker", (n_e + n_s) * sizeof(float) + (size_t)B * sizeof(int) + 4096, [&] { return body(true); }, [&] { return body(false); });
+    });
 }
 
 extern "C" int pd_safety_blank(pd_engine* e, float* images, int32_t B, int64_t per_image, const int32_t* flags, int32_t mem_flags, float value) {

@@ -343,31 +343,42 @@ int pd_engine::check_arena() {
     return 1;
 }
 
-int pd_engine::in_side_workspace(const char* what, size_t io_bytes, const std::function<int()>& sizing, const std::function<int()>& run) {
-    std::swap(arena, arena2);
-    Arena saved = arena;
-    arena.base = nullptr; arena.cap = 0; arena.top = 0; arena.peak = 0; arena.dry = true;
-    int r = sizing();
-    const size_t need = arena.peak + io_bytes + (64u << 20);
-    arena = saved;
-    arena.dry = false;
-    if (!r && need > arena.cap) {
-        hipStreamSynchronize(stream);
-        if (stream2) hipStreamSynchronize(stream2);
-        clear_graphs();   // captured step loops point into this workspace
-        if (arena.base) hipFree(arena.base);
-        arena.base = nullptr; arena.cap = 0;
-        void* p = nullptr;
-        if (hipMalloc(&p, need) != hipSuccess) { pd_set_error("%s workspace allocation of %.2f GiB failed", what, (double)need / (1 << 30)); r = 1; }
-        else { arena.base = reinterpret_cast<char*>(p); arena.cap = need; }
+// the side workspace (`arena` while a side_call runs) holds at least `need` bytes afterwards
+int pd_engine::side_grow(const char* what, size_t need) {
+    if (need <= arena.cap) return 0;
+    hipStreamSynchronize(stream);
+    if (stream2) hipStreamSynchronize(stream2);
+    clear_graphs();   // captured step loops point into this workspace
+    if (arena.base) hipFree(arena.base);
+    arena.base = nullptr; arena.cap = 0;
+    void* p = nullptr;
+    if (hipMalloc(&p, need) != hipSuccess) { pd_set_error("%s workspace allocation of %.2f GiB failed", what, (double)need / (1 << 30)); return 1; }
+    arena.base = reinterpret_cast<char*>(p); arena.cap = need;
+    return 0;
+}
+
+int SideCall::upload(void* dev, const void* host, size_t bytes) {
+    if (e.arena.dry) return 0;
+    PD_TRY(e.check_arena());
+    HIP_OK(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, e.stream));
+    return 0;
+}
+
+void* SideCall::stage(void* p, size_t width, size_t rows, size_t pitch, int mem) {
+    void* d = e.arena.alloc(width * rows);
+    if (!e.arena.dry) backs.push_back({p, d, width, rows, pitch, mem});
+    return d;
+}
+
+int SideCall::finish() {
+    PD_TRY(e.check_arena());
+    for (const Back& b : backs) {
+        const hipMemcpyKind kind = b.mem == PD_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+        if (b.rows == 1) HIP_OK(hipMemcpyAsync(b.dst, b.src, b.width, kind, e.stream));
+        else HIP_OK(hipMemcpy2DAsync(b.dst, b.pitch ? b.pitch : b.width, b.src, b.width, b.width, b.rows, kind, e.stream));
     }
-    if (!r) {
-        arena.top = 0; arena.peak = 0;
-        r = run();
-        arena.top = 0;
-    }
-    std::swap(arena, arena2);
-    return r;
+    HIP_OK(hipStreamSynchronize(e.stream));
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------ weights
@@ -1027,13 +1038,7 @@ int pd_engine::gn_stats(const Act& x, int& nchunk) {
     if (nchunk < 1) nchunk = 1;
     if (nchunk > 64) nchunk = 64;
     while ((size_t)x.B * nchunk * 32 * 2 * sizeof(double) > gn_partial_cap && nchunk > 1) nchunk /= 2;
-    if (arena.dry) return 0;
-    PD_TRY(check_arena());
-    ++launches;
-    if (launch_gn_stats(x.p, x.dt, gn_partial, x.B, HW, x.C, 32, nchunk, stream)) {
-        pd_set_error("groupnorm stats launch failed (C=%d)", x.C);
-        return 1;
-    }
+    PD_LAUNCH(this, launch_gn_stats(x.p, x.dt, gn_partial, x.B, HW, x.C, 32, nchunk, stream), "groupnorm stats launch failed (C=%d)", x.C);
     return 0;
 }
 
@@ -1052,13 +1057,8 @@ int pd_engine::groupnorm(const Act& x, Act& y, const float* g, const float* b, f
         return 0;
     }
     if (opt.gn_single && gn_fused_bundle(x.dt, x.H * x.W, x.C, 32, opt.gn_reg)) {   // slab fits in LDS: one kernel, one read
-        if (arena.dry) return 0;
-        PD_TRY(check_arena());
-        ++launches;
-        if (launch_gn_fused(x.p, x.dt, y.p, y.dt, g, b, x.B, x.H * x.W, x.C, 32, eps, silu ? 1 : 0, opt.gn_reg, stream, &gn_kernel)) {
-            pd_set_error("groupnorm (single kernel) launch failed (C=%d)", x.C);
-            return 1;
-        }
+        PD_LAUNCH(this, launch_gn_fused(x.p, x.dt, y.p, y.dt, g, b, x.B, x.H * x.W, x.C, 32, eps, silu ? 1 : 0, opt.gn_reg, stream, &gn_kernel),
+                  "groupnorm (single kernel) launch failed (C=%d)", x.C);
         return 0;
     }
     int nchunk = 1;
@@ -1092,10 +1092,7 @@ int pd_engine::conv_gn(const ConvW& c, const Act& x, Act& out, const float* g, c
     PD_TRY(gn_stats(x, nchunk));
     const size_t mk = arena.mark();
     float* coef = reinterpret_cast<float*>(arena.alloc((size_t)x.B * x.C * 2 * sizeof(float)));
-    if (!arena.dry) {
-        ++launches;
-        if (launch_gn_coef(gn_partial, g, b, coef, x.B, x.H * x.W, x.C, 32, nchunk, eps, stream)) { pd_set_error("groupnorm coefficient launch failed"); return 1; }
-    }
+    PD_LAUNCH(this, launch_gn_coef(gn_partial, g, b, coef, x.B, x.H * x.W, x.C, 32, nchunk, eps, stream), "groupnorm coefficient launch failed");
     call.gn_coef = coef; call.gn_silu = silu; call.defer = nullptr;
     PD_TRY(gemm(c.m, x, out, call));
     arena.release(mk);
@@ -1103,13 +1100,7 @@ int pd_engine::conv_gn(const ConvW& c, const Act& x, Act& out, const float* g, c
 }
 
 int pd_engine::layernorm(const Act& x, Act& y, const float* g, const float* b, float eps) {
-    if (arena.dry) return 0;
-    PD_TRY(check_arena());
-    ++launches;
-    if (launch_layernorm(x.p, x.dt, y.p, y.dt, g, b, (int)x.rows(), x.C, eps, stream)) {
-        pd_set_error("layernorm launch failed (C=%d)", x.C);
-        return 1;
-    }
+    PD_LAUNCH(this, launch_layernorm(x.p, x.dt, y.p, y.dt, g, b, (int)x.rows(), x.C, eps, stream), "layernorm launch failed (C=%d)", x.C);
     return 0;
 }
 
@@ -1420,19 +1411,12 @@ int pd_engine::run_unet(const Act& x_in_full, int emb_row, int emb_stride, bool 
         // FreeU (pd_set_freeu): diffusers' up_blocks[0] / [1] are the first two stages of num_res_blocks + 1 decoder blocks
         const int stage = (int)i / (cfg.num_res_blocks + 1);
         const bool fu = stage < 2 && freeu_on();
-        if (!arena.dry) {
-            PD_TRY(check_arena());
-            ++launches;
-            const int rc = fu ? launch_freeu_concat(h.p, a_add ? a_add->p : nullptr, skip.p, b_add ? b_add->p : nullptr, cat.p, S,
-                                                    h.B, h.H, h.W, h.C, skip.C, freeu[stage], freeu[2 + stage], stream, skip.rows(),
-                                                    b_add ? b_add->rows() : 0)
-                              : launch_concat_add(h.p, a_add ? a_add->p : nullptr, skip.p, b_add ? b_add->p : nullptr, cat.p, S,
-                                                  h.rows(), h.C, skip.C, stream, skip.rows(), b_add ? b_add->rows() : 0);
-            if (rc) {
-                pd_set_error(fu ? "FreeU concat launch failed" : "concat launch failed");
-                return 1;
-            }
-        }
+        PD_LAUNCH(this,
+                  fu ? launch_freeu_concat(h.p, a_add ? a_add->p : nullptr, skip.p, b_add ? b_add->p : nullptr, cat.p, S, h.B, h.H, h.W, h.C, skip.C,
+                                           freeu[stage], freeu[2 + stage], stream, skip.rows(), b_add ? b_add->rows() : 0)
+                     : launch_concat_add(h.p, a_add ? a_add->p : nullptr, skip.p, b_add ? b_add->p : nullptr, cat.p, S, h.rows(), h.C, skip.C, stream,
+                                         skip.rows(), b_add ? b_add->rows() : 0),
+                  fu ? "FreeU concat launch failed" : "concat launch failed");
         Act o;
         PD_TRY(resblock(b.res, cat, o, emb_ptr(ses.emb_u, b.res, emb_row), emb_stride ? b.res.cout : 0));
         if (b.attn) {

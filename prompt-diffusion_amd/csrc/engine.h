@@ -1,7 +1,6 @@
 // pdengine: engine object behind the C ABI of include/pdengine.h (host-side orchestration).
 #pragma once
 #include <cstdint>
-#include <functional>
 #include <map>
 #include <string>
 #include <unordered_map>
@@ -36,6 +35,23 @@ int pd_unipc_table(const pd_config& cfg, const pd_unipc_args& u, const int64_t* 
         int _r = (expr);        \
         if (_r) return _r;      \
     } while (0)
+// One launch protocol for every enqueue function of engine `eng`: nothing in a dry pass, nothing after a workspace overflow, `n`
+// launches counted in stat "launches", an event bracket of profiling class `k` around them (k < 0: none); a non-zero `call` sets the
+// printf-style message that follows and returns 1.
+#define PD_LAUNCH_K(eng, n, k, call, ...)       \
+    do {                                        \
+        pd_engine* _pe = (eng);                 \
+        if (!_pe->arena.dry) {                  \
+            PD_TRY(_pe->check_arena());         \
+            Bracket _br(_pe, (k));              \
+            _pe->launches += (n);               \
+            if (call) {                         \
+                pd_set_error(__VA_ARGS__);      \
+                return 1;                       \
+            }                                   \
+        }                                       \
+    } while (0)
+#define PD_LAUNCH(eng, call, ...) PD_LAUNCH_K(eng, 1, -1, call, __VA_ARGS__)
 
 // A GEMM weight matrix [Nalloc][Kpad] in the compute type, K-contiguous, plus its fp32 bias.
 struct WMat {
@@ -604,10 +620,17 @@ struct pd_engine {
     int vae_decode_managed(VaeW& v, int which, const float* src, int B, int h, int w, float* dout, float scale, float shift);
     int vae_encode_managed(VaeEncW& v, int which, const float* src, int B, int H, int W, int what, const float* noise, float* dout, float scale,
                            float shift);
-    // Everything that runs outside a sampling step (first stage, HED, text encoders): `sizing` (a dry pass of the forward) measures the
-    // workspace, which is the ControlNet context's (arena2, idle outside a sampling step) grown to that plus io_bytes if needed; then `run`
-    // enqueues for real on the main stream.  `what` names the caller in the allocation-failure message.
-    int in_side_workspace(const char* what, size_t io_bytes, const std::function<int()>& sizing, const std::function<int()>& run);
+    // Everything that runs outside a sampling step (first stage, annotators, text / image encoders): body(SideCall&) is written once and
+    // run twice in the ControlNet context's workspace (arena2, idle outside a sampling step).  The first run is dry and measures the
+    // workspace -- the staging the body takes from its SideCall included -- which is grown to that plus 64 MiB of slack if needed (both
+    // streams synchronised, captured graphs dropped); the second enqueues for real on the main stream.  Then the staged destinations are
+    // copied out and the stream is synchronised, once.  `what` names the caller in the allocation-failure message.
+    template <class Body> int side_call(const char* what, Body&& body);
+    int side_grow(const char* what, size_t need);
+    // The frame of the seven pd_*_configure: session refusal, check() (the caller's own argument checks, in their old place), device,
+    // build() with the parameters it registers in group g, and the allocation-failure report; `who` is the entry point's name.
+    template <class Check, class Build> int configure(const char* who, WeightGroup g, Check&& check, Build&& build);
+    template <class Build> int configure(const char* who, WeightGroup g, Build&& build) { return configure(who, g, [] { return 0; }, build); }
 
     // CLIP text stack (text.cpp).  build_clip registers one CLIPTextModel under `prefix` (its "text_model."); the caller has filled the
     // dimensions and sized w.layers.  clip_blocks runs blocks [first, last) on the residual stream x, whose type the block's sums follow.
@@ -620,9 +643,6 @@ struct pd_engine {
     int clip_block(const TextLayerW& l, Act& x, int heads, Activation act, bool causal, float eps = 1e-5f);
     int clip_blocks(const ClipW& w, int first, int last, Act& x);
     int text_forward(const int* ids_dev, int B, float* out_dev, int clip_skip);
-    // token ids (int32, `mem` space) -> a workspace allocation; fp32 results back to the caller's `mem` space (both on the main stream)
-    int upload_ids(const int32_t* ids, size_t n, int mem, int** dev);
-    int download(float* dst, const float* src, size_t n, int mem);
 
     // HED edge detector (hed.cpp): registered by pd_hed_configure, runs in the same workspace as the first stage
     HedW hed;
@@ -805,3 +825,85 @@ struct pd_engine {
     int make_schedule(int steps, float eta, std::vector<int64_t>& ts, std::vector<float>& a, std::vector<float>& ap,
                       std::vector<float>& sg, std::vector<float>& s1m, const int64_t* custom_desc = nullptr);
 };
+
+// One profiled launch (option "profile"): an event bracket of class `klass` around what is enqueued while it lives.  Nothing with
+// profiling off, in a dry pass, or for klass < 0 (PD_LAUNCH).
+struct Bracket {
+    pd_engine* e;
+    pd_engine::ProfRec rec{};
+    const bool on;
+    Bracket(pd_engine* e_, int klass) : e(e_), on(klass >= 0 && e_->profiling && !e_->arena.dry) {
+        if (on) e->prof_begin(rec, klass, 0.0);
+    }
+    ~Bracket() {
+        if (on) e->prof_end(rec);
+    }
+};
+
+// Parameters registered while it lives belong to group g; GROUP_SAMPLER again on every path out.
+struct RegGroup {
+    pd_engine& e;
+    RegGroup(pd_engine& e_, int g) : e(e_) { e.reg_group = (WeightGroup)g; }
+    ~RegGroup() { e.reg_group = GROUP_SAMPLER; }
+};
+
+// The staging of one pd_engine::side_call, handed to its body.  Every allocation comes from the workspace in both passes, so the dry
+// pass measures it; copies are enqueued on the main stream in the real pass only.  n counts elements of T.
+struct SideCall {
+    pd_engine& e;
+    template <class T> T* scratch(size_t n) { return reinterpret_cast<T*>(e.arena.alloc(n * sizeof(T))); }
+    // *dev = the caller's p [n] as device memory: p itself from the device, a workspace copy (uploaded here) from the host
+    template <class T> int src(const T** dev, const T* p, size_t n, int mem) {
+        *dev = p;
+        if (mem == PD_MEM_DEVICE) return 0;
+        T* d = scratch<T>(n);
+        *dev = d;
+        return upload(d, p, n * sizeof(T));
+    }
+    int upload(void* dev, const void* host, size_t bytes);   // host memory -> a workspace allocation made elsewhere
+    // A workspace buffer that is copied to the caller's p (either memory space) after the body: `rows` rows of n elements, the caller's
+    // rows `pitch` elements apart (0: dense)
+    template <class T> T* dst(T* p, size_t n, int mem, size_t rows = 1, size_t pitch = 0) {
+        return reinterpret_cast<T*>(stage(p, n * sizeof(T), rows, pitch * sizeof(T), mem));
+    }
+    void* stage(void* p, size_t width, size_t rows, size_t pitch, int mem);
+    int finish();   // the copies out, then the call's one stream synchronisation
+    struct Back { void* dst; const void* src; size_t width, rows, pitch; int mem; };
+    std::vector<Back> backs;
+};
+
+template <class Body>
+int pd_engine::side_call(const char* what, Body&& body) {
+    SideCall f{*this};
+    std::swap(arena, arena2);
+    const Arena saved = arena;
+    arena.base = nullptr; arena.cap = 0; arena.top = 0; arena.peak = 0; arena.dry = true;
+    int r = body(f);
+    const size_t need = arena.peak + (64u << 20);
+    arena = saved;
+    arena.dry = false;
+    if (!r) r = side_grow(what, need);
+    if (!r) {
+        arena.top = 0; arena.peak = 0;
+        r = body(f);
+        if (!r) r = f.finish();
+        else hipStreamSynchronize(stream);   // an upload from the caller's memory may still be in flight
+        arena.top = 0;
+    }
+    std::swap(arena, arena2);
+    return r;
+}
+
+template <class Check, class Build>
+int pd_engine::configure(const char* who, WeightGroup g, Check&& check, Build&& build) {
+    if (ses.active) { pd_set_error("%s: end the sampling session first", who); return 1; }
+    PD_TRY(check());
+    HIP_OK(hipSetDevice(device));
+    alloc_failed = false;
+    {
+        RegGroup rg(*this, g);
+        build();
+    }
+    if (alloc_failed) { pd_set_error("%s: weight allocation failed", who); return 1; }
+    return 0;
+}

@@ -15,7 +15,7 @@ const int kWidth[5] = {64, 128, 256, 512, 512};
 // Registered in the order Network.__init__ creates the modules (= state_dict order): netVggOne .. netVggFiv, netScoreOne .. netScoreFiv,
 // netCombine; "hed." + Network's own names (the checkpoint's "module" prefix is "net", :69)
 void pd_engine::build_hed() {
-    reg_group = GROUP_HED;
+    RegGroup rg(*this, GROUP_HED);
     HedW& v = hed;
     int ci = 0, cin = 3;
     for (int s = 0; s < 5; ++s) {
@@ -37,18 +37,12 @@ void pd_engine::build_hed() {
     params.back().shape = {1, 5, 1, 1};
     reg_vec("hed.netCombine.0.bias", 1, &v.comb_b, 'b');
     v.built = true;
-    reg_group = GROUP_SAMPLER;
 }
 
 extern "C" int pd_hed_configure(pd_engine* e) {
     if (!e) { pd_set_error("bad argument"); return 1; }
     if (e->hed.built) return 0;
-    if (e->ses.active) { pd_set_error("pd_hed_configure: end the sampling session first"); return 1; }
-    HIP_OK(hipSetDevice(e->device));
-    e->alloc_failed = false;
-    e->build_hed();
-    if (e->alloc_failed) { pd_set_error("pd_hed_configure: weight allocation failed"); return 1; }
-    return 0;
+    return e->configure("pd_hed_configure", GROUP_HED, [&] { e->build_hed(); });
 }
 
 extern "C" int pd_hed_weights_missing(pd_engine* e) { return e ? e->missing(GROUP_HED) : 0; }
@@ -63,11 +57,7 @@ int pd_engine::hed_forward(const float* images_dev, int B, int H, int W, int wha
     Act cur = new_act(B, H, W, v.conv[0].m.cin_pad, T);
     float* score[5];
     for (int s = 0; s < 5; ++s) score[s] = reinterpret_cast<float*>(arena.alloc((size_t)B * (H >> s) * (W >> s) * sizeof(float)));
-    if (!arena.dry) {
-        PD_TRY(check_arena());
-        ++launches;
-        if (launch_hed_upload(images_dev, cur.p, T, B, H, W, cur.C, stream)) { pd_set_error("HED image upload launch failed"); return 1; }
-    }
+    PD_LAUNCH(this, launch_hed_upload(images_dev, cur.p, T, B, H, W, cur.C, stream), "HED image upload launch failed");
     int which = 0, ci = 0, h = H, w = W;
     for (int s = 0; s < 5; ++s) {
         for (int j = 0; j < kConvs[s]; ++j) {
@@ -81,25 +71,15 @@ int pd_engine::hed_forward(const float* images_dev, int B, int H, int W, int wha
         const bool pool = s < 4;
         Act pooled = cur;
         pooled.p = buf[which]; pooled.H = h / 2; pooled.W = w / 2;
-        if (!arena.dry) {
-            PD_TRY(check_arena());
-            ++launches;
-            if (launch_hed_stage_tail(cur.p, T, v.score_w[s], v.score_b[s], score[s], pool ? pooled.p : nullptr, B, h, w, cur.C, stream)) {
-                pd_set_error("HED stage-tail launch failed (stage %d, %d x %d x %d)", s + 1, h, w, cur.C);
-                return 1;
-            }
-        }
+        PD_LAUNCH(this, launch_hed_stage_tail(cur.p, T, v.score_w[s], v.score_b[s], score[s], pool ? pooled.p : nullptr, B, h, w, cur.C, stream),
+                  "HED stage-tail launch failed (stage %d, %d x %d x %d)", s + 1, h, w, cur.C);
         if (pool) {
             cur = pooled;
             which ^= 1;
             h /= 2; w /= 2;
         }
     }
-    if (!arena.dry) {
-        PD_TRY(check_arena());
-        ++launches;
-        if (launch_hed_fuse(score, v.comb_w, v.comb_b, out_dev, B, H, W, what, stream)) { pd_set_error("HED fuse launch failed"); return 1; }
-    }
+    PD_LAUNCH(this, launch_hed_fuse(score, v.comb_w, v.comb_b, out_dev, B, H, W, what, stream), "HED fuse launch failed");
     return 0;
 }
 
@@ -119,22 +99,9 @@ extern "C" int pd_hed_detect(pd_engine* e, const float* images, int32_t B, int32
     if ((long long)B * H * W * 5 >= (1ll << 31)) { pd_set_error("pd_hed_detect: B * H * W too large (%d x %d x %d); split the batch", B, H, W); return 1; }
     HIP_OK(hipSetDevice(e->device));
     const size_t n_in = (size_t)B * 3 * H * W, n_out = (size_t)B * (what == PD_HED_SIDES ? 5 : 1) * H * W;
-    return e->in_side_workspace("HED", (n_in + n_out) * sizeof(float), [&] { return e->hed_forward(nullptr, B, H, W, what, nullptr); }, [&] {
-        int r = 0;
-        float* din = reinterpret_cast<float*>(e->arena.alloc(n_in * sizeof(float)));
-        float* dout = reinterpret_cast<float*>(e->arena.alloc(n_out * sizeof(float)));
-        const float* src = images;
-        if (mem != PD_MEM_DEVICE) {
-            if (hipMemcpyAsync(din, images, n_in * sizeof(float), hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-                hipStreamSynchronize(e->stream) != hipSuccess) { pd_set_error("image upload failed"); r = 1; }
-            src = din;
-        }
-        if (!r) r = e->hed_forward(src, B, H, W, what, dout);
-        if (!r) {
-            if (hipMemcpyAsync(out, dout, n_out * sizeof(float), mem == PD_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
-                               e->stream) != hipSuccess ||
-                hipStreamSynchronize(e->stream) != hipSuccess) { pd_set_error("edge-map read-back failed"); r = 1; }
-        }
-        return r;
+    return e->side_call("HED", [&](SideCall& f) {
+        const float* src;
+        PD_TRY(f.src(&src, images, n_in, mem));
+        return e->hed_forward(src, B, H, W, what, f.dst(out, n_out, mem));
     });
 }

@@ -13,17 +13,7 @@
 
 namespace {
 
-// one profiled launch (option "profile"): klass 8 depthwise conv, 9 the detector's other element-wise kernels, 10 decode + raster
-struct Bracket {
-    pd_engine* e;
-    pd_engine::ProfRec rec{};
-    Bracket(pd_engine* e_, int klass) : e(e_) {
-        if (e->profiling && !e->arena.dry) e->prof_begin(rec, klass, 0.0);
-    }
-    ~Bracket() {
-        if (e->profiling && !e->arena.dry) e->prof_end(rec);
-    }
-};
+// profiling classes of the launches (Bracket): 8 depthwise conv, 9 the detector's other element-wise kernels, 10 decode + raster
 
 // inverted_residual_setting of MobileNetV2.__init__ (:173-182): expansion t, width c, repeats n, first stride s
 const int kSetting[5][4] = {{1, 16, 1, 1}, {6, 24, 2, 2}, {6, 32, 3, 2}, {6, 64, 4, 2}, {6, 96, 3, 1}};
@@ -48,7 +38,7 @@ void pd_engine::build_dw_bn(const std::string& conv, const std::string& bn, Mlsd
 
 // Registered in state_dict() order: per conv its weight, then the bias of the BatchNorm behind it (block23.conv3: its own bias)
 void pd_engine::build_mlsd() {
-    reg_group = GROUP_MLSD;
+    RegGroup rg(*this, GROUP_MLSD);
     MlsdW& v = mlsd;
     const std::string f = "mlsd.backbone.features.";
     build_conv_bn(f + "0.0.", f + "0.1.", v.conv0, 4, 32, 3, 2);
@@ -80,18 +70,12 @@ void pd_engine::build_mlsd() {
     build_conv_bn("mlsd.block23.conv2.0.", "mlsd.block23.conv2.1.", v.c2, 64, 64, 3, 1);
     build_conv("mlsd.block23.conv3.", v.c3, 64, 16, 1, 1);
     v.built = true;
-    reg_group = GROUP_SAMPLER;
 }
 
 extern "C" int pd_mlsd_configure(pd_engine* e) {
     if (!e) { pd_set_error("bad argument"); return 1; }
     if (e->mlsd.built) return 0;
-    if (e->ses.active) { pd_set_error("pd_mlsd_configure: end the sampling session first"); return 1; }
-    HIP_OK(hipSetDevice(e->device));
-    e->alloc_failed = false;
-    e->build_mlsd();
-    if (e->alloc_failed) { pd_set_error("pd_mlsd_configure: weight allocation failed"); return 1; }
-    return 0;
+    return e->configure("pd_mlsd_configure", GROUP_MLSD, [&] { e->build_mlsd(); });
 }
 
 extern "C" int pd_mlsd_weights_missing(pd_engine* e) { return e ? e->missing(GROUP_MLSD) : 0; }
@@ -115,12 +99,7 @@ int pd_engine::mlsd_forward(const uint8_t* images_dev, int B, int H, int W, floa
     MlsdW& v = mlsd;
     const size_t es = dt_size(T);
     Act x0 = new_act(B, H, W, 8, T);
-    if (!arena.dry) {
-        PD_TRY(check_arena());
-        Bracket br(this, 9);
-        ++launches;
-        if (launch_mlsd_upload(images_dev, x0.p, T, B, H, W, stream)) { pd_set_error("M-LSD image upload launch failed"); return 1; }
-    }
+    PD_LAUNCH_K(this, 1, 9, launch_mlsd_upload(images_dev, x0.p, T, B, H, W, stream), "M-LSD image upload launch failed");
     Act cur = new_act(B, H / 2, W / 2, 32, T);
     PD_TRY(conv(v.conv0, x0, cur, {.act = ACT_RELU}));
     Act tap[5];
@@ -159,12 +138,7 @@ int pd_engine::mlsd_forward(const uint8_t* images_dev, int B, int H, int W, floa
         } else {
             Act t = new_act(B, x.H, x.W, 64, T);
             PD_TRY(conv(v.a1[j], x, t, {.act = ACT_RELU}));
-            if (!arena.dry) {
-                PD_TRY(check_arena());
-                Bracket br(this, 9);
-                ++launches;
-                if (launch_mlsd_upcat(t.p, 64, hi.p, 128, T, B, x.H, x.W, 64, stream)) { pd_set_error("M-LSD upsample launch failed (block %d)", 15 + 2 * j); return 1; }
-            }
+            PD_LAUNCH_K(this, 1, 9, launch_mlsd_upcat(t.p, 64, hi.p, 128, T, B, x.H, x.W, 64, stream), "M-LSD upsample launch failed (block %d)", 15 + 2 * j);
         }
         // BlockTypeB: conv2(conv1(x) + x), ReLU inside both convs
         Act y1 = new_act(B, skip.H, skip.W, 128, T);
@@ -177,23 +151,14 @@ int pd_engine::mlsd_forward(const uint8_t* images_dev, int B, int H, int W, floa
     PD_TRY(conv(v.c1, x, z1, {.act = ACT_RELU}));
     PD_TRY(conv(v.c2, z1, z2, {.act = ACT_RELU}));
     PD_TRY(conv(v.c3, z2, z3));
-    if (!arena.dry) {
-        PD_TRY(check_arena());
-        Bracket br(this, 9);
-        ++launches;
-        if (launch_mlsd_tpmap(reinterpret_cast<const float*>(z3.p), tp_dev, B, x.H, x.W, stream)) { pd_set_error("M-LSD output launch failed"); return 1; }
-    }
+    PD_LAUNCH_K(this, 1, 9, launch_mlsd_tpmap(reinterpret_cast<const float*>(z3.p), tp_dev, B, x.H, x.W, stream), "M-LSD output launch failed");
     return 0;
 }
 
 int pd_engine::mlsd_decode(const float* tp_dev, int B, int h, int w, float thr_v, float thr_d, int* segs_dev, int* count_dev) {
     unsigned long long* cand = reinterpret_cast<unsigned long long*>(arena.alloc((size_t)B * h * w * sizeof(unsigned long long)));
     int* ncand = reinterpret_cast<int*>(arena.alloc((size_t)B * sizeof(int)));
-    if (arena.dry) return 0;
-    PD_TRY(check_arena());
-    Bracket br(this, 10);
-    launches += 2;
-    if (launch_mlsd_decode(tp_dev, cand, ncand, segs_dev, count_dev, B, h, w, thr_v, thr_d, stream)) { pd_set_error("M-LSD decode launch failed"); return 1; }
+    PD_LAUNCH_K(this, 2, 10, launch_mlsd_decode(tp_dev, cand, ncand, segs_dev, count_dev, B, h, w, thr_v, thr_d, stream), "M-LSD decode launch failed");
     return 0;
 }
 
@@ -226,50 +191,34 @@ extern "C" int pd_mlsd_detect_ex(pd_engine* e, const pd_mlsd_args* a) {
     const size_t n_px = (size_t)B * H * W, n_tp = (size_t)B * 9 * h * w, n_seg = (size_t)B * MLSD_TOPK * 4;
     const bool dev = a->mem == PD_MEM_DEVICE;
     const bool f_host = a->dst_f && a->mem_f != PD_MEM_DEVICE;
-    const size_t io = n_px * 3 + n_tp * 4 + (size_t)B * h * w * 8 + (n_seg + 2 * B) * 4 + 2 * n_px + (f_host ? n_px * 12 : 0);
-    return e->in_side_workspace("M-LSD", io, [&] { return e->mlsd_forward(nullptr, B, H, W, nullptr); }, [&] {
-        uint8_t* din = reinterpret_cast<uint8_t*>(e->arena.alloc(n_px * 3));
-        float* tp = reinterpret_cast<float*>(e->arena.alloc(n_tp * 4));
-        int* segs = reinterpret_cast<int*>(e->arena.alloc((n_seg + B) * 4));   // [B][200][4], then the B counts
+    return e->side_call("M-LSD", [&](SideCall& f) {
+        const uint8_t* src;
+        PD_TRY(f.src(&src, a->images, n_px * 3, a->mem));
+        // a device destination is written by the kernels themselves (tp-map, byte map); everything else is staged
+        float* tp = what != PD_MLSD_TPMAP ? f.scratch<float>(n_tp) : dev ? reinterpret_cast<float*>(a->out) : f.dst(reinterpret_cast<float*>(a->out), n_tp, a->mem);
+        PD_TRY(e->mlsd_forward(src, B, H, W, tp));
+        if (what == PD_MLSD_TPMAP) return 0;
+        // [B][200][4], then the B counts
+        int* segs = what == PD_MLSD_SEGMENTS ? f.dst(reinterpret_cast<int*>(a->out), n_seg + B, a->mem) : f.scratch<int>(n_seg + B);
         int* count = segs + n_seg;
-        uint8_t* map = reinterpret_cast<uint8_t*>(e->arena.alloc(n_px));
-        uint8_t* d8 = reinterpret_cast<uint8_t*>(e->arena.alloc(n_px));
-        float* fstage = f_host ? reinterpret_cast<float*>(e->arena.alloc(n_px * 12)) : nullptr;
-        const uint8_t* src = a->images;
-        if (!dev) {
-            HIP_OK(hipMemcpyAsync(din, a->images, n_px * 3, hipMemcpyHostToDevice, e->stream));
-            src = din;
-        }
-        float* tp_out = (what == PD_MLSD_TPMAP && dev) ? reinterpret_cast<float*>(a->out) : tp;
-        PD_TRY(e->mlsd_forward(src, B, H, W, tp_out));
-        if (what == PD_MLSD_TPMAP) {
-            if (!dev) HIP_OK(hipMemcpyAsync(a->out, tp, n_tp * 4, hipMemcpyDeviceToHost, e->stream));
-            HIP_OK(hipStreamSynchronize(e->stream));
-            return 0;
-        }
         PD_TRY(e->mlsd_decode(tp, B, h, w, a->thr_v, a->thr_d, segs, count));
-        if (what == PD_MLSD_SEGMENTS) {
-            HIP_OK(hipMemcpyAsync(a->out, segs, (n_seg + B) * 4, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, e->stream));
-            HIP_OK(hipStreamSynchronize(e->stream));
-            return 0;
-        }
-        uint8_t* o8 = a->out ? (dev ? reinterpret_cast<uint8_t*>(a->out) : d8) : nullptr;
+        if (what == PD_MLSD_SEGMENTS) return 0;
+        uint8_t* map = f.scratch<uint8_t>(n_px);
+        uint8_t* o8 = reinterpret_cast<uint8_t*>(a->out);
+        if (o8 && !dev) o8 = f.dst(o8, n_px, a->mem);
         float* df = a->dst_f;
         int Cf = a->Cf, c_off = a->c_off;
-        if (f_host) { df = fstage; Cf = 3; c_off = 0; }
-        {
+        if (f_host) {   // the three channels as a [B, 3, H, W] tensor, copied into channels c_off .. of the caller's Cf
+            df = f.dst(a->dst_f + (size_t)a->c_off * H * W, (size_t)3 * H * W, a->mem_f, (size_t)B, (size_t)a->Cf * H * W);
+            Cf = 3; c_off = 0;
+        }
+        if (!e->arena.dry) {   // both launches under one bracket
+            PD_TRY(e->check_arena());
             Bracket br(e, 10);
             e->launches += 2;
             if (launch_mlsd_draw(segs, count, MLSD_TOPK, map, B, H, W, e->stream)) { pd_set_error("pd_mlsd_detect: raster launch failed"); return 1; }
             if (launch_canny_emit(map, o8, df, B, H, W, Cf, c_off, a->mul, a->add, e->stream)) { pd_set_error("pd_mlsd_detect: emit launch failed"); return 1; }
         }
-        if (o8 && !dev) HIP_OK(hipMemcpyAsync(a->out, o8, n_px, hipMemcpyDeviceToHost, e->stream));
-        if (f_host) {
-            const size_t row = (size_t)3 * H * W * sizeof(float);
-            HIP_OK(hipMemcpy2DAsync(a->dst_f + (size_t)a->c_off * H * W, (size_t)a->Cf * H * W * sizeof(float), df, row, row, (size_t)B,
-                                    hipMemcpyDeviceToHost, e->stream));
-        }
-        HIP_OK(hipStreamSynchronize(e->stream));
         return 0;
     });
 }

@@ -76,7 +76,7 @@ int64_t pd_get_stat(pd_engine* e, const char* key) {
     if (!strcmp(key, "graph_captures")) return (int64_t)e->graph_captures;
     if (!strcmp(key, "graph_replays")) return (int64_t)e->graph_replays;
     if (!strcmp(key, "workspace_bytes")) return (int64_t)e->arena.cap;
-    if (!strcmp(key, "side_workspace_bytes")) return (int64_t)e->arena2.cap;   // what the first stage / HED / text encoders run in (in_side_workspace)
+    if (!strcmp(key, "side_workspace_bytes")) return (int64_t)e->arena2.cap;   // what the first stage / HED / text encoders run in (side_call)
     if (!strcmp(key, "weight_bytes")) return (int64_t)e->weight_bytes;
     if (!strcmp(key, "launches")) return (int64_t)e->launches;
     if (!strcmp(key, "image_allocs")) return (int64_t)e->image_allocs;   // allocations of pd_image_load / pd_image_store / pd_canny so far

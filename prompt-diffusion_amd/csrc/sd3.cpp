@@ -136,28 +136,18 @@ int pd_engine::sd3_embed(Sd3NetW& net, const Sd3Io& io, bool controlnet, Act& hs
     pe.taps = 1; pe.cin = pe.cin_pad = net.pe.K;
     Act pos = new_act(B, N, 1, D, DT_F32);
     Act rows = new_act(B, N, 1, net.pe.K, T);
-    if (!arena.dry) {
-        PD_TRY(check_arena());
-        launches += 2;
-        if (launch_pos_crop(net.pos, reinterpret_cast<float*>(pos.p), B, h, w, net.pos_max, D, stream) ||
-            launch_patchify(io.latents, rows.p, T, B, sd3.in_channels, io.H, io.W, ps, net.pe.cin_pad, net.pe.K, stream)) {
-            pd_set_error("sd3: patch embedding launch failed (latent %dx%d, pos_embed_max_size %d)", io.H, io.W, net.pos_max);
-            return 1;
-        }
-    }
+    PD_LAUNCH_K(this, 2, -1,
+                launch_pos_crop(net.pos, reinterpret_cast<float*>(pos.p), B, h, w, net.pos_max, D, stream) ||
+                    launch_patchify(io.latents, rows.p, T, B, sd3.in_channels, io.H, io.W, ps, net.pe.cin_pad, net.pe.K, stream),
+                "sd3: patch embedding launch failed (latent %dx%d, pos_embed_max_size %d)", io.H, io.W, net.pos_max);
     PD_TRY(gemm(pe, rows, hs, {.R = &pos}));
     if (controlnet) {   // hidden_states + pos_embed_input(cond) + pos_embed_input(example pair)   (:440)
         WMat pi = net.pe_in;
         pi.taps = 1; pi.cin = pi.cin_pad = net.pe_in.K;
         const float* src[2] = {io.cond, io.pair};
         for (int j = 0; j < 2; ++j) {
-            if (!arena.dry) {
-                ++launches;
-                if (launch_patchify(src[j], rows.p, T, B, sd3.in_channels, io.H, io.W, ps, net.pe_in.cin_pad, net.pe_in.K, stream)) {
-                    pd_set_error("sd3: condition patchify launch failed");
-                    return 1;
-                }
-            }
+            PD_LAUNCH(this, launch_patchify(src[j], rows.p, T, B, sd3.in_channels, io.H, io.W, ps, net.pe_in.cin_pad, net.pe_in.K, stream),
+                      "sd3: condition patchify launch failed");
             PD_TRY(gemm(pi, rows, hs, {.R = &hs}));   // in place: R == C element-wise
         }
     }
@@ -186,13 +176,7 @@ int pd_engine::sd3_embed(Sd3NetW& net, const Sd3Io& io, bool controlnet, Act& hs
     // context_embedder
     if (net.single) { arena.release(mk); return 0; }
     Act ctx = new_act(B, io.S, 1, round_up(sd3.joint_dim, 8), T);
-    if (!arena.dry) {
-        ++launches;
-        if (launch_cast_rows(io.context, ctx.p, T, (long long)B * io.S, sd3.joint_dim, ctx.C, stream)) {
-            pd_set_error("sd3: context cast launch failed");
-            return 1;
-        }
-    }
+    PD_LAUNCH(this, launch_cast_rows(io.context, ctx.p, T, (long long)B * io.S, sd3.joint_dim, ctx.C, stream), "sd3: context cast launch failed");
     PD_TRY(gemm(net.ctx_emb, ctx, c));
     arena.release(mk);
     return 0;
@@ -220,15 +204,10 @@ int pd_engine::sd3_block(const Sd3BlockW& b, Act& x, Act& c, const Act& modbuf, 
     constexpr float kBoundMargin = 1.13f;
     auto adaln = [&](const Act& in, Act& out, int shift_off, int scale_off, float* row_scale, const void* add = nullptr,
                      float* bound_out = nullptr, const WMat* consumer = nullptr) -> int {
-        if (arena.dry) return 0;
-        PD_TRY(check_arena());
-        ++launches;
         const float bmul = consumer ? kBoundMargin * consumer->wnorm_max / 448.0f : 0.f, badd = consumer ? consumer->bias_max / 448.0f : 0.f;
-        if (launch_adaln(in.p, in.dt, out.p, out.dt, mod, ms, shift_off, scale_off, (int)in.rows(), in.H, D, 1e-6f, stream, row_scale, add,
-                         bound_out, bmul, badd)) {
-            pd_set_error("sd3: AdaLN launch failed (C=%d)", D);
-            return 1;
-        }
+        PD_LAUNCH(this, launch_adaln(in.p, in.dt, out.p, out.dt, mod, ms, shift_off, scale_off, (int)in.rows(), in.H, D, 1e-6f, stream, row_scale, add,
+                                     bound_out, bmul, badd),
+                  "sd3: AdaLN launch failed (C=%d)", D);
         return 0;
     };
     auto scales = [&](int rows) { return f8 ? reinterpret_cast<float*>(arena.alloc((size_t)rows * sizeof(float))) : nullptr; };
@@ -246,12 +225,9 @@ int pd_engine::sd3_block(const Sd3BlockW& b, Act& x, Act& c, const Act& modbuf, 
         PD_TRY(adaln(x, xn2, b.mod_off + 6 * D, b.mod_off + 7 * D, nullptr));
     }
     auto qk_norm = [&](const Act& buf, int rows_per_sample, int n_first, const float* wq, const float* wk, const float* wq2, const float* wk2) -> int {
-        if (!sd3.qk_norm || arena.dry) return 0;
-        ++launches;
-        if (launch_qk_rmsnorm(buf.p, T, (long long)B * rows_per_sample, rows_per_sample, n_first, heads, D / heads, wq, wk, wq2, wk2, 1e-6f, stream)) {
-            pd_set_error("sd3: qk RMSNorm launch failed");
-            return 1;
-        }
+        if (!sd3.qk_norm) return 0;
+        PD_LAUNCH(this, launch_qk_rmsnorm(buf.p, T, (long long)B * rows_per_sample, rows_per_sample, n_first, heads, D / heads, wq, wk, wq2, wk2, 1e-6f, stream),
+                  "sd3: qk RMSNorm launch failed");
         return 0;
     };
     // both QKV GEMMs store straight into the joint buffers
@@ -397,13 +373,7 @@ int pd_engine::sd3_forward(const Sd3Io& io, float* v_out, int control_index, flo
                 Act in = hs;
                 if (hs.dt != T) {   // stream_f32: the zero Linear reads 2-byte operands
                     in = new_act(B, N, 1, D, T);
-                    if (!arena.dry) {
-                        ++launches;
-                        if (launch_cast_rows(reinterpret_cast<const float*>(hs.p), in.p, T, (long long)B * N, D, D, stream)) {
-                            pd_set_error("sd3: cast launch failed");
-                            return 1;
-                        }
-                    }
+                    PD_LAUNCH(this, launch_cast_rows(reinterpret_cast<const float*>(hs.p), in.p, T, (long long)B * N, D, D, stream), "sd3: cast launch failed");
                 }
                 PD_TRY(gemm(net.zero[i], in, control[i], {.scale = io.scale}));
                 if (two && !arena.dry) HIP_OK(hipEventRecord(sd3_ev[i], stream));   // residual i is ready (`stream` is stream2 here)
@@ -450,23 +420,11 @@ int pd_engine::sd3_forward(const Sd3Io& io, float* v_out, int control_index, flo
     // norm_out (AdaLayerNormContinuous: scale, shift) + proj_out + unpatchify
     Act nx = new_act(B, N, 1, D, T);
     Act out = new_act(B, N, 1, net.proj_out.N, DT_F32);
-    if (!arena.dry) {
-        PD_TRY(check_arena());
-        ++launches;
-        if (launch_adaln(hs.p, hs.dt, nx.p, T, reinterpret_cast<const float*>(modbuf.p), modbuf.C, net.norm_out_off + D, net.norm_out_off,
-                         B * N, N, D, 1e-6f, stream)) {
-            pd_set_error("sd3: norm_out launch failed");
-            return 1;
-        }
-    }
+    PD_LAUNCH(this, launch_adaln(hs.p, hs.dt, nx.p, T, reinterpret_cast<const float*>(modbuf.p), modbuf.C, net.norm_out_off + D, net.norm_out_off, B * N, N, D,
+                                 1e-6f, stream),
+              "sd3: norm_out launch failed");
     PD_TRY(gemm(net.proj_out, nx, out));
-    if (!arena.dry) {
-        ++launches;
-        if (launch_unpatchify(out.p, DT_F32, out.C, v_out, B, sd3.out_channels, h, w, ps, stream)) {
-            pd_set_error("sd3: unpatchify launch failed");
-            return 1;
-        }
-    }
+    PD_LAUNCH(this, launch_unpatchify(out.p, DT_F32, out.C, v_out, B, sd3.out_channels, h, w, ps, stream), "sd3: unpatchify launch failed");
     arena.release(mk0);
     return 0;
 }
@@ -475,32 +433,30 @@ int pd_engine::sd3_forward(const Sd3Io& io, float* v_out, int control_index, flo
 extern "C" int pd_sd3_configure(pd_engine* e, const pd_sd3_config* c) {
     if (!e || !c) { pd_set_error("bad argument"); return 1; }
     if (e->sd3_tr.built) { pd_set_error("pd_sd3_configure: already configured"); return 1; }
-    if (e->ses.active) { pd_set_error("pd_sd3_configure: end the sampling session first"); return 1; }
-    const long long D = (long long)c->heads * c->head_dim;
-    if (c->in_channels < 1 || c->out_channels < 1 || c->patch_size < 1 || c->patch_size > 4 || c->heads < 1 || c->layers < 1 ||
-        c->cn_layers < 0 || c->joint_dim < 1 || c->pooled_dim < 1 || c->pos_embed_max_size < 1 || c->cn_pos_embed_max_size < 0) {
-        pd_set_error("pd_sd3_configure: invalid configuration");
-        return 1;
-    }
-    if (c->head_dim != 8 && c->head_dim != 16 && c->head_dim != 32 && c->head_dim != 64) {
-        pd_set_error("pd_sd3_configure: head_dim %d not supported (8, 16, 32, 64)", c->head_dim);
-        return 1;
-    }
-    if (D % 8 || D > 2048) { pd_set_error("pd_sd3_configure: hidden size %lld must be a multiple of 8 and <= 2048", D); return 1; }
-    if ((c->cn_single != 0 && c->cn_single != 1) || (c->cn_single && c->cn_dual_mask)) {
-        pd_set_error("pd_sd3_configure: cn_single must be 0 or 1, and single blocks have no second attention (cn_dual_mask %u)", c->cn_dual_mask);
-        return 1;
-    }
-    if (c->cn_layers > c->layers) { pd_set_error("pd_sd3_configure: more ControlNet blocks (%d) than transformer blocks (%d)", c->cn_layers, c->layers); return 1; }
-    HIP_OK(hipSetDevice(e->device));
-    e->sd3 = *c;
-    e->alloc_failed = false;
-    e->reg_group = GROUP_SD3;
-    e->build_sd3_net("transformer.", e->sd3_tr, false);
-    if (c->cn_layers > 0) e->build_sd3_net("controlnet.", e->sd3_cn, true);
-    e->reg_group = GROUP_SAMPLER;
-    if (e->alloc_failed) { pd_set_error("pd_sd3_configure: weight allocation failed"); return 1; }
-    return 0;
+    auto check = [&]() -> int {
+        const long long D = (long long)c->heads * c->head_dim;
+        if (c->in_channels < 1 || c->out_channels < 1 || c->patch_size < 1 || c->patch_size > 4 || c->heads < 1 || c->layers < 1 ||
+            c->cn_layers < 0 || c->joint_dim < 1 || c->pooled_dim < 1 || c->pos_embed_max_size < 1 || c->cn_pos_embed_max_size < 0) {
+            pd_set_error("pd_sd3_configure: invalid configuration");
+            return 1;
+        }
+        if (c->head_dim != 8 && c->head_dim != 16 && c->head_dim != 32 && c->head_dim != 64) {
+            pd_set_error("pd_sd3_configure: head_dim %d not supported (8, 16, 32, 64)", c->head_dim);
+            return 1;
+        }
+        if (D % 8 || D > 2048) { pd_set_error("pd_sd3_configure: hidden size %lld must be a multiple of 8 and <= 2048", D); return 1; }
+        if ((c->cn_single != 0 && c->cn_single != 1) || (c->cn_single && c->cn_dual_mask)) {
+            pd_set_error("pd_sd3_configure: cn_single must be 0 or 1, and single blocks have no second attention (cn_dual_mask %u)", c->cn_dual_mask);
+            return 1;
+        }
+        if (c->cn_layers > c->layers) { pd_set_error("pd_sd3_configure: more ControlNet blocks (%d) than transformer blocks (%d)", c->cn_layers, c->layers); return 1; }
+        return 0;
+    };
+    return e->configure("pd_sd3_configure", GROUP_SD3, check, [&] {
+        e->sd3 = *c;
+        e->build_sd3_net("transformer.", e->sd3_tr, false);
+        if (c->cn_layers > 0) e->build_sd3_net("controlnet.", e->sd3_cn, true);
+    });
 }
 
 extern "C" int pd_sd3_weights_missing(pd_engine* e) { return e ? e->missing(GROUP_SD3) : 0; }

@@ -46,63 +46,56 @@ void pd_engine::build_sd3_t5(const std::string& prefix) {
 extern "C" int pd_sd3_text_configure(pd_engine* e, const pd_sd3_text_config* c) {
     if (!e || !c) { pd_set_error("bad argument"); return 1; }
     if (e->sd3_clip[0].built || e->sd3_clip[1].built || e->sd3_t5.built) { pd_set_error("pd_sd3_text_configure: already configured"); return 1; }
-    if (e->ses.active) { pd_set_error("pd_sd3_text_configure: end the sampling session first"); return 1; }
     const pd_sd3_clip_config* cl[2] = {&c->clip_l, &c->clip_g};
-    int clip_width = 0;
-    for (int i = 0; i < 2; ++i) {
-        const pd_sd3_clip_config& k = *cl[i];
-        if (k.layers == 0) continue;
-        if (k.layers < 0 || k.vocab < 1 || k.hidden < 64 || k.heads < 1 || k.hidden != 64 * k.heads || k.ff < 8 || k.ff % 8 || k.max_positions != kClipLen ||
-            k.proj_dim < 1 || k.hidden > 2048 || (k.act != PD_CLIP_ACT_QUICK_GELU && k.act != PD_CLIP_ACT_GELU)) {
-            pd_set_error("pd_sd3_text_configure: CLIP slot %d: need hidden = 64 * heads <= 2048, ff a multiple of 8, max_positions 77, proj_dim >= 1, a known act", i);
-            return 1;
-        }
-        clip_width += k.hidden;
-    }
     const pd_sd3_t5_config& t = c->t5;
-    if (t.layers != 0) {
-        if (t.layers < 0 || t.vocab < 1 || t.d_kv != 64 || t.heads < 1 || t.d_model < 8 || t.d_model % 8 || t.d_ff < 8 || t.d_ff % 8 || t.num_buckets < 4 ||
-            t.num_buckets % 2 || t.max_distance <= t.num_buckets / 4 || !(t.eps > 0.f)) {
-            pd_set_error("pd_sd3_text_configure: T5: need d_kv 64, d_model and d_ff multiples of 8, an even num_buckets >= 4, max_distance > num_buckets / 4, eps > 0");
-            return 1;
+    auto check = [&]() -> int {
+        int clip_width = 0;
+        for (int i = 0; i < 2; ++i) {
+            const pd_sd3_clip_config& k = *cl[i];
+            if (k.layers == 0) continue;
+            if (k.layers < 0 || k.vocab < 1 || k.hidden < 64 || k.heads < 1 || k.hidden != 64 * k.heads || k.ff < 8 || k.ff % 8 || k.max_positions != kClipLen ||
+                k.proj_dim < 1 || k.hidden > 2048 || (k.act != PD_CLIP_ACT_QUICK_GELU && k.act != PD_CLIP_ACT_GELU)) {
+                pd_set_error("pd_sd3_text_configure: CLIP slot %d: need hidden = 64 * heads <= 2048, ff a multiple of 8, max_positions 77, proj_dim >= 1, a known act", i);
+                return 1;
+            }
+            clip_width += k.hidden;
         }
-        if (c->joint_dim != t.d_model) { pd_set_error("pd_sd3_text_configure: joint_dim %d must equal T5's d_model %d (the reference concatenates them row-wise)", c->joint_dim, t.d_model); return 1; }
-    }
-    if (c->joint_dim < clip_width || c->joint_dim % 4) { pd_set_error("pd_sd3_text_configure: joint_dim %d must be a multiple of 4 and hold both CLIP hidden states (%d)", c->joint_dim, clip_width); return 1; }
-    HIP_OK(hipSetDevice(e->device));
-    e->alloc_failed = false;
-    e->reg_group = GROUP_SD3_TEXT;
-    e->sd3_text_joint = c->joint_dim;
-    const std::string prefix[2] = {"text_encoder.", "text_encoder_2."};
-    for (int i = 0; i < 2; ++i) {
-        const pd_sd3_clip_config& k = *cl[i];
-        if (k.layers == 0) continue;
-        ClipW& w = e->sd3_clip[i];
-        w.vocab = k.vocab; w.hidden = k.hidden; w.ff = k.ff; w.heads = k.heads; w.positions = k.max_positions;
-        w.proj_dim = k.proj_dim; w.eos_token_id = k.eos_token_id;
-        w.act = k.act == PD_CLIP_ACT_GELU ? ACT_ERF_GELU : ACT_QUICK_GELU;
-        w.layers.resize(k.layers);
-        e->build_clip(prefix[i] + "text_model.", w);
-        e->make_mat(w.proj, w.proj_dim, w.hidden, 1, w.hidden, false);
-        e->reg_mat(prefix[i] + "text_projection.weight", {w.proj_dim, w.hidden}, &w.proj, 0, false);
-    }
-    if (t.layers > 0) { e->sd3_t5.c = t; e->build_sd3_t5("text_encoder_3."); }
-    e->reg_group = GROUP_SAMPLER;
-    if (e->alloc_failed) { pd_set_error("pd_sd3_text_configure: weight allocation failed"); return 1; }
-    return 0;
+        if (t.layers != 0) {
+            if (t.layers < 0 || t.vocab < 1 || t.d_kv != 64 || t.heads < 1 || t.d_model < 8 || t.d_model % 8 || t.d_ff < 8 || t.d_ff % 8 || t.num_buckets < 4 ||
+                t.num_buckets % 2 || t.max_distance <= t.num_buckets / 4 || !(t.eps > 0.f)) {
+                pd_set_error("pd_sd3_text_configure: T5: need d_kv 64, d_model and d_ff multiples of 8, an even num_buckets >= 4, max_distance > num_buckets / 4, eps > 0");
+                return 1;
+            }
+            if (c->joint_dim != t.d_model) { pd_set_error("pd_sd3_text_configure: joint_dim %d must equal T5's d_model %d (the reference concatenates them row-wise)", c->joint_dim, t.d_model); return 1; }
+        }
+        if (c->joint_dim < clip_width || c->joint_dim % 4) { pd_set_error("pd_sd3_text_configure: joint_dim %d must be a multiple of 4 and hold both CLIP hidden states (%d)", c->joint_dim, clip_width); return 1; }
+        return 0;
+    };
+    return e->configure("pd_sd3_text_configure", GROUP_SD3_TEXT, check, [&] {
+        e->sd3_text_joint = c->joint_dim;
+        const std::string prefix[2] = {"text_encoder.", "text_encoder_2."};
+        for (int i = 0; i < 2; ++i) {
+            const pd_sd3_clip_config& k = *cl[i];
+            if (k.layers == 0) continue;
+            ClipW& w = e->sd3_clip[i];
+            w.vocab = k.vocab; w.hidden = k.hidden; w.ff = k.ff; w.heads = k.heads; w.positions = k.max_positions;
+            w.proj_dim = k.proj_dim; w.eos_token_id = k.eos_token_id;
+            w.act = k.act == PD_CLIP_ACT_GELU ? ACT_ERF_GELU : ACT_QUICK_GELU;
+            w.layers.resize(k.layers);
+            e->build_clip(prefix[i] + "text_model.", w);
+            e->make_mat(w.proj, w.proj_dim, w.hidden, 1, w.hidden, false);
+            e->reg_mat(prefix[i] + "text_projection.weight", {w.proj_dim, w.hidden}, &w.proj, 0, false);
+        }
+        if (t.layers > 0) { e->sd3_t5.c = t; e->build_sd3_t5("text_encoder_3."); }
+    });
 }
 
 extern "C" int pd_sd3_text_weights_missing(pd_engine* e) { return e ? e->missing(GROUP_SD3_TEXT) : 0; }
 
 int pd_engine::rmsnorm(const Act& x, void* y, int y_dt, const float* w, float eps, int y_sample_rows, int y_row_off, int y_ld) {
-    if (arena.dry) return 0;
-    PD_TRY(check_arena());
-    ++launches;
-    if (x.dt != DT_F32 || launch_rmsnorm_rows(reinterpret_cast<const float*>(x.p), y, y_dt, w, x.rows(), x.C, eps, x.H * x.W, y_sample_rows, y_row_off,
-                                              y_ld ? y_ld : x.C, stream)) {
-        pd_set_error("rmsnorm launch failed (C=%d)", x.C);
-        return 1;
-    }
+    PD_LAUNCH(this, x.dt != DT_F32 || launch_rmsnorm_rows(reinterpret_cast<const float*>(x.p), y, y_dt, w, x.rows(), x.C, eps, x.H * x.W, y_sample_rows,
+                                                          y_row_off, y_ld ? y_ld : x.C, stream),
+              "rmsnorm launch failed (C=%d)", x.C);
     return 0;
 }
 
@@ -178,25 +171,20 @@ extern "C" int pd_sd3_encode_prompt(pd_engine* e, const pd_sd3_text_args* a, flo
     HIP_OK(hipSetDevice(e->device));
     const int B = a->batch, Lt = t5 ? a->t5_len : 0, J = e->sd3_text_joint, rows = kClipLen + Lt;
     const int Cl = e->sd3_clip[0].hidden, Pl = e->sd3_clip[0].proj_dim, Pg = e->sd3_clip[1].proj_dim;
-    const size_t n_pe = (size_t)B * rows * J, n_po = (size_t)B * (Pl + Pg), n_ids = (size_t)B * (2 * kClipLen + Lt);
-    auto body = [&](bool dry) -> int {
-        int *il = nullptr, *ig = nullptr, *it = nullptr;
-        PD_TRY(e->upload_ids(a->ids_clip_l, (size_t)B * kClipLen, a->mem, &il));
-        PD_TRY(e->upload_ids(a->ids_clip_g, (size_t)B * kClipLen, a->mem, &ig));
-        if (t5) PD_TRY(e->upload_ids(a->ids_t5, (size_t)B * Lt, a->mem, &it));
-        float* dpe = reinterpret_cast<float*>(e->arena.alloc(n_pe * sizeof(float)));
-        float* dpo = reinterpret_cast<float*>(e->arena.alloc(n_po * sizeof(float)));
+    const size_t n_pe = (size_t)B * rows * J, n_po = (size_t)B * (Pl + Pg);
+    return e->side_call("SD3 text", [&](SideCall& f) {
+        const int *il, *ig, *it = nullptr;
+        PD_TRY(f.src(&il, a->ids_clip_l, (size_t)B * kClipLen, a->mem));
+        PD_TRY(f.src(&ig, a->ids_clip_g, (size_t)B * kClipLen, a->mem));
+        if (t5) PD_TRY(f.src(&it, a->ids_t5, (size_t)B * Lt, a->mem));
+        float* dpe = f.dst(prompt_embeds, n_pe, a->mem);
+        float* dpo = f.dst(pooled, n_po, a->mem);
         // rows 0..76: CLIP-L | CLIP-G | zeros up to joint_dim (the second write carries the pad); rows 77..: T5
         PD_TRY(e->sd3_clip_forward(e->sd3_clip[0], il, B, a->clip_skip, dpe, rows, J, 0, Cl, dpo, Pl + Pg));
         PD_TRY(e->sd3_clip_forward(e->sd3_clip[1], ig, B, a->clip_skip, dpe, rows, J, Cl, J - Cl, dpo + Pl, Pl + Pg));
         if (t5) PD_TRY(e->sd3_t5_forward(it, B, Lt, dpe, rows, kClipLen));
-        if (dry) return 0;
-        PD_TRY(e->download(prompt_embeds, dpe, n_pe, a->mem));
-        PD_TRY(e->download(pooled, dpo, n_po, a->mem));
-        HIP_OK(hipStreamSynchronize(e->stream));
         return 0;
-    };
-    return e->in_side_workspace("SD3 text", (n_pe + n_po) * sizeof(float) + n_ids * sizeof(int) + 4096, [&] { return body(true); }, [&] { return body(false); });
+    });
 }
 
 extern "C" int pd_sd3_text_encoder(pd_engine* e, int32_t which, const int32_t* ids, int32_t B, int32_t len, int32_t clip_skip, int32_t mem,
@@ -209,19 +197,11 @@ extern "C" int pd_sd3_text_encoder(pd_engine* e, int32_t which, const int32_t* i
     PD_TRY(text_ready(e, "pd_sd3_text_encoder"));
     HIP_OK(hipSetDevice(e->device));
     const int L = t5 ? len : kClipLen, C = t5 ? e->sd3_t5.c.d_model : e->sd3_clip[which].hidden, Pd = t5 ? 0 : e->sd3_clip[which].proj_dim;
-    const size_t n_h = hidden ? (size_t)B * L * C : 0, n_p = pooled ? (size_t)B * Pd : 0;
-    auto body = [&](bool dry) -> int {
-        int* di = nullptr;
-        PD_TRY(e->upload_ids(ids, (size_t)B * L, mem, &di));
-        float* dh = hidden ? reinterpret_cast<float*>(e->arena.alloc(n_h * sizeof(float))) : nullptr;
-        float* dp = pooled ? reinterpret_cast<float*>(e->arena.alloc(n_p * sizeof(float))) : nullptr;
-        if (t5) PD_TRY(e->sd3_t5_forward(di, B, L, dh, L, 0));
-        else PD_TRY(e->sd3_clip_forward(e->sd3_clip[which], di, B, clip_skip, dh, L, C, 0, C, dp, Pd));
-        if (dry) return 0;
-        if (hidden) PD_TRY(e->download(hidden, dh, n_h, mem));
-        if (pooled) PD_TRY(e->download(pooled, dp, n_p, mem));
-        HIP_OK(hipStreamSynchronize(e->stream));
-        return 0;
-    };
-    return e->in_side_workspace("SD3 text", (n_h + n_p) * sizeof(float) + (size_t)B * L * sizeof(int) + 4096, [&] { return body(true); }, [&] { return body(false); });
+    return e->side_call("SD3 text", [&](SideCall& f) {
+        const int* di;
+        PD_TRY(f.src(&di, ids, (size_t)B * L, mem));
+        float* dh = hidden ? f.dst(hidden, (size_t)B * L * C, mem) : nullptr;
+        float* dp = pooled ? f.dst(pooled, (size_t)B * Pd, mem) : nullptr;
+        return t5 ? e->sd3_t5_forward(di, B, L, dh, L, 0) : e->sd3_clip_forward(e->sd3_clip[which], di, B, clip_skip, dh, L, C, 0, C, dp, Pd);
+    });
 }

@@ -21,41 +21,42 @@ extern "C" int pd_sd3_vae_config_layout(int32_t* size, int32_t* off_scaling, int
 extern "C" int pd_sd3_vae_configure(pd_engine* e, const pd_sd3_vae_config* c) {
     if (!e || !c) { pd_set_error("bad argument"); return 1; }
     if (e->sd3_vae.built) { pd_set_error("pd_sd3_vae_configure: already configured"); return 1; }
-    if (e->ses.active) { pd_set_error("pd_sd3_vae_configure: end the sampling session first"); return 1; }
-    bool ok = c->ch >= 32 && c->ch % 32 == 0 && c->num_levels >= 1 && c->num_levels <= PD_MAX_LEVELS && c->num_res_blocks >= 1 && c->z_channels >= 1 &&
-              c->out_ch >= 1 && c->out_ch <= 4 && c->scaling_factor > 0.0;
-    for (int i = 0; ok && i < c->num_levels; ++i) ok = c->ch_mult[i] >= 1;
-    if (!ok) {
-        pd_set_error("pd_sd3_vae_configure: need ch a multiple of 32 (GroupNorm groups), 1 <= num_levels <= %d, ch_mult >= 1, num_res_blocks >= 1, "
-                     "z_channels >= 1, 1 <= out_ch <= 4, scaling_factor > 0", PD_MAX_LEVELS);
-        return 1;
-    }
-    HIP_OK(hipSetDevice(e->device));
-    e->alloc_failed = false;
-    VaeDesc d;
-    d.z = c->z_channels;
-    d.zpad = round_up(d.z, 8);
-    d.ch = c->ch;
-    d.num_levels = c->num_levels;
-    for (int i = 0; i < c->num_levels; ++i) d.ch_mult[i] = c->ch_mult[i];
-    d.num_res_blocks = c->num_res_blocks;
-    d.out_ch = c->out_ch;
-    d.scaling = c->scaling_factor;
-    d.shift = c->shift_factor;
-    d.flash_auto = true;
-    d.diffusers = true;
-    d.group = GROUP_SD3_VAE;
-    d.enc_group = GROUP_SD3_VAE_ENCODER;
-    d.quant = c->post_quant_conv != 0;
-    e->sd3_vae.d = d;
-    e->build_vae_decoder(e->sd3_vae, "vae.");
-    if (c->encoder) {
-        d.quant = c->quant_conv != 0;
-        e->sd3_vae_enc.d = d;
-        e->build_vae_encoder(e->sd3_vae_enc, "vae.");
-    }
-    if (e->alloc_failed) { pd_set_error("pd_sd3_vae_configure: weight allocation failed"); return 1; }
-    return 0;
+    auto check = [&]() -> int {
+        bool ok = c->ch >= 32 && c->ch % 32 == 0 && c->num_levels >= 1 && c->num_levels <= PD_MAX_LEVELS && c->num_res_blocks >= 1 && c->z_channels >= 1 &&
+                  c->out_ch >= 1 && c->out_ch <= 4 && c->scaling_factor > 0.0;
+        for (int i = 0; ok && i < c->num_levels; ++i) ok = c->ch_mult[i] >= 1;
+        if (!ok) {
+            pd_set_error("pd_sd3_vae_configure: need ch a multiple of 32 (GroupNorm groups), 1 <= num_levels <= %d, ch_mult >= 1, num_res_blocks >= 1, "
+                         "z_channels >= 1, 1 <= out_ch <= 4, scaling_factor > 0", PD_MAX_LEVELS);
+            return 1;
+        }
+        return 0;
+    };
+    // (the builders register under the groups of their VaeDesc)
+    return e->configure("pd_sd3_vae_configure", GROUP_SD3_VAE, check, [&] {
+        VaeDesc d;
+        d.z = c->z_channels;
+        d.zpad = round_up(d.z, 8);
+        d.ch = c->ch;
+        d.num_levels = c->num_levels;
+        for (int i = 0; i < c->num_levels; ++i) d.ch_mult[i] = c->ch_mult[i];
+        d.num_res_blocks = c->num_res_blocks;
+        d.out_ch = c->out_ch;
+        d.scaling = c->scaling_factor;
+        d.shift = c->shift_factor;
+        d.flash_auto = true;
+        d.diffusers = true;
+        d.group = GROUP_SD3_VAE;
+        d.enc_group = GROUP_SD3_VAE_ENCODER;
+        d.quant = c->post_quant_conv != 0;
+        e->sd3_vae.d = d;
+        e->build_vae_decoder(e->sd3_vae, "vae.");
+        if (c->encoder) {
+            d.quant = c->quant_conv != 0;
+            e->sd3_vae_enc.d = d;
+            e->build_vae_encoder(e->sd3_vae_enc, "vae.");
+        }
+    });
 }
 
 extern "C" int pd_sd3_vae_weights_missing(pd_engine* e) {

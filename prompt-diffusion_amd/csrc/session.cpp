@@ -204,23 +204,14 @@ int pd_engine::session_setup(const pd_sample_args& a, const int64_t* t_rows, int
             if (s.mask) HIP_OK(hipMemcpyAsync(s.mask, a.mask, (size_t)B * HW * 4, kind, stream));
             HIP_OK(hipStreamSynchronize(stream));
             const BlendCoef& b0 = s.blend[0];
-            ++launches;
-            if (launch_init_latents(s.init_z0, s.init_eps, b0.sa, b0.sb, (a.init_flags & PD_INIT_PURE_NOISE) ? 1 : 0, s.x_state, s.x_in,
-                                    s.per_step, B, Bf / B, C, 8, HW, stream, xt_seeded ? rng_dev : nullptr, s.init_eps)) {
-                pd_set_error("start latents launch failed");
-                return 1;
-            }
+            PD_LAUNCH(this, launch_init_latents(s.init_z0, s.init_eps, b0.sa, b0.sb, (a.init_flags & PD_INIT_PURE_NOISE) ? 1 : 0, s.x_state, s.x_in,
+                                                s.per_step, B, Bf / B, C, 8, HW, stream, xt_seeded ? rng_dev : nullptr, s.init_eps),
+                      "start latents launch failed");
         }
     } else if (xt_seeded) {
         // x_T drawn by the start kernel itself: no staging copy, no layout conversion
-        if (!arena.dry) {
-            ++launches;
-            if (launch_init_latents(nullptr, nullptr, 1.f, 0.f, 1, s.x_state, s.x_in, s.per_step, B, Bf / B, C, 8, HW, stream, rng_dev,
-                                    nullptr)) {
-                pd_set_error("start latents launch failed");
-                return 1;
-            }
-        }
+        PD_LAUNCH(this, launch_init_latents(nullptr, nullptr, 1.f, 0.f, 1, s.x_state, s.x_in, s.per_step, B, Bf / B, C, 8, HW, stream, rng_dev, nullptr),
+                  "start latents launch failed");
     } else {
         const float* xT = stage(a.x_T, (size_t)B * C * HW);
         if (!xT && !arena.dry) { pd_set_error("copy of x_T failed"); return 1; }
@@ -258,13 +249,9 @@ int pd_engine::session_setup(const pd_sample_args& a, const int64_t* t_rows, int
             Act k;
             k.p = kv[st->kv_slot].K; k.B = Bf; k.H = L; k.W = 1; k.C = st->C; k.dt = T;
             PD_TRY(gemm(st->kv2, ctx, k, {.VT = kv[st->kv_slot].VT, .vt_begin = st->C, .vt_ld = lpad}));
-            if (kv[st->kv_slot].P && !arena.dry) {   // the same K / V^T in the fused tail's fragment order
-                ++launches;
-                if (launch_st_tail_kv_pack(k.p, kv[st->kv_slot].VT, kv[st->kv_slot].P, Bf, L, lpad, stream)) {
-                    pd_set_error("context K/V packing for the fused transformer tail failed");
-                    return 1;
-                }
-            }
+            if (kv[st->kv_slot].P)   // the same K / V^T in the fused tail's fragment order
+                PD_LAUNCH(this, launch_st_tail_kv_pack(k.p, kv[st->kv_slot].VT, kv[st->kv_slot].P, Bf, L, lpad, stream),
+                          "context K/V packing for the fused transformer tail failed");
         }
     }
     // ---- guided_hint = input_hint_block(pair) + input_cond_block(query), cldm/cldm.py:306-308

@@ -59,20 +59,14 @@ void pd_engine::build_text() {
     ClipW& t = text;
     t.vocab = cfg.text_vocab; t.hidden = cfg.context_dim; t.ff = cfg.text_ff; t.heads = cfg.text_heads; t.positions = cfg.context_len;
     t.layers.resize(cfg.text_layers);
-    reg_group = GROUP_TEXT;
+    RegGroup rg(*this, GROUP_TEXT);
     build_clip("cond_stage_model.transformer.text_model.", t);
-    reg_group = GROUP_SAMPLER;
 }
 
 // token + position embeddings of ids [B, L] int32 (device) -> the residual stream x [B, L, 1, C]
 int pd_engine::clip_embed(const ClipW& t, const int* ids_dev, Act& x) {
-    if (arena.dry) return 0;
-    PD_TRY(check_arena());
-    ++launches;
-    if (launch_embed_tokens(ids_dev, t.tok.w, t.tok.Kpad, t.pos.w, t.pos.Kpad, T, x.p, x.dt, x.B, x.H, x.C, t.vocab, stream)) {
-        pd_set_error("CLIP embedding launch failed");
-        return 1;
-    }
+    PD_LAUNCH(this, launch_embed_tokens(ids_dev, t.tok.w, t.tok.Kpad, t.pos.w, t.pos.Kpad, T, x.p, x.dt, x.B, x.H, x.C, t.vocab, stream),
+              "CLIP embedding launch failed");
     return 0;
 }
 
@@ -133,57 +127,22 @@ int pd_engine::sd3_clip_forward(ClipW& t, const int* ids_dev, int B, int clip_sk
     PD_TRY(clip_embed(t, ids_dev, x));
     const int capture = n - 1 - clip_skip;   // blocks run before hidden_states[-(clip_skip + 2)] is complete
     PD_TRY(clip_blocks(t, 0, capture, x));
-    if (hid && !arena.dry) {
-        ++launches;
-        if (launch_joint_write(reinterpret_cast<const float*>(x.p), hid, B, L, C, width, hid_rows, hid_ld, c_off, stream)) {
-            pd_set_error("CLIP hidden-state write launch failed");
-            return 1;
-        }
-    }
+    if (hid)
+        PD_LAUNCH(this, launch_joint_write(reinterpret_cast<const float*>(x.p), hid, B, L, C, width, hid_rows, hid_ld, c_off, stream),
+                  "CLIP hidden-state write launch failed");
     if (pooled) {
         PD_TRY(clip_blocks(t, capture, n, x));
         // last_hidden_state[b, eos(b)] @ text_projection^T: LayerNorm is per row, so the EOS rows are gathered first
         Act rows = new_act(B, 1, 1, C, DT_F32), lnr = new_act(B, 1, 1, C, DT_F32);
-        if (!arena.dry) {
-            PD_TRY(check_arena());
-            ++launches;
-            if (launch_eos_gather(ids_dev, reinterpret_cast<const float*>(x.p), reinterpret_cast<float*>(rows.p), B, L, C, t.eos_token_id, stream)) {
-                pd_set_error("CLIP EOS gather launch failed");
-                return 1;
-            }
-        }
+        PD_LAUNCH(this, launch_eos_gather(ids_dev, reinterpret_cast<const float*>(x.p), reinterpret_cast<float*>(rows.p), B, L, C, t.eos_token_id, stream),
+                  "CLIP EOS gather launch failed");
         PD_TRY(layernorm(rows, lnr, t.fln_g, t.fln_b));
-        if (!arena.dry) {
-            for (int b0 = 0; b0 < B; b0 += 4) {   // launch_gemv streams the weights once per <= 4 rows
-                ++launches;
-                if (launch_gemv(reinterpret_cast<const float*>(lnr.p) + (size_t)b0 * C, C, t.proj.w, T, t.proj.Kpad, nullptr, pooled + (size_t)b0 * pooled_ld,
-                                pooled_ld, std::min(4, B - b0), t.proj_dim, C, 0, stream)) {
-                    pd_set_error("CLIP text_projection launch failed");
-                    return 1;
-                }
-            }
-        }
+        for (int b0 = 0; b0 < B; b0 += 4)   // launch_gemv streams the weights once per <= 4 rows
+            PD_LAUNCH(this, launch_gemv(reinterpret_cast<const float*>(lnr.p) + (size_t)b0 * C, C, t.proj.w, T, t.proj.Kpad, nullptr,
+                                        pooled + (size_t)b0 * pooled_ld, pooled_ld, std::min(4, B - b0), t.proj_dim, C, 0, stream),
+                      "CLIP text_projection launch failed");
     }
     arena.release(mk0);
-    return 0;
-}
-
-int pd_engine::upload_ids(const int32_t* ids, size_t n, int mem, int** dev) {
-    *dev = reinterpret_cast<int*>(arena.alloc(n * sizeof(int)));
-    if (arena.dry) return 0;
-    PD_TRY(check_arena());
-    if (hipMemcpyAsync(*dev, ids, n * sizeof(int), mem == PD_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream) != hipSuccess) {
-        pd_set_error("token upload failed");
-        return 1;
-    }
-    return 0;
-}
-
-int pd_engine::download(float* dst, const float* src, size_t n, int mem) {
-    if (hipMemcpyAsync(dst, src, n * sizeof(float), mem == PD_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream) != hipSuccess) {
-        pd_set_error("embedding read-back failed");
-        return 1;
-    }
     return 0;
 }
 
@@ -200,14 +159,10 @@ extern "C" int pd_text_encode_ex(pd_engine* e, const int32_t* ids, int32_t B, in
     PD_TRY(e->require_loaded(GROUP_TEXT, "text transformer"));
     HIP_OK(hipSetDevice(e->device));
     const size_t n_in = (size_t)B * e->text.positions, n_out = n_in * e->text.hidden;
-    return e->in_side_workspace("text", n_in * sizeof(int) + n_out * sizeof(float), [&] { return e->text_forward(nullptr, B, nullptr, 0); }, [&] {
-        int* din = nullptr;
-        PD_TRY(e->upload_ids(ids, n_in, mem, &din));
-        float* dout = reinterpret_cast<float*>(e->arena.alloc(n_out * sizeof(float)));
-        PD_TRY(e->text_forward(din, B, dout, clip_skip));
-        PD_TRY(e->download(out, dout, n_out, mem));
-        HIP_OK(hipStreamSynchronize(e->stream));
-        return 0;
+    return e->side_call("text", [&](SideCall& f) {
+        const int* din;
+        PD_TRY(f.src(&din, ids, n_in, mem));
+        return e->text_forward(din, B, f.dst(out, n_out, mem), clip_skip);
     });
 }
 

@@ -71,7 +71,7 @@ void pd_engine::build_vae() {
 void pd_engine::build_vae_decoder(VaeW& v, const std::string& P) {
     const VaeDesc& d = v.d;
     const bool dif = d.diffusers;
-    reg_group = (WeightGroup)d.group;
+    RegGroup rg(*this, d.group);
     const std::string D = P + "decoder.";
     const int nl = d.num_levels;
     const int top = d.ch * d.ch_mult[nl - 1];
@@ -109,7 +109,6 @@ void pd_engine::build_vae_decoder(VaeW& v, const std::string& P) {
     build_conv(D + "conv_out.", v.conv_out, d.ch, d.out_ch, 3, 1);
     if (d.quant) build_conv(P + "post_quant_conv.", v.post_quant, d.z, d.z, 1, 1);
     v.built = true;
-    reg_group = GROUP_SAMPLER;
 }
 
 // Encoder.__init__ (model.py:452-506) with double_z and attn_resolutions = [] (models/cldm_v15.yaml:64-85), then quant_conv =
@@ -123,7 +122,7 @@ void pd_engine::build_vae_encoder() {
 void pd_engine::build_vae_encoder(VaeEncW& v, const std::string& P) {
     const VaeDesc& d = v.d;
     const bool dif = d.diffusers;
-    reg_group = (WeightGroup)d.enc_group;
+    RegGroup rg(*this, d.enc_group);
     const std::string E = P + "encoder.";
     const int nl = d.num_levels, z2 = 2 * d.z;
     build_conv(E + "conv_in.", v.conv_in, d.out_ch, d.ch, 3, 1);
@@ -153,7 +152,6 @@ void pd_engine::build_vae_encoder(VaeEncW& v, const std::string& P) {
     build_conv(E + "conv_out.", v.conv_out, block_in, z2, 3, 1);
     if (d.quant) build_conv(P + "quant_conv.", v.quant, z2, z2, 1, 1);
     v.built = true;
-    reg_group = GROUP_SAMPLER;
 }
 
 // Which path the mid-block attention takes.  Measured on an MI355X at C = 512 (profiles/sd3_vae_bench.json): the flash kernel is SLOWER
@@ -300,26 +298,11 @@ int pd_engine::vae_decode_call(VaeW& v, int which, const float* latents, int B, 
     const size_t n_in = (size_t)B * v.d.z * h * w, n_out = (size_t)B * v.d.out_ch * H * W;
     // tiling / slicing (pd_vae_set_tiling): vae_decode_managed; with both off, vae_forward as ever
     const bool managed = vae_tiling[which].tiling || vae_tiling[which].slicing;
-    auto fwd = [&](const float* s, float* o) {
-        return managed ? vae_decode_managed(v, which, s, B, h, w, o, scale, shift) : vae_forward(v, s, B, h, w, o, scale, shift);
-    };
-    return in_side_workspace("VAE", (n_in + n_out) * sizeof(float), [&] { return fwd(nullptr, nullptr); }, [&] {
-        int r = 0;
-        float* din = reinterpret_cast<float*>(arena.alloc(n_in * sizeof(float)));
-        float* dout = reinterpret_cast<float*>(arena.alloc(n_out * sizeof(float)));
-        const float* src = latents;
-        if (mem != PD_MEM_DEVICE) {
-            if (hipMemcpyAsync(din, latents, n_in * sizeof(float), hipMemcpyHostToDevice, stream) != hipSuccess ||
-                hipStreamSynchronize(stream) != hipSuccess) { pd_set_error("latent upload failed"); r = 1; }
-            src = din;
-        }
-        if (!r) r = fwd(src, dout);
-        if (!r) {
-            if (hipMemcpyAsync(images_out, dout, n_out * sizeof(float),
-                               mem == PD_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream) != hipSuccess ||
-                hipStreamSynchronize(stream) != hipSuccess) { pd_set_error("image read-back failed"); r = 1; }
-        }
-        return r;
+    return side_call("VAE", [&](SideCall& f) {
+        const float* src;
+        PD_TRY(f.src(&src, latents, n_in, mem));
+        float* dout = f.dst(images_out, n_out, mem);
+        return managed ? vae_decode_managed(v, which, src, B, h, w, dout, scale, shift) : vae_forward(v, src, B, h, w, dout, scale, shift);
     });
 }
 
@@ -343,22 +326,12 @@ int pd_engine::vae_encoder_forward(VaeEncW& v, const float* images_dev, int B, i
     const VaeDesc& d = v.d;
     const int cin = d.out_ch, z = d.z;
     Act x = new_act(B, H, W, v.conv_in.m.cin_pad, T);
-    if (!arena.dry) {
-        PD_TRY(check_arena());
-        ++launches;
-        if (launch_nchw_to_nhwc(images_dev, x.p, T, B, cin, H, W, x.C, stream)) { pd_set_error("image upload launch failed"); return 1; }
-    }
+    PD_LAUNCH(this, launch_nchw_to_nhwc(images_dev, x.p, T, B, cin, H, W, x.C, stream), "image upload launch failed");
     const int dn = 1 << (d.num_levels - 1);
     Act mom = new_act(B, H / dn, W / dn, d.quant ? v.quant.m.N : v.conv_out.m.N, DT_F32);
     PD_TRY(vae_encode_layers(v, x, mom));
-    if (!arena.dry) {
-        PD_TRY(check_arena());
-        ++launches;
-        if (launch_vae_posterior(mom.p, DT_F32, mom.C, noise_dev, out_dev, B, z, mom.H * mom.W, what, scale, stream, rng_dev, shift)) {
-            pd_set_error("posterior launch failed");
-            return 1;
-        }
-    }
+    PD_LAUNCH(this, launch_vae_posterior(mom.p, DT_F32, mom.C, noise_dev, out_dev, B, z, mom.H * mom.W, what, scale, stream, rng_dev, shift),
+              "posterior launch failed");
     return 0;
 }
 
@@ -404,30 +377,13 @@ int pd_engine::vae_encode_call(VaeEncW& v, int which, const float* images, int B
     // (noise NULL with PD_VAE_SAMPLE: the posterior kernel draws at (PD_RNG_VAE, draw 0) itself)
     const size_t n_noise = (what == PD_VAE_SAMPLE && noise) ? n_lat : 0, n_out = what == PD_VAE_MOMENTS ? 2 * n_lat : n_lat;
     const bool managed = vae_tiling[which].tiling || vae_tiling[which].slicing;
-    auto fwd = [&](const float* s, const float* n, float* o) {
-        return managed ? vae_encode_managed(v, which, s, B, H, W, what, n, o, scale, shift) : vae_encoder_forward(v, s, B, H, W, what, n, o, scale, shift);
-    };
-    return in_side_workspace("VAE", (n_in + n_noise + n_out) * sizeof(float), [&] { return fwd(nullptr, nullptr, nullptr); }, [&] {
-        int r = 0;
-        float* din = reinterpret_cast<float*>(arena.alloc(n_in * sizeof(float)));
-        float* dnoise = n_noise ? reinterpret_cast<float*>(arena.alloc(n_noise * sizeof(float))) : nullptr;
-        float* dout = reinterpret_cast<float*>(arena.alloc(n_out * sizeof(float)));
-        const float* src = images;
-        const float* nz = noise;
-        if (mem != PD_MEM_DEVICE) {
-            if (hipMemcpyAsync(din, images, n_in * sizeof(float), hipMemcpyHostToDevice, stream) != hipSuccess ||
-                (dnoise && hipMemcpyAsync(dnoise, noise, n_noise * sizeof(float), hipMemcpyHostToDevice, stream) != hipSuccess) ||
-                hipStreamSynchronize(stream) != hipSuccess) { pd_set_error("image upload failed"); r = 1; }
-            src = din;
-            nz = dnoise;
-        }
-        if (!r) r = fwd(src, what == PD_VAE_SAMPLE ? nz : nullptr, dout);
-        if (!r) {
-            if (hipMemcpyAsync(out, dout, n_out * sizeof(float), mem == PD_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
-                               stream) != hipSuccess ||
-                hipStreamSynchronize(stream) != hipSuccess) { pd_set_error("latent read-back failed"); r = 1; }
-        }
-        return r;
+    return side_call("VAE", [&](SideCall& f) {
+        const float *src, *nz = nullptr;
+        PD_TRY(f.src(&src, images, n_in, mem));
+        if (n_noise) PD_TRY(f.src(&nz, noise, n_noise, mem));
+        float* dout = f.dst(out, n_out, mem);
+        return managed ? vae_encode_managed(v, which, src, B, H, W, what, nz, dout, scale, shift)
+                       : vae_encoder_forward(v, src, B, H, W, what, nz, dout, scale, shift);
     });
 }
 

@@ -217,15 +217,12 @@ int pd_engine::vae_tile_setup(const VaeTilePlan& p, int B, int cpad, VaeTileRun&
 }
 
 int pd_engine::vae_tile_blend(const VaeTilePlan& p, const VaeTileRun& run, int B, int C, int cpad, bool nchw, float* out) {
-    if (arena.dry) return 0;
-    PD_TRY(check_arena());
     const pd_vae_tile& last = p.tiles.back();
     VaeBlendParams bp{};
     bp.tiles = run.res[0]; bp.tile_off = run.tile_off; bp.rows = run.rows; bp.cols = run.cols; bp.wtab = run.wtab; bp.out = out;
     bp.B = B; bp.C = C; bp.Cpad = cpad; bp.H = last.oy + last.oh; bp.W = last.ox + last.ow;
     bp.nrow = p.nrow; bp.ncol = p.ncol; bp.limit = p.limit; bp.nchw = nchw ? 1 : 0;
-    ++launches;
-    if (launch_vae_tile_blend(bp, stream)) { pd_set_error("vae tiling: blend launch failed"); return 1; }
+    PD_LAUNCH(this, launch_vae_tile_blend(bp, stream), "vae tiling: blend launch failed");
     return 0;
 }
 
@@ -309,11 +306,7 @@ int pd_engine::vae_encode_managed(VaeEncW& v, int which, const float* src, int B
         const size_t mk = arena.mark();
         if (!p.tiled) {
             Act x = new_act(Bs, H, W, cin_pad, T);
-            if (!arena.dry) {
-                PD_TRY(check_arena());
-                ++launches;
-                if (launch_nchw_to_nhwc(in, x.p, T, Bs, d.out_ch, H, W, x.C, stream)) { pd_set_error("image upload launch failed"); return 1; }
-            }
+            PD_LAUNCH(this, launch_nchw_to_nhwc(in, x.p, T, Bs, d.out_ch, H, W, x.C, stream), "image upload launch failed");
             PD_TRY(vae_encode_layers(v, x, ms));
         } else {
             vae_tile_odd_flash = true;
@@ -345,14 +338,7 @@ int pd_engine::vae_encode_managed(VaeEncW& v, int which, const float* src, int B
         }
         arena.release(mk);
     }
-    if (!arena.dry) {
-        PD_TRY(check_arena());
-        ++launches;
-        if (launch_vae_posterior(mom.p, DT_F32, mom.C, noise, dout, B, d.z, h * w, what, scale, stream, rng_dev, shift)) {
-            pd_set_error("posterior launch failed");
-            return 1;
-        }
-    }
+    PD_LAUNCH(this, launch_vae_posterior(mom.p, DT_F32, mom.C, noise, dout, B, d.z, h * w, what, scale, stream, rng_dev, shift), "posterior launch failed");
     return 0;
 }
 
@@ -366,7 +352,6 @@ extern "C" int pd_op_vae_tile_blend(pd_engine* e, const float* tiles, const pd_v
     p.tiled = true; p.nrow = rows; p.ncol = cols; p.nclass = rows * cols;
     p.tiles.assign(plan, plan + (size_t)rows * cols);
     p.limit = plan[0].oh > plan[0].ow ? plan[0].oh : plan[0].ow;
-    size_t total = 0;
     for (int ti = 0; ti < rows; ++ti)
         for (int tj = 0; tj < cols; ++tj) {
             const pd_vae_tile& t = p.tiles[(size_t)ti * cols + tj];
@@ -382,25 +367,19 @@ extern "C" int pd_op_vae_tile_blend(pd_engine* e, const float* tiles, const pd_v
             if (ok && tj == 0) ok = t.eh == 0;
             if (!ok) { pd_set_error("pd_op_vae_tile_blend: tile (%d, %d) of the plan is inconsistent", ti, tj); return 1; }
             p.members.push_back({ti * cols + tj});
-            total += (size_t)B * t.th * t.tw * Cpad;
         }
     const pd_vae_tile& last = p.tiles.back();
     const int H = last.oy + last.oh, W = last.ox + last.ow;
     const size_t n_out = (size_t)B * (nchw ? C : Cpad) * H * W;
-    return e->in_side_workspace("VAE", (total + n_out) * sizeof(float) + (1u << 20), [&] { return 0; }, [&] {
+    return e->side_call("VAE", [&](SideCall& f) {
         VaeTileRun run;
         PD_TRY(e->vae_tile_setup(p, B, Cpad, run));   // one class per tile, in plan order: the caller's layout
-        float* dout = reinterpret_cast<float*>(e->arena.alloc(n_out * sizeof(float)));
-        PD_TRY(e->check_arena());
         const float* src = tiles;
         for (int c = 0; c < p.nclass; ++c) {
             const size_t n = (size_t)B * p.tiles[c].th * p.tiles[c].tw * Cpad;
-            HIP_OK(hipMemcpyAsync(run.res[c], src, n * sizeof(float), hipMemcpyHostToDevice, e->stream));
+            PD_TRY(f.upload(run.res[c], src, n * sizeof(float)));
             src += n;
         }
-        PD_TRY(e->vae_tile_blend(p, run, B, C, Cpad, nchw != 0, dout));
-        HIP_OK(hipMemcpyAsync(out, dout, n_out * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-        HIP_OK(hipStreamSynchronize(e->stream));
-        return 0;
+        return e->vae_tile_blend(p, run, B, C, Cpad, nchw != 0, f.dst(out, n_out, PD_MEM_HOST));
     });
 }

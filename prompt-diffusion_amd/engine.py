@@ -650,6 +650,22 @@ class _Buf:
             a = np.ascontiguousarray(x, dtype=dtype)
             self.owner, self.ptr, self.mem = a, a.ctypes.data, PD_MEM_HOST
 
+    @property
+    def device(self):
+        """The torch device of a CUDA buffer, None for host memory (and for no buffer)."""
+        return self.owner.device if self.mem == PD_MEM_DEVICE else None
+
+
+def _new_out(shape, dtype=np.float32, device=None):
+    """(output, pointer) of an uninitialised result: a torch tensor on `device` -- what a _Buf's .device gives for a CUDA caller --
+    or, with device None, a NumPy array.  dtype: a NumPy type, or a torch dtype NumPy has no name for."""
+    if device is None:
+        out = np.empty(shape, dtype)
+        return out, out.ctypes.data
+    import torch
+    out = torch.empty(shape, dtype=dtype if isinstance(dtype, torch.dtype) else getattr(torch, np.dtype(dtype).name), device=device)
+    return out, out.data_ptr()
+
 
 class Engine:
     """One engine <-> one GPU <-> one HIP stream (SURVEY.md §8b threading row)."""
@@ -885,13 +901,8 @@ class Engine:
         st = RNG_STREAMS[stream] if isinstance(stream, str) else int(stream)
         shape = tuple(int(v) for v in shape)
         B, per = shape[0], int(np.prod(shape[1:], dtype=np.int64))
-        if device is not None:
-            import torch
-            out = torch.empty(shape, dtype=torch.float32, device=device)
-            self._check(self.lib.pd_randn(self._h, st, int(draw), B, per, PD_MEM_DEVICE, out.data_ptr()))
-        else:
-            out = np.empty(shape, np.float32)
-            self._check(self.lib.pd_randn(self._h, st, int(draw), B, per, PD_MEM_HOST, out.ctypes.data))
+        out, op = _new_out(shape, device=device)
+        self._check(self.lib.pd_randn(self._h, st, int(draw), B, per, PD_MEM_HOST if device is None else PD_MEM_DEVICE, op))
         return out
 
     def init_random_weights(self, seed: int = 1234) -> None:
@@ -907,13 +918,7 @@ class Engine:
         """decode_first_stage (ddpm.py:820-828): latents [B,4,h,w] -> images [B,3,8h,8w] in about [-1, 1]."""
         b = _Buf(latents)
         B, _, h, w = b.owner.shape
-        if b.mem == PD_MEM_DEVICE:
-            import torch
-            out = torch.empty((B, self.cfg.vae_out_ch, 8 * h, 8 * w), dtype=torch.float32, device=b.owner.device)
-            op = out.data_ptr()
-        else:
-            out = np.empty((B, self.cfg.vae_out_ch, 8 * h, 8 * w), np.float32)
-            op = out.ctypes.data
+        out, op = _new_out((B, self.cfg.vae_out_ch, 8 * h, 8 * w), device=b.device)
         self._order_after_torch(b.mem)
         self._check(self.lib.pd_vae_decode(self._h, b.ptr, B, h, w, b.mem, op))
         return out
@@ -992,14 +997,7 @@ class Engine:
             raise PdError("images and noise must live in the same memory space")
         B, _, H, W = b.owner.shape
         z = self.cfg.in_channels
-        shape = (B, 2 * z if what == PD_VAE_MOMENTS else z, H // 8, W // 8)
-        if b.mem == PD_MEM_DEVICE:
-            import torch
-            out = torch.empty(shape, dtype=torch.float32, device=b.owner.device)
-            op = out.data_ptr()
-        else:
-            out = np.empty(shape, np.float32)
-            op = out.ctypes.data
+        out, op = _new_out((B, 2 * z if what == PD_VAE_MOMENTS else z, H // 8, W // 8), device=b.device)
         if nb.owner is not None and tuple(nb.owner.shape) != (B, z, H // 8, W // 8):
             raise ValueError(f"noise must be [{B}, {z}, {H // 8}, {W // 8}]")
         self._order_after_torch(b.mem)
@@ -1033,14 +1031,7 @@ class Engine:
         if b.owner.ndim != 4 or b.owner.shape[1] != 3:
             raise ValueError(f"images must be [B, 3, H, W], got {tuple(b.owner.shape)}")
         B, _, H, W = b.owner.shape
-        shape = (B, 5 if what == "sides" else 1, H, W)
-        if b.mem == PD_MEM_DEVICE:
-            import torch
-            out = torch.empty(shape, dtype=torch.float32, device=b.owner.device)
-            op = out.data_ptr()
-        else:
-            out = np.empty(shape, np.float32)
-            op = out.ctypes.data
+        out, op = _new_out((B, 5 if what == "sides" else 1, H, W), device=b.device)
         self._order_after_torch(b.mem)
         self._check(self.lib.pd_hed_detect(self._h, b.ptr, B, H, W, b.mem, HED_OUTPUTS[what], op))
         return out
@@ -1138,16 +1129,11 @@ class Engine:
                 raise ValueError(f"image_size {S} is no multiple of patch {patch}")
             shape, ndt = (B * (S // int(patch)) ** 2, clip_patch_width(patch)), (np.uint16 if two_byte else np.float32)
         to_host = host or (smem == PD_MEM_HOST and not _is_torch(images))
-        if to_host:
-            out = np.empty(shape, ndt)
-            dp, dmem = out.ctypes.data, PD_MEM_HOST
-        else:
+        dmem = PD_MEM_HOST if to_host else PD_MEM_DEVICE
+        if not to_host and ndt == np.uint16:   # the operand type itself on the device
             import torch
-            tdt = {np.float32: torch.float32, np.uint8: torch.uint8}.get(ndt)
-            if tdt is None:
-                tdt = torch.float16 if self.precision == PD_PREC_F16 else torch.bfloat16
-            out = torch.empty(shape, dtype=tdt, device=self._torch_device())
-            dp, dmem = out.data_ptr(), PD_MEM_DEVICE
+            ndt = torch.float16 if self.precision == PD_PREC_F16 else torch.bfloat16
+        out, dp = _new_out(shape, ndt, None if to_host else self._torch_device())
         a = pd_clip_preprocess_args()
         a.src, a.B, a.H, a.W, a.mem_src = sp, B, H, W, smem
         a.image_size, a.patch, a.out_mode, a.mem_dst, a.dst = S, int(patch), CLIP_PREPROCESS_OUTPUTS[what], dmem, dp
@@ -1184,14 +1170,9 @@ class Engine:
             B, H, W = int(owner.shape[0]), int(owner.shape[2]), int(owner.shape[3])
             dev = owner.device if mem == PD_MEM_DEVICE else None
         shapes = {"embeds": (B, cfg.proj_dim), "pooled": (B, cfg.hidden), "hidden": (B, cfg.patches + 1, cfg.hidden)}
-        outs = {}
-        for n in names:
-            if mem == PD_MEM_DEVICE:
-                import torch
-                outs[n] = torch.empty(shapes[n], dtype=torch.float32, device=dev)
-            else:
-                outs[n] = np.empty(shapes[n], np.float32)
-        ptr_of = lambda n: None if n not in outs else (outs[n].data_ptr() if mem == PD_MEM_DEVICE else outs[n].ctypes.data)
+        made = {n: _new_out(shapes[n], device=dev) for n in names}
+        outs = {n: o for n, (o, _) in made.items()}
+        ptr_of = lambda n: made[n][1] if n in made else None
         a = pd_clip_vision_args()
         pre = prefix.encode()
         a.prefix, a.input, a.input_kind = pre, ptr, PD_CLIP_IN_U8 if is_u8 else PD_CLIP_IN_PIXEL_VALUES
@@ -1214,15 +1195,8 @@ class Engine:
         if b.owner.ndim != 2:
             raise ValueError(f"embeds must be [B, D], got {tuple(b.owner.shape)}")
         B = int(b.owner.shape[0])
-        if b.mem == PD_MEM_DEVICE:
-            import torch
-            flags = torch.empty((B,), dtype=torch.int32, device=b.owner.device)
-            scores = torch.empty((B, PD_SAFETY_SPECIAL + PD_SAFETY_CONCEPTS), dtype=torch.float32, device=b.owner.device) if return_scores else None
-            fp, sp = flags.data_ptr(), scores.data_ptr() if return_scores else None
-        else:
-            flags = np.empty((B,), np.int32)
-            scores = np.empty((B, PD_SAFETY_SPECIAL + PD_SAFETY_CONCEPTS), np.float32) if return_scores else None
-            fp, sp = flags.ctypes.data, scores.ctypes.data if return_scores else None
+        flags, fp = _new_out((B,), np.int32, b.device)
+        scores, sp = _new_out((B, PD_SAFETY_SPECIAL + PD_SAFETY_CONCEPTS), device=b.device) if return_scores else (None, None)
         self._order_after_torch(b.mem)
         self._check(self.lib.pd_safety_check(self._h, b.ptr, B, b.mem, fp, sp))
         flags = _to_host(flags).astype(bool)
@@ -1301,13 +1275,7 @@ class Engine:
             shape, dt = (B * MLSD_TOPK * 4 + B,), np.int32
         else:
             shape, dt = (B, H, W), np.uint8
-        if on_dev:
-            import torch
-            res = torch.empty(shape, dtype={np.float32: torch.float32, np.int32: torch.int32, np.uint8: torch.uint8}[dt], device=owner.device)
-            a.out = res.data_ptr()
-        else:
-            res = np.empty(shape, dt)
-            a.out = res.ctypes.data
+        res, a.out = _new_out(shape, dt, owner.device if on_dev else None)
         self._order_after_torch(PD_MEM_DEVICE if on_dev or (out is not None and a.mem_f == PD_MEM_DEVICE) else PD_MEM_HOST)
         self._check(self.lib.pd_mlsd_detect_ex(self._h, C.byref(a)))
         del owner
@@ -1368,13 +1336,9 @@ class Engine:
                     raise ValueError("out must be a C-contiguous float32 array")
                 dp, dmem = out.ctypes.data, PD_MEM_HOST
             channels = int(out.shape[1])
-        elif host:
-            out = np.empty((B, channels, H, W), np.float32)
-            dp, dmem = out.ctypes.data, PD_MEM_HOST
         else:
-            import torch
-            out = torch.empty((B, channels, H, W), dtype=torch.float32, device=self._torch_device())
-            dp, dmem = out.data_ptr(), PD_MEM_DEVICE
+            dmem = PD_MEM_HOST if host else PD_MEM_DEVICE
+            out, dp = _new_out((B, channels, H, W), device=None if host else self._torch_device())
         a = pd_image_load_args()
         a.src, a.Bs, a.Hs, a.Ws, a.mem_src = sp, Bs, Hs, Ws, smem
         a.dst, a.B, a.C, a.H, a.W, a.c_off, a.mem_dst = dp, B, channels, H, W, int(c_off), dmem
@@ -1393,13 +1357,8 @@ class Engine:
         if b.owner.ndim != 4 or b.owner.shape[1] not in (1, 3):
             raise ValueError(f"x must be [B, 1 or 3, H, W], got {tuple(b.owner.shape)}")
         B, Cc, H, W = (int(v) for v in b.owner.shape)
-        if host:
-            out = np.empty((B, H, W, Cc), np.uint8)
-            dp, dmem = out.ctypes.data, PD_MEM_HOST
-        else:
-            import torch
-            out = torch.empty((B, H, W, Cc), dtype=torch.uint8, device=b.owner.device if b.mem == PD_MEM_DEVICE else self._torch_device())
-            dp, dmem = out.data_ptr(), PD_MEM_DEVICE
+        dmem = PD_MEM_HOST if host else PD_MEM_DEVICE
+        out, dp = _new_out((B, H, W, Cc), np.uint8, None if host else (b.device or self._torch_device()))
         self._order_after_torch(PD_MEM_DEVICE if PD_MEM_DEVICE in (b.mem, dmem) else PD_MEM_HOST)
         self._check(self.lib.pd_image_store(self._h, b.ptr, B, Cc, H, W, b.mem, float(mul), float(add), IMAGE_ROUNDINGS[rounding], dp, dmem))
         return out
@@ -1436,14 +1395,10 @@ class Engine:
                 a.dst_f, a.mem_f = out.ctypes.data, PD_MEM_HOST
             a.Cf, a.c_off, a.mul, a.add = int(out.shape[1]), int(c_off), float(mul), float(add)
             any_dev = any_dev or a.mem_f == PD_MEM_DEVICE
-        if host or not _is_torch(images):
-            edges = np.empty((B, H, W), np.uint8)
-            a.dst_u8, a.mem_u8 = edges.ctypes.data, PD_MEM_HOST
-        else:
-            import torch
-            edges = torch.empty((B, H, W), dtype=torch.uint8, device=owner.device if smem == PD_MEM_DEVICE else self._torch_device())
-            a.dst_u8, a.mem_u8 = edges.data_ptr(), PD_MEM_DEVICE
-            any_dev = True
+        to_host = host or not _is_torch(images)
+        edges, a.dst_u8 = _new_out((B, H, W), np.uint8, None if to_host else (owner.device if smem == PD_MEM_DEVICE else self._torch_device()))
+        a.mem_u8 = PD_MEM_HOST if to_host else PD_MEM_DEVICE
+        any_dev = any_dev or not to_host
         self._order_after_torch(PD_MEM_DEVICE if any_dev else PD_MEM_HOST)
         self._check(self.lib.pd_canny(self._h, C.byref(a)))
         del owner
@@ -1456,13 +1411,7 @@ class Engine:
         owner, sp, smem, sh = self._u8_source(states)
         if len(sh) != 3:
             raise ValueError(f"states must be uint8 [B, H, W], got {tuple(sh)}")
-        if _is_torch(states) and smem == PD_MEM_DEVICE:
-            import torch
-            out = torch.empty(tuple(sh), dtype=torch.uint8, device=owner.device)
-            op = out.data_ptr()
-        else:
-            out = np.empty(tuple(sh), np.uint8)
-            op = out.ctypes.data
+        out, op = _new_out(tuple(sh), np.uint8, owner.device if smem == PD_MEM_DEVICE else None)
         self._order_after_torch(smem)
         self._check(self.lib.pd_op_canny_hysteresis(self._h, sp, int(sh[0]), int(sh[1]), int(sh[2]), smem, op))
         del owner
@@ -1480,16 +1429,16 @@ class Engine:
             import torch
             ids = input_ids.to(torch.int32).contiguous()
             if ids.is_cuda:
-                out = torch.empty(tuple(ids.shape) + (self.cfg.context_dim,), dtype=torch.float32, device=ids.device)
+                out, op = _new_out(tuple(ids.shape) + (self.cfg.context_dim,), device=ids.device)
                 self._order_after_torch(PD_MEM_DEVICE)
-                self._check(self.lib.pd_text_encode_ex(self._h, ids.data_ptr(), ids.shape[0], PD_MEM_DEVICE, clip_skip, out.data_ptr()))
+                self._check(self.lib.pd_text_encode_ex(self._h, ids.data_ptr(), ids.shape[0], PD_MEM_DEVICE, clip_skip, op))
                 return out
             input_ids = ids.numpy()
         ids = np.ascontiguousarray(input_ids, np.int32)
         if ids.ndim != 2 or ids.shape[1] != self.cfg.context_len:
             raise ValueError(f"input_ids must be [B, {self.cfg.context_len}]")
-        out = np.empty(ids.shape + (self.cfg.context_dim,), np.float32)
-        self._check(self.lib.pd_text_encode_ex(self._h, ids.ctypes.data, ids.shape[0], PD_MEM_HOST, clip_skip, out.ctypes.data))
+        out, op = _new_out(ids.shape + (self.cfg.context_dim,))
+        self._check(self.lib.pd_text_encode_ex(self._h, ids.ctypes.data, ids.shape[0], PD_MEM_HOST, clip_skip, op))
         return out
 
     # ------------------------------------------------------------------ operator boundary
@@ -1518,16 +1467,8 @@ class Engine:
             raise PdError("t must live in the same memory space as x")
         sc = None if scales is None else np.ascontiguousarray(scales, dtype=np.float32)
         shapes = self.control_shapes(h, w)
-        if mem == PD_MEM_DEVICE:
-            import torch
-            eps = torch.empty((Bf, self.cfg.out_channels, h, w), dtype=torch.float32, device=xb.owner.device)
-            res = torch.empty(sum(Bf * c * a * b for c, a, b in shapes), dtype=torch.float32,
-                              device=xb.owner.device) if return_control else None
-            ep, rp = eps.data_ptr(), (res.data_ptr() if res is not None else None)
-        else:
-            eps = np.empty((Bf, self.cfg.out_channels, h, w), np.float32)
-            res = np.empty(sum(Bf * c * a * b for c, a, b in shapes), np.float32) if return_control else None
-            ep, rp = eps.ctypes.data, (res.ctypes.data if res is not None else None)
+        eps, ep = _new_out((Bf, self.cfg.out_channels, h, w), device=xb.device)
+        res, rp = _new_out(sum(Bf * c * a * b for c, a, b in shapes), device=xb.device) if return_control else (None, None)
         self._order_after_torch(mem)
         self._check(self.lib.pd_eps_ctx(self._h, xb.ptr, tb.ptr, cb.ptr, L, pb.ptr, qb.ptr,
                                         None if sc is None else sc.ctypes.data, Bf, h, w, mem, ep, rp))
@@ -1640,16 +1581,9 @@ class Engine:
     def _sample_out(self, a, keep, B, h, w, S, return_intermediates):
         """out [B,4,h,w] and optionally inter [S+1,B,4,h,w] in the memory space of the inputs, and their addresses."""
         Cc = self.cfg.in_channels
-        if a.mem == PD_MEM_DEVICE:
-            import torch
-            dev = keep[0].owner.device
-            out = torch.empty((B, Cc, h, w), dtype=torch.float32, device=dev)
-            inter = torch.empty((S + 1, B, Cc, h, w), dtype=torch.float32, device=dev) if return_intermediates else None
-            op, ip = out.data_ptr(), (inter.data_ptr() if inter is not None else None)
-        else:
-            out = np.empty((B, Cc, h, w), np.float32)
-            inter = np.empty((S + 1, B, Cc, h, w), np.float32) if return_intermediates else None
-            op, ip = out.ctypes.data, (inter.ctypes.data if inter is not None else None)
+        dev = keep[0].owner.device if a.mem == PD_MEM_DEVICE else None
+        out, op = _new_out((B, Cc, h, w), device=dev)
+        inter, ip = _new_out((S + 1, B, Cc, h, w), device=dev) if return_intermediates else (None, None)
         return out, inter, op, ip
 
     def ddim_sample(self, *, return_intermediates: bool = False, **kw):
@@ -1740,13 +1674,8 @@ class Engine:
 
     def sample_get(self, what: int = PD_GET_LATENTS):
         (B, h, w), mem, like = self._ses
-        if mem == PD_MEM_DEVICE:
-            import torch
-            out = torch.empty((B, self.cfg.in_channels, h, w), dtype=torch.float32, device=like.device)
-            self._check(self.lib.pd_sample_get(self._h, what, mem, out.data_ptr()))
-        else:
-            out = np.empty((B, self.cfg.in_channels, h, w), np.float32)
-            self._check(self.lib.pd_sample_get(self._h, what, mem, out.ctypes.data))
+        out, op = _new_out((B, self.cfg.in_channels, h, w), device=like.device if mem == PD_MEM_DEVICE else None)
+        self._check(self.lib.pd_sample_get(self._h, what, mem, op))
         return out
 
     def sample_set_latents(self, latents) -> None:
@@ -1796,13 +1725,8 @@ class Engine:
         self._order_after_torch(b.mem)
         shape = (world * b.owner.shape[0],) + tuple(b.owner.shape[1:])
         count = int(np.prod(b.owner.shape))
-        if b.mem == PD_MEM_DEVICE:
-            import torch
-            out = torch.empty(shape, dtype=torch.float32, device=b.owner.device)
-            self._check(self.lib.pd_comm_all_gather(self._h, b.ptr, out.data_ptr(), count, b.mem))
-        else:
-            out = np.empty(shape, np.float32)
-            self._check(self.lib.pd_comm_all_gather(self._h, b.ptr, out.ctypes.data, count, b.mem))
+        out, op = _new_out(shape, device=b.device)
+        self._check(self.lib.pd_comm_all_gather(self._h, b.ptr, op, count, b.mem))
         return out
 
     def comm_destroy(self) -> None:
