@@ -518,6 +518,49 @@ int pd_safety_weights_missing(pd_engine* e);   /* 0 when not configured */
 int pd_safety_check(pd_engine* e, const float* embeds, int32_t B, int32_t mem, int32_t* flags, float* scores);
 int pd_safety_blank(pd_engine* e, float* images, int32_t B, int64_t per_image, const int32_t* flags, int32_t mem_flags, float value);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * IP-Adapter image prompts (the reference pipeline's ip_adapter_image / ip_adapter_image_embeds; diffusers' IPAdapterAttnProcessor with
+ * the linear ImageProjection: ip-adapter_sd15, ip-adapter_sd15_light).  Opt-in engine state like pd_set_freeu: an engine that never
+ * configures an adapter, has no image set, or has every scale at 0 makes exactly the launches it makes without this section.
+ *
+ * pd_ip_adapter_configure registers, in a registry group of its own and under the flattened checkpoint names,
+ *   image_proj.proj.{weight [T D, E], bias [T D]}, image_proj.norm.{weight, bias} [D]           (D = pd_config.context_dim)
+ *   ip_adapter.{2 j + 1}.to_k_ip.weight, ip_adapter.{2 j + 1}.to_v_ip.weight   [C_j, D] each, no bias
+ * for the UNet's cross-attention blocks j in diffusers' processor order: those of the input blocks, then those of the output blocks,
+ * then the middle block (16 blocks, ids 1 .. 31, for the SD1.5 topology).  The ControlNet carries no adapter.  They load through
+ * pd_load_weights.  1 <= num_tokens <= 64; embed_dim and context_dim multiples of 8; every block's head dim one of 8, 16, 32, 40, 80, 160.
+ * One adapter per engine; configuring again does nothing.
+ *
+ * pd_ip_adapter_set_image: cond [Bi, E] fp32 image embeddings in `mem`, uncond [Bi, E] or NULL (zeros, as the reference's encode_image
+ * returns for the unconditional half -- their projection is LayerNorm(bias), not zero, and runs through the same code).  Right then, once:
+ *   tok = LayerNorm_D(reshape(proj.weight e + proj.bias, [T, D]), eps 1e-5);  K_ip,j = tok to_k_ip_j^T,  V_ip,j = tok to_v_ip_j^T
+ * for both halves and every block, into engine-owned buffers in the compute type.  pd_ip_adapter_clear_image drops the state (the buffers stay
+ * allocated).  Setting an image is refused while a sampling session is open; clearing is not, so that a caller can always leave.  A sampling call of batch B needs Bi == B or Bi == 1 (one image for every sample).
+ *
+ * pd_ip_adapter_set_scale: n = 1 (every block) or one scale per block; all 1 after configure.  The adapter is active when an image is
+ * set and at least one scale is non-zero.  Then every UNet evaluation of the engine (pd_ddim_sample, pd_unipc_sample, pd_lms_sample,
+ * pd_sample_step, pd_eps, pd_sample_eps_at, captured graphs) computes in every block with s_j != 0
+ *   attn2(x) = to_out(softmax(q k^T / sqrt(dh)) v + s_j softmax(q K_ip,j^T / sqrt(dh)) V_ip,j)
+ * with the block's own q and heads and a softmax of its own over the T image keys: one launch per block and guidance half after the text
+ * cross-attention, in fp32 with one rounding to the compute type (ip_attention.hip).  With use_cfg the unconditional half of the batch
+ * reads the unconditional buffers; without it only the conditional ones are used.  A UNet block with a term runs its per-layer path
+ * (the fused 320-channel tail cannot take the term); the ControlNet is untouched.  Every setter drops the captured graphs.  Stat
+ * "ip_launches" counts the term's launches. */
+typedef struct pd_ip_adapter_config {
+    int32_t num_tokens;       /* T */
+    int32_t embed_dim;        /* E */
+    int32_t reserved[6];      /* zero */
+} pd_ip_adapter_config;
+int pd_ip_adapter_configure(pd_engine* e, const pd_ip_adapter_config* cfg);
+int pd_ip_adapter_weights_missing(pd_engine* e);   /* 0 when not configured */
+int pd_ip_adapter_set_scale(pd_engine* e, const float* scales, int32_t n);
+int pd_ip_adapter_get_scale(pd_engine* e, float* scales, int32_t n);   /* n = the number of blocks */
+int pd_ip_adapter_set_image(pd_engine* e, const float* cond, const float* uncond, int32_t Bi, int32_t mem);
+int pd_ip_adapter_clear_image(pd_engine* e);
+/* The term's kernel alone on random data in the compute type (one key set for every sample, heads = pd_config.num_heads): ms per launch
+ * over `iters` back-to-back launches, and ms per device-to-device copy of the 3 B N C elements the kernel moves, timed the same way. */
+int pd_bench_ip_attention(pd_engine* e, int32_t B, int32_t N, int32_t C, int32_t T, int32_t iters, float* ms_kernel, float* ms_copy);
+
 /* Canny edge detector: the annotator of the reference's `canny` task (annotator/canny/__init__.py: cv2.Canny(img, low, high), called
  * with 100 and 200).  It has no weights and every step is integer arithmetic, so the result is pinned byte for byte -- to a
  * restatement of OpenCV's portable C++ path (canny.cpp, aperture 3, L2gradient = false), which tests/canny_ref.py states in NumPy:

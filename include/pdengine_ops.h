@@ -19,6 +19,8 @@
  *   pd_op_vae_downsample  the KL-VAE encoder's Downsample (asymmetric pad)          ldm/modules/diffusionmodules/model.py:68-88
  *   pd_op_canny_hysteresis  the flood of cv2.Canny's hysteresis on a given state map  annotator/canny/__init__.py
  *   pd_op_sd3_update  the update kernel of the SD3 img2img / inpainting / seeded loops (start state, CFG + Euler, blend)
+ *   pd_op_ip_attention_add  IP-Adapter's image term, att + s softmax(q K_ip^T) V_ip (ip_attention.hip)
+ *   pd_op_spatial_transformer_ip  one SpatialTransformer block of the UNet with that term
  */
 #ifndef PDENGINE_OPS_H
 #define PDENGINE_OPS_H
@@ -135,6 +137,17 @@ int pd_op_spatial_transformer(pd_engine* e, const char* prefix, const float* x, 
  * L <= 288 (one to three 96-key windows, st_tail.hip); longer contexts take the per-layer path.  pd_op_spatial_transformer is this call
  * with L = pd_config.context_len. */
 int pd_op_spatial_transformer_ctx(pd_engine* e, const char* prefix, const float* x, const float* context, int B, int H, int W, int L, float* y);
+/* IP-Adapter's image term alone (ip_attn_add_kernel): out = round_T(att + s * softmax(q2 k_ip^T scale) v_ip) per head, every operand
+ * rounded to the compute type T first, logits / softmax / the product with v_ip / the multiply by s / the add in fp32.  q2, att, out
+ * [B, N, C]; k_ip, v_ip [Bk, T, C] with Bk = B, or 1: one set of keys for every sample; heads 0: pd_config.num_heads; C / heads one of
+ * 8, 16, 32, 40, 80, 160; 1 <= T <= 64; C a multiple of 8; scale 0: dh^-0.5. */
+int pd_op_ip_attention_add(pd_engine* e, const float* q2, const float* att, const float* k_ip, const float* v_ip, int B, int N, int C, int heads, int T,
+                           int Bk, float scale, float s, float* out);
+/* pd_op_spatial_transformer_ctx of a UNet block with IP-Adapter's image term (pd_ip_adapter_configure, adapter weights loaded): tokens
+ * [B, T, context_dim] go through the block's to_k_ip / to_v_ip and the term enters at the block's current scale (pd_ip_adapter_set_scale),
+ * through the code path of a sampling step.  At scale 0 the call is pd_op_spatial_transformer_ctx, fused tail included. */
+int pd_op_spatial_transformer_ip(pd_engine* e, const char* prefix, const float* x, const float* context, const float* tokens, int B, int H, int W,
+                                 int L, int T, float* y);
 /* timestep_embedding(t, model_channels) (util.py:154-174: [cos | sin], max_period 10000, frequencies i / half) -> temb [n][model_channels],
  * and time_embed(temb) = Linear -> SiLU -> Linear of the loaded network (net 0: UNet, 1: ControlNet; openaimodel.py:526-531) -> emb
  * [n][4 * model_channels]; exactly what the sampler computes once per call for all its steps (pd_engine::compute_emb). */

@@ -1164,7 +1164,10 @@ int pd_engine::resblock(const ResW& r, const Act& x, Act& out, const float* embr
 // halves of cat([x] * 2) (ddim_hacked.py:189) are the same numbers until the first cross-attention reads their different contexts --
 // so GroupNorm, proj_in, norm1, attn1 (and, per layer, attn1.to_out, norm2, attn2.to_q) run once on x.B samples and the block's
 // output has out_B = 2 x.B: sample j of it continues from shared sample j % x.B with context j.
-int pd_engine::transformer(const STW& s, const Act& x, Act& out, const KVSlot& kv, int out_B) {
+//
+// ip (IP-Adapter, ip_adapter.cpp): the image term is added to the text cross-attention's output before attn2.to_out.  The fused tail
+// cannot take it, so a block with a term runs the per-layer path.
+int pd_engine::transformer(const STW& s, const Act& x, Act& out, const KVSlot& kv, int out_B, const IpTerm* ip) {
     int B = x.B;
     const int H = x.H, W = x.W, C = s.C, N = H * W;
     if (out_B <= 0) out_B = B;
@@ -1173,7 +1176,7 @@ int pd_engine::transformer(const STW& s, const Act& x, Act& out, const KVSlot& k
     out = new_act(out_B, H, W, C, S);
     const size_t mk = arena.mark();
     const int L = kv.L > 0 ? kv.L : cfg.context_len, lpad = round_up(L, 8);   // context keys of this call
-    const bool fused = st_tail_on(s, N, L) && s.tail_w && s.front_w && kv.P;
+    const bool fused = !ip && st_tail_on(s, N, L) && s.tail_w && s.front_w && kv.P;
     const int npad = round_up(N, 8);
     Act h, qk, vt, ln;
     LnStats st0, st1;
@@ -1259,10 +1262,13 @@ int pd_engine::transformer(const STW& s, const Act& x, Act& out, const KVSlot& k
             PD_TRY(attention(q2.p, C, reinterpret_cast<const char*>(kv.K) + (size_t)r * B * L * C * eb, C,
                              reinterpret_cast<const char*>(kv.VT) + (size_t)r * B * C * lpad * eb, lpad,
                              reinterpret_cast<char*>(att.p) + (size_t)r * B * N * C * eb, C, B, N, L, C));
+        if (ip) PD_TRY(ip_image_term(q2.p, att.p, *ip, out_B, N, C, reps));
         PD_TRY(repeat_act(h1, reps, h1));
         PD_TRY(repeat_act(x, reps, xr));
-    } else
-    PD_TRY(attention(q2.p, C, kv.K, C, kv.VT, lpad, att.p, C, B, N, L, C));
+    } else {
+        PD_TRY(attention(q2.p, C, kv.K, C, kv.VT, lpad, att.p, C, B, N, L, C));
+        if (ip) PD_TRY(ip_image_term(q2.p, att.p, *ip, out_B, N, C, 1));
+    }
     B = out_B;
     Act h2 = new_act(B, H, W, C, S);
     PD_TRY(gemm(s.out2, att, h2, {.R = &h1}));
@@ -1386,7 +1392,8 @@ int pd_engine::run_unet(const Act& x_in_full, int emb_row, int emb_stride, bool 
             PD_TRY(resblock(b.res, h, o, emb_ptr(ses.emb_u, b.res, emb_row), emb_stride ? b.res.cout : 0));
             if (b.attn) {
                 Act o2;
-                PD_TRY(transformer(b.st, o, o2, ses.kv_u[b.st.kv_slot], Bf));
+                IpTerm it;
+                PD_TRY(transformer(b.st, o, o2, ses.kv_u[b.st.kv_slot], Bf, ip_term(b.st, Bf, ses.a.use_cfg != 0, it) ? &it : nullptr));
                 o = o2;
             }
         }
@@ -1395,7 +1402,8 @@ int pd_engine::run_unet(const Act& x_in_full, int emb_row, int emb_stride, bool 
     }
     Act m0, m1, m2;
     PD_TRY(resblock(n.mid0, h, m0, emb_ptr(ses.emb_u, n.mid0, emb_row), emb_stride ? n.mid0.cout : 0));
-    PD_TRY(transformer(n.mid1, m0, m1, ses.kv_u[n.mid1.kv_slot], Bf));
+    IpTerm it_mid;
+    PD_TRY(transformer(n.mid1, m0, m1, ses.kv_u[n.mid1.kv_slot], Bf, ip_term(n.mid1, Bf, ses.a.use_cfg != 0, it_mid) ? &it_mid : nullptr));
     PD_TRY(resblock(n.mid2, m1, m2, emb_ptr(ses.emb_u, n.mid2, emb_row), emb_stride ? n.mid2.cout : 0));
     h = m2;
     PD_TRY(join_controlnet());   // the decoder is the first consumer of the control tensors
@@ -1421,7 +1429,8 @@ int pd_engine::run_unet(const Act& x_in_full, int emb_row, int emb_stride, bool 
         PD_TRY(resblock(b.res, cat, o, emb_ptr(ses.emb_u, b.res, emb_row), emb_stride ? b.res.cout : 0));
         if (b.attn) {
             Act o2;
-            PD_TRY(transformer(b.st, o, o2, ses.kv_u[b.st.kv_slot]));
+            IpTerm it;
+            PD_TRY(transformer(b.st, o, o2, ses.kv_u[b.st.kv_slot], 0, ip_term(b.st, Bf, ses.a.use_cfg != 0, it) ? &it : nullptr));
             o = o2;
         }
         if (b.up) {

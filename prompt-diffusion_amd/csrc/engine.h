@@ -111,6 +111,7 @@ struct STW {
     ConvW proj_in, proj_out;
     WMat qkv, out1, q2, kv2, out2, ff1, ff2;
     int kv_slot = -1;  // index into the per-net table of hoisted context K / V^T
+    int ip_slot = -1;  // UNet only, set by pd_ip_adapter_configure: the block's index j among the UNet's cross-attention blocks (IpAdapterW)
     // fused tail (st_tail.hip): the block's matrices after self-attention in MFMA-fragment order + its fp32 vectors
     void* tail_w = nullptr;
     float* tail_vec = nullptr;
@@ -287,6 +288,40 @@ struct SafetyW {
     float *cpt = nullptr, *spc = nullptr, *cpt_thr = nullptr, *spc_thr = nullptr;   // concept / special-care rows and thresholds
 };
 
+// IP-Adapter for the UNet (ip_adapter.cpp; pd_ip_adapter_configure): the linear ImageProjection, and to_k_ip / to_v_ip of every UNet
+// cross-attention block j in diffusers' processor order (input blocks, output blocks, middle block; checkpoint id 2 j + 1).
+// The image state (pd_ip_adapter_set_image): K_ip / V_ip of every block for both guidance halves in one engine-owned allocation,
+// half 0 = unconditional, 1 = conditional, each [Bi][T][C_j] in the compute type.
+struct IpAdapterW {
+    bool built = false, broken = false;    // broken: as ClipVisionW's
+    int T = 0, E = 0;                      // image tokens; width of the image embedding
+    WMat proj;                             // image_proj.proj [T * D][E] + bias
+    float *norm_g = nullptr, *norm_b = nullptr;
+    std::vector<WMat> to_k, to_v;          // [C_j][D] each, no bias
+    std::vector<STW*> blocks;              // block j
+    std::vector<float> scale;              // s_j (all 1 after configure)
+    int Bi = 0;                            // images of the state; 0: none set
+    void* kv = nullptr;                    // the allocation (grown on demand, never shrunk)
+    size_t kv_cap = 0;
+    std::vector<size_t> k_off, v_off;      // byte offset of half 0 of block j; half 1 follows at + Bi * T * C_j elements
+    uint64_t gen = 0;                      // bumped by every set / clear: part of the graph replay key
+    bool active() const {
+        if (!built || broken || Bi < 1) return false;
+        for (float s : scale)
+            if (s != 0.f) return true;
+        return false;
+    }
+};
+// What pd_engine::transformer adds to a block's text cross-attention: nseg equal runs of the block's output batch, run r against K[r] /
+// V[r] ([Bk][T][C], kv_bs elements apart, 0 = one set for every sample of the run)
+struct IpTerm {
+    const void* K[2] = {nullptr, nullptr};
+    const void* V[2] = {nullptr, nullptr};
+    int nseg = 1, T = 0;
+    long long kv_bs = 0;
+    float s = 0.f;
+};
+
 // SD3's T5 encoder stack (sd3_text.cpp): no biases anywhere, RMSNorm weights only, wi = [wi_1 | wi_0] packed like a GEGLU matrix
 struct T5LayerW {
     float *ln1 = nullptr, *ln2 = nullptr;
@@ -341,6 +376,7 @@ enum WeightGroup {
     GROUP_CLIP_VISION_0 = 10,   // the two image towers, one group each
     GROUP_CLIP_VISION_1 = 11,
     GROUP_SAFETY = 12,
+    GROUP_IP_ADAPTER = 13,
 };
 
 struct Param {
@@ -800,7 +836,15 @@ struct pd_engine {
     int groupnorm(const Act& x, Act& y, const float* g, const float* b, float eps, bool silu, const SlabDefer* from_slabs = nullptr);
     int layernorm(const Act& x, Act& y, const float* g, const float* b, float eps = 1e-5f);
     int resblock(const ResW& r, const Act& x, Act& out, const float* embrow, int emb_stride);
-    int transformer(const STW& s, const Act& x, Act& out, const KVSlot& kv, int out_B = 0);
+    int transformer(const STW& s, const Act& x, Act& out, const KVSlot& kv, int out_B = 0, const IpTerm* ip = nullptr);
+    // IP-Adapter (ip_adapter.cpp)
+    IpAdapterW ip;
+    long long ip_launches = 0;   // stat "ip_launches": image-term launches so far
+    // the term of block s in a network evaluation at batch Bf (use_cfg: [unconditional ; conditional] halves); false: none (inactive, not a
+    // UNet block, s_j == 0)
+    bool ip_term(const STW& s, int Bf, bool use_cfg, IpTerm& t) const;
+    int ip_check_batch(int B) const;   // non-zero with the error set when the image state does not fit a sampling batch B
+    int ip_image_term(const void* q2, void* att, const IpTerm& t, int B, int N, int C, int q_shared);
     int repeat_act(const Act& src, int reps, Act& dst);
     static Act batch_view(const Act& a, int first, int count);
     int attention(const void* Q, int ldq, const void* K, int ldk, const void* VT, int vt_ld, void* O, int ldo, int B, int Nq,

@@ -688,6 +688,40 @@ int pd_op_vae_attention(pd_engine* e, const float* q, const float* k, const floa
     return 0;
 }
 
+// IP-Adapter's image term alone (launch_ip_attention_add): out = round_T(att + s * softmax(q2 k_ip^T scale) v_ip) per head, every operand
+// rounded to the compute type first; q2, att, out [B, N, C]; k_ip, v_ip [Bk, T, C], Bk = B or 1 (one set for every sample); scale 0: dh^-0.5
+int pd_op_ip_attention_add(pd_engine* e, const float* q2, const float* att, const float* k_ip, const float* v_ip, int B, int N, int C, int heads, int T,
+                           int Bk, float scale, float s, float* out) {
+    if (!e || !q2 || !att || !k_ip || !v_ip || !out) { pd_set_error("null argument"); return 1; }
+    if (heads <= 0) heads = e->cfg.num_heads;
+    if (B < 1 || N < 1 || C < 8 || C % 8 || C % heads || T < 1 || T > 64 || (Bk != 1 && Bk != B)) {
+        pd_set_error("pd_op_ip_attention_add: need B, N >= 1, C a multiple of 8 and of heads, 1 <= T <= 64, Bk = 1 or B (got B %d N %d C %d heads %d T %d Bk %d)", B,
+                     N, C, heads, T, Bk);
+        return 1;
+    }
+    if ((long long)B * N * C > INT32_MAX) { pd_set_error("pd_op_ip_attention_add: more than 2^31 elements"); return 1; }
+    HIP_OK(hipSetDevice(e->device));
+    const size_t eb = dt_size(e->T), no = (size_t)B * N * C, nk = (size_t)Bk * T * C;
+    DevBuf fq(no * 4), fa(no * 4), fk(nk * 4), fv(nk * 4), dq(no * eb), da(no * eb), dk(nk * eb), dv(nk * eb);
+    if (!fq.p || !fa.p || !fk.p || !fv.p || !dq.p || !da.p || !dk.p || !dv.p) { pd_set_error("allocation failed"); return 1; }
+    HIP_OK(hipMemcpy(fq.p, q2, no * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(fa.p, att, no * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(fk.p, k_ip, nk * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(fv.p, v_ip, nk * 4, hipMemcpyHostToDevice));
+    if (launch_cast_rows(reinterpret_cast<const float*>(fq.p), dq.p, e->T, (long long)B * N, C, C, e->stream)) return 1;
+    if (launch_cast_rows(reinterpret_cast<const float*>(fa.p), da.p, e->T, (long long)B * N, C, C, e->stream)) return 1;
+    if (launch_cast_rows(reinterpret_cast<const float*>(fk.p), dk.p, e->T, (long long)Bk * T, C, C, e->stream)) return 1;
+    if (launch_cast_rows(reinterpret_cast<const float*>(fv.p), dv.p, e->T, (long long)Bk * T, C, C, e->stream)) return 1;
+    if (scale == 0.f) scale = (float)(1.0 / std::sqrt((double)(C / heads)));
+    ++e->launches;
+    const int r = launch_ip_attention_add(dq.p, da.p, dk.p, dv.p, Bk == 1 ? 0 : (long long)T * C, B, N, C, heads, T, scale, s, e->T, e->stream);
+    if (r) { pd_set_error(r == 2 ? "pd_op_ip_attention_add: unsupported head dim %d" : "pd_op_ip_attention_add: launch failed (dh %d)", C / heads); return 1; }
+    if (launch_nhwc_to_nchw(da.p, e->T, reinterpret_cast<float*>(fa.p), 1, 1, 1, (int)no, 1, 1.f, e->stream)) return 1;
+    HIP_OK(hipStreamSynchronize(e->stream));
+    HIP_OK(hipMemcpy(out, fa.p, no * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // One whole SpatialTransformer block of the engine's own networks (GroupNorm eps 1e-6, proj_in, BasicTransformerBlock, proj_out, + x;
 // attention.py:321-340 and :271-275) with the weights loaded under `prefix` (e.g. "model.diffusion_model.input_blocks.1.1.") on
 // x [B, C, H, W] and context [B, context_len, context_dim], through exactly the code path a sampling step takes -- including the fused
@@ -698,7 +732,22 @@ int pd_op_spatial_transformer(pd_engine* e, const char* prefix, const float* x, 
 }
 
 // ... on a context of any length: [B, L, context_dim], 1 <= L <= PD_MAX_CONTEXT_LEN
+static int spatial_transformer_hook(pd_engine* e, const char* prefix, const float* x, const float* ctx, const float* tokens, int B, int H, int W, int L,
+                                    int T, float* y);
 int pd_op_spatial_transformer_ctx(pd_engine* e, const char* prefix, const float* x, const float* ctx, int B, int H, int W, int L, float* y) {
+    return spatial_transformer_hook(e, prefix, x, ctx, nullptr, B, H, W, L, 0, y);
+}
+
+// ... with IP-Adapter's image term: tokens [B, T, context_dim] go through the block's loaded to_k_ip / to_v_ip (the engine's own GEMMs),
+// then the block runs with the term at the block's current scale, as in a sampling step.  Scale 0: exactly the call above.
+int pd_op_spatial_transformer_ip(pd_engine* e, const char* prefix, const float* x, const float* ctx, const float* tokens, int B, int H, int W, int L,
+                                 int T, float* y) {
+    if (!tokens) { pd_set_error("null argument"); return 1; }
+    return spatial_transformer_hook(e, prefix, x, ctx, tokens, B, H, W, L, T, y);
+}
+
+static int spatial_transformer_hook(pd_engine* e, const char* prefix, const float* x, const float* ctx, const float* tokens, int B, int H, int W, int L,
+                                    int T, float* y) {
     if (!e || !prefix || !x || !ctx || !y) { pd_set_error("null argument"); return 1; }
     if (L < 1 || L > PD_MAX_CONTEXT_LEN) { pd_set_error("context length %d out of range 1 .. %d", L, PD_MAX_CONTEXT_LEN); return 1; }
     HIP_OK(hipSetDevice(e->device));
@@ -713,6 +762,16 @@ int pd_op_spatial_transformer_ctx(pd_engine* e, const char* prefix, const float*
     if (!st) { pd_set_error("no SpatialTransformer under '%s'", prefix); return 1; }
     for (const Param& p : e->params)
         if (!p.loaded && p.name.compare(0, pre.size(), pre) == 0) { pd_set_error("weights not loaded: '%s'", p.name.c_str()); return 1; }
+    const int ipj = st->ip_slot;
+    if (tokens) {
+        if (ipj < 0 || !e->ip.built || e->ip.broken) { pd_set_error("no IP-Adapter weights for the block under '%s' (pd_ip_adapter_configure; UNet blocks only)", prefix); return 1; }
+        if (T < 1 || T > 64) { pd_set_error("pd_op_spatial_transformer_ip: T %d outside 1 .. 64", T); return 1; }
+        for (const char* w : {"to_k_ip", "to_v_ip"}) {   // (this block's pair is all the call reads)
+            const std::string n = "ip_adapter." + std::to_string(2 * ipj + 1) + "." + w + ".weight";
+            auto pi = e->index.find(n);
+            if (pi == e->index.end() || !e->params[pi->second].loaded) { pd_set_error("weights not loaded: '%s'", n.c_str()); return 1; }
+        }
+    }
     e->ln_dirty = true;
     PD_TRY(e->fold_layernorms());
     const int C = st->C, D = e->cfg.context_dim, Dp = round_up(D, 8), lpad = round_up(L, 8), N = H * W;
@@ -721,7 +780,9 @@ int pd_op_spatial_transformer_ctx(pd_engine* e, const char* prefix, const float*
     const size_t ws = (size_t)64 << 20, act = (size_t)B * N * C * 4;
     DevBuf work(ws + 48 * act), cin((size_t)B * L * D * 4), cdev((size_t)B * L * Dp * eb), kbuf((size_t)B * L * C * eb), vtbuf((size_t)B * C * lpad * eb),
         kvp(e->st_tail_on(*st, H * W, L) ? st_tail_kv_bytes(B, L) : 256), xin((size_t)B * N * C * dt_size(e->S));
-    if (!work.p || !cin.p || !cdev.p || !kbuf.p || !vtbuf.p || !kvp.p || !xin.p) { pd_set_error("allocation failed"); return 1; }
+    const size_t ntok = tokens ? (size_t)B * T : 0;
+    DevBuf tin(ntok * D * 4), tdev(ntok * Dp * eb), kip(ntok * C * eb), vip(ntok * C * eb);
+    if (!work.p || !cin.p || !cdev.p || !kbuf.p || !vtbuf.p || !kvp.p || !xin.p || !tin.p || !tdev.p || !kip.p || !vip.p) { pd_set_error("allocation failed"); return 1; }
     const Arena saved = e->arena;
     e->arena = Arena{};
     e->arena.base = reinterpret_cast<char*>(work.p);
@@ -741,9 +802,22 @@ int pd_op_spatial_transformer_ctx(pd_engine* e, const char* prefix, const float*
             if ((rc = launch_st_tail_kv_pack(kbuf.p, vtbuf.p, kvp.p, B, L, lpad, e->stream))) break;
             kv.P = kvp.p;
         }
+        IpTerm term;
+        const bool with_term = tokens && e->ip.scale[ipj] != 0.f;
+        if (with_term) {
+            if (hipMemcpy(tin.p, tokens, ntok * D * 4, hipMemcpyHostToDevice) != hipSuccess) { rc = 1; break; }
+            if ((rc = launch_cast_rows(reinterpret_cast<const float*>(tin.p), tdev.p, e->T, (long long)ntok, D, Dp, e->stream))) break;
+            Act t, ko, vo;
+            t.p = tdev.p; t.B = (int)ntok; t.H = 1; t.W = 1; t.C = Dp; t.dt = e->T;
+            ko = t; ko.p = kip.p; ko.C = C;
+            vo = ko; vo.p = vip.p;
+            if ((rc = e->gemm(e->ip.to_k[ipj], t, ko))) break;
+            if ((rc = e->gemm(e->ip.to_v[ipj], t, vo))) break;
+            term.K[0] = kip.p; term.V[0] = vip.p; term.nseg = 1; term.T = T; term.kv_bs = (long long)T * C; term.s = e->ip.scale[ipj];
+        }
         Act a, o;
         a.p = xin.p; a.B = B; a.H = H; a.W = W; a.C = C; a.dt = e->S;
-        if ((rc = e->transformer(*st, a, o, kv))) break;
+        if ((rc = e->transformer(*st, a, o, kv, 0, with_term ? &term : nullptr))) break;
         rc = from_dev_nhwc(e, o.p, e->S, y, B, C, H, W, C);
     } while (0);
     (void)hipStreamSynchronize(e->stream);

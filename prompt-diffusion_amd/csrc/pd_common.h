@@ -392,6 +392,11 @@ int launch_add_inplace(void* a, const void* b, int dt, long long n, hipStream_t 
 // half passed through fourier_filter(threshold 1, scale s) per (sample, channel) plane; rows = B * H * W
 int launch_freeu_concat(const void* h, const void* h_add, const void* skip, const void* skip_add, void* out, int dt, int B, int H,
                         int W, int Ch, int Cs, float s, float b, hipStream_t st, long long skip_rows = 0, long long skip_add_rows = 0);
+// IP-Adapter's image term (ip_attention.hip): att [B][N][C] += s * softmax(q2 K_ip^T scale) V_ip per head, in place, one rounding to
+// dt at the store.  q2, att [B][N][C], K_ip / V_ip [.][T][C] in dt, kv_sample_stride elements between two samples' keys (0: one set
+// for every sample); 1 <= T <= 64, C % 8 == 0, C / heads one of 8, 16, 32, 40, 80, 160.  0 launched, 1 launch failure, 2 shape refused
+int launch_ip_attention_add(const void* q2, void* att, const void* K_ip, const void* V_ip, long long kv_sample_stride, int B, int N, int C, int heads,
+                            int T, float scale, float s, int dt, hipStream_t stream);
 // The end of a denoising step (sampler_update.hip): guidance + solver update (+ inpainting blend) + the next step's x_in.
 // What every update launch of a session shares: the UNet's eps [Bf, HW, eps_C] (uncond half first) in eps_dt, x_state
 // [B, HW, Cpad] fp32 updated in place, pred_x0 / eps_guided [B, HW, C] fp32, x_in [dup * B, HW, Cpad] fp32.

@@ -134,6 +134,7 @@ int pd_engine::session_setup(const pd_sample_args& a, const int64_t* t_rows, int
     const int IH = a.h * 8, IW = a.w * 8;
     const bool dev = a.mem == PD_MEM_DEVICE;
     const bool xt_seeded = (a.init_flags & PD_XT_FROM_SEED) != 0;
+    PD_TRY(ip_check_batch(B));
     arena.top = 0;
     arena.overflow = false;
     s.x_state = reinterpret_cast<float*>(arena.alloc((size_t)B * HW * 8 * 4));
@@ -643,6 +644,11 @@ int pd_engine::run_steps_graph() {
     hash_mix(key, ses.lms_coef.data(), ses.lms_coef.size() * sizeof(double));
     hash_mix(key, ses.lms_times.data(), ses.lms_times.size() * sizeof(double));
     hash_mix(key, freeu, sizeof(freeu));   // FreeU values are kernel arguments (pd_set_freeu also drops the graphs)
+    // IP-Adapter: whether the term's launches are in the loop, their arguments (scales, T, Bi -> the key stride) and which fill of the
+    // image buffers they were captured against (every setter also drops the graphs)
+    const uint64_t ipk[] = {ip.active() ? 1u : 0u, (uint64_t)ip.T, (uint64_t)ip.Bi, ip.gen, (uint64_t)(uintptr_t)ip.kv};
+    hash_mix(key, ipk, sizeof(ipk));
+    hash_mix(key, ip.scale.data(), ip.scale.size() * sizeof(float));
     // img2img / inpainting: the blend kernels and their coefficients (the start runs before the captured loop)
     const int32_t init[] = {ses.init_z0 ? 1 : 0, ses.mask ? 1 : 0, a.init_flags};
     const void* iptrs[] = {ses.init_z0, ses.init_eps, ses.mask};
@@ -730,6 +736,7 @@ void pd_engine_destroy(pd_engine* e) {
     e->clear_graphs();
     e->lora_release();
     e->image_release();
+    if (e->ip.kv) hipFree(e->ip.kv);
     if (e->stream2) { hipStreamSynchronize(e->stream2); hipStreamDestroy(e->stream2); }
     for (hipEvent_t ev : e->sd3_ev) hipEventDestroy(ev);
     if (e->ev_fork) hipEventDestroy(e->ev_fork);

@@ -142,6 +142,10 @@ class pd_clip_vision_args(C.Structure):
                [("image_embeds", C.c_void_p), ("pooler_output", C.c_void_p), ("hidden", C.c_void_p), ("reserved", C.c_int64 * 2)]
 
 
+class pd_ip_adapter_config(C.Structure):
+    _fields_ = [("num_tokens", C.c_int32), ("embed_dim", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
 class pd_mlsd_args(C.Structure):
     _fields_ = [("images", C.c_void_p), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("mem", C.c_int32), ("what", C.c_int32),
                 ("thr_v", C.c_float), ("thr_d", C.c_float), ("out", C.c_void_p), ("dst_f", C.c_void_p), ("mem_f", C.c_int32),
@@ -340,6 +344,16 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.pd_safety_weights_missing.argtypes = [C.c_void_p]
         lib.pd_safety_check.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         lib.pd_safety_blank.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_float]
+    if hasattr(lib, "pd_ip_adapter_configure"):   # (as above: an older build lacks the adapter)
+        lib.pd_ip_adapter_configure.argtypes = [C.c_void_p, C.POINTER(pd_ip_adapter_config)]
+        lib.pd_ip_adapter_weights_missing.argtypes = [C.c_void_p]
+        lib.pd_ip_adapter_set_scale.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        lib.pd_ip_adapter_get_scale.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        lib.pd_ip_adapter_set_image.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
+        lib.pd_ip_adapter_clear_image.argtypes = [C.c_void_p]
+        lib.pd_bench_ip_attention.argtypes = [C.c_void_p] + [C.c_int32] * 5 + [C.POINTER(C.c_float)] * 2
+        lib.pd_op_ip_attention_add.argtypes = [C.c_void_p, fp, fp, fp, fp] + [C.c_int] * 6 + [C.c_float, C.c_float, fp]
+        lib.pd_op_spatial_transformer_ip.argtypes = [C.c_void_p, C.c_char_p, fp, fp, fp] + [C.c_int] * 5 + [fp]
     lib.pd_image_store.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_int32]
     lib.pd_canny.argtypes = [C.c_void_p, C.POINTER(pd_canny_args)]
     lib.pd_op_canny_hysteresis.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
@@ -381,6 +395,8 @@ EXPORTS = [
     "pd_sd3_text_configure", "pd_sd3_text_weights_missing", "pd_sd3_encode_prompt", "pd_sd3_text_encoder", "pd_t5_relative_buckets",
     "pd_resample_coefficients_ex", "pd_clip_preprocess", "pd_clip_preprocess_geometry", "pd_clip_patch_width", "pd_clip_vision_configure",
     "pd_clip_vision_weights_missing", "pd_clip_vision_forward", "pd_safety_configure", "pd_safety_weights_missing", "pd_safety_check", "pd_safety_blank",
+    "pd_ip_adapter_configure", "pd_ip_adapter_weights_missing", "pd_ip_adapter_set_scale", "pd_ip_adapter_get_scale", "pd_ip_adapter_set_image",
+    "pd_ip_adapter_clear_image", "pd_bench_ip_attention", "pd_op_ip_attention_add", "pd_op_spatial_transformer_ip",
     "pd_sd3_vae_configure", "pd_sd3_vae_weights_missing", "pd_sd3_vae_config_layout", "pd_sd3_vae_decode", "pd_sd3_vae_encode", "pd_op_vae_attention", "pd_bench_vae_attention",
 ]
 
@@ -691,6 +707,9 @@ class Engine:
             self.configure_clip_vision(cv)
         if getattr(cfg, "safety_checker", False):
             self.configure_safety_checker()
+        self._ip_adapter: Optional[Tuple[int, int]] = None    # (num_tokens, embed_dim) once configured
+        if getattr(cfg, "ip_adapter", ()):
+            self.configure_ip_adapter(*cfg.ip_adapter)
         self._keep: List[_Buf] = []
         self._rng_set = False    # the caller has chosen a seed (set_rng): draws nobody supplied may come from the engine
 
@@ -1064,6 +1083,67 @@ class Engine:
             self.configure_clip_vision(cfg, SAFETY_PREFIX)
         self._check(self.lib.pd_safety_configure(self._h))
         self._shapes = None
+
+    # ------------------------------------------------------------------ IP-Adapter (pd_ip_adapter_*)
+    def configure_ip_adapter(self, num_tokens: int = 4, embed_dim: int = 1024) -> None:
+        """Registers the adapter's tensors (image_proj.*, ip_adapter.{2j+1}.to_k_ip / to_v_ip for the UNet's cross-attention blocks j in
+        diffusers' processor order) in a registry group of their own; they load through load_state_dict.  Once per engine; a second
+        call with the same numbers does nothing."""
+        if self._ip_adapter is not None:
+            if self._ip_adapter != (int(num_tokens), int(embed_dim)):
+                raise NotImplementedError(f"this engine's registry already holds an IP-Adapter with (num_tokens, embed_dim) = {self._ip_adapter}; "
+                                          f"one with {(int(num_tokens), int(embed_dim))} needs a new engine (tensors cannot be re-registered)")
+            return
+        c = pd_ip_adapter_config(num_tokens=int(num_tokens), embed_dim=int(embed_dim))
+        self._check(self.lib.pd_ip_adapter_configure(self._h, C.byref(c)))
+        self._ip_adapter = (int(num_tokens), int(embed_dim))
+        self._shapes = None
+
+    @property
+    def ip_adapter_blocks(self) -> int:
+        """Cross-attention blocks of the UNet (16 for the SD1.5 topology): the length of a per-block scale list."""
+        from .weights import decoder_layout, encoder_layout
+        return sum(b["attn"] for b in encoder_layout(self.cfg)) + sum(b["attn"] for b in decoder_layout(self.cfg)) + 1
+
+    def ip_adapter_weights_missing(self) -> int:
+        return self.lib.pd_ip_adapter_weights_missing(self._h)
+
+    def ip_adapter_set_scale(self, scale) -> None:
+        """One scale for every block, or one per block (ip_adapter_blocks values, processor order).  0 everywhere switches the adapter
+        off: the engine then launches exactly what it launches without one."""
+        s = np.ascontiguousarray(np.atleast_1d(np.asarray(scale, np.float32)).reshape(-1))
+        self._check(self.lib.pd_ip_adapter_set_scale(self._h, s.ctypes.data, int(s.size)))
+
+    def ip_adapter_scale(self) -> np.ndarray:
+        out = np.zeros(self.ip_adapter_blocks, np.float32)
+        self._check(self.lib.pd_ip_adapter_get_scale(self._h, out.ctypes.data, int(out.size)))
+        return out
+
+    def ip_adapter_set_image(self, embeds, negative_embeds=None) -> None:
+        """embeds [Bi, E] (NumPy or a CUDA tensor): the image embeddings of the conditional half; negative_embeds [Bi, E] or None (zeros).
+        Runs the projection and every block's K / V GEMMs now; every later UNet evaluation of this engine adds the image term until
+        ip_adapter_clear_image.  A sampling call of batch B needs Bi == B or Bi == 1."""
+        c = _Buf(embeds)
+        if c.owner.ndim != 2:
+            raise ValueError(f"ip_adapter_set_image: embeds must be [Bi, E], got {tuple(c.owner.shape)}")
+        n = None
+        if negative_embeds is not None:
+            n = _Buf(negative_embeds)
+            if tuple(n.owner.shape) != tuple(c.owner.shape) or n.mem != c.mem:
+                raise ValueError("ip_adapter_set_image: negative_embeds must match embeds in shape and memory space")
+        if self._ip_adapter is not None and int(c.owner.shape[1]) != self._ip_adapter[1]:
+            raise ValueError(f"ip_adapter_set_image: embeddings of width {int(c.owner.shape[1])}, the adapter takes {self._ip_adapter[1]}")
+        self._order_after_torch(c.mem, c.device)
+        self._check(self.lib.pd_ip_adapter_set_image(self._h, c.ptr, None if n is None else n.ptr, int(c.owner.shape[0]), c.mem))
+
+    def ip_adapter_clear_image(self) -> None:
+        self._check(self.lib.pd_ip_adapter_clear_image(self._h))
+
+    def bench_ip_attention(self, B: int, N: int, Cc: int, T: int = 4, iters: int = 50) -> Tuple[float, float]:
+        """(ms per launch of the image term's kernel, ms per device-to-device copy of the 3 B N C elements it moves), random data"""
+        k, c = C.c_float(), C.c_float()
+        self._check(self.lib.pd_bench_ip_attention(self._h, B, N, Cc, T, iters, C.byref(k), C.byref(c)))
+        return float(k.value), float(c.value)
 
     def _clip_prefix(self, prefix: Optional[str]) -> str:
         if prefix is None:
@@ -2122,6 +2202,30 @@ class Engine:
                                               float(guidance), float(dsigma), float(sigma), int(bool(pure)), int(bool(seeded)), PD_MEM_HOST,
                                               ptr(out), ptr(x_in)))
         return (out, x_in) if want_x_in else out
+
+    def op_ip_attention_add(self, q2, att, k_ip, v_ip, heads: int = 0, s: float = 1.0, scale: float = 0.0):
+        """IP-Adapter's image term alone (ip_attn_add_kernel): att + s * softmax(q2 k_ip^T scale) v_ip per head in the compute type;
+        q2, att [B, N, C]; k_ip, v_ip [B or 1, T, C]."""
+        f = lambda a: np.ascontiguousarray(a, np.float32)
+        q2, att, k_ip, v_ip = f(q2), f(att), f(k_ip), f(v_ip)
+        B, N, Cc = q2.shape
+        Bk, T, _ = k_ip.shape
+        assert att.shape == q2.shape and v_ip.shape == k_ip.shape and k_ip.shape[2] == Cc
+        out = np.empty_like(q2)
+        self._check(self.lib.pd_op_ip_attention_add(self._h, q2.ctypes.data, att.ctypes.data, k_ip.ctypes.data, v_ip.ctypes.data, B, N, Cc,
+                                                    int(heads), T, Bk, float(scale), float(s), out.ctypes.data))
+        return out
+
+    def op_spatial_transformer_ip(self, prefix: str, x, context, tokens):
+        """op_spatial_transformer of a UNet block with the image term of tokens [B, T, context_dim] at the block's current scale."""
+        x = np.ascontiguousarray(x, np.float32); ctx = np.ascontiguousarray(context, np.float32); tok = np.ascontiguousarray(tokens, np.float32)
+        B, Cc, H, W = x.shape
+        L = self._context_len(ctx, B, "context")
+        assert tok.ndim == 3 and tok.shape[0] == B and tok.shape[2] == self.cfg.context_dim, tok.shape
+        y = np.empty_like(x)
+        self._check(self.lib.pd_op_spatial_transformer_ip(self._h, prefix.encode(), x.ctypes.data, ctx.ctypes.data, tok.ctypes.data, B, H, W, L,
+                                                          int(tok.shape[1]), y.ctypes.data))
+        return y
 
     def op_spatial_transformer(self, prefix: str, x, context):
         """SpatialTransformer.forward (attention.py:321-340) of the block loaded under `prefix`, through the sampling code path;

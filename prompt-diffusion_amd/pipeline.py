@@ -27,6 +27,7 @@ from typing import Any, Callable, Dict, List, Optional, Sequence, Union
 import numpy as np
 
 from . import engine as E
+from .ip_adapter import IPAdapterMixin
 from .lora_pipeline import AdapterMixin
 
 
@@ -165,7 +166,7 @@ def prepare_inpaint_mask(mask_image, width, height, batch_size, scale_factor):
     return PromptDiffusionPipeline._tile(m, batch_size, "`mask_image`")
 
 
-class PromptDiffusionPipeline(AdapterMixin):
+class PromptDiffusionPipeline(AdapterMixin, IPAdapterMixin):
     _callback_tensor_inputs = ["latents", "prompt_embeds", "negative_prompt_embeds"]
     vae_scale_factor = 8
     vae_scaling_factor = 0.18215      # models/cldm_v15.yaml:17
@@ -750,7 +751,7 @@ class PromptDiffusionPipeline(AdapterMixin):
                  timesteps: List[int] = None, guidance_scale: float = 7.5,
                  negative_prompt: Optional[Union[str, List[str]]] = None, num_images_per_prompt: Optional[int] = 1,
                  eta: float = 0.0, generator=None, latents=None, prompt_embeds=None, negative_prompt_embeds=None,
-                 ip_adapter_image=None, output_type: Optional[str] = "pil", return_dict: bool = True,
+                 ip_adapter_image=None, ip_adapter_image_embeds=None, output_type: Optional[str] = "pil", return_dict: bool = True,
                  cross_attention_kwargs: Optional[Dict[str, Any]] = None,
                  controlnet_conditioning_scale: Union[float, List[float]] = 1.0, guess_mode: bool = False,
                  control_guidance_start: Union[float, List[float]] = 0.0, control_guidance_end: Union[float, List[float]] = 1.0,
@@ -760,22 +761,28 @@ class PromptDiffusionPipeline(AdapterMixin):
                          num_inference_steps=num_inference_steps, timesteps=timesteps, guidance_scale=guidance_scale,
                          negative_prompt=negative_prompt, num_images_per_prompt=num_images_per_prompt, eta=eta, generator=generator,
                          latents=latents, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
-                         ip_adapter_image=ip_adapter_image, output_type=output_type, return_dict=return_dict,
+                         ip_adapter_image=ip_adapter_image, ip_adapter_image_embeds=ip_adapter_image_embeds, output_type=output_type,
+                         return_dict=return_dict,
                          cross_attention_kwargs=cross_attention_kwargs, controlnet_conditioning_scale=controlnet_conditioning_scale,
                          guess_mode=guess_mode, control_guidance_start=control_guidance_start,
                          control_guidance_end=control_guidance_end, clip_skip=clip_skip, callback_on_step_end=callback_on_step_end,
                          callback_on_step_end_tensor_inputs=callback_on_step_end_tensor_inputs, kwargs=kwargs)
 
-    def _run(self, prompt, image, image_pair, height, width, num_inference_steps, timesteps, guidance_scale, negative_prompt,
-             num_images_per_prompt, eta, generator, latents, prompt_embeds, negative_prompt_embeds, ip_adapter_image, output_type,
-             return_dict, cross_attention_kwargs, controlnet_conditioning_scale, guess_mode, control_guidance_start,
-             control_guidance_end, clip_skip, callback_on_step_end, callback_on_step_end_tensor_inputs, kwargs, init=None):
+    def _run(self, *, ip_adapter_image=None, ip_adapter_image_embeds=None, **body):
+        """_run_body(**body) inside the IP-Adapter bracket of the call (IPAdapterMixin._ip_image_of_call): the image state is set in the
+        engine before the body runs and cleared when it ends, with or without an exception."""
+        with self._ip_image_of_call(ip_adapter_image, ip_adapter_image_embeds, body["prompt"], body["prompt_embeds"],
+                                    body["num_images_per_prompt"], body["guidance_scale"]):
+            return self._run_body(**body)
+
+    def _run_body(self, prompt, image, image_pair, height, width, num_inference_steps, timesteps, guidance_scale, negative_prompt,
+                  num_images_per_prompt, eta, generator, latents, prompt_embeds, negative_prompt_embeds, output_type,
+                  return_dict, cross_attention_kwargs, controlnet_conditioning_scale, guess_mode, control_guidance_start,
+                  control_guidance_end, clip_skip, callback_on_step_end, callback_on_step_end_tensor_inputs, kwargs, init=None):
         """The body of __call__.  `image` is the ControlNet query.  init (img2img / inpainting, the subclasses below):
         dict(image=init image, mask=mask image or None, strength=float); None runs the plain text-to-image loop."""
         callback = kwargs.pop("callback", None)
         callback_steps = kwargs.pop("callback_steps", None)
-        if ip_adapter_image is not None:
-            raise NotImplementedError("ip_adapter_image is outside the hot path this engine replaces")
         lora_scale = 1.0
         if cross_attention_kwargs:
             if not self._lora_adapters:
@@ -1092,7 +1099,7 @@ class PromptDiffusionImg2ImgPipeline(PromptDiffusionPipeline):
                  timesteps: List[int] = None, guidance_scale: float = 7.5,
                  negative_prompt: Optional[Union[str, List[str]]] = None, num_images_per_prompt: Optional[int] = 1,
                  eta: float = 0.0, generator=None, latents=None, prompt_embeds=None, negative_prompt_embeds=None,
-                 ip_adapter_image=None, output_type: Optional[str] = "pil", return_dict: bool = True,
+                 ip_adapter_image=None, ip_adapter_image_embeds=None, output_type: Optional[str] = "pil", return_dict: bool = True,
                  cross_attention_kwargs: Optional[Dict[str, Any]] = None,
                  controlnet_conditioning_scale: Union[float, List[float]] = 1.0, guess_mode: bool = False,
                  control_guidance_start: Union[float, List[float]] = 0.0, control_guidance_end: Union[float, List[float]] = 1.0,
@@ -1102,7 +1109,8 @@ class PromptDiffusionImg2ImgPipeline(PromptDiffusionPipeline):
                          num_inference_steps=num_inference_steps, timesteps=timesteps, guidance_scale=guidance_scale,
                          negative_prompt=negative_prompt, num_images_per_prompt=num_images_per_prompt, eta=eta, generator=generator,
                          latents=latents, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
-                         ip_adapter_image=ip_adapter_image, output_type=output_type, return_dict=return_dict,
+                         ip_adapter_image=ip_adapter_image, ip_adapter_image_embeds=ip_adapter_image_embeds, output_type=output_type,
+                         return_dict=return_dict,
                          cross_attention_kwargs=cross_attention_kwargs, controlnet_conditioning_scale=controlnet_conditioning_scale,
                          guess_mode=guess_mode, control_guidance_start=control_guidance_start,
                          control_guidance_end=control_guidance_end, clip_skip=clip_skip, callback_on_step_end=callback_on_step_end,
@@ -1123,7 +1131,7 @@ class PromptDiffusionInpaintPipeline(PromptDiffusionPipeline):
                  num_inference_steps: int = 50, timesteps: List[int] = None, guidance_scale: float = 7.5,
                  negative_prompt: Optional[Union[str, List[str]]] = None, num_images_per_prompt: Optional[int] = 1,
                  eta: float = 0.0, generator=None, latents=None, prompt_embeds=None, negative_prompt_embeds=None,
-                 ip_adapter_image=None, output_type: Optional[str] = "pil", return_dict: bool = True,
+                 ip_adapter_image=None, ip_adapter_image_embeds=None, output_type: Optional[str] = "pil", return_dict: bool = True,
                  cross_attention_kwargs: Optional[Dict[str, Any]] = None,
                  controlnet_conditioning_scale: Union[float, List[float]] = 1.0, guess_mode: bool = False,
                  control_guidance_start: Union[float, List[float]] = 0.0, control_guidance_end: Union[float, List[float]] = 1.0,
@@ -1139,7 +1147,8 @@ class PromptDiffusionInpaintPipeline(PromptDiffusionPipeline):
                          num_inference_steps=num_inference_steps, timesteps=timesteps, guidance_scale=guidance_scale,
                          negative_prompt=negative_prompt, num_images_per_prompt=num_images_per_prompt, eta=eta, generator=generator,
                          latents=latents, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
-                         ip_adapter_image=ip_adapter_image, output_type=output_type, return_dict=return_dict,
+                         ip_adapter_image=ip_adapter_image, ip_adapter_image_embeds=ip_adapter_image_embeds, output_type=output_type,
+                         return_dict=return_dict,
                          cross_attention_kwargs=cross_attention_kwargs, controlnet_conditioning_scale=controlnet_conditioning_scale,
                          guess_mode=guess_mode, control_guidance_start=control_guidance_start,
                          control_guidance_end=control_guidance_end, clip_skip=clip_skip, callback_on_step_end=callback_on_step_end,

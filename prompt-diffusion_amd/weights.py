@@ -70,6 +70,8 @@ class ModelConfig:
     # pd_clip_vision_configure; safety_checker = True also registers StableDiffusionSafetyChecker's buffers (pd_safety_configure)
     clip_vision: Tuple = ()
     safety_checker: bool = False
+    # (num_tokens, embed_dim) of an IP-Adapter (pd_ip_adapter_configure), or () for none
+    ip_adapter: Tuple = ()
 
     @property
     def time_embed_dim(self) -> int:
