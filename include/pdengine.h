@@ -208,6 +208,36 @@ int pd_lora_add_ex(pd_engine* e, int32_t adapter, const char* name, const pd_lor
 int pd_set_freeu(pd_engine* e, float s1, float s2, float b1, float b2);
 int pd_get_freeu(pd_engine* e, float out[4]);
 
+/* Perturbed-attention guidance, PAG (Ahn et al., arXiv:2403.17377; diffusers' PAGMixin and PAGCFGIdentitySelfAttnProcessor2_0):
+ * engine state like pd_set_freeu, so pd_sample_args and pd_abi_version() are what they were.  While it is on, every evaluation that is
+ * followed by a guided eps (pd_ddim_sample, pd_unipc_sample, pd_lms_sample, pd_sample_step, pd_sample_eps_at, captured graphs, img2img
+ * and inpainting; not pd_eps, which forms none) carries `batch` more samples: perturbed sample j is conditional sample j -- latent,
+ * timestep, text context, example pair, query, the conditional ControlNet residuals (also in guess mode) and IP-Adapter tokens, FreeU,
+ * LoRA -- except that in the UNet transformer blocks of layer_mask the self-attention is the identity: attn1 = to_out(to_v(norm1(h))),
+ * bias included, no softmax.  The ControlNet is never perturbed.  The guided eps is, in fp32 with every operation rounded on its own,
+ *   (e_u + s (e_c - e_u)) + p_i (e_c - e_p)      with use_cfg,          e_c + p_i (e_c - e_p)      without,
+ * p_i = scale when adaptive_scale == 0, else max(scale - adaptive_scale (1000 - t_i), 0) with t_i the timestep of evaluation i (the
+ * literal is 1000), computed on the host in double and passed to the update kernel as fp32.
+ *   layer_mask  bit j = UNet transformer block j in the order of pd_ip_adapter_configure's blocks: the encoder's, then the decoder's,
+ *               then the middle block (SD1.5: 0-5, 6-14, 15).  Bits beyond the network's blocks are refused.
+ * scale == 0 or layer_mask == 0 means off: every call then launches exactly what it launches on an engine that never heard of PAG.
+ * Negative or non-finite values are refused, and so is switching it on while a sampling session is active (the session's workspace
+ * was sized at its begin; switching off is always possible).  A call that changes the state drops the captured graphs.
+ * The perturbed samples exist from the first masked block on (they carry the conditional samples' numbers before it): the batch grows
+ * from Bf to Bf + batch there, ordered [uncond ; cond ; perturbed].  Option "pag_fork" 0 (pd_set_option; not in pd_option_info's list)
+ * instead runs them as a full third of the UNet's batch from conv_in on -- the plain evaluation the fork is tested against.  A masked
+ * block runs layer by layer, never the fused 320-channel kernels.  Stats: "pag_launches" counts the identity launches and the second
+ * launch of everything the branch splits (its cross-attention, its image term, its skip concat, an unmasked block behind the fork),
+ * "pag_fork_block" is the block where the last evaluation forked (-1: none, or pag_fork 0).  "pag_launches" does not count what a masked
+ * 320-channel block adds by leaving the fused front / tail kernels for its per-layer path.  Option "pag_fork" is refused inside a session.
+ * The guided eps of an evaluation with the state off is computed exactly as before the state existed (the CFG multiply-add as one FMA).
+ * pd_get_pag: out[2] = {scale, adaptive_scale}, *layer_mask (may be NULL) as set; returns 0. */
+int pd_set_pag(pd_engine* e, float scale, float adaptive_scale, uint32_t layer_mask);
+int pd_get_pag(pd_engine* e, float out[2], uint32_t* layer_mask);
+/* The identity-attention kernel alone (pag.hip) on B samples of N tokens and C channels in the engine's storage type, `iters` launches
+ * between two events, and a device-to-device copy of the bytes it moves (B N C elements read and written); milliseconds per launch. */
+int pd_bench_pag_identity(pd_engine* e, int32_t B, int32_t N, int32_t C, int32_t iters, float* ms_kernel, float* ms_copy);
+
 /* Seeded noise.  The engine draws standard normals itself with the counter-based generator Philox4x32-10 (multipliers
  * 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85, ten rounds): one block maps (counter[4], key[2]) to four
  * uint32 r0..r3, and Box-Muller in fp32 turns them into four normals:

@@ -21,6 +21,9 @@
  *   pd_op_sd3_update  the update kernel of the SD3 img2img / inpainting / seeded loops (start state, CFG + Euler, blend)
  *   pd_op_ip_attention_add  IP-Adapter's image term, att + s softmax(q K_ip^T) V_ip (ip_attention.hip)
  *   pd_op_spatial_transformer_ip  one SpatialTransformer block of the UNet with that term
+ *   pd_op_pag_identity  perturbed-attention guidance's identity attention: the transposition of V^T into token rows (pag.hip)
+ *   pd_op_cfg_combine   the guidance of the update kernel alone: CFG and the perturbed-attention term (sampler_update.hip)
+ *   pd_op_spatial_transformer_pag  one SpatialTransformer block with its last samples perturbed
  */
 #ifndef PDENGINE_OPS_H
 #define PDENGINE_OPS_H
@@ -143,6 +146,20 @@ int pd_op_spatial_transformer_ctx(pd_engine* e, const char* prefix, const float*
  * 8, 16, 32, 40, 80, 160; 1 <= T <= 64; C a multiple of 8; scale 0: dh^-0.5. */
 int pd_op_ip_attention_add(pd_engine* e, const float* q2, const float* att, const float* k_ip, const float* v_ip, int B, int N, int C, int heads, int T,
                            int Bk, float scale, float s, float* out);
+/* launch_pag_identity: out [count, N, C] = vt[src : src + count] transposed, vt [Bs, C, N].  vt is rounded to the engine's storage type
+ * and laid out as the QKV GEMM writes V^T (rows of round_up(N, 8), pad columns holding a non-zero fill the kernel must not copy); the
+ * kernel is a bit copy, so values that type holds exactly come back exactly. */
+int pd_op_pag_identity(pd_engine* e, const float* vt, int Bs, int C, int N, int src, int count, float* out);
+/* cfg_update_kernel with do_update = 0, in the form an evaluation with pd_set_pag on launches it (every operation of the guidance rounded
+ * on its own; pag_scale 0 is a step at the adaptive scale's clamp -- an engine with the state off keeps the earlier CFG line, whose
+ * multiply-add the compiler contracts): out [B, HW, C] = the guided eps of eps [Bt, HW, C], Bt = (use_cfg ? 2 : 1) * B samples
+ * [uncond ;] cond and, when pag_scale != 0, B more, the perturbed branch.  eps is converted to eps_dtype (PD_DT_*) on the host first. */
+int pd_op_cfg_combine(pd_engine* e, const float* eps, int B, int HW, int C, int eps_dtype, int use_cfg, float cfg_scale, float pag_scale,
+                      float* out);
+/* pd_op_spatial_transformer_ctx with the last n_perturbed of the B samples perturbed from their own V (PagTerm without a fork): their
+ * self-attention is the identity, their cross-attention reads their own context in a launch of its own. */
+int pd_op_spatial_transformer_pag(pd_engine* e, const char* prefix, const float* x, const float* context, int B, int H, int W, int L,
+                                  int n_perturbed, float* y);
 /* pd_op_spatial_transformer_ctx of a UNet block with IP-Adapter's image term (pd_ip_adapter_configure, adapter weights loaded): tokens
  * [B, T, context_dim] go through the block's to_k_ip / to_v_ip and the term enters at the block's current scale (pd_ip_adapter_set_scale),
  * through the code path of a sampling step.  At scale 0 the call is pd_op_spatial_transformer_ctx, fused tail included. */

@@ -1167,16 +1167,29 @@ int pd_engine::resblock(const ResW& r, const Act& x, Act& out, const float* embr
 //
 // ip (IP-Adapter, ip_adapter.cpp): the image term is added to the text cross-attention's output before attn2.to_out.  The fused tail
 // cannot take it, so a block with a term runs the per-layer path.
-int pd_engine::transformer(const STW& s, const Act& x, Act& out, const KVSlot& kv, int out_B, const IpTerm* ip) {
+//
+// pag (perturbed-attention guidance, PagTerm): GroupNorm, proj_in, norm1 and the QKV GEMM run on the samples x holds, self-attention on
+// the first Ba of them; the last pag->n rows of att are the transposition of V (pag.hip) -- of x's own last samples, or, at the fork,
+// of samples [src, src + n), whose h and residual rows the new samples copy.  From attn1.to_out on the batch is Ba + n; the
+// cross-attention of the last n reads the context of samples [src, src + n) in a launch of its own.  Per-layer path only.
+int pd_engine::transformer(const STW& s, const Act& x, Act& out, const KVSlot& kv, int out_B, const IpTerm* ip, const PagTerm* pag, bool out_given) {
     int B = x.B;
     const int H = x.H, W = x.W, C = s.C, N = H * W;
     if (out_B <= 0) out_B = B;
     if (out_B % B) { pd_set_error("internal: transformer output batch %d over %d shared samples", out_B, B); return 1; }
     const int reps = out_B / B;
-    out = new_act(out_B, H, W, C, S);
+    const int n_p = pag ? pag->n : 0;
+    const int Ba = pag && !pag->fork ? B - n_p : B;   // samples whose self-attention runs
+    if (pag && (reps != 1 || n_p < 1 || Ba < 1 || pag->src < 0 || pag->src + n_p > Ba + (pag->fork ? 0 : n_p))) {
+        pd_set_error("internal: perturbed block of %d samples (%d perturbed from %d, %d shared)", B, n_p, pag->src, reps);
+        return 1;
+    }
+    if (pag) out_B = Ba + n_p;
+    if (!out_given) out = new_act(out_B, H, W, C, S);
+    else if (out.B != out_B || out.H != H || out.W != W || out.C != C || out.dt != S) { pd_set_error("internal: transformer output tensor of another shape"); return 1; }
     const size_t mk = arena.mark();
     const int L = kv.L > 0 ? kv.L : cfg.context_len, lpad = round_up(L, 8);   // context keys of this call
-    const bool fused = !ip && st_tail_on(s, N, L) && s.tail_w && s.front_w && kv.P;
+    const bool fused = !ip && !pag && st_tail_on(s, N, L) && s.tail_w && s.front_w && kv.P;
     const int npad = round_up(N, 8);
     Act h, qk, vt, ln;
     LnStats st0, st1;
@@ -1212,7 +1225,7 @@ int pd_engine::transformer(const STW& s, const Act& x, Act& out, const KVSlot& k
     // (fold_layernorms): one partial per 80-column wave range of the narrowest tile
     if (fuse) {
         st0.cap_parts = st1.cap_parts = ((C + 159) / 160) * 2;
-        const size_t cap = (size_t)B * N * (size_t)st0.cap_parts * 2 * sizeof(float);
+        const size_t cap = (size_t)std::max(B, out_B) * N * (size_t)st0.cap_parts * 2 * sizeof(float);
         st0.stats = reinterpret_cast<float*>(arena.alloc(cap));
         st1.stats = reinterpret_cast<float*>(arena.alloc(cap));
     }
@@ -1227,9 +1240,19 @@ int pd_engine::transformer(const STW& s, const Act& x, Act& out, const KVSlot& k
     vt = new_act(B, C, 1, npad, T);
     PD_TRY(gemm(s.qkv, fuse ? h : ln, qk, {.VT = vt.p, .vt_begin = 2 * C, .vt_ld = npad, .ln_in = fuse ? &st0 : nullptr}));
     }
-    Act att = new_act(B, H, W, C, T);
+    Act att = new_act(pag ? out_B : B, H, W, C, T);
     const size_t eb = dt_size(T);
-    PD_TRY(attention(qk.p, 2 * C, reinterpret_cast<char*>(qk.p) + (size_t)C * eb, 2 * C, vt.p, npad, att.p, C, B, N, N, C));
+    PD_TRY(attention(qk.p, 2 * C, reinterpret_cast<char*>(qk.p) + (size_t)C * eb, 2 * C, vt.p, npad, att.p, C, Ba, N, N, C));
+    Act xr = x;   // the block's residual at the output batch
+    if (pag) {
+        if (!arena.dry) ++pag_launches;
+        PD_LAUNCH(this, launch_pag_identity(vt.p, reinterpret_cast<char*>(att.p) + (size_t)Ba * N * C * eb, (int)eb, pag->fork ? pag->src : Ba, n_p, N, C, npad, stream),
+                  "perturbed-attention identity launch failed (N %d, C %d)", N, C);
+        if (pag->fork) {
+            PD_TRY(extend_act(h, pag->src, n_p, h));
+            PD_TRY(extend_act(x, pag->src, n_p, xr));
+        }
+    }
     if (fused) {
         // everything after the self-attention product in one kernel (st_tail.hip): no h1 / q2 / h2 / norm3 / GEGLU / h3 round trips
         if (!arena.dry) {
@@ -1248,13 +1271,14 @@ int pd_engine::transformer(const STW& s, const Act& x, Act& out, const KVSlot& k
         arena.release(mk);
         return 0;
     }
-    Act h1 = new_act(B, H, W, C, S);
+    const int Bw = pag ? out_B : B;   // (the perturbed branch joins the batch at attn1.to_out)
+    Act h1 = new_act(Bw, H, W, C, S);
     PD_TRY(gemm(s.out1, att, h1, {.R = &h, .ln_out = fuse ? &st1 : nullptr}));
     // cross-attention against the hoisted context K / V^T
+    if (!fuse && Bw != B) ln = new_act(Bw, H, W, C, T);
     if (!fuse) PD_TRY(layernorm(h1, ln, s.ln_g[1], s.ln_b[1]));
-    Act q2 = new_act(B, H, W, C, T);
+    Act q2 = new_act(Bw, H, W, C, T);
     PD_TRY(gemm(s.q2, fuse ? h1 : ln, q2, {.ln_in = fuse ? &st1 : nullptr}));
-    Act xr = x;   // the block's residual at the output batch
     if (reps > 1) {
         // the shared queries meet each half's own context keys: one launch per half; from here on the batch is out_B
         att = new_act(out_B, H, W, C, T);
@@ -1265,6 +1289,28 @@ int pd_engine::transformer(const STW& s, const Act& x, Act& out, const KVSlot& k
         if (ip) PD_TRY(ip_image_term(q2.p, att.p, *ip, out_B, N, C, reps));
         PD_TRY(repeat_act(h1, reps, h1));
         PD_TRY(repeat_act(x, reps, xr));
+    } else if (pag) {
+        // the perturbed rows against the context of the samples they were forked from: a launch of their own, like a half of the shared front
+        const size_t tail = (size_t)Ba * N * C * eb;
+        const KVSlot kp = kv_from(kv, C, pag->src);
+        PD_TRY(attention(q2.p, C, kv.K, C, kv.VT, lpad, att.p, C, Ba, N, L, C));
+        if (!arena.dry) ++pag_launches;
+        PD_TRY(attention(reinterpret_cast<char*>(q2.p) + tail, C, kp.K, C, kp.VT, lpad, reinterpret_cast<char*>(att.p) + tail, C, n_p, N, L, C));
+        if (ip) {
+            // ... and the conditional image tokens (the last run of the term)
+            IpTerm ipp = *ip;
+            ipp.nseg = 1;
+            ipp.K[0] = ip->K[ip->nseg - 1];
+            ipp.V[0] = ip->V[ip->nseg - 1];
+            if (ip->nseg == 1 && ip->kv_bs) {   // one run over samples with their own tokens: the perturbed rows read those of [src, src + n)
+                ipp.K[0] = reinterpret_cast<const char*>(ipp.K[0]) + (size_t)pag->src * ip->kv_bs * eb;
+                ipp.V[0] = reinterpret_cast<const char*>(ipp.V[0]) + (size_t)pag->src * ip->kv_bs * eb;
+            }
+            PD_TRY(ip_image_term(q2.p, att.p, *ip, Ba, N, C, 1));
+            const long long l0 = ip_launches;
+            PD_TRY(ip_image_term(reinterpret_cast<char*>(q2.p) + tail, reinterpret_cast<char*>(att.p) + tail, ipp, n_p, N, C, 1));
+            pag_launches += ip_launches - l0;
+        }
     } else {
         PD_TRY(attention(q2.p, C, kv.K, C, kv.VT, lpad, att.p, C, B, N, L, C));
         if (ip) PD_TRY(ip_image_term(q2.p, att.p, *ip, out_B, N, C, 1));
@@ -1273,7 +1319,7 @@ int pd_engine::transformer(const STW& s, const Act& x, Act& out, const KVSlot& k
     Act h2 = new_act(B, H, W, C, S);
     PD_TRY(gemm(s.out2, att, h2, {.R = &h1}));
     // GEGLU feed-forward (norm3 as a kernel: see fold_layernorms)
-    if (fuse || reps > 1) ln = new_act(B, H, W, C, T);
+    if (fuse || reps > 1 || pag) ln = new_act(B, H, W, C, T);
     PD_TRY(layernorm(h2, ln, s.ln_g[2], s.ln_b[2]));
     Act g = new_act(B, H, W, 4 * C, T);
     PD_TRY(gemm(s.ff1, ln, g));
@@ -1294,6 +1340,30 @@ int pd_engine::repeat_act(const Act& src, int reps, Act& dst) {
     }
     dst = d;
     return 0;
+}
+
+int pd_engine::extend_act(const Act& src, int first, int count, Act& dst) {
+    Act d = new_act(src.B + count, src.H, src.W, src.C, src.dt);
+    if (!arena.dry) {
+        PD_TRY(check_arena());
+        const size_t per = src.bytes() / (size_t)src.B;
+        HIP_OK(hipMemcpyAsync(d.p, src.p, src.bytes(), hipMemcpyDeviceToDevice, stream));
+        HIP_OK(hipMemcpyAsync(reinterpret_cast<char*>(d.p) + src.bytes(), reinterpret_cast<const char*>(src.p) + (size_t)first * per, (size_t)count * per,
+                              hipMemcpyDeviceToDevice, stream));
+    }
+    dst = d;
+    return 0;
+}
+
+KVSlot pd_engine::kv_from(const KVSlot& k, int C, int first) const {
+    KVSlot r = k;
+    if (!first) return r;
+    const size_t eb = dt_size(T);
+    const int L = k.L > 0 ? k.L : cfg.context_len, lpad = round_up(L, 8);
+    r.K = reinterpret_cast<char*>(k.K) + (size_t)first * L * C * eb;
+    r.VT = reinterpret_cast<char*>(k.VT) + (size_t)first * C * lpad * eb;
+    if (k.P) r.P = reinterpret_cast<char*>(k.P) + st_tail_kv_bytes(first, L);
+    return r;
 }
 
 // ------------------------------------------------------------------------------------ networks
@@ -1379,31 +1449,76 @@ int pd_engine::run_unet(const Act& x_in_full, int emb_row, int emb_stride, bool 
     const int Bf = x_in_full.B;
     Act x_in = x_in_full;
     if (ses.share_u) x_in.B = Bf / 2;   // shared CFG front, as in run_controlnet; the skip tensors of the front stay at half batch
+    // Perturbed-attention guidance (pd_set_pag): nP more samples, the conditional branch with the self-attention of the masked blocks
+    // replaced by the identity.  Until the first masked block they would carry the conditional samples' numbers, so they begin there
+    // (PagTerm::fork) and the batch is [u ; c ; p] = Bf + nP from then on; with option pag_fork 0 they begin behind conv_in.  Tensors
+    // from before the fork (skips, control residuals, context K / V^T, time embedding) keep their batch: the perturbed rows read the
+    // conditional ones, from sample `csrc` on.
+    const int nP = ses.pag_B, csrc = ses.a.use_cfg ? Bf - nP : 0;
+    bool forked = false;
+    int blk = 0;   // index of the next transformer block in pd_set_pag's order
+    pag_fork_block = -1;
+    auto st_block = [&](const STW& st, Act& o, int out_B) -> int {
+        const int j = blk++;
+        IpTerm it;
+        const bool has_ip = ip_term(st, Bf, ses.a.use_cfg != 0, it);
+        const KVSlot& kv = ses.kv_u[st.kv_slot];
+        const bool pert = nP && ((pag_mask >> j) & 1u);
+        Act o2;
+        if (!forked && !pert) {
+            PD_TRY(transformer(st, o, o2, kv, out_B, has_ip ? &it : nullptr));
+        } else if (pert) {
+            if (o.B < Bf) PD_TRY(repeat_act(o, Bf / o.B, o));   // a shared CFG front ends in front of a perturbed block
+            const PagTerm pt{nP, !forked, csrc};
+            if (!forked) pag_fork_block = j;
+            forked = true;
+            PD_TRY(transformer(st, o, o2, kv, 0, has_ip ? &it : nullptr, &pt));
+        } else {
+            // an unperturbed block behind the fork: the Bf samples as ever, then the perturbed ones against the conditional context and tokens
+            o2 = new_act(o.B, o.H, o.W, st.C, S);
+            Act ya = batch_view(o2, 0, Bf), yb = batch_view(o2, Bf, nP);
+            PD_TRY(transformer(st, batch_view(o, 0, Bf), ya, kv, 0, has_ip ? &it : nullptr, nullptr, true));
+            IpTerm ipp = it;
+            ipp.nseg = 1;
+            ipp.K[0] = it.K[it.nseg - 1];
+            ipp.V[0] = it.V[it.nseg - 1];
+            const long long l0 = launches;
+            PD_TRY(transformer(st, batch_view(o, Bf, nP), yb, kv_from(kv, st.C, csrc), 0, has_ip ? &ipp : nullptr, nullptr, true));
+            pag_launches += launches - l0;
+        }
+        o = o2;
+        return 0;
+    };
     for (size_t i = 0; i < n.enc.size(); ++i) {
         EncBlock& b = n.enc[i];
         Act o;
         if (b.kind == 0) {
             o = new_act(x_in.B, x_in.H, x_in.W, b.cout, S);
             PD_TRY(conv(b.conv, x_in, o));
+            if (nP && !opt.pag_fork) {   // the plain evaluation: a full third of the batch from here on
+                PD_TRY(extend_act(o, csrc, nP, o));
+                forked = true;
+            }
         } else if (b.kind == 2) {
             o = new_act(h.B, h.H / 2, h.W / 2, b.cout, S);
             PD_TRY(conv(b.conv, h, o));
         } else {
             PD_TRY(resblock(b.res, h, o, emb_ptr(ses.emb_u, b.res, emb_row), emb_stride ? b.res.cout : 0));
-            if (b.attn) {
-                Act o2;
-                IpTerm it;
-                PD_TRY(transformer(b.st, o, o2, ses.kv_u[b.st.kv_slot], Bf, ip_term(b.st, Bf, ses.a.use_cfg != 0, it) ? &it : nullptr));
-                o = o2;
-            }
+            if (b.attn) PD_TRY(st_block(b.st, o, forked ? 0 : Bf));
         }
         h = o;
         hs.push_back(h);
     }
     Act m0, m1, m2;
     PD_TRY(resblock(n.mid0, h, m0, emb_ptr(ses.emb_u, n.mid0, emb_row), emb_stride ? n.mid0.cout : 0));
-    IpTerm it_mid;
-    PD_TRY(transformer(n.mid1, m0, m1, ses.kv_u[n.mid1.kv_slot], Bf, ip_term(n.mid1, Bf, ses.a.use_cfg != 0, it_mid) ? &it_mid : nullptr));
+    {
+        // (the middle block is the last of pd_set_pag's order, behind the decoder's)
+        const int enc_blocks = blk;
+        for (const DecBlock& d : n.dec) blk += d.attn ? 1 : 0;
+        m1 = m0;
+        PD_TRY(st_block(n.mid1, m1, forked ? 0 : Bf));
+        blk = enc_blocks;
+    }
     PD_TRY(resblock(n.mid2, m1, m2, emb_ptr(ses.emb_u, n.mid2, emb_row), emb_stride ? n.mid2.cout : 0));
     h = m2;
     PD_TRY(join_controlnet());   // the decoder is the first consumer of the control tensors
@@ -1419,20 +1534,32 @@ int pd_engine::run_unet(const Act& x_in_full, int emb_row, int emb_stride, bool 
         // FreeU (pd_set_freeu): diffusers' up_blocks[0] / [1] are the first two stages of num_res_blocks + 1 decoder blocks
         const int stage = (int)i / (cfg.num_res_blocks + 1);
         const bool fu = stage < 2 && freeu_on();
-        PD_LAUNCH(this,
-                  fu ? launch_freeu_concat(h.p, a_add ? a_add->p : nullptr, skip.p, b_add ? b_add->p : nullptr, cat.p, S, h.B, h.H, h.W, h.C, skip.C,
-                                           freeu[stage], freeu[2 + stage], stream, skip.rows(), b_add ? b_add->rows() : 0)
-                     : launch_concat_add(h.p, a_add ? a_add->p : nullptr, skip.p, b_add ? b_add->p : nullptr, cat.p, S, h.rows(), h.C, skip.C, stream,
-                                         skip.rows(), b_add ? b_add->rows() : 0),
-                  fu ? "FreeU concat launch failed" : "concat launch failed");
+        auto concat = [&](const Act& hv, const Act* av, const Act& sv, const Act* bv, const Act& cv) -> int {
+            PD_LAUNCH(this,
+                      fu ? launch_freeu_concat(hv.p, av ? av->p : nullptr, sv.p, bv ? bv->p : nullptr, cv.p, S, hv.B, hv.H, hv.W, hv.C, sv.C, freeu[stage],
+                                               freeu[2 + stage], stream, sv.rows(), bv ? bv->rows() : 0)
+                         : launch_concat_add(hv.p, av ? av->p : nullptr, sv.p, bv ? bv->p : nullptr, cv.p, S, hv.rows(), hv.C, sv.C, stream, sv.rows(),
+                                             bv ? bv->rows() : 0),
+                      fu ? "FreeU concat launch failed" : "concat launch failed");
+            return 0;
+        };
+        if (h.B > Bf) {
+            // behind the fork of a perturbed branch: the first Bf samples as ever; perturbed sample i reads conditional sample i of every
+            // tensor made before the fork (a Bf-sample source: from sample csrc on; a shared-front source of nP samples: all of it)
+            auto head = [&](const Act& t) { return t.B > Bf ? batch_view(t, 0, Bf) : t; };
+            auto tail = [&](const Act& t) { return t.B > Bf ? batch_view(t, Bf, nP) : t.B == Bf ? batch_view(t, csrc, nP) : t; };
+            Act ah, at, bh, bt;
+            if (a_add) { ah = head(*a_add); at = tail(*a_add); }
+            if (b_add) { bh = head(*b_add); bt = tail(*b_add); }
+            PD_TRY(concat(head(h), a_add ? &ah : nullptr, head(skip), b_add ? &bh : nullptr, head(cat)));
+            PD_TRY(concat(tail(h), a_add ? &at : nullptr, tail(skip), b_add ? &bt : nullptr, tail(cat)));
+            if (!arena.dry) ++pag_launches;
+        } else {
+            PD_TRY(concat(h, a_add, skip, b_add, cat));
+        }
         Act o;
         PD_TRY(resblock(b.res, cat, o, emb_ptr(ses.emb_u, b.res, emb_row), emb_stride ? b.res.cout : 0));
-        if (b.attn) {
-            Act o2;
-            IpTerm it;
-            PD_TRY(transformer(b.st, o, o2, ses.kv_u[b.st.kv_slot], 0, ip_term(b.st, Bf, ses.a.use_cfg != 0, it) ? &it : nullptr));
-            o = o2;
-        }
+        if (b.attn) PD_TRY(st_block(b.st, o, 0));
         if (b.up) {
             Act o3 = new_act(o.B, o.H * 2, o.W * 2, o.C, S);
             PD_TRY(conv(b.upconv, o, o3, {.ups = 1}));  // Upsample: nearest x2 then conv, :115-117
@@ -1440,6 +1567,7 @@ int pd_engine::run_unet(const Act& x_in_full, int emb_row, int emb_stride, bool 
         }
         h = o;
     }
+    if (h.B != Bf + nP) { pd_set_error("internal: the UNet ends at batch %d, %d + %d perturbed expected", h.B, Bf, nP); return 1; }
     eps = new_act(h.B, h.H, h.W, round_up(cfg.out_channels, 4), DT_F32);
     PD_TRY(conv_gn(n.outconv, h, eps, n.out_g, n.out_b, 1e-5f, true));
     return 0;
@@ -1486,6 +1614,10 @@ int pd_engine::forward_eps(int emb_row, int emb_stride, const float* scales, Act
     ses.share_u = share;
     ses.share_c = share && ses.hint_shared && !a.guess_mode;
     ses.cn_cond_only = opt.cfg_share && a.guess_mode && a.use_cfg && emb_stride == 0 && Bf % 2 == 0;
+    // perturbed-attention guidance wherever a guided eps follows (one time-embedding row for the whole batch: not pd_eps); its plain form
+    // (option pag_fork 0) runs the UNet unshared
+    ses.pag_B = pag_on() && emb_stride == 0 ? a.batch : 0;
+    if (ses.pag_B && !opt.pag_fork) ses.share_u = false;
     // the 13 control tensors outlive the ControlNet pass
     int hh = a.h, ww = a.w;
     bool front = ses.share_c;

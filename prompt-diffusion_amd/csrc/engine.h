@@ -322,6 +322,16 @@ struct IpTerm {
     float s = 0.f;
 };
 
+// Perturbed-attention guidance (pd_set_pag) in one transformer block: the last n samples of the block's output are the perturbed
+// branch, whose self-attention is the identity (attn1 = to_out(V), pag.hip).  fork: x does not hold them yet -- they begin here as
+// copies of x's samples [src, src + n), and take those samples' V; otherwise they are x's own last n samples.  Their cross-attention
+// (and image term) reads the context of samples [src, src + n).
+struct PagTerm {
+    int n = 0;
+    bool fork = false;
+    int src = 0;
+};
+
 // SD3's T5 encoder stack (sd3_text.cpp): no biases anywhere, RMSNorm weights only, wi = [wi_1 | wi_0] packed like a GEGLU matrix
 struct T5LayerW {
     float *ln1 = nullptr, *ln2 = nullptr;
@@ -505,6 +515,7 @@ struct Session {
     // shared CFG front (pd_engine::forward_eps): both halves of the batch see the same guided_hint; this evaluation runs the UNet's /
     // the ControlNet's layers in front of the first cross-attention once for both halves
     bool hint_shared = false, share_u = false, share_c = false;
+    int pag_B = 0;               // perturbed-attention guidance: samples of the perturbed branch in this evaluation (forward_eps); 0: none
     bool cn_cond_only = false;   // guess mode under guidance: this evaluation runs the ControlNet on the conditional half only (run_controlnet)
     // solver of step(): DDIM, or the fused UniPC loop (pd_sample_begin_unipc / pd_unipc_sample)
     int solver = 0;                  // SOLVER_DDIM / SOLVER_UNIPC / SOLVER_LMS
@@ -571,6 +582,14 @@ struct pd_engine {
     // FreeU (pd_set_freeu): {s1, s2, b1, b2}, all zero when off; per engine, read by run_unet at every decoder block
     float freeu[4] = {0.f, 0.f, 0.f, 0.f};
     bool freeu_on() const { return freeu[0] != 0.f && freeu[1] != 0.f && freeu[2] != 0.f && freeu[3] != 0.f; }
+    // Perturbed-attention guidance (pd_set_pag): {scale, adaptive scale} and the mask of perturbed UNet transformer blocks (bit j = block
+    // j of IpAdapterW's order: encoder, decoder, middle); per engine, read by forward_eps / run_unet and by the update launch
+    float pag[2] = {0.f, 0.f};
+    uint32_t pag_mask = 0;
+    bool pag_on() const { return pag[0] != 0.f && pag_mask != 0; }
+    float pag_scale_at(double t) const;   // p_i of an evaluation at model time t (the adaptive rule, in double), 0 when off
+    long long pag_launches = 0;           // stat "pag_launches": the identity launches and the second launch of everything split for the branch
+    int pag_fork_block = -1;              // stat "pag_fork_block": the block where the last evaluation forked; -1: none, or option pag_fork 0
     // seeded noise (pd_set_rng; addressing in include/pdengine.h): {seed_lo, seed_hi, base_lo, base_hi} on the device, read by the
     // update / start / posterior / fill kernels, rewritten by a copy ordered on `stream` (captured graphs see the new values)
     uint32_t* rng_dev = nullptr;
@@ -836,7 +855,12 @@ struct pd_engine {
     int groupnorm(const Act& x, Act& y, const float* g, const float* b, float eps, bool silu, const SlabDefer* from_slabs = nullptr);
     int layernorm(const Act& x, Act& y, const float* g, const float* b, float eps = 1e-5f);
     int resblock(const ResW& r, const Act& x, Act& out, const float* embrow, int emb_stride);
-    int transformer(const STW& s, const Act& x, Act& out, const KVSlot& kv, int out_B = 0, const IpTerm* ip = nullptr);
+    // out_given: `out` is the caller's tensor (a batch view of a larger one) instead of a new allocation
+    int transformer(const STW& s, const Act& x, Act& out, const KVSlot& kv, int out_B = 0, const IpTerm* ip = nullptr, const PagTerm* pag = nullptr,
+                    bool out_given = false);
+    // src and a copy of its samples [first, first + count) behind them
+    int extend_act(const Act& src, int first, int count, Act& dst);
+    KVSlot kv_from(const KVSlot& k, int C, int first) const;   // the hoisted context K / V^T from sample `first` on
     // IP-Adapter (ip_adapter.cpp)
     IpAdapterW ip;
     long long ip_launches = 0;   // stat "ip_launches": image-term launches so far
@@ -862,7 +886,7 @@ struct pd_engine {
     int compute_emb(NetW& net, std::vector<float*>& tabs, const int64_t* t, int n, int row0, const double* tf = nullptr);   // tf: fractional times instead of t
     int begin(const pd_sample_args* a, bool want_per_step, const pd_unipc_args* u = nullptr, const pd_lms_args* l = nullptr);
     int step(int i);   // eps, then the solver's update launch (step_ddim / step_unipc / step_lms), then the optional per-step copy
-    UpdateState update_state(const Act& eps) const;
+    UpdateState update_state(const Act& eps, double t) const;   // t: the model time of the evaluation (the adaptive PAG scale)
     int step_ddim(int i, const UpdateState& u, const BlendArgs* bl);
     int step_unipc(int i, const UpdateState& u, const BlendArgs* bl);
     int step_lms(int i, const UpdateState& u, const BlendArgs* bl);

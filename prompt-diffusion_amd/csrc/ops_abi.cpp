@@ -722,6 +722,94 @@ int pd_op_ip_attention_add(pd_engine* e, const float* q2, const float* att, cons
     return 0;
 }
 
+// launch_pag_identity on host data: vt [Bs, C, N] -> out [count, N, C] = samples [src, src + count) transposed, through the engine's
+// storage type and the V^T layout of the QKV GEMM (row stride round_up(N, 8)); the pad columns hold 1.0, which a correct kernel never copies
+int pd_op_pag_identity(pd_engine* e, const float* vt, int Bs, int C, int N, int src, int count, float* out) {
+    if (!e || !vt || !out) { pd_set_error("null argument"); return 1; }
+    if (Bs < 1 || C < 1 || N < 1 || src < 0 || count < 1 || src + count > Bs) {
+        pd_set_error("pd_op_pag_identity: need Bs, C, N >= 1 and 0 <= src, src + count <= Bs (got Bs %d C %d N %d src %d count %d)", Bs, C, N, src, count);
+        return 1;
+    }
+    HIP_OK(hipSetDevice(e->device));
+    const int npad = round_up(N, 8);
+    const size_t eb = dt_size(e->T), nin = (size_t)Bs * C * npad, nout = (size_t)count * N * C;
+    std::vector<float> host(nin, 1.0f);
+    for (size_t r = 0; r < (size_t)Bs * C; ++r) std::memcpy(&host[r * npad], vt + r * N, (size_t)N * sizeof(float));
+    DevBuf fin(nin * 4), din(nin * eb), dout(nout * eb), fout(nout * 4);
+    if (!fin.p || !din.p || !dout.p || !fout.p) { pd_set_error("allocation failed"); return 1; }
+    HIP_OK(hipMemcpy(fin.p, host.data(), nin * 4, hipMemcpyHostToDevice));
+    if (launch_cast_rows(reinterpret_cast<const float*>(fin.p), din.p, e->T, (long long)Bs * C, npad, npad, e->stream)) return 1;
+    ++e->launches;
+    ++e->pag_launches;
+    if (launch_pag_identity(din.p, dout.p, (int)eb, src, count, N, C, npad, e->stream)) { pd_set_error("pd_op_pag_identity: launch failed (N %d, C %d)", N, C); return 1; }
+    if (launch_nhwc_to_nchw(dout.p, e->T, reinterpret_cast<float*>(fout.p), 1, 1, 1, (int)nout, 1, 1.f, e->stream)) return 1;
+    HIP_OK(hipStreamSynchronize(e->stream));
+    HIP_OK(hipMemcpy(out, fout.p, nout * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int pd_bench_pag_identity(pd_engine* e, int32_t B, int32_t N, int32_t C, int32_t iters, float* ms_kernel, float* ms_copy) {
+    if (!e || !ms_kernel || !ms_copy || iters < 1 || B < 1 || N < 1 || C < 1) { pd_set_error("pd_bench_pag_identity: bad argument"); return 1; }
+    HIP_OK(hipSetDevice(e->device));
+    const int npad = round_up(N, 8);
+    const size_t eb = dt_size(e->T), nin = (size_t)B * C * npad, nout = (size_t)B * N * C;
+    DevBuf vt(nin * eb), att(nout * eb), src(nout * eb), dst(nout * eb);
+    if (!vt.p || !att.p || !src.p || !dst.p) { pd_set_error("pd_bench_pag_identity: allocation failed"); return 1; }
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIP_OK(hipEventCreate(&e0));
+    HIP_OK(hipEventCreate(&e1));
+    int rc = 0;
+    float t = 0.f;
+    for (int i = 0; i < 3 && !rc; ++i) rc = launch_pag_identity(vt.p, att.p, (int)eb, 0, B, N, C, npad, e->stream);
+    hipEventRecord(e0, e->stream);
+    for (int i = 0; i < iters && !rc; ++i) rc = launch_pag_identity(vt.p, att.p, (int)eb, 0, B, N, C, npad, e->stream);
+    hipEventRecord(e1, e->stream);
+    hipEventSynchronize(e1);
+    hipEventElapsedTime(&t, e0, e1);
+    *ms_kernel = t / (float)iters;
+    for (int i = 0; i < 3; ++i) hipMemcpyAsync(dst.p, src.p, nout * eb, hipMemcpyDeviceToDevice, e->stream);
+    hipEventRecord(e0, e->stream);
+    for (int i = 0; i < iters; ++i) hipMemcpyAsync(dst.p, src.p, nout * eb, hipMemcpyDeviceToDevice, e->stream);
+    hipEventRecord(e1, e->stream);
+    hipEventSynchronize(e1);
+    hipEventElapsedTime(&t, e0, e1);
+    *ms_copy = t / (float)iters;
+    hipEventDestroy(e0);
+    hipEventDestroy(e1);
+    if (rc) { pd_set_error("pd_bench_pag_identity: launch failed (N %d, C %d)", N, C); return 1; }
+    return 0;
+}
+
+// The guidance of cfg_update_kernel alone (do_update 0) as an evaluation with perturbed-attention guidance on runs it (UpdateState::pag;
+// pag_scale 0 is then a step at the adaptive scale's clamp): eps [Bt, HW, C] in eps_dtype -> out [B, HW, C] fp32
+int pd_op_cfg_combine(pd_engine* e, const float* eps, int B, int HW, int C, int eps_dtype, int use_cfg, float cfg_scale, float pag_scale,
+                      float* out) {
+    if (!e || !eps || !out) { pd_set_error("null argument"); return 1; }
+    if (B < 1 || HW < 1 || C < 1 || (eps_dtype != PD_DT_F32 && eps_dtype != PD_DT_F16 && eps_dtype != PD_DT_BF16)) {
+        pd_set_error("pd_op_cfg_combine: need B, HW, C >= 1 and eps_dtype one of PD_DT_F32 / F16 / BF16 (got %d, %d, %d, %d)", B, HW, C, eps_dtype);
+        return 1;
+    }
+    HIP_OK(hipSetDevice(e->device));
+    const int Bf = use_cfg ? 2 * B : B, Bt = Bf + (pag_scale != 0.f ? B : 0);
+    const int dt = eps_dtype == PD_DT_F32 ? DT_F32 : eps_dtype == PD_DT_F16 ? DT_F16 : DT_BF16;
+    const size_t nin = (size_t)Bt * HW * C, nout = (size_t)B * HW * C;
+    DevBuf fin(nin * 4), din(nin * dt_size(dt)), dout(nout * 4);
+    if (!fin.p || !din.p || !dout.p) { pd_set_error("allocation failed"); return 1; }
+    HIP_OK(hipMemcpy(fin.p, eps, nin * 4, hipMemcpyHostToDevice));
+    if (launch_cast_rows(reinterpret_cast<const float*>(fin.p), din.p, dt, (long long)Bt * HW, C, C, e->stream)) return 1;
+    UpdateState u{din.p, dt, C, nullptr, nullptr, reinterpret_cast<float*>(dout.p), nullptr, B, HW, C, C, use_cfg ? 1 : 0};
+    u.pag = 1;      // the guidance of an evaluation with the state on, whatever the step's scale
+    u.pag_scale = pag_scale;
+    u.pag_off = Bf;
+    DdimCoef k{};
+    k.cfg_scale = cfg_scale;
+    ++e->launches;
+    if (launch_cfg_ddim(u, k, nullptr, 1.f, 0, nullptr, e->stream)) { pd_set_error("pd_op_cfg_combine: launch failed"); return 1; }
+    HIP_OK(hipStreamSynchronize(e->stream));
+    HIP_OK(hipMemcpy(out, dout.p, nout * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // One whole SpatialTransformer block of the engine's own networks (GroupNorm eps 1e-6, proj_in, BasicTransformerBlock, proj_out, + x;
 // attention.py:321-340 and :271-275) with the weights loaded under `prefix` (e.g. "model.diffusion_model.input_blocks.1.1.") on
 // x [B, C, H, W] and context [B, context_len, context_dim], through exactly the code path a sampling step takes -- including the fused
@@ -733,7 +821,13 @@ int pd_op_spatial_transformer(pd_engine* e, const char* prefix, const float* x, 
 
 // ... on a context of any length: [B, L, context_dim], 1 <= L <= PD_MAX_CONTEXT_LEN
 static int spatial_transformer_hook(pd_engine* e, const char* prefix, const float* x, const float* ctx, const float* tokens, int B, int H, int W, int L,
-                                    int T, float* y);
+                                    int T, float* y, int n_perturbed = 0);
+// ... with the last n_perturbed samples perturbed (perturbed-attention guidance, PagTerm): identity self-attention from their own V
+int pd_op_spatial_transformer_pag(pd_engine* e, const char* prefix, const float* x, const float* ctx, int B, int H, int W, int L, int n_perturbed,
+                                  float* y) {
+    if (n_perturbed < 1 || n_perturbed >= B) { pd_set_error("pd_op_spatial_transformer_pag: n_perturbed %d outside 1 .. B - 1 = %d", n_perturbed, B - 1); return 1; }
+    return spatial_transformer_hook(e, prefix, x, ctx, nullptr, B, H, W, L, 0, y, n_perturbed);
+}
 int pd_op_spatial_transformer_ctx(pd_engine* e, const char* prefix, const float* x, const float* ctx, int B, int H, int W, int L, float* y) {
     return spatial_transformer_hook(e, prefix, x, ctx, nullptr, B, H, W, L, 0, y);
 }
@@ -747,7 +841,7 @@ int pd_op_spatial_transformer_ip(pd_engine* e, const char* prefix, const float* 
 }
 
 static int spatial_transformer_hook(pd_engine* e, const char* prefix, const float* x, const float* ctx, const float* tokens, int B, int H, int W, int L,
-                                    int T, float* y) {
+                                    int T, float* y, int n_perturbed) {
     if (!e || !prefix || !x || !ctx || !y) { pd_set_error("null argument"); return 1; }
     if (L < 1 || L > PD_MAX_CONTEXT_LEN) { pd_set_error("context length %d out of range 1 .. %d", L, PD_MAX_CONTEXT_LEN); return 1; }
     HIP_OK(hipSetDevice(e->device));
@@ -817,7 +911,8 @@ static int spatial_transformer_hook(pd_engine* e, const char* prefix, const floa
         }
         Act a, o;
         a.p = xin.p; a.B = B; a.H = H; a.W = W; a.C = C; a.dt = e->S;
-        if ((rc = e->transformer(*st, a, o, kv, 0, with_term ? &term : nullptr))) break;
+        const PagTerm pt{n_perturbed, false, B - n_perturbed};
+        if ((rc = e->transformer(*st, a, o, kv, 0, with_term ? &term : nullptr, n_perturbed ? &pt : nullptr))) break;
         rc = from_dev_nhwc(e, o.p, e->S, y, B, C, H, W, C);
     } while (0);
     (void)hipStreamSynchronize(e->stream);

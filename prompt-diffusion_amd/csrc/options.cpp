@@ -8,6 +8,8 @@
 static const OptionRow* find_option(const char* key) {
     for (const OptionRow& r : kOptions)
         if (!strcmp(key, r.key)) return &r;
+    for (const OptionRow& r : kSwitches)
+        if (!strcmp(key, r.key)) return &r;
     return nullptr;
 }
 
@@ -47,6 +49,8 @@ int pd_set_option(pd_engine* e, const char* key, int64_t value) {
     e->clear_graphs();   // every other knob changes what a step launches
     const OptionRow* r = find_option(key);
     if (!r) { pd_set_error("unknown option '%s'", key); return 1; }
+    for (const OptionRow& sw : kSwitches)      // (a session's workspace was sized for the evaluation its switches chose)
+        if (r == &sw && e->ses.active) { pd_set_error("option '%s': end the sampling session first", key); return 1; }
     if (r->accepts && !r->accepts(value)) { pd_set_error("%s", r->range_error); return 1; }
     if (r->kind == OPT_COMMAND) { set_profiling(e, value != 0); return 0; }
     e->opt.*r->member = r->kind == OPT_BOOL ? value != 0 : r->kind == OPT_TRI ? (value < 0 ? -1 : value != 0) : (int)value;
@@ -80,6 +84,8 @@ int64_t pd_get_stat(pd_engine* e, const char* key) {
     if (!strcmp(key, "weight_bytes")) return (int64_t)e->weight_bytes;
     if (!strcmp(key, "launches")) return (int64_t)e->launches;
     if (!strcmp(key, "ip_launches")) return (int64_t)e->ip_launches;   // of which: IP-Adapter's image term (ip_attention.hip)
+    if (!strcmp(key, "pag_launches")) return (int64_t)e->pag_launches;   // of which: made for the perturbed branch of pd_set_pag (engine.h)
+    if (!strcmp(key, "pag_fork_block")) return (int64_t)e->pag_fork_block;   // block where the last evaluation forked that branch off; -1: none
     if (!strcmp(key, "image_allocs")) return (int64_t)e->image_allocs;   // allocations of pd_image_load / pd_image_store / pd_canny so far
     if (!strcmp(key, "canny_sweeps")) return (int64_t)e->canny_sweeps;   // hysteresis launches of the last pd_canny / pd_op_canny_hysteresis
     if (!strcmp(key, "gn_from_slabs")) return (int64_t)e->gn_from_slabs;

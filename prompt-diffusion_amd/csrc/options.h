@@ -54,6 +54,8 @@ struct EngineOptions {
     int ups_fold = 1;          // decoder Upsample convs as four 2x2-tap phase convs (2-byte modes)
     int ups_fold_tiles = -1;   // ... when the phase grid has at least this many blocks; -1: where patch_unsplit() admits an unsplit launch
     int vae_flash = -1;        // option "vae_flash": -1 per VAE (VaeDesc::flash_auto), 0 / 1 forced; 2-byte modes only
+    int pag_fork = 1;          // perturbed-attention guidance: the perturbed branch begins at the first perturbed block (1) or is a full third of
+                               // the UNet's batch from conv_in on (0: the plain evaluation the fork is tested and timed against); kSwitches
     int gemm_tile = -1;        // test surface: GemmPlan::big_tile of every igemm-family launch (-1: the plan's own)
     int gemm_splitk = -1;      // ... its K slices: -1 the plan's own, 1 never, n >= 2 that many where launch_gemm takes a split launch
 };
@@ -119,5 +121,10 @@ inline constexpr OptionRow kOptions[] = {
     PD_OPT(gemm_tile, OPT_INT, OPT_FX_NONE, [](int64_t v) { return v >= -1 && v <= 4; }, "option gemm_tile: -1 (the plan's own) or a tile 0 .. 4"),
     PD_OPT(gemm_splitk, OPT_INT, OPT_FX_NONE, [](int64_t v) { return v >= -1 && v != 0 && v <= 64; },
            "option gemm_splitk: -1 (the plan's own), 1 (never) or 2 .. 64 slices"),
+};
+// Switches of pd_set_option / pd_get_option that pd_option_info does not enumerate: the enumerated table above is the documented list of
+// tuning knobs; a row here is the A/B switch of one feature, documented with that feature
+inline constexpr OptionRow kSwitches[] = {
+    PD_OPT(pag_fork, OPT_BOOL),
 };
 #undef PD_OPT

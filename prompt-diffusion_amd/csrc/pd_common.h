@@ -397,6 +397,9 @@ int launch_freeu_concat(const void* h, const void* h_add, const void* skip, cons
 // for every sample); 1 <= T <= 64, C % 8 == 0, C / heads one of 8, 16, 32, 40, 80, 160.  0 launched, 1 launch failure, 2 shape refused
 int launch_ip_attention_add(const void* q2, void* att, const void* K_ip, const void* V_ip, long long kv_sample_stride, int B, int N, int C, int heads,
                             int T, float scale, float s, int dt, hipStream_t stream);
+// Perturbed-attention guidance (pag.hip): att [count][N][C] = the transposition of samples [src, src + count) of VT [.][C][npad], a bit
+// copy of a storage type of elem_bytes (2 or 4)
+int launch_pag_identity(const void* VT, void* att, int elem_bytes, int src, int count, int N, int C, int npad, hipStream_t s);
 // The end of a denoising step (sampler_update.hip): guidance + solver update (+ inpainting blend) + the next step's x_in.
 // What every update launch of a session shares: the UNet's eps [Bf, HW, eps_C] (uncond half first) in eps_dt, x_state
 // [B, HW, Cpad] fp32 updated in place, pred_x0 / eps_guided [B, HW, C] fp32, x_in [dup * B, HW, Cpad] fp32.
@@ -404,6 +407,13 @@ struct UpdateState {
     const void* eps; int eps_dt, eps_C;
     float* x_state; float* pred_x0; float* eps_guided; float* x_in;
     int B, HW, C, Cpad, use_cfg;
+    // perturbed-attention guidance (pd_set_pag): eps holds a third run of B samples from sample pag_off on (2 B under CFG, else B), the
+    // conditional branch with perturbed self-attention, and the guided eps gains pag_scale * (eps_cond - eps_perturbed).  pag: the
+    // evaluation carries that run (0: none, and the kernel executes what it executed before the state existed); pag_scale may then
+    // still be 0 on a step (the adaptive clamp): the run is not read, the guidance is formed without FMA contraction all the same
+    int pag = 0;
+    float pag_scale = 0.f;
+    int pag_off = 0;
 };
 // img2img / inpainting (semantics in include/pdengine.h, pd_sample_args.init_latents / mask).  z0, ieps: [B, C, HW] fp32 NCHW;
 // mask: [B, HW].  The blend (1 - m) k + m x, k = last ? z0 : sa z0 + sb eps, is evaluated in fp32 without contraction and

@@ -5,7 +5,8 @@
 // __device__ functions it calls; the kernels are its instantiations over the solver, a compile-time "blend or not" and, for DDIM
 // and the linear multistep rows, a compile-time "draws seeded noise or not" (pd_philox.h): the instantiations that draw none
 // carry nothing of the generator.  The small fill kernel behind pd_randn evaluates the same address -> value map.
-//   eps      [Bf, HW, eps_C] fp32 / 16-bit: UNet output, uncond half first (ddim_hacked.py:189-192)
+//   eps      [Bf, HW, eps_C] fp32 / 16-bit: UNet output, uncond half first (ddim_hacked.py:189-192); with perturbed-attention
+//            guidance (UpdateState::pag_scale != 0) B more samples, the perturbed branch, from sample pag_off on
 //   x_state  [B, HW, Cpad] fp32 (channels >= C are zero)    -> updated in place
 //   x_in     [dup*B, HW, Cpad] fp32: the CFG-duplicated latents the next step's conv_in reads
 //   pred_x0, eps_guided  [B, HW, C] fp32, index i
@@ -127,7 +128,8 @@ __device__ __forceinline__ float blend(float x, const BlendArgs& bl, long long j
     return __fadd_rn(__fmul_rn(__fsub_rn(1.0f, m), k), __fmul_rn(m, x));
 }
 
-// The one update kernel: guided eps (eps_uncond + scale (eps_cond - eps_uncond), ddim_hacked.py:193) -> eps_guided, the solver's
+// The one update kernel: guided eps (eps_uncond + scale (eps_cond - eps_uncond), ddim_hacked.py:193; + pag_scale (eps_cond -
+// eps_perturbed) where the evaluation carried a perturbed branch) -> eps_guided, the solver's
 // update, the blend where BLEND (compile-time: the plain instantiations carry nothing of it), and the new sample -> x_state, x_in
 // and x_in's CFG half.
 template <class Solver, bool BLEND>
@@ -142,13 +144,26 @@ __global__ void cfg_update_kernel(UpdateState u, Solver s, BlendArgs bl) {
         auto ld = [&](long long q) {
             return u.eps_dt == DT_F32 ? reinterpret_cast<const float*>(u.eps)[q] : cvt32_rt(reinterpret_cast<const uint16_t*>(u.eps)[q], u.eps_dt);
         };
-        float e;
+        float e, eu = 0.f, ec;
         if (u.use_cfg) {
-            const float eu = ld(((long long)b * u.HW + p) * u.eps_C + c);
-            const float ec = ld(((long long)(u.B + b) * u.HW + p) * u.eps_C + c);
+            eu = ld(((long long)b * u.HW + p) * u.eps_C + c);
+            ec = ld(((long long)(u.B + b) * u.HW + p) * u.eps_C + c);
             e = __fadd_rn(eu, __fmul_rn(k.cfg_scale, __fsub_rn(ec, eu)));
         } else {
-            e = ld(((long long)b * u.HW + p) * u.eps_C + c);
+            e = ec = ld(((long long)b * u.HW + p) * u.eps_C + c);
+        }
+        if (u.pag) {
+            // An evaluation with perturbed-attention guidance: (e_u + s (e_c - e_u)) + p (e_c - e_p), every operation rounded on its own.
+            // The lines above are compiled with the scale's multiply-add contracted into one FMA (hipcc takes __fmul_rn / __fadd_rn for
+            // plain operators); that is the arithmetic of every evaluation without the state and stays as it is.  Here contraction is
+            // off and the CFG sum is formed again, so a NumPy fp32 restatement gives the same bits -- also on the steps whose p is 0
+            // (the clamp of the adaptive scale), where the third run of eps is not read.
+#pragma clang fp contract(off)
+            e = u.use_cfg ? eu + k.cfg_scale * (ec - eu) : ec;
+            if (u.pag_scale != 0.f) {
+                const float ep = ld(((long long)(u.pag_off + b) * u.HW + p) * u.eps_C + c);
+                e = e + u.pag_scale * (ec - ep);
+            }
         }
         u.eps_guided[i] = e;
         if (!s.active()) continue;

@@ -496,9 +496,23 @@ int pd_engine::begin(const pd_sample_args* a, bool want_per_step, const pd_unipc
 }
 
 // What every update launch of the session shares (sampler_update.hip), for the eps of this evaluation
-UpdateState pd_engine::update_state(const Act& eps) const {
+UpdateState pd_engine::update_state(const Act& eps, double t) const {
     const Session& s = ses;
-    return UpdateState{eps.p, eps.dt, eps.C, s.x_state, s.pred_x0, s.eps_g, s.x_in, s.a.batch, s.a.h * s.a.w, cfg.in_channels, 8, s.a.use_cfg};
+    UpdateState u{eps.p, eps.dt, eps.C, s.x_state, s.pred_x0, s.eps_g, s.x_in, s.a.batch, s.a.h * s.a.w, cfg.in_channels, 8, s.a.use_cfg};
+    if (s.pag_B) {   // the evaluation carried a perturbed branch behind the Bf samples
+        u.pag = 1;
+        u.pag_scale = pag_scale_at(t);
+        u.pag_off = s.Bf;
+    }
+    return u;
+}
+
+// p_i = max(scale - adaptive_scale (1000 - t), 0), in double (diffusers' PAGMixin._get_pag_scale; the literal is 1000)
+float pd_engine::pag_scale_at(double t) const {
+    if (!pag_on()) return 0.f;
+    if (pag[1] == 0.f) return pag[0];
+    const double v = (double)pag[0] - (double)pag[1] * (1000.0 - t);
+    return (float)(v > 0.0 ? v : 0.0);
 }
 
 int pd_engine::step(int i) {
@@ -513,7 +527,7 @@ int pd_engine::step(int i) {
     const size_t mk = arena.mark();
     Act eps;
     PD_TRY(forward_eps(i, 0, &s.scales_step[(size_t)si * PD_NUM_CONTROL], eps));
-    const UpdateState u = update_state(eps);
+    const UpdateState u = update_state(eps, lms ? s.lms_times[i] : (double)s.timesteps[s.S - 1 - i]);
     // inpainting: the same update with the known region put back before the sample is stored
     const bool blend_on = s.mask && done;
     const BlendArgs bl{s.init_z0, s.init_eps, s.mask, blend_on ? s.blend[si + 1] : BlendCoef{}};
@@ -644,6 +658,10 @@ int pd_engine::run_steps_graph() {
     hash_mix(key, ses.lms_coef.data(), ses.lms_coef.size() * sizeof(double));
     hash_mix(key, ses.lms_times.data(), ses.lms_times.size() * sizeof(double));
     hash_mix(key, freeu, sizeof(freeu));   // FreeU values are kernel arguments (pd_set_freeu also drops the graphs)
+    // perturbed-attention guidance: the launches of the branch and the per-step scales (pd_set_pag also drops the graphs)
+    const uint32_t pagk[] = {pag_on() ? 1u : 0u, pag_mask, opt.pag_fork ? 1u : 0u};
+    hash_mix(key, pagk, sizeof(pagk));
+    hash_mix(key, pag, sizeof(pag));
     // IP-Adapter: whether the term's launches are in the loop, their arguments (scales, T, Bi -> the key stride) and which fill of the
     // image buffers they were captured against (every setter also drops the graphs)
     const uint64_t ipk[] = {ip.active() ? 1u : 0u, (uint64_t)ip.T, (uint64_t)ip.Bi, ip.gen, (uint64_t)(uintptr_t)ip.kv};
@@ -936,7 +954,7 @@ int pd_sample_eps_at(pd_engine* e, int64_t t, const float* scales13) {
     PD_TRY(e->forward_eps(row, 0, scales13, eps));
     DdimCoef k{};
     k.cfg_scale = s.a.cfg_scale;
-    if (launch_cfg_ddim(e->update_state(eps), k, nullptr, 1.f, 0, nullptr, e->stream)) return 1;
+    if (launch_cfg_ddim(e->update_state(eps, (double)t), k, nullptr, 1.f, 0, nullptr, e->stream)) return 1;
     e->arena.release(mk);
     return 0;
 }
@@ -1029,6 +1047,36 @@ int pd_set_freeu(pd_engine* e, float s1, float s2, float b1, float b2) {
     HIP_OK(hipSetDevice(e->device));
     e->clear_graphs();   // the values are kernel arguments of the captured loops
     memcpy(e->freeu, v, sizeof(v));
+    return 0;
+}
+
+int pd_set_pag(pd_engine* e, float scale, float adaptive_scale, uint32_t layer_mask) {
+    if (!e) { pd_set_error("null engine"); return 1; }
+    if (!std::isfinite(scale) || !std::isfinite(adaptive_scale) || scale < 0.f || adaptive_scale < 0.f) {
+        pd_set_error("pd_set_pag: scale and adaptive_scale must be finite and >= 0 (got %g, %g)", scale, adaptive_scale);
+        return 1;
+    }
+    const int nb = (int)e->unet.st_list.size();
+    if (nb < 32 && (layer_mask >> nb)) {
+        pd_set_error("pd_set_pag: layer_mask 0x%x names blocks beyond the UNet's %d transformer blocks", (unsigned)layer_mask, nb);
+        return 1;
+    }
+    if (nb > 32) { pd_set_error("pd_set_pag: a UNet of %d transformer blocks does not fit the 32-bit mask", nb); return 1; }
+    const float v[2] = {scale, adaptive_scale};
+    if (!memcmp(v, e->pag, sizeof(v)) && layer_mask == e->pag_mask) return 0;
+    // the workspace of a running session was sized for the batch its evaluations run at: switching off is always possible
+    if (e->ses.active && scale != 0.f && layer_mask != 0) { pd_set_error("pd_set_pag: end the sampling session first"); return 1; }
+    HIP_OK(hipSetDevice(e->device));
+    e->clear_graphs();   // the branch's launches and the scales are part of the captured loops
+    memcpy(e->pag, v, sizeof(v));
+    e->pag_mask = layer_mask;
+    return 0;
+}
+
+int pd_get_pag(pd_engine* e, float out[2], uint32_t* layer_mask) {
+    if (!e || !out) { pd_set_error("null argument"); return 1; }
+    memcpy(out, e->pag, sizeof(e->pag));
+    if (layer_mask) *layer_mask = e->pag_mask;
     return 0;
 }
 

@@ -354,6 +354,13 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.pd_bench_ip_attention.argtypes = [C.c_void_p] + [C.c_int32] * 5 + [C.POINTER(C.c_float)] * 2
         lib.pd_op_ip_attention_add.argtypes = [C.c_void_p, fp, fp, fp, fp] + [C.c_int] * 6 + [C.c_float, C.c_float, fp]
         lib.pd_op_spatial_transformer_ip.argtypes = [C.c_void_p, C.c_char_p, fp, fp, fp] + [C.c_int] * 5 + [fp]
+    if hasattr(lib, "pd_set_pag"):   # (as above: an older build lacks perturbed-attention guidance)
+        lib.pd_set_pag.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_uint32]
+        lib.pd_get_pag.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]
+        lib.pd_bench_pag_identity.argtypes = [C.c_void_p] + [C.c_int32] * 4 + [C.POINTER(C.c_float)] * 2
+        lib.pd_op_pag_identity.argtypes = [C.c_void_p, fp] + [C.c_int] * 5 + [fp]
+        lib.pd_op_cfg_combine.argtypes = [C.c_void_p, fp] + [C.c_int] * 5 + [C.c_float, C.c_float, fp]
+        lib.pd_op_spatial_transformer_pag.argtypes = [C.c_void_p, C.c_char_p, fp, fp] + [C.c_int] * 5 + [fp]
     lib.pd_image_store.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_int32]
     lib.pd_canny.argtypes = [C.c_void_p, C.POINTER(pd_canny_args)]
     lib.pd_op_canny_hysteresis.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
@@ -397,6 +404,7 @@ EXPORTS = [
     "pd_clip_vision_weights_missing", "pd_clip_vision_forward", "pd_safety_configure", "pd_safety_weights_missing", "pd_safety_check", "pd_safety_blank",
     "pd_ip_adapter_configure", "pd_ip_adapter_weights_missing", "pd_ip_adapter_set_scale", "pd_ip_adapter_get_scale", "pd_ip_adapter_set_image",
     "pd_ip_adapter_clear_image", "pd_bench_ip_attention", "pd_op_ip_attention_add", "pd_op_spatial_transformer_ip",
+    "pd_set_pag", "pd_get_pag", "pd_bench_pag_identity", "pd_op_pag_identity", "pd_op_cfg_combine", "pd_op_spatial_transformer_pag",
     "pd_sd3_vae_configure", "pd_sd3_vae_weights_missing", "pd_sd3_vae_config_layout", "pd_sd3_vae_decode", "pd_sd3_vae_encode", "pd_op_vae_attention", "pd_bench_vae_attention",
 ]
 
@@ -897,6 +905,38 @@ class Engine:
         self._check(self.lib.pd_get_freeu(self._h, out))
         v = tuple(float(x) for x in out)
         return None if not any(v) else v
+
+    # ------------------------------------------------------------------ perturbed-attention guidance (pd_set_pag)
+    def set_pag(self, scale: float, layers, adaptive_scale: float = 0.0) -> None:
+        """Perturbed-attention guidance (arXiv:2403.17377, as diffusers' PAGMixin) in every later guided evaluation of this engine: a
+        third branch, the conditional one with the self-attention of the UNet transformer blocks in `layers` replaced by the identity,
+        and eps += p_i (eps_cond - eps_perturbed), p_i = scale, or max(scale - adaptive_scale (1000 - t_i), 0).  `layers` is a bit
+        mask or an iterable of block indices (encoder blocks, then decoder blocks, then the middle block: parse_pag_layers of
+        prompt_diffusion_amd.pag turns diffusers' names into one).  Scale 0 or no layer leaves every call exactly as without it;
+        negative or non-finite values and blocks the UNet does not have raise PdError."""
+        if isinstance(layers, (int, np.integer)):
+            mask = int(layers)
+        else:
+            mask = 0
+            for j in layers:
+                if not 0 <= int(j) < 32:
+                    raise ValueError(f"set_pag: block index {j} outside 0 .. 31")
+                mask |= 1 << int(j)
+        if not 0 <= mask < 2 ** 32:
+            raise ValueError(f"set_pag: layer mask {mask:#x} does not fit 32 bits")
+        self._check(self.lib.pd_set_pag(self._h, float(scale), float(adaptive_scale), mask))
+
+    def disable_pag(self) -> None:
+        self._check(self.lib.pd_set_pag(self._h, 0.0, 0.0, 0))
+
+    @property
+    def pag(self) -> Optional[Tuple[float, float, int]]:
+        """(scale, adaptive_scale, layer mask) as last set (the scales as float32), or None while it is off (scale 0 or mask 0)."""
+        out, mask = (C.c_float * 2)(), C.c_uint32(0)
+        self._check(self.lib.pd_get_pag(self._h, out, C.byref(mask)))
+        if float(out[0]) == 0.0 or mask.value == 0:
+            return None
+        return float(out[0]), float(out[1]), int(mask.value)
 
     # ------------------------------------------------------------------ seeded noise (pd_set_rng / pd_randn)
     def set_rng(self, seed: int, sample_base: int = 0) -> None:
@@ -2235,4 +2275,39 @@ class Engine:
         L = self._context_len(ctx, B, "context")
         y = np.empty_like(x)
         self._check(self.lib.pd_op_spatial_transformer_ctx(self._h, prefix.encode(), x.ctypes.data, ctx.ctypes.data, B, H, W, L, y.ctypes.data))
+        return y
+
+    def bench_pag_identity(self, B: int, N: int, Cc: int, iters: int = 50) -> Tuple[float, float]:
+        """(kernel ms, copy ms) per launch of pag_identity_kernel on [B, N, Cc] and of a device-to-device copy of the same bytes."""
+        k, c = C.c_float(0), C.c_float(0)
+        self._check(self.lib.pd_bench_pag_identity(self._h, int(B), int(N), int(Cc), int(iters), C.byref(k), C.byref(c)))
+        return float(k.value), float(c.value)
+
+    def op_pag_identity(self, vt, src: int, count: int):
+        """pag_identity_kernel alone: vt [Bs, C, N] -> [count, N, C], samples [src, src + count) transposed, through the engine's storage type."""
+        vt = np.ascontiguousarray(vt, np.float32)
+        Bs, Cc, N = vt.shape
+        out = np.empty((int(count), N, Cc), np.float32)
+        self._check(self.lib.pd_op_pag_identity(self._h, vt.ctypes.data, Bs, Cc, N, int(src), int(count), out.ctypes.data))
+        return out
+
+    def op_cfg_combine(self, eps, B: int, use_cfg: bool, cfg_scale: float, pag_scale: float, eps_dtype: int = PD_DT_F32):
+        """The guidance of the update kernel alone: eps [Bt, HW, C] = [uncond ;] cond [; perturbed] (the last only with pag_scale != 0),
+        converted to eps_dtype on the device -> the guided eps [B, HW, C] fp32."""
+        eps = np.ascontiguousarray(eps, np.float32)
+        Bt, HW, Cc = eps.shape
+        assert Bt == (2 if use_cfg else 1) * B + (B if pag_scale != 0 else 0), eps.shape
+        out = np.empty((B, HW, Cc), np.float32)
+        self._check(self.lib.pd_op_cfg_combine(self._h, eps.ctypes.data, int(B), HW, Cc, int(eps_dtype), int(bool(use_cfg)), float(cfg_scale),
+                                               float(pag_scale), out.ctypes.data))
+        return out
+
+    def op_spatial_transformer_pag(self, prefix: str, x, context, n_perturbed: int):
+        """op_spatial_transformer with the last n_perturbed samples perturbed: identity self-attention from their own V."""
+        x = np.ascontiguousarray(x, np.float32); ctx = np.ascontiguousarray(context, np.float32)
+        B, Cc, H, W = x.shape
+        L = self._context_len(ctx, B, "context")
+        y = np.empty_like(x)
+        self._check(self.lib.pd_op_spatial_transformer_pag(self._h, prefix.encode(), x.ctypes.data, ctx.ctypes.data, B, H, W, L, int(n_perturbed),
+                                                           y.ctypes.data))
         return y

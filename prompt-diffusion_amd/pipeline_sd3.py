@@ -362,8 +362,11 @@ class StableDiffusion3PromptDiffusionPipeline(AdapterMixin):
                  negative_pooled_prompt_embeds=None, ip_adapter_image=None, ip_adapter_image_embeds=None,
                  output_type: Optional[str] = "pil", return_dict: bool = True, joint_attention_kwargs: Optional[Dict[str, Any]] = None,
                  clip_skip: Optional[int] = None, callback_on_step_end: Optional[Callable] = None,
-                 callback_on_step_end_tensor_inputs: List[str] = ["latents"], max_sequence_length: int = 256, _edit: Optional[dict] = None):
+                 callback_on_step_end_tensor_inputs: List[str] = ["latents"], max_sequence_length: int = 256, _edit: Optional[dict] = None,
+                 pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0):
         """_edit: set by the img2img / inpaint subclasses -- {"image", "strength", "mask_image"}."""
+        if pag_scale:
+            raise NotImplementedError("pag_scale: perturbed-attention guidance is built for the SD1.5 pipelines only (not the MMDiT path)")
         if ip_adapter_image is not None or ip_adapter_image_embeds is not None:
             raise NotImplementedError("ip_adapter_image / ip_adapter_image_embeds are outside the engine's path")
         lora_scale = 1.0
